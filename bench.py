@@ -10,6 +10,9 @@ torch.distributed.run, one rank per GPU) prints ONE JSON line on rank 0.
   value = faces embedded per second, whole job (all ranks).  One step = one batch.
 * multi-GPU: frames are sharded one batch per rank (weak scaling); the headline path has no
   exchange step, so no collective is on the data path — only the timing barrier / max-reduce.
+* a plain run sets up, warms up, times the K steps and prints the line; the legs below (and the
+  sustained / serial-reference steps) run only with --full.  --dump-outputs DIR writes the last
+  timed step's results as .npy files (same arguments -> same seeded inputs, run to run).
 * roofline: the dominant kernel is the f32-MFMA implicit-GEMM convolution; every launch of it is
   bracketed by HIP events inside the library (fh_timing_*, on the stream the kernels run on) in an
   instrumented pass of the same steps right after the timed region (the ~250 event records per
@@ -59,8 +62,8 @@ def parse():
     ap.add_argument("--of-world", type=int, default=8)
     ap.add_argument("--stream-priority", default="rec", choices=["rec", "det", "none"],
                     help="streaming e2e form: which of the two HIP streams gets the higher priority (tuning)")
-    ap.add_argument("--sustain-steps", type=int, default=200, help="extra steps of the same form right after the timed region, reported as "
-                    "`sustained` beside `value` (0 = off)")
+    ap.add_argument("--sustain-steps", type=int, default=200, help="--full: extra steps of the same form right after the timed region, "
+                    "reported as `sustained` beside `value` (0 = off)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-kernel-timing", action="store_true")
     ap.add_argument("--cpu-sample-frames", type=int, default=32)
@@ -89,6 +92,11 @@ def parse():
     ap.add_argument("--dry-run", action="store_true", help="launcher / rendezvous rehearsal without a GPU: ranks start, meet on gloo, "
                     "run the barrier + max-over-ranks timing protocol around EMPTY steps and rank 0 prints a line with value = null and "
                     "\"dry_run\": true.  Not a measurement; exists so that the N > 1 launch path is testable on a CPU-only host")
+    ap.add_argument("--full", action="store_true", help="also run the legs beside the headline: per-step HIP-event spread, the sustained "
+                    "and serial-reference steps, the instrumented per-kernel roofline, the CPU baselines (and --workload match's kernel "
+                    "timing, --workload latency's eager leg).  Off: set-up, warm-up, the timed steps and the result line only")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last timed step computed (rank 0) "
+                    "as DIR/<name>.npy, float32 / float64, at most 64 MB in all")
     return ap.parse_args()
 
 
@@ -158,6 +166,34 @@ def cpu_model_name():
     except OSError:
         pass
     return "unknown"
+
+
+def face_fields(recs):
+    """Face records (fa.FACE_DTYPE rows: x, y, w, h int32, score, 10 landmark floats; a device buffer of 15 words per row or a
+    host record array) -> the three arrays --dump-outputs writes."""
+    from facerecognizeonnx_amd import FACE_DTYPE
+    a = recs.cpu().numpy() if hasattr(recs, "cpu") else recs
+    r = np.ascontiguousarray(a).view(np.uint8).reshape(-1, FACE_DTYPE.itemsize).copy().view(FACE_DTYPE).reshape(-1)
+    return {"face_boxes": np.stack([r[k] for k in "xywh"], 1), "face_scores": r["score"], "face_landmarks": r["lm"]}
+
+
+DUMP_LIMIT = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: each array as <name>.npy, integer results as float64 (exact), the rest as float32.  Over 64 MB in all, the
+    same seeded choice of leading-axis rows is kept of every array, in order."""
+    os.makedirs(path, exist_ok=True)
+    arrs = {}
+    for name, a in arrays.items():
+        a = a.cpu().numpy() if hasattr(a, "cpu") else np.asarray(a)
+        arrs[name] = a.astype(np.float64 if a.dtype.kind in "iub" else np.float32)
+    total = sum(a.nbytes for a in arrs.values())
+    for name, a in arrs.items():
+        if total > DUMP_LIMIT and a.ndim and len(a) > 1:
+            keep = max(1, int(len(a) * DUMP_LIMIT / total))
+            a = a[np.sort(np.random.default_rng(0).choice(len(a), keep, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def traffic_from_profile(workload, kernel):
@@ -290,22 +326,23 @@ def bench_match(args, rank, world, local, dist, cdev, fa, torch):
     if dist is not None:
         dist.barrier()
     dt = time.perf_counter() - t0
-    # kernel-level: HIP events on the stream the scan runs on, around the library call only (scan + list merge)
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    reps = max(5, min(args.steps, 20))
-    e0.record()
-    for _ in range(reps):
-        gallery.topk_dev(q.data_ptr(), Q, k, sc.data_ptr(), ix.data_ptr(), stream)
-    e1.record(); torch.cuda.synchronize()
-    kms = e0.elapsed_time(e1) / reps
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"topk_scores": sc, "topk_indices": ix})
+    if args.full:
+        # kernel-level: HIP events on the stream the scan runs on, around the library call only (scan + list merge)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        reps = max(5, min(args.steps, 20))
+        e0.record()
+        for _ in range(reps):
+            gallery.topk_dev(q.data_ptr(), Q, k, sc.data_ptr(), ix.data_ptr(), stream)
+        e1.record(); torch.cuda.synchronize()
+        kms = e0.elapsed_time(e1) / reps
     max_dt, tot = dt, float(units)
     if dist is not None:
         t = torch.tensor([dt], device=cdev, dtype=torch.float64); dist.all_reduce(t, op=dist.ReduceOp.MAX)
         max_dt = float(t.item())                   # every rank answers the SAME Q queries against its shard: units are not summed
     if rank == 0:
         rows_local = ge - gb
-        gbs = rows_local * dim * 4 / (kms * 1e-3) / 1e9
-        tf = 2.0 * Q * rows_local * dim / (kms * 1e-3) / 1e12
         out = {"metric": "queries/sec 1:N compareFaces top-k against a 512-d gallery", "value": tot / max_dt, "unit": "queries/s", "n_gpus": world,
                "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * max_dt / max(args.steps, 1), "higher_is_better": True,
                "scaling": "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
@@ -315,17 +352,21 @@ def bench_match(args, rank, world, local, dist, cdev, fa, torch):
                                          (f"; this GPU plays rank {args.as_rank} of {args.of_world} (rows [{gb}, {ge}), global indices; the exchange itself is not run)"
                                           if args.as_rank >= 0 and world == 1 else "")},
                "roofline": None}
-        # the scan is priced against whichever of its two floors is higher: every gallery row once from HBM (rows x dim x 4 B at 8 TB/s) or
-        # 2 Q rows dim FLOP on the f32 matrix cores (157.3 TFLOP/s) — at Q = 64 the matrix cores bind (0.43 ms against 0.26 ms per 1 M rows)
-        t_hbm, t_mfma = rows_local * dim * 4 / 8000e9, 2.0 * Q * rows_local * dim / (F32_MFMA_PEAK_TFLOPS * 1e12)
-        common = {"kernel": "gallery_topk_kernel (+ topk_merge_kernel)", "traffic": None, "avg_launch_us": 1e3 * kms,
-                  "algorithmic_mbytes_per_launch": rows_local * dim * 4 / 1e6, "algorithmic_gflop_per_launch": 2.0 * Q * rows_local * dim / 1e9,
-                  "hbm_gbs": gbs, "hbm_frac": gbs / 8000.0, "mfma_tflops": tf, "mfma_frac": tf / F32_MFMA_PEAK_TFLOPS,
-                  "floor_ms": {"hbm": 1e3 * t_hbm, "mfma": 1e3 * t_mfma}}
-        if t_mfma >= t_hbm:
-            out["roofline"] = {"bound": "mfma", "achieved": tf, "peak": F32_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": tf / F32_MFMA_PEAK_TFLOPS, **common}
-        else:
-            out["roofline"] = {"bound": "hbm", "achieved": gbs, "peak": 8000.0, "unit": "GB/s", "frac": gbs / 8000.0, **common}
+        if args.full:
+            gbs = rows_local * dim * 4 / (kms * 1e-3) / 1e9
+            tf = 2.0 * Q * rows_local * dim / (kms * 1e-3) / 1e12
+            # the scan is priced against whichever of its two floors is higher: every gallery row once from HBM (rows x dim x 4 B at
+            # 8 TB/s) or 2 Q rows dim FLOP on the f32 matrix cores (157.3 TFLOP/s) — at Q = 64 the matrix cores bind (0.43 ms against
+            # 0.26 ms per 1 M rows)
+            t_hbm, t_mfma = rows_local * dim * 4 / 8000e9, 2.0 * Q * rows_local * dim / (F32_MFMA_PEAK_TFLOPS * 1e12)
+            common = {"kernel": "gallery_topk_kernel (+ topk_merge_kernel)", "traffic": None, "avg_launch_us": 1e3 * kms,
+                      "algorithmic_mbytes_per_launch": rows_local * dim * 4 / 1e6, "algorithmic_gflop_per_launch": 2.0 * Q * rows_local * dim / 1e9,
+                      "hbm_gbs": gbs, "hbm_frac": gbs / 8000.0, "mfma_tflops": tf, "mfma_frac": tf / F32_MFMA_PEAK_TFLOPS,
+                      "floor_ms": {"hbm": 1e3 * t_hbm, "mfma": 1e3 * t_mfma}}
+            if t_mfma >= t_hbm:
+                out["roofline"] = {"bound": "mfma", "achieved": tf, "peak": F32_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": tf / F32_MFMA_PEAK_TFLOPS, **common}
+            else:
+                out["roofline"] = {"bound": "hbm", "achieved": gbs, "peak": 8000.0, "unit": "GB/s", "frac": gbs / 8000.0, **common}
         print(json.dumps(out), flush=True)
     if dist is not None:
         dist.barrier(); dist.destroy_process_group()
@@ -364,13 +405,17 @@ def bench_latency(args, fa, torch, models):
     def f_rec(i):
         return rec.extractFeature(imgs[0], face0[0])
     res = {}
-    for mode in ("graph", "eager"):
+    for mode in ("graph", "eager") if args.full else ("graph",):
         L.fh_set_graph_replay(1 if mode == "graph" else 0)
         res[mode] = {"detect": sample(f_det), "extractFeature": sample(f_rec)}
+        if args.dump_outputs and mode == "graph":                     # the last timed calls: frame (calls - 1) % 8, faces[0] of frame 0
+            dump_outputs(args.dump_outputs, {**face_fields(f_det(calls - 1)), "embedding": f_rec(0)})
     L.fh_set_graph_replay(1)
-    f_det(0); f_det(0); f_det(0); f_rec(0); f_rec(0); f_rec(0)
-    n = C.c_longlong(0)
-    det_nodes = L.fh_det_graph_stats(det.handle, C.byref(n)); rec_nodes = L.fh_rec_graph_stats(rec.handle, C.byref(n))
+    det_nodes = rec_nodes = None
+    if args.full:
+        f_det(0); f_det(0); f_det(0); f_rec(0); f_rec(0); f_rec(0)
+        n = C.c_longlong(0)
+        det_nodes = L.fh_det_graph_stats(det.handle, C.byref(n)); rec_nodes = L.fh_rec_graph_stats(rec.handle, C.byref(n))
     step_us = res["graph"]["detect"]["p50_us"] + res["graph"]["extractFeature"]["p50_us"]
     out = {"metric": "faces/sec, batch-1 drop-in calls (detect + extractFeature of the best face, host image in / host results out)",
            "value": 1e6 / step_us, "unit": "faces/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "ms_per_step": step_us / 1e3,
@@ -580,26 +625,48 @@ def main():
         step()
     torch.cuda.synchronize()
     drain()
-    timing = not args.no_kernel_timing
+    timing = args.full and not args.no_kernel_timing
     if dist is not None:
         dist.barrier()
     torch.cuda.synchronize()
-    # per-step HIP events on the stream the kernels run on (torch's current stream = `stream`): the timed region is a fraction of a
-    # second, so min / median / max over its steps say whether `ms_per_step` is one lucky wall-clock sample (a record costs ~2 us)
-    marks = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
+    # --full: per-step HIP events on the stream the kernels run on (torch's current stream = `stream`): the timed region is a fraction
+    # of a second, so min / median / max over its steps say whether `ms_per_step` is one lucky wall-clock sample (a record costs ~2 us)
+    marks = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)] if args.full else None
     t0 = time.perf_counter()
-    units = 0
+    units = n_last = 0
     mark_stream = locals().get("s_rec")                                   # streaming form: a batch ends on the recogniser's stream
-    marks[0].record(mark_stream) if mark_stream is not None else marks[0].record()
+    if marks:
+        marks[0].record(mark_stream) if mark_stream is not None else marks[0].record()
     for i in range(args.steps):
-        units += step()
-        marks[i + 1].record(mark_stream) if mark_stream is not None else marks[i + 1].record()
+        n_last = step()
+        units += n_last
+        if marks:
+            marks[i + 1].record(mark_stream) if mark_stream is not None else marks[i + 1].record()
     torch.cuda.synchronize()
     if dist is not None:
         dist.barrier()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:                                   # before anything below reuses the result buffers
+        if args.from_host and args.workload == "e2e":                     # the last batch is the one still in flight
+            recs, fo, e = fstream.collect()
+            state["inflight"] -= 1
+            outs = {**face_fields(recs), "frame_of": fo, "embeddings": e}
+        elif args.workload == "embed":
+            outs = {"embeddings": emb}
+        elif args.workload == "detect":                                   # the first min(count, F) slots of every frame
+            c = np.minimum(counts.cpu().numpy(), F)
+            live = torch.from_numpy((np.arange(F)[None, :] < c[:, None]).reshape(-1)).cuda()
+            outs = {**face_fields(faces[live]), "counts": c}
+        else:
+            slot = (state["k"] - 1) % RING if locals().get("pipelined") else None
+            f_, o_, e_ = (faces, frame_of, emb) if slot is None else (rf[slot], ro[slot], re_[slot])
+            outs = {**face_fields(f_[:n_last]), "frame_of": o_[:n_last], "embeddings": e_[:n_last]}
+            if args.gallery:
+                s_, i_ = (sc, ix) if slot is None else (gsc[slot], gix[slot])
+                outs.update(topk_scores=s_[:n_last], topk_indices=i_[:n_last])
+        dump_outputs(args.dump_outputs, outs)
     units += drain()
-    step_ms = sorted(marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps))
+    step_ms = sorted(marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps)) if marks else []
     # Kernel-level roofline leg: the same steps again with the library's per-launch HIP events switched on.
     # It runs right AFTER the timed region (not inside it) because the ~250 event records per step cost
     # ~6 % of the step (22.8 vs 21.5 ms); `value` must not carry the instrumentation.
@@ -607,7 +674,7 @@ def main():
     # over seconds (MI355X_MICROARCH.md, DVFS give-back) and is invisible to a 5 s utilisation sampler.  The SAME step, same form, is
     # therefore repeated for --sustain-steps more steps right after it and reported beside `value` (never as `value`).
     sustained = None
-    if args.sustain_steps > 0 and args.workload in ("e2e", "embed", "detect") and not args.from_host:
+    if args.full and args.sustain_steps > 0 and args.workload in ("e2e", "embed", "detect") and not args.from_host:
         torch.cuda.synchronize()
         tq0 = time.perf_counter()
         su = 0
@@ -620,7 +687,7 @@ def main():
                      "what": "the same step in the same form, repeated right after the timed region on rank 0 (clock settling, visibility to "
                              "utilisation samplers); `value` stays the K timed steps"}
     serial_dt = None
-    if locals().get("pipelined"):                                         # the same K steps once more, one batch at a time on one stream
+    if args.full and locals().get("pipelined"):                           # the same K steps once more, one batch at a time on one stream
         step = step_serial
         for _ in range(2):
             step()
@@ -668,7 +735,7 @@ def main():
             "timed_step_ms_min": step_ms[0] if step_ms else None, "timed_step_ms_median": step_ms[len(step_ms) // 2] if step_ms else None,
             "timed_step_ms_max": step_ms[-1] if step_ms else None,
             "timed_step_ms_source": "HIP events around each of the timed steps on the launch stream, rank 0 (value / ms_per_step stay the "
-                                    "barrier-bracketed wall clock, max over ranks)",
+                                    "barrier-bracketed wall clock, max over ranks)" if marks else "not measured (--full only)",
             "sustained": sustained,
             "serial_reference": None if serial_dt is None else {
                 "ms_per_step": 1e3 * serial_dt / max(args.steps, 1), "value": per_step_faces * args.steps / serial_dt, "unit": "faces/s",
@@ -739,7 +806,7 @@ def main():
                 r.update({"f32_equivalent_achieved": r["achieved"], "achieved": 3 * r["achieved"], "peak": BF16_MFMA_PEAK_TFLOPS,
                           "frac": 3 * r["achieved"] / BF16_MFMA_PEAK_TFLOPS,
                           "flops_counted": "3 bf16 products (hi*hi, hi*mid, mid*hi) per f32-equivalent product of the 36 Winograd GEMMs"})
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(det_path, rec_path, host, args)                  # the reference's own setting: 4 threads
             try:                                             # second leg: an optimised CPU engine's view of the same sample (torch / oneDNN)
                 out["cpu_baseline_torch"] = cpu_baseline(det_path, rec_path, host, args, engine="torch")

@@ -15,7 +15,7 @@ rows = [("headline", "headline: 128 frames 640x640, detect+align+embed, F=1 (str
         ("mbf_embed", "MobileFaceNet (w600k_mbf, the buffalo_sc recogniser) instead of w600k_r50: 256 pre-aligned crops", "`--workload embed --recogniser mbf`"),
         ("mbf_e2e", "headline pipeline with MobileFaceNet as the recogniser", "`--recogniser mbf`")]
 out = [f"# Round {tag} — other BASELINE.json configurations (same build as profiles/{tag}_summary.md)", "",
-       "`python bench.py --steps 10 --warmup 3 --no-cpu-baseline <args>` on one MI355X, HBM-resident inputs unless stated, fp32.", "",
+       "`python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline <args>` on one MI355X, HBM-resident inputs unless stated, fp32.", "",
        "| config | args | value | ms / step | dominant kernel (achieved, frac of its roofline) | all conv launches |", "|---|---|---|---|---|---|"]
 for name, desc, args in rows:
     p = os.path.join(ROOT, "gpurun_out", "secondary", name + ".json")

@@ -111,7 +111,7 @@ bj = os.path.join(src, "bench_under_rocprof.json")
 if os.path.exists(bj):
     bench = open(bj).read().strip()
 with open(os.path.join(dst, f"{tag}_summary.md"), "w") as f:
-    f.write(f"# rocprofv3 summary {tag} — `python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --serial` ({workload})\n\n")
+    f.write(f"# rocprofv3 summary {tag} — `python3 bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --serial` ({workload})\n\n")
     f.write("`rocprofv3 --kernel-trace --stats` (all steps of the run: warm-up + timed + instrumented; a profiled run is slower than an un-profiled one):\n\n")
     f.write("| kernel | calls | total ms | avg us | % |\n|---|---|---|---|---|\n")
     for r in rows[:16]:

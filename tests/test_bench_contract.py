@@ -34,7 +34,7 @@ def test_committed_bench_line_has_the_contract_fields():
 def test_bench_cli_accepts_the_driver_flags():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
     assert out.returncode == 0
-    for flag in ("--gpus", "--steps", "--warmup"):
+    for flag in ("--gpus", "--steps", "--warmup", "--full", "--dump-outputs"):
         assert flag in out.stdout
 
 
