@@ -97,6 +97,9 @@ PROTOTYPES = {
     "fh_gallery_size": (_ll, [_vp]),
     "fh_gallery_label_dev": (_i, [_vp, _vp, _i, _f, _vp, _vp, _vp]),
     "fh_gallery_topk_dev": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp]),
+    "fh_gallery_set_scan": (_i, [_vp, _i]),
+    "fh_gallery_get_scan": (_i, [_vp]),
+    "fh_gallery_scan_stats": (_i, [_vp, C.POINTER(_ll), C.POINTER(_ll)]),
     "fh_topk_merge_dev": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "fh_comm_unique_id": (_i, [_vp]),
     "fh_comm_create": (_vp, [_i, _i, _vp, _i]),

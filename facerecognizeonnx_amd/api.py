@@ -266,11 +266,33 @@ class FrameStream:
 
 
 class Gallery:
-    """1:N generalisation of compareFaces: top-k mapped scores (dot+1)/2 over enrolled rows."""
+    """1:N generalisation of compareFaces: top-k mapped scores (dot+1)/2 over enrolled rows.
 
-    def __init__(self, dim: int = 512):
+    scan="f16": fp16 scan + exact fp32 re-rank (fh_gallery_set_scan), the same answer as "fp32" bit for bit; G x dim x 2 bytes more."""
+
+    _SCANS = {"fp32": 0, "f16": 1}
+
+    def __init__(self, dim: int = 512, scan: str = "fp32"):
         self._h = _lib.lib().fh_gallery_create(dim)
         self.dim = dim
+        if scan != "fp32":
+            self.set_scan(scan)
+
+    def set_scan(self, mode: str = "fp32"):
+        """"fp32" (default) or "f16" (fp16 candidate scan, fp32 re-score, per-query certificate, fp32 fallback); synchronous."""
+        if mode not in self._SCANS:
+            raise ValueError(f"scan {mode!r}: expected one of {sorted(self._SCANS)}")
+        check(_lib.lib().fh_gallery_set_scan(self._h, self._SCANS[mode]), "fh_gallery_set_scan")
+
+    @property
+    def scan(self) -> str:
+        return "f16" if _lib.lib().fh_gallery_get_scan(self._h) == 1 else "fp32"
+
+    def scan_stats(self):
+        """(certified, fallback): queries answered by the certified fp16 path / by the fp32 fallback since the last call (resets)."""
+        c, f = C.c_longlong(0), C.c_longlong(0)
+        check(_lib.lib().fh_gallery_scan_stats(self._h, C.byref(c), C.byref(f)), "fh_gallery_scan_stats")
+        return int(c.value), int(f.value)
 
     def __del__(self):
         if getattr(self, "_h", None) and _lib is not None and getattr(_lib, "_LIB", None) is not None:

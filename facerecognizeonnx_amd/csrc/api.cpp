@@ -666,6 +666,17 @@ int fh_gallery_topk_dev(fh_gallery* g, const float* q, int nq, int k, float* sco
     return guarded([&] { g->g.topk_dev(q, nq, k, scores, indices, S(stream)); return nq; });
 }
 
+int fh_gallery_set_scan(fh_gallery* g, int mode) {
+    if (!g) return arg_error("fh_gallery_set_scan: null handle");
+    if (mode != FH_GAL_SCAN_FP32 && mode != FH_GAL_SCAN_F16_RERANK) return arg_error("fh_gallery_set_scan: unknown mode");
+    return guarded([&] { g->g.set_scan(mode); return 0; });
+}
+int fh_gallery_get_scan(const fh_gallery* g) { return g ? g->g.scan() : arg_error("fh_gallery_get_scan: null handle"); }
+int fh_gallery_scan_stats(fh_gallery* g, long long* certified, long long* fallback) {
+    if (!g) return arg_error("fh_gallery_scan_stats: null handle");
+    return guarded([&] { g->g.scan_stats(certified, fallback); return 0; });
+}
+
 int fh_topk_merge_dev(const float* ps, const int* pi, int nparts, int nq, int k, float* scores, int* indices, void* stream) {
     if (!ps || !pi || !scores || !indices) return arg_error("fh_topk_merge_dev: null argument");
     if (nparts <= 0 || nq <= 0 || k <= 0 || k > 16 || (long)nparts * k > 65536) return arg_error("fh_topk_merge_dev: bad size");

@@ -717,6 +717,54 @@ void Gallery::upload(const float* rows, long n, bool device_src, long index_base
     rows_.ensure((size_t)n * dim_ * sizeof(float));
     FH_HIP(hipMemcpy(rows_.p, rows, (size_t)n * dim_ * sizeof(float), device_src ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
     n_ = n; base_ = index_base;
+    if (scan_ == 1) {
+        rows16_.ensure((size_t)n * dim_ * sizeof(uint16_t));
+        convert16(0, n);
+    }
+}
+
+void Gallery::convert16(long first, long n) {
+    gstat_.ensure(4 * sizeof(unsigned));
+    if (first == 0) FH_HIP(hipMemset(gstat_.p, 0, 4 * sizeof(unsigned)));      // a new row set: fresh bounds (enroll keeps the maxima)
+    launch_gallery16_convert(rows_.as<float>() + (size_t)first * dim_, rows16_.as<uint16_t>() + (size_t)first * dim_, n, dim_,
+                             gstat_.as<unsigned>(), nullptr);
+    FH_HIP(hipGetLastError());
+    unsigned h[4];
+    FH_HIP(hipMemcpy(h, gstat_.p, sizeof(h), hipMemcpyDeviceToHost));
+    for (int i = 0; i < 3; ++i) memcpy(&gbound_[i], &h[i], sizeof(float));
+    f16_bad_ = h[3] != 0;
+}
+
+void Gallery::set_scan(int mode) {
+    if (mode != 0 && mode != 1) throw std::invalid_argument("gallery: unknown scan mode");
+    if (mode == 0) {
+        DevBuf none;
+        std::swap(none.p, rows16_.p);
+        std::swap(none.bytes, rows16_.bytes);
+        scan_ = 0;
+        return;
+    }
+    if (scan_ != 1) {
+        ctr_.ensure(2 * sizeof(unsigned long long));
+        FH_HIP(hipMemset(ctr_.p, 0, 2 * sizeof(unsigned long long)));
+        if (n_ > 0) {
+            rows16_.ensure((size_t)n_ * dim_ * sizeof(uint16_t));
+            convert16(0, n_);
+        }
+        scan_ = 1;
+    }
+}
+
+void Gallery::scan_stats(long long* certified, long long* fallback) {
+    unsigned long long h[2] = {0, 0};
+    FH_HIP(hipDeviceSynchronize());
+    if (ctr_.p) {
+        FH_HIP(hipMemcpy(h, ctr_.p, sizeof(h), hipMemcpyDeviceToHost));
+        FH_HIP(hipMemset(ctr_.p, 0, sizeof(h)));
+    }
+    if (certified) *certified = (long long)h[0];
+    if (fallback) *fallback = (long long)h[1] + host_fallback_;
+    host_fallback_ = 0;
 }
 
 long Gallery::enroll(const float* rows, long n, bool device_src) {
@@ -732,6 +780,17 @@ long Gallery::enroll(const float* rows, long n, bool device_src) {
     }
     FH_HIP(hipMemcpy(static_cast<char*>(rows_.p) + (size_t)n_ * row_bytes, rows, (size_t)n * row_bytes,
                      device_src ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
+    if (scan_ == 1) {                                            // the fp16 copy grows with the fp32 rows (same capacity in rows)
+        const size_t row16 = (size_t)dim_ * sizeof(uint16_t), cap16 = rows_.bytes / row_bytes * row16;
+        if (cap16 > rows16_.bytes) {
+            DevBuf bigger;
+            bigger.ensure(cap16);
+            if (n_ > 0) FH_HIP(hipMemcpy(bigger.p, rows16_.p, (size_t)n_ * row16, hipMemcpyDeviceToDevice));
+            std::swap(bigger.p, rows16_.p);
+            std::swap(bigger.bytes, rows16_.bytes);
+        }
+        convert16(n_, n);
+    }
     const long first = base_ + n_;
     n_ += n;
     return first;
@@ -746,11 +805,55 @@ void Gallery::label_dev(const float* q, int Q, float thr, int* out_label, float*
 void Gallery::topk_dev(const float* q, int Q, int k, float* out_score, int* out_idx, hipStream_t s) {
     if (Q <= 0 || Q > 256 || k <= 0 || k > 16) throw std::runtime_error("gallery: need 0 < Q <= 256 and 0 < k <= 16");
     if (dim_ % 64) throw std::runtime_error("gallery: dim must be a multiple of 64");
+    if (scan_ == 1) {
+        // F16_RERANK (gallery_f16.hip): fp16 scan for 32 candidates per query -> exact fp32 re-score + certificate -> the uncertified
+        // queries, compacted on the device, through the fp32 scan below.  Rows with a value the fp16 copy cannot hold (non-finite,
+        // > 65504), an empty gallery and dims that are not a multiple of 128 take the fp32 scan for the whole batch.
+        if (!f16_bad_ && n_ > 0 && dim_ % 128 == 0) {
+            topk_f16(q, Q, k, out_score, out_idx, s);
+            return;
+        }
+        host_fallback_ += Q;
+    }
+    topk_f32(q, Q, k, out_score, out_idx, s, nullptr);
+}
+
+void Gallery::topk_f16(const float* q, int Q, int k, float* out_score, int* out_idx, hipStream_t s) {
+    const int qrows = (Q + 63) / 64 * 64, KC = GAL16_KC;
+    const int parts16 = gallery16_parts(n_, Q, nullptr);
+    q16_.ensure((size_t)qrows * dim_ * sizeof(uint16_t));
+    ps16_.ensure((size_t)parts16 * Q * KC * sizeof(float));
+    pi16_.ensure((size_t)parts16 * Q * KC * sizeof(int));
+    seed16_s_.ensure((size_t)Q * KC * sizeof(float));
+    seed16_i_.ensure((size_t)Q * KC * sizeof(int));
+    cand_s_.ensure((size_t)Q * KC * sizeof(float));
+    cand_i_.ensure((size_t)Q * KC * sizeof(int));
+    fb_cnt_.ensure(sizeof(int));
+    fb_idx_.ensure((size_t)Q * sizeof(int));
+    fb_s_.ensure((size_t)Q * k * sizeof(float));
+    fb_i_.ensure((size_t)Q * k * sizeof(int));
+    FH_HIP(hipMemsetAsync(fb_cnt_.p, 0, sizeof(int), s));
+    launch_gallery16_candidates(rows16_.as<uint16_t>(), n_, dim_, q, q16_.as<uint16_t>(), Q, base_, ps16_.as<float>(), pi16_.as<int>(),
+                                seed16_s_.as<float>(), seed16_i_.as<int>(), cand_s_.as<float>(), cand_i_.as<int>(), s);
+    launch_gallery16_rescore(rows_.as<float>(), n_, dim_, q, Q, k, base_, cand_s_.as<float>(), cand_i_.as<int>(), gbound_[0], gbound_[1],
+                             gbound_[2], out_score, out_idx, fb_cnt_.as<int>(), fb_idx_.as<int>(), ctr_.as<unsigned long long>(), s);
+    // fall-back: the fp32 scan for the compacted uncertified queries (workgroups beyond the device count exit at once), then scatter
+    qpack_.ensure((size_t)qrows * dim_ * sizeof(float));
+    launch_gallery16_gather(q, Q, dim_, fb_cnt_.as<int>(), fb_idx_.as<int>(), qpack_.as<float>(), s);
+    topk_f32(nullptr, Q, k, fb_s_.as<float>(), fb_i_.as<int>(), s, fb_cnt_.as<int>());
+    launch_gallery16_scatter(fb_s_.as<float>(), fb_i_.as<int>(), Q, k, fb_cnt_.as<int>(), fb_idx_.as<int>(), out_score, out_idx, s);
+    FH_HIP(hipGetLastError());
+}
+
+// q == nullptr: qpack_ is already filled (the F16_RERANK fall-back); qcount (device, optional): only that many queries are live
+void Gallery::topk_f32(const float* q, int Q, int k, float* out_score, int* out_idx, hipStream_t s, const int* qcount) {
     // queries as the GEMM's N operand: whole 64-row tiles, zero rows behind Q (only that tail is cleared)
     const int qrows = (Q + 63) / 64 * 64;
     qpack_.ensure((size_t)qrows * dim_ * sizeof(float));
-    if (qrows > Q) FH_HIP(hipMemsetAsync(qpack_.as<float>() + (size_t)Q * dim_, 0, (size_t)(qrows - Q) * dim_ * sizeof(float), s));
-    FH_HIP(hipMemcpyAsync(qpack_.p, q, (size_t)Q * dim_ * sizeof(float), hipMemcpyDeviceToDevice, s));
+    if (q) {
+        if (qrows > Q) FH_HIP(hipMemsetAsync(qpack_.as<float>() + (size_t)Q * dim_, 0, (size_t)(qrows - Q) * dim_ * sizeof(float), s));
+        FH_HIP(hipMemcpyAsync(qpack_.p, q, (size_t)Q * dim_ * sizeof(float), hipMemcpyDeviceToDevice, s));
+    }
     int tpp = 0;
     const int parts = n_ > 0 ? gallery_parts(n_, Q, &tpp) : 0;
     ps_.ensure((size_t)std::max(parts, 1) * Q * k * sizeof(float));
@@ -758,9 +861,9 @@ void Gallery::topk_dev(const float* q, int Q, int k, float* out_score, int* out_
     // ONE pass over the gallery: dot products stay in the MFMA accumulators, per-workgroup top-k lists come out (gallery.hip)
     seed_s_.ensure((size_t)Q * k * sizeof(float));
     seed_i_.ensure((size_t)Q * k * sizeof(int));
-    launch_gallery_topk(rows_.as<float>(), n_, dim_, qpack_.as<float>(), Q, k, base_, ps_.as<float>(), pi_.as<int>(), seed_s_.as<float>(),
-                        seed_i_.as<int>(), s);
-    launch_topk_merge(ps_.as<float>(), pi_.as<int>(), parts, Q, k, out_score, out_idx, s);
+    launch_gallery_topk(rows_.as<float>(), n_, dim_, qpack_.as<float>(), Q, k, base_, ps_.as<float>(), pi_.as<int>(),
+                        qcount ? nullptr : seed_s_.as<float>(), qcount ? nullptr : seed_i_.as<int>(), s, qcount);
+    launch_topk_merge(ps_.as<float>(), pi_.as<int>(), parts, Q, k, out_score, out_idx, s, qcount);
     FH_HIP(hipGetLastError());
 }
 

@@ -177,11 +177,26 @@ class Gallery {
     void topk_dev(const float* q, int Q, int k, float* out_score, int* out_idx, hipStream_t s);
     long size() const { return n_; }
     int dim() const { return dim_; }
+    // fh_gallery_set_scan: 1 = F16_RERANK (an fp16 copy of the rows beside the fp32 rows, G x dim x 2 bytes; same answer bit for bit),
+    // 0 = FP32 (frees the copy).  Synchronous.
+    void set_scan(int mode);
+    int scan() const { return scan_; }
+    void scan_stats(long long* certified, long long* fallback);   // waits for the device; resets both
 
   private:
+    void convert16(long first, long n);                          // rows [first, first + n) -> rows16_, bounds + flag (synchronous)
+    void topk_f16(const float* q, int Q, int k, float* out_score, int* out_idx, hipStream_t s);
+    void topk_f32(const float* q, int Q, int k, float* out_score, int* out_idx, hipStream_t s, const int* qcount);
     int dim_;
     long n_ = 0, base_ = 0;
     DevBuf rows_, qpack_, ps_, pi_, best_i_, seed_s_, seed_i_;
+    // F16_RERANK state: the fp16 rows, [max|g|, max|g^|, max|g - g^| (float bits), non-finite / > 65504 flag] on the device and its host
+    // copy, per-call scratch, the certified / fallback counters
+    int scan_ = 0;
+    bool f16_bad_ = false;
+    float gbound_[3] = {0.f, 0.f, 0.f};
+    long long host_fallback_ = 0;
+    DevBuf rows16_, gstat_, q16_, ps16_, pi16_, seed16_s_, seed16_i_, cand_s_, cand_i_, fb_cnt_, fb_idx_, fb_s_, fb_i_, ctr_;
 };
 
 }  // namespace fh

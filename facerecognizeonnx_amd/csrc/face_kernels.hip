@@ -474,10 +474,12 @@ __device__ __forceinline__ bool better(float s1, int i1, float s2, int i2) { ret
 // a wave reduction + one LDS hand-off between the four waves; otherwise each round re-reads the lists from memory (L2).
 template <bool CACHED>
 __global__ __launch_bounds__(256) void topk_merge_kernel(const float* __restrict__ ps, const int* __restrict__ pi, int nparts, int Q, int k,
-                                                         long part_stride, float* __restrict__ out_s, int* __restrict__ out_i) {
+                                                         long part_stride, float* __restrict__ out_s, int* __restrict__ out_i,
+                                                         const int* __restrict__ qcount) {
     __shared__ float rs[256];
     __shared__ int ri[256];
     const int q = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    if (qcount && q >= *qcount) return;                  // (optional device query count: the compacted fall-back of the f16 re-rank scan)
     const int total = nparts * k;
     constexpr int E = 32;
     float es[E]; int ei[E];
@@ -558,13 +560,13 @@ void launch_label(const float* best_score, const int* best_idx, int n, float thr
 // part_stride = words between the lists of consecutive parts (Q * k when they are packed; the sharded exchange of comm.cpp interleaves
 // score and index planes per rank)
 void launch_topk_merge_strided(const float* part_score, const int* part_idx, int nparts, int Q, int k, long part_stride, float* out_score,
-                               int* out_idx, hipStream_t s) {
-    if ((long)nparts * k <= 8192) hipLaunchKernelGGL(topk_merge_kernel<true>, dim3(Q), dim3(256), 0, s, part_score, part_idx, nparts, Q, k, part_stride, out_score, out_idx);
-    else hipLaunchKernelGGL(topk_merge_kernel<false>, dim3(Q), dim3(256), 0, s, part_score, part_idx, nparts, Q, k, part_stride, out_score, out_idx);
+                               int* out_idx, hipStream_t s, const int* qcount) {
+    if ((long)nparts * k <= 8192) hipLaunchKernelGGL(topk_merge_kernel<true>, dim3(Q), dim3(256), 0, s, part_score, part_idx, nparts, Q, k, part_stride, out_score, out_idx, qcount);
+    else hipLaunchKernelGGL(topk_merge_kernel<false>, dim3(Q), dim3(256), 0, s, part_score, part_idx, nparts, Q, k, part_stride, out_score, out_idx, qcount);
 }
 void launch_topk_merge(const float* part_score, const int* part_idx, int nparts, int Q, int k, float* out_score, int* out_idx,
-                       hipStream_t s) {
-    launch_topk_merge_strided(part_score, part_idx, nparts, Q, k, (long)Q * k, out_score, out_idx, s);
+                       hipStream_t s, const int* qcount) {
+    launch_topk_merge_strided(part_score, part_idx, nparts, Q, k, (long)Q * k, out_score, out_idx, s, qcount);
 }
 
 // ------------------------------------------------------------------------------------------

@@ -71,6 +71,7 @@ struct GalArgs {
     int* pi;
     const float* seed_s;    // optional [Q][k]: exact top-k of a PREFIX of the gallery — its k-th entry is a valid admission threshold for
     const int* seed_i;      // the whole scan (k rows at least as good exist), so the per-workgroup lists start almost closed
+    const int* qcount;      // optional (device): query tiles at or beyond *qcount exit at once (null: all Q)
 };
 
 __device__ __forceinline__ bool gal_better(float s1, int i1, float s2, int i2) { return s1 > s2 || (s1 == s2 && i1 < i2); }
@@ -94,6 +95,7 @@ __global__ __launch_bounds__(256, 2) void gallery_topk_kernel(const GalArgs p) {
     }
     const int tile_n = t % p.tiles_n, part = t / p.tiles_n;
     const int n0 = tile_n * BN;
+    if (p.qcount && n0 >= *p.qcount) return;                  // (workgroup-uniform, before any barrier)
     const int K = p.dim, chunks = K / 64, k = p.k;
     const int rt0 = part * p.tiles_per_part, rt1 = min(p.row_tiles, rt0 + p.tiles_per_part);
 
@@ -279,14 +281,14 @@ int gallery_parts(long G, int Q, int* tiles_per_part) {
 // Two passes for a large gallery: the exact top-k of the first GAL_SEED_ROWS rows (same kernel + merge) gives every query an admission
 // threshold, then the full scan runs with it — without the seed every workgroup spends its first tiles sorting rows that cannot matter.
 void launch_gallery_topk(const float* gal, long G, int dim, const float* qpacked, int Q, int k, long idx_base, float* part_score, int* part_idx,
-                         float* seed_score, int* seed_idx, hipStream_t s) {
+                         float* seed_score, int* seed_idx, hipStream_t s, const int* qcount) {
     if (G <= 0 || Q <= 0) return;
     if (dim % 64 || k < 1 || k > GAL_KMAX) throw std::runtime_error("gallery: need dim % 64 == 0 and 1 <= k <= 16");
     if (idx_base + G > (long)INT_MAX) throw std::runtime_error("gallery: global row indices must fit in 31 bits");
     GalArgs a{};
     a.gal = gal; a.q = qpacked; a.zeros = conv_zero_line(); a.idx_base = idx_base; a.dim = dim; a.Q = Q; a.k = k;
     a.tiles_n = (Q + GAL_BN - 1) / GAL_BN;
-    a.ps = part_score; a.pi = part_idx;
+    a.ps = part_score; a.pi = part_idx; a.qcount = qcount;
     constexpr long GAL_SEED_ROWS = 4096;
     static int seed_on = -1;
     if (seed_on < 0) { const char* e = getenv("FACEHIP_GAL_SEED"); seed_on = e ? atoi(e) : 1; }     // (0: no seed pass — A / B timing)

@@ -276,13 +276,38 @@ void launch_l2_normalize(const float* in, float* out, int n, int dim, hipStream_
 // gallery.hip: ONE streaming pass — gallery rows x queries on the matrix cores, per-workgroup top-k lists [gallery_parts][Q][k] kept in
 // LDS while the rows go by (no G x Q matrix in memory); then launch_topk_merge.  qpacked = [ceil64(Q)][dim], zero rows behind Q.
 int gallery_parts(long G, int Q, int* tiles_per_part);
+// qcount (optional, device): only query tiles below *qcount are scanned, the grid stays sized for Q (the compacted fall-back of the
+// f16 re-rank scan); null = all Q
 void launch_gallery_topk(const float* gal, long G, int dim, const float* qpacked, int Q, int k, long idx_base, float* part_score, int* part_idx,
-                         float* seed_score, int* seed_idx, hipStream_t s);      // seed_*: [Q][k] scratch (threshold pre-pass of large galleries)
+                         float* seed_score, int* seed_idx, hipStream_t s,       // seed_*: [Q][k] scratch (threshold pre-pass of large galleries)
+                         const int* qcount = nullptr);
 void launch_label(const float* best_score, const int* best_idx, int n, float thr, int* labels, hipStream_t s);
 void launch_topk_merge(const float* part_score, const int* part_idx, int nparts, int Q, int k, float* out_score,
-                       int* out_idx, hipStream_t s);
+                       int* out_idx, hipStream_t s, const int* qcount = nullptr);     // qcount (device, optional): queries >= *qcount skipped
 void launch_topk_merge_strided(const float* part_score, const int* part_idx, int nparts, int Q, int k, long part_stride, float* out_score,
-                               int* out_idx, hipStream_t s);
+                               int* out_idx, hipStream_t s, const int* qcount = nullptr);
+
+// gallery_f16.hip — the opt-in F16_RERANK scan (fh_gallery_set_scan): an fp16 copy of the rows is scanned for the top GAL16_KC candidates
+// per query, the candidates are re-scored from the fp32 rows exactly as gallery_topk_kernel scores them, and a per-query certificate
+// proves that no other row can reach the top-k; uncertified queries are compacted on the device (fb_count / fb_idx) for the fp32 scan.
+constexpr int GAL16_KC = 32;
+// f32 -> f16 (round to nearest even) of n rows; stats[0..2] = float bits of max ||g||, max ||g^||, max ||g - g^|| (rounded up, atomicMax
+// into what is there), stats[3] |= 1 when a value is non-finite or |x| > 65504
+void launch_gallery16_convert(const float* rows, uint16_t* rows16, long n, int dim, unsigned* stats, hipStream_t s);
+int gallery16_parts(long G, int Q, int* tiles_per_part);
+// queries [Q][dim] f32 -> q16 [ceil64(Q)][dim] -> fp16 scan + merge: cand_* = [Q][GAL16_KC] (fp16 mapped score, global index; -1 = none)
+// part_*: [gallery16_parts][Q][GAL16_KC], seed_*: [Q][GAL16_KC]
+void launch_gallery16_candidates(const uint16_t* rows16, long G, int dim, const float* q, uint16_t* q16, int Q, long idx_base, float* part_score,
+                                 int* part_idx, float* seed_score, int* seed_idx, float* cand_score, int* cand_idx, hipStream_t s);
+// exact fp32 re-score of the candidates + top-k + certificate (bounds = max ||g||, max ||g^||, max ||g - g^||); certified queries are
+// written to out_*, the others appended to fb_idx (fb_count must be 0 before); counters[0] += certified, counters[1] += fallback
+void launch_gallery16_rescore(const float* rows, long G, int dim, const float* q, int Q, int k, long idx_base, const float* cand_score,
+                              const int* cand_idx, float gn, float ghn, float dn, float* out_score, int* out_idx, int* fb_count, int* fb_idx,
+                              unsigned long long* counters, hipStream_t s);
+// qpacked [ceil64(Q)][dim]: row r < *fb_count = q[fb_idx[r]], zero behind; then the fp32 answers fb_* [*fb_count][k] back to rows fb_idx
+void launch_gallery16_gather(const float* q, int Q, int dim, const int* fb_count, const int* fb_idx, float* qpacked, hipStream_t s);
+void launch_gallery16_scatter(const float* fb_score, const int* fb_idx_out, int Q, int k, const int* fb_count, const int* fb_idx, float* out_score,
+                              int* out_idx, hipStream_t s);
 
 // detect -> embed hand-off: first min(count,F) faces per frame, densely packed (n <= 4096 frames)
 void launch_select_faces(const FaceRec* det, const int* counts, int n, int per_frame, int F, FaceRec* faces, int* frame_of,

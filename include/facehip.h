@@ -165,6 +165,21 @@ FH_API void fh_gallery_destroy(fh_gallery* g);
 FH_API int fh_gallery_upload(fh_gallery* g, const float* rows, long long n, int rows_on_device, long long index_base);
 FH_API int fh_gallery_topk_dev(fh_gallery* g, const float* d_queries, int nq, int k, float* d_scores, int* d_indices,
                                void* stream);
+/* Scan mode of a gallery (default FP32).  F16_RERANK scans an fp16 copy of the rows for 32 candidates per query, re-scores
+ * them from the fp32 rows exactly as the fp32 scan does and proves per query that no other row can reach the top-k; a query
+ * whose proof fails is answered by the fp32 scan on the device.  fh_gallery_topk_dev, fh_gallery_label_dev and
+ * fh_gallery_topk_sharded_dev return the FP32 answer bit for bit (scores and indices, -1 slots included) for finite rows and
+ * queries, asynchronously on the caller's stream, capturable into a graph after one call of the same (nq, k); limits as
+ * fh_gallery_topk_dev.  Extra device memory: G x dim x 2 bytes.  A gallery holding a non-finite value or one beyond the fp16
+ * range (|x| > 65504), or a dim that is not a multiple of 128, is scanned in fp32 whatever the mode. */
+enum fh_gallery_scan { FH_GAL_SCAN_FP32 = 0, FH_GAL_SCAN_F16_RERANK = 1 };
+/* Synchronous.  F16_RERANK builds an fp16 copy of the rows already uploaded / enrolled (and keeps it in step with later
+ * upload / enroll calls) beside the fp32 rows; FP32 frees it.  FH_ERR_ARG for an unknown mode or a NULL handle. */
+FH_API int fh_gallery_set_scan(fh_gallery* g, int mode);
+FH_API int fh_gallery_get_scan(const fh_gallery* g);
+/* Waits for the handle's queued calls; number of queries answered by the certified fp16 path and by the fp32 fallback
+ * since the last call of this function (which resets both). */
+FH_API int fh_gallery_scan_stats(fh_gallery* g, long long* certified, long long* fallback);
 /* Merge step of a row-SHARDED gallery (one shard per rank): d_part_scores / d_part_idx = [nparts][nq][k]
  * per-shard top-k lists (global row indices, -1 = empty slot) as one all-gather delivers them -> the overall top-k by
  * (score desc, index asc), the same total order and the same kernel fh_gallery_topk_dev finishes with, so a sharded
