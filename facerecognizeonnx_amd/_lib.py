@@ -130,6 +130,7 @@ PROTOTYPES = {
     "fh_rec_set_cus": (_i, [_vp, _i]),
     "fh_debug_streamk": (_i, [_i, _i]),
     "fh_debug_wino_slots": (_i, [_i]),
+    "fh_debug_topk_merge_strided_dev": (_i, [_vp, _vp, _i, _i, _i, _ll, _vp, _vp, _vp]),
     "fh_set_graph_replay": (_i, [_i]),
     "fh_det_workspace_dev": (_vp, [_vp]),
     "fh_det_graph_stats": (_i, [_vp, _vp]),

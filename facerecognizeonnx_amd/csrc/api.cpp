@@ -687,6 +687,18 @@ int fh_topk_merge_dev(const float* ps, const int* pi, int nparts, int nq, int k,
     });
 }
 
+int fh_debug_topk_merge_strided_dev(const float* ps, const int* pi, int nparts, int nq, int k, long long part_stride, float* scores, int* indices,
+                                    void* stream) {
+    if (!ps || !pi || !scores || !indices) return arg_error("fh_debug_topk_merge_strided_dev: null argument");
+    if (nparts <= 0 || nq <= 0 || k <= 0 || k > 16 || (long)nparts * k > 65536 || part_stride < (long long)nq * k)
+        return arg_error("fh_debug_topk_merge_strided_dev: bad size");
+    return guarded([&] {
+        fh::launch_topk_merge_strided(ps, pi, nparts, nq, k, (long)part_stride, scores, indices, S(stream));
+        FH_HIP(hipGetLastError());
+        return nq;
+    });
+}
+
 // ---------------------------------------------------------------------------------- timing / tuning
 int fh_timing_enable(int on) { fh::KernelTimer::get().enabled = on != 0; return FH_OK; }
 int fh_timing_num_tags(void) { return fh::KernelTimer::kTags; }

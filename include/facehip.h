@@ -324,6 +324,11 @@ FH_API int fh_debug_streamk(int drop_publish, int timeout_ms);
  * slots walk several tiles per workgroup; slots > 0 makes the launcher pretend the device has that many (rounded up to 8), so that small
  * test layers take the multi-tile path with many tiles per workgroup; 0 restores the device's own count. */
 FH_API int fh_debug_wino_slots(int slots);
+/* Test hook of the top-k merge (face_kernels.hip topk_merge_kernel) with the list layout of the sharded exchange: part w's [nq][k]
+ * scores start at ps + w * part_stride and its indices at pi + w * part_stride (comm.cpp gathers [scores | indices] per rank, so
+ * part_stride = 2 * nq * k there).  Needs 1 <= k <= 16, nparts * k <= 65536 and part_stride >= nq * k; returns nq. */
+FH_API int fh_debug_topk_merge_strided_dev(const float* d_ps, const int* d_pi, int nparts, int nq, int k, long long part_stride,
+                                           float* d_scores, int* d_indices, void* stream);
 FH_API int fh_conv_wt_rows(int cout);
 /* host: weights [cout][ksize*ksize][cin] (O,H,W,I) -> the kernel's packed image [fh_conv_wt_rows][fh_conv_kpad] */
 FH_API int fh_conv_pack_weights(const float* w_ohwi, int cout, int cin, int ksize, float* dst_packed);

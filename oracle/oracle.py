@@ -312,6 +312,30 @@ def gallery_topk(q, gal, k):
     return s, i
 
 
+def gallery_topk_mfma(q, gal, k, base=0):
+    """Exact model of the GPU gallery scan (gallery_topk_kernel): every score is the k-ordered f32 fma chain of
+    v_mfma_f32_32x32x2_f32 (k0 = 64 kc + 8 s + e, k1 = k0 + 4), mapped (acc + 1) / 2 in f32; top-k by (score desc, index asc),
+    NaN never listed, empty slots (-1.0, -1); indices are base + row."""
+    q = np.ascontiguousarray(q, np.float32); gal = np.ascontiguousarray(gal, np.float32)
+    Q, dim = q.shape; G = gal.shape[0]
+    assert dim % 64 == 0 and gal.shape[1] == dim and k > 0 and base + G <= 2**31 - 1
+    s = np.empty((Q, k), np.float32); i = np.empty((Q, k), np.int32)
+    rc = lib().orc_gallery_topk_mfma(_f(q), Q, _f(gal), C.c_long(G), dim, k, C.c_long(base), _f(s),
+                                     i.ctypes.data_as(C.POINTER(C.c_int)))
+    assert rc == 0
+    return s, i
+
+
+def dot_mfma(q, gal):
+    """Raw accumulators (before the (acc + 1) / 2 mapping) of one query against every row, in the scan's fma order."""
+    q = np.ascontiguousarray(q, np.float32).reshape(-1); gal = np.ascontiguousarray(gal, np.float32)
+    G, dim = gal.shape
+    assert dim % 64 == 0 and q.size == dim
+    out = np.empty(G, np.float32)
+    assert lib().orc_dot_mfma(_f(q), _f(gal), C.c_long(G), dim, _f(out)) == 0
+    return out
+
+
 # ------------------------------------------------------------------ reference-shaped classes
 class OracleDetector:
     """Restates FaceDetector (face_detector.h:14-43)."""

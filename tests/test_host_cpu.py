@@ -213,6 +213,23 @@ def test_round5_test_entry_points_validate_their_arguments_without_a_gpu():
     assert L.fh_debug_wino_slots(24) == 0 and L.fh_debug_wino_slots(0) == 0
 
 
+def test_strided_merge_hook_validates_its_arguments_without_a_gpu():
+    """fh_debug_topk_merge_strided_dev (the sharded exchange's merge layout) rejects what fh_topk_merge_dev rejects, and a part
+    stride shorter than one part's nq * k lists, before anything touches a device."""
+    L = fa.lib()
+    one = ctypes.c_void_p(16)
+    M = L.fh_debug_topk_merge_strided_dev
+    for nulls in range(4):
+        args = [one] * 4
+        args[nulls] = None
+        assert M(args[0], args[1], 2, 3, 4, 24, args[2], args[3], None) == -1
+        assert "null argument" in _lib.last_error()
+    for nparts, nq, k, stride in ((2, 3, 0, 24), (2, 3, 17, 102), (4097, 1, 16, 16), (65537, 1, 1, 1), (0, 3, 4, 12), (2, 0, 4, 12),
+                                  (2, 3, 4, 11), (2, 3, 4, -1)):
+        assert M(one, one, nparts, nq, k, stride, one, one, None) == -1, (nparts, nq, k, stride)
+        assert "fh_debug_topk_merge_strided_dev: bad size" in _lib.last_error()
+
+
 def test_public_header_is_plain_c_and_the_integration_snippet_compiles(tmp_path):
     """include/facehip.h is the drop-in boundary: it must be consumable from C (cgo / JNI / ctypes-style bindings), not only from C++.
     The sharded-gallery loop of INTEGRATION.md section 4, written out as C99, compiles with -Wall -Wextra -Werror -pedantic and links
