@@ -890,7 +890,10 @@ std::string Plan::describe() const {
         if (o.out2 >= 0) os << (o.out >= 0 ? " +bn2nd" : " bn2nd-only");
         if (o.bn_src >= 0) os << " bn<-op" << o.bn_src;
         if (o.sc_src >= 0) os << " sc<-op" << o.sc_src;
-        os << "  [in t" << o.in << " out t" << o.out << " out2 t" << o.out2 << "]";
+        // every tensor the op itself reads or writes (the links above add the implied reads)
+        os << "  [in t" << o.in << " out t" << o.out << " out2 t" << o.out2 << " in2 t" << o.in2 << " res t" << o.res;
+        for (size_t k = 0; k < o.outs.size(); ++k) os << (k ? ",t" : " outs t") << o.outs[k];
+        os << "]";
         os << "  MMAC " << o.macs * 1e-6 << "\n";
     }
     for (auto& d : outputs) os << "out " << d.name << " [" << d.rows << "x" << d.cols << "]\n";

@@ -152,8 +152,8 @@ def run_graph(g: onnx_min.Graph, feeds: dict) -> dict:
                 y = np.asarray(i[0])[np.asarray(i[1], np.int64)]
             else:
                 y = np.atleast_1d(i[0])
-        elif n.op == "Resize":
-            scales = i[2] if len(i) > 2 and i[2] is not None and i[2].size else None
+        elif n.op in ("Resize", "Upsample"):
+            scales = i[1] if n.op == "Upsample" else i[2] if len(i) > 2 and i[2] is not None and i[2].size else None
             if scales is not None:
                 s = int(scales[2]); assert list(scales) == [1, 1, s, s]
             else:

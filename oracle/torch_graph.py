@@ -64,6 +64,10 @@ def _run(g, inits, feeds, dtype) -> dict:
             y = torch.cat([v.reshape(-1) for v in i])
         elif n.op == "Cast":
             y = i[0].to(torch.int64)
+        elif n.op == "Upsample":
+            s = int(i[1][2])
+            assert a.get("mode", "nearest") == "nearest" and [float(v) for v in i[1]] == [1, 1, s, s], (a, i[1])
+            y = F.interpolate(i[0], scale_factor=s, mode="nearest")
         elif n.op == "Resize":
             s = int(i[2][2]) if len(i) > 2 and i[2] is not None and i[2].numel() else int(i[3][2]) // i[0].shape[2]
             y = F.interpolate(i[0], scale_factor=s, mode="nearest")
