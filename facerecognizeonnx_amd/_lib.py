@@ -65,6 +65,7 @@ PROTOTYPES = {
     "fh_det_detect": (_i, [_vp, _vp, _i, _i, _i, _f, _f, _vp, _i]),
     "fh_det_detect_batch_dev": (_i, [_vp, _vp, _i, _i, _i, _i, _ll, _f, _f, _vp, _i, _vp, _vp]),
     "fh_det_run_network_dev": (_i, [_vp, _vp, _i, _i, _i, _i, _ll, _vp]),
+    "fh_det_run_input_dev": (_i, [_vp, _vp, _i, _vp]),
     "fh_det_num_outputs": (_i, [_vp]),
     "fh_det_output_dev": (_vp, [_vp, _i, _ip, _ip]),
     "fh_det_input_dev": (_vp, [_vp]),
@@ -81,6 +82,7 @@ PROTOTYPES = {
     "fh_rec_extract_simple": (_i, [_vp, _vp, _i, _i, _i, _vp, _i]),
     "fh_compare": (_f, [_vp, _i, _vp, _i]),
     "fh_rec_embed_aligned_dev": (_i, [_vp, _vp, _i, _vp, _vp, _vp]),
+    "fh_rec_run_input_dev": (_i, [_vp, _vp, _i, _vp, _vp, _vp]),
     "fh_rec_align_dev": (_i, [_vp, _vp, _i, _i, _i, _ll, _vp, _vp, _i, _vp, _vp, _vp]),
     "fh_rec_input_dev": (_vp, [_vp]),
     "fh_rec_embed_faces_dev": (_i, [_vp, _vp, _i, _i, _i, _ll, _vp, _vp, _i, _vp, _vp, _vp]),

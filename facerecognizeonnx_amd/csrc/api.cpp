@@ -308,6 +308,12 @@ int fh_det_run_network_dev(fh_det* d, const uint8_t* frames, int n, int rows, in
     Owns owns(&d->det.net());
     return guarded([&] { d->det.run_network_dev(frames, n, rows, cols, step, (long)stride, S(stream)); return n; });
 }
+int fh_det_run_input_dev(fh_det* d, const float* input, int n, void* stream) {
+    if (!d || !input || n <= 0) return arg_error("fh_det_run_input_dev: bad argument");
+    if (d->det.net().plan().tensors[d->det.net().plan().input].C != 4) return arg_error("fh_det_run_input_dev: the graph input is not a 3-channel image");
+    Owns owns(&d->det.net());
+    return guarded([&] { d->det.run_input_dev(input, n, S(stream)); return n; });
+}
 int fh_det_num_outputs(const fh_det* d) { return d ? (int)const_cast<fh_det*>(d)->det.net().plan().outputs.size() : arg_error("null handle"); }
 const float* fh_det_output_dev(fh_det* d, int index, int* rows, int* cols) {
     if (!d || index < 0 || index >= (int)d->det.net().plan().outputs.size()) { g_err = "bad output index"; return nullptr; }
@@ -395,6 +401,12 @@ int fh_rec_embed_aligned_dev(fh_rec* r, const uint8_t* crops, int n, float* out,
     if (!r || !crops || !out || n <= 0) return arg_error("fh_rec_embed_aligned_dev: bad argument");
     Owns owns(&r->rec.net());
     return guarded([&] { r->rec.embed_aligned_dev(crops, n, out, S(stream), raw); return n; });
+}
+int fh_rec_run_input_dev(fh_rec* r, const float* input, int n, float* out, float* raw, void* stream) {
+    if (!r || !input || !out || n <= 0) return arg_error("fh_rec_run_input_dev: bad argument");
+    if (r->rec.net().plan().tensors[r->rec.net().plan().input].C != 4) return arg_error("fh_rec_run_input_dev: the graph input is not a 3-channel image");
+    Owns owns(&r->rec.net());
+    return guarded([&] { r->rec.embed_input_dev(input, n, out, S(stream), raw); return n; });
 }
 int fh_rec_sync(fh_rec* r, void* stream) {
     if (!r) return arg_error("fh_rec_sync: null handle");

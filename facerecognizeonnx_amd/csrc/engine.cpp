@@ -643,6 +643,13 @@ void Detector::run_network_dev(const uint8_t* frames, int n, int rows, int cols,
     net_.run_u8(src, sstride, newH, newW, sstep, n, s);
 }
 
+void Detector::run_input_dev(const float* input, int n, hipStream_t s) {
+    reserve(n, 0, 0);
+    const size_t per = (size_t)net_.in_h() * net_.in_w() * 4;
+    FH_HIP(hipMemcpyAsync(net_.input(), input, (size_t)n * per * sizeof(float), hipMemcpyDeviceToDevice, s));
+    net_.run(n, s);
+}
+
 void Detector::postprocess_dev(int n, float score_thr, float nms_thr, FaceRec* out, int max_out, int* counts, hipStream_t s) {
     if (anchors_ <= 0) { FH_HIP(hipMemsetAsync(counts, 0, (size_t)n * sizeof(int), s)); return; }
     FH_HIP(hipMemsetAsync(count_.p, 0, (size_t)n * sizeof(int), s));
@@ -680,6 +687,19 @@ void Recognizer::embed_aligned_dev(const uint8_t* crops, int n, float* out, hipS
     for (int off = 0; off < n; off += max_chunk) {
         const int c = std::min(max_chunk, n - off);
         net_.run_u8(crops + (size_t)off * H * W * 3, (long)H * W * 3, H, W, W * 3, c, s);
+        if (raw_out) FH_HIP(hipMemcpyAsync(raw_out + (size_t)off * dim_, net_.output(0), (size_t)c * dim_ * sizeof(float), hipMemcpyDeviceToDevice, s));
+        launch_l2_normalize(net_.output(0), out + (size_t)off * dim_, c, dim_, s);
+    }
+    FH_HIP(hipGetLastError());
+}
+
+void Recognizer::embed_input_dev(const float* input, int n, float* out, hipStream_t s, float* raw_out) {
+    const size_t per = (size_t)net_.in_h() * net_.in_w() * 4;
+    net_.reserve(std::min(n, max_chunk));
+    for (int off = 0; off < n; off += max_chunk) {
+        const int c = std::min(max_chunk, n - off);
+        FH_HIP(hipMemcpyAsync(net_.input(), input + (size_t)off * per, (size_t)c * per * sizeof(float), hipMemcpyDeviceToDevice, s));
+        net_.run(c, s);
         if (raw_out) FH_HIP(hipMemcpyAsync(raw_out + (size_t)off * dim_, net_.output(0), (size_t)c * dim_ * sizeof(float), hipMemcpyDeviceToDevice, s));
         launch_l2_normalize(net_.output(0), out + (size_t)off * dim_, c, dim_, s);
     }

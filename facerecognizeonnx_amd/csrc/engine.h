@@ -135,6 +135,9 @@ class Detector {
     // stage hooks used by parity tests (device pointers)
     void run_network_dev(const uint8_t* frames, int n, int rows, int cols, int step, long stride, hipStream_t s);
     void postprocess_dev(int n, float score_thr, float nms_thr, FaceRec* out, int max_out, int* counts, hipStream_t s);
+    // input: device [n][inH][inW][4] preprocessed floats (lane 3 = 0) -> copied into net().input(), then every op runs (the path
+    // run_u8 takes with the fused stem off, minus the preprocess kernel)
+    void run_input_dev(const float* input, int n, hipStream_t s);
 
   private:
     void reserve(int n, int rows, int cols);
@@ -158,6 +161,8 @@ class Recognizer {
     void align_dev(const uint8_t* frames, int rows, int cols, int step, long stride, const FaceRec* faces, const int* frame_of,
                    int n, uint8_t* crops, int* ok, hipStream_t s);
     void resize_embed_dev(const uint8_t* frames, int n, int rows, int cols, int step, long stride, float* out, hipStream_t s);
+    // input: device [n][H][W][4] preprocessed floats (lane 3 = 0) instead of u8 crops; otherwise embed_aligned_dev
+    void embed_input_dev(const float* input, int n, float* out, hipStream_t s, float* raw_out = nullptr);
     int max_chunk = 256;                                 // faces per network pass
 
   private:

@@ -96,19 +96,31 @@ __global__ __launch_bounds__(256, 2) void wino_input_kernel(const float* __restr
         v4f as4 = {1.f, 1.f, 1.f, 1.f}, at4 = {0.f, 0.f, 0.f, 0.f};
         if (aff_s) { as4 = *reinterpret_cast<const v4f*>(aff_s + c4 * 4); at4 = *reinterpret_cast<const v4f*>(aff_t + c4 * 4); }
         v4f t[6][6];                                         // t[i][c] = (B^T d)[i][c]: columns of the patch first
+        // All 36 loads UNCONDITIONAL and up front, from clamped coordinates (an out-of-image tap reads the nearest pixel of the SAME
+        // image): a load under a branch is waited for at the branch's join — 36 serialised memory latencies per thread instead of 36
+        // loads in flight.  The scheduling barrier keeps the selects below from being interleaved with the loads (which left ~5 in flight).
+        v4f raw[6][6];
 #pragma unroll
         for (int c = 0; c < 6; ++c) {
             const int ix = ix0 + c;
-            v4f d[6];
 #pragma unroll
             for (int r = 0; r < 6; ++r) {
                 const int iy = iy0 + r;
-                const bool ok = (unsigned)iy < (unsigned)H && (unsigned)ix < (unsigned)W;
-                // UNCONDITIONAL load (out-of-image taps read pixel 0 and are zeroed afterwards): a load under a branch is waited for at
-                // the branch's join — 36 serialised memory latencies per thread instead of 36 loads in flight
-                const v4f raw = *reinterpret_cast<const v4f*>(img + (ok ? ((size_t)iy * W + ix) * C : (size_t)0));
-                const float okf = ok ? 1.f : 0.f;                    // (a select on the RESULT would let the compiler sink the load back under a branch)
-                d[r] = raw * (as4 * okf) + at4 * okf;
+                raw[c][r] = *reinterpret_cast<const v4f*>(img + ((size_t)min(max(iy, 0), H - 1) * W + min(max(ix, 0), W - 1)) * C);
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int c = 0; c < 6; ++c) {
+            const bool okx = (unsigned)(ix0 + c) < (unsigned)W;
+            v4f d[6];
+#pragma unroll
+            for (int r = 0; r < 6; ++r) {
+                const bool ok = okx && (unsigned)(iy0 + r) < (unsigned)H;
+                v4f x;                                               // a select (v_cndmask), not a multiply: the clamped neighbour may be Inf / NaN
+#pragma unroll
+                for (int e = 0; e < 4; ++e) x[e] = ok ? raw[c][r][e] : 0.f;
+                d[r] = x * as4 + (ok ? at4 : v4f{0.f, 0.f, 0.f, 0.f});
             }
             v4f tc[6];
             wino_bt(d, tc);

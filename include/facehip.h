@@ -76,6 +76,9 @@ FH_API int fh_det_detect_batch_dev(fh_det* d, const uint8_t* d_frames, int n, in
  * (device pointer to [n][rows][cols] fp32, valid until the next call on the handle). */
 FH_API int fh_det_run_network_dev(fh_det* d, const uint8_t* d_frames, int n, int rows, int cols, int step,
                                   long long frame_stride, void* stream);
+/* Locality tests: the network on a caller-supplied PREPROCESSED input, d_input_nhwc4 = device [n][H][W][4] fp32 with lane 3 = 0
+ * (copied into the handle's input tensor; what fh_det_run_network_dev computes with the fused stem off, minus the preprocess). */
+FH_API int fh_det_run_input_dev(fh_det* d, const float* d_input_nhwc4, int n, void* stream);
 FH_API int fh_det_num_outputs(const fh_det* d);
 FH_API const float* fh_det_output_dev(fh_det* d, int index, int* rows, int* cols);
 FH_API const float* fh_det_input_dev(fh_det* d);          /* preprocessed input, NHWC with 4 lanes */
@@ -110,6 +113,8 @@ FH_API float fh_compare(const float* f1, int n1, const float* f2, int n2);
 /* n pre-aligned crops [n][H][W][3] BGR u8 in HBM -> d_out [n][dim] L2-normalised; d_raw (may be
  * NULL) receives the un-normalised network output. */
 FH_API int fh_rec_embed_aligned_dev(fh_rec* r, const uint8_t* d_crops, int n, float* d_out, float* d_raw, void* stream);
+/* Locality tests: as above from a caller-supplied preprocessed input, device [n][H][W][4] fp32 with lane 3 = 0. */
+FH_API int fh_rec_run_input_dev(fh_rec* r, const float* d_input_nhwc4, int n, float* d_emb, float* d_raw, void* stream);
 /* Waits for `stream` and reports an error a launch of THIS handle raised after its asynchronous call had already returned (today: a
  * convolution hand-off that timed out, FH_ERR_DEVICE + fh_last_error()).  Such an error is otherwise returned by the next call
  * on the same handle; calls on other handles never see it.  FH_OK when the queued work completed. */

@@ -114,20 +114,7 @@ DWPW_CASES = [
 @pytest.mark.parametrize("H,W,Cc,Cout,ds", DWPW_CASES)
 def test_depthwise_pointwise_block_matches_oracle(tmp_path, H, W, Cc, Cout, ds):
     """The fused depthwise 3x3 -> pointwise 1x1 kernel (dwpw_mfma.hip) on a three-conv graph, vs the oracle."""
-    from facerecognizeonnx_amd.synth.onnx_writer import OnnxBuilder
-    rng = np.random.default_rng(H * 100 + Cc)
-    b = OnnxBuilder("dwpw")
-    x = b.add_input("input", [1, 3, H, W])
-    def conv(x, w, bias, relu=True, **kw):
-        y = b.node("Conv", [x, b.init(b.uid("w"), w.astype(np.float32)), b.init(b.uid("b"), bias.astype(np.float32))], **kw)
-        return b.node("Relu", [y]) if relu else y
-    y = conv(x, rng.standard_normal((Cc, 3, 3, 3)) / 5, rng.standard_normal(Cc) / 10, kernel_shape=[3, 3], pads=[1, 1, 1, 1], strides=[1, 1])
-    y = conv(y, rng.standard_normal((Cc, 1, 3, 3)) / 3, rng.standard_normal(Cc) / 10, kernel_shape=[3, 3], pads=[1, 1, 1, 1], strides=[ds, ds], group=Cc)
-    y = conv(y, rng.standard_normal((Cout, Cc, 1, 1)) / np.sqrt(Cc), rng.standard_normal(Cout) / 10, kernel_shape=[1, 1], strides=[1, 1])
-    y = b.node("Transpose", [y], perm=[0, 2, 3, 1])
-    b.node("Reshape", [y, b.init("shape", np.array([-1, Cout], np.int64))], outputs=["out"])
-    b.add_output("out", ["A", Cout])
-    path = b.save(str(tmp_path / "dwpw.onnx"))
+    path = util.dwpw_graph(str(tmp_path / "dwpw.onnx"), H, W, Cc, Cout, ds)
     assert "DW+PW" in fa.plan_describe(path, H, W) and ("(depthwise s2)" in fa.plan_describe(path, H, W)) == (ds == 2)
     det = fa.FaceDetector(); odet = oracle.OracleDetector()
     assert det.loadModel(path) and odet.loadModel(path)
@@ -1230,25 +1217,7 @@ HALO_CASES = [
 def test_halo_conv_matches_oracle(tmp_path, H, W, Cin, Cout, res):
     """Spatial-tile 3x3 convolution (conv_halo.hip) inside a small graph — stem conv -> [3x3 (-> ReLU) (+ residual)] — vs the oracle,
     and vs the generic implicit-GEMM kernel on the same graph."""
-    from facerecognizeonnx_amd.synth.onnx_writer import OnnxBuilder
-    rng = np.random.default_rng(H * 100 + Cin + Cout)
-    b = OnnxBuilder("halo")
-    x = b.add_input("input", [1, 3, H, W])
-    def conv(x, cout, cin, k, relu):
-        w = (rng.standard_normal((cout, cin, k, k)) / np.sqrt(cin * k * k)).astype(np.float32)
-        y = b.node("Conv", [x, b.init(b.uid("w"), w), b.init(b.uid("b"), (rng.standard_normal(cout) / 10).astype(np.float32))],
-                   kernel_shape=[k, k], pads=[k // 2] * 4, strides=[1, 1])
-        return b.node("Relu", [y]) if relu else y
-    y0 = conv(x, Cin, 3, 3, True)
-    if res:                                                  # the residual must have Cout channels: a 1x1 projection of the stem map
-        side = conv(y0, Cout, Cin, 1, False)
-        y = b.node("Add", [conv(y0, Cout, Cin, 3, False), side])
-    else:
-        y = conv(y0, Cout, Cin, 3, True)
-    y = b.node("Transpose", [y], perm=[0, 2, 3, 1])
-    b.node("Reshape", [y, b.init("shape", np.array([-1, Cout], np.int64))], outputs=["out"])
-    b.add_output("out", ["A", Cout])
-    path = b.save(str(tmp_path / "halo.onnx"))
+    path = util.halo_graph(str(tmp_path / "halo.onnx"), H, W, Cin, Cout, res)
     det = fa.FaceDetector(); odet = oracle.OracleDetector()
     assert det.loadModel(path) and odet.loadModel(path)
     n = 3

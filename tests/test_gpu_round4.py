@@ -249,33 +249,7 @@ def test_wino2_fused_conv_layer_matches_oracle(B, H, W, Cin, Cout, act, with_res
     np.testing.assert_allclose(got, ref.astype(np.float32), rtol=0, atol=5e-5)
 
 
-def _dw_graph(path, H, W, CH, stride, act, seed):
-    """input [1,3,H,W] -> Conv3x3(3 -> CH)+ReLU -> depthwise 3x3 stride `stride` (+act) -> depthwise 3x3 stride 1 (+act) -> [H'W', CH]"""
-    from facerecognizeonnx_amd.synth.onnx_writer import OnnxBuilder
-    rng = np.random.default_rng(seed)
-    b = OnnxBuilder("dw")
-    x = b.add_input("input.1", [1, 3, H, W])
-
-    def conv(x, cin, cout, stride, tag, group=1):
-        w = (rng.standard_normal((cout, cin // group, 3, 3)) * (0.6 / np.sqrt(9 * cin // group))).astype(np.float32)
-        bias = (rng.standard_normal(cout) * 0.1).astype(np.float32)
-        return b.node("Conv", [x, b.init(f"{tag}.w", w), b.init(f"{tag}.b", bias)], kernel_shape=[3, 3], strides=[stride, stride],
-                      pads=[1, 1, 1, 1], dilations=[1, 1], group=group)
-
-    def activation(x, tag):
-        if act == "relu":
-            return b.node("Relu", [x])
-        if act == "prelu":
-            return b.node("PRelu", [x, b.init(f"{tag}.slope", (0.25 * rng.uniform(0.5, 1.5, (CH, 1, 1))).astype(np.float32))])
-        return x
-
-    x = b.node("Relu", [conv(x, 3, CH, 1, "stem")])
-    x = activation(conv(x, CH, CH, stride, "dw1", group=CH), "a1")
-    x = activation(conv(x, CH, CH, 1, "dw2", group=CH), "a2")
-    x = b.node("Transpose", [x], perm=[0, 2, 3, 1])
-    b.node("Reshape", [x, b.init("shape", np.array([-1, CH], np.int64))], outputs=["out"])
-    b.add_output("out", ["A", CH])
-    return b.save(path)
+_dw_graph = util.dw_graph                            # (shared with tests/test_gpu_locality.py)
 
 
 @pytest.mark.parametrize("H,W,CH,stride,act", [

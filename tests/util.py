@@ -124,3 +124,73 @@ def assert_records_equivalent(got, ref, score_thr, nms_thr, box_tol=1, lm_tol=1e
             unexplained.append((side, i, float(r["score"]), [int(r[k]) for k in ("x", "y", "w", "h")]))
     assert len(unexplained) <= max_unexplained, (len(got), len(ref), unexplained[:8])
     return len(missing), len(surplus)
+
+
+def dwpw_graph(path, H, W, Cc, Cout, ds):
+    """input [1,3,H,W] -> Conv3x3(3 -> Cc)+ReLU -> depthwise 3x3 stride `ds` +ReLU -> pointwise 1x1 (Cc -> Cout)+ReLU -> [H'W', Cout]"""
+    from facerecognizeonnx_amd.synth.onnx_writer import OnnxBuilder
+    rng = np.random.default_rng(H * 100 + Cc)
+    b = OnnxBuilder("dwpw")
+    x = b.add_input("input", [1, 3, H, W])
+    def conv(x, w, bias, relu=True, **kw):
+        y = b.node("Conv", [x, b.init(b.uid("w"), w.astype(np.float32)), b.init(b.uid("b"), bias.astype(np.float32))], **kw)
+        return b.node("Relu", [y]) if relu else y
+    y = conv(x, rng.standard_normal((Cc, 3, 3, 3)) / 5, rng.standard_normal(Cc) / 10, kernel_shape=[3, 3], pads=[1, 1, 1, 1], strides=[1, 1])
+    y = conv(y, rng.standard_normal((Cc, 1, 3, 3)) / 3, rng.standard_normal(Cc) / 10, kernel_shape=[3, 3], pads=[1, 1, 1, 1], strides=[ds, ds], group=Cc)
+    y = conv(y, rng.standard_normal((Cout, Cc, 1, 1)) / np.sqrt(Cc), rng.standard_normal(Cout) / 10, kernel_shape=[1, 1], strides=[1, 1])
+    y = b.node("Transpose", [y], perm=[0, 2, 3, 1])
+    b.node("Reshape", [y, b.init("shape", np.array([-1, Cout], np.int64))], outputs=["out"])
+    b.add_output("out", ["A", Cout])
+    return b.save(path)
+
+
+def dw_graph(path, H, W, CH, stride, act, seed):
+    """input [1,3,H,W] -> Conv3x3(3 -> CH)+ReLU -> depthwise 3x3 stride `stride` (+act) -> depthwise 3x3 stride 1 (+act) -> [H'W', CH]"""
+    from facerecognizeonnx_amd.synth.onnx_writer import OnnxBuilder
+    rng = np.random.default_rng(seed)
+    b = OnnxBuilder("dw")
+    x = b.add_input("input.1", [1, 3, H, W])
+
+    def conv(x, cin, cout, stride, tag, group=1):
+        w = (rng.standard_normal((cout, cin // group, 3, 3)) * (0.6 / np.sqrt(9 * cin // group))).astype(np.float32)
+        bias = (rng.standard_normal(cout) * 0.1).astype(np.float32)
+        return b.node("Conv", [x, b.init(f"{tag}.w", w), b.init(f"{tag}.b", bias)], kernel_shape=[3, 3], strides=[stride, stride],
+                      pads=[1, 1, 1, 1], dilations=[1, 1], group=group)
+
+    def activation(x, tag):
+        if act == "relu":
+            return b.node("Relu", [x])
+        if act == "prelu":
+            return b.node("PRelu", [x, b.init(f"{tag}.slope", (0.25 * rng.uniform(0.5, 1.5, (CH, 1, 1))).astype(np.float32))])
+        return x
+
+    x = b.node("Relu", [conv(x, 3, CH, 1, "stem")])
+    x = activation(conv(x, CH, CH, stride, "dw1", group=CH), "a1")
+    x = activation(conv(x, CH, CH, 1, "dw2", group=CH), "a2")
+    x = b.node("Transpose", [x], perm=[0, 2, 3, 1])
+    b.node("Reshape", [x, b.init("shape", np.array([-1, CH], np.int64))], outputs=["out"])
+    b.add_output("out", ["A", CH])
+    return b.save(path)
+
+
+def halo_graph(path, H, W, Cin, Cout, res):
+    """input [1,3,H,W] -> stem Conv3x3(3 -> Cin)+ReLU -> [3x3 (Cin -> Cout) (-> ReLU), or + a 1x1 projection of the stem map] -> [HW, Cout]"""
+    from facerecognizeonnx_amd.synth.onnx_writer import OnnxBuilder
+    rng = np.random.default_rng(H * 100 + Cin + Cout)
+    b = OnnxBuilder("halo")
+    x = b.add_input("input", [1, 3, H, W])
+    def conv(x, cout, cin, k, relu):
+        w = (rng.standard_normal((cout, cin, k, k)) / np.sqrt(cin * k * k)).astype(np.float32)
+        y = b.node("Conv", [x, b.init(b.uid("w"), w), b.init(b.uid("b"), (rng.standard_normal(cout) / 10).astype(np.float32))],
+                   kernel_shape=[k, k], pads=[k // 2] * 4, strides=[1, 1])
+        return b.node("Relu", [y]) if relu else y
+    y0 = conv(x, Cin, 3, 3, True)
+    if res:                                                  # the residual must have Cout channels: a 1x1 projection of the stem map
+        side = conv(y0, Cout, Cin, 1, False)
+        y = b.node("Add", [conv(y0, Cout, Cin, 3, False), side])
+    else:
+        y = conv(y0, Cout, Cin, 3, True)
+    y = b.node("Transpose", [y], perm=[0, 2, 3, 1])
+    b.node("Reshape", [y, b.init("shape", np.array([-1, Cout], np.int64))], outputs=["out"])
+    b.add_output("out", ["A", Cout])
+    return b.save(path)
