@@ -103,6 +103,13 @@ PROTOTYPES = {
     "fh_gallery_get_scan": (_i, [_vp]),
     "fh_gallery_scan_stats": (_i, [_vp, C.POINTER(_ll), C.POINTER(_ll)]),
     "fh_topk_merge_dev": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
+    "fh_gallery_enroll_ids": (_ll, [_vp, _vp, _vp, _ll, _i]),
+    "fh_gallery_upload_ids": (_i, [_vp, _vp, _vp, _ll, _i, _ll]),
+    "fh_gallery_topk_ids_dev": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),
+    "fh_gallery_label_ids_dev": (_i, [_vp, _vp, _i, _f, _vp, _vp, _vp]),
+    "fh_gallery_remove_ids": (_ll, [_vp, _vp, _ll]),
+    "fh_gallery_get_ids": (_ll, [_vp, _ll, _ll, _vp]),
+    "fh_topk_merge_ids_dev": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "fh_comm_unique_id": (_i, [_vp]),
     "fh_comm_create": (_vp, [_i, _i, _vp, _i]),
     "fh_comm_destroy": (None, [_vp]),

@@ -299,17 +299,51 @@ class Gallery:
             _lib._LIB.fh_gallery_destroy(self._h)
         self._h = None
 
-    def upload(self, rows_ptr: int, n: int, on_device: bool, index_base: int = 0):
-        check(_lib.lib().fh_gallery_upload(self._h, rows_ptr, n, int(on_device), index_base), "fh_gallery_upload")
+    def upload(self, rows_ptr: int, n: int, on_device: bool, index_base: int = 0, ids_ptr: Optional[int] = None):
+        """Replace the row set.  ids_ptr (int32[n], host or device as the rows): one identity id >= 0 per row -> a LABELLED gallery
+        (fh_gallery_upload_ids), for topk_ids_dev / label_ids_dev / remove_ids."""
+        if ids_ptr is None:
+            check(_lib.lib().fh_gallery_upload(self._h, rows_ptr, n, int(on_device), index_base), "fh_gallery_upload")
+        else:
+            check(_lib.lib().fh_gallery_upload_ids(self._h, rows_ptr, ids_ptr, n, int(on_device), index_base), "fh_gallery_upload_ids")
 
     def topk_dev(self, q_ptr: int, nq: int, k: int, scores_ptr: int, idx_ptr: int, stream: int = 0):
         check(_lib.lib().fh_gallery_topk_dev(self._h, q_ptr, nq, k, scores_ptr, idx_ptr, stream), "fh_gallery_topk_dev")
 
-    def enroll(self, rows) -> int:
+    def enroll(self, rows, ids=None) -> int:
         """Append L2-normalised feature rows (host array [n, dim]); the webcam loop's 's' key (main.cpp:253-256).
+        ids (int32[n] >= 0, or one int for all rows): the identity each row is a template of (a labelled gallery).
         Returns the index of the first new row."""
         rows = np.ascontiguousarray(rows, np.float32).reshape(-1, self.dim)
-        return check(_lib.lib().fh_gallery_enroll(self._h, rows.ctypes.data, rows.shape[0], 0), "fh_gallery_enroll")
+        if ids is None:
+            return check(_lib.lib().fh_gallery_enroll(self._h, rows.ctypes.data, rows.shape[0], 0), "fh_gallery_enroll")
+        ids = np.ascontiguousarray(np.broadcast_to(np.asarray(ids, np.int32).reshape(-1), (rows.shape[0],)))
+        return check(_lib.lib().fh_gallery_enroll_ids(self._h, rows.ctypes.data, ids.ctypes.data, rows.shape[0], 0), "fh_gallery_enroll_ids")
+
+    def topk_ids_dev(self, q_ptr: int, nq: int, k: int, scores_ptr: int, ids_ptr: int, rows_ptr: Optional[int] = None, stream: int = 0):
+        """The best k IDENTITIES per query, each by its best row: [nq][k] scores / identity ids / (optional) global row indices,
+        empty slots (-1.0, -1, -1).  Scores are the fp32 scan's, bit for bit."""
+        check(_lib.lib().fh_gallery_topk_ids_dev(self._h, q_ptr, nq, k, scores_ptr, ids_ptr, rows_ptr, stream), "fh_gallery_topk_ids_dev")
+
+    def label_ids_dev(self, q_ptr: int, nq: int, threshold: float, ids_ptr: int, scores_ptr: int, stream: int = 0):
+        """ids[q] = the best identity's id if (dot+1)/2 > threshold else -1."""
+        check(_lib.lib().fh_gallery_label_ids_dev(self._h, q_ptr, nq, threshold, ids_ptr, scores_ptr, stream), "fh_gallery_label_ids_dev")
+
+    def remove_ids(self, ids) -> int:
+        """Un-enrol: remove every row of the listed identities (stable compaction; later rows' global indices shrink).
+        Returns the number of rows removed."""
+        ids = np.ascontiguousarray(np.asarray(ids, np.int32).reshape(-1))
+        if ids.size == 0:
+            return 0
+        return check(_lib.lib().fh_gallery_remove_ids(self._h, ids.ctypes.data, ids.size), "fh_gallery_remove_ids")
+
+    def ids(self, first: int = 0, n: Optional[int] = None) -> np.ndarray:
+        """Identity ids of rows [first, first + n) by position (default: to the end)."""
+        if n is None:
+            n = len(self) - first
+        out = np.empty(max(n, 0), np.int32)
+        check(_lib.lib().fh_gallery_get_ids(self._h, first, n, out.ctypes.data if n > 0 else None), "fh_gallery_get_ids")
+        return out
 
     def __len__(self) -> int:
         return int(_lib.lib().fh_gallery_size(self._h))
@@ -359,6 +393,14 @@ class Comm:
         scores / indices = [world * nq_local][k] on every rank."""
         return check(_lib.lib().fh_gallery_topk_sharded_dev(gallery._h, self._h, q_ptr, nq_local, k, scores_ptr, idx_ptr, stream),
                      "fh_gallery_topk_sharded_dev")
+
+
+def topk_merge_ids_dev(part_scores_ptr: int, part_ids_ptr: int, part_rows_ptr: int, nparts: int, nq: int, k: int, scores_ptr: int,
+                       ids_ptr: int, rows_ptr: int, stream: int = 0) -> int:
+    """Merge step of a row-sharded labelled gallery (fh_topk_merge_ids_dev): [nparts][nq][k] identity lists -> the identity top-k of
+    their union."""
+    return check(_lib.lib().fh_topk_merge_ids_dev(part_scores_ptr, part_ids_ptr, part_rows_ptr, nparts, nq, k, scores_ptr, ids_ptr,
+                                                  rows_ptr, stream), "fh_topk_merge_ids_dev")
 
 
 def plan_describe(path: str, default_h: int, default_w: int) -> str:

@@ -660,12 +660,12 @@ fh_gallery* fh_gallery_create(int dim) {
 void fh_gallery_destroy(fh_gallery* g) { delete g; }
 int fh_gallery_upload(fh_gallery* g, const float* rows, long long n, int on_device, long long index_base) {
     if (!g || !rows || n <= 0) return arg_error("fh_gallery_upload: bad argument");
-    return guarded([&] { g->g.upload(rows, (long)n, on_device != 0, (long)index_base); return 0; });
+    return guarded([&] { g->g.upload(rows, nullptr, (long)n, on_device != 0, (long)index_base); return 0; });
 }
 long long fh_gallery_enroll(fh_gallery* g, const float* rows, long long n, int on_device) {
     if (!g || !rows || n <= 0) return arg_error("fh_gallery_enroll: bad argument");
     long long first = -1;
-    const int rc = guarded([&] { first = g->g.enroll(rows, (long)n, on_device != 0); return 0; });
+    const int rc = guarded([&] { first = g->g.enroll(rows, nullptr, (long)n, on_device != 0); return 0; });
     return rc < 0 ? rc : first;
 }
 long long fh_gallery_size(fh_gallery* g) { return g ? (long long)g->g.size() : (long long)arg_error("fh_gallery_size: null handle"); }
@@ -694,6 +694,68 @@ int fh_topk_merge_dev(const float* ps, const int* pi, int nparts, int nq, int k,
     if (nparts <= 0 || nq <= 0 || k <= 0 || k > 16 || (long)nparts * k > 65536) return arg_error("fh_topk_merge_dev: bad size");
     return guarded([&] {
         fh::launch_topk_merge(ps, pi, nparts, nq, k, scores, indices, S(stream));
+        FH_HIP(hipGetLastError());
+        return nq;
+    });
+}
+
+// ---- labelled gallery (gallery_ids.hip).  Ids are checked before anything changes: a host list here, a device list after one copy.
+namespace {
+bool any_negative(const int* ids, long long n) {
+    for (long long i = 0; i < n; ++i)
+        if (ids[i] < 0) return true;
+    return false;
+}
+// 0 = fine, FH_ERR_ARG = a negative id, other < 0 = the copy failed
+int check_ids(const char* who, const int* ids, long long n, int on_device) {
+    if (!on_device) return any_negative(ids, n) ? arg_error(who) : 0;
+    std::vector<int> h((size_t)n);
+    const int rc = guarded([&] { FH_HIP(hipMemcpy(h.data(), ids, (size_t)n * sizeof(int), hipMemcpyDeviceToHost)); return 0; });
+    if (rc < 0) return rc;
+    return any_negative(h.data(), n) ? arg_error(who) : 0;
+}
+}  // namespace
+long long fh_gallery_enroll_ids(fh_gallery* g, const float* rows, const int* ids, long long n, int on_device) {
+    if (!g || !rows || !ids || n <= 0) return arg_error("fh_gallery_enroll_ids: bad argument");
+    if (const int rc = check_ids("fh_gallery_enroll_ids: negative id", ids, n, on_device)) return rc;
+    long long first = -1;
+    const int rc = guarded([&] { first = g->g.enroll(rows, ids, (long)n, on_device != 0); return 0; });
+    return rc < 0 ? rc : first;
+}
+int fh_gallery_upload_ids(fh_gallery* g, const float* rows, const int* ids, long long n, int on_device, long long index_base) {
+    if (!g || !rows || !ids || n <= 0) return arg_error("fh_gallery_upload_ids: bad argument");
+    if (const int rc = check_ids("fh_gallery_upload_ids: negative id", ids, n, on_device)) return rc;
+    return guarded([&] { g->g.upload(rows, ids, (long)n, on_device != 0, (long)index_base); return 0; });
+}
+int fh_gallery_topk_ids_dev(fh_gallery* g, const float* q, int nq, int k, float* scores, int* ids, int* rows, void* stream) {
+    if (!g || !q || !scores || !ids) return arg_error("fh_gallery_topk_ids_dev: null argument");
+    if (nq <= 0 || nq > 256 || k <= 0 || k > 16) return arg_error("fh_gallery_topk_ids_dev: need 0 < nq <= 256 and 0 < k <= 16");
+    return guarded([&] { g->g.topk_ids_dev(q, nq, k, scores, ids, rows, S(stream)); return nq; });
+}
+int fh_gallery_label_ids_dev(fh_gallery* g, const float* q, int nq, float threshold, int* ids, float* scores, void* stream) {
+    if (!g || !q || !ids || !scores) return arg_error("fh_gallery_label_ids_dev: null argument");
+    if (nq <= 0 || nq > 256) return arg_error("fh_gallery_label_ids_dev: need 0 < nq <= 256");
+    return guarded([&] { g->g.label_ids_dev(q, nq, threshold, ids, scores, S(stream)); return nq; });
+}
+long long fh_gallery_remove_ids(fh_gallery* g, const int* ids_host, long long n_ids) {
+    if (!g || !ids_host || n_ids <= 0) return arg_error("fh_gallery_remove_ids: bad argument");
+    if (any_negative(ids_host, n_ids)) return arg_error("fh_gallery_remove_ids: negative id");
+    long long removed = 0;
+    const int rc = guarded([&] { removed = g->g.remove_ids(ids_host, (long)n_ids); return 0; });
+    return rc < 0 ? rc : removed;
+}
+long long fh_gallery_get_ids(fh_gallery* g, long long first, long long n, int* ids_host_out) {
+    if (!g || first < 0 || n < 0 || (n > 0 && !ids_host_out)) return arg_error("fh_gallery_get_ids: bad argument");
+    if (first + n > (long long)g->g.size()) return arg_error("fh_gallery_get_ids: range outside the gallery");
+    const int rc = guarded([&] { g->g.get_ids((long)first, (long)n, ids_host_out); return 0; });
+    return rc < 0 ? rc : n;
+}
+int fh_topk_merge_ids_dev(const float* ps, const int* pd, const int* pr, int nparts, int nq, int k, float* scores, int* ids, int* rows,
+                          void* stream) {
+    if (!ps || !pd || !pr || !scores || !ids || !rows) return arg_error("fh_topk_merge_ids_dev: null argument");
+    if (nparts <= 0 || nq <= 0 || k <= 0 || k > 16 || (long)nparts * k > 65536) return arg_error("fh_topk_merge_ids_dev: bad size");
+    return guarded([&] {
+        fh::launch_topk_merge_ids(ps, pd, pr, nparts, nq, k, scores, ids, rows, S(stream));
         FH_HIP(hipGetLastError());
         return nq;
     });

@@ -732,11 +732,14 @@ void Recognizer::resize_embed_dev(const uint8_t* frames, int n, int rows, int co
 }
 
 // ------------------------------------------------------------------------------------------ Gallery
-void Gallery::upload(const float* rows, long n, bool device_src, long index_base) {
+void Gallery::upload(const float* rows, const int* ids, long n, bool device_src, long index_base) {
     if (dim_ % 64) throw std::runtime_error("gallery: dim must be a multiple of 64");
+    if (!ids && n_ > 0 && labelled_) throw std::runtime_error("gallery: the gallery is labelled: upload rows with their ids (fh_gallery_upload_ids)");
     rows_.ensure((size_t)n * dim_ * sizeof(float));
+    if (ids) ids_.ensure(rows_.bytes / ((size_t)dim_ * sizeof(float)) * sizeof(int));
     FH_HIP(hipMemcpy(rows_.p, rows, (size_t)n * dim_ * sizeof(float), device_src ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
-    n_ = n; base_ = index_base;
+    if (ids) FH_HIP(hipMemcpy(ids_.p, ids, (size_t)n * sizeof(int), device_src ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
+    n_ = n; base_ = index_base; labelled_ = ids != nullptr;
     if (scan_ == 1) {
         rows16_.ensure((size_t)n * dim_ * sizeof(uint16_t));
         convert16(0, n);
@@ -787,8 +790,11 @@ void Gallery::scan_stats(long long* certified, long long* fallback) {
     host_fallback_ = 0;
 }
 
-long Gallery::enroll(const float* rows, long n, bool device_src) {
+long Gallery::enroll(const float* rows, const int* ids, long n, bool device_src) {
     if (dim_ % 64) throw std::runtime_error("gallery: dim must be a multiple of 64");
+    if (n_ > 0 && labelled_ != (ids != nullptr))
+        throw std::runtime_error(labelled_ ? "gallery: the gallery is labelled: enrol rows with their ids (fh_gallery_enroll_ids)"
+                                           : "gallery: the gallery is unlabelled: fh_gallery_enroll_ids needs an empty or labelled gallery");
     const size_t row_bytes = (size_t)dim_ * sizeof(float);
     const size_t need = (size_t)(n_ + n) * row_bytes;
     if (need > rows_.bytes) {                                    // grow geometrically, keeping the enrolled rows
@@ -811,9 +817,109 @@ long Gallery::enroll(const float* rows, long n, bool device_src) {
         }
         convert16(n_, n);
     }
+    if (ids) {                                                   // the ids grow with the rows too
+        const size_t cap = rows_.bytes / row_bytes * sizeof(int);
+        if (cap > ids_.bytes) {
+            DevBuf bigger;
+            bigger.ensure(cap);
+            if (n_ > 0) FH_HIP(hipMemcpy(bigger.p, ids_.p, (size_t)n_ * sizeof(int), hipMemcpyDeviceToDevice));
+            std::swap(bigger.p, ids_.p);
+            std::swap(bigger.bytes, ids_.bytes);
+        }
+        FH_HIP(hipMemcpy(ids_.as<int>() + n_, ids, (size_t)n * sizeof(int), device_src ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
+    }
+    if (n_ == 0) labelled_ = ids != nullptr;
     const long first = base_ + n_;
     n_ += n;
     return first;
+}
+
+void Gallery::need_labelled(const char* what) const {
+    if (n_ > 0 && !labelled_) throw std::runtime_error(std::string("gallery: ") + what + " needs a labelled gallery (rows enrolled with ids)");
+}
+
+void Gallery::get_ids(long first, long n, int* out_host) {
+    need_labelled("fh_gallery_get_ids");
+    if (first < 0 || n < 0 || first + n > n_) throw std::invalid_argument("gallery: id range outside the gallery");
+    if (n > 0) FH_HIP(hipMemcpy(out_host, ids_.as<int>() + first, (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
+}
+
+// Stable compaction through a second buffer: the host reads the ids, lists the surviving positions in order, and whole rows are
+// gathered by that list (gallery_ids.hip).  index_base stays; the certificate's gallery maxima and bad-value flag stay as they are —
+// an upper bound over a superset of the rows is still an upper bound, so F16_RERANK stays exact (a gallery whose only bad row was
+// removed keeps taking the fp32 route until the next upload).
+long Gallery::remove_ids(const int* ids_host, long n_ids) {
+    need_labelled("fh_gallery_remove_ids");
+    if (n_ == 0 || n_ids <= 0) return 0;
+    FH_HIP(hipDeviceSynchronize());                              // queued scans still read the buffers that are about to be replaced
+    std::vector<int> have((size_t)n_), gone(ids_host, ids_host + n_ids), map;
+    FH_HIP(hipMemcpy(have.data(), ids_.p, (size_t)n_ * sizeof(int), hipMemcpyDeviceToHost));
+    std::sort(gone.begin(), gone.end());
+    map.reserve((size_t)n_);
+    for (long r = 0; r < n_; ++r)
+        if (!std::binary_search(gone.begin(), gone.end(), have[(size_t)r])) map.push_back((int)r);
+    const long m = (long)map.size(), removed = n_ - m;
+    if (removed == 0) return 0;
+    if (m == 0) { n_ = 0; return removed; }                      // empty again (capacity kept); the next enrol decides the kind afresh
+    const size_t row_bytes = (size_t)dim_ * sizeof(float), row16 = (size_t)dim_ * sizeof(uint16_t);
+    DevBuf dmap, rows2, ids2, rows16b;
+    dmap.ensure((size_t)m * sizeof(int));
+    FH_HIP(hipMemcpy(dmap.p, map.data(), (size_t)m * sizeof(int), hipMemcpyHostToDevice));
+    rows2.ensure((size_t)m * row_bytes);
+    ids2.ensure((size_t)m * sizeof(int));
+    launch_gather_rows(rows_.p, rows2.p, dmap.as<int>(), m, row_bytes, nullptr);
+    launch_gather_ids(ids_.as<int>(), ids2.as<int>(), dmap.as<int>(), m, nullptr);
+    if (scan_ == 1) {
+        rows16b.ensure((size_t)m * row16);
+        launch_gather_rows(rows16_.p, rows16b.p, dmap.as<int>(), m, row16, nullptr);
+    }
+    FH_HIP(hipGetLastError());
+    FH_HIP(hipDeviceSynchronize());
+    std::swap(rows2.p, rows_.p); std::swap(rows2.bytes, rows_.bytes);
+    std::swap(ids2.p, ids_.p); std::swap(ids2.bytes, ids_.bytes);
+    if (scan_ == 1) { std::swap(rows16b.p, rows16_.p); std::swap(rows16b.bytes, rows16_.bytes); }
+    n_ = m;
+    return removed;
+}
+
+void Gallery::label_ids_dev(const float* q, int Q, float thr, int* out_id, float* out_score, hipStream_t s) {
+    need_labelled("fh_gallery_label_ids_dev");
+    // the best identity is the identity of the best row: the k = 1 row scan of the scan mode, then a gather of its id
+    best_i_.ensure((size_t)std::max(Q, 1) * sizeof(int));
+    topk_dev(q, Q, 1, out_score, best_i_.as<int>(), s);
+    launch_ids_of_rows(out_score, best_i_.as<int>(), Q, ids_.as<int>(), base_, thr, true, out_id, s);
+    FH_HIP(hipGetLastError());
+}
+
+void Gallery::topk_ids_dev(const float* q, int Q, int k, float* out_score, int* out_id, int* out_row, hipStream_t s) {
+    if (Q <= 0 || Q > 256 || k <= 0 || k > 16) throw std::runtime_error("gallery: need 0 < Q <= 256 and 0 < k <= 16");
+    if (dim_ % 64) throw std::runtime_error("gallery: dim must be a multiple of 64");
+    need_labelled("fh_gallery_topk_ids_dev");
+    if (k == 1) {
+        if (!out_row) { best_i_.ensure((size_t)Q * sizeof(int)); out_row = best_i_.as<int>(); }
+        topk_dev(q, Q, 1, out_score, out_row, s);
+        launch_ids_of_rows(out_score, out_row, Q, ids_.as<int>(), base_, 0.f, false, out_id, s);
+        FH_HIP(hipGetLastError());
+        return;
+    }
+    if (scan_ == 1) host_fallback_ += Q;                         // an identity list is always the fp32 scan's
+    const int qrows = (Q + 63) / 64 * 64;
+    qpack_.ensure((size_t)qrows * dim_ * sizeof(float));
+    if (qrows > Q) FH_HIP(hipMemsetAsync(qpack_.as<float>() + (size_t)Q * dim_, 0, (size_t)(qrows - Q) * dim_ * sizeof(float), s));
+    FH_HIP(hipMemcpyAsync(qpack_.p, q, (size_t)Q * dim_ * sizeof(float), hipMemcpyDeviceToDevice, s));
+    int tpp = 0;
+    const int parts = n_ > 0 ? gallery_parts(n_, Q, &tpp) : 0;
+    const size_t plane = (size_t)std::max(parts, 1) * Q * k;
+    ps_.ensure(plane * sizeof(float));
+    pi_.ensure(plane * sizeof(int));
+    pd_.ensure(plane * sizeof(int));
+    seed_s_.ensure((size_t)Q * k * sizeof(float));
+    seed_i_.ensure((size_t)Q * k * sizeof(int));
+    seed_d_.ensure((size_t)Q * k * sizeof(int));
+    launch_gallery_topk_ids(rows_.as<float>(), ids_.as<int>(), n_, dim_, qpack_.as<float>(), Q, k, base_, ps_.as<float>(), pi_.as<int>(),
+                            pd_.as<int>(), seed_s_.as<float>(), seed_i_.as<int>(), seed_d_.as<int>(), s);
+    launch_topk_merge_ids(ps_.as<float>(), pd_.as<int>(), pi_.as<int>(), parts, Q, k, out_score, out_id, out_row, s);
+    FH_HIP(hipGetLastError());
 }
 
 void Gallery::label_dev(const float* q, int Q, float thr, int* out_label, float* out_score, hipStream_t s) {

@@ -174,12 +174,23 @@ class Recognizer {
 class Gallery {
   public:
     explicit Gallery(int dim) : dim_(dim) {}
-    void upload(const float* rows, long n, bool device_src, long index_base);
-    long enroll(const float* rows, long n, bool device_src);     // append; returns the global index of the first new row
+    // ids == nullptr: an unlabelled row set; otherwise one identity id >= 0 per row (host or device, as the rows) and the gallery is
+    // LABELLED.  A gallery is one or the other: the mixed calls throw (FH_ERR_STATE) and change nothing.
+    void upload(const float* rows, const int* ids, long n, bool device_src, long index_base);
+    long enroll(const float* rows, const int* ids, long n, bool device_src);     // append; returns the global index of the first new row
     // best row per query if its mapped score > thr, else -1 (main.cpp:229-233); out_score = that best score
     void label_dev(const float* q, int Q, float thr, int* out_label, float* out_score, hipStream_t s);
     // queries [Q][dim] device, Q <= 256, k <= 16 -> out_score/out_idx [Q][k] device
     void topk_dev(const float* q, int Q, int k, float* out_score, int* out_idx, hipStream_t s);
+    // labelled gallery: the best k IDENTITIES per query, each by its best row -> out_score / out_id / out_row (may be null) [Q][k];
+    // k > 1 always takes the fp32 scan (32 row candidates cannot certify an identity list), k == 1 is the row top-1 of the scan mode
+    void topk_ids_dev(const float* q, int Q, int k, float* out_score, int* out_id, int* out_row, hipStream_t s);
+    void label_ids_dev(const float* q, int Q, float thr, int* out_id, float* out_score, hipStream_t s);
+    // removes every row whose id is listed (stable compaction through a second buffer: transiently the surviving fp32 rows, ids and
+    // fp16 rows exist twice, plus 4 bytes per survivor); synchronous; returns the number of rows removed
+    long remove_ids(const int* ids_host, long n_ids);
+    void get_ids(long first, long n, int* out_host);
+    bool labelled() const { return labelled_; }
     long size() const { return n_; }
     int dim() const { return dim_; }
     // fh_gallery_set_scan: 1 = F16_RERANK (an fp16 copy of the rows beside the fp32 rows, G x dim x 2 bytes; same answer bit for bit),
@@ -192,9 +203,12 @@ class Gallery {
     void convert16(long first, long n);                          // rows [first, first + n) -> rows16_, bounds + flag (synchronous)
     void topk_f16(const float* q, int Q, int k, float* out_score, int* out_idx, hipStream_t s);
     void topk_f32(const float* q, int Q, int k, float* out_score, int* out_idx, hipStream_t s, const int* qcount);
+    void need_labelled(const char* what) const;                  // throws on a non-empty unlabelled gallery
     int dim_;
     long n_ = 0, base_ = 0;
+    bool labelled_ = false;                                      // meaningful while n_ > 0; an empty gallery takes either kind
     DevBuf rows_, qpack_, ps_, pi_, best_i_, seed_s_, seed_i_;
+    DevBuf ids_, pd_, seed_d_;                                   // identity id per row (capacity in rows = rows_'), id planes of the part / seed lists
     // F16_RERANK state: the fp16 rows, [max|g|, max|g^|, max|g - g^| (float bits), non-finite / > 65504 flag] on the device and its host
     // copy, per-call scratch, the certified / fallback counters
     int scan_ = 0;

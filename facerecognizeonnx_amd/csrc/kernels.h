@@ -287,6 +287,21 @@ void launch_topk_merge(const float* part_score, const int* part_idx, int nparts,
 void launch_topk_merge_strided(const float* part_score, const int* part_idx, int nparts, int Q, int k, long part_stride, float* out_score,
                                int* out_idx, hipStream_t s, const int* qcount = nullptr);
 
+// gallery_ids.hip — the labelled gallery: every row carries an identity id >= 0, a query is answered with its best k IDENTITIES, each
+// represented by its best row (score desc, global row index asc).  Same streaming scan (gallery_scan.h), lists of (score, row, id) with
+// at most one entry per identity; part_* / seed_*: [gallery_parts][Q][k] / [Q][k] scratch as launch_gallery_topk, with an id plane.
+void launch_gallery_topk_ids(const float* gal, const int* ids, long G, int dim, const float* qpacked, int Q, int k, long idx_base,
+                             float* part_score, int* part_idx, int* part_id, float* seed_score, int* seed_idx, int* seed_id, hipStream_t s);
+// [nparts][Q][k] identity lists (each list: distinct ids, -1 rows = empty) -> the identity top-k of their union; out_idx may be null
+void launch_topk_merge_ids(const float* part_score, const int* part_id, const int* part_idx, int nparts, int Q, int k, float* out_score,
+                           int* out_id, int* out_idx, hipStream_t s, const int* qcount = nullptr);
+// out_id[i] = ids[idx[i] - idx_base] for idx[i] >= 0 (and, with use_thr, score[i] > thr), else -1
+void launch_ids_of_rows(const float* score, const int* idx, int n, const int* ids, long idx_base, float thr, bool use_thr, int* out_id,
+                        hipStream_t s);
+// stable compaction: dst row j = src row map[j] (rows of row_bytes, a multiple of 16; 16-byte aligned buffers), j < m
+void launch_gather_rows(const void* src, void* dst, const int* map, long m, size_t row_bytes, hipStream_t s);
+void launch_gather_ids(const int* src, int* dst, const int* map, long m, hipStream_t s);
+
 // gallery_f16.hip — the opt-in F16_RERANK scan (fh_gallery_set_scan): an fp16 copy of the rows is scanned for the top GAL16_KC candidates
 // per query, the candidates are re-scored from the fp32 rows exactly as gallery_topk_kernel scores them, and a per-query certificate
 // proves that no other row can reach the top-k; uncertified queries are compacted on the device (fb_count / fb_idx) for the fp32 scan.

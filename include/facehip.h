@@ -227,6 +227,45 @@ FH_API long long fh_gallery_size(fh_gallery* g);
 FH_API int fh_gallery_label_dev(fh_gallery* g, const float* d_queries, int nq, float threshold, int* d_labels,
                                 float* d_scores, void* stream);
 
+/* ---- labelled gallery: every row carries an identity id (int32 >= 0, chosen by the caller: arbitrary, neither dense nor sorted),
+ * real enrolments hold several templates per person, and the identity queries answer with k different PEOPLE where
+ * fh_gallery_topk_dev answers with k rows.
+ *   kind      a gallery is labelled or unlabelled: the first *_ids enrol or upload into an empty gallery makes it labelled.  A mix
+ *             is an error, not a guess: fh_gallery_enroll / fh_gallery_upload on a non-empty labelled gallery, fh_gallery_enroll_ids
+ *             on a non-empty unlabelled one, and the identity queries, fh_gallery_get_ids and fh_gallery_remove_ids on a non-empty
+ *             unlabelled one return FH_ERR_STATE and change nothing.  fh_gallery_upload_ids replaces everything and makes the gallery
+ *             labelled; an emptied gallery takes either kind.  A negative id returns FH_ERR_ARG and nothing changes.  rows and ids
+ *             are both host or both device pointers.
+ *   scores    exactly fh_gallery_topk_dev's fp32 score of the row; entry (s, r) is better than (s', r') iff s > s', or s == s' and
+ *             r < r' (r = global row index); NaN scores are never listed.
+ *   topk_ids  an identity is represented by its best row; the answer is the first k representatives: d_scores / d_ids / d_rows
+ *             (may be NULL) = [nq][k] (score, identity id, representative's global row index), empty slots (-1.0f, -1, -1).
+ *             Limits as fh_gallery_topk_dev (1 <= k <= 16, nq <= 256, dim % 64 == 0); asynchronous on `stream`, capturable into
+ *             a graph after one call of the same (nq, k).  With k > 1 it ALWAYS runs the fp32 scan, whatever the scan mode (the 32
+ *             row candidates of F16_RERANK cannot certify an identity list); fh_gallery_scan_stats counts those queries as
+ *             fall-backs.  k == 1 and label_ids are the row top-1 of the scan mode plus its id.
+ *   label_ids d_ids[q] = the best identity's id when the best score is strictly above the threshold, else -1; d_scores as
+ *             fh_gallery_label_dev.
+ *   remove    fh_gallery_remove_ids removes every row whose id is in the host list and returns the number of rows removed (unknown
+ *             ids: 0; duplicates in the list are harmless).  Synchronous, like enroll.  The compaction is stable: surviving rows
+ *             keep their order and move down, so the global indices of later rows shrink; index_base stays.  It goes through a
+ *             second buffer: transiently the surviving rows (fp32, ids, the fp16 copy of F16_RERANK) are held twice, plus 4 bytes
+ *             per surviving row.  After removing everything the gallery is empty: queries answer -1, enrolment starts afresh.
+ *   get_ids   the ids of rows [first, first + n) by position (persistence, tests); returns n.
+ *   merge_ids the merge step of a row-SHARDED labelled gallery: part w = the identity top-k of shard w, [nparts][nq][k] in three
+ *             planes as topk_ids writes them -> the identity top-k of the union (per-part lists suffice: an identity of the answer
+ *             is listed, with its representative, by the part that holds it).  nparts * k <= 65536. */
+FH_API long long fh_gallery_enroll_ids(fh_gallery* g, const float* rows, const int* ids, long long n, int on_device);
+FH_API int fh_gallery_upload_ids(fh_gallery* g, const float* rows, const int* ids, long long n, int on_device, long long index_base);
+FH_API int fh_gallery_topk_ids_dev(fh_gallery* g, const float* d_queries, int nq, int k, float* d_scores, int* d_ids, int* d_rows,
+                                   void* stream);
+FH_API int fh_gallery_label_ids_dev(fh_gallery* g, const float* d_queries, int nq, float threshold, int* d_ids_out, float* d_scores,
+                                    void* stream);
+FH_API long long fh_gallery_remove_ids(fh_gallery* g, const int* ids_host, long long n_ids);
+FH_API long long fh_gallery_get_ids(fh_gallery* g, long long first, long long n, int* ids_host_out);
+FH_API int fh_topk_merge_ids_dev(const float* d_part_scores, const int* d_part_ids, const int* d_part_rows, int nparts, int nq, int k,
+                                 float* d_scores, int* d_ids, int* d_rows, void* stream);
+
 /* ---- measurement hooks (bench.py): per-launch HIP-event timing of the network kernels.
  * Tags 0..3 = conv_igemm tile configs (128x128, 256x64, 128x32, 64x64), 4 = depthwise / depthwise+pointwise,
  * 5 = other graph ops, 6 = conv stream-K fix-up, 7 = Winograd GEMM (its FLOPs = executed; bytes slot = the layer's
