@@ -903,19 +903,8 @@ void Gallery::topk_ids_dev(const float* q, int Q, int k, float* out_score, int* 
         return;
     }
     if (scan_ == 1) host_fallback_ += Q;                         // an identity list is always the fp32 scan's
-    const int qrows = (Q + 63) / 64 * 64;
-    qpack_.ensure((size_t)qrows * dim_ * sizeof(float));
-    if (qrows > Q) FH_HIP(hipMemsetAsync(qpack_.as<float>() + (size_t)Q * dim_, 0, (size_t)(qrows - Q) * dim_ * sizeof(float), s));
-    FH_HIP(hipMemcpyAsync(qpack_.p, q, (size_t)Q * dim_ * sizeof(float), hipMemcpyDeviceToDevice, s));
-    int tpp = 0;
-    const int parts = n_ > 0 ? gallery_parts(n_, Q, &tpp) : 0;
-    const size_t plane = (size_t)std::max(parts, 1) * Q * k;
-    ps_.ensure(plane * sizeof(float));
-    pi_.ensure(plane * sizeof(int));
-    pd_.ensure(plane * sizeof(int));
-    seed_s_.ensure((size_t)Q * k * sizeof(float));
-    seed_i_.ensure((size_t)Q * k * sizeof(int));
-    seed_d_.ensure((size_t)Q * k * sizeof(int));
+    pack_queries(q, Q, s);
+    const int parts = size_lists(Q, k, true);
     launch_gallery_topk_ids(rows_.as<float>(), ids_.as<int>(), n_, dim_, qpack_.as<float>(), Q, k, base_, ps_.as<float>(), pi_.as<int>(),
                             pd_.as<int>(), seed_s_.as<float>(), seed_i_.as<int>(), seed_d_.as<int>(), s);
     launch_topk_merge_ids(ps_.as<float>(), pd_.as<int>(), pi_.as<int>(), parts, Q, k, out_score, out_id, out_row, s);
@@ -971,22 +960,31 @@ void Gallery::topk_f16(const float* q, int Q, int k, float* out_score, int* out_
     FH_HIP(hipGetLastError());
 }
 
-// q == nullptr: qpack_ is already filled (the F16_RERANK fall-back); qcount (device, optional): only that many queries are live
-void Gallery::topk_f32(const float* q, int Q, int k, float* out_score, int* out_idx, hipStream_t s, const int* qcount) {
-    // queries as the GEMM's N operand: whole 64-row tiles, zero rows behind Q (only that tail is cleared)
+// queries as the GEMM's N operand: whole 64-row tiles, zero rows behind Q (only that tail is cleared)
+void Gallery::pack_queries(const float* q, int Q, hipStream_t s) {
     const int qrows = (Q + 63) / 64 * 64;
     qpack_.ensure((size_t)qrows * dim_ * sizeof(float));
-    if (q) {
-        if (qrows > Q) FH_HIP(hipMemsetAsync(qpack_.as<float>() + (size_t)Q * dim_, 0, (size_t)(qrows - Q) * dim_ * sizeof(float), s));
-        FH_HIP(hipMemcpyAsync(qpack_.p, q, (size_t)Q * dim_ * sizeof(float), hipMemcpyDeviceToDevice, s));
-    }
-    int tpp = 0;
-    const int parts = n_ > 0 ? gallery_parts(n_, Q, &tpp) : 0;
-    ps_.ensure((size_t)std::max(parts, 1) * Q * k * sizeof(float));
-    pi_.ensure((size_t)std::max(parts, 1) * Q * k * sizeof(int));
+    if (qrows > Q) FH_HIP(hipMemsetAsync(qpack_.as<float>() + (size_t)Q * dim_, 0, (size_t)(qrows - Q) * dim_ * sizeof(float), s));
+    FH_HIP(hipMemcpyAsync(qpack_.p, q, (size_t)Q * dim_ * sizeof(float), hipMemcpyDeviceToDevice, s));
+}
+
+// part planes [gallery_parts][Q][k] and seed planes [Q][k] of the fp32 scans (ids: with their identity planes); returns the parts
+int Gallery::size_lists(int Q, int k, bool ids) {
+    const int parts = n_ > 0 ? gallery_parts(n_, Q, nullptr) : 0;
+    const size_t plane = (size_t)std::max(parts, 1) * Q * k, seed = (size_t)Q * k;
+    ps_.ensure(plane * sizeof(float));
+    pi_.ensure(plane * sizeof(int));
+    seed_s_.ensure(seed * sizeof(float));
+    seed_i_.ensure(seed * sizeof(int));
+    if (ids) { pd_.ensure(plane * sizeof(int)); seed_d_.ensure(seed * sizeof(int)); }
+    return parts;
+}
+
+// q == nullptr: qpack_ is already filled (the F16_RERANK fall-back); qcount (device, optional): only that many queries are live
+void Gallery::topk_f32(const float* q, int Q, int k, float* out_score, int* out_idx, hipStream_t s, const int* qcount) {
+    if (q) pack_queries(q, Q, s);
+    const int parts = size_lists(Q, k, false);
     // ONE pass over the gallery: dot products stay in the MFMA accumulators, per-workgroup top-k lists come out (gallery.hip)
-    seed_s_.ensure((size_t)Q * k * sizeof(float));
-    seed_i_.ensure((size_t)Q * k * sizeof(int));
     launch_gallery_topk(rows_.as<float>(), n_, dim_, qpack_.as<float>(), Q, k, base_, ps_.as<float>(), pi_.as<int>(),
                         qcount ? nullptr : seed_s_.as<float>(), qcount ? nullptr : seed_i_.as<int>(), s, qcount);
     launch_topk_merge(ps_.as<float>(), pi_.as<int>(), parts, Q, k, out_score, out_idx, s, qcount);

@@ -203,6 +203,8 @@ class Gallery {
     void convert16(long first, long n);                          // rows [first, first + n) -> rows16_, bounds + flag (synchronous)
     void topk_f16(const float* q, int Q, int k, float* out_score, int* out_idx, hipStream_t s);
     void topk_f32(const float* q, int Q, int k, float* out_score, int* out_idx, hipStream_t s, const int* qcount);
+    void pack_queries(const float* q, int Q, hipStream_t s);     // q -> qpack_: whole 64-row tiles with a zero tail
+    int size_lists(int Q, int k, bool ids);                      // sizes the part and seed planes of an fp32 scan; returns the parts
     void need_labelled(const char* what) const;                  // throws on a non-empty unlabelled gallery
     int dim_;
     long n_ = 0, base_ = 0;

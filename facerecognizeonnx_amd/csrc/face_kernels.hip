@@ -461,92 +461,6 @@ void launch_l2_normalize(const float* in, float* out, int n, int dim, hipStream_
     hipLaunchKernelGGL(l2norm_kernel, dim3((n + 3) / 4), dim3(256), 0, s, in, out, n, dim);
 }
 
-// ------------------------------------------------------------------------------------------
-// FaceRecognizer::compareFaces generalised to a gallery (src/face_recognizer.cpp:320-334):
-// mapped score (dot + 1) / 2, ranked (score desc, gallery index asc).  The scan itself is
-// gallery.hip (one pass, per-workgroup top-k lists); here: the merge of those lists — also the
-// merge step of a row-sharded gallery (fh_topk_merge_dev).
-// ------------------------------------------------------------------------------------------
-__device__ __forceinline__ bool better(float s1, int i1, float s2, int i2) { return s1 > s2 || (s1 == s2 && i1 < i2); }
-
-// one workgroup per query: k rounds of "best entry that comes after the previous pick".
-// CACHED: the nparts * k <= 8192 candidate entries are read ONCE into registers (32 per thread) and every round is a register scan +
-// a wave reduction + one LDS hand-off between the four waves; otherwise each round re-reads the lists from memory (L2).
-template <bool CACHED>
-__global__ __launch_bounds__(256) void topk_merge_kernel(const float* __restrict__ ps, const int* __restrict__ pi, int nparts, int Q, int k,
-                                                         long part_stride, float* __restrict__ out_s, int* __restrict__ out_i,
-                                                         const int* __restrict__ qcount) {
-    __shared__ float rs[256];
-    __shared__ int ri[256];
-    const int q = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    if (qcount && q >= *qcount) return;                  // (optional device query count: the compacted fall-back of the f16 re-rank scan)
-    const int total = nparts * k;
-    constexpr int E = 32;
-    float es[E]; int ei[E];
-    if (CACHED) {
-#pragma unroll
-        for (int j = 0; j < E; ++j) {
-            const int e = j * 256 + tid;
-            es[j] = -INFINITY; ei[j] = -1;
-            if (e < total) {
-                const int part = e / k, pos = e - part * k;
-                const size_t o = (size_t)part * part_stride + (size_t)q * k + pos;
-                es[j] = ps[o]; ei[j] = pi[o];
-            }
-        }
-    }
-    float last_s = 0.f; int last_i = -1; bool have_last = false, exhausted = false;
-    for (int round = 0; round < k; ++round) {
-        float best_s = -INFINITY; int best_i = 0x7fffffff;                   // (emptiness is told by the index, not by the score: rows need not be unit vectors)
-        if (CACHED) {
-#pragma unroll
-            for (int j = 0; j < E; ++j) {
-                const float sc = es[j]; const int gi = ei[j];
-                const bool ok = !exhausted && gi >= 0 && (!have_last || better(last_s, last_i, sc, gi)) && better(sc, gi, best_s, best_i);
-                best_s = ok ? sc : best_s; best_i = ok ? gi : best_i;
-            }
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) {               // wave reduction
-                const float os = __shfl_xor(best_s, o); const int oi = __shfl_xor(best_i, o);
-                const bool t = better(os, oi, best_s, best_i);
-                best_s = t ? os : best_s; best_i = t ? oi : best_i;
-            }
-            if (lane == 0) { rs[wv] = best_s; ri[wv] = best_i; }
-            __syncthreads();
-            best_s = rs[0]; best_i = ri[0];
-#pragma unroll
-            for (int w = 1; w < 4; ++w)
-                if (better(rs[w], ri[w], best_s, best_i)) { best_s = rs[w]; best_i = ri[w]; }
-            __syncthreads();
-            last_s = best_s; last_i = best_i;
-        } else {
-            for (int e = tid; e < total; e += 256) {
-                const int part = e / k, pos = e - part * k;
-                const size_t o = (size_t)part * part_stride + (size_t)q * k + pos;
-                const float sc = ps[o]; const int gi = pi[o];
-                if (gi < 0 || exhausted) continue;
-                if (have_last && !better(last_s, last_i, sc, gi)) continue;     // must come strictly after the last pick
-                if (better(sc, gi, best_s, best_i)) { best_s = sc; best_i = gi; }
-            }
-            rs[tid] = best_s; ri[tid] = best_i;
-            __syncthreads();
-            for (int st = 128; st > 0; st >>= 1) {
-                if (tid < st && better(rs[tid + st], ri[tid + st], rs[tid], ri[tid])) { rs[tid] = rs[tid + st]; ri[tid] = ri[tid + st]; }
-                __syncthreads();
-            }
-            last_s = rs[0]; last_i = ri[0];
-            __syncthreads();
-        }
-        have_last = true;
-        if (tid == 0) {
-            const bool found = last_i != 0x7fffffff;
-            out_s[(size_t)q * k + round] = found ? last_s : -1.0f;
-            out_i[(size_t)q * k + round] = found ? last_i : -1;
-        }
-        if (last_i == 0x7fffffff) exhausted = true;      // nothing left: later rounds find nothing either (workgroup-uniform)
-    }
-}
-
 // Match / Unknown decision of the reference's webcam loop (src/main.cpp:229-233): a query is labelled with its best
 // gallery row when the mapped score (dot+1)/2 is STRICTLY above the threshold, else -1.
 __global__ void label_kernel(const float* __restrict__ best_s, const int* __restrict__ best_i, int n, float thr, int* __restrict__ labels) {
@@ -555,18 +469,6 @@ __global__ void label_kernel(const float* __restrict__ best_s, const int* __rest
 }
 void launch_label(const float* best_score, const int* best_idx, int n, float thr, int* labels, hipStream_t s) {
     if (n > 0) hipLaunchKernelGGL(label_kernel, dim3((n + 255) / 256), dim3(256), 0, s, best_score, best_idx, n, thr, labels);
-}
-
-// part_stride = words between the lists of consecutive parts (Q * k when they are packed; the sharded exchange of comm.cpp interleaves
-// score and index planes per rank)
-void launch_topk_merge_strided(const float* part_score, const int* part_idx, int nparts, int Q, int k, long part_stride, float* out_score,
-                               int* out_idx, hipStream_t s, const int* qcount) {
-    if ((long)nparts * k <= 8192) hipLaunchKernelGGL(topk_merge_kernel<true>, dim3(Q), dim3(256), 0, s, part_score, part_idx, nparts, Q, k, part_stride, out_score, out_idx, qcount);
-    else hipLaunchKernelGGL(topk_merge_kernel<false>, dim3(Q), dim3(256), 0, s, part_score, part_idx, nparts, Q, k, part_stride, out_score, out_idx, qcount);
-}
-void launch_topk_merge(const float* part_score, const int* part_idx, int nparts, int Q, int k, float* out_score, int* out_idx,
-                       hipStream_t s, const int* qcount) {
-    launch_topk_merge_strided(part_score, part_idx, nparts, Q, k, (long)Q * k, out_score, out_idx, s, qcount);
 }
 
 // ------------------------------------------------------------------------------------------

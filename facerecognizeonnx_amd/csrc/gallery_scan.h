@@ -1,33 +1,101 @@
-// gallery_scan.h — the streaming 1:N scan shared by gallery_topk_kernel (gallery.hip: lists of rows) and gallery_topk_ids_kernel
-// (gallery_ids.hip: lists of identities).  The design notes and measurements are in gallery.hip's header; IDS = false compiles to
-// exactly the row-level kernel (every identity statement sits behind `if constexpr (IDS)`), and both instantiations run the same K
-// loop with the same operand placement and k order, so a score has the same bits in either.
+// gallery_scan.h — the streaming 1:N scan of the gallery: ONE body, instantiated as gallery_topk_kernel (gallery.hip: fp32 rows, lists of
+// rows), gallery_topk_ids_kernel (gallery_ids.hip: fp32 rows, lists of identities) and gal16_scan_kernel (gallery_f16.hip: fp16 rows,
+// 32-deep candidate lists); with it the ranking predicate, the kernel arguments and the two-pass launcher all three share.
+//
+// One kernel streams the gallery ONCE: the dot products live only in MFMA accumulators, never in memory.
+//   * The scan is an HBM stream with NO reuse on the gallery side: what limits it is bytes in flight (Little: ~50 KB per CU for 5 TB/s at
+//     ~2.5 us loaded latency).  Each wave fetches ITS OWN 32 gallery rows straight into registers — the fragment layout is the one a
+//     ds_read_b128 would deliver: lane (row fr, half fh2) takes 16 bytes at k = (2s + fh2) * 4 of its row; the s-steps of a 128-byte line
+//     are consecutive instructions — in 64-deep chunks, one chunk (8 loads, 32 VGPRs) ahead of the one being multiplied: 8 waves x 8 KB in
+//     flight per CU, no LDS traffic and no barrier on the gallery side.  Only the 64 queries of the tile (shared by the four waves) go
+//     through LDS: 16 KB per chunk, through registers (see the K loop), double buffered, 16-byte column XOR-swizzled by (row & 15) on the
+//     source side.
+//   * v_mfma_f32_32x32x2_f32 with the GALLERY fragment as A and the QUERY fragment as B: a lane ends up with ONE query (column) and 16
+//     gallery rows of it per 32x32 block.  Workgroup tile: 128 gallery rows x 64 queries.
+//   * top-k: every workgroup owns a contiguous run of row tiles.  Thread q < 64 keeps query q's sorted k-list in REGISTERS (a compare-
+//     exchange pass per insertion, no LDS latency chain) and publishes its k-th entry — the admission threshold — in LDS.  After a tile's
+//     K loop each lane compares its 32 scores with the threshold of its query; the few that pass are appended to that query's slot queue
+//     (LDS atomic counter) and thread q inserts them.  A queue holds 32 entries: if a tile overflows one (only the first tiles of a run
+//     can, while the lists are still filling), the tile's scores — still in registers — are replayed in four 32-row rounds, which cannot.
+//   * per-workgroup lists go to memory as [part][Q][k]; topk_merge_kernel (gallery.hip) selects the overall top-k.
+// Bounds: HBM scan (G x dim x 4 bytes once) against 2*Q*G*dim FLOP on the f32 matrix cores — at Q = 64 the two meet.
+//
+// The instantiations differ only behind `if constexpr`:
+//   * IDS = false compiles to exactly the row-level kernel, and both fp32 instantiations run the same K loop with the same operand
+//     placement and k order, so a score has the same bits in either.
+//   * T = _Float16 (gal16_scan_kernel): 8 elements per 16-byte column, so a chunk is 128 deep and 256 bytes per row — the loads, the
+//     column swizzle and the LDS image of a chunk are those of the 64-deep f32 chunk — multiplied by v_mfma_f32_32x32x16_f16 with f32
+//     accumulation: 8 MFMAs per 32x32 block and chunk where the f32 kernels issue 32.  Its lists are KD = 32 deep and k IS the list
+//     depth (KFIX), so the threshold entry is ls[31] instead of a select by k - 1.  It is launched at one workgroup per CU (the 32-deep
+//     lists + two row chunks in flight need more than the 256 registers of two waves per SIMD: 104 bytes of spills at (256, 2)).
+//
+// Round 3, measured and NOT kept (1 M x 512, Q = 64, k = 16; this kernel: 0.82 ms per call = seed pass 88 us + scan ~700 + two merges
+// 39 us each): a scan with the whole 64-query tile RESIDENT in LDS (128 KB, one 8-wave workgroup per CU, no per-chunk barrier, query
+// fragments read a step ahead), tried with three top-k schemes:
+//   * this kernel's queues + two barriers per 256-row tile + its own seed launch: 0.86 ms (the seed launch alone 196 us: sixteen
+//     workgroups each loading 128 KB of queries for one tile; a barrier stalls the whole CU on its slowest wave);
+//   * wave-private lists in registers (lane l = query l, one lane^32 exchange per accumulator position, one compare-exchange pass per
+//     candidate), thresholds shared through LDS, no barrier and no seed: 0.91 ms — the K loop + loads alone 0.67 ms, but the
+//     insertions cost 0.3 ms: the k-th score of ONE wave's rows (or the maximum of several waves' k-ths) is a far weaker threshold
+//     than the k-th of their union, so ~20 of the 32 insertion passes of a tile still fire half-way through the scan;
+//   * the same with chip-wide thresholds through atomicMax on 64 words: 1.18 ms (contended atomics, and the maximum of per-workgroup
+//     k-ths is still not a chip-wide k-th).
+// Where a call's 0.82 ms go (rocprofv3, 1 M x 512, Q = 64, k = 16): seed scan 89 us (32 workgroups, one tile each: a latency chain plus the
+// first-tile insertions) + seed merge 26 + main scan 658 (67.1 GFLOP = 102 TFLOP/s: at Q = 64 the f32 matrix cores bind, not HBM —
+// 0.43 ms at the nominal peak, ~0.58 at the 115 TFLOP/s plateau) + final merge 50.  Without the seed pass (FACEHIP_GAL_SEED=0) the call
+// takes 0.844 ms: the per-workgroup list warm-up costs more than the 115 us the seed does.  A pruned final merge (threshold = best over
+// the parts of a full part's worst entry, survivors compacted to LDS, one entry per thread in the rounds) ran 35 us SLOWER with
+// part-per-thread loads (64 lines per load instruction) and was not kept.
+// Side results worth keeping: a wave streaming its own 32 rows into registers reaches 6.2 TB/s whatever the lane-to-row mapping
+// (scripts/ubench/row_stream.hip: 32, 16, 8 rows per instruction or fully coalesced, all 6.2-6.5 TB/s), so the scan is not bound by
+// its access pattern; with loads and top-k switched off the MFMA + fragment-read loop alone runs at ~75 % of the f32 peak.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <climits>
+#include <type_traits>
 
 namespace fh {
 
 typedef float v4f __attribute__((ext_vector_type(4)));
 typedef float v16f __attribute__((ext_vector_type(16)));
+typedef _Float16 v8h __attribute__((ext_vector_type(8)));
 
 constexpr int GAL_BM = 128, GAL_BN = 64, GAL_KMAX = 16, GAL_QCAP = 32;
 
 struct GalArgs {
-    const float* gal;       // [G][dim]
-    const float* q;         // [tiles_n * 64][dim], rows >= Q are zero
-    const float* zeros;
+    const void* gal;        // [G][dim], elements of the instantiation's type T
+    const void* q;          // [tiles_n * 64][dim], rows >= Q are zero
+    const void* zeros;
     long G, idx_base;
     int dim, Q, k, tiles_n, row_tiles, tiles_per_part;
     float* ps;              // [parts][Q][k]
     int* pi;
     const float* seed_s;    // optional [Q][k]: exact top-k of a PREFIX of the gallery — its k-th entry is a valid admission threshold for
     const int* seed_i;      // the whole scan (k rows at least as good exist), so the per-workgroup lists start almost closed
-    const int* qcount;      // optional (device): query tiles at or beyond *qcount exit at once (null: all Q)
+    const int* qcount;      // optional (device), fp32 scans: query tiles at or beyond *qcount exit at once (null: all Q)
     const int* ids;         // IDS: identity id of every row [G]
     int* pd;                // IDS: [parts][Q][k] identity ids beside ps / pi
 };
+
+// ---- host side (gallery.hip); they sit here and not in kernels.h because they speak of GalArgs
+struct GalScan {            // what the host needs to know about an instantiation of the scan
+    const char* name;       // for error messages
+    void (*kernel)(const GalArgs);
+    int chunk;              // K-chunk depth: dim must be a multiple
+    int depth;              // list depth: 1 <= k <= depth
+    int wg_per_cu;          // resident workgroups per CU (__launch_bounds__) = parts per CU
+    long max_parts;         // cap on the parts per query tile
+    bool has_qcount;        // the kernel honours GalArgs::qcount
+};
+constexpr int GAL_WG_PER_CU = 2;             // fp32 scans (3 measured: no faster, and 768 lists per query leave the merge its slow path)
+int gallery_parts_for(long G, int Q, int wg_per_cu, long max_parts, int* tiles_per_part);
+void gallery_check_args(const GalScan& sc, const GalArgs& a, long G);     // throws: dim, k, 31-bit indices, qcount
+// The two passes every scan of a large gallery makes: the exact top-k of the first 4096 rows (same kernel + merge into seed_*) gives every
+// query an admission threshold, then the full scan runs with it — without the seed every workgroup spends its first tiles sorting rows
+// that cannot matter.  `a` carries gal / q / ids, idx_base, dim, Q, k, the part planes and qcount; seed_* = [Q][k] scratch.  The row range
+// is cut into gallery_parts_for(G, Q, wg_per_cu, max_parts) parts; returns that number (the caller merges the part lists).
+int launch_gallery_two_pass(const GalScan& sc, GalArgs a, long G, bool seed, float* seed_s, int* seed_i, int* seed_d, hipStream_t s);
 
 __device__ __forceinline__ bool gal_better(float s1, int i1, float s2, int i2) { return s1 > s2 || (s1 == s2 && i1 < i2); }
 
@@ -37,10 +105,14 @@ __device__ __forceinline__ bool gal_better(float s1, int i1, float s2, int i2) {
 // as a third word.  The insertion stays ONE compare-exchange pass: whatever the pass holds in hand after position pos — the new
 // entry (not yet placed: the listed one is better, the new one is dropped) or the entry it displaced (the new one is better and took
 // an earlier place) — is discarded when the entry listed at pos carried the new entry's id.
-template <bool IDS>
+//
+// T: element type of rows and queries (float | _Float16); KD: list depth; KFIX: k is KD (else the runtime p.k <= KD).
+template <typename T, int KD, bool KFIX, bool IDS>
 __device__ __forceinline__ void gallery_scan_body(const GalArgs& p) {
+    constexpr bool F16 = std::is_same<T, _Float16>::value;
     constexpr int BM = GAL_BM, BN = GAL_BN, TN = BN / 32;
-    __shared__ v4f ldsq[2][BN * 16];                          // query chunk [64 rows][64 k], 16-byte column XOR (row & 15)
+    constexpr int EC = 16 / (int)sizeof(T), CD = 16 * EC;     // elements per 16-byte column, chunk depth (16 columns)
+    __shared__ v4f ldsq[2][BN * 16];                          // query chunk [64 rows][CD k], 16-byte column XOR (row & 15)
     __shared__ float tau_s[BN];                               // admission threshold per query = the k-th entry of its list
     __shared__ int tau_i[BN];
     __shared__ float que_s[BN][GAL_QCAP];
@@ -58,18 +130,20 @@ __device__ __forceinline__ void gallery_scan_body(const GalArgs& p) {
     }
     const int tile_n = t % p.tiles_n, part = t / p.tiles_n;
     const int n0 = tile_n * BN;
-    if (p.qcount && n0 >= *p.qcount) return;                  // (workgroup-uniform, before any barrier)
-    const int K = p.dim, chunks = K / 64, k = p.k;
+    if constexpr (!F16) {                                     // (the fp16 scan is never the compacted fall-back: no test, its scalar side stays lean)
+        if (p.qcount && n0 >= *p.qcount) return;              // (workgroup-uniform, before any barrier)
+    }
+    const int K = p.dim, chunks = K / CD, k = KFIX ? KD : p.k;
     const int rt0 = part * p.tiles_per_part, rt1 = min(p.row_tiles, rt0 + p.tiles_per_part);
 
-    float ls[GAL_KMAX];                                       // thread q < 64: sorted list of query q (entries >= k stay sentinels)
-    int li[GAL_KMAX];
-    int ld[IDS ? GAL_KMAX : 1];
+    float ls[KD];                                             // thread q < 64: sorted list of query q (entries >= k stay sentinels)
+    int li[KD];
+    int ld[IDS ? KD : 1];
 #pragma unroll
-    for (int i = 0; i < GAL_KMAX; ++i) { ls[i] = -INFINITY; li[i] = INT_MAX; }
+    for (int i = 0; i < KD; ++i) { ls[i] = -INFINITY; li[i] = INT_MAX; }
     if constexpr (IDS) {
 #pragma unroll
-        for (int i = 0; i < GAL_KMAX; ++i) ld[i] = -1;
+        for (int i = 0; i < KD; ++i) ld[i] = -1;
     }
     if (tid < BN) {
         float ts = -INFINITY; int ti = INT_MAX;                   // (-inf, INT_MAX): below every real entry, whatever the rows' norms (compareFaces does not clamp, face_recognizer.cpp:320-334)
@@ -81,9 +155,11 @@ __device__ __forceinline__ void gallery_scan_body(const GalArgs& p) {
     }
     if (tid == 0) overflow = 0;
 
-    // query loader: pass i fills rows i*16 + (tid >> 4), slot tid & 15 <- source column (tid & 15) ^ (row & 15)
+    // query loader: pass i fills rows i*16 + (tid >> 4), slot tid & 15 <- source 16-byte column (tid & 15) ^ (row & 15)
     const int qrow = tid >> 4;
-    const float* const q_base = p.q + (size_t)(n0 + qrow) * K + (((tid & 15) ^ (qrow & 15)) * 4);
+    const T* const gal = static_cast<const T*>(p.gal);
+    const T* const zeros = static_cast<const T*>(p.zeros);
+    const T* const q_base = static_cast<const T*>(p.q) + (size_t)(n0 + qrow) * K + (((tid & 15) ^ (qrow & 15)) * EC);
     const size_t q16 = (size_t)16 * K;
     const int fsw = fr & 15;
 
@@ -91,13 +167,13 @@ __device__ __forceinline__ void gallery_scan_body(const GalArgs& p) {
         const long m0 = (long)rt * BM;
         const long myrow = m0 + wid * 32 + fr;
         const bool live = myrow < p.G;
-        const float* a_ptr = (live ? p.gal + (size_t)myrow * K : p.zeros) + fh2 * 4;       // dead rows read the zero line (and are masked below)
-        const int a_step = live ? 64 : 0;
-        const float* q_src = q_base;
+        const T* a_ptr = (live ? gal + (size_t)myrow * K : zeros) + fh2 * EC;          // dead rows read the zero line (and are masked below)
+        const int a_step = live ? CD : 0;
+        const T* q_src = q_base;
         v4f xa[2][8];
-        auto load_a = [&](v4f (&x)[8]) {
+        auto load_a = [&](v4f (&x)[8]) {                      // 16-byte column 2s + fh2 of the chunk
 #pragma unroll
-            for (int s = 0; s < 8; ++s) x[s] = *reinterpret_cast<const v4f*>(a_ptr + s * 8);
+            for (int s = 0; s < 8; ++s) x[s] = *reinterpret_cast<const v4f*>(a_ptr + s * 2 * EC);
             a_ptr += a_step;
         };
         v16f acc[TN];
@@ -110,13 +186,21 @@ __device__ __forceinline__ void gallery_scan_body(const GalArgs& p) {
 #pragma unroll
             for (int s = 0; s < 8; ++s) {
                 const int col = (2 * s + fh2) ^ fsw;
-                v4f w[TN];
+                if constexpr (F16) {
 #pragma unroll
-                for (int j = 0; j < TN; ++j) w[j] = Wt[j * 32 * 16 + col];
+                    for (int j = 0; j < TN; ++j) {
+                        const v4f w = Wt[j * 32 * 16 + col];
+                        acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(v8h, x[s]), __builtin_bit_cast(v8h, w), acc[j], 0, 0, 0);
+                    }
+                } else {
+                    v4f w[TN];
 #pragma unroll
-                for (int e = 0; e < 4; ++e)
+                    for (int j = 0; j < TN; ++j) w[j] = Wt[j * 32 * 16 + col];
 #pragma unroll
-                    for (int j = 0; j < TN; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(x[s][e], w[j][e], acc[j], 0, 0, 0);
+                    for (int e = 0; e < 4; ++e)
+#pragma unroll
+                        for (int j = 0; j < TN; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(x[s][e], w[j][e], acc[j], 0, 0, 0);
+                }
             }
         };
         // The query chunk goes global -> registers -> LDS (not by LDS-DMA): the compiler makes every LDS read wait for ALL vector-memory
@@ -129,7 +213,7 @@ __device__ __forceinline__ void gallery_scan_body(const GalArgs& p) {
         auto fetch_q = [&]() {
 #pragma unroll
             for (int i = 0; i < 4; ++i) qv[i] = *reinterpret_cast<const v4f*>(q_src + i * q16);
-            q_src += 64;
+            q_src += CD;
         };
         auto store_q = [&](int buf) {
 #pragma unroll
@@ -153,11 +237,11 @@ __device__ __forceinline__ void gallery_scan_body(const GalArgs& p) {
             multiply(xa[1], 1);
             if (kc + 2 < chunks) store_q(0);
         }
-        if (kc < chunks) {                                 // odd number of 64-deep chunks
+        if (kc < chunks) {                                 // odd number of chunks
             __syncthreads();
             multiply(xa[0], 0);
         }
-        // ---- top-k epilogue (as gallery_topk_kernel)
+        // ---- top-k epilogue
         const long rbase = m0 + wid * 32 + 4 * fh2;
         auto push = [&](int g_lo, int g_hi) {
 #pragma unroll
@@ -191,7 +275,7 @@ __device__ __forceinline__ void gallery_scan_body(const GalArgs& p) {
                         const int idn = que_d[tid][c];
                         int d = idn;
 #pragma unroll
-                        for (int pos = 0; pos < GAL_KMAX; ++pos) {  // the same pass; the entry in hand is discarded behind the listed entry of identity idn
+                        for (int pos = 0; pos < KD; ++pos) {  // the same pass; the entry in hand is discarded behind the listed entry of identity idn
                             const bool sw = gal_better(s, gi, ls[pos], li[pos]);
                             const float os = ls[pos]; const int oi = li[pos], od = ld[pos];
                             ls[pos] = sw ? s : os; li[pos] = sw ? gi : oi; ld[pos] = sw ? d : od;
@@ -200,7 +284,7 @@ __device__ __forceinline__ void gallery_scan_body(const GalArgs& p) {
                         }
                     } else {
 #pragma unroll
-                        for (int pos = 0; pos < GAL_KMAX; ++pos) {      // one compare-exchange pass keeps all 16 slots sorted (score desc, index asc)
+                        for (int pos = 0; pos < KD; ++pos) {      // one compare-exchange pass keeps all KD slots sorted (score desc, index asc)
                             const bool sw = gal_better(s, gi, ls[pos], li[pos]);
                             const float os = ls[pos]; const int oi = li[pos];
                             ls[pos] = sw ? s : os; li[pos] = sw ? gi : oi;
@@ -209,13 +293,16 @@ __device__ __forceinline__ void gallery_scan_body(const GalArgs& p) {
                     }
                 }
                 if (n > 0) {
-                    int km1 = k - 1;
+                    float ts = ls[KD - 1]; int ti = li[KD - 1];     // the k-th entry: the last one, or selected by the runtime k
+                    if constexpr (!KFIX) {
+                        int km1 = k - 1;
 #if defined(__HIP_DEVICE_COMPILE__)
-                    asm volatile("" : "+v"(km1));                // (keeps the 16 position tests on the vector side: no SGPR mask per slot)
+                        asm volatile("" : "+v"(km1));            // (keeps the 16 position tests on the vector side: no SGPR mask per slot)
 #endif
-                    float ts = ls[0]; int ti = li[0];
+                        ts = ls[0]; ti = li[0];
 #pragma unroll
-                    for (int pos = 1; pos < GAL_KMAX; ++pos) { ts = pos == km1 ? ls[pos] : ts; ti = pos == km1 ? li[pos] : ti; }
+                        for (int pos = 1; pos < KD; ++pos) { ts = pos == km1 ? ls[pos] : ts; ti = pos == km1 ? li[pos] : ti; }
+                    }
                     // the local k-th entry bounds the global one as soon as the list holds k real rows; keep the tighter of it and the seed
                     if (ti != INT_MAX && gal_better(ts, ti, tau_s[tid], tau_i[tid])) { tau_s[tid] = ts; tau_i[tid] = ti; }
                 }
@@ -242,7 +329,7 @@ __device__ __forceinline__ void gallery_scan_body(const GalArgs& p) {
     if (tid < BN && n0 + tid < p.Q) {
         const size_t o = ((size_t)part * p.Q + n0 + tid) * k;
 #pragma unroll
-        for (int pos = 0; pos < GAL_KMAX; ++pos)
+        for (int pos = 0; pos < KD; ++pos)
             if (pos < k) {
                 p.ps[o + pos] = li[pos] == INT_MAX ? -1.0f : ls[pos]; p.pi[o + pos] = li[pos] == INT_MAX ? -1 : li[pos];
                 if constexpr (IDS) p.pd[o + pos] = li[pos] == INT_MAX ? -1 : ld[pos];

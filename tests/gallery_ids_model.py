@@ -1,4 +1,4 @@
-"""Exact numpy model of the labelled gallery's identity top-k (gallery_topk_ids_kernel + topk_merge_ids_kernel).  A helper, not a
+"""Exact numpy model of the labelled gallery's identity top-k (gallery_topk_ids_kernel + topk_merge_kernel<CACHED, true>).  A helper, not a
 test file.
 
   * a row's score is `oracle.dot_mfma`'s accumulator (the scan's own fma order) mapped (acc + 1) / 2 in float32;
