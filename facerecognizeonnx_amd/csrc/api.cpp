@@ -876,12 +876,16 @@ int fh_resize_u8c3_dev(const uint8_t* src, int sh, int sw, int sstep, uint8_t* d
         return 0;
     });
 }
-// Winograd form of one 3x3 stride-1 pad-1 convolution (+bias), for the parity tests: w_ohwi = host weights [cout][3*3][cin]
-int fh_conv_winograd_dev(const float* d_in, const float* w_ohwi, const float* d_bias, float* d_out, int batch, int h, int w, int cin,
-                         int cout, void* stream) {
-    if (!d_in || !w_ohwi || !d_out || cin % 32 || cout % 4) return arg_error("fh_conv_winograd_dev: bad argument");
+// Winograd form of one 3x3 stride-1 pad-1 convolution (+bias), for the parity tests: w_ohwi = host weights [cout][3*3][cin];
+// precision = FH_PREC_BF16X2: the split-bf16 operand format (U packed here as Net::set_bf16x2 does, V by the input transform)
+int fh_conv_winograd_ex_dev(const float* d_in, const float* w_ohwi, const float* d_bias, float* d_out, int batch, int h, int w, int cin,
+                            int cout, int precision, void* stream) {
+    if (!d_in || !w_ohwi || !d_out || cin % 32 || cout % 4 || (precision != FH_PREC_FP32 && precision != FH_PREC_BF16X2))
+        return arg_error("fh_conv_winograd_dev: bad argument");
+    const bool bf2 = precision == FH_PREC_BF16X2;
     Owns owns(nullptr);                                                  // (no Net: the process-wide watchdog record)
     return guarded([&] {
+        if (bf2 && !fh::wino_gemm_ok_bf16x2(cin, cout)) throw std::runtime_error("winograd: this layer has no split-bf16 GEMM");
         const int rows = fh::conv_wt_rows(cout);
         std::vector<float> u36((size_t)36 * rows * cin, 0.f), uf((size_t)cout * cin);
         std::vector<double> uall((size_t)cout * cin * 36);
@@ -902,6 +906,11 @@ int fh_conv_winograd_dev(const float* d_in, const float* w_ohwi, const float* d_
         dV.ensure((36 * (size_t)fh::wino_rows((long)tiles) + 100 * 128) * cin * sizeof(float));
         dM.ensure((36 * (size_t)fh::wino_rows((long)tiles) + 100 * 128) * cout * sizeof(float));
         FH_HIP(hipMemcpy(dU.p, u36.data(), u36.size() * sizeof(float), hipMemcpyHostToDevice));
+        fh::DevBuf dUp;
+        if (bf2) {
+            dUp.ensure(u36.size() * sizeof(float));
+            fh::launch_pack_bf16x2(dU.as<float>(), dUp.as<float>(), (long)u36.size(), S(stream));
+        }
         static fh::DevBuf slabs;
         static unsigned slabs_gen = 0;
         if (!slabs.p) { slabs.ensure(fh::conv_slab_floats() * sizeof(float)); fh::conv_workspace_init(slabs.as<float>()); slabs_gen = fh::conv_error_generation(); }
@@ -910,8 +919,66 @@ int fh_conv_winograd_dev(const float* d_in, const float* w_ohwi, const float* d_
         a.in = d_in; a.bias = d_bias; a.out1 = d_out; a.slabs = slabs.as<float>(); a.sk_enable = 1;
         a.B = batch; a.H = h; a.W = w; a.Ho = h; a.Wo = w; a.Cin = cin; a.Cout = cout; a.ks = 3; a.stride = 1; a.pad = 1;
         a.act = (int)fh::Act::NONE; a.res_mode = (int)fh::ResMode::NONE;
-        fh::launch_conv_winograd(a, dU.as<float>(), dV.as<float>(), dM.as<float>(), 2, nullptr, nullptr, S(stream));
+        fh::launch_conv_winograd(a, (bf2 ? dUp : dU).as<float>(), dV.as<float>(), dM.as<float>(), 2, nullptr, nullptr, S(stream), bf2);
         FH_HIP(hipStreamSynchronize(S(stream)));                 // the workspaces die with this scope
+        return 0;
+    });
+}
+int fh_conv_winograd_dev(const float* d_in, const float* w_ohwi, const float* d_bias, float* d_out, int batch, int h, int w, int cin,
+                         int cout, void* stream) {
+    return fh_conv_winograd_ex_dev(d_in, w_ohwi, d_bias, d_out, batch, h, w, cin, cout, FH_PREC_FP32, stream);
+}
+// fp32 words -> split-bf16 words (winograd.hip wino_pack_bf16x2), for the format test.  Synchronous.
+int fh_debug_pack_bf16x2_dev(const float* d_in, float* d_out, long long n) {
+    if (!d_in || !d_out || n < 0 || n % 4) return arg_error("fh_debug_pack_bf16x2_dev: bad argument (n % 4 == 0)");
+    return guarded([&] {
+        fh::launch_pack_bf16x2(d_in, d_out, (long)n, nullptr);
+        FH_HIP(hipGetLastError());
+        FH_HIP(hipStreamSynchronize(nullptr));
+        return 0;
+    });
+}
+// The GEMM stage of the Winograd form alone.  Rows of V / M for a layer of `batch` h x w maps: the uniform tiling's 36 planes of
+// wino_rows(tiles) rows, or (mixed) the mixed tiling's planes; < 0 where the arguments are bad or the mixed layout does not apply.
+static long long wino_gemm_rows(int batch, int h, int w, int k, int n, int mixed, fh::WinoPlanes* pl) {
+    if (batch <= 0 || h <= 0 || w <= 0 || k <= 0 || n <= 0 || k % 32 || n % 32) return -1;
+    if (!mixed) return 36LL * fh::wino_rows((long)batch * ((h + 3) / 4) * ((w + 3) / 4));
+    fh::WinoPlanes p{};
+    if (!fh::wino_mix_layout(batch, h, w, k, n, &p)) return -2;
+    if (pl) *pl = p;
+    return 128LL * p.total_tiles;
+}
+long long fh_debug_wino_gemm_rows(int batch, int h, int w, int k, int n, int mixed) {
+    const long long r = wino_gemm_rows(batch, h, w, k, n, mixed, nullptr);
+    if (r == -2) return arg_error("fh_debug_wino_gemm_rows: the mixed tiling does not apply to this layer");
+    if (r < 0) return arg_error("fh_debug_wino_gemm_rows: bad argument (k % 32 == 0, n % 32 == 0)");
+    return r;
+}
+int fh_debug_wino_gemm_dev(const float* d_V, const float* d_U, float* d_M, int batch, int h, int w, int k, int n, int precision, int mixed,
+                           void* stream) {
+    if (!d_V || !d_U || !d_M || (precision != FH_PREC_FP32 && precision != FH_PREC_BF16X2))
+        return arg_error("fh_debug_wino_gemm_dev: bad argument");
+    fh::WinoPlanes pl{};
+    const long long rows = wino_gemm_rows(batch, h, w, k, n, mixed, &pl);
+    if (rows == -2) return arg_error("fh_debug_wino_gemm_dev: the mixed tiling does not apply to this layer");
+    if (rows < 0) return arg_error("fh_debug_wino_gemm_dev: bad argument (k % 32 == 0, n % 32 == 0)");
+    const bool bf2 = precision == FH_PREC_BF16X2;
+    Owns owns(nullptr);                                                  // (no Net: the process-wide watchdog record)
+    return guarded([&] {
+        if (bf2 && !fh::wino_gemm_ok_bf16x2(k, n)) throw std::runtime_error("winograd: this layer has no split-bf16 GEMM");
+        const size_t nv = (size_t)rows * k, nu = (size_t)36 * fh::conv_wt_rows(n) * k;
+        fh::DevBuf dVp, dUp;
+        if (bf2) {                                                       // the caller's operands stay f32: packed copies
+            dVp.ensure(nv * sizeof(float)); dUp.ensure(nu * sizeof(float));
+            fh::launch_pack_bf16x2(d_V, dVp.as<float>(), (long)nv, S(stream));
+            fh::launch_pack_bf16x2(d_U, dUp.as<float>(), (long)nu, S(stream));
+        }
+        fh::ConvArgs a{};
+        a.B = batch; a.H = h; a.W = w; a.Ho = h; a.Wo = w; a.Cin = k; a.Cout = n; a.ks = 3; a.stride = 1; a.pad = 1;
+        a.act = (int)fh::Act::NONE; a.res_mode = (int)fh::ResMode::NONE;
+        fh::launch_wino_gemm(a, bf2 ? dUp.as<float>() : d_U, bf2 ? dVp.as<float>() : d_V, d_M, 2, bf2, S(stream), mixed ? &pl : nullptr);
+        FH_HIP(hipGetLastError());
+        FH_HIP(hipStreamSynchronize(S(stream)));                 // the packed copies die with this scope
         return 0;
     });
 }

@@ -155,8 +155,9 @@ void launch_dwpw(const ConvArgs& a, hipStream_t s);
 // Winograd F(4x4,3x3) form of a 3x3 stride-1 pad-1 convolution (winograd.hip): a = the convolution's arguments,
 // wt36 = U[36][conv_wt_rows(Cout)][Cin], V / M = workspaces of 36 * tiles * max(Cin, Cout) floats each
 // in_scale / in_shift (optional): per-input-channel affine applied to in-image pixels by the input transform
+// bf16x2: the split-bf16 operand format below (wt36 already packed; the input transform packs V)
 void launch_conv_winograd(const ConvArgs& a, const float* wt36, float* V, float* M, int cfg, const float* in_scale, const float* in_shift,
-                          hipStream_t s);
+                          hipStream_t s, bool bf16x2 = false);
 // the three stages separately, and stage 3 of one convolution fused with stage 1 of the next (same map, C = Cout = next Cin)
 // pack / bf16x2 / pack_next: the opt-in split-bf16 operand format (V and U as (hi, mid) bf16 pairs in 32-bit words, see winograd.hip)
 struct WinoPlanes;

@@ -37,6 +37,10 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 // hi = bf16(x) in the low half and mid = bf16(x - hi) in the high half — 16 mantissa bits, same bytes as fp32, so the V / U buffers,
 // their indexing and the GEMM's LDS-DMA loader do not change at all; only the matrix instruction does (three bf16 products
 // hh + hm + mh with f32 accumulation instead of one f32 product).
+// Range: both halves are bf16 values, so hi overflows where bf16 does.  A finite |x| >= 0x7F7F8000 (2^127 * 1.99609375, half a bf16 ulp
+// under the largest bf16) rounds hi to +-Inf, the residual x - hi is -+Inf and the word holds (Inf, -Inf): it unpacks to NaN.  +-Inf
+// gives (Inf, NaN) and NaN gives (NaN, NaN) — every non-finite input, and every finite one above that threshold, stays non-finite.  At
+// the other end a non-zero mid is at least x's last fp32 bit, 2^-23 |x|: it can be a bf16 subnormal only for |x| < 2^-103 (the layers' values are O(1)).
 __device__ __forceinline__ v4f wino_pack_bf16x2(const v4f x) {
     v4u out;
 #pragma unroll
@@ -1247,18 +1251,18 @@ void launch_wino_mix(const ConvArgs& a, const WinoPlanes& pl, const float* M, fl
     timer.end(s, 8, 0.0, 0.0);
 }
 
-// all three stages of one convolution (used by the single-layer test entry point)
+// all three stages of one convolution (used by the single-layer test entry point); bf16x2: wt36 holds split-bf16 words, V is packed
 void launch_conv_winograd(const ConvArgs& a, const float* wt36, float* V, float* M, int cfg, const float* in_scale, const float* in_shift,
-                          hipStream_t s) {
+                          hipStream_t s, bool bf16x2) {
     WinoPlanes pl;
     if (cfg == 2 && wino_mix_layout(a.B, a.H, a.W, a.Cin, a.Cout, &pl)) {
-        launch_wino_mix(a, pl, nullptr, V, 0, in_scale, in_shift, false, s);
-        launch_wino_gemm(a, wt36, V, M, cfg, false, s, &pl);
+        launch_wino_mix(a, pl, nullptr, V, 0, in_scale, in_shift, bf16x2, s);
+        launch_wino_gemm(a, wt36, V, M, cfg, bf16x2, s, &pl);
         launch_wino_mix(a, pl, M, nullptr, 0, nullptr, nullptr, false, s);
         return;
     }
-    launch_wino_input(a, V, in_scale, in_shift, false, s);
-    launch_wino_gemm(a, wt36, V, M, cfg, false, s);
+    launch_wino_input(a, V, in_scale, in_shift, bf16x2, s);
+    launch_wino_gemm(a, wt36, V, M, cfg, bf16x2, s);
     launch_wino_output(a, M, s);
 }
 

@@ -334,6 +334,11 @@ FH_API int fh_conv_forward_dev(const float* d_in, const float* d_wt_packed, cons
  * [cout][3*3][cin]; cin % 32 == 0, cout % 4 == 0.  Synchronous. */
 FH_API int fh_conv_winograd_dev(const float* d_in, const float* w_ohwi_host, const float* d_bias, float* d_out, int batch, int h, int w,
                                 int cin, int cout, void* stream);
+/* The same with a precision argument (enum fh_precision).  FH_PREC_BF16X2: the split-bf16 operand format of fh_rec_set_precision on this
+ * one layer — the weight image is packed as the engine packs it, the input transform writes packed V, the GEMM is the three-product bf16
+ * form.  Layers without that form (cin % 32 != 0 or cout % 64 != 0) are refused ("... no split-bf16 GEMM"). */
+FH_API int fh_conv_winograd_ex_dev(const float* d_in, const float* w_ohwi_host, const float* d_bias, float* d_out, int batch, int h, int w,
+                                   int cin, int cout, int precision, void* stream);
 /* The same convolution in the fused Winograd F(2x2,3x3) form the 64-channel stages use (conv_wino2.hip): cin == 64, cout % 64 == 0;
  * d_bias = [cout] or, with bias_cls != 0, [9][cout] (one vector per border class of the output pixel: a pre-conv BatchNorm folded in);
  * act = 0 none / 1 ReLU / 2 PReLU (d_slope [cout]) ...; d_res = optional residual of the output's shape.  Synchronous. */
@@ -368,6 +373,17 @@ FH_API int fh_debug_streamk(int drop_publish, int timeout_ms);
  * slots walk several tiles per workgroup; slots > 0 makes the launcher pretend the device has that many (rounded up to 8), so that small
  * test layers take the multi-tile path with many tiles per workgroup; 0 restores the device's own count. */
 FH_API int fh_debug_wino_slots(int slots);
+/* Test hook of the split-bf16 operand format (winograd.hip wino_pack_bf16x2): n f32 words -> n packed words, hi = bf16(x) in the low half,
+ * mid = bf16(x - hi) in the high half, both round-to-nearest-even.  n % 4 == 0.  Synchronous. */
+FH_API int fh_debug_pack_bf16x2_dev(const float* d_in, float* d_out, long long n);
+/* Test hook: the GEMM stage of the Winograd form alone, M[plane] = V[plane] * U[frequency of the plane]^T, on caller-supplied f32
+ * operands.  d_V [rows][k] and d_M [rows][n] in the plane layout the transforms use (rows = fh_debug_wino_gemm_rows: 36 planes of the
+ * tile count rounded up to 256 or, mixed != 0, the planes of the mixed F(4x4) / F(2x2) tiling — refused where that tiling does not
+ * apply); d_U [36][fh_conv_wt_rows(n)][k] row-major.  k % 32 == 0, n % 32 == 0.  precision = FH_PREC_BF16X2 packs copies of V and U
+ * and runs the three-product bf16 kernel (n % 64 == 0).  Synchronous. */
+FH_API long long fh_debug_wino_gemm_rows(int batch, int h, int w, int k, int n, int mixed);
+FH_API int fh_debug_wino_gemm_dev(const float* d_V, const float* d_U, float* d_M, int batch, int h, int w, int k, int n, int precision,
+                                  int mixed, void* stream);
 /* Test hook of the top-k merge (face_kernels.hip topk_merge_kernel) with the list layout of the sharded exchange: part w's [nq][k]
  * scores start at ps + w * part_stride and its indices at pi + w * part_stride (comm.cpp gathers [scores | indices] per rank, so
  * part_stride = 2 * nq * k there).  Needs 1 <= k <= 16, nparts * k <= 65536 and part_stride >= nq * k; returns nq. */

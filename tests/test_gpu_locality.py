@@ -160,29 +160,50 @@ def test_conv_layer_locality(B, H, W, Cin, Cout, k, stride, cfg):
                        loc.R_DIRECT3 if k == 3 else loc.R_1X1, k, [True], clean_check)
 
 
-@pytest.mark.parametrize("B,H,W,Cin,Cout", WINO_CASES)
-def test_winograd_layer_locality(B, H, W, Cin, Cout):
-    """F(4x4,3x3), uniform and mixed F(4) / F(2) tiling: wino_input_kernel / wino_mix_kernel -> GEMM -> output transform."""
+def _winograd_layer_locality(B, H, W, Cin, Cout, precision):
+    """precision = 1: the split-bf16 operand format through fh_conv_winograd_ex_dev — the same plants, aggressors, guards and radius; a
+    plant's word holds a NaN mid beside its NaN / Inf hi, nothing else changes."""
     rng = np.random.default_rng(B * 1000 + H * 10 + Cin)
     x = rng.standard_normal((B, Cin, H, W)).astype(np.float32)
     w = (rng.standard_normal((Cout, Cin, 3, 3)) / np.sqrt(Cin * 9)).astype(np.float32)
     b = rng.standard_normal(Cout).astype(np.float32)
-    ref = oracle.conv2d(x, w, b, 1, 1, 1)
     ohwi = np.ascontiguousarray(w.transpose(0, 2, 3, 1))
     bd = dev(b)
+    if precision:                                                                                  # test_layer_against_fp64_...'s bars
+        from tests.test_gpu_wino_bf16x2 import conv_fp64, layer_bars
+        ref = conv_fp64(x, w, b)
+        bar_max, bar_rms, _, _ = layer_bars(x, w, b, ref)
+    else:
+        ref = oracle.conv2d(x, w, b, 1, 1, 1)
 
     def launch(xp, _rp, outs):
-        rc = fa.lib().fh_conv_winograd_dev(xp, ohwi.ctypes.data, bd.data_ptr(), outs[0], B, H, W, Cin, Cout, 0)
+        rc = fa.lib().fh_conv_winograd_ex_dev(xp, ohwi.ctypes.data, bd.data_ptr(), outs[0], B, H, W, Cin, Cout, precision, 0)
         assert rc == 0, _lib.last_error()
 
     def clean_check(clean):                                                                        # test_winograd_conv_matches_oracle's bars
         got = clean[0].transpose(0, 3, 1, 2)
         assert np.isfinite(got).all()
+        if precision:
+            assert np.abs(got - ref).max() <= bar_max and np.sqrt(((got - ref) ** 2).mean()) <= bar_rms
+            return
         np.testing.assert_allclose(got, ref, rtol=0, atol=2e-4)
         assert np.sqrt(((got - ref) ** 2).mean()) < 2e-5
 
-    _single_layer_legs("winograd F(4x4)", np.ascontiguousarray(x.transpose(0, 2, 3, 1)), None, [(B, H, W, Cout)], launch, 1, loc.R_WINO4, 3,
-                       [True], clean_check)
+    _single_layer_legs("winograd F(4x4) bf16x2" if precision else "winograd F(4x4)", np.ascontiguousarray(x.transpose(0, 2, 3, 1)), None,
+                       [(B, H, W, Cout)], launch, 1, loc.R_WINO4, 3, [True], clean_check)
+
+
+@pytest.mark.parametrize("B,H,W,Cin,Cout", WINO_CASES)
+def test_winograd_layer_locality(B, H, W, Cin, Cout):
+    """F(4x4,3x3), uniform and mixed F(4) / F(2) tiling: wino_input_kernel / wino_mix_kernel -> GEMM -> output transform."""
+    _winograd_layer_locality(B, H, W, Cin, Cout, 0)
+
+
+@pytest.mark.parametrize("B,H,W,Cin,Cout", [c for c in WINO_CASES if c[3] % 32 == 0 and c[4] % 64 == 0])
+def test_winograd_layer_locality_bf16x2(B, H, W, Cin, Cout):
+    """The same layers in the split-bf16 operand format (those that have that form): the packing writers of V and
+    wino_gemm_bf16x2_kernel under the same plants, aggressors and guards."""
+    _winograd_layer_locality(B, H, W, Cin, Cout, 1)
 
 
 @pytest.mark.parametrize("B,H,W,Cin,Cout,act,with_res,cls", WINO2_CASES)
