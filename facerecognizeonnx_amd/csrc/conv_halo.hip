@@ -16,21 +16,11 @@
 
 #include <stdexcept>
 
+#include "gemm_tile.h"
 #include "kernels.h"
 #include "plan.h"
 
 namespace fh {
-
-typedef float v4f __attribute__((ext_vector_type(4)));
-typedef float v16f __attribute__((ext_vector_type(16)));
-
-__device__ __forceinline__ void halo_dma16(const float* src, v4f* dst) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    __builtin_amdgcn_global_load_lds(src, (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
-#else
-    (void)src; (void)dst;
-#endif
-}
 
 constexpr int CH_TH = 8, CH_TW = 16, CH_HW = CH_TW + 2, CH_HALO = (CH_TH + 2) * CH_HW;      // 128 outputs, 10 x 18 = 180 halo pixels
 
@@ -51,11 +41,7 @@ __global__ __launch_bounds__(256, CIN4 == 4 ? 4 : 3) void conv3x3_halo_kernel(co
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int fr = lane & 31, fh2 = lane >> 5;
     const int C = p.Cin;
-    int t;
-    {   // XCD-contiguous tile order: neighbouring tiles (shared halo rows / columns) on one L2
-        const int nb = gridDim.x, q = nb >> 3, r8 = nb & 7, x = blockIdx.x & 7;
-        t = x * q + min(x, r8) + (int)(blockIdx.x >> 3);
-    }
+    int t = xcd_tile(blockIdx.x, gridDim.x);                      // neighbouring tiles (shared halo rows / columns) on one L2
     const int tx0 = (t % tiles_x) * CH_TW; t /= tiles_x;
     const int ty0 = (t % tiles_y) * CH_TH;
     const int n = t / tiles_y;
@@ -72,7 +58,7 @@ __global__ __launch_bounds__(256, CIN4 == 4 ? 4 : 3) void conv3x3_halo_kernel(co
             const int iy = ty0 + hy - 1, ix = tx0 + hx - 1;
             if ((unsigned)iy < (unsigned)p.H && (unsigned)ix < (unsigned)p.W) src = img + ((size_t)iy * p.W + ix) * C + ((cp ^ key(hx)) * 4);
         }
-        halo_dma16(src, halo + j * 256 + wid * 64);
+        lds_dma16(src, halo + j * 256 + wid * 64);
     }
     v16f acc[TN];
 #pragma unroll
@@ -186,11 +172,7 @@ __global__ __launch_bounds__(256, 4) void conv3x3_halo16_kernel(const ConvArgs p
     const int tid = threadIdx.x, lane = tid & 63;
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int j = lane & 15, q = lane >> 4;
-    int t;
-    {
-        const int nb = gridDim.x, qq = nb >> 3, r8 = nb & 7, x = blockIdx.x & 7;
-        t = x * qq + min(x, r8) + (int)(blockIdx.x >> 3);
-    }
+    int t = xcd_tile(blockIdx.x, gridDim.x);
     const int tx0 = (t % tiles_x) * CH_TW; t /= tiles_x;
     const int ty0 = (t % tiles_y) * CH_TH;
     const int n = t / tiles_y;
@@ -204,7 +186,7 @@ __global__ __launch_bounds__(256, 4) void conv3x3_halo16_kernel(const ConvArgs p
             const int iy = ty0 + hy - 1, ix = tx0 + hx - 1;
             if ((unsigned)iy < (unsigned)p.H && (unsigned)ix < (unsigned)p.W) src = img + ((size_t)iy * p.W + ix) * 16 + ((cp ^ ((hx >> 2) & 3)) * 4);
         }
-        halo_dma16(src, halo + jj * 256 + wid * 64);
+        lds_dma16(src, halo + jj * 256 + wid * 64);
     }
     v4f w[9];
 #pragma unroll

@@ -47,13 +47,11 @@
 #include <stdexcept>
 #include <vector>
 
+#include "gemm_tile.h"
 #include "kernels.h"
 #include "plan.h"
 
 namespace fh {
-
-typedef float v4f __attribute__((ext_vector_type(4)));
-typedef float v16f __attribute__((ext_vector_type(16)));
 
 // stream-K workspace: accumulator slabs followed by one counter word per remainder tile
 constexpr size_t SK_SLAB_FLOATS = (size_t)2 * 1280 * 128 * 128;
@@ -83,17 +81,6 @@ __device__ __forceinline__ float apply_act(float v, int act, float slope) {
     if (act == (int)Act::PRELU) return v >= 0.f ? v : v * slope;
     if (act == (int)Act::SIGMOID) return 1.0f / (1.0f + expf(-v));
     return v;
-}
-
-// global -> LDS without a register round trip (global_load_lds_dwordx4).  The global address is
-// per lane; the LDS address is the wave-uniform `dst` + 16 * lane.  (The builtin only exists in the
-// device pass; the host pass of hipcc just needs the kernel body to parse.)
-__device__ __forceinline__ void lds_dma16(const float* src, v4f* dst) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    __builtin_amdgcn_global_load_lds(src, (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
-#else
-    (void)src; (void)dst;
-#endif
 }
 
 template <int BM, int BN, int WM, int WN>
@@ -940,43 +927,39 @@ __global__ __launch_bounds__(WM * WN * 64, OCC) void conv_tall_kernel(const Conv
 // conv_pw_kernel (round 3) — 1x1 stride-1 convolutions as the plain GEMM they are: out [M][N] = in [M][K] * W^T.
 // conv_igemm_kernel spends ~650 vector + ~490 scalar instructions per wave on tap / padding / index bookkeeping around the MFMAs of a
 // short-K tile (that is why the Winograd GEMMs got wino_gemm_kernel); SCRFD's 1x1 convolutions (K = 72 / 152 / 288, 0.8 ms of the
-// detector at B = 128) and MobileFaceNet's ran at 65-88 TFLOP/s in it.  Here: wino_gemm_kernel's loop — rows are contiguous, a lane's
+// detector at B = 128) and MobileFaceNet's ran at 65-88 TFLOP/s in it.  Here: the lean GEMM tile of gemm_tile.h — rows are contiguous, a lane's
 // source address only advances by 32 floats per chunk — with a zero-line source for the float4 columns behind K in the last chunk
 // (K % 4 == 0, any remainder), 128 x BN tiles with BN = 96 (N = 288: three exact column tiles) / 64 / 32, and the shared
 // conv_epilogue (bias, ReLU / PReLU, residual incl. the FPN's 2x upsampled one, second output) with its vectors parked in LDS.
 // M % 128 == 0 (whole tiles) and at least one tile per CU, else launch_conv keeps the generic kernel and its stream-K.
+#ifdef FACEHIP_PW_ABL
+// Diagnostic build (scripts/pw_ablate.sh, scripts/pw_phases.py; an ablated run's results are garbage).  ABL = the loop masks of
+// gemm_chunk_f32 (1 = no loads in the K loop, 2 = no LDS reads, 4 = no barriers in the K loop), chosen by launch_pw_cfg from the low bits
+// of FACEHIP_PW_ABL; the higher bits stay run-time, in p.sk_test_drop: 8 = no epilogue, 16 = epilogue stores from one lane only,
+// 32 = the CU's second workgroup starts (bits 8..) x 0.64 us late, 64 = wait for the stores' acknowledgement before the last stamp.
+// Phase stamps (100 MHz ticks) of the 20x20x288 layers go to the stream-K workspace: [workgroup][entry, first chunk landed, K loop
+// done, epilogue done] and, from 8192 on, [workgroup][epilogue entry, first block in LDS, last store issued, ep vectors parked].
+// (Only this build has the third parameter: the kernel's name in the production build is what the profiles and scripts key on.)
+template <int BN, int OCC, int ABL = 0>
+#else
 template <int BN, int OCC>
+#endif
 __global__ __launch_bounds__(256, OCC) void conv_pw_kernel(const ConvArgs p, const int tiles_n, const int chunks) {
-    constexpr int BM = 128, TN = BN / 32, AL = BM / 32, BL = BN / 32;
+    constexpr int BM = GEMM_BM, TN = BN / 32;
+#ifndef FACEHIP_PW_ABL
+    constexpr int ABL = 0;
+#endif
     __shared__ v4f lds[2][(BM + BN) * 8];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int fr = lane & 31, fh2 = lane >> 5, fsw = (fr >> 1) & 7;
-    const int nb = gridDim.x, q = nb >> 3, r8 = nb & 7, x = blockIdx.x & 7;
-    const int tile = x * q + min(x, r8) + (blockIdx.x >> 3);                // XCD-contiguous tile order
+    const GemmLane l = gemm_lane();
+    const int tid = l.tid;
+    const int tile = xcd_tile(blockIdx.x, gridDim.x);
     const int tile_n = tile % tiles_n, tile_m = tile / tiles_n;
     const int m0 = tile_m * BM, n0 = tile_n * BN;
     const int K = p.Cin;
 
-    const int lrow = tid >> 3;
-    const int lqs = (tid & 7) ^ ((lrow >> 1) & 7);                          // source k-column of this lane (swizzle on the source side)
-    const float* a_src = p.in + (size_t)(m0 + lrow) * K + lqs * 4;
-    const float* b_src = p.wt + (size_t)(n0 + lrow) * p.Kpad + lqs * 4;
-    const size_t a32 = (size_t)32 * K, b32 = (size_t)32 * p.Kpad;
-    const float* const zsrc = p.zeros + lqs * 4;
-    int kleft = K - lqs * 4;                                                // > 0: this lane's float4 of the current chunk lies inside a row
-    v4f* const dstA = &lds[0][wid * 64];
-    v4f* const dstB = &lds[0][BM * 8 + wid * 64];
-    auto load_chunk = [&](int buf) {
-        v4f* const dA = dstA + buf * ((BM + BN) * 8);
-        v4f* const dB = dstB + buf * ((BM + BN) * 8);
-        const bool in_k = kleft > 0;
-#pragma unroll
-        for (int i = 0; i < AL; ++i) lds_dma16(in_k ? a_src + i * a32 : zsrc, dA + i * 32 * 8);
-#pragma unroll
-        for (int i = 0; i < BL; ++i) lds_dma16(b_src + i * b32, dB + i * 32 * 8);
-        a_src += 32; b_src += 32; kleft -= 32;
-    };
+    GemmSrc src = gemm_src<BN>(lds, p.in, m0, K, p.wt, n0, p.Kpad, l);
+    const float* const zsrc = p.zeros + l.lqs() * 4;
+    int kleft = K - l.lqs() * 4;                                            // > 0: this lane's float4 of the current chunk lies inside a row
     v16f acc[1][TN];
 #pragma unroll
     for (int j = 0; j < TN; ++j)
@@ -999,71 +982,27 @@ __global__ __launch_bounds__(256, OCC) void conv_pw_kernel(const ConvArgs p, con
     }
 
 #ifdef FACEHIP_PW_ABL
-    // Diagnostic build (scripts/pw_ablate.sh, scripts/pw_phases.py; an ablated run's results are garbage).  p.sk_test_drop bits: 1 = no loads
-    // in the K loop, 2 = no LDS reads, 4 = no barriers in the K loop, 8 = no epilogue, 16 = epilogue stores from one lane only,
-    // 32 = the CU's second workgroup starts (bits 8..) x 0.64 us late, 64 = wait for the stores' acknowledgement before the last stamp.
-    // Phase stamps (100 MHz ticks) of the 20x20x288 layers go to the stream-K workspace: [workgroup][entry, first chunk landed, K loop
-    // done, epilogue done] and, from 8192 on, [workgroup][epilogue entry, first block in LDS, last store issued, ep vectors parked].
     const int abl = p.sk_test_drop;
     const unsigned long long ts0 = wall_clock64();
     if ((abl & 32) && blockIdx.x >= 256u && blockIdx.x < 512u)
         while (wall_clock64() - ts0 < (unsigned long long)(abl >> 8) * 64ull) __builtin_amdgcn_s_sleep(32);
-    load_chunk(0);
+#endif
+    gemm_load_chunk<BN>(src, 0, kleft > 0, zsrc);
+    kleft -= 32;
     __syncthreads();
+#ifdef FACEHIP_PW_ABL
     const unsigned long long ts1 = wall_clock64();
-    v4f xk = lds[0][(wid * 32 + fr) * 8 + (fh2 ^ fsw)], wk[TN];
-#pragma unroll
-    for (int j = 0; j < TN; ++j) wk[j] = lds[0][BM * 8 + fr * 8 + j * 32 * 8 + (fh2 ^ fsw)];
+#endif
+    GemmFrag<TN> held{};
+    if constexpr ((ABL & 2) != 0) held = gemm_frag<TN>(lds[0], l, 0);
     for (int kc = 0; kc < chunks; ++kc) {
-        const int buf = (abl & 1) ? 0 : (kc & 1);
-        if (!(abl & 1) && kc + 1 < chunks) load_chunk(buf ^ 1);
-        const v4f* X = lds[buf] + (wid * 32 + fr) * 8;
-        const v4f* Wt = lds[buf] + BM * 8 + fr * 8;
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            const int col = (2 * s + fh2) ^ fsw;
-            v4f xv = xk;
-            v4f w[TN];
-#pragma unroll
-            for (int j = 0; j < TN; ++j) w[j] = wk[j];
-            if (!(abl & 2)) {
-                xv = X[col];
-#pragma unroll
-                for (int j = 0; j < TN; ++j) w[j] = Wt[j * 32 * 8 + col];
-            }
-            asm volatile("" : "+v"(xv));
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-#pragma unroll
-                for (int j = 0; j < TN; ++j) acc[0][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(w[j][e], xv[e], acc[0][j], 0, 0, 0);
-        }
-        if (!(abl & 4)) __syncthreads();
+        gemm_chunk_f32<BN, ABL>(acc[0], lds, kc & 1, kc + 1 < chunks, src, l, kleft > 0, zsrc, &held);
+        kleft -= 32;
     }
+#ifdef FACEHIP_PW_ABL
     __syncthreads();
     const unsigned long long ts2 = wall_clock64();
     if ((abl & 8) && acc[0][0][0] != 123.456f) return;
-#else
-    load_chunk(0);
-    __syncthreads();
-    for (int kc = 0; kc < chunks; ++kc) {
-        const int buf = kc & 1;
-        if (kc + 1 < chunks) load_chunk(buf ^ 1);
-        const v4f* X = lds[buf] + (wid * 32 + fr) * 8;
-        const v4f* Wt = lds[buf] + BM * 8 + fr * 8;
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            const int col = (2 * s + fh2) ^ fsw;
-            const v4f xv = X[col];
-            v4f w[TN];
-#pragma unroll
-            for (int j = 0; j < TN; ++j) w[j] = Wt[j * 32 * 8 + col];
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-#pragma unroll
-                for (int j = 0; j < TN; ++j) acc[0][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(w[j][e], xv[e], acc[0][j], 0, 0, 0);
-        }
-        __syncthreads();
-    }
 #endif
     float* const ep = reinterpret_cast<float*>(&lds[0][0]);
 #pragma unroll
@@ -1077,7 +1016,7 @@ __global__ __launch_bounds__(256, OCC) void conv_pw_kernel(const ConvArgs p, con
     const bool stamp = tid == 0 && p.slabs && p.Cout == 288 && p.Cin == 288;
     if (stamp) reinterpret_cast<unsigned long long*>(p.slabs)[8192 + (size_t)blockIdx.x * 4 + 3] = wall_clock64();
 #endif
-    conv_epilogue<BM, BN, 4, 1>(p, acc, m0, n0, wid, 0, lane, -1, -1, ep, conv_ep_lines(p) ? ep + 12 * BN : nullptr);
+    conv_epilogue<BM, BN, 4, 1>(p, acc, m0, n0, l.wid, 0, l.lane, -1, -1, ep, conv_ep_lines(p) ? ep + 12 * BN : nullptr);
 #ifdef FACEHIP_PW_ABL
     if (stamp) {
         const unsigned long long ts3 = wall_clock64();                  // stores issued
@@ -1093,7 +1032,15 @@ static void launch_pw_cfg(const ConvArgs& a, long M, hipStream_t s) {
     const int tiles_n = (a.Cout + BN - 1) / BN;
     KernelTimer& timer = KernelTimer::get();
     timer.begin(s);
-    hipLaunchKernelGGL((conv_pw_kernel<BN, OCC>), dim3((unsigned)((M / 128) * tiles_n)), dim3(256), 0, s, a, tiles_n, a.Kpad / 32);
+    const dim3 grid((unsigned)((M / 128) * tiles_n));
+#ifdef FACEHIP_PW_ABL
+#define PWABL(X) case X: hipLaunchKernelGGL((conv_pw_kernel<BN, OCC, X>), grid, dim3(256), 0, s, a, tiles_n, a.Kpad / 32); break;
+    switch (a.sk_test_drop & 7) { PWABL(1) PWABL(2) PWABL(4) PWABL(7)                   // (the loop masks scripts/pw_ablate.sh uses)
+        default: hipLaunchKernelGGL((conv_pw_kernel<BN, OCC>), grid, dim3(256), 0, s, a, tiles_n, a.Kpad / 32); }
+#undef PWABL
+#else
+    hipLaunchKernelGGL((conv_pw_kernel<BN, OCC>), grid, dim3(256), 0, s, a, tiles_n, a.Kpad / 32);
+#endif
     timer.end(s, 11, a.t_flops, a.t_bytes);
 }
 

@@ -41,23 +41,13 @@
 #include <stdexcept>
 #include <vector>
 
+#include "gemm_tile.h"
 #include "kernels.h"
 #include "plan.h"
 
 namespace fh {
 
-typedef float v4f __attribute__((ext_vector_type(4)));
-
 namespace {
-
-// global -> LDS without a register round trip: the global address is per lane, the LDS address is the WAVE-UNIFORM dst + 16 * lane
-__device__ __forceinline__ void dma16(const float* src, void* dst) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    __builtin_amdgcn_global_load_lds(src, (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
-#else
-    (void)src; (void)dst;
-#endif
-}
 
 // NONE / ReLU / PReLU without a branch per element: sl = 1 (none) or the PReLU slope; relu is wave-uniform
 __device__ __forceinline__ float act1(float v, bool relu, float sl) {
@@ -117,7 +107,7 @@ __global__ __launch_bounds__(64 * NW, NW == 1 ? 2 : 3) void wino2_kernel(const C
             const int y = y0 + 2 * pr, x = x0 + 2 * pc;
             const bool ok = (unsigned)y < (unsigned)H && (unsigned)x < (unsigned)W;
             if (NW > 1 && (i % NW) != wv) continue;                        // (wave-uniform: the waves of a workgroup take alternate pieces)
-            dma16(ok ? img + ((long)2 * pr * W + 2 * pc) * 64 + ((col ^ key(pr, pc)) << 2) : p.zeros, halo + i * 1024);
+            lds_dma16(ok ? img + ((long)2 * pr * W + 2 * pc) * 64 + ((col ^ key(pr, pc)) << 2) : p.zeros, halo + i * 1024);
         }
     }
     typedef const __attribute__((address_space(3))) v4f* lds_v4f;

@@ -21,21 +21,11 @@
 #include <stdexcept>
 #include <type_traits>
 
+#include "gemm_tile.h"
 #include "kernels.h"
 #include "plan.h"
 
 namespace fh {
-
-typedef float v4f __attribute__((ext_vector_type(4)));
-typedef float v16f __attribute__((ext_vector_type(16)));
-
-__device__ __forceinline__ void dwpw_dma16(const float* src, v4f* dst) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    __builtin_amdgcn_global_load_lds(src, (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
-#else
-    (void)src; (void)dst;
-#endif
-}
 
 typedef const unsigned __attribute__((address_space(1))) dwpw_gmem_u32;
 constexpr int DP_TH = 8, DP_TW = 16, DP_BM = DP_TH * DP_TW;            // 128 output pixels per tile
@@ -75,11 +65,7 @@ __global__ __launch_bounds__(256, DIRECT ? (HC == 4 ? 3 : BN * DS <= 64 ? 3 : 2)
     // Workgroups are dealt round-robin over the 8 XCDs (blockIdx % 8), each with its own L2: neighbouring tiles share halo rows /
     // columns, so give every XCD a CONTIGUOUS run of tiles (whole images, row after row) — the halo is then fetched once per XCD
     // instead of once per tile (rocprofv3, 320x320x16 layer: FETCH_SIZE 1.54x the input with the linear order).
-    int t;
-    {
-        const int nb = gridDim.x, q = nb >> 3, r8 = nb & 7, x = blockIdx.x & 7;
-        t = x * q + min(x, r8) + (int)(blockIdx.x >> 3);
-    }
+    int t = xcd_tile(blockIdx.x, gridDim.x);
     const int tile_n = t % tiles_n; t /= tiles_n;
     const int tx0 = (t % tiles_x) * DP_TW; t /= tiles_x;
     const int ty0 = (t % tiles_y) * DP_TH;
@@ -143,11 +129,11 @@ __global__ __launch_bounds__(256, DIRECT ? (HC == 4 ? 3 : BN * DS <= 64 ? 3 : 2)
                     src = ch < C ? (k < 9 ? p.dw_w + (size_t)k * C + ch : p.dw_b + ch) : p.zeros;
                     go = true;
                 }
-                if (go) dwpw_dma16(src, halo + j * 256 + wid * 64);
+                if (go) lds_dma16(src, halo + j * 256 + wid * 64);
             }
         }
 #pragma unroll
-        for (int i = 0; i < BL; ++i) dwpw_dma16(reinterpret_cast<const float*>(w_base + w_off[i]), Wt + i * 256 + wid * 64);
+        for (int i = 0; i < BL; ++i) lds_dma16(reinterpret_cast<const float*>(w_base + w_off[i]), Wt + i * 256 + wid * 64);
         w_base += 128;
         // depthwise weights / bias of this thread's 4 channels (channels >= C: zero line -> zero output)
         const int cw = c0 + dq * 4;
@@ -327,8 +313,6 @@ static void launch_dwpw_cfg(const ConvArgs& a, hipStream_t s) {
 //   4. pointwise product on v_mfma_f32_32x32x2_f32 (K = 16), bias + ReLU, stores.
 // Three barriers per tile.  Tiles are dealt so that the workgroups of one XCD work on neighbouring tiles at the same time (shared
 // window rows hit that XCD's L2).
-typedef unsigned v4u __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 // Folded stem weights wf [27][16] (tap-major: (ky*9 + kx*3 + byte) x channel) as the A fragments of v_mfma_f32_16x16x32_bf16: three
 // bf16 terms (hi, mid, lo — their sum is the fp32 weight exactly), lane l = channel l & 15, K block l >> 4; K index 8g + j = byte j of
@@ -399,7 +383,7 @@ __global__ __launch_bounds__(256, 4) void front_kernel(const ConvArgs p, const i
     // ---- once per workgroup: pointwise weights -> LDS, depthwise weights / biases -> LDS, stem fragments -> registers
     {
         const int lrow = tid >> 3, lqs = (tid & 7) ^ ((lrow >> 1) & 7);
-        dwpw_dma16(p.wt + (size_t)lrow * p.Kpad + lqs * 4, Wt + wid * 64);
+        lds_dma16(p.wt + (size_t)lrow * p.Kpad + lqs * 4, Wt + wid * 64);
     }
     // depthwise weights [9][16], depthwise bias [16], pointwise bias [32] live in LDS (re-read per tile) — in registers they would push
     // the kernel past the 128 VGPRs that 4 workgroups per CU allow

@@ -193,13 +193,13 @@ bool wino_mix_layout(int B, int H, int W, int Cin, int Cout, WinoPlanes* out);
 //   Vnext != null: V = B^T d B for the next convolution (= `a` itself when M is null) from that image (feed_aff: through a.s2 / a.t2).
 void launch_wino_mix(const ConvArgs& a, const WinoPlanes& pl, const float* M, float* Vnext, int feed_aff, const float* in_scale,
                      const float* in_shift, bool pack_next, hipStream_t s);
-void wino_filter_transform(const double g[9], double u[36]);
+void wino_filter_transform(const double g[9], double u[36]);     // host: G g G^T of one 3x3 filter
 void wino_debug_slots(int slots);            // test hook: workgroup slots the multi-tile Winograd GEMM sizes its grid for (0 = the device)
-long wino_rows(long tiles);                  // rows per frequency plane of the V / M workspaces (tiles rounded up to 256)     // host: G g G^T of one 3x3 filter
+long wino_rows(long tiles);                  // rows per frequency plane of the V / M workspaces (tiles rounded up to 256)
 int conv_wt_rows(int Cout);                   // packed weight rows (Cout rounded up to 128)
-size_t conv_slab_floats();
+size_t conv_slab_floats();                    // size of the stream-K slab workspace
 // host: plan-layout weights [Cout][ks*ks][Cin] -> packed [conv_wt_rows(Cout)][conv_kpad(ks*ks*Cin)] (dst pre-zeroed)
-void conv_pack_weights(const float* w, int Cout, int Cin, int ks, float* dst);                    // size of the stream-K slab workspace
+void conv_pack_weights(const float* w, int Cout, int Cin, int ks, float* dst);
 inline int conv_kpad(int Ktot) { return (Ktot + 31) / 32 * 32; }
 
 // --------------------------------------------------------------------------------------------

@@ -21,17 +21,14 @@
 #include <cstdlib>
 #include <stdexcept>
 
+#include "gemm_tile.h"
 #include "kernels.h"
 #include "plan.h"
 
 namespace fh {
 
-typedef float v4f __attribute__((ext_vector_type(4)));
-typedef float v16f __attribute__((ext_vector_type(16)));
 typedef float v2f __attribute__((ext_vector_type(2)));
-typedef unsigned v4u __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 // Split-bf16 operand format of the opt-in "bf16x2" mode (fh_rec_set_precision): a value x travels as ONE 32-bit word holding
 // hi = bf16(x) in the low half and mid = bf16(x - hi) in the high half — 16 mantissa bits, same bytes as fp32, so the V / U buffers,
@@ -458,17 +455,10 @@ static bool wino_slice_shape(int H, int W, int C) {
 }
 
 // ---- the 36 GEMMs: M[f] = V[f] (rows x K) * U[f] (K x N), frequency planes stacked along the rows --------------------------
-// Same tile anatomy as conv_igemm_kernel (LDS-DMA with source-side swizzle, [row][32 k] LDS images, one ds_read_b128 per 4 MFMAs,
-// weights as the MFMA A operand) but nothing else: rows are contiguous, K and N are multiples of 32, the row count a multiple of
-// 256, the epilogue a plain store.  The generic kernel spends ~650 VALU + ~490 SALU instructions per wave on tap / padding / index
-// bookkeeping around the 128 MFMAs of such a short-K tile (rocprofv3: matrix pipe busy 58 %); this one does not.
-__device__ __forceinline__ void wino_dma16(const float* src, v4f* dst) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    __builtin_amdgcn_global_load_lds(src, (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
-#else
-    (void)src; (void)dst;
-#endif
-}
+// The lean GEMM tile of gemm_tile.h (LDS-DMA with source-side swizzle, [row][32 k] LDS images, one ds_read_b128 per 4 MFMAs, weights
+// as the MFMA A operand) and nothing else: rows are contiguous, K and N are multiples of 32, the row count a multiple of 256, the
+// epilogue a plain store.  conv_igemm_kernel spends ~650 VALU + ~490 SALU instructions per wave on tap / padding / index bookkeeping
+// around the 128 MFMAs of such a short-K tile (rocprofv3: matrix pipe busy 58 %); this one does not.
 
 // weight matrix (frequency 6 i + j of the F(4x4) set) of the plane GEMM tile `tile_m` belongs to — see WinoPlanes (kernels.h)
 __device__ __forceinline__ int wino_plane_freq(const WinoPlanes& pl, const int tile_m) {
@@ -481,36 +471,6 @@ __device__ __forceinline__ int wino_plane_freq(const WinoPlanes& pl, const int t
     return 6 * i + j;
 }
 
-// A wave's 32 x (32 TN) accumulator block -> M as whole rows (see the comment at wino_gemm_kernel's stores): turned around in the wave's
-// own region of `scratch` (the tile buffers, free after the K loop's last barrier), two 32-column blocks at a time.
-template <int TN>
-__device__ __forceinline__ void wino_store_lines(const v16f (&acc)[TN], float* scratch, size_t scratch_bytes, float* __restrict__ M, int N,
-                                                 int m0, int n0, int wid, int lane) {
-    constexpr int JB = TN >= 2 ? 2 : 1, W = JB * 32;                        // column blocks turned around at a time (BN = 128: two halves)
-    constexpr int PITCH = W + 4, RPI = 64 / (W / 4);                        // floats per LDS row; rows per store instruction
-    static_assert(TN % JB == 0, "store scratch");
-    (void)scratch_bytes;
-    const int fr = lane & 31, fh2 = lane >> 5;
-    float* const blk = scratch + wid * 32 * PITCH;
-    const int rr = lane / (W / 4), cq = lane % (W / 4);
-#pragma unroll
-    for (int h = 0; h < TN / JB; ++h) {
-        wave_lds_order();                                                   // (the previous half's scratch reads lie above these writes)
-#pragma unroll
-        for (int jj = 0; jj < JB; ++jj)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const int j = h * JB + jj;
-                *reinterpret_cast<v4f*>(blk + fr * PITCH + jj * 32 + 8 * g + 4 * fh2) = v4f{acc[j][4 * g], acc[j][4 * g + 1], acc[j][4 * g + 2], acc[j][4 * g + 3]};
-            }
-        wave_lds_order();                                                   // (lane (rr, cq) reads rows other lanes wrote)
-        float* const obase = M + (size_t)(m0 + wid * 32 + rr) * N + n0 + h * W + 4 * cq;
-#pragma unroll
-        for (int i = 0; i < 32 / RPI; ++i)
-            *reinterpret_cast<v4f*>(obase + (size_t)i * RPI * N) = *reinterpret_cast<const v4f*>(blk + (rr + i * RPI) * PITCH + 4 * cq);
-    }
-}
-
 // Round 5 measured two more arrangements of this loop, both bit-identical and both SLOWER, neither kept in the tree: the next chunk's 8 (6)
 // LDS-DMA requests spread over the four k-steps between the MFMAs with the next step's fragments read a half-step ahead (GEMM sum of
 // IResNet-50 at B = 128: 3 189-3 227 us against 3 127-3 160 in the same runs), and several tiles per workgroup (wino_gemm_pers_kernel below).
@@ -521,7 +481,7 @@ __device__ unsigned long long g_wino_stamp[8 * 4096];
 extern "C" __attribute__((visibility("default"))) int fh_debug_wino_stamps(unsigned long long* host, int n) {
     return hipMemcpyFromSymbol(host, HIP_SYMBOL(g_wino_stamp), sizeof(unsigned long long) * (size_t)(n < 8 * 4096 ? n : 8 * 4096)) == hipSuccess ? 0 : -1;
 }
-#define WINO_STAMP(i) if (tid == 0 && blockIdx.x < 4096) g_wino_stamp[blockIdx.x * 8 + (i)] = __builtin_amdgcn_s_memrealtime()
+#define WINO_STAMP(i) if (threadIdx.x == 0 && blockIdx.x < 4096) g_wino_stamp[blockIdx.x * 8 + (i)] = __builtin_amdgcn_s_memrealtime()
 #else
 #define WINO_STAMP(i)
 #endif
@@ -530,107 +490,51 @@ extern "C" __attribute__((visibility("default"))) int fh_debug_wino_stamps(unsig
 // turn-around + stores 2.6 us; the second round starts at 35-44 us with a 4.7 us prologue and a 25.6 us K loop — a workgroup ALONE on its CU
 // does not run twice as fast (one wave per SIMD cannot cover its own chunk latency), which is why a half-tile start stagger of every CU's
 // second workgroup measured +-0 (3 125-3 149 us GEMM sum at 3-9 us of stagger against 3 149-3 158 without).
-// ABL (diagnostic instantiations only, results are garbage): 1 = no loads in the K loop (the first chunk is computed over and over),
-// 2 = no LDS reads (operands stay in registers), 4 = no barriers in the K loop, 8 = no stores, 16 = stores straight from registers
+// ABL (diagnostic instantiations only, results are garbage): bits 1 / 2 / 4 = the loop masks of gemm_chunk_f32 (no loads, no LDS reads, no
+// barriers in the K loop), 8 = no stores, 16 = stores straight from registers
 template <int BN, int OCC, int ABL = 0>
 __global__ __launch_bounds__(256, OCC) void wino_gemm_kernel(const float* __restrict__ V, const float* __restrict__ U, float* __restrict__ M,
                                                             const int K, const int N, const WinoPlanes pl, const long wt_gs,
                                                             const int tiles_n, const int chunks) {
-    constexpr int BM = 128, TN = BN / 32, AL = BM / 32, BL = BN / 32;
+    constexpr int BM = GEMM_BM, TN = BN / 32, JB = TN >= 2 ? 2 : 1;         // (stores: two 32-column blocks at a time; BN = 128: two halves)
     __shared__ v4f lds[2][(BM + BN) * 8];
-    const int tid = threadIdx.x, lane = tid & 63;
     WINO_STAMP(0);
-    const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int fr = lane & 31, fh2 = lane >> 5, fsw = (fr >> 1) & 7;
-    // XCD-contiguous tile order (blockIdx % 8 = XCD): the tiles_n workgroups that read the same rows share an L2
-    const int nb = gridDim.x, q = nb >> 3, r8 = nb & 7, x = blockIdx.x & 7;
-    const int tile = x * q + min(x, r8) + (blockIdx.x >> 3);
+    const GemmLane l = gemm_lane();
+    const int tile = xcd_tile(blockIdx.x, gridDim.x);                       // (the tiles_n workgroups that read the same rows share an L2)
     const int tile_n = tile % tiles_n, tile_m = tile / tiles_n;
     const int m0 = tile_m * BM, n0 = tile_n * BN;
     const float* Ug = U + (size_t)wino_plane_freq(pl, tile_m) * wt_gs;
-
-    const int lrow = tid >> 3;
-    const int lqs = (tid & 7) ^ ((lrow >> 1) & 7);              // source k-column of this lane (swizzle on the source side)
-    const float* a_src = V + (size_t)(m0 + lrow) * K + lqs * 4;
-    const float* b_src = Ug + (size_t)(n0 + lrow) * K + lqs * 4;
-    const size_t row32 = (size_t)32 * K;
-    v4f* const dstA = &lds[0][wid * 64];
-    v4f* const dstB = &lds[0][BM * 8 + wid * 64];
-    auto load_chunk = [&](int buf) {
-        v4f* const dA = dstA + buf * ((BM + BN) * 8);
-        v4f* const dB = dstB + buf * ((BM + BN) * 8);
-#pragma unroll
-        for (int i = 0; i < AL; ++i) wino_dma16(a_src + i * row32, dA + i * 32 * 8);
-#pragma unroll
-        for (int i = 0; i < BL; ++i) wino_dma16(b_src + i * row32, dB + i * 32 * 8);
-        a_src += 32; b_src += 32;
-    };
+    GemmSrc src = gemm_src<BN>(lds, V, m0, K, Ug, n0, K, l);
     v16f acc[TN];
 #pragma unroll
     for (int j = 0; j < TN; ++j)
 #pragma unroll
         for (int e = 0; e < 16; ++e) acc[j][e] = 0.f;
-    load_chunk(0);
+    gemm_load_chunk<BN>(src, 0);
     __syncthreads();
     WINO_STAMP(1);
-    v4f xk = v4f{0.f, 0.f, 0.f, 0.f}, wk[TN];
-    if constexpr ((ABL & 2) != 0) {
-        xk = lds[0][(wid * 32 + fr) * 8 + (fh2 ^ fsw)];
-#pragma unroll
-        for (int j = 0; j < TN; ++j) wk[j] = lds[0][BM * 8 + fr * 8 + j * 32 * 8 + (fh2 ^ fsw)];
-    }
-    for (int kc = 0; kc < chunks; ++kc) {
-        const int buf = (ABL & 1) ? 0 : (kc & 1);
-        if ((ABL & 1) == 0 && kc + 1 < chunks) load_chunk(buf ^ 1);
-        const v4f* X = lds[buf] + (wid * 32 + fr) * 8;
-        const v4f* Wt = lds[buf] + BM * 8 + fr * 8;
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            const int col = (2 * s + fh2) ^ fsw;
-            v4f xv;
-            v4f w[TN];
-            if constexpr ((ABL & 2) != 0) {
-                xv = xk;
-#pragma unroll
-                for (int j = 0; j < TN; ++j) w[j] = wk[j];
-#if defined(__HIP_DEVICE_COMPILE__)
-                asm volatile("" : "+v"(xv));                  // (opaque: the compiler must not fold the steps together)
-#endif
-            } else {
-                xv = X[col];
-#pragma unroll
-                for (int j = 0; j < TN; ++j) w[j] = Wt[j * 32 * 8 + col];
-            }
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-#pragma unroll
-                for (int j = 0; j < TN; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(w[j][e], xv[e], acc[j], 0, 0, 0);
-        }
-        if constexpr ((ABL & 4) == 0) __syncthreads();
-    }
+    GemmFrag<TN> held{};
+    if constexpr ((ABL & 2) != 0) held = gemm_frag<TN>(lds[0], l, 0);
+    for (int kc = 0; kc < chunks; ++kc) gemm_chunk_f32<BN, ABL & 7>(acc, lds, kc & 1, kc + 1 < chunks, src, l, true, nullptr, &held);
     WINO_STAMP(2);
     if constexpr ((ABL & 8) != 0) { if (acc[0][0] != 123.456f) return; }
-    // Stores.  A lane's accumulators are 4-column pieces of ITS row: stored straight from registers, one instruction writes 32 bytes to
-    // each of 32 rows (a quarter of a 128-byte line each, 8 instructions per row).  Instead the wave turns its 32 x BN block around in
-    // LDS (its own region of the tile buffers, which every wave has finished reading at the loop's last barrier; row pitch BN + 4 floats:
-    // the 16 lanes of a b128 phase hit 64 different banks) and stores whole rows: 64 / (BN / 4) rows x BN * 4 contiguous bytes per instruction.
     if constexpr ((ABL & 16) == 0) {
-        static_assert(4 * 32 * ((TN >= 2 ? 64 : 32) + 4) * sizeof(float) <= sizeof(lds), "store scratch");
-        wino_store_lines<TN>(acc, reinterpret_cast<float*>(&lds[0][0]), sizeof(lds), M, N, m0, n0, wid, lane);
+        static_assert(GemmStore<TN, JB>::BYTES <= sizeof(lds), "store scratch");
+        gemm_store_lines<TN, JB>(acc, reinterpret_cast<float*>(&lds[0][0]), M, N, m0, n0, l.wid, l.lane);
         WINO_STAMP(3);
 #ifdef FACEHIP_WINO_STAMP
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                    // (diagnostic: when the stores are acknowledged)
         WINO_STAMP(4);
-        if (tid == 0 && blockIdx.x < 4096) { g_wino_stamp[blockIdx.x * 8 + 5] = (unsigned long long)tile; g_wino_stamp[blockIdx.x * 8 + 6] = __builtin_amdgcn_s_getreg((3 << 11) | 20); }
+        if (l.tid == 0 && blockIdx.x < 4096) { g_wino_stamp[blockIdx.x * 8 + 5] = (unsigned long long)tile; g_wino_stamp[blockIdx.x * 8 + 6] = __builtin_amdgcn_s_getreg((3 << 11) | 20); }
 #endif
-        return;
+    } else {                                                                // a quarter of a 128-byte line per row and instruction (see gemm_store_lines)
+        float* orow = M + (size_t)(m0 + l.wid * 32 + l.fr) * N + n0 + 4 * l.fh2;
+#pragma unroll
+        for (int j = 0; j < TN; ++j)
+#pragma unroll
+            for (int g = 0; g < 4; ++g)
+                *reinterpret_cast<v4f*>(orow + j * 32 + 8 * g) = v4f{acc[j][4 * g], acc[j][4 * g + 1], acc[j][4 * g + 2], acc[j][4 * g + 3]};
     }
-    float* orow = M + (size_t)(m0 + wid * 32 + fr) * N + n0 + 4 * fh2;
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-        for (int g = 0; g < 4; ++g)
-            *reinterpret_cast<v4f*>(orow + j * 32 + 8 * g) = v4f{acc[j][4 * g], acc[j][4 * g + 1], acc[j][4 * g + 2], acc[j][4 * g + 3]};
 }
 
 // ---- the same GEMM with several tiles per workgroup (round 5) ------------------------------------------------------------------------
@@ -647,41 +551,25 @@ template <int BN, int OCC>
 __global__ __launch_bounds__(256, OCC) void wino_gemm_pers_kernel(const float* __restrict__ V, const float* __restrict__ U, float* __restrict__ M,
                                                                  const int K, const int N, const WinoPlanes pl, const long wt_gs,
                                                                  const int tiles_n, const int chunks, const int ntiles) {
-    constexpr int BM = 128, TN = BN / 32, AL = BM / 32, BL = BN / 32;
-    constexpr int BUF = (BM + BN) * 8;                                      // float4 slots per tile buffer
+    constexpr int BM = GEMM_BM, TN = BN / 32;
+    constexpr int BUF = gemm_buf_slots<BN>();
     __shared__ v4f lds[2][BUF];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int fr = lane & 31, fh2 = lane >> 5, fsw = (fr >> 1) & 7;
-    const int lrow = tid >> 3;
-    const int lqs = (tid & 7) ^ ((lrow >> 1) & 7);              // source k-column of this lane (swizzle on the source side)
-    const size_t row32 = (size_t)32 * K;
+    const GemmLane l = gemm_lane();
     // XCD-contiguous tile order over the VIRTUAL block index (gridDim.x is a multiple of 8: vb % 8 = this workgroup's XCD for every vb)
-    const int q = ntiles >> 3, r8 = ntiles & 7;
-    auto tile_of = [&](int vb) { const int x = vb & 7; return x * q + min(x, r8) + (vb >> 3); };
-    const float* a_src; const float* b_src;
+    auto tile_of = [&](int vb) { return xcd_tile(vb, ntiles); };
+    GemmSrc src;
     auto point_at = [&](int tile) {
         const int tile_n = tile % tiles_n, tile_m = tile / tiles_n;
         const float* Ug = U + (size_t)wino_plane_freq(pl, tile_m) * wt_gs;
-        a_src = V + (size_t)(tile_m * BM + lrow) * K + lqs * 4;
-        b_src = Ug + (size_t)(tile_n * BN + lrow) * K + lqs * 4;
+        src = gemm_src<BN>(lds, V, tile_m * BM, K, Ug, tile_n * BN, K, l);
     };
-    auto load_chunk = [&](int buf) {
-        v4f* const dA = &lds[0][wid * 64] + buf * BUF;
-        v4f* const dB = &lds[0][BM * 8 + wid * 64] + buf * BUF;
-#pragma unroll
-        for (int i = 0; i < AL; ++i) wino_dma16(a_src + i * row32, dA + i * 32 * 8);
-#pragma unroll
-        for (int i = 0; i < BL; ++i) wino_dma16(b_src + i * row32, dB + i * 32 * 8);
-        a_src += 32; b_src += 32;
-    };
-    constexpr int JB = 1, W = JB * 32, PITCH = W + 4, RPI = 64 / (W / 4);    // turn-around in 32-column blocks: 4 waves x 32 x 36 floats = 18 KB <= one buffer
-    static_assert(4 * 32 * PITCH * sizeof(float) <= BUF * sizeof(v4f), "store scratch must fit ONE tile buffer");
-    constexpr int NSTORE = TN * (32 / RPI);                                 // global store instructions per wave and tile
+    // turn-around in 32-column blocks: 4 waves x 32 x 36 floats = 18 KB <= one buffer
+    using Store = GemmStore<TN, 1>;
+    static_assert(Store::BYTES <= BUF * sizeof(v4f), "store scratch must fit ONE tile buffer");
     int base = 0;                                                           // buffer that holds the current tile's chunk 0
     int vb = blockIdx.x;
     point_at(tile_of(vb));
-    load_chunk(0);
+    gemm_load_chunk<BN>(src, 0);
     __syncthreads();
     for (;;) {
         const int tile = tile_of(vb);
@@ -691,135 +579,60 @@ __global__ __launch_bounds__(256, OCC) void wino_gemm_pers_kernel(const float* _
         for (int j = 0; j < TN; ++j)
 #pragma unroll
             for (int e = 0; e < 16; ++e) acc[j][e] = 0.f;
-        for (int kc = 0; kc < chunks; ++kc) {
-            const int buf = (base + kc) & 1;
-            if (kc + 1 < chunks) load_chunk(buf ^ 1);
-            const v4f* X = lds[buf] + (wid * 32 + fr) * 8;
-            const v4f* Wt = lds[buf] + BM * 8 + fr * 8;
-#pragma unroll
-            for (int s4 = 0; s4 < 4; ++s4) {
-                const int col = (2 * s4 + fh2) ^ fsw;
-                const v4f xv = X[col];
-                v4f w[TN];
-#pragma unroll
-                for (int j = 0; j < TN; ++j) w[j] = Wt[j * 32 * 8 + col];
-#pragma unroll
-                for (int e = 0; e < 4; ++e)
-#pragma unroll
-                    for (int j = 0; j < TN; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(w[j][e], xv[e], acc[j], 0, 0, 0);
-            }
-            __syncthreads();
-        }
+        for (int kc = 0; kc < chunks; ++kc) gemm_chunk_f32<BN>(acc, lds, (base + kc) & 1, kc + 1 < chunks, src, l);
         // every wave is past the last chunk: both buffers are free.  last = the buffer of the final chunk -> scratch; the other -> next tile
         const int last = (base + chunks - 1) & 1;
         const int nvb = vb + gridDim.x;
         const bool more = nvb < ntiles;
         if (more) {
             point_at(tile_of(nvb));
-            load_chunk(last ^ 1);
+            gemm_load_chunk<BN>(src, last ^ 1);
 #if defined(__HIP_DEVICE_COMPILE__)
             __builtin_amdgcn_sched_barrier(0);                              // (the DMA is issued in front of the stores it is counted against)
 #endif
         }
-        {
-            float* const blk = reinterpret_cast<float*>(&lds[last][0]) + wid * 32 * PITCH;
-            const int rr = lane / (W / 4), cq = lane % (W / 4);
-#pragma unroll
-            for (int j = 0; j < TN; ++j) {
-                wave_lds_order();
-#pragma unroll
-                for (int g = 0; g < 4; ++g)
-                    *reinterpret_cast<v4f*>(blk + fr * PITCH + 8 * g + 4 * fh2) = v4f{acc[j][4 * g], acc[j][4 * g + 1], acc[j][4 * g + 2], acc[j][4 * g + 3]};
-                wave_lds_order();
-                float* const obase = M + (size_t)(m0 + wid * 32 + rr) * N + n0 + j * W + 4 * cq;
-#pragma unroll
-                for (int i = 0; i < 32 / RPI; ++i)
-                    *reinterpret_cast<v4f*>(obase + (size_t)i * RPI * N) = *reinterpret_cast<const v4f*>(blk + (rr + i * RPI) * PITCH + 4 * cq);
-            }
-        }
+        gemm_store_lines<TN, 1>(acc, reinterpret_cast<float*>(&lds[last][0]), M, N, m0, n0, l.wid, l.lane);
         if (!more) break;
         vb = nvb; base = last ^ 1;
 #if defined(__HIP_DEVICE_COMPILE__)
-        // the next tile's chunk 0 has landed once all but the NSTORE youngest vector-memory operations (this tile's stores) are done
-        asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(NSTORE) : "memory");
+        // the next tile's chunk 0 has landed once all but the youngest vector-memory operations — this tile's Store::NSTORE stores — are done
+        asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(Store::NSTORE) : "memory");
         __builtin_amdgcn_s_barrier();
         __builtin_amdgcn_sched_barrier(0);
 #endif
     }
 }
 
-// Split-bf16 form of the same GEMM (opt-in precision mode): V and U hold (hi, mid) bf16 pairs in 32-bit words, everything up to the
-// fragment reads is byte-for-byte the f32 kernel.  A lane takes 8 consecutive k of its row per 16-deep MFMA step (two ds_read_b128),
-// separates the hi and the mid halves with v_perm_b32 and issues v_mfma_f32_32x32x16_bf16 three times: mid*hi + hi*mid + hi*hi
-// (the dropped mid*mid term is 2^-32 relative).  5x less matrix-core time per FLOP than v_mfma_f32_32x32x2_f32; the kernel is then bound
+// Split-bf16 form of the same GEMM (opt-in precision mode): V and U hold (hi, mid) bf16 pairs in 32-bit words, everything but the MMA
+// step (gemm_mma_bf16x2) is the f32 kernel.  5x less matrix-core time per FLOP than v_mfma_f32_32x32x2_f32; the kernel is then bound
 // by the L2 -> LDS stream it shares with the f32 form.
 template <int BN, int OCC>
 __global__ __launch_bounds__(256, OCC) void wino_gemm_bf16x2_kernel(const float* __restrict__ V, const float* __restrict__ U, float* __restrict__ M,
                                                                    const int K, const int N, const WinoPlanes pl, const long wt_gs,
                                                                    const int tiles_n, const int chunks) {
-    constexpr int BM = 128, TN = BN / 32, AL = BM / 32, BL = BN / 32;
+    constexpr int BM = GEMM_BM, TN = BN / 32, JB = TN >= 2 ? 2 : 1;
     __shared__ v4f lds[2][(BM + BN) * 8];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int fr = lane & 31, fh2 = lane >> 5, fsw = (fr >> 1) & 7;
-    const int nb = gridDim.x, q = nb >> 3, r8 = nb & 7, x = blockIdx.x & 7;
-    const int tile = x * q + min(x, r8) + (blockIdx.x >> 3);
+    const GemmLane l = gemm_lane();
+    const int tile = xcd_tile(blockIdx.x, gridDim.x);
     const int tile_n = tile % tiles_n, tile_m = tile / tiles_n;
     const int m0 = tile_m * BM, n0 = tile_n * BN;
     const float* Ug = U + (size_t)wino_plane_freq(pl, tile_m) * wt_gs;
-    const int lrow = tid >> 3;
-    const int lqs = (tid & 7) ^ ((lrow >> 1) & 7);
-    const float* a_src = V + (size_t)(m0 + lrow) * K + lqs * 4;
-    const float* b_src = Ug + (size_t)(n0 + lrow) * K + lqs * 4;
-    const size_t row32 = (size_t)32 * K;
-    v4f* const dstA = &lds[0][wid * 64];
-    v4f* const dstB = &lds[0][BM * 8 + wid * 64];
-    auto load_chunk = [&](int buf) {
-        v4f* const dA = dstA + buf * ((BM + BN) * 8);
-        v4f* const dB = dstB + buf * ((BM + BN) * 8);
-#pragma unroll
-        for (int i = 0; i < AL; ++i) wino_dma16(a_src + i * row32, dA + i * 32 * 8);
-#pragma unroll
-        for (int i = 0; i < BL; ++i) wino_dma16(b_src + i * row32, dB + i * 32 * 8);
-        a_src += 32; b_src += 32;
-    };
-    auto split = [](const v4u lo4, const v4u hi4, bf16x8& h, bf16x8& m) {       // 8 packed words -> 8 hi halves, 8 mid halves
-        const v4u hh = {__builtin_amdgcn_perm(lo4[1], lo4[0], 0x05040100u), __builtin_amdgcn_perm(lo4[3], lo4[2], 0x05040100u),
-                        __builtin_amdgcn_perm(hi4[1], hi4[0], 0x05040100u), __builtin_amdgcn_perm(hi4[3], hi4[2], 0x05040100u)};
-        const v4u mm = {__builtin_amdgcn_perm(lo4[1], lo4[0], 0x07060302u), __builtin_amdgcn_perm(lo4[3], lo4[2], 0x07060302u),
-                        __builtin_amdgcn_perm(hi4[1], hi4[0], 0x07060302u), __builtin_amdgcn_perm(hi4[3], hi4[2], 0x07060302u)};
-        h = __builtin_bit_cast(bf16x8, hh); m = __builtin_bit_cast(bf16x8, mm);
-    };
+    GemmSrc src = gemm_src<BN>(lds, V, m0, K, Ug, n0, K, l);
     v16f acc[TN];
 #pragma unroll
     for (int j = 0; j < TN; ++j)
 #pragma unroll
         for (int e = 0; e < 16; ++e) acc[j][e] = 0.f;
-    load_chunk(0);
+    gemm_load_chunk<BN>(src, 0);
     __syncthreads();
     for (int kc = 0; kc < chunks; ++kc) {
         const int buf = kc & 1;
-        if (kc + 1 < chunks) load_chunk(buf ^ 1);
-        const v4u* X = reinterpret_cast<const v4u*>(lds[buf]) + (wid * 32 + fr) * 8;
-        const v4u* Wt = reinterpret_cast<const v4u*>(lds[buf]) + BM * 8 + fr * 8;
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {                             // two 16-deep steps per 32-deep chunk; lane half fh2 owns k = 8*fh2 .. 8*fh2+7
-            const int c0 = (4 * ks + 2 * fh2) ^ fsw, c1 = (4 * ks + 2 * fh2 + 1) ^ fsw;
-            bf16x8 xh, xm;
-            split(X[c0], X[c1], xh, xm);
-#pragma unroll
-            for (int j = 0; j < TN; ++j) {
-                bf16x8 wh, wm;
-                split(Wt[j * 32 * 8 + c0], Wt[j * 32 * 8 + c1], wh, wm);
-                acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wm, xh, acc[j], 0, 0, 0);
-                acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh, xm, acc[j], 0, 0, 0);
-                acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh, xh, acc[j], 0, 0, 0);
-            }
-        }
+        if (kc + 1 < chunks) gemm_load_chunk<BN>(src, buf ^ 1);
+        gemm_mma_bf16x2<TN>(acc, lds[buf], l);
         __syncthreads();
     }
-    static_assert(4 * 32 * ((TN >= 2 ? 64 : 32) + 4) * sizeof(float) <= sizeof(lds), "store scratch");
-    wino_store_lines<TN>(acc, reinterpret_cast<float*>(&lds[0][0]), sizeof(lds), M, N, m0, n0, wid, lane);
+    static_assert(GemmStore<TN, JB>::BYTES <= sizeof(lds), "store scratch");
+    gemm_store_lines<TN, JB>(acc, reinterpret_cast<float*>(&lds[0][0]), M, N, m0, n0, l.wid, l.lane);
 }
 
 long wino_rows(long tiles) { return (tiles + 255) / 256 * 256; }   // rows of one frequency plane: whole tiles of every GEMM configuration
@@ -959,42 +772,40 @@ void launch_wino_gemm(const ConvArgs& a, const float* wt36, const float* V, floa
     }
     if (a.Cout % 32 == 0 && cfg == 2) {
         // the lean kernel: 128 x 64 tiles (IResNet-50 at B = 128 / 256: 9.89 / 19.5 ms; 128 x 32: 9.96 / 19.8; 128 x 128: 10.2 / 19.6)
-        const long rows = 128L * pl.total_tiles;
+        const long row_tiles = pl.total_tiles;
         const int chunks = a.Cin / 32;
         const bool wide = a.Cout % 64 == 0;
+        // one workgroup per 128 x BN tile — or, for the multi-tile form, one per slot when it is switched on and the launch has more tiles than slots
+        using TileKernel = void (*)(const float*, const float*, float*, int, int, WinoPlanes, long, int, int);
+        auto launch = [&](TileKernel kernel, int BN) {
+            hipLaunchKernelGGL(kernel, dim3((unsigned)(row_tiles * (a.Cout / BN))), dim3(256), 0, s, V, wt36, M, a.Cin, a.Cout, pl, g.wt_gs, a.Cout / BN, chunks);
+        };
+        auto launch_pers = [&](auto kernel, int BN, int OCC) {                  // false = not launched
+            const long nt = row_tiles * (a.Cout / BN), slots = wino_slots(OCC, a.cus);
+            if (!wino_pers_enabled() || nt <= slots) return false;
+            hipLaunchKernelGGL(kernel, dim3((unsigned)slots), dim3(256), 0, s, V, wt36, M, a.Cin, a.Cout, pl, g.wt_gs, a.Cout / BN, chunks, (int)nt);
+            return true;
+        };
         timer.begin(s);
         if (bf16x2) {
             if (!wino_gemm_ok_bf16x2(a.Cin, a.Cout)) throw std::runtime_error("winograd: this layer has no split-bf16 GEMM");
-            hipLaunchKernelGGL((wino_gemm_bf16x2_kernel<64, 3>), dim3((unsigned)((rows / 128) * (a.Cout / 64))), dim3(256), 0, s, V, wt36, M, a.Cin,
-                               a.Cout, pl, g.wt_gs, a.Cout / 64, chunks);
-        } else if (wide && a.Cout % 128 == 0 && wino_pick_bn128(rows / 128, a.Cout, mix != nullptr, a.cus)) {
-            const long nt = (rows / 128) * (a.Cout / 128), slots = wino_slots(2, a.cus);
-            if (wino_pers_enabled() && nt > slots)
-                hipLaunchKernelGGL((wino_gemm_pers_kernel<128, 2>), dim3((unsigned)slots), dim3(256), 0, s, V, wt36, M, a.Cin, a.Cout, pl, g.wt_gs,
-                                   a.Cout / 128, chunks, (int)nt);
-            else
-                hipLaunchKernelGGL((wino_gemm_kernel<128, 2>), dim3((unsigned)nt), dim3(256), 0, s, V, wt36, M, a.Cin, a.Cout, pl, g.wt_gs, a.Cout / 128,
-                                   chunks);
-        } else if (wide && wino_pers_enabled() && (rows / 128) * (a.Cout / 64) > wino_slots(3, a.cus)) {
-            const long nt = (rows / 128) * (a.Cout / 64), slots = wino_slots(3, a.cus);
-            hipLaunchKernelGGL((wino_gemm_pers_kernel<64, 3>), dim3((unsigned)slots), dim3(256), 0, s, V, wt36, M, a.Cin, a.Cout, pl, g.wt_gs, a.Cout / 64,
-                               chunks, (int)nt);
+            launch(wino_gemm_bf16x2_kernel<64, 3>, 64);
+        } else if (wide && a.Cout % 128 == 0 && wino_pick_bn128(row_tiles, a.Cout, mix != nullptr, a.cus)) {
+            if (!launch_pers(wino_gemm_pers_kernel<128, 2>, 128, 2)) launch(wino_gemm_kernel<128, 2>, 128);
         } else if (wide) {
+            if (!launch_pers(wino_gemm_pers_kernel<64, 3>, 64, 3)) {
 #ifdef FACEHIP_WINO_ABL
-            static const int abl = [] { const char* e = getenv("FACEHIP_WINO_ABL"); return e ? atoi(e) : 0; }();
-            const dim3 grid((unsigned)((rows / 128) * (a.Cout / 64)));
-#define WABL(X) case X: hipLaunchKernelGGL((wino_gemm_kernel<64, 3, X>), grid, dim3(256), 0, s, V, wt36, M, a.Cin, a.Cout, pl, g.wt_gs, a.Cout / 64, chunks); break;
-            switch (abl) { WABL(1) WABL(2) WABL(3) WABL(4) WABL(5) WABL(6) WABL(7) WABL(8) WABL(15) WABL(16) WABL(17) WABL(24)
-                default: hipLaunchKernelGGL((wino_gemm_kernel<64, 3>), grid, dim3(256), 0, s, V, wt36, M, a.Cin, a.Cout, pl, g.wt_gs, a.Cout / 64, chunks); }
+                static const int abl = [] { const char* e = getenv("FACEHIP_WINO_ABL"); return e ? atoi(e) : 0; }();
+#define WABL(X) case X: launch(wino_gemm_kernel<64, 3, X>, 64); break;
+                switch (abl) { WABL(1) WABL(2) WABL(3) WABL(4) WABL(5) WABL(6) WABL(7) WABL(8) WABL(15) WABL(16) WABL(17) WABL(24)
+                    default: launch(wino_gemm_kernel<64, 3>, 64); }
 #undef WABL
 #else
-            hipLaunchKernelGGL((wino_gemm_kernel<64, 3>), dim3((unsigned)((rows / 128) * (a.Cout / 64))), dim3(256), 0, s, V, wt36, M, a.Cin, a.Cout,
-                                   pl, g.wt_gs, a.Cout / 64, chunks);
+                launch(wino_gemm_kernel<64, 3>, 64);
 #endif
-        }
-        else
-            hipLaunchKernelGGL((wino_gemm_kernel<32, 4>), dim3((unsigned)((rows / 128) * (a.Cout / 32))), dim3(256), 0, s, V, wt36, M, a.Cin, a.Cout,
-                               pl, g.wt_gs, a.Cout / 32, chunks);
+            }
+        } else
+            launch(wino_gemm_kernel<32, 4>, 32);
         timer.end(s, 7, g.t_flops, g.t_bytes);
     } else {
         if (bf16x2) throw std::runtime_error("winograd: this layer has no split-bf16 GEMM");

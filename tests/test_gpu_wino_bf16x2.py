@@ -25,7 +25,7 @@ from facerecognizeonnx_amd.synth import models  # noqa: E402
 from oracle import onnx_min, oracle, torch_graph  # noqa: E402
 from tests import util                        # noqa: E402
 from tests import wino_split_model as wm      # noqa: E402
-from tests.test_gpu_parity import dev         # noqa: E402
+from tests.test_gpu_parity import dev, pack_weights  # noqa: E402
 
 NAN = np.float32("nan")
 
@@ -202,6 +202,31 @@ def test_gemm_dense_within_derived_bound(K, N, tiles):
 def test_gemm_dense_within_derived_bound_mixed_layout():
     B, H, W, K, N = MIXED
     _dense_case(B, H, W, K, N, 1, True)
+
+
+@pytest.mark.parametrize("K", (32, 160))
+def test_conv_pw_and_wino_gemm_give_one_bit_pattern(K):
+    """conv_pw_kernel and wino_gemm_kernel run the same tile body (gemm_tile.h) and add every output's products in the same order: with
+    K % 32 == 0, no bias and no activation, a 1x1 convolution over 9216 rows is the GEMM of the uniform Winograd layout of 256 tiles
+    (36 planes x 256 rows) whose 36 frequencies all carry the same weight matrix.  K = 32 is one chunk, 160 an odd number of chunks;
+    B = 36 maps of 16 x 16 give 72 x 4 tiles of 128 x 64, at least one per CU, so the convolution takes conv_pw_kernel.  Equality of
+    VALUES: the epilogue's + 0 may turn a -0 into +0."""
+    N, tiles = 256, 256
+    rng = np.random.default_rng(7000 + K)
+    V = rng.standard_normal((36 * tiles, K)).astype(np.float32)
+    Wm = (rng.standard_normal((N, K)) / np.sqrt(K)).astype(np.float32)
+    wino = _gemm_gpu(V, np.broadcast_to(Wm, (36, N, K)), tiles, 4, 4, K, N, 0, 0)
+    wp, kpad = pack_weights(Wm[:, :, None, None])
+    assert kpad == K
+    xd, wd = dev(V), dev(wp)
+    out = torch.full((36 * tiles, N), float("nan"), device="cuda")
+    rc = fa.lib().fh_conv_forward_dev(xd.data_ptr(), wd.data_ptr(), None, out.data_ptr(), 36, 16, 16, K, N, 1, 1, kpad, -1, 0)
+    assert rc == 0, _lib.last_error()
+    torch.cuda.synchronize()
+    conv = out.cpu().numpy()
+    assert np.isfinite(wino).all() and np.abs(wino).max() > 1.0
+    bad = np.argwhere(conv != wino)
+    assert np.array_equal(conv, wino), (len(bad), bad[:4], conv[tuple(bad[0])], wino[tuple(bad[0])])
 
 
 def test_gemm_hook_checks_its_arguments():
