@@ -25,6 +25,11 @@ class FhFace(C.Structure):
                 ("score", C.c_float), ("lm", C.c_float * 10)]
 
 
+class FhFrame(C.Structure):
+    """fh_frame: one image of a mixed-size batch (device pixels; host pixels for fh_pipeline_run_images).  24 bytes."""
+    _fields_ = [("bgr", C.c_void_p), ("rows", C.c_int32), ("cols", C.c_int32), ("step", C.c_int32)]
+
+
 def build(force: bool = False) -> str:
     """Compile libfacehip.so in-tree (so that it travels with the source snapshot)."""
     srcs = [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [os.path.join(_HERE, "..", "include", "facehip.h")]
@@ -88,6 +93,14 @@ PROTOTYPES = {
     "fh_rec_embed_faces_dev": (_i, [_vp, _vp, _i, _i, _i, _ll, _vp, _vp, _i, _vp, _vp, _vp]),
     "fh_pipeline_run_dev": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _ll, _f, _f, _i, _vp, _vp, _vp, _vp]),
     "fh_pipeline_submit_dev": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _ll, _f, _f, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "fh_letterbox_plan": (_i, [_i, _i, _i, _i, _ip, _ip, C.POINTER(C.c_float)]),
+    "fh_det_letterbox_ragged_dev": (_i, [_vp, _vp, _i, _vp, _vp]),
+    "fh_det_run_network_ragged_dev": (_i, [_vp, _vp, _i, _vp]),
+    "fh_det_detect_ragged_dev": (_i, [_vp, _vp, _i, _f, _f, _vp, _i, _vp, _vp]),
+    "fh_rec_align_ragged_dev": (_i, [_vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp]),
+    "fh_rec_embed_faces_ragged_dev": (_i, [_vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp]),
+    "fh_pipeline_run_ragged_dev": (_i, [_vp, _vp, _vp, _i, _f, _f, _i, _vp, _vp, _vp, _vp]),
+    "fh_pipeline_run_images": (_i, [_vp, _vp, _vp, _i, _f, _f, _i, _vp, _vp, _vp, _i]),
     "fh_stream_create": (_vp, [_vp, _vp, _i, _i, _i, _i]),
     "fh_stream_destroy": (None, [_vp]),
     "fh_stream_submit": (_i, [_vp, _vp, _i, _f, _f]),

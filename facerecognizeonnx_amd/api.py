@@ -55,6 +55,35 @@ def _img(image) -> Optional[np.ndarray]:
     return a
 
 
+def frame_array(frames):
+    """A ctypes array of fh_frame from an iterable of (ptr, rows, cols[, step]) — ptr an int device (or host) address, step defaulting
+    to cols * 3; None or a zero ptr / size is an empty frame.  A ready-made ``(FhFrame * n)`` array passes through."""
+    if isinstance(frames, C.Array) and getattr(frames, "_type_", None) is _lib.FhFrame:
+        return frames
+    frames = list(frames)
+    arr = (_lib.FhFrame * max(len(frames), 1))()
+    for i, f in enumerate(frames):
+        if f is None:
+            continue
+        ptr, rows, cols = f[0], int(f[1]), int(f[2])
+        step = int(f[3]) if len(f) > 3 and f[3] else cols * 3
+        arr[i].bgr, arr[i].rows, arr[i].cols, arr[i].step = (int(ptr) or None), rows, cols, step
+    arr._n = len(frames)
+    return arr
+
+
+def _frame_count(arr) -> int:
+    return getattr(arr, "_n", len(arr))
+
+
+def letterbox_plan(rows: int, cols: int, in_w: int, in_h: int):
+    """FaceDetector::preprocess' letterbox arithmetic (face_detector.cpp:101-113) as the detector does it (fh_letterbox_plan, host
+    code): returns (live, new_w, new_h, scale); a dead frame (empty image or "Invalid resize dimensions") is (False, 0, 0, 0.0)."""
+    nw, nh, sc = C.c_int(), C.c_int(), C.c_float()
+    live = _lib.lib().fh_letterbox_plan(int(rows), int(cols), int(in_w), int(in_h), C.byref(nw), C.byref(nh), C.byref(sc))
+    return bool(live), nw.value, nh.value, float(sc.value)
+
+
 class FaceDetector:
     def __init__(self):
         self._h = None
@@ -114,6 +143,14 @@ class FaceDetector:
         return check(_lib.lib().fh_det_detect_batch_dev(self._h, frames_ptr, n, rows, cols, step, frame_stride,
                                                         scoreThreshold, nmsThreshold, out_ptr, max_per_frame,
                                                         counts_ptr, stream), "fh_det_detect_batch_dev")
+
+    def detect_ragged_dev(self, frames, out_ptr: int, max_per_frame: int, counts_ptr: int, scoreThreshold: float = 0.5,
+                          nmsThreshold: float = 0.4, stream: int = 0) -> int:
+        """detect on frames of ANY sizes in one call (fh_det_detect_ragged_dev): frames = iterable of (device ptr, rows, cols[, step])
+        or an fh_frame array (frame_array); out / counts as detect_batch_dev.  Empty frames count 0."""
+        arr = frame_array(frames)
+        return check(_lib.lib().fh_det_detect_ragged_dev(self._h, arr, _frame_count(arr), scoreThreshold, nmsThreshold, out_ptr,
+                                                         max_per_frame, counts_ptr, stream), "fh_det_detect_ragged_dev")
 
     def sync(self, stream: int = 0) -> None:
         """Waits for `stream`; raises if a launch of this handle failed after its asynchronous call returned (fh_det_sync)."""
@@ -215,6 +252,37 @@ def pipeline_run_dev(det: FaceDetector, rec: FaceRecognizer, frames_ptr: int, n:
     return check(_lib.lib().fh_pipeline_run_dev(det.handle, rec.handle, frames_ptr, n, rows, cols, step, rows * step,
                                                 scoreThreshold, nmsThreshold, faces_per_frame, faces_ptr,
                                                 frame_of_ptr, emb_ptr, stream), "fh_pipeline_run_dev")
+
+
+def pipeline_run_ragged_dev(det: FaceDetector, rec: FaceRecognizer, frames, faces_per_frame: int, faces_ptr: int, frame_of_ptr: int,
+                            emb_ptr: int, scoreThreshold: float = 0.5, nmsThreshold: float = 0.4, stream: int = 0) -> int:
+    """pipeline_run_dev on HBM-resident frames of any sizes (fh_pipeline_run_ragged_dev); frames as FaceDetector.detect_ragged_dev.
+    The output buffers hold len(frames) * faces_per_frame entries; returns the number of faces embedded."""
+    arr = frame_array(frames)
+    return check(_lib.lib().fh_pipeline_run_ragged_dev(det.handle, rec.handle, arr, _frame_count(arr), scoreThreshold, nmsThreshold,
+                                                       faces_per_frame, faces_ptr, frame_of_ptr, emb_ptr, stream),
+                 "fh_pipeline_run_ragged_dev")
+
+
+def pipeline_images(det: FaceDetector, rec: FaceRecognizer, images, faces_per_frame: int = 1, scoreThreshold: float = 0.5,
+                    nmsThreshold: float = 0.4, cap: Optional[int] = None):
+    """The enrolment loop over decoded photographs (main.cpp:42,88-104: imread, detect, extractFeature per file) as ONE call:
+    images = list of uint8[rows, cols, 3] BGR arrays of any sizes (None / empty = no image).  Returns (faces: FACE_DTYPE[m],
+    frame_of: int32[m], emb: float32[m][dim]) with m = the total number of faces (the first min(count, faces_per_frame) of every
+    image, in image order), or the first `cap` of them when cap is given."""
+    imgs = [_img(im) for im in images]
+    n = len(imgs)
+    dim = rec.feature_dim()
+    if n == 0:
+        return np.zeros(0, FACE_DTYPE), np.zeros(0, np.int32), np.zeros((0, dim), np.float32)
+    arr = frame_array([None if a is None else (a.ctypes.data, a.shape[0], a.shape[1], a.strides[0]) for a in imgs])
+    room = n * faces_per_frame if cap is None else max(int(cap), 0)
+    faces = np.zeros(max(room, 1), FACE_DTYPE); frame_of = np.zeros(max(room, 1), np.int32); emb = np.zeros((max(room, 1), dim), np.float32)
+    total = check(_lib.lib().fh_pipeline_run_images(det.handle, rec.handle, arr, n, scoreThreshold, nmsThreshold, faces_per_frame,
+                                                    faces.ctypes.data, frame_of.ctypes.data, emb.ctypes.data, room),
+                  "fh_pipeline_run_images")
+    m = min(total, room)
+    return faces[:m].copy(), frame_of[:m].copy(), emb[:m].copy()
 
 
 def pipeline_submit_dev(det: FaceDetector, rec: FaceRecognizer, frames_ptr: int, n: int, rows: int, cols: int,

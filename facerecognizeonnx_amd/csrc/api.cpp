@@ -1,5 +1,6 @@
 // api.cpp — the extern "C" boundary declared in include/facehip.h.
 #include <algorithm>
+#include <cstddef>
 #include <cstdio>
 #include <cstring>
 #include <memory>
@@ -10,6 +11,8 @@
 #include "engine.h"
 
 static_assert(sizeof(fh_face) == 60 && sizeof(fh::FaceRec) == 60, "FaceBox mirror must stay 60 bytes");
+static_assert(sizeof(fh_frame) == 24 && sizeof(fh::FrameIn) == 24 && offsetof(fh_frame, rows) == offsetof(fh::FrameIn, rows) &&
+              offsetof(fh_frame, step) == offsetof(fh::FrameIn, step), "fh_frame and the engine's FrameIn are one layout");
 
 namespace {
 thread_local std::string g_err;
@@ -49,6 +52,19 @@ int arg_error(const char* msg) { g_err = msg; return FH_ERR_ARG; }
 // cols*3 bytes, not after a whole pitch
 size_t host_image_bytes(int rows, int cols, int step) { return (size_t)(rows - 1) * step + (size_t)cols * 3; }
 hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); }
+// the descriptor array of a ragged entry point: 1 <= n <= 4096, and a non-empty frame's pitch holds its row (empty frames — the
+// reference's empty image, src/face_detector.cpp:148-156 — are legal: they yield nothing).  Null on success, else the complaint.
+const char* bad_frames(const fh_frame* frames, int n) {
+    if (!frames) return "null frame descriptors";
+    if (n <= 0 || n > 4096) return "need 1 <= n <= 4096 frames";
+    for (int i = 0; i < n; ++i) {
+        const fh_frame& f = frames[i];
+        if (f.bgr && f.rows > 0 && f.cols > 0 && (long long)f.step < (long long)f.cols * 3) return "a frame's step is smaller than cols * 3";
+    }
+    return nullptr;
+}
+int frames_error(const char* fn, const char* what) { g_err = std::string(fn) + ": " + what; return FH_ERR_ARG; }
+const fh::FrameIn* FI(const fh_frame* f) { return reinterpret_cast<const fh::FrameIn*>(f); }
 }  // namespace
 
 namespace fh {
@@ -138,6 +154,8 @@ struct fh_det {
     fh::DevBuf p_det, p_cnt, p_total;    // pipeline scratch
     hipEvent_t ev_sel = nullptr;         // detect -> embed hand-off (face count known / stream_rec may start)
     int* h_total = nullptr;              // pinned landing word of the face count
+    PinnedBuf h_arena;                   // fh_pipeline_run_images: the live images packed row by row / their device copy / device results
+    fh::DevBuf arena, i_faces, i_fo, i_emb;
     ~fh_det() { if (ev_sel) (void)hipEventDestroy(ev_sel); if (h_total) (void)hipHostFree(h_total); }
 };
 struct fh_rec {
@@ -248,6 +266,35 @@ int fh_det_detect_batch_dev(fh_det* d, const uint8_t* frames, int n, int rows, i
     return guarded([&] {
         d->det.detect_dev(frames, n, rows, cols, step, (long)stride, score_thr, nms_thr, reinterpret_cast<fh::FaceRec*>(out), max_pf,
                           counts, S(stream));
+        return n;
+    });
+}
+
+// ---------------------------------------------------------------------------------- mixed-size batches (detector side)
+int fh_letterbox_plan(int rows, int cols, int in_w, int in_h, int* new_w, int* new_h, float* scale) {
+    return fh::letterbox_plan(rows, cols, in_w, in_h, new_w, new_h, scale);              // src/face_detector.cpp:94-113
+}
+int fh_det_letterbox_ragged_dev(fh_det* d, const fh_frame* frames, int n, uint8_t* canvas, void* stream) {
+    if (!d || !canvas) return arg_error("fh_det_letterbox_ragged_dev: null argument");
+    if (const char* bad = bad_frames(frames, n)) return frames_error("fh_det_letterbox_ragged_dev", bad);
+    if (reinterpret_cast<uintptr_t>(canvas) & 3) return arg_error("fh_det_letterbox_ragged_dev: the canvas must be 4-byte aligned");
+    Owns owns(&d->det.net());
+    return guarded([&] { d->det.letterbox_ragged_dev(FI(frames), n, canvas, S(stream)); return n; });
+}
+int fh_det_run_network_ragged_dev(fh_det* d, const fh_frame* frames, int n, void* stream) {
+    if (!d) return arg_error("fh_det_run_network_ragged_dev: null handle");
+    if (const char* bad = bad_frames(frames, n)) return frames_error("fh_det_run_network_ragged_dev", bad);
+    Owns owns(&d->det.net());
+    return guarded([&] { d->det.run_network_ragged_dev(FI(frames), n, S(stream)); return n; });
+}
+int fh_det_detect_ragged_dev(fh_det* d, const fh_frame* frames, int n, float score_thr, float nms_thr, fh_face* out, int max_pf,
+                             int* counts, void* stream) {
+    if (!d || !out || !counts) return arg_error("fh_det_detect_ragged_dev: null argument");
+    if (const char* bad = bad_frames(frames, n)) return frames_error("fh_det_detect_ragged_dev", bad);
+    if (max_pf <= 0) return arg_error("fh_det_detect_ragged_dev: bad size");
+    Owns owns(&d->det.net());
+    return guarded([&] {
+        d->det.detect_ragged_dev(FI(frames), n, score_thr, nms_thr, reinterpret_cast<fh::FaceRec*>(out), max_pf, counts, S(stream));
         return n;
     });
 }
@@ -432,6 +479,29 @@ int fh_rec_embed_faces_dev(fh_rec* r, const uint8_t* frames, int rows, int cols,
     });
 }
 
+int fh_rec_align_ragged_dev(fh_rec* r, const fh_frame* frames, int n_frames, const fh_face* faces, const int* frame_of, int n,
+                            uint8_t* crops, int* ok, void* stream) {
+    if (!r || !faces || !crops || !ok) return arg_error("fh_rec_align_ragged_dev: null argument");
+    if (const char* bad = bad_frames(frames, n_frames)) return frames_error("fh_rec_align_ragged_dev", bad);
+    if (n <= 0 || (!frame_of && n > n_frames)) return arg_error("fh_rec_align_ragged_dev: bad size");
+    Owns owns(&r->rec.net());
+    return guarded([&] {
+        r->rec.align_ragged_dev(FI(frames), n_frames, reinterpret_cast<const fh::FaceRec*>(faces), frame_of, n, crops, ok, S(stream));
+        return n;
+    });
+}
+int fh_rec_embed_faces_ragged_dev(fh_rec* r, const fh_frame* frames, int n_frames, const fh_face* faces, const int* frame_of, int n,
+                                  float* out, int* ok, void* stream) {
+    if (!r || !faces || !out) return arg_error("fh_rec_embed_faces_ragged_dev: null argument");
+    if (const char* bad = bad_frames(frames, n_frames)) return frames_error("fh_rec_embed_faces_ragged_dev", bad);
+    if (n <= 0 || (!frame_of && n > n_frames)) return arg_error("fh_rec_embed_faces_ragged_dev: bad size");
+    Owns owns(&r->rec.net());
+    return guarded([&] {
+        r->rec.embed_faces_ragged_dev(FI(frames), n_frames, reinterpret_cast<const fh::FaceRec*>(faces), frame_of, n, out, ok, S(stream));
+        return n;
+    });
+}
+
 int fh_rec_extract(fh_rec* r, const uint8_t* bgr, int rows, int cols, int step, const fh_face* face, float* out, int out_cap) {
     if (!r) return arg_error("Model not loaded!");                        // src/face_recognizer.cpp:239-242
     if (!bgr || rows <= 0 || cols <= 0) return 0;                         // :245-248 -> empty vector
@@ -511,20 +581,36 @@ namespace {
 // detect + decode + NMS + face selection on stream sd, then the ONE host hand-off of the pipeline: the number of live faces
 // (4 bytes through pinned memory, behind an event on sd).  Everything after it — align + embed — is sized by that count, so
 // the recogniser never runs on empty slots (the reference embeds "for every face", src/main.cpp:221-238: 0..F per frame).
-int detect_select_count(fh_det* d, const uint8_t* frames, int n, int rows, int cols, int step, long stride, float score_thr, float nms_thr,
-                        int F, fh_face* faces, int* frame_of, int* d_total, hipStream_t sd) {
+// (detect(out, max_per_frame, counts) runs the detector of the caller's kind — uniform or ragged — on sd)
+extern "C++" template <class Detect>
+int detect_select_count_with(fh_det* d, int n, int F, fh_face* faces, int* frame_of, int* d_total, hipStream_t sd, Detect&& detect) {
     d->p_det.ensure((size_t)n * F * sizeof(fh_face));
     d->p_cnt.ensure((size_t)n * sizeof(int));
     d->p_total.ensure(sizeof(int));
     if (!d->ev_sel) FH_HIP(hipEventCreateWithFlags(&d->ev_sel, hipEventDisableTiming));
     if (!d->h_total) FH_HIP(hipHostMalloc(reinterpret_cast<void**>(&d->h_total), sizeof(int), hipHostMallocDefault));
     int* dt = d_total ? d_total : d->p_total.as<int>();
-    d->det.detect_dev(frames, n, rows, cols, step, stride, score_thr, nms_thr, d->p_det.as<fh::FaceRec>(), F, d->p_cnt.as<int>(), sd);
+    detect(d->p_det.as<fh::FaceRec>(), F, d->p_cnt.as<int>());
     fh::launch_select_faces(d->p_det.as<fh::FaceRec>(), d->p_cnt.as<int>(), n, F, F, reinterpret_cast<fh::FaceRec*>(faces), frame_of, dt, sd);
     FH_HIP(hipMemcpyAsync(d->h_total, dt, sizeof(int), hipMemcpyDeviceToHost, sd));
     FH_HIP(hipEventRecord(d->ev_sel, sd));
     FH_HIP(hipEventSynchronize(d->ev_sel));               // waits for the DETECTOR of this batch only; a recogniser queued earlier on another stream keeps running
     return *d->h_total;
+}
+int detect_select_count(fh_det* d, const uint8_t* frames, int n, int rows, int cols, int step, long stride, float score_thr, float nms_thr,
+                        int F, fh_face* faces, int* frame_of, int* d_total, hipStream_t sd) {
+    return detect_select_count_with(d, n, F, faces, frame_of, d_total, sd, [&](fh::FaceRec* out, int max_pf, int* counts) {
+        d->det.detect_dev(frames, n, rows, cols, step, stride, score_thr, nms_thr, out, max_pf, counts, sd);
+    });
+}
+// fh_pipeline_run_ragged_dev's body (arguments checked by the caller): the detector builds the frame table once, the align reads it
+int pipeline_ragged(fh_det* d, fh_rec* r, const fh_frame* frames, int n, float score_thr, float nms_thr, int F, fh_face* faces,
+                    int* frame_of, float* emb, hipStream_t s) {
+    const int total = detect_select_count_with(d, n, F, faces, frame_of, nullptr, s, [&](fh::FaceRec* out, int max_pf, int* counts) {
+        d->det.detect_ragged_dev(FI(frames), n, score_thr, nms_thr, out, max_pf, counts, s);
+    });
+    r->rec.embed_faces_table_dev(d->det.frame_table().table(), n, reinterpret_cast<const fh::FaceRec*>(faces), frame_of, total, emb, nullptr, s);
+    return total;
 }
 }  // namespace
 
@@ -537,6 +623,63 @@ int fh_pipeline_run_dev(fh_det* d, fh_rec* r, const uint8_t* frames, int n, int 
         hipStream_t s = S(stream);
         const int total = detect_select_count(d, frames, n, rows, cols, step, (long)stride, score_thr, nms_thr, F, faces, frame_of, nullptr, s);
         r->rec.embed_faces_dev(frames, rows, cols, step, (long)stride, reinterpret_cast<const fh::FaceRec*>(faces), frame_of, total, emb, nullptr, s);
+        return total;
+    });
+}
+
+int fh_pipeline_run_ragged_dev(fh_det* d, fh_rec* r, const fh_frame* frames, int n, float score_thr, float nms_thr, int F, fh_face* faces,
+                               int* frame_of, float* emb, void* stream) {
+    if (!d || !r || !faces || !frame_of || !emb) return arg_error("fh_pipeline_run_ragged_dev: null argument");
+    if (const char* bad = bad_frames(frames, n)) return frames_error("fh_pipeline_run_ragged_dev", bad);
+    if (F <= 0) return arg_error("fh_pipeline_run_ragged_dev: bad size");
+    Owns owns(&d->det.net(), &r->rec.net());
+    return guarded([&] { return pipeline_ragged(d, r, frames, n, score_thr, nms_thr, F, faces, frame_of, emb, S(stream)); });
+}
+
+// The per-file enrolment loop (src/main.cpp:42,88-104) as one blocking call on host images of any sizes.
+int fh_pipeline_run_images(fh_det* d, fh_rec* r, const fh_frame* imgs, int n, float score_thr, float nms_thr, int F, fh_face* faces,
+                           int* frame_of, float* emb, int cap) {
+    if (!d || !r) return arg_error("fh_pipeline_run_images: null handle");
+    if (const char* bad = bad_frames(imgs, n)) return frames_error("fh_pipeline_run_images", bad);
+    if (F <= 0 || cap < 0) return arg_error("fh_pipeline_run_images: bad size");
+    size_t bytes = 0;
+    int live = 0;
+    for (int i = 0; i < n; ++i)
+        if (imgs[i].bgr && imgs[i].rows > 0 && imgs[i].cols > 0) { bytes += (size_t)imgs[i].rows * imgs[i].cols * 3; ++live; }
+    if (live == 0) return 0;                                                  // only empty images: no faces (src/face_detector.cpp:148-156)
+    Owns owns(&d->det.net(), &r->rec.net());
+    return guarded([&] {
+        hipStream_t s = d->cs.get();
+        FH_HIP(hipStreamSynchronize(s));                                      // (a failed earlier call may have left a copy from the arena queued)
+        d->h_arena.ensure(bytes);
+        d->arena.ensure(bytes);
+        const int dim = r->rec.dim();
+        d->i_faces.ensure((size_t)n * F * sizeof(fh_face));
+        d->i_fo.ensure((size_t)n * F * sizeof(int));
+        d->i_emb.ensure((size_t)n * F * dim * sizeof(float));
+        std::vector<fh_frame> dev_frames((size_t)n);
+        uint8_t* const h = static_cast<uint8_t*>(d->h_arena.p);
+        size_t off = 0;
+        for (int i = 0; i < n; ++i) {
+            const fh_frame& f = imgs[i];
+            fh_frame& o = dev_frames[(size_t)i];
+            o = fh_frame{nullptr, 0, 0, 0};
+            if (!(f.bgr && f.rows > 0 && f.cols > 0)) continue;
+            const size_t row = (size_t)f.cols * 3;
+            for (int y = 0; y < f.rows; ++y) memcpy(h + off + (size_t)y * row, f.bgr + (size_t)y * f.step, row);
+            o.bgr = d->arena.as<uint8_t>() + off; o.rows = f.rows; o.cols = f.cols; o.step = (int32_t)row;
+            off += (size_t)f.rows * row;
+        }
+        FH_HIP(hipMemcpyAsync(d->arena.p, h, bytes, hipMemcpyHostToDevice, s));
+        const int total = pipeline_ragged(d, r, dev_frames.data(), n, score_thr, nms_thr, F, d->i_faces.as<fh_face>(), d->i_fo.as<int>(),
+                                          d->i_emb.as<float>(), s);
+        FH_HIP(hipStreamSynchronize(s));
+        const int m = total < cap ? total : cap;
+        if (m > 0) {
+            if (faces) FH_HIP(hipMemcpy(faces, d->i_faces.p, (size_t)m * sizeof(fh_face), hipMemcpyDeviceToHost));
+            if (frame_of) FH_HIP(hipMemcpy(frame_of, d->i_fo.p, (size_t)m * sizeof(int), hipMemcpyDeviceToHost));
+            if (emb) FH_HIP(hipMemcpy(emb, d->i_emb.p, (size_t)m * dim * sizeof(float), hipMemcpyDeviceToHost));
+        }
         return total;
     });
 }

@@ -624,14 +624,31 @@ void Detector::reserve(int n, int rows, int cols) {
     }
 }
 
+// src/face_detector.cpp:94-113 in float, as the reference computes it
+int letterbox_plan(int rows, int cols, int in_w, int in_h, int* new_w, int* new_h, float* scale) {
+    int nw = 0, nh = 0;
+    float sc = 0.f;
+    if (rows > 0 && cols > 0 && in_w > 0 && in_h > 0) {
+        const float scaleW = (float)in_w / (float)cols, scaleH = (float)in_h / (float)rows;   // :101-102
+        sc = std::min(scaleW, scaleH);                                                        // :103
+        nw = (int)((float)cols * sc); nh = (int)((float)rows * sc);                           // :105-106
+    }
+    const int live = nw > 0 && nh > 0;                                                        // :109-113
+    if (!live) { nw = 0; nh = 0; sc = 0.f; }
+    if (new_w) *new_w = nw;
+    if (new_h) *new_h = nh;
+    if (scale) *scale = sc;
+    return live;
+}
+
 void Detector::run_network_dev(const uint8_t* frames, int n, int rows, int cols, int step, long stride, hipStream_t s) {
     reserve(n, rows, cols);
     const int inW = net_.in_w(), inH = net_.in_h();
-    // src/face_detector.cpp:101-106
-    const float scaleW = (float)inW / (float)cols, scaleH = (float)inH / (float)rows;
-    scale_ = std::min(scaleW, scaleH);
-    const int newW = (int)((float)cols * scale_), newH = (int)((float)rows * scale_);
-    if (newW <= 0 || newH <= 0) throw std::runtime_error("Invalid resize dimensions");   // :109-113
+    int newW = 0, newH = 0;
+    float sc = 0.f;
+    if (!letterbox_plan(rows, cols, inW, inH, &newW, &newH, &sc)) throw std::runtime_error("Invalid resize dimensions");   // :109-113
+    scale_ = sc;
+    ragged_ = false;
     const uint8_t* src = frames;
     long sstride = stride;
     int sstep = step;
@@ -643,8 +660,73 @@ void Detector::run_network_dev(const uint8_t* frames, int n, int rows, int cols,
     net_.run_u8(src, sstride, newH, newW, sstep, n, s);
 }
 
+// ------------------------------------------------------------------------------------------ mixed-size batches
+FrameTable::~FrameTable() {
+    for (auto& sl : slot_) {
+        if (sl.ev) { if (sl.pending) (void)hipEventSynchronize(sl.ev); (void)hipEventDestroy(sl.ev); }
+        if (sl.p) (void)hipHostFree(sl.p);
+    }
+}
+
+const FrameDesc* FrameTable::upload(const FrameIn* frames, int n, int in_w, int in_h, hipStream_t s) {
+    const size_t bytes = (size_t)n * (sizeof(FrameDesc) + sizeof(float));
+    Slot& sl = slot_[next_];
+    next_ = (next_ + 1) % kSlots;
+    if (!sl.ev) FH_HIP(hipEventCreateWithFlags(&sl.ev, hipEventDisableTiming));
+    if (sl.pending) { FH_HIP(hipEventSynchronize(sl.ev)); sl.pending = false; }   // the copy issued kSlots calls ago: long done in practice
+    if (sl.bytes < bytes) {
+        if (sl.p) (void)hipHostFree(sl.p);
+        sl.p = nullptr; sl.bytes = 0;
+        FH_HIP(hipHostMalloc(&sl.p, bytes, hipHostMallocDefault));
+        sl.bytes = bytes;
+    }
+    FrameDesc* t = static_cast<FrameDesc*>(sl.p);
+    float* sc = reinterpret_cast<float*>(t + n);
+    for (int i = 0; i < n; ++i) {
+        const FrameIn& f = frames[i];
+        FrameDesc d{};
+        sc[i] = 0.f;
+        if (!frame_empty(f)) {
+            d.bgr = f.bgr; d.rows = f.rows; d.cols = f.cols; d.step = f.step;
+            if (in_w > 0) letterbox_plan(f.rows, f.cols, in_w, in_h, &d.new_w, &d.new_h, &sc[i]);
+        }
+        t[i] = d;
+    }
+    dev_.ensure(bytes);
+    n_ = n;
+    FH_HIP(hipMemcpyAsync(dev_.p, sl.p, bytes, hipMemcpyHostToDevice, s));
+    FH_HIP(hipEventRecord(sl.ev, s));
+    sl.pending = true;
+    return table();
+}
+
+void Detector::letterbox_ragged_dev(const FrameIn* frames, int n, uint8_t* canvas, hipStream_t s) {
+    const int inW = net_.in_w(), inH = net_.in_h();
+    if (inW % 4) throw std::runtime_error("ragged letterbox: the network input width must be a multiple of 4");
+    const FrameDesc* t = table_.upload(frames, n, inW, inH, s);
+    launch_letterbox_ragged(t, n, inH, inW, canvas, s);
+    FH_HIP(hipGetLastError());
+}
+
+void Detector::run_network_ragged_dev(const FrameIn* frames, int n, hipStream_t s) {
+    reserve(n, 0, 0);
+    const int inW = net_.in_w(), inH = net_.in_h();
+    resized_.ensure((size_t)n * inH * inW * 3);                      // the canvas shares the uniform path's resize buffer
+    letterbox_ragged_dev(frames, n, resized_.as<uint8_t>(), s);
+    ragged_ = true;
+    net_.run_u8(resized_.as<uint8_t>(), (long)inH * inW * 3, inH, inW, inW * 3, n, s);   // a batch of input-sized frames
+}
+
+void Detector::detect_ragged_dev(const FrameIn* frames, int n, float score_thr, float nms_thr, FaceRec* out, int max_out, int* counts,
+                                 hipStream_t s) {
+    if (n <= 0) return;
+    run_network_ragged_dev(frames, n, s);
+    postprocess_dev(n, score_thr, nms_thr, out, max_out, counts, s);
+}
+
 void Detector::run_input_dev(const float* input, int n, hipStream_t s) {
     reserve(n, 0, 0);
+    ragged_ = false;
     const size_t per = (size_t)net_.in_h() * net_.in_w() * 4;
     FH_HIP(hipMemcpyAsync(net_.input(), input, (size_t)n * per * sizeof(float), hipMemcpyDeviceToDevice, s));
     net_.run(n, s);
@@ -653,13 +735,15 @@ void Detector::run_input_dev(const float* input, int n, hipStream_t s) {
 void Detector::postprocess_dev(int n, float score_thr, float nms_thr, FaceRec* out, int max_out, int* counts, hipStream_t s) {
     if (anchors_ <= 0) { FH_HIP(hipMemsetAsync(counts, 0, (size_t)n * sizeof(int), s)); return; }
     FH_HIP(hipMemsetAsync(count_.p, 0, (size_t)n * sizeof(int), s));
+    if (ragged_ && n > table_.size()) throw std::runtime_error("detector: more frames than the last ragged call described");
+    const float* scales = ragged_ ? table_.scales() : nullptr;       // per frame after a ragged run, else the uniform scale_
     if (predecoded_) {
         launch_rows_threshold(net_.output(0), n, anchors_, feat_, scale_, score_thr, cand_.as<FaceRec>(),
-                              keys_.as<unsigned long long>(), count_.as<int>(), cap_, s);
+                              keys_.as<unsigned long long>(), count_.as<int>(), cap_, s, scales);
     } else {
         DecodeArgs a{};
         for (int i = 0; i < 3; ++i) { a.score[i] = net_.output(i); a.bbox[i] = net_.output(3 + i); a.kps[i] = net_.output(6 + i); }
-        a.inH = net_.in_h(); a.inW = net_.in_w(); a.B = n; a.scale = scale_; a.thr = score_thr;
+        a.inH = net_.in_h(); a.inW = net_.in_w(); a.B = n; a.scale = scale_; a.scales = scales; a.thr = score_thr;
         a.cand = cand_.as<FaceRec>(); a.keys = keys_.as<unsigned long long>(); a.count = count_.as<int>(); a.cap = cap_;
         launch_scrfd_decode(a, s);
     }
@@ -721,6 +805,33 @@ void Recognizer::embed_faces_dev(const uint8_t* frames, int rows, int cols, int 
     int* okp = ok ? ok : ok_.as<int>();
     align_dev(frames, rows, cols, step, stride, faces, frame_of, n, crops_.as<uint8_t>(), okp, s);
     embed_aligned_dev(crops_.as<uint8_t>(), n, out, s);
+}
+
+void Recognizer::align_table_dev(const FrameDesc* table, int n_frames, const FaceRec* faces, const int* frame_of, int n, uint8_t* crops,
+                                 int* ok, hipStream_t s) {
+    launch_align_ragged(table, n_frames, faces, frame_of, n, net_.in_h(), net_.in_w(), crops, ok, s);
+    FH_HIP(hipGetLastError());
+}
+
+void Recognizer::embed_faces_table_dev(const FrameDesc* table, int n_frames, const FaceRec* faces, const int* frame_of, int n, float* out,
+                                       int* ok, hipStream_t s) {
+    if (n <= 0) return;
+    const size_t crop = (size_t)net_.in_h() * net_.in_w() * 3;
+    crops_.ensure((size_t)n * crop);
+    ok_.ensure((size_t)n * sizeof(int));
+    align_table_dev(table, n_frames, faces, frame_of, n, crops_.as<uint8_t>(), ok ? ok : ok_.as<int>(), s);
+    embed_aligned_dev(crops_.as<uint8_t>(), n, out, s);
+}
+
+void Recognizer::align_ragged_dev(const FrameIn* frames, int n_frames, const FaceRec* faces, const int* frame_of, int n, uint8_t* crops,
+                                  int* ok, hipStream_t s) {
+    align_table_dev(table_.upload(frames, n_frames, 0, 0, s), n_frames, faces, frame_of, n, crops, ok, s);
+}
+
+void Recognizer::embed_faces_ragged_dev(const FrameIn* frames, int n_frames, const FaceRec* faces, const int* frame_of, int n, float* out,
+                                        int* ok, hipStream_t s) {
+    if (n <= 0) return;
+    embed_faces_table_dev(table_.upload(frames, n_frames, 0, 0, s), n_frames, faces, frame_of, n, out, ok, s);
 }
 
 void Recognizer::resize_embed_dev(const uint8_t* frames, int n, int rows, int cols, int step, long stride, float* out, hipStream_t s) {

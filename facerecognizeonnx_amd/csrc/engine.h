@@ -120,6 +120,42 @@ class Net {
     bool front_ok_ = false;                                   // ops 0 + 1 = stem conv (16 channels) -> DW+PW: one kernel
 };
 
+// FaceDetector::preprocess' letterbox arithmetic (src/face_detector.cpp:101-113), the ONE place it lives: scale = min((float)in_w / cols,
+// (float)in_h / rows), new_w = (int)((float)cols * scale), new_h likewise.  Returns 1 for a live frame; 0 — with scale = 0 and a 0 x 0
+// plan — for an empty image (:94-98) or "Invalid resize dimensions" (:109-113).  Host code (fh_letterbox_plan).
+int letterbox_plan(int rows, int cols, int in_w, int in_h, int* new_w, int* new_h, float* scale);
+
+// One frame of a mixed-size batch as the caller describes it (layout of fh_frame, include/facehip.h): bgr = DEVICE pixels.
+struct FrameIn {
+    const uint8_t* bgr;
+    int32_t rows, cols, step;
+};
+inline bool frame_empty(const FrameIn& f) { return !f.bgr || f.rows <= 0 || f.cols <= 0; }     // the reference's empty image
+
+// The device image of a call's frame descriptors: [n] FrameDesc rows followed by [n] float scales, built on the host from the caller's
+// descriptors and letterbox_plan and sent with ONE asynchronous copy on the caller's stream.  The copy's source must outlive it, and the
+// next call on the handle may follow at once with another table, so the pinned staging memory is a RING of kSlots buffers, each with an
+// event recorded behind its copy: a call takes the next slot and — only when the ring has wrapped round to a slot whose copy may still
+// be pending — waits for that slot's event before it rewrites it.  (The device side needs no ring: it is rewritten in stream order.)
+class FrameTable {
+  public:
+    FrameTable() = default;
+    FrameTable(const FrameTable&) = delete;
+    FrameTable& operator=(const FrameTable&) = delete;
+    ~FrameTable();
+    // in_w / in_h > 0: plan the letterbox of every frame; 0: geometry only (the recogniser's align).  Returns the device table.
+    const FrameDesc* upload(const FrameIn* frames, int n, int in_w, int in_h, hipStream_t s);
+    const FrameDesc* table() const { return dev_.as<FrameDesc>(); }
+    const float* scales() const { return reinterpret_cast<const float*>(dev_.as<FrameDesc>() + n_); }
+    int size() const { return n_; }
+
+  private:
+    static constexpr int kSlots = 4;
+    struct Slot { void* p = nullptr; size_t bytes = 0; hipEvent_t ev = nullptr; bool pending = false; } slot_[kSlots];
+    int next_ = 0, n_ = 0;
+    DevBuf dev_;
+};
+
 class Detector {
   public:
     explicit Detector(const std::string& onnx_path);
@@ -138,6 +174,13 @@ class Detector {
     // input: device [n][inH][inW][4] preprocessed floats (lane 3 = 0) -> copied into net().input(), then every op runs (the path
     // run_u8 takes with the fused stem off, minus the preprocess kernel)
     void run_input_dev(const float* input, int n, hipStream_t s);
+    // Mixed-size batches (frames: HOST array of n descriptors of device images).  plan -> table -> letterbox_ragged_kernel -> run_u8 on
+    // the canvas, the path a batch of input-sized frames takes; postprocess_dev then divides by the per-frame scales.
+    void letterbox_ragged_dev(const FrameIn* frames, int n, uint8_t* canvas, hipStream_t s);        // canvas [n][inH][inW][3], caller's
+    void run_network_ragged_dev(const FrameIn* frames, int n, hipStream_t s);
+    void detect_ragged_dev(const FrameIn* frames, int n, float score_thr, float nms_thr, FaceRec* out, int max_out, int* counts,
+                           hipStream_t s);
+    const FrameTable& frame_table() const { return table_; }   // of the last ragged call: handed to the recogniser's align by the pipeline
 
   private:
     void reserve(int n, int rows, int cols);
@@ -145,7 +188,9 @@ class Detector {
     bool predecoded_ = false;
     int anchors_ = 0, feat_ = 15, cap_ = 0, nb_ = 0;
     float scale_ = 1.f;
-    DevBuf resized_, cand_, keys_, count_, ws_;
+    bool ragged_ = false;                                 // the last network run was a ragged one: postprocess_dev reads table_.scales()
+    FrameTable table_;
+    DevBuf resized_, cand_, keys_, count_, ws_;           // resized_: the uniform path's resized frames / the ragged path's canvas
 };
 
 class Recognizer {
@@ -161,6 +206,16 @@ class Recognizer {
     void align_dev(const uint8_t* frames, int rows, int cols, int step, long stride, const FaceRec* faces, const int* frame_of,
                    int n, uint8_t* crops, int* ok, hipStream_t s);
     void resize_embed_dev(const uint8_t* frames, int n, int rows, int cols, int step, long stride, float* out, hipStream_t s);
+    // the same two on a mixed-size batch: face i lies on frame frame_of[i] (null = i) of a device table of n_frames rows — the
+    // detector's (pipeline) or, from host descriptors, one this object builds
+    void align_table_dev(const FrameDesc* table, int n_frames, const FaceRec* faces, const int* frame_of, int n, uint8_t* crops, int* ok,
+                         hipStream_t s);
+    void embed_faces_table_dev(const FrameDesc* table, int n_frames, const FaceRec* faces, const int* frame_of, int n, float* out, int* ok,
+                               hipStream_t s);
+    void align_ragged_dev(const FrameIn* frames, int n_frames, const FaceRec* faces, const int* frame_of, int n, uint8_t* crops, int* ok,
+                          hipStream_t s);
+    void embed_faces_ragged_dev(const FrameIn* frames, int n_frames, const FaceRec* faces, const int* frame_of, int n, float* out, int* ok,
+                                hipStream_t s);
     // input: device [n][H][W][4] preprocessed floats (lane 3 = 0) instead of u8 crops; otherwise embed_aligned_dev
     void embed_input_dev(const float* input, int n, float* out, hipStream_t s, float* raw_out = nullptr);
     int max_chunk = 256;                                 // faces per network pass
@@ -168,6 +223,7 @@ class Recognizer {
   private:
     Net net_;
     int dim_ = 0;
+    FrameTable table_;
     DevBuf crops_, ok_, raw_;
 };
 

@@ -119,6 +119,147 @@ void launch_resize_u8c3(const uint8_t* src, long src_stride, int sh, int sw, int
 }
 
 // ------------------------------------------------------------------------------------------
+// FaceDetector::preprocess' resize + paste (src/face_detector.cpp:101-121) for a batch of frames that each have their own size:
+// canvas[f] = frame f resized to its plan new_h x new_w (every sample the value resize_px gives, bit for bit — same-size copy and
+// exact-2x INTER_AREA branches included), top-left on a zero canvas; a dead frame's canvas is all zero.
+// One workgroup = one (frame, band of LB_BAND canvas rows); grid = ceil(inH / LB_BAND) x n.  The branch (copy / 2x area / bilinear) is
+// decided once per frame, so it is uniform in the workgroup.  A thread owns groups of four neighbouring columns: their horizontal
+// coefficients (source column, the 11-bit weight pair, the second tap's byte offset — 0 at the right edge, where resize_px reads one
+// tap with weight 2048) are computed once and kept in registers across the rows of the band; the vertical coefficients are computed
+// once per row by the first LB_BAND threads and shared through LDS; the three channels share both.  Source reads are byte loads
+// (pitch and alignment are the caller's); a thread writes its four pixels of a row as three dwords (inW % 4 == 0, canvas 4-byte
+// aligned), neighbouring threads neighbouring 12-byte pieces.  Block = gx * ry threads: gx column-group lanes (min(inW / 4, 256)), ry row
+// lanes (rows r, r + ry, ... of the band), rounded up to whole waves.
+// kernel-resource-usage (gfx950, hipcc -O3): 81 VGPRs, 0 AGPRs, 65 SGPRs, no scratch, no spills, 192 bytes of LDS, 5 waves per SIMD.
+// ------------------------------------------------------------------------------------------
+constexpr int LB_BAND = 16;
+
+__device__ __forceinline__ unsigned lb_pack4(const int* v) {      // bytes v[0..3] -> one little-endian dword
+    return (unsigned)v[0] | (unsigned)v[1] << 8 | (unsigned)v[2] << 16 | (unsigned)v[3] << 24;
+}
+
+__global__ __launch_bounds__(256) void letterbox_ragged_kernel(const FrameDesc* __restrict__ table, int inH, int inW, int gx, int ry,
+                                                               uint8_t* __restrict__ canvas) {
+    __shared__ int vy0[LB_BAND], vy1[LB_BAND], vb[LB_BAND];          // source rows of the two taps, weights b0 | b1 << 16
+    const int f = blockIdx.y, band0 = blockIdx.x * LB_BAND, tid = threadIdx.x;
+    const FrameDesc fd = table[f];
+    const uint8_t* __restrict__ src = fd.bgr;
+    const int sh = fd.rows, sw = fd.cols, sstep = fd.step, dh = fd.new_h, dw = fd.new_w;
+    // once per frame: resize_px's dispatch (the same fp64 expressions)
+    int mode = 0;                                                    // 0 dead, 1 copy, 2 exact 2x area, 3 bilinear
+    double scale_x = 0.0, scale_y = 0.0;
+    if (dh > 0 && dw > 0) {
+        if (dh == sh && dw == sw) mode = 1;
+        else {
+            const double inv_sx = (double)dw / sw, inv_sy = (double)dh / sh;
+            scale_x = 1.0 / inv_sx; scale_y = 1.0 / inv_sy;
+            const int isx = cv_round_d(scale_x), isy = cv_round_d(scale_y);
+            const bool area_fast = fabs(scale_x - isx) < 2.220446049250313e-16 && fabs(scale_y - isy) < 2.220446049250313e-16;
+            mode = (area_fast && isx == 2 && isy == 2) ? 2 : 3;
+        }
+    }
+    if (mode == 3 && tid < LB_BAND) {                                // vertical coefficients, once per row of the band
+        const int dy = band0 + tid;
+        float fy = (float)((dy + 0.5) * scale_y - 0.5);
+        const int sy = cv_floor_f(fy);
+        fy -= sy;
+        const int b0 = sat_short_f((1.f - fy) * 2048.f), b1 = sat_short_f(fy * 2048.f);
+        int y0 = sy, y1 = sy + 1;
+        y0 = y0 >= 0 ? (y0 < sh ? y0 : sh - 1) : 0;
+        y1 = y1 >= 0 ? (y1 < sh ? y1 : sh - 1) : 0;
+        vy0[tid] = y0; vy1[tid] = y1; vb[tid] = (b0 & 0xffff) | b1 << 16;
+    }
+    __syncthreads();
+    const int gi = tid % gx, r0 = tid / gx;
+    if (r0 >= ry) return;                                            // lanes that only round the block up to whole waves
+    const int ngroups = inW >> 2;
+    uint8_t* const cv = canvas + (size_t)f * inH * inW * 3;
+    for (int g = gi; g < ngroups; g += gx) {
+        const int x0 = g * 4;
+        // horizontal coefficients of the four columns, once per (thread, group)
+        int sxo[4], aw[4], tap[4];                                   // byte offset of the left tap (-1: outside the plan), a0 | a1 << 16, 0 | 3
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int dx = x0 + j;
+            sxo[j] = -1; aw[j] = 0; tap[j] = 0;
+            if (dx < dw) {
+                if (mode == 1) sxo[j] = dx * 3;
+                else if (mode == 2) sxo[j] = dx * 6;
+                else if (mode == 3) {
+                    float fx = (float)((dx + 0.5) * scale_x - 0.5);
+                    int sx = cv_floor_f(fx);
+                    fx -= sx;
+                    if (sx < 0) { fx = 0; sx = 0; }
+                    bool edge = false;
+                    if (sx + 1 >= sw) { edge = true; if (sx >= sw - 1) { fx = 0; sx = sw - 1; } }
+                    const int a0 = sat_short_f((1.f - fx) * 2048.f), a1 = sat_short_f(fx * 2048.f);
+                    // the edge sample is r[0] * 2048: fx = 0 there, so a0 = 2048, a1 = 0 and a second tap ON the first gives that value
+                    sxo[j] = sx * 3; aw[j] = (a0 & 0xffff) | a1 << 16; tap[j] = edge ? 0 : 3;
+                }
+            }
+        }
+        for (int r = r0; r < LB_BAND; r += ry) {
+            const int dy = band0 + r;
+            if (dy >= inH) break;
+            int px[12];
+#pragma unroll
+            for (int k = 0; k < 12; ++k) px[k] = 0;
+            if (dy < dh) {
+                if (mode == 1) {
+                    const uint8_t* row = src + (size_t)dy * sstep;
+#pragma unroll
+                    for (int j = 0; j < 4; ++j)
+                        if (sxo[j] >= 0) {
+#pragma unroll
+                            for (int c = 0; c < 3; ++c) px[j * 3 + c] = row[sxo[j] + c];
+                        }
+                } else if (mode == 2) {
+                    const uint8_t* s0 = src + (size_t)(2 * dy) * sstep;
+                    const uint8_t* s1 = s0 + sstep;
+#pragma unroll
+                    for (int j = 0; j < 4; ++j)
+                        if (sxo[j] >= 0) {
+#pragma unroll
+                            for (int c = 0; c < 3; ++c)
+                                px[j * 3 + c] = (s0[sxo[j] + c] + s0[sxo[j] + 3 + c] + s1[sxo[j] + c] + s1[sxo[j] + 3 + c] + 2) >> 2;
+                        }
+                } else if (mode == 3) {
+                    const uint8_t* q0 = src + (size_t)vy0[r] * sstep;
+                    const uint8_t* q1 = src + (size_t)vy1[r] * sstep;
+                    const int bw = vb[r];
+                    const int b0 = (short)(bw & 0xffff), b1 = bw >> 16;
+#pragma unroll
+                    for (int j = 0; j < 4; ++j)
+                        if (sxo[j] >= 0) {
+                            const int a0 = (short)(aw[j] & 0xffff), a1 = aw[j] >> 16;
+#pragma unroll
+                            for (int c = 0; c < 3; ++c) {
+                                const int o = sxo[j] + c;
+                                const int S0 = q0[o] * a0 + q0[o + tap[j]] * a1;
+                                const int S1 = q1[o] * a0 + q1[o + tap[j]] * a1;
+                                const int v = (((b0 * (S0 >> 4)) >> 16) + ((b1 * (S1 >> 4)) >> 16) + 2) >> 2;
+                                px[j * 3 + c] = v < 0 ? 0 : v > 255 ? 255 : v;
+                            }
+                        }
+                }
+            }
+            unsigned* out = reinterpret_cast<unsigned*>(cv + ((size_t)dy * inW + x0) * 3);
+            out[0] = lb_pack4(px); out[1] = lb_pack4(px + 4); out[2] = lb_pack4(px + 8);
+        }
+    }
+}
+
+void launch_letterbox_ragged(const FrameDesc* table, int n, int inH, int inW, uint8_t* canvas, hipStream_t s) {
+    if (n <= 0 || inH <= 0 || inW <= 0) return;
+    const int ngroups = inW / 4;
+    const int gx = ngroups < 256 ? ngroups : 256;
+    int ry = 256 / gx;
+    ry = ry < LB_BAND ? ry : LB_BAND;
+    const int threads = (gx * ry + 63) / 64 * 64;
+    hipLaunchKernelGGL(letterbox_ragged_kernel, dim3((inH + LB_BAND - 1) / LB_BAND, n), dim3(threads), 0, s, table, inH, inW, gx, ry, canvas);
+}
+
+// ------------------------------------------------------------------------------------------
 // Anchor decode (the step the reference lacks) + FaceDetector::postprocess row
 // loop (src/face_detector.cpp:249-278): strict score > thr, /scale, int truncation, width from
 // the float difference.  Payload goes to cand[frame][anchor]; the surviving anchors' sort keys
@@ -144,6 +285,8 @@ __global__ __launch_bounds__(256) void scrfd_decode_kernel(const DecodeArgs a) {
     const int n8 = gw8 * gh8 * 2, n16 = gw16 * gh16 * 2, n32 = gw32 * gh32 * 2;
     const int N = n8 + n16 + n32;
     const int b = blockIdx.y;                              // one grid row per frame: no 64-bit index arithmetic per anchor
+    const float scale = a.scales ? a.scales[b] : a.scale;  // per frame on the ragged path
+    if (!(scale > 0.f)) return;                            // a dead frame emits nothing: its count stays 0
     for (int r = blockIdx.x * blockDim.x + threadIdx.x; r < N; r += gridDim.x * blockDim.x) {
         int si, i, gw, s, ns;
         if (r < n8) { si = 0; i = r; gw = gw8; s = 8; ns = n8; }
@@ -161,7 +304,7 @@ __global__ __launch_bounds__(256) void scrfd_decode_kernel(const DecodeArgs a) {
         o[4] = score;
 #pragma unroll
         for (int j = 0; j < 5; ++j) { o[5 + 2 * j] = cx + k[2 * j] * fs; o[6 + 2 * j] = cy + k[2 * j + 1] * fs; }
-        emit_face(o, a.scale, a.cand + (size_t)b * a.cap + r);
+        emit_face(o, scale, a.cand + (size_t)b * a.cap + r);
         const int pos = atomicAdd(a.count + b, 1);
         if (pos < a.cap) a.keys[(size_t)b * a.cap + pos] = make_key(score, (unsigned)r);
     }
@@ -174,15 +317,17 @@ void launch_scrfd_decode(const DecodeArgs& a, hipStream_t s) {
 }
 
 // The reference's own layout: rows [n, feat >= 15] = x1,y1,x2,y2,score,kps (src/face_detector.cpp:242-325)
-__global__ __launch_bounds__(256) void rows_threshold_kernel(const float* __restrict__ rows, int B, int n, int feat, float scale,
-                                                             float thr, FaceRec* cand, unsigned long long* keys, int* count, int cap) {
+__global__ __launch_bounds__(256) void rows_threshold_kernel(const float* __restrict__ rows, int B, int n, int feat, float scale_all,
+                                                             const float* __restrict__ scales, float thr, FaceRec* cand,
+                                                             unsigned long long* keys, int* count, int cap) {
     const long total = (long)B * n;
     for (long t = (long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (long)gridDim.x * blockDim.x) {
         const int b = (int)(t / n);
         const int r = (int)(t - (long)b * n);
         const float* o = rows + (size_t)t * feat;
         const float score = o[4];
-        if (!(score > thr) || r >= cap) continue;
+        const float scale = scales ? scales[b] : scale_all;
+        if (!(score > thr) || r >= cap || !(scale > 0.f)) continue;      // (a dead frame of the ragged path emits nothing)
         float o15[15];
 #pragma unroll
         for (int j = 0; j < 15; ++j) o15[j] = o[j];
@@ -193,9 +338,9 @@ __global__ __launch_bounds__(256) void rows_threshold_kernel(const float* __rest
 }
 
 void launch_rows_threshold(const float* rows, int B, int n, int feat, float scale, float thr, FaceRec* cand,
-                           unsigned long long* keys, int* count, int cap, hipStream_t s) {
-    hipLaunchKernelGGL(rows_threshold_kernel, dim3(grid_for((long)B * n)), dim3(256), 0, s, rows, B, n, feat, scale, thr, cand, keys,
-                       count, cap);
+                           unsigned long long* keys, int* count, int cap, hipStream_t s, const float* scales) {
+    hipLaunchKernelGGL(rows_threshold_kernel, dim3(grid_for((long)B * n)), dim3(256), 0, s, rows, B, n, feat, scale, scales, thr, cand,
+                       keys, count, cap);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -359,7 +504,10 @@ __device__ int estimate_similarity5(const float* from, const float* to, double* 
 
 constexpr int ALIGN_PARTS = 4;
 
+// table != null (mixed-size batches): the image, rows, cols and step of face n come from table[frame_of[n]] instead of the uniform
+// arguments, for all three modes; a frame index outside [0, n_frames) or an empty frame gives the empty result.
 __global__ __launch_bounds__(256) void align_kernel(const uint8_t* __restrict__ frames, long img_stride, int rows, int cols, int step,
+                                                    const FrameDesc* __restrict__ table, int n_frames,
                                                     const FaceRec* __restrict__ faces, const int* __restrict__ frame_of, int outH,
                                                     int outW, uint8_t* __restrict__ crops, int* __restrict__ ok) {
     __shared__ double Ms[6];
@@ -369,11 +517,25 @@ __global__ __launch_bounds__(256) void align_kernel(const uint8_t* __restrict__ 
     // with one workgroup per face a 128-face batch left half the CUs idle behind that serial section
     const int n = blockIdx.x / ALIGN_PARTS, part = blockIdx.x - n * ALIGN_PARTS, tid = threadIdx.x;
     const FaceRec face = faces[n];
-    const uint8_t* img = frames + (size_t)(frame_of ? frame_of[n] : n) * img_stride;
+    const int fr = frame_of ? frame_of[n] : n;
+    const uint8_t* img;
+    bool no_image = false;
+    if (table) {
+        img = nullptr;
+        no_image = fr < 0 || fr >= n_frames;
+        if (!no_image) {
+            const FrameDesc fd = table[fr];
+            img = fd.bgr; rows = fd.rows; cols = fd.cols; step = fd.step;
+            no_image = !img || rows <= 0 || cols <= 0;               // alignFace on an empty image (src/face_recognizer.cpp:93-133)
+        }
+    } else {
+        img = frames + (size_t)fr * img_stride;
+    }
     if (tid == 0) {
         const float tmpl[10] = {38.2946f, 51.6963f, 73.5318f, 51.5014f, 56.0252f, 71.7366f, 41.5493f, 92.3655f, 70.7299f, 92.2041f};
         double M[6];
-        if (estimate_similarity5(face.lm, tmpl, M)) {
+        if (no_image) mode = 0;
+        else if (estimate_similarity5(face.lm, tmpl, M)) {
             double D = M[0] * M[4] - M[1] * M[3];
             D = D != 0 ? 1. / D : 0;
             const double A11 = M[4] * D, A22 = M[0] * D;
@@ -436,7 +598,15 @@ __global__ __launch_bounds__(256) void align_kernel(const uint8_t* __restrict__ 
 void launch_align(const uint8_t* frames, long img_stride, int rows, int cols, int step, const FaceRec* faces, const int* frame_of,
                   int n, int outH, int outW, uint8_t* crops, int* ok, hipStream_t s) {
     if (n <= 0) return;
-    hipLaunchKernelGGL(align_kernel, dim3(n * ALIGN_PARTS), dim3(256), 0, s, frames, img_stride, rows, cols, step, faces, frame_of, outH, outW, crops, ok);
+    hipLaunchKernelGGL(align_kernel, dim3(n * ALIGN_PARTS), dim3(256), 0, s, frames, img_stride, rows, cols, step,
+                       static_cast<const FrameDesc*>(nullptr), 0, faces, frame_of, outH, outW, crops, ok);
+}
+
+void launch_align_ragged(const FrameDesc* table, int n_frames, const FaceRec* faces, const int* frame_of, int n, int outH, int outW,
+                         uint8_t* crops, int* ok, hipStream_t s) {
+    if (n <= 0) return;
+    hipLaunchKernelGGL(align_kernel, dim3(n * ALIGN_PARTS), dim3(256), 0, s, static_cast<const uint8_t*>(nullptr), 0L, 0, 0, 0, table,
+                       n_frames, faces, frame_of, outH, outW, crops, ok);
 }
 
 // ------------------------------------------------------------------------------------------

@@ -249,6 +249,8 @@ struct DecodeArgs {
     const float* kps[3];    // [B, gh*gw*2, 10]
     int inH, inW, B;
     float scale, thr;
+    const float* scales;    // [B] per-frame letterbox scale (the ragged path) or null = `scale` for every frame; a frame whose scale is
+                            // not > 0 (a dead frame) emits nothing
     FaceRec* cand;          // [B][cap]
     unsigned long long* keys;   // [B][cap]  sort keys (score desc, anchor index asc)
     int* count;             // [B]
@@ -256,8 +258,9 @@ struct DecodeArgs {
 };
 void launch_scrfd_decode(const DecodeArgs& a, hipStream_t s);
 // generic [rows, feat>=15] pre-decoded layout (src/face_detector.cpp:242-325)
+// scales (optional, device [B]): per-frame scale as DecodeArgs::scales
 void launch_rows_threshold(const float* rows, int B, int n, int feat, float scale, float thr, FaceRec* cand,
-                           unsigned long long* keys, int* count, int cap, hipStream_t s);
+                           unsigned long long* keys, int* count, int cap, hipStream_t s, const float* scales = nullptr);
 // sort by key + greedy integer-IoU NMS (src/face_detector.cpp:340-384); writes survivors
 // (score-descending) to out[B][max_out], counts to out_count[B].
 void launch_sort_nms(const FaceRec* cand, unsigned long long* keys, const int* count, int cap, int B, float nms_thr,
@@ -267,6 +270,20 @@ void launch_sort_nms(const FaceRec* cand, unsigned long long* keys, const int* c
 //   faces[n] with frame index frame_of[n]; writes crops [n,112,112,3] BGR u8 and ok[n].
 void launch_align(const uint8_t* frames, long img_stride, int rows, int cols, int step, const FaceRec* faces,
                   const int* frame_of, int n, int outH, int outW, uint8_t* crops, int* ok, hipStream_t s);
+// Mixed-size batches: one row per frame of the device table the ragged entry points build (engine.cpp FrameTable).  bgr = device pixels
+// (any alignment), step = row pitch in bytes; new_h x new_w = the letterbox plan (fh_letterbox_plan), 0 x 0 for a dead frame.
+struct FrameDesc {
+    const uint8_t* bgr;
+    int32_t rows, cols, step, new_h, new_w, pad_;
+};
+static_assert(sizeof(FrameDesc) == 32, "FrameDesc is a 32-byte table row");
+// FaceDetector::preprocess' resize + paste (src/face_detector.cpp:101-121) for n frames of different sizes in one launch: canvas
+// [n][inH][inW][3] u8 (4-byte aligned, inW % 4 == 0) = the frame resized to new_h x new_w (resize_px, bit for bit) top-left on zeros
+void launch_letterbox_ragged(const FrameDesc* table, int n, int inH, int inW, uint8_t* canvas, hipStream_t s);
+// launch_align with per-face frame geometry: face i lies on table[frame_of ? frame_of[i] : i] (an index outside [0, n_frames) or a dead
+// frame gives the empty result, ok = 0)
+void launch_align_ragged(const FrameDesc* table, int n_frames, const FaceRec* faces, const int* frame_of, int n, int outH, int outW,
+                         uint8_t* crops, int* ok, hipStream_t s);
 void launch_resize_u8c3(const uint8_t* src, long src_stride, int sh, int sw, int sstep, uint8_t* dst, long dst_stride,
                         int dh, int dw, int dstep, int n, hipStream_t s);
 

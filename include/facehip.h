@@ -141,6 +141,52 @@ FH_API int fh_pipeline_run_dev(fh_det* d, fh_rec* r, const uint8_t* d_frames, in
                                long long frame_stride, float score_thr, float nms_thr, int faces_per_frame,
                                fh_face* d_faces, int* d_frame_of, float* d_emb, void* stream);
 
+/* ---- mixed-size frame batches: detect, align and embed a COLLECTION of images that each have their own size in one call (gallery
+ * enrolment from photographs; the reference's per-file flow, src/main.cpp:42,71-72,88-104, over a batch).  The uniform entry points
+ * above stay the path for same-size streams.
+ * fh_frame  one image: cv::Mat data / rows / cols / step (src/face_detector.cpp:139).  The ARRAY of descriptors is host memory (read
+ *           before the call returns); bgr points to DEVICE memory, anywhere and with any alignment (fh_pipeline_run_images: host).
+ *           bgr == NULL, rows <= 0 or cols <= 0 is the reference's empty image (src/face_detector.cpp:148-156): that frame yields zero
+ *           faces and the call succeeds.  step < cols * 3 on a non-empty frame fails the call with FH_ERR_ARG before anything is
+ *           launched.  1 <= n <= 4096.
+ * fh_letterbox_plan  host only, no GPU: FaceDetector::preprocess' float arithmetic (src/face_detector.cpp:101-113) — scale =
+ *           min((float)in_w / cols, (float)in_h / rows), new_w = (int)((float)cols * scale), new_h likewise.  Returns 1 for a live frame;
+ *           0, with *scale = 0 and a 0 x 0 plan, for an empty image or new_w <= 0 || new_h <= 0 ("Invalid resize dimensions",
+ *           :109-113).  The uniform and the ragged detector both plan through this one function.  Output pointers may be NULL. */
+typedef struct fh_frame { const uint8_t* bgr; int32_t rows, cols, step; } fh_frame;   /* 24 bytes; bgr = DEVICE pointer */
+FH_API int fh_letterbox_plan(int rows, int cols, int in_w, int in_h, int* new_w, int* new_h, float* scale);
+/* Stage hooks, for the parity tests and for callers that want the canvas.  fh_det_letterbox_ragged_dev: cv::resize + the paste onto the
+ * zero canvas (src/face_detector.cpp:117-121) for all n frames in one launch: d_canvas = [n][inH][inW][3] BGR u8 (4-byte aligned), frame
+ * i resized to its plan top-left, zeros elsewhere, all zeros for a dead frame.  fh_det_run_network_ragged_dev: that canvas (the
+ * handle's own) through the network (:170); read the heads with fh_det_output_dev, fh_det_postprocess_dev then un-scales per frame. */
+FH_API int fh_det_letterbox_ragged_dev(fh_det* d, const fh_frame* frames, int n, uint8_t* d_canvas, void* stream);
+FH_API int fh_det_run_network_ragged_dev(fh_det* d, const fh_frame* frames, int n, void* stream);
+/* FaceDetector::detect (src/face_detector.cpp:139-222) on n frames of ANY sizes: d_out / d_counts / max_per_frame, ordering and
+ * truncation exactly as fh_det_detect_batch_dev; every frame's records are divided by its own scale (:255-275); a dead frame's count
+ * is 0.  Asynchronous on `stream`; the next call on the handle may follow at once with another descriptor array. */
+FH_API int fh_det_detect_ragged_dev(fh_det* d, const fh_frame* frames, int n, float score_thr, float nms_thr, fh_face* d_out,
+                                    int max_per_frame, int* d_counts, void* stream);
+/* alignFace (src/face_recognizer.cpp:93-133) / alignFace + extractFeature's network pass (:236-304) for n faces on n_frames frames of
+ * different sizes: d_frame_of[i] = index into `frames` of face i's image (NULL = identity, as fh_rec_align_dev; n <= n_frames then);
+ * crops, d_ok (1 warped, 2 crop-resize fallback, 0 empty — also for a face on an empty frame or with a frame index outside
+ * [0, n_frames)) and embeddings as fh_rec_align_dev / fh_rec_embed_faces_dev. */
+FH_API int fh_rec_align_ragged_dev(fh_rec* r, const fh_frame* frames, int n_frames, const fh_face* d_faces, const int* d_frame_of,
+                                   int n, uint8_t* d_crops, int* d_ok, void* stream);
+FH_API int fh_rec_embed_faces_ragged_dev(fh_rec* r, const fh_frame* frames, int n_frames, const fh_face* d_faces, const int* d_frame_of,
+                                         int n, float* d_out, int* d_ok, void* stream);
+/* fh_pipeline_run_dev on frames of any sizes ("for every face", src/main.cpp:221-238): same selection (first min(count,
+ * faces_per_frame) faces per frame), compaction, d_frame_of, host hand-off and return value; dead frames contribute nothing; slots
+ * beyond the returned count are not written.  The frame table is built once and shared by the detector and the align. */
+FH_API int fh_pipeline_run_ragged_dev(fh_det* d, fh_rec* r, const fh_frame* frames, int n, float score_thr, float nms_thr,
+                                      int faces_per_frame, fh_face* d_faces, int* d_frame_of, float* d_emb, void* stream);
+/* The enrolment loop over files (src/main.cpp:42,88-104: imread, detect, extractFeature per image) as ONE call on HOST images of any
+ * sizes; blocking.  imgs[i].bgr is a HOST pointer here (fh_imread's output fits).  The live images are packed row by row, without
+ * padding, into one pinned arena, sent with one copy and run through fh_pipeline_run_ragged_dev; the first min(total, cap) faces /
+ * frame indices / embeddings ([cap][dim]) come back (any of the three pointers may be NULL).  Returns the total number of faces.  The
+ * arena and the device buffers belong to the fh_det handle and grow on demand. */
+FH_API int fh_pipeline_run_images(fh_det* d, fh_rec* r, const fh_frame* imgs, int n, float score_thr, float nms_thr,
+                                  int faces_per_frame, fh_face* faces, int* frame_of, float* emb, int cap);
+
 /* Two-stream form for streaming callers (the testWebcam loop shape, src/main.cpp:214-258, over batches): detect + decode +
  * NMS + face selection on stream_det, align + embed on stream_rec behind an event.  The host waits for the detector's face
  * count only; a recogniser queued earlier on stream_rec keeps running, so submitting batch k+1 straight after batch k
