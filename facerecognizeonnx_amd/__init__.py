@@ -5,8 +5,8 @@ FaceRecognizer::extractFeature / compareFaces) behind a C ABI (include/facehip.h
 as hand-written gfx950 HIP kernels (csrc/).  See DESIGN.md.
 """
 from .api import (Comm, FaceBox, FaceDetector, FaceRecognizer, FrameStream, Gallery, pipeline_run_dev, pipeline_submit_dev,  # noqa: F401
-                  imread, plan_describe, topk_merge_ids_dev, frame_array, letterbox_plan, pipeline_run_ragged_dev, pipeline_images)
+                  imread, plan_describe, topk_merge_ids_dev, group_ids, frame_array, letterbox_plan, pipeline_run_ragged_dev, pipeline_images)
 from ._lib import FACE_DTYPE, FaceHipError, FhFrame, build, lib  # noqa: F401
 
-__all__ = ["Comm", "FaceBox", "FaceDetector", "FaceRecognizer", "Gallery", "FrameStream", "pipeline_run_dev", "pipeline_submit_dev", "plan_describe", "imread", "topk_merge_ids_dev", "frame_array", "letterbox_plan", "pipeline_run_ragged_dev", "pipeline_images", "FhFrame",
+__all__ = ["Comm", "FaceBox", "FaceDetector", "FaceRecognizer", "Gallery", "FrameStream", "pipeline_run_dev", "pipeline_submit_dev", "plan_describe", "imread", "topk_merge_ids_dev", "group_ids", "frame_array", "letterbox_plan", "pipeline_run_ragged_dev", "pipeline_images", "FhFrame",
            "FACE_DTYPE", "FaceHipError", "build", "lib"]

@@ -123,6 +123,10 @@ PROTOTYPES = {
     "fh_gallery_remove_ids": (_ll, [_vp, _vp, _ll]),
     "fh_gallery_get_ids": (_ll, [_vp, _ll, _ll, _vp]),
     "fh_topk_merge_ids_dev": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "fh_gallery_group_ids": (_ll, [_vp, _ll, _vp, _vp, _vp]),
+    "fh_gallery_fuse_ids": (_ll, [_vp, _vp, _i]),
+    "fh_gallery_get_rows": (_ll, [_vp, _ll, _ll, _vp]),
+    "fh_gallery_self_scores_dev": (_i, [_vp, _vp, _vp, _vp]),
     "fh_comm_unique_id": (_i, [_vp]),
     "fh_comm_create": (_vp, [_i, _i, _vp, _i]),
     "fh_comm_destroy": (None, [_vp]),

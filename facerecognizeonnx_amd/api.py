@@ -413,6 +413,32 @@ class Gallery:
         check(_lib.lib().fh_gallery_get_ids(self._h, first, n, out.ctypes.data if n > 0 else None), "fh_gallery_get_ids")
         return out
 
+    def rows(self, first: int = 0, n: Optional[int] = None) -> np.ndarray:
+        """fp32 rows [first, first + n) by position (default: to the end), of either kind of gallery (fh_gallery_get_rows)."""
+        if n is None:
+            n = len(self) - first
+        out = np.empty((max(n, 0), self.dim), np.float32)
+        check(_lib.lib().fh_gallery_get_rows(self._h, first, n, out.ctypes.data if n > 0 else None), "fh_gallery_get_rows")
+        return out
+
+    _FUSE = {"unit": 0, "sum": 1}
+
+    def fuse(self, dst: Optional["Gallery"] = None, mode: str = "unit") -> "Gallery":
+        """Template pooling (fh_gallery_fuse_ids): `dst` (default: a new gallery of the same dim) is replaced by one row per identity
+        of this labelled gallery, ascending ids — the identity's rows summed in a fixed order, L2-normalised ("unit") or as the sum is
+        ("sum"); an identity of one template keeps its row verbatim.  Synchronous; returns dst."""
+        if mode not in self._FUSE:
+            raise ValueError(f"fuse mode {mode!r}: expected one of {sorted(self._FUSE)}")
+        if dst is None:
+            dst = Gallery(self.dim)
+        check(_lib.lib().fh_gallery_fuse_ids(self._h, dst._h, self._FUSE[mode]), "fh_gallery_fuse_ids")
+        return dst
+
+    def self_scores_dev(self, tmpl: "Gallery", scores_ptr: int, stream: int = 0):
+        """The mislabel audit: scores[r] = (dot(row r, tmpl's row of row r's identity) + 1) / 2, -1 where tmpl lacks the identity;
+        tmpl = the result of fuse() (fh_gallery_self_scores_dev).  Asynchronous on `stream`."""
+        check(_lib.lib().fh_gallery_self_scores_dev(self._h, tmpl._h, scores_ptr, stream), "fh_gallery_self_scores_dev")
+
     def __len__(self) -> int:
         return int(_lib.lib().fh_gallery_size(self._h))
 
@@ -469,6 +495,17 @@ def topk_merge_ids_dev(part_scores_ptr: int, part_ids_ptr: int, part_rows_ptr: i
     their union."""
     return check(_lib.lib().fh_topk_merge_ids_dev(part_scores_ptr, part_ids_ptr, part_rows_ptr, nparts, nq, k, scores_ptr, ids_ptr,
                                                   rows_ptr, stream), "fh_topk_merge_ids_dev")
+
+
+def group_ids(ids):
+    """(order, starts, uniq) of fh_gallery_group_ids — host only: row positions by (id, position), each identity's offset into them
+    (len(uniq) + 1 entries), the distinct ids ascending.  The grouping Gallery.fuse sums by."""
+    ids = np.ascontiguousarray(np.asarray(ids, np.int32).reshape(-1))
+    n = ids.size
+    order, starts, uniq = np.empty(n, np.int32), np.empty(n + 1, np.int64), np.empty(n, np.int32)
+    m = check(_lib.lib().fh_gallery_group_ids(ids.ctypes.data if n else None, n, order.ctypes.data if n else None, starts.ctypes.data,
+                                              uniq.ctypes.data if n else None), "fh_gallery_group_ids")
+    return order, starts[:m + 1].copy(), uniq[:m].copy()
 
 
 def plan_describe(path: str, default_h: int, default_w: int) -> str:

@@ -9,6 +9,7 @@
 
 #include "../../include/facehip.h"
 #include "engine.h"
+#include "group_ids.h"
 
 static_assert(sizeof(fh_face) == 60 && sizeof(fh::FaceRec) == 60, "FaceBox mirror must stay 60 bytes");
 static_assert(sizeof(fh_frame) == 24 && sizeof(fh::FrameIn) == 24 && offsetof(fh_frame, rows) == offsetof(fh::FrameIn, rows) &&
@@ -902,6 +903,38 @@ int fh_topk_merge_ids_dev(const float* ps, const int* pd, const int* pr, int npa
         FH_HIP(hipGetLastError());
         return nq;
     });
+}
+
+// ---- template pooling (gallery_fuse.hip) and what goes with it: the grouping on the host, the rows read back, the mislabel audit
+long long fh_gallery_group_ids(const int* ids, long long n, int* order, long long* starts, int* uniq) {
+    if (n < 0 || (n > 0 && !ids)) return arg_error("fh_gallery_group_ids: bad argument");
+    long long m = -1;
+    const int rc = guarded([&] { m = fh::group_ids(ids, n, order, starts, uniq); return 0; });      // (the sort may run out of memory)
+    if (rc < 0) return rc;
+    return m < 0 ? arg_error("fh_gallery_group_ids: negative id (or more than 2^31 - 1 rows)") : m;
+}
+long long fh_gallery_fuse_ids(fh_gallery* src, fh_gallery* dst, int mode) {
+    if (!src || !dst || src == dst) return arg_error("fh_gallery_fuse_ids: need two different galleries");
+    if (src->g.dim() != dst->g.dim()) return arg_error("fh_gallery_fuse_ids: the galleries' dims differ");
+    if (mode != FH_FUSE_UNIT && mode != FH_FUSE_SUM) return arg_error("fh_gallery_fuse_ids: unknown mode");
+    if (src->g.size() > 0 && !src->g.labelled()) {
+        g_err = "gallery: fh_gallery_fuse_ids needs a labelled gallery (rows enrolled with ids)";
+        return FH_ERR_STATE;
+    }
+    long long m = 0;
+    const int rc = guarded([&] { m = dst->g.fuse_from(src->g, mode == FH_FUSE_UNIT, FH_FUSE_CHUNK); return 0; });
+    return rc < 0 ? rc : m;
+}
+long long fh_gallery_get_rows(fh_gallery* g, long long first, long long n, float* rows_host_out) {
+    if (!g || first < 0 || n < 0 || (n > 0 && !rows_host_out)) return arg_error("fh_gallery_get_rows: bad argument");
+    if (first + n > (long long)g->g.size()) return arg_error("fh_gallery_get_rows: range outside the gallery");
+    const int rc = guarded([&] { g->g.get_rows((long)first, (long)n, rows_host_out); return 0; });
+    return rc < 0 ? rc : n;
+}
+int fh_gallery_self_scores_dev(fh_gallery* src, fh_gallery* tmpl, float* d_scores, void* stream) {
+    if (!src || !tmpl || !d_scores) return arg_error("fh_gallery_self_scores_dev: null argument");
+    if (src->g.dim() != tmpl->g.dim()) return arg_error("fh_gallery_self_scores_dev: the galleries' dims differ");
+    return guarded([&] { src->g.self_scores_dev(tmpl->g, d_scores, S(stream)); return (int)FH_OK; });
 }
 
 int fh_debug_topk_merge_strided_dev(const float* ps, const int* pi, int nparts, int nq, int k, long long part_stride, float* scores, int* indices,

@@ -1,6 +1,8 @@
 // engine.cpp — weight upload, arena management and the launch sequences of the face path.
 #include "engine.h"
 
+#include "group_ids.h"
+
 #include <atomic>
 #include <cstdio>
 #include <cstdlib>
@@ -850,7 +852,7 @@ void Gallery::upload(const float* rows, const int* ids, long n, bool device_src,
     if (ids) ids_.ensure(rows_.bytes / ((size_t)dim_ * sizeof(float)) * sizeof(int));
     FH_HIP(hipMemcpy(rows_.p, rows, (size_t)n * dim_ * sizeof(float), device_src ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
     if (ids) FH_HIP(hipMemcpy(ids_.p, ids, (size_t)n * sizeof(int), device_src ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
-    n_ = n; base_ = index_base; labelled_ = ids != nullptr;
+    n_ = n; base_ = index_base; labelled_ = ids != nullptr; fused_ = false;
     if (scan_ == 1) {
         rows16_.ensure((size_t)n * dim_ * sizeof(uint16_t));
         convert16(0, n);
@@ -940,6 +942,7 @@ long Gallery::enroll(const float* rows, const int* ids, long n, bool device_src)
         FH_HIP(hipMemcpy(ids_.as<int>() + n_, ids, (size_t)n * sizeof(int), device_src ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
     }
     if (n_ == 0) labelled_ = ids != nullptr;
+    fused_ = false;                                              // appended ids are neither distinct nor in order
     const long first = base_ + n_;
     n_ += n;
     return first;
@@ -953,6 +956,71 @@ void Gallery::get_ids(long first, long n, int* out_host) {
     need_labelled("fh_gallery_get_ids");
     if (first < 0 || n < 0 || first + n > n_) throw std::invalid_argument("gallery: id range outside the gallery");
     if (n > 0) FH_HIP(hipMemcpy(out_host, ids_.as<int>() + first, (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
+}
+
+void Gallery::get_rows(long first, long n, float* out_host) {
+    if (first < 0 || n < 0 || first + n > n_) throw std::invalid_argument("gallery: row range outside the gallery");
+    if (n > 0) FH_HIP(hipMemcpy(out_host, rows_.as<float>() + (size_t)first * dim_, (size_t)n * dim_ * sizeof(float), hipMemcpyDeviceToHost));
+}
+
+// Template pooling.  The host reads src's ids (as remove_ids does), groups them (group_ids.h: the one definition of the grouping) and
+// turns the groups into work items of at most `chunk` rows: an identity of one chunk is summed straight into its row, a longer one
+// chunk by chunk into scratch partials that a second launch adds in chunk order (gallery_fuse.hip).  Everything is computed before a
+// member of this gallery changes, except that its buffers may have grown.
+long Gallery::fuse_from(Gallery& src, bool unit, int chunk) {
+    if (dim_ % 64) throw std::runtime_error("gallery: dim must be a multiple of 64");
+    if (src.n_ == 0) {                                           // nothing to read, nothing to launch: the capacity stays
+        n_ = 0; base_ = 0; fused_ = true;
+        return 0;
+    }
+    FH_HIP(hipDeviceSynchronize());                              // queued scans of either handle still read what is about to change
+    const long n = src.n_;
+    std::vector<int> ids((size_t)n), order((size_t)n), uniq((size_t)n);
+    std::vector<long long> starts((size_t)n + 1);
+    FH_HIP(hipMemcpy(ids.data(), src.ids_.p, (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
+    const long m = (long)group_ids(ids.data(), n, order.data(), starts.data(), uniq.data());
+    if (m <= 0) throw std::runtime_error("gallery: the gallery's ids cannot be grouped (a negative id, or more rows than an int counts)");
+    std::vector<FuseItem> items, finish;
+    items.reserve((size_t)m);
+    int parts = 0;
+    for (long j = 0; j < m; ++j) {
+        const long b = (long)starts[(size_t)j], cnt = (long)starts[(size_t)j + 1] - b;
+        if (cnt <= chunk) { items.push_back({(int)b, (int)cnt, (int)j, 1}); continue; }
+        const int first = parts;
+        for (long c = 0; c < cnt; c += chunk) items.push_back({(int)(b + c), (int)std::min<long>(chunk, cnt - c), parts++, 0});
+        finish.push_back({first, parts - first, (int)j, 1});
+    }
+    const size_t row_bytes = (size_t)dim_ * sizeof(float), n1 = items.size(), n2 = finish.size();
+    items.insert(items.end(), finish.begin(), finish.end());
+    DevBuf d_order, d_items, d_part;
+    d_order.ensure((size_t)n * sizeof(int));
+    d_items.ensure(items.size() * sizeof(FuseItem));
+    if (parts > 0) d_part.ensure((size_t)parts * row_bytes);
+    FH_HIP(hipMemcpy(d_order.p, order.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice));
+    FH_HIP(hipMemcpy(d_items.p, items.data(), items.size() * sizeof(FuseItem), hipMemcpyHostToDevice));
+    rows_.ensure((size_t)m * row_bytes);
+    ids_.ensure(rows_.bytes / row_bytes * sizeof(int));          // the ids' capacity follows the rows', as upload keeps it
+    FH_HIP(hipMemcpy(ids_.p, uniq.data(), (size_t)m * sizeof(int), hipMemcpyHostToDevice));
+    launch_gallery_fuse_sum(src.rows_.as<float>(), d_order.as<int>(), d_items.as<FuseItem>(), (long)n1, dim_, rows_.as<float>(),
+                            d_part.as<float>(), unit, nullptr);
+    launch_gallery_fuse_sum(d_part.as<float>(), nullptr, d_items.as<FuseItem>() + n1, (long)n2, dim_, rows_.as<float>(), nullptr, unit, nullptr);
+    FH_HIP(hipGetLastError());
+    FH_HIP(hipDeviceSynchronize());
+    n_ = m; base_ = 0; labelled_ = true; fused_ = true;
+    if (scan_ == 1) {
+        rows16_.ensure((size_t)m * dim_ * sizeof(uint16_t));
+        convert16(0, m);
+    }
+    return m;
+}
+
+void Gallery::self_scores_dev(const Gallery& tmpl, float* out, hipStream_t s) {
+    need_labelled("fh_gallery_self_scores_dev");
+    if (!tmpl.fused_)
+        throw std::runtime_error("gallery: fh_gallery_self_scores_dev needs a template gallery that fh_gallery_fuse_ids made (and no upload / enroll since)");
+    if (n_ == 0) return;
+    launch_gallery_self_scores(rows_.as<float>(), ids_.as<int>(), n_, tmpl.rows_.as<float>(), tmpl.ids_.as<int>(), tmpl.n_, dim_, out, s);
+    FH_HIP(hipGetLastError());
 }
 
 // Stable compaction through a second buffer: the host reads the ids, lists the surviving positions in order, and whole rows are

@@ -246,6 +246,14 @@ class Gallery {
     // fp16 rows exist twice, plus 4 bytes per survivor); synchronous; returns the number of rows removed
     long remove_ids(const int* ids_host, long n_ids);
     void get_ids(long first, long n, int* out_host);
+    void get_rows(long first, long n, float* out_host);           // fp32 rows by position, either kind of gallery
+    // Template pooling (gallery_fuse.hip): THIS gallery is replaced by one row per identity of src, ascending ids, index base 0 — the
+    // identity's rows summed in the fixed chunked order (chunks of `chunk` rows), normalised when `unit`.  Synchronous; returns the
+    // number of identities.  src must be another gallery of the same dim, labelled unless empty (the caller checks the first two).
+    long fuse_from(Gallery& src, bool unit, int chunk);
+    bool fused() const { return fused_; }                        // ids distinct and ascending: set by fuse_from, cleared by upload / enroll
+    // out[r] = (dot(row r, tmpl's row of row r's id) + 1) / 2, -1 where tmpl has no such id; tmpl.fused() required.  Asynchronous.
+    void self_scores_dev(const Gallery& tmpl, float* out, hipStream_t s);
     bool labelled() const { return labelled_; }
     long size() const { return n_; }
     int dim() const { return dim_; }
@@ -265,6 +273,7 @@ class Gallery {
     int dim_;
     long n_ = 0, base_ = 0;
     bool labelled_ = false;                                      // meaningful while n_ > 0; an empty gallery takes either kind
+    bool fused_ = false;
     DevBuf rows_, qpack_, ps_, pi_, best_i_, seed_s_, seed_i_;
     DevBuf ids_, pd_, seed_d_;                                   // identity id per row (capacity in rows = rows_'), id planes of the part / seed lists
     // F16_RERANK state: the fp16 rows, [max|g|, max|g^|, max|g - g^| (float bits), non-finite / > 65504 flag] on the device and its host

@@ -320,6 +320,17 @@ void launch_ids_of_rows(const float* score, const int* idx, int n, const int* id
 void launch_gather_rows(const void* src, void* dst, const int* map, long m, size_t row_bytes, hipStream_t s);
 void launch_gather_ids(const int* src, int* dst, const int* map, long m, hipStream_t s);
 
+// gallery_fuse.hip — template pooling (fh_gallery_fuse_ids): one wave per work item sums the rows src[order[begin + i]], i < count,
+// strictly in that order (p = row0; p = p + row1; ...), into row `out` of dst (final != 0; L2-normalised when `unit` and count > 1: a
+// one-row list is copied verbatim) or of the scratch `part` (final == 0: a chunk's partial sum, never normalised).  order == nullptr:
+// the list is the consecutive rows begin .. begin + count of src (an identity's partials, added in chunk order by a second launch).
+struct FuseItem { int begin, count, out, final; };
+void launch_gallery_fuse_sum(const float* src, const int* order, const FuseItem* items, long n_items, int dim, float* dst, float* part,
+                             bool unit, hipStream_t s);
+// out[r] = (dot(src row r, the tmpl row whose id is src_ids[r]) + 1) / 2, or -1 when tmpl_ids (ascending, distinct, m of them) lacks it
+void launch_gallery_self_scores(const float* src, const int* src_ids, long n, const float* tmpl, const int* tmpl_ids, long m, int dim,
+                                float* out, hipStream_t s);
+
 // gallery_f16.hip — the opt-in F16_RERANK scan (fh_gallery_set_scan): an fp16 copy of the rows is scanned for the top GAL16_KC candidates
 // per query, the candidates are re-scored from the fp32 rows exactly as gallery_topk_kernel scores them, and a per-query certificate
 // proves that no other row can reach the top-k; uncertified queries are compacted on the device (fb_count / fb_idx) for the fp32 scan.

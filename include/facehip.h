@@ -297,7 +297,7 @@ FH_API int fh_gallery_label_dev(fh_gallery* g, const float* d_queries, int nq, f
  *             keep their order and move down, so the global indices of later rows shrink; index_base stays.  It goes through a
  *             second buffer: transiently the surviving rows (fp32, ids, the fp16 copy of F16_RERANK) are held twice, plus 4 bytes
  *             per surviving row.  After removing everything the gallery is empty: queries answer -1, enrolment starts afresh.
- *   get_ids   the ids of rows [first, first + n) by position (persistence, tests); returns n.
+ *   get_ids   the ids of rows [first, first + n) by position (persistence, tests; fh_gallery_get_rows returns the rows); returns n.
  *   merge_ids the merge step of a row-SHARDED labelled gallery: part w = the identity top-k of shard w, [nparts][nq][k] in three
  *             planes as topk_ids writes them -> the identity top-k of the union (per-part lists suffice: an identity of the answer
  *             is listed, with its representative, by the part that holds it).  nparts * k <= 65536. */
@@ -311,6 +311,48 @@ FH_API long long fh_gallery_remove_ids(fh_gallery* g, const int* ids_host, long 
 FH_API long long fh_gallery_get_ids(fh_gallery* g, long long first, long long n, int* ids_host_out);
 FH_API int fh_topk_merge_ids_dev(const float* d_part_scores, const int* d_part_ids, const int* d_part_rows, int nparts, int nq, int k,
                                  float* d_scores, int* d_ids, int* d_rows, void* stream);
+
+/* ---- template pooling: one row per PERSON.  A labelled gallery keeps every template as a row for ever: the scan grows with templates,
+ * not with people, and an identity list (k > 1) is closed to F16_RERANK.  fh_gallery_fuse_ids builds, on the device, the gallery that
+ * holds one row per identity — the L2-normalised sum of that identity's rows — so that the identity top-k IS the row top-k
+ * (fh_gallery_topk_dev / fh_gallery_topk_ids_dev) of a gallery T times smaller, in either scan mode; pooling changes scores by design.
+ *   group_ids   host only, no GPU, and the one place the grouping is defined (fuse_ids groups through it): order[n] = the row positions
+ *               sorted by (id ascending, position ascending), uniq[m] = the distinct ids, ascending, starts[m + 1] = each identity's
+ *               offset into order; returns m.  Any of the three output pointers may be NULL.  A negative id (or n > 2^31 - 1) returns
+ *               FH_ERR_ARG; n == 0 returns 0.
+ *   fuse_ids    dst is replaced entirely, as by fh_gallery_upload_ids with index base 0: a labelled gallery of m rows in ascending id
+ *               order, row j carrying uniq[j]; returns m.  Synchronous, like remove_ids, and like it waits first for the work queued on
+ *               both handles (an empty src needs no wait: nothing is read, freed or rewritten, dst only forgets its rows).  fp32 throughout, and the ORDER of the additions is part of the contract, so a result reproduces bit for
+ *               bit: an identity with one template keeps that row verbatim (the same bits, not re-normalised, in both modes); otherwise
+ *               the identity's rows, in row order, are cut into chunks of FH_FUSE_CHUNK rows, each chunk is summed sequentially from its
+ *               first row (p = row0; p = p + row1; ...), and the chunk partials are added sequentially in chunk order.  FH_FUSE_SUM
+ *               stores that sum (for callers that keep running sums, and for exact tests); FH_FUSE_UNIT applies FaceRecognizer::normalize
+ *               (src/face_recognizer.cpp:306-318): divided by sqrt(sum s^2) when that is > 0, else left as it is (a cancelled sum stays
+ *               zero, a NaN stays NaN).  dst keeps its scan mode; with F16_RERANK its fp16 copy, bounds and bad-value flag are rebuilt as
+ *               upload does.  The argument and state errors change nothing: NULL handle, src == dst, unequal dims or an unknown mode ->
+ *               FH_ERR_ARG; a non-empty unlabelled src -> FH_ERR_STATE.  Past those checks a failure leaves dst undefined until its next
+ *               upload or fuse (its buffers may have grown and its ids been rewritten): FH_ERR_DEVICE for a failed allocation, copy or
+ *               launch, FH_ERR_STATE for a src whose device ids cannot be grouped (a negative id, which no entry point lets in, or more
+ *               than 2^31 - 1 rows) or a host allocation that failed.  An empty src empties dst and returns 0.  Transient device memory: 4 bytes per src row,
+ *               16 bytes per work item, one scratch row per chunk of an identity longer than one chunk.  The ids are grouped on the host
+ *               (a sort) and that sort IS the call's time: measured at 1 M x 512 with 8 templates per identity, 52 ms for the call, the
+ *               sum kernel 0.43 - 0.48 ms of it (profiles/gallery_fuse.md) — a maintenance call that sits beside remove_ids, not a
+ *               per-frame one.  Fusion is PER GALLERY: a sharded deployment fuses first and shards the fused gallery; fusing each shard
+ *               would leave a person whose templates straddle shards with one row per shard.
+ *   get_rows    the fp32 rows [first, first + n) by position, of either kind of gallery (persistence next to get_ids; tests); argument
+ *               and range checks as fh_gallery_get_ids; returns n.
+ *   self_scores the mislabel audit: d_scores[r] (device, one float per row of src) = (dot(src row r, the row of tmpl whose id is src's
+ *               id of row r) + 1) / 2 in fp32, -1.0f when tmpl has no such id; a template that is somebody else's face scores far
+ *               below its identity's other rows.  tmpl must be the result of fh_gallery_fuse_ids, possibly after fh_gallery_remove_ids
+ *               (which keeps ids distinct and ascending): the handle remembers that, upload and enroll forget it, and any other tmpl
+ *               returns FH_ERR_STATE, as does a non-empty unlabelled src.  NULL or unequal dims -> FH_ERR_ARG.  Asynchronous on `stream`;
+ *               returns FH_OK. */
+#define FH_FUSE_CHUNK 512
+enum fh_gallery_fuse { FH_FUSE_UNIT = 0, FH_FUSE_SUM = 1 };
+FH_API long long fh_gallery_group_ids(const int* ids, long long n, int* order, long long* starts, int* uniq);
+FH_API long long fh_gallery_fuse_ids(fh_gallery* src, fh_gallery* dst, int mode);
+FH_API long long fh_gallery_get_rows(fh_gallery* g, long long first, long long n, float* rows_host_out);
+FH_API int fh_gallery_self_scores_dev(fh_gallery* src, fh_gallery* tmpl, float* d_scores, void* stream);
 
 /* ---- measurement hooks (bench.py): per-launch HIP-event timing of the network kernels.
  * Tags 0..3 = conv_igemm tile configs (128x128, 256x64, 128x32, 64x64), 4 = depthwise / depthwise+pointwise,
