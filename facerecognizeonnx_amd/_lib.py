@@ -30,6 +30,16 @@ class FhFrame(C.Structure):
     _fields_ = [("bgr", C.c_void_p), ("rows", C.c_int32), ("cols", C.c_int32), ("step", C.c_int32)]
 
 
+class FhTiling(C.Structure):
+    """fh_tiling: tile size, overlap and border of a tiled detection.  16 bytes."""
+    _fields_ = [("tile_w", C.c_int32), ("tile_h", C.c_int32), ("overlap", C.c_int32), ("border", C.c_int32)]
+
+
+class FhView(C.Structure):
+    """fh_view: one view of a tile plan (edges: bit 0 left, 1 top, 2 right, 3 bottom = interior).  20 bytes."""
+    _fields_ = [("x", C.c_int32), ("y", C.c_int32), ("w", C.c_int32), ("h", C.c_int32), ("edges", C.c_int32)]
+
+
 def build(force: bool = False) -> str:
     """Compile libfacehip.so in-tree (so that it travels with the source snapshot)."""
     srcs = [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [os.path.join(_HERE, "..", "include", "facehip.h")]
@@ -101,6 +111,12 @@ PROTOTYPES = {
     "fh_rec_embed_faces_ragged_dev": (_i, [_vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp]),
     "fh_pipeline_run_ragged_dev": (_i, [_vp, _vp, _vp, _i, _f, _f, _i, _vp, _vp, _vp, _vp]),
     "fh_pipeline_run_images": (_i, [_vp, _vp, _vp, _i, _f, _f, _i, _vp, _vp, _vp, _i]),
+    "fh_tile_plan": (_i, [_i, _i, _vp, _vp, _i]),
+    "fh_det_detect_tiled_dev": (_i, [_vp, _vp, _i, _vp, _f, _f, _vp, _i, _vp, _vp]),
+    "fh_det_run_network_tiled_dev": (_i, [_vp, _vp, _i, _vp, _vp]),
+    "fh_postprocess_rows_tiled_dev": (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _f, _f, _vp, _i, _vp, _vp]),
+    "fh_pipeline_run_tiled_dev": (_i, [_vp, _vp, _vp, _i, _vp, _f, _f, _i, _vp, _vp, _vp, _vp]),
+    "fh_det_detect_tiled": (_i, [_vp, _vp, _i, _i, _i, _vp, _f, _f, _vp, _i]),
     "fh_stream_create": (_vp, [_vp, _vp, _i, _i, _i, _i]),
     "fh_stream_destroy": (None, [_vp]),
     "fh_stream_submit": (_i, [_vp, _vp, _i, _f, _f]),

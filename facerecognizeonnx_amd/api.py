@@ -84,6 +84,27 @@ def letterbox_plan(rows: int, cols: int, in_w: int, in_h: int):
     return bool(live), nw.value, nh.value, float(sc.value)
 
 
+def Tiling(tile, overlap: int = 0, border: int = 2):
+    """An fh_tiling for the tiled calls: tile = the side of a square tile or (tile_w, tile_h); border < 0 switches the border rule
+    off.  (FaceDetector.tiling fills `tile` with the detector's input size.)"""
+    tw, th = (tile, tile) if np.isscalar(tile) else tile
+    return _lib.FhTiling(int(tw), int(th), int(overlap), int(border))
+
+
+def _tiling(t):
+    return t if isinstance(t, _lib.FhTiling) else Tiling(*t)
+
+
+def tile_plan(rows: int, cols: int, tile, overlap: int = 0, border: int = 2):
+    """The views of a tiled detection of a rows x cols frame (fh_tile_plan, host code): a list of (x, y, w, h, edges), view 0 the
+    whole frame, then the tiles row-major; edges bit 0 left, 1 top, 2 right, 3 bottom = that edge is interior."""
+    t = Tiling(tile, overlap, border)
+    n = check(_lib.lib().fh_tile_plan(int(rows), int(cols), C.byref(t), None, 0), "fh_tile_plan")
+    views = (_lib.FhView * max(n, 1))()
+    n = check(_lib.lib().fh_tile_plan(int(rows), int(cols), C.byref(t), views, n), "fh_tile_plan")
+    return [(v.x, v.y, v.w, v.h, v.edges) for v in views[:n]]
+
+
 class FaceDetector:
     def __init__(self):
         self._h = None
@@ -151,6 +172,35 @@ class FaceDetector:
         arr = frame_array(frames)
         return check(_lib.lib().fh_det_detect_ragged_dev(self._h, arr, _frame_count(arr), scoreThreshold, nmsThreshold, out_ptr,
                                                          max_per_frame, counts_ptr, stream), "fh_det_detect_ragged_dev")
+
+    def tiling(self, tile=None, overlap: int = 0, border: int = 2):
+        """A Tiling whose tile defaults to this detector's input size (views of that size reach the network at scale 1)."""
+        return Tiling(self.input_size() if tile is None else tile, overlap, border)
+
+    def detect_tiled_dev(self, frames, tiling, out_ptr: int, max_per_frame: int, counts_ptr: int, scoreThreshold: float = 0.5,
+                         nmsThreshold: float = 0.4, stream: int = 0) -> int:
+        """detect_ragged_dev on the whole frame AND overlapping tiles of it, merged by one NMS per frame (fh_det_detect_tiled_dev);
+        tiling = Tiling(...) / self.tiling(...) or a (tile, overlap, border) tuple."""
+        arr, t = frame_array(frames), _tiling(tiling)
+        return check(_lib.lib().fh_det_detect_tiled_dev(self._h, arr, _frame_count(arr), C.byref(t), scoreThreshold, nmsThreshold,
+                                                        out_ptr, max_per_frame, counts_ptr, stream), "fh_det_detect_tiled_dev")
+
+    def detect_tiled_records(self, image, tiling=None, scoreThreshold: float = 0.5, nmsThreshold: float = 0.4,
+                             max_faces: Optional[int] = None) -> np.ndarray:
+        """detect_records with tiled detection on one host image (fh_det_detect_tiled); tiling defaults to self.tiling()."""
+        if not self._h:
+            return np.zeros(0, FACE_DTYPE)
+        a = _img(image)
+        if a is None:
+            return np.zeros(0, FACE_DTYPE)
+        t = self.tiling() if tiling is None else _tiling(tiling)
+        if max_faces is None:                                         # every candidate of every view can survive
+            views = check(_lib.lib().fh_tile_plan(a.shape[0], a.shape[1], C.byref(t), None, 0), "fh_tile_plan")
+            max_faces = max(1, self.num_anchors() * views)
+        out = np.zeros(max_faces, FACE_DTYPE)
+        n = check(_lib.lib().fh_det_detect_tiled(self._h, a.ctypes.data, a.shape[0], a.shape[1], a.strides[0], C.byref(t),
+                                                  scoreThreshold, nmsThreshold, out.ctypes.data, max_faces), "fh_det_detect_tiled")
+        return out[:n].copy()
 
     def sync(self, stream: int = 0) -> None:
         """Waits for `stream`; raises if a launch of this handle failed after its asynchronous call returned (fh_det_sync)."""
@@ -262,6 +312,16 @@ def pipeline_run_ragged_dev(det: FaceDetector, rec: FaceRecognizer, frames, face
     return check(_lib.lib().fh_pipeline_run_ragged_dev(det.handle, rec.handle, arr, _frame_count(arr), scoreThreshold, nmsThreshold,
                                                        faces_per_frame, faces_ptr, frame_of_ptr, emb_ptr, stream),
                  "fh_pipeline_run_ragged_dev")
+
+
+def pipeline_run_tiled_dev(det: FaceDetector, rec: FaceRecognizer, frames, tiling, faces_per_frame: int, faces_ptr: int,
+                           frame_of_ptr: int, emb_ptr: int, scoreThreshold: float = 0.5, nmsThreshold: float = 0.4,
+                           stream: int = 0) -> int:
+    """pipeline_run_ragged_dev with tiled detection (fh_pipeline_run_tiled_dev); tiling as FaceDetector.detect_tiled_dev."""
+    arr, t = frame_array(frames), _tiling(tiling)
+    return check(_lib.lib().fh_pipeline_run_tiled_dev(det.handle, rec.handle, arr, _frame_count(arr), C.byref(t), scoreThreshold,
+                                                      nmsThreshold, faces_per_frame, faces_ptr, frame_of_ptr, emb_ptr, stream),
+                 "fh_pipeline_run_tiled_dev")
 
 
 def pipeline_images(det: FaceDetector, rec: FaceRecognizer, images, faces_per_frame: int = 1, scoreThreshold: float = 0.5,

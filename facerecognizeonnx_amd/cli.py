@@ -1,6 +1,6 @@
 """Text-mode counterpart of the reference's demo executable (reference src/main.cpp:264-319):
 
-    python -m facerecognizeonnx_amd.cli detect  <image>            [--det det.onnx]
+    python -m facerecognizeonnx_amd.cli detect  <image>            [--det det.onnx] [--tile N --overlap M [--border B]]
     python -m facerecognizeonnx_amd.cli compare <image1> <image2>  [--det det.onnx] [--rec rec.onnx]
     python -m facerecognizeonnx_amd.cli simple  <image1> <image2>  [--rec rec.onnx]
 
@@ -8,6 +8,7 @@ Same flows as testDetection / testRecognition / testRecognitionSimple (main.cpp:
 faces[0] of each image, extractFeature, compareFaces, threshold 0.6 — but boxes / scores / similarity
 are printed instead of drawn (no GUI, no webcam).  Images are read by the library's own cv::imread replacement
 (fh_imread: JPEG / PNG / BMP / PPM -> BGR u8) or from `.npy` arrays of shape [rows, cols, 3] (BGR u8).
+`detect --tile N` runs the tiled detection of large frames (whole frame + overlapping N x N tiles, one merged NMS; facehip.h).
 Model paths default to the reference's (models/det_500m.onnx, models/w600k_r50.onnx, main.cpp:269-270).
 """
 from __future__ import annotations
@@ -35,6 +36,9 @@ def main(argv=None) -> int:
     ap.add_argument("--rec", default="models/w600k_r50.onnx")
     ap.add_argument("--score", type=float, default=0.5)
     ap.add_argument("--nms", type=float, default=0.4)
+    ap.add_argument("--tile", type=int, default=0, help="detect: tile side in pixels (0 = plain detection)")
+    ap.add_argument("--overlap", type=int, default=0, help="detect --tile: overlap of neighbouring tiles in pixels")
+    ap.add_argument("--border", type=int, default=2, help="detect --tile: drop boxes within this many pixels of an interior tile edge (< 0: off)")
     a = ap.parse_args(argv)
     det, rec = FaceDetector(), FaceRecognizer()
     if a.mode != "simple" and not det.loadModel(a.det):
@@ -49,7 +53,11 @@ def main(argv=None) -> int:
             print(f"Cannot read image: {p}", file=sys.stderr)                   # main.cpp:43-46
             return -1
     if a.mode == "detect":                                                     # main.cpp:39-65
-        faces = det.detect(imgs[0], a.score, a.nms)
+        if a.tile > 0:
+            recs = det.detect_tiled_records(imgs[0], api.Tiling(a.tile, a.overlap, a.border), a.score, a.nms)
+            faces = [api.FaceBox.from_record(r) for r in recs]
+        else:
+            faces = det.detect(imgs[0], a.score, a.nms)
         print(f"Detected {len(faces)} faces")
         for i, f in enumerate(faces):
             print(f"Face {i}: box={f.box} score={f.score:.4f} landmarks={np.round(f.landmarks, 1).tolist()}")

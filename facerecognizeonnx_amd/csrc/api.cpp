@@ -14,6 +14,9 @@
 static_assert(sizeof(fh_face) == 60 && sizeof(fh::FaceRec) == 60, "FaceBox mirror must stay 60 bytes");
 static_assert(sizeof(fh_frame) == 24 && sizeof(fh::FrameIn) == 24 && offsetof(fh_frame, rows) == offsetof(fh::FrameIn, rows) &&
               offsetof(fh_frame, step) == offsetof(fh::FrameIn, step), "fh_frame and the engine's FrameIn are one layout");
+static_assert(sizeof(fh_tiling) == sizeof(fh::Tiling) && offsetof(fh_tiling, border) == offsetof(fh::Tiling, border) &&
+              sizeof(fh_view) == sizeof(fh::View) && offsetof(fh_view, edges) == offsetof(fh::View, edges) &&
+              FH_TILE_MAX_VIEWS == fh::kTileMaxViews && FH_ERR_ARG == fh::kTilePlanBadArg, "fh_tiling / fh_view mirror tile_plan.h");
 
 namespace {
 thread_local std::string g_err;
@@ -66,6 +69,25 @@ const char* bad_frames(const fh_frame* frames, int n) {
 }
 int frames_error(const char* fn, const char* what) { g_err = std::string(fn) + ": " + what; return FH_ERR_ARG; }
 const fh::FrameIn* FI(const fh_frame* f) { return reinterpret_cast<const fh::FrameIn*>(f); }
+const fh::Tiling& TL(const fh_tiling* t) { return *reinterpret_cast<const fh::Tiling*>(t); }
+// the view count of a tiled call (empty frames have none), or -1: a bad tiling or more than FH_TILE_MAX_VIEWS views.  Host arithmetic
+// only — every tiled entry point asks this before it launches anything.
+int tiled_view_total(const int* rows, const int* cols, const fh_frame* frames, int n, const fh_tiling* t) {
+    long long total = 0;
+    for (int i = 0; i < n; ++i) {
+        if (frames && !frames[i].bgr) continue;
+        const int c = fh::tile_plan(frames ? frames[i].rows : rows[i], frames ? frames[i].cols : cols[i], &TL(t), nullptr, 0);
+        if (c < 0) return -1;
+        total += c;
+        if (total > FH_TILE_MAX_VIEWS) return -1;
+    }
+    return (int)total;
+}
+const char* bad_tiling(const fh_tiling* t) {
+    if (!t) return "null tiling";
+    if (!fh::tiling_ok(&TL(t))) return "need tile_w, tile_h >= 16 and 0 <= overlap < min(tile_w, tile_h)";
+    return nullptr;
+}
 }  // namespace
 
 namespace fh {
@@ -157,6 +179,7 @@ struct fh_det {
     int* h_total = nullptr;              // pinned landing word of the face count
     PinnedBuf h_arena;                   // fh_pipeline_run_images: the live images packed row by row / their device copy / device results
     fh::DevBuf arena, i_faces, i_fo, i_emb;
+    fh::DevBuf t_img, t_out;             // fh_det_detect_tiled: the image on the device / its records + count
     ~fh_det() { if (ev_sel) (void)hipEventDestroy(ev_sel); if (h_total) (void)hipHostFree(h_total); }
 };
 struct fh_rec {
@@ -300,6 +323,62 @@ int fh_det_detect_ragged_dev(fh_det* d, const fh_frame* frames, int n, float sco
     });
 }
 
+// ---------------------------------------------------------------------------------- tiled detection (detector side)
+int fh_tile_plan(int rows, int cols, const fh_tiling* t, fh_view* views, int cap) {
+    const int c = fh::tile_plan(rows, cols, reinterpret_cast<const fh::Tiling*>(t), reinterpret_cast<fh::View*>(views), cap);
+    if (c < 0) g_err = "fh_tile_plan: bad tiling, or more views than cap";
+    return c;
+}
+int fh_det_run_network_tiled_dev(fh_det* d, const fh_frame* frames, int n, const fh_tiling* t, void* stream) {
+    if (!d) return arg_error("fh_det_run_network_tiled_dev: null handle");
+    if (const char* bad = bad_frames(frames, n)) return frames_error("fh_det_run_network_tiled_dev", bad);
+    if (const char* bad = bad_tiling(t)) return frames_error("fh_det_run_network_tiled_dev", bad);
+    if (tiled_view_total(nullptr, nullptr, frames, n, t) < 0) return arg_error("fh_det_run_network_tiled_dev: more than FH_TILE_MAX_VIEWS views");
+    Owns owns(&d->det.net());
+    return guarded([&] { return d->det.run_network_tiled_dev(FI(frames), n, TL(t), S(stream)); });
+}
+int fh_det_detect_tiled_dev(fh_det* d, const fh_frame* frames, int n, const fh_tiling* t, float score_thr, float nms_thr, fh_face* out,
+                            int max_pf, int* counts, void* stream) {
+    if (!d || !out || !counts) return arg_error("fh_det_detect_tiled_dev: null argument");
+    if (const char* bad = bad_frames(frames, n)) return frames_error("fh_det_detect_tiled_dev", bad);
+    if (const char* bad = bad_tiling(t)) return frames_error("fh_det_detect_tiled_dev", bad);
+    if (max_pf <= 0) return arg_error("fh_det_detect_tiled_dev: bad size");
+    if (tiled_view_total(nullptr, nullptr, frames, n, t) < 0) return arg_error("fh_det_detect_tiled_dev: more than FH_TILE_MAX_VIEWS views");
+    Owns owns(&d->det.net());
+    return guarded([&] {
+        d->det.detect_tiled_dev(FI(frames), n, TL(t), score_thr, nms_thr, reinterpret_cast<fh::FaceRec*>(out), max_pf, counts, S(stream));
+        return n;
+    });
+}
+// FaceDetector::detect on ONE host image, tiled: upload, fh_det_detect_tiled_dev with n = 1, fetch.  Blocking and eager.
+int fh_det_detect_tiled(fh_det* d, const uint8_t* bgr, int rows, int cols, int step, const fh_tiling* t, float score_thr, float nms_thr,
+                        fh_face* out, int max_out) {
+    if (!d) return arg_error("Model not loaded!");                       // src/face_detector.cpp:142-145
+    if (const char* bad = bad_tiling(t)) return frames_error("fh_det_detect_tiled", bad);
+    if (!bgr || rows <= 0 || cols <= 0) return 0;                        // :148-156 -> empty result
+    if (!out || max_out <= 0 || step < cols * 3) return arg_error("fh_det_detect_tiled: bad output buffer / step");
+    const fh_frame host{bgr, rows, cols, step};
+    if (tiled_view_total(nullptr, nullptr, &host, 1, t) < 0) return arg_error("fh_det_detect_tiled: more than FH_TILE_MAX_VIEWS views");
+    Owns owns(&d->det.net());
+    return guarded([&] {
+        const size_t used = host_image_bytes(rows, cols, step);
+        hipStream_t s = d->cs.get();
+        FH_HIP(hipStreamSynchronize(s));
+        d->t_img.ensure(used);
+        d->t_out.ensure((size_t)max_out * sizeof(fh_face) + sizeof(int));
+        int* const d_cnt = reinterpret_cast<int*>(d->t_out.as<fh_face>() + max_out);
+        const fh_frame f{d->t_img.as<uint8_t>(), rows, cols, step};
+        FH_HIP(hipMemcpyAsync(d->t_img.p, bgr, used, hipMemcpyHostToDevice, s));
+        d->det.detect_tiled_dev(FI(&f), 1, TL(t), score_thr, nms_thr, d->t_out.as<fh::FaceRec>(), max_out, d_cnt, s);
+        int c = 0;
+        FH_HIP(hipMemcpyAsync(&c, d_cnt, sizeof(int), hipMemcpyDeviceToHost, s));
+        FH_HIP(hipStreamSynchronize(s));
+        c = c < max_out ? c : max_out;
+        if (c > 0) FH_HIP(hipMemcpy(out, d->t_out.p, (size_t)c * sizeof(fh_face), hipMemcpyDeviceToHost));
+        return c;
+    });
+}
+
 int fh_det_detect(fh_det* d, const uint8_t* bgr, int rows, int cols, int step, float score_thr, float nms_thr, fh_face* out,
                   int max_out) {
     if (!d) return arg_error("Model not loaded!");                       // src/face_detector.cpp:142-145
@@ -410,6 +489,51 @@ int fh_postprocess_rows_dev(const float* rows, int n, int rows_per_frame, int fe
         fh::launch_sort_nms(cand.as<fh::FaceRec>(), keys.as<unsigned long long>(), count.as<int>(), cap, n, nms_thr,
                             reinterpret_cast<fh::FaceRec*>(out), counts, max_pf, ws.as<int>(), s);
         FH_HIP(hipGetLastError());
+        FH_HIP(hipEventRecord(sc.done, s));
+        sc.last = s; sc.used = true;
+        return n;
+    });
+}
+
+// fh_postprocess_rows_dev's tiled twin: the view-aware threshold + one NMS per frame on caller-supplied rows of every view
+int fh_postprocess_rows_tiled_dev(const float* rows, const int* frame_rows, const int* frame_cols, int n, const fh_tiling* t, int in_w,
+                                  int in_h, int rows_per_view, int feat, float score_thr, float nms_thr, fh_face* out, int max_pf,
+                                  int* counts, void* stream) {
+    if (!rows || !frame_rows || !frame_cols || !out || !counts) return arg_error("fh_postprocess_rows_tiled_dev: null argument");
+    if (const char* bad = bad_tiling(t)) return frames_error("fh_postprocess_rows_tiled_dev", bad);
+    if (n <= 0 || n > 4096 || in_w <= 0 || in_h <= 0 || rows_per_view <= 0 || max_pf <= 0) return arg_error("fh_postprocess_rows_tiled_dev: bad size");
+    if (rows_per_view > (1 << 21)) return arg_error("fh_postprocess_rows_tiled_dev: too many rows per view");   // 2 * 256 * cap keys < 2^31
+    if (tiled_view_total(frame_rows, frame_cols, nullptr, n, t) < 0) return arg_error("fh_postprocess_rows_tiled_dev: more than FH_TILE_MAX_VIEWS views");
+    return guarded([&] {
+        hipStream_t s = S(stream);
+        if (feat < 15) {                                                   // "Unexpected output shape format" :300-303,326-328 -> no boxes
+            FH_HIP(hipMemsetAsync(counts, 0, (size_t)n * sizeof(int), s));
+            return n;
+        }
+        // one scratch set per calling thread, fenced by an event across streams, never destroyed: as fh_postprocess_rows_dev
+        struct Scratch { fh::DevBuf cand, keys, ws, count; fh::TilePlan plan; fh::TileTable tab; hipEvent_t done = nullptr; hipStream_t last = nullptr; bool used = false; };
+        thread_local Scratch* scp = new Scratch();
+        Scratch& sc = *scp;
+        if (!sc.done) FH_HIP(hipEventCreateWithFlags(&sc.done, hipEventDisableTiming));
+        if (sc.used && sc.last != s) FH_HIP(hipStreamWaitEvent(s, sc.done, 0));
+        int cap = 1;
+        while (cap < rows_per_view) cap <<= 1;
+        static const uint8_t live = 0;                                     // (the planner only asks whether a frame HAS pixels)
+        std::vector<fh::FrameIn> fr((size_t)n);
+        for (int i = 0; i < n; ++i) fr[(size_t)i] = fh::FrameIn{&live, frame_rows[i], frame_cols[i], 0};
+        const int V = sc.plan.plan(fr.data(), n, TL(t), in_w, in_h, cap, FH_TILE_MAX_VIEWS);
+        if (V <= 0) {
+            FH_HIP(hipMemsetAsync(counts, 0, (size_t)n * sizeof(int), s));
+            return n;
+        }
+        sc.tab.upload(sc.plan, s);
+        sc.cand.ensure((size_t)V * cap * sizeof(fh::FaceRec));
+        sc.keys.ensure(sc.plan.key_total * sizeof(unsigned long long));
+        sc.ws.ensure(sc.plan.key_total * sizeof(int));
+        sc.count.ensure((size_t)n * sizeof(int));
+        fh::tiled_postprocess(nullptr, rows, rows_per_view, feat, sc.plan, sc.tab, cap, t->border, score_thr, nms_thr, sc.cand.as<fh::FaceRec>(),
+                              sc.keys.as<unsigned long long>(), sc.ws.as<int>(), sc.count.as<int>(), reinterpret_cast<fh::FaceRec*>(out),
+                              max_pf, counts, s);
         FH_HIP(hipEventRecord(sc.done, s));
         sc.last = s; sc.used = true;
         return n;
@@ -635,6 +759,27 @@ int fh_pipeline_run_ragged_dev(fh_det* d, fh_rec* r, const fh_frame* frames, int
     if (F <= 0) return arg_error("fh_pipeline_run_ragged_dev: bad size");
     Owns owns(&d->det.net(), &r->rec.net());
     return guarded([&] { return pipeline_ragged(d, r, frames, n, score_thr, nms_thr, F, faces, frame_of, emb, S(stream)); });
+}
+
+// fh_pipeline_run_ragged_dev over tiled detection: the faces are in FRAME coordinates, so the align reads the detector's table of the
+// frames (the ragged table of that call holds the views)
+int fh_pipeline_run_tiled_dev(fh_det* d, fh_rec* r, const fh_frame* frames, int n, const fh_tiling* t, float score_thr, float nms_thr, int F,
+                              fh_face* faces, int* frame_of, float* emb, void* stream) {
+    if (!d || !r || !faces || !frame_of || !emb) return arg_error("fh_pipeline_run_tiled_dev: null argument");
+    if (const char* bad = bad_frames(frames, n)) return frames_error("fh_pipeline_run_tiled_dev", bad);
+    if (const char* bad = bad_tiling(t)) return frames_error("fh_pipeline_run_tiled_dev", bad);
+    if (F <= 0) return arg_error("fh_pipeline_run_tiled_dev: bad size");
+    if (tiled_view_total(nullptr, nullptr, frames, n, t) < 0) return arg_error("fh_pipeline_run_tiled_dev: more than FH_TILE_MAX_VIEWS views");
+    Owns owns(&d->det.net(), &r->rec.net());
+    return guarded([&] {
+        hipStream_t s = S(stream);
+        const int total = detect_select_count_with(d, n, F, faces, frame_of, nullptr, s, [&](fh::FaceRec* out, int max_pf, int* counts) {
+            d->det.detect_tiled_dev(FI(frames), n, TL(t), score_thr, nms_thr, out, max_pf, counts, s);
+        });
+        r->rec.embed_faces_table_dev(d->det.tiled_frame_table().table(), n, reinterpret_cast<const fh::FaceRec*>(faces), frame_of, total, emb,
+                                     nullptr, s);
+        return total;
+    });
 }
 
 // The per-file enrolment loop (src/main.cpp:42,88-104) as one blocking call on host images of any sizes.

@@ -663,16 +663,16 @@ void Detector::run_network_dev(const uint8_t* frames, int n, int rows, int cols,
 }
 
 // ------------------------------------------------------------------------------------------ mixed-size batches
-FrameTable::~FrameTable() {
+StagedTable::~StagedTable() {
     for (auto& sl : slot_) {
         if (sl.ev) { if (sl.pending) (void)hipEventSynchronize(sl.ev); (void)hipEventDestroy(sl.ev); }
         if (sl.p) (void)hipHostFree(sl.p);
     }
 }
 
-const FrameDesc* FrameTable::upload(const FrameIn* frames, int n, int in_w, int in_h, hipStream_t s) {
-    const size_t bytes = (size_t)n * (sizeof(FrameDesc) + sizeof(float));
-    Slot& sl = slot_[next_];
+void* StagedTable::stage(size_t bytes) {
+    cur_ = next_;
+    Slot& sl = slot_[cur_];
     next_ = (next_ + 1) % kSlots;
     if (!sl.ev) FH_HIP(hipEventCreateWithFlags(&sl.ev, hipEventDisableTiming));
     if (sl.pending) { FH_HIP(hipEventSynchronize(sl.ev)); sl.pending = false; }   // the copy issued kSlots calls ago: long done in practice
@@ -682,7 +682,21 @@ const FrameDesc* FrameTable::upload(const FrameIn* frames, int n, int in_w, int 
         FH_HIP(hipHostMalloc(&sl.p, bytes, hipHostMallocDefault));
         sl.bytes = bytes;
     }
-    FrameDesc* t = static_cast<FrameDesc*>(sl.p);
+    return sl.p;
+}
+
+void* StagedTable::send(size_t bytes, hipStream_t s) {
+    Slot& sl = slot_[cur_];
+    dev_.ensure(bytes);
+    FH_HIP(hipMemcpyAsync(dev_.p, sl.p, bytes, hipMemcpyHostToDevice, s));
+    FH_HIP(hipEventRecord(sl.ev, s));
+    sl.pending = true;
+    return dev_.p;
+}
+
+const FrameDesc* FrameTable::upload(const FrameIn* frames, int n, int in_w, int in_h, hipStream_t s) {
+    const size_t bytes = (size_t)n * (sizeof(FrameDesc) + sizeof(float));
+    FrameDesc* t = static_cast<FrameDesc*>(st_.stage(bytes));
     float* sc = reinterpret_cast<float*>(t + n);
     for (int i = 0; i < n; ++i) {
         const FrameIn& f = frames[i];
@@ -694,11 +708,8 @@ const FrameDesc* FrameTable::upload(const FrameIn* frames, int n, int in_w, int 
         }
         t[i] = d;
     }
-    dev_.ensure(bytes);
     n_ = n;
-    FH_HIP(hipMemcpyAsync(dev_.p, sl.p, bytes, hipMemcpyHostToDevice, s));
-    FH_HIP(hipEventRecord(sl.ev, s));
-    sl.pending = true;
+    st_.send(bytes, s);
     return table();
 }
 
@@ -724,6 +735,95 @@ void Detector::detect_ragged_dev(const FrameIn* frames, int n, float score_thr, 
     if (n <= 0) return;
     run_network_ragged_dev(frames, n, s);
     postprocess_dev(n, score_thr, nms_thr, out, max_out, counts, s);
+}
+
+// ------------------------------------------------------------------------------------------ tiled detection
+int TilePlan::plan(const FrameIn* frames, int n, const Tiling& t, int in_w, int in_h, int cap, int max_views) {
+    long long total = 0;
+    std::vector<int> nv((size_t)n, 0);
+    for (int i = 0; i < n; ++i) {
+        if (frame_empty(frames[i])) continue;
+        const int c = tile_plan(frames[i].rows, frames[i].cols, &t, nullptr, 0);
+        if (c < 0) throw std::invalid_argument("tiled detection: bad tiling");
+        nv[(size_t)i] = c;
+        total += c;
+        if (total > max_views) return -1;
+    }
+    view_frames.clear(); views.clear(); segs.clear();
+    key_total = 0;
+    std::vector<View> tmp;
+    for (int i = 0; i < n; ++i) {
+        const int c = nv[(size_t)i];
+        FrameSeg sg{(int32_t)views.size(), c, (int32_t)key_total, 0};
+        if (c > 0) {
+            tmp.resize((size_t)c);
+            tile_plan(frames[i].rows, frames[i].cols, &t, tmp.data(), c);
+            for (int j = 0; j < c; ++j) {
+                const View& v = tmp[(size_t)j];
+                ViewDesc d{i, j, v.x, v.y, v.w, v.h, v.edges, 0.f};
+                letterbox_plan(v.h, v.w, in_w, in_h, nullptr, nullptr, &d.scale);
+                views.push_back(d);
+                const uint8_t* p = frames[i].bgr ? frames[i].bgr + (size_t)v.y * frames[i].step + (size_t)v.x * 3 : nullptr;
+                view_frames.push_back(FrameIn{p, v.h, v.w, frames[i].step});
+            }
+            size_t sc = 1;
+            while (sc < (size_t)c * cap) sc <<= 1;            // the in-place bitonic sort pads to a power of two
+            sg.seg_cap = (int32_t)sc;
+            key_total += sc;
+        }
+        segs.push_back(sg);
+    }
+    return (int)views.size();
+}
+
+void TileTable::upload(const TilePlan& p, hipStream_t s) {
+    const size_t vb = p.views.size() * sizeof(ViewDesc), sb = p.segs.size() * sizeof(FrameSeg);
+    char* h = static_cast<char*>(st_.stage(vb + sb));
+    if (vb) memcpy(h, p.views.data(), vb);
+    if (sb) memcpy(h + vb, p.segs.data(), sb);
+    V_ = (int)p.views.size();
+    st_.send(vb + sb, s);
+}
+
+void tiled_postprocess(const TiledHeads* heads, const float* rows, int rows_per_view, int feat, const TilePlan& plan, const TileTable& tab,
+                       int cap, int border, float score_thr, float nms_thr, FaceRec* cand, unsigned long long* keys, int* sup, int* count,
+                       FaceRec* out, int max_out, int* counts, hipStream_t s) {
+    const int n = (int)plan.segs.size();
+    FH_HIP(hipMemsetAsync(count, 0, (size_t)n * sizeof(int), s));
+    TiledArgs a{};
+    a.views = tab.views(); a.segs = tab.segs(); a.V = (int)plan.views.size(); a.cap = cap; a.border = border; a.thr = score_thr;
+    a.cand = cand; a.keys = keys; a.count = count;
+    if (heads) launch_scrfd_decode_tiled(*heads, a, s);
+    else launch_rows_threshold_tiled(rows, rows_per_view, feat, a, s);
+    launch_sort_nms_frames(cand, keys, count, tab.segs(), cap, n, nms_thr, out, counts, max_out, sup, s);
+    FH_HIP(hipGetLastError());
+}
+
+int Detector::run_network_tiled_dev(const FrameIn* frames, int n, const Tiling& t, hipStream_t s) {
+    const int V = tplan_.plan(frames, n, t, net_.in_w(), net_.in_h(), cap_, kTileMaxViews);
+    if (V < 0) throw std::invalid_argument("tiled detection: more than FH_TILE_MAX_VIEWS views in one call, split the batch");
+    frames_table_.upload(frames, n, 0, 0, s);
+    ttab_.upload(tplan_, s);
+    if (V > 0) run_network_ragged_dev(tplan_.view_frames.data(), V, s);
+    return V;
+}
+
+void Detector::detect_tiled_dev(const FrameIn* frames, int n, const Tiling& t, float score_thr, float nms_thr, FaceRec* out, int max_out,
+                                int* counts, hipStream_t s) {
+    if (n <= 0) return;
+    const int V = run_network_tiled_dev(frames, n, t, s);
+    if (V == 0 || anchors_ <= 0) { FH_HIP(hipMemsetAsync(counts, 0, (size_t)n * sizeof(int), s)); return; }
+    keys_.ensure(tplan_.key_total * sizeof(unsigned long long));          // (reserve(V) sized them for V * cap: a frame's segment is
+    ws_.ensure(tplan_.key_total * sizeof(int));                           //  the power of two above its views * cap)
+    count_.ensure((size_t)n * sizeof(int));
+    TiledHeads h{};
+    if (!predecoded_) {
+        for (int i = 0; i < 3; ++i) { h.score[i] = net_.output(i); h.bbox[i] = net_.output(3 + i); h.kps[i] = net_.output(6 + i); }
+        h.inH = net_.in_h(); h.inW = net_.in_w();
+    }
+    tiled_postprocess(predecoded_ ? nullptr : &h, predecoded_ ? net_.output(0) : nullptr, anchors_, feat_, tplan_, ttab_, cap_, t.border,
+                      score_thr, nms_thr, cand_.as<FaceRec>(), keys_.as<unsigned long long>(), ws_.as<int>(), count_.as<int>(), out,
+                      max_out, counts, s);
 }
 
 void Detector::run_input_dev(const float* input, int n, hipStream_t s) {

@@ -11,6 +11,7 @@
 
 #include "kernels.h"
 #include "plan.h"
+#include "tile_plan.h"
 
 namespace fh {
 
@@ -132,29 +133,72 @@ struct FrameIn {
 };
 inline bool frame_empty(const FrameIn& f) { return !f.bgr || f.rows <= 0 || f.cols <= 0; }     // the reference's empty image
 
-// The device image of a call's frame descriptors: [n] FrameDesc rows followed by [n] float scales, built on the host from the caller's
-// descriptors and letterbox_plan and sent with ONE asynchronous copy on the caller's stream.  The copy's source must outlive it, and the
-// next call on the handle may follow at once with another table, so the pinned staging memory is a RING of kSlots buffers, each with an
-// event recorded behind its copy: a call takes the next slot and — only when the ring has wrapped round to a slot whose copy may still
-// be pending — waits for that slot's event before it rewrites it.  (The device side needs no ring: it is rewritten in stream order.)
-class FrameTable {
+// A small host-built table sent to the device with ONE asynchronous copy on the caller's stream.  The copy's source must outlive it, and
+// the next call on the handle may follow at once with another table, so the pinned staging memory is a RING of kSlots buffers, each with
+// an event recorded behind its copy: stage() takes the next slot and — only when the ring has wrapped round to a slot whose copy may
+// still be pending — waits for that slot's event before the caller rewrites it.  (The device side needs no ring: it is rewritten in
+// stream order.)
+class StagedTable {
   public:
-    FrameTable() = default;
-    FrameTable(const FrameTable&) = delete;
-    FrameTable& operator=(const FrameTable&) = delete;
-    ~FrameTable();
-    // in_w / in_h > 0: plan the letterbox of every frame; 0: geometry only (the recogniser's align).  Returns the device table.
-    const FrameDesc* upload(const FrameIn* frames, int n, int in_w, int in_h, hipStream_t s);
-    const FrameDesc* table() const { return dev_.as<FrameDesc>(); }
-    const float* scales() const { return reinterpret_cast<const float*>(dev_.as<FrameDesc>() + n_); }
-    int size() const { return n_; }
+    StagedTable() = default;
+    StagedTable(const StagedTable&) = delete;
+    StagedTable& operator=(const StagedTable&) = delete;
+    ~StagedTable();
+    void* stage(size_t bytes);                       // pinned host memory for the next table
+    void* send(size_t bytes, hipStream_t s);         // the staged bytes -> the device buffer (returned), asynchronously on s
+    void* dev() const { return dev_.p; }
 
   private:
     static constexpr int kSlots = 4;
     struct Slot { void* p = nullptr; size_t bytes = 0; hipEvent_t ev = nullptr; bool pending = false; } slot_[kSlots];
-    int next_ = 0, n_ = 0;
+    int next_ = 0, cur_ = 0;
     DevBuf dev_;
 };
+
+// The device image of a call's frame descriptors: [n] FrameDesc rows followed by [n] float scales, built on the host from the caller's
+// descriptors and letterbox_plan (StagedTable).
+class FrameTable {
+  public:
+    // in_w / in_h > 0: plan the letterbox of every frame; 0: geometry only (the recogniser's align).  Returns the device table.
+    const FrameDesc* upload(const FrameIn* frames, int n, int in_w, int in_h, hipStream_t s);
+    const FrameDesc* table() const { return static_cast<const FrameDesc*>(st_.dev()); }
+    const float* scales() const { return reinterpret_cast<const float*>(table() + n_); }
+    int size() const { return n_; }
+
+  private:
+    int n_ = 0;
+    StagedTable st_;
+};
+
+// The tables of one tiled call, planned on the host (tile_plan.h): the views as plain frames (what the ragged letterbox + network run
+// on), one ViewDesc per view and one FrameSeg per frame.  plan() returns the total view count, or -1 when it exceeds max_views (nothing
+// is changed then); cap = the per-view candidate capacity (a power of two).
+struct TilePlan {
+    std::vector<FrameIn> view_frames;
+    std::vector<ViewDesc> views;
+    std::vector<FrameSeg> segs;
+    size_t key_total = 0;                            // sum of the frames' seg_cap
+    int plan(const FrameIn* frames, int n, const Tiling& t, int in_w, int in_h, int cap, int max_views);
+};
+constexpr int kTileMaxViews = 256;                   // FH_TILE_MAX_VIEWS
+
+// the device image of a TilePlan's views + segs
+class TileTable {
+  public:
+    void upload(const TilePlan& p, hipStream_t s);
+    const ViewDesc* views() const { return static_cast<const ViewDesc*>(st_.dev()); }
+    const FrameSeg* segs() const { return reinterpret_cast<const FrameSeg*>(views() + V_); }
+
+  private:
+    int V_ = 0;
+    StagedTable st_;
+};
+
+// decode / threshold (view-aware) + one NMS per frame on the rows of a tiled call: heads == nullptr -> pre-decoded rows
+// [V][rows_per_view][feat].  counts of frames without views are 0.
+void tiled_postprocess(const TiledHeads* heads, const float* rows, int rows_per_view, int feat, const TilePlan& plan, const TileTable& tab,
+                       int cap, int border, float score_thr, float nms_thr, FaceRec* cand, unsigned long long* keys, int* sup, int* count,
+                       FaceRec* out, int max_out, int* counts, hipStream_t s);
 
 class Detector {
   public:
@@ -181,6 +225,15 @@ class Detector {
     void detect_ragged_dev(const FrameIn* frames, int n, float score_thr, float nms_thr, FaceRec* out, int max_out, int* counts,
                            hipStream_t s);
     const FrameTable& frame_table() const { return table_; }   // of the last ragged call: handed to the recogniser's align by the pipeline
+    // Tiled detection (include/facehip.h): the views of all frames are ONE ragged batch (table_ then holds the VIEWS), decoded by the
+    // view-aware kernels and merged by one NMS per frame.  run_network_tiled_dev returns the total view count (0: only empty frames),
+    // or throws std::invalid_argument when the call has more than kTileMaxViews views — before anything is launched.
+    int run_network_tiled_dev(const FrameIn* frames, int n, const Tiling& t, hipStream_t s);
+    void detect_tiled_dev(const FrameIn* frames, int n, const Tiling& t, float score_thr, float nms_thr, FaceRec* out, int max_out,
+                          int* counts, hipStream_t s);
+    // the FRAMES of the last tiled call (geometry only): the faces are in frame coordinates, so this — not table_ — is what the
+    // pipeline's align reads
+    const FrameTable& tiled_frame_table() const { return frames_table_; }
 
   private:
     void reserve(int n, int rows, int cols);
@@ -189,7 +242,9 @@ class Detector {
     int anchors_ = 0, feat_ = 15, cap_ = 0, nb_ = 0;
     float scale_ = 1.f;
     bool ragged_ = false;                                 // the last network run was a ragged one: postprocess_dev reads table_.scales()
-    FrameTable table_;
+    FrameTable table_, frames_table_;
+    TilePlan tplan_;
+    TileTable ttab_;
     DevBuf resized_, cand_, keys_, count_, ws_;           // resized_: the uniform path's resized frames / the ragged path's canvas
 };
 

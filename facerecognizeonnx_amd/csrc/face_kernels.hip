@@ -4,6 +4,7 @@
 // arithmetic are meant to be bit-identical to the CPU oracle (oracle/face_oracle.c).
 #include <hip/hip_runtime.h>
 
+#include "face_emit.h"
 #include "kernels.h"
 
 namespace fh {
@@ -266,20 +267,7 @@ void launch_letterbox_ragged(const FrameDesc* table, int n, int inH, int inW, ui
 // (score descending, anchor index ascending — the total order this build fixes for the
 // reference's unstable std::sort, :357) are compacted with one atomic per survivor.
 // ------------------------------------------------------------------------------------------
-__device__ __forceinline__ unsigned long long make_key(float score, unsigned idx) {
-    unsigned u = __float_as_uint(score);
-    u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);        // ascending-orderable
-    return ((unsigned long long)(~u) << 32) | idx;          // descending score, ascending index
-}
-
-__device__ __forceinline__ void emit_face(const float* o15, float scale, FaceRec* f) {
-    const float x1 = o15[0] / scale, y1 = o15[1] / scale, x2 = o15[2] / scale, y2 = o15[3] / scale;
-    f->x = (int)x1; f->y = (int)y1; f->w = (int)(x2 - x1); f->h = (int)(y2 - y1);
-    f->score = o15[4];
-#pragma unroll
-    for (int j = 0; j < 10; ++j) f->lm[j] = o15[5 + j] / scale;
-}
-
+// (make_key / emit_face: face_emit.h, shared with the view-aware kernels of tiled_kernels.hip)
 __global__ __launch_bounds__(256) void scrfd_decode_kernel(const DecodeArgs a) {
     const int gw8 = a.inW / 8, gh8 = a.inH / 8, gw16 = a.inW / 16, gh16 = a.inH / 16, gw32 = a.inW / 32, gh32 = a.inH / 32;
     const int n8 = gw8 * gh8 * 2, n16 = gw16 * gh16 * 2, n32 = gw32 * gh32 * 2;
@@ -362,25 +350,24 @@ __device__ __forceinline__ float iou_int(int4 a, int4 b) {
 constexpr int NMS_T = 1024;
 constexpr int NMS_SMALL = 2048;
 
-__global__ __launch_bounds__(NMS_T) void sort_nms_kernel(const FaceRec* __restrict__ cand, unsigned long long* __restrict__ keys_g,
-                                                         const int* __restrict__ count, int cap, float thr, FaceRec* __restrict__ out,
-                                                         int* __restrict__ out_count, int max_out, int* __restrict__ ws) {
+// One workgroup, one segment: fc = the payload the keys' low words index, keys_seg / sup_seg = the segment's key list (n live entries) and
+// suppression flags in global memory — both with room for the next power of two >= n (the in-place sort pads up to it).
+__device__ __forceinline__ void sort_nms_segment(const FaceRec* __restrict__ fc, unsigned long long* __restrict__ keys_seg,
+                                                 int* __restrict__ sup_g, int n, float thr, FaceRec* __restrict__ out,
+                                                 int* __restrict__ out_count, int max_out) {
     __shared__ unsigned long long skeys[NMS_SMALL];
     __shared__ int4 sbox[NMS_SMALL];
     __shared__ unsigned char ssup[NMS_SMALL];
     __shared__ int wave_tot[NMS_T / 64];
     __shared__ int run_base;
-    const int b = blockIdx.x, tid = threadIdx.x;
-    const int n = min(count[b], cap);
-    const FaceRec* fc = cand + (size_t)b * cap;
-    if (n <= 0) { if (tid == 0) out_count[b] = 0; return; }
+    const int tid = threadIdx.x;
+    if (n <= 0) { if (tid == 0) *out_count = 0; return; }
     int np2 = 1;
     while (np2 < n) np2 <<= 1;
     const bool small = np2 <= NMS_SMALL;
-    unsigned long long* keys = small ? skeys : keys_g + (size_t)b * cap;   // cap is a power of two >= n (host guarantees)
-    int* sup_g = ws + (size_t)b * cap;
+    unsigned long long* keys = small ? skeys : keys_seg;
     for (int i = tid; i < np2; i += NMS_T) {
-        const unsigned long long k = i < n ? keys_g[(size_t)b * cap + i] : ~0ull;
+        const unsigned long long k = i < n ? keys_seg[i] : ~0ull;
         keys[i] = k;
     }
     __syncthreads();
@@ -434,18 +421,47 @@ __global__ __launch_bounds__(NMS_T) void sort_nms_kernel(const FaceRec* __restri
         __syncthreads();
         int off = run_base;
         for (int w = 0; w < wv; ++w) off += wave_tot[w];
-        if (keep && off + pre < max_out) out[(size_t)b * max_out + off + pre] = fc[(unsigned)(keys[i] & 0xffffffffu)];
+        if (keep && off + pre < max_out) out[off + pre] = fc[(unsigned)(keys[i] & 0xffffffffu)];
         __syncthreads();
         if (tid == 0) { int t = 0; for (int w = 0; w < NMS_T / 64; ++w) t += wave_tot[w]; run_base += t; }
         __syncthreads();
     }
-    if (tid == 0) out_count[b] = run_base;
+    if (tid == 0) *out_count = run_base;
+}
+
+// one workgroup per frame; the frame's segment is its [cap] block (cap is a power of two >= count, host guarantees)
+__global__ __launch_bounds__(NMS_T) void sort_nms_kernel(const FaceRec* __restrict__ cand, unsigned long long* __restrict__ keys_g,
+                                                         const int* __restrict__ count, int cap, float thr, FaceRec* __restrict__ out,
+                                                         int* __restrict__ out_count, int max_out, int* __restrict__ ws) {
+    const int b = blockIdx.x;
+    sort_nms_segment(cand + (size_t)b * cap, keys_g + (size_t)b * cap, ws + (size_t)b * cap, min(count[b], cap), thr,
+                     out + (size_t)b * max_out, out_count + b, max_out);
+}
+
+// Tiled detection: one workgroup per FRAME over the candidates of all its views.  The frame owns the payload blocks of its views
+// (cand[first_view .. first_view + views)[cap], which the keys' low words local_view * cap + index address) and the key / flag segment
+// [key_off, key_off + seg_cap) — seg_cap the power of two >= views * cap.
+__global__ __launch_bounds__(NMS_T) void sort_nms_frames_kernel(const FaceRec* __restrict__ cand, unsigned long long* __restrict__ keys_g,
+                                                                const int* __restrict__ count, const FrameSeg* __restrict__ segs, int cap,
+                                                                float thr, FaceRec* __restrict__ out, int* __restrict__ out_count,
+                                                                int max_out, int* __restrict__ ws) {
+    const int b = blockIdx.x;
+    const FrameSeg sg = segs[b];
+    sort_nms_segment(cand + (size_t)sg.first_view * cap, keys_g + sg.key_off, ws + sg.key_off, min(count[b], sg.seg_cap), thr,
+                     out + (size_t)b * max_out, out_count + b, max_out);
 }
 
 void launch_sort_nms(const FaceRec* cand, unsigned long long* keys, const int* count, int cap, int B, float nms_thr, FaceRec* out,
                      int* out_count, int max_out, int* order_ws, hipStream_t s) {
     hipLaunchKernelGGL(sort_nms_kernel, dim3(B), dim3(NMS_T), 0, s, cand, keys, count, cap, nms_thr, out, out_count, max_out,
                        order_ws);
+}
+
+void launch_sort_nms_frames(const FaceRec* cand, unsigned long long* keys, const int* count, const FrameSeg* segs, int cap, int n_frames,
+                            float nms_thr, FaceRec* out, int* out_count, int max_out, int* order_ws, hipStream_t s) {
+    if (n_frames <= 0) return;
+    hipLaunchKernelGGL(sort_nms_frames_kernel, dim3(n_frames), dim3(NMS_T), 0, s, cand, keys, count, segs, cap, nms_thr, out, out_count,
+                       max_out, order_ws);
 }
 
 // ------------------------------------------------------------------------------------------

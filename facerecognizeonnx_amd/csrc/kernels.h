@@ -266,6 +266,43 @@ void launch_rows_threshold(const float* rows, int B, int n, int feat, float scal
 void launch_sort_nms(const FaceRec* cand, unsigned long long* keys, const int* count, int cap, int B, float nms_thr,
                      FaceRec* out, int* out_count, int max_out, int* order_ws, hipStream_t s);
 
+// ---- tiled detection (tiled_kernels.hip; the contract is stated in include/facehip.h) ----------------------------------------------
+// One row per VIEW of a call, in plan order (the views of frame 0, then of frame 1, ...): the frame it belongs to, its index among the
+// frame's views, its rectangle in the frame, its interior-edge mask (fh_view::edges; 0 for view 0) and its letterbox scale
+// (fh_letterbox_plan of h x w; 0 = a dead view, which emits nothing).
+struct ViewDesc {
+    int32_t frame, local, x, y, w, h, edges;
+    float scale;
+};
+static_assert(sizeof(ViewDesc) == 32, "ViewDesc is a 32-byte table row");
+// One row per FRAME: its views are rows [first_view, first_view + views) of the view table, its keys and suppression flags live in
+// [key_off, key_off + seg_cap) of the key / flag buffers, seg_cap = the power of two >= views * cap (the in-place sort pads up to it).
+struct FrameSeg {
+    int32_t first_view, views, key_off, seg_cap;
+};
+struct TiledArgs {
+    const ViewDesc* views;      // [V]
+    const FrameSeg* segs;       // [n_frames]
+    int V, cap, border;         // border < 0: the border rule is off
+    float thr;
+    FaceRec* cand;              // [V][cap] payload, one block per view
+    unsigned long long* keys;   // per-frame segments; key = (score desc, local_view * cap + index asc)
+    int* count;                 // [n_frames]
+};
+// the view-aware twins of launch_scrfd_decode / launch_rows_threshold: the same row arithmetic per view (emit_face), then the border
+// rule, the integer / fp32 shift into frame coordinates, and the key appended to the FRAME's list
+struct TiledHeads {
+    const float* score[3];      // per stride [V, gh*gw*2]
+    const float* bbox[3];
+    const float* kps[3];
+    int inH, inW;
+};
+void launch_scrfd_decode_tiled(const TiledHeads& h, const TiledArgs& a, hipStream_t s);
+void launch_rows_threshold_tiled(const float* rows, int rows_per_view, int feat, const TiledArgs& a, hipStream_t s);
+// launch_sort_nms with one workgroup per frame over the frame's segment (face_kernels.hip, the same sort + sweep + compaction)
+void launch_sort_nms_frames(const FaceRec* cand, unsigned long long* keys, const int* count, const FrameSeg* segs, int cap, int n_frames,
+                            float nms_thr, FaceRec* out, int* out_count, int max_out, int* order_ws, hipStream_t s);
+
 // FaceRecognizer::alignFace (src/face_recognizer.cpp:93-133): similarity estimate + warpAffine
 //   faces[n] with frame index frame_of[n]; writes crops [n,112,112,3] BGR u8 and ok[n].
 void launch_align(const uint8_t* frames, long img_stride, int rows, int cols, int step, const FaceRec* faces,

@@ -187,6 +187,60 @@ FH_API int fh_pipeline_run_ragged_dev(fh_det* d, fh_rec* r, const fh_frame* fram
 FH_API int fh_pipeline_run_images(fh_det* d, fh_rec* r, const fh_frame* imgs, int n, float score_thr, float nms_thr,
                                   int faces_per_frame, fh_face* faces, int* frame_of, float* emb, int cap);
 
+/* ---- tiled detection of large frames.  The detector letterboxes a frame of any size onto its one input canvas, so a face in a
+ * 1920 x 1080 or 4K frame reaches the network 3x / 6x smaller.  These calls run the detector on the whole frame AND on overlapping
+ * full-resolution tiles of it, and merge everything with ONE NMS per frame.  The existing entry points are unchanged.
+ *
+ * fh_tile_plan  host only, no GPU; the detector plans through the same function.  Per axis (x shown, y alike), integers only:
+ *     cols <= tile_w: one tile at 0, cols wide; otherwise sx = tile_w - overlap, nx = ceil((cols - tile_w) / sx) + 1,
+ *     x_j = min(j * sx, cols - tile_w), tile_w wide (the last tile is shifted inward, never cut short).
+ *   View 0 is the whole frame (0, 0, cols, rows), edges = 0; if nx * ny > 1 the nx * ny tiles follow, row-major.  fh_view::edges: bit
+ *   0 left, 1 top, 2 right, 3 bottom = that edge is INTERIOR (x > 0, y > 0, x + w < cols, y + h < rows).  Returns the view count; 0
+ *   for an empty image (rows <= 0 || cols <= 0); FH_ERR_ARG for tile_w or tile_h < 16, overlap < 0, overlap >= min(tile_w, tile_h),
+ *   or — with views != NULL — more views than cap.  views == NULL only counts.  border < 0 switches the border rule off.
+ *
+ * The contract of a tiled detection, for frame f with views v = 0..V-1 of the plan:
+ *   1. per view  the view (pixels at bgr + y * step + 3 * x, the frame's step) is the reference's image for FaceDetector::preprocess /
+ *      postprocess: letterbox plan fh_letterbox_plan(view.h, view.w, in_w, in_h), candidates by the reference's row loop (strict
+ *      score > thr, / scale, (int) truncation, width from the float difference; src/face_detector.cpp:249-278).  A view whose plan is
+ *      dead contributes nothing (a frame whose whole view is dead may still have live tiles).
+ *   2. border rule, tiles only (never view 0), with b = border >= 0 and the integer box in VIEW coordinates — dropped if:  left edge
+ *      interior and x <= b;  right interior and x + w >= view.w - b;  top interior and y <= b;  bottom interior and y + h >= view.h - b.
+ *   3. shift, tiles only (view 0 is at the origin and is left as it is): x += view.x, y += view.y as integers; each landmark
+ *      coordinate becomes lm + (float)view.x / (float)view.y — one fp32 add after the division.
+ *   4. merge  the surviving candidates of ALL views of the frame go through FaceDetector::nms once (integer IoU, strict >, greedy;
+ *      :340-384) in the total order (score descending, view index ascending, anchor / row index ascending).  No per-view NMS.
+ *   5. output as fh_det_detect_batch_dev: d_out[f][max_per_frame] in that order, d_counts[f] = all survivors, stored or not.
+ *   A frame that fits one tile has only view 0: its records are bitwise those of fh_det_detect_ragged_dev.
+ * Limits: 1 <= n <= 4096 frames, and at most FH_TILE_MAX_VIEWS views per call IN TOTAL — more returns FH_ERR_ARG before anything is
+ * launched; split the batch.  Memory: the views of a call are one ragged batch, so the handle reserves what a ragged batch of that many
+ * frames needs (canvas, activations, one [cap] candidate block per view; cap = the power of two >= the anchor count), plus key / flag
+ * segments of the power of two >= views * cap per frame.  Asynchronous on `stream`; the next call may follow at once with other tables.
+ * What this proves: the composition is exact.  Whether tiling finds faces the plain call misses depends on trained weights. */
+#define FH_TILE_MAX_VIEWS 256
+typedef struct fh_tiling { int32_t tile_w, tile_h, overlap, border; } fh_tiling;
+typedef struct fh_view { int32_t x, y, w, h, edges; } fh_view;
+FH_API int fh_tile_plan(int rows, int cols, const fh_tiling* t, fh_view* views, int cap);
+FH_API int fh_det_detect_tiled_dev(fh_det* d, const fh_frame* frames, int n, const fh_tiling* t, float score_thr, float nms_thr,
+                                   fh_face* d_out, int max_per_frame, int* d_counts, void* stream);
+/* Stage hook: plan + letterbox + network on every view; returns the total view count (0: only empty frames).  The heads are read
+ * with fh_det_output_dev: one row block per view, in plan order (the views of frame 0, then of frame 1, ...). */
+FH_API int fh_det_run_network_tiled_dev(fh_det* d, const fh_frame* frames, int n, const fh_tiling* t, void* stream);
+/* fh_postprocess_rows_dev's tiled twin, steps 1 (from the row loop on) to 5 on caller-supplied pre-decoded rows: d_rows =
+ * [total views][rows_per_view][feat >= 15] for every view of every frame in plan order; frame_rows / frame_cols = HOST arrays of the
+ * n frame sizes (<= 0: an empty frame, no views); in_w x in_h = the network input the view scales are planned for.  The same device
+ * code as the detector's, without a graph in front; rows_per_view <= 2^21.  One scratch per calling thread: calls must not overlap. */
+FH_API int fh_postprocess_rows_tiled_dev(const float* d_rows, const int* frame_rows, const int* frame_cols, int n_frames,
+                                         const fh_tiling* t, int in_w, int in_h, int rows_per_view, int feat, float score_thr,
+                                         float nms_thr, fh_face* d_out, int max_per_frame, int* d_counts, void* stream);
+/* fh_pipeline_run_ragged_dev over tiled detection: same selection, compaction, d_frame_of, hand-off and return value; the align reads
+ * the FRAMES (the faces are in frame coordinates), not the views. */
+FH_API int fh_pipeline_run_tiled_dev(fh_det* d, fh_rec* r, const fh_frame* frames, int n, const fh_tiling* t, float score_thr,
+                                     float nms_thr, int faces_per_frame, fh_face* d_faces, int* d_frame_of, float* d_emb, void* stream);
+/* FaceDetector::detect on ONE host image, tiled (fh_det_detect's arguments and return value); blocking, eager (not graph-captured). */
+FH_API int fh_det_detect_tiled(fh_det* d, const uint8_t* bgr, int rows, int cols, int step, const fh_tiling* t, float score_thr,
+                               float nms_thr, fh_face* out, int max_out);
+
 /* Two-stream form for streaming callers (the testWebcam loop shape, src/main.cpp:214-258, over batches): detect + decode +
  * NMS + face selection on stream_det, align + embed on stream_rec behind an event.  The host waits for the detector's face
  * count only; a recogniser queued earlier on stream_rec keeps running, so submitting batch k+1 straight after batch k

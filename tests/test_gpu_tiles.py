@@ -1,0 +1,374 @@
+"""Tiled detection of large frames on the GPU (include/facehip.h: fh_det_detect_tiled_dev and friends): the whole frame and its
+overlapping tiles go through the detector as one ragged batch and are merged by ONE NMS per frame.  The composition is held bit for
+bit to the numpy model (tests/tile_model.py: the plan, the border rule, the shift, oracle.nms on the concatenation) given the heads
+the device computed, and to the existing ragged entry points wherever the same bytes go through the same kernels.
+
+Base set, tiling (128, 128, overlap 32, border 2): frames that fit one tile, tiles one pixel apart, 7 / 5 / 6 / 4 views, a padded row
+pitch, a frame whose whole view is dead but whose 21 one-pixel-high tiles live, and an empty descriptor — 49 views in all.  The first
+four frames also run with tiling (64, 64, 16, 2): tile != input, scale 2.
+
+Seeds (chosen on the CPU with the oracle's network on every view): frame i of the base set is util.frames_u8(seed = 700 + i).  With
+thresholds (0.5, 0.4) and border 2 that gives four multi-view frames with survivors from two views ((300, 200), (128, 400), (64, 500),
+(37, 300)), border drops in every multi-view frame and cross-view suppression in (129, 128); border -1 gives survivors from every view
+of (300, 200) and cross-view suppression in five frames."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+torch = pytest.importorskip("torch")
+
+import facerecognizeonnx_amd as fa            # noqa: E402
+from facerecognizeonnx_amd import _lib        # noqa: E402
+from oracle import oracle                     # noqa: E402
+from tests import tile_model, util            # noqa: E402
+from tests.test_gpu_ragged import Frames, _det_outputs, _records, dev      # noqa: E402
+
+IN = 128                                                       # tiny_scrfd(hw=128): 672 anchors
+SEED = 700
+S = [(128, 128, 0), (100, 90, 0), (129, 128, 0), (300, 200, 0), (128, 400, 0), (64, 500, 0), (37, 300, 300 * 3 + 5), (1, 2000, 0), None]
+VIEWS_A = [1, 1, 3, 7, 5, 6, 4, 22, 0]
+TA = (128, 32)                                                 # tile, overlap
+TB = (64, 16)
+MAX_PF = 1024
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _gpu():
+    if not torch.cuda.is_available():
+        pytest.fail("GPU tests need a real device: the product path has no CPU fallback")
+    fa.lib().fh_init(0)
+    oracle.set_threads(8)
+
+
+@pytest.fixture(scope="module")
+def models_(models_dir):
+    det, rec = fa.FaceDetector(), fa.FaceRecognizer()
+    assert det.loadModel(util.tiny_scrfd(models_dir, hw=128, cls_bias=-2.0)) and rec.loadModel(util.tiny_iresnet(models_dir))
+    assert det.input_size() == (IN, IN) and det.num_anchors() == 672
+    return det, rec
+
+
+@pytest.fixture(scope="module")
+def base():
+    return Frames(S, seed=SEED)
+
+
+def _plans(fr, idx, tile, overlap):
+    """Per frame of `idx`: the model's views (an empty descriptor has none)."""
+    return [tile_model.plan(fr.shapes[i][0], fr.shapes[i][1], tile, tile, overlap) if fr.shapes[i] is not None else [] for i in idx]
+
+
+def _view_descs(fr, idx, plans):
+    """The views of a call as plain frames: pointer = frame pointer + y * step + 3 * x, the frame's step."""
+    out = []
+    for i, views in zip(idx, plans):
+        for x, y, w, h, _ in views:
+            ptr, _, _, step = fr.desc(i)
+            out.append((ptr + y * step + 3 * x, h, w, step))
+    return out
+
+
+def _detect_tiled(det, descs, tiling, thr=0.5, nms=0.4, max_pf=MAX_PF, sync=True):
+    n = len(descs)
+    out = torch.zeros((n, max_pf, 15), device="cuda"); cnt = torch.full((n,), -1, dtype=torch.int32, device="cuda")
+    assert det.detect_tiled_dev(descs, tiling, out.data_ptr(), max_pf, cnt.data_ptr(), thr, nms) == n
+    if sync:
+        torch.cuda.synchronize()
+    return out, cnt
+
+
+def _provenance(cs, nms):
+    """The greedy sweep restated over (candidate, view) pairs: (views of the survivors, suppressions across views)."""
+    allc = np.concatenate([s for _, _, s in cs]); vid = np.concatenate([np.full(len(s), v) for v, (_, _, s) in enumerate(cs)])
+    order = np.lexsort((np.arange(len(allc)), -allc["score"].astype(np.float64)))
+    sup = np.zeros(len(allc), bool)
+    cross, views = 0, []
+    for a, i in enumerate(order):
+        if sup[i]:
+            continue
+        views.append(int(vid[i]))
+        for j in order[a + 1:]:
+            if not sup[j] and util._iou_int(allc[i], allc[j]) > nms:
+                sup[j] = True
+                cross += int(vid[i] != vid[j])
+    return views, cross
+
+
+def test_plan_of_the_base_set():
+    for sh, want in zip(S, VIEWS_A):
+        got = fa.tile_plan(sh[0], sh[1], TA[0], TA[1], 2) if sh is not None else []
+        assert len(got) == want and got == (tile_model.plan(sh[0], sh[1], TA[0], TA[0], TA[1]) if sh is not None else [])
+    v = fa.tile_plan(1, 2000, TA[0], TA[1], 2)
+    assert not fa.letterbox_plan(1, 2000, IN, IN)[0] and all(fa.letterbox_plan(h, w, IN, IN)[0] for _, _, w, h, _ in v[1:])
+
+
+@pytest.mark.parametrize("idx,tile,overlap", [(list(range(len(S))), *TA), ([0, 1, 2, 3], *TB)])
+def test_heads_bitwise_against_the_ragged_call_on_the_listed_views(models_, base, idx, tile, overlap):
+    det, _ = models_
+    plans = _plans(base, idx, tile, overlap)
+    V = sum(len(p) for p in plans)
+    arr, t = fa.frame_array(base.descs(idx)), fa.Tiling(tile, overlap, 2)
+    assert fa.lib().fh_det_run_network_tiled_dev(det.handle, arr, len(idx), C.byref(t), 0) == V, _lib.last_error()
+    torch.cuda.synchronize()
+    got = _det_outputs(det, V)
+    varr = fa.frame_array(_view_descs(base, idx, plans))
+    assert fa.lib().fh_det_run_network_ragged_dev(det.handle, varr, V, 0) == V, _lib.last_error()
+    torch.cuda.synchronize()
+    ref = _det_outputs(det, V)
+    assert len(got) == 9
+    for i, (a, b) in enumerate(zip(got, ref)):
+        assert a.tobytes() == b.tobytes(), (i, float(np.abs(a - b).max()))       # same bytes in, same batch, same kernels
+
+
+def test_records_bitwise_given_the_heads(models_, base):
+    det, _ = models_
+    two_views, dropped, cross_total = set(), 0, 0
+    for idx, (tile, overlap) in ((list(range(len(S))), TA), ([0, 1, 2, 3], TB)):
+        plans = _plans(base, idx, tile, overlap)
+        V = sum(len(p) for p in plans)
+        for thr, nms in ((0.5, 0.4), (0.3, 0.2)):
+            for border in (2, -1):
+                out, cnt = _detect_tiled(det, base.descs(idx), fa.Tiling(tile, overlap, border), thr, nms)
+                heads = _det_outputs(det, V)                   # the heads these records were decoded from
+                rec, cnt = _records(out, len(idx), MAX_PF), cnt.cpu().numpy()
+                gv = 0
+                for b, views in enumerate(plans):
+                    rows = [oracle.scrfd_decode([h[gv + v] for h in heads], IN, IN) for v in range(len(views))]
+                    gv += len(views)
+                    ref = tile_model.merge(rows, views, IN, IN, border, thr, nms)
+                    print("tiled records:", (tile, overlap, border), (thr, nms), "frame", S[idx[b]], "views", len(views), "count", int(cnt[b]), "model", len(ref))
+                    assert cnt[b] == len(ref) <= MAX_PF, (tile, thr, nms, border, b, cnt[b], len(ref))
+                    assert rec[b, :len(ref)].tobytes() == ref.tobytes(), (tile, thr, nms, border, b)
+                    if len(views) > 1:
+                        cs = tile_model.candidates(rows, views, IN, IN, border, thr)
+                        dropped += sum(int((~k).sum()) for _, k, _ in cs)
+                        if sum(len(s) for _, _, s in cs):
+                            sv, cross = _provenance(cs, nms)
+                            assert len(sv) == len(ref)
+                            cross_total += cross
+                            if len(set(sv)) >= 2 and (tile, overlap) == TA and border == 2 and thr == 0.5:
+                                two_views.add(idx[b])
+                    if S[idx[b]] is None:
+                        assert cnt[b] == 0
+                    elif S[idx[b]][:2] == (1, 2000):
+                        assert cnt[b] > 0                       # the whole view is dead, the tiles live
+    assert len(two_views) >= 3, two_views                      # multi-view frames with survivors from two different views
+    assert dropped >= 1 and cross_total >= 1, (dropped, cross_total)
+
+
+def test_frames_that_fit_one_tile_are_bitwise_the_ragged_call(models_, base):
+    det, _ = models_
+    descs = base.descs([0, 1])
+    out, cnt = _detect_tiled(det, descs, fa.Tiling(*TA, 2), max_pf=672)
+    ref = torch.zeros((2, 672, 15), device="cuda"); rc = torch.full((2,), -1, dtype=torch.int32, device="cuda")
+    assert det.detect_ragged_dev(descs, ref.data_ptr(), 672, rc.data_ptr(), 0.5, 0.4) == 2
+    torch.cuda.synchronize()
+    assert rc.cpu().numpy().min() > 0
+    assert cnt.cpu().numpy().tobytes() == rc.cpu().numpy().tobytes() and out.cpu().numpy().tobytes() == ref.cpu().numpy().tobytes()
+
+
+# ---------------------------------------------------------------------------------------------- crafted rows
+def _row(x1, y1, x2, y2, score, lm0=0.0):
+    return np.array([x1, y1, x2, y2, score] + [lm0 + k for k in range(10)], np.float32)
+
+
+def _rows_tiled(frames, view_rows, tiling, thr, nms, max_pf, rpv):
+    """frames = [(rows, cols)], view_rows[f][v] = [rpv][15]; returns (records [n][max_pf], counts) of fh_postprocess_rows_tiled_dev."""
+    n = len(frames)
+    flat = np.concatenate([r for f in view_rows for r in f]) if any(len(f) for f in view_rows) else np.zeros((1, 15), np.float32)
+    d = dev(flat.astype(np.float32))
+    fr = np.array([f[0] for f in frames], np.int32); fc = np.array([f[1] for f in frames], np.int32)
+    out = torch.full((n, max_pf, 15), 3.0, device="cuda"); cnt = torch.full((n,), -1, dtype=torch.int32, device="cuda")
+    rc = fa.lib().fh_postprocess_rows_tiled_dev(d.data_ptr(), fr.ctypes.data, fc.ctypes.data, n, C.byref(tiling), IN, IN, rpv, 15, thr, nms,
+                                                out.data_ptr(), max_pf, cnt.data_ptr(), 0)
+    assert rc == n, _lib.last_error()
+    torch.cuda.synchronize()
+    return _records(out, n, max_pf), cnt.cpu().numpy()
+
+
+def _check_rows(frames, view_rows, tile, overlap, border, thr, nms, max_pf, rpv):
+    rec, cnt = _rows_tiled(frames, view_rows, fa.Tiling(tile, overlap, border), thr, nms, max_pf, rpv)
+    refs = []
+    for b, (sh, vr) in enumerate(zip(frames, view_rows)):
+        views = tile_model.plan(sh[0], sh[1], tile, tile, overlap)
+        assert len(views) == len(vr)
+        ref = tile_model.merge(vr, views, IN, IN, border, thr, nms)
+        assert cnt[b] == len(ref), (b, cnt[b], len(ref))
+        m = min(len(ref), max_pf)
+        assert rec[b, :m].tobytes() == ref[:m].tobytes(), b
+        refs.append(ref)
+    return rec, cnt, refs
+
+
+def _blank(views, rpv):
+    return [np.zeros((rpv, 15), np.float32) for _ in range(views)]                # score 0: below every threshold used
+
+
+def test_crafted_rows_duplicates_ties_and_the_border_rule():
+    """Frame (128, 200): view 0 = the whole frame (scale 0.64), tiles at x = 0 and x = 72 (scale 1; tile 0's right edge and tile 1's
+    left edge are interior)."""
+    rpv, sh = 8, (128, 200)
+    assert tile_model.plan(*sh, 128, 128, 32) == [(0, 0, 200, 128, 0), (0, 0, 128, 128, 4), (72, 0, 128, 128, 1)]
+    frames, vr = [], []
+
+    def frame():
+        frames.append(sh); vr.append(_blank(3, rpv)); return vr[-1]
+    f = frame()                                                # 0: the same face in two tiles, equal scores: the lower view wins
+    f[1][3] = _row(80, 40, 110, 70, 0.9, 1.0); f[2][1] = _row(8, 40, 38, 70, 0.9, 2.0)
+    f = frame()                                                # 1: unequal scores: the higher score wins
+    f[1][3] = _row(80, 40, 110, 70, 0.9, 1.0); f[2][1] = _row(8, 40, 38, 70, 0.95, 2.0)
+    f = frame()                                                # 2: touching tile 0's interior right edge (dropped); the same box at tile 1's
+    f[1][0] = _row(100, 10, 126, 30, 0.9); f[2][0] = _row(100, 40, 126, 60, 0.9)      # right edge = the frame's (kept)
+    f[1][1] = _row(2, 70, 20, 90, 0.8); f[2][1] = _row(2, 100, 20, 120, 0.8)          # left: the frame's edge (kept) / interior (dropped)
+    f[1][2] = _row(100, 100, 125, 120, 0.7); f[2][2] = _row(3, 70, 20, 90, 0.7)       # one pixel clear of the rule: kept
+    f = frame()                                                # 3: equal scores across three views: order view, then row
+    for v, x in ((0, 6.4), (1, 40.0), (2, 5.0)):
+        f[v][5] = _row(x, 10, x + 4, 14, 0.75, v); f[v][2] = _row(x, 60, x + 4, 64, 0.75, 10 + v)
+    f = frame()                                                # 4: score == thr, NaN, zero-area boxes, negative coordinates
+    f[1][0] = _row(10, 10, 30, 30, 0.5); f[1][1] = _row(10, 40, 30, 60, np.nan); f[1][2] = _row(50, 50, 50, 50, 0.9)
+    f[1][3] = _row(50.2, 80, 50.9, 100, 0.8); f[2][0] = _row(-20.5, -3.5, 30, 40, 0.9); f[2][1] = _row(60, -8, 90, -2, 0.85)
+    f[0][0] = _row(-9.6, -5, 20, 30, 0.95); f[0][1] = _row(30, 30, 30, 30, 0.6); f[2][2] = _row(-20.5, -3.5, 30, 40, np.float32(0.5) + np.float32(1e-7))
+    for border in (2, -1):
+        rec, cnt, refs = _check_rows(frames, vr, 128, 32, border, 0.5, 0.4, 16, rpv)
+        assert cnt[0] == 1 and rec[0, 0]["lm"][0] == 1.0 and rec[0, 0]["x"] == 80        # tile 0's record
+        assert cnt[1] == 1 and rec[1, 0]["lm"][0] == 2.0 + 72 and rec[1, 0]["x"] == 80   # tile 1's, shifted
+        assert cnt[2] == (4 if border == 2 else 6)
+        assert [int(r["lm"][0]) for r in rec[3, :cnt[3]]] == [15, 0, 11, 1, 72 + 12, 72 + 2]    # view, then row 2 before row 5 (view 0: 10 / 0.64; view 2 carries the shift)
+        assert cnt[4] >= 5 and rec[4, :cnt[4]]["x"].min() < 0 and (rec[4, :cnt[4]]["w"] == 0).any()
+    # max_per_frame smaller than the count: the first records are stored, the count is the total, the tail is untouched
+    rec, cnt, refs = _check_rows(frames, vr, 128, 32, -1, 0.5, 0.4, 2, rpv)
+    assert cnt[3] == 6 and cnt[2] == 6
+    t = _rows_tiled(frames, vr, fa.Tiling(128, 32, -1), 0.5, 0.4, 2, rpv)[0]
+    assert t.shape == (len(frames), 2)
+
+
+def test_crafted_rows_more_than_2048_survivors_in_one_frame():
+    """Frame (128, 400), 5 views x 1024 rows: 960 disjoint 2 x 2 boxes per tile (3840 candidates, > 2048 of them survive: the NMS's
+    global-memory branch, sorting in the frame's key segment of 8192) next to a frame with 3 survivors."""
+    rpv = 1024
+    big = _blank(5, rpv)
+    rng = np.random.default_rng(5)
+    for v in range(1, 5):
+        k = 0
+        for j in range(24):
+            for i in range(40):
+                x, y = 3 + 3 * i, 3 + 3 * j
+                big[v][k] = _row(x, y, x + 2, y + 2, 0.6 + 0.01 * rng.integers(0, 30), k)       # many score ties
+                k += 1
+        big[v] = big[v][rng.permutation(rpv)]
+    small = _blank(3, rpv)
+    small[0][7] = _row(10, 10, 30, 30, 0.9); small[1][1000] = _row(60, 60, 90, 90, 0.8); small[2][3] = _row(40, 5, 50, 15, 0.7)
+    rec, cnt, refs = _check_rows([(128, 400), (128, 200)], [big, small], 128, 32, 2, 0.5, 0.4, 4096, rpv)
+    assert cnt[0] > 2048 and cnt[1] == 3, cnt
+    rec, cnt, _ = _check_rows([(128, 200), (128, 400), (0, 0)], [small, big, []], 128, 32, 2, 0.5, 0.4, 100, rpv)      # other slots, truncated
+    assert cnt[1] > 2048 and cnt[0] == 3 and cnt[2] == 0
+
+
+# ---------------------------------------------------------------------------------------------- pipeline, host entry, limits
+def test_tiled_pipeline(models_, base):
+    det, rec = models_
+    n, F = len(S), 2
+    t = fa.Tiling(*TA, 2)
+    _, cnt = _detect_tiled(det, base.descs(), t)
+    want = np.minimum(cnt.cpu().numpy(), F)
+    assert want[-1] == 0 and (want > 0).sum() >= 6 and (want == F).sum() >= 3
+    faces = torch.full((n * F, 15), 7.0, device="cuda"); fo = torch.full((n * F,), -7, dtype=torch.int32, device="cuda")
+    emb = torch.full((n * F, 512), 7.0, device="cuda")
+    total = fa.pipeline_run_tiled_dev(det, rec, base.descs(), t, F, faces.data_ptr(), fo.data_ptr(), emb.data_ptr(), 0.5, 0.4)
+    torch.cuda.synchronize()
+    assert total == int(want.sum())
+    got_fo = fo.cpu().numpy()
+    assert np.array_equal(got_fo[:total], np.repeat(np.arange(n), want))
+    ser = torch.zeros((total, 512), device="cuda")
+    zero = torch.zeros(1, dtype=torch.int32, device="cuda")
+    for i in range(total):                                       # every face against the per-face call on its FRAME
+        ptr, rows, cols, step = base.desc(int(got_fo[i]))
+        one = faces[i:i + 1].contiguous()
+        assert fa.lib().fh_rec_embed_faces_dev(rec.handle, ptr, rows, cols, step, rows * step, one.data_ptr(), zero.data_ptr(), 1,
+                                               ser[i:i + 1].data_ptr(), 0, 0) == 1, _lib.last_error()
+    torch.cuda.synchronize()
+    a, b = emb[:total].cpu().numpy().astype(np.float64), ser.cpu().numpy().astype(np.float64)
+    worst = float((1.0 - (a * b).sum(1)).max())
+    print("tiled pipeline: total", total, "max 1 - cos vs batch of one", worst)
+    assert worst < 1e-6                                          # the bound test_mixed_pipeline holds for batch-of-many against batch-of-one
+    assert torch.all(emb[total:] == 7.0) and torch.all(faces[total:] == 7.0) and torch.all(fo[total:] == -7)
+
+
+def test_host_entry_back_to_back_calls_and_the_view_limit(models_, base):
+    det, _ = models_
+    t = fa.Tiling(*TA, 2)
+    out, cnt = _detect_tiled(det, base.descs([3]), t)
+    c = int(cnt.cpu().numpy()[0])
+    host = det.detect_tiled_records(base.imgs[3], t, 0.5, 0.4)
+    assert c > 0 and len(host) == c and host.tobytes() == _records(out, 1, MAX_PF)[0, :c].tobytes()
+    padded = np.full((37, 300 * 3 + 64), 0xEE, np.uint8); padded[:, :900] = base.imgs[6].reshape(37, -1)      # a strided host view
+    view = np.lib.stride_tricks.as_strided(padded, shape=(37, 300, 3), strides=(padded.strides[0], 3, 1))
+    assert det.detect_tiled_records(view, t).tobytes() == det.detect_tiled_records(base.imgs[6], t).tobytes()
+    assert len(det.detect_tiled_records(base.imgs[3], t, max_faces=1)) == 1 and len(det.detect_tiled_records(None, t)) == 0
+    # two calls with different tables and no synchronise in between equal the calls made alone
+    first, second = base.descs(), base.descs([4, 8, 2, 0])
+    alone = []
+    for d, tt in ((first, t), (second, fa.Tiling(*TB, 2))):
+        o, k = _detect_tiled(det, d, tt)
+        alone.append((o.cpu().numpy().tobytes(), k.cpu().numpy().tobytes()))
+    o1, c1 = _detect_tiled(det, first, t, sync=False)
+    o2, c2 = _detect_tiled(det, second, fa.Tiling(*TB, 2), sync=False)
+    torch.cuda.synchronize()
+    assert (o1.cpu().numpy().tobytes(), c1.cpu().numpy().tobytes()) == alone[0]
+    assert (o2.cpu().numpy().tobytes(), c2.cpu().numpy().tobytes()) == alone[1]
+    assert c2.cpu().numpy()[1] == 0 and c2.cpu().numpy()[0] > 0
+    # more than FH_TILE_MAX_VIEWS = 256 views in one call: FH_ERR_ARG, nothing launched
+    many = fa.frame_array(base.descs([7] * 12))                   # 12 x 22 = 264 views
+    o = torch.full((12, 4, 15), 3.0, device="cuda"); k = torch.full((12,), -1, dtype=torch.int32, device="cuda")
+    assert fa.lib().fh_det_detect_tiled_dev(det.handle, many, 12, C.byref(t), 0.5, 0.4, o.data_ptr(), 4, k.data_ptr(), 0) == -1
+    assert "FH_TILE_MAX_VIEWS" in _lib.last_error()
+    assert fa.lib().fh_det_run_network_tiled_dev(det.handle, many, 12, C.byref(t), 0) == -1
+    torch.cuda.synchronize()
+    assert torch.all(o == 3.0) and torch.all(k == -1)
+    assert fa.lib().fh_det_detect_tiled_dev(det.handle, many, 11, C.byref(t), 0.5, 0.4, o.data_ptr(), 4, k.data_ptr(), 0) == 11   # 242 views
+    torch.cuda.synchronize()
+    bad = fa.Tiling(8, 0, 2)
+    assert fa.lib().fh_det_detect_tiled_dev(det.handle, many, 1, C.byref(bad), 0.5, 0.4, o.data_ptr(), 4, k.data_ptr(), 0) == -1
+
+
+# ---------------------------------------------------------------------------------------------- end to end against the oracle
+# Fixed list of seeds; per frame shape the seed with the LARGEST pair margin among those that meet the criteria below was chosen on
+# the CPU, with the oracle alone (thresholds 0.5 / 0.4, tiling (128, 128, 32, 2)):  (300, 200) -> 901,  (128, 400) -> 905.
+E2E_SEEDS = [900, 901, 902, 903, 904, 905, 906, 907]
+E2E = [((300, 200), 901), ((128, 400), 905)]
+
+
+def test_end_to_end_against_the_oracle(models_, models_dir):
+    det, _ = models_
+    od = oracle.OracleDetector()
+    assert od.loadModel(util.tiny_scrfd(models_dir, hw=128, cls_bias=-2.0))
+    thr, nms, border = 0.5, 0.4, 2
+    shapes = [(r, c, 0) for (r, c), _ in E2E]
+    imgs = [np.ascontiguousarray(util.frames_u8(1, r, c, seed=s, smooth=True)[0]) for (r, c), s in E2E]
+    assert all(s in E2E_SEEDS for _, s in E2E)
+    refs = []
+    for img in imgs:                                             # the oracle's full path per view, then the model's merge
+        views = tile_model.plan(img.shape[0], img.shape[1], TA[0], TA[0], TA[1])
+        assert len(views) > 1
+        rows = []
+        for x, y, w, h, _ in views:
+            inp, scale = oracle.det_preprocess(np.ascontiguousarray(img[y:y + h, x:x + w]), IN, IN)
+            assert inp is not None and scale == tile_model.letterbox_scale(h, w, IN, IN)
+            rows.append(od.rows_from_outputs(od.run_network(inp)))
+        # the criteria the seeds were chosen by: no candidate within 1e-4 of the score threshold, no pair within 0.02 of the NMS threshold
+        assert np.abs(np.concatenate(rows)[:, 4] - thr).min() >= 1e-4
+        allc = np.concatenate([s for _, _, s in tile_model.candidates(rows, views, IN, IN, border, thr)])
+        pair = [util._iou_int(allc[i], allc[j]) for i in range(len(allc)) for j in range(i + 1, len(allc))]
+        assert all(abs(v - nms) >= 0.02 for v in pair if v == v)
+        refs.append(tile_model.merge(rows, views, IN, IN, border, thr, nms))
+    fr = Frames(shapes)
+    for i, img in enumerate(imgs):                               # (Frames draws its own pixels: put the chosen images in their place)
+        fr.buf[fr.offs[i]:fr.offs[i] + img.size] = dev(img.reshape(-1))
+    out, cnt = _detect_tiled(det, fr.descs(), fa.Tiling(*TA, border), thr, nms)
+    rec, cnt = _records(out, len(imgs), MAX_PF), cnt.cpu().numpy()
+    for b, ref in enumerate(refs):
+        assert len(ref) >= 2
+        util.assert_records_equivalent(rec[b, :cnt[b]], ref, thr, nms, max_unexplained=0)
