@@ -397,7 +397,7 @@ void Net::run_u8(const uint8_t* src, long img_stride, int srcH, int srcW, int st
         launch_stem_conv_u8(src, img_stride, srcH, srcW, step, batch, plan_.inH, plan_.inW, op.stride, op.Cout, P + d.w27, P + d.bias, P + d.wf,
                             P + d.bf, d.has_slope ? P + d.slope : nullptr, (int)op.act, op.out >= 0 ? tensor_ptr(op.out) : nullptr,
                             op.out2 >= 0 && !d.bn_fold_dst ? tensor_ptr(op.out2) : nullptr, d.has_aff ? P + d.s2 : nullptr,
-                            d.has_aff ? P + d.t2 : nullptr, s, d.wfr ? reinterpret_cast<const unsigned*>(P + d.wfr) : nullptr);
+                            d.has_aff ? P + d.t2 : nullptr, s, d.wfr ? reinterpret_cast<const unsigned*>(P + d.wfr) : nullptr, cus);
         timer.end(s, 5, 2.0 * op.macs * batch, op.bytes * batch);
         run(batch, s, 1);
         return;
@@ -548,6 +548,7 @@ void Net::run(int batch, hipStream_t s, int first_op) {
                 a.ks = 1; a.stride = 1; a.pad = 0; a.Kpad = d.Kpad; a.act = (int)op.act;
                 a.t_flops = 2.0 * op.macs * batch; a.t_bytes = op.bytes * batch;
                 a.slabs = partial_.as<float>();                             // (diagnostic builds park their phase stamps there)
+                a.cus = cus;
                 launch_dwpw(a, s);
                 break;
             }

@@ -239,9 +239,11 @@ void launch_rec_preprocess(const uint8_t* crops, int n, int H, int W, float* out
 // wf / biasf (optional): the same filter with the normalisation folded in, for the thread-per-pixel kernel: wf[(tap*3 + j)][Cout] =
 // w27[tap*3 + (2-j)] / 128 (j = byte of the BGR pixel), biasf = bias - 127.5/128 * sum_k w27[k].
 // wfrag (optional, Cout % 16 == 0, Cout <= 64): the folded weights as bf16 MFMA fragments (stem_pack_wfrag) -> matrix-core stem kernel
+// cus: compute units the persistent grids are sized for (0 = the whole device), as ConvArgs::cus
 void launch_stem_conv_u8(const uint8_t* src, long img_stride, int srcH, int srcW, int step, int B, int inH, int inW, int stride,
                          int Cout, const float* w27, const float* bias, const float* wf, const float* biasf, const float* slope, int act,
-                         float* out1, float* out2, const float* s2, const float* t2, hipStream_t s, const unsigned* wfrag = nullptr);
+                         float* out1, float* out2, const float* s2, const float* t2, hipStream_t s, const unsigned* wfrag = nullptr,
+                         int cus = 0);
 
 struct DecodeArgs {
     const float* score[3];  // per stride [B, gh*gw*2]

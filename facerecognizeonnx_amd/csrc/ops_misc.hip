@@ -822,12 +822,12 @@ __global__ __launch_bounds__(256, 3) void stem_mfma_kernel(const uint8_t* __rest
 template <int STRIDE>
 static bool launch_stem_mfma(const uint8_t* src, long img_stride, int srcH, int srcW, int step, int B, int inH, int inW, int Cout,
                              const unsigned* wfrag, const float* biasf, const float* slope, int act, float* out1, float* out2, const float* s2,
-                             const float* t2, hipStream_t s) {
+                             const float* t2, hipStream_t s, int cus) {
     const int Ho = (inH + 2 - 3) / STRIDE + 1, Wo = (inW + 2 - 3) / STRIDE + 1;
     const int tiles_x = (Wo + STEM_TILE - 1) / STEM_TILE, tiles_y = (Ho + STEM_TILE - 1) / STEM_TILE;
     const int tiles_total = B * tiles_x * tiles_y;
     if ((long)srcH * step >= (1L << 31)) return false;
-    const int grid = std::max(8, std::min((tiles_total + 7) / 8 * 8, conv_num_cus() * 3) / 8 * 8);
+    const int grid = std::max(8, std::min((tiles_total + 7) / 8 * 8, (cus > 0 ? cus : conv_num_cus()) * 3) / 8 * 8);
 #define FH_STEM_MFMA(CB)                                                                                                                   \
     hipLaunchKernelGGL((stem_mfma_kernel<STRIDE, CB>), dim3(grid), dim3(256), 0, s, src, img_stride, srcH, srcW, step, inH, inW, Ho, Wo, wfrag, \
                        biasf, slope, act, out1, out2, s2, t2, tiles_x, tiles_y, tiles_total)
@@ -841,11 +841,11 @@ static bool launch_stem_mfma(const uint8_t* src, long img_stride, int srcH, int 
 
 void launch_stem_conv_u8(const uint8_t* src, long img_stride, int srcH, int srcW, int step, int B, int inH, int inW, int stride,
                          int Cout, const float* w27, const float* bias, const float* wf, const float* biasf, const float* slope, int act,
-                         float* out1, float* out2, const float* s2, const float* t2, hipStream_t s, const unsigned* wfrag) {
+                         float* out1, float* out2, const float* s2, const float* t2, hipStream_t s, const unsigned* wfrag, int cus) {
     static const bool mfma_on = !(getenv("FACEHIP_STEM_MFMA") && atoi(getenv("FACEHIP_STEM_MFMA")) == 0);       // A/B switch
     if (wfrag && biasf && mfma_on && Cout > 32) {                  // (16 / 32 channels: the thread-per-pixel kernel below is at its output-write bound)
-        if (stride == 1 ? launch_stem_mfma<1>(src, img_stride, srcH, srcW, step, B, inH, inW, Cout, wfrag, biasf, slope, act, out1, out2, s2, t2, s)
-                        : launch_stem_mfma<2>(src, img_stride, srcH, srcW, step, B, inH, inW, Cout, wfrag, biasf, slope, act, out1, out2, s2, t2, s))
+        if (stride == 1 ? launch_stem_mfma<1>(src, img_stride, srcH, srcW, step, B, inH, inW, Cout, wfrag, biasf, slope, act, out1, out2, s2, t2, s, cus)
+                        : launch_stem_mfma<2>(src, img_stride, srcH, srcW, step, B, inH, inW, Cout, wfrag, biasf, slope, act, out1, out2, s2, t2, s, cus))
             return;
     }
     if (wf && stem_px_enabled()) {
@@ -860,7 +860,7 @@ void launch_stem_conv_u8(const uint8_t* src, long img_stride, int srcH, int srcW
     }
     const int Ho = (inH + 2 - 3) / stride + 1, Wo = (inW + 2 - 3) / stride + 1;
     const int ntiles = B * ((Wo + STEM_TILE - 1) / STEM_TILE) * ((Ho + STEM_TILE - 1) / STEM_TILE);
-    const int blocks = ntiles < 256 * 8 ? ntiles : 256 * 8;
+    const int blocks = std::min(ntiles, (cus > 0 ? cus : 256) * 8);
     if (stride == 1)
         hipLaunchKernelGGL(stem_conv_u8_kernel<1>, dim3(blocks), dim3(256), 0, s, src, img_stride, srcH, srcW, step, inH, inW, Ho, Wo, Cout,
                            w27, bias, slope, act, out1, out2, s2, t2, ntiles);

@@ -126,8 +126,9 @@ def assert_records_equivalent(got, ref, score_thr, nms_thr, box_tol=1, lm_tol=1e
     return len(missing), len(surplus)
 
 
-def dwpw_graph(path, H, W, Cc, Cout, ds):
-    """input [1,3,H,W] -> Conv3x3(3 -> Cc)+ReLU -> depthwise 3x3 stride `ds` +ReLU -> pointwise 1x1 (Cc -> Cout)+ReLU -> [H'W', Cout]"""
+def dwpw_graph(path, H, W, Cc, Cout, ds, stem_stride=1):
+    """input [1,3,H,W] -> Conv3x3(3 -> Cc) stride `stem_stride` +ReLU -> depthwise 3x3 stride `ds` +ReLU -> pointwise 1x1 (Cc -> Cout)+ReLU
+    -> [H'W', Cout]"""
     from facerecognizeonnx_amd.synth.onnx_writer import OnnxBuilder
     rng = np.random.default_rng(H * 100 + Cc)
     b = OnnxBuilder("dwpw")
@@ -135,7 +136,8 @@ def dwpw_graph(path, H, W, Cc, Cout, ds):
     def conv(x, w, bias, relu=True, **kw):
         y = b.node("Conv", [x, b.init(b.uid("w"), w.astype(np.float32)), b.init(b.uid("b"), bias.astype(np.float32))], **kw)
         return b.node("Relu", [y]) if relu else y
-    y = conv(x, rng.standard_normal((Cc, 3, 3, 3)) / 5, rng.standard_normal(Cc) / 10, kernel_shape=[3, 3], pads=[1, 1, 1, 1], strides=[1, 1])
+    y = conv(x, rng.standard_normal((Cc, 3, 3, 3)) / 5, rng.standard_normal(Cc) / 10, kernel_shape=[3, 3], pads=[1, 1, 1, 1],
+             strides=[stem_stride, stem_stride])
     y = conv(y, rng.standard_normal((Cc, 1, 3, 3)) / 3, rng.standard_normal(Cc) / 10, kernel_shape=[3, 3], pads=[1, 1, 1, 1], strides=[ds, ds], group=Cc)
     y = conv(y, rng.standard_normal((Cout, Cc, 1, 1)) / np.sqrt(Cc), rng.standard_normal(Cout) / 10, kernel_shape=[1, 1], strides=[1, 1])
     y = b.node("Transpose", [y], perm=[0, 2, 3, 1])
