@@ -40,6 +40,16 @@ class FhView(C.Structure):
     _fields_ = [("x", C.c_int32), ("y", C.c_int32), ("w", C.c_int32), ("h", C.c_int32), ("edges", C.c_int32)]
 
 
+TRACK_DTYPE = np.dtype([(k, "<i4") for k in ("id", "x", "y", "w", "h", "last_seen", "last_embed", "hits")])
+assert TRACK_DTYPE.itemsize == 32
+TRACK_MAX = 64                                                 # FH_TRACK_MAX
+
+
+class FhTrackState(C.Structure):
+    """fh_track_state: one track slot of a stream (id = -1: free).  32 bytes."""
+    _fields_ = [(k, C.c_int32) for k in ("id", "x", "y", "w", "h", "last_seen", "last_embed", "hits")]
+
+
 def build(force: bool = False) -> str:
     """Compile libfacehip.so in-tree (so that it travels with the source snapshot)."""
     srcs = [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [os.path.join(_HERE, "..", "include", "facehip.h")]
@@ -121,6 +131,14 @@ PROTOTYPES = {
     "fh_stream_destroy": (None, [_vp]),
     "fh_stream_submit": (_i, [_vp, _vp, _i, _f, _f]),
     "fh_stream_collect": (_i, [_vp, _vp, _vp, _vp, _i]),
+    "fh_tracker_create": (_vp, [_i, _i, _f, _i, _i]),
+    "fh_tracker_destroy": (None, [_vp]),
+    "fh_tracker_reset": (_i, [_vp, _i]),
+    "fh_tracker_get_state": (_i, [_vp, _i, _vp, _ip, _ip]),
+    "fh_track_plan": (_i, [_vp, _i, _i, _vp, _vp]),
+    "fh_track_update_dev": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),
+    "fh_track_select_dev": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "fh_pipeline_run_tracked_dev": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _ll, _vp, _f, _f, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "fh_gallery_create": (_vp, [_i]),
     "fh_gallery_destroy": (None, [_vp]),
     "fh_gallery_upload": (_i, [_vp, _vp, _ll, _i, _ll]),

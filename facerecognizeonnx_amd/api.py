@@ -19,7 +19,7 @@ from typing import List, Optional
 import numpy as np
 
 from . import _lib
-from ._lib import FACE_DTYPE, check
+from ._lib import FACE_DTYPE, TRACK_DTYPE, check
 
 
 @dataclass
@@ -322,6 +322,89 @@ def pipeline_run_tiled_dev(det: FaceDetector, rec: FaceRecognizer, frames, tilin
     return check(_lib.lib().fh_pipeline_run_tiled_dev(det.handle, rec.handle, arr, _frame_count(arr), C.byref(t), scoreThreshold,
                                                       nmsThreshold, faces_per_frame, faces_ptr, frame_of_ptr, emb_ptr, stream),
                  "fh_pipeline_run_tiled_dev")
+
+
+def _stream_of(stream_of, n: int):
+    """HOST int32[n] stream indices of a tracker call (None = every frame on stream 0): (array kept alive by the caller, pointer)."""
+    if stream_of is None:
+        return None, None
+    a = np.ascontiguousarray(np.asarray(stream_of, np.int32).reshape(-1))
+    if a.size != n:
+        raise ValueError(f"stream_of holds {a.size} entries for {n} frames")
+    return a, a.ctypes.data
+
+
+def track_plan(stream_of, streams: int):
+    """(order, starts) of fh_track_plan — host only: the frame indices grouped by stream, ascending within a stream, and each stream's
+    offset into them (streams + 1 entries).  The order in which Tracker.update_dev walks a batch."""
+    a = np.ascontiguousarray(np.asarray(stream_of, np.int32).reshape(-1))
+    order, starts = np.empty(max(a.size, 1), np.int32), np.empty(max(int(streams), 0) + 1, np.int32)
+    check(_lib.lib().fh_track_plan(a.ctypes.data if a.size else None, a.size, int(streams), order.ctypes.data, starts.ctypes.data),
+          "fh_track_plan")
+    return order[:a.size].copy(), starts
+
+
+class Tracker:
+    """fh_tracker: device-resident face tracks per camera stream (include/facehip.h, "face tracker").  `refresh` = 0 embeds a track
+    once, when it opens; k > 0 again every k frames.  A track survives `max_missed` consecutive frames without a detection."""
+
+    def __init__(self, streams: int = 1, max_tracks: int = _lib.TRACK_MAX, iou_thr: float = 0.3, max_missed: int = 0, refresh: int = 0):
+        self._h = _lib.lib().fh_tracker_create(int(streams), int(max_tracks), float(iou_thr), int(max_missed), int(refresh))
+        if not self._h:
+            raise _lib.FaceHipError(f"fh_tracker_create failed: {_lib.last_error()}")
+        self.streams, self.max_tracks = int(streams), int(max_tracks)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            _lib.lib().fh_tracker_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        self.close()
+
+    @property
+    def handle(self):
+        return self._h
+
+    def update_dev(self, det_ptr: int, counts_ptr: int, n: int, per_frame: int, track_ptr: int, embed_ptr: int, stream_of=None,
+                   stream: int = 0) -> int:
+        """Steps 1-4 of the contract on n frames of [per_frame] records; writes track ids and embed flags [n][per_frame]."""
+        keep, sp = _stream_of(stream_of, n)
+        return check(_lib.lib().fh_track_update_dev(self._h, det_ptr, counts_ptr, n, per_frame, sp, track_ptr, embed_ptr, stream),
+                     "fh_track_update_dev")
+
+    @staticmethod
+    def select_dev(det_ptr: int, embed_ptr: int, n: int, per_frame: int, faces_ptr: int, frame_of_ptr: int, track_ptr: int,
+                   track_of_ptr: int, total_ptr: int, stream: int = 0) -> int:
+        """The flagged records, densely in (frame, slot) order, with frame index and track id; total_ptr[0] = their number."""
+        return check(_lib.lib().fh_track_select_dev(det_ptr, embed_ptr, n, per_frame, faces_ptr, frame_of_ptr, track_ptr, track_of_ptr,
+                                                    total_ptr, stream), "fh_track_select_dev")
+
+    def reset(self, stream: int = -1) -> None:
+        check(_lib.lib().fh_tracker_reset(self._h, int(stream)), "fh_tracker_reset")
+
+    def state(self, stream: int = 0, counters: bool = False):
+        """The live slots of one stream, ascending, as TRACK_DTYPE records; with counters=True: (records, frame_no, next_id)."""
+        out = np.zeros(self.max_tracks, TRACK_DTYPE)
+        fno, nid = C.c_int(), C.c_int()
+        live = check(_lib.lib().fh_tracker_get_state(self._h, int(stream), out.ctypes.data, C.byref(fno), C.byref(nid)),
+                     "fh_tracker_get_state")
+        return (out[:live].copy(), fno.value, nid.value) if counters else out[:live].copy()
+
+
+def pipeline_run_tracked_dev(det: FaceDetector, rec: FaceRecognizer, tracker: Tracker, frames_ptr: int, n: int, rows: int, cols: int,
+                             faces_per_frame: int, all_ptr: int, counts_ptr: int, track_ptr: int, faces_ptr: int, frame_of_ptr: int,
+                             track_of_ptr: int, emb_ptr: int, stream_of=None, scoreThreshold: float = 0.5, nmsThreshold: float = 0.4,
+                             stream: int = 0) -> int:
+    """pipeline_run_dev for video (fh_pipeline_run_tracked_dev): detect every frame, track, and align + embed only the faces that open a
+    track, are due for a refresh or found no free slot.  all_ptr / counts_ptr / track_ptr = every frame's records [n][F], counts [n]
+    and track ids [n][F]; the embedded list (faces, frame index, track id, embedding) holds up to n * F entries.  Returns its length."""
+    step = cols * 3
+    keep, sp = _stream_of(stream_of, n)
+    return check(_lib.lib().fh_pipeline_run_tracked_dev(det.handle, rec.handle, tracker.handle if tracker is not None else None,
+                                                        frames_ptr, n, rows, cols, step, rows * step, sp, scoreThreshold, nmsThreshold,
+                                                        faces_per_frame, all_ptr, counts_ptr, track_ptr, faces_ptr, frame_of_ptr,
+                                                        track_of_ptr, emb_ptr, stream), "fh_pipeline_run_tracked_dev")
 
 
 def pipeline_images(det: FaceDetector, rec: FaceRecognizer, images, faces_per_frame: int = 1, scoreThreshold: float = 0.5,

@@ -10,10 +10,13 @@
 #include "../../include/facehip.h"
 #include "engine.h"
 #include "group_ids.h"
+#include "track_plan.h"
 
 static_assert(sizeof(fh_face) == 60 && sizeof(fh::FaceRec) == 60, "FaceBox mirror must stay 60 bytes");
 static_assert(sizeof(fh_frame) == 24 && sizeof(fh::FrameIn) == 24 && offsetof(fh_frame, rows) == offsetof(fh::FrameIn, rows) &&
               offsetof(fh_frame, step) == offsetof(fh::FrameIn, step), "fh_frame and the engine's FrameIn are one layout");
+static_assert(sizeof(fh_track_state) == sizeof(fh::TrackState) && offsetof(fh_track_state, hits) == offsetof(fh::TrackState, hits) &&
+              FH_TRACK_MAX == 64, "fh_track_state mirrors TrackState; one slot per lane of a wave");
 static_assert(sizeof(fh_tiling) == sizeof(fh::Tiling) && offsetof(fh_tiling, border) == offsetof(fh::Tiling, border) &&
               sizeof(fh_view) == sizeof(fh::View) && offsetof(fh_view, edges) == offsetof(fh::View, edges) &&
               FH_TILE_MAX_VIEWS == fh::kTileMaxViews && FH_ERR_ARG == fh::kTilePlanBadArg, "fh_tiling / fh_view mirror tile_plan.h");
@@ -707,6 +710,12 @@ namespace {
 // (4 bytes through pinned memory, behind an event on sd).  Everything after it — align + embed — is sized by that count, so
 // the recogniser never runs on empty slots (the reference embeds "for every face", src/main.cpp:221-238: 0..F per frame).
 // (detect(out, max_per_frame, counts) runs the detector of the caller's kind — uniform or ragged — on sd)
+int count_handoff(fh_det* d, const int* dt, hipStream_t sd) {
+    FH_HIP(hipMemcpyAsync(d->h_total, dt, sizeof(int), hipMemcpyDeviceToHost, sd));
+    FH_HIP(hipEventRecord(d->ev_sel, sd));
+    FH_HIP(hipEventSynchronize(d->ev_sel));               // waits for the DETECTOR of this batch only; a recogniser queued earlier on another stream keeps running
+    return *d->h_total;
+}
 extern "C++" template <class Detect>
 int detect_select_count_with(fh_det* d, int n, int F, fh_face* faces, int* frame_of, int* d_total, hipStream_t sd, Detect&& detect) {
     d->p_det.ensure((size_t)n * F * sizeof(fh_face));
@@ -717,10 +726,7 @@ int detect_select_count_with(fh_det* d, int n, int F, fh_face* faces, int* frame
     int* dt = d_total ? d_total : d->p_total.as<int>();
     detect(d->p_det.as<fh::FaceRec>(), F, d->p_cnt.as<int>());
     fh::launch_select_faces(d->p_det.as<fh::FaceRec>(), d->p_cnt.as<int>(), n, F, F, reinterpret_cast<fh::FaceRec*>(faces), frame_of, dt, sd);
-    FH_HIP(hipMemcpyAsync(d->h_total, dt, sizeof(int), hipMemcpyDeviceToHost, sd));
-    FH_HIP(hipEventRecord(d->ev_sel, sd));
-    FH_HIP(hipEventSynchronize(d->ev_sel));               // waits for the DETECTOR of this batch only; a recogniser queued earlier on another stream keeps running
-    return *d->h_total;
+    return count_handoff(d, dt, sd);
 }
 int detect_select_count(fh_det* d, const uint8_t* frames, int n, int rows, int cols, int step, long stride, float score_thr, float nms_thr,
                         int F, fh_face* faces, int* frame_of, int* d_total, hipStream_t sd) {
@@ -844,6 +850,95 @@ int fh_pipeline_submit_dev(fh_det* d, fh_rec* r, const uint8_t* frames, int n, i
         const int total = detect_select_count(d, frames, n, rows, cols, step, (long)stride, score_thr, nms_thr, F, faces, frame_of, d_total, sd);
         if (sd != sr) FH_HIP(hipStreamWaitEvent(sr, d->ev_sel, 0));
         r->rec.embed_faces_dev(frames, rows, cols, step, (long)stride, reinterpret_cast<const fh::FaceRec*>(faces), frame_of, total, emb, nullptr, sr);
+        return total;
+    });
+}
+
+// ---------------------------------------------------------------------------------- face tracker
+struct fh_tracker {
+    fh_tracker(int streams, int max_tracks, float iou_thr, int max_missed, int refresh) : t(streams, max_tracks, iou_thr, max_missed, refresh) {}
+    fh::Tracker t;
+};
+namespace {
+// the batch of a tracker call: 1 <= n <= 4096, per_frame >= 1, every stream index inside the tracker.  Null on success.
+const char* bad_track_batch(const fh_tracker* t, int n, int per_frame, const int* stream_of) {
+    if (n < 1 || n > fh::kTrackMaxFrames) return "need 1 <= n <= 4096 frames";
+    if (per_frame < 1) return "need per_frame >= 1";
+    if (stream_of)
+        for (int f = 0; f < n; ++f)
+            if (stream_of[f] < 0 || stream_of[f] >= t->t.streams()) return "a stream_of entry is outside [0, streams)";
+    return nullptr;
+}
+}  // namespace
+
+fh_tracker* fh_tracker_create(int streams, int max_tracks, float iou_thr, int max_missed, int refresh) {
+    if (streams < 1 || streams > fh::kTrackMaxStreams || max_tracks < 1 || max_tracks > FH_TRACK_MAX || max_missed < 0 || refresh < 0) {
+        g_err = "fh_tracker_create: need 1 <= streams <= 4096, 1 <= max_tracks <= FH_TRACK_MAX, max_missed >= 0, refresh >= 0";
+        return nullptr;
+    }
+    fh_tracker* h = nullptr;
+    const int rc = guarded([&] { h = new fh_tracker(streams, max_tracks, iou_thr, max_missed, refresh); return 0; });
+    return rc == 0 ? h : nullptr;
+}
+void fh_tracker_destroy(fh_tracker* t) { delete t; }
+int fh_tracker_reset(fh_tracker* t, int stream) {
+    if (!t) return arg_error("fh_tracker_reset: null handle");
+    if (stream < -1 || stream >= t->t.streams()) return arg_error("fh_tracker_reset: no such stream");
+    return guarded([&] { t->t.reset(stream); return 0; });
+}
+int fh_tracker_get_state(fh_tracker* t, int stream, fh_track_state* out, int* frame_no, int* next_id) {
+    if (!t) return arg_error("fh_tracker_get_state: null handle");
+    if (stream < 0 || stream >= t->t.streams()) return arg_error("fh_tracker_get_state: no such stream");
+    return guarded([&] { return t->t.get_state(stream, reinterpret_cast<fh::TrackState*>(out), frame_no, next_id); });
+}
+int fh_track_plan(const int* stream_of, int n, int streams, int* order, int* starts) {
+    if (!order || !starts) return arg_error("fh_track_plan: null argument");
+    if (fh::track_plan(stream_of, n, streams, order, starts) != 0)
+        return arg_error("fh_track_plan: need 1 <= n <= 4096, 1 <= streams <= 4096 and every stream index in [0, streams)");
+    return 0;
+}
+int fh_track_update_dev(fh_tracker* t, const fh_face* det, const int* counts, int n, int per_frame, const int* stream_of, int* track,
+                        int* embed, void* stream) {
+    if (!t || !det || !counts || !track || !embed) return arg_error("fh_track_update_dev: null argument");
+    if (const char* bad = bad_track_batch(t, n, per_frame, stream_of)) return frames_error("fh_track_update_dev", bad);
+    return guarded([&] {
+        t->t.update_dev(reinterpret_cast<const fh::FaceRec*>(det), counts, n, per_frame, stream_of, track, embed, S(stream));
+        return n;
+    });
+}
+int fh_track_select_dev(const fh_face* det, const int* embed, int n, int per_frame, fh_face* faces, int* frame_of, const int* track,
+                        int* track_of, int* total, void* stream) {
+    if (!det || !embed || !faces || !frame_of || !track || !track_of || !total) return arg_error("fh_track_select_dev: null argument");
+    if (n < 1 || n > fh::kTrackMaxFrames || per_frame < 1) return arg_error("fh_track_select_dev: need 1 <= n <= 4096 frames and per_frame >= 1");
+    return guarded([&] {
+        fh::launch_track_select(reinterpret_cast<const fh::FaceRec*>(det), embed, track, n, per_frame, reinterpret_cast<fh::FaceRec*>(faces),
+                                frame_of, track_of, total, S(stream));
+        FH_HIP(hipGetLastError());
+        return n;
+    });
+}
+// fh_pipeline_run_dev with the tracker between the NMS and the selection: detect -> update -> flagged select -> the one 4-byte
+// hand-off -> align + embed on exactly the flagged faces, all on `stream`.
+int fh_pipeline_run_tracked_dev(fh_det* d, fh_rec* r, fh_tracker* t, const uint8_t* frames, int n, int rows, int cols, int step,
+                                long long stride, const int* stream_of, float score_thr, float nms_thr, int F, fh_face* all, int* counts,
+                                int* track, fh_face* faces, int* frame_of, int* track_of, float* emb, void* stream) {
+    if (!d || !r || !t || !frames || !all || !counts || !track || !faces || !frame_of || !track_of || !emb)
+        return arg_error("fh_pipeline_run_tracked_dev: null argument");
+    if (const char* bad = bad_track_batch(t, n, F, stream_of)) return frames_error("fh_pipeline_run_tracked_dev", bad);
+    if (rows <= 0 || cols <= 0 || step < cols * 3) return arg_error("fh_pipeline_run_tracked_dev: bad size");
+    Owns owns(&d->det.net(), &r->rec.net());
+    return guarded([&] {
+        hipStream_t s = S(stream);
+        d->p_total.ensure(sizeof(int));
+        if (!d->ev_sel) FH_HIP(hipEventCreateWithFlags(&d->ev_sel, hipEventDisableTiming));
+        if (!d->h_total) FH_HIP(hipHostMalloc(reinterpret_cast<void**>(&d->h_total), sizeof(int), hipHostMallocDefault));
+        int* flags = t->t.embed_scratch((size_t)n * F);
+        fh::FaceRec* rec_all = reinterpret_cast<fh::FaceRec*>(all);
+        d->det.detect_dev(frames, n, rows, cols, step, (long)stride, score_thr, nms_thr, rec_all, F, counts, s);
+        t->t.update_dev(rec_all, counts, n, F, stream_of, track, flags, s);
+        fh::launch_track_select(rec_all, flags, track, n, F, reinterpret_cast<fh::FaceRec*>(faces), frame_of, track_of, d->p_total.as<int>(), s);
+        const int total = count_handoff(d, d->p_total.as<int>(), s);
+        r->rec.embed_faces_dev(frames, rows, cols, step, (long)stride, reinterpret_cast<const fh::FaceRec*>(faces), frame_of, total, emb, nullptr, s);
         return total;
     });
 }

@@ -2,6 +2,7 @@
 #include "engine.h"
 
 #include "group_ids.h"
+#include "track_plan.h"
 
 #include <atomic>
 #include <cstdio>
@@ -1268,6 +1269,47 @@ void Gallery::topk_f32(const float* q, int Q, int k, float* out_score, int* out_
     launch_gallery_topk(rows_.as<float>(), n_, dim_, qpack_.as<float>(), Q, k, base_, ps_.as<float>(), pi_.as<int>(),
                         qcount ? nullptr : seed_s_.as<float>(), qcount ? nullptr : seed_i_.as<int>(), s, qcount);
     launch_topk_merge(ps_.as<float>(), pi_.as<int>(), parts, Q, k, out_score, out_idx, s, qcount);
+    FH_HIP(hipGetLastError());
+}
+
+// ------------------------------------------------------------------------------------------ face tracker
+Tracker::Tracker(int streams, int max_tracks, float iou_thr, int max_missed, int refresh)
+    : streams_(streams), p_{max_tracks, iou_thr, max_missed, refresh} {
+    state_.ensure((size_t)streams * (2 * sizeof(int) + (size_t)max_tracks * sizeof(TrackState)));
+    reset(-1);
+}
+
+void Tracker::reset(int stream) {
+    FH_HIP(hipDeviceSynchronize());                              // a queued update still reads and writes the state
+    const int first = stream < 0 ? 0 : stream, count = stream < 0 ? streams_ : 1;
+    const std::vector<TrackState> free_slots((size_t)count * p_.max_tracks, TrackState{-1, 0, 0, 0, 0, 0, 0, 0});
+    FH_HIP(hipMemset(heads() + 2 * (size_t)first, 0, (size_t)count * 2 * sizeof(int)));
+    FH_HIP(hipMemcpy(slots() + (size_t)first * p_.max_tracks, free_slots.data(), free_slots.size() * sizeof(TrackState), hipMemcpyHostToDevice));
+}
+
+int Tracker::get_state(int stream, TrackState* out, int* frame_no, int* next_id) {
+    FH_HIP(hipDeviceSynchronize());
+    int head[2];
+    std::vector<TrackState> all((size_t)p_.max_tracks);
+    FH_HIP(hipMemcpy(head, heads() + 2 * (size_t)stream, sizeof head, hipMemcpyDeviceToHost));
+    FH_HIP(hipMemcpy(all.data(), slots() + (size_t)stream * p_.max_tracks, all.size() * sizeof(TrackState), hipMemcpyDeviceToHost));
+    if (frame_no) *frame_no = head[0];
+    if (next_id) *next_id = head[1];
+    int live = 0;
+    for (const TrackState& t : all)
+        if (t.id >= 0) { if (out) out[live] = t; ++live; }
+    if (out)
+        for (int i = live; i < p_.max_tracks; ++i) out[i] = TrackState{-1, 0, 0, 0, 0, 0, 0, 0};
+    return live;
+}
+
+void Tracker::update_dev(const FaceRec* det, const int* counts, int n, int per_frame, const int* stream_of, int* track, int* embed,
+                         hipStream_t s) {
+    const size_t bytes = ((size_t)n + streams_ + 1) * sizeof(int);
+    int* order = static_cast<int*>(plan_.stage(bytes));
+    if (track_plan(stream_of, n, streams_, order, order + n) != 0) throw std::runtime_error("tracker: bad stream_of");   // (checked by the caller)
+    const int* d_order = static_cast<const int*>(plan_.send(bytes, s));
+    launch_track_update(heads(), slots(), streams_, p_, det, counts, per_frame, d_order, d_order + n, track, embed, s);
     FH_HIP(hipGetLastError());
 }
 

@@ -282,6 +282,31 @@ class Recognizer {
     DevBuf crops_, ok_, raw_;
 };
 
+// The face tracker behind fh_tracker (include/facehip.h): per stream a (frame_no, next_id) head and max_tracks slots, resident on the
+// device; one wave per stream updates them (track.hip).  The walk order of a call is planned on the host (track_plan.h) and sent
+// through a StagedTable, so the next call may follow at once with another stream_of.
+class Tracker {
+  public:
+    Tracker(int streams, int max_tracks, float iou_thr, int max_missed, int refresh);
+    int streams() const { return streams_; }
+    int max_tracks() const { return p_.max_tracks; }
+    void reset(int stream);                                      // -1: all; synchronous
+    // live slots of one stream, ascending, into out[max_tracks] (the rest: id = -1); returns their number; synchronous
+    int get_state(int stream, TrackState* out, int* frame_no, int* next_id);
+    // stream_of: HOST [n], already checked against [0, streams) (null: all stream 0).  track / embed = device [n][per_frame].
+    void update_dev(const FaceRec* det, const int* counts, int n, int per_frame, const int* stream_of, int* track, int* embed,
+                    hipStream_t s);
+    int* embed_scratch(size_t entries) { embed_.ensure(entries * sizeof(int)); return embed_.as<int>(); }   // the pipeline's flags
+
+  private:
+    int* heads() const { return state_.as<int>(); }
+    TrackState* slots() const { return reinterpret_cast<TrackState*>(state_.as<int>() + 2 * (size_t)streams_); }
+    int streams_;
+    TrackParams p_;
+    DevBuf state_, embed_;                                       // [streams][2] heads, then [streams][max_tracks] slots
+    StagedTable plan_;                                           // order[n], then starts[streams + 1]
+};
+
 class Gallery {
   public:
     explicit Gallery(int dim) : dim_(dim) {}

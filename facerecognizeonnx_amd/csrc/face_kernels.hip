@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include "face_emit.h"
+#include "face_iou.h"
 #include "kernels.h"
 
 namespace fh {
@@ -338,15 +339,7 @@ void launch_rows_threshold(const float* rows, int B, int n, int feat, float scal
 // place in global memory otherwise), then the greedy sweep with all lanes testing one pivot
 // against the remaining boxes, then an ordered compaction of the survivors.
 // ------------------------------------------------------------------------------------------
-__device__ __forceinline__ float iou_int(int4 a, int4 b) {
-    const int x1 = max(a.x, b.x), y1 = max(a.y, b.y);
-    const int x2 = min(a.x + a.z, b.x + b.z), y2 = min(a.y + a.w, b.y + b.w);
-    const int w = max(0, x2 - x1), h = max(0, y2 - y1);
-    const int inter = w * h;
-    const int area1 = a.z * a.w, area2 = b.z * b.w;
-    return (float)inter / (float)(area1 + area2 - inter);
-}
-
+// (iou_int: face_iou.h, shared with the tracker)
 constexpr int NMS_T = 1024;
 constexpr int NMS_SMALL = 2048;
 

@@ -396,4 +396,23 @@ void launch_gallery16_scatter(const float* fb_score, const int* fb_idx_out, int 
 void launch_select_faces(const FaceRec* det, const int* counts, int n, int per_frame, int F, FaceRec* faces, int* frame_of,
                          int* total, hipStream_t s);
 
+// --------------------------------------------------------------------------------------------
+// Face tracker (track.hip; the contract is in include/facehip.h)
+// --------------------------------------------------------------------------------------------
+struct TrackState {         // layout of fh_track_state, 32 B; id = -1: a free slot
+    int32_t id, x, y, w, h, last_seen, last_embed, hits;
+};
+struct TrackParams {
+    int max_tracks;         // 1 .. 64 slots per stream (one lane each)
+    float iou_thr;
+    int max_missed, refresh;
+};
+// One wave per stream walks starts[s] .. starts[s + 1] of `order` (track_plan.h).  heads = [streams][2] (frame_no, next_id), slots =
+// [streams][max_tracks].  det = [n][per_frame] records, counts = [n]; track / embed = [n][per_frame] are written entirely.
+void launch_track_update(int* heads, TrackState* slots, int streams, TrackParams p, const FaceRec* det, const int* counts, int per_frame,
+                         const int* order, const int* starts, int* track, int* embed, hipStream_t s);
+// the flagged twin of launch_select_faces: the records with embed != 0, densely in (frame, slot) order, with frame index and track id
+void launch_track_select(const FaceRec* det, const int* embed, const int* track, int n, int per_frame, FaceRec* faces, int* frame_of,
+                         int* track_of, int* total, hipStream_t s);
+
 }  // namespace fh

@@ -264,6 +264,63 @@ FH_API void fh_stream_destroy(fh_stream* s);
 FH_API int fh_stream_submit(fh_stream* s, const uint8_t* host_frames, int n_frames, float score_thr, float nms_thr);
 FH_API int fh_stream_collect(fh_stream* s, fh_face* faces, int* frame_of, float* emb, int cap);
 
+/* ---- face tracker for VIDEO: stable per-camera track ids on the device, and a recogniser that runs once per track instead of once per
+ * face per frame.  The entry points above reproduce the webcam loop literally (src/main.cpp:214-258: detect, then embed EVERY face of
+ * EVERY frame) and are unchanged.  The tracker sits between the detector's NMS and the face selection; fh_pipeline_run_tracked_dev then
+ * aligns and embeds only the faces that OPEN a track, whose track is due for a REFRESH, or that found NO FREE SLOT.  Everything is
+ * integers plus FaceDetector::iou (src/face_detector.cpp:340-354: integer intersection and areas, one fp32 division — the function the
+ * NMS uses), so the result is defined to the bit.
+ *
+ * Limits (anything else: FH_ERR_ARG — NULL from fh_tracker_create — before anything is launched, no state changes): 1 <= streams <= 4096,
+ * 1 <= max_tracks <= FH_TRACK_MAX, max_missed >= 0, refresh >= 0, 1 <= n <= 4096, per_frame >= 1, every stream_of[f] in [0, streams).
+ * Frame order: within one call the frames of a stream are consecutive in time in batch order, and successive calls continue the
+ *   stream.  stream_of (HOST memory, read before the call returns; NULL = every frame on stream 0) may interleave cameras freely: a
+ *   [t][camera] live batch and one camera's clip are the same case.  The next call may follow at once with another array.
+ * fh_track_plan (host only, no GPU) is the stable counting sort the device walks: order[n] = the frame indices grouped by stream,
+ *   ascending within a stream; stream s owns order[starts[s] .. starts[s + 1]).  Returns 0 or FH_ERR_ARG.
+ * State, per stream, on the device: frame_no (frames ever seen, from 0), next_id (from 0) and max_tracks slots of fh_track_state; a
+ *   slot with id = -1 is free.  All counters are int32: a stream of more than 2^31 - 1 frames is outside the contract.
+ *
+ * The update.  Frame f belongs to stream s and t = that stream's frame_no; its considered detections are j = 0 .. c - 1 in the
+ * detector's (score) order, c = min(max(d_counts[f], 0), per_frame).
+ *   1. expire  every live slot that has been absent for more than max_missed frames, t - last_seen - 1 > max_missed, is freed: a track
+ *              may miss max_missed consecutive frames and still be matched in the next one; after max_missed + 1 it is gone.
+ *   2. match   for each j ascending: the candidates are the live slots neither matched nor opened earlier in this frame; a candidate
+ *              qualifies when iou(track box, detection box) > iou_thr (strict, so the NaN of 0 / 0 fails); the largest iou wins, ties
+ *              go to the smallest track id.  The winner's box becomes the detection's, last_seen = t, hits += 1, d_track[f][j] = id;
+ *              d_embed[f][j] = 1 and last_embed = t when refresh > 0 && t - last_embed >= refresh, else d_embed[f][j] = 0.
+ *   3. open    an unmatched detection takes the LOWEST free slot: id = next_id++, the detection's box, last_seen = last_embed = t,
+ *              hits = 1, d_track[f][j] = id, d_embed[f][j] = 1.  With no free slot the face is untracked: d_track[f][j] = -1,
+ *              d_embed[f][j] = 1 (the reference's behaviour: embed it) and no state changes.
+ *   4. close   entries j >= c of both outputs are written as (-1, 0); frame_no += 1, also for a frame without detections.
+ *   refresh == 0: a track is embedded once, when it opens.  Greedy in score order, as the NMS in front of it.
+ * fh_tracker_reset / fh_tracker_get_state are synchronous (they wait for the device).  get_state writes the live slots, ascending, to
+ *   the front of host_out[max_tracks] (the rest: id = -1) and returns their number; frame_no / next_id may be NULL.
+ * fh_track_select_dev  the flagged twin of the pipeline's face selection: the records with d_embed != 0, densely in (frame, slot)
+ *   order, into d_faces with d_frame_of and d_track_of (= d_track of that entry); d_total[0] = their number; room for n * per_frame.
+ * fh_pipeline_run_tracked_dev  on `stream`: fh_det_detect_batch_dev with max_per_frame = faces_per_frame into d_all / d_counts (bit
+ *   for bit that call's output), the update, the select, the ONE 4-byte hand-off of fh_pipeline_run_dev, then align + embed of exactly
+ *   the selected faces.  d_track = [n][F]; d_faces / d_frame_of / d_track_of / d_emb hold up to n * F entries.  Returns the number of
+ *   faces embedded.  One tracker serves one pipeline at a time (it owns the flag buffer).  The ragged, tiled, two-stream and fh_stream
+ *   forms have no tracked twin yet. */
+#define FH_TRACK_MAX 64                      /* track slots per stream (one wave's lanes) */
+typedef struct fh_tracker fh_tracker;
+typedef struct fh_track_state { int32_t id, x, y, w, h, last_seen, last_embed, hits; } fh_track_state;  /* 32 bytes */
+FH_API fh_tracker* fh_tracker_create(int streams, int max_tracks, float iou_thr, int max_missed, int refresh);
+FH_API void fh_tracker_destroy(fh_tracker* t);
+FH_API int fh_tracker_reset(fh_tracker* t, int stream /* -1: all */);
+FH_API int fh_tracker_get_state(fh_tracker* t, int stream, fh_track_state* host_out /*[max_tracks]*/, int* frame_no, int* next_id);
+FH_API int fh_track_plan(const int* stream_of, int n, int streams, int* order, int* starts /*[streams+1]*/);
+FH_API int fh_track_update_dev(fh_tracker* t, const fh_face* d_det, const int* d_counts, int n, int per_frame,
+                               const int* stream_of /*HOST [n] or NULL*/, int* d_track /*[n][per_frame]*/, int* d_embed /*[n][per_frame]*/,
+                               void* stream);
+FH_API int fh_track_select_dev(const fh_face* d_det, const int* d_embed, int n, int per_frame, fh_face* d_faces, int* d_frame_of,
+                               const int* d_track, int* d_track_of, int* d_total, void* stream);
+FH_API int fh_pipeline_run_tracked_dev(fh_det* d, fh_rec* r, fh_tracker* t, const uint8_t* d_frames, int n, int rows, int cols, int step,
+                                       long long frame_stride, const int* stream_of, float score_thr, float nms_thr, int faces_per_frame,
+                                       fh_face* d_all /*[n][F]*/, int* d_counts /*[n]*/, int* d_track /*[n][F]*/, fh_face* d_faces,
+                                       int* d_frame_of, int* d_track_of, float* d_emb, void* stream);
+
 /* ---- gallery (1:N compareFaces): rows are L2-normalised features; scores are (dot+1)/2. */
 FH_API fh_gallery* fh_gallery_create(int dim);
 FH_API void fh_gallery_destroy(fh_gallery* g);

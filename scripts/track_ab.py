@@ -1,0 +1,181 @@
+"""Interleaved A/B of the tracked pipeline (fh_pipeline_run_tracked_dev) on one MI355X, one process, full-size seeded models (det_500m +
+w600k_r50), 128 frames of 640x640 per step, F = 8 faces per frame, HIP events around every block of steps, the legs alternated round
+by round after a warm-up.
+
+  (a) fh_pipeline_run_dev (unchanged code) on 128 distinct frames: every face embedded.  Against the parent commit's figure for the same
+      call this is the regression check of the untracked path.
+  (b) video: every stream repeats ONE frame, so every track survives.  128 frames as 1 stream x 128 and as 16 streams x 8 ([t][camera]
+      order), each through fh_pipeline_run_dev (every face embedded) and through fh_pipeline_run_tracked_dev with refresh 0 and 8.  The
+      tracker is NOT reset between steps: a step is the next 128 frames of the same cameras (steady state); the faces of the first
+      step, on a fresh tracker, are reported beside it.
+  (c) the update call alone (plan copy + track_update_kernel) on the detector's records of the (a) frames, as 1, 16 and 128 streams,
+      beside fh_det_detect_batch_dev on the same frames in the same run.
+
+Writes --md (default profiles/track_ab.md) and prints one JSON line per case.  Needs a GPU; there is no fallback."""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--frames", type=int, default=128)
+ap.add_argument("--warmup", type=int, default=20)
+ap.add_argument("--steps", type=int, default=100, help="timed steps per leg (at least)")
+ap.add_argument("--rounds", type=int, default=5)
+ap.add_argument("--block", type=int, default=5, help="steps per HIP-event sample")
+ap.add_argument("--cases", nargs="+", default=["a", "b", "c"])
+ap.add_argument("--md", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "track_ab.md"))
+a = ap.parse_args()
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+import facerecognizeonnx_amd as fa  # noqa: E402
+from facerecognizeonnx_amd.synth import models  # noqa: E402
+
+THR, NMS, F, HW = 0.5, 0.4, 8, 640
+IOU_THR, MAX_TRACKS = 0.3, 64
+
+
+def samples(step, steps, block):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    per, faces = [], 0
+    for _ in range((steps + block - 1) // block):
+        e0.record()
+        for _ in range(block):
+            faces = step()
+        e1.record(); e1.synchronize()
+        per.append(e0.elapsed_time(e1) / block)
+    return per, faces
+
+
+def stats(v):
+    q = statistics.quantiles(v, n=10) if len(v) >= 10 else [min(v)] * 9
+    return {"median_ms": round(statistics.median(v), 4), "min_ms": round(min(v), 4), "max_ms": round(max(v), 4),
+            "p10_ms": round(q[0], 4), "p90_ms": round(q[-1], 4), "samples": len(v)}
+
+
+def ab(legs, warmup, steps, rounds, block):
+    """legs: name -> step.  The faces of every leg's FIRST step, a warm-up of every leg, then the legs alternated round by round."""
+    res, faces, first = {k: [] for k in legs}, {}, {}
+    for name, step in legs.items():
+        first[name] = step()
+        samples(step, warmup, block)
+    for _ in range(rounds):
+        for name, step in legs.items():
+            per, faces[name] = samples(step, (steps + rounds - 1) // rounds, block)
+            res[name] += per
+    return {k: stats(v) for k, v in res.items()}, faces, first
+
+
+def main():
+    if not torch.cuda.is_available():
+        raise SystemExit("track_ab.py measures on a GPU; none found")
+    torch.cuda.set_device(0)
+    fa._lib.check(fa.lib().fh_init(0), "fh_init")
+    det, rec = fa.FaceDetector(), fa.FaceRecognizer()
+    if not det.loadModel(models.cached("det_500m_seed100.onnx", models.make_det_500m)) or \
+            not rec.loadModel(models.cached("w600k_r50_seed200.onnx", models.make_w600k_r50)):
+        raise SystemExit("model load failed: " + fa._lib.last_error())
+    B = a.frames
+    stream = torch.cuda.current_stream().cuda_stream
+    i32 = dict(dtype=torch.int32, device="cuda")
+    faces = torch.zeros((B * F, 15), device="cuda"); frame_of = torch.zeros(B * F, **i32); track_of = torch.zeros(B * F, **i32)
+    emb = torch.zeros((B * F, 512), device="cuda")
+    all_ = torch.zeros((B * F, 15), device="cuda"); counts = torch.zeros(B, **i32); track = torch.zeros((B, F), **i32)
+    rng = np.random.default_rng(0)
+    distinct = torch.from_numpy(rng.integers(0, 256, (B, HW, HW, 3), dtype=np.uint8)).cuda()
+    out = {}
+
+    def untracked(data):
+        return lambda: fa.pipeline_run_dev(det, rec, data.data_ptr(), B, HW, HW, F, faces.data_ptr(), frame_of.data_ptr(), emb.data_ptr(),
+                                           THR, NMS, stream)
+
+    def tracked(data, trk, stream_of):
+        return lambda: fa.pipeline_run_tracked_dev(det, rec, trk, data.data_ptr(), B, HW, HW, F, all_.data_ptr(), counts.data_ptr(),
+                                                   track.data_ptr(), faces.data_ptr(), frame_of.data_ptr(), track_of.data_ptr(),
+                                                   emb.data_ptr(), stream_of, THR, NMS, stream)
+
+    if "a" in a.cases:
+        st, fc, _ = ab({"untracked": untracked(distinct)}, a.warmup, a.steps, a.rounds, a.block)
+        out["a"] = {"frames": B, "faces_per_step": fc["untracked"], **st}
+        print(json.dumps({"case": "a", **out["a"]}), flush=True)
+
+    if "b" in a.cases:
+        out["b"] = {}
+        for streams in (1, 16):
+            if B % streams:
+                continue
+            stream_of = np.tile(np.arange(streams, dtype=np.int32), B // streams)                  # [t][camera]
+            data = distinct[torch.from_numpy(stream_of.astype(np.int64)).cuda()].contiguous()      # camera s shows frame s, always
+            trk = {r: fa.Tracker(streams, MAX_TRACKS, IOU_THR, 0, r) for r in (0, 8)}
+            legs = {"untracked": untracked(data), "tracked_refresh0": tracked(data, trk[0], stream_of),
+                    "tracked_refresh8": tracked(data, trk[8], stream_of)}
+            st, fc, first = ab(legs, a.warmup, a.steps, a.rounds, a.block)
+            out["b"][f"{streams}x{B // streams}"] = {"faces_per_step": fc, "faces_first_step": first, **st}
+            del data
+        print(json.dumps({"case": "b", **out["b"]}), flush=True)
+
+    if "c" in a.cases:
+        det.detect_batch_dev(distinct.data_ptr(), B, HW, HW, all_.data_ptr(), F, counts.data_ptr(), THR, NMS, stream=stream)
+        torch.cuda.synchronize()
+        embed = torch.zeros((B, F), **i32)
+        legs, so = {}, {}
+        for streams in (1, 16, B):
+            so[streams] = np.tile(np.arange(streams, dtype=np.int32), B // streams)
+            trk = fa.Tracker(streams, MAX_TRACKS, IOU_THR, 0, 8)
+            legs[f"update_{streams}_streams"] = (lambda t, s: lambda: t.update_dev(all_.data_ptr(), counts.data_ptr(), B, F, track.data_ptr(),
+                                                                                   embed.data_ptr(), stream_of=s, stream=stream))(trk, so[streams])
+        legs["detector"] = lambda: det.detect_batch_dev(distinct.data_ptr(), B, HW, HW, faces.data_ptr(), F, frame_of.data_ptr(), THR, NMS,
+                                                        stream=stream)
+        st, _, _ = ab(legs, a.warmup, a.steps, a.rounds, a.block)
+        out["c"] = {"frames": B, "faces_in_records": int(torch.clamp(counts, 0, F).sum().item()), **st}
+        print(json.dumps({"case": "c", **out["c"]}), flush=True)
+
+    if a.md and out:
+        write_md(out)
+
+
+def fmt(s):
+    return f"{s['median_ms']:.3f} ({s['min_ms']:.3f}-{s['max_ms']:.3f}; p10-p90 {s['p10_ms']:.3f}-{s['p90_ms']:.3f}; {s['samples']} samples)"
+
+
+def write_md(out):
+    L = ["# Tracked pipeline: interleaved A/B", "",
+         f"`scripts/track_ab.py` on one MI355X, one process: det_500m + w600k_r50 (seeded), {a.frames} frames of {HW}x{HW} per step, up to "
+         f"{F} faces per frame, thresholds {THR} / {NMS}, tracker iou_thr {IOU_THR}, max_missed 0, {MAX_TRACKS} slots; {a.warmup} warm-up "
+         f"steps per leg, then the legs alternated for {a.rounds} rounds, >= {a.steps} timed steps per leg, HIP events around blocks of "
+         f"{a.block} steps (ms per step: median, min-max, p10-p90 over the block samples).", ""]
+    if "a" in out:
+        d = out["a"]
+        L += ["## (a) the untracked path, on the parent's terms", "",
+              "| leg | ms per step | faces embedded per step |", "|---|---|---|",
+              f"| `fh_pipeline_run_dev`, {d['frames']} distinct frames | {fmt(d['untracked'])} | {d['faces_per_step']} |", ""]
+    if "b" in out:
+        L += ["## (b) video: every camera shows one frame, the tracker carries on from step to step", "",
+              "| streams x frames | leg | ms per step | faces embedded per step | ... on the first step |", "|---|---|---|---|---|"]
+        names = {"untracked": "`fh_pipeline_run_dev` (every face)", "tracked_refresh0": "`fh_pipeline_run_tracked_dev`, refresh 0",
+                 "tracked_refresh8": "`fh_pipeline_run_tracked_dev`, refresh 8"}
+        for shape, d in out["b"].items():
+            for k, label in names.items():
+                L.append(f"| {shape} | {label} | {fmt(d[k])} | {d['faces_per_step'][k]} | {d['faces_first_step'][k]} |")
+        L += [""]
+    if "c" in out:
+        d = out["c"]
+        det_ms = d["detector"]["median_ms"]
+        L += [f"## (c) the update call alone ({d['frames']} frames, {d['faces_in_records']} faces in the records)", "",
+              "One `fh_track_update_dev` = the copy of the walk plan plus `track_update_kernel` (one wave per stream).", "",
+              "| leg | ms per call | share of the detector's time |", "|---|---|---|"]
+        for k, s in d.items():
+            if k.startswith("update_"):
+                L.append(f"| {k.replace('_', ' ')} | {fmt(s)} | {100 * s['median_ms'] / det_ms:.1f} % |")
+        L += [f"| `fh_det_detect_batch_dev`, same frames, same run | {fmt(d['detector'])} | |", ""]
+    os.makedirs(os.path.dirname(os.path.abspath(a.md)), exist_ok=True)
+    with open(a.md, "w") as f:
+        f.write("\n".join(L))
+
+
+if __name__ == "__main__":
+    main()
