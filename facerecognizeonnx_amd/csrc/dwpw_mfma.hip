@@ -19,8 +19,8 @@
 #include <algorithm>
 #include <cstring>
 #include <stdexcept>
-#include <type_traits>
 
+#include "dwpw_tile.h"
 #include "gemm_tile.h"
 #include "kernels.h"
 #include "plan.h"
@@ -28,8 +28,6 @@
 namespace fh {
 
 typedef const unsigned __attribute__((address_space(1))) dwpw_gmem_u32;
-constexpr int DP_TH = 8, DP_TW = 16, DP_BM = DP_TH * DP_TW;            // 128 output pixels per tile
-constexpr int DP_HW = DP_TW + 2, DP_HALO = (DP_TH + 2) * DP_HW;         // 10 x 18 = 180 halo pixels
 
 // DS = stride of the depthwise part (1 | 2).
 // DIRECT = no halo in LDS: a thread owns 4 channels of a vertical strip of SR output pixels and gathers the
@@ -345,27 +343,6 @@ constexpr int FR_PITCH = 32;                                               // dw
 constexpr int FR_ROWS = 21;                                                // 9*2 + 3
 constexpr int FR_SLOTS = (FR_ROWS * FR_PITCH + 255) / 256;                 // staged dwords per thread (3)
 
-// Wave priority by tile count, for the persistent kernels below.  A SIMD's instruction arbiter prefers its OLDEST wave: with several
-// persistent workgroups per CU and a static share of tiles each, the first-launched workgroup runs at full speed and the last-launched one
-// on what is left (front_kernel's phase stamps: a workgroup's loop took 586 k / 690 k / 811 k / 936 k cycles by launch order on its CU) —
-// the kernel ends with the slowest while the fast ones' slots idle.  s_setprio beats age, so every workgroup takes each level in turn.
-__device__ __forceinline__ void rotate_wave_priority(int it) {
-    switch (it & 3) {                                                      // (s_setprio takes an immediate)
-        case 0: __builtin_amdgcn_s_setprio(0); break;
-        case 1: __builtin_amdgcn_s_setprio(1); break;
-        case 2: __builtin_amdgcn_s_setprio(2); break;
-        default: __builtin_amdgcn_s_setprio(3); break;
-    }
-}
-
-// workgroup barrier that orders LDS traffic only: __syncthreads() also drains vmcnt, which would make every barrier of the tile loop
-// wait for the NEXT tile's window loads
-__device__ __forceinline__ void front_barrier() {
-#if defined(__HIP_DEVICE_COMPILE__)
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-#endif
-}
-
 // STEP4: the frames' row pitch is a multiple of 4 — the misalignment of a staged row is then the same for every row of a tile (one
 // scalar) instead of a per-row value.
 template <bool STEP4>
@@ -400,7 +377,7 @@ __global__ __launch_bounds__(256, 4) void front_kernel(const ConvArgs p, const i
     asm volatile("" ::"v"(wq_hi), "v"(wq_mid), "v"(wq_lo), "v"(sbias));
 #endif
     const bf16x8 w_hi = __builtin_bit_cast(bf16x8, wq_hi), w_mid = __builtin_bit_cast(bf16x8, wq_mid), w_lo = __builtin_bit_cast(bf16x8, wq_lo);
-    const int fr = lane & 31, fh2 = lane >> 5, fsw = (fr >> 1) & 7;
+    const int fh2 = lane >> 5;
 
     // ---- everything about a lane's three stem groups that does not depend on the tile: halo pixel (hy, hx), its slot in the staged
     // image (row rr, byte cb relative to the tile's window origin) and in the halo image
@@ -419,25 +396,17 @@ __global__ __launch_bounds__(256, 4) void front_kernel(const ConvArgs p, const i
     // whole halo does take the plain path; the others patch the conv padding in, see the stem below)
     const int AY0 = 1, AY1 = min(p.H - 1, (p.u8_inH - 2) / S), AX0 = 1, AX1 = min(p.W - 1, (p.u8_inW - 2) / S);
 
-    // ---- tiles of this workgroup: XCD x owns a contiguous run, its workgroups walk it side by side (t, t + wgs, ...); the tile
-    // coordinates move by the same three steps every time: no division in the loop
-    const int xcd = blockIdx.x & 7, wg = blockIdx.x >> 3, wgs = gridDim.x >> 3;      // (gridDim.x is a multiple of 8)
-    const int q8 = tiles_total >> 3, r8 = tiles_total & 7;
-    const int run0 = xcd * q8 + min(xcd, r8), run1 = run0 + q8 + (xcd < r8 ? 1 : 0);
-    const int d_tx = wgs % tiles_x, d_ty = (wgs / tiles_x) % tiles_y, d_n = wgs / (tiles_x * tiles_y);
-    int t = run0 + wg;
-    int n = t / (tiles_x * tiles_y), tyi = (t / tiles_x) % tiles_y, txi = t % tiles_x;      // the tile being PREFETCHED
-    auto advance = [&]() {
-        txi += d_tx; if (txi >= tiles_x) { txi -= tiles_x; ++tyi; }
-        tyi += d_ty; if (tyi >= tiles_y) { tyi -= tiles_y; ++n; }
-        n += d_n;
-    };
+    // ---- tiles of this workgroup (xcd_run); (n, tyi, txi) is the tile being PREFETCHED
+    const XcdRun run = xcd_run(tiles_total);
+    const int run1 = run.run1, wgs = run.wgs;
+    int t = run.run0 + run.wg;
+    TileWalk tw(t, wgs, tiles_x, tiles_y);
 
     unsigned pf[FR_SLOTS];
     const int pr = tid / FR_PITCH, pd4 = (tid % FR_PITCH) * 4;             // this thread's slots: rows pr + 8k, dword pd
     auto prefetch = [&]() __attribute__((always_inline)) {                // the u8 window of tile (n, tyi, txi) -> registers (issued, not waited for)
-        const uint8_t* frame = p.u8_src + (size_t)n * p.u8_img_stride;
-        const int sy0 = (tyi * DP_TH - 1) * S - 1, sx3 = ((txi * DP_TW - 1) * S - 1) * 3;
+        const uint8_t* frame = p.u8_src + (size_t)tw.n * p.u8_img_stride;
+        const int sy0 = (tw.tyi * DP_TH - 1) * S - 1, sx3 = ((tw.txi * DP_TW - 1) * S - 1) * 3;
         const unsigned base_lo = (unsigned)(unsigned long long)frame + (unsigned)(sy0 * step + sx3);     // low bits of the window origin's address
 #pragma unroll
         for (int k = 0; k < FR_SLOTS; ++k) {
@@ -454,27 +423,19 @@ __global__ __launch_bounds__(256, 4) void front_kernel(const ConvArgs p, const i
     };
 
     // the prologue's loads and the weight DMA have landed — the only full memory wait of the kernel: the barriers of the tile loop
-    // order LDS traffic only (front_barrier), so a tile's prefetch stays in flight across them
+    // order LDS traffic only (lds_barrier), so a tile's prefetch stays in flight across them
 #if defined(__HIP_DEVICE_COMPILE__)
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #endif
-    front_barrier();
+    lds_barrier();
     if (t < run1) prefetch();
     int buf = 0;
-#ifdef FACEHIP_DWPW_PROF
-    long long fph[6] = {0, 0, 0, 0, 0, 0}; long long fst0; int fnt = 0;
-    const long long fclk0 = __builtin_readcyclecounter(), frt0 = __builtin_amdgcn_s_memrealtime();   // shader clock vs the constant 100 MHz counter
-#define FRONT_STAMP(i) { const long long now_ = __builtin_readcyclecounter(); fph[i] += now_ - fst0; fst0 = now_; }
-#else
-#define FRONT_STAMP(i)
-#endif
+    DwpwStamps stamps;
     int prio_it = (int)(blockIdx.x >> 8);                                  // (launch order on the CU, as far as the dispatcher deals round-robin)
     for (; t < run1; t += wgs, buf ^= 1) {
         if (!p.no_prio) rotate_wave_priority(prio_it++);                   // (see rotate_wave_priority; no_prio: A / B switch)
-#ifdef FACEHIP_DWPW_PROF
-        fst0 = __builtin_readcyclecounter(); ++fnt;
-#endif
-        const int cn = n, cty0 = tyi * DP_TH, ctx0 = txi * DP_TW;          // this tile (n / tyi / txi move on to the prefetched one)
+        stamps.tile();
+        const int cn = tw.n, cty0 = tw.tyi * DP_TH, ctx0 = tw.txi * DP_TW;   // this tile (tw moves on to the prefetched one)
         const uint8_t* frame = p.u8_src + (size_t)cn * p.u8_img_stride;
         const int sy0 = (cty0 - 1) * S - 1, sx0 = (ctx0 - 1) * S - 1;
         const unsigned base_lo = (unsigned)(unsigned long long)frame + (unsigned)(sy0 * step + sx0 * 3);
@@ -495,12 +456,12 @@ __global__ __launch_bounds__(256, 4) void front_kernel(const ConvArgs p, const i
             }
             if (tid + 256 * k < FR_ROWS * FR_PITCH) stage[buf][tid + 256 * k] = v;
         }
-        FRONT_STAMP(0)
-        advance();
+        DWPW_STAMP(0)
+        tw.advance();
         if (t + wgs < run1) prefetch();
-        FRONT_STAMP(1)
-        front_barrier();
-        FRONT_STAMP(2)
+        DWPW_STAMP(1)
+        lds_barrier();
+        DWPW_STAMP(2)
         // 2. stem, every pixel from the staged image — no global access in this loop, so nothing here waits on the prefetch (a global load
         // anywhere in it would make the compiler drain vmcnt at its join: the NEXT tile's window, in every group).  Tiles that touch the
         // border of the map (wave-uniform test) patch the convolution's zero padding in: a byte OUTSIDE the net input counts as 127.5 —
@@ -586,81 +547,25 @@ __global__ __launch_bounds__(256, 4) void front_kernel(const ConvArgs p, const i
             }
             stem_finish(f, inmap, hp >= 0, hp);
         }
-        FRONT_STAMP(3)
-        front_barrier();
-        // 3 + 4 merged (round 3, as dwpw_reg_kernel): a wave owns 32 pixels, lane = (pixel fr, half fh2); the depthwise 3x3 of channels
+        DWPW_STAMP(3)
+        lds_barrier();
+        // 3 + 4 merged (as dwpw_reg_kernel, dwpw_tile.h): a wave owns 32 pixels, lane = (pixel fr, half fh2); the depthwise 3x3 of channels
         // 8 j + 4 fh2 .. + 3 of ITS pixel is the B fragment of the pointwise MFMAs — no A tile, no barrier between the two, and the
-        // 16 KB the A tile took are gone from LDS.  Accumulators start from the pointwise bias.  One MFMA per slot, the next
-        // step's tap reads RA tap-slots ahead (ring registers), pinned by sched_barrier.
+        // 16 KB the A tile took are gone from LDS.  Accumulators start from the pointwise bias (cst[40..47]); taps [tap][4] at cst, bias at
+        // tap 9.  (RA, RING = 2, 3: a deeper ring spills — the kernel lives within 128 VGPRs for 4 workgroups per CU.)
         {
-            const int pr_ = wid * 32 + fr, py = pr_ / DP_TW, pxx = (py & 1) ? (pr_ - py * DP_TW - 2) & (DP_TW - 1) : pr_ - py * DP_TW;   // (rotation: see dwpw_reg_kernel)
-            const v4f* const hb = halo + (py * DP_HW + pxx) * 5 + fh2;
-            const v4f* const db = cst + fh2;                                // [tap][4] + 2 j ; bias at tap 9
-            v16f acc;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const v4f pb = cst[40 + fh2 + 2 * q];
-#pragma unroll
-                for (int c = 0; c < 4; ++c) acc[4 * q + c] = pb[c];
-            }
-            constexpr int NT = 10, RA = 2, RING = 3, STEPS = 2;            // (a deeper ring spills: the kernel lives within 128 VGPRs for 4 workgroups per CU)
-            v4f hv[RING], dv[RING];
-            auto issue = [&](int G) __attribute__((always_inline)) {
-                const int jj = G / NT, tt = G % NT;
-                if (jj >= STEPS) return;
-                dv[G % RING] = db[(tt == 0 ? 9 : tt - 1) * 4 + 2 * jj];
-                if (tt > 0) hv[G % RING] = hb[(((tt - 1) / 3) * DP_HW + (tt - 1) % 3) * 5 + 2 * jj];
-            };
-            v4f an;
-            auto consume = [&](int G) __attribute__((always_inline)) {
-                if (G / NT >= STEPS) return;
-                if (G % NT == 0) an = dv[G % RING]; else an += hv[G % RING] * dv[G % RING];
-            };
+            const DwpwLane ln = dwpw_lane<1, 5>(halo, cst, wid, lane);
+            const int wrow[1] = {(lane & 31) * 8};                         // the lane's row of the swizzled Wt image
+            v16f acc[1];
+            dwpw_acc_from_bias<1>(acc, reinterpret_cast<const float*>(cst + 40), fh2);
             const float dfl = p.dw_act == (int)Act::RELU ? 0.f : -INFINITY, ofl = p.act == (int)Act::RELU ? 0.f : -INFINITY;
-            const v4f* Wp = Wt + fr * 8;
-#pragma unroll
-            for (int G = 0; G < RA; ++G) issue(G);
-#pragma unroll
-            for (int G = 0; G < NT; ++G) { issue(G + RA); consume(G); }
-#pragma unroll
-            for (int j = 0; j < STEPS; ++j) {
-                v4f a;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) a[e] = fmaxf(an[e], dfl);
-                const v4f w = Wp[(2 * j + fh2) ^ fsw];
-#pragma unroll
-                for (int sl = 0; sl < 4; ++sl) {
-                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(w[sl], a[sl], acc, 0, 0, 0);
-#pragma unroll
-                    for (int G = NT * (j + 1) + sl * NT / 4; G < NT * (j + 1) + (sl + 1) * NT / 4; ++G) { issue(G + RA); consume(G); }
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            }
-            FRONT_STAMP(4)
-            const int oy = cty0 + py, ox = ctx0 + pxx;
-            if (oy < p.Ho && ox < p.Wo) {
-                float* __restrict__ orow = p.out1 + (((size_t)cn * p.Ho + oy) * p.Wo + ox) * p.Cout;
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const int co = 4 * fh2 + 8 * q;
-                    if (co >= p.Cout) continue;
-                    v4f v;
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) v[c] = fmaxf(acc[4 * q + c], ofl);
-                    *reinterpret_cast<v4f*>(orow + co) = v;
-                }
-            }
-            FRONT_STAMP(5)
+            dwpw_k_steps<0, 2, 1, 2, 3, 1, 5, 4, true>(acc, ln.hbase, ln.dbase, dfl, Wt, 0, wrow);
+            DWPW_STAMP(4)
+            dwpw_store<1>(acc, p, cn, cty0 + ln.py, ctx0 + ln.px, fh2, ofl);
+            DWPW_STAMP(5)
         }
     }
-#ifdef FACEHIP_DWPW_PROF
-    if (lane == 0 && p.slabs) {
-        long long* o = reinterpret_cast<long long*>(p.slabs) + ((size_t)blockIdx.x * 4 + wid) * 8;
-        for (int i = 0; i < 6; ++i) o[i] = fph[i];
-        o[6] = fnt;
-        o[7] = (__builtin_readcyclecounter() - fclk0) * 1000 / ((long long)__builtin_amdgcn_s_memrealtime() - frt0 + 1);   // shader cycles per 100 MHz tick x 1000 = MHz x 10
-    }
-#endif
+    stamps.write(p.slabs, wid, lane);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
@@ -670,20 +575,15 @@ __global__ __launch_bounds__(256, 4) void front_kernel(const ConvArgs p, const i
 // depthwise 8.9 k, prologue 9.5 k cycles per tile): per 32-channel chunk every wave waits at two barriers, the depthwise result makes a
 // round trip through LDS, a chunk with few live channels (40 = 32 + 8) idles three quarters of the depthwise lanes, and every tile pays
 // the prologue again.  Here:
-//   * a wave owns 32 pixels of the 8 x 16 tile for the WHOLE K loop: lane = (pixel r = lane & 31, half h = lane >> 5).  For the 8-channel
-//     step j it evaluates the depthwise 3x3 (+bias +ReLU) of channels 8j + 4h .. + 3 of ITS pixel straight from the halo image — a
-//     float4 that is exactly the B fragment v_mfma_f32_32x32x2_f32 wants from that lane (k = 8j + e for h = 0, 8j + 4 + e for h = 1,
-//     e = 0..3): the result goes from the vector ALU into the matrix core without touching LDS.  Waves never wait for each other
-//     inside a tile, so one wave's depthwise FMAs / LDS reads overlap another's MFMAs on the same SIMD.
-//   * the halo holds ALL channels of the tile at once ([180 pixels][C + 4 floats]: pitch 4 * odd, so the 16-byte reads of
-//     neighbouring pixels spread over all banks), the pointwise weights sit in LDS in fragment order for the kernel's lifetime,
-//     depthwise taps + biases too.
-//   * persistent workgroups; the NEXT tile's halo is fetched global -> registers while this tile computes (front_kernel's scheme: no
-//     second halo buffer, so the occupancy stays), written to LDS between two LDS-only barriers.
-//   * the halo comes in through BUFFER loads with a per-image descriptor: rows above / below the image are out of range and read as
-//     zero in hardware, columns left / right of it are pushed out of range by one select (edge tiles only) — no per-item bounds
-//     arithmetic, no branches, and the loads of a tile issue back to back.
+//   * a wave owns 32 pixels of the 8 x 16 tile for the WHOLE K loop and feeds its depthwise results straight into the MFMAs as B fragments
+//     (dwpw_k_steps); waves never wait for each other inside a tile;
+//   * the halo holds ALL channels of the tile at once, the pointwise weights (in fragment order), depthwise taps and biases sit in LDS
+//     for the kernel's lifetime (dwpw_fill_constants);
+//   * persistent workgroups (xcd_run); the NEXT tile's halo is fetched global -> registers through buffer loads while this tile computes
+//     and parked in LDS between two LDS-only barriers (DwpwHaloPart);
 //   * accumulators start from the pointwise bias; the epilogue is ReLU + float4 stores.
+// The pieces and their design notes are in dwpw_tile.h; this kernel is their plain sequence, dwpw_reg2_kernel and front_kernel's tail are
+// the other two users.
 // Phase stamps (scripts/dwpw_prof.sh, 80x80x72 -> 72, cycles per tile and workgroup): barriers 1.4 k, registers -> LDS 0.8 k, prefetch
 // issue 1.8 k, K loop 14.7 k (= two waves per SIMD sharing the matrix pipe at 6.9 k of MFMA issue each: the loop is MFMA-bound; a
 // third of those MFMAs multiply the padding 72 -> 96 columns), stores 2.4 k.
@@ -694,208 +594,61 @@ __global__ __launch_bounds__(256, 4) void front_kernel(const ConvArgs p, const i
 template <int CQ, int TN, int OCC, int DS>
 __global__ __launch_bounds__(256, OCC) void dwpw_reg_kernel(const ConvArgs p, const int tiles_x, const int tiles_y, const int tiles_total) {
     static_assert(CQ % 2 == 0, "whole 8-channel MFMA steps");
-    constexpr int C = CQ * 4, STEPS = C / 8;
+    constexpr int STEPS = CQ / 2;
     constexpr int PQ = CQ + 1;                                             // halo pixel pitch in float4 (odd)
-    // halo of an 8 x 16 output tile under a depthwise stride DS: rows 2 oy - 1 .. 2 oy + 1 -> (8 - 1) DS + 3 rows, same for the columns
-    constexpr int HH = (DP_TH - 1) * DS + 3, HWD = (DP_TW - 1) * DS + 3, HALO = HH * HWD;   // 10 x 18 = 180 (DS = 1), 17 x 33 = 561 (DS = 2)
-    constexpr int NPF = (HALO * CQ + 255) / 256;                           // prefetched float4 per thread
-    // LDS slot of halo pixel hp = hy * HWD + hx.  Stride 1: hp itself.  Stride 2 (round 5): a row's EVEN columns first, then its odd ones —
-    // lane = output pixel reads input column 2 px + kx, i.e. slot px + (kx >> 1) of plane kx & 1: neighbouring lanes are ONE pixel pitch
-    // (odd in float4) apart.  With interleaved columns they were two apart: every halo index of an instruction had the same parity, 8 bank
-    // quads for the 16 lanes of a ds_read_b128 group, a 2-way conflict on every tap (SQ_LDS_BANK_CONFLICT 0.34 of the LDS cycles, round 4).
-    constexpr int HW2 = (HWD + 1) / 2;
-    auto slot = [](int hp) { if (DS == 1) return hp; const int hy = hp / HWD, hx = hp - hy * HWD; return hy * HWD + (hx & 1) * HW2 + (hx >> 1); };
-    auto tapoff = [](int ky, int kx) { return DS == 1 ? ky * HWD + kx : ky * HWD + (kx & 1) * HW2 + (kx >> 1); };
     extern __shared__ v4f smem[];
+    const int Cout = p.Cout;
     v4f* const halo = smem;                                                // [HALO][PQ]
-    v4f* const dwl = halo + HALO * PQ;                                  // [10][CQ]: 9 taps + bias
-    v4f* const Wl = dwl + 10 * CQ;                                         // [STEPS][2][Cout]: A fragments (n = row, 4 k of half h)
-    float* const pwb = reinterpret_cast<float*>(Wl + STEPS * 2 * p.Cout);  // [32 * TN] pointwise bias (zero behind Cout)
+    v4f* const dwl = halo + DwpwHalo<DS>::HALO * PQ;                       // [10][CQ]
+    v4f* const Wl = dwl + 10 * CQ;                                         // [STEPS][2][Cout]
+    float* const pwb = reinterpret_cast<float*>(Wl + STEPS * 2 * Cout);    // [32 * TN]
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int r = lane & 31, h = lane >> 5;
-    const int Cout = p.Cout;
-    // ReLU (floor 0) or none (floor -inf) as one v_max: a branch per step would end the basic block and with it the overlap of the steps
+    const int h = lane >> 5;
     const float dw_floor = p.dw_act == (int)Act::RELU ? 0.f : -INFINITY, out_floor = p.act == (int)Act::RELU ? 0.f : -INFINITY;
 
     // ---- once per workgroup
-    for (int i = tid; i < 10 * CQ; i += 256) {
-        const int k = i / CQ, q = i - k * CQ;
-        dwl[i] = *reinterpret_cast<const v4f*>(k < 9 ? p.dw_w + (size_t)k * C + 4 * q : p.dw_b + 4 * q);
-    }
-    for (int i = tid; i < STEPS * 2 * Cout; i += 256) {
-        const int n = i % Cout, jh = i / Cout;                             // jh = 2 j + h
-        Wl[i] = *reinterpret_cast<const v4f*>(p.wt + (size_t)n * p.Kpad + 4 * jh);
-    }
-    for (int i = tid; i < 32 * TN; i += 256) pwb[i] = i < Cout ? p.bias[i] : 0.f;
-
-    // this lane's pixel and fragment addresses (float4 units)
-    // (stride 1: the wave's second pixel row takes its columns rotated by 2.  A ds_read_b128 serves lanes {0-3, 12-15, 20-27} and
-    //  {4-11, 16-19, 28-31} together; with an odd pixel pitch the 16 addresses fall into 16 different bank quads iff the pixels' linear halo
-    //  indices differ mod 16, and a halo row is 18 = 16 + 2 pixels: unrotated, lanes 12 / 13 collide with lanes 26 / 27 and lanes 4 / 5 with
-    //  lanes 18 / 19 — every fragment read took 8 LDS cycles instead of 4 (SQ_LDS_BANK_CONFLICT = 27-34 % of SQ_LDS_IDX_ACTIVE, round-4 counters))
-    //  (stride 2 with its column planes: consecutive slots again and a row pitch of 2 * 33 = 66 = 64 + 2 slots — the same rotation)
-    const int pix = wid * 32 + r, py = pix / DP_TW, px = (py & 1) ? (pix - py * DP_TW - 2) & (DP_TW - 1) : pix - py * DP_TW;
-    const v4f* const hbase = halo + (py * DS * HWD + px) * PQ + h;            // + tapoff(ky, kx) * PQ + 2 j   (stride 2: px indexes a column plane)
-    const v4f* const dbase = dwl + h;                                      // + tap * CQ + 2 j
+    dwpw_fill_constants<CQ, TN>(dwl, Wl, pwb, p, tid);
+    const DwpwLane ln = dwpw_lane<DS, PQ>(halo, dwl, wid, lane);
     int wrow[TN];
-#pragma unroll
-    for (int jn = 0; jn < TN; ++jn) wrow[jn] = h * Cout + min(32 * jn + r, Cout - 1);   // rows >= Cout: any valid address (their columns are never stored)
+    dwpw_wrows<TN>(wrow, Cout, lane);
 
     // ---- tiles: XCD x owns a contiguous run, its workgroups walk it side by side
-    const int xcd = blockIdx.x & 7, wg = blockIdx.x >> 3, wgs = gridDim.x >> 3;       // (gridDim.x is a multiple of 8)
-    const int q8 = tiles_total >> 3, r8 = tiles_total & 7;
-    const int run0 = xcd * q8 + min(xcd, r8), run1 = run0 + q8 + (xcd < r8 ? 1 : 0);
+    const XcdRun run = xcd_run(tiles_total);
+    const int run1 = run.run1, wgs = run.wgs;
     const int per_img = tiles_x * tiles_y;
-
-    // halo of tile t: global -> registers (issued, not waited for).  Per thread and item the byte offset relative to the tile's halo
-    // origin is tile-invariant (voff); per tile: one add each, and on tiles that touch the left / right border a select.
-    v4f pf[NPF];
-    int voff[NPF];
-#pragma unroll
-    for (int k = 0; k < NPF; ++k) {
-        const int i = min(tid + 256 * k, HALO * CQ - 1);
-        const int hp = i / CQ, q = i - hp * CQ;
-        const int hy = hp / HWD, hx = hp - hy * HWD;
-        voff[k] = ((hy * p.W + hx) * C + 4 * q) * 4;
-    }
-    const int img_bytes = p.H * p.W * C * 4;
-    auto prefetch = [&](int t) __attribute__((always_inline)) {
-        const int n = t / per_img, rem = t - n * per_img;
-        const int tyi = rem / tiles_x, txi = rem - tyi * tiles_x;
-        const int y0 = tyi * DP_TH * DS - 1, x0 = txi * DP_TW * DS - 1;
-        const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.in + (size_t)n * p.H * p.W * C), 0, img_bytes, 0x00020000);
-        const int tile_off = (y0 * p.W + x0) * C * 4;                       // (negative on the first tile row / column: wraps out of range)
-        int vo[NPF];
-#pragma unroll
-        for (int k = 0; k < NPF; ++k) vo[k] = tile_off + voff[k];
-        if (x0 < 0 || x0 + HWD > p.W) {                                   // wave-uniform: only the first / last tile column
-#pragma unroll
-            for (int k = 0; k < NPF; ++k) {
-                const int i = min(tid + 256 * k, HALO * CQ - 1);
-                const int hx = (i / CQ) % HWD;
-                vo[k] = (unsigned)(x0 + hx) < (unsigned)p.W ? vo[k] : (int)0x80000000;
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < NPF; ++k) pf[k] = __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(rsrc, vo[k], 0, 0));
-    };
-    int t = run0 + wg;
-    if (t < run1) prefetch(t);
-    front_barrier();                                                        // dwl / Wl / pwb written by all waves
-#ifdef FACEHIP_DWPW_PROF
-    long long ph[6] = {0, 0, 0, 0, 0, 0}; long long st0; int ntiles = 0;
-    const long long clk0 = __builtin_readcyclecounter(), rt0 = __builtin_amdgcn_s_memrealtime();
-#define DWPW_STAMP(i) { const long long now_ = __builtin_readcyclecounter(); ph[i] += now_ - st0; st0 = now_; }
-#else
-#define DWPW_STAMP(i)
-#endif
-    int prio_it = (int)(blockIdx.x >> 8);
+    const int img_bytes = p.H * p.W * CQ * 16;
+    DwpwHaloPart<DS, CQ, CQ, 0> hp;
+    hp.init(p, tid);
+    int t = run.run0 + run.wg;
+    if (t < run1) hp.prefetch(p, img_bytes, t, per_img, tiles_x, tid);
+    lds_barrier();                                                          // dwl / Wl / pwb written by all waves
+    DwpwStamps stamps;
+    int prio_it = (int)(blockIdx.x >> 8);                                  // (launch order on the CU, as far as the dispatcher deals round-robin)
     for (; t < run1; t += wgs) {
-        if (!p.no_prio) rotate_wave_priority(prio_it++);                   // (oldest-first arbitration vs static tile shares: see rotate_wave_priority)
+        if (!p.no_prio) rotate_wave_priority(prio_it++);                   // (oldest-first arbitration vs static tile shares; no_prio: A / B switch)
         const int n = t / per_img, rem = t - n * per_img;
         const int tyi = rem / tiles_x, txi = rem - tyi * tiles_x;
         const int ty0 = tyi * DP_TH, tx0 = txi * DP_TW;
-#ifdef FACEHIP_DWPW_PROF
-        st0 = __builtin_readcyclecounter(); ++ntiles;
-#endif
-        front_barrier();                                                    // every wave is done reading the previous tile's halo
+        stamps.tile();
+        lds_barrier();                                                      // every wave is done reading the previous tile's halo
         DWPW_STAMP(0)
-#pragma unroll
-        for (int k = 0; k < NPF; ++k) {
-            const int i = tid + 256 * k;
-            if (i < HALO * CQ) { const int hp = i / CQ; halo[slot(hp) * PQ + (i - hp * CQ)] = pf[k]; }   // pixel pitch PQ = CQ + 1
-        }
+        hp.template park<PQ>(halo, tid);
         DWPW_STAMP(1)
-        if (t + wgs < run1) prefetch(t + wgs);
+        if (t + wgs < run1) hp.prefetch(p, img_bytes, t + wgs, per_img, tiles_x, tid);
         DWPW_STAMP(2)
-        front_barrier();                                                    // halo complete
+        lds_barrier();                                                      // halo complete
         DWPW_STAMP(3)
 
         v16f acc[TN];
-#pragma unroll
-        for (int jn = 0; jn < TN; ++jn)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const v4f b = *reinterpret_cast<const v4f*>(pwb + 32 * jn + 8 * g + 4 * h);
-#pragma unroll
-                for (int c = 0; c < 4; ++c) acc[jn][4 * g + c] = b[c];
-            }
-        // ---- K loop, hand-scheduled.  Left to itself the compiler emits, per step, nine times (2 ds_read, wait, 2 FMA) and only then the
-        // step's MFMAs (ds_read, wait, 4 MFMA): every LDS latency exposed, nothing beside the matrix pipe.  So the order is written
-        // out: one MFMA per SLOT; behind it the slot's share of the NEXT step's depthwise — each tap's two LDS reads are issued RA
-        // tap-slots ahead of their FMAs (ring registers hv / dv), the next 32-column group's weight fragment four slots ahead — and a
-        // sched_barrier(0) pins the slot.  The counted lgkmcnt waits the compiler inserts are then exact (LDS returns in order).
-        constexpr int NS = 4 * TN;                                          // MFMA slots per 8-channel step
-        constexpr int NT = 10;                                              // tap-slots per step: the depthwise bias, then the 9 taps
-        constexpr int RA = 4, RING = 5;
-        v4f hv[RING], dv[RING], wq[2];
-        auto issue = [&](int G) __attribute__((always_inline)) {           // LDS reads of global tap-slot G = NT * step + t
-            const int jj = G / NT, tt = G % NT;
-            if (jj >= STEPS) return;
-            dv[G % RING] = dbase[(tt == 0 ? 9 : tt - 1) * CQ + 2 * jj];
-            if (tt > 0) hv[G % RING] = hbase[tapoff((tt - 1) / 3, (tt - 1) % 3) * PQ + 2 * jj];
-        };
-        v4f an;
-        auto consume = [&](int G) __attribute__((always_inline)) {
-            if (G / NT >= STEPS) return;
-            if (G % NT == 0) an = dv[G % RING]; else an += hv[G % RING] * dv[G % RING];
-        };
-        auto wfrag = [&](int grp) __attribute__((always_inline)) {         // A fragment of (step grp / TN, column group grp % TN)
-            if (grp < STEPS * TN) wq[grp & 1] = Wl[2 * (grp / TN) * Cout + wrow[grp % TN]];
-        };
-        wfrag(0);
-#pragma unroll
-        for (int G = 0; G < RA; ++G) issue(G);
-#pragma unroll
-        for (int G = 0; G < NT; ++G) { issue(G + RA); consume(G); }         // step 0's depthwise: nothing to hide behind yet
-        v4f a;
-#pragma unroll
-        for (int j = 0; j < STEPS; ++j) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) a[e] = fmaxf(an[e], dw_floor);
-#pragma unroll
-            for (int sl = 0; sl < NS; ++sl) {
-                const int grp = j * TN + sl / 4;
-                if (sl % 4 == 0) wfrag(grp + 1);
-                acc[sl / 4] = __builtin_amdgcn_mfma_f32_32x32x2f32(wq[grp & 1][sl % 4], a[sl % 4], acc[sl / 4], 0, 0, 0);
-#pragma unroll
-                for (int G = NT * (j + 1) + sl * NT / NS; G < NT * (j + 1) + (sl + 1) * NT / NS; ++G) { issue(G + RA); consume(G); }
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        }
+        dwpw_acc_from_bias<TN>(acc, pwb, h);
+        dwpw_k_steps<0, STEPS, TN, 4, 5, DS, PQ, CQ, false>(acc, ln.hbase, ln.dbase, dw_floor, Wl, Cout, wrow);
         DWPW_STAMP(4)
-        // ---- epilogue: lane = pixel, accumulator quads = 4 consecutive channels.
-        // (Stride-2 form, 320x320x16 -> 160x160x40: the phase stamps show stores 6.3 k + next prefetch's issue 4.1 k of 16.4 k cycles per
-        // tile — queueing behind the memory pipeline.  Parking the wave's pixels in the halo rows it owns exclusively (4 wid + 1 .. + 3) and
-        // writing them back as whole lines changed nothing (296 vs 301 us, stores still 5.9 k): it is the 4.6 TB/s of mixed read / write
-        // traffic itself, not the 16-byte pieces, that the block waits for.)
-        const int oy = ty0 + py, ox = tx0 + px;
-        if (oy < p.Ho && ox < p.Wo) {
-            float* __restrict__ orow = p.out1 + (((size_t)n * p.Ho + oy) * p.Wo + ox) * Cout;
-#pragma unroll
-            for (int jn = 0; jn < TN; ++jn)
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    const int co = 32 * jn + 8 * g + 4 * h;
-                    if (co >= Cout) continue;
-                    v4f v;
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) v[c] = fmaxf(acc[jn][4 * g + c], out_floor);
-                    *reinterpret_cast<v4f*>(orow + co) = v;
-                }
-        }
+        dwpw_store<TN>(acc, p, n, ty0 + ln.py, tx0 + ln.px, h, out_floor);
         DWPW_STAMP(5)
     }
-#ifdef FACEHIP_DWPW_PROF
-    if (lane == 0 && p.slabs) {                                             // [workgroup][wave][8]: 6 phase sums, tile count
-        long long* o = reinterpret_cast<long long*>(p.slabs) + ((size_t)blockIdx.x * 4 + wid) * 8;
-        for (int i = 0; i < 6; ++i) o[i] = ph[i];
-        o[6] = ntiles;
-        o[7] = (__builtin_readcyclecounter() - clk0) * 1000 / ((long long)__builtin_amdgcn_s_memrealtime() - rt0 + 1);
-    }
-#endif
+    stamps.write(p.slabs, wid, lane);
 }
 
 // ---- stride-2 block with more channels than one halo image can hold (SCRFD: 160x160x40 -> 80x80x72).  A 17 x 33 halo of all 40 channels is
@@ -907,87 +660,37 @@ __global__ __launch_bounds__(256, OCC) void dwpw_reg_kernel(const ConvArgs p, co
 template <int CQA, int CQB, int TN, int OCC>
 __global__ __launch_bounds__(256, OCC) void dwpw_reg2_kernel(const ConvArgs p, const int tiles_x, const int tiles_y, const int tiles_total) {
     static_assert(CQA % 2 == 0 && CQB % 2 == 0 && CQB <= CQA, "whole 8-channel MFMA steps per part; part B fits part A's buffer");
-    constexpr int DS = 2, CQ = CQA + CQB, C = CQ * 4, STEPS = C / 8, SA = CQA / 2;
+    constexpr int DS = 2, CQ = CQA + CQB, STEPS = CQ / 2, SA = CQA / 2;
     constexpr int PQ = CQA + 1;                                            // halo pixel pitch in float4 (odd)
-    constexpr int HH = (DP_TH - 1) * DS + 3, HWD = (DP_TW - 1) * DS + 3, HALO = HH * HWD;   // 17 x 33 = 561
-    constexpr int NPA = (HALO * CQA + 255) / 256, NPB = (HALO * CQB + 255) / 256;
-    constexpr int HW2 = (HWD + 1) / 2;                                     // column planes of the stride-2 halo: see dwpw_reg_kernel
-    auto slot = [](int hp) { const int hy = hp / HWD, hx = hp - hy * HWD; return hy * HWD + (hx & 1) * HW2 + (hx >> 1); };
-    auto tapoff = [](int ky, int kx) { return ky * HWD + (kx & 1) * HW2 + (kx >> 1); };
+    constexpr int RA = 3, RING = 4;                                        // (a ring of 5 spills 34 registers beside the two prefetch sets; this one still spills 18)
     extern __shared__ v4f smem[];
+    const int Cout = p.Cout;
     v4f* const halo = smem;                                                // [HALO][PQ]
-    v4f* const dwl = halo + HALO * PQ;                                     // [10][CQ]: 9 taps + bias
+    v4f* const dwl = halo + DwpwHalo<DS>::HALO * PQ;                       // [10][CQ]
     v4f* const Wl = dwl + 10 * CQ;                                         // [STEPS][2][Cout]
-    float* const pwb = reinterpret_cast<float*>(Wl + STEPS * 2 * p.Cout);  // [32 * TN]
+    float* const pwb = reinterpret_cast<float*>(Wl + STEPS * 2 * Cout);    // [32 * TN]
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int r = lane & 31, h = lane >> 5;
-    const int Cout = p.Cout;
+    const int h = lane >> 5;
     const float dw_floor = p.dw_act == (int)Act::RELU ? 0.f : -INFINITY, out_floor = p.act == (int)Act::RELU ? 0.f : -INFINITY;
 
-    for (int i = tid; i < 10 * CQ; i += 256) {
-        const int k = i / CQ, q = i - k * CQ;
-        dwl[i] = *reinterpret_cast<const v4f*>(k < 9 ? p.dw_w + (size_t)k * C + 4 * q : p.dw_b + 4 * q);
-    }
-    for (int i = tid; i < STEPS * 2 * Cout; i += 256) {
-        const int n = i % Cout, jh = i / Cout;
-        Wl[i] = *reinterpret_cast<const v4f*>(p.wt + (size_t)n * p.Kpad + 4 * jh);
-    }
-    for (int i = tid; i < 32 * TN; i += 256) pwb[i] = i < Cout ? p.bias[i] : 0.f;
-
-    const int pix = wid * 32 + r, py = pix / DP_TW, px = (py & 1) ? (pix - py * DP_TW - 2) & (DP_TW - 1) : pix - py * DP_TW;   // (rotation: see dwpw_reg_kernel)
-    const v4f* const hbase = halo + (py * DS * HWD + px) * PQ + h;         // + tapoff(ky, kx) * PQ + 2 (j - first step of the part)
-    const v4f* const dbase = dwl + h;
+    dwpw_fill_constants<CQ, TN>(dwl, Wl, pwb, p, tid);
+    const DwpwLane ln = dwpw_lane<DS, PQ>(halo, dwl, wid, lane);
     int wrow[TN];
-#pragma unroll
-    for (int jn = 0; jn < TN; ++jn) wrow[jn] = h * Cout + min(32 * jn + r, Cout - 1);
+    dwpw_wrows<TN>(wrow, Cout, lane);
 
-    const int xcd = blockIdx.x & 7, wg = blockIdx.x >> 3, wgs = gridDim.x >> 3;
-    const int q8 = tiles_total >> 3, r8 = tiles_total & 7;
-    const int run0 = xcd * q8 + min(xcd, r8), run1 = run0 + q8 + (xcd < r8 ? 1 : 0);
+    const XcdRun run = xcd_run(tiles_total);
+    const int run1 = run.run1, wgs = run.wgs;
     const int per_img = tiles_x * tiles_y;
-
-    v4f pfa[NPA], pfb[NPB];
-    int voa[NPA], vob[NPB];
-#pragma unroll
-    for (int k = 0; k < NPA; ++k) {
-        const int i = min(tid + 256 * k, HALO * CQA - 1);
-        const int hp = i / CQA, q = i - hp * CQA;
-        const int hy = hp / HWD, hx = hp - hy * HWD;
-        voa[k] = ((hy * p.W + hx) * C + 4 * q) * 4;
-    }
-#pragma unroll
-    for (int k = 0; k < NPB; ++k) {
-        const int i = min(tid + 256 * k, HALO * CQB - 1);
-        const int hp = i / CQB, q = i - hp * CQB;
-        const int hy = hp / HWD, hx = hp - hy * HWD;
-        vob[k] = ((hy * p.W + hx) * C + 4 * (CQA + q)) * 4;
-    }
-    const int img_bytes = p.H * p.W * C * 4;
-    // (one part of tile t's halo: global -> registers, issued and not waited for; rows outside the image are out of the descriptor's range and
-    //  read as zero, columns left / right of it are pushed out of range on the first / last tile column)
-#define DWPW2_PREFETCH(PF, VO, NP, CQP, T)                                                                                                  \
-    {                                                                                                                                       \
-        const int n_ = (T) / per_img, rem_ = (T) - n_ * per_img;                                                                            \
-        const int tyi_ = rem_ / tiles_x, txi_ = rem_ - tyi_ * tiles_x;                                                                      \
-        const int y0_ = tyi_ * DP_TH * DS - 1, x0_ = txi_ * DP_TW * DS - 1;                                                                 \
-        const __amdgpu_buffer_rsrc_t rsrc_ = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.in + (size_t)n_ * p.H * p.W * C), 0, img_bytes, 0x00020000); \
-        const int tile_off_ = (y0_ * p.W + x0_) * C * 4;                                                                                    \
-        int vo_[NP];                                                                                                                        \
-        _Pragma("unroll") for (int k = 0; k < NP; ++k) vo_[k] = tile_off_ + VO[k];                                                          \
-        if (x0_ < 0 || x0_ + HWD > p.W) {                                                                                                   \
-            _Pragma("unroll") for (int k = 0; k < NP; ++k) {                                                                                \
-                const int i = min(tid + 256 * k, HALO * CQP - 1);                                                                           \
-                const int hx = (i / CQP) % HWD;                                                                                             \
-                vo_[k] = (unsigned)(x0_ + hx) < (unsigned)p.W ? vo_[k] : (int)0x80000000;                                                   \
-            }                                                                                                                               \
-        }                                                                                                                                   \
-        _Pragma("unroll") for (int k = 0; k < NP; ++k) PF[k] = __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(rsrc_, vo_[k], 0, 0)); \
-    }
-    int t = run0 + wg;
-    if (t < run1) { DWPW2_PREFETCH(pfa, voa, NPA, CQA, t) DWPW2_PREFETCH(pfb, vob, NPB, CQB, t) }
-    front_barrier();
+    const int img_bytes = p.H * p.W * CQ * 16;
+    DwpwHaloPart<DS, CQ, CQA, 0> ha;
+    DwpwHaloPart<DS, CQ, CQB, CQA> hb;
+    ha.init(p, tid);
+    hb.init(p, tid);
+    int t = run.run0 + run.wg;
+    if (t < run1) { ha.prefetch(p, img_bytes, t, per_img, tiles_x, tid); hb.prefetch(p, img_bytes, t, per_img, tiles_x, tid); }
+    lds_barrier();
     int prio_it = (int)(blockIdx.x >> 8);
     for (; t < run1; t += wgs) {
         if (!p.no_prio) rotate_wave_priority(prio_it++);
@@ -995,92 +698,21 @@ __global__ __launch_bounds__(256, OCC) void dwpw_reg2_kernel(const ConvArgs p, c
         const int tyi = rem / tiles_x, txi = rem - tyi * tiles_x;
         const int ty0 = tyi * DP_TH, tx0 = txi * DP_TW;
         v16f acc[TN];
-#pragma unroll
-        for (int jn = 0; jn < TN; ++jn)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const v4f b = *reinterpret_cast<const v4f*>(pwb + 32 * jn + 8 * g + 4 * h);
-#pragma unroll
-                for (int c = 0; c < 4; ++c) acc[jn][4 * g + c] = b[c];
-            }
-        constexpr int NS = 4 * TN, NT = 10, RA = 3, RING = 4;              // (a ring of 5 spills 34 registers beside the two prefetch sets)
-        // the K loop of one part: steps [J0, J1) of the block, whose channels are columns 2 (j - J0) + h of the halo now in LDS
-        auto kpart = [&](auto j0c, auto j1c) __attribute__((always_inline)) {
-            constexpr int J0 = decltype(j0c)::value, J1 = decltype(j1c)::value, NJ = J1 - J0;
-            v4f hv[RING], dv[RING], wq[2];
-            auto issue = [&](int G) __attribute__((always_inline)) {       // LDS reads of the part's tap-slot G = NT * (step - J0) + t
-                const int jl = G / NT, tt = G % NT;
-                if (jl >= NJ) return;
-                dv[G % RING] = dbase[(tt == 0 ? 9 : tt - 1) * CQ + 2 * (J0 + jl)];
-                if (tt > 0) hv[G % RING] = hbase[tapoff((tt - 1) / 3, (tt - 1) % 3) * PQ + 2 * jl];
-            };
-            v4f an;
-            auto consume = [&](int G) __attribute__((always_inline)) {
-                if (G / NT >= NJ) return;
-                if (G % NT == 0) an = dv[G % RING]; else an += hv[G % RING] * dv[G % RING];
-            };
-            auto wfrag = [&](int grp) __attribute__((always_inline)) {     // A fragment of (step J0 + grp / TN, column group grp % TN)
-                if (grp < NJ * TN) wq[grp & 1] = Wl[2 * (J0 + grp / TN) * Cout + wrow[grp % TN]];
-            };
-            wfrag(0);
-#pragma unroll
-            for (int G = 0; G < RA; ++G) issue(G);
-#pragma unroll
-            for (int G = 0; G < NT; ++G) { issue(G + RA); consume(G); }
-            v4f a;
-#pragma unroll
-            for (int j = 0; j < NJ; ++j) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) a[e] = fmaxf(an[e], dw_floor);
-#pragma unroll
-                for (int sl = 0; sl < NS; ++sl) {
-                    const int grp = j * TN + sl / 4;
-                    if (sl % 4 == 0) wfrag(grp + 1);
-                    acc[sl / 4] = __builtin_amdgcn_mfma_f32_32x32x2f32(wq[grp & 1][sl % 4], a[sl % 4], acc[sl / 4], 0, 0, 0);
-#pragma unroll
-                    for (int G = NT * (j + 1) + sl * NT / NS; G < NT * (j + 1) + (sl + 1) * NT / NS; ++G) { issue(G + RA); consume(G); }
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            }
-        };
+        dwpw_acc_from_bias<TN>(acc, pwb, h);
         // ---- part A
-        front_barrier();                                                    // every wave is done reading the previous tile's part-B halo
-#pragma unroll
-        for (int k = 0; k < NPA; ++k) {
-            const int i = tid + 256 * k;
-            if (i < HALO * CQA) halo[slot(i / CQA) * PQ + i % CQA] = pfa[k];
-        }
-        if (t + wgs < run1) DWPW2_PREFETCH(pfa, voa, NPA, CQA, t + wgs)
-        front_barrier();
-        kpart(std::integral_constant<int, 0>{}, std::integral_constant<int, SA>{});
+        lds_barrier();                                                      // every wave is done reading the previous tile's part-B halo
+        ha.template park<PQ>(halo, tid);
+        if (t + wgs < run1) ha.prefetch(p, img_bytes, t + wgs, per_img, tiles_x, tid);
+        lds_barrier();
+        dwpw_k_steps<0, SA, TN, RA, RING, DS, PQ, CQ, false>(acc, ln.hbase, ln.dbase, dw_floor, Wl, Cout, wrow);
         // ---- part B (same buffer)
-        front_barrier();                                                    // every wave is done reading part A
-#pragma unroll
-        for (int k = 0; k < NPB; ++k) {
-            const int i = tid + 256 * k;
-            if (i < HALO * CQB) halo[slot(i / CQB) * PQ + i % CQB] = pfb[k];
-        }
-        if (t + wgs < run1) DWPW2_PREFETCH(pfb, vob, NPB, CQB, t + wgs)
-        front_barrier();
-        kpart(std::integral_constant<int, SA>{}, std::integral_constant<int, STEPS>{});
-        // ---- epilogue: lane = pixel, accumulator quads = 4 consecutive channels
-        const int oy = ty0 + py, ox = tx0 + px;
-        if (oy < p.Ho && ox < p.Wo) {
-            float* __restrict__ orow = p.out1 + (((size_t)n * p.Ho + oy) * p.Wo + ox) * Cout;
-#pragma unroll
-            for (int jn = 0; jn < TN; ++jn)
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    const int co = 32 * jn + 8 * g + 4 * h;
-                    if (co >= Cout) continue;
-                    v4f v;
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) v[c] = fmaxf(acc[jn][4 * g + c], out_floor);
-                    *reinterpret_cast<v4f*>(orow + co) = v;
-                }
-        }
+        lds_barrier();                                                      // every wave is done reading part A
+        hb.template park<PQ>(halo, tid);
+        if (t + wgs < run1) hb.prefetch(p, img_bytes, t + wgs, per_img, tiles_x, tid);
+        lds_barrier();
+        dwpw_k_steps<SA, STEPS, TN, RA, RING, DS, PQ, CQ, false>(acc, ln.hbase, ln.dbase, dw_floor, Wl, Cout, wrow);
+        dwpw_store<TN>(acc, p, n, ty0 + ln.py, tx0 + ln.px, h, out_floor);
     }
-#undef DWPW2_PREFETCH
 }
 
 // Measured and not kept (round 3): the register-fed form WITHOUT a halo image for the stride-2 blocks (every lane gathers the nine taps of
@@ -1089,10 +721,6 @@ __global__ __launch_bounds__(256, OCC) void dwpw_reg2_kernel(const ConvArgs p, c
 // different 128-byte lines (16 bytes each, stride 2 pixels): the loads are bound by tag look-ups, not by bytes.  The strip form of
 // dwpw_kernel (lane = 16-byte channel column, 4 lanes per 64-byte pixel) keeps them coalesced and stays.
 
-static size_t dwpw_reg_lds(int CQ, int Cout, int TN, int DS) {
-    const int halo = ((DP_TH - 1) * DS + 3) * ((DP_TW - 1) * DS + 3);
-    return ((size_t)halo * (CQ + 1) + 10 * CQ + (size_t)(CQ / 2) * 2 * Cout) * 16 + (size_t)32 * TN * 4;
-}
 static bool dwpw_reg_enabled() {
     static int v = -1;
     if (v < 0) { const char* e = getenv("FACEHIP_DWPW_REG"); v = e ? atoi(e) : 1; }
@@ -1100,40 +728,14 @@ static bool dwpw_reg_enabled() {
 }
 template <int CQ, int TN, int OCC, int DS = 1>
 static void launch_dwpw_reg_cfg(const ConvArgs& a, hipStream_t s) {
-    const int tiles_x = (a.Wo + DP_TW - 1) / DP_TW, tiles_y = (a.Ho + DP_TH - 1) / DP_TH;
-    const int tiles_total = a.B * tiles_y * tiles_x;
-    const int cus = a.cus > 0 ? a.cus : conv_num_cus();
-    const size_t lds = dwpw_reg_lds(CQ, a.Cout, TN, DS);
-    static bool attr_set = false;                                          // (per instantiation) dynamic LDS beyond the 64 KB default needs the opt-in
-    if (!attr_set) {
-        FH_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&dwpw_reg_kernel<CQ, TN, OCC, DS>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        attr_set = true;
-    }
-    int grid = std::min((tiles_total + 7) / 8 * 8, cus * OCC);
-    grid = std::max(8, grid / 8 * 8);
-    ConvArgs ap = a;
-    { static int pr = -1; if (pr < 0) { const char* e = getenv("FACEHIP_DWPW_PRIO"); pr = e ? atoi(e) : 1; } ap.no_prio = pr ? 0 : 1; }   // (0: no priority rotation — A / B timing)
-    hipLaunchKernelGGL((dwpw_reg_kernel<CQ, TN, OCC, DS>), dim3((unsigned)grid), dim3(256), lds, s, ap, tiles_x, tiles_y, tiles_total);
+    launch_dwpw_persistent<&dwpw_reg_kernel<CQ, TN, OCC, DS>, OCC>(a, dwpw_reg_lds(CQ, a.Cout, TN, DS, CQ), s);
 }
 template <int CQA, int CQB, int TN, int OCC>
 static void launch_dwpw_reg2_cfg(const ConvArgs& a, hipStream_t s) {
-    const int tiles_x = (a.Wo + DP_TW - 1) / DP_TW, tiles_y = (a.Ho + DP_TH - 1) / DP_TH;
-    const int tiles_total = a.B * tiles_y * tiles_x;
-    const int cus = a.cus > 0 ? a.cus : conv_num_cus();
-    constexpr int CQ = CQA + CQB;
-    const size_t lds = ((size_t)(7 * 2 + 3) * (15 * 2 + 3) * (CQA + 1) + 10 * CQ + (size_t)(CQ / 2) * 2 * a.Cout) * 16 + (size_t)32 * TN * 4;
-    static bool attr_set = false;
-    if (!attr_set) {
-        FH_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&dwpw_reg2_kernel<CQA, CQB, TN, OCC>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        attr_set = true;
-    }
-    int grid = std::min((tiles_total + 7) / 8 * 8, cus * OCC);
-    grid = std::max(8, grid / 8 * 8);
-    ConvArgs ap = a;
-    { static int pr = -1; if (pr < 0) { const char* e = getenv("FACEHIP_DWPW_PRIO"); pr = e ? atoi(e) : 1; } ap.no_prio = pr ? 0 : 1; }
-    hipLaunchKernelGGL((dwpw_reg2_kernel<CQA, CQB, TN, OCC>), dim3((unsigned)grid), dim3(256), lds, s, ap, tiles_x, tiles_y, tiles_total);
+    launch_dwpw_persistent<&dwpw_reg2_kernel<CQA, CQB, TN, OCC>, OCC>(a, dwpw_reg_lds(CQA + CQB, a.Cout, TN, 2, CQA), s);
 }
-// true = launched.  Instantiated for SCRFD-500M's stride-1 blocks (C = 16 / 40 / 64 / 72) with any Cout <= 96.
+// true = launched.  Instantiated for SCRFD-500M's blocks — stride 1: C = 16 / 40 / 64 / 72 with any Cout <= 96; stride 2: C = 16 with
+// Cout <= 64, C = 40 with 64 < Cout <= 96.
 static bool launch_dwpw_reg(const ConvArgs& a, hipStream_t s) {
     if (!dwpw_reg_enabled() || a.u8_src || a.Cout % 4 || a.Cout > 96) return false;
     if (a.act != (int)Act::NONE && a.act != (int)Act::RELU) return false;
@@ -1141,7 +743,8 @@ static bool launch_dwpw_reg(const ConvArgs& a, hipStream_t s) {
     const int tn = (a.Cout + 31) / 32;
     if (a.dw_stride == 2) {
         // the stride-2 block of 16 channels (SCRFD: 320x320x16 -> 160x160x40): a 17 x 33 halo of all channels is 45 KB, three workgroups per
-        // CU; with 40 channels it would be 99 KB (one workgroup per CU) — those blocks stay with dwpw_kernel
+        // CU; with 40 channels it would be 99 KB (one workgroup per CU) — that block splits its K loop (dwpw_reg2_kernel); any other
+        // stride-2 shape stays with dwpw_kernel
         static int s2 = -1;
         if (s2 < 0) { const char* e = getenv("FACEHIP_DWPW_REG_S2"); s2 = e ? atoi(e) : 1; }
         if (!s2 || a.Ho != (a.H - 1) / 2 + 1 || a.Wo != (a.W - 1) / 2 + 1) return false;

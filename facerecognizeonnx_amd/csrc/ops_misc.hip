@@ -10,6 +10,7 @@
 #include <cstdlib>
 #include <stdexcept>
 
+#include "dwpw_tile.h"
 #include "kernels.h"
 #include "plan.h"
 #include "stem_fma.h"
@@ -633,11 +634,7 @@ static bool stem_px_enabled() {                               // tuning hook (A/
 // consecutive channels = one 16-byte store.  Persistent workgroups, a tile = 16 x 16 output pixels, its u8 window prefetched one tile
 // ahead into registers and parked in LDS, one LDS-only barrier per tile; per-channel vectors (bias, slope, s2, t2) in LDS so that no
 // global load sits between the stores.  Border tiles run a second, per-byte pass for the pixels whose window leaves the frame.
-__device__ __forceinline__ void stem_barrier() {                    // workgroup barrier that orders LDS traffic only (no vmcnt drain)
-#if defined(__HIP_DEVICE_COMPILE__)
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-#endif
-}
+// The walk — XCD-contiguous run, division-free advance, LDS-only barrier — is dwpw_tile.h's.
 typedef unsigned stem_v4u __attribute__((ext_vector_type(4)));
 typedef __bf16 stem_bf16x8 __attribute__((ext_vector_type(8)));
 
@@ -676,22 +673,15 @@ __global__ __launch_bounds__(256, 3) void stem_mfma_kernel(const uint8_t* __rest
     // a pixel's window lies inside the frame iff  AY0 <= oy <= AY1  and  AX0 <= ox <= AX1
     const int AY0 = 1, AY1 = min(Ho - 1, (srcH - 2) / S), AX0 = (2 + S - 1) / S, AX1 = min(Wo - 1, (srcW - 3) / S);
 
-    const int xcd = blockIdx.x & 7, wg = blockIdx.x >> 3, wgs = gridDim.x >> 3;      // (gridDim.x is a multiple of 8)
-    const int q8 = tiles_total >> 3, r8 = tiles_total & 7;
-    const int run0 = xcd * q8 + min(xcd, r8), run1 = run0 + q8 + (xcd < r8 ? 1 : 0);
-    const int d_tx = wgs % tiles_x, d_ty = (wgs / tiles_x) % tiles_y, d_n = wgs / (tiles_x * tiles_y);
-    int t = run0 + wg;
-    int n = t / (tiles_x * tiles_y), tyi = (t / tiles_x) % tiles_y, txi = t % tiles_x;      // the tile being PREFETCHED
-    auto advance = [&]() {
-        txi += d_tx; if (txi >= tiles_x) { txi -= tiles_x; ++tyi; }
-        tyi += d_ty; if (tyi >= tiles_y) { tyi -= tiles_y; ++n; }
-        n += d_n;
-    };
+    const XcdRun run = xcd_run(tiles_total);
+    const int run1 = run.run1, wgs = run.wgs;
+    int t = run.run0 + run.wg;
+    TileWalk tw(t, wgs, tiles_x, tiles_y);                                 // the tile being PREFETCHED
     unsigned pf[SLOTS];
     const int pr = tid / PITCH, pd4 = (tid % PITCH) * 4;
     auto prefetch = [&]() __attribute__((always_inline)) {
-        const uint8_t* frame = src + (size_t)n * img_stride;
-        const int sy0 = tyi * T * S - 1, sx3 = (txi * T * S - 1) * 3;
+        const uint8_t* frame = src + (size_t)tw.n * img_stride;
+        const int sy0 = tw.tyi * T * S - 1, sx3 = (tw.txi * T * S - 1) * 3;
         const unsigned base_lo = (unsigned)(unsigned long long)frame + (unsigned)(sy0 * step + sx3);
 #pragma unroll
         for (int k = 0; k < SLOTS; ++k) {
@@ -705,20 +695,20 @@ __global__ __launch_bounds__(256, 3) void stem_mfma_kernel(const uint8_t* __rest
 #if defined(__HIP_DEVICE_COMPILE__)
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #endif
-    stem_barrier();
+    lds_barrier();
     if (t < run1) prefetch();
     int buf = 0;
     for (; t < run1; t += wgs, buf ^= 1) {
-        const int cn = n, ty0 = tyi * T, tx0 = txi * T;
+        const int cn = tw.n, ty0 = tw.tyi * T, tx0 = tw.txi * T;
         const uint8_t* frame = src + (size_t)cn * img_stride;
         const int sy0 = ty0 * S - 1, sx0 = tx0 * S - 1;
         const unsigned base_lo = (unsigned)(unsigned long long)frame + (unsigned)(sy0 * step + sx0 * 3);
 #pragma unroll
         for (int k = 0; k < SLOTS; ++k)
             if (tid + 256 * k < ROWS * PITCH) stage[buf][tid + 256 * k] = pf[k];
-        advance();
+        tw.advance();
         if (t + wgs < run1) prefetch();
-        stem_barrier();
+        lds_barrier();
         const unsigned* st = stage[buf];
         const bool tile_inside = ty0 >= AY0 && ty0 + T - 1 <= AY1 && tx0 >= AX0 && tx0 + T - 1 <= AX1;
         auto finish = [&](const float (&f)[8], bool store, int oy, int ox) __attribute__((always_inline)) {

@@ -413,7 +413,7 @@ def _m_dw_forms(n, c):
 
 
 def _m_front(n, stem_stride):
-    """16-channel stem + DW->PW (front_fused_ok, dwpw_mfma.hip:1187)."""
+    """16-channel stem + DW->PW (front_fused_ok, dwpw_mfma.hip:774)."""
     x = conv_act(n, "input", 16, 3, stem_stride, act="relu", bn=True)
     x = dwpw_block(n, x, 1, 32)
     n.head_nhwc(x)

@@ -1,6 +1,7 @@
 """Long tile walks of the persistent detector and stem kernels.
 
-front_kernel, dwpw_reg_kernel, dwpw_reg2_kernel (csrc/dwpw_mfma.hip), stem_mfma_kernel and stem_conv_u8_kernel (csrc/ops_misc.hip) keep
+front_kernel, dwpw_reg_kernel, dwpw_reg2_kernel (csrc/dwpw_mfma.hip over csrc/dwpw_tile.h), stem_mfma_kernel and stem_conv_u8_kernel
+(csrc/ops_misc.hip) keep
 their workgroups alive: a workgroup computes tile t while tile t + wgs is already on its way into registers, and it reuses one LDS halo /
 stage buffer from tile to tile.  Their launchers give every tile a workgroup of its own as long as there are at most 2 .. 4 tiles per
 compute unit, which is every single-layer case of the other test files — the loop-carried part of the kernels (the prefetch one tile ahead,
