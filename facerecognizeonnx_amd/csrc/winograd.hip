@@ -4,7 +4,7 @@
 // src/face_recognizer.cpp:279-283).  Y = A^T [ (G g G^T) (.) (B^T d B) ] A on 4x4 output tiles: 36 multiplies per
 // 16 outputs and input channel instead of 144 — the matrix-core work of these layers drops 4x, at the price of two
 // bandwidth-bound transform passes and of fp32 rounding errors ~25x those of the direct form (measured in
-// DESIGN.md; far inside the path's tolerance, but it is why the direct kernel stays the default for thin layers
+// docs/kernels.md §3.1c; far inside the path's tolerance, but it is why the direct kernel stays the default for thin layers
 // and why the switch fh_rec_set_winograd exists).
 //
 //   wino_input_kernel   d (6x6 input patch per tile, zero padded)  ->  V[f][tile][ci] = B^T d B, f = 6*i + j
@@ -14,7 +14,9 @@
 //
 // U[f] = G g G^T is computed once at load time in fp64 (engine.cpp).  Interpolation points 0, +-1, +-2, inf
 // (Lavin & Gray 2016).  Thread = one tile x 4 channels; every load / store is a 16-byte lane access and
-// consecutive lanes walk the channels, so all transfers are whole 128-byte lines.
+// consecutive lanes walk the channels, so all transfers are whole 128-byte lines.  The 1-D transforms and the two tile phases of the
+// transform kernels (output: M -> Y -> epilogue, input: patch -> V) live once, in wino_xform.h; the kernels here are thread mappings,
+// LDS address rules and calls into it.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -24,33 +26,9 @@
 #include "gemm_tile.h"
 #include "kernels.h"
 #include "plan.h"
+#include "wino_xform.h"
 
 namespace fh {
-
-typedef float v2f __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-
-// Split-bf16 operand format of the opt-in "bf16x2" mode (fh_rec_set_precision): a value x travels as ONE 32-bit word holding
-// hi = bf16(x) in the low half and mid = bf16(x - hi) in the high half — 16 mantissa bits, same bytes as fp32, so the V / U buffers,
-// their indexing and the GEMM's LDS-DMA loader do not change at all; only the matrix instruction does (three bf16 products
-// hh + hm + mh with f32 accumulation instead of one f32 product).
-// Range: both halves are bf16 values, so hi overflows where bf16 does.  A finite |x| >= 0x7F7F8000 (2^127 * 1.99609375, half a bf16 ulp
-// under the largest bf16) rounds hi to +-Inf, the residual x - hi is -+Inf and the word holds (Inf, -Inf): it unpacks to NaN.  +-Inf
-// gives (Inf, NaN) and NaN gives (NaN, NaN) — every non-finite input, and every finite one above that threshold, stays non-finite.  At
-// the other end a non-zero mid is at least x's last fp32 bit, 2^-23 |x|: it can be a bf16 subnormal only for |x| < 2^-103 (the layers' values are O(1)).
-__device__ __forceinline__ v4f wino_pack_bf16x2(const v4f x) {
-    v4u out;
-#pragma unroll
-    for (int p = 0; p < 2; ++p) {
-        const v2f a = {x[2 * p], x[2 * p + 1]};
-        const unsigned hb = __builtin_bit_cast(unsigned, __builtin_convertvector(a, bf16x2));        // v_cvt_pk_bf16_f32 (round to nearest even)
-        const v2f r = {a[0] - __builtin_bit_cast(float, hb << 16), a[1] - __builtin_bit_cast(float, hb & 0xffff0000u)};   // exact
-        const unsigned mb = __builtin_bit_cast(unsigned, __builtin_convertvector(r, bf16x2));
-        out[2 * p] = (hb & 0xffffu) | (mb << 16);
-        out[2 * p + 1] = (hb >> 16) | (mb & 0xffff0000u);
-    }
-    return __builtin_bit_cast(v4f, out);
-}
 
 __global__ __launch_bounds__(256) void pack_bf16x2_kernel(const float* __restrict__ in, float* __restrict__ out, long n4) {
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x)
@@ -59,23 +37,6 @@ __global__ __launch_bounds__(256) void pack_bf16x2_kernel(const float* __restric
 void launch_pack_bf16x2(const float* in, float* out, long n, hipStream_t s) {       // n % 4 == 0
     const long n4 = n / 4;
     if (n4 > 0) hipLaunchKernelGGL(pack_bf16x2_kernel, dim3((unsigned)std::min<long>((n4 + 255) / 256, 256 * 64)), dim3(256), 0, s, in, out, n4);
-}
-
-// B^T (6x6) applied to a 6-vector
-__device__ __forceinline__ void wino_bt(const v4f (&d)[6], v4f (&t)[6]) {
-    t[0] = 4.f * d[0] - 5.f * d[2] + d[4];
-    t[1] = -4.f * d[1] - 4.f * d[2] + d[3] + d[4];
-    t[2] = 4.f * d[1] - 4.f * d[2] - d[3] + d[4];
-    t[3] = -2.f * d[1] - d[2] + 2.f * d[3] + d[4];
-    t[4] = 2.f * d[1] - d[2] - 2.f * d[3] + d[4];
-    t[5] = 4.f * d[1] - 5.f * d[3] + d[5];
-}
-// A^T (4x6) applied to a 6-vector
-__device__ __forceinline__ void wino_at(const v4f (&m)[6], v4f (&y)[4]) {
-    y[0] = m[0] + m[1] + m[2] + m[3] + m[4];
-    y[1] = m[1] - m[2] + 2.f * m[3] - 2.f * m[4];
-    y[2] = m[1] + m[2] + 4.f * m[3] + 4.f * m[4];
-    y[3] = m[1] - m[2] + 8.f * m[3] - 8.f * m[4] + m[5];
 }
 
 // in [B,H,W,C] -> V [36][NT][C], NT = B*TY*TX tiles of 4x4 outputs (input patch rows 4ty-1 .. 4ty+4)
@@ -130,23 +91,12 @@ __global__ __launch_bounds__(256, 2) void wino_input_kernel(const float* __restr
         }
         float* dst = V + (size_t)tile * C + c4 * 4;
         const size_t fs = (size_t)NTp * C;                   // stride between frequency planes (rows padded to whole GEMM tiles)
-#pragma unroll
-        for (int i = 0; i < 6; ++i) {
-            v4f o[6];
-            wino_bt(t[i], o);                                // (B^T d B)[i][j] = sum_c (B^T d)[i][c] * B^T[j][c]
-#pragma unroll
-            for (int j = 0; j < 6; ++j) *reinterpret_cast<v4f*>(dst + (size_t)(i * 6 + j) * fs) = pack ? wino_pack_bf16x2(o[j]) : o[j];
-        }
+        wino_input_rows<false>(t, false, pack, [&](int f, v4f o) { *reinterpret_cast<v4f*>(dst + (size_t)f * fs) = o; });
     }
 }
 
-struct WinoOutArgs {
-    const float* M; const float* bias; const float* slope; const float* res; float* out1; float* out2; const float* s2; const float* t2;
-    int B, H, W, C, TY, TX, act;
-    long NTp;
-};
-
 // M [36][NT][C] -> out [B,H,W,C] (H x W = output grid = input grid), epilogue as conv_mfma.hip's
+// A row of four residual reads in front of that row's stores: all 16 up front would not fit the register file here.
 __global__ __launch_bounds__(256, 2) void wino_output_kernel(const WinoOutArgs p) {
     const int C = p.C, C4 = C >> 2;
     const int NT = p.B * p.TY * p.TX;
@@ -157,55 +107,8 @@ __global__ __launch_bounds__(256, 2) void wino_output_kernel(const WinoOutArgs p
         const int tile = idx / C4;
         const int tx = tile % p.TX, ty = (tile / p.TX) % p.TY, b = tile / (p.TX * p.TY);
         const float* src = p.M + (size_t)tile * C + c4 * 4;
-        v4f t[4][6];                                         // t[y][j] = (A^T M)[y][j]
-#pragma unroll
-        for (int j = 0; j < 6; ++j) {
-            v4f m[6];
-#pragma unroll
-            for (int i = 0; i < 6; ++i) m[i] = *reinterpret_cast<const v4f*>(src + (size_t)(i * 6 + j) * fs);
-            v4f y[4];
-            wino_at(m, y);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) t[r][j] = y[r];
-        }
-        const v4f b4 = p.bias ? *reinterpret_cast<const v4f*>(p.bias + c4 * 4) : v4f{0.f, 0.f, 0.f, 0.f};
-        v4f sl = {0.f, 0.f, 0.f, 0.f}, s2 = sl, t2 = sl;
-        if (p.act == (int)Act::PRELU) sl = *reinterpret_cast<const v4f*>(p.slope + c4 * 4);
-        if (p.out2) { s2 = *reinterpret_cast<const v4f*>(p.s2 + c4 * 4); t2 = *reinterpret_cast<const v4f*>(p.t2 + c4 * 4); }
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int oy = 4 * ty + r;
-            if (oy >= p.H) continue;
-            v4f y[4];
-            wino_at(t[r], y);
-            // the row's four residual reads BEFORE its stores: loads and stores share the in-order vmcnt, a residual read issued after a
-            // store can only be waited for together with that store's acknowledgement (16 round trips per thread otherwise; all 16 reads
-            // up front would not fit the register file here — the fused kernel does that)
-            v4f rs[4];
-            if (p.res) {
-#pragma unroll
-                for (int x = 0; x < 4; ++x)
-                    rs[x] = *reinterpret_cast<const v4f*>(p.res + (((size_t)b * p.H + oy) * p.W + min(4 * tx + x, p.W - 1)) * C + c4 * 4);   // (clamped: unconditional load)
-            }
-#pragma unroll
-            for (int x = 0; x < 4; ++x) {
-                const int ox = 4 * tx + x;
-                if (ox >= p.W) continue;
-                v4f v = y[x] + b4;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    float u = v[e];
-                    if (p.act == (int)Act::RELU) u = u > 0.f ? u : 0.f;
-                    else if (p.act == (int)Act::PRELU) u = u >= 0.f ? u : u * sl[e];
-                    else if (p.act == (int)Act::SIGMOID) u = 1.0f / (1.0f + expf(-u));
-                    v[e] = u;
-                }
-                const size_t o = (((size_t)b * p.H + oy) * p.W + ox) * C + c4 * 4;
-                if (p.res) v += rs[x];
-                if (p.out1) *reinterpret_cast<v4f*>(p.out1 + o) = v;
-                if (p.out2) *reinterpret_cast<v4f*>(p.out2 + o) = v * s2 + t2;
-            }
-        }
+        wino_output_phase<false, false, false>(
+            p, b, ty, tx, c4, false, false, [&](int f) { return *reinterpret_cast<const v4f*>(src + (size_t)f * fs); }, [](int, int, v4f, v4f) {});
     }
 }
 
@@ -242,90 +145,18 @@ __global__ __launch_bounds__(256, 2) void wino_fused_kernel(const WinoFuseArgs a
     const size_t fs = (size_t)p.NTp * C;
     const size_t tg = ((size_t)b * p.TY + ty) * p.TX + tx;    // tile row of the V / M planes
     if (live) {
-        // ---- phase 1: Y = A^T M A, epilogue, LDS image
         const float* src = p.M + tg * C + c4 * 4;
-        v4f t[4][6];
-#pragma unroll
-        for (int j = 0; j < 6; ++j) {
-            v4f m[6];
-#pragma unroll
-            for (int i = 0; i < 6; ++i) m[i] = *reinterpret_cast<const v4f*>(src + (size_t)(i * 6 + j) * fs);
-            v4f y[4];
-            wino_at(m, y);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) t[r][j] = y[r];
-        }
-        const v4f b4 = p.bias ? *reinterpret_cast<const v4f*>(p.bias + c4 * 4) : v4f{0.f, 0.f, 0.f, 0.f};
-        v4f rs[4][4];                                        // residual reads before the first store (see wino_output_kernel)
-        if (p.res) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-#pragma unroll
-                for (int x = 0; x < 4; ++x) {
-                    const int oy = 4 * ty + r, ox = 4 * tx + x;
-                    rs[r][x] = *reinterpret_cast<const v4f*>(p.res + (((size_t)b * p.H + min(oy, p.H - 1)) * p.W + min(ox, p.W - 1)) * C + c4 * 4);   // (clamped: unconditional)
-                }
-        }
-        v4f sl = {0.f, 0.f, 0.f, 0.f}, s2 = {1.f, 1.f, 1.f, 1.f}, t2 = {0.f, 0.f, 0.f, 0.f};
-        if (p.act == (int)Act::PRELU) sl = *reinterpret_cast<const v4f*>(p.slope + c4 * 4);
-        if (p.s2) { s2 = *reinterpret_cast<const v4f*>(p.s2 + c4 * 4); t2 = *reinterpret_cast<const v4f*>(p.t2 + c4 * 4); }
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int oy = 4 * ty + r;
-            if (oy >= p.H) continue;
-            v4f y[4];
-            wino_at(t[r], y);
-#pragma unroll
-            for (int x = 0; x < 4; ++x) {
-                const int ox = 4 * tx + x;
-                if (ox >= p.W) continue;
-                v4f v = y[x] + b4;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    float u = v[e];
-                    if (p.act == (int)Act::RELU) u = u > 0.f ? u : 0.f;
-                    else if (p.act == (int)Act::PRELU) u = u >= 0.f ? u : u * sl[e];
-                    else if (p.act == (int)Act::SIGMOID) u = 1.0f / (1.0f + expf(-u));
-                    v[e] = u;
-                }
-                const size_t o = (((size_t)b * p.H + oy) * p.W + ox) * C + c4 * 4;
-                if (p.res) v += rs[r][x];
-                if (p.out1) *reinterpret_cast<v4f*>(p.out1 + o) = v;
-                const v4f vb = v * s2 + t2;
-                if (p.out2) *reinterpret_cast<v4f*>(p.out2 + o) = vb;
-                act[(il * HW + oy * p.W + ox) * PITCH + c4l] = a.feed_aff ? vb : v;
-            }
-        }
+        wino_output_phase<false, true, true>(
+            p, b, ty, tx, c4, false, false, [&](int f) { return *reinterpret_cast<const v4f*>(src + (size_t)f * fs); },
+            [&](int oy, int ox, v4f v, v4f vb) { act[(il * HW + oy * p.W + ox) * PITCH + c4l] = a.feed_aff ? vb : v; });
     }
     __syncthreads();
     if (!live) return;
-    // ---- phase 2: V = B^T d B from the LDS image (6x6 patch, rows / columns 4t-1 .. 4t+4, zeros outside the map)
     const v4f* img = act + (size_t)il * HW * PITCH + c4l;
-    const int iy0 = 4 * ty - 1, ix0 = 4 * tx - 1;
-    v4f tt[6][6];
-#pragma unroll
-    for (int c = 0; c < 6; ++c) {
-        const int ix = ix0 + c;
-        v4f d[6];
-#pragma unroll
-        for (int r = 0; r < 6; ++r) {
-            const int iy = iy0 + r;
-            const bool ok = (unsigned)iy < (unsigned)p.H && (unsigned)ix < (unsigned)p.W;
-            d[r] = ok ? img[(iy * p.W + ix) * PITCH] : v4f{0.f, 0.f, 0.f, 0.f};
-        }
-        v4f tc[6];
-        wino_bt(d, tc);
-#pragma unroll
-        for (int i = 0; i < 6; ++i) tt[i][c] = tc[i];
-    }
     float* dst = a.V + tg * C + c4 * 4;
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {
-        v4f o6[6];
-        wino_bt(tt[i], o6);
-#pragma unroll
-        for (int j = 0; j < 6; ++j) *reinterpret_cast<v4f*>(dst + (size_t)(i * 6 + j) * fs) = a.pack ? wino_pack_bf16x2(o6[j]) : o6[j];
-    }
+    wino_input_phase<false>(
+        p.H, p.W, ty, tx, false, false, a.pack, [&](int iy, int ix) { return img[(iy * p.W + ix) * PITCH]; },
+        [&](int f, v4f o) { *reinterpret_cast<v4f*>(dst + (size_t)f * fs) = o; });
 }
 
 // ---- the same fusion for maps of up to 56 tiles (28x28 = 49): one workgroup = ONE image x a 32-channel slice -------------------------
@@ -353,99 +184,25 @@ __global__ __launch_bounds__(kSliceThreads) void wino_slice_kernel(const WinoFus
     const bool live = tile < TPI;
     const int c4 = cs * 8 + c4l;
     const size_t fs = (size_t)p.NTp * C;
-    const bool slice_nt = a.img == 2;                          // (experiment switch FACEHIP_WINO_SLICE=2: M is read once and dead afterwards)
     const size_t tg = ((size_t)b * p.TY + ty) * p.TX + tx;
-    if (live) {
-        // ---- phase 1: Y = A^T M A, epilogue, LDS image (every global access of the 8 lanes of a tile is one 128-byte line)
+    if (live) {                                                // (every global access of the 8 lanes of a tile is one 128-byte line)
         const float* src = p.M + tg * C + c4 * 4;
-        v4f t[4][6];
-#pragma unroll
-        for (int j = 0; j < 6; ++j) {
-            v4f m[6];
-#pragma unroll
-            for (int i = 0; i < 6; ++i) m[i] = slice_nt ? __builtin_nontemporal_load(reinterpret_cast<const v4f*>(src + (size_t)(i * 6 + j) * fs)) : *reinterpret_cast<const v4f*>(src + (size_t)(i * 6 + j) * fs);
-            v4f y[4];
-            wino_at(m, y);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) t[r][j] = y[r];
-        }
-        const v4f b4 = p.bias ? *reinterpret_cast<const v4f*>(p.bias + c4 * 4) : v4f{0.f, 0.f, 0.f, 0.f};
-        v4f rs[4][4];                                        // residual reads before the first store (see wino_output_kernel)
-        if (p.res) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-#pragma unroll
-                for (int x = 0; x < 4; ++x) {
-                    const int oy = 4 * ty + r, ox = 4 * tx + x;
-                    rs[r][x] = *reinterpret_cast<const v4f*>(p.res + (((size_t)b * p.H + min(oy, p.H - 1)) * p.W + min(ox, p.W - 1)) * C + c4 * 4);   // (clamped: unconditional)
-                }
-        }
-        v4f sl = {0.f, 0.f, 0.f, 0.f}, s2 = {1.f, 1.f, 1.f, 1.f}, t2 = {0.f, 0.f, 0.f, 0.f};
-        if (p.act == (int)Act::PRELU) sl = *reinterpret_cast<const v4f*>(p.slope + c4 * 4);
-        if (p.s2) { s2 = *reinterpret_cast<const v4f*>(p.s2 + c4 * 4); t2 = *reinterpret_cast<const v4f*>(p.t2 + c4 * 4); }
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int oy = 4 * ty + r;
-            if (oy >= p.H) continue;
-            v4f y[4];
-            wino_at(t[r], y);
-#pragma unroll
-            for (int x = 0; x < 4; ++x) {
-                const int ox = 4 * tx + x;
-                if (ox >= p.W) continue;
-                v4f v = y[x] + b4;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    float u = v[e];
-                    if (p.act == (int)Act::RELU) u = u > 0.f ? u : 0.f;
-                    else if (p.act == (int)Act::PRELU) u = u >= 0.f ? u : u * sl[e];
-                    else if (p.act == (int)Act::SIGMOID) u = 1.0f / (1.0f + expf(-u));
-                    v[e] = u;
-                }
-                const size_t o = (((size_t)b * p.H + oy) * p.W + ox) * C + c4 * 4;
-                if (p.res) v += rs[r][x];
-                if (p.out1) *reinterpret_cast<v4f*>(p.out1 + o) = v;
-                const v4f vb = v * s2 + t2;
-                if (p.out2) *reinterpret_cast<v4f*>(p.out2 + o) = vb;
-                act[(oy * 32 + wino_slice_slot(ox)) * 8 + c4l] = a.feed_aff ? vb : v;
-            }
-        }
+        wino_output_phase<false, true, true>(
+            p, b, ty, tx, c4, false, false, [&](int f) { return *reinterpret_cast<const v4f*>(src + (size_t)f * fs); },
+            [&](int oy, int ox, v4f v, v4f vb) { act[(oy * 32 + wino_slice_slot(ox)) * 8 + c4l] = a.feed_aff ? vb : v; });
     }
     __syncthreads();
     if (!live) return;
-    // ---- phase 2: V = B^T d B from the LDS image (6x6 patch, rows / columns 4t-1 .. 4t+4, zeros outside the map)
     const v4f* img = act + c4l;
-    const int iy0 = 4 * ty - 1, ix0 = 4 * tx - 1;
-    v4f tt[6][6];
-#pragma unroll
-    for (int c = 0; c < 6; ++c) {
-        const int ix = ix0 + c;
-        const int sx = wino_slice_slot(ix & 31);
-        v4f d[6];
-#pragma unroll
-        for (int r = 0; r < 6; ++r) {
-            const int iy = iy0 + r;
-            const bool ok = (unsigned)iy < (unsigned)p.H && (unsigned)ix < (unsigned)p.W;
-            d[r] = ok ? img[(iy * 32 + sx) * 8] : v4f{0.f, 0.f, 0.f, 0.f};
-        }
-        v4f tc[6];
-        wino_bt(d, tc);
-#pragma unroll
-        for (int i = 0; i < 6; ++i) tt[i][c] = tc[i];
-    }
     float* dst = a.V + tg * C + c4 * 4;
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {
-        v4f o6[6];
-        wino_bt(tt[i], o6);
-#pragma unroll
-        for (int j = 0; j < 6; ++j) *reinterpret_cast<v4f*>(dst + (size_t)(i * 6 + j) * fs) = a.pack ? wino_pack_bf16x2(o6[j]) : o6[j];
-    }
+    wino_input_phase<false>(
+        p.H, p.W, ty, tx, false, false, a.pack, [&](int iy, int ix) { return img[(iy * 32 + wino_slice_slot(ix & 31)) * 8]; },
+        [&](int f, v4f o) { *reinterpret_cast<v4f*>(dst + (size_t)f * fs) = o; });
 }
 
 static int wino_slice_enabled() {
     static int v = -1;
-    if (v < 0) { const char* e = getenv("FACEHIP_WINO_SLICE"); v = e ? atoi(e) : 1; }          // (0: the round-4 behaviour, for A / B timing)
+    if (v < 0) { const char* e = getenv("FACEHIP_WINO_SLICE"); v = e ? atoi(e) : 1; }          // (0: the round-4 behaviour, for A / B timing; any other value: on)
     return v;
 }
 // maps of 17 .. 56 tiles whose 32-channel slice fits the LDS: W <= 32 (slot arithmetic), whole 32-channel slices
@@ -658,19 +415,6 @@ static void wino_check(long NT, int cmax) {
         throw std::runtime_error("winograd: batch too large for the 32-bit tile index (split the batch)");
 }
 
-// stage 1: in [B,H,W,Cin] -> V (optional per-channel affine on in-image pixels)
-void launch_wino_input(const ConvArgs& a, float* V, const float* in_scale, const float* in_shift, bool pack, hipStream_t s) {
-    const int TY = (a.H + 3) / 4, TX = (a.W + 3) / 4;
-    const long NT = (long)a.B * TY * TX;
-    if (NT <= 0) return;
-    wino_check(NT, std::max(a.Cin, a.Cout));
-    KernelTimer& timer = KernelTimer::get();
-    timer.begin(s);
-    hipLaunchKernelGGL(wino_input_kernel, dim3(wino_grid(NT * (a.Cin >> 2))), dim3(256), 0, s, a.in, V, a.B, a.H, a.W, a.Cin, TY, TX, wino_rows(NT), in_scale,
-                       in_shift, pack ? 1 : 0);
-    timer.end(s, 8, 0.0, 0.0);
-}
-
 // stage 2: the 36 GEMMs  M[f] = V[f] * U[f]   (wt36 = 36 packed weight images [conv_wt_rows(Cout)][Cin])
 // bf16x2: V and wt36 hold split-bf16 words (wino_gemm_ok_bf16x2 says whether this layer's GEMM has that form)
 bool wino_gemm_ok_bf16x2(int Cin, int Cout) { return Cout % 64 == 0 && Cin % 32 == 0; }
@@ -821,15 +565,31 @@ static WinoOutArgs wino_out_args(const ConvArgs& a, const float* M) {
     return o;
 }
 
+// one transform launch, booked under timer tag 8 (no FLOPs, no bytes: bench.py prices these kernels by their time alone)
+template <class Kernel, class... Args>
+static void launch_wino_xform(Kernel kernel, dim3 grid, dim3 block, size_t lds, hipStream_t s, const Args&... args) {
+    KernelTimer& timer = KernelTimer::get();
+    timer.begin(s);
+    hipLaunchKernelGGL(kernel, grid, block, lds, s, args...);
+    timer.end(s, 8, 0.0, 0.0);
+}
+
+// stage 1: in [B,H,W,Cin] -> V (optional per-channel affine on in-image pixels)
+void launch_wino_input(const ConvArgs& a, float* V, const float* in_scale, const float* in_shift, bool pack, hipStream_t s) {
+    const int TY = (a.H + 3) / 4, TX = (a.W + 3) / 4;
+    const long NT = (long)a.B * TY * TX;
+    if (NT <= 0) return;
+    wino_check(NT, std::max(a.Cin, a.Cout));
+    launch_wino_xform(wino_input_kernel, dim3(wino_grid(NT * (a.Cin >> 2))), dim3(256), 0, s, a.in, V, a.B, a.H, a.W, a.Cin, TY, TX, wino_rows(NT),
+                      in_scale, in_shift, pack ? 1 : 0);
+}
+
 // stage 3: M -> out (bias -> activation -> + residual -> out1, optional out2 = out1 * s2 + t2)
 void launch_wino_output(const ConvArgs& a, const float* M, hipStream_t s) {
     const WinoOutArgs o = wino_out_args(a, M);
     const long NT = (long)a.B * o.TY * o.TX;
     if (NT <= 0) return;
-    KernelTimer& timer = KernelTimer::get();
-    timer.begin(s);
-    hipLaunchKernelGGL(wino_output_kernel, dim3(wino_grid(NT * (a.Cout >> 2))), dim3(256), 0, s, o);
-    timer.end(s, 8, 0.0, 0.0);
+    launch_wino_xform(wino_output_kernel, dim3(wino_grid(NT * (a.Cout >> 2))), dim3(256), 0, s, o);
 }
 
 // can stage 3 of this convolution be fused with stage 1 of a following Winograd convolution on the same map?
@@ -856,46 +616,34 @@ bool wino_can_fuse(int H, int W, int C, bool touches_memory) {
 // stage 3 of convolution `a` + stage 1 of the next one in one kernel: M -> (out1 / out2 if non-null) and -> V of the next convolution,
 // which sees out1 (feed_aff = 0) or out1 * s2 + t2 (feed_aff = 1; a.s2 / a.t2 must then be set even when a.out2 is null).
 void launch_wino_fused(const ConvArgs& a, const float* M, float* Vnext, int feed_aff, bool pack_next, hipStream_t s) {
+    const bool slice = wino_slice_shape(a.H, a.W, a.Cout);
     WinoFuseArgs f{};
-    if (wino_slice_shape(a.H, a.W, a.Cout)) {
-        f.o = wino_out_args(a, M);
-        f.V = Vnext; f.feed_aff = feed_aff; f.pack = pack_next ? 1 : 0; f.csl4 = 8; f.pitch = 8; f.img = wino_slice_enabled() == 2 ? 2 : 1;
-        if (a.B <= 0) return;
-        wino_check((long)a.B * f.o.TY * f.o.TX, a.Cout);
-        const size_t lds = (size_t)a.H * 32 * 8 * sizeof(v4f);
-        static const bool attr = [] {                          // > 64 KB of dynamic LDS must be asked for once
-            FH_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&wino_slice_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            return true;
-        }();
-        (void)attr;
-        KernelTimer& timer = KernelTimer::get();
-        timer.begin(s);
-        hipLaunchKernelGGL(wino_slice_kernel, dim3((unsigned)(a.B * (a.Cout / 32))), dim3(kSliceThreads), lds, s, f);
-        timer.end(s, 8, 0.0, 0.0);
-        return;
-    }
-    if (!wino_fuse_shape(a.H, a.W, a.Cout, &f.csl4, &f.pitch, &f.img)) throw std::runtime_error("winograd: this map cannot take the fused transform");
+    f.csl4 = 8; f.pitch = 8; f.img = 1;                        // the slice kernel's split: one image x 32 channels
+    if (!slice && !wino_fuse_shape(a.H, a.W, a.Cout, &f.csl4, &f.pitch, &f.img)) throw std::runtime_error("winograd: this map cannot take the fused transform");
     f.o = wino_out_args(a, M);
     f.V = Vnext; f.feed_aff = feed_aff; f.pack = pack_next ? 1 : 0;
     const long NT = (long)a.B * f.o.TY * f.o.TX;
     if (NT <= 0) return;
     wino_check(NT, a.Cout);
-    const size_t lds = (size_t)f.img * a.H * a.W * f.pitch * sizeof(v4f);
-    KernelTimer& timer = KernelTimer::get();
-    timer.begin(s);
-    hipLaunchKernelGGL(wino_fused_kernel, dim3((unsigned)(((a.B + f.img - 1) / f.img) * (a.Cout / (4 * f.csl4)))), dim3(256), lds, s, f);
-    timer.end(s, 8, 0.0, 0.0);
+    if (slice) {
+        static const bool attr = [] {                          // > 64 KB of dynamic LDS must be asked for once
+            FH_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&wino_slice_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+            return true;
+        }();
+        (void)attr;
+        launch_wino_xform(wino_slice_kernel, dim3((unsigned)(a.B * (a.Cout / 32))), dim3(kSliceThreads), (size_t)a.H * 32 * 8 * sizeof(v4f), s, f);
+    } else {
+        launch_wino_xform(wino_fused_kernel, dim3((unsigned)(((a.B + f.img - 1) / f.img) * (a.Cout / (4 * f.csl4)))), dim3(256),
+                          (size_t)f.img * a.H * a.W * f.pitch * sizeof(v4f), s, f);
+    }
 }
 
 // ---- mixed F(4x4) / F(2x2) tiling: the transform kernel (see WinoPlanes in kernels.h) --------------------------------------------------
 // wino_fused_kernel's anatomy (one image x 64 channels per workgroup, thread = (tile, float4 column), LDS image between the two phases)
 // with the tile's class decided per thread: the row direction of a tile is wave-uniform (wave = tile row), the column direction differs
-// between the 16-lane groups of a wave.  Both 1-D transforms are evaluated and selected (the kernel is bound by its V / M traffic, not by
-// the vector ALU); frequencies a class does not have are addressed OUT OF RANGE of the buffer descriptor, so their loads return zero
-// and their stores are dropped by the hardware — no branch, and the 36 loads of a thread stay in flight together.
-// F(2x2,3x3) with the points {0, 1, -1, inf}: B^T rows (d0 - d2, d1 + d2, d2 - d1, d1 - d3), A^T = [1 1 1 0; 0 1 -1 -1]; its G rows are
-// (4, -3, -3, 1) x the rows {0, 1, 2, 5} of F(4x4,3x3)'s G, so with those factors on the B^T rows the planes multiply the F(4x4) weight
-// matrices U[6 i + j] unchanged.
+// between the 16-lane groups of a wave.  The phases of wino_xform.h evaluate both 1-D transforms and select; frequencies a class does not
+// have are addressed OUT OF RANGE of the buffer descriptor, so their loads return zero and their stores are dropped by the hardware — no
+// branch, and the 36 loads of a thread stay in flight together.
 struct WinoMixArgs {
     WinoOutArgs o;          // (o.M null: the image comes from `in`)
     WinoPlanes pl;
@@ -904,15 +652,6 @@ struct WinoMixArgs {
     unsigned plane_bytes;   // size of the V / M workspace in this layout (bytes): the buffer descriptors' range
     int feed_aff, pack;
 };
-
-__device__ __forceinline__ void wino_bt2s(const v4f (&d)[6], v4f (&t)[6]) {
-    t[0] = 4.f * (d[0] - d[2]);
-    t[1] = -3.f * (d[1] + d[2]);
-    t[2] = 3.f * (d[1] - d[2]);
-    t[3] = d[1] - d[3];
-    t[4] = v4f{0.f, 0.f, 0.f, 0.f};
-    t[5] = t[4];
-}
 
 __global__ __launch_bounds__(256, 2) void wino_mix_kernel(const WinoMixArgs a) {
     const WinoOutArgs& p = a.o;
@@ -934,69 +673,16 @@ __global__ __launch_bounds__(256, 2) void wino_mix_kernel(const WinoMixArgs a) {
     const int c4 = cs * 16 + c4l;
     const unsigned off0 = (unsigned)(((base_c + b * n_c + lidx) * C + c4 * 4) * 4);       // byte offset of frequency (0, 0)
     const unsigned pstride = (unsigned)rows_c * (unsigned)C * 4u;                            // bytes between frequency planes
-    constexpr unsigned OOB = 0x80000000u;
+    // byte offset of frequency f = 6 i + j of the F(4x4) set in this tile's class; out of the descriptor's range if the class lacks it
+    auto plane_off = [&](int f) {
+        const int i = f / 6, j = f % 6;
+        return i < nfr && j < nfc ? off0 + (unsigned)(i * nfc + j) * pstride : 0x80000000u;
+    };
     if (p.M) {
-        // ---- phase 1: Y = A^T M A, epilogue, LDS image
         const __amdgpu_buffer_rsrc_t rm = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.M), 0, a.plane_bytes, 0x00020000);
-        v4f t[4][6];
-#pragma unroll
-        for (int j = 0; j < 6; ++j) {
-            v4f m[6];
-#pragma unroll
-            for (int i = 0; i < 6; ++i) {
-                const bool ok = i < nfr && j < nfc;
-                m[i] = __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(rm, ok ? off0 + (unsigned)(i * nfc + j) * pstride : OOB, 0, 0));
-            }
-            v4f y4[4];
-            wino_at(m, y4);
-            const v4f y20 = m[0] + m[1] + m[2], y21 = m[1] - m[2] - m[3];
-            t[0][j] = rF2 ? y20 : y4[0];
-            t[1][j] = rF2 ? y21 : y4[1];
-            t[2][j] = y4[2];                                  // (rows 2, 3 of an F(2) tile lie outside the map: never stored)
-            t[3][j] = y4[3];
-        }
-        const v4f b4 = p.bias ? *reinterpret_cast<const v4f*>(p.bias + c4 * 4) : v4f{0.f, 0.f, 0.f, 0.f};
-        v4f rs[4][4];                                        // residual reads before the first store (see wino_output_kernel)
-        if (p.res) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-#pragma unroll
-                for (int x = 0; x < 4; ++x) {
-                    const int oy = 4 * ty + r, ox = 4 * tx + x;
-                    rs[r][x] = *reinterpret_cast<const v4f*>(p.res + (((size_t)b * p.H + min(oy, p.H - 1)) * p.W + min(ox, p.W - 1)) * C + c4 * 4);   // (clamped: unconditional)
-                }
-        }
-        v4f sl = {0.f, 0.f, 0.f, 0.f}, s2 = {1.f, 1.f, 1.f, 1.f}, t2 = {0.f, 0.f, 0.f, 0.f};
-        if (p.act == (int)Act::PRELU) sl = *reinterpret_cast<const v4f*>(p.slope + c4 * 4);
-        if (p.s2) { s2 = *reinterpret_cast<const v4f*>(p.s2 + c4 * 4); t2 = *reinterpret_cast<const v4f*>(p.t2 + c4 * 4); }
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int oy = 4 * ty + r;
-            if (oy >= p.H) continue;
-            v4f y[4];
-            wino_at(t[r], y);
-            if (cF2) { y[0] = t[r][0] + t[r][1] + t[r][2]; y[1] = t[r][1] - t[r][2] - t[r][3]; }
-#pragma unroll
-            for (int x = 0; x < 4; ++x) {
-                const int ox = 4 * tx + x;
-                if (ox >= p.W) continue;
-                v4f v = y[x] + b4;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    float u = v[e];
-                    if (p.act == (int)Act::RELU) u = u > 0.f ? u : 0.f;
-                    else if (p.act == (int)Act::PRELU) u = u >= 0.f ? u : u * sl[e];
-                    else if (p.act == (int)Act::SIGMOID) u = 1.0f / (1.0f + expf(-u));
-                    v[e] = u;
-                }
-                const size_t o = (((size_t)b * p.H + oy) * p.W + ox) * C + c4 * 4;
-                if (p.res) v += rs[r][x];
-                if (p.out1) *reinterpret_cast<v4f*>(p.out1 + o) = v;
-                const v4f vb = v * s2 + t2;
-                if (p.out2) *reinterpret_cast<v4f*>(p.out2 + o) = vb;
-                act[(oy * p.W + ox) * 16 + c4l] = a.feed_aff ? vb : v;
-            }
-        }
+        wino_output_phase<true, true, true>(
+            p, b, ty, tx, c4, rF2, cF2, [&](int f) { return __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(rm, plane_off(f), 0, 0)); },
+            [&](int oy, int ox, v4f v, v4f vb) { act[(oy * p.W + ox) * 16 + c4l] = a.feed_aff ? vb : v; });
     } else {
         // ---- the image comes from memory (first convolution of a chain): whole 256-byte pixel rows per 16 lanes
         v4f as4 = {1.f, 1.f, 1.f, 1.f}, at4 = {0.f, 0.f, 0.f, 0.f};
@@ -1006,40 +692,11 @@ __global__ __launch_bounds__(256, 2) void wino_mix_kernel(const WinoMixArgs a) {
     }
     if (!a.V) return;
     __syncthreads();
-    // ---- phase 2: V = B^T d B from the LDS image (zeros outside the map)
     const __amdgpu_buffer_rsrc_t rv = __builtin_amdgcn_make_buffer_rsrc(a.V, 0, a.plane_bytes, 0x00020000);
     const v4f* img = act + c4l;
-    const int iy0 = 4 * ty - 1, ix0 = 4 * tx - 1;
-    v4f tt[6][6];
-#pragma unroll
-    for (int c = 0; c < 6; ++c) {
-        const int ix = ix0 + c;
-        v4f d[6];
-#pragma unroll
-        for (int r = 0; r < 6; ++r) {
-            const int iy = iy0 + r;
-            const bool ok = (unsigned)iy < (unsigned)p.H && (unsigned)ix < (unsigned)p.W;
-            d[r] = ok ? img[(iy * p.W + ix) * 16] : v4f{0.f, 0.f, 0.f, 0.f};
-        }
-        v4f t4[6], t2s[6];
-        wino_bt(d, t4);
-        wino_bt2s(d, t2s);
-#pragma unroll
-        for (int i = 0; i < 6; ++i) tt[i][c] = rF2 ? t2s[i] : t4[i];
-    }
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {
-        v4f o4[6], o2[6];
-        wino_bt(tt[i], o4);
-        wino_bt2s(tt[i], o2);
-#pragma unroll
-        for (int j = 0; j < 6; ++j) {
-            const bool ok = i < nfr && j < nfc;
-            const v4f o = cF2 ? o2[j] : o4[j];
-            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u, a.pack ? wino_pack_bf16x2(o) : o), rv,
-                                                   ok ? off0 + (unsigned)(i * nfc + j) * pstride : OOB, 0, 0);
-        }
-    }
+    wino_input_phase<true>(
+        p.H, p.W, ty, tx, rF2, cF2, a.pack, [&](int iy, int ix) { return img[(iy * p.W + ix) * 16]; },
+        [&](int f, v4f o) { __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u, o), rv, plane_off(f), 0, 0); });
 }
 
 void launch_wino_mix(const ConvArgs& a, const WinoPlanes& pl, const float* M, float* Vnext, int feed_aff, const float* in_scale,
@@ -1055,11 +712,7 @@ void launch_wino_mix(const ConvArgs& a, const WinoPlanes& pl, const float* M, fl
     for (int c = 0; c < 4; ++c) rows += (long)((c & 2) ? 4 : 6) * pl.nfc[c] * pl.rows[c];
     f.plane_bytes = (unsigned)(rows * f.o.C * 4);
     if (f.o.C % 64 || f.o.TY * f.o.TX != 16 || rows * f.o.C * 4 >= (1L << 31)) throw std::runtime_error("winograd: this map cannot take the mixed tiling");
-    const size_t lds = (size_t)a.H * a.W * 16 * sizeof(v4f);
-    KernelTimer& timer = KernelTimer::get();
-    timer.begin(s);
-    hipLaunchKernelGGL(wino_mix_kernel, dim3((unsigned)(a.B * (f.o.C / 64))), dim3(256), lds, s, f);
-    timer.end(s, 8, 0.0, 0.0);
+    launch_wino_xform(wino_mix_kernel, dim3((unsigned)(a.B * (f.o.C / 64))), dim3(256), (size_t)a.H * a.W * 16 * sizeof(v4f), s, f);
 }
 
 // all three stages of one convolution (used by the single-layer test entry point); bf16x2: wt36 holds split-bf16 words, V is packed

@@ -430,7 +430,7 @@ def _m_halo(n):
 
 
 def _m_wino2(n):
-    """64-channel 3x3 s1 convs (wino2_ok, conv_wino2.hip:384)."""
+    """64-channel 3x3 s1 convs (wino2_ok in conv_wino2.hip)."""
     x = conv_act(n, "input", 64, 3, 2, act="relu", bn=False)
     x = conv_act(n, x, 64, 3, 1, act="relu", bn=False)
     x = res_block(n, x, False)
@@ -438,8 +438,8 @@ def _m_wino2(n):
 
 
 def _m_wino_chain(n):
-    """Chains of 3x3 s1 convs with >= 128 channels on a 14x14 map (side 4k+2: the mixed F(4x4)/F(2x2) tiling, wino_mix_layout,
-    winograd.hip:894) and on a 7x7 map, with fused transforms between consecutive layers (engine.cpp:260-279, 515-527)."""
+    """Chains of 3x3 s1 convs with >= 128 channels on a 14x14 map (side 4k+2: the mixed F(4x4)/F(2x2) tiling, wino_mix_layout in
+    winograd.hip) and on a 7x7 map, with fused transforms between consecutive layers (engine.cpp:260-279, 515-527)."""
     x = conv_act(n, "input", 32, 3, 2, act="relu", bn=True)
     x = conv_act(n, x, 128, 3, 1, act="relu", bn=True)
     x = conv_act(n, x, 128, 3, 1, act="prelu", bn=True)

@@ -35,7 +35,7 @@ SEEDS = list(range(N_RANDOM)) + sorted(gg.MOTIFS) + sorted(gg.REGRESSIONS)
 K_WINO_MIN_TILES = 256       # engine.cpp:88 kWinoMinTiles (4x4-output tiles per launch)
 WINO_MIN_CIN = 128           # engine.cpp:87 kWinoMinCin
 WINO2_MIN_BLOCKS = 64        # engine.cpp:94 wino2_min_blocks() default
-MIX_MIN_B = 64               # winograd.hip:899 wino_mix_layout: B >= 64
+MIX_MIN_B = 64               # winograd.hip wino_mix_layout: B >= 64
 N_CUS = 256                  # conv_mfma.hip num_cus() on an MI355X (the pw / tall predicates count tiles per CU)
 TAGS = 13                    # kernels.h KernelTimer::kTags
 SMALL_KERNELS = ("ACT", "ADD", "AFFINE", "UPSAMPLE", "DWGLOBAL", "GCONV",
