@@ -43,6 +43,9 @@ class FhView(C.Structure):
 TRACK_DTYPE = np.dtype([(k, "<i4") for k in ("id", "x", "y", "w", "h", "last_seen", "last_embed", "hits")])
 assert TRACK_DTYPE.itemsize == 32
 TRACK_MAX = 64                                                 # FH_TRACK_MAX
+TRACK_IDENT_DTYPE = np.dtype([("id", "<i4"), ("n_emb", "<i4"), ("label", "<i4"), ("score", "<f4")])     # fh_track_ident
+assert TRACK_IDENT_DTYPE.itemsize == 16
+TRACK_POOL_LAST, TRACK_POOL_SUM = 0, 1                         # enum fh_track_pool
 
 
 class FhTrackState(C.Structure):
@@ -139,6 +142,13 @@ PROTOTYPES = {
     "fh_track_update_dev": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),
     "fh_track_select_dev": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "fh_pipeline_run_tracked_dev": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _ll, _vp, _f, _f, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "fh_track_update_slots_dev": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "fh_tracker_enable_identity": (_i, [_vp, _i, _i]),
+    "fh_track_identify_dev": (_i, [_vp, _vp, _f, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "fh_tracker_queries_dev": (_vp, [_vp]),
+    "fh_tracker_get_identity": (_i, [_vp, _i, _vp, _vp]),
+    "fh_pipeline_run_identified_dev": (_i, [_vp, _vp, _vp, _vp, _f, _vp, _i, _i, _i, _i, _ll, _vp, _f, _f, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                            _vp, _vp, _vp]),
     "fh_gallery_create": (_vp, [_i]),
     "fh_gallery_destroy": (None, [_vp]),
     "fh_gallery_upload": (_i, [_vp, _vp, _ll, _i, _ll]),

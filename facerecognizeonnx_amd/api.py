@@ -367,11 +367,44 @@ class Tracker:
         return self._h
 
     def update_dev(self, det_ptr: int, counts_ptr: int, n: int, per_frame: int, track_ptr: int, embed_ptr: int, stream_of=None,
-                   stream: int = 0) -> int:
-        """Steps 1-4 of the contract on n frames of [per_frame] records; writes track ids and embed flags [n][per_frame]."""
+                   stream: int = 0, slot_ptr=None) -> int:
+        """Steps 1-4 of the contract on n frames of [per_frame] records; writes track ids and embed flags [n][per_frame] — and, with
+        slot_ptr, the slot of each detection's track (fh_track_update_slots_dev), which identify_dev needs."""
         keep, sp = _stream_of(stream_of, n)
-        return check(_lib.lib().fh_track_update_dev(self._h, det_ptr, counts_ptr, n, per_frame, sp, track_ptr, embed_ptr, stream),
-                     "fh_track_update_dev")
+        if slot_ptr is None:
+            return check(_lib.lib().fh_track_update_dev(self._h, det_ptr, counts_ptr, n, per_frame, sp, track_ptr, embed_ptr, stream),
+                         "fh_track_update_dev")
+        return check(_lib.lib().fh_track_update_slots_dev(self._h, det_ptr, counts_ptr, n, per_frame, sp, track_ptr, embed_ptr, slot_ptr,
+                                                          stream), "fh_track_update_slots_dev")
+
+    def enable_identity(self, dim: int, pool: int = _lib.TRACK_POOL_SUM) -> None:
+        """Allocate (or clear and re-size) the per-track identity state: a running template of `dim` floats per track slot, pooled as
+        the sum of the track's embeddings (TRACK_POOL_SUM) or just the latest one (TRACK_POOL_LAST)."""
+        check(_lib.lib().fh_tracker_enable_identity(self._h, int(dim), int(pool)), "fh_tracker_enable_identity")
+        self.identity_dim = int(dim)
+
+    def identify_dev(self, gallery, threshold: float, track_ptr: int, slot_ptr: int, embed_ptr: int, emb_ptr, total: int, n: int,
+                     per_frame: int, label_ptr: int, score_ptr: int, stream_of=None, stream: int = 0) -> int:
+        """After update_dev(..., slot_ptr=...) and the embedding of the `total` flagged faces (emb_ptr = [total][dim], in select_dev's
+        order): pool each into its track's template, label the templates against `gallery`, and write a label and a score for EVERY
+        entry [n][per_frame] — the faces that were not embedded carry their track's."""
+        keep, sp = _stream_of(stream_of, n)
+        return check(_lib.lib().fh_track_identify_dev(self._h, gallery._h if gallery is not None else None, float(threshold), track_ptr,
+                                                      slot_ptr, embed_ptr, emb_ptr, int(total), n, per_frame, sp, label_ptr, score_ptr,
+                                                      stream), "fh_track_identify_dev")
+
+    def queries_ptr(self) -> int:
+        """Device pointer of the [total][dim] queries of the last identify_dev (a stage hook for tests)."""
+        return _lib.lib().fh_tracker_queries_dev(self._h) or 0
+
+    def identity(self, stream: int = 0, sums: bool = False):
+        """The live slots' identities, ascending (the positions of state()), as TRACK_IDENT_DTYPE records; with sums=True: (records,
+        float32 [live][dim] running templates)."""
+        out = np.zeros(self.max_tracks, _lib.TRACK_IDENT_DTYPE)
+        acc = np.zeros((self.max_tracks, getattr(self, "identity_dim", 0)), np.float32) if sums else None
+        live = check(_lib.lib().fh_tracker_get_identity(self._h, int(stream), out.ctypes.data, acc.ctypes.data if sums else None),
+                     "fh_tracker_get_identity")
+        return (out[:live].copy(), acc[:live].copy()) if sums else out[:live].copy()
 
     @staticmethod
     def select_dev(det_ptr: int, embed_ptr: int, n: int, per_frame: int, faces_ptr: int, frame_of_ptr: int, track_ptr: int,
@@ -405,6 +438,22 @@ def pipeline_run_tracked_dev(det: FaceDetector, rec: FaceRecognizer, tracker: Tr
                                                         frames_ptr, n, rows, cols, step, rows * step, sp, scoreThreshold, nmsThreshold,
                                                         faces_per_frame, all_ptr, counts_ptr, track_ptr, faces_ptr, frame_of_ptr,
                                                         track_of_ptr, emb_ptr, stream), "fh_pipeline_run_tracked_dev")
+
+
+def pipeline_run_identified_dev(det: FaceDetector, rec: FaceRecognizer, tracker: Tracker, gallery, threshold: float, frames_ptr: int, n: int,
+                                rows: int, cols: int, faces_per_frame: int, all_ptr: int, counts_ptr: int, track_ptr: int, faces_ptr: int,
+                                frame_of_ptr: int, track_of_ptr: int, emb_ptr: int, label_ptr: int, score_ptr: int, stream_of=None,
+                                scoreThreshold: float = 0.5, nmsThreshold: float = 0.4, stream: int = 0) -> int:
+    """pipeline_run_tracked_dev plus a name for every face (fh_pipeline_run_identified_dev): the embedded faces are pooled into their
+    tracks' templates and labelled against `gallery`; label_ptr / score_ptr = [n][F], where the faces that were not embedded carry their
+    track's answer.  The tracker needs enable_identity(rec.feature dim).  Returns the number of faces embedded."""
+    step = cols * 3
+    keep, sp = _stream_of(stream_of, n)
+    return check(_lib.lib().fh_pipeline_run_identified_dev(det.handle, rec.handle, tracker.handle if tracker is not None else None,
+                                                           gallery._h if gallery is not None else None, float(threshold), frames_ptr, n,
+                                                           rows, cols, step, rows * step, sp, scoreThreshold, nmsThreshold, faces_per_frame,
+                                                           all_ptr, counts_ptr, track_ptr, faces_ptr, frame_of_ptr, track_of_ptr, emb_ptr,
+                                                           label_ptr, score_ptr, stream), "fh_pipeline_run_identified_dev")
 
 
 def pipeline_images(det: FaceDetector, rec: FaceRecognizer, images, faces_per_frame: int = 1, scoreThreshold: float = 0.5,

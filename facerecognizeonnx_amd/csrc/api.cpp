@@ -17,6 +17,8 @@ static_assert(sizeof(fh_frame) == 24 && sizeof(fh::FrameIn) == 24 && offsetof(fh
               offsetof(fh_frame, step) == offsetof(fh::FrameIn, step), "fh_frame and the engine's FrameIn are one layout");
 static_assert(sizeof(fh_track_state) == sizeof(fh::TrackState) && offsetof(fh_track_state, hits) == offsetof(fh::TrackState, hits) &&
               FH_TRACK_MAX == 64, "fh_track_state mirrors TrackState; one slot per lane of a wave");
+static_assert(sizeof(fh_track_ident) == 16 && sizeof(fh::TrackIdent) == 16 && offsetof(fh_track_ident, score) == offsetof(fh::TrackIdent, score),
+              "fh_track_ident mirrors TrackIdent");
 static_assert(sizeof(fh_tiling) == sizeof(fh::Tiling) && offsetof(fh_tiling, border) == offsetof(fh::Tiling, border) &&
               sizeof(fh_view) == sizeof(fh::View) && offsetof(fh_view, edges) == offsetof(fh::View, edges) &&
               FH_TILE_MAX_VIEWS == fh::kTileMaxViews && FH_ERR_ARG == fh::kTilePlanBadArg, "fh_tiling / fh_view mirror tile_plan.h");
@@ -897,14 +899,19 @@ int fh_track_plan(const int* stream_of, int n, int streams, int* order, int* sta
         return arg_error("fh_track_plan: need 1 <= n <= 4096, 1 <= streams <= 4096 and every stream index in [0, streams)");
     return 0;
 }
-int fh_track_update_dev(fh_tracker* t, const fh_face* det, const int* counts, int n, int per_frame, const int* stream_of, int* track,
-                        int* embed, void* stream) {
-    if (!t || !det || !counts || !track || !embed) return arg_error("fh_track_update_dev: null argument");
-    if (const char* bad = bad_track_batch(t, n, per_frame, stream_of)) return frames_error("fh_track_update_dev", bad);
+int fh_track_update_slots_dev(fh_tracker* t, const fh_face* det, const int* counts, int n, int per_frame, const int* stream_of, int* track,
+                              int* embed, int* slot, void* stream) {
+    const char* const fn = slot ? "fh_track_update_slots_dev" : "fh_track_update_dev";
+    if (!t || !det || !counts || !track || !embed) return frames_error(fn, "null argument");
+    if (const char* bad = bad_track_batch(t, n, per_frame, stream_of)) return frames_error(fn, bad);
     return guarded([&] {
-        t->t.update_dev(reinterpret_cast<const fh::FaceRec*>(det), counts, n, per_frame, stream_of, track, embed, S(stream));
+        t->t.update_dev(reinterpret_cast<const fh::FaceRec*>(det), counts, n, per_frame, stream_of, track, embed, slot, S(stream));
         return n;
     });
+}
+int fh_track_update_dev(fh_tracker* t, const fh_face* det, const int* counts, int n, int per_frame, const int* stream_of, int* track,
+                        int* embed, void* stream) {
+    return fh_track_update_slots_dev(t, det, counts, n, per_frame, stream_of, track, embed, nullptr, stream);
 }
 int fh_track_select_dev(const fh_face* det, const int* embed, int n, int per_frame, fh_face* faces, int* frame_of, const int* track,
                         int* track_of, int* total, void* stream) {
@@ -918,7 +925,29 @@ int fh_track_select_dev(const fh_face* det, const int* embed, int n, int per_fra
     });
 }
 // fh_pipeline_run_dev with the tracker between the NMS and the selection: detect -> update -> flagged select -> the one 4-byte
-// hand-off -> align + embed on exactly the flagged faces, all on `stream`.
+// hand-off -> align + embed on exactly the flagged faces, all on `stream`.  (slot: null, or the update's third output.)
+namespace {
+int pipeline_tracked(fh_det* d, fh_rec* r, fh_tracker* t, const uint8_t* frames, int n, int rows, int cols, int step, long long stride,
+                     const int* stream_of, float score_thr, float nms_thr, int F, fh_face* all, int* counts, int* track, int* flags, int* slot,
+                     fh_face* faces, int* frame_of, int* track_of, float* emb, hipStream_t s) {
+    d->p_total.ensure(sizeof(int));
+    if (!d->ev_sel) FH_HIP(hipEventCreateWithFlags(&d->ev_sel, hipEventDisableTiming));
+    if (!d->h_total) FH_HIP(hipHostMalloc(reinterpret_cast<void**>(&d->h_total), sizeof(int), hipHostMallocDefault));
+    fh::FaceRec* rec_all = reinterpret_cast<fh::FaceRec*>(all);
+    d->det.detect_dev(frames, n, rows, cols, step, (long)stride, score_thr, nms_thr, rec_all, F, counts, s);
+    t->t.update_dev(rec_all, counts, n, F, stream_of, track, flags, slot, s);
+    fh::launch_track_select(rec_all, flags, track, n, F, reinterpret_cast<fh::FaceRec*>(faces), frame_of, track_of, d->p_total.as<int>(), s);
+    const int total = count_handoff(d, d->p_total.as<int>(), s);
+    r->rec.embed_faces_dev(frames, rows, cols, step, (long)stride, reinterpret_cast<const fh::FaceRec*>(faces), frame_of, total, emb, nullptr, s);
+    return total;
+}
+// what fh_track_identify_dev and fh_pipeline_run_identified_dev ask of the tracker and the gallery.  Null on success.
+const char* bad_identity(const fh_tracker* t, const fh_gallery* g) {
+    if (t->t.identity_dim() == 0) return "identity is not enabled (fh_tracker_enable_identity)";
+    if (g->g.dim() != t->t.identity_dim()) return "the gallery's dim is not the identity dim";
+    return nullptr;
+}
+}  // namespace
 int fh_pipeline_run_tracked_dev(fh_det* d, fh_rec* r, fh_tracker* t, const uint8_t* frames, int n, int rows, int cols, int step,
                                 long long stride, const int* stream_of, float score_thr, float nms_thr, int F, fh_face* all, int* counts,
                                 int* track, fh_face* faces, int* frame_of, int* track_of, float* emb, void* stream) {
@@ -928,17 +957,56 @@ int fh_pipeline_run_tracked_dev(fh_det* d, fh_rec* r, fh_tracker* t, const uint8
     if (rows <= 0 || cols <= 0 || step < cols * 3) return arg_error("fh_pipeline_run_tracked_dev: bad size");
     Owns owns(&d->det.net(), &r->rec.net());
     return guarded([&] {
+        return pipeline_tracked(d, r, t, frames, n, rows, cols, step, stride, stream_of, score_thr, nms_thr, F, all, counts, track,
+                                t->t.embed_scratch((size_t)n * F), nullptr, faces, frame_of, track_of, emb, S(stream));
+    });
+}
+
+// ---------------------------------------------------------------------------------- track identity
+int fh_tracker_enable_identity(fh_tracker* t, int dim, int pool) {
+    if (!t) return arg_error("fh_tracker_enable_identity: null handle");
+    if (dim < 64 || dim > 4096 || dim % 64) return arg_error("fh_tracker_enable_identity: need dim % 64 == 0 and 64 <= dim <= 4096");
+    if (pool != FH_TRACK_POOL_LAST && pool != FH_TRACK_POOL_SUM) return arg_error("fh_tracker_enable_identity: unknown pool mode");
+    return guarded([&] { t->t.enable_identity(dim, pool); return 0; });
+}
+int fh_track_identify_dev(fh_tracker* t, fh_gallery* g, float threshold, const int* track, const int* slot, const int* embed, const float* emb,
+                          int total, int n, int per_frame, const int* stream_of, int* label, float* score, void* stream) {
+    if (!t || !g || !track || !slot || !embed || !label || !score) return arg_error("fh_track_identify_dev: null argument");
+    if (const char* bad = bad_track_batch(t, n, per_frame, stream_of)) return frames_error("fh_track_identify_dev", bad);
+    if (const char* bad = bad_identity(t, g)) return frames_error("fh_track_identify_dev", bad);
+    if (total < 0 || (long long)total > (long long)n * per_frame) return arg_error("fh_track_identify_dev: need 0 <= total <= n * per_frame");
+    if (total > 0 && !emb) return arg_error("fh_track_identify_dev: null embeddings with total > 0");
+    return guarded([&] {
+        t->t.identify_dev(g->g, threshold, track, slot, embed, emb, total, n, per_frame, stream_of, label, score, S(stream));
+        return n;
+    });
+}
+const float* fh_tracker_queries_dev(fh_tracker* t) { return t ? t->t.queries() : nullptr; }
+int fh_tracker_get_identity(fh_tracker* t, int stream, fh_track_ident* out, float* sums_out) {
+    if (!t) return arg_error("fh_tracker_get_identity: null handle");
+    if (stream < 0 || stream >= t->t.streams()) return arg_error("fh_tracker_get_identity: no such stream");
+    if (t->t.identity_dim() == 0) return arg_error("fh_tracker_get_identity: identity is not enabled (fh_tracker_enable_identity)");
+    return guarded([&] { return t->t.get_identity(stream, reinterpret_cast<fh::TrackIdent*>(out), sums_out); });
+}
+// fh_pipeline_run_tracked_dev with the update reporting slots, then the identify step on what the recogniser produced
+int fh_pipeline_run_identified_dev(fh_det* d, fh_rec* r, fh_tracker* t, fh_gallery* g, float threshold, const uint8_t* frames, int n, int rows,
+                                   int cols, int step, long long stride, const int* stream_of, float score_thr, float nms_thr, int F,
+                                   fh_face* all, int* counts, int* track, fh_face* faces, int* frame_of, int* track_of, float* emb, int* label,
+                                   float* score, void* stream) {
+    if (!d || !r || !t || !g || !frames || !all || !counts || !track || !faces || !frame_of || !track_of || !emb || !label || !score)
+        return arg_error("fh_pipeline_run_identified_dev: null argument");
+    if (const char* bad = bad_track_batch(t, n, F, stream_of)) return frames_error("fh_pipeline_run_identified_dev", bad);
+    if (rows <= 0 || cols <= 0 || step < cols * 3) return arg_error("fh_pipeline_run_identified_dev: bad size");
+    if (const char* bad = bad_identity(t, g)) return frames_error("fh_pipeline_run_identified_dev", bad);
+    if (r->rec.dim() != t->t.identity_dim()) return arg_error("fh_pipeline_run_identified_dev: the recogniser's feature dim is not the identity dim");
+    Owns owns(&d->det.net(), &r->rec.net());
+    return guarded([&] {
         hipStream_t s = S(stream);
-        d->p_total.ensure(sizeof(int));
-        if (!d->ev_sel) FH_HIP(hipEventCreateWithFlags(&d->ev_sel, hipEventDisableTiming));
-        if (!d->h_total) FH_HIP(hipHostMalloc(reinterpret_cast<void**>(&d->h_total), sizeof(int), hipHostMallocDefault));
-        int* flags = t->t.embed_scratch((size_t)n * F);
-        fh::FaceRec* rec_all = reinterpret_cast<fh::FaceRec*>(all);
-        d->det.detect_dev(frames, n, rows, cols, step, (long)stride, score_thr, nms_thr, rec_all, F, counts, s);
-        t->t.update_dev(rec_all, counts, n, F, stream_of, track, flags, s);
-        fh::launch_track_select(rec_all, flags, track, n, F, reinterpret_cast<fh::FaceRec*>(faces), frame_of, track_of, d->p_total.as<int>(), s);
-        const int total = count_handoff(d, d->p_total.as<int>(), s);
-        r->rec.embed_faces_dev(frames, rows, cols, step, (long)stride, reinterpret_cast<const fh::FaceRec*>(faces), frame_of, total, emb, nullptr, s);
+        int* const flags = t->t.embed_scratch((size_t)n * F);
+        int* const slot = t->t.slot_scratch((size_t)n * F);
+        const int total = pipeline_tracked(d, r, t, frames, n, rows, cols, step, stride, stream_of, score_thr, nms_thr, F, all, counts, track,
+                                           flags, slot, faces, frame_of, track_of, emb, s);
+        t->t.identify_dev(g->g, threshold, track, slot, flags, emb, total, n, F, stream_of, label, score, s);
         return total;
     });
 }

@@ -1285,6 +1285,47 @@ void Tracker::reset(int stream) {
     const std::vector<TrackState> free_slots((size_t)count * p_.max_tracks, TrackState{-1, 0, 0, 0, 0, 0, 0, 0});
     FH_HIP(hipMemset(heads() + 2 * (size_t)first, 0, (size_t)count * 2 * sizeof(int)));
     FH_HIP(hipMemcpy(slots() + (size_t)first * p_.max_tracks, free_slots.data(), free_slots.size() * sizeof(TrackState), hipMemcpyHostToDevice));
+    if (idim_ > 0) clear_identity(first, count);                 // track ids restart at 0: a stale owner must not survive
+}
+
+void Tracker::clear_identity(int first, int count) {
+    const size_t entries = (size_t)count * p_.max_tracks, at = (size_t)first * p_.max_tracks;
+    const std::vector<TrackIdent> none(entries, TrackIdent{-1, 0, -1, -1.0f});
+    FH_HIP(hipMemcpy(ident_.as<TrackIdent>() + at, none.data(), entries * sizeof(TrackIdent), hipMemcpyHostToDevice));
+    FH_HIP(hipMemset(isum_.as<float>() + at * idim_, 0, entries * idim_ * sizeof(float)));
+}
+
+void Tracker::enable_identity(int dim, int pool) {
+    FH_HIP(hipDeviceSynchronize());                              // a queued identify still reads and writes the state
+    const size_t entries = (size_t)streams_ * p_.max_tracks;
+    ident_.ensure(entries * sizeof(TrackIdent));
+    isum_.ensure(entries * dim * sizeof(float));
+    idim_ = dim; ipool_ = pool;
+    clear_identity(0, streams_);
+}
+
+int Tracker::get_identity(int stream, TrackIdent* out, float* sums_out) {
+    FH_HIP(hipDeviceSynchronize());
+    const size_t mt = (size_t)p_.max_tracks, at = (size_t)stream * mt;
+    std::vector<TrackState> all(mt);
+    std::vector<TrackIdent> ident(mt);
+    FH_HIP(hipMemcpy(all.data(), slots() + at, mt * sizeof(TrackState), hipMemcpyDeviceToHost));
+    FH_HIP(hipMemcpy(ident.data(), ident_.as<TrackIdent>() + at, mt * sizeof(TrackIdent), hipMemcpyDeviceToHost));
+    int live = 0;
+    for (size_t i = 0; i < mt; ++i) {
+        if (all[i].id < 0) continue;
+        const bool mine = ident[i].owner == all[i].id;           // else: identify was skipped for this track
+        if (out) out[live] = mine ? TrackIdent{all[i].id, ident[i].n_emb, ident[i].label, ident[i].score} : TrackIdent{all[i].id, 0, -1, -1.0f};
+        if (sums_out) {
+            float* const dst = sums_out + (size_t)live * idim_;
+            if (mine) FH_HIP(hipMemcpy(dst, isum_.as<float>() + (at + i) * idim_, (size_t)idim_ * sizeof(float), hipMemcpyDeviceToHost));
+            else std::fill(dst, dst + idim_, 0.0f);
+        }
+        ++live;
+    }
+    if (out)
+        for (size_t i = (size_t)live; i < mt; ++i) out[i] = TrackIdent{-1, 0, -1, -1.0f};
+    return live;
 }
 
 int Tracker::get_state(int stream, TrackState* out, int* frame_no, int* next_id) {
@@ -1304,12 +1345,41 @@ int Tracker::get_state(int stream, TrackState* out, int* frame_no, int* next_id)
 }
 
 void Tracker::update_dev(const FaceRec* det, const int* counts, int n, int per_frame, const int* stream_of, int* track, int* embed,
-                         hipStream_t s) {
+                         int* slot, hipStream_t s) {
     const size_t bytes = ((size_t)n + streams_ + 1) * sizeof(int);
     int* order = static_cast<int*>(plan_.stage(bytes));
     if (track_plan(stream_of, n, streams_, order, order + n) != 0) throw std::runtime_error("tracker: bad stream_of");   // (checked by the caller)
     const int* d_order = static_cast<const int*>(plan_.send(bytes, s));
-    launch_track_update(heads(), slots(), streams_, p_, det, counts, per_frame, d_order, d_order + n, track, embed, s);
+    launch_track_update(heads(), slots(), streams_, p_, det, counts, per_frame, d_order, d_order + n, track, embed, slot, s);
+    FH_HIP(hipGetLastError());
+}
+
+// Pool first, label the whole batch of queries, propagate afterwards: the gallery scan wants every query of the call at once, and only
+// the per-slot chains of stages A and C are serial.
+void Tracker::identify_dev(Gallery& g, float thr, const int* track, const int* slot, const int* embed, const float* emb, int total, int n,
+                           int per_frame, const int* stream_of, int* label, float* score, hipStream_t s) {
+    const size_t bytes = ((size_t)n + streams_ + 1) * sizeof(int);
+    int* order = static_cast<int*>(iplan_.stage(bytes));
+    if (track_plan(stream_of, n, streams_, order, order + n) != 0) throw std::runtime_error("tracker: bad stream_of");   // (checked by the caller)
+    const size_t rows = (size_t)std::max(total, 1);
+    queries_.ensure(rows * idim_ * sizeof(float));
+    ans_label_.ensure(rows * sizeof(int));
+    ans_score_.ensure(rows * sizeof(float));
+    frame_off_.ensure(((size_t)n + 1) * sizeof(int));
+    const int* d_order = static_cast<const int*>(iplan_.send(bytes, s));
+    launch_track_ranks(embed, n, per_frame, frame_off_.as<int>(), s);
+    launch_track_pool(ident_.as<TrackIdent>(), isum_.as<float>(), streams_, p_.max_tracks, idim_, ipool_, track, slot, embed,
+                      frame_off_.as<int>(), emb, total, per_frame, d_order, d_order + n, queries_.as<float>(), s);
+    FH_HIP(hipGetLastError());
+    const bool ids = g.labelled() && g.size() > 0;               // labels are identity ids / row indices
+    for (int c0 = 0; c0 < total; c0 += 256) {
+        const int Q = std::min(256, total - c0);
+        const float* q = queries_.as<float>() + (size_t)c0 * idim_;
+        if (ids) g.label_ids_dev(q, Q, thr, ans_label_.as<int>() + c0, ans_score_.as<float>() + c0, s);
+        else g.label_dev(q, Q, thr, ans_label_.as<int>() + c0, ans_score_.as<float>() + c0, s);
+    }
+    launch_track_propagate(ident_.as<TrackIdent>(), streams_, p_.max_tracks, track, slot, embed, frame_off_.as<int>(), ans_label_.as<int>(),
+                           ans_score_.as<float>(), total, per_frame, d_order, d_order + n, label, score, s);
     FH_HIP(hipGetLastError());
 }
 

@@ -284,7 +284,9 @@ class Recognizer {
 
 // The face tracker behind fh_tracker (include/facehip.h): per stream a (frame_no, next_id) head and max_tracks slots, resident on the
 // device; one wave per stream updates them (track.hip).  The walk order of a call is planned on the host (track_plan.h) and sent
-// through a StagedTable, so the next call may follow at once with another stream_of.
+// through a StagedTable, so the next call may follow at once with another stream_of.  Identity (enable_identity; track_ident.hip): one
+// TrackIdent and one fp32 sum row per (stream, slot), pooled, labelled against a gallery and carried forward by identify_dev.
+class Gallery;
 class Tracker {
   public:
     Tracker(int streams, int max_tracks, float iou_thr, int max_missed, int refresh);
@@ -294,17 +296,33 @@ class Tracker {
     // live slots of one stream, ascending, into out[max_tracks] (the rest: id = -1); returns their number; synchronous
     int get_state(int stream, TrackState* out, int* frame_no, int* next_id);
     // stream_of: HOST [n], already checked against [0, streams) (null: all stream 0).  track / embed = device [n][per_frame].
-    void update_dev(const FaceRec* det, const int* counts, int n, int per_frame, const int* stream_of, int* track, int* embed,
+    // slot (optional) = device [n][per_frame]: the lane of each detection's track, else -1.
+    void update_dev(const FaceRec* det, const int* counts, int n, int per_frame, const int* stream_of, int* track, int* embed, int* slot,
                     hipStream_t s);
     int* embed_scratch(size_t entries) { embed_.ensure(entries * sizeof(int)); return embed_.as<int>(); }   // the pipeline's flags
+    int* slot_scratch(size_t entries) { slot_.ensure(entries * sizeof(int)); return slot_.as<int>(); }      // ... and its slots
+    // identity: dim % 64 == 0, 64 <= dim <= 4096, pool 0 (last) / 1 (sum), checked by the caller; synchronous; clears on every call
+    void enable_identity(int dim, int pool);
+    int identity_dim() const { return idim_; }                   // 0: not enabled
+    // stages A (pool), B (label through g, chunks of <= 256 queries) and C (propagate) on s; arguments checked by the caller
+    void identify_dev(Gallery& g, float thr, const int* track, const int* slot, const int* embed, const float* emb, int total, int n,
+                      int per_frame, const int* stream_of, int* label, float* score, hipStream_t s);
+    const float* queries() const { return queries_.as<float>(); }   // [total][dim] of the last identify_dev
+    // the live slots' identities, ascending, into out[max_tracks] (the rest: id = -1) and their sums into sums_out[max_tracks][dim]
+    // (may be null); returns their number; synchronous
+    int get_identity(int stream, TrackIdent* out, float* sums_out);
 
   private:
     int* heads() const { return state_.as<int>(); }
     TrackState* slots() const { return reinterpret_cast<TrackState*>(state_.as<int>() + 2 * (size_t)streams_); }
     int streams_;
     TrackParams p_;
-    DevBuf state_, embed_;                                       // [streams][2] heads, then [streams][max_tracks] slots
-    StagedTable plan_;                                           // order[n], then starts[streams + 1]
+    DevBuf state_, embed_, slot_;                                // [streams][2] heads, then [streams][max_tracks] slots
+    StagedTable plan_, iplan_;                                   // order[n], then starts[streams + 1] (update's / identify's)
+    void clear_identity(int first, int count);
+    int idim_ = 0, ipool_ = 0;
+    DevBuf ident_, isum_;                                        // [streams][max_tracks] TrackIdent / [streams][max_tracks][idim_] sums
+    DevBuf queries_, ans_label_, ans_score_, frame_off_;         // of one identify_dev: [total][idim_], [total], [total], [n + 1]
 };
 
 class Gallery {

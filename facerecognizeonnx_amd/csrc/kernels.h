@@ -408,11 +408,28 @@ struct TrackParams {
     int max_missed, refresh;
 };
 // One wave per stream walks starts[s] .. starts[s + 1] of `order` (track_plan.h).  heads = [streams][2] (frame_no, next_id), slots =
-// [streams][max_tracks].  det = [n][per_frame] records, counts = [n]; track / embed = [n][per_frame] are written entirely.
+// [streams][max_tracks].  det = [n][per_frame] records, counts = [n]; track / embed = [n][per_frame] are written entirely, and so is
+// slot (the lane of the detection's track, else -1) unless it is null.
 void launch_track_update(int* heads, TrackState* slots, int streams, TrackParams p, const FaceRec* det, const int* counts, int per_frame,
-                         const int* order, const int* starts, int* track, int* embed, hipStream_t s);
+                         const int* order, const int* starts, int* track, int* embed, int* slot, hipStream_t s);
 // the flagged twin of launch_select_faces: the records with embed != 0, densely in (frame, slot) order, with frame index and track id
 void launch_track_select(const FaceRec* det, const int* embed, const int* track, int n, int per_frame, FaceRec* faces, int* frame_of,
                          int* track_of, int* total, hipStream_t s);
+
+// Per-track identity (track_ident.hip).  One TrackIdent (layout of fh_track_ident, 16 B) and one fp32 sum row [dim] per (stream, slot).
+struct TrackIdent {
+    int32_t owner, n_emb, label;    // owner = the track id the entry belongs to, -1: none
+    float score;
+};
+// frame_off[n + 1] = the exclusive prefix of the frames' flag counts: the rank of a flagged entry is frame_off[f] + the flags before it
+void launch_track_ranks(const int* embed, int n, int per_frame, int* frame_off, hipStream_t s);
+// stage A: one wave per (stream, slot), one more per stream for the untracked faces; writes queries[min(total, flags)][dim]
+void launch_track_pool(TrackIdent* ident, float* sums, int streams, int max_tracks, int dim, int pool_sum, const int* track, const int* slot,
+                       const int* embed, const int* frame_off, const float* emb, int total, int per_frame, const int* order, const int* starts,
+                       float* queries, hipStream_t s);
+// stage C: one wave per stream; ans_label / ans_score = [total] answers of the queries; label / score = [n][per_frame], written entirely
+void launch_track_propagate(TrackIdent* ident, int streams, int max_tracks, const int* track, const int* slot, const int* embed,
+                            const int* frame_off, const int* ans_label, const float* ans_score, int total, int per_frame, const int* order,
+                            const int* starts, int* label, float* score, hipStream_t s);
 
 }  // namespace fh

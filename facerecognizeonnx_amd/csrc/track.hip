@@ -22,12 +22,13 @@ __device__ __forceinline__ unsigned ordered_bits(float v) {
 // winner is the largest (iou, then smaller id) — found by a 64-lane butterfly on (ordered iou bits, 0x7fffffff - id) when more than
 // one slot qualifies — and an unmatched detection opens the lowest free slot (__ballot + find-first-set).  Every branch below that
 // contains a cross-lane operation is taken by the whole wave: its condition comes from a ballot, a shuffle or a kernel argument.
-// No atomics: a stream belongs to one wave.
+// No atomics: a stream belongs to one wave.  slot (optional, [n][per_frame]): the lane that holds the detection's track, -1 for an untracked
+// detection and for the entries behind the count — what the identity step (track_ident.hip) keys its per-slot state by.
 // ------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(64) void track_update_kernel(int* __restrict__ heads, TrackState* __restrict__ slots, TrackParams p,
                                                           const FaceRec* __restrict__ det, const int* __restrict__ counts, int per_frame,
                                                           const int* __restrict__ order, const int* __restrict__ starts,
-                                                          int* __restrict__ track, int* __restrict__ embed) {
+                                                          int* __restrict__ track, int* __restrict__ embed, int* __restrict__ slot) {
     __shared__ int4 sbox[64];
     const int s = blockIdx.x, lane = threadIdx.x;
     const int b = starts[s], e = starts[s + 1];
@@ -86,6 +87,7 @@ __global__ __launch_bounds__(64) void track_update_kernel(int* __restrict__ head
                             if (again) st.last_embed = t;
                             track[o] = st.id;
                             embed[o] = again;
+                            if (slot) slot[o] = lane;
                         }
                     } else {
                         // 3. open: the lowest free slot, or untracked (and embedded, as the reference embeds every face)
@@ -96,17 +98,23 @@ __global__ __launch_bounds__(64) void track_update_kernel(int* __restrict__ head
                                 taken = true;
                                 track[o] = next_id;
                                 embed[o] = 1;
+                                if (slot) slot[o] = lane;
                             }
                             ++next_id;
                         } else if (lane == 0) {
                             track[o] = -1;
                             embed[o] = 1;
+                            if (slot) slot[o] = -1;
                         }
                     }
                 }
             }
             // 4. close the frame
-            for (int j = c + lane; j < per_frame; j += 64) { track[row + j] = -1; embed[row + j] = 0; }
+            for (int j = c + lane; j < per_frame; j += 64) {
+                track[row + j] = -1;
+                embed[row + j] = 0;
+                if (slot) slot[row + j] = -1;
+            }
             ++t;
         }
     }
@@ -115,9 +123,9 @@ __global__ __launch_bounds__(64) void track_update_kernel(int* __restrict__ head
 }
 
 void launch_track_update(int* heads, TrackState* slots, int streams, TrackParams p, const FaceRec* det, const int* counts, int per_frame,
-                         const int* order, const int* starts, int* track, int* embed, hipStream_t s) {
+                         const int* order, const int* starts, int* track, int* embed, int* slot, hipStream_t s) {
     hipLaunchKernelGGL(track_update_kernel, dim3(streams), dim3(64), 0, s, heads, slots, p, det, counts, per_frame, order, starts, track,
-                       embed);
+                       embed, slot);
 }
 
 // ------------------------------------------------------------------------------------------

@@ -321,6 +321,59 @@ FH_API int fh_pipeline_run_tracked_dev(fh_det* d, fh_rec* r, fh_tracker* t, cons
                                        fh_face* d_all /*[n][F]*/, int* d_counts /*[n]*/, int* d_track /*[n][F]*/, fh_face* d_faces,
                                        int* d_frame_of, int* d_track_of, float* d_emb, void* stream);
 
+/* ---- track identity: a label and a similarity for EVERY face of EVERY frame, what the webcam loop (src/main.cpp:221-238: embed each
+ * face, compare, "Match" / "Unknown") produces, from one recogniser run per track.  Each track keeps a running template (the sum of its
+ * embeddings, in time order); each newly embedded face is labelled against a gallery THROUGH its track's pooled template, and the answer
+ * is carried on the device to every later face of the track until the next refresh replaces it.  Everything but the float normalisation
+ * is defined to the bit.
+ *
+ * fh_track_update_slots_dev  fh_track_update_dev with a third output (fh_track_update_dev is this call with d_slot = NULL; one kernel):
+ *   d_slot[f][j] = the slot (lane) that holds the detection's track for a matched or opened detection, -1 for an untracked one and for
+ *   j >= c.  All other outputs and the state are bit for bit fh_track_update_dev's.
+ * fh_tracker_enable_identity  synchronous; needs dim % 64 == 0, 64 <= dim <= 4096 and a known pool mode (else FH_ERR_ARG, nothing
+ *   changes); allocates, per (stream, slot): owner (a track id, -1: none), n_emb, label, score and sum[dim] in fp32.  A second call clears
+ *   and re-sizes.  fh_tracker_reset(stream) clears the identity state of that stream too (track ids restart at 0 there).
+ * fh_track_identify_dev  called once after each update, in the updates' order and with their stream_of.  d_emb = [total][dim], 16-byte
+ *   aligned; row e belongs to the e-th flagged entry (d_embed != 0) in (frame, slot) order — the order fh_track_select_dev writes — and
+ *   total is that call's d_total.  A flagged entry of rank >= total is never read, answers (-1, -1.0f) and leaves the state alone.  Three
+ *   stages, asynchronous on `stream`:
+ *   A. pool   the flagged faces of a stream in time order (fh_track_plan; j ascending within a frame); face e with tid = d_track, slot =
+ *             d_slot.  slot < 0 (untracked): the query q_e is emb_e verbatim, no state changes.  owner[slot] != tid: the slot is
+ *             (re)opened — owner = tid, n_emb = 1, sum = emb_e, q_e = emb_e verbatim (the same bits, not re-normalised).  Otherwise
+ *             n_emb += 1 and, FH_TRACK_POOL_SUM: sum = sum + emb_e (one fp32 add per component, strictly in time order), q_e =
+ *             FaceRecognizer::normalize of sum (src/face_recognizer.cpp:306-318: sum / sqrt(sum of squares) when that is > 0, else sum as
+ *             it is); FH_TRACK_POOL_LAST: sum = emb_e, q_e = emb_e verbatim.  fh_tracker_queries_dev returns the [total][dim] queries
+ *             (a stage hook; valid until the next identify call on the handle).
+ *   B. label  the queries, in chunks of at most 256, through fh_gallery_label_ids_dev (a labelled gallery: labels are identity ids) or
+ *             fh_gallery_label_dev (labels are row indices): strict > threshold; an empty gallery answers (-1, -1.0f).
+ *   C. carry  frames in time order; a flagged entry takes its query's answer, which — if slot >= 0 — also becomes the slot's (label,
+ *             score) with owner = tid; an unflagged entry with slot >= 0 gets the slot's current (label, score) (so a track whose
+ *             identify call was skipped or cut short by `total` shows what the slot last held); every other entry gets (-1, -1.0f).
+ *   FH_ERR_ARG before anything is launched, no state changes: a NULL tracker, gallery or buffer (d_emb may be NULL only when total == 0),
+ *   identity not enabled, the gallery's dim != the identity dim, total < 0 or > n * per_frame, and fh_track_update_dev's batch checks.
+ * fh_tracker_get_identity  synchronous; the live slots, ascending, in the positions of fh_tracker_get_state (the rest: id = -1), their
+ *   sums into sums_out[max_tracks][dim] (may be NULL); returns their number.  A live slot whose identity owner is not its track id —
+ *   identify was skipped for it — reports n_emb = 0, label = -1, score = -1.0f (and a zero sum).
+ * fh_pipeline_run_identified_dev  fh_pipeline_run_tracked_dev (the same hand-off, the same return value, every output bit for bit) with
+ *   the update reporting slots into a buffer of the tracker's, then fh_track_identify_dev on d_emb; the recogniser's feature dim must
+ *   be the identity dim (FH_ERR_ARG).  The ragged, tiled, two-stream and fh_stream forms have no identified twin either. */
+enum fh_track_pool { FH_TRACK_POOL_LAST = 0, FH_TRACK_POOL_SUM = 1 };
+typedef struct fh_track_ident { int32_t id, n_emb, label; float score; } fh_track_ident;   /* 16 bytes */
+FH_API int fh_track_update_slots_dev(fh_tracker* t, const fh_face* d_det, const int* d_counts, int n, int per_frame, const int* stream_of,
+                                     int* d_track, int* d_embed, int* d_slot /*[n][per_frame] or NULL*/, void* stream);
+FH_API int fh_tracker_enable_identity(fh_tracker* t, int dim, int pool);
+FH_API int fh_track_identify_dev(fh_tracker* t, fh_gallery* g, float threshold, const int* d_track, const int* d_slot, const int* d_embed,
+                                 const float* d_emb, int total, int n, int per_frame, const int* stream_of /*HOST [n] or NULL*/,
+                                 int* d_label /*[n][per_frame]*/, float* d_score /*[n][per_frame]*/, void* stream);
+FH_API const float* fh_tracker_queries_dev(fh_tracker* t);
+FH_API int fh_tracker_get_identity(fh_tracker* t, int stream, fh_track_ident* host_out /*[max_tracks]*/,
+                                   float* sums_out /*[max_tracks][dim] or NULL*/);
+FH_API int fh_pipeline_run_identified_dev(fh_det* d, fh_rec* r, fh_tracker* t, fh_gallery* g, float threshold, const uint8_t* d_frames, int n,
+                                          int rows, int cols, int step, long long frame_stride, const int* stream_of, float score_thr,
+                                          float nms_thr, int faces_per_frame, fh_face* d_all, int* d_counts, int* d_track, fh_face* d_faces,
+                                          int* d_frame_of, int* d_track_of, float* d_emb, int* d_label /*[n][F]*/, float* d_score /*[n][F]*/,
+                                          void* stream);
+
 /* ---- gallery (1:N compareFaces): rows are L2-normalised features; scores are (dot+1)/2. */
 FH_API fh_gallery* fh_gallery_create(int dim);
 FH_API void fh_gallery_destroy(fh_gallery* g);

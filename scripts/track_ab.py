@@ -11,6 +11,10 @@ by round after a warm-up.
   (c) the update call alone (plan copy + track_update_kernel) on the detector's records of the (a) frames, as 1, 16 and 128 streams,
       beside fh_det_detect_batch_dev on the same frames in the same run.
 
+  (d) identity: the video of (b) and a gallery of 10 000 rows; fh_pipeline_run_tracked_dev (the parent commit's path, unchanged) beside
+      fh_pipeline_run_identified_dev with refresh 0 and 8, and — the serial chain at its worst — the update with slots alone beside
+      update + fh_track_identify_dev on one stream with refresh 1, where every face of every frame is pooled into its track's sum.
+
 Writes --md (default profiles/track_ab.md) and prints one JSON line per case.  Needs a GPU; there is no fallback."""
 import argparse
 import json
@@ -24,7 +28,7 @@ ap.add_argument("--warmup", type=int, default=20)
 ap.add_argument("--steps", type=int, default=100, help="timed steps per leg (at least)")
 ap.add_argument("--rounds", type=int, default=5)
 ap.add_argument("--block", type=int, default=5, help="steps per HIP-event sample")
-ap.add_argument("--cases", nargs="+", default=["a", "b", "c"])
+ap.add_argument("--cases", nargs="+", default=["a", "b", "c", "d"])
 ap.add_argument("--md", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "track_ab.md"))
 a = ap.parse_args()
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -37,6 +41,7 @@ from facerecognizeonnx_amd.synth import models  # noqa: E402
 
 THR, NMS, F, HW = 0.5, 0.4, 8, 640
 IOU_THR, MAX_TRACKS = 0.3, 64
+GALLERY_ROWS, ID_THRESHOLD = 10000, 0.6
 
 
 def samples(step, steps, block):
@@ -134,6 +139,54 @@ def main():
         out["c"] = {"frames": B, "faces_in_records": int(torch.clamp(counts, 0, F).sum().item()), **st}
         print(json.dumps({"case": "c", **out["c"]}), flush=True)
 
+    if "d" in a.cases:
+        gal = fa.Gallery(512)
+        g = rng.standard_normal((GALLERY_ROWS, 512), dtype=np.float32)
+        gal.enroll(g / np.linalg.norm(g, axis=1, keepdims=True))
+        label = torch.zeros((B, F), **i32); score = torch.zeros((B, F), device="cuda")
+
+        def identified(data, trk, stream_of):
+            return lambda: fa.pipeline_run_identified_dev(det, rec, trk, gal, ID_THRESHOLD, data.data_ptr(), B, HW, HW, F, all_.data_ptr(),
+                                                          counts.data_ptr(), track.data_ptr(), faces.data_ptr(), frame_of.data_ptr(),
+                                                          track_of.data_ptr(), emb.data_ptr(), label.data_ptr(), score.data_ptr(), stream_of,
+                                                          THR, NMS, stream)
+        out["d"] = {"pipeline": {}}
+        for streams in (1, 16):
+            if B % streams:
+                continue
+            stream_of = np.tile(np.arange(streams, dtype=np.int32), B // streams)
+            data = distinct[torch.from_numpy(stream_of.astype(np.int64)).cuda()].contiguous()
+            legs = {}
+            for r in (0, 8):
+                legs[f"tracked_refresh{r}"] = tracked(data, fa.Tracker(streams, MAX_TRACKS, IOU_THR, 0, r), stream_of)
+                t = fa.Tracker(streams, MAX_TRACKS, IOU_THR, 0, r)
+                t.enable_identity(512)
+                legs[f"identified_refresh{r}"] = identified(data, t, stream_of)
+            st, fc, first = ab(legs, a.warmup, a.steps, a.rounds, a.block)
+            out["d"]["pipeline"][f"{streams}x{B // streams}"] = {"faces_per_step": fc, "faces_first_step": first, **st}
+            del data
+        # the serial chain: one camera shows one frame, refresh 1 -> every face is flagged and pooled, 128 adds deep per slot and call
+        one = distinct[:1].expand(B, HW, HW, 3).contiguous()
+        det.detect_batch_dev(one.data_ptr(), B, HW, HW, all_.data_ptr(), F, counts.data_ptr(), THR, NMS, stream=stream)
+        torch.cuda.synchronize()
+        flagged = int(torch.clamp(counts, 0, F).sum().item())
+        embed = torch.zeros((B, F), **i32); slot = torch.zeros((B, F), **i32)
+        rows = torch.nn.functional.normalize(torch.randn((max(flagged, 1), 512), device="cuda"), dim=1)
+        t_upd, t_id = fa.Tracker(1, MAX_TRACKS, IOU_THR, 0, 1), fa.Tracker(1, MAX_TRACKS, IOU_THR, 0, 1)
+        t_id.enable_identity(512)
+
+        def update(t):
+            return t.update_dev(all_.data_ptr(), counts.data_ptr(), B, F, track.data_ptr(), embed.data_ptr(), stream=stream,
+                                slot_ptr=slot.data_ptr())
+
+        def update_identify():
+            update(t_id)
+            return t_id.identify_dev(gal, ID_THRESHOLD, track.data_ptr(), slot.data_ptr(), embed.data_ptr(), rows.data_ptr(), flagged, B, F,
+                                     label.data_ptr(), score.data_ptr(), stream=stream)
+        st, _, _ = ab({"update_slots": lambda: update(t_upd), "update_slots_identify": update_identify}, a.warmup, a.steps, a.rounds, a.block)
+        out["d"]["chain"] = {"frames": B, "faces_pooled_per_call": flagged, **st}
+        print(json.dumps({"case": "d", **out["d"]}), flush=True)
+
     if a.md and out:
         write_md(out)
 
@@ -172,6 +225,21 @@ def write_md(out):
             if k.startswith("update_"):
                 L.append(f"| {k.replace('_', ' ')} | {fmt(s)} | {100 * s['median_ms'] / det_ms:.1f} % |")
         L += [f"| `fh_det_detect_batch_dev`, same frames, same run | {fmt(d['detector'])} | |", ""]
+    if "d" in out:
+        L += [f"## (d) identity: a label for every face, against a gallery of {GALLERY_ROWS} rows", "",
+              "The video of (b); `fh_pipeline_run_tracked_dev` is the parent commit's path, `fh_pipeline_run_identified_dev` adds the slots, "
+              "the pooling, the 1:N label and the carry.", "",
+              "| streams x frames | leg | ms per step | faces embedded per step | ... on the first step |", "|---|---|---|---|---|"]
+        for shape, d in out["d"]["pipeline"].items():
+            for k in d["faces_per_step"]:
+                L.append(f"| {shape} | `fh_pipeline_run_{k.split('_')[0]}_dev`, refresh {k[-1]} | {fmt(d[k])} | {d['faces_per_step'][k]} | "
+                         f"{d['faces_first_step'][k]} |")
+        c = out["d"]["chain"]
+        L += ["", f"The serial chain at its worst: one camera, {c['frames']} frames, refresh 1, so all {c['faces_pooled_per_call']} faces of a "
+              "call are pooled (each slot's sum takes one 2 KB read-add-write per frame) and labelled.", "",
+              "| leg | ms per call |", "|---|---|",
+              f"| `fh_track_update_slots_dev` | {fmt(c['update_slots'])} |",
+              f"| `fh_track_update_slots_dev` + `fh_track_identify_dev` | {fmt(c['update_slots_identify'])} |", ""]
     os.makedirs(os.path.dirname(os.path.abspath(a.md)), exist_ok=True)
     with open(a.md, "w") as f:
         f.write("\n".join(L))
