@@ -45,7 +45,7 @@ assert TRACK_DTYPE.itemsize == 32
 TRACK_MAX = 64                                                 # FH_TRACK_MAX
 TRACK_IDENT_DTYPE = np.dtype([("id", "<i4"), ("n_emb", "<i4"), ("label", "<i4"), ("score", "<f4")])     # fh_track_ident
 assert TRACK_IDENT_DTYPE.itemsize == 16
-TRACK_POOL_LAST, TRACK_POOL_SUM = 0, 1                         # enum fh_track_pool
+TRACK_POOL_LAST, TRACK_POOL_SUM, TRACK_POOL_WEIGHTED = 0, 1, 2    # enum fh_track_pool
 
 
 class FhTrackState(C.Structure):
@@ -149,6 +149,13 @@ PROTOTYPES = {
     "fh_tracker_get_identity": (_i, [_vp, _i, _vp, _vp]),
     "fh_pipeline_run_identified_dev": (_i, [_vp, _vp, _vp, _vp, _f, _vp, _i, _i, _i, _i, _ll, _vp, _f, _f, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                             _vp, _vp, _vp]),
+    "fh_face_quality_dev": (_i, [_vp, _i, _i, _i, _i, _ll, _vp, _vp, _i, _vp, _vp]),
+    "fh_face_quality_ragged_dev": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp]),
+    "fh_tracker_set_bestshot": (_i, [_vp, _i, _i, _i, _i]),
+    "fh_tracker_get_quality": (_i, [_vp, _i, _vp]),
+    "fh_tracker_quality_dev": (_vp, [_vp]),
+    "fh_track_update_q_dev": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "fh_track_identify_q_dev": (_i, [_vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "fh_gallery_create": (_vp, [_i]),
     "fh_gallery_destroy": (None, [_vp]),
     "fh_gallery_upload": (_i, [_vp, _vp, _ll, _i, _ll]),

@@ -344,6 +344,21 @@ def track_plan(stream_of, streams: int):
     return order[:a.size].copy(), starts
 
 
+def face_quality_dev(frames, det_ptr: int, counts_ptr: int, per_frame: int, quality_ptr: int, n: Optional[int] = None,
+                     rows: Optional[int] = None, cols: Optional[int] = None, step: Optional[int] = None, stream: int = 0) -> int:
+    """The quality score of every detected face (include/facehip.h, "face quality") into quality_ptr = int32 [n][per_frame]; entries
+    behind a frame's count get 0.  frames = a device pointer of n uniform frames of rows x cols (row pitch step, default cols * 3; the
+    frames follow each other at rows * step) — or, with n = None, frames of any sizes as FaceDetector.detect_ragged_dev takes them
+    (fh_face_quality_ragged_dev)."""
+    if n is None:
+        arr = frame_array(frames)
+        return check(_lib.lib().fh_face_quality_ragged_dev(arr, _frame_count(arr), det_ptr, counts_ptr, per_frame, quality_ptr, stream),
+                     "fh_face_quality_ragged_dev")
+    step = cols * 3 if step is None else step
+    return check(_lib.lib().fh_face_quality_dev(frames, n, rows, cols, step, rows * step, det_ptr, counts_ptr, per_frame, quality_ptr,
+                                                stream), "fh_face_quality_dev")
+
+
 class Tracker:
     """fh_tracker: device-resident face tracks per camera stream (include/facehip.h, "face tracker").  `refresh` = 0 embeds a track
     once, when it opens; k > 0 again every k frames.  A track survives `max_missed` consecutive frames without a detection."""
@@ -367,28 +382,58 @@ class Tracker:
         return self._h
 
     def update_dev(self, det_ptr: int, counts_ptr: int, n: int, per_frame: int, track_ptr: int, embed_ptr: int, stream_of=None,
-                   stream: int = 0, slot_ptr=None) -> int:
+                   stream: int = 0, slot_ptr=None, quality_ptr=None) -> int:
         """Steps 1-4 of the contract on n frames of [per_frame] records; writes track ids and embed flags [n][per_frame] — and, with
-        slot_ptr, the slot of each detection's track (fh_track_update_slots_dev), which identify_dev needs."""
+        slot_ptr, the slot of each detection's track (fh_track_update_slots_dev), which identify_dev needs.  quality_ptr = the faces'
+        qualities [n][per_frame] (face_quality_dev): what the best-shot policy decides by (fh_track_update_q_dev)."""
         keep, sp = _stream_of(stream_of, n)
+        if quality_ptr is not None:
+            return check(_lib.lib().fh_track_update_q_dev(self._h, det_ptr, counts_ptr, n, per_frame, sp, track_ptr, embed_ptr, slot_ptr,
+                                                          quality_ptr, stream), "fh_track_update_q_dev")
         if slot_ptr is None:
             return check(_lib.lib().fh_track_update_dev(self._h, det_ptr, counts_ptr, n, per_frame, sp, track_ptr, embed_ptr, stream),
                          "fh_track_update_dev")
         return check(_lib.lib().fh_track_update_slots_dev(self._h, det_ptr, counts_ptr, n, per_frame, sp, track_ptr, embed_ptr, slot_ptr,
                                                           stream), "fh_track_update_slots_dev")
 
+    def set_bestshot(self, num: int = 5, den: int = 4, min_gap: int = 1) -> None:
+        """Switch the best-shot policy on: a track is embedded again when its face's quality q has become better than the best one
+        embedded so far by more than num / den (q * den > best_q * num) and min_gap frames or more have passed since its last
+        embedding.  Clears the per-slot best qualities."""
+        check(_lib.lib().fh_tracker_set_bestshot(self._h, 1, int(num), int(den), int(min_gap)), "fh_tracker_set_bestshot")
+
+    def clear_bestshot(self) -> None:
+        """Switch the best-shot policy off (and clear the per-slot best qualities)."""
+        check(_lib.lib().fh_tracker_set_bestshot(self._h, 0, 1, 1, 1), "fh_tracker_set_bestshot")
+
+    def best_quality(self, stream: int = 0) -> np.ndarray:
+        """The best embedded quality of the live slots of one stream, ascending (the positions of state()), int32."""
+        out = np.zeros(self.max_tracks, np.int32)
+        live = check(_lib.lib().fh_tracker_get_quality(self._h, int(stream), out.ctypes.data), "fh_tracker_get_quality")
+        return out[:live].copy()
+
+    def quality_ptr(self) -> int:
+        """Device pointer of the [n][F] qualities of the last pipeline call with the best-shot policy on (a stage hook for tests)."""
+        return _lib.lib().fh_tracker_quality_dev(self._h) or 0
+
     def enable_identity(self, dim: int, pool: int = _lib.TRACK_POOL_SUM) -> None:
         """Allocate (or clear and re-size) the per-track identity state: a running template of `dim` floats per track slot, pooled as
-        the sum of the track's embeddings (TRACK_POOL_SUM) or just the latest one (TRACK_POOL_LAST)."""
+        the sum of the track's embeddings (TRACK_POOL_SUM), that sum weighted by the faces' qualities (TRACK_POOL_WEIGHTED; only after
+        set_bestshot() or clear_bestshot() has opted the tracker into the quality feature) or just the latest one (TRACK_POOL_LAST)."""
         check(_lib.lib().fh_tracker_enable_identity(self._h, int(dim), int(pool)), "fh_tracker_enable_identity")
         self.identity_dim = int(dim)
 
     def identify_dev(self, gallery, threshold: float, track_ptr: int, slot_ptr: int, embed_ptr: int, emb_ptr, total: int, n: int,
-                     per_frame: int, label_ptr: int, score_ptr: int, stream_of=None, stream: int = 0) -> int:
+                     per_frame: int, label_ptr: int, score_ptr: int, stream_of=None, stream: int = 0, quality_ptr=None) -> int:
         """After update_dev(..., slot_ptr=...) and the embedding of the `total` flagged faces (emb_ptr = [total][dim], in select_dev's
         order): pool each into its track's template, label the templates against `gallery`, and write a label and a score for EVERY
-        entry [n][per_frame] — the faces that were not embedded carry their track's."""
+        entry [n][per_frame] — the faces that were not embedded carry their track's.  quality_ptr = the faces' qualities
+        [n][per_frame], which TRACK_POOL_WEIGHTED needs (fh_track_identify_q_dev)."""
         keep, sp = _stream_of(stream_of, n)
+        if quality_ptr is not None:
+            return check(_lib.lib().fh_track_identify_q_dev(self._h, gallery._h if gallery is not None else None, float(threshold),
+                                                            track_ptr, slot_ptr, embed_ptr, quality_ptr, emb_ptr, int(total), n, per_frame,
+                                                            sp, label_ptr, score_ptr, stream), "fh_track_identify_q_dev")
         return check(_lib.lib().fh_track_identify_dev(self._h, gallery._h if gallery is not None else None, float(threshold), track_ptr,
                                                       slot_ptr, embed_ptr, emb_ptr, int(total), n, per_frame, sp, label_ptr, score_ptr,
                                                       stream), "fh_track_identify_dev")

@@ -19,6 +19,8 @@ static_assert(sizeof(fh_track_state) == sizeof(fh::TrackState) && offsetof(fh_tr
               FH_TRACK_MAX == 64, "fh_track_state mirrors TrackState; one slot per lane of a wave");
 static_assert(sizeof(fh_track_ident) == 16 && sizeof(fh::TrackIdent) == 16 && offsetof(fh_track_ident, score) == offsetof(fh::TrackIdent, score),
               "fh_track_ident mirrors TrackIdent");
+static_assert(FH_TRACK_POOL_LAST == fh::kTrackPoolLast && FH_TRACK_POOL_SUM == fh::kTrackPoolSum && FH_TRACK_POOL_WEIGHTED == fh::kTrackPoolWeighted,
+              "fh_track_pool mirrors the pool kernel's modes");
 static_assert(sizeof(fh_tiling) == sizeof(fh::Tiling) && offsetof(fh_tiling, border) == offsetof(fh::Tiling, border) &&
               sizeof(fh_view) == sizeof(fh::View) && offsetof(fh_view, edges) == offsetof(fh::View, edges) &&
               FH_TILE_MAX_VIEWS == fh::kTileMaxViews && FH_ERR_ARG == fh::kTilePlanBadArg, "fh_tiling / fh_view mirror tile_plan.h");
@@ -899,15 +901,19 @@ int fh_track_plan(const int* stream_of, int n, int streams, int* order, int* sta
         return arg_error("fh_track_plan: need 1 <= n <= 4096, 1 <= streams <= 4096 and every stream index in [0, streams)");
     return 0;
 }
-int fh_track_update_slots_dev(fh_tracker* t, const fh_face* det, const int* counts, int n, int per_frame, const int* stream_of, int* track,
-                              int* embed, int* slot, void* stream) {
-    const char* const fn = slot ? "fh_track_update_slots_dev" : "fh_track_update_dev";
+int fh_track_update_q_dev(fh_tracker* t, const fh_face* det, const int* counts, int n, int per_frame, const int* stream_of, int* track,
+                          int* embed, int* slot, const int* quality, void* stream) {
+    const char* const fn = quality ? "fh_track_update_q_dev" : slot ? "fh_track_update_slots_dev" : "fh_track_update_dev";
     if (!t || !det || !counts || !track || !embed) return frames_error(fn, "null argument");
     if (const char* bad = bad_track_batch(t, n, per_frame, stream_of)) return frames_error(fn, bad);
     return guarded([&] {
-        t->t.update_dev(reinterpret_cast<const fh::FaceRec*>(det), counts, n, per_frame, stream_of, track, embed, slot, S(stream));
+        t->t.update_dev(reinterpret_cast<const fh::FaceRec*>(det), counts, n, per_frame, stream_of, track, embed, slot, quality, S(stream));
         return n;
     });
+}
+int fh_track_update_slots_dev(fh_tracker* t, const fh_face* det, const int* counts, int n, int per_frame, const int* stream_of, int* track,
+                              int* embed, int* slot, void* stream) {
+    return fh_track_update_q_dev(t, det, counts, n, per_frame, stream_of, track, embed, slot, nullptr, stream);
 }
 int fh_track_update_dev(fh_tracker* t, const fh_face* det, const int* counts, int n, int per_frame, const int* stream_of, int* track,
                         int* embed, void* stream) {
@@ -925,7 +931,8 @@ int fh_track_select_dev(const fh_face* det, const int* embed, int n, int per_fra
     });
 }
 // fh_pipeline_run_dev with the tracker between the NMS and the selection: detect -> update -> flagged select -> the one 4-byte
-// hand-off -> align + embed on exactly the flagged faces, all on `stream`.  (slot: null, or the update's third output.)
+// hand-off -> align + embed on exactly the flagged faces, all on `stream`.  (slot: null, or the update's third output.)  With the
+// best-shot policy on, the quality kernel runs between the detector and the update, into the tracker's buffer, and the update reads it.
 namespace {
 int pipeline_tracked(fh_det* d, fh_rec* r, fh_tracker* t, const uint8_t* frames, int n, int rows, int cols, int step, long long stride,
                      const int* stream_of, float score_thr, float nms_thr, int F, fh_face* all, int* counts, int* track, int* flags, int* slot,
@@ -935,7 +942,9 @@ int pipeline_tracked(fh_det* d, fh_rec* r, fh_tracker* t, const uint8_t* frames,
     if (!d->h_total) FH_HIP(hipHostMalloc(reinterpret_cast<void**>(&d->h_total), sizeof(int), hipHostMallocDefault));
     fh::FaceRec* rec_all = reinterpret_cast<fh::FaceRec*>(all);
     d->det.detect_dev(frames, n, rows, cols, step, (long)stride, score_thr, nms_thr, rec_all, F, counts, s);
-    t->t.update_dev(rec_all, counts, n, F, stream_of, track, flags, slot, s);
+    int* const quality = t->t.bestshot() ? t->t.quality_scratch((size_t)n * F) : nullptr;
+    if (quality) fh::launch_face_quality(frames, (long)stride, rows, cols, step, nullptr, n, rec_all, counts, F, quality, s);
+    t->t.update_dev(rec_all, counts, n, F, stream_of, track, flags, slot, quality, s);
     fh::launch_track_select(rec_all, flags, track, n, F, reinterpret_cast<fh::FaceRec*>(faces), frame_of, track_of, d->p_total.as<int>(), s);
     const int total = count_handoff(d, d->p_total.as<int>(), s);
     r->rec.embed_faces_dev(frames, rows, cols, step, (long)stride, reinterpret_cast<const fh::FaceRec*>(faces), frame_of, total, emb, nullptr, s);
@@ -962,24 +971,88 @@ int fh_pipeline_run_tracked_dev(fh_det* d, fh_rec* r, fh_tracker* t, const uint8
     });
 }
 
+// ---------------------------------------------------------------------------------- face quality and the best-shot policy
+namespace {
+const char* bad_quality_batch(const fh_face* det, const int* counts, int n, int per_frame, const int* quality) {
+    if (!det || !counts || !quality) return "null argument";
+    if (n < 1 || n > fh::kTrackMaxFrames) return "need 1 <= n <= 4096 frames";
+    if (per_frame < 1 || (long long)n * per_frame > 0x7fffffffLL) return "need per_frame >= 1 and n * per_frame < 2^31";
+    return nullptr;
+}
+}  // namespace
+int fh_face_quality_dev(const uint8_t* frames, int n, int rows, int cols, int step, long long stride, const fh_face* det, const int* counts,
+                        int per_frame, int* quality, void* stream) {
+    if (const char* bad = bad_quality_batch(det, counts, n, per_frame, quality)) return frames_error("fh_face_quality_dev", bad);
+    if (!frames) return arg_error("fh_face_quality_dev: null argument");
+    if (rows <= 0 || cols <= 0 || step < cols * 3) return arg_error("fh_face_quality_dev: bad size");
+    return guarded([&] {
+        fh::launch_face_quality(frames, (long)stride, rows, cols, step, nullptr, n, reinterpret_cast<const fh::FaceRec*>(det), counts, per_frame,
+                                quality, S(stream));
+        FH_HIP(hipGetLastError());
+        return n;
+    });
+}
+int fh_face_quality_ragged_dev(const fh_frame* frames, int n, const fh_face* det, const int* counts, int per_frame, int* quality, void* stream) {
+    if (const char* bad = bad_frames(frames, n)) return frames_error("fh_face_quality_ragged_dev", bad);
+    if (const char* bad = bad_quality_batch(det, counts, n, per_frame, quality)) return frames_error("fh_face_quality_ragged_dev", bad);
+    return guarded([&] {
+        hipStream_t s = S(stream);
+        // the frame table of this entry point: one per calling thread, and a call on a DIFFERENT stream than the previous one first
+        // waits for that one's kernel (as fh_postprocess_rows_dev's scratch; never destroyed, for the same reason)
+        struct Scratch { fh::FrameTable tab; hipEvent_t done = nullptr; hipStream_t last = nullptr; bool used = false; };
+        thread_local Scratch* scp = new Scratch();
+        Scratch& sc = *scp;
+        if (!sc.done) FH_HIP(hipEventCreateWithFlags(&sc.done, hipEventDisableTiming));
+        if (sc.used && sc.last != s) FH_HIP(hipStreamWaitEvent(s, sc.done, 0));
+        const fh::FrameDesc* table = sc.tab.upload(FI(frames), n, 0, 0, s);
+        fh::launch_face_quality(nullptr, 0, 0, 0, 0, table, n, reinterpret_cast<const fh::FaceRec*>(det), counts, per_frame, quality, s);
+        FH_HIP(hipGetLastError());
+        FH_HIP(hipEventRecord(sc.done, s));
+        sc.last = s; sc.used = true;
+        return n;
+    });
+}
+int fh_tracker_set_bestshot(fh_tracker* t, int on, int num, int den, int min_gap) {
+    if (!t) return arg_error("fh_tracker_set_bestshot: null handle");
+    if (den < 1 || num < den || num > 32768 || min_gap < 1) return arg_error("fh_tracker_set_bestshot: need 1 <= den <= num <= 32768 and min_gap >= 1");
+    return guarded([&] { t->t.set_bestshot(on != 0, num, den, min_gap); return 0; });
+}
+int fh_tracker_get_quality(fh_tracker* t, int stream, int* out) {
+    if (!t || !out) return arg_error("fh_tracker_get_quality: null argument");
+    if (stream < 0 || stream >= t->t.streams()) return arg_error("fh_tracker_get_quality: no such stream");
+    if (!t->t.has_best_quality()) return arg_error("fh_tracker_get_quality: the best-shot policy was never set (fh_tracker_set_bestshot)");
+    return guarded([&] { return t->t.get_quality(stream, out); });
+}
+const int* fh_tracker_quality_dev(fh_tracker* t) { return t ? t->t.quality() : nullptr; }
+
 // ---------------------------------------------------------------------------------- track identity
 int fh_tracker_enable_identity(fh_tracker* t, int dim, int pool) {
     if (!t) return arg_error("fh_tracker_enable_identity: null handle");
     if (dim < 64 || dim > 4096 || dim % 64) return arg_error("fh_tracker_enable_identity: need dim % 64 == 0 and 64 <= dim <= 4096");
-    if (pool != FH_TRACK_POOL_LAST && pool != FH_TRACK_POOL_SUM) return arg_error("fh_tracker_enable_identity: unknown pool mode");
+    // the weighted pool belongs to the quality feature: a tracker takes it only once fh_tracker_set_bestshot has been called on it
+    const bool weighted_ok = pool == FH_TRACK_POOL_WEIGHTED && t->t.has_best_quality();
+    if (pool != FH_TRACK_POOL_LAST && pool != FH_TRACK_POOL_SUM && !weighted_ok)
+        return arg_error("fh_tracker_enable_identity: unknown pool mode (FH_TRACK_POOL_WEIGHTED needs fh_tracker_set_bestshot first)");
     return guarded([&] { t->t.enable_identity(dim, pool); return 0; });
+}
+int fh_track_identify_q_dev(fh_tracker* t, fh_gallery* g, float threshold, const int* track, const int* slot, const int* embed,
+                            const int* quality, const float* emb, int total, int n, int per_frame, const int* stream_of, int* label,
+                            float* score, void* stream) {
+    const char* const fn = quality ? "fh_track_identify_q_dev" : "fh_track_identify_dev";
+    if (!t || !g || !track || !slot || !embed || !label || !score) return frames_error(fn, "null argument");
+    if (const char* bad = bad_track_batch(t, n, per_frame, stream_of)) return frames_error(fn, bad);
+    if (const char* bad = bad_identity(t, g)) return frames_error(fn, bad);
+    if (total < 0 || (long long)total > (long long)n * per_frame) return frames_error(fn, "need 0 <= total <= n * per_frame");
+    if (total > 0 && !emb) return frames_error(fn, "null embeddings with total > 0");
+    if (!quality && t->t.identity_pool() == FH_TRACK_POOL_WEIGHTED) return frames_error(fn, "the weighted pool needs the qualities (fh_track_identify_q_dev)");
+    return guarded([&] {
+        t->t.identify_dev(g->g, threshold, track, slot, embed, quality, emb, total, n, per_frame, stream_of, label, score, S(stream));
+        return n;
+    });
 }
 int fh_track_identify_dev(fh_tracker* t, fh_gallery* g, float threshold, const int* track, const int* slot, const int* embed, const float* emb,
                           int total, int n, int per_frame, const int* stream_of, int* label, float* score, void* stream) {
-    if (!t || !g || !track || !slot || !embed || !label || !score) return arg_error("fh_track_identify_dev: null argument");
-    if (const char* bad = bad_track_batch(t, n, per_frame, stream_of)) return frames_error("fh_track_identify_dev", bad);
-    if (const char* bad = bad_identity(t, g)) return frames_error("fh_track_identify_dev", bad);
-    if (total < 0 || (long long)total > (long long)n * per_frame) return arg_error("fh_track_identify_dev: need 0 <= total <= n * per_frame");
-    if (total > 0 && !emb) return arg_error("fh_track_identify_dev: null embeddings with total > 0");
-    return guarded([&] {
-        t->t.identify_dev(g->g, threshold, track, slot, embed, emb, total, n, per_frame, stream_of, label, score, S(stream));
-        return n;
-    });
+    return fh_track_identify_q_dev(t, g, threshold, track, slot, embed, nullptr, emb, total, n, per_frame, stream_of, label, score, stream);
 }
 const float* fh_tracker_queries_dev(fh_tracker* t) { return t ? t->t.queries() : nullptr; }
 int fh_tracker_get_identity(fh_tracker* t, int stream, fh_track_ident* out, float* sums_out) {
@@ -999,6 +1072,8 @@ int fh_pipeline_run_identified_dev(fh_det* d, fh_rec* r, fh_tracker* t, fh_galle
     if (rows <= 0 || cols <= 0 || step < cols * 3) return arg_error("fh_pipeline_run_identified_dev: bad size");
     if (const char* bad = bad_identity(t, g)) return frames_error("fh_pipeline_run_identified_dev", bad);
     if (r->rec.dim() != t->t.identity_dim()) return arg_error("fh_pipeline_run_identified_dev: the recogniser's feature dim is not the identity dim");
+    if (t->t.identity_pool() == FH_TRACK_POOL_WEIGHTED && !t->t.bestshot())
+        return arg_error("fh_pipeline_run_identified_dev: the weighted pool needs the qualities: set the best-shot policy (fh_tracker_set_bestshot)");
     Owns owns(&d->det.net(), &r->rec.net());
     return guarded([&] {
         hipStream_t s = S(stream);
@@ -1006,7 +1081,8 @@ int fh_pipeline_run_identified_dev(fh_det* d, fh_rec* r, fh_tracker* t, fh_galle
         int* const slot = t->t.slot_scratch((size_t)n * F);
         const int total = pipeline_tracked(d, r, t, frames, n, rows, cols, step, stride, stream_of, score_thr, nms_thr, F, all, counts, track,
                                            flags, slot, faces, frame_of, track_of, emb, s);
-        t->t.identify_dev(g->g, threshold, track, slot, flags, emb, total, n, F, stream_of, label, score, s);
+        t->t.identify_dev(g->g, threshold, track, slot, flags, t->t.bestshot() ? t->t.quality() : nullptr, emb, total, n, F, stream_of, label,
+                          score, s);
         return total;
     });
 }

@@ -1274,7 +1274,7 @@ void Gallery::topk_f32(const float* q, int Q, int k, float* out_score, int* out_
 
 // ------------------------------------------------------------------------------------------ face tracker
 Tracker::Tracker(int streams, int max_tracks, float iou_thr, int max_missed, int refresh)
-    : streams_(streams), p_{max_tracks, iou_thr, max_missed, refresh} {
+    : streams_(streams), p_{max_tracks, iou_thr, max_missed, refresh, 1, 1, 1} {
     state_.ensure((size_t)streams * (2 * sizeof(int) + (size_t)max_tracks * sizeof(TrackState)));
     reset(-1);
 }
@@ -1286,6 +1286,31 @@ void Tracker::reset(int stream) {
     FH_HIP(hipMemset(heads() + 2 * (size_t)first, 0, (size_t)count * 2 * sizeof(int)));
     FH_HIP(hipMemcpy(slots() + (size_t)first * p_.max_tracks, free_slots.data(), free_slots.size() * sizeof(TrackState), hipMemcpyHostToDevice));
     if (idim_ > 0) clear_identity(first, count);                 // track ids restart at 0: a stale owner must not survive
+    if (best_.p) FH_HIP(hipMemset(best_.as<int>() + (size_t)first * p_.max_tracks, 0, (size_t)count * p_.max_tracks * sizeof(int)));
+}
+
+void Tracker::set_bestshot(bool on, int num, int den, int min_gap) {
+    FH_HIP(hipDeviceSynchronize());                              // a queued update still reads and writes best_q
+    const size_t bytes = (size_t)streams_ * p_.max_tracks * sizeof(int);
+    best_.ensure(bytes);
+    FH_HIP(hipMemset(best_.p, 0, bytes));
+    bestshot_ = on;
+    p_.bs_num = num; p_.bs_den = den; p_.bs_gap = min_gap;
+}
+
+int Tracker::get_quality(int stream, int* out) {
+    FH_HIP(hipDeviceSynchronize());
+    const size_t mt = (size_t)p_.max_tracks, at = (size_t)stream * mt;
+    std::vector<TrackState> all(mt);
+    std::vector<int> best(mt);
+    FH_HIP(hipMemcpy(all.data(), slots() + at, mt * sizeof(TrackState), hipMemcpyDeviceToHost));
+    FH_HIP(hipMemcpy(best.data(), best_.as<int>() + at, mt * sizeof(int), hipMemcpyDeviceToHost));
+    int live = 0;
+    for (size_t i = 0; i < mt; ++i)
+        if (all[i].id >= 0) { if (out) out[live] = best[i]; ++live; }
+    if (out)
+        for (size_t i = (size_t)live; i < mt; ++i) out[i] = 0;
+    return live;
 }
 
 void Tracker::clear_identity(int first, int count) {
@@ -1345,19 +1370,20 @@ int Tracker::get_state(int stream, TrackState* out, int* frame_no, int* next_id)
 }
 
 void Tracker::update_dev(const FaceRec* det, const int* counts, int n, int per_frame, const int* stream_of, int* track, int* embed,
-                         int* slot, hipStream_t s) {
+                         int* slot, const int* quality, hipStream_t s) {
     const size_t bytes = ((size_t)n + streams_ + 1) * sizeof(int);
     int* order = static_cast<int*>(plan_.stage(bytes));
     if (track_plan(stream_of, n, streams_, order, order + n) != 0) throw std::runtime_error("tracker: bad stream_of");   // (checked by the caller)
     const int* d_order = static_cast<const int*>(plan_.send(bytes, s));
-    launch_track_update(heads(), slots(), streams_, p_, det, counts, per_frame, d_order, d_order + n, track, embed, slot, s);
+    launch_track_update(heads(), slots(), streams_, p_, det, counts, per_frame, d_order, d_order + n, track, embed, slot,
+                        bestshot_ ? quality : nullptr, bestshot_ ? best_.as<int>() : nullptr, s);
     FH_HIP(hipGetLastError());
 }
 
 // Pool first, label the whole batch of queries, propagate afterwards: the gallery scan wants every query of the call at once, and only
 // the per-slot chains of stages A and C are serial.
-void Tracker::identify_dev(Gallery& g, float thr, const int* track, const int* slot, const int* embed, const float* emb, int total, int n,
-                           int per_frame, const int* stream_of, int* label, float* score, hipStream_t s) {
+void Tracker::identify_dev(Gallery& g, float thr, const int* track, const int* slot, const int* embed, const int* quality, const float* emb,
+                           int total, int n, int per_frame, const int* stream_of, int* label, float* score, hipStream_t s) {
     const size_t bytes = ((size_t)n + streams_ + 1) * sizeof(int);
     int* order = static_cast<int*>(iplan_.stage(bytes));
     if (track_plan(stream_of, n, streams_, order, order + n) != 0) throw std::runtime_error("tracker: bad stream_of");   // (checked by the caller)
@@ -1369,7 +1395,7 @@ void Tracker::identify_dev(Gallery& g, float thr, const int* track, const int* s
     const int* d_order = static_cast<const int*>(iplan_.send(bytes, s));
     launch_track_ranks(embed, n, per_frame, frame_off_.as<int>(), s);
     launch_track_pool(ident_.as<TrackIdent>(), isum_.as<float>(), streams_, p_.max_tracks, idim_, ipool_, track, slot, embed,
-                      frame_off_.as<int>(), emb, total, per_frame, d_order, d_order + n, queries_.as<float>(), s);
+                      quality, frame_off_.as<int>(), emb, total, per_frame, d_order, d_order + n, queries_.as<float>(), s);
     FH_HIP(hipGetLastError());
     const bool ids = g.labelled() && g.size() > 0;               // labels are identity ids / row indices
     for (int c0 = 0; c0 < total; c0 += 256) {

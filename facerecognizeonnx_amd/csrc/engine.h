@@ -285,7 +285,8 @@ class Recognizer {
 // The face tracker behind fh_tracker (include/facehip.h): per stream a (frame_no, next_id) head and max_tracks slots, resident on the
 // device; one wave per stream updates them (track.hip).  The walk order of a call is planned on the host (track_plan.h) and sent
 // through a StagedTable, so the next call may follow at once with another stream_of.  Identity (enable_identity; track_ident.hip): one
-// TrackIdent and one fp32 sum row per (stream, slot), pooled, labelled against a gallery and carried forward by identify_dev.
+// TrackIdent and one fp32 sum row per (stream, slot), pooled, labelled against a gallery and carried forward by identify_dev.  Best
+// shot (set_bestshot): one int32 best_q per (stream, slot), kept by the update kernel when it is given the faces' qualities.
 class Gallery;
 class Tracker {
   public:
@@ -296,17 +297,29 @@ class Tracker {
     // live slots of one stream, ascending, into out[max_tracks] (the rest: id = -1); returns their number; synchronous
     int get_state(int stream, TrackState* out, int* frame_no, int* next_id);
     // stream_of: HOST [n], already checked against [0, streams) (null: all stream 0).  track / embed = device [n][per_frame].
-    // slot (optional) = device [n][per_frame]: the lane of each detection's track, else -1.
+    // slot (optional) = device [n][per_frame]: the lane of each detection's track, else -1.  quality (optional) = device
+    // [n][per_frame]: with the best-shot policy on, the update applies it; null or the policy off: the plain update.
     void update_dev(const FaceRec* det, const int* counts, int n, int per_frame, const int* stream_of, int* track, int* embed, int* slot,
-                    hipStream_t s);
+                    const int* quality, hipStream_t s);
+    // the best-shot policy: 1 <= den <= num <= 32768, min_gap >= 1, checked by the caller; synchronous; clears best_q on every call
+    void set_bestshot(bool on, int num, int den, int min_gap);
+    bool bestshot() const { return bestshot_; }
+    bool has_best_quality() const { return best_.p != nullptr; }     // set_bestshot was called
+    // best_q of the live slots, ascending, into out[max_tracks] (the rest: 0); returns their number; synchronous
+    int get_quality(int stream, int* out);
+    int* quality_scratch(size_t entries) { quality_.ensure(entries * sizeof(int)); return quality_.as<int>(); }   // the pipeline's qualities
+    const int* quality() const { return quality_.as<int>(); }
     int* embed_scratch(size_t entries) { embed_.ensure(entries * sizeof(int)); return embed_.as<int>(); }   // the pipeline's flags
     int* slot_scratch(size_t entries) { slot_.ensure(entries * sizeof(int)); return slot_.as<int>(); }      // ... and its slots
-    // identity: dim % 64 == 0, 64 <= dim <= 4096, pool 0 (last) / 1 (sum), checked by the caller; synchronous; clears on every call
+    // identity: dim % 64 == 0, 64 <= dim <= 4096, pool 0 (last) / 1 (sum) / 2 (quality-weighted sum), checked by the caller;
+    // synchronous; clears on every call
     void enable_identity(int dim, int pool);
     int identity_dim() const { return idim_; }                   // 0: not enabled
-    // stages A (pool), B (label through g, chunks of <= 256 queries) and C (propagate) on s; arguments checked by the caller
-    void identify_dev(Gallery& g, float thr, const int* track, const int* slot, const int* embed, const float* emb, int total, int n,
-                      int per_frame, const int* stream_of, int* label, float* score, hipStream_t s);
+    int identity_pool() const { return ipool_; }
+    // stages A (pool), B (label through g, chunks of <= 256 queries) and C (propagate) on s; arguments checked by the caller.  quality =
+    // device [n][per_frame], needed (and read) by the weighted pool only.
+    void identify_dev(Gallery& g, float thr, const int* track, const int* slot, const int* embed, const int* quality, const float* emb,
+                      int total, int n, int per_frame, const int* stream_of, int* label, float* score, hipStream_t s);
     const float* queries() const { return queries_.as<float>(); }   // [total][dim] of the last identify_dev
     // the live slots' identities, ascending, into out[max_tracks] (the rest: id = -1) and their sums into sums_out[max_tracks][dim]
     // (may be null); returns their number; synchronous
@@ -318,6 +331,8 @@ class Tracker {
     int streams_;
     TrackParams p_;
     DevBuf state_, embed_, slot_;                                // [streams][2] heads, then [streams][max_tracks] slots
+    bool bestshot_ = false;
+    DevBuf best_, quality_;                                      // [streams][max_tracks] best_q / the pipeline's [n][per_frame] qualities
     StagedTable plan_, iplan_;                                   // order[n], then starts[streams + 1] (update's / identify's)
     void clear_identity(int first, int count);
     int idim_ = 0, ipool_ = 0;

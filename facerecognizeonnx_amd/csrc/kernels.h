@@ -406,12 +406,19 @@ struct TrackParams {
     int max_tracks;         // 1 .. 64 slots per stream (one lane each)
     float iou_thr;
     int max_missed, refresh;
+    int bs_num, bs_den, bs_gap;     // the best-shot rule: re-embed when q * den > best_q * num and min_gap frames have passed
 };
 // One wave per stream walks starts[s] .. starts[s + 1] of `order` (track_plan.h).  heads = [streams][2] (frame_no, next_id), slots =
 // [streams][max_tracks].  det = [n][per_frame] records, counts = [n]; track / embed = [n][per_frame] are written entirely, and so is
-// slot (the lane of the detection's track, else -1) unless it is null.
+// slot (the lane of the detection's track, else -1) unless it is null.  quality = [n][per_frame] and best_q = [streams][max_tracks]:
+// both non-null = the best-shot policy is on for this call; either null = the update without it, bit for bit.
 void launch_track_update(int* heads, TrackState* slots, int streams, TrackParams p, const FaceRec* det, const int* counts, int per_frame,
-                         const int* order, const int* starts, int* track, int* embed, int* slot, hipStream_t s);
+                         const int* order, const int* starts, int* track, int* embed, int* slot, const int* quality, int* best_q,
+                         hipStream_t s);
+// face_quality.hip: quality[n][per_frame] = the score of face_quality.h for the entries below each frame's count, 0 behind it.  table ==
+// nullptr: frame f = frames + f * stride (rows x cols, row pitch step); otherwise the ragged table's row f (frames etc. unused).
+void launch_face_quality(const uint8_t* frames, long stride, int rows, int cols, int step, const FrameDesc* table, int n, const FaceRec* det,
+                         const int* counts, int per_frame, int* quality, hipStream_t s);
 // the flagged twin of launch_select_faces: the records with embed != 0, densely in (frame, slot) order, with frame index and track id
 void launch_track_select(const FaceRec* det, const int* embed, const int* track, int n, int per_frame, FaceRec* faces, int* frame_of,
                          int* track_of, int* total, hipStream_t s);
@@ -423,10 +430,12 @@ struct TrackIdent {
 };
 // frame_off[n + 1] = the exclusive prefix of the frames' flag counts: the rank of a flagged entry is frame_off[f] + the flags before it
 void launch_track_ranks(const int* embed, int n, int per_frame, int* frame_off, hipStream_t s);
-// stage A: one wave per (stream, slot), one more per stream for the untracked faces; writes queries[min(total, flags)][dim]
-void launch_track_pool(TrackIdent* ident, float* sums, int streams, int max_tracks, int dim, int pool_sum, const int* track, const int* slot,
-                       const int* embed, const int* frame_off, const float* emb, int total, int per_frame, const int* order, const int* starts,
-                       float* queries, hipStream_t s);
+constexpr int kTrackPoolLast = 0, kTrackPoolSum = 1, kTrackPoolWeighted = 2;     // enum fh_track_pool
+// stage A: one wave per (stream, slot), one more per stream for the untracked faces; writes queries[min(total, flags)][dim].  quality =
+// [n][per_frame], read only by kTrackPoolWeighted (which needs it).
+void launch_track_pool(TrackIdent* ident, float* sums, int streams, int max_tracks, int dim, int pool, const int* track, const int* slot,
+                       const int* embed, const int* quality, const int* frame_off, const float* emb, int total, int per_frame, const int* order,
+                       const int* starts, float* queries, hipStream_t s);
 // stage C: one wave per stream; ans_label / ans_score = [total] answers of the queries; label / score = [n][per_frame], written entirely
 void launch_track_propagate(TrackIdent* ident, int streams, int max_tracks, const int* track, const int* slot, const int* embed,
                             const int* frame_off, const int* ans_label, const float* ans_score, int total, int per_frame, const int* order,

@@ -24,18 +24,29 @@ __device__ __forceinline__ unsigned ordered_bits(float v) {
 // contains a cross-lane operation is taken by the whole wave: its condition comes from a ballot, a shuffle or a kernel argument.
 // No atomics: a stream belongs to one wave.  slot (optional, [n][per_frame]): the lane that holds the detection's track, -1 for an untracked
 // detection and for the entries behind the count — what the identity step (track_ident.hip) keys its per-slot state by.
+// Best shot (quality and best_q both given, else nothing below differs from the plain update): lane l also keeps best_q of slot l in a
+// register beside st — the quality of the best face of the track embedded so far; an opened track starts it, and a matched track whose
+// face has become better than best_q by the ratio num / den, min_gap frames or more after its last embedding, is embedded again.  The
+// qualities of a chunk travel through LDS with its boxes.  BESTSHOT is a template parameter so that the plain update compiles to the
+// code it was: nothing of the policy is left in it.
 // ------------------------------------------------------------------------------------------
+template <bool BESTSHOT>
 __global__ __launch_bounds__(64) void track_update_kernel(int* __restrict__ heads, TrackState* __restrict__ slots, TrackParams p,
                                                           const FaceRec* __restrict__ det, const int* __restrict__ counts, int per_frame,
                                                           const int* __restrict__ order, const int* __restrict__ starts,
-                                                          int* __restrict__ track, int* __restrict__ embed, int* __restrict__ slot) {
+                                                          int* __restrict__ track, int* __restrict__ embed, int* __restrict__ slot,
+                                                          const int* __restrict__ quality, int* __restrict__ best_q) {
     __shared__ int4 sbox[64];
+    __shared__ int squal[64];
     const int s = blockIdx.x, lane = threadIdx.x;
     const int b = starts[s], e = starts[s + 1];
     if (b == e) return;                                                 // no frame of this stream in the call
     const bool usable = lane < p.max_tracks;
     TrackState st{-1, 0, 0, 0, 0, 0, 0, 0};
     if (usable) st = slots[(size_t)s * p.max_tracks + lane];
+    constexpr bool bestshot = BESTSHOT;                                 // (the launcher: quality and best_q are both given)
+    int bq = 0;
+    if (bestshot && usable) bq = best_q[(size_t)s * p.max_tracks + lane];
     int t = heads[2 * s], next_id = heads[2 * s + 1];
 
     for (int i0 = b; i0 < e; i0 += 64) {
@@ -58,6 +69,7 @@ __global__ __launch_bounds__(64) void track_update_kernel(int* __restrict__ head
                 if (lane < nj) {
                     const FaceRec& r = det[row + j0 + lane];
                     sbox[lane] = make_int4(r.x, r.y, r.w, r.h);
+                    if (bestshot) squal[lane] = quality[row + j0 + lane];
                 }
                 __syncthreads();
                 for (int jj = 0; jj < nj; ++jj) {
@@ -83,7 +95,12 @@ __global__ __launch_bounds__(64) void track_update_kernel(int* __restrict__ head
                             st.last_seen = t;
                             st.hits += 1;
                             taken = true;
-                            const int again = (p.refresh > 0 && t - st.last_embed >= p.refresh) ? 1 : 0;
+                            int again = (p.refresh > 0 && t - st.last_embed >= p.refresh) ? 1 : 0;
+                            if (bestshot) {
+                                const int q = squal[jj];
+                                if ((long long)q * p.bs_den > (long long)bq * p.bs_num && t - st.last_embed >= p.bs_gap) again = 1;
+                                if (again) bq = max(bq, q);
+                            }
                             if (again) st.last_embed = t;
                             track[o] = st.id;
                             embed[o] = again;
@@ -95,6 +112,7 @@ __global__ __launch_bounds__(64) void track_update_kernel(int* __restrict__ head
                         if (fm != 0) {
                             if (lane == __ffsll((long long)fm) - 1) {
                                 st = TrackState{next_id, box.x, box.y, box.z, box.w, t, t, 1};
+                                if (bestshot) bq = squal[jj];
                                 taken = true;
                                 track[o] = next_id;
                                 embed[o] = 1;
@@ -119,13 +137,19 @@ __global__ __launch_bounds__(64) void track_update_kernel(int* __restrict__ head
         }
     }
     if (usable) slots[(size_t)s * p.max_tracks + lane] = st;
+    if (bestshot && usable) best_q[(size_t)s * p.max_tracks + lane] = bq;
     if (lane == 0) { heads[2 * s] = t; heads[2 * s + 1] = next_id; }
 }
 
 void launch_track_update(int* heads, TrackState* slots, int streams, TrackParams p, const FaceRec* det, const int* counts, int per_frame,
-                         const int* order, const int* starts, int* track, int* embed, int* slot, hipStream_t s) {
-    hipLaunchKernelGGL(track_update_kernel, dim3(streams), dim3(64), 0, s, heads, slots, p, det, counts, per_frame, order, starts, track,
-                       embed, slot);
+                         const int* order, const int* starts, int* track, int* embed, int* slot, const int* quality, int* best_q,
+                         hipStream_t s) {
+    if (quality && best_q)
+        hipLaunchKernelGGL(track_update_kernel<true>, dim3(streams), dim3(64), 0, s, heads, slots, p, det, counts, per_frame, order, starts,
+                           track, embed, slot, quality, best_q);
+    else
+        hipLaunchKernelGGL(track_update_kernel<false>, dim3(streams), dim3(64), 0, s, heads, slots, p, det, counts, per_frame, order, starts,
+                           track, embed, slot, nullptr, nullptr);
 }
 
 // ------------------------------------------------------------------------------------------

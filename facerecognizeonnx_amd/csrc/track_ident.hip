@@ -15,6 +15,7 @@ namespace fh {
 namespace {
 
 __device__ __forceinline__ float4 add4(const float4 a, const float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
+__device__ __forceinline__ float4 mul4(const float w, const float4 a) { return make_float4(w * a.x, w * a.y, w * a.z, w * a.w); }
 __device__ __forceinline__ float wave_sum(float s) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
@@ -81,14 +82,16 @@ __global__ __launch_bounds__(256) void track_ranks_kernel(const int* __restrict_
 // ------------------------------------------------------------------------------------------
 // Stage A.  Wave (s, l), l < max_tracks, owns slot l of stream s: it picks the flagged entries whose slot is l with a ballot and runs
 // their chain in time order — (re)open: sum = row, query = row verbatim; else sum += row (POOL_SUM; POOL_LAST: sum = row) and the
-// query is the normalised sum.  Wave (s, max_tracks) copies the rows of the stream's untracked faces.  Each lane owns the 16-byte
+// query is the normalised sum.  POOL_WEIGHTED is POOL_SUM with every row entering the sum as wq * row, wq = (float)max(quality, 1): one
+// multiply, then one add per component (the file is built without contraction).  Wave (s, max_tracks) copies the rows of the stream's
+// untracked faces.  Each lane owns the 16-byte
 // columns lane, lane + 64, ...; the sum row lives in the state and is read, added to and written back by the lane that owns the column.
 // A flagged entry of rank >= total is nobody's.
 // ------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void track_pool_kernel(TrackIdent* __restrict__ ident, float4* __restrict__ sums, int streams,
-                                                         int max_tracks, int vpr, int pool_sum, const int* __restrict__ track,
+                                                         int max_tracks, int vpr, int pool, const int* __restrict__ track,
                                                          const int* __restrict__ slot, const int* __restrict__ embed,
-                                                         const int* __restrict__ frame_off, const float4* __restrict__ emb, int total,
+                                                         const int* __restrict__ quality, const int* __restrict__ frame_off, const float4* __restrict__ emb, int total,
                                                          int per_frame, const int* __restrict__ order, const int* __restrict__ starts,
                                                          float4* __restrict__ queries) {
     const int w = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -102,31 +105,34 @@ __global__ __launch_bounds__(256) void track_pool_kernel(TrackIdent* __restrict_
     float4* const sm = sums + ((size_t)s * max_tracks + (my < 0 ? 0 : my)) * vpr;
     int owner = -1, n_emb = 0;
     if (my >= 0) { owner = id->owner; n_emb = id->n_emb; }
+    const bool weighted = pool == kTrackPoolWeighted;
 
     walk_entries(order, b, e, per_frame, embed, frame_off, lane, [&](bool, int, int, size_t idx, bool fl, int rank) {
         const int sl = fl ? slot[idx] : -2;
         const int tid = fl ? track[idx] : -1;
+        const int qual = (weighted && fl) ? quality[idx] : 1;
         unsigned long long m = __ballot(fl && rank < total && sl == my);
         while (m != 0) {                                                 // ascending lanes = (frame, slot) order = time order
             const int src = __ffsll((long long)m) - 1;
             m &= m - 1;
             const int q_e = __shfl(rank, src), t_e = __shfl(tid, src);
+            const float wq = (float)max(__shfl(qual, src), 1);
             const float4* const row = emb + (size_t)q_e * vpr;
             float4* const q = queries + (size_t)q_e * vpr;
             if (my < 0) {
                 for (int c = lane; c < vpr; c += 64) q[c] = row[c];
-            } else if (owner != t_e || !pool_sum) {
+            } else if (owner != t_e || pool == kTrackPoolLast) {
                 if (owner != t_e) { owner = t_e; n_emb = 1; } else ++n_emb;
                 for (int c = lane; c < vpr; c += 64) {
                     const float4 v = row[c];
-                    sm[c] = v;
+                    sm[c] = weighted ? mul4(wq, v) : v;
                     q[c] = v;
                 }
             } else {
                 ++n_emb;
                 float sq = 0.f;
                 for (int c = lane; c < vpr; c += 64) {
-                    const float4 a = add4(sm[c], row[c]);
+                    const float4 a = add4(sm[c], weighted ? mul4(wq, row[c]) : row[c]);
                     sm[c] = a;
                     sq += a.x * a.x + a.y * a.y + a.z * a.z + a.w * a.w;
                 }
@@ -195,12 +201,12 @@ void launch_track_ranks(const int* embed, int n, int per_frame, int* frame_off, 
     hipLaunchKernelGGL(track_ranks_kernel, dim3(1), dim3(256), 0, s, embed, n, per_frame, frame_off);
 }
 
-void launch_track_pool(TrackIdent* ident, float* sums, int streams, int max_tracks, int dim, int pool_sum, const int* track, const int* slot,
-                       const int* embed, const int* frame_off, const float* emb, int total, int per_frame, const int* order, const int* starts,
-                       float* queries, hipStream_t s) {
+void launch_track_pool(TrackIdent* ident, float* sums, int streams, int max_tracks, int dim, int pool, const int* track, const int* slot,
+                       const int* embed, const int* quality, const int* frame_off, const float* emb, int total, int per_frame, const int* order,
+                       const int* starts, float* queries, hipStream_t s) {
     const int waves = streams * (max_tracks + 1);
     hipLaunchKernelGGL(track_pool_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, ident, reinterpret_cast<float4*>(sums), streams,
-                       max_tracks, dim / 4, pool_sum, track, slot, embed, frame_off, reinterpret_cast<const float4*>(emb), total, per_frame,
+                       max_tracks, dim / 4, pool, track, slot, embed, quality, frame_off, reinterpret_cast<const float4*>(emb), total, per_frame,
                        order, starts, reinterpret_cast<float4*>(queries));
 }
 

@@ -357,7 +357,7 @@ FH_API int fh_pipeline_run_tracked_dev(fh_det* d, fh_rec* r, fh_tracker* t, cons
  * fh_pipeline_run_identified_dev  fh_pipeline_run_tracked_dev (the same hand-off, the same return value, every output bit for bit) with
  *   the update reporting slots into a buffer of the tracker's, then fh_track_identify_dev on d_emb; the recogniser's feature dim must
  *   be the identity dim (FH_ERR_ARG).  The ragged, tiled, two-stream and fh_stream forms have no identified twin either. */
-enum fh_track_pool { FH_TRACK_POOL_LAST = 0, FH_TRACK_POOL_SUM = 1 };
+enum fh_track_pool { FH_TRACK_POOL_LAST = 0, FH_TRACK_POOL_SUM = 1, FH_TRACK_POOL_WEIGHTED = 2 };
 typedef struct fh_track_ident { int32_t id, n_emb, label; float score; } fh_track_ident;   /* 16 bytes */
 FH_API int fh_track_update_slots_dev(fh_tracker* t, const fh_face* d_det, const int* d_counts, int n, int per_frame, const int* stream_of,
                                      int* d_track, int* d_embed, int* d_slot /*[n][per_frame] or NULL*/, void* stream);
@@ -373,6 +373,73 @@ FH_API int fh_pipeline_run_identified_dev(fh_det* d, fh_rec* r, fh_tracker* t, f
                                           float nms_thr, int faces_per_frame, fh_face* d_all, int* d_counts, int* d_track, fh_face* d_faces,
                                           int* d_frame_of, int* d_track_of, float* d_emb, int* d_label /*[n][F]*/, float* d_score /*[n][F]*/,
                                           void* stream);
+
+/* ---- face quality and best-shot re-embedding: WHICH frame of a track the recogniser sees.  The tracker above embeds a track when it
+ * opens — the frame on which the face enters the picture — and then on a timer.  This section adds a per-face quality score, a tracker
+ * policy that embeds a track again when its face has become clearly better than the best one embedded so far, and a quality-weighted
+ * template pool.  All of it is opt-in: with the policy off and the old pool modes every entry point above is bit for bit what it was.
+ * The score is DEFINED TO THE BIT (integers, plus one fp32 term in a fixed order), so the policy is reproducible; its constants are a
+ * proposal whose effect on recognition accuracy nobody has measured.
+ *
+ * The score.  Frame f, entry j < c, c = min(max(d_counts[f], 0), per_frame), record (x, y, w, h, score, lm[10]):
+ *     q = (S * Z * P) >> 8, an int32 >= 0 (at most 1020 * 112 * 256 >> 8);    entries j >= c get 0.
+ *   S  sharpness, integers only.  Clip the box to where 4-neighbours exist, in int64 (records can hold anything): x0 = max(x, 1), y0 =
+ *      max(y, 1), x1 = min(x + w, cols - 1), y1 = min(y + h, rows - 1).  x1 - x0 < 8 or y1 - y0 < 8: S = 0.  Otherwise the stride is d =
+ *      max(1, min(x1 - x0, y1 - y0) / 64) and the samples are px = x0 + i * d < x1, py = y0 + k * d < y1 (i, k = 0, 1, ...).  Luma Y =
+ *      (29 * B + 150 * G + 77 * R + 128) >> 8.  At each sample L = |4 * Y(px, py) - Y(px - 1, py) - Y(px + 1, py) - Y(px, py - 1) -
+ *      Y(px, py + 1)|: the neighbour distance is 1 whatever the stride — the sharpness of the capture, not of the face's scale.  S =
+ *      (sum of L) / (number of samples), an integer division of an int64 sum; 0 <= S <= 1020.  Every read is inside the frame.
+ *   Z  size.  Z = min(max(min(w, h), 0), 112): 112 is the recogniser's input side, a larger face adds nothing.
+ *   P  pose, fp32 in this order, one division, not contracted (as FaceDetector::iou).  Landmarks in the record's order: left eye le =
+ *      lm[0..1], right eye re = lm[2..3], nose = lm[4..5].  dx = |re.x - le.x|; e = dx > 1.0f ? dx : 1.0f; m = (le.x + re.x) * 0.5f;
+ *      v = 256.0f * (1.0f - 2.0f * |nose.x - m| / e); P = v > 0 ? min((int)(v < 256.0f ? v : 256.0f), 256) : 0.  A NaN landmark fails
+ *      the comparison: P = 0.
+ * fh_face_quality_dev  the scores of n uniform frames (frame f at d_frames + f * frame_stride, rows x cols, row pitch step) into
+ *   d_quality[n][per_frame], asynchronously on `stream`.  FH_ERR_ARG before anything is launched: a NULL pointer, n outside 1 .. 4096,
+ *   per_frame < 1, n * per_frame >= 2^31, rows or cols <= 0, step < cols * 3.
+ * fh_face_quality_ragged_dev  the same kernel over frames of any sizes (fh_frame as fh_det_detect_ragged_dev: HOST descriptors of
+ *   DEVICE pixels, read before the call returns); an empty frame scores 0 everywhere.  One frame table per calling thread: calls on
+ *   different streams are ordered one after the other.
+ *
+ * The policy.  fh_tracker_set_bestshot(t, on, num, den, min_gap)  synchronous; needs 1 <= den <= num <= 32768 and min_gap >= 1 (else
+ *   FH_ERR_ARG, nothing changes).  Allocates one int32 best_q per (stream, slot) and clears it — on every call, whatever `on` is;
+ *   fh_tracker_reset(stream) clears that stream's.  on = 0 switches the policy off.
+ * fh_track_update_q_dev  fh_track_update_slots_dev with one more input, d_quality[n][per_frame] (fh_track_update_slots_dev is this call
+ *   with d_quality = NULL; one kernel).  With d_quality == NULL or the policy off, the outputs and the state are bit for bit
+ *   fh_track_update_slots_dev's and best_q is not touched.  With the policy on and qualities given, q = d_quality[f][j], and steps 2
+ *   and 3 of the update read:
+ *   2. match   ... timer = refresh > 0 && t - last_embed >= refresh (the rule above); better = (int64)q * den > (int64)best_q * num
+ *              && t - last_embed >= min_gap; d_embed[f][j] = timer || better.  When it is set: last_embed = t and best_q =
+ *              max(best_q, q).  Strict: a face exactly num / den times as good as the best one is not embedded again.
+ *   3. open    ... as above (d_embed[f][j] = 1), and best_q[slot] = q.  An untracked face: as above.
+ *   TrackState stays 32 bytes: best_q lives beside it.  fh_tracker_get_quality  synchronous; best_q of the live slots, ascending, in the
+ *   positions of fh_tracker_get_state (the rest: 0); returns their number; FH_ERR_ARG before fh_tracker_set_bestshot was ever called.
+ *
+ * The pool.  FH_TRACK_POOL_WEIGHTED for fh_tracker_enable_identity — on a tracker on which fh_tracker_set_bestshot has been called (with
+ *   on = 0 or 1: that call is what opts a tracker into the quality feature); on any other tracker the mode stays unknown, FH_ERR_ARG,
+ *   nothing changes, as before — and fh_track_identify_q_dev = fh_track_identify_dev plus
+ *   d_quality[n][per_frame] (the old call is the new one with NULL).  In stage A, flagged face e with quality q has the weight wq =
+ *   (float)max(q, 1).  (Re)opened slot: sum = wq * emb_e, q_e = emb_e verbatim.  Otherwise: sum = sum + wq * emb_e — one fp32 multiply
+ *   and one fp32 add per component, not fused, in time order — and q_e = normalize(sum).  WEIGHTED with d_quality == NULL: FH_ERR_ARG
+ *   before anything is launched.  The other two modes ignore the array and stay bit for bit as they are.
+ *
+ * The pipelines.  With the policy on, fh_pipeline_run_tracked_dev and fh_pipeline_run_identified_dev run fh_face_quality_dev on `stream`
+ *   between the detector and the update, into a buffer of the tracker's (fh_tracker_quality_dev: a stage hook, [n][F], valid until the
+ *   next pipeline call on the handle), call fh_track_update_q_dev and — the identified one — fh_track_identify_q_dev.  With the policy
+ *   off nothing new is launched; the identified pipeline then refuses FH_TRACK_POOL_WEIGHTED (FH_ERR_ARG). */
+FH_API int fh_face_quality_dev(const uint8_t* d_frames, int n, int rows, int cols, int step, long long frame_stride, const fh_face* d_det,
+                               const int* d_counts, int per_frame, int* d_quality /*[n][per_frame]*/, void* stream);
+FH_API int fh_face_quality_ragged_dev(const fh_frame* frames, int n, const fh_face* d_det, const int* d_counts, int per_frame,
+                                      int* d_quality /*[n][per_frame]*/, void* stream);
+FH_API int fh_tracker_set_bestshot(fh_tracker* t, int on, int num, int den, int min_gap);
+FH_API int fh_tracker_get_quality(fh_tracker* t, int stream, int* host_out /*[max_tracks]*/);
+FH_API const int* fh_tracker_quality_dev(fh_tracker* t);
+FH_API int fh_track_update_q_dev(fh_tracker* t, const fh_face* d_det, const int* d_counts, int n, int per_frame, const int* stream_of,
+                                 int* d_track, int* d_embed, int* d_slot /*or NULL*/, const int* d_quality /*[n][per_frame] or NULL*/,
+                                 void* stream);
+FH_API int fh_track_identify_q_dev(fh_tracker* t, fh_gallery* g, float threshold, const int* d_track, const int* d_slot, const int* d_embed,
+                                   const int* d_quality /*[n][per_frame] or NULL*/, const float* d_emb, int total, int n, int per_frame,
+                                   const int* stream_of, int* d_label, float* d_score, void* stream);
 
 /* ---- gallery (1:N compareFaces): rows are L2-normalised features; scores are (dot+1)/2. */
 FH_API fh_gallery* fh_gallery_create(int dim);

@@ -15,6 +15,11 @@ by round after a warm-up.
       fh_pipeline_run_identified_dev with refresh 0 and 8, and — the serial chain at its worst — the update with slots alone beside
       update + fh_track_identify_dev on one stream with refresh 1, where every face of every frame is pooled into its track's sum.
 
+  (e) best shot: the identified pipeline of (d) with the best-shot policy on (the quality kernel between the detector and the update,
+      the update and the identify reading the qualities), beside the same pipeline with the policy off in the same run; and the
+      quality kernel alone on the detector's records of the (a) frames.  Every camera of the video repeats one frame, so no face ever
+      gets better: the step pays for the score and embeds nothing more.
+
 Writes --md (default profiles/track_ab.md) and prints one JSON line per case.  Needs a GPU; there is no fallback."""
 import argparse
 import json
@@ -28,7 +33,7 @@ ap.add_argument("--warmup", type=int, default=20)
 ap.add_argument("--steps", type=int, default=100, help="timed steps per leg (at least)")
 ap.add_argument("--rounds", type=int, default=5)
 ap.add_argument("--block", type=int, default=5, help="steps per HIP-event sample")
-ap.add_argument("--cases", nargs="+", default=["a", "b", "c", "d"])
+ap.add_argument("--cases", nargs="+", default=["a", "b", "c", "d", "e"])
 ap.add_argument("--md", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "track_ab.md"))
 a = ap.parse_args()
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -42,6 +47,7 @@ from facerecognizeonnx_amd.synth import models  # noqa: E402
 THR, NMS, F, HW = 0.5, 0.4, 8, 640
 IOU_THR, MAX_TRACKS = 0.3, 64
 GALLERY_ROWS, ID_THRESHOLD = 10000, 0.6
+BESTSHOT = (5, 4, 1)                                               # num, den, min_gap
 
 
 def samples(step, steps, block):
@@ -139,7 +145,7 @@ def main():
         out["c"] = {"frames": B, "faces_in_records": int(torch.clamp(counts, 0, F).sum().item()), **st}
         print(json.dumps({"case": "c", **out["c"]}), flush=True)
 
-    if "d" in a.cases:
+    if "d" in a.cases or "e" in a.cases:
         gal = fa.Gallery(512)
         g = rng.standard_normal((GALLERY_ROWS, 512), dtype=np.float32)
         gal.enroll(g / np.linalg.norm(g, axis=1, keepdims=True))
@@ -150,6 +156,8 @@ def main():
                                                           counts.data_ptr(), track.data_ptr(), faces.data_ptr(), frame_of.data_ptr(),
                                                           track_of.data_ptr(), emb.data_ptr(), label.data_ptr(), score.data_ptr(), stream_of,
                                                           THR, NMS, stream)
+
+    if "d" in a.cases:
         out["d"] = {"pipeline": {}}
         for streams in (1, 16):
             if B % streams:
@@ -186,6 +194,34 @@ def main():
         st, _, _ = ab({"update_slots": lambda: update(t_upd), "update_slots_identify": update_identify}, a.warmup, a.steps, a.rounds, a.block)
         out["d"]["chain"] = {"frames": B, "faces_pooled_per_call": flagged, **st}
         print(json.dumps({"case": "d", **out["d"]}), flush=True)
+
+    if "e" in a.cases:
+        out["e"] = {"pipeline": {}}
+        for streams in (1, 16):
+            if B % streams:
+                continue
+            stream_of = np.tile(np.arange(streams, dtype=np.int32), B // streams)
+            data = distinct[torch.from_numpy(stream_of.astype(np.int64)).cuda()].contiguous()
+            legs = {}
+            for r in (0, 8):
+                for policy in ("off", "bestshot"):
+                    t = fa.Tracker(streams, MAX_TRACKS, IOU_THR, 0, r)
+                    t.enable_identity(512)
+                    if policy == "bestshot":
+                        t.set_bestshot(*BESTSHOT)
+                    legs[f"identified_{policy}_refresh{r}"] = identified(data, t, stream_of)
+            st, fc, first = ab(legs, a.warmup, a.steps, a.rounds, a.block)
+            out["e"]["pipeline"][f"{streams}x{B // streams}"] = {"faces_per_step": fc, "faces_first_step": first, **st}
+            del data
+        det.detect_batch_dev(distinct.data_ptr(), B, HW, HW, all_.data_ptr(), F, counts.data_ptr(), THR, NMS, stream=stream)
+        torch.cuda.synchronize()
+        quality = torch.zeros((B, F), **i32)
+        st, _, _ = ab({"quality": lambda: fa.face_quality_dev(distinct.data_ptr(), all_.data_ptr(), counts.data_ptr(), F, quality.data_ptr(),
+                                                              n=B, rows=HW, cols=HW, stream=stream)}, a.warmup, a.steps, a.rounds, a.block)
+        q = quality.cpu().numpy()
+        out["e"]["kernel"] = {"frames": B, "faces_in_records": int(torch.clamp(counts, 0, F).sum().item()),
+                              "quality_min_median_max": [int(q.min()), int(np.median(q)), int(q.max())], **st}
+        print(json.dumps({"case": "e", **out["e"]}), flush=True)
 
     if a.md and out:
         write_md(out)
@@ -240,6 +276,19 @@ def write_md(out):
               "| leg | ms per call |", "|---|---|",
               f"| `fh_track_update_slots_dev` | {fmt(c['update_slots'])} |",
               f"| `fh_track_update_slots_dev` + `fh_track_identify_dev` | {fmt(c['update_slots_identify'])} |", ""]
+    if "e" in out:
+        L += [f"## (e) best shot: the identified pipeline with the policy {BESTSHOT[0]} / {BESTSHOT[1]}, min_gap {BESTSHOT[2]}", "",
+              "The video of (b) and the gallery of (d).  Every camera repeats one frame, so no face ever gets better: the policy pays for "
+              "`fh_face_quality_dev` and the extended update and embeds nothing more.", "",
+              "| streams x frames | leg | ms per step | faces embedded per step | ... on the first step |", "|---|---|---|---|---|"]
+        for shape, d in out["e"]["pipeline"].items():
+            for k in d["faces_per_step"]:
+                L.append(f"| {shape} | `fh_pipeline_run_identified_dev`, policy {k.split('_')[1]}, refresh {k[-1]} | {fmt(d[k])} | "
+                         f"{d['faces_per_step'][k]} | {d['faces_first_step'][k]} |")
+        c = out["e"]["kernel"]
+        L += ["", f"The quality kernel alone: {c['frames']} frames of {HW}x{HW}, {c['faces_in_records']} faces in the records (up to {F} per "
+              f"frame), scores min / median / max {c['quality_min_median_max']}.", "",
+              "| leg | ms per call |", "|---|---|", f"| `fh_face_quality_dev` | {fmt(c['quality'])} |", ""]
     os.makedirs(os.path.dirname(os.path.abspath(a.md)), exist_ok=True)
     with open(a.md, "w") as f:
         f.write("\n".join(L))
