@@ -178,6 +178,9 @@ PROTOTYPES = {
     "fh_gallery_fuse_ids": (_ll, [_vp, _vp, _i]),
     "fh_gallery_get_rows": (_ll, [_vp, _ll, _ll, _vp]),
     "fh_gallery_self_scores_dev": (_i, [_vp, _vp, _vp, _vp]),
+    "fh_cluster_scores": (_i, [_vp, _i, _f, _i, _i, _vp, _vp]),
+    "fh_gallery_cluster_dev": (_i, [_vp, _f, _i, _i, _vp, _vp, _vp]),
+    "fh_gallery_set_ids": (_ll, [_vp, _vp, _i]),
     "fh_comm_unique_id": (_i, [_vp]),
     "fh_comm_create": (_vp, [_i, _i, _vp, _i]),
     "fh_comm_destroy": (None, [_vp]),
@@ -207,6 +210,7 @@ PROTOTYPES = {
     "fh_rec_set_cus": (_i, [_vp, _i]),
     "fh_debug_streamk": (_i, [_i, _i]),
     "fh_debug_wino_slots": (_i, [_i]),
+    "fh_debug_cluster_tiles": (_i, [_i]),
     "fh_debug_topk_merge_strided_dev": (_i, [_vp, _vp, _i, _i, _i, _ll, _vp, _vp, _vp]),
     "fh_set_graph_replay": (_i, [_i]),
     "fh_det_workspace_dev": (_vp, [_vp]),

@@ -676,6 +676,36 @@ class Gallery:
         tmpl = the result of fuse() (fh_gallery_self_scores_dev).  Asynchronous on `stream`."""
         check(_lib.lib().fh_gallery_self_scores_dev(self._h, tmpl._h, scores_ptr, stream), "fh_gallery_self_scores_dev")
 
+    def cluster_dev(self, threshold: float, min_pts: int, noise, labels_ptr: int, info_ptr: Optional[int] = None, stream: int = 0):
+        """Exact DBSCAN over the gallery's own rows (fh_gallery_cluster_dev): labels[len(self)] (device int32) = the position of the
+        cluster's smallest core row, -1 ("none") or the row's own position ("self") for noise; info[4] (device int32, optional) =
+        (clusters, core, border, noise).  Two rows are linked iff the fp32 scan scores the pair above `threshold`; a row is core iff it
+        has at least min_pts - 1 such neighbours.  Asynchronous on `stream`."""
+        check(_lib.lib().fh_gallery_cluster_dev(self._h, threshold, min_pts, _noise_mode(noise), labels_ptr, info_ptr, stream),
+              "fh_gallery_cluster_dev")
+
+    def cluster(self, threshold: float, min_pts: int = 1, noise="none"):
+        """(labels int32[len(self)], info int32[4]) of cluster_dev — a synchronous convenience that allocates and copies back."""
+        import torch
+        n = len(self)
+        labels = torch.empty(max(n, 1), dtype=torch.int32, device="cuda")
+        info = torch.empty(4, dtype=torch.int32, device="cuda")
+        self.cluster_dev(threshold, min_pts, noise, labels.data_ptr(), info.data_ptr(), torch.cuda.current_stream().cuda_stream)
+        return labels[:n].cpu().numpy(), info.cpu().numpy()
+
+    def set_ids(self, ids) -> int:
+        """Replace the ids of all rows by position (int32[len(self)] >= 0, host array or a device tensor) and make the gallery labelled
+        (fh_gallery_set_ids); with noise="self" labels: cluster -> set_ids -> fuse.  Synchronous; returns the row count."""
+        if hasattr(ids, "data_ptr"):                                   # a torch tensor: device or host memory, as it is
+            import torch
+            if ids.dtype != torch.int32 or not ids.is_contiguous() or ids.numel() != len(self):
+                raise ValueError("set_ids: need a contiguous int32 tensor with one id per row")
+            return check(_lib.lib().fh_gallery_set_ids(self._h, ids.data_ptr(), int(ids.is_cuda)), "fh_gallery_set_ids")
+        ids = np.ascontiguousarray(np.asarray(ids, np.int32).reshape(-1))
+        if ids.size != len(self):
+            raise ValueError("set_ids: need one id per row")
+        return check(_lib.lib().fh_gallery_set_ids(self._h, ids.ctypes.data if ids.size else None, 0), "fh_gallery_set_ids")
+
     def __len__(self) -> int:
         return int(_lib.lib().fh_gallery_size(self._h))
 
@@ -743,6 +773,33 @@ def group_ids(ids):
     m = check(_lib.lib().fh_gallery_group_ids(ids.ctypes.data if n else None, n, order.ctypes.data if n else None, starts.ctypes.data,
                                               uniq.ctypes.data if n else None), "fh_gallery_group_ids")
     return order, starts[:m + 1].copy(), uniq[:m].copy()
+
+
+_NOISE = {"none": 0, "self": 1}                                # enum fh_cluster_noise
+
+
+def _noise_mode(noise) -> int:
+    """"none" / "self" -> the enum; an int passes through (the library checks it)."""
+    if isinstance(noise, str):
+        if noise not in _NOISE:
+            raise ValueError(f"noise {noise!r}: expected one of {sorted(_NOISE)}")
+        return _NOISE[noise]
+    return int(noise)
+
+
+def cluster_scores(scores, threshold: float, min_pts: int = 1, noise="none"):
+    """(labels int32[n], info int32[4]) of fh_cluster_scores — host only, the one definition of the clustering rule: rows i < j are
+    linked iff scores[i, j] > threshold (strict, fp32; only the upper triangle is read), core iff degree + 1 >= min_pts, a cluster =
+    a component of the core rows labelled by its smallest position, a non-core row joins its best core neighbour (higher score, then
+    lower position), the rest is noise (-1, or the row's own position with noise="self").  info = (clusters, core, border, noise)."""
+    scores = np.ascontiguousarray(scores, np.float32)
+    if scores.ndim != 2 or scores.shape[0] != scores.shape[1]:
+        raise ValueError("cluster_scores: need a square matrix")
+    n = scores.shape[0]
+    labels, info = np.empty(n, np.int32), np.zeros(4, np.int32)
+    check(_lib.lib().fh_cluster_scores(scores.ctypes.data if n else None, n, threshold, min_pts, _noise_mode(noise),
+                                       labels.ctypes.data if n else None, info.ctypes.data), "fh_cluster_scores")
+    return labels, info
 
 
 def plan_describe(path: str, default_h: int, default_w: int) -> str:

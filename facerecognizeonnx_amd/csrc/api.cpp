@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "../../include/facehip.h"
+#include "cluster_plan.h"
 #include "engine.h"
 #include "group_ids.h"
 #include "track_plan.h"
@@ -1320,6 +1321,38 @@ int fh_gallery_self_scores_dev(fh_gallery* src, fh_gallery* tmpl, float* d_score
     if (src->g.dim() != tmpl->g.dim()) return arg_error("fh_gallery_self_scores_dev: the galleries' dims differ");
     return guarded([&] { src->g.self_scores_dev(tmpl->g, d_scores, S(stream)); return (int)FH_OK; });
 }
+
+// ---- unsupervised grouping: the rule on the host (cluster_plan.h), the same rule over the gallery's own rows (gallery_cluster.hip)
+namespace {
+const char* bad_cluster(int min_pts, int noise) {
+    if (min_pts < 1) return "need min_pts >= 1";
+    if (noise != FH_CLUSTER_NOISE_NONE && noise != FH_CLUSTER_NOISE_SELF) return "unknown noise mode";
+    return nullptr;
+}
+}  // namespace
+int fh_cluster_scores(const float* scores, int n, float threshold, int min_pts, int noise, int* labels, int* info) {
+    if (n < 0 || (n > 0 && (!scores || !labels))) return arg_error("fh_cluster_scores: bad argument");
+    if (const char* why = bad_cluster(min_pts, noise)) return frames_error("fh_cluster_scores", why);
+    int m = -1;
+    const int rc = guarded([&] { m = fh::cluster_scores(scores, n, threshold, min_pts, noise, labels, info); return 0; });   // (its scratch may run out of memory)
+    if (rc < 0) return rc;
+    return m < 0 ? arg_error("fh_cluster_scores: bad argument") : m;
+}
+int fh_gallery_cluster_dev(fh_gallery* g, float threshold, int min_pts, int noise, int* d_labels, int* d_info, void* stream) {
+    if (!g || !d_labels) return arg_error("fh_gallery_cluster_dev: null argument");
+    if (const char* why = bad_cluster(min_pts, noise)) return frames_error("fh_gallery_cluster_dev", why);
+    return guarded([&] { g->g.cluster_dev(threshold, min_pts, noise == FH_CLUSTER_NOISE_SELF, d_labels, d_info, S(stream)); return (int)FH_OK; });
+}
+long long fh_gallery_set_ids(fh_gallery* g, const int* ids, int on_device) {
+    if (!g) return arg_error("fh_gallery_set_ids: null handle");
+    const long long n = (long long)g->g.size();
+    if (n > 0 && !ids) return arg_error("fh_gallery_set_ids: null ids");
+    if (n > 0)
+        if (const int rc = check_ids("fh_gallery_set_ids: negative id", ids, n, on_device)) return rc;
+    const int rc = guarded([&] { g->g.set_ids(ids, on_device != 0); return 0; });
+    return rc < 0 ? rc : n;
+}
+int fh_debug_cluster_tiles(int tiles_per_wg) { fh::cluster_debug_tiles(tiles_per_wg); return 0; }
 
 int fh_debug_topk_merge_strided_dev(const float* ps, const int* pi, int nparts, int nq, int k, long long part_stride, float* scores, int* indices,
                                     void* stream) {

@@ -5,6 +5,7 @@
 #include "track_plan.h"
 
 #include <atomic>
+#include <climits>
 #include <cstdio>
 #include <cstdlib>
 #include <algorithm>
@@ -1123,6 +1124,29 @@ void Gallery::self_scores_dev(const Gallery& tmpl, float* out, hipStream_t s) {
     if (n_ == 0) return;
     launch_gallery_self_scores(rows_.as<float>(), ids_.as<int>(), n_, tmpl.rows_.as<float>(), tmpl.ids_.as<int>(), tmpl.n_, dim_, out, s);
     FH_HIP(hipGetLastError());
+}
+
+void Gallery::cluster_dev(float thr, int min_pts, bool noise_self, int* labels, int* info, hipStream_t s) {
+    if (dim_ % 64) throw std::runtime_error("gallery: dim must be a multiple of 64");
+    if (n_ == 0) {
+        if (info) FH_HIP(hipMemsetAsync(info, 0, 4 * sizeof(int), s));
+        return;
+    }
+    if (n_ > (long)INT_MAX) throw std::runtime_error("gallery: row positions must fit in 31 bits");
+    cl_deg_.ensure((size_t)n_ * sizeof(int));
+    cl_parent_.ensure((size_t)n_ * sizeof(int));
+    cl_best_.ensure((size_t)n_ * sizeof(unsigned long long));
+    launch_gallery_cluster(rows_.as<float>(), n_, dim_, thr, min_pts, noise_self, cl_deg_.as<int>(), cl_parent_.as<int>(),
+                           cl_best_.as<unsigned long long>(), labels, info, s);
+    FH_HIP(hipGetLastError());
+}
+
+void Gallery::set_ids(const int* ids, bool device_src) {
+    if (n_ == 0) return;
+    FH_HIP(hipDeviceSynchronize());                              // queued scans still read the ids that are about to change
+    ids_.ensure(rows_.bytes / ((size_t)dim_ * sizeof(float)) * sizeof(int));      // the ids' capacity follows the rows', as upload keeps it
+    FH_HIP(hipMemcpy(ids_.p, ids, (size_t)n_ * sizeof(int), device_src ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
+    labelled_ = true; fused_ = false;
 }
 
 // Stable compaction through a second buffer: the host reads the ids, lists the surviving positions in order, and whole rows are

@@ -367,6 +367,11 @@ class Gallery {
     bool fused() const { return fused_; }                        // ids distinct and ascending: set by fuse_from, cleared by upload / enroll
     // out[r] = (dot(row r, tmpl's row of row r's id) + 1) / 2, -1 where tmpl has no such id; tmpl.fused() required.  Asynchronous.
     void self_scores_dev(const Gallery& tmpl, float* out, hipStream_t s);
+    // Exact DBSCAN over the fp32 rows (gallery_cluster.hip; the rule: cluster_plan.h): labels [size] = positions, info [4] (may be null),
+    // both device.  Arguments checked by the caller.  Asynchronous; the scratch (16 bytes per row) is cleared on s at every call.
+    void cluster_dev(float thr, int min_pts, bool noise_self, int* labels, int* info, hipStream_t s);
+    // replaces every row's id by position (host or device list, checked by the caller: none negative); synchronous
+    void set_ids(const int* ids, bool device_src);
     bool labelled() const { return labelled_; }
     long size() const { return n_; }
     int dim() const { return dim_; }
@@ -388,6 +393,7 @@ class Gallery {
     bool labelled_ = false;                                      // meaningful while n_ > 0; an empty gallery takes either kind
     bool fused_ = false;
     DevBuf rows_, qpack_, ps_, pi_, best_i_, seed_s_, seed_i_;
+    DevBuf cl_deg_, cl_parent_, cl_best_;                        // cluster_dev: degree, union-find parent, best core neighbour per row
     DevBuf ids_, pd_, seed_d_;                                   // identity id per row (capacity in rows = rows_'), id planes of the part / seed lists
     // F16_RERANK state: the fp16 rows, [max|g|, max|g^|, max|g - g^| (float bits), non-finite / > 65504 flag] on the device and its host
     // copy, per-call scratch, the certified / fallback counters

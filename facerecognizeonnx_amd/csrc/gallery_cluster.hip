@@ -1,0 +1,325 @@
+// gallery_cluster.hip — exact DBSCAN over the rows of a gallery (fh_gallery_cluster_dev): the rule of cluster_plan.h on the matrix
+// s(i, j) = the mapped score the fp32 scan (gallery_scan.h) reports for query = row i against row j.
+//
+// The pair pass is the scan's arithmetic with another epilogue.  Tile layout and operand placement are gallery_scan_body's: the gallery
+// is the A operand — each wave streams ITS OWN 32 rows into registers, one 64-deep chunk ahead — and it is also the B operand: a 64-row
+// tile goes through the swizzled, double-buffered LDS image the scan keeps its queries in, loaded from the rows themselves.  Rows at or
+// beyond G read the zero line and are masked.  The K loop issues the same v_mfma_f32_32x32x2_f32 sequence in the same k order (k0 =
+// 64 kc + 8 s + e, k1 = k0 + 4), so an accumulator has the scan's bits; the chain is symmetric in its operands (a product commutes), so
+// s(i, j) and s(j, i) have the same bits and every unordered pair is evaluated ONCE: a workgroup owns one B tile (64 columns) and a
+// run of A tiles (128 rows each); A tiles wholly below the diagonal are skipped and `row < col` masks the straddling ones.  (A shared
+// K loop with the scan is a later refactor with its own ISA comparison; gallery_scan_body is not touched here.)
+//
+// Launches of one call, all on the caller's stream:
+//   init      deg[i] = 0, parent[i] = i, best[i] = 0, info[0..3] = 0
+//   degree    (skipped when min_pts == 1) deg[i] = edges at i.  The B side — one column per lane pair — is counted in registers over
+//             the run, summed through LDS and flushed with one global atomicAdd per column per run.  The A side needs a reduction across
+//             lanes: __ballot of the edge predicate per accumulator position holds, in its low and high 32 bits, the counts of the two
+//             rows of that position; lane r of the wave keeps row r's count and adds it once per tile.
+//   link      the same pass with core[i] = deg[i] + 1 >= min_pts.  An edge between two cores is a union in a lock-free union-find on
+//             parent[]: find both roots, CAS the LARGER root's parent from itself to the smaller root, on failure go on from the value
+//             the CAS returned.  parent[x] <= x always and only ever decreases, so there are no cycles and a component's final root is
+//             its smallest core position — the label the rule asks for, whatever order the edges arrive in.  An edge from a core to a
+//             non-core row is a 64-bit atomicMax on best[non-core]: monotone-mapped score bits in the high word, ~position of the core
+//             in the low word, so the maximum is exactly gal_better's choice (a real key is never 0: ~position has its top bit set).
+//   flatten   label = root for cores, root of best's core for border rows, -1 / own position for noise; the four counters.
+//
+// Memory model (MI355X: eight XCDs whose L2s are not coherent with each other, and a vector L1 that another CU's stores never refresh):
+// inside the link kernel EVERY read of parent[] is an agent-scope relaxed atomic load (served by L2, never by a stale L1 line) and
+// every write is an atomic RMW (atomicCAS; atomicMin for the path halving).  A find that kept seeing a stale "I am a root" would fail
+// its CAS for ever.  No loop in these kernels waits for another workgroup: a failed CAS means some thread has ALREADY linked that
+// root, and the retry starts from the returned parent, strictly below the root it tried — the larger of the two roots in hand strictly
+// descends, so a union ends after at most `position` rounds whatever the others do.  deg[] and best[] are only written (atomics) in the
+// kernel that builds them and read by plain loads in a later launch.
+#include <hip/hip_runtime.h>
+
+#include <stdexcept>
+
+#include "gallery_scan.h"
+#include "kernels.h"
+
+namespace fh {
+
+namespace {
+
+struct ClusterArgs {
+    const float* gal;                   // [G][dim]
+    const float* zeros;
+    long G;
+    int dim, tiles_n, row_tiles, tiles_per_wg, min_pts;
+    float thr;
+    int* deg;                           // [G]
+    int* parent;                        // [G]
+    unsigned long long* best;           // [G]
+};
+
+__device__ __forceinline__ int parent_load(const int* parent, int x) {
+    return __hip_atomic_load(parent + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// root of x; halves the path on the way (atomicMin: a parent only ever decreases, and a grandparent is an ancestor)
+__device__ __forceinline__ int cluster_find(int* parent, int x) {
+    int p = parent_load(parent, x);
+    while (p != x) {
+        const int gp = parent_load(parent, p);
+        if (gp != p) atomicMin(parent + x, gp);
+        x = p; p = gp;
+    }
+    return x;
+}
+
+__device__ __forceinline__ void cluster_union(int* parent, int a, int b) {
+    int ra = cluster_find(parent, a), rb = cluster_find(parent, b);
+    while (ra != rb) {                                       // (roots already equal: no atomic at all — the common case in a dense cluster)
+        const int hi = max(ra, rb), lo = min(ra, rb);
+        const int old = atomicCAS(parent + hi, hi, lo);
+        if (old == hi) break;                                // linked
+        ra = cluster_find(parent, old);                      // hi had been linked already: old < hi, go on from there
+        rb = cluster_find(parent, lo);
+    }
+}
+
+// score bits -> unsigned, monotone in the score (scores here are (acc + 1) / 2, never NaN past the edge test and never -0)
+__device__ __forceinline__ unsigned long long cluster_key(float s, int pos) {
+    const unsigned u = __float_as_uint(s);
+    const unsigned m = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+    return ((unsigned long long)m << 32) | (unsigned)~pos;
+}
+
+template <bool LINK>
+__device__ __forceinline__ void cluster_pair_body(const ClusterArgs& p) {
+    constexpr int BM = GAL_BM, BN = GAL_BN, TN = BN / 32, CD = 64;
+    __shared__ v4f ldsq[2][BN * 16];                          // B chunk [64 rows][64 k], 16-byte column XOR (row & 15)
+    __shared__ int colcnt[BN];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int fr = lane & 31, fh2 = lane >> 5;
+    const int bt = (int)(blockIdx.x % (unsigned)p.tiles_n), run = (int)(blockIdx.x / (unsigned)p.tiles_n);
+    const long n0 = (long)bt * BN;
+    // A tiles that hold a row below some column of this B tile: rt * 128 <= n0 + 62
+    const int rt0 = run * p.tiles_per_wg, rt1 = min(min(p.row_tiles, (int)((n0 + BN - 2) / BM) + 1), rt0 + p.tiles_per_wg);
+    if (rt0 >= rt1) return;                                   // (workgroup-uniform, before any barrier)
+    const int K = p.dim, chunks = K / CD;
+    if (tid < BN) colcnt[tid] = 0;
+
+    // B loader: pass i fills rows i*16 + (tid >> 4), slot tid & 15 <- source 16-byte column (tid & 15) ^ (row & 15)
+    const int qrow = tid >> 4;
+    const int bcol = ((tid & 15) ^ (qrow & 15)) * 4;
+    const float* b_base[4];
+    int b_step[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const long brow = n0 + qrow + 16 * i;
+        const bool live = brow < p.G;
+        b_base[i] = (live ? p.gal + (size_t)brow * K : p.zeros) + bcol;
+        b_step[i] = live ? CD : 0;
+    }
+    const int fsw = fr & 15;
+
+    // what the epilogue knows about this lane's columns
+    long col[TN];
+    bool col_ok[TN];
+    bool col_core[TN];
+    int col_deg[TN];
+#pragma unroll
+    for (int j = 0; j < TN; ++j) {
+        col[j] = n0 + j * 32 + fr;
+        col_ok[j] = col[j] < p.G;
+        col_deg[j] = 0;
+        col_core[j] = false;
+        if constexpr (LINK) col_core[j] = col_ok[j] && p.deg[col[j]] + 1 >= p.min_pts;
+    }
+
+    for (int rt = rt0; rt < rt1; ++rt) {
+        const long m0 = (long)rt * BM;
+        const long myrow = m0 + wid * 32 + fr;
+        const bool live = myrow < p.G;
+        const float* a_ptr = (live ? p.gal + (size_t)myrow * K : p.zeros) + fh2 * 4;
+        const int a_step = live ? CD : 0;
+        const float* b_src[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) b_src[i] = b_base[i];
+        v4f xa[2][8];
+        auto load_a = [&](v4f (&x)[8]) {                      // 16-byte column 2s + fh2 of the chunk
+#pragma unroll
+            for (int s = 0; s < 8; ++s) x[s] = *reinterpret_cast<const v4f*>(a_ptr + s * 8);
+            a_ptr += a_step;
+        };
+        v16f acc[TN];
+#pragma unroll
+        for (int j = 0; j < TN; ++j)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) acc[j][e] = 0.f;
+        auto multiply = [&](const v4f (&x)[8], int buf) {
+            const v4f* Wt = ldsq[buf] + fr * 16;
+#pragma unroll
+            for (int s = 0; s < 8; ++s) {
+                const int c = (2 * s + fh2) ^ fsw;
+                v4f w[TN];
+#pragma unroll
+                for (int j = 0; j < TN; ++j) w[j] = Wt[j * 32 * 16 + c];
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+#pragma unroll
+                    for (int j = 0; j < TN; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(x[s][e], w[j][e], acc[j], 0, 0, 0);
+            }
+        };
+        // B chunk: global -> registers -> LDS, issued before the row loads (see gallery_scan_body for why not LDS-DMA)
+        v4f qv[4];
+        auto fetch_b = [&]() {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) { qv[i] = *reinterpret_cast<const v4f*>(b_src[i]); b_src[i] += b_step[i]; }
+        };
+        auto store_b = [&](int buf) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) ldsq[buf][i * 256 + tid] = qv[i];
+        };
+        __syncthreads();                                   // the previous tile's last multiply is done with ldsq
+        fetch_b();
+        load_a(xa[0]);
+        store_b(0);
+        int kc = 0;
+        for (; kc + 2 <= chunks; kc += 2) {
+            __syncthreads();
+            fetch_b();
+            load_a(xa[1]);
+            __builtin_amdgcn_sched_barrier(0);
+            multiply(xa[0], 0);
+            store_b(1);
+            __syncthreads();
+            if (kc + 2 < chunks) { fetch_b(); load_a(xa[0]); }
+            __builtin_amdgcn_sched_barrier(0);
+            multiply(xa[1], 1);
+            if (kc + 2 < chunks) store_b(0);
+        }
+        if (kc < chunks) {                                 // odd number of chunks
+            __syncthreads();
+            multiply(xa[0], 0);
+        }
+
+        // ---- epilogue: accumulator e of block j is (row rbase + 8 * (e >> 2) + (e & 3), column col[j])
+        const long wrow0 = m0 + wid * 32;
+        const long rbase = wrow0 + 4 * fh2;
+        if constexpr (!LINK) {
+            int row_deg = 0;                               // lane r < 32: edges found at row wrow0 + r in this tile
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                const long row = rbase + 8 * (e >> 2) + (e & 3);
+                int lo = 0, hi = 0;
+#pragma unroll
+                for (int j = 0; j < TN; ++j) {
+                    const float sc = (acc[j][e] + 1.0f) / 2.0f;
+                    const bool edge = col_ok[j] && row < col[j] && sc > p.thr;      // (row < col < G)
+                    col_deg[j] += edge ? 1 : 0;
+                    const unsigned long long b = __ballot(edge);
+                    lo += __popc((unsigned)b); hi += __popc((unsigned)(b >> 32));
+                }
+                const int r_lo = 8 * (e >> 2) + (e & 3);
+                row_deg += lane == r_lo ? lo : lane == r_lo + 4 ? hi : 0;
+            }
+            if (lane < 32 && row_deg > 0) atomicAdd(p.deg + wrow0 + lane, row_deg);    // (row_deg > 0 implies the row is below G)
+        } else {
+            const long arow = wrow0 + fr;
+            const unsigned row_core = (unsigned)__ballot(arow < p.G && p.deg[arow < p.G ? arow : 0] + 1 >= p.min_pts);   // bit r: row wrow0 + r
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                const int r = 8 * (e >> 2) + (e & 3) + 4 * fh2;
+                const long row = wrow0 + r;
+                const bool rc = (row_core >> r) & 1u;
+#pragma unroll
+                for (int j = 0; j < TN; ++j) {
+                    const float sc = (acc[j][e] + 1.0f) / 2.0f;
+                    if (col_ok[j] && row < col[j] && sc > p.thr) {
+                        if (rc && col_core[j]) cluster_union(p.parent, (int)row, (int)col[j]);
+                        else if (rc) atomicMax(p.best + col[j], cluster_key(sc, (int)row));
+                        else if (col_core[j]) atomicMax(p.best + row, cluster_key(sc, (int)col[j]));
+                    }
+                }
+            }
+        }
+    }
+    if constexpr (!LINK) {
+#pragma unroll
+        for (int j = 0; j < TN; ++j)
+            if (col_deg[j] > 0) atomicAdd(&colcnt[j * 32 + fr], col_deg[j]);
+        __syncthreads();
+        if (tid < BN && colcnt[tid] > 0) atomicAdd(p.deg + n0 + tid, colcnt[tid]);     // (a count > 0 implies the column is below G)
+    }
+}
+
+__global__ __launch_bounds__(256, 2) void cluster_degree_kernel(const ClusterArgs p) { cluster_pair_body<false>(p); }
+__global__ __launch_bounds__(256, 2) void cluster_link_kernel(const ClusterArgs p) { cluster_pair_body<true>(p); }
+
+__global__ __launch_bounds__(256) void cluster_init_kernel(long G, int* deg, int* parent, unsigned long long* best, int* info) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i < G) { deg[i] = 0; parent[i] = (int)i; best[i] = 0ull; }
+    if (info && i < 4) info[i] = 0;
+}
+
+// a separate launch: everything the link kernel wrote is visible, plain loads are fine
+__global__ __launch_bounds__(256) void cluster_flatten_kernel(long G, int min_pts, int noise_self, const int* __restrict__ deg,
+                                                              const int* __restrict__ parent, const unsigned long long* __restrict__ best,
+                                                              int* __restrict__ labels, int* info) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    bool core = false, border = false, root = false, noise = false;
+    if (i < G) {
+        core = deg[i] + 1 >= min_pts;
+        const unsigned long long b = best[i];
+        border = !core && b != 0ull;
+        noise = !core && !border;
+        int label = noise_self ? (int)i : -1;
+        if (core || border) {
+            int x = core ? (int)i : (int)~(unsigned)b;
+            while (parent[x] != x) x = parent[x];
+            label = x;
+            root = core && x == (int)i;
+        }
+        labels[i] = label;
+    }
+    if (info) {
+        const int c0 = __popcll(__ballot(root)), c1 = __popcll(__ballot(core)), c2 = __popcll(__ballot(border)), c3 = __popcll(__ballot(noise));
+        if ((threadIdx.x & 63) == 0) {
+            if (c0) atomicAdd(info + 0, c0);
+            if (c1) atomicAdd(info + 1, c1);
+            if (c2) atomicAdd(info + 2, c2);
+            if (c3) atomicAdd(info + 3, c3);
+        }
+    }
+}
+
+int g_cluster_tiles = 0;
+
+}  // namespace
+
+void cluster_debug_tiles(int tiles_per_wg) { g_cluster_tiles = tiles_per_wg > 0 ? tiles_per_wg : 0; }
+
+void launch_gallery_cluster(const float* gal, long G, int dim, float thr, int min_pts, bool noise_self, int* deg, int* parent,
+                            unsigned long long* best, int* labels, int* info, hipStream_t s) {
+    if (G <= 0) return;
+    if (dim % 64) throw std::runtime_error("gallery: dim must be a multiple of 64");
+    ClusterArgs a{};
+    a.gal = gal; a.zeros = conv_zero_line(); a.G = G; a.dim = dim; a.min_pts = min_pts; a.thr = thr;
+    a.deg = deg; a.parent = parent; a.best = best;
+    a.tiles_n = (int)((G + GAL_BN - 1) / GAL_BN);
+    a.row_tiles = (int)((G + GAL_BM - 1) / GAL_BM);
+    // A tiles per workgroup: a longer run flushes the column counts less often and re-reads the core flags less often, a shorter one
+    // balances the triangle better; runs only grow once every CU has several workgroups' worth of live tile pairs anyway
+    const long pairs = (long)a.tiles_n * a.row_tiles / 2;
+    long t = g_cluster_tiles;
+    if (t <= 0) {
+        t = pairs / (16L * conv_num_cus());
+        t = t < 1 ? 1 : t > 8 ? 8 : t;
+    }
+    a.tiles_per_wg = (int)(t > a.row_tiles ? a.row_tiles : t);
+    // a rectangular grid of (B tile, run): the last B tile reaches every row tile; runs wholly below a B tile's diagonal exit at once
+    const long runs = (a.row_tiles + a.tiles_per_wg - 1) / a.tiles_per_wg;
+    const long grid = runs * a.tiles_n;
+    if (grid > 0x7fffffffL) throw std::runtime_error("gallery: too many rows for one clustering launch");
+    const unsigned gb = (unsigned)((G + 255) / 256);
+    hipLaunchKernelGGL(cluster_init_kernel, dim3(gb), dim3(256), 0, s, G, deg, parent, best, info);
+    if (min_pts > 1) hipLaunchKernelGGL(cluster_degree_kernel, dim3((unsigned)grid), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(cluster_link_kernel, dim3((unsigned)grid), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(cluster_flatten_kernel, dim3(gb), dim3(256), 0, s, G, min_pts, noise_self ? 1 : 0, deg, parent, best, labels, info);
+}
+
+}  // namespace fh

@@ -370,6 +370,12 @@ void launch_gallery_fuse_sum(const float* src, const int* order, const FuseItem*
 void launch_gallery_self_scores(const float* src, const int* src_ids, long n, const float* tmpl, const int* tmpl_ids, long m, int dim,
                                 float* out, hipStream_t s);
 
+// gallery_cluster.hip — exact DBSCAN over the gallery's own rows (fh_gallery_cluster_dev; the rule: cluster_plan.h): init, degree pass
+// (min_pts > 1), link pass and flatten on s.  deg / parent [G] and best [G] are scratch; labels [G] and info [4] (may be null) the result.
+void launch_gallery_cluster(const float* gal, long G, int dim, float thr, int min_pts, bool noise_self, int* deg, int* parent,
+                            unsigned long long* best, int* labels, int* info, hipStream_t s);
+void cluster_debug_tiles(int tiles_per_wg);   // test hook: A tiles per workgroup run of the pair passes (0 = automatic)
+
 // gallery_f16.hip — the opt-in F16_RERANK scan (fh_gallery_set_scan): an fp16 copy of the rows is scanned for the top GAL16_KC candidates
 // per query, the candidates are re-scored from the fp32 rows exactly as gallery_topk_kernel scores them, and a per-query certificate
 // proves that no other row can reach the top-k; uncertified queries are compacted on the device (fb_count / fb_idx) for the fp32 scan.

@@ -585,6 +585,42 @@ FH_API long long fh_gallery_fuse_ids(fh_gallery* src, fh_gallery* dst, int mode)
 FH_API long long fh_gallery_get_rows(fh_gallery* g, long long first, long long n, float* rows_host_out);
 FH_API int fh_gallery_self_scores_dev(fh_gallery* src, fh_gallery* tmpl, float* d_scores, void* stream);
 
+/* ---- unsupervised grouping: rows in, one identity label per row out (exact DBSCAN).  Everything above needs ids that come from outside;
+ * the embeddings of a photo collection, the pooled templates of the tracker's tracks and the "Unknown" faces of the identified pipeline
+ * have none.  The output feeds the calls above: fh_gallery_set_ids -> fh_gallery_fuse_ids (one row per person), fh_gallery_self_scores_dev.
+ *   cluster_scores  host only, no GPU, and the one place the rule is defined.  scores[n][n] row-major; labels[n]; info[4] or NULL.
+ *               edge    (i, j), i != j, iff s(i, j) > threshold: strict, in fp32, so a NaN score and a NaN threshold give no edge.  Only
+ *                       the entries with i < j are read: the matrix is taken as symmetric; the self pair is never an edge.
+ *               core    deg(i) = the number of edges at i; row i is core iff deg(i) + 1 >= min_pts (the row counts itself).  min_pts == 1
+ *                       makes every row core: plain single-linkage connected components.
+ *               cluster a connected component of the graph restricted to core rows and core-core edges; its label is the smallest
+ *                       position of a core row in it.
+ *               border  a non-core row with at least one core neighbour takes the label of its best core neighbour: higher score, then
+ *                       lower position (the scan's ranking).  Border rows never link clusters.
+ *               noise   every other row: label -1 (FH_CLUSTER_NOISE_NONE) or its own position (FH_CLUSTER_NOISE_SELF; no collision: a
+ *                       cluster's label is a core row's position).
+ *               info    {clusters, core rows, border rows, noise rows}; the last three sum to n.
+ *               Returns the number of clusters; n == 0 returns 0.  FH_ERR_ARG, nothing written: NULL scores or labels with n > 0, n < 0,
+ *               min_pts < 1, an unknown noise mode.  All indexing in 64 bits; 16 bytes of host scratch per row.
+ *   cluster_dev     exactly cluster_scores on s(i, j) = the fp32 mapped score fh_gallery_topk_dev reports for query = row i against
+ *               row j — the v_mfma_f32_32x32x2_f32 chain in k order (k0 = 64 kc + 8 s + e, k1 = k0 + 4), then (acc + 1.0f) / 2.0f — so
+ *               "row i and row j are linked" means precisely "the scan scores the pair above the threshold"; the chain is symmetric in
+ *               its operands, so s(i, j) and s(j, i) have the same bits and every pair is evaluated once.  d_labels[size] are positions,
+ *               0-based (the index base plays no part); ids are ignored (labelled and unlabelled galleries alike); the fp32 rows are
+ *               read whatever the scan mode.  Asynchronous on `stream`; returns FH_OK.  An empty gallery writes zeros to d_info and
+ *               nothing else.  dim % 64 == 0 as for every scan.  FH_ERR_ARG before anything is launched: the errors of cluster_scores,
+ *               a NULL handle or d_labels.  Scratch lives in the handle and grows on demand — 4 bytes (degree) + 4 (union-find parent) +
+ *               8 (best core neighbour) per row — and is cleared on `stream` at the start of every call.  Two G x G pair passes (degree,
+ *               then link; min_pts == 1 skips the first) and a flatten; labels and counters are identical to the host rule's, not close.
+ *   set_ids     replaces the ids of ALL rows by position (ids[size], host or device) and makes an unlabelled gallery labelled;
+ *               synchronous like enroll; returns the row count.  An id < 0 returns FH_ERR_ARG and changes nothing.  Clears the handle's
+ *               "fused" mark (fh_gallery_self_scores_dev); rows, the fp16 copy and the scan mode are untouched.  The intended flow with
+ *               FH_CLUSTER_NOISE_SELF: fh_gallery_cluster_dev -> fh_gallery_set_ids(d_labels, 1) -> fh_gallery_fuse_ids. */
+enum fh_cluster_noise { FH_CLUSTER_NOISE_NONE = 0, FH_CLUSTER_NOISE_SELF = 1 };
+FH_API int fh_cluster_scores(const float* scores, int n, float threshold, int min_pts, int noise, int* labels, int* info);
+FH_API int fh_gallery_cluster_dev(fh_gallery* g, float threshold, int min_pts, int noise, int* d_labels, int* d_info, void* stream);
+FH_API long long fh_gallery_set_ids(fh_gallery* g, const int* ids, int on_device);
+
 /* ---- measurement hooks (bench.py): per-launch HIP-event timing of the network kernels.
  * Tags 0..3 = conv_igemm tile configs (128x128, 256x64, 128x32, 64x64), 4 = depthwise / depthwise+pointwise,
  * 5 = other graph ops, 6 = conv stream-K fix-up, 7 = Winograd GEMM (its FLOPs = executed; bytes slot = the layer's
@@ -692,6 +728,10 @@ FH_API int fh_debug_streamk(int drop_publish, int timeout_ms);
  * slots walk several tiles per workgroup; slots > 0 makes the launcher pretend the device has that many (rounded up to 8), so that small
  * test layers take the multi-tile path with many tiles per workgroup; 0 restores the device's own count. */
 FH_API int fh_debug_wino_slots(int slots);
+/* Test hook of the clustering pair passes (gallery_cluster.hip): a workgroup walks a run of A tiles (128 rows each) against its B tile, and
+ * the launcher gives runs of more than one tile only to large galleries; tiles_per_wg > 0 fixes the run length, so that a small gallery
+ * walks runs of several tiles; 0 restores the automatic choice. */
+FH_API int fh_debug_cluster_tiles(int tiles_per_wg);
 /* Test hook of the split-bf16 operand format (winograd.hip wino_pack_bf16x2): n f32 words -> n packed words, hi = bf16(x) in the low half,
  * mid = bf16(x - hi) in the high half, both round-to-nearest-even.  n % 4 == 0.  Synchronous. */
 FH_API int fh_debug_pack_bf16x2_dev(const float* d_in, float* d_out, long long n);
