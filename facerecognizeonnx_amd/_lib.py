@@ -46,6 +46,10 @@ TRACK_MAX = 64                                                 # FH_TRACK_MAX
 TRACK_IDENT_DTYPE = np.dtype([("id", "<i4"), ("n_emb", "<i4"), ("label", "<i4"), ("score", "<f4")])     # fh_track_ident
 assert TRACK_IDENT_DTYPE.itemsize == 16
 TRACK_POOL_LAST, TRACK_POOL_SUM, TRACK_POOL_WEIGHTED = 0, 1, 2    # enum fh_track_pool
+TRACK_LINK_DTYPE = np.dtype([("owner", "<i4"), ("root", "<i4"), ("n_emb", "<i4"), ("label", "<i4"), ("score", "<f4"), ("last_seen", "<i4"),
+                             ("links", "<i4"), ("pad", "<i4")])  # fh_track_link
+assert TRACK_LINK_DTYPE.itemsize == 32
+TRACK_LINK_MEMORY = 256                                        # FH_TRACK_LINK_MEMORY
 
 
 class FhTrackState(C.Structure):
@@ -156,6 +160,10 @@ PROTOTYPES = {
     "fh_tracker_quality_dev": (_vp, [_vp]),
     "fh_track_update_q_dev": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "fh_track_identify_q_dev": (_i, [_vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "fh_tracker_enable_relink": (_i, [_vp, _i, _f, _i]),
+    "fh_track_identify_link_dev": (_i, [_vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "fh_tracker_get_links": (_i, [_vp, _i, _vp, _vp]),
+    "fh_tracker_roots_dev": (_vp, [_vp]),
     "fh_gallery_create": (_vp, [_i]),
     "fh_gallery_destroy": (None, [_vp]),
     "fh_gallery_upload": (_i, [_vp, _vp, _ll, _i, _ll]),

@@ -424,12 +424,20 @@ class Tracker:
         self.identity_dim = int(dim)
 
     def identify_dev(self, gallery, threshold: float, track_ptr: int, slot_ptr: int, embed_ptr: int, emb_ptr, total: int, n: int,
-                     per_frame: int, label_ptr: int, score_ptr: int, stream_of=None, stream: int = 0, quality_ptr=None) -> int:
+                     per_frame: int, label_ptr: int, score_ptr: int, stream_of=None, stream: int = 0, quality_ptr=None,
+                     root_ptr=None) -> int:
         """After update_dev(..., slot_ptr=...) and the embedding of the `total` flagged faces (emb_ptr = [total][dim], in select_dev's
         order): pool each into its track's template, label the templates against `gallery`, and write a label and a score for EVERY
         entry [n][per_frame] — the faces that were not embedded carry their track's.  quality_ptr = the faces' qualities
-        [n][per_frame], which TRACK_POOL_WEIGHTED needs (fh_track_identify_q_dev)."""
+        [n][per_frame], which TRACK_POOL_WEIGHTED needs (fh_track_identify_q_dev).  root_ptr = int32 [n][per_frame] selects
+        fh_track_identify_link_dev: the chain root of every tracked entry (its own track id unless enable_relink() is on), the call a
+        tracker with re-linking on needs."""
         keep, sp = _stream_of(stream_of, n)
+        if root_ptr is not None:
+            return check(_lib.lib().fh_track_identify_link_dev(self._h, gallery._h if gallery is not None else None, float(threshold),
+                                                               track_ptr, slot_ptr, embed_ptr, quality_ptr, emb_ptr, int(total), n,
+                                                               per_frame, sp, label_ptr, score_ptr, root_ptr, stream),
+                         "fh_track_identify_link_dev")
         if quality_ptr is not None:
             return check(_lib.lib().fh_track_identify_q_dev(self._h, gallery._h if gallery is not None else None, float(threshold),
                                                             track_ptr, slot_ptr, embed_ptr, quality_ptr, emb_ptr, int(total), n, per_frame,
@@ -450,6 +458,28 @@ class Tracker:
         live = check(_lib.lib().fh_tracker_get_identity(self._h, int(stream), out.ctypes.data, acc.ctypes.data if sums else None),
                      "fh_tracker_get_identity")
         return (out[:live].copy(), acc[:live].copy()) if sums else out[:live].copy()
+
+    def enable_relink(self, memory: int = 64, link_thr: float = 0.6, max_age: int = 150) -> None:
+        """Switch track re-linking on (after enable_identity): a newly opened track whose first embedding scores above link_thr against
+        the template of a track lost at most max_age frames ago continues it — template, count and chain root.  `memory` = how many
+        lost tracks per stream are remembered beyond those still sitting in slots.  The defaults (the reference's match threshold;
+        five seconds at 30 fps) are a proposal: their effect on accuracy has not been measured.  Clears the identity state."""
+        check(_lib.lib().fh_tracker_enable_relink(self._h, int(memory), float(link_thr), int(max_age)), "fh_tracker_enable_relink")
+        self.link_memory = int(memory)
+
+    def roots_ptr(self) -> int:
+        """Device pointer of the [n][F] chain roots of the last identified pipeline call with re-linking on (a stage hook)."""
+        return _lib.lib().fh_tracker_roots_dev(self._h) or 0
+
+    def links(self, stream: int = 0, sums: bool = False):
+        """The whole re-linking table of one stream by row (slot rows, then the memory) as TRACK_LINK_DTYPE records, free rows with
+        owner = -1; with sums=True: (records, float32 [rows][dim] templates)."""
+        rows = check(_lib.lib().fh_tracker_get_links(self._h, int(stream), None, None), "fh_tracker_get_links")   # the library's count
+        out = np.zeros(rows, _lib.TRACK_LINK_DTYPE)
+        acc = np.zeros((rows, getattr(self, "identity_dim", 0)), np.float32) if sums else None
+        check(_lib.lib().fh_tracker_get_links(self._h, int(stream), out.ctypes.data, acc.ctypes.data if sums else None),
+              "fh_tracker_get_links")
+        return (out, acc) if sums else out
 
     @staticmethod
     def select_dev(det_ptr: int, embed_ptr: int, n: int, per_frame: int, faces_ptr: int, frame_of_ptr: int, track_ptr: int,

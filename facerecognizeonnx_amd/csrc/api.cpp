@@ -1,5 +1,6 @@
 // api.cpp — the extern "C" boundary declared in include/facehip.h.
 #include <algorithm>
+#include <cmath>
 #include <cstddef>
 #include <cstdio>
 #include <cstring>
@@ -20,6 +21,8 @@ static_assert(sizeof(fh_track_state) == sizeof(fh::TrackState) && offsetof(fh_tr
               FH_TRACK_MAX == 64, "fh_track_state mirrors TrackState; one slot per lane of a wave");
 static_assert(sizeof(fh_track_ident) == 16 && sizeof(fh::TrackIdent) == 16 && offsetof(fh_track_ident, score) == offsetof(fh::TrackIdent, score),
               "fh_track_ident mirrors TrackIdent");
+static_assert(sizeof(fh_track_link) == 32 && sizeof(fh::TrackLink) == 32 && offsetof(fh_track_link, last_seen) == offsetof(fh::TrackLink, last_seen) &&
+              FH_TRACK_LINK_MEMORY == fh::kTrackLinkMemory, "fh_track_link mirrors TrackLink");
 static_assert(FH_TRACK_POOL_LAST == fh::kTrackPoolLast && FH_TRACK_POOL_SUM == fh::kTrackPoolSum && FH_TRACK_POOL_WEIGHTED == fh::kTrackPoolWeighted,
               "fh_track_pool mirrors the pool kernel's modes");
 static_assert(sizeof(fh_tiling) == sizeof(fh::Tiling) && offsetof(fh_tiling, border) == offsetof(fh::Tiling, border) &&
@@ -1046,6 +1049,10 @@ int fh_track_identify_q_dev(fh_tracker* t, fh_gallery* g, float threshold, const
     if (total < 0 || (long long)total > (long long)n * per_frame) return frames_error(fn, "need 0 <= total <= n * per_frame");
     if (total > 0 && !emb) return frames_error(fn, "null embeddings with total > 0");
     if (!quality && t->t.identity_pool() == FH_TRACK_POOL_WEIGHTED) return frames_error(fn, "the weighted pool needs the qualities (fh_track_identify_q_dev)");
+    if (t->t.relink()) {
+        g_err = std::string(fn) + ": re-linking is on for this tracker: call fh_track_identify_link_dev";
+        return FH_ERR_STATE;
+    }
     return guarded([&] {
         t->t.identify_dev(g->g, threshold, track, slot, embed, quality, emb, total, n, per_frame, stream_of, label, score, S(stream));
         return n;
@@ -1082,11 +1089,50 @@ int fh_pipeline_run_identified_dev(fh_det* d, fh_rec* r, fh_tracker* t, fh_galle
         int* const slot = t->t.slot_scratch((size_t)n * F);
         const int total = pipeline_tracked(d, r, t, frames, n, rows, cols, step, stride, stream_of, score_thr, nms_thr, F, all, counts, track,
                                            flags, slot, faces, frame_of, track_of, emb, s);
+        // re-linking on: the link form of the identify step, into the tracker's roots buffer (fh_tracker_roots_dev)
         t->t.identify_dev(g->g, threshold, track, slot, flags, t->t.bestshot() ? t->t.quality() : nullptr, emb, total, n, F, stream_of, label,
-                          score, s);
+                          score, s, t->t.relink() ? t->t.roots_scratch((size_t)n * F) : nullptr);
         return total;
     });
 }
+
+// ---------------------------------------------------------------------------------- track re-linking
+int fh_tracker_enable_relink(fh_tracker* t, int memory, float link_thr, int max_age) {
+    if (!t) return arg_error("fh_tracker_enable_relink: null handle");
+    if (t->t.identity_dim() == 0) {
+        g_err = "fh_tracker_enable_relink: identity is not enabled (fh_tracker_enable_identity)";
+        return FH_ERR_STATE;
+    }
+    if (memory < 0 || memory > fh::kTrackLinkMemory || !std::isfinite(link_thr) || max_age <= t->t.max_missed())
+        return arg_error("fh_tracker_enable_relink: need 0 <= memory <= 256, a finite link_thr and max_age > max_missed");
+    return guarded([&] { t->t.enable_relink(memory, link_thr, max_age); return 0; });
+}
+int fh_track_identify_link_dev(fh_tracker* t, fh_gallery* g, float threshold, const int* track, const int* slot, const int* embed,
+                               const int* quality, const float* emb, int total, int n, int per_frame, const int* stream_of, int* label,
+                               float* score, int* root, void* stream) {
+    const char* const fn = "fh_track_identify_link_dev";
+    if (!t || !g || !track || !slot || !embed || !label || !score || !root) return frames_error(fn, "null argument");
+    if (const char* bad = bad_track_batch(t, n, per_frame, stream_of)) return frames_error(fn, bad);
+    if (const char* bad = bad_identity(t, g)) return frames_error(fn, bad);
+    if (total < 0 || (long long)total > (long long)n * per_frame) return frames_error(fn, "need 0 <= total <= n * per_frame");
+    if (total > 0 && !emb) return frames_error(fn, "null embeddings with total > 0");
+    if (!quality && t->t.identity_pool() == FH_TRACK_POOL_WEIGHTED) return frames_error(fn, "the weighted pool needs the qualities");
+    return guarded([&] {
+        t->t.identify_dev(g->g, threshold, track, slot, embed, quality, emb, total, n, per_frame, stream_of, label, score, S(stream), root);
+        return n;
+    });
+}
+int fh_tracker_get_links(fh_tracker* t, int stream, fh_track_link* out, float* sums_out) {
+    if (!t || (!out && sums_out)) return arg_error("fh_tracker_get_links: null argument");
+    if (stream < 0 || stream >= t->t.streams()) return arg_error("fh_tracker_get_links: no such stream");
+    if (!t->t.relink()) {
+        g_err = "fh_tracker_get_links: re-linking is not enabled (fh_tracker_enable_relink)";
+        return FH_ERR_STATE;
+    }
+    if (!out) return t->t.link_rows();                           // the size query: nothing is written
+    return guarded([&] { t->t.get_links(stream, reinterpret_cast<fh::TrackLink*>(out), sums_out); return t->t.link_rows(); });
+}
+const int* fh_tracker_roots_dev(fh_tracker* t) { return t ? t->t.roots() : nullptr; }
 
 // ---------------------------------------------------------------------------------- streaming front end (host frames)
 // The caller of the path (reference testWebcam, src/main.cpp:214-258: grab a frame, detect, embed every face, compare) over

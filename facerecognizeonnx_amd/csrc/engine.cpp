@@ -1310,6 +1310,7 @@ void Tracker::reset(int stream) {
     FH_HIP(hipMemset(heads() + 2 * (size_t)first, 0, (size_t)count * 2 * sizeof(int)));
     FH_HIP(hipMemcpy(slots() + (size_t)first * p_.max_tracks, free_slots.data(), free_slots.size() * sizeof(TrackState), hipMemcpyHostToDevice));
     if (idim_ > 0) clear_identity(first, count);                 // track ids restart at 0: a stale owner must not survive
+    if (relink_) clear_links(first, count);
     if (best_.p) FH_HIP(hipMemset(best_.as<int>() + (size_t)first * p_.max_tracks, 0, (size_t)count * p_.max_tracks * sizeof(int)));
 }
 
@@ -1350,7 +1351,45 @@ void Tracker::enable_identity(int dim, int pool) {
     ident_.ensure(entries * sizeof(TrackIdent));
     isum_.ensure(entries * dim * sizeof(float));
     idim_ = dim; ipool_ = pool;
+    relink_ = false;
     clear_identity(0, streams_);
+}
+
+void Tracker::clear_links(int first, int count) {
+    const size_t rows = (size_t)link_rows(), entries = (size_t)count * rows;
+    const std::vector<TrackLink> none(entries, TrackLink{-1, -1, 0, -1, -1.0f, 0, 0, 0});
+    FH_HIP(hipMemcpy(link_.as<TrackLink>() + (size_t)first * rows, none.data(), entries * sizeof(TrackLink), hipMemcpyHostToDevice));
+    const size_t per = (size_t)lp_.memory * idim_;
+    if (per > 0) FH_HIP(hipMemset(msum_.as<float>() + (size_t)first * per, 0, (size_t)count * per * sizeof(float)));
+}
+
+void Tracker::enable_relink(int memory, float thr, int max_age) {
+    FH_HIP(hipDeviceSynchronize());                              // a queued identify still reads and writes the state
+    lp_ = TrackLinkParams{memory, thr, p_.max_missed, max_age};
+    link_.ensure((size_t)streams_ * link_rows() * sizeof(TrackLink));
+    msum_.ensure(std::max<size_t>((size_t)streams_ * memory * idim_ * sizeof(float), 16));
+    relink_ = true;
+    clear_identity(0, streams_);
+    clear_links(0, streams_);
+}
+
+void Tracker::get_links(int stream, TrackLink* out, float* sums_out) {
+    FH_HIP(hipDeviceSynchronize());
+    const size_t mt = (size_t)p_.max_tracks, rows = (size_t)link_rows();
+    FH_HIP(hipMemcpy(out, link_.as<TrackLink>() + (size_t)stream * rows, rows * sizeof(TrackLink), hipMemcpyDeviceToHost));
+    std::vector<TrackIdent> ident(mt);
+    FH_HIP(hipMemcpy(ident.data(), ident_.as<TrackIdent>() + (size_t)stream * mt, mt * sizeof(TrackIdent), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < mt; ++i) {                            // a slot's (label, score) are stage C's; a free row reports nothing
+        if (out[i].owner != -1) { out[i].label = ident[i].label; out[i].score = ident[i].score; }
+        else out[i] = TrackLink{-1, -1, 0, -1, -1.0f, 0, 0, 0};
+    }
+    if (!sums_out) return;
+    FH_HIP(hipMemcpy(sums_out, isum_.as<float>() + (size_t)stream * mt * idim_, mt * idim_ * sizeof(float), hipMemcpyDeviceToHost));
+    if (lp_.memory > 0)
+        FH_HIP(hipMemcpy(sums_out + mt * idim_, msum_.as<float>() + (size_t)stream * lp_.memory * idim_,
+                         (size_t)lp_.memory * idim_ * sizeof(float), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < rows; ++i)                            // a free row reports a zero sum
+        if (out[i].owner == -1) std::fill(sums_out + i * idim_, sums_out + (i + 1) * idim_, 0.0f);
 }
 
 int Tracker::get_identity(int stream, TrackIdent* out, float* sums_out) {
@@ -1407,7 +1446,7 @@ void Tracker::update_dev(const FaceRec* det, const int* counts, int n, int per_f
 // Pool first, label the whole batch of queries, propagate afterwards: the gallery scan wants every query of the call at once, and only
 // the per-slot chains of stages A and C are serial.
 void Tracker::identify_dev(Gallery& g, float thr, const int* track, const int* slot, const int* embed, const int* quality, const float* emb,
-                           int total, int n, int per_frame, const int* stream_of, int* label, float* score, hipStream_t s) {
+                           int total, int n, int per_frame, const int* stream_of, int* label, float* score, hipStream_t s, int* root) {
     const size_t bytes = ((size_t)n + streams_ + 1) * sizeof(int);
     int* order = static_cast<int*>(iplan_.stage(bytes));
     if (track_plan(stream_of, n, streams_, order, order + n) != 0) throw std::runtime_error("tracker: bad stream_of");   // (checked by the caller)
@@ -1418,8 +1457,15 @@ void Tracker::identify_dev(Gallery& g, float thr, const int* track, const int* s
     frame_off_.ensure(((size_t)n + 1) * sizeof(int));
     const int* d_order = static_cast<const int*>(iplan_.send(bytes, s));
     launch_track_ranks(embed, n, per_frame, frame_off_.as<int>(), s);
-    launch_track_pool(ident_.as<TrackIdent>(), isum_.as<float>(), streams_, p_.max_tracks, idim_, ipool_, track, slot, embed,
-                      quality, frame_off_.as<int>(), emb, total, per_frame, d_order, d_order + n, queries_.as<float>(), s);
+    if (relink_) {
+        launch_track_link(link_.as<TrackLink>(), ident_.as<TrackIdent>(), isum_.as<float>(), msum_.as<float>(), heads(), streams_,
+                          p_.max_tracks, lp_, idim_, ipool_, track, slot, embed, quality, frame_off_.as<int>(), emb, total, per_frame, d_order,
+                          d_order + n, queries_.as<float>(), root, s);
+    } else {
+        launch_track_pool(ident_.as<TrackIdent>(), isum_.as<float>(), streams_, p_.max_tracks, idim_, ipool_, track, slot, embed,
+                          quality, frame_off_.as<int>(), emb, total, per_frame, d_order, d_order + n, queries_.as<float>(), s);
+        if (root) launch_track_roots(track, slot, (long)n * per_frame, root, s);
+    }
     FH_HIP(hipGetLastError());
     const bool ids = g.labelled() && g.size() > 0;               // labels are identity ids / row indices
     for (int c0 = 0; c0 < total; c0 += 256) {

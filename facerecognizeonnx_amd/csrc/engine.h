@@ -287,6 +287,8 @@ class Recognizer {
 // through a StagedTable, so the next call may follow at once with another stream_of.  Identity (enable_identity; track_ident.hip): one
 // TrackIdent and one fp32 sum row per (stream, slot), pooled, labelled against a gallery and carried forward by identify_dev.  Best
 // shot (set_bestshot): one int32 best_q per (stream, slot), kept by the update kernel when it is given the faces' qualities.
+// Re-linking (enable_relink): per stream a table of max_tracks + memory TrackLink records — the slots' rows, then a memory of lost
+// tracks with sums of its own — through which identify_dev's stage A resumes a lost track when its face comes back.
 class Gallery;
 class Tracker {
   public:
@@ -318,8 +320,20 @@ class Tracker {
     int identity_pool() const { return ipool_; }
     // stages A (pool), B (label through g, chunks of <= 256 queries) and C (propagate) on s; arguments checked by the caller.  quality =
     // device [n][per_frame], needed (and read) by the weighted pool only.
+    // root (optional) = device [n][per_frame]: the entries' chain roots (re-linking off: their own track ids).  With re-linking on it
+    // is needed, and stage A is the link kernel.
     void identify_dev(Gallery& g, float thr, const int* track, const int* slot, const int* embed, const int* quality, const float* emb,
-                      int total, int n, int per_frame, const int* stream_of, int* label, float* score, hipStream_t s);
+                      int total, int n, int per_frame, const int* stream_of, int* label, float* score, hipStream_t s, int* root = nullptr);
+    // re-linking: 0 <= memory <= kTrackLinkMemory, a finite thr, max_age > max_missed and identity enabled, checked by the caller;
+    // synchronous; clears the identity state and the table.  enable_identity switches it off again.
+    void enable_relink(int memory, float thr, int max_age);
+    bool relink() const { return relink_; }
+    int link_rows() const { return p_.max_tracks + lp_.memory; }
+    int max_missed() const { return p_.max_missed; }
+    // the whole table of one stream by row into out[link_rows()] and its sums into sums_out[link_rows()][dim] (may be null); synchronous
+    void get_links(int stream, TrackLink* out, float* sums_out);
+    int* roots_scratch(size_t entries) { roots_.ensure(entries * sizeof(int)); return roots_.as<int>(); }     // the pipeline's roots
+    const int* roots() const { return roots_.as<int>(); }
     const float* queries() const { return queries_.as<float>(); }   // [total][dim] of the last identify_dev
     // the live slots' identities, ascending, into out[max_tracks] (the rest: id = -1) and their sums into sums_out[max_tracks][dim]
     // (may be null); returns their number; synchronous
@@ -338,6 +352,10 @@ class Tracker {
     int idim_ = 0, ipool_ = 0;
     DevBuf ident_, isum_;                                        // [streams][max_tracks] TrackIdent / [streams][max_tracks][idim_] sums
     DevBuf queries_, ans_label_, ans_score_, frame_off_;         // of one identify_dev: [total][idim_], [total], [total], [n + 1]
+    void clear_links(int first, int count);
+    bool relink_ = false;
+    TrackLinkParams lp_{0, 0.f, 0, 0};
+    DevBuf link_, msum_, roots_;                                 // [streams][max_tracks + memory] TrackLink / [streams][memory][idim_] / [n][F]
 };
 
 class Gallery {

@@ -447,4 +447,26 @@ void launch_track_propagate(TrackIdent* ident, int streams, int max_tracks, cons
                             const int* frame_off, const int* ans_label, const float* ans_score, int total, int per_frame, const int* order,
                             const int* starts, int* label, float* score, hipStream_t s);
 
+// Track re-linking (track_ident.hip; include/facehip.h, "track re-linking").  Per stream a table of max_tracks + memory records: rows
+// below max_tracks belong to the slots (their sums are the identity's `sums`), the rest is the memory of lost tracks (`msums`).
+struct TrackLink {          // layout of fh_track_link, 32 B; owner = -1: a free row
+    int32_t owner, root, n_emb, label;
+    float score;
+    int32_t last_seen, links, pad;
+};
+constexpr int kTrackLinkMemory = 256;                                            // memory rows per stream, at most
+struct TrackLinkParams {
+    int memory;             // 0 .. kTrackLinkMemory
+    float link_thr;
+    int max_missed, max_age;
+};
+// stage A with re-linking on: one workgroup per stream; heads = the tracker's [streams][2] (frame_no, next_id) after the update.
+// Writes queries as launch_track_pool does (the untracked faces' copies included) and root[n][per_frame] entirely.
+void launch_track_link(TrackLink* links, TrackIdent* ident, float* sums, float* msums, const int* heads, int streams, int max_tracks,
+                       TrackLinkParams lp, int dim, int pool, const int* track, const int* slot, const int* embed, const int* quality,
+                       const int* frame_off, const float* emb, int total, int per_frame, const int* order, const int* starts, float* queries,
+                       int* root, hipStream_t s);
+// re-linking off: root[i] = track[i] where slot[i] >= 0, else -1 (entries = n * per_frame)
+void launch_track_roots(const int* track, const int* slot, long entries, int* root, hipStream_t s);
+
 }  // namespace fh

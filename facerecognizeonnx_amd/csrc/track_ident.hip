@@ -6,6 +6,7 @@
 //     unit form is FaceRecognizer::normalize (src/face_recognizer.cpp:306-318) with gallery_fuse.hip's reduction: a lane-strided sum
 //     of squares, then a butterfly.  Compiled with -ffp-contract=off, as track.hip.
 //   * no atomics and nothing that depends on timing: a (stream, slot) chain belongs to one wave, a stream's labels to one wave.
+//   * with track re-linking on (include/facehip.h, "track re-linking") stage A is track_link_kernel instead: one workgroup per stream.
 #include <hip/hip_runtime.h>
 
 #include "kernels.h"
@@ -195,6 +196,277 @@ __global__ __launch_bounds__(64) void track_propagate_kernel(TrackIdent* __restr
         TrackIdent* const id = ident + (size_t)s * max_tracks + lane;
         id->owner = st.owner; id->label = st.label; id->score = st.score;      // (n_emb is stage A's)
     }
+}
+
+// ------------------------------------------------------------------------------------------
+// Stage A with re-linking on (include/facehip.h, "track re-linking").  A newly opened track may continue a LOST one, whose template sits
+// in another row of the stream's table, so a stream's chains are no longer independent: ONE workgroup of four waves walks the stream's
+// entries serially, in walk_entries's order (every wave walks; the walk and the slots' owners — lane l of EVERY wave holds slot l's —
+// are replicated, so all four agree on where the open events are without talking).
+//   * wave 0 owns the table (a copy in LDS, loaded once, stored once) and the sums: it is the only writer of both, and every one of its
+//     lanes performs the same record updates, so each lane reads back what it wrote itself;
+//   * wave 1 copies the untracked faces' rows, which touch no state;
+//   * at an OPEN event the four waves meet (barrier: wave 0's table and sums become visible), wave w scores rows w, w + 4, ... — lanes
+//     over the 16-byte columns, dot and sum of squares in the order the contract states — and keeps its best (score, owner); the four
+//     bests meet in LDS (barrier) and wave 0 folds them in wave order, moves the records and pools the face.
+// No atomics, nothing that depends on timing: every barrier is reached by all four waves under conditions that all four evaluate alike.
+// ------------------------------------------------------------------------------------------
+namespace {
+// component-wise choice (a float4 chosen whole at run time would live in scratch)
+__device__ __forceinline__ float4 sel4(bool c, const float4 a, const float4 b) {
+    return make_float4(c ? a.x : b.x, c ? a.y : b.y, c ? a.z : b.z, c ? a.w : b.w);
+}
+// a candidate (score, owner, row); row < 0 = none
+__device__ __forceinline__ void link_put(TrackLink& d, int owner, int root, int n_emb, int label, float score, int last_seen, int links) {
+    d.owner = owner; d.root = root; d.n_emb = n_emb; d.label = label; d.score = score; d.last_seen = last_seen; d.links = links; d.pad = 0;
+}
+// (a) beats (b): the higher score, then the smaller owner; row < 0 = nothing yet
+__device__ __forceinline__ bool link_beats(float a_score, int a_owner, int a_row, float b_score, int b_owner, int b_row) {
+    return a_row >= 0 && (b_row < 0 || a_score > b_score || (a_score == b_score && a_owner < b_owner));
+}
+}  // namespace
+
+__global__ __launch_bounds__(256) void track_link_kernel(TrackLink* __restrict__ links, TrackIdent* __restrict__ ident,
+                                                         float4* __restrict__ sums, float4* __restrict__ msums,
+                                                         const int* __restrict__ heads, int max_tracks, TrackLinkParams lp, int vpr, int pool,
+                                                         const int* __restrict__ track, const int* __restrict__ slot,
+                                                         const int* __restrict__ embed, const int* __restrict__ quality,
+                                                         const int* __restrict__ frame_off, const float4* __restrict__ emb, int total,
+                                                         int per_frame, const int* __restrict__ order, const int* __restrict__ starts,
+                                                         float4* __restrict__ queries, int* __restrict__ root) {
+    __shared__ TrackLink tab[64 + kTrackLinkMemory];
+    __shared__ float best_score[4];
+    __shared__ int best_owner[4], best_row[4];
+    const int s = blockIdx.x, lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int b = starts[s], e = starts[s + 1];
+    if (b == e) return;
+    const int R = max_tracks + lp.memory;
+    TrackLink* const mine_rows = links + (size_t)s * R;
+    for (int r = threadIdx.x; r < R; r += 256) {
+        tab[r] = mine_rows[r];
+        if (r < max_tracks) {                                            // a slot's (label, score) are stage C's: what the last call left
+            const TrackIdent* const id = ident + (size_t)s * max_tracks + r;
+            tab[r].label = id->label; tab[r].score = id->score;
+        }
+    }
+    __syncthreads();
+    const int frame_no = heads[2 * s];
+    int owner = lane < max_tracks ? tab[lane].owner : -1;
+    const bool weighted = pool == kTrackPoolWeighted;
+    const int pieces = per_frame <= 64 ? 1 : (per_frame + 63) / 64;     // body calls per frame (per_frame > 64: one frame in pieces)
+    int pos = b, piece = 0;
+    float4* const slot_sums = sums + (size_t)s * max_tracks * vpr;
+    float4* const mem_sums = msums + (size_t)s * lp.memory * vpr;
+    auto sum_row = [&](int r) { return r < max_tracks ? slot_sums + (size_t)r * vpr : mem_sums + (size_t)(r - max_tracks) * vpr; };
+
+    walk_entries(order, b, e, per_frame, embed, frame_off, lane, [&](bool valid, int k, int nk, size_t idx, bool fl, int rank) {
+        const int sl = valid ? slot[idx] : -1;
+        const int tid = valid ? track[idx] : -1;
+        const bool known = fl && rank < total;
+        const int qual = (weighted && known) ? quality[idx] : 1;
+        int root_out = -1;
+        for (int kk = 0; kk < nk; ++kk) {
+            const int t = frame_no - (e - (pos + kk));                   // the update's frame time of this frame
+            const bool here = valid && k == kk;
+            unsigned long long un = __ballot(here && known && sl < 0);
+            if (wave == 1) {
+                while (un != 0) {
+                    const int src = __ffsll((long long)un) - 1;
+                    un &= un - 1;
+                    const int q_e = __shfl(rank, src);
+                    const float4* const row = emb + (size_t)q_e * vpr;
+                    float4* const q = queries + (size_t)q_e * vpr;
+                    for (int c = lane; c < vpr; c += 64) q[c] = row[c];
+                }
+            }
+            const bool tracked = sl >= 0 && sl < max_tracks;             // (a slot the update cannot have written is nobody's)
+            unsigned long long ev = __ballot(here && known && tracked);
+            unsigned long long rest = __ballot(here && !known && tracked);
+            // steps 3 and 4 of the entries that pool nothing, lane-parallel (a frame holds a slot at most once), kept in the serial
+            // order relative to the events: the ones below an event's lane are done before it
+            auto passive = [&](unsigned long long m) {
+                if (wave == 0 && ((m >> lane) & 1ull) != 0 && tab[sl].owner == tid) {
+                    tab[sl].last_seen = t;
+                    root_out = tab[sl].root;
+                }
+                __builtin_amdgcn_wave_barrier();
+            };
+            while (ev != 0) {
+                const int src = __ffsll((long long)ev) - 1;
+                ev &= ev - 1;
+                const unsigned long long below = (1ull << src) - 1ull;
+                if ((rest & below) != 0) { passive(rest & below); rest &= ~below; }
+                const int q_e = __shfl(rank, src), t_e = __shfl(tid, src), s_e = __shfl(sl, src);
+                const float wq = (float)max(__shfl(qual, src), 1);
+                const float4* const row = emb + (size_t)q_e * vpr;
+                float4* const q = queries + (size_t)q_e * vpr;
+                float4* const sm = slot_sums + (size_t)s_e * vpr;
+                const bool open = __shfl(owner, s_e) != t_e;
+                if (!open) {                                             // 2. a continued track: track_pool_kernel's arithmetic
+                    if (wave == 0) {
+                        tab[s_e].n_emb += 1;
+                        tab[s_e].last_seen = t;
+                        if (lane == src) root_out = tab[s_e].root;
+                        if (pool == kTrackPoolLast) {
+                            for (int c = lane; c < vpr; c += 64) { const float4 v = row[c]; sm[c] = v; q[c] = v; }
+                        } else {
+                            float sq = 0.f;
+                            for (int c = lane; c < vpr; c += 64) {
+                                const float4 a = add4(sm[c], weighted ? mul4(wq, row[c]) : row[c]);
+                                sm[c] = a;
+                                sq += a.x * a.x + a.y * a.y + a.z * a.z + a.w * a.w;
+                            }
+                            const float norm = sqrtf(wave_sum(sq));
+                            const bool scale = norm > 0.f;
+                            for (int c = lane; c < vpr; c += 64) {
+                                const float4 a = sm[c];
+                                q[c] = scale ? make_float4(a.x / norm, a.y / norm, a.z / norm, a.w / norm) : a;
+                            }
+                        }
+                    }
+                    continue;
+                }
+                // 1. an open event
+                __syncthreads();                                         // wave 0's table and sums, as they stand now
+                float m_score = 0.f;
+                int m_owner = 0, m_row = -1;
+                for (int r = wave; r < R; r += 4) {
+                    const int c_owner = tab[r].owner, gap = t - tab[r].last_seen - 1;
+                    if (c_owner == -1 || gap <= lp.max_missed || gap > lp.max_age) continue;      // not dead at t, or out of reach
+                    const float4* const cs = sum_row(r);
+                    float d = 0.f, ss = 0.f;
+                    for (int c = lane; c < vpr; c += 64) {
+                        const float4 a = cs[c], v = row[c];
+                        d += v.x * a.x + v.y * a.y + v.z * a.z + v.w * a.w;
+                        ss += a.x * a.x + a.y * a.y + a.z * a.z + a.w * a.w;
+                    }
+                    d = wave_sum(d);
+                    ss = wave_sum(ss);
+                    const float nrm = sqrtf(ss);
+                    const float cosv = nrm > 0.f ? d / nrm : d;
+                    const float c_score = (cosv + 1.0f) * 0.5f;
+                    if (c_score > lp.link_thr && link_beats(c_score, c_owner, r, m_score, m_owner, m_row)) {      // (a NaN never exceeds it)
+                        m_score = c_score; m_owner = c_owner; m_row = r;
+                    }
+                }
+                if (lane == 0) { best_score[wave] = m_score; best_owner[wave] = m_owner; best_row[wave] = m_row; }
+                __syncthreads();
+                float w_score = best_score[0];
+                int w_owner = best_owner[0], w_row = best_row[0];
+                for (int w = 1; w < 4; ++w)
+                    if (link_beats(best_score[w], best_owner[w], best_row[w], w_score, w_owner, w_row)) {
+                        w_score = best_score[w]; w_owner = best_owner[w]; w_row = best_row[w];
+                    }
+                if (lane == w_row) owner = -1;                         // every wave: a slot row that is taken is free ...
+                if (lane == s_e) owner = t_e;                            // ... and the slot is this track's now, linked or not
+                if (wave != 0) continue;
+                // (the records travel as scalars: whole-struct copies chosen at run time would live in scratch)
+                const int o_owner = tab[s_e].owner, o_root = tab[s_e].root, o_n = tab[s_e].n_emb, o_label = tab[s_e].label;
+                const float o_score = tab[s_e].score;
+                const int o_seen = tab[s_e].last_seen, o_links = tab[s_e].links;
+                const int old_gap = t - o_seen - 1;
+                bool retire = o_owner != -1 && old_gap > lp.max_missed && old_gap <= lp.max_age && lp.memory > 0;
+                int r_root = t_e, r_n = 1, r_label = -1, r_links = 0;    // no winner: the slot opens as today, unnamed
+                float r_score = -1.0f;
+                if (w_row >= 0) {                                      // the winner's record, continued
+                    const TrackLink& c = tab[w_row];
+                    r_root = c.root; r_n = c.n_emb + 1; r_label = c.label; r_score = c.score; r_links = c.links + 1;
+                    link_put(tab[w_row], -1, -1, 0, -1, -1.0f, 0, 0);
+                    if (w_row == s_e) retire = false;
+                }
+                int to = -1;                                             // the memory row the old record retires to
+                if (retire) {
+                    for (int m0 = 0; m0 < lp.memory && to < 0; m0 += 64) {
+                        const int m = m0 + lane;
+                        bool avail = false;
+                        if (m < lp.memory) {
+                            const TrackLink& x = tab[max_tracks + m];
+                            avail = x.owner == -1 || t - x.last_seen - 1 > lp.max_age;
+                        }
+                        const unsigned long long am = __ballot(avail);
+                        if (am != 0) to = max_tracks + m0 + __ffsll((long long)am) - 1;
+                    }
+                    if (to < 0) {                                        // all in reach: the smallest last_seen goes, then the smaller owner
+                        int b_seen = 0x7fffffff, b_owner = 0x7fffffff, b_row = -1;
+                        for (int m = lane; m < lp.memory; m += 64) {
+                            const TrackLink& x = tab[max_tracks + m];
+                            if (b_row < 0 || x.last_seen < b_seen || (x.last_seen == b_seen && x.owner < b_owner)) {
+                                b_seen = x.last_seen; b_owner = x.owner; b_row = max_tracks + m;
+                            }
+                        }
+#pragma unroll
+                        for (int o = 32; o > 0; o >>= 1) {
+                            const int o_seen = __shfl_xor(b_seen, o), o_owner = __shfl_xor(b_owner, o), o_row = __shfl_xor(b_row, o);
+                            if (o_row >= 0 && (b_row < 0 || o_seen < b_seen || (o_seen == b_seen && o_owner < b_owner))) {
+                                b_seen = o_seen; b_owner = o_owner; b_row = o_row;
+                            }
+                        }
+                        to = b_row;
+                    }
+                }
+                // the sums: every column is read whole before it is written, by the lane that owns it, so the rows may coincide
+                const float4* const cs = w_row >= 0 ? sum_row(w_row) : sm;
+                float4* const ts = to >= 0 ? sum_row(to) : sm;
+                const bool pooled = w_row >= 0 && pool != kTrackPoolLast;
+                float sq = 0.f;
+                for (int c = lane; c < vpr; c += 64) {
+                    const float4 a = sm[c], base = cs[c], v = row[c];
+                    const float4 in = sel4(weighted, mul4(wq, v), v);
+                    if (to >= 0) ts[c] = a;
+                    if (pooled) {
+                        const float4 n4 = add4(base, in);
+                        sm[c] = n4;
+                        sq += n4.x * n4.x + n4.y * n4.y + n4.z * n4.z + n4.w * n4.w;
+                    } else {
+                        sm[c] = sel4(w_row >= 0, v, in);               // a resumed POOL_LAST track: sum = row; a new one: as today
+                        q[c] = v;
+                    }
+                }
+                if (pooled) {
+                    const float norm = sqrtf(wave_sum(sq));
+                    const bool scale = norm > 0.f;
+                    for (int c = lane; c < vpr; c += 64) {
+                        const float4 a = sm[c];
+                        q[c] = scale ? make_float4(a.x / norm, a.y / norm, a.z / norm, a.w / norm) : a;
+                    }
+                }
+                if (to >= 0) link_put(tab[to], o_owner, o_root, o_n, o_label, o_score, o_seen, o_links);
+                link_put(tab[s_e], t_e, r_root, r_n, r_label, r_score, t, r_links);
+                if (lane == src) root_out = r_root;
+            }
+            if (rest != 0) passive(rest);
+        }
+        if (wave == 0 && valid) root[idx] = root_out;
+        if (++piece == pieces) { piece = 0; pos += nk; }
+    });
+    __syncthreads();
+    for (int r = threadIdx.x; r < R; r += 256) {
+        mine_rows[r] = tab[r];
+        if (r < max_tracks) {
+            TrackIdent* const id = ident + (size_t)s * max_tracks + r;
+            id->owner = tab[r].owner; id->n_emb = tab[r].n_emb;          // (label and score are stage C's)
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void track_roots_kernel(const int* __restrict__ track, const int* __restrict__ slot, long entries,
+                                                          int* __restrict__ root) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i < entries) root[i] = slot[i] >= 0 ? track[i] : -1;
+}
+
+void launch_track_link(TrackLink* links, TrackIdent* ident, float* sums, float* msums, const int* heads, int streams, int max_tracks,
+                       TrackLinkParams lp, int dim, int pool, const int* track, const int* slot, const int* embed, const int* quality,
+                       const int* frame_off, const float* emb, int total, int per_frame, const int* order, const int* starts, float* queries,
+                       int* root, hipStream_t s) {
+    hipLaunchKernelGGL(track_link_kernel, dim3(streams), dim3(256), 0, s, links, ident, reinterpret_cast<float4*>(sums),
+                       reinterpret_cast<float4*>(msums), heads, max_tracks, lp, dim / 4, pool, track, slot, embed, quality, frame_off,
+                       reinterpret_cast<const float4*>(emb), total, per_frame, order, starts, reinterpret_cast<float4*>(queries), root);
+}
+
+void launch_track_roots(const int* track, const int* slot, long entries, int* root, hipStream_t s) {
+    hipLaunchKernelGGL(track_roots_kernel, dim3((unsigned)((entries + 255) / 256)), dim3(256), 0, s, track, slot, entries, root);
 }
 
 void launch_track_ranks(const int* embed, int n, int per_frame, int* frame_off, hipStream_t s) {

@@ -441,6 +441,76 @@ FH_API int fh_track_identify_q_dev(fh_tracker* t, fh_gallery* g, float threshold
                                    const int* d_quality /*[n][per_frame] or NULL*/, const float* d_emb, int total, int n, int per_frame,
                                    const int* stream_of, int* d_label, float* d_score, void* stream);
 
+/* ---- track re-linking: a lost track is RESUMED by appearance when its face comes back.  The tracker above associates by IoU alone: a
+ * face hidden for more than max_missed frames loses its track, returns under a new id, and its pooled template, n_emb and name start
+ * again.  With re-linking on, the first embedding of every newly opened track is compared with the templates of the stream's recently
+ * lost tracks, and the new track continues the best one: template, count and chain root carry over, and d_root tells the caller which
+ * track ids are one person.  Opt-in: with re-linking off every entry point above is bit for bit what it was.  Everything but the float
+ * normalisation of the queries is defined to the bit.  The defaults of the Python layer (link_thr 0.6 = the reference's match
+ * threshold, main.cpp:229-233; max_age 150 = five seconds at 30 fps) are a proposal whose effect on accuracy nobody has measured.
+ * No spatial or motion gate, no linking across streams (the gallery label does that for enrolled people).
+ *
+ * fh_tracker_enable_relink(t, memory, link_thr, max_age)  synchronous.  Needs fh_tracker_enable_identity first (else FH_ERR_STATE,
+ *   nothing changes), 0 <= memory <= FH_TRACK_LINK_MEMORY, a finite link_thr and max_age > max_missed (else FH_ERR_ARG, nothing
+ *   changes).  Allocates, per stream, a table of max_tracks + memory fh_track_link records and one sum[dim] per record.  Rows 0 ..
+ *   max_tracks - 1 are the slots' records (their owner, n_emb, label, score and sum ARE the identity state above); the other rows are
+ *   the stream's memory of lost tracks.  owner = -1: the row is free; root = the id of the first track of the chain; last_seen = the
+ *   frame time t of the last entry that carried the track; links = how many times the chain was resumed.  The call CLEARS the identity
+ *   state and the table of every stream (a track that is live then is re-opened by its next embedding).  A second
+ *   fh_tracker_enable_identity clears everything and switches re-linking off; fh_tracker_reset(stream) clears that stream's table.
+ *   memory = 0 is legal: only records still sitting in slots are candidates.
+ * fh_track_identify_link_dev  fh_track_identify_q_dev's arguments (d_quality may be NULL unless the pool is WEIGHTED) plus d_root
+ *   [n][per_frame], which must not be NULL.  Re-linking off: fh_track_identify_q_dev, plus d_root = the entry's own track id where
+ *   d_slot >= 0, -1 elsewhere.  Re-linking on: stage A below; fh_track_identify_dev / _q_dev then return FH_ERR_STATE (nothing
+ *   launched), so that a caller never gets a silently different answer.
+ *   t = the update contract's frame time of the entry's frame: identify is called once after each update, so t = the stream's frame_no
+ *   after the update minus the number of that stream's frames from this one (included) to the end of the call.  A record is DEAD at t
+ *   iff owner != -1 && t - last_seen - 1 > max_missed (the tracker's own expiry rule) and IN REACH iff also t - last_seen - 1 <= max_age.
+ *   A. ONE serial walk per stream: its frames in time order, j ascending, all slots interleaved.  For each entry with slot >= 0 and track
+ *      id tid, rec = the slot's record:
+ *      1. open event: the entry is flagged, rank < total, rec.owner != tid.  Every record of the table — slot rows, this slot's own
+ *         included, and memory rows — that is dead at t and in reach is a candidate, scored against emb_e (below).  The best candidate
+ *         with score > link_thr (strict) wins: the higher score, then the smaller owner.
+ *         no winner: the slot's old record is RETIRED (below) if it is dead at t and in reach, else dropped; the slot opens as above —
+ *           owner = tid, n_emb = 1, sum = (wq *) emb_e, q_e = emb_e verbatim — with root = tid, links = 0.
+ *         winner c: c is taken out of the table (copied, its row freed); the slot's old record is retired as above unless it was c;
+ *           c is installed in the slot with owner = tid, links + 1; root, n_emb and sum are kept, and the face is the next embedding of
+ *           a continued track: n_emb += 1 and, SUM / WEIGHTED: sum = sum + (wq *) emb_e, q_e = normalize(sum); LAST: sum = emb_e, q_e =
+ *           emb_e verbatim.
+ *      2. continued track (flagged, rank < total, rec.owner == tid): as above.
+ *      3. then, for EVERY entry with slot >= 0, flagged or not, rank < total or not: if rec.owner == tid, rec.last_seen = t.
+ *      4. d_root[f][j] = rec.root if rec.owner == tid, else -1; also -1 for untracked entries and j >= c.
+ *      A flagged entry of rank >= total takes no part in 1 and 2, as above.
+ *      label, score: stage C runs after stage A, so during the walk a slot's record carries the (label, score) its slot held when the
+ *      CALL began — until an open event replaces the record: a record opened without a winner is UNNAMED, (-1, -1.0f); a resumed one
+ *      keeps the WINNER's (label, score), as it keeps its root and sum.  Whatever the record carries goes to the memory with it when
+ *      it retires (also later in the same call) and is reported there by fh_tracker_get_links.  A slot row itself is named by stage C
+ *      of the same call, from the face's own query, as any flagged face; fh_tracker_get_links reports that for the slot rows.
+ *      retiring: the record goes to the lowest memory row that is free or no longer in reach at t; if there is none it replaces the row
+ *      with the smallest last_seen, ties to the smaller owner; with memory == 0 it is dropped.
+ *      score of candidate c against emb_e, to the bit (fp32, not contracted): d = dot(emb_e, sum_c), ss = dot(sum_c, sum_c).  Lane l of
+ *      64 owns the 16-byte columns l, l + 64, ... in ascending order; per column acc = acc + (((x0 * y0 + x1 * y1) + x2 * y2) + x3 * y3)
+ *      (the form of the pool's sum of squares), acc from 0.0f; the lanes meet in the xor butterfly 32, 16, .., 1 (v = v + v[lane ^ o]).
+ *      One wave scores one row at a time.  nrm = sqrtf(ss); c = nrm > 0 ? d / nrm : d; score = (c + 1.0f) * 0.5f.  A NaN never exceeds
+ *      the threshold.
+ *   B, C. unchanged; of the table stage C writes the slot rows' label and score and nothing else (a row's owner is stage A's: a slot
+ *      whose record a link took away later in the call stays free, whatever face stage C saw there last).
+ * fh_tracker_get_links  synchronous; the whole table of one stream by row into host_out[max_tracks + memory] and the sums into sums_out
+ *   [max_tracks + memory][dim] (may be NULL; zero for a free row); returns the number of rows.  With host_out and sums_out both NULL it
+ *   writes nothing and only returns the number of rows (what a caller sizes its buffers by).  FH_ERR_STATE with re-linking off.
+ * fh_tracker_roots_dev  a stage hook: the [n][F] roots of the last fh_pipeline_run_identified_dev on a tracker with re-linking on,
+ *   which then runs fh_track_identify_link_dev (with the tracker's quality buffer when the best-shot policy is on) into a buffer of the
+ *   tracker's; every other output is produced as before.  With re-linking off nothing new is allocated or launched. */
+#define FH_TRACK_LINK_MEMORY 256             /* memory rows per stream, at most */
+typedef struct fh_track_link { int32_t owner, root, n_emb, label; float score; int32_t last_seen, links, pad; } fh_track_link;  /* 32 bytes */
+FH_API int fh_tracker_enable_relink(fh_tracker* t, int memory, float link_thr, int max_age);
+FH_API int fh_track_identify_link_dev(fh_tracker* t, fh_gallery* g, float threshold, const int* d_track, const int* d_slot, const int* d_embed,
+                                      const int* d_quality /*[n][per_frame] or NULL*/, const float* d_emb, int total, int n, int per_frame,
+                                      const int* stream_of, int* d_label, float* d_score, int* d_root /*[n][per_frame]*/, void* stream);
+FH_API int fh_tracker_get_links(fh_tracker* t, int stream, fh_track_link* host_out /*[max_tracks + memory] or NULL*/,
+                                float* sums_out /*[max_tracks + memory][dim] or NULL*/);
+FH_API const int* fh_tracker_roots_dev(fh_tracker* t);
+
 /* ---- gallery (1:N compareFaces): rows are L2-normalised features; scores are (dot+1)/2. */
 FH_API fh_gallery* fh_gallery_create(int dim);
 FH_API void fh_gallery_destroy(fh_gallery* g);

@@ -20,6 +20,10 @@ by round after a warm-up.
       quality kernel alone on the detector's records of the (a) frames.  Every camera of the video repeats one frame, so no face ever
       gets better: the step pays for the score and embeds nothing more.
 
+  (f) re-linking: one camera shows a frame for 12 frames and a blank one for 4, over and over, with max_missed 0: every face loses its
+      track in each pause and comes back as a new one.  fh_pipeline_run_identified_dev with re-linking off and on (memory 64, link_thr
+      0.6, max_age 150) in the same run; the open events and links of a step are counted from the roots of the last step.
+
 Writes --md (default profiles/track_ab.md) and prints one JSON line per case.  Needs a GPU; there is no fallback."""
 import argparse
 import json
@@ -33,7 +37,7 @@ ap.add_argument("--warmup", type=int, default=20)
 ap.add_argument("--steps", type=int, default=100, help="timed steps per leg (at least)")
 ap.add_argument("--rounds", type=int, default=5)
 ap.add_argument("--block", type=int, default=5, help="steps per HIP-event sample")
-ap.add_argument("--cases", nargs="+", default=["a", "b", "c", "d", "e"])
+ap.add_argument("--cases", nargs="+", default=["a", "b", "c", "d", "e", "f"])
 ap.add_argument("--md", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "track_ab.md"))
 a = ap.parse_args()
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -48,6 +52,7 @@ THR, NMS, F, HW = 0.5, 0.4, 8, 640
 IOU_THR, MAX_TRACKS = 0.3, 64
 GALLERY_ROWS, ID_THRESHOLD = 10000, 0.6
 BESTSHOT = (5, 4, 1)                                               # num, den, min_gap
+RELINK = (64, 0.6, 150)                                            # memory, link_thr, max_age
 
 
 def samples(step, steps, block):
@@ -145,7 +150,7 @@ def main():
         out["c"] = {"frames": B, "faces_in_records": int(torch.clamp(counts, 0, F).sum().item()), **st}
         print(json.dumps({"case": "c", **out["c"]}), flush=True)
 
-    if "d" in a.cases or "e" in a.cases:
+    if "d" in a.cases or "e" in a.cases or "f" in a.cases:
         gal = fa.Gallery(512)
         g = rng.standard_normal((GALLERY_ROWS, 512), dtype=np.float32)
         gal.enroll(g / np.linalg.norm(g, axis=1, keepdims=True))
@@ -223,6 +228,30 @@ def main():
                               "quality_min_median_max": [int(q.min()), int(np.median(q)), int(q.max())], **st}
         print(json.dumps({"case": "e", **out["e"]}), flush=True)
 
+    if "f" in a.cases:
+        shown = (np.arange(B) % 16) < 12                                                           # 12 frames of the face, 4 blank ones
+        data = distinct[:1].expand(B, HW, HW, 3).contiguous()
+        data[torch.from_numpy(~shown).cuda()] = 0
+        legs, trks = {}, {}
+        for mode in ("off", "on"):
+            t = fa.Tracker(1, MAX_TRACKS, IOU_THR, 0, 0)
+            t.enable_identity(512)
+            if mode == "on":
+                t.enable_relink(*RELINK)
+            trks[mode] = t
+            legs[f"identified_relink_{mode}"] = identified(data, t, None)
+        st, fc, first = ab(legs, a.warmup, a.steps, a.rounds, a.block)
+        torch.cuda.synchronize()
+        roots = np.empty((B, F), np.int32)
+        fa._lib.check(fa.lib().fh_memcpy_d2h(roots.ctypes.data, trks["on"].roots_ptr(), roots.nbytes), "fh_memcpy_d2h")
+        tr = track.cpu().numpy()
+        per_frame = torch.clamp(counts, 0, F).cpu().numpy()
+        out["f"] = {"frames": B, "faces_per_step": fc, "faces_first_step": first, "open_events_per_step": fc["identified_relink_on"],
+                    "faces_in_shown_frames": int(per_frame[shown].sum()), "faces_in_blank_frames": int(per_frame[~shown].sum()),
+                    "links_per_step": int(len({int(t_) for t_, r in zip(tr.reshape(-1), roots.reshape(-1)) if r >= 0 and r != t_})),
+                    "relink_cost_ms": round(st["identified_relink_on"]["median_ms"] - st["identified_relink_off"]["median_ms"], 4), **st}
+        print(json.dumps({"case": "f", **out["f"]}), flush=True)
+
     if a.md and out:
         write_md(out)
 
@@ -289,6 +318,18 @@ def write_md(out):
         L += ["", f"The quality kernel alone: {c['frames']} frames of {HW}x{HW}, {c['faces_in_records']} faces in the records (up to {F} per "
               f"frame), scores min / median / max {c['quality_min_median_max']}.", "",
               "| leg | ms per call |", "|---|---|", f"| `fh_face_quality_dev` | {fmt(c['quality'])} |", ""]
+    if "f" in out:
+        d = out["f"]
+        L += [f"## (f) re-linking: memory {RELINK[0]}, link_thr {RELINK[1]}, max_age {RELINK[2]}", "",
+              f"One camera, {d['frames']} frames per step: 12 frames of one picture, 4 blank ones, repeated; max_missed 0, refresh 0, so every "
+              "face loses its track in each pause and opens a new one when it is back.  The gallery of (d).  The detector's records hold "
+              f"{d['faces_in_shown_frames']} faces in the {int(d['frames'] * 12 / 16)} frames of the picture and {d['faces_in_blank_frames']} in the blank ones.", "",
+              "| leg | ms per step | faces embedded per step | ... on the first step |", "|---|---|---|---|"]
+        for k in ("identified_relink_off", "identified_relink_on"):
+            L.append(f"| `fh_pipeline_run_identified_dev`, re-linking {k.split('_')[-1]} | {fmt(d[k])} | {d['faces_per_step'][k]} | "
+                     f"{d['faces_first_step'][k]} |")
+        L += ["", f"Re-linking on minus off: {d['relink_cost_ms']:+.3f} ms per step, for {d['open_events_per_step']} open events and "
+              f"{d['links_per_step']} resumed tracks per step.", ""]
     os.makedirs(os.path.dirname(os.path.abspath(a.md)), exist_ok=True)
     with open(a.md, "w") as f:
         f.write("\n".join(L))
