@@ -50,6 +50,10 @@ TRACK_LINK_DTYPE = np.dtype([("owner", "<i4"), ("root", "<i4"), ("n_emb", "<i4")
                              ("links", "<i4"), ("pad", "<i4")])  # fh_track_link
 assert TRACK_LINK_DTYPE.itemsize == 32
 TRACK_LINK_MEMORY = 256                                        # FH_TRACK_LINK_MEMORY
+HIST_BINS = 2048                                               # FH_HIST_BINS
+ROC_POINT_DTYPE = np.dtype([("threshold", "<f4"), ("bin", "<i4"), ("true_accepts", "<u8"), ("false_accepts", "<u8"), ("genuine", "<u8"),
+                            ("impostor", "<u8")])              # fh_roc_point
+assert ROC_POINT_DTYPE.itemsize == 40
 
 
 class FhTrackState(C.Structure):
@@ -188,6 +192,9 @@ PROTOTYPES = {
     "fh_gallery_self_scores_dev": (_i, [_vp, _vp, _vp, _vp]),
     "fh_cluster_scores": (_i, [_vp, _i, _f, _i, _i, _vp, _vp]),
     "fh_gallery_cluster_dev": (_i, [_vp, _f, _i, _i, _vp, _vp, _vp]),
+    "fh_hist_bin": (_i, [_f]),
+    "fh_roc_from_hist": (_i, [_vp, _d, _vp]),
+    "fh_gallery_pair_hist_dev": (_i, [_vp, _vp, _vp, _vp]),
     "fh_gallery_set_ids": (_ll, [_vp, _vp, _i]),
     "fh_comm_unique_id": (_i, [_vp]),
     "fh_comm_create": (_vp, [_i, _i, _vp, _i]),
@@ -219,6 +226,7 @@ PROTOTYPES = {
     "fh_debug_streamk": (_i, [_i, _i]),
     "fh_debug_wino_slots": (_i, [_i]),
     "fh_debug_cluster_tiles": (_i, [_i]),
+    "fh_debug_hist_copies": (_i, [_i]),
     "fh_debug_topk_merge_strided_dev": (_i, [_vp, _vp, _i, _i, _i, _ll, _vp, _vp, _vp]),
     "fh_set_graph_replay": (_i, [_i]),
     "fh_det_workspace_dev": (_vp, [_vp]),

@@ -723,6 +723,22 @@ class Gallery:
         self.cluster_dev(threshold, min_pts, noise, labels.data_ptr(), info.data_ptr(), torch.cuda.current_stream().cuda_stream)
         return labels[:n].cpu().numpy(), info.cpu().numpy()
 
+    def pair_hist_dev(self, hist_ptr: int, nan_ptr: Optional[int] = None, stream: int = 0):
+        """Exact genuine / impostor score histograms over all unordered pairs of the gallery's rows (fh_gallery_pair_hist_dev):
+        hist[2][HIST_BINS] (device uint64; plane 0 = pairs with the same id, plane 1 = the rest) and nan[2] (device uint64, optional:
+        the NaN-scored pairs per class) are overwritten.  A pair's score is the fp32 scan's, its bin is hist_bin's.  Needs a labelled
+        gallery.  Asynchronous on `stream`."""
+        check(_lib.lib().fh_gallery_pair_hist_dev(self._h, hist_ptr, nan_ptr, stream), "fh_gallery_pair_hist_dev")
+
+    def pair_hist(self):
+        """(hist uint64[2, HIST_BINS], nan uint64[2]) of pair_hist_dev — a synchronous convenience that allocates and copies back;
+        roc_from_hist reads the operating thresholds off it."""
+        import torch
+        buf = torch.empty(2 * _lib.HIST_BINS + 2, dtype=torch.int64, device="cuda")
+        self.pair_hist_dev(buf.data_ptr(), buf.data_ptr() + 2 * _lib.HIST_BINS * 8, torch.cuda.current_stream().cuda_stream)
+        out = buf.cpu().numpy().view(np.uint64)
+        return out[:2 * _lib.HIST_BINS].reshape(2, _lib.HIST_BINS).copy(), out[2 * _lib.HIST_BINS:].copy()
+
     def set_ids(self, ids) -> int:
         """Replace the ids of all rows by position (int32[len(self)] >= 0, host array or a device tensor) and make the gallery labelled
         (fh_gallery_set_ids); with noise="self" labels: cluster -> set_ids -> fuse.  Synchronous; returns the row count."""
@@ -830,6 +846,34 @@ def cluster_scores(scores, threshold: float, min_pts: int = 1, noise="none"):
     check(_lib.lib().fh_cluster_scores(scores.ctypes.data if n else None, n, threshold, min_pts, _noise_mode(noise),
                                        labels.ctypes.data if n else None, info.ctypes.data), "fh_cluster_scores")
     return labels, info
+
+
+def hist_bin(score: float) -> int:
+    """The bin of a mapped score (fh_hist_bin — host only, the one definition of the bin rule): -1 for a NaN, else b with
+    b/2048 < score <= (b+1)/2048, clamped to 0 below and HIST_BINS - 1 above, so that the suffix sum of a histogram from bin b >= 1 is
+    exactly the number of scores the strict test `score > b/2048` accepts."""
+    return int(_lib.lib().fh_hist_bin(float(np.float32(score))))
+
+
+def roc_from_hist(hist, max_far: float):
+    """(operating point of max_far, equal-error point) of fh_roc_from_hist — host only.  hist = uint64[2, HIST_BINS] (genuine,
+    impostor: Gallery.pair_hist).  A point is a dict of the struct's fields — threshold, bin, true_accepts, false_accepts, genuine,
+    impostor — plus far = false_accepts / impostor and tar = true_accepts / genuine as Python floats.  The first is the smallest
+    threshold b/2048 whose false accepts stay within floor(max_far * impostor); feed its threshold to label / cluster / the tracker.
+    bin == -1 (threshold 1.0, no accepts): no such threshold exists."""
+    hist = np.ascontiguousarray(hist, np.uint64)
+    if hist.shape != (2, _lib.HIST_BINS):
+        raise ValueError(f"roc_from_hist: need a [2, {_lib.HIST_BINS}] histogram")
+    out = np.zeros(2, _lib.ROC_POINT_DTYPE)
+    check(_lib.lib().fh_roc_from_hist(hist.ctypes.data, float(max_far), out.ctypes.data), "fh_roc_from_hist")
+    pts = []
+    for p in out:
+        d = {"threshold": float(p["threshold"]), "bin": int(p["bin"])}
+        d.update({k: int(p[k]) for k in ("true_accepts", "false_accepts", "genuine", "impostor")})
+        d["far"] = d["false_accepts"] / d["impostor"]
+        d["tar"] = d["true_accepts"] / d["genuine"]
+        pts.append(d)
+    return pts[0], pts[1]
 
 
 def plan_describe(path: str, default_h: int, default_w: int) -> str:

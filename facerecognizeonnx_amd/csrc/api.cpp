@@ -10,6 +10,7 @@
 
 #include "../../include/facehip.h"
 #include "cluster_plan.h"
+#include "roc_plan.h"
 #include "engine.h"
 #include "group_ids.h"
 #include "track_plan.h"
@@ -1399,6 +1400,34 @@ long long fh_gallery_set_ids(fh_gallery* g, const int* ids, int on_device) {
     return rc < 0 ? rc : n;
 }
 int fh_debug_cluster_tiles(int tiles_per_wg) { fh::cluster_debug_tiles(tiles_per_wg); return 0; }
+
+// ---- threshold calibration: the bin rule and the ROC read-out on the host (roc_plan.h), the pair histogram over the gallery's own rows
+// (gallery_cluster.hip)
+static_assert(FH_HIST_BINS == fh::kHistBins && sizeof(fh_roc_point) == sizeof(fh::RocPoint) && sizeof(unsigned long long) == sizeof(uint64_t) &&
+              offsetof(fh_roc_point, bin) == offsetof(fh::RocPoint, bin) && offsetof(fh_roc_point, impostor) == offsetof(fh::RocPoint, impostor),
+              "fh_roc_point mirrors roc_plan.h");
+int fh_hist_bin(float score) { return fh::hist_bin(score); }
+int fh_roc_from_hist(const unsigned long long* hist, double max_far, fh_roc_point out[2]) {
+    if (!hist || !out) return arg_error("fh_roc_from_hist: null argument");
+    if (!(max_far >= 0.0 && max_far <= 1.0)) return arg_error("fh_roc_from_hist: need 0 <= max_far <= 1");
+    fh::RocPoint pt[2];
+    if (fh::roc_from_hist(reinterpret_cast<const uint64_t*>(hist), max_far, pt) < 0) {
+        g_err = "fh_roc_from_hist: a plane of the histogram is empty (no genuine or no impostor pairs)";
+        return FH_ERR_STATE;
+    }
+    for (int k = 0; k < 2; ++k)
+        out[k] = fh_roc_point{pt[k].threshold, pt[k].bin, pt[k].true_accepts, pt[k].false_accepts, pt[k].genuine, pt[k].impostor};
+    return FH_OK;
+}
+int fh_gallery_pair_hist_dev(fh_gallery* g, unsigned long long* d_hist, unsigned long long* d_nan, void* stream) {
+    if (!g || !d_hist) return arg_error("fh_gallery_pair_hist_dev: null argument");
+    if (g->g.size() > 0 && !g->g.labelled()) {
+        g_err = "gallery: fh_gallery_pair_hist_dev needs a labelled gallery (rows enrolled with ids, or fh_gallery_set_ids)";
+        return FH_ERR_STATE;
+    }
+    return guarded([&] { g->g.pair_hist_dev(d_hist, d_nan, S(stream)); return (int)FH_OK; });
+}
+int fh_debug_hist_copies(int copies) { fh::cluster_debug_hist_copies(copies); return 0; }
 
 int fh_debug_topk_merge_strided_dev(const float* ps, const int* pi, int nparts, int nq, int k, long long part_stride, float* scores, int* indices,
                                     void* stream) {

@@ -2,6 +2,7 @@
 #include "engine.h"
 
 #include "group_ids.h"
+#include "roc_plan.h"
 #include "track_plan.h"
 
 #include <atomic>
@@ -1138,6 +1139,20 @@ void Gallery::cluster_dev(float thr, int min_pts, bool noise_self, int* labels, 
     cl_best_.ensure((size_t)n_ * sizeof(unsigned long long));
     launch_gallery_cluster(rows_.as<float>(), n_, dim_, thr, min_pts, noise_self, cl_deg_.as<int>(), cl_parent_.as<int>(),
                            cl_best_.as<unsigned long long>(), labels, info, s);
+    FH_HIP(hipGetLastError());
+}
+
+void Gallery::pair_hist_dev(unsigned long long* hist, unsigned long long* nan, hipStream_t s) {
+    need_labelled("fh_gallery_pair_hist_dev");
+    if (dim_ % 64) throw std::runtime_error("gallery: dim must be a multiple of 64");
+    if (n_ == 0) {
+        FH_HIP(hipMemsetAsync(hist, 0, 2 * (size_t)kHistBins * sizeof(unsigned long long), s));
+        if (nan) FH_HIP(hipMemsetAsync(nan, 0, 2 * sizeof(unsigned long long), s));
+        return;
+    }
+    if (n_ > (long)INT_MAX) throw std::runtime_error("gallery: row positions must fit in 31 bits");
+    cl_hist_.ensure(gallery_pair_hist_scratch_bytes());
+    launch_gallery_pair_hist(rows_.as<float>(), ids_.as<int>(), n_, dim_, cl_hist_.as<unsigned long long>(), hist, nan, s);
     FH_HIP(hipGetLastError());
 }
 

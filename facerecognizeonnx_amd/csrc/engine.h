@@ -388,6 +388,10 @@ class Gallery {
     // Exact DBSCAN over the fp32 rows (gallery_cluster.hip; the rule: cluster_plan.h): labels [size] = positions, info [4] (may be null),
     // both device.  Arguments checked by the caller.  Asynchronous; the scratch (16 bytes per row) is cleared on s at every call.
     void cluster_dev(float thr, int min_pts, bool noise_self, int* labels, int* info, hipStream_t s);
+    // Genuine / impostor score histograms over all unordered pairs of the fp32 rows (gallery_cluster.hip; the bin rule: roc_plan.h):
+    // hist [2][2048] and nan [2] (may be null), both device, both overwritten.  Needs a labelled gallery unless empty (the caller
+    // checks).  Asynchronous; the scratch (the histogram the workgroups flush into) lives in the handle and is cleared on s at every call.
+    void pair_hist_dev(unsigned long long* hist, unsigned long long* nan, hipStream_t s);
     // replaces every row's id by position (host or device list, checked by the caller: none negative); synchronous
     void set_ids(const int* ids, bool device_src);
     bool labelled() const { return labelled_; }
@@ -412,6 +416,7 @@ class Gallery {
     bool fused_ = false;
     DevBuf rows_, qpack_, ps_, pi_, best_i_, seed_s_, seed_i_;
     DevBuf cl_deg_, cl_parent_, cl_best_;                        // cluster_dev: degree, union-find parent, best core neighbour per row
+    DevBuf cl_hist_;                                             // pair_hist_dev: the histogram the workgroups flush into
     DevBuf ids_, pd_, seed_d_;                                   // identity id per row (capacity in rows = rows_'), id planes of the part / seed lists
     // F16_RERANK state: the fp16 rows, [max|g|, max|g^|, max|g - g^| (float bits), non-finite / > 65504 flag] on the device and its host
     // copy, per-call scratch, the certified / fallback counters

@@ -24,6 +24,14 @@
 //             in the low word, so the maximum is exactly gal_better's choice (a real key is never 0: ~position has its top bit set).
 //   flatten   label = root for cores, root of best's core for border rows, -1 / own position for noise; the four counters.
 //
+// fh_gallery_pair_hist_dev is the same pair pass with a third epilogue (clear the scratch, histogram pass, write-out):
+//   histogram every live pair (row < col < G) is ONE LDS atomicAdd into the workgroup's uint32 [2][2048] histogram — plane = the two rows'
+//             ids differ, bin = hist_bin (roc_plan.h) of the mapped score — or into one of two NaN counters.  A lane keeps the id of
+//             row wrow0 + (lane & 31) of the current A tile and an accumulator's row id comes by shuffle; its two column ids are loaded
+//             once per run.  16 KB of LDS beside the body's 32 KB: two workgroups per CU as before.  At the end of the run the non-zero
+//             counters are flushed to the scratch histogram with 64-bit global atomics.
+//   write-out the caller's hist [2][2048] and nan [2] (may be null) are overwritten from the scratch.
+//
 // Memory model (MI355X: eight XCDs whose L2s are not coherent with each other, and a vector L1 that another CU's stores never refresh):
 // inside the link kernel EVERY read of parent[] is an agent-scope relaxed atomic load (served by L2, never by a stale L1 line) and
 // every write is an atomic RMW (atomicCAS; atomicMin for the path halving).  A find that kept seeing a stale "I am a root" would fail
@@ -37,6 +45,7 @@
 
 #include "gallery_scan.h"
 #include "kernels.h"
+#include "roc_plan.h"
 
 namespace fh {
 
@@ -51,7 +60,22 @@ struct ClusterArgs {
     int* deg;                           // [G]
     int* parent;                        // [G]
     unsigned long long* best;           // [G]
+    // the histogram pass only
+    const int* ids;                     // [G]
+    unsigned long long* hist;           // [copies][kHistSlots]
+    int copies;
 };
+
+// one histogram: [2][kHistBins] bins (plane 0 genuine, plane 1 impostor), then the two NaN counters
+constexpr int kHistSlots = 2 * kHistBins + 2;
+enum { PAIR_DEGREE = 0, PAIR_LINK = 1, PAIR_HIST = 2 };
+constexpr int kHistDefaultCopies = 1;     // measured: 1, 8, 64 and 512 copies time the same (profiles/gallery_hist.md)
+
+// the histogram pass's per-workgroup counters: 16 KB + 8 bytes beside the body's 32 KB, so two workgroups still share a CU's 160 KB
+__device__ __forceinline__ unsigned* pair_hist_lds() {
+    __shared__ unsigned h[kHistSlots];
+    return h;
+}
 
 __device__ __forceinline__ int parent_load(const int* parent, int x) {
     return __hip_atomic_load(parent + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -86,8 +110,9 @@ __device__ __forceinline__ unsigned long long cluster_key(float s, int pos) {
     return ((unsigned long long)m << 32) | (unsigned)~pos;
 }
 
-template <bool LINK>
+template <int MODE>
 __device__ __forceinline__ void cluster_pair_body(const ClusterArgs& p) {
+    constexpr bool LINK = MODE == PAIR_LINK;
     constexpr int BM = GAL_BM, BN = GAL_BN, TN = BN / 32, CD = 64;
     __shared__ v4f ldsq[2][BN * 16];                          // B chunk [64 rows][64 k], 16-byte column XOR (row & 15)
     __shared__ int colcnt[BN];
@@ -101,6 +126,10 @@ __device__ __forceinline__ void cluster_pair_body(const ClusterArgs& p) {
     if (rt0 >= rt1) return;                                   // (workgroup-uniform, before any barrier)
     const int K = p.dim, chunks = K / CD;
     if (tid < BN) colcnt[tid] = 0;
+    if constexpr (MODE == PAIR_HIST) {
+        unsigned* h = pair_hist_lds();
+        for (int i = tid; i < kHistSlots; i += 256) h[i] = 0u;           // (the first tile's barriers come before the first add)
+    }
 
     // B loader: pass i fills rows i*16 + (tid >> 4), slot tid & 15 <- source 16-byte column (tid & 15) ^ (row & 15)
     const int qrow = tid >> 4;
@@ -121,13 +150,16 @@ __device__ __forceinline__ void cluster_pair_body(const ClusterArgs& p) {
     bool col_ok[TN];
     bool col_core[TN];
     int col_deg[TN];
+    int col_id[TN];
 #pragma unroll
     for (int j = 0; j < TN; ++j) {
         col[j] = n0 + j * 32 + fr;
         col_ok[j] = col[j] < p.G;
         col_deg[j] = 0;
         col_core[j] = false;
+        col_id[j] = 0;
         if constexpr (LINK) col_core[j] = col_ok[j] && p.deg[col[j]] + 1 >= p.min_pts;
+        if constexpr (MODE == PAIR_HIST) col_id[j] = col_ok[j] ? p.ids[col[j]] : 0;
     }
 
     for (int rt = rt0; rt < rt1; ++rt) {
@@ -200,7 +232,7 @@ __device__ __forceinline__ void cluster_pair_body(const ClusterArgs& p) {
         // ---- epilogue: accumulator e of block j is (row rbase + 8 * (e >> 2) + (e & 3), column col[j])
         const long wrow0 = m0 + wid * 32;
         const long rbase = wrow0 + 4 * fh2;
-        if constexpr (!LINK) {
+        if constexpr (MODE == PAIR_DEGREE) {
             int row_deg = 0;                               // lane r < 32: edges found at row wrow0 + r in this tile
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
@@ -218,7 +250,7 @@ __device__ __forceinline__ void cluster_pair_body(const ClusterArgs& p) {
                 row_deg += lane == r_lo ? lo : lane == r_lo + 4 ? hi : 0;
             }
             if (lane < 32 && row_deg > 0) atomicAdd(p.deg + wrow0 + lane, row_deg);    // (row_deg > 0 implies the row is below G)
-        } else {
+        } else if constexpr (MODE == PAIR_LINK) {
             const long arow = wrow0 + fr;
             const unsigned row_core = (unsigned)__ballot(arow < p.G && p.deg[arow < p.G ? arow : 0] + 1 >= p.min_pts);   // bit r: row wrow0 + r
 #pragma unroll
@@ -236,9 +268,42 @@ __device__ __forceinline__ void cluster_pair_body(const ClusterArgs& p) {
                     }
                 }
             }
+        } else {
+            // lane r (and r + 32) holds the id of row wrow0 + r; an accumulator's row id comes by shuffle.  Every live pair is one LDS
+            // atomic: bin `hist_bin(sc)` of its class' plane, or the class' NaN counter.
+            unsigned* h = pair_hist_lds();
+            const long arow = wrow0 + fr;
+            const int my_id = arow < p.G ? p.ids[arow] : 0;
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                const int r = 8 * (e >> 2) + (e & 3) + 4 * fh2;
+                const long row = wrow0 + r;
+                const int row_id = __shfl(my_id, r);
+#pragma unroll
+                for (int j = 0; j < TN; ++j) {
+                    const float sc = (acc[j][e] + 1.0f) / 2.0f;
+                    if (col_ok[j] && row < col[j]) {                    // (row < col < G)
+                        const int b = hist_bin(sc);
+                        const int cls = row_id == col_id[j] ? 0 : 1;
+                        atomicAdd(&h[b >= 0 ? cls * kHistBins + b : 2 * kHistBins + cls], 1u);
+                    }
+                }
+            }
         }
     }
-    if constexpr (!LINK) {
+    if constexpr (MODE == PAIR_HIST) {
+        // A run of t tiles adds at most t * 128 * 64 = t * 8192 to one 32-bit counter; the launcher keeps t <= 2^18 (automatic runs are at
+        // most 8 tiles), so a counter never exceeds 2^31.  Non-zero counters go to the scratch histogram (copy blockIdx.x % copies of it)
+        // with 64-bit atomics.
+        unsigned* h = pair_hist_lds();
+        unsigned long long* dst = p.hist + (size_t)(blockIdx.x % (unsigned)p.copies) * kHistSlots;
+        __syncthreads();
+        for (int i = tid; i < kHistSlots; i += 256) {
+            const unsigned c = h[i];
+            if (c) atomicAdd(dst + i, (unsigned long long)c);
+        }
+    }
+    if constexpr (MODE == PAIR_DEGREE) {
 #pragma unroll
         for (int j = 0; j < TN; ++j)
             if (col_deg[j] > 0) atomicAdd(&colcnt[j * 32 + fr], col_deg[j]);
@@ -247,8 +312,20 @@ __device__ __forceinline__ void cluster_pair_body(const ClusterArgs& p) {
     }
 }
 
-__global__ __launch_bounds__(256, 2) void cluster_degree_kernel(const ClusterArgs p) { cluster_pair_body<false>(p); }
-__global__ __launch_bounds__(256, 2) void cluster_link_kernel(const ClusterArgs p) { cluster_pair_body<true>(p); }
+__global__ __launch_bounds__(256, 2) void cluster_degree_kernel(const ClusterArgs p) { cluster_pair_body<PAIR_DEGREE>(p); }
+__global__ __launch_bounds__(256, 2) void cluster_link_kernel(const ClusterArgs p) { cluster_pair_body<PAIR_LINK>(p); }
+__global__ __launch_bounds__(256, 2) void cluster_hist_kernel(const ClusterArgs p) { cluster_pair_body<PAIR_HIST>(p); }
+
+// sums the privatised copies into the caller's buffers (both overwritten); d_nan may be null
+__global__ __launch_bounds__(256) void cluster_hist_reduce_kernel(const unsigned long long* __restrict__ part, int copies,
+                                                                  unsigned long long* __restrict__ hist, unsigned long long* __restrict__ nan) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= kHistSlots) return;
+    unsigned long long s = 0ull;
+    for (int c = 0; c < copies; ++c) s += part[(size_t)c * kHistSlots + i];
+    if (i < 2 * kHistBins) hist[i] = s;
+    else if (nan) nan[i - 2 * kHistBins] = s;
+}
 
 __global__ __launch_bounds__(256) void cluster_init_kernel(long G, int* deg, int* parent, unsigned long long* best, int* info) {
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
@@ -288,18 +365,10 @@ __global__ __launch_bounds__(256) void cluster_flatten_kernel(long G, int min_pt
 }
 
 int g_cluster_tiles = 0;
+int g_hist_copies = 0;
 
-}  // namespace
-
-void cluster_debug_tiles(int tiles_per_wg) { g_cluster_tiles = tiles_per_wg > 0 ? tiles_per_wg : 0; }
-
-void launch_gallery_cluster(const float* gal, long G, int dim, float thr, int min_pts, bool noise_self, int* deg, int* parent,
-                            unsigned long long* best, int* labels, int* info, hipStream_t s) {
-    if (G <= 0) return;
-    if (dim % 64) throw std::runtime_error("gallery: dim must be a multiple of 64");
-    ClusterArgs a{};
-    a.gal = gal; a.zeros = conv_zero_line(); a.G = G; a.dim = dim; a.min_pts = min_pts; a.thr = thr;
-    a.deg = deg; a.parent = parent; a.best = best;
+// the pair passes' grid: tiles, the run length (A tiles per workgroup) and the number of workgroups
+unsigned cluster_pair_grid(ClusterArgs& a, long G) {
     a.tiles_n = (int)((G + GAL_BN - 1) / GAL_BN);
     a.row_tiles = (int)((G + GAL_BM - 1) / GAL_BM);
     // A tiles per workgroup: a longer run flushes the column counts less often and re-reads the core flags less often, a shorter one
@@ -310,16 +379,54 @@ void launch_gallery_cluster(const float* gal, long G, int dim, float thr, int mi
         t = pairs / (16L * conv_num_cus());
         t = t < 1 ? 1 : t > 8 ? 8 : t;
     }
+    t = t > (1L << 18) ? (1L << 18) : t;                                 // (the histogram pass's 32-bit LDS counters: t * 8192 < 2^32)
     a.tiles_per_wg = (int)(t > a.row_tiles ? a.row_tiles : t);
     // a rectangular grid of (B tile, run): the last B tile reaches every row tile; runs wholly below a B tile's diagonal exit at once
     const long runs = (a.row_tiles + a.tiles_per_wg - 1) / a.tiles_per_wg;
     const long grid = runs * a.tiles_n;
     if (grid > 0x7fffffffL) throw std::runtime_error("gallery: too many rows for one clustering launch");
+    return (unsigned)grid;
+}
+
+}  // namespace
+
+void cluster_debug_tiles(int tiles_per_wg) { g_cluster_tiles = tiles_per_wg > 0 ? tiles_per_wg : 0; }
+void cluster_debug_hist_copies(int copies) { g_hist_copies = copies > 0 ? (copies > 4096 ? 4096 : copies) : 0; }
+
+void launch_gallery_cluster(const float* gal, long G, int dim, float thr, int min_pts, bool noise_self, int* deg, int* parent,
+                            unsigned long long* best, int* labels, int* info, hipStream_t s) {
+    if (G <= 0) return;
+    if (dim % 64) throw std::runtime_error("gallery: dim must be a multiple of 64");
+    ClusterArgs a{};
+    a.gal = gal; a.zeros = conv_zero_line(); a.G = G; a.dim = dim; a.min_pts = min_pts; a.thr = thr;
+    a.deg = deg; a.parent = parent; a.best = best;
+    const unsigned grid = cluster_pair_grid(a, G);
     const unsigned gb = (unsigned)((G + 255) / 256);
     hipLaunchKernelGGL(cluster_init_kernel, dim3(gb), dim3(256), 0, s, G, deg, parent, best, info);
-    if (min_pts > 1) hipLaunchKernelGGL(cluster_degree_kernel, dim3((unsigned)grid), dim3(256), 0, s, a);
-    hipLaunchKernelGGL(cluster_link_kernel, dim3((unsigned)grid), dim3(256), 0, s, a);
+    if (min_pts > 1) hipLaunchKernelGGL(cluster_degree_kernel, dim3(grid), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(cluster_link_kernel, dim3(grid), dim3(256), 0, s, a);
     hipLaunchKernelGGL(cluster_flatten_kernel, dim3(gb), dim3(256), 0, s, G, min_pts, noise_self ? 1 : 0, deg, parent, best, labels, info);
+}
+
+// The workgroups flush into a scratch histogram and a small kernel writes the caller's two buffers from it (d_nan may be null, and the
+// 64-bit atomics stay off the caller's memory).  The impostor scores of real embeddings pile into a few hundred bins and every live
+// workgroup flushes those same bins, so the scratch may hold several privatised copies (copy = blockIdx.x % copies) that the small
+// kernel sums — measured at G = 65 536 and 262 144, 1 to 512 copies change the call's time by under 1 % either way
+// (profiles/gallery_hist.md: the flush is not what the epilogue costs), so the default is one; cluster_debug_hist_copies re-measures.
+int gallery_pair_hist_copies() { return g_hist_copies > 0 ? g_hist_copies : kHistDefaultCopies; }
+size_t gallery_pair_hist_scratch_bytes() { return (size_t)gallery_pair_hist_copies() * kHistSlots * sizeof(unsigned long long); }
+
+void launch_gallery_pair_hist(const float* gal, const int* ids, long G, int dim, unsigned long long* scratch, unsigned long long* hist,
+                              unsigned long long* nan, hipStream_t s) {
+    if (G <= 0) return;
+    if (dim % 64) throw std::runtime_error("gallery: dim must be a multiple of 64");
+    ClusterArgs a{};
+    a.gal = gal; a.zeros = conv_zero_line(); a.G = G; a.dim = dim;
+    a.ids = ids; a.hist = scratch; a.copies = gallery_pair_hist_copies();
+    const unsigned grid = cluster_pair_grid(a, G);
+    FH_HIP(hipMemsetAsync(scratch, 0, gallery_pair_hist_scratch_bytes(), s));
+    hipLaunchKernelGGL(cluster_hist_kernel, dim3(grid), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(cluster_hist_reduce_kernel, dim3((kHistSlots + 255) / 256), dim3(256), 0, s, scratch, a.copies, hist, nan);
 }
 
 }  // namespace fh

@@ -375,6 +375,13 @@ void launch_gallery_self_scores(const float* src, const int* src_ids, long n, co
 void launch_gallery_cluster(const float* gal, long G, int dim, float thr, int min_pts, bool noise_self, int* deg, int* parent,
                             unsigned long long* best, int* labels, int* info, hipStream_t s);
 void cluster_debug_tiles(int tiles_per_wg);   // test hook: A tiles per workgroup run of the pair passes (0 = automatic)
+// The same pair pass with the histogram epilogue (fh_gallery_pair_hist_dev; the bin rule: roc_plan.h): hist [2][kHistBins] (genuine,
+// impostor) and nan [2] (may be null) are overwritten with the counts over all pairs row < col < G; scratch holds
+// gallery_pair_hist_scratch_bytes() and is cleared on s first.  G <= 0 launches nothing.
+void launch_gallery_pair_hist(const float* gal, const int* ids, long G, int dim, unsigned long long* scratch, unsigned long long* hist,
+                              unsigned long long* nan, hipStream_t s);
+size_t gallery_pair_hist_scratch_bytes();
+void cluster_debug_hist_copies(int copies);   // measurement hook: privatised histogram copies the workgroups flush into (0 = default)
 
 // gallery_f16.hip — the opt-in F16_RERANK scan (fh_gallery_set_scan): an fp16 copy of the rows is scanned for the top GAL16_KC candidates
 // per query, the candidates are re-scored from the fp32 rows exactly as gallery_topk_kernel scores them, and a per-query certificate

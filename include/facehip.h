@@ -691,6 +691,45 @@ FH_API int fh_cluster_scores(const float* scores, int n, float threshold, int mi
 FH_API int fh_gallery_cluster_dev(fh_gallery* g, float threshold, int min_pts, int noise, int* d_labels, int* d_info, void* stream);
 FH_API long long fh_gallery_set_ids(fh_gallery* g, const int* ids, int on_device);
 
+/* ---- threshold calibration: every decision above is the strict test `score > threshold`; these calls measure, on the caller's own
+ * labelled gallery, what a threshold does: exact genuine / impostor score histograms over all pairs of rows, and the operating points
+ * read off them.  (What the resulting thresholds mean for recognition accuracy depends on the trained weights: not measured here.)
+ *   hist_bin    host only, and the one place the bin rule is defined (the device runs the same function).  FH_HIST_BINS = 2048 bins over
+ *               the mapped score: with t = score * 2048.0f (a power of two: exact) it returns -1 for a NaN, 0 for t <= 1, 2047 for
+ *               t > 2047 (+inf too), (int)ceilf(t) - 1 otherwise.  Bin b holds b/2048 < s <= (b+1)/2048; bin 0 also everything at or
+ *               below 1/2048 (scores <= 0), bin 2047 everything above 2047/2048 (a score a hair above 1).  The half-open side makes the
+ *               suffix sum A[b] = sum of h[b'] over b' >= b EXACTLY the number of pairs that `s > b/2048` accepts, for every b in
+ *               1..2047 (b/2048 is an exact fp32 value); A[0] counts every non-NaN pair.
+ *   roc_from_hist   host only, no GPU.  hist[2][FH_HIST_BINS]: plane 0 genuine, plane 1 impostor; N_g, N_i = the plane sums.
+ *               out[0] = the operating point of max_far: the smallest b in 1..2047 with A_i[b] <= (uint64)floor(max_far * (double)N_i);
+ *               out[1] = the equal-error point: the smallest b in 1..2047 with FAR_b <= FRR_b, decided in integers
+ *               (A_i[b] * N_g <= (N_g - A_g[b]) * N_i in 128 bits).  A point is {threshold = b / 2048.0f, bin = b, true_accepts = A_g[b],
+ *               false_accepts = A_i[b], genuine = N_g, impostor = N_i}; one for which no b exists has bin -1, threshold 1.0f and zero
+ *               accept counts.  Returns FH_OK; nothing is written on FH_ERR_ARG (NULL pointer, max_far outside [0, 1] or NaN) and on
+ *               FH_ERR_STATE (N_g == 0 or N_i == 0).
+ *   pair_hist_dev   over all G (G - 1) / 2 unordered pairs of the gallery's fp32 rows, whatever the scan mode: the score of a pair is
+ *               exactly the one fh_gallery_topk_dev reports for query = row i against row j (see fh_gallery_cluster_dev: the same pair
+ *               pass with another epilogue), binned by hist_bin; a pair is genuine iff the two rows carry the same id.  d_hist
+ *               [2][FH_HIST_BINS] and d_nan [2] (may be NULL) are device buffers and are OVERWRITTEN, not accumulated; a NaN-scored pair
+ *               is in no bin and is counted per class in d_nan.  So
+ *                   sum(hist[0]) + nan[0] = sum over identities of n_id (n_id - 1) / 2,
+ *                   sum(hist[0]) + sum(hist[1]) + nan[0] + nan[1] = G (G - 1) / 2.
+ *               The index base plays no part.  Asynchronous on `stream`; returns FH_OK.  Before anything is launched: FH_ERR_ARG for a
+ *               NULL handle or d_hist, FH_ERR_STATE for a non-empty UNLABELLED gallery (such a caller uses fh_gallery_set_ids first).  An
+ *               empty gallery writes zeros and launches nothing else.  dim % 64 == 0 as for every scan.  Scratch (one
+ *               histogram, 32 KB) lives in the handle, grows on demand and is cleared on `stream` by every call.  Counts are
+ *               identical to the host rule's on the scan's scores, not close.  Pairs are PER GALLERY: cross-shard pairs of a sharded
+ *               deployment are out of scope, so such a deployment calibrates on an unsharded sample. */
+#define FH_HIST_BINS 2048
+typedef struct fh_roc_point {
+    float threshold;
+    int32_t bin;
+    unsigned long long true_accepts, false_accepts, genuine, impostor;
+} fh_roc_point;
+FH_API int fh_hist_bin(float score);
+FH_API int fh_roc_from_hist(const unsigned long long* hist, double max_far, fh_roc_point out[2]);
+FH_API int fh_gallery_pair_hist_dev(fh_gallery* g, unsigned long long* d_hist, unsigned long long* d_nan, void* stream);
+
 /* ---- measurement hooks (bench.py): per-launch HIP-event timing of the network kernels.
  * Tags 0..3 = conv_igemm tile configs (128x128, 256x64, 128x32, 64x64), 4 = depthwise / depthwise+pointwise,
  * 5 = other graph ops, 6 = conv stream-K fix-up, 7 = Winograd GEMM (its FLOPs = executed; bytes slot = the layer's
@@ -802,6 +841,9 @@ FH_API int fh_debug_wino_slots(int slots);
  * the launcher gives runs of more than one tile only to large galleries; tiles_per_wg > 0 fixes the run length, so that a small gallery
  * walks runs of several tiles; 0 restores the automatic choice. */
 FH_API int fh_debug_cluster_tiles(int tiles_per_wg);
+/* Measurement hook of fh_gallery_pair_hist_dev: the number of privatised histogram copies its workgroups flush into (1..4096; 0 restores
+ * the default, 1).  The result does not depend on it (scripts/gallery_hist_ab.py --copies). */
+FH_API int fh_debug_hist_copies(int copies);
 /* Test hook of the split-bf16 operand format (winograd.hip wino_pack_bf16x2): n f32 words -> n packed words, hi = bf16(x) in the low half,
  * mid = bf16(x - hi) in the high half, both round-to-nearest-even.  n % 4 == 0.  Synchronous. */
 FH_API int fh_debug_pack_bf16x2_dev(const float* d_in, float* d_out, long long n);
