@@ -51,6 +51,7 @@ TRACK_LINK_DTYPE = np.dtype([("owner", "<i4"), ("root", "<i4"), ("n_emb", "<i4")
 assert TRACK_LINK_DTYPE.itemsize == 32
 TRACK_LINK_MEMORY = 256                                        # FH_TRACK_LINK_MEMORY
 HIST_BINS = 2048                                               # FH_HIST_BINS
+TAG_ALL = 0xFFFFFFFF                                           # FH_TAG_ALL
 ROC_POINT_DTYPE = np.dtype([("threshold", "<f4"), ("bin", "<i4"), ("true_accepts", "<u8"), ("false_accepts", "<u8"), ("genuine", "<u8"),
                             ("impostor", "<u8")])              # fh_roc_point
 assert ROC_POINT_DTYPE.itemsize == 40
@@ -196,6 +197,14 @@ PROTOTYPES = {
     "fh_roc_from_hist": (_i, [_vp, _d, _vp]),
     "fh_gallery_pair_hist_dev": (_i, [_vp, _vp, _vp, _vp]),
     "fh_gallery_set_ids": (_ll, [_vp, _vp, _i]),
+    "fh_gallery_set_tags": (_ll, [_vp, _ll, _ll, _vp, _i]),
+    "fh_gallery_get_tags": (_ll, [_vp, _ll, _ll, _vp]),
+    "fh_gallery_topk_tagged_dev": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp]),
+    "fh_gallery_topk_ids_tagged_dev": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),
+    "fh_gallery_label_tagged_dev": (_i, [_vp, _vp, _vp, _i, _f, _vp, _vp, _vp]),
+    "fh_gallery_label_ids_tagged_dev": (_i, [_vp, _vp, _vp, _i, _f, _vp, _vp, _vp]),
+    "fh_gallery_tag_stats": (_i, [_vp, C.POINTER(_ll), C.POINTER(_ll)]),
+    "fh_tracker_set_stream_masks": (_i, [_vp, _vp]),
     "fh_comm_unique_id": (_i, [_vp]),
     "fh_comm_create": (_vp, [_i, _i, _vp, _i]),
     "fh_comm_destroy": (None, [_vp]),
@@ -227,6 +236,7 @@ PROTOTYPES = {
     "fh_debug_wino_slots": (_i, [_i]),
     "fh_debug_cluster_tiles": (_i, [_i]),
     "fh_debug_hist_copies": (_i, [_i]),
+    "fh_debug_tag_skip": (_i, [_i]),
     "fh_debug_topk_merge_strided_dev": (_i, [_vp, _vp, _i, _i, _i, _ll, _vp, _vp, _vp]),
     "fh_set_graph_replay": (_i, [_i]),
     "fh_det_workspace_dev": (_vp, [_vp]),

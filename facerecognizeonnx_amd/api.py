@@ -446,6 +446,17 @@ class Tracker:
                                                       slot_ptr, embed_ptr, emb_ptr, int(total), n, per_frame, sp, label_ptr, score_ptr,
                                                       stream), "fh_track_identify_dev")
 
+    def set_stream_masks(self, masks=None) -> None:
+        """A watchlist per camera (fh_tracker_set_stream_masks): masks = uint32[streams]; identify_dev then labels every face of
+        stream s against the gallery rows whose tag shares a bit with masks[s] (Gallery.set_tags).  None switches the masks off."""
+        if masks is None:
+            check(_lib.lib().fh_tracker_set_stream_masks(self._h, None), "fh_tracker_set_stream_masks")
+            return
+        masks = np.ascontiguousarray(np.asarray(masks).reshape(-1).astype(np.uint32))
+        if masks.size != self.streams:
+            raise ValueError("set_stream_masks: need one mask per stream")
+        check(_lib.lib().fh_tracker_set_stream_masks(self._h, masks.ctypes.data), "fh_tracker_set_stream_masks")
+
     def queries_ptr(self) -> int:
         """Device pointer of the [total][dim] queries of the last identify_dev (a stage hook for tests)."""
         return _lib.lib().fh_tracker_queries_dev(self._h) or 0
@@ -751,6 +762,55 @@ class Gallery:
         if ids.size != len(self):
             raise ValueError("set_ids: need one id per row")
         return check(_lib.lib().fh_gallery_set_ids(self._h, ids.ctypes.data if ids.size else None, 0), "fh_gallery_set_ids")
+
+    def set_tags(self, tags, first: int = 0) -> int:
+        """Set the watchlist tags (uint32 bit sets; one int for all rows) of rows [first, first + len(tags)) by position
+        (fh_gallery_set_tags): a host array or a contiguous device tensor of 4-byte integers.  Row r is admitted for a query with mask
+        m iff tag[r] & m != 0; rows whose tags were never set carry TAG_ALL.  Synchronous; returns the number of rows set."""
+        if hasattr(tags, "data_ptr"):
+            if tags.element_size() != 4 or not tags.is_contiguous():
+                raise ValueError("set_tags: need a contiguous tensor of 4-byte integers")
+            return check(_lib.lib().fh_gallery_set_tags(self._h, first, tags.numel(), tags.data_ptr(), int(tags.is_cuda)), "fh_gallery_set_tags")
+        tags = np.asarray(tags)
+        if tags.ndim == 0:
+            tags = np.full(len(self) - first, tags)
+        tags = np.ascontiguousarray(tags.reshape(-1).astype(np.uint32))
+        return check(_lib.lib().fh_gallery_set_tags(self._h, first, tags.size, tags.ctypes.data if tags.size else None, 0), "fh_gallery_set_tags")
+
+    def get_tags(self, first: int = 0, n: Optional[int] = None) -> np.ndarray:
+        """Tags of rows [first, first + n) by position (default: to the end), uint32 (fh_gallery_get_tags)."""
+        if n is None:
+            n = len(self) - first
+        out = np.empty(max(n, 0), np.uint32)
+        check(_lib.lib().fh_gallery_get_tags(self._h, first, n, out.ctypes.data if n > 0 else None), "fh_gallery_get_tags")
+        return out
+
+    def topk_tagged_dev(self, q_ptr: int, masks_ptr: int, nq: int, k: int, scores_ptr: int, idx_ptr: int, stream: int = 0):
+        """topk_dev over each query's ADMITTED rows only (masks = device uint32[nq]); indices stay global; exact, bit for bit."""
+        check(_lib.lib().fh_gallery_topk_tagged_dev(self._h, q_ptr, masks_ptr, nq, k, scores_ptr, idx_ptr, stream), "fh_gallery_topk_tagged_dev")
+
+    def topk_ids_tagged_dev(self, q_ptr: int, masks_ptr: int, nq: int, k: int, scores_ptr: int, ids_ptr: int, rows_ptr: Optional[int] = None,
+                            stream: int = 0):
+        """topk_ids_dev over each query's admitted rows only: an identity is represented by its best ADMITTED row."""
+        check(_lib.lib().fh_gallery_topk_ids_tagged_dev(self._h, q_ptr, masks_ptr, nq, k, scores_ptr, ids_ptr, rows_ptr, stream),
+              "fh_gallery_topk_ids_tagged_dev")
+
+    def label_tagged_dev(self, q_ptr: int, masks_ptr: int, nq: int, threshold: float, labels_ptr: int, scores_ptr: int, stream: int = 0):
+        """label_dev over each query's admitted rows only (mask 0: -1, -1.0)."""
+        check(_lib.lib().fh_gallery_label_tagged_dev(self._h, q_ptr, masks_ptr, nq, threshold, labels_ptr, scores_ptr, stream),
+              "fh_gallery_label_tagged_dev")
+
+    def label_ids_tagged_dev(self, q_ptr: int, masks_ptr: int, nq: int, threshold: float, ids_ptr: int, scores_ptr: int, stream: int = 0):
+        """label_ids_dev over each query's admitted rows only."""
+        check(_lib.lib().fh_gallery_label_ids_tagged_dev(self._h, q_ptr, masks_ptr, nq, threshold, ids_ptr, scores_ptr, stream),
+              "fh_gallery_label_ids_tagged_dev")
+
+    def tag_stats(self):
+        """(tiles_scanned, tiles_skipped): the (workgroup, 128-row tile) visits the tagged scans multiplied / skipped since the last
+        call (resets; waits for the handle's queued work)."""
+        a, b = C.c_longlong(0), C.c_longlong(0)
+        check(_lib.lib().fh_gallery_tag_stats(self._h, C.byref(a), C.byref(b)), "fh_gallery_tag_stats")
+        return int(a.value), int(b.value)
 
     def __len__(self) -> int:
         return int(_lib.lib().fh_gallery_size(self._h))

@@ -1108,6 +1108,10 @@ int fh_tracker_enable_relink(fh_tracker* t, int memory, float link_thr, int max_
         return arg_error("fh_tracker_enable_relink: need 0 <= memory <= 256, a finite link_thr and max_age > max_missed");
     return guarded([&] { t->t.enable_relink(memory, link_thr, max_age); return 0; });
 }
+int fh_tracker_set_stream_masks(fh_tracker* t, const uint32_t* masks_host) {
+    if (!t) return arg_error("fh_tracker_set_stream_masks: null handle");
+    return guarded([&] { t->t.set_stream_masks(masks_host); return 0; });
+}
 int fh_track_identify_link_dev(fh_tracker* t, fh_gallery* g, float threshold, const int* track, const int* slot, const int* embed,
                                const int* quality, const float* emb, int total, int n, int per_frame, const int* stream_of, int* label,
                                float* score, int* root, void* stream) {
@@ -1326,6 +1330,47 @@ long long fh_gallery_get_ids(fh_gallery* g, long long first, long long n, int* i
     const int rc = guarded([&] { g->g.get_ids((long)first, (long)n, ids_host_out); return 0; });
     return rc < 0 ? rc : n;
 }
+
+// ---- watchlists (gallery_tags.hip): a tag per row, a mask per query, the predicate inside the scan's admission test
+long long fh_gallery_set_tags(fh_gallery* g, long long first, long long n, const uint32_t* tags, int on_device) {
+    if (!g || first < 0 || n < 0 || (n > 0 && !tags)) return arg_error("fh_gallery_set_tags: bad argument");
+    if (first + n > (long long)g->g.size()) return arg_error("fh_gallery_set_tags: range outside the gallery");
+    const int rc = guarded([&] { g->g.set_tags((long)first, (long)n, tags, on_device != 0); return 0; });
+    return rc < 0 ? rc : n;
+}
+long long fh_gallery_get_tags(fh_gallery* g, long long first, long long n, uint32_t* tags_host_out) {
+    if (!g || first < 0 || n < 0 || (n > 0 && !tags_host_out)) return arg_error("fh_gallery_get_tags: bad argument");
+    if (first + n > (long long)g->g.size()) return arg_error("fh_gallery_get_tags: range outside the gallery");
+    const int rc = guarded([&] { g->g.get_tags((long)first, (long)n, tags_host_out); return 0; });
+    return rc < 0 ? rc : n;
+}
+int fh_gallery_topk_tagged_dev(fh_gallery* g, const float* q, const uint32_t* masks, int nq, int k, float* scores, int* indices, void* stream) {
+    if (!g || !q || !masks || !scores || !indices) return arg_error("fh_gallery_topk_tagged_dev: null argument");
+    return guarded([&] { g->g.topk_tagged_dev(q, masks, nq, k, scores, indices, S(stream)); return nq; });
+}
+int fh_gallery_topk_ids_tagged_dev(fh_gallery* g, const float* q, const uint32_t* masks, int nq, int k, float* scores, int* ids, int* rows,
+                                   void* stream) {
+    if (!g || !q || !masks || !scores || !ids) return arg_error("fh_gallery_topk_ids_tagged_dev: null argument");
+    if (nq <= 0 || nq > 256 || k <= 0 || k > 16) return arg_error("fh_gallery_topk_ids_tagged_dev: need 0 < nq <= 256 and 0 < k <= 16");
+    return guarded([&] { g->g.topk_ids_tagged_dev(q, masks, nq, k, scores, ids, rows, S(stream)); return nq; });
+}
+int fh_gallery_label_tagged_dev(fh_gallery* g, const float* q, const uint32_t* masks, int nq, float threshold, int* labels, float* scores,
+                                void* stream) {
+    if (!g || !q || !masks || !labels || !scores) return arg_error("fh_gallery_label_tagged_dev: null argument");
+    return guarded([&] { g->g.label_tagged_dev(q, masks, nq, threshold, labels, scores, S(stream)); return nq; });
+}
+int fh_gallery_label_ids_tagged_dev(fh_gallery* g, const float* q, const uint32_t* masks, int nq, float threshold, int* ids, float* scores,
+                                    void* stream) {
+    if (!g || !q || !masks || !ids || !scores) return arg_error("fh_gallery_label_ids_tagged_dev: null argument");
+    if (nq <= 0 || nq > 256) return arg_error("fh_gallery_label_ids_tagged_dev: need 0 < nq <= 256");
+    return guarded([&] { g->g.label_ids_tagged_dev(q, masks, nq, threshold, ids, scores, S(stream)); return nq; });
+}
+int fh_gallery_tag_stats(fh_gallery* g, long long* tiles_scanned, long long* tiles_skipped) {
+    if (!g) return arg_error("fh_gallery_tag_stats: null handle");
+    return guarded([&] { g->g.tag_stats(tiles_scanned, tiles_skipped); return 0; });
+}
+int fh_debug_tag_skip(int on) { fh::gallery_debug_tag_skip(on); return 0; }
+
 int fh_topk_merge_ids_dev(const float* ps, const int* pd, const int* pr, int nparts, int nq, int k, float* scores, int* ids, int* rows,
                           void* stream) {
     if (!ps || !pd || !pr || !scores || !ids || !rows) return arg_error("fh_topk_merge_ids_dev: null argument");

@@ -957,6 +957,7 @@ void Gallery::upload(const float* rows, const int* ids, long n, bool device_src,
     FH_HIP(hipMemcpy(rows_.p, rows, (size_t)n * dim_ * sizeof(float), device_src ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
     if (ids) FH_HIP(hipMemcpy(ids_.p, ids, (size_t)n * sizeof(int), device_src ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
     n_ = n; base_ = index_base; labelled_ = ids != nullptr; fused_ = false;
+    has_tags_ = false;                                           // a new row set: every row admitted everywhere until set_tags
     if (scan_ == 1) {
         rows16_.ensure((size_t)n * dim_ * sizeof(uint16_t));
         convert16(0, n);
@@ -1048,8 +1049,122 @@ long Gallery::enroll(const float* rows, const int* ids, long n, bool device_src)
     if (n_ == 0) labelled_ = ids != nullptr;
     fused_ = false;                                              // appended ids are neither distinct nor in order
     const long first = base_ + n_;
+    if (has_tags_) {                                             // the tags grow with the rows; the new rows are admitted everywhere
+        need_tags();
+        FH_HIP(hipMemset(tags_.as<unsigned>() + n_, 0xFF, (size_t)n * sizeof(unsigned)));
+        launch_tag_tile_or(tags_.as<unsigned>(), n_ + n, n_, n, tile_or_.as<unsigned>(), nullptr);
+        FH_HIP(hipGetLastError());
+        FH_HIP(hipDeviceSynchronize());
+    }
     n_ += n;
     return first;
+}
+
+// Tags.  The buffers follow the rows' capacity (as the ids do), so enroll appends in place; tile_or is rebuilt by position for the tiles
+// a change touches (set_tags: its range; enroll: from the old last tile on; remove_ids and fuse: all of them).
+void Gallery::need_tags() {
+    const size_t cap = rows_.bytes / ((size_t)dim_ * sizeof(float)), tiles = (cap + GAL_TAG_TILE - 1) / GAL_TAG_TILE;
+    const size_t have = has_tags_ ? (size_t)n_ : 0;
+    if (cap * sizeof(unsigned) > tags_.bytes) {
+        DevBuf bigger;
+        bigger.ensure(cap * sizeof(unsigned));
+        if (have > 0) FH_HIP(hipMemcpy(bigger.p, tags_.p, have * sizeof(unsigned), hipMemcpyDeviceToDevice));
+        std::swap(bigger.p, tags_.p);
+        std::swap(bigger.bytes, tags_.bytes);
+    }
+    if (tiles * sizeof(unsigned) > tile_or_.bytes) {
+        DevBuf bigger;
+        bigger.ensure(tiles * sizeof(unsigned));
+        if (have > 0) FH_HIP(hipMemcpy(bigger.p, tile_or_.p, (have + GAL_TAG_TILE - 1) / GAL_TAG_TILE * sizeof(unsigned), hipMemcpyDeviceToDevice));
+        std::swap(bigger.p, tile_or_.p);
+        std::swap(bigger.bytes, tile_or_.bytes);
+    }
+    if (!tag_ctr_.p) {
+        tag_ctr_.ensure(2 * sizeof(unsigned long long));
+        FH_HIP(hipMemset(tag_ctr_.p, 0, 2 * sizeof(unsigned long long)));
+    }
+    if (!has_tags_) {
+        if (n_ > 0) {
+            FH_HIP(hipDeviceSynchronize());                      // a queued tagged scan of an earlier row set may still read the buffers
+            FH_HIP(hipMemset(tags_.p, 0xFF, (size_t)n_ * sizeof(unsigned)));
+            launch_tag_tile_or(tags_.as<unsigned>(), n_, 0, n_, tile_or_.as<unsigned>(), nullptr);
+            FH_HIP(hipGetLastError());
+            FH_HIP(hipDeviceSynchronize());
+        }
+        has_tags_ = true;
+    }
+}
+
+void Gallery::set_tags(long first, long n, const unsigned* tags, bool device_src) {
+    if (first < 0 || n < 0 || first + n > n_) throw std::invalid_argument("gallery: tag range outside the gallery");
+    if (n == 0) return;
+    FH_HIP(hipDeviceSynchronize());                              // queued scans still read the tags that are about to change
+    need_tags();
+    FH_HIP(hipMemcpy(tags_.as<unsigned>() + first, tags, (size_t)n * sizeof(unsigned), device_src ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
+    launch_tag_tile_or(tags_.as<unsigned>(), n_, first, n, tile_or_.as<unsigned>(), nullptr);
+    FH_HIP(hipGetLastError());
+    FH_HIP(hipDeviceSynchronize());
+}
+
+void Gallery::get_tags(long first, long n, unsigned* out_host) {
+    if (first < 0 || n < 0 || first + n > n_) throw std::invalid_argument("gallery: tag range outside the gallery");
+    if (n == 0) return;
+    if (!has_tags_) { std::fill(out_host, out_host + n, 0xFFFFFFFFu); return; }
+    FH_HIP(hipDeviceSynchronize());
+    FH_HIP(hipMemcpy(out_host, tags_.as<unsigned>() + first, (size_t)n * sizeof(unsigned), hipMemcpyDeviceToHost));
+}
+
+void Gallery::tag_stats(long long* scanned, long long* skipped) {
+    unsigned long long h[2] = {0, 0};
+    FH_HIP(hipDeviceSynchronize());
+    if (tag_ctr_.p) {
+        FH_HIP(hipMemcpy(h, tag_ctr_.p, sizeof(h), hipMemcpyDeviceToHost));
+        FH_HIP(hipMemset(tag_ctr_.p, 0, sizeof(h)));
+    }
+    if (scanned) *scanned = (long long)h[0];
+    if (skipped) *skipped = (long long)h[1];
+}
+
+// A tagged query is always the fp32 scan: the 32 unfiltered fp16 candidates of F16_RERANK certify nothing about a subset of the rows.
+void Gallery::scan_tagged(const float* q, const unsigned* masks, int Q, int k, bool ids, float* out_score, int* out_id, int* out_row,
+                          hipStream_t s) {
+    if (Q <= 0 || Q > 256 || k <= 0 || k > 16) throw std::runtime_error("gallery: need 0 < Q <= 256 and 0 < k <= 16");
+    if (dim_ % 64) throw std::runtime_error("gallery: dim must be a multiple of 64");
+    if (scan_ == 1) host_fallback_ += Q;
+    if (n_ > 0) need_tags();
+    pack_queries(q, Q, s);
+    const int parts = size_lists(Q, k, ids);
+    launch_gallery_topk_tagged(rows_.as<float>(), ids ? ids_.as<int>() : nullptr, tags_.as<unsigned>(), tile_or_.as<unsigned>(), n_, dim_,
+                               qpack_.as<float>(), masks, Q, k, base_, ps_.as<float>(), pi_.as<int>(), pd_.as<int>(), seed_s_.as<float>(),
+                               seed_i_.as<int>(), seed_d_.as<int>(), tag_ctr_.as<unsigned long long>(), s);
+    if (ids) launch_topk_merge_ids(ps_.as<float>(), pd_.as<int>(), pi_.as<int>(), parts, Q, k, out_score, out_id, out_row, s);
+    else launch_topk_merge(ps_.as<float>(), pi_.as<int>(), parts, Q, k, out_score, out_row, s);
+    FH_HIP(hipGetLastError());
+}
+
+void Gallery::topk_tagged_dev(const float* q, const unsigned* masks, int Q, int k, float* out_score, int* out_idx, hipStream_t s) {
+    scan_tagged(q, masks, Q, k, false, out_score, nullptr, out_idx, s);
+}
+
+void Gallery::topk_ids_tagged_dev(const float* q, const unsigned* masks, int Q, int k, float* out_score, int* out_id, int* out_row,
+                                  hipStream_t s) {
+    need_labelled("fh_gallery_topk_ids_tagged_dev");
+    scan_tagged(q, masks, Q, k, true, out_score, out_id, out_row, s);
+}
+
+void Gallery::label_tagged_dev(const float* q, const unsigned* masks, int Q, float thr, int* out_label, float* out_score, hipStream_t s) {
+    best_i_.ensure((size_t)std::max(Q, 1) * sizeof(int));
+    scan_tagged(q, masks, Q, 1, false, out_score, nullptr, best_i_.as<int>(), s);
+    launch_label(out_score, best_i_.as<int>(), Q, thr, out_label, s);
+}
+
+void Gallery::label_ids_tagged_dev(const float* q, const unsigned* masks, int Q, float thr, int* out_id, float* out_score, hipStream_t s) {
+    need_labelled("fh_gallery_label_ids_tagged_dev");
+    // the best admitted identity is the identity of the best admitted row
+    best_i_.ensure((size_t)std::max(Q, 1) * sizeof(int));
+    scan_tagged(q, masks, Q, 1, false, out_score, nullptr, best_i_.as<int>(), s);
+    launch_ids_of_rows(out_score, best_i_.as<int>(), Q, ids_.as<int>(), base_, thr, true, out_id, s);
+    FH_HIP(hipGetLastError());
 }
 
 void Gallery::need_labelled(const char* what) const {
@@ -1074,7 +1189,7 @@ void Gallery::get_rows(long first, long n, float* out_host) {
 long Gallery::fuse_from(Gallery& src, bool unit, int chunk) {
     if (dim_ % 64) throw std::runtime_error("gallery: dim must be a multiple of 64");
     if (src.n_ == 0) {                                           // nothing to read, nothing to launch: the capacity stays
-        n_ = 0; base_ = 0; fused_ = true;
+        n_ = 0; base_ = 0; fused_ = true; has_tags_ = false;
         return 0;
     }
     FH_HIP(hipDeviceSynchronize());                              // queued scans of either handle still read what is about to change
@@ -1111,6 +1226,17 @@ long Gallery::fuse_from(Gallery& src, bool unit, int chunk) {
     FH_HIP(hipGetLastError());
     FH_HIP(hipDeviceSynchronize());
     n_ = m; base_ = 0; labelled_ = true; fused_ = true;
+    has_tags_ = false;
+    if (src.has_tags_) {                                         // row j carries the OR of the tags of identity j's rows
+        DevBuf d_starts;
+        d_starts.ensure(((size_t)m + 1) * sizeof(long long));
+        FH_HIP(hipMemcpy(d_starts.p, starts.data(), ((size_t)m + 1) * sizeof(long long), hipMemcpyHostToDevice));
+        need_tags();                                             // (all ones first: one more pass over m words)
+        launch_fuse_tags(src.tags_.as<unsigned>(), d_order.as<int>(), d_starts.as<long long>(), m, tags_.as<unsigned>(), nullptr);
+        launch_tag_tile_or(tags_.as<unsigned>(), m, 0, m, tile_or_.as<unsigned>(), nullptr);
+        FH_HIP(hipGetLastError());
+        FH_HIP(hipDeviceSynchronize());
+    }
     if (scan_ == 1) {
         rows16_.ensure((size_t)m * dim_ * sizeof(uint16_t));
         convert16(0, m);
@@ -1182,7 +1308,7 @@ long Gallery::remove_ids(const int* ids_host, long n_ids) {
     if (removed == 0) return 0;
     if (m == 0) { n_ = 0; return removed; }                      // empty again (capacity kept); the next enrol decides the kind afresh
     const size_t row_bytes = (size_t)dim_ * sizeof(float), row16 = (size_t)dim_ * sizeof(uint16_t);
-    DevBuf dmap, rows2, ids2, rows16b;
+    DevBuf dmap, rows2, ids2, rows16b, tags2;
     dmap.ensure((size_t)m * sizeof(int));
     FH_HIP(hipMemcpy(dmap.p, map.data(), (size_t)m * sizeof(int), hipMemcpyHostToDevice));
     rows2.ensure((size_t)m * row_bytes);
@@ -1193,12 +1319,22 @@ long Gallery::remove_ids(const int* ids_host, long n_ids) {
         rows16b.ensure((size_t)m * row16);
         launch_gather_rows(rows16_.p, rows16b.p, dmap.as<int>(), m, row16, nullptr);
     }
+    if (has_tags_) {                                             // the tags are 4-byte words: the ids' gather moves them with the rows
+        tags2.ensure((size_t)m * sizeof(unsigned));
+        launch_gather_ids(tags_.as<int>(), tags2.as<int>(), dmap.as<int>(), m, nullptr);
+    }
     FH_HIP(hipGetLastError());
     FH_HIP(hipDeviceSynchronize());
     std::swap(rows2.p, rows_.p); std::swap(rows2.bytes, rows_.bytes);
     std::swap(ids2.p, ids_.p); std::swap(ids2.bytes, ids_.bytes);
     if (scan_ == 1) { std::swap(rows16b.p, rows16_.p); std::swap(rows16b.bytes, rows16_.bytes); }
     n_ = m;
+    if (has_tags_) {                                             // rows moved across tile borders: every tile's OR anew (m < the old row count: it fits)
+        std::swap(tags2.p, tags_.p); std::swap(tags2.bytes, tags_.bytes);
+        launch_tag_tile_or(tags_.as<unsigned>(), m, 0, m, tile_or_.as<unsigned>(), nullptr);
+        FH_HIP(hipGetLastError());
+        FH_HIP(hipDeviceSynchronize());
+    }
     return removed;
 }
 
@@ -1370,6 +1506,14 @@ void Tracker::enable_identity(int dim, int pool) {
     clear_identity(0, streams_);
 }
 
+void Tracker::set_stream_masks(const unsigned* masks_host) {
+    FH_HIP(hipDeviceSynchronize());                              // a queued identify still reads the masks
+    masks_on_ = masks_host != nullptr;
+    if (!masks_on_) return;
+    smask_.ensure((size_t)streams_ * sizeof(unsigned));
+    FH_HIP(hipMemcpy(smask_.p, masks_host, (size_t)streams_ * sizeof(unsigned), hipMemcpyHostToDevice));
+}
+
 void Tracker::clear_links(int first, int count) {
     const size_t rows = (size_t)link_rows(), entries = (size_t)count * rows;
     const std::vector<TrackLink> none(entries, TrackLink{-1, -1, 0, -1, -1.0f, 0, 0, 0});
@@ -1483,9 +1627,20 @@ void Tracker::identify_dev(Gallery& g, float thr, const int* track, const int* s
     }
     FH_HIP(hipGetLastError());
     const bool ids = g.labelled() && g.size() > 0;               // labels are identity ids / row indices
+    if (masks_on_ && total > 0) {                                // a watchlist per camera: every query carries its stream's mask
+        qmask_.ensure(rows * sizeof(unsigned));
+        launch_track_query_masks(smask_.as<unsigned>(), streams_, d_order, d_order + n, frame_off_.as<int>(), n, total, qmask_.as<unsigned>(), s);
+        FH_HIP(hipGetLastError());
+    }
     for (int c0 = 0; c0 < total; c0 += 256) {
         const int Q = std::min(256, total - c0);
         const float* q = queries_.as<float>() + (size_t)c0 * idim_;
+        if (masks_on_) {
+            const unsigned* m = qmask_.as<unsigned>() + c0;
+            if (ids) g.label_ids_tagged_dev(q, m, Q, thr, ans_label_.as<int>() + c0, ans_score_.as<float>() + c0, s);
+            else g.label_tagged_dev(q, m, Q, thr, ans_label_.as<int>() + c0, ans_score_.as<float>() + c0, s);
+            continue;
+        }
         if (ids) g.label_ids_dev(q, Q, thr, ans_label_.as<int>() + c0, ans_score_.as<float>() + c0, s);
         else g.label_dev(q, Q, thr, ans_label_.as<int>() + c0, ans_score_.as<float>() + c0, s);
     }

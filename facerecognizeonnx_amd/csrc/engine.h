@@ -335,6 +335,9 @@ class Tracker {
     int* roots_scratch(size_t entries) { roots_.ensure(entries * sizeof(int)); return roots_.as<int>(); }     // the pipeline's roots
     const int* roots() const { return roots_.as<int>(); }
     const float* queries() const { return queries_.as<float>(); }   // [total][dim] of the last identify_dev
+    // a watchlist per camera: masks_host [streams] (null: off, the default); with masks on, stage B of identify_dev labels every query
+    // through the gallery's tagged label call with the mask of its frame's stream.  Synchronous.
+    void set_stream_masks(const unsigned* masks_host);
     // the live slots' identities, ascending, into out[max_tracks] (the rest: id = -1) and their sums into sums_out[max_tracks][dim]
     // (may be null); returns their number; synchronous
     int get_identity(int stream, TrackIdent* out, float* sums_out);
@@ -356,6 +359,8 @@ class Tracker {
     bool relink_ = false;
     TrackLinkParams lp_{0, 0.f, 0, 0};
     DevBuf link_, msum_, roots_;                                 // [streams][max_tracks + memory] TrackLink / [streams][memory][idim_] / [n][F]
+    bool masks_on_ = false;
+    DevBuf smask_, qmask_;                                       // [streams] watchlist masks / [total] per-query masks of one identify_dev
 };
 
 class Gallery {
@@ -402,8 +407,22 @@ class Gallery {
     void set_scan(int mode);
     int scan() const { return scan_; }
     void scan_stats(long long* certified, long long* fallback);   // waits for the device; resets both
+    // Watchlists (gallery_tags.hip): a 32-bit tag per row, a 32-bit mask per query (device [Q]); row r is admitted for query q iff
+    // (tag[r] & mask[q]) != 0.  A gallery whose tags were never set (or not since the last upload) has none: it behaves as if every
+    // row carried all ones, and the tag buffers come into being with the first set_tags or tagged query.  Arguments checked by the
+    // caller except the ranges.  set_tags / get_tags: rows [first, first + n) by position; synchronous.
+    void set_tags(long first, long n, const unsigned* tags, bool device_src);
+    void get_tags(long first, long n, unsigned* out_host);
+    // the untagged calls of the same names on the sub-gallery of each query's admitted rows, global indices kept; always the fp32 scan
+    void topk_tagged_dev(const float* q, const unsigned* masks, int Q, int k, float* out_score, int* out_idx, hipStream_t s);
+    void topk_ids_tagged_dev(const float* q, const unsigned* masks, int Q, int k, float* out_score, int* out_id, int* out_row, hipStream_t s);
+    void label_tagged_dev(const float* q, const unsigned* masks, int Q, float thr, int* out_label, float* out_score, hipStream_t s);
+    void label_ids_tagged_dev(const float* q, const unsigned* masks, int Q, float thr, int* out_id, float* out_score, hipStream_t s);
+    void tag_stats(long long* scanned, long long* skipped);       // waits for the device; resets both
 
   private:
+    void need_tags();                                            // the tag buffers exist, sized to the rows' capacity (first use: all ones)
+    void scan_tagged(const float* q, const unsigned* masks, int Q, int k, bool ids, float* out_score, int* out_id, int* out_row, hipStream_t s);
     void convert16(long first, long n);                          // rows [first, first + n) -> rows16_, bounds + flag (synchronous)
     void topk_f16(const float* q, int Q, int k, float* out_score, int* out_idx, hipStream_t s);
     void topk_f32(const float* q, int Q, int k, float* out_score, int* out_idx, hipStream_t s, const int* qcount);
@@ -418,6 +437,8 @@ class Gallery {
     DevBuf cl_deg_, cl_parent_, cl_best_;                        // cluster_dev: degree, union-find parent, best core neighbour per row
     DevBuf cl_hist_;                                             // pair_hist_dev: the histogram the workgroups flush into
     DevBuf ids_, pd_, seed_d_;                                   // identity id per row (capacity in rows = rows_'), id planes of the part / seed lists
+    bool has_tags_ = false;
+    DevBuf tags_, tile_or_, tag_ctr_;                            // tag per row (capacity in rows = rows_'), OR per 128-row tile, [2] visit counters
     // F16_RERANK state: the fp16 rows, [max|g|, max|g^|, max|g - g^| (float bits), non-finite / > 65504 flag] on the device and its host
     // copy, per-call scratch, the certified / fallback counters
     int scan_ = 0;

@@ -76,6 +76,12 @@ struct GalArgs {
     const int* qcount;      // optional (device), fp32 scans: query tiles at or beyond *qcount exit at once (null: all Q)
     const int* ids;         // IDS: identity id of every row [G]
     int* pd;                // IDS: [parts][Q][k] identity ids beside ps / pi
+    // TAGS (gallery_tags.hip) — behind everything else, so that the other instantiations read their arguments where they always did
+    const unsigned* tags;     // tag word of every row [G]
+    const unsigned* qmask;    // mask word of every query [Q]
+    const unsigned* tile_or;  // OR of the tags of each 128-row tile, by position [row tiles of the WHOLE gallery]
+    unsigned long long* tag_ctr;   // [2]: (workgroup, row tile) visits multiplied / skipped, one atomic add each per workgroup
+    int tag_skip;             // 0: every tile is multiplied (fh_debug_tag_skip)
 };
 
 // ---- host side (gallery.hip); they sit here and not in kernels.h because they speak of GalArgs
@@ -106,8 +112,17 @@ __device__ __forceinline__ bool gal_better(float s1, int i1, float s2, int i2) {
 // entry (not yet placed: the listed one is better, the new one is dropped) or the entry it displaced (the new one is better and took
 // an earlier place) — is discarded when the entry listed at pos carried the new entry's id.
 //
+// TAGS: row r is ADMITTED for query q iff (tags[r] & qmask[q]) != 0, and only admitted rows pass the push test.  Nothing else changes:
+// the list then holds admitted rows only, so its k-th entry is the k-th ADMITTED row — k admitted rows at least that good exist — and
+// stays a valid threshold for the admitted sub-gallery; the same holds for a seed list computed with the same masks (a seed list with
+// fewer than k admitted rows has an empty k-th slot and gives no threshold).  A score does not depend on the tags: same K loop, same
+// operand placement.  The 64 masks of the query tile sit in LDS for the whole run (queries behind Q: mask 0), the 128 tags of a row
+// tile beside them for the tile (rows behind G: tag 0).  U = the OR of the workgroup's masks lives in an SGPR; a tile whose tile_or has
+// no bit of U holds no admitted row for any of the 64 queries and is skipped before any of its loads or barriers is issued.  So that
+// the tiles left over spread evenly, a TAGS workgroup walks the row tiles strided by the number of parts (see the tile loop).
+//
 // T: element type of rows and queries (float | _Float16); KD: list depth; KFIX: k is KD (else the runtime p.k <= KD).
-template <typename T, int KD, bool KFIX, bool IDS>
+template <typename T, int KD, bool KFIX, bool IDS, bool TAGS = false>
 __device__ __forceinline__ void gallery_scan_body(const GalArgs& p) {
     constexpr bool F16 = std::is_same<T, _Float16>::value;
     constexpr int BM = GAL_BM, BN = GAL_BN, TN = BN / 32;
@@ -120,6 +135,8 @@ __device__ __forceinline__ void gallery_scan_body(const GalArgs& p) {
     __shared__ int que_d[IDS ? BN : 1][GAL_QCAP];
     __shared__ int cnt[BN];
     __shared__ int overflow;
+    __shared__ unsigned mask_s[TAGS ? BN : 1];
+    __shared__ __attribute__((aligned(16))) unsigned tag_s[TAGS ? BM : 4];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int fr = lane & 31, fh2 = lane >> 5;
@@ -154,6 +171,15 @@ __device__ __forceinline__ void gallery_scan_body(const GalArgs& p) {
         cnt[tid] = 0; tau_s[tid] = ts; tau_i[tid] = ti;
     }
     if (tid == 0) overflow = 0;
+    unsigned U = 0;                                           // TAGS: OR of the tile's 64 masks (every wave forms it: no barrier needed)
+    int n_scan = 0, n_skip = 0;
+    if constexpr (TAGS) {
+        unsigned m = n0 + lane < p.Q ? p.qmask[n0 + lane] : 0u;
+        if (tid < BN) mask_s[tid] = m;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) m |= (unsigned)__shfl_xor((int)m, o);
+        U = (unsigned)__builtin_amdgcn_readfirstlane((int)m);
+    }
 
     // query loader: pass i fills rows i*16 + (tid >> 4), slot tid & 15 <- source 16-byte column (tid & 15) ^ (row & 15)
     const int qrow = tid >> 4;
@@ -163,8 +189,19 @@ __device__ __forceinline__ void gallery_scan_body(const GalArgs& p) {
     const size_t q16 = (size_t)16 * K;
     const int fsw = fr & 15;
 
-    for (int rt = rt0; rt < rt1; ++rt) {
+    // TAGS: part p walks the tiles p, p + parts, p + 2 parts, ... instead of a contiguous run — enrolments grouped by tag are long
+    // contiguous blocks, and with contiguous runs the few workgroups that own an admitted block would multiply all of their tiles
+    // while the others skip all of theirs: the call would take as long as a full scan.  Strided, every workgroup owns its share of
+    // every block.  (The part lists are merged whatever rows they cover.)
+    const int rt_first = TAGS ? part : rt0, rt_last = TAGS ? p.row_tiles : rt1, rt_step = TAGS ? (int)gridDim.x / p.tiles_n : 1;
+    for (int rt = rt_first; rt < rt_last; rt += rt_step) {
         const long m0 = (long)rt * BM;
+        unsigned my_tag = 0;
+        if constexpr (TAGS) {
+            if (p.tag_skip && (p.tile_or[rt] & U) == 0) { ++n_skip; continue; }      // (workgroup-uniform: rt and U are scalars)
+            ++n_scan;
+            if (tid < BM && m0 + tid < p.G) my_tag = p.tags[m0 + tid];
+        }
         const long myrow = m0 + wid * 32 + fr;
         const bool live = myrow < p.G;
         const T* a_ptr = (live ? gal + (size_t)myrow * K : zeros) + fh2 * EC;          // dead rows read the zero line (and are masked below)
@@ -220,6 +257,9 @@ __device__ __forceinline__ void gallery_scan_body(const GalArgs& p) {
             for (int i = 0; i < 4; ++i) ldsq[buf][i * 256 + tid] = qv[i];
         };
         __syncthreads();                                   // previous tile's epilogue is done with the LDS lists / queues
+        if constexpr (TAGS) {
+            if (tid < BM) tag_s[tid] = my_tag;             // (read behind the K loop's barriers)
+        }
         fetch_q();
         load_a(xa[0]);
         store_q(0);
@@ -249,13 +289,21 @@ __device__ __forceinline__ void gallery_scan_body(const GalArgs& p) {
                 const int qi = j * 32 + fr;
                 const float ts = tau_s[qi];
                 const int ti = tau_i[qi];
+                unsigned mq = 0;
+                if constexpr (TAGS) mq = mask_s[qi];
 #pragma unroll
                 for (int e = 0; e < 16; ++e) {
                     if ((e >> 2) < g_lo || (e >> 2) >= g_hi) continue;
                     const long row = rbase + 8 * (e >> 2) + (e & 3);
                     const float sc = (acc[j][e] + 1.0f) / 2.0f;
                     const int gi = (int)(p.idx_base + row);
-                    if (row < p.G && !gal_better(ts, ti, sc, gi)) {          // at least as good as the threshold entry (which may be this very row)
+                    bool admitted = true;
+                    if constexpr (TAGS) {                  // a lane's rows are four runs of four: one 16-byte LDS read per run, two addresses per wave
+                        const uint4 tg = *reinterpret_cast<const uint4*>(&tag_s[wid * 32 + 4 * fh2 + 8 * (e >> 2)]);
+                        const unsigned tw = (e & 3) == 0 ? tg.x : (e & 3) == 1 ? tg.y : (e & 3) == 2 ? tg.z : tg.w;
+                        admitted = (tw & mq) != 0;
+                    }
+                    if (row < p.G && admitted && !gal_better(ts, ti, sc, gi)) {          // at least as good as the threshold entry (which may be this very row)
                         const int slot = atomicAdd(&cnt[qi], 1);
                         if (slot < GAL_QCAP) {
                             que_s[qi][slot] = sc; que_i[qi][slot] = gi;
@@ -334,6 +382,12 @@ __device__ __forceinline__ void gallery_scan_body(const GalArgs& p) {
                 p.ps[o + pos] = li[pos] == INT_MAX ? -1.0f : ls[pos]; p.pi[o + pos] = li[pos] == INT_MAX ? -1 : li[pos];
                 if constexpr (IDS) p.pd[o + pos] = li[pos] == INT_MAX ? -1 : ld[pos];
             }
+    }
+    if constexpr (TAGS) {
+        if (tid == 0) {
+            atomicAdd(&p.tag_ctr[0], (unsigned long long)n_scan);
+            atomicAdd(&p.tag_ctr[1], (unsigned long long)n_skip);
+        }
     }
 }
 

@@ -359,6 +359,24 @@ void launch_ids_of_rows(const float* score, const int* idx, int n, const int* id
 void launch_gather_rows(const void* src, void* dst, const int* map, long m, size_t row_bytes, hipStream_t s);
 void launch_gather_ids(const int* src, int* dst, const int* map, long m, hipStream_t s);
 
+// gallery_tags.hip — watchlists: a 32-bit tag per row, a 32-bit mask per query, row r admitted for query q iff (tags[r] & qmask[q]) != 0;
+// the answer is the exact top-k of the query's admitted rows (ids == nullptr) or of their identities (part_id / seed_id then as
+// launch_gallery_topk_ids), global indices kept.  Same streaming scan, same part / seed planes, same merges.  tile_or[t] = OR of the tags
+// of rows [128 t, 128 t + 128) by position; tag_ctr [2] (device) counts the (workgroup, tile) visits multiplied / skipped.
+void launch_gallery_topk_tagged(const float* gal, const int* ids, const unsigned* tags, const unsigned* tile_or, long G, int dim,
+                                const float* qpacked, const unsigned* qmask, int Q, int k, long idx_base, float* part_score, int* part_idx,
+                                int* part_id, float* seed_score, int* seed_idx, int* seed_id, unsigned long long* tag_ctr, hipStream_t s);
+constexpr int GAL_TAG_TILE = 128;                            // rows per tile_or entry = the scan's row tile
+void gallery_debug_tag_skip(int on);                         // 0: tagged scans multiply every tile (same answer)
+// rebuilds tile_or for the tiles that rows [first, first + n) of a gallery of G rows touch
+void launch_tag_tile_or(const unsigned* tags, long G, long first, long n, unsigned* tile_or, hipStream_t s);
+// dst_tags[j] = OR of src_tags[order[i]], starts[j] <= i < starts[j + 1] (the inverted index of fh_gallery_group_ids), j < m
+void launch_fuse_tags(const unsigned* src_tags, const int* order, const long long* starts, long m, unsigned* dst_tags, hipStream_t s);
+// qmask[j] = stream_mask[stream of the frame that query j belongs to] for the `total` queries of a Tracker::identify_dev
+// (order / starts: the stream plan of track_plan.h on the device; frame_off [n + 1]: the frames' first queries)
+void launch_track_query_masks(const unsigned* stream_mask, int streams, const int* order, const int* starts, const int* frame_off, int n,
+                              int total, unsigned* qmask, hipStream_t s);
+
 // gallery_fuse.hip — template pooling (fh_gallery_fuse_ids): one wave per work item sums the rows src[order[begin + i]], i < count,
 // strictly in that order (p = row0; p = p + row1; ...), into row `out` of dst (final != 0; L2-normalised when `unit` and count > 1: a
 // one-row list is copied verbatim) or of the scratch `part` (final == 0: a chunk's partial sum, never normalised).  order == nullptr:

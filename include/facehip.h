@@ -730,6 +730,58 @@ FH_API int fh_hist_bin(float score);
 FH_API int fh_roc_from_hist(const unsigned long long* hist, double max_far, fh_roc_point out[2]);
 FH_API int fh_gallery_pair_hist_dev(fh_gallery* g, unsigned long long* d_hist, unsigned long long* d_nan, void* stream);
 
+/* ---- watchlists: row tags and tag-filtered exact 1:N search.  One gallery serves several tenants, doors or lists: every row carries a
+ * uint32 TAG (a bit set of up to 32 caller-defined groups), every query a uint32 MASK, and row r is ADMITTED for query q iff
+ * (tag[r] & mask[q]) != 0.  The predicate sits inside the scan's admission test, so a tagged query is answered from its admitted rows
+ * alone — asking for the top 16 and filtering afterwards is wrong as soon as more than 16 excluded rows outrank the first admitted one.
+ *   tags      a gallery whose tags were never set behaves as if every row carried FH_TAG_ALL.  Rows added by fh_gallery_enroll* get
+ *             FH_TAG_ALL; fh_gallery_upload* replaces everything and resets all tags to FH_TAG_ALL.  fh_gallery_remove_ids moves the
+ *             tags with the rows, in the same stable compaction.  fh_gallery_fuse_ids gives dst row j the OR of the tags of identity
+ *             j's rows (a src whose tags were never set leaves dst without tags).  fh_gallery_set_ids, clustering and the pair
+ *             histogram ignore tags.  Memory: 4 bytes per row of capacity and 4 bytes per 128 rows, from the first set_tags or tagged
+ *             query on.
+ *   set_tags  the tags of rows [first, first + n) by position (tags[n], host or device); synchronous, like fh_gallery_set_ids, and like
+ *             it waits for the handle's queued work; labelled and unlabelled galleries alike; argument and range checks as
+ *             fh_gallery_get_ids (FH_ERR_ARG, nothing changes); returns n.
+ *   get_tags  the twin of fh_gallery_get_ids: the tags of rows [first, first + n) into tags_host_out; returns n.
+ *   queries   d_masks = device [nq] uint32, read on the device when the call runs (a replayed graph sees the buffer's current contents).
+ *             The answer of query q is EXACTLY — scores, indices, ids, rows, bit for bit — the answer the untagged call of the same
+ *             name gives on the gallery made of q's admitted rows only, with every listed row keeping its global index in the full
+ *             gallery (index_base + position): score bits are the fp32 scan's (a row's score does not depend on its position or its
+ *             neighbours), entry order is (score desc, global index asc), NaN is never listed, empty slots are (-1.0f, -1[, -1]); in the
+ *             identity forms an identity is represented by its best ADMITTED row.  Mask 0 admits nothing: all slots empty, the label
+ *             forms answer (-1, -1.0f) as for an empty gallery.  Limits as fh_gallery_topk_dev (1 <= k <= 16, nq <= 256, dim % 64 == 0);
+ *             asynchronous on `stream`, capturable into a graph after one call of the same (nq, k).  Labelled / unlabelled state errors
+ *             are those of the untagged twins; a NULL mask pointer returns FH_ERR_ARG.  Tagged queries ALWAYS run the fp32 scan,
+ *             whatever the scan mode (the 32 unfiltered fp16 candidates of F16_RERANK certify nothing about a subset — the precedent of
+ *             topk_ids with k > 1); fh_gallery_scan_stats counts them as fall-backs.
+ *   skipping  the handle keeps the OR of the tags of every 128-row tile, by position; a workgroup of the scan (64 queries) passes over a
+ *             tile that has no bit in common with the OR of its 64 masks without reading it, so a selective query against enrolments
+ *             GROUPED by tag reads a fraction of the gallery, while scattered tags read all of it.  The answer does not depend on it.
+ *   tag_stats waits for the handle's queued work; the (workgroup, row tile) visits that tagged scans multiplied / skipped since the last
+ *             call of this function, which resets both; the seed passes of large galleries are included.
+ *   sharding  there is no sharded tagged entry point; fh_topk_merge_dev and fh_topk_merge_ids_dev merge per-shard tagged lists unchanged
+ *             (a tagged list is a top-k list of a sub-gallery, and the merge never looks at tags).
+ *   tracker   fh_tracker_set_stream_masks: masks_host[streams], one watchlist per camera; NULL switches the masks off (the default);
+ *             synchronous, the masks are copied to the device.  With masks set, stage B of fh_track_identify_dev (and of the _q, _link
+ *             and fh_pipeline_run_identified_dev forms) labels every query — those of untracked faces too — through
+ *             fh_gallery_label_ids_tagged_dev / fh_gallery_label_tagged_dev with the mask of the stream its frame belongs to.  Stages A
+ *             and C, re-linking and pooling are untouched; with masks off the call issues no extra launch and every output is bit for
+ *             bit what it was. */
+#define FH_TAG_ALL 0xFFFFFFFFu
+FH_API long long fh_gallery_set_tags(fh_gallery* g, long long first, long long n, const uint32_t* tags, int on_device);
+FH_API long long fh_gallery_get_tags(fh_gallery* g, long long first, long long n, uint32_t* tags_host_out);
+FH_API int fh_gallery_topk_tagged_dev(fh_gallery* g, const float* d_queries, const uint32_t* d_masks, int nq, int k, float* d_scores,
+                                      int* d_indices, void* stream);
+FH_API int fh_gallery_topk_ids_tagged_dev(fh_gallery* g, const float* d_queries, const uint32_t* d_masks, int nq, int k, float* d_scores,
+                                          int* d_ids, int* d_rows, void* stream);
+FH_API int fh_gallery_label_tagged_dev(fh_gallery* g, const float* d_queries, const uint32_t* d_masks, int nq, float threshold,
+                                       int* d_labels, float* d_scores, void* stream);
+FH_API int fh_gallery_label_ids_tagged_dev(fh_gallery* g, const float* d_queries, const uint32_t* d_masks, int nq, float threshold,
+                                           int* d_ids_out, float* d_scores, void* stream);
+FH_API int fh_gallery_tag_stats(fh_gallery* g, long long* tiles_scanned, long long* tiles_skipped);
+FH_API int fh_tracker_set_stream_masks(fh_tracker* t, const uint32_t* masks_host /*[streams] or NULL*/);
+
 /* ---- measurement hooks (bench.py): per-launch HIP-event timing of the network kernels.
  * Tags 0..3 = conv_igemm tile configs (128x128, 256x64, 128x32, 64x64), 4 = depthwise / depthwise+pointwise,
  * 5 = other graph ops, 6 = conv stream-K fix-up, 7 = Winograd GEMM (its FLOPs = executed; bytes slot = the layer's
@@ -844,6 +896,9 @@ FH_API int fh_debug_cluster_tiles(int tiles_per_wg);
 /* Measurement hook of fh_gallery_pair_hist_dev: the number of privatised histogram copies its workgroups flush into (1..4096; 0 restores
  * the default, 1).  The result does not depend on it (scripts/gallery_hist_ab.py --copies). */
 FH_API int fh_debug_hist_copies(int copies);
+/* Test / measurement hook of the tagged scans (gallery_tags.hip): 0 = every tile is multiplied, none is skipped; non-zero (the default)
+ * = tiles without an admitted row for any of a workgroup's queries are skipped.  The answer is the same bits either way. */
+FH_API int fh_debug_tag_skip(int on);
 /* Test hook of the split-bf16 operand format (winograd.hip wino_pack_bf16x2): n f32 words -> n packed words, hi = bf16(x) in the low half,
  * mid = bf16(x - hi) in the high half, both round-to-nearest-even.  n % 4 == 0.  Synchronous. */
 FH_API int fh_debug_pack_bf16x2_dev(const float* d_in, float* d_out, long long n);
