@@ -1251,11 +1251,11 @@ long long fh_gallery_enroll(fh_gallery* g, const float* rows, long long n, int o
 long long fh_gallery_size(fh_gallery* g) { return g ? (long long)g->g.size() : (long long)arg_error("fh_gallery_size: null handle"); }
 int fh_gallery_label_dev(fh_gallery* g, const float* q, int nq, float threshold, int* labels, float* scores, void* stream) {
     if (!g || !q || !labels || !scores) return arg_error("fh_gallery_label_dev: null argument");
-    return guarded([&] { g->g.label_dev(q, nq, threshold, labels, scores, S(stream)); return nq; });
+    return guarded([&] { g->g.label_dev(q, nullptr, nq, threshold, false, labels, scores, S(stream)); return nq; });
 }
 int fh_gallery_topk_dev(fh_gallery* g, const float* q, int nq, int k, float* scores, int* indices, void* stream) {
     if (!g || !q || !scores || !indices) return arg_error("fh_gallery_topk_dev: null argument");
-    return guarded([&] { g->g.topk_dev(q, nq, k, scores, indices, S(stream)); return nq; });
+    return guarded([&] { g->g.topk_dev(q, nullptr, nq, k, false, scores, nullptr, indices, S(stream)); return nq; });
 }
 
 int fh_gallery_set_scan(fh_gallery* g, int mode) {
@@ -1310,12 +1310,12 @@ int fh_gallery_upload_ids(fh_gallery* g, const float* rows, const int* ids, long
 int fh_gallery_topk_ids_dev(fh_gallery* g, const float* q, int nq, int k, float* scores, int* ids, int* rows, void* stream) {
     if (!g || !q || !scores || !ids) return arg_error("fh_gallery_topk_ids_dev: null argument");
     if (nq <= 0 || nq > 256 || k <= 0 || k > 16) return arg_error("fh_gallery_topk_ids_dev: need 0 < nq <= 256 and 0 < k <= 16");
-    return guarded([&] { g->g.topk_ids_dev(q, nq, k, scores, ids, rows, S(stream)); return nq; });
+    return guarded([&] { g->g.topk_dev(q, nullptr, nq, k, true, scores, ids, rows, S(stream)); return nq; });
 }
 int fh_gallery_label_ids_dev(fh_gallery* g, const float* q, int nq, float threshold, int* ids, float* scores, void* stream) {
     if (!g || !q || !ids || !scores) return arg_error("fh_gallery_label_ids_dev: null argument");
     if (nq <= 0 || nq > 256) return arg_error("fh_gallery_label_ids_dev: need 0 < nq <= 256");
-    return guarded([&] { g->g.label_ids_dev(q, nq, threshold, ids, scores, S(stream)); return nq; });
+    return guarded([&] { g->g.label_dev(q, nullptr, nq, threshold, true, ids, scores, S(stream)); return nq; });
 }
 long long fh_gallery_remove_ids(fh_gallery* g, const int* ids_host, long long n_ids) {
     if (!g || !ids_host || n_ids <= 0) return arg_error("fh_gallery_remove_ids: bad argument");
@@ -1346,24 +1346,24 @@ long long fh_gallery_get_tags(fh_gallery* g, long long first, long long n, uint3
 }
 int fh_gallery_topk_tagged_dev(fh_gallery* g, const float* q, const uint32_t* masks, int nq, int k, float* scores, int* indices, void* stream) {
     if (!g || !q || !masks || !scores || !indices) return arg_error("fh_gallery_topk_tagged_dev: null argument");
-    return guarded([&] { g->g.topk_tagged_dev(q, masks, nq, k, scores, indices, S(stream)); return nq; });
+    return guarded([&] { g->g.topk_dev(q, masks, nq, k, false, scores, nullptr, indices, S(stream)); return nq; });
 }
 int fh_gallery_topk_ids_tagged_dev(fh_gallery* g, const float* q, const uint32_t* masks, int nq, int k, float* scores, int* ids, int* rows,
                                    void* stream) {
     if (!g || !q || !masks || !scores || !ids) return arg_error("fh_gallery_topk_ids_tagged_dev: null argument");
     if (nq <= 0 || nq > 256 || k <= 0 || k > 16) return arg_error("fh_gallery_topk_ids_tagged_dev: need 0 < nq <= 256 and 0 < k <= 16");
-    return guarded([&] { g->g.topk_ids_tagged_dev(q, masks, nq, k, scores, ids, rows, S(stream)); return nq; });
+    return guarded([&] { g->g.topk_dev(q, masks, nq, k, true, scores, ids, rows, S(stream)); return nq; });
 }
 int fh_gallery_label_tagged_dev(fh_gallery* g, const float* q, const uint32_t* masks, int nq, float threshold, int* labels, float* scores,
                                 void* stream) {
     if (!g || !q || !masks || !labels || !scores) return arg_error("fh_gallery_label_tagged_dev: null argument");
-    return guarded([&] { g->g.label_tagged_dev(q, masks, nq, threshold, labels, scores, S(stream)); return nq; });
+    return guarded([&] { g->g.label_dev(q, masks, nq, threshold, false, labels, scores, S(stream)); return nq; });
 }
 int fh_gallery_label_ids_tagged_dev(fh_gallery* g, const float* q, const uint32_t* masks, int nq, float threshold, int* ids, float* scores,
                                     void* stream) {
     if (!g || !q || !masks || !ids || !scores) return arg_error("fh_gallery_label_ids_tagged_dev: null argument");
     if (nq <= 0 || nq > 256) return arg_error("fh_gallery_label_ids_tagged_dev: need 0 < nq <= 256");
-    return guarded([&] { g->g.label_ids_tagged_dev(q, masks, nq, threshold, ids, scores, S(stream)); return nq; });
+    return guarded([&] { g->g.label_dev(q, masks, nq, threshold, true, ids, scores, S(stream)); return nq; });
 }
 int fh_gallery_tag_stats(fh_gallery* g, long long* tiles_scanned, long long* tiles_skipped) {
     if (!g) return arg_error("fh_gallery_tag_stats: null handle");

@@ -155,7 +155,7 @@ int fh_gallery_topk_sharded_dev(fh_gallery* g, fh_comm* c, const float* d_q, int
         int* li = reinterpret_cast<int*>(ls + plane);
         for (int q0 = 0; q0 < Q; q0 += 256) {
             const int n = std::min(256, Q - q0);
-            gal.topk_dev(c->qall.as<float>() + (size_t)q0 * dim, n, k, ls + (size_t)q0 * k, li + (size_t)q0 * k, s);
+            gal.topk_dev(c->qall.as<float>() + (size_t)q0 * dim, nullptr, n, k, false, ls + (size_t)q0 * k, nullptr, li + (size_t)q0 * k, s);
         }
         // (3) ONE collective for both planes (indices travel as raw 32-bit words), rank-major
         fh::nccl_check(fh::rccl().AllGather(c->planes.p, c->gathered.p, 2 * plane, ncclFloat, c->comm, s), "ncclAllGather(top-k)");

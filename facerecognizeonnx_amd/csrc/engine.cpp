@@ -948,505 +948,6 @@ void Recognizer::resize_embed_dev(const uint8_t* frames, int n, int rows, int co
     embed_aligned_dev(crops_.as<uint8_t>(), n, out, s);
 }
 
-// ------------------------------------------------------------------------------------------ Gallery
-void Gallery::upload(const float* rows, const int* ids, long n, bool device_src, long index_base) {
-    if (dim_ % 64) throw std::runtime_error("gallery: dim must be a multiple of 64");
-    if (!ids && n_ > 0 && labelled_) throw std::runtime_error("gallery: the gallery is labelled: upload rows with their ids (fh_gallery_upload_ids)");
-    rows_.ensure((size_t)n * dim_ * sizeof(float));
-    if (ids) ids_.ensure(rows_.bytes / ((size_t)dim_ * sizeof(float)) * sizeof(int));
-    FH_HIP(hipMemcpy(rows_.p, rows, (size_t)n * dim_ * sizeof(float), device_src ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
-    if (ids) FH_HIP(hipMemcpy(ids_.p, ids, (size_t)n * sizeof(int), device_src ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
-    n_ = n; base_ = index_base; labelled_ = ids != nullptr; fused_ = false;
-    has_tags_ = false;                                           // a new row set: every row admitted everywhere until set_tags
-    if (scan_ == 1) {
-        rows16_.ensure((size_t)n * dim_ * sizeof(uint16_t));
-        convert16(0, n);
-    }
-}
-
-void Gallery::convert16(long first, long n) {
-    gstat_.ensure(4 * sizeof(unsigned));
-    if (first == 0) FH_HIP(hipMemset(gstat_.p, 0, 4 * sizeof(unsigned)));      // a new row set: fresh bounds (enroll keeps the maxima)
-    launch_gallery16_convert(rows_.as<float>() + (size_t)first * dim_, rows16_.as<uint16_t>() + (size_t)first * dim_, n, dim_,
-                             gstat_.as<unsigned>(), nullptr);
-    FH_HIP(hipGetLastError());
-    unsigned h[4];
-    FH_HIP(hipMemcpy(h, gstat_.p, sizeof(h), hipMemcpyDeviceToHost));
-    for (int i = 0; i < 3; ++i) memcpy(&gbound_[i], &h[i], sizeof(float));
-    f16_bad_ = h[3] != 0;
-}
-
-void Gallery::set_scan(int mode) {
-    if (mode != 0 && mode != 1) throw std::invalid_argument("gallery: unknown scan mode");
-    if (mode == 0) {
-        DevBuf none;
-        std::swap(none.p, rows16_.p);
-        std::swap(none.bytes, rows16_.bytes);
-        scan_ = 0;
-        return;
-    }
-    if (scan_ != 1) {
-        ctr_.ensure(2 * sizeof(unsigned long long));
-        FH_HIP(hipMemset(ctr_.p, 0, 2 * sizeof(unsigned long long)));
-        if (n_ > 0) {
-            rows16_.ensure((size_t)n_ * dim_ * sizeof(uint16_t));
-            convert16(0, n_);
-        }
-        scan_ = 1;
-    }
-}
-
-void Gallery::scan_stats(long long* certified, long long* fallback) {
-    unsigned long long h[2] = {0, 0};
-    FH_HIP(hipDeviceSynchronize());
-    if (ctr_.p) {
-        FH_HIP(hipMemcpy(h, ctr_.p, sizeof(h), hipMemcpyDeviceToHost));
-        FH_HIP(hipMemset(ctr_.p, 0, sizeof(h)));
-    }
-    if (certified) *certified = (long long)h[0];
-    if (fallback) *fallback = (long long)h[1] + host_fallback_;
-    host_fallback_ = 0;
-}
-
-long Gallery::enroll(const float* rows, const int* ids, long n, bool device_src) {
-    if (dim_ % 64) throw std::runtime_error("gallery: dim must be a multiple of 64");
-    if (n_ > 0 && labelled_ != (ids != nullptr))
-        throw std::runtime_error(labelled_ ? "gallery: the gallery is labelled: enrol rows with their ids (fh_gallery_enroll_ids)"
-                                           : "gallery: the gallery is unlabelled: fh_gallery_enroll_ids needs an empty or labelled gallery");
-    const size_t row_bytes = (size_t)dim_ * sizeof(float);
-    const size_t need = (size_t)(n_ + n) * row_bytes;
-    if (need > rows_.bytes) {                                    // grow geometrically, keeping the enrolled rows
-        DevBuf bigger;
-        bigger.ensure(std::max(need, rows_.bytes * 2));
-        if (n_ > 0) FH_HIP(hipMemcpy(bigger.p, rows_.p, (size_t)n_ * row_bytes, hipMemcpyDeviceToDevice));
-        std::swap(bigger.p, rows_.p);
-        std::swap(bigger.bytes, rows_.bytes);
-    }
-    FH_HIP(hipMemcpy(static_cast<char*>(rows_.p) + (size_t)n_ * row_bytes, rows, (size_t)n * row_bytes,
-                     device_src ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
-    if (scan_ == 1) {                                            // the fp16 copy grows with the fp32 rows (same capacity in rows)
-        const size_t row16 = (size_t)dim_ * sizeof(uint16_t), cap16 = rows_.bytes / row_bytes * row16;
-        if (cap16 > rows16_.bytes) {
-            DevBuf bigger;
-            bigger.ensure(cap16);
-            if (n_ > 0) FH_HIP(hipMemcpy(bigger.p, rows16_.p, (size_t)n_ * row16, hipMemcpyDeviceToDevice));
-            std::swap(bigger.p, rows16_.p);
-            std::swap(bigger.bytes, rows16_.bytes);
-        }
-        convert16(n_, n);
-    }
-    if (ids) {                                                   // the ids grow with the rows too
-        const size_t cap = rows_.bytes / row_bytes * sizeof(int);
-        if (cap > ids_.bytes) {
-            DevBuf bigger;
-            bigger.ensure(cap);
-            if (n_ > 0) FH_HIP(hipMemcpy(bigger.p, ids_.p, (size_t)n_ * sizeof(int), hipMemcpyDeviceToDevice));
-            std::swap(bigger.p, ids_.p);
-            std::swap(bigger.bytes, ids_.bytes);
-        }
-        FH_HIP(hipMemcpy(ids_.as<int>() + n_, ids, (size_t)n * sizeof(int), device_src ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
-    }
-    if (n_ == 0) labelled_ = ids != nullptr;
-    fused_ = false;                                              // appended ids are neither distinct nor in order
-    const long first = base_ + n_;
-    if (has_tags_) {                                             // the tags grow with the rows; the new rows are admitted everywhere
-        need_tags();
-        FH_HIP(hipMemset(tags_.as<unsigned>() + n_, 0xFF, (size_t)n * sizeof(unsigned)));
-        launch_tag_tile_or(tags_.as<unsigned>(), n_ + n, n_, n, tile_or_.as<unsigned>(), nullptr);
-        FH_HIP(hipGetLastError());
-        FH_HIP(hipDeviceSynchronize());
-    }
-    n_ += n;
-    return first;
-}
-
-// Tags.  The buffers follow the rows' capacity (as the ids do), so enroll appends in place; tile_or is rebuilt by position for the tiles
-// a change touches (set_tags: its range; enroll: from the old last tile on; remove_ids and fuse: all of them).
-void Gallery::need_tags() {
-    const size_t cap = rows_.bytes / ((size_t)dim_ * sizeof(float)), tiles = (cap + GAL_TAG_TILE - 1) / GAL_TAG_TILE;
-    const size_t have = has_tags_ ? (size_t)n_ : 0;
-    if (cap * sizeof(unsigned) > tags_.bytes) {
-        DevBuf bigger;
-        bigger.ensure(cap * sizeof(unsigned));
-        if (have > 0) FH_HIP(hipMemcpy(bigger.p, tags_.p, have * sizeof(unsigned), hipMemcpyDeviceToDevice));
-        std::swap(bigger.p, tags_.p);
-        std::swap(bigger.bytes, tags_.bytes);
-    }
-    if (tiles * sizeof(unsigned) > tile_or_.bytes) {
-        DevBuf bigger;
-        bigger.ensure(tiles * sizeof(unsigned));
-        if (have > 0) FH_HIP(hipMemcpy(bigger.p, tile_or_.p, (have + GAL_TAG_TILE - 1) / GAL_TAG_TILE * sizeof(unsigned), hipMemcpyDeviceToDevice));
-        std::swap(bigger.p, tile_or_.p);
-        std::swap(bigger.bytes, tile_or_.bytes);
-    }
-    if (!tag_ctr_.p) {
-        tag_ctr_.ensure(2 * sizeof(unsigned long long));
-        FH_HIP(hipMemset(tag_ctr_.p, 0, 2 * sizeof(unsigned long long)));
-    }
-    if (!has_tags_) {
-        if (n_ > 0) {
-            FH_HIP(hipDeviceSynchronize());                      // a queued tagged scan of an earlier row set may still read the buffers
-            FH_HIP(hipMemset(tags_.p, 0xFF, (size_t)n_ * sizeof(unsigned)));
-            launch_tag_tile_or(tags_.as<unsigned>(), n_, 0, n_, tile_or_.as<unsigned>(), nullptr);
-            FH_HIP(hipGetLastError());
-            FH_HIP(hipDeviceSynchronize());
-        }
-        has_tags_ = true;
-    }
-}
-
-void Gallery::set_tags(long first, long n, const unsigned* tags, bool device_src) {
-    if (first < 0 || n < 0 || first + n > n_) throw std::invalid_argument("gallery: tag range outside the gallery");
-    if (n == 0) return;
-    FH_HIP(hipDeviceSynchronize());                              // queued scans still read the tags that are about to change
-    need_tags();
-    FH_HIP(hipMemcpy(tags_.as<unsigned>() + first, tags, (size_t)n * sizeof(unsigned), device_src ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
-    launch_tag_tile_or(tags_.as<unsigned>(), n_, first, n, tile_or_.as<unsigned>(), nullptr);
-    FH_HIP(hipGetLastError());
-    FH_HIP(hipDeviceSynchronize());
-}
-
-void Gallery::get_tags(long first, long n, unsigned* out_host) {
-    if (first < 0 || n < 0 || first + n > n_) throw std::invalid_argument("gallery: tag range outside the gallery");
-    if (n == 0) return;
-    if (!has_tags_) { std::fill(out_host, out_host + n, 0xFFFFFFFFu); return; }
-    FH_HIP(hipDeviceSynchronize());
-    FH_HIP(hipMemcpy(out_host, tags_.as<unsigned>() + first, (size_t)n * sizeof(unsigned), hipMemcpyDeviceToHost));
-}
-
-void Gallery::tag_stats(long long* scanned, long long* skipped) {
-    unsigned long long h[2] = {0, 0};
-    FH_HIP(hipDeviceSynchronize());
-    if (tag_ctr_.p) {
-        FH_HIP(hipMemcpy(h, tag_ctr_.p, sizeof(h), hipMemcpyDeviceToHost));
-        FH_HIP(hipMemset(tag_ctr_.p, 0, sizeof(h)));
-    }
-    if (scanned) *scanned = (long long)h[0];
-    if (skipped) *skipped = (long long)h[1];
-}
-
-// A tagged query is always the fp32 scan: the 32 unfiltered fp16 candidates of F16_RERANK certify nothing about a subset of the rows.
-void Gallery::scan_tagged(const float* q, const unsigned* masks, int Q, int k, bool ids, float* out_score, int* out_id, int* out_row,
-                          hipStream_t s) {
-    if (Q <= 0 || Q > 256 || k <= 0 || k > 16) throw std::runtime_error("gallery: need 0 < Q <= 256 and 0 < k <= 16");
-    if (dim_ % 64) throw std::runtime_error("gallery: dim must be a multiple of 64");
-    if (scan_ == 1) host_fallback_ += Q;
-    if (n_ > 0) need_tags();
-    pack_queries(q, Q, s);
-    const int parts = size_lists(Q, k, ids);
-    launch_gallery_topk_tagged(rows_.as<float>(), ids ? ids_.as<int>() : nullptr, tags_.as<unsigned>(), tile_or_.as<unsigned>(), n_, dim_,
-                               qpack_.as<float>(), masks, Q, k, base_, ps_.as<float>(), pi_.as<int>(), pd_.as<int>(), seed_s_.as<float>(),
-                               seed_i_.as<int>(), seed_d_.as<int>(), tag_ctr_.as<unsigned long long>(), s);
-    if (ids) launch_topk_merge_ids(ps_.as<float>(), pd_.as<int>(), pi_.as<int>(), parts, Q, k, out_score, out_id, out_row, s);
-    else launch_topk_merge(ps_.as<float>(), pi_.as<int>(), parts, Q, k, out_score, out_row, s);
-    FH_HIP(hipGetLastError());
-}
-
-void Gallery::topk_tagged_dev(const float* q, const unsigned* masks, int Q, int k, float* out_score, int* out_idx, hipStream_t s) {
-    scan_tagged(q, masks, Q, k, false, out_score, nullptr, out_idx, s);
-}
-
-void Gallery::topk_ids_tagged_dev(const float* q, const unsigned* masks, int Q, int k, float* out_score, int* out_id, int* out_row,
-                                  hipStream_t s) {
-    need_labelled("fh_gallery_topk_ids_tagged_dev");
-    scan_tagged(q, masks, Q, k, true, out_score, out_id, out_row, s);
-}
-
-void Gallery::label_tagged_dev(const float* q, const unsigned* masks, int Q, float thr, int* out_label, float* out_score, hipStream_t s) {
-    best_i_.ensure((size_t)std::max(Q, 1) * sizeof(int));
-    scan_tagged(q, masks, Q, 1, false, out_score, nullptr, best_i_.as<int>(), s);
-    launch_label(out_score, best_i_.as<int>(), Q, thr, out_label, s);
-}
-
-void Gallery::label_ids_tagged_dev(const float* q, const unsigned* masks, int Q, float thr, int* out_id, float* out_score, hipStream_t s) {
-    need_labelled("fh_gallery_label_ids_tagged_dev");
-    // the best admitted identity is the identity of the best admitted row
-    best_i_.ensure((size_t)std::max(Q, 1) * sizeof(int));
-    scan_tagged(q, masks, Q, 1, false, out_score, nullptr, best_i_.as<int>(), s);
-    launch_ids_of_rows(out_score, best_i_.as<int>(), Q, ids_.as<int>(), base_, thr, true, out_id, s);
-    FH_HIP(hipGetLastError());
-}
-
-void Gallery::need_labelled(const char* what) const {
-    if (n_ > 0 && !labelled_) throw std::runtime_error(std::string("gallery: ") + what + " needs a labelled gallery (rows enrolled with ids)");
-}
-
-void Gallery::get_ids(long first, long n, int* out_host) {
-    need_labelled("fh_gallery_get_ids");
-    if (first < 0 || n < 0 || first + n > n_) throw std::invalid_argument("gallery: id range outside the gallery");
-    if (n > 0) FH_HIP(hipMemcpy(out_host, ids_.as<int>() + first, (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
-}
-
-void Gallery::get_rows(long first, long n, float* out_host) {
-    if (first < 0 || n < 0 || first + n > n_) throw std::invalid_argument("gallery: row range outside the gallery");
-    if (n > 0) FH_HIP(hipMemcpy(out_host, rows_.as<float>() + (size_t)first * dim_, (size_t)n * dim_ * sizeof(float), hipMemcpyDeviceToHost));
-}
-
-// Template pooling.  The host reads src's ids (as remove_ids does), groups them (group_ids.h: the one definition of the grouping) and
-// turns the groups into work items of at most `chunk` rows: an identity of one chunk is summed straight into its row, a longer one
-// chunk by chunk into scratch partials that a second launch adds in chunk order (gallery_fuse.hip).  Everything is computed before a
-// member of this gallery changes, except that its buffers may have grown.
-long Gallery::fuse_from(Gallery& src, bool unit, int chunk) {
-    if (dim_ % 64) throw std::runtime_error("gallery: dim must be a multiple of 64");
-    if (src.n_ == 0) {                                           // nothing to read, nothing to launch: the capacity stays
-        n_ = 0; base_ = 0; fused_ = true; has_tags_ = false;
-        return 0;
-    }
-    FH_HIP(hipDeviceSynchronize());                              // queued scans of either handle still read what is about to change
-    const long n = src.n_;
-    std::vector<int> ids((size_t)n), order((size_t)n), uniq((size_t)n);
-    std::vector<long long> starts((size_t)n + 1);
-    FH_HIP(hipMemcpy(ids.data(), src.ids_.p, (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
-    const long m = (long)group_ids(ids.data(), n, order.data(), starts.data(), uniq.data());
-    if (m <= 0) throw std::runtime_error("gallery: the gallery's ids cannot be grouped (a negative id, or more rows than an int counts)");
-    std::vector<FuseItem> items, finish;
-    items.reserve((size_t)m);
-    int parts = 0;
-    for (long j = 0; j < m; ++j) {
-        const long b = (long)starts[(size_t)j], cnt = (long)starts[(size_t)j + 1] - b;
-        if (cnt <= chunk) { items.push_back({(int)b, (int)cnt, (int)j, 1}); continue; }
-        const int first = parts;
-        for (long c = 0; c < cnt; c += chunk) items.push_back({(int)(b + c), (int)std::min<long>(chunk, cnt - c), parts++, 0});
-        finish.push_back({first, parts - first, (int)j, 1});
-    }
-    const size_t row_bytes = (size_t)dim_ * sizeof(float), n1 = items.size(), n2 = finish.size();
-    items.insert(items.end(), finish.begin(), finish.end());
-    DevBuf d_order, d_items, d_part;
-    d_order.ensure((size_t)n * sizeof(int));
-    d_items.ensure(items.size() * sizeof(FuseItem));
-    if (parts > 0) d_part.ensure((size_t)parts * row_bytes);
-    FH_HIP(hipMemcpy(d_order.p, order.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice));
-    FH_HIP(hipMemcpy(d_items.p, items.data(), items.size() * sizeof(FuseItem), hipMemcpyHostToDevice));
-    rows_.ensure((size_t)m * row_bytes);
-    ids_.ensure(rows_.bytes / row_bytes * sizeof(int));          // the ids' capacity follows the rows', as upload keeps it
-    FH_HIP(hipMemcpy(ids_.p, uniq.data(), (size_t)m * sizeof(int), hipMemcpyHostToDevice));
-    launch_gallery_fuse_sum(src.rows_.as<float>(), d_order.as<int>(), d_items.as<FuseItem>(), (long)n1, dim_, rows_.as<float>(),
-                            d_part.as<float>(), unit, nullptr);
-    launch_gallery_fuse_sum(d_part.as<float>(), nullptr, d_items.as<FuseItem>() + n1, (long)n2, dim_, rows_.as<float>(), nullptr, unit, nullptr);
-    FH_HIP(hipGetLastError());
-    FH_HIP(hipDeviceSynchronize());
-    n_ = m; base_ = 0; labelled_ = true; fused_ = true;
-    has_tags_ = false;
-    if (src.has_tags_) {                                         // row j carries the OR of the tags of identity j's rows
-        DevBuf d_starts;
-        d_starts.ensure(((size_t)m + 1) * sizeof(long long));
-        FH_HIP(hipMemcpy(d_starts.p, starts.data(), ((size_t)m + 1) * sizeof(long long), hipMemcpyHostToDevice));
-        need_tags();                                             // (all ones first: one more pass over m words)
-        launch_fuse_tags(src.tags_.as<unsigned>(), d_order.as<int>(), d_starts.as<long long>(), m, tags_.as<unsigned>(), nullptr);
-        launch_tag_tile_or(tags_.as<unsigned>(), m, 0, m, tile_or_.as<unsigned>(), nullptr);
-        FH_HIP(hipGetLastError());
-        FH_HIP(hipDeviceSynchronize());
-    }
-    if (scan_ == 1) {
-        rows16_.ensure((size_t)m * dim_ * sizeof(uint16_t));
-        convert16(0, m);
-    }
-    return m;
-}
-
-void Gallery::self_scores_dev(const Gallery& tmpl, float* out, hipStream_t s) {
-    need_labelled("fh_gallery_self_scores_dev");
-    if (!tmpl.fused_)
-        throw std::runtime_error("gallery: fh_gallery_self_scores_dev needs a template gallery that fh_gallery_fuse_ids made (and no upload / enroll since)");
-    if (n_ == 0) return;
-    launch_gallery_self_scores(rows_.as<float>(), ids_.as<int>(), n_, tmpl.rows_.as<float>(), tmpl.ids_.as<int>(), tmpl.n_, dim_, out, s);
-    FH_HIP(hipGetLastError());
-}
-
-void Gallery::cluster_dev(float thr, int min_pts, bool noise_self, int* labels, int* info, hipStream_t s) {
-    if (dim_ % 64) throw std::runtime_error("gallery: dim must be a multiple of 64");
-    if (n_ == 0) {
-        if (info) FH_HIP(hipMemsetAsync(info, 0, 4 * sizeof(int), s));
-        return;
-    }
-    if (n_ > (long)INT_MAX) throw std::runtime_error("gallery: row positions must fit in 31 bits");
-    cl_deg_.ensure((size_t)n_ * sizeof(int));
-    cl_parent_.ensure((size_t)n_ * sizeof(int));
-    cl_best_.ensure((size_t)n_ * sizeof(unsigned long long));
-    launch_gallery_cluster(rows_.as<float>(), n_, dim_, thr, min_pts, noise_self, cl_deg_.as<int>(), cl_parent_.as<int>(),
-                           cl_best_.as<unsigned long long>(), labels, info, s);
-    FH_HIP(hipGetLastError());
-}
-
-void Gallery::pair_hist_dev(unsigned long long* hist, unsigned long long* nan, hipStream_t s) {
-    need_labelled("fh_gallery_pair_hist_dev");
-    if (dim_ % 64) throw std::runtime_error("gallery: dim must be a multiple of 64");
-    if (n_ == 0) {
-        FH_HIP(hipMemsetAsync(hist, 0, 2 * (size_t)kHistBins * sizeof(unsigned long long), s));
-        if (nan) FH_HIP(hipMemsetAsync(nan, 0, 2 * sizeof(unsigned long long), s));
-        return;
-    }
-    if (n_ > (long)INT_MAX) throw std::runtime_error("gallery: row positions must fit in 31 bits");
-    cl_hist_.ensure(gallery_pair_hist_scratch_bytes());
-    launch_gallery_pair_hist(rows_.as<float>(), ids_.as<int>(), n_, dim_, cl_hist_.as<unsigned long long>(), hist, nan, s);
-    FH_HIP(hipGetLastError());
-}
-
-void Gallery::set_ids(const int* ids, bool device_src) {
-    if (n_ == 0) return;
-    FH_HIP(hipDeviceSynchronize());                              // queued scans still read the ids that are about to change
-    ids_.ensure(rows_.bytes / ((size_t)dim_ * sizeof(float)) * sizeof(int));      // the ids' capacity follows the rows', as upload keeps it
-    FH_HIP(hipMemcpy(ids_.p, ids, (size_t)n_ * sizeof(int), device_src ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
-    labelled_ = true; fused_ = false;
-}
-
-// Stable compaction through a second buffer: the host reads the ids, lists the surviving positions in order, and whole rows are
-// gathered by that list (gallery_ids.hip).  index_base stays; the certificate's gallery maxima and bad-value flag stay as they are —
-// an upper bound over a superset of the rows is still an upper bound, so F16_RERANK stays exact (a gallery whose only bad row was
-// removed keeps taking the fp32 route until the next upload).
-long Gallery::remove_ids(const int* ids_host, long n_ids) {
-    need_labelled("fh_gallery_remove_ids");
-    if (n_ == 0 || n_ids <= 0) return 0;
-    FH_HIP(hipDeviceSynchronize());                              // queued scans still read the buffers that are about to be replaced
-    std::vector<int> have((size_t)n_), gone(ids_host, ids_host + n_ids), map;
-    FH_HIP(hipMemcpy(have.data(), ids_.p, (size_t)n_ * sizeof(int), hipMemcpyDeviceToHost));
-    std::sort(gone.begin(), gone.end());
-    map.reserve((size_t)n_);
-    for (long r = 0; r < n_; ++r)
-        if (!std::binary_search(gone.begin(), gone.end(), have[(size_t)r])) map.push_back((int)r);
-    const long m = (long)map.size(), removed = n_ - m;
-    if (removed == 0) return 0;
-    if (m == 0) { n_ = 0; return removed; }                      // empty again (capacity kept); the next enrol decides the kind afresh
-    const size_t row_bytes = (size_t)dim_ * sizeof(float), row16 = (size_t)dim_ * sizeof(uint16_t);
-    DevBuf dmap, rows2, ids2, rows16b, tags2;
-    dmap.ensure((size_t)m * sizeof(int));
-    FH_HIP(hipMemcpy(dmap.p, map.data(), (size_t)m * sizeof(int), hipMemcpyHostToDevice));
-    rows2.ensure((size_t)m * row_bytes);
-    ids2.ensure((size_t)m * sizeof(int));
-    launch_gather_rows(rows_.p, rows2.p, dmap.as<int>(), m, row_bytes, nullptr);
-    launch_gather_ids(ids_.as<int>(), ids2.as<int>(), dmap.as<int>(), m, nullptr);
-    if (scan_ == 1) {
-        rows16b.ensure((size_t)m * row16);
-        launch_gather_rows(rows16_.p, rows16b.p, dmap.as<int>(), m, row16, nullptr);
-    }
-    if (has_tags_) {                                             // the tags are 4-byte words: the ids' gather moves them with the rows
-        tags2.ensure((size_t)m * sizeof(unsigned));
-        launch_gather_ids(tags_.as<int>(), tags2.as<int>(), dmap.as<int>(), m, nullptr);
-    }
-    FH_HIP(hipGetLastError());
-    FH_HIP(hipDeviceSynchronize());
-    std::swap(rows2.p, rows_.p); std::swap(rows2.bytes, rows_.bytes);
-    std::swap(ids2.p, ids_.p); std::swap(ids2.bytes, ids_.bytes);
-    if (scan_ == 1) { std::swap(rows16b.p, rows16_.p); std::swap(rows16b.bytes, rows16_.bytes); }
-    n_ = m;
-    if (has_tags_) {                                             // rows moved across tile borders: every tile's OR anew (m < the old row count: it fits)
-        std::swap(tags2.p, tags_.p); std::swap(tags2.bytes, tags_.bytes);
-        launch_tag_tile_or(tags_.as<unsigned>(), m, 0, m, tile_or_.as<unsigned>(), nullptr);
-        FH_HIP(hipGetLastError());
-        FH_HIP(hipDeviceSynchronize());
-    }
-    return removed;
-}
-
-void Gallery::label_ids_dev(const float* q, int Q, float thr, int* out_id, float* out_score, hipStream_t s) {
-    need_labelled("fh_gallery_label_ids_dev");
-    // the best identity is the identity of the best row: the k = 1 row scan of the scan mode, then a gather of its id
-    best_i_.ensure((size_t)std::max(Q, 1) * sizeof(int));
-    topk_dev(q, Q, 1, out_score, best_i_.as<int>(), s);
-    launch_ids_of_rows(out_score, best_i_.as<int>(), Q, ids_.as<int>(), base_, thr, true, out_id, s);
-    FH_HIP(hipGetLastError());
-}
-
-void Gallery::topk_ids_dev(const float* q, int Q, int k, float* out_score, int* out_id, int* out_row, hipStream_t s) {
-    if (Q <= 0 || Q > 256 || k <= 0 || k > 16) throw std::runtime_error("gallery: need 0 < Q <= 256 and 0 < k <= 16");
-    if (dim_ % 64) throw std::runtime_error("gallery: dim must be a multiple of 64");
-    need_labelled("fh_gallery_topk_ids_dev");
-    if (k == 1) {
-        if (!out_row) { best_i_.ensure((size_t)Q * sizeof(int)); out_row = best_i_.as<int>(); }
-        topk_dev(q, Q, 1, out_score, out_row, s);
-        launch_ids_of_rows(out_score, out_row, Q, ids_.as<int>(), base_, 0.f, false, out_id, s);
-        FH_HIP(hipGetLastError());
-        return;
-    }
-    if (scan_ == 1) host_fallback_ += Q;                         // an identity list is always the fp32 scan's
-    pack_queries(q, Q, s);
-    const int parts = size_lists(Q, k, true);
-    launch_gallery_topk_ids(rows_.as<float>(), ids_.as<int>(), n_, dim_, qpack_.as<float>(), Q, k, base_, ps_.as<float>(), pi_.as<int>(),
-                            pd_.as<int>(), seed_s_.as<float>(), seed_i_.as<int>(), seed_d_.as<int>(), s);
-    launch_topk_merge_ids(ps_.as<float>(), pd_.as<int>(), pi_.as<int>(), parts, Q, k, out_score, out_id, out_row, s);
-    FH_HIP(hipGetLastError());
-}
-
-void Gallery::label_dev(const float* q, int Q, float thr, int* out_label, float* out_score, hipStream_t s) {
-    best_i_.ensure((size_t)std::max(Q, 1) * sizeof(int));
-    topk_dev(q, Q, 1, out_score, best_i_.as<int>(), s);
-    launch_label(out_score, best_i_.as<int>(), Q, thr, out_label, s);
-}
-
-void Gallery::topk_dev(const float* q, int Q, int k, float* out_score, int* out_idx, hipStream_t s) {
-    if (Q <= 0 || Q > 256 || k <= 0 || k > 16) throw std::runtime_error("gallery: need 0 < Q <= 256 and 0 < k <= 16");
-    if (dim_ % 64) throw std::runtime_error("gallery: dim must be a multiple of 64");
-    if (scan_ == 1) {
-        // F16_RERANK (gallery_f16.hip): fp16 scan for 32 candidates per query -> exact fp32 re-score + certificate -> the uncertified
-        // queries, compacted on the device, through the fp32 scan below.  Rows with a value the fp16 copy cannot hold (non-finite,
-        // > 65504), an empty gallery and dims that are not a multiple of 128 take the fp32 scan for the whole batch.
-        if (!f16_bad_ && n_ > 0 && dim_ % 128 == 0) {
-            topk_f16(q, Q, k, out_score, out_idx, s);
-            return;
-        }
-        host_fallback_ += Q;
-    }
-    topk_f32(q, Q, k, out_score, out_idx, s, nullptr);
-}
-
-void Gallery::topk_f16(const float* q, int Q, int k, float* out_score, int* out_idx, hipStream_t s) {
-    const int qrows = (Q + 63) / 64 * 64, KC = GAL16_KC;
-    const int parts16 = gallery16_parts(n_, Q, nullptr);
-    q16_.ensure((size_t)qrows * dim_ * sizeof(uint16_t));
-    ps16_.ensure((size_t)parts16 * Q * KC * sizeof(float));
-    pi16_.ensure((size_t)parts16 * Q * KC * sizeof(int));
-    seed16_s_.ensure((size_t)Q * KC * sizeof(float));
-    seed16_i_.ensure((size_t)Q * KC * sizeof(int));
-    cand_s_.ensure((size_t)Q * KC * sizeof(float));
-    cand_i_.ensure((size_t)Q * KC * sizeof(int));
-    fb_cnt_.ensure(sizeof(int));
-    fb_idx_.ensure((size_t)Q * sizeof(int));
-    fb_s_.ensure((size_t)Q * k * sizeof(float));
-    fb_i_.ensure((size_t)Q * k * sizeof(int));
-    FH_HIP(hipMemsetAsync(fb_cnt_.p, 0, sizeof(int), s));
-    launch_gallery16_candidates(rows16_.as<uint16_t>(), n_, dim_, q, q16_.as<uint16_t>(), Q, base_, ps16_.as<float>(), pi16_.as<int>(),
-                                seed16_s_.as<float>(), seed16_i_.as<int>(), cand_s_.as<float>(), cand_i_.as<int>(), s);
-    launch_gallery16_rescore(rows_.as<float>(), n_, dim_, q, Q, k, base_, cand_s_.as<float>(), cand_i_.as<int>(), gbound_[0], gbound_[1],
-                             gbound_[2], out_score, out_idx, fb_cnt_.as<int>(), fb_idx_.as<int>(), ctr_.as<unsigned long long>(), s);
-    // fall-back: the fp32 scan for the compacted uncertified queries (workgroups beyond the device count exit at once), then scatter
-    qpack_.ensure((size_t)qrows * dim_ * sizeof(float));
-    launch_gallery16_gather(q, Q, dim_, fb_cnt_.as<int>(), fb_idx_.as<int>(), qpack_.as<float>(), s);
-    topk_f32(nullptr, Q, k, fb_s_.as<float>(), fb_i_.as<int>(), s, fb_cnt_.as<int>());
-    launch_gallery16_scatter(fb_s_.as<float>(), fb_i_.as<int>(), Q, k, fb_cnt_.as<int>(), fb_idx_.as<int>(), out_score, out_idx, s);
-    FH_HIP(hipGetLastError());
-}
-
-// queries as the GEMM's N operand: whole 64-row tiles, zero rows behind Q (only that tail is cleared)
-void Gallery::pack_queries(const float* q, int Q, hipStream_t s) {
-    const int qrows = (Q + 63) / 64 * 64;
-    qpack_.ensure((size_t)qrows * dim_ * sizeof(float));
-    if (qrows > Q) FH_HIP(hipMemsetAsync(qpack_.as<float>() + (size_t)Q * dim_, 0, (size_t)(qrows - Q) * dim_ * sizeof(float), s));
-    FH_HIP(hipMemcpyAsync(qpack_.p, q, (size_t)Q * dim_ * sizeof(float), hipMemcpyDeviceToDevice, s));
-}
-
-// part planes [gallery_parts][Q][k] and seed planes [Q][k] of the fp32 scans (ids: with their identity planes); returns the parts
-int Gallery::size_lists(int Q, int k, bool ids) {
-    const int parts = n_ > 0 ? gallery_parts(n_, Q, nullptr) : 0;
-    const size_t plane = (size_t)std::max(parts, 1) * Q * k, seed = (size_t)Q * k;
-    ps_.ensure(plane * sizeof(float));
-    pi_.ensure(plane * sizeof(int));
-    seed_s_.ensure(seed * sizeof(float));
-    seed_i_.ensure(seed * sizeof(int));
-    if (ids) { pd_.ensure(plane * sizeof(int)); seed_d_.ensure(seed * sizeof(int)); }
-    return parts;
-}
-
-// q == nullptr: qpack_ is already filled (the F16_RERANK fall-back); qcount (device, optional): only that many queries are live
-void Gallery::topk_f32(const float* q, int Q, int k, float* out_score, int* out_idx, hipStream_t s, const int* qcount) {
-    if (q) pack_queries(q, Q, s);
-    const int parts = size_lists(Q, k, false);
-    // ONE pass over the gallery: dot products stay in the MFMA accumulators, per-workgroup top-k lists come out (gallery.hip)
-    launch_gallery_topk(rows_.as<float>(), n_, dim_, qpack_.as<float>(), Q, k, base_, ps_.as<float>(), pi_.as<int>(),
-                        qcount ? nullptr : seed_s_.as<float>(), qcount ? nullptr : seed_i_.as<int>(), s, qcount);
-    launch_topk_merge(ps_.as<float>(), pi_.as<int>(), parts, Q, k, out_score, out_idx, s, qcount);
-    FH_HIP(hipGetLastError());
-}
-
 // ------------------------------------------------------------------------------------------ face tracker
 Tracker::Tracker(int streams, int max_tracks, float iou_thr, int max_missed, int refresh)
     : streams_(streams), p_{max_tracks, iou_thr, max_missed, refresh, 1, 1, 1} {
@@ -1635,14 +1136,7 @@ void Tracker::identify_dev(Gallery& g, float thr, const int* track, const int* s
     for (int c0 = 0; c0 < total; c0 += 256) {
         const int Q = std::min(256, total - c0);
         const float* q = queries_.as<float>() + (size_t)c0 * idim_;
-        if (masks_on_) {
-            const unsigned* m = qmask_.as<unsigned>() + c0;
-            if (ids) g.label_ids_tagged_dev(q, m, Q, thr, ans_label_.as<int>() + c0, ans_score_.as<float>() + c0, s);
-            else g.label_tagged_dev(q, m, Q, thr, ans_label_.as<int>() + c0, ans_score_.as<float>() + c0, s);
-            continue;
-        }
-        if (ids) g.label_ids_dev(q, Q, thr, ans_label_.as<int>() + c0, ans_score_.as<float>() + c0, s);
-        else g.label_dev(q, Q, thr, ans_label_.as<int>() + c0, ans_score_.as<float>() + c0, s);
+        g.label_dev(q, masks_on_ ? qmask_.as<unsigned>() + c0 : nullptr, Q, thr, ids, ans_label_.as<int>() + c0, ans_score_.as<float>() + c0, s);
     }
     launch_track_propagate(ident_.as<TrackIdent>(), streams_, p_.max_tracks, track, slot, embed, frame_off_.as<int>(), ans_label_.as<int>(),
                            ans_score_.as<float>(), total, per_frame, d_order, d_order + n, label, score, s);

@@ -7,6 +7,7 @@
 #include <cstdint>
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "kernels.h"
@@ -24,6 +25,15 @@ struct DevBuf {                // owning hipMalloc buffer
     DevBuf& operator=(const DevBuf&) = delete;
     ~DevBuf();
     void ensure(size_t n);     // grow-only (re)allocation
+    void swap(DevBuf& o) { std::swap(p, o.p); std::swap(bytes, o.bytes); }
+    void grow(size_t n, size_t keep) {   // ensure(n) that keeps the first `keep` bytes: a second buffer takes them, the old one is freed
+        if (n <= bytes) return;
+        if (keep == 0) return ensure(n);
+        DevBuf bigger;
+        bigger.ensure(n);
+        FH_HIP(hipMemcpy(bigger.p, p, keep, hipMemcpyDeviceToDevice));
+        swap(bigger);
+    }
     template <class T> T* as() const { return reinterpret_cast<T*>(p); }
 };
 
@@ -370,14 +380,16 @@ class Gallery {
     // LABELLED.  A gallery is one or the other: the mixed calls throw (FH_ERR_STATE) and change nothing.
     void upload(const float* rows, const int* ids, long n, bool device_src, long index_base);
     long enroll(const float* rows, const int* ids, long n, bool device_src);     // append; returns the global index of the first new row
-    // best row per query if its mapped score > thr, else -1 (main.cpp:229-233); out_score = that best score
-    void label_dev(const float* q, int Q, float thr, int* out_label, float* out_score, hipStream_t s);
-    // queries [Q][dim] device, Q <= 256, k <= 16 -> out_score/out_idx [Q][k] device
-    void topk_dev(const float* q, int Q, int k, float* out_score, int* out_idx, hipStream_t s);
-    // labelled gallery: the best k IDENTITIES per query, each by its best row -> out_score / out_id / out_row (may be null) [Q][k];
-    // k > 1 always takes the fp32 scan (32 row candidates cannot certify an identity list), k == 1 is the row top-1 of the scan mode
-    void topk_ids_dev(const float* q, int Q, int k, float* out_score, int* out_id, int* out_row, hipStream_t s);
-    void label_ids_dev(const float* q, int Q, float thr, int* out_id, float* out_score, hipStream_t s);
+    // The two queries.  queries [Q][dim] device, Q <= 256, k <= 16; masks (device [Q], may be null): the watchlist form — the same call
+    // on the sub-gallery of each query's admitted rows, global indices kept, always the fp32 scan; ids: answer with IDENTITIES
+    // (labelled gallery unless empty), each by its best row.
+    // topk_dev -> out_score / out_row [Q][k], with ids also out_id [Q][k] (then out_row may be null; without ids out_id is unused).
+    // Without masks the rows, and the k == 1 identity (the identity of the best row), are the top-k of the scan mode; an identity
+    // list of k > 1 always takes the fp32 scan (32 row candidates cannot certify it).
+    void topk_dev(const float* q, const unsigned* masks, int Q, int k, bool ids, float* out_score, int* out_id, int* out_row, hipStream_t s);
+    // label_dev -> the best row (ids: its identity) per query if its mapped score > thr, else -1 (main.cpp:229-233); out_score = that
+    // best score
+    void label_dev(const float* q, const unsigned* masks, int Q, float thr, bool ids, int* out_label, float* out_score, hipStream_t s);
     // removes every row whose id is listed (stable compaction through a second buffer: transiently the surviving fp32 rows, ids and
     // fp16 rows exist twice, plus 4 bytes per survivor); synchronous; returns the number of rows removed
     long remove_ids(const int* ids_host, long n_ids);
@@ -399,13 +411,13 @@ class Gallery {
     void pair_hist_dev(unsigned long long* hist, unsigned long long* nan, hipStream_t s);
     // replaces every row's id by position (host or device list, checked by the caller: none negative); synchronous
     void set_ids(const int* ids, bool device_src);
-    bool labelled() const { return labelled_; }
+    bool labelled() const { return ids_.live; }                  // meaningful while size() > 0; an empty gallery takes either kind
     long size() const { return n_; }
     int dim() const { return dim_; }
     // fh_gallery_set_scan: 1 = F16_RERANK (an fp16 copy of the rows beside the fp32 rows, G x dim x 2 bytes; same answer bit for bit),
     // 0 = FP32 (frees the copy).  Synchronous.
     void set_scan(int mode);
-    int scan() const { return scan_; }
+    int scan() const { return rows16_.live ? 1 : 0; }
     void scan_stats(long long* certified, long long* fallback);   // waits for the device; resets both
     // Watchlists (gallery_tags.hip): a 32-bit tag per row, a 32-bit mask per query (device [Q]); row r is admitted for query q iff
     // (tag[r] & mask[q]) != 0.  A gallery whose tags were never set (or not since the last upload) has none: it behaves as if every
@@ -413,39 +425,46 @@ class Gallery {
     // caller except the ranges.  set_tags / get_tags: rows [first, first + n) by position; synchronous.
     void set_tags(long first, long n, const unsigned* tags, bool device_src);
     void get_tags(long first, long n, unsigned* out_host);
-    // the untagged calls of the same names on the sub-gallery of each query's admitted rows, global indices kept; always the fp32 scan
-    void topk_tagged_dev(const float* q, const unsigned* masks, int Q, int k, float* out_score, int* out_idx, hipStream_t s);
-    void topk_ids_tagged_dev(const float* q, const unsigned* masks, int Q, int k, float* out_score, int* out_id, int* out_row, hipStream_t s);
-    void label_tagged_dev(const float* q, const unsigned* masks, int Q, float thr, int* out_label, float* out_score, hipStream_t s);
-    void label_ids_tagged_dev(const float* q, const unsigned* masks, int Q, float thr, int* out_id, float* out_score, hipStream_t s);
     void tag_stats(long long* scanned, long long* skipped);       // waits for the device; resets both
 
   private:
-    void need_tags();                                            // the tag buffers exist, sized to the rows' capacity (first use: all ones)
-    void scan_tagged(const float* q, const unsigned* masks, int Q, int k, bool ids, float* out_score, int* out_id, int* out_row, hipStream_t s);
+    // The row set: ONE capacity in rows and the per-row columns that share it.  A live column always holds cap_ rows; a dead one keeps
+    // whatever buffer it had and is sized afresh when it comes to life (its contents are then the caller's to fill).
+    struct Column {
+        size_t row_bytes;
+        bool live;
+        DevBuf buf;
+        template <class T> T* as() const { return buf.as<T>(); }
+    };
+    void set_live(Column& c, bool on);                           // on: cap_ rows (nothing kept)
+    void reserve(long cap);                                      // every live column holds max(cap, cap_) rows, the first n_ kept
+    long append(long n);                                         // room for n more rows (grows to max(need, 2 x capacity)); returns n_
+    void compact(const int* map, long m);                        // row j <- row map[j] (device, ascending), j < m; capacity = m; synchronous
+    void need_tags();                                            // the tags are live (first use: all ones) and their counters exist
+    void rebuild_tile_or(long first, long n);                    // tile_or of the tiles rows [first, first + n) touch; synchronous
     void convert16(long first, long n);                          // rows [first, first + n) -> rows16_, bounds + flag (synchronous)
     void topk_f16(const float* q, int Q, int k, float* out_score, int* out_idx, hipStream_t s);
-    void topk_f32(const float* q, int Q, int k, float* out_score, int* out_idx, hipStream_t s, const int* qcount);
-    void pack_queries(const float* q, int Q, hipStream_t s);     // q -> qpack_: whole 64-row tiles with a zero tail
-    int size_lists(int Q, int k, bool ids);                      // sizes the part and seed planes of an fp32 scan; returns the parts
-    void need_labelled(const char* what) const;                  // throws on a non-empty unlabelled gallery
+    // the ONE fp32 scan: pack the queries (q == nullptr: qpack_ is filled already), size the lists, launch, merge
+    void scan_f32(const float* q, const unsigned* masks, int Q, int k, bool ids, float* out_score, int* out_id, int* out_row, hipStream_t s,
+                  const int* qcount);
+    void need_labelled(const std::string& what) const;           // throws on a non-empty unlabelled gallery
     int dim_;
-    long n_ = 0, base_ = 0;
-    bool labelled_ = false;                                      // meaningful while n_ > 0; an empty gallery takes either kind
+    long n_ = 0, cap_ = 0, base_ = 0;
     bool fused_ = false;
-    DevBuf rows_, qpack_, ps_, pi_, best_i_, seed_s_, seed_i_;
+    Column rows_{(size_t)dim_ * sizeof(float), true}, rows16_{(size_t)dim_ * sizeof(uint16_t), false};   // fp32 rows; fp16 rows, live in F16_RERANK
+    Column ids_{sizeof(int), false}, tags_{sizeof(unsigned), false};     // identity id per row, live while labelled; tag per row, live once set
+    static constexpr int kCols = 4;
+    Column* const cols_[kCols] = {&rows_, &rows16_, &ids_, &tags_};
+    DevBuf tile_or_, tag_ctr_;                                   // follows the tags: their OR per 128-row tile; [2] visit counters
+    DevBuf qpack_, ps_, pi_, pd_, best_i_, seed_s_, seed_i_, seed_d_;    // packed queries; part / seed lists of the fp32 scan (pd_, seed_d_: id planes)
     DevBuf cl_deg_, cl_parent_, cl_best_;                        // cluster_dev: degree, union-find parent, best core neighbour per row
     DevBuf cl_hist_;                                             // pair_hist_dev: the histogram the workgroups flush into
-    DevBuf ids_, pd_, seed_d_;                                   // identity id per row (capacity in rows = rows_'), id planes of the part / seed lists
-    bool has_tags_ = false;
-    DevBuf tags_, tile_or_, tag_ctr_;                            // tag per row (capacity in rows = rows_'), OR per 128-row tile, [2] visit counters
-    // F16_RERANK state: the fp16 rows, [max|g|, max|g^|, max|g - g^| (float bits), non-finite / > 65504 flag] on the device and its host
-    // copy, per-call scratch, the certified / fallback counters
-    int scan_ = 0;
+    // F16_RERANK state: [max|g|, max|g^|, max|g - g^| (float bits), non-finite / > 65504 flag] on the device and its host copy,
+    // per-call scratch, the certified / fallback counters
     bool f16_bad_ = false;
     float gbound_[3] = {0.f, 0.f, 0.f};
     long long host_fallback_ = 0;
-    DevBuf rows16_, gstat_, q16_, ps16_, pi16_, seed16_s_, seed16_i_, cand_s_, cand_i_, fb_cnt_, fb_idx_, fb_s_, fb_i_, ctr_;
+    DevBuf gstat_, q16_, ps16_, pi16_, seed16_s_, seed16_i_, cand_s_, cand_i_, fb_cnt_, fb_idx_, fb_s_, fb_i_, ctr_;
 };
 
 }  // namespace fh

@@ -1,10 +1,11 @@
 // gallery.hip — 1:N generalisation of FaceRecognizer::compareFaces (reference src/face_recognizer.cpp:320-334): every query against
 // every enrolled row, mapped score (dot + 1) / 2, top-k per query ranked (score desc, global row index asc).
 // Here: the row-level instantiation of the streaming scan (gallery_scan.h holds the scan, its design notes and measurements), the
-// two-pass launcher all three scans go through, and the merge of the per-workgroup lists — also the merge step of a row-sharded
-// gallery (fh_topk_merge_dev, fh_topk_merge_ids_dev).
+// two-pass launcher every scan goes through, launch_gallery_scan — the one launcher of the four fp32 scans — and the merge of the
+// per-workgroup lists — also the merge step of a row-sharded gallery (fh_topk_merge_dev, fh_topk_merge_ids_dev).
 #include <hip/hip_runtime.h>
 
+#include <atomic>
 #include <climits>
 #include <cstdlib>
 #include <stdexcept>
@@ -61,17 +62,24 @@ int launch_gallery_two_pass(const GalScan& sc, GalArgs a, long G, bool seed, flo
     return parts;
 }
 
-// queries: packed [ceil64(Q)][dim] with zero rows behind Q; part_score / part_idx: [gallery_parts][Q][k]; seed_score / seed_idx: [Q][k] scratch.
-void launch_gallery_topk(const float* gal, long G, int dim, const float* qpacked, int Q, int k, long idx_base, float* part_score, int* part_idx,
-                         float* seed_score, int* seed_idx, hipStream_t s, const int* qcount) {
-    if (G <= 0 || Q <= 0) return;
+// The one launcher of the fp32 scans.  The kernel comes from a table indexed by (lists of identities?, tags?): a.ids / a.qmask say which.
+namespace {
+std::atomic<int> g_tag_skip{1};
+}
+void gallery_debug_tag_skip(int on) { g_tag_skip.store(on != 0); }
+
+void launch_gallery_scan(GalArgs a, long G, float* seed_s, int* seed_i, int* seed_d, hipStream_t s) {
+    if (G <= 0 || a.Q <= 0) return;
     static int seed_on = -1;
-    if (seed_on < 0) { const char* e = getenv("FACEHIP_GAL_SEED"); seed_on = e ? atoi(e) : 1; }     // (0: no seed pass — A / B timing)
-    GalArgs a{};
-    a.gal = gal; a.q = qpacked; a.idx_base = idx_base; a.dim = dim; a.Q = Q; a.k = k;
-    a.ps = part_score; a.pi = part_idx; a.qcount = qcount;
-    static const GalScan scan{"gallery", gallery_topk_kernel, /*chunk*/ 64, /*depth*/ GAL_KMAX, GAL_WG_PER_CU, /*max_parts*/ LONG_MAX, /*has_qcount*/ true};
-    launch_gallery_two_pass(scan, a, G, seed_on != 0, seed_score, seed_idx, nullptr, s);
+    if (seed_on < 0) { const char* e = getenv("FACEHIP_GAL_SEED"); seed_on = e ? atoi(e) : 1; }     // (0: no seed pass — A / B timing of the plain row scan)
+    static const GalScan scans[2][2] = {
+        {{"gallery", gallery_topk_kernel, /*chunk*/ 64, /*depth*/ GAL_KMAX, GAL_WG_PER_CU, /*max_parts*/ LONG_MAX, /*has_qcount*/ true},
+         {"gallery (tagged)", gallery_topk_tagged_kernel, 64, GAL_KMAX, GAL_WG_PER_CU, LONG_MAX, true}},
+        {{"gallery", gallery_topk_ids_kernel, 64, GAL_KMAX, GAL_WG_PER_CU, LONG_MAX, true},
+         {"gallery (tagged)", gallery_topk_ids_tagged_kernel, 64, GAL_KMAX, GAL_WG_PER_CU, LONG_MAX, true}}};
+    const bool ids = a.ids != nullptr, tags = a.qmask != nullptr;
+    a.tag_skip = g_tag_skip.load();
+    launch_gallery_two_pass(scans[ids][tags], a, G, ids || tags || seed_on != 0, seed_s, seed_i, seed_d, s);
 }
 
 // ------------------------------------------------------------------------------------------ the merge of the part lists

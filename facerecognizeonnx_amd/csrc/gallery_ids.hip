@@ -28,17 +28,6 @@ namespace fh {
 
 __global__ __launch_bounds__(256, 2) void gallery_topk_ids_kernel(const GalArgs p) { gallery_scan_body<float, GAL_KMAX, false, true>(p); }
 
-// the two passes of launch_gallery_topk: identity top-k of the first rows as admission thresholds, then the full scan
-void launch_gallery_topk_ids(const float* gal, const int* ids, long G, int dim, const float* qpacked, int Q, int k, long idx_base,
-                             float* part_score, int* part_idx, int* part_id, float* seed_score, int* seed_idx, int* seed_id, hipStream_t s) {
-    if (G <= 0 || Q <= 0) return;
-    GalArgs a{};
-    a.gal = gal; a.ids = ids; a.q = qpacked; a.idx_base = idx_base; a.dim = dim; a.Q = Q; a.k = k;
-    a.ps = part_score; a.pi = part_idx; a.pd = part_id;
-    static const GalScan scan{"gallery", gallery_topk_ids_kernel, /*chunk*/ 64, /*depth*/ GAL_KMAX, GAL_WG_PER_CU, /*max_parts*/ LONG_MAX, /*has_qcount*/ true};
-    launch_gallery_two_pass(scan, a, G, true, seed_score, seed_idx, seed_id, s);
-}
-
 __global__ void ids_of_rows_kernel(const float* __restrict__ score, const int* __restrict__ idx, int n, const int* __restrict__ ids, long idx_base,
                                    float thr, int use_thr, int* __restrict__ out_id) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;

@@ -1,6 +1,7 @@
 // gallery_scan.h — the streaming 1:N scan of the gallery: ONE body, instantiated as gallery_topk_kernel (gallery.hip: fp32 rows, lists of
-// rows), gallery_topk_ids_kernel (gallery_ids.hip: fp32 rows, lists of identities) and gal16_scan_kernel (gallery_f16.hip: fp16 rows,
-// 32-deep candidate lists); with it the ranking predicate, the kernel arguments and the two-pass launcher all three share.
+// rows), gallery_topk_ids_kernel (gallery_ids.hip: fp32 rows, lists of identities), their tagged twins (gallery_tags.hip) and
+// gal16_scan_kernel (gallery_f16.hip: fp16 rows, 32-deep candidate lists); with it the ranking predicate, the kernel arguments, the
+// two-pass launcher all of them share and the one launcher of the four fp32 scans.
 //
 // One kernel streams the gallery ONCE: the dot products live only in MFMA accumulators, never in memory.
 //   * The scan is an HBM stream with NO reuse on the gallery side: what limits it is bytes in flight (Little: ~50 KB per CU for 5 TB/s at
@@ -102,6 +103,15 @@ void gallery_check_args(const GalScan& sc, const GalArgs& a, long G);     // thr
 // that cannot matter.  `a` carries gal / q / ids, idx_base, dim, Q, k, the part planes and qcount; seed_* = [Q][k] scratch.  The row range
 // is cut into gallery_parts_for(G, Q, wg_per_cu, max_parts) parts; returns that number (the caller merges the part lists).
 int launch_gallery_two_pass(const GalScan& sc, GalArgs a, long G, bool seed, float* seed_s, int* seed_i, int* seed_d, hipStream_t s);
+// The fp32 scans: the four instantiations (gallery.hip, gallery_ids.hip, gallery_tags.hip) and their ONE launcher (gallery.hip).  `a` as
+// above, filled by the caller; a.ids (with a.pd) asks for lists of identities, a.qmask (with a.tags, a.tile_or, a.tag_ctr) for the
+// tagged scan; a.qcount only for plain lists of rows.  seed_d: needed with a.ids.  G <= 0 or Q <= 0 launches nothing.  The seed pass is
+// always on, except that FACEHIP_GAL_SEED=0 switches it off for the plain row scan; fh_debug_tag_skip sets a.tag_skip.
+__global__ __launch_bounds__(256, 2) void gallery_topk_kernel(const GalArgs p);
+__global__ __launch_bounds__(256, 2) void gallery_topk_ids_kernel(const GalArgs p);
+__global__ __launch_bounds__(256, 2) void gallery_topk_tagged_kernel(const GalArgs p);
+__global__ __launch_bounds__(256, 2) void gallery_topk_ids_tagged_kernel(const GalArgs p);
+void launch_gallery_scan(GalArgs a, long G, float* seed_s, int* seed_i, int* seed_d, hipStream_t s);
 
 __device__ __forceinline__ bool gal_better(float s1, int i1, float s2, int i2) { return s1 > s2 || (s1 == s2 && i1 < i2); }
 

@@ -11,7 +11,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <atomic>
 #include <climits>
 
 #include "gallery_scan.h"
@@ -23,25 +22,6 @@ __global__ __launch_bounds__(256, 2) void gallery_topk_tagged_kernel(const GalAr
 __global__ __launch_bounds__(256, 2) void gallery_topk_ids_tagged_kernel(const GalArgs p) { gallery_scan_body<float, GAL_KMAX, false, true, true>(p); }
 
 static_assert(GAL_TAG_TILE == GAL_BM, "tile_or is kept per row tile of the scan");
-
-namespace {
-std::atomic<int> g_tag_skip{1};
-}
-void gallery_debug_tag_skip(int on) { g_tag_skip.store(on != 0); }
-
-// ids == nullptr: lists of rows; otherwise lists of identities (part_id / seed_id as launch_gallery_topk_ids)
-void launch_gallery_topk_tagged(const float* gal, const int* ids, const unsigned* tags, const unsigned* tile_or, long G, int dim,
-                                const float* qpacked, const unsigned* qmask, int Q, int k, long idx_base, float* part_score, int* part_idx,
-                                int* part_id, float* seed_score, int* seed_idx, int* seed_id, unsigned long long* tag_ctr, hipStream_t s) {
-    if (G <= 0 || Q <= 0) return;
-    GalArgs a{};
-    a.gal = gal; a.ids = ids; a.q = qpacked; a.idx_base = idx_base; a.dim = dim; a.Q = Q; a.k = k;
-    a.ps = part_score; a.pi = part_idx; a.pd = ids ? part_id : nullptr;
-    a.tags = tags; a.qmask = qmask; a.tile_or = tile_or; a.tag_ctr = tag_ctr; a.tag_skip = g_tag_skip.load();
-    static const GalScan rows{"gallery (tagged)", gallery_topk_tagged_kernel, /*chunk*/ 64, /*depth*/ GAL_KMAX, GAL_WG_PER_CU, /*max_parts*/ LONG_MAX, /*has_qcount*/ true};
-    static const GalScan idsc{"gallery (tagged)", gallery_topk_ids_tagged_kernel, /*chunk*/ 64, /*depth*/ GAL_KMAX, GAL_WG_PER_CU, /*max_parts*/ LONG_MAX, /*has_qcount*/ true};
-    launch_gallery_two_pass(ids ? idsc : rows, a, G, true, seed_score, seed_idx, ids ? seed_id : nullptr, s);
-}
 
 // one wave per row tile: tile_or[t] = OR of tags[128 t .. 128 t + 128) (rows behind G count as 0)
 __global__ __launch_bounds__(64) void tag_tile_or_kernel(const unsigned* __restrict__ tags, long G, long tile0, unsigned* __restrict__ tile_or) {

@@ -331,13 +331,9 @@ void launch_l2_normalize(const float* in, float* out, int n, int dim, hipStream_
 
 // compareFaces generalised to 1:N (src/face_recognizer.cpp:320-334): top-k of (dot+1)/2 ranked (score desc, gallery index asc).
 // gallery.hip: ONE streaming pass — gallery rows x queries on the matrix cores, per-workgroup top-k lists [gallery_parts][Q][k] kept in
-// LDS while the rows go by (no G x Q matrix in memory); then launch_topk_merge.  qpacked = [ceil64(Q)][dim], zero rows behind Q.
+// LDS while the rows go by (no G x Q matrix in memory); then launch_topk_merge.  The scans' launcher speaks of their argument struct
+// and sits beside it: launch_gallery_scan, gallery_scan.h.
 int gallery_parts(long G, int Q, int* tiles_per_part);
-// qcount (optional, device): only query tiles below *qcount are scanned, the grid stays sized for Q (the compacted fall-back of the
-// f16 re-rank scan); null = all Q
-void launch_gallery_topk(const float* gal, long G, int dim, const float* qpacked, int Q, int k, long idx_base, float* part_score, int* part_idx,
-                         float* seed_score, int* seed_idx, hipStream_t s,       // seed_*: [Q][k] scratch (threshold pre-pass of large galleries)
-                         const int* qcount = nullptr);
 void launch_label(const float* best_score, const int* best_idx, int n, float thr, int* labels, hipStream_t s);
 void launch_topk_merge(const float* part_score, const int* part_idx, int nparts, int Q, int k, float* out_score,
                        int* out_idx, hipStream_t s, const int* qcount = nullptr);     // qcount (device, optional): queries >= *qcount skipped
@@ -346,9 +342,7 @@ void launch_topk_merge_strided(const float* part_score, const int* part_idx, int
 
 // gallery_ids.hip — the labelled gallery: every row carries an identity id >= 0, a query is answered with its best k IDENTITIES, each
 // represented by its best row (score desc, global row index asc).  Same streaming scan (gallery_scan.h), lists of (score, row, id) with
-// at most one entry per identity; part_* / seed_*: [gallery_parts][Q][k] / [Q][k] scratch as launch_gallery_topk, with an id plane.
-void launch_gallery_topk_ids(const float* gal, const int* ids, long G, int dim, const float* qpacked, int Q, int k, long idx_base,
-                             float* part_score, int* part_idx, int* part_id, float* seed_score, int* seed_idx, int* seed_id, hipStream_t s);
+// at most one entry per identity, and an id plane beside the part / seed planes.
 // [nparts][Q][k] identity lists (each list: distinct ids, -1 rows = empty) -> the identity top-k of their union; out_idx may be null
 void launch_topk_merge_ids(const float* part_score, const int* part_id, const int* part_idx, int nparts, int Q, int k, float* out_score,
                            int* out_id, int* out_idx, hipStream_t s, const int* qcount = nullptr);
@@ -360,14 +354,11 @@ void launch_gather_rows(const void* src, void* dst, const int* map, long m, size
 void launch_gather_ids(const int* src, int* dst, const int* map, long m, hipStream_t s);
 
 // gallery_tags.hip — watchlists: a 32-bit tag per row, a 32-bit mask per query, row r admitted for query q iff (tags[r] & qmask[q]) != 0;
-// the answer is the exact top-k of the query's admitted rows (ids == nullptr) or of their identities (part_id / seed_id then as
-// launch_gallery_topk_ids), global indices kept.  Same streaming scan, same part / seed planes, same merges.  tile_or[t] = OR of the tags
-// of rows [128 t, 128 t + 128) by position; tag_ctr [2] (device) counts the (workgroup, tile) visits multiplied / skipped.
-void launch_gallery_topk_tagged(const float* gal, const int* ids, const unsigned* tags, const unsigned* tile_or, long G, int dim,
-                                const float* qpacked, const unsigned* qmask, int Q, int k, long idx_base, float* part_score, int* part_idx,
-                                int* part_id, float* seed_score, int* seed_idx, int* seed_id, unsigned long long* tag_ctr, hipStream_t s);
+// the answer is the exact top-k of the query's admitted rows or of their identities, global indices kept.  Same streaming scan, same
+// part / seed planes, same merges.  tile_or[t] = OR of the tags of rows [128 t, 128 t + 128) by position; tag_ctr [2] (device) counts
+// the (workgroup, tile) visits multiplied / skipped.
 constexpr int GAL_TAG_TILE = 128;                            // rows per tile_or entry = the scan's row tile
-void gallery_debug_tag_skip(int on);                         // 0: tagged scans multiply every tile (same answer)
+void gallery_debug_tag_skip(int on);                         // 0: tagged scans multiply every tile (same answer); gallery.hip
 // rebuilds tile_or for the tiles that rows [first, first + n) of a gallery of G rows touch
 void launch_tag_tile_or(const unsigned* tags, long G, long first, long n, unsigned* tile_or, hipStream_t s);
 // dst_tags[j] = OR of src_tags[order[i]], starts[j] <= i < starts[j + 1] (the inverted index of fh_gallery_group_ids), j < m
