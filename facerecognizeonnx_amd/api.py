@@ -805,6 +805,32 @@ class Gallery:
         check(_lib.lib().fh_gallery_label_ids_tagged_dev(self._h, q_ptr, masks_ptr, nq, threshold, ids_ptr, scores_ptr, stream),
               "fh_gallery_label_ids_tagged_dev")
 
+    def range_dev(self, q_ptr: int, nq: int, threshold: float, cap: int, counts_ptr: int, scores_ptr: Optional[int] = None,
+                  idx_ptr: Optional[int] = None, ids_ptr: Optional[int] = None, masks_ptr: Optional[int] = None, stream: int = 0):
+        """Threshold search (fh_gallery_range_dev): counts[nq] (device int64) = the exact number of rows — admitted rows with masks
+        (device uint32[nq]) — whose mapped score is strictly above `threshold`; scores / idx / ids [nq][cap] (device, each optional) =
+        the best min(count, cap) of them, (score desc, global row asc), empty slots (-1.0, -1, -1).  Scores are the fp32 scan's, bit
+        for bit, in either scan mode.  ids needs a labelled gallery.  1 <= cap <= RANGE_MAX_CAP.  Asynchronous on `stream`."""
+        check(_lib.lib().fh_gallery_range_dev(self._h, q_ptr, masks_ptr, nq, threshold, cap, counts_ptr, scores_ptr, idx_ptr, ids_ptr, stream),
+              "fh_gallery_range_dev")
+
+    def range(self, queries, threshold: float, cap: int = 64, masks=None, ids: bool = False):
+        """(counts int64[nq], scores float32[nq, cap], indices int32[nq, cap][, ids int32[nq, cap]]) of range_dev for host queries
+        [nq, dim] (masks: uint32[nq], optional) — a synchronous convenience that uploads, allocates and copies back."""
+        import torch
+        q = np.array(queries, np.float32, order="C").reshape(-1, self.dim)      # (a copy: torch takes no read-only array)
+        nq = q.shape[0]
+        qd = torch.from_numpy(q).cuda()
+        md = None if masks is None else torch.from_numpy(np.ascontiguousarray(np.asarray(masks).astype(np.uint32)).view(np.int32).reshape(nq)).cuda()
+        counts = torch.zeros(max(nq, 1), dtype=torch.int64, device="cuda")
+        sc = torch.empty((max(nq, 1), cap), dtype=torch.float32, device="cuda")
+        ix = torch.empty((max(nq, 1), cap), dtype=torch.int32, device="cuda")
+        di = torch.empty((max(nq, 1), cap), dtype=torch.int32, device="cuda") if ids else None
+        self.range_dev(qd.data_ptr(), nq, threshold, cap, counts.data_ptr(), sc.data_ptr(), ix.data_ptr(), None if di is None else di.data_ptr(),
+                       None if md is None else md.data_ptr(), torch.cuda.current_stream().cuda_stream)
+        out = (counts[:nq].cpu().numpy(), sc[:nq].cpu().numpy(), ix[:nq].cpu().numpy())
+        return out + (di[:nq].cpu().numpy(),) if ids else out
+
     def tag_stats(self):
         """(tiles_scanned, tiles_skipped): the (workgroup, 128-row tile) visits the tagged scans multiplied / skipped since the last
         call (resets; waits for the handle's queued work)."""
@@ -934,6 +960,26 @@ def roc_from_hist(hist, max_far: float):
         d["tar"] = d["true_accepts"] / d["genuine"]
         pts.append(d)
     return pts[0], pts[1]
+
+
+def range_from_scores(scores, threshold: float, cap: int = 64, index_base: int = 0, tags=None, mask: int = _lib.TAG_ALL):
+    """(count, scores float32[cap], indices int32[cap]) of fh_range_from_scores — host only, the one definition of the threshold search
+    rule, for ONE query's row of mapped scores: a row is a hit iff (tag & mask) != 0 (tags=None: every row carries TAG_ALL), its score
+    is strictly above `threshold` in float32 and is not a NaN; count is exact, the lists hold the best min(count, cap) hits (score
+    desc, index_base + position asc) and (-1.0, -1) behind them."""
+    scores = np.ascontiguousarray(scores, np.float32).reshape(-1)
+    n = scores.size
+    if tags is not None:
+        tags = np.ascontiguousarray(np.asarray(tags).reshape(-1).astype(np.uint32))
+        if tags.size != n:
+            raise ValueError("range_from_scores: need one tag per score")
+    cap = int(cap)
+    out_s, out_i = np.empty(max(cap, 0), np.float32), np.empty(max(cap, 0), np.int32)
+    count = C.c_longlong(0)
+    check(_lib.lib().fh_range_from_scores(scores.ctypes.data if n else None, n, int(index_base), None if tags is None or n == 0 else tags.ctypes.data,
+                                          int(mask) & 0xFFFFFFFF, float(np.float32(threshold)), cap, C.byref(count), out_s.ctypes.data,
+                                          out_i.ctypes.data), "fh_range_from_scores")
+    return int(count.value), out_s, out_i
 
 
 def plan_describe(path: str, default_h: int, default_w: int) -> str:

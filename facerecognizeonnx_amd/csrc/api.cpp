@@ -10,6 +10,7 @@
 
 #include "../../include/facehip.h"
 #include "cluster_plan.h"
+#include "range_plan.h"
 #include "roc_plan.h"
 #include "engine.h"
 #include "group_ids.h"
@@ -1473,6 +1474,35 @@ int fh_gallery_pair_hist_dev(fh_gallery* g, unsigned long long* d_hist, unsigned
     return guarded([&] { g->g.pair_hist_dev(d_hist, d_nan, S(stream)); return (int)FH_OK; });
 }
 int fh_debug_hist_copies(int copies) { fh::cluster_debug_hist_copies(copies); return 0; }
+
+// ---- threshold search: the rule on the host (range_plan.h), the same rule on the scan's accumulators (gallery_range.hip)
+static_assert(FH_RANGE_MAX_CAP == fh::kRangeMaxCap && FH_TAG_ALL == fh::kRangeTagAll, "facehip.h mirrors range_plan.h");
+int fh_range_from_scores(const float* scores, long long n, long long index_base, const uint32_t* tags, uint32_t mask, float threshold, int cap,
+                         long long* count, float* out_scores, int* out_indices) {
+    int listed = -1;
+    const int rc = guarded([&] {                                   // (its scratch may run out of memory)
+        listed = fh::range_from_scores(scores, n, index_base, tags, mask, threshold, cap, count, out_scores, out_indices);
+        return 0;
+    });
+    if (rc < 0) return rc;
+    return listed < 0 ? arg_error("fh_range_from_scores: bad argument (null scores or count, NaN threshold, cap outside 1..1024, index beyond 31 bits)")
+                      : listed;
+}
+int fh_gallery_range_dev(fh_gallery* g, const float* d_queries, const uint32_t* d_masks, int nq, float threshold, int cap, long long* d_counts,
+                         float* d_scores, int* d_indices, int* d_ids, void* stream) {
+    if (!g) return arg_error("fh_gallery_range_dev: null handle");
+    if (nq < 0 || nq > 256) return arg_error("fh_gallery_range_dev: need 0 <= nq <= 256");
+    if (cap < 1 || cap > FH_RANGE_MAX_CAP) return arg_error("fh_gallery_range_dev: need 1 <= cap <= FH_RANGE_MAX_CAP");
+    if (threshold != threshold) return arg_error("fh_gallery_range_dev: the threshold is a NaN");
+    if (g->g.dim() % 64) return arg_error("fh_gallery_range_dev: the gallery's dim must be a multiple of 64");
+    if (nq == 0) return 0;
+    if (!d_queries || !d_counts) return arg_error("fh_gallery_range_dev: null argument");
+    if (d_ids && g->g.size() > 0 && !g->g.labelled()) {
+        g_err = "gallery: fh_gallery_range_dev with d_ids needs a labelled gallery (rows enrolled with ids, or fh_gallery_set_ids)";
+        return FH_ERR_STATE;
+    }
+    return guarded([&] { g->g.range_dev(d_queries, d_masks, nq, threshold, cap, d_counts, d_scores, d_indices, d_ids, S(stream)); return nq; });
+}
 
 int fh_debug_topk_merge_strided_dev(const float* ps, const int* pi, int nparts, int nq, int k, long long part_stride, float* scores, int* indices,
                                     void* stream) {

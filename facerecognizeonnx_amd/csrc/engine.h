@@ -390,6 +390,14 @@ class Gallery {
     // label_dev -> the best row (ids: its identity) per query if its mapped score > thr, else -1 (main.cpp:229-233); out_score = that
     // best score
     void label_dev(const float* q, const unsigned* masks, int Q, float thr, bool ids, int* out_label, float* out_score, hipStream_t s);
+    // Threshold search (gallery_range.hip; the rule: range_plan.h): counts [Q] = the exact number of rows whose mapped score is above
+    // thr (admitted rows only with masks), and — each may be null — out_score / out_row / out_id [Q][cap] = the best min(count, cap) of
+    // them, (score desc, global row asc), empty slots (-1, -1, -1).  Always the fp32 rows, whatever the scan mode.  out_id needs a
+    // labelled gallery unless empty.  Q, cap and thr are checked by the caller.  Asynchronous; the scratch (hit bitmap: 4 bytes per 32
+    // rows and query of a whole 64-query tile, at most ceil(size / 32) * 1 KB = 1.6 % of the fp32 rows at dim 512; count planes: 1 / 256
+    // of that) lives in the handle and grows, synchronously, with the first call of a larger (Q, size).
+    void range_dev(const float* q, const unsigned* masks, int Q, float thr, int cap, long long* counts, float* out_score, int* out_row,
+                   int* out_id, hipStream_t s);
     // removes every row whose id is listed (stable compaction through a second buffer: transiently the surviving fp32 rows, ids and
     // fp16 rows exist twice, plus 4 bytes per survivor); synchronous; returns the number of rows removed
     long remove_ids(const int* ids_host, long n_ids);
@@ -447,6 +455,7 @@ class Gallery {
     // the ONE fp32 scan: pack the queries (q == nullptr: qpack_ is filled already), size the lists, launch, merge
     void scan_f32(const float* q, const unsigned* masks, int Q, int k, bool ids, float* out_score, int* out_id, int* out_row, hipStream_t s,
                   const int* qcount);
+    void pack_queries(const float* q, int Q, hipStream_t s);     // qpack_ <- q as whole 64-row tiles, zero rows behind Q
     void need_labelled(const std::string& what) const;           // throws on a non-empty unlabelled gallery
     int dim_;
     long n_ = 0, cap_ = 0, base_ = 0;
@@ -459,6 +468,7 @@ class Gallery {
     DevBuf qpack_, ps_, pi_, pd_, best_i_, seed_s_, seed_i_, seed_d_;    // packed queries; part / seed lists of the fp32 scan (pd_, seed_d_: id planes)
     DevBuf cl_deg_, cl_parent_, cl_best_;                        // cluster_dev: degree, union-find parent, best core neighbour per row
     DevBuf cl_hist_;                                             // pair_hist_dev: the histogram the workgroups flush into
+    DevBuf rg_hits_, rg_units_;                                  // range_dev: hit bitmap [32-row block][query], hits per (8192 rows, query)
     // F16_RERANK state: [max|g|, max|g^|, max|g - g^| (float bits), non-finite / > 65504 flag] on the device and its host copy,
     // per-call scratch, the certified / fallback counters
     bool f16_bad_ = false;

@@ -130,22 +130,8 @@ __global__ __launch_bounds__(64) void gal16_rescore_kernel(const Gal16Rescore p)
     const int gi = p.cand_i[(size_t)qn * G16_KC + fr];
     const bool live = gi >= 0;
     // the fp32 score of candidate fr: gallery_topk_kernel's multiply, with the query in every column of B
-    const float* a_ptr = (live ? p.gal + (size_t)(gi - p.idx_base) * K : p.zeros) + fh2 * 4;
-    const int a_step = live ? 64 : 0;
-    const float* b_ptr = qrow + fh2 * 4;
-    v16f acc;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) acc[e] = 0.f;
-    for (int kc = 0; kc < chunks; ++kc) {
-        v4f x[8], w[8];
-#pragma unroll
-        for (int s = 0; s < 8; ++s) { x[s] = *reinterpret_cast<const v4f*>(a_ptr + s * 8); w[s] = *reinterpret_cast<const v4f*>(b_ptr + s * 8); }
-        a_ptr += a_step; b_ptr += 64;
-#pragma unroll
-        for (int s = 0; s < 8; ++s)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(x[s][e], w[s][e], acc, 0, 0, 0);
-    }
+    // (gal_rescore32, gallery_scan.h)
+    const v16f acc = gal_rescore32((live ? p.gal + (size_t)(gi - p.idx_base) * K : p.zeros) + fh2 * 4, live ? 64 : 0, qrow + fh2 * 4, chunks);
     if (fr == 0) {                                            // column 0: rows 8 * (e >> 2) + 4 * fh2 + (e & 3)
 #pragma unroll
         for (int e = 0; e < 16; ++e) cs[8 * (e >> 2) + 4 * fh2 + (e & 3)] = (acc[e] + 1.0f) / 2.0f;

@@ -1,6 +1,6 @@
 // gallery_host.cpp — the host side of fh::Gallery (engine.h): the row store (one capacity, the per-row columns that share it), the
-// maintenance calls written on its three operations (reserve, append, compact), and the two queries over the one fp32 scan sequence
-// (gallery_scan.h: launch_gallery_scan) and the F16_RERANK path (gallery_f16.hip).
+// maintenance calls written on its three operations (reserve, append, compact), the two queries over the one fp32 scan sequence
+// (gallery_scan.h: launch_gallery_scan) and the F16_RERANK path (gallery_f16.hip), and the threshold search (gallery_range.hip).
 #include "engine.h"
 
 #include "gallery_scan.h"
@@ -385,18 +385,36 @@ void Gallery::topk_f16(const float* q, int Q, int k, float* out_score, int* out_
     FH_HIP(hipGetLastError());
 }
 
+// queries as the GEMM's N operand: whole 64-row tiles, zero rows behind Q (only that tail is cleared)
+void Gallery::pack_queries(const float* q, int Q, hipStream_t s) {
+    const int qrows = (Q + 63) / 64 * 64;
+    qpack_.ensure((size_t)qrows * dim_ * sizeof(float));
+    if (qrows > Q) FH_HIP(hipMemsetAsync(qpack_.as<float>() + (size_t)Q * dim_, 0, (size_t)(qrows - Q) * dim_ * sizeof(float), s));
+    FH_HIP(hipMemcpyAsync(qpack_.p, q, (size_t)Q * dim_ * sizeof(float), hipMemcpyDeviceToDevice, s));
+}
+
+// The threshold search: the scan with the hit bitmap as its epilogue, counts, lists (gallery_range.hip) — on the fp32 rows always, so
+// the answer is the same in either scan mode and the F16_RERANK counters stay as they are.
+void Gallery::range_dev(const float* q, const unsigned* masks, int Q, float thr, int cap, long long* counts, float* out_score, int* out_row,
+                        int* out_id, hipStream_t s) {
+    if (dim_ % 64) throw std::runtime_error("gallery: dim must be a multiple of 64");
+    if (out_id) need_labelled("fh_gallery_range_dev with d_ids");
+    if (masks && n_ > 0) need_tags();
+    pack_queries(q, Q, s);
+    rg_hits_.ensure(gallery_range_hits_bytes(n_, Q));
+    rg_units_.ensure(gallery_range_units_bytes(n_, Q));
+    launch_gallery_range(rows_.as<float>(), n_, dim_, qpack_.as<float>(), tags_.as<unsigned>(), masks, Q, base_, thr, cap,
+                         rg_hits_.as<unsigned>(), rg_units_.as<int>(), out_id ? ids_.as<int>() : nullptr, counts, out_score, out_row, out_id, s);
+    FH_HIP(hipGetLastError());
+}
+
 // ONE pass over the gallery: dot products stay in the MFMA accumulators, per-workgroup top-k lists come out and are merged
 // (gallery_scan.h).  masks: only each query's admitted rows; ids: lists of identities (out_id; out_row may be null); qcount (device,
 // the F16_RERANK fall-back): only that many queries are live, and the scan runs unseeded.
 void Gallery::scan_f32(const float* q, const unsigned* masks, int Q, int k, bool ids, float* out_score, int* out_id, int* out_row, hipStream_t s,
                        const int* qcount) {
     if (masks && n_ > 0) need_tags();
-    if (q) {                                                     // queries as the GEMM's N operand: whole 64-row tiles, zero rows behind Q
-        const int qrows = (Q + 63) / 64 * 64;                    // (only that tail is cleared)
-        qpack_.ensure((size_t)qrows * dim_ * sizeof(float));
-        if (qrows > Q) FH_HIP(hipMemsetAsync(qpack_.as<float>() + (size_t)Q * dim_, 0, (size_t)(qrows - Q) * dim_ * sizeof(float), s));
-        FH_HIP(hipMemcpyAsync(qpack_.p, q, (size_t)Q * dim_ * sizeof(float), hipMemcpyDeviceToDevice, s));
-    }
+    if (q) pack_queries(q, Q, s);
     // part planes [gallery_parts][Q][k] and seed planes [Q][k] (ids: with their identity planes)
     const int parts = n_ > 0 ? gallery_parts(n_, Q, nullptr) : 0;
     const size_t plane = (size_t)std::max(parts, 1) * Q * k, seed = (size_t)Q * k;

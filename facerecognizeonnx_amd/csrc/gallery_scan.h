@@ -1,7 +1,8 @@
 // gallery_scan.h — the streaming 1:N scan of the gallery: ONE body, instantiated as gallery_topk_kernel (gallery.hip: fp32 rows, lists of
 // rows), gallery_topk_ids_kernel (gallery_ids.hip: fp32 rows, lists of identities), their tagged twins (gallery_tags.hip) and
-// gal16_scan_kernel (gallery_f16.hip: fp16 rows, 32-deep candidate lists); with it the ranking predicate, the kernel arguments, the
-// two-pass launcher all of them share and the one launcher of the four fp32 scans.
+// gal16_scan_kernel (gallery_f16.hip: fp16 rows, 32-deep candidate lists) and gallery_range_kernel (gallery_range.hip: fp32 rows, no
+// lists at all — a bit per (row, query) whose score is above a threshold); with it the ranking predicate, the kernel arguments, the
+// two-pass launcher the top-k scans share, the one launcher of the four fp32 top-k scans and the re-score of single (row, query) pairs.
 //
 // One kernel streams the gallery ONCE: the dot products live only in MFMA accumulators, never in memory.
 //   * The scan is an HBM stream with NO reuse on the gallery side: what limits it is bytes in flight (Little: ~50 KB per CU for 5 TB/s at
@@ -29,6 +30,10 @@
 //     accumulation: 8 MFMAs per 32x32 block and chunk where the f32 kernels issue 32.  Its lists are KD = 32 deep and k IS the list
 //     depth (KFIX), so the threshold entry is ls[31] instead of a select by k - 1.  It is launched at one workgroup per CU (the 32-deep
 //     lists + two row chunks in flight need more than the 256 registers of two waves per SIMD: 104 bytes of spills at (256, 2)).
+//   * RANGE (gallery_range_kernel): the same K loop, then an epilogue of its own INSTEAD of the lists, queues, thresholds and seeds —
+//     every lane turns its 2 x 16 accumulators into hit bits ((acc + 1) / 2 > thr, row < G, tag & mask) and the wave stores one 32-bit
+//     word per (32-row block, query).  No LDS beyond the query chunks, no barrier beyond the K loop's, no atomics; masks are optional at
+//     run time (p.qmask), every tile is multiplied and a workgroup's tiles are the contiguous run.
 //
 // Round 3, measured and NOT kept (1 M x 512, Q = 64, k = 16; this kernel: 0.82 ms per call = seed pass 88 us + scan ~700 + two merges
 // 39 us each): a scan with the whole 64-query tile RESIDENT in LDS (128 KB, one 8-wave workgroup per CU, no per-chunk barrier, query
@@ -83,6 +88,9 @@ struct GalArgs {
     const unsigned* tile_or;  // OR of the tags of each 128-row tile, by position [row tiles of the WHOLE gallery]
     unsigned long long* tag_ctr;   // [2]: (workgroup, row tile) visits multiplied / skipped, one atomic add each per workgroup
     int tag_skip;             // 0: every tile is multiplied (fh_debug_tag_skip)
+    // RANGE (gallery_range.hip) — behind the TAGS fields in turn; it also reads tags / qmask (qmask null: every row admitted)
+    float range_thr;          // row r is a hit of query q iff (acc + 1) / 2 > range_thr (and r < G, and admitted)
+    unsigned* hits;           // [row_tiles * 4][tiles_n * 64]: bit b of word [m][q] = row 32 m + b is a hit of query q
 };
 
 // ---- host side (gallery.hip); they sit here and not in kernels.h because they speak of GalArgs
@@ -115,6 +123,28 @@ void launch_gallery_scan(GalArgs a, long G, float* seed_s, int* seed_i, int* see
 
 __device__ __forceinline__ bool gal_better(float s1, int i1, float s2, int i2) { return s1 > s2 || (s1 == s2 && i1 < i2); }
 
+// The fp32 scan's score of up to 32 single (row, query) pairs, by one wave: the multiply of gallery_scan_body with the query in EVERY
+// column of B — lane (row fr, half fh2) holds k = kc * 64 + (2s + fh2) * 4 + e of its row; loop kc, s = 0..7, e = 0..3; accumulator from
+// 0.  One output element depends only on its row, its column and that sequence, so (acc + 1) / 2 has the bits the scan gives the pair.
+// a_ptr: the lane's row + fh2 * 4 (a dead lane: the zero line, a_step 0; else a_step 64); b_ptr: the query + fh2 * 4.  Every column of
+// the result is the same: element e of a lane is row 8 * (e >> 2) + 4 * fh2 + (e & 3).
+__device__ __forceinline__ v16f gal_rescore32(const float* a_ptr, int a_step, const float* b_ptr, int chunks) {
+    v16f acc;
+#pragma unroll
+    for (int e = 0; e < 16; ++e) acc[e] = 0.f;
+    for (int kc = 0; kc < chunks; ++kc) {
+        v4f x[8], w[8];
+#pragma unroll
+        for (int s = 0; s < 8; ++s) { x[s] = *reinterpret_cast<const v4f*>(a_ptr + s * 8); w[s] = *reinterpret_cast<const v4f*>(b_ptr + s * 8); }
+        a_ptr += a_step; b_ptr += 64;
+#pragma unroll
+        for (int s = 0; s < 8; ++s)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(x[s][e], w[s][e], acc, 0, 0, 0);
+    }
+    return acc;
+}
+
 // IDS: thread q's list holds at most ONE entry per identity — the identity's best row seen so far — so its k-th entry is the k-th
 // DISTINCT identity and a valid admission threshold: k identities already have a row at least that good, and a listed identity only
 // ever improves.  A row's id is fetched (4-byte gather) only when the row passes the threshold, and travels through the slot queue
@@ -132,9 +162,11 @@ __device__ __forceinline__ bool gal_better(float s1, int i1, float s2, int i2) {
 // the tiles left over spread evenly, a TAGS workgroup walks the row tiles strided by the number of parts (see the tile loop).
 //
 // T: element type of rows and queries (float | _Float16); KD: list depth; KFIX: k is KD (else the runtime p.k <= KD).
-template <typename T, int KD, bool KFIX, bool IDS, bool TAGS = false>
+// RANGE: no lists — the epilogue is the hit bitmap (KD, KFIX, IDS and TAGS play no part; see the header).
+template <typename T, int KD, bool KFIX, bool IDS, bool TAGS = false, bool RANGE = false>
 __device__ __forceinline__ void gallery_scan_body(const GalArgs& p) {
     constexpr bool F16 = std::is_same<T, _Float16>::value;
+    static_assert(!RANGE || (!F16 && !IDS && !TAGS), "the threshold scan reads fp32 rows and takes its masks at run time");
     constexpr int BM = GAL_BM, BN = GAL_BN, TN = BN / 32;
     constexpr int EC = 16 / (int)sizeof(T), CD = 16 * EC;     // elements per 16-byte column, chunk depth (16 columns)
     __shared__ v4f ldsq[2][BN * 16];                          // query chunk [64 rows][CD k], 16-byte column XOR (row & 15)
@@ -157,7 +189,7 @@ __device__ __forceinline__ void gallery_scan_body(const GalArgs& p) {
     }
     const int tile_n = t % p.tiles_n, part = t / p.tiles_n;
     const int n0 = tile_n * BN;
-    if constexpr (!F16) {                                     // (the fp16 scan is never the compacted fall-back: no test, its scalar side stays lean)
+    if constexpr (!F16 && !RANGE) {                           // (the fp16 scan is never the compacted fall-back: no test, its scalar side stays lean)
         if (p.qcount && n0 >= *p.qcount) return;              // (workgroup-uniform, before any barrier)
     }
     const int K = p.dim, chunks = K / CD, k = KFIX ? KD : p.k;
@@ -172,7 +204,7 @@ __device__ __forceinline__ void gallery_scan_body(const GalArgs& p) {
 #pragma unroll
         for (int i = 0; i < KD; ++i) ld[i] = -1;
     }
-    if (tid < BN) {
+    if (!RANGE && tid < BN) {
         float ts = -INFINITY; int ti = INT_MAX;                   // (-inf, INT_MAX): below every real entry, whatever the rows' norms (compareFaces does not clamp, face_recognizer.cpp:320-334)
         if (p.seed_i && n0 + tid < p.Q) {
             const size_t o = (size_t)(n0 + tid) * k + (k - 1);
@@ -180,7 +212,7 @@ __device__ __forceinline__ void gallery_scan_body(const GalArgs& p) {
         }
         cnt[tid] = 0; tau_s[tid] = ts; tau_i[tid] = ti;
     }
-    if (tid == 0) overflow = 0;
+    if (!RANGE && tid == 0) overflow = 0;
     unsigned U = 0;                                           // TAGS: OR of the tile's 64 masks (every wave forms it: no barrier needed)
     int n_scan = 0, n_skip = 0;
     if constexpr (TAGS) {
@@ -291,8 +323,38 @@ __device__ __forceinline__ void gallery_scan_body(const GalArgs& p) {
             __syncthreads();
             multiply(xa[0], 0);
         }
-        // ---- top-k epilogue
         const long rbase = m0 + wid * 32 + 4 * fh2;
+        // ---- threshold epilogue: bit 4 * fh2 + 8 * (e >> 2) + (e & 3) of the lane's word = its row of that position in the wave's 32-row
+        // block; the lane pair (fr, fr ^ 32) holds the two interleaved halves of one query's word, so after one exchange per query block
+        // lane l owns the whole word of query n0 + l and the wave stores 64 words = 256 contiguous bytes of row [block] of the bitmap
+        if constexpr (RANGE) {
+            static_assert(TN == 2, "one query block per lane half");
+            unsigned tg[16];                               // the tags of the lane's 16 rows (rows behind G, and a call without masks: unused)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                const long row = rbase + 8 * (e >> 2) + (e & 3);
+                tg[e] = p.qmask && row < p.G ? p.tags[row] : 0xFFFFFFFFu;
+            }
+            unsigned word[TN];
+#pragma unroll
+            for (int j = 0; j < TN; ++j) {
+                const int qn = n0 + j * 32 + fr;
+                const unsigned mq = qn >= p.Q ? 0u : p.qmask ? p.qmask[qn] : 0xFFFFFFFFu;     // (queries behind Q: no hits)
+                unsigned bits = 0;
+#pragma unroll
+                for (int e = 0; e < 16; ++e) {
+                    const long row = rbase + 8 * (e >> 2) + (e & 3);
+                    const float sc = (acc[j][e] + 1.0f) / 2.0f;
+                    const bool hit = row < p.G && (tg[e] & mq) != 0 && sc > p.range_thr;      // (false for a NaN score)
+                    bits |= (hit ? 1u : 0u) << (4 * fh2 + 8 * (e >> 2) + (e & 3));
+                }
+                word[j] = bits | (unsigned)__shfl_xor((int)bits, 32);
+            }
+            // word [32-row block of the gallery][query, padded to whole tiles]: every word of the bitmap is written by exactly one lane
+            p.hits[((size_t)rt * 4 + wid) * ((size_t)p.tiles_n * BN) + n0 + lane] = fh2 ? word[1] : word[0];
+            continue;
+        }
+        // ---- top-k epilogue
         auto push = [&](int g_lo, int g_hi) {
 #pragma unroll
             for (int j = 0; j < TN; ++j) {
@@ -384,7 +446,7 @@ __device__ __forceinline__ void gallery_scan_body(const GalArgs& p) {
             insert();
         }
     }
-    if (tid < BN && n0 + tid < p.Q) {
+    if (!RANGE && tid < BN && n0 + tid < p.Q) {
         const size_t o = ((size_t)part * p.Q + n0 + tid) * k;
 #pragma unroll
         for (int pos = 0; pos < KD; ++pos)

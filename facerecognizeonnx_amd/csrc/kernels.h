@@ -414,6 +414,19 @@ void launch_gallery16_gather(const float* q, int Q, int dim, const int* fb_count
 void launch_gallery16_scatter(const float* fb_score, const int* fb_idx_out, int Q, int k, const int* fb_count, const int* fb_idx, float* out_score,
                               int* out_idx, hipStream_t s);
 
+// gallery_range.hip — exact threshold search (fh_gallery_range_dev; the rule: range_plan.h): the scan of gallery_scan.h with the hit
+// bitmap as its epilogue, popcounts, then per query the best `cap` hits re-scored from the fp32 rows and sorted.  qpacked
+// [ceil64(Q)][dim], zero rows behind Q; masks (device [Q]) with tags (device [G]), or both null; hits / unit_cnt: scratch of
+// gallery_range_hits_bytes / gallery_range_units_bytes (G, Q), written before they are read: never cleared.  counts [Q]; out_* [Q][cap],
+// each may be null — all three null: counts only, no row is gathered; ids (needed with out_d): the id of every row.  G == 0: zero counts,
+// empty lists.  Q <= 0 launches nothing.
+constexpr int GAL_RANGE_UNIT = 256;                          // 32-row blocks per unit of the count planes (8192 rows)
+size_t gallery_range_hits_bytes(long G, int Q);
+size_t gallery_range_units_bytes(long G, int Q);
+void launch_gallery_range(const float* rows, long G, int dim, const float* qpacked, const unsigned* tags, const unsigned* masks, int Q,
+                          long idx_base, float thr, int cap, unsigned* hits, int* unit_cnt, const int* ids, long long* counts, float* out_s,
+                          int* out_i, int* out_d, hipStream_t s);
+
 // detect -> embed hand-off: first min(count,F) faces per frame, densely packed (n <= 4096 frames)
 void launch_select_faces(const FaceRec* det, const int* counts, int n, int per_frame, int F, FaceRec* faces, int* frame_of,
                          int* total, hipStream_t s);

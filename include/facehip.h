@@ -782,6 +782,42 @@ FH_API int fh_gallery_label_ids_tagged_dev(fh_gallery* g, const float* d_queries
 FH_API int fh_gallery_tag_stats(fh_gallery* g, long long* tiles_scanned, long long* tiles_skipped);
 FH_API int fh_tracker_set_stream_masks(fh_tracker* t, const uint32_t* masks_host /*[streams] or NULL*/);
 
+/* ---- threshold search: EVERY row above a score, not the best k <= 16.  "Which rows score above thr for this face, all of them?" — a
+ * person enrolled with 20 templates, a watchlist with several matching entries, every photo of one person in an archive, the rows a new
+ * enrolment would duplicate.  fh_gallery_pair_hist_dev / fh_roc_from_hist hand the caller a threshold; this is the query behind it.
+ *   hit       row r is a hit of query q iff it is ADMITTED (d_masks == NULL, or (tag[r] & mask[q]) != 0; a gallery whose tags were never
+ *             set carries FH_TAG_ALL), its mapped score is STRICTLY above the threshold — (dot + 1) / 2 > threshold in fp32, the test
+ *             of fh_gallery_label_dev and of the clustering — and its score is not a NaN (a NaN score is never a hit).
+ *   scores    the fp32 scan's, bit for bit: the bits fh_gallery_topk_dev returns for that pair, whichever scan mode the gallery is in
+ *             (the call always reads the fp32 rows and leaves fh_gallery_scan_stats and fh_gallery_tag_stats alone).
+ *   counts    d_counts[q] = the exact number of hits, NOT clipped by cap; written even when all three list pointers are NULL — the
+ *             count-only form, which gathers no row.
+ *   lists     row q of d_scores / d_indices / d_ids [nq][cap] holds the best min(count, cap) hits ranked as everywhere (score
+ *             descending, then global row index ascending); the slots behind them carry (-1.0f, -1, -1); nothing outside [nq][cap] is
+ *             written.  Indices are global (index_base + position).  d_ids = each listed row's identity id and needs a labelled gallery
+ *             (FH_ERR_STATE otherwise, unless the gallery is empty).  Any subset of the three may be NULL.  A count above cap still
+ *             yields the BEST cap hits, not the first.
+ *   limits    as fh_gallery_topk_dev: nq <= 256, dim % 64 == 0; 1 <= cap <= FH_RANGE_MAX_CAP.  FH_ERR_ARG before anything is launched
+ *             for a NULL handle, queries or d_counts, a NaN threshold, a bad cap, nq outside 0..256 or such a dim; nq == 0 returns 0.
+ *             An empty gallery gives counts of 0 and empty lists.  Returns nq.
+ *   execution asynchronous on `stream`; two calls with the same inputs produce identical bytes (no atomics, nothing timing-dependent).
+ *             Scratch lives in the handle and grows, synchronously, on the first call of a larger (nq, rows): the hit bitmap — one bit
+ *             per (row, query of a whole 64-query tile), at most ceil(G / 32) * 256 * 4 bytes = 1.6 % of the fp32 rows at dim 512 — and
+ *             its per-8192-row counts.  The scan costs what a top-k scan costs; the lists cost grows with the number of hits: a
+ *             threshold that admits a large share of the gallery is slow, and still right.
+ *   sharding  there is no sharded entry point: a shard's call already returns global indices, and the shards' hits concatenate.
+ *   range_from_scores   host only, no GPU, and the one definition of the rule: the same answer for ONE query from its row of n
+ *             precomputed mapped scores (global index = index_base + position).  tags == NULL: every row carries FH_TAG_ALL; the
+ *             unmasked query is tags == NULL with mask == FH_TAG_ALL.  *count = the hits; out_scores / out_indices [cap] (either may
+ *             be NULL) as above.  Returns the number of entries listed; FH_ERR_ARG — nothing written — for n < 0, NULL scores with
+ *             n > 0, a NULL count, a NaN threshold, a bad cap or an index beyond 31 bits. */
+#define FH_RANGE_MAX_CAP 1024
+FH_API int fh_gallery_range_dev(fh_gallery* g, const float* d_queries, const uint32_t* d_masks /* [nq] or NULL */, int nq, float threshold,
+                                int cap, long long* d_counts /* [nq] */, float* d_scores /* [nq][cap] or NULL */,
+                                int* d_indices /* [nq][cap] or NULL */, int* d_ids /* [nq][cap] or NULL */, void* stream);
+FH_API int fh_range_from_scores(const float* scores, long long n, long long index_base, const uint32_t* tags /* or NULL */, uint32_t mask,
+                                float threshold, int cap, long long* count, float* out_scores, int* out_indices);
+
 /* ---- measurement hooks (bench.py): per-launch HIP-event timing of the network kernels.
  * Tags 0..3 = conv_igemm tile configs (128x128, 256x64, 128x32, 64x64), 4 = depthwise / depthwise+pointwise,
  * 5 = other graph ops, 6 = conv stream-K fix-up, 7 = Winograd GEMM (its FLOPs = executed; bytes slot = the layer's
