@@ -4,11 +4,11 @@
 // The pair pass is the scan's arithmetic with another epilogue.  Tile layout and operand placement are gallery_scan_body's: the gallery
 // is the A operand — each wave streams ITS OWN 32 rows into registers, one 64-deep chunk ahead — and it is also the B operand: a 64-row
 // tile goes through the swizzled, double-buffered LDS image the scan keeps its queries in, loaded from the rows themselves.  Rows at or
-// beyond G read the zero line and are masked.  The K loop issues the same v_mfma_f32_32x32x2_f32 sequence in the same k order (k0 =
-// 64 kc + 8 s + e, k1 = k0 + 4), so an accumulator has the scan's bits; the chain is symmetric in its operands (a product commutes), so
-// s(i, j) and s(j, i) have the same bits and every unordered pair is evaluated ONCE: a workgroup owns one B tile (64 columns) and a
-// run of A tiles (128 rows each); A tiles wholly below the diagonal are skipped and `row < col` masks the straddling ones.  (A shared
-// K loop with the scan is a later refactor with its own ISA comparison; gallery_scan_body is not touched here.)
+// beyond G read the zero line and are masked.  The K loop IS the scan's — gal_tile_dot (gallery_scan.h), the one definition, called here
+// with a B fetch from four row pointers — so an accumulator has the scan's bits by construction (k0 = 64 kc + 8 s + e, k1 = k0 + 4); the
+// chain is symmetric in its operands (a product commutes), so s(i, j) and s(j, i) have the same bits and every unordered pair is
+// evaluated ONCE: a workgroup owns one B tile (64 columns) and a run of A tiles (128 rows each); A tiles wholly below the diagonal are
+// skipped and `row < col` masks the straddling ones.
 //
 // Launches of one call, all on the caller's stream:
 //   init      deg[i] = 0, parent[i] = i, best[i] = 0, info[0..3] = 0
@@ -110,10 +110,86 @@ __device__ __forceinline__ unsigned long long cluster_key(float s, int pos) {
     return ((unsigned long long)m << 32) | (unsigned)~pos;
 }
 
+// what an epilogue knows about the lane's two columns (one per 32-column block), for the whole run
+struct PairCols {
+    long col[2];
+    bool ok[2];                         // col < G
+    bool core[2];                       // link
+    int deg[2];                         // degree: edges counted at the column over the run
+    int id[2];                          // histogram
+};
+
+// The three epilogues of one tile: accumulator e of block j is (row wrow0 + 4 * fh2 + gal_acc_row(e), column c.col[j]).
+// degree: the A side needs a reduction across lanes — __ballot per accumulator position; lane r < 32 keeps row wrow0 + r's count
+__device__ __forceinline__ void pair_degree_tile(const ClusterArgs& p, const v16f (&acc)[2], PairCols& c, long wrow0, int lane, int fh2) {
+    const long rbase = wrow0 + 4 * fh2;
+    int row_deg = 0;                                       // lane r < 32: edges found at row wrow0 + r in this tile
+#pragma unroll
+    for (int e = 0; e < 16; ++e) {
+        const long row = rbase + gal_acc_row(e);
+        int lo = 0, hi = 0;
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const float sc = gal_score(acc[j][e]);
+            const bool edge = c.ok[j] && row < c.col[j] && sc > p.thr;      // (row < col < G)
+            c.deg[j] += edge ? 1 : 0;
+            const unsigned long long b = __ballot(edge);
+            lo += __popc((unsigned)b); hi += __popc((unsigned)(b >> 32));
+        }
+        const int r_lo = gal_acc_row(e);
+        row_deg += lane == r_lo ? lo : lane == r_lo + 4 ? hi : 0;
+    }
+    if (lane < 32 && row_deg > 0) atomicAdd(p.deg + wrow0 + lane, row_deg);    // (row_deg > 0 implies the row is below G)
+}
+
+__device__ __forceinline__ void pair_link_tile(const ClusterArgs& p, const v16f (&acc)[2], const PairCols& c, long wrow0, int fr, int fh2) {
+    const long arow = wrow0 + fr;
+    const unsigned row_core = (unsigned)__ballot(arow < p.G && p.deg[arow < p.G ? arow : 0] + 1 >= p.min_pts);   // bit r: row wrow0 + r
+#pragma unroll
+    for (int e = 0; e < 16; ++e) {
+        const int r = gal_acc_row(e) + 4 * fh2;
+        const long row = wrow0 + r;
+        const bool rc = (row_core >> r) & 1u;
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const float sc = gal_score(acc[j][e]);
+            if (c.ok[j] && row < c.col[j] && sc > p.thr) {
+                if (rc && c.core[j]) cluster_union(p.parent, (int)row, (int)c.col[j]);
+                else if (rc) atomicMax(p.best + c.col[j], cluster_key(sc, (int)row));
+                else if (c.core[j]) atomicMax(p.best + row, cluster_key(sc, (int)c.col[j]));
+            }
+        }
+    }
+}
+
+// lane r (and r + 32) holds the id of row wrow0 + r; an accumulator's row id comes by shuffle.  Every live pair is one LDS atomic: bin
+// `hist_bin(sc)` of its class' plane, or the class' NaN counter.
+__device__ __forceinline__ void pair_hist_tile(const ClusterArgs& p, const v16f (&acc)[2], const PairCols& c, long wrow0, int fr, int fh2) {
+    unsigned* h = pair_hist_lds();
+    const long arow = wrow0 + fr;
+    const int my_id = arow < p.G ? p.ids[arow] : 0;
+#pragma unroll
+    for (int e = 0; e < 16; ++e) {
+        const int r = gal_acc_row(e) + 4 * fh2;
+        const long row = wrow0 + r;
+        const int row_id = __shfl(my_id, r);
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const float sc = gal_score(acc[j][e]);
+            if (c.ok[j] && row < c.col[j]) {                            // (row < col < G)
+                const int b = hist_bin(sc);
+                const int cls = row_id == c.id[j] ? 0 : 1;
+                atomicAdd(&h[b >= 0 ? cls * kHistBins + b : 2 * kHistBins + cls], 1u);
+            }
+        }
+    }
+}
+
+// setup -> per A tile: gal_tile_dot (gallery_scan.h: THE K loop, with the B chunks fetched from gallery rows) + the mode's epilogue -> flush
 template <int MODE>
 __device__ __forceinline__ void cluster_pair_body(const ClusterArgs& p) {
-    constexpr bool LINK = MODE == PAIR_LINK;
     constexpr int BM = GAL_BM, BN = GAL_BN, TN = BN / 32, CD = 64;
+    static_assert(TN == 2, "PairCols holds one column per 32-column block");
     __shared__ v4f ldsq[2][BN * 16];                          // B chunk [64 rows][64 k], 16-byte column XOR (row & 15)
     __shared__ int colcnt[BN];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -133,163 +209,43 @@ __device__ __forceinline__ void cluster_pair_body(const ClusterArgs& p) {
 
     // B loader: pass i fills rows i*16 + (tid >> 4), slot tid & 15 <- source 16-byte column (tid & 15) ^ (row & 15)
     const int qrow = tid >> 4;
-    const int bcol = ((tid & 15) ^ (qrow & 15)) * 4;
-    const float* b_base[4];
-    int b_step[4];
+    GalSrc<float> b_row[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const long brow = n0 + qrow + 16 * i;
-        const bool live = brow < p.G;
-        b_base[i] = (live ? p.gal + (size_t)brow * K : p.zeros) + bcol;
-        b_step[i] = live ? CD : 0;
+        b_row[i] = gal_row_or_zeros(brow < p.G, p.gal, (size_t)brow, K, p.zeros, ((tid & 15) ^ (qrow & 15)) * 4, CD);
     }
-    const int fsw = fr & 15;
 
-    // what the epilogue knows about this lane's columns
-    long col[TN];
-    bool col_ok[TN];
-    bool col_core[TN];
-    int col_deg[TN];
-    int col_id[TN];
+    PairCols c;
 #pragma unroll
     for (int j = 0; j < TN; ++j) {
-        col[j] = n0 + j * 32 + fr;
-        col_ok[j] = col[j] < p.G;
-        col_deg[j] = 0;
-        col_core[j] = false;
-        col_id[j] = 0;
-        if constexpr (LINK) col_core[j] = col_ok[j] && p.deg[col[j]] + 1 >= p.min_pts;
-        if constexpr (MODE == PAIR_HIST) col_id[j] = col_ok[j] ? p.ids[col[j]] : 0;
+        c.col[j] = n0 + j * 32 + fr;
+        c.ok[j] = c.col[j] < p.G;
+        c.deg[j] = 0;
+        c.core[j] = false;
+        c.id[j] = 0;
+        if constexpr (MODE == PAIR_LINK) c.core[j] = c.ok[j] && p.deg[c.col[j]] + 1 >= p.min_pts;
+        if constexpr (MODE == PAIR_HIST) c.id[j] = c.ok[j] ? p.ids[c.col[j]] : 0;
     }
 
     for (int rt = rt0; rt < rt1; ++rt) {
         const long m0 = (long)rt * BM;
         const long myrow = m0 + wid * 32 + fr;
-        const bool live = myrow < p.G;
-        const float* a_ptr = (live ? p.gal + (size_t)myrow * K : p.zeros) + fh2 * 4;
-        const int a_step = live ? CD : 0;
+        const GalSrc<float> a = gal_row_or_zeros(myrow < p.G, p.gal, (size_t)myrow, K, p.zeros, fh2 * 4, CD);
         const float* b_src[4];
 #pragma unroll
-        for (int i = 0; i < 4; ++i) b_src[i] = b_base[i];
-        v4f xa[2][8];
-        auto load_a = [&](v4f (&x)[8]) {                      // 16-byte column 2s + fh2 of the chunk
+        for (int i = 0; i < 4; ++i) b_src[i] = b_row[i].ptr;
+        auto fetch_b = [&](v4f (&qv)[4]) {
 #pragma unroll
-            for (int s = 0; s < 8; ++s) x[s] = *reinterpret_cast<const v4f*>(a_ptr + s * 8);
-            a_ptr += a_step;
+            for (int i = 0; i < 4; ++i) { qv[i] = *reinterpret_cast<const v4f*>(b_src[i]); b_src[i] += b_row[i].step; }
         };
         v16f acc[TN];
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[j][e] = 0.f;
-        auto multiply = [&](const v4f (&x)[8], int buf) {
-            const v4f* Wt = ldsq[buf] + fr * 16;
-#pragma unroll
-            for (int s = 0; s < 8; ++s) {
-                const int c = (2 * s + fh2) ^ fsw;
-                v4f w[TN];
-#pragma unroll
-                for (int j = 0; j < TN; ++j) w[j] = Wt[j * 32 * 16 + c];
-#pragma unroll
-                for (int e = 0; e < 4; ++e)
-#pragma unroll
-                    for (int j = 0; j < TN; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(x[s][e], w[j][e], acc[j], 0, 0, 0);
-            }
-        };
-        // B chunk: global -> registers -> LDS, issued before the row loads (see gallery_scan_body for why not LDS-DMA)
-        v4f qv[4];
-        auto fetch_b = [&]() {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) { qv[i] = *reinterpret_cast<const v4f*>(b_src[i]); b_src[i] += b_step[i]; }
-        };
-        auto store_b = [&](int buf) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) ldsq[buf][i * 256 + tid] = qv[i];
-        };
         __syncthreads();                                   // the previous tile's last multiply is done with ldsq
-        fetch_b();
-        load_a(xa[0]);
-        store_b(0);
-        int kc = 0;
-        for (; kc + 2 <= chunks; kc += 2) {
-            __syncthreads();
-            fetch_b();
-            load_a(xa[1]);
-            __builtin_amdgcn_sched_barrier(0);
-            multiply(xa[0], 0);
-            store_b(1);
-            __syncthreads();
-            if (kc + 2 < chunks) { fetch_b(); load_a(xa[0]); }
-            __builtin_amdgcn_sched_barrier(0);
-            multiply(xa[1], 1);
-            if (kc + 2 < chunks) store_b(0);
-        }
-        if (kc < chunks) {                                 // odd number of chunks
-            __syncthreads();
-            multiply(xa[0], 0);
-        }
-
-        // ---- epilogue: accumulator e of block j is (row rbase + 8 * (e >> 2) + (e & 3), column col[j])
-        const long wrow0 = m0 + wid * 32;
-        const long rbase = wrow0 + 4 * fh2;
-        if constexpr (MODE == PAIR_DEGREE) {
-            int row_deg = 0;                               // lane r < 32: edges found at row wrow0 + r in this tile
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const long row = rbase + 8 * (e >> 2) + (e & 3);
-                int lo = 0, hi = 0;
-#pragma unroll
-                for (int j = 0; j < TN; ++j) {
-                    const float sc = (acc[j][e] + 1.0f) / 2.0f;
-                    const bool edge = col_ok[j] && row < col[j] && sc > p.thr;      // (row < col < G)
-                    col_deg[j] += edge ? 1 : 0;
-                    const unsigned long long b = __ballot(edge);
-                    lo += __popc((unsigned)b); hi += __popc((unsigned)(b >> 32));
-                }
-                const int r_lo = 8 * (e >> 2) + (e & 3);
-                row_deg += lane == r_lo ? lo : lane == r_lo + 4 ? hi : 0;
-            }
-            if (lane < 32 && row_deg > 0) atomicAdd(p.deg + wrow0 + lane, row_deg);    // (row_deg > 0 implies the row is below G)
-        } else if constexpr (MODE == PAIR_LINK) {
-            const long arow = wrow0 + fr;
-            const unsigned row_core = (unsigned)__ballot(arow < p.G && p.deg[arow < p.G ? arow : 0] + 1 >= p.min_pts);   // bit r: row wrow0 + r
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const int r = 8 * (e >> 2) + (e & 3) + 4 * fh2;
-                const long row = wrow0 + r;
-                const bool rc = (row_core >> r) & 1u;
-#pragma unroll
-                for (int j = 0; j < TN; ++j) {
-                    const float sc = (acc[j][e] + 1.0f) / 2.0f;
-                    if (col_ok[j] && row < col[j] && sc > p.thr) {
-                        if (rc && col_core[j]) cluster_union(p.parent, (int)row, (int)col[j]);
-                        else if (rc) atomicMax(p.best + col[j], cluster_key(sc, (int)row));
-                        else if (col_core[j]) atomicMax(p.best + row, cluster_key(sc, (int)col[j]));
-                    }
-                }
-            }
-        } else {
-            // lane r (and r + 32) holds the id of row wrow0 + r; an accumulator's row id comes by shuffle.  Every live pair is one LDS
-            // atomic: bin `hist_bin(sc)` of its class' plane, or the class' NaN counter.
-            unsigned* h = pair_hist_lds();
-            const long arow = wrow0 + fr;
-            const int my_id = arow < p.G ? p.ids[arow] : 0;
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const int r = 8 * (e >> 2) + (e & 3) + 4 * fh2;
-                const long row = wrow0 + r;
-                const int row_id = __shfl(my_id, r);
-#pragma unroll
-                for (int j = 0; j < TN; ++j) {
-                    const float sc = (acc[j][e] + 1.0f) / 2.0f;
-                    if (col_ok[j] && row < col[j]) {                    // (row < col < G)
-                        const int b = hist_bin(sc);
-                        const int cls = row_id == col_id[j] ? 0 : 1;
-                        atomicAdd(&h[b >= 0 ? cls * kHistBins + b : 2 * kHistBins + cls], 1u);
-                    }
-                }
-            }
-        }
+        gal_tile_dot<float>(ldsq, a.ptr, a.step, chunks, tid, fr, fh2, fetch_b, acc);
+        const long wrow0 = m0 + wid * 32;                  // the wave's 32-row block
+        if constexpr (MODE == PAIR_DEGREE) pair_degree_tile(p, acc, c, wrow0, lane, fh2);
+        else if constexpr (MODE == PAIR_LINK) pair_link_tile(p, acc, c, wrow0, fr, fh2);
+        else pair_hist_tile(p, acc, c, wrow0, fr, fh2);
     }
     if constexpr (MODE == PAIR_HIST) {
         // A run of t tiles adds at most t * 128 * 64 = t * 8192 to one 32-bit counter; the launcher keeps t <= 2^18 (automatic runs are at
@@ -299,14 +255,14 @@ __device__ __forceinline__ void cluster_pair_body(const ClusterArgs& p) {
         unsigned long long* dst = p.hist + (size_t)(blockIdx.x % (unsigned)p.copies) * kHistSlots;
         __syncthreads();
         for (int i = tid; i < kHistSlots; i += 256) {
-            const unsigned c = h[i];
-            if (c) atomicAdd(dst + i, (unsigned long long)c);
+            const unsigned cnt = h[i];
+            if (cnt) atomicAdd(dst + i, (unsigned long long)cnt);
         }
     }
     if constexpr (MODE == PAIR_DEGREE) {
 #pragma unroll
         for (int j = 0; j < TN; ++j)
-            if (col_deg[j] > 0) atomicAdd(&colcnt[j * 32 + fr], col_deg[j]);
+            if (c.deg[j] > 0) atomicAdd(&colcnt[j * 32 + fr], c.deg[j]);
         __syncthreads();
         if (tid < BN && colcnt[tid] > 0) atomicAdd(p.deg + n0 + tid, colcnt[tid]);     // (a count > 0 implies the column is below G)
     }

@@ -131,10 +131,11 @@ __global__ __launch_bounds__(64) void gal16_rescore_kernel(const Gal16Rescore p)
     const bool live = gi >= 0;
     // the fp32 score of candidate fr: gallery_topk_kernel's multiply, with the query in every column of B
     // (gal_rescore32, gallery_scan.h)
-    const v16f acc = gal_rescore32((live ? p.gal + (size_t)(gi - p.idx_base) * K : p.zeros) + fh2 * 4, live ? 64 : 0, qrow + fh2 * 4, chunks);
-    if (fr == 0) {                                            // column 0: rows 8 * (e >> 2) + 4 * fh2 + (e & 3)
+    const GalSrc<float> a = gal_row_or_zeros(live, p.gal, (size_t)(gi - p.idx_base), K, p.zeros, fh2 * 4, 64);
+    const v16f acc = gal_rescore32(a.ptr, a.step, qrow + fh2 * 4, chunks);
+    if (fr == 0) {                                            // column 0: rows gal_acc_row(e) + 4 * fh2
 #pragma unroll
-        for (int e = 0; e < 16; ++e) cs[8 * (e >> 2) + 4 * fh2 + (e & 3)] = (acc[e] + 1.0f) / 2.0f;
+        for (int e = 0; e < 16; ++e) cs[gal_acc_row(e) + 4 * fh2] = gal_score(acc[e]);
     }
     if (lane < G16_KC) ci[lane] = gi;
     // query norms (the same f16 conversion the scan's queries went through)

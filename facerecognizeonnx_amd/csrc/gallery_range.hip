@@ -98,12 +98,13 @@ __global__ __launch_bounds__(256) void range_list_kernel(const RangeList p) {
             const int c = g * 32 + fr;
             const bool live = c < npend;
             const int pos = live ? pend[c] : 0;
-            const v16f acc = gal_rescore32((live ? p.gal + (size_t)pos * K : p.zeros) + fh2 * 4, live ? 64 : 0, qrow + fh2 * 4, chunks);
-            if (fr == 0) {                                                 // column 0: candidates 8 * (e >> 2) + 4 * fh2 + (e & 3) of the group
+            const GalSrc<float> a = gal_row_or_zeros(live, p.gal, (size_t)pos, K, p.zeros, fh2 * 4, 64);
+            const v16f acc = gal_rescore32(a.ptr, a.step, qrow + fh2 * 4, chunks);
+            if (fr == 0) {                                                 // column 0: candidates gal_acc_row(e) + 4 * fh2 of the group
 #pragma unroll
                 for (int e = 0; e < 16; ++e) {
-                    const int r = g * 32 + 8 * (e >> 2) + 4 * fh2 + (e & 3);
-                    if (r < npend) ss[nbest + r] = (acc[e] + 1.0f) / 2.0f;
+                    const int r = g * 32 + gal_acc_row(e) + 4 * fh2;
+                    if (r < npend) ss[nbest + r] = gal_score(acc[e]);
                 }
             }
             if (live && fh2 == 0) si[nbest + c] = (int)(p.idx_base + pos);

@@ -3,6 +3,8 @@
 // gal16_scan_kernel (gallery_f16.hip: fp16 rows, 32-deep candidate lists) and gallery_range_kernel (gallery_range.hip: fp32 rows, no
 // lists at all — a bit per (row, query) whose score is above a threshold); with it the ranking predicate, the kernel arguments, the
 // two-pass launcher the top-k scans share, the one launcher of the four fp32 top-k scans and the re-score of single (row, query) pairs.
+// The multiply of one (128-row tile, 64-row tile) pair — THE K loop — is gal_tile_dot below, written once: this body calls it with the
+// query tile as B, cluster_pair_body (gallery_cluster.hip: DBSCAN's degree / link passes and the pair histogram) with gallery rows as B.
 //
 // One kernel streams the gallery ONCE: the dot products live only in MFMA accumulators, never in memory.
 //   * The scan is an HBM stream with NO reuse on the gallery side: what limits it is bytes in flight (Little: ~50 KB per CU for 5 TB/s at
@@ -10,7 +12,7 @@
 //     ds_read_b128 would deliver: lane (row fr, half fh2) takes 16 bytes at k = (2s + fh2) * 4 of its row; the s-steps of a 128-byte line
 //     are consecutive instructions — in 64-deep chunks, one chunk (8 loads, 32 VGPRs) ahead of the one being multiplied: 8 waves x 8 KB in
 //     flight per CU, no LDS traffic and no barrier on the gallery side.  Only the 64 queries of the tile (shared by the four waves) go
-//     through LDS: 16 KB per chunk, through registers (see the K loop), double buffered, 16-byte column XOR-swizzled by (row & 15) on the
+//     through LDS: 16 KB per chunk, through registers (see gal_tile_dot), double buffered, 16-byte column XOR-swizzled by (row & 15) on the
 //     source side.
 //   * v_mfma_f32_32x32x2_f32 with the GALLERY fragment as A and the QUERY fragment as B: a lane ends up with ONE query (column) and 16
 //     gallery rows of it per 32x32 block.  Workgroup tile: 128 gallery rows x 64 queries.
@@ -123,11 +125,108 @@ void launch_gallery_scan(GalArgs a, long G, float* seed_s, int* seed_i, int* see
 
 __device__ __forceinline__ bool gal_better(float s1, int i1, float s2, int i2) { return s1 > s2 || (s1 == s2 && i1 < i2); }
 
-// The fp32 scan's score of up to 32 single (row, query) pairs, by one wave: the multiply of gallery_scan_body with the query in EVERY
+// ---- what belongs with the K loop: the three small maps every epilogue of it uses
+// accumulator element e of a lane is row 8 * (e >> 2) + (e & 3) (+ 4 * fh2) of the wave's 32-row block
+__device__ __forceinline__ constexpr int gal_acc_row(int e) { return 8 * (e >> 2) + (e & 3); }
+// the mapped score (compareFaces' (cos + 1) / 2; a division, as there)
+__device__ __forceinline__ float gal_score(float acc) { return (acc + 1.0f) / 2.0f; }
+// where a lane streams a row from: the live row, or the zero line with step 0 (dead rows multiply zeros and are masked by the caller)
+template <typename T> struct GalSrc { const T* ptr; int step; };
+template <typename T>
+__device__ __forceinline__ GalSrc<T> gal_row_or_zeros(bool live, const T* rows, size_t row, int K, const T* zeros, int off, int step) {
+    return {(live ? rows + row * K : zeros) + off, live ? step : 0};
+}
+
+// THE K loop of the gallery family: acc = (the wave's 32 rows of a 128-row A tile) x (a 64-row B tile), over `chunks` chunks of 16
+// 16-byte columns (64 deep in fp32, 128 in fp16).  gallery_scan_body (B = the query tile) and cluster_pair_body (gallery_cluster.hip: B =
+// gallery rows) both call it, so a score has the same bits in every kernel built from either: lane (row fr, half fh2) holds k = 64 kc +
+// 8 s + 4 fh2 + e of its row, loop kc, s = 0..7, e = 0..3, both 32-column blocks per step, accumulators from 0.
+//   a_ptr / a_step: the lane's row + fh2 columns and its step per chunk (gal_row_or_zeros); each wave streams ITS OWN 32 rows into
+//   registers, one chunk (8 loads, 32 VGPRs) ahead of the one being multiplied.
+//   fetch_b(qv): loads the calling thread's four 16-byte pieces of the NEXT B chunk — piece i is row 16 i + (tid >> 4), source column
+//   (tid & 15) ^ (row & 15) — and advances the caller's pointers.  The scan passes one pointer and a stride, the pair pass four row
+//   pointers; the helper does not care (and the scans have no registers to spare for the general form).
+//   ldsq: the double-buffered B chunk [64 rows][16 columns], 16-byte column XOR (row & 15).  The CALLER issues the barrier that frees it
+//   from the previous tile; everything from the first fetch to the last MFMA is here.
+// The B chunk goes global -> registers -> LDS (not by LDS-DMA): the compiler makes every LDS read wait for ALL vector-memory traffic
+// while an LDS-DMA is in flight (it cannot tell the two halves of ldsq apart: `s_waitcnt vmcnt(0)` in front of each multiply, i.e. every
+// chunk waited out its own gallery-row loads).  Through registers the dependencies are exact: the 4 B loads are issued BEFORE the 8 row
+// loads, so the ds_write after the multiply waits with vmcnt(8) and the row loads fly on until the next barrier.  sched_barrier: left
+// alone, the scheduler sinks the row loads below the multiply (one register set instead of two) and serialises them with it.
+template <typename T, typename FetchB>
+__device__ __forceinline__ void gal_tile_dot(v4f (&ldsq)[2][GAL_BN * 16], const T* a_ptr, int a_step, int chunks, int tid, int fr, int fh2,
+                                             FetchB&& fetch_b, v16f (&acc)[GAL_BN / 32]) {
+    constexpr bool F16 = std::is_same<T, _Float16>::value;
+    constexpr int TN = GAL_BN / 32, EC = 16 / (int)sizeof(T);
+    const int fsw = fr & 15;
+    v4f xa[2][8], qv[4];
+    v16f c[TN];                                               // accumulators of the loop: locals, written to acc ONCE at the end (with acc itself
+                                                              // in the loop the compiler copies all 32 registers at the loop's exit)
+    auto load_a = [&](v4f (&x)[8]) {                          // 16-byte column 2s + fh2 of the chunk
+#pragma unroll
+        for (int s = 0; s < 8; ++s) x[s] = *reinterpret_cast<const v4f*>(a_ptr + s * 2 * EC);
+        a_ptr += a_step;
+    };
+    auto multiply = [&](const v4f (&x)[8], int buf) {
+        const v4f* Wt = ldsq[buf] + fr * 16;
+#pragma unroll
+        for (int s = 0; s < 8; ++s) {
+            const int col = (2 * s + fh2) ^ fsw;
+            if constexpr (F16) {
+#pragma unroll
+                for (int j = 0; j < TN; ++j) {
+                    const v4f w = Wt[j * 32 * 16 + col];
+                    c[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(v8h, x[s]), __builtin_bit_cast(v8h, w), c[j], 0, 0, 0);
+                }
+            } else {
+                v4f w[TN];
+#pragma unroll
+                for (int j = 0; j < TN; ++j) w[j] = Wt[j * 32 * 16 + col];
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+#pragma unroll
+                    for (int j = 0; j < TN; ++j) c[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(x[s][e], w[j][e], c[j], 0, 0, 0);
+            }
+        }
+    };
+    auto store_b = [&](int buf) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) ldsq[buf][i * 256 + tid] = qv[i];
+    };
+#pragma unroll
+    for (int j = 0; j < TN; ++j)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) c[j][e] = 0.f;
+    fetch_b(qv);
+    load_a(xa[0]);
+    store_b(0);
+    int kc = 0;
+    for (; kc + 2 <= chunks; kc += 2) {
+        __syncthreads();                                   // B of chunk kc is in LDS (and xa[0] has landed: the barrier drains vmcnt)
+        fetch_b(qv);
+        load_a(xa[1]);
+        __builtin_amdgcn_sched_barrier(0);
+        multiply(xa[0], 0);
+        store_b(1);
+        __syncthreads();
+        if (kc + 2 < chunks) { fetch_b(qv); load_a(xa[0]); }
+        __builtin_amdgcn_sched_barrier(0);
+        multiply(xa[1], 1);
+        if (kc + 2 < chunks) store_b(0);
+    }
+    if (kc < chunks) {                                     // odd number of chunks
+        __syncthreads();
+        multiply(xa[0], 0);
+    }
+#pragma unroll
+    for (int j = 0; j < TN; ++j) acc[j] = c[j];
+}
+
+// The fp32 scan's score of up to 32 single (row, query) pairs, by one wave: the multiply of gal_tile_dot with the query in EVERY
 // column of B — lane (row fr, half fh2) holds k = kc * 64 + (2s + fh2) * 4 + e of its row; loop kc, s = 0..7, e = 0..3; accumulator from
 // 0.  One output element depends only on its row, its column and that sequence, so (acc + 1) / 2 has the bits the scan gives the pair.
 // a_ptr: the lane's row + fh2 * 4 (a dead lane: the zero line, a_step 0; else a_step 64); b_ptr: the query + fh2 * 4.  Every column of
-// the result is the same: element e of a lane is row 8 * (e >> 2) + 4 * fh2 + (e & 3).
+// the result is the same: element e of a lane is row gal_acc_row(e) + 4 * fh2.  (No LDS, no double buffering: a loop of its own.)
 __device__ __forceinline__ v16f gal_rescore32(const float* a_ptr, int a_step, const float* b_ptr, int chunks) {
     v16f acc;
 #pragma unroll
@@ -229,7 +328,6 @@ __device__ __forceinline__ void gallery_scan_body(const GalArgs& p) {
     const T* const zeros = static_cast<const T*>(p.zeros);
     const T* const q_base = static_cast<const T*>(p.q) + (size_t)(n0 + qrow) * K + (((tid & 15) ^ (qrow & 15)) * EC);
     const size_t q16 = (size_t)16 * K;
-    const int fsw = fr & 15;
 
     // TAGS: part p walks the tiles p, p + parts, p + 2 parts, ... instead of a contiguous run — enrolments grouped by tag are long
     // contiguous blocks, and with contiguous runs the few workgroups that own an admitted block would multiply all of their tiles
@@ -246,83 +344,19 @@ __device__ __forceinline__ void gallery_scan_body(const GalArgs& p) {
         }
         const long myrow = m0 + wid * 32 + fr;
         const bool live = myrow < p.G;
-        const T* a_ptr = (live ? gal + (size_t)myrow * K : zeros) + fh2 * EC;          // dead rows read the zero line (and are masked below)
-        const int a_step = live ? CD : 0;
+        const GalSrc<T> a = gal_row_or_zeros(live, gal, (size_t)myrow, K, zeros, fh2 * EC, CD);      // (dead rows are masked below)
         const T* q_src = q_base;
-        v4f xa[2][8];
-        auto load_a = [&](v4f (&x)[8]) {                      // 16-byte column 2s + fh2 of the chunk
-#pragma unroll
-            for (int s = 0; s < 8; ++s) x[s] = *reinterpret_cast<const v4f*>(a_ptr + s * 2 * EC);
-            a_ptr += a_step;
-        };
-        v16f acc[TN];
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[j][e] = 0.f;
-        auto multiply = [&](const v4f (&x)[8], int buf) {
-            const v4f* Wt = ldsq[buf] + fr * 16;
-#pragma unroll
-            for (int s = 0; s < 8; ++s) {
-                const int col = (2 * s + fh2) ^ fsw;
-                if constexpr (F16) {
-#pragma unroll
-                    for (int j = 0; j < TN; ++j) {
-                        const v4f w = Wt[j * 32 * 16 + col];
-                        acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(v8h, x[s]), __builtin_bit_cast(v8h, w), acc[j], 0, 0, 0);
-                    }
-                } else {
-                    v4f w[TN];
-#pragma unroll
-                    for (int j = 0; j < TN; ++j) w[j] = Wt[j * 32 * 16 + col];
-#pragma unroll
-                    for (int e = 0; e < 4; ++e)
-#pragma unroll
-                        for (int j = 0; j < TN; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(x[s][e], w[j][e], acc[j], 0, 0, 0);
-                }
-            }
-        };
-        // The query chunk goes global -> registers -> LDS (not by LDS-DMA): the compiler makes every LDS read wait for ALL vector-memory
-        // traffic while an LDS-DMA is in flight (it cannot tell the two halves of ldsq apart: `s_waitcnt vmcnt(0)` in front of each
-        // multiply, i.e. every chunk waited out its own gallery-row loads).  Through registers the dependencies are exact: the 4 query
-        // loads are issued BEFORE the 8 row loads, so the ds_write after the multiply waits with vmcnt(8) and the row loads fly on until
-        // the next barrier.  sched_barrier: left alone, the scheduler sinks the row loads below the multiply (one register set instead
-        // of two) and serialises them with it.
-        v4f qv[4];
-        auto fetch_q = [&]() {
+        auto fetch_q = [&](v4f (&qv)[4]) {
 #pragma unroll
             for (int i = 0; i < 4; ++i) qv[i] = *reinterpret_cast<const v4f*>(q_src + i * q16);
             q_src += CD;
         };
-        auto store_q = [&](int buf) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) ldsq[buf][i * 256 + tid] = qv[i];
-        };
-        __syncthreads();                                   // previous tile's epilogue is done with the LDS lists / queues
+        v16f acc[TN];
+        __syncthreads();                                   // previous tile's epilogue is done with the LDS lists / queues (and ldsq)
         if constexpr (TAGS) {
             if (tid < BM) tag_s[tid] = my_tag;             // (read behind the K loop's barriers)
         }
-        fetch_q();
-        load_a(xa[0]);
-        store_q(0);
-        int kc = 0;
-        for (; kc + 2 <= chunks; kc += 2) {
-            __syncthreads();                               // queries of chunk kc are in LDS (and xa[0] has landed: the barrier drains vmcnt)
-            fetch_q();
-            load_a(xa[1]);
-            __builtin_amdgcn_sched_barrier(0);
-            multiply(xa[0], 0);
-            store_q(1);
-            __syncthreads();
-            if (kc + 2 < chunks) { fetch_q(); load_a(xa[0]); }
-            __builtin_amdgcn_sched_barrier(0);
-            multiply(xa[1], 1);
-            if (kc + 2 < chunks) store_q(0);
-        }
-        if (kc < chunks) {                                 // odd number of chunks
-            __syncthreads();
-            multiply(xa[0], 0);
-        }
+        gal_tile_dot<T>(ldsq, a.ptr, a.step, chunks, tid, fr, fh2, fetch_q, acc);
         const long rbase = m0 + wid * 32 + 4 * fh2;
         // ---- threshold epilogue: bit 4 * fh2 + 8 * (e >> 2) + (e & 3) of the lane's word = its row of that position in the wave's 32-row
         // block; the lane pair (fr, fr ^ 32) holds the two interleaved halves of one query's word, so after one exchange per query block
@@ -332,7 +366,7 @@ __device__ __forceinline__ void gallery_scan_body(const GalArgs& p) {
             unsigned tg[16];                               // the tags of the lane's 16 rows (rows behind G, and a call without masks: unused)
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
-                const long row = rbase + 8 * (e >> 2) + (e & 3);
+                const long row = rbase + gal_acc_row(e);
                 tg[e] = p.qmask && row < p.G ? p.tags[row] : 0xFFFFFFFFu;
             }
             unsigned word[TN];
@@ -343,10 +377,10 @@ __device__ __forceinline__ void gallery_scan_body(const GalArgs& p) {
                 unsigned bits = 0;
 #pragma unroll
                 for (int e = 0; e < 16; ++e) {
-                    const long row = rbase + 8 * (e >> 2) + (e & 3);
-                    const float sc = (acc[j][e] + 1.0f) / 2.0f;
+                    const long row = rbase + gal_acc_row(e);
+                    const float sc = gal_score(acc[j][e]);
                     const bool hit = row < p.G && (tg[e] & mq) != 0 && sc > p.range_thr;      // (false for a NaN score)
-                    bits |= (hit ? 1u : 0u) << (4 * fh2 + 8 * (e >> 2) + (e & 3));
+                    bits |= (hit ? 1u : 0u) << (4 * fh2 + gal_acc_row(e));
                 }
                 word[j] = bits | (unsigned)__shfl_xor((int)bits, 32);
             }
@@ -366,8 +400,8 @@ __device__ __forceinline__ void gallery_scan_body(const GalArgs& p) {
 #pragma unroll
                 for (int e = 0; e < 16; ++e) {
                     if ((e >> 2) < g_lo || (e >> 2) >= g_hi) continue;
-                    const long row = rbase + 8 * (e >> 2) + (e & 3);
-                    const float sc = (acc[j][e] + 1.0f) / 2.0f;
+                    const long row = rbase + gal_acc_row(e);
+                    const float sc = gal_score(acc[j][e]);
                     const int gi = (int)(p.idx_base + row);
                     bool admitted = true;
                     if constexpr (TAGS) {                  // a lane's rows are four runs of four: one 16-byte LDS read per run, two addresses per wave

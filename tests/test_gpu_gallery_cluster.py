@@ -1,7 +1,8 @@
 """Exact DBSCAN over a gallery's rows on the GPU (fh_gallery_cluster_dev, gallery_cluster.hip).  Expected = the numpy rule of
 tests/cluster_model.py on gallery_ids_model.scores(rows, rows) — the oracle.dot_mfma bits the fp32 scan reports; got = cluster_dev into
 buffers prefilled with a sentinel.  Labels and the four counters must be IDENTICAL: there is no tolerance.  Shapes: dim 64 (the odd-chunk
-tail), 128, 192 (even + tail); G around the 64-row B tile and the 128-row A tile, the diagonal inside a tile, several tiles each way;
+tail), 128, 192 (even + tail), 256 (two loop rounds, the second without refetch or tail) and 512 (eight chunks: the production depth);
+G around the 64-row B tile and the 128-row A tile, the diagonal inside a tile, several tiles each way;
 runs of three and more A tiles per workgroup through the debug hook.  Then fh_gallery_set_ids and the cluster -> set_ids -> fuse flow."""
 import numpy as np
 import pytest
@@ -78,6 +79,11 @@ def sparse_threshold(S, per_row=3.0):
 
 
 SIZES = (1, 2, 63, 64, 65, 127, 128, 129, 300, 1100)
+DEEP_SIZES = (65, 129, 300)         # dims 256 and 512: one partial B tile, a diagonal inside an A tile, several tiles each way
+
+
+def sizes_for(dim):
+    return SIZES if dim < 256 else DEEP_SIZES
 _CASES = {}
 
 
@@ -94,10 +100,10 @@ def case(dim, G):
 
 
 @pytest.mark.timeout(300)
-@pytest.mark.parametrize("dim", [64, 128, 192])
+@pytest.mark.parametrize("dim", [64, 128, 192, 256, 512])
 def test_sizes_around_the_tiles(dim):
     seen = np.zeros(4, np.int64)
-    for G in SIZES:
+    for G in sizes_for(dim):
         rows, S, thr = case(dim, G)
         g = gallery(rows)
         for min_pts, noise in ((1, "none"), (3, "self"), (4, "none")):

@@ -2,7 +2,7 @@
 gallery_cluster.hip).  Expected = gallery_ids_model.scores(rows, rows) — the oracle.dot_mfma bits the fp32 scan reports — pushed through
 the bin rule of tests/roc_model.py; got = pair_hist_dev into buffers prefilled with a sentinel.  Counts must be IDENTICAL: there is no
 tolerance.  Shapes as for the clustering passes (the rows and score matrices are shared with tests/test_gpu_gallery_cluster.py): dim 64
-(the odd-chunk tail), 128, 192; G around the 64-row B tile and the 128-row A tile; runs of several A tiles through the debug hook.  Then
+(the odd-chunk tail), 128, 192, 256 and 512 (four and eight chunks, at three sizes); G around the 64-row B tile and the 128-row A tile; runs of several A tiles through the debug hook.  Then
 the bin rule's edges on the device with dyadic rows, the call's contract, and histogram -> threshold -> clustering end to end."""
 import ctypes as C
 
@@ -65,10 +65,10 @@ def check(g, S, ids, what, **kw):
 
 
 @pytest.mark.timeout(300)
-@pytest.mark.parametrize("dim", [64, 128, 192])
+@pytest.mark.parametrize("dim", [64, 128, 192, 256, 512])
 def test_sizes_around_the_tiles(dim):
     used = np.zeros((2, BINS), bool)
-    for G in tc.SIZES:
+    for G in tc.sizes_for(dim):
         rows, S, _ = tc.case(dim, G)
         ids = ids_for(G, 7 * dim + G)
         want_h, _ = check(tc.gallery(rows, ids), S, ids, f"dim {dim}")
