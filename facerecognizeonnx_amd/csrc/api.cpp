@@ -469,6 +469,48 @@ int fh_det_postprocess_dev(fh_det* d, int n, float score_thr, float nms_thr, fh_
     return guarded([&] { d->det.postprocess_dev(n, score_thr, nms_thr, reinterpret_cast<fh::FaceRec*>(out), max_pf, counts, S(stream)); return n; });
 }
 
+// Scratch of the two fh_postprocess_rows*_dev entry points: one set per calling thread, and a call on a DIFFERENT stream than the
+// previous one first waits for that one's kernels (event), so overlapping calls cannot race on cand / keys / ws / count.  Heap-allocated
+// and never destroyed: a static DevBuf's destructor would call hipFree after the HIP runtime has been torn down at process exit.
+namespace {
+struct RowsScratch {
+    fh::DevBuf cand, keys, ws, count;
+    fh::TilePlan plan;                                                     // (tiled calls only)
+    fh::TileTable tab;
+    hipEvent_t done = nullptr;
+    hipStream_t last = nullptr;
+    bool used = false;
+    void begin(hipStream_t s) {
+        if (!done) FH_HIP(hipEventCreateWithFlags(&done, hipEventDisableTiming));
+        if (used && last != s) FH_HIP(hipStreamWaitEvent(s, done, 0));
+    }
+    // threshold + NMS of V views of n frames, cap candidates per view, key_total keys in all; then the fence for the next call
+    void run(fh::PostArgs a, int n, size_t key_total, const fh::TileTable* tb, float nms_thr, fh_face* out, int max_pf, int* counts,
+             hipStream_t s) {
+        cand.ensure((size_t)a.V * a.cap * sizeof(fh::FaceRec));
+        keys.ensure(key_total * sizeof(unsigned long long));
+        ws.ensure(key_total * sizeof(int));
+        count.ensure((size_t)n * sizeof(int));
+        a.cand = cand.as<fh::FaceRec>(); a.keys = keys.as<unsigned long long>(); a.count = count.as<int>();
+        fh::postprocess_views(a, n, tb, nms_thr, ws.as<int>(), reinterpret_cast<fh::FaceRec*>(out), max_pf, counts, s);
+        FH_HIP(hipEventRecord(done, s));
+        last = s; used = true;
+    }
+    static RowsScratch& mine() {
+        thread_local RowsScratch* p = new RowsScratch();
+        return *p;
+    }
+};
+// caller's rows [V][rows_per_view][feat] with the smallest power-of-two capacity (the in-place bitonic sort needs one)
+fh::PostArgs rows_source(const float* rows, int V, int rows_per_view, int feat, float score_thr) {
+    fh::PostArgs a{};
+    a.rows = rows; a.n_rows = rows_per_view; a.feat = feat; a.V = V; a.thr = score_thr; a.border = -1;
+    a.cap = 1;
+    while (a.cap < rows_per_view) a.cap <<= 1;
+    return a;
+}
+}  // namespace
+
 // FaceDetector::postprocess + nms on caller-supplied pre-decoded rows (src/face_detector.cpp:224-338,356-384)
 int fh_postprocess_rows_dev(const float* rows, int n, int rows_per_frame, int feat, float scale, float score_thr, float nms_thr,
                             fh_face* out, int max_pf, int* counts, void* stream) {
@@ -481,34 +523,16 @@ int fh_postprocess_rows_dev(const float* rows, int n, int rows_per_frame, int fe
             FH_HIP(hipMemsetAsync(counts, 0, (size_t)n * sizeof(int), s));
             return n;
         }
-        // scratch of this entry point: one set per calling thread, and a call on a DIFFERENT stream than the previous one first waits
-        // for that one's kernels (event), so overlapping calls cannot race on cand / keys / ws / count.  Heap-allocated and never
-        // destroyed: a static DevBuf's destructor would call hipFree after the HIP runtime has been torn down at process exit.
-        struct Scratch { fh::DevBuf cand, keys, ws, count; hipEvent_t done = nullptr; hipStream_t last = nullptr; bool used = false; };
-        thread_local Scratch* scp = new Scratch();
-        Scratch& sc = *scp;
-        if (!sc.done) FH_HIP(hipEventCreateWithFlags(&sc.done, hipEventDisableTiming));
-        if (sc.used && sc.last != s) FH_HIP(hipStreamWaitEvent(s, sc.done, 0));
-        fh::DevBuf &cand = sc.cand, &keys = sc.keys, &ws = sc.ws, &count = sc.count;
-        int cap = 1;
-        while (cap < rows_per_frame) cap <<= 1;                           // the in-place bitonic sort needs a power of two
-        cand.ensure((size_t)n * cap * sizeof(fh::FaceRec));
-        keys.ensure((size_t)n * cap * sizeof(unsigned long long));
-        ws.ensure((size_t)n * cap * sizeof(int));
-        count.ensure((size_t)n * sizeof(int));
-        FH_HIP(hipMemsetAsync(count.p, 0, (size_t)n * sizeof(int), s));
-        fh::launch_rows_threshold(rows, n, rows_per_frame, feat, scale, score_thr, cand.as<fh::FaceRec>(), keys.as<unsigned long long>(),
-                                  count.as<int>(), cap, s);
-        fh::launch_sort_nms(cand.as<fh::FaceRec>(), keys.as<unsigned long long>(), count.as<int>(), cap, n, nms_thr,
-                            reinterpret_cast<fh::FaceRec*>(out), counts, max_pf, ws.as<int>(), s);
-        FH_HIP(hipGetLastError());
-        FH_HIP(hipEventRecord(sc.done, s));
-        sc.last = s; sc.used = true;
+        RowsScratch& sc = RowsScratch::mine();
+        sc.begin(s);
+        fh::PostArgs a = rows_source(rows, n, rows_per_frame, feat, score_thr);
+        a.scale = scale;
+        sc.run(a, n, (size_t)n * a.cap, nullptr, nms_thr, out, max_pf, counts, s);
         return n;
     });
 }
 
-// fh_postprocess_rows_dev's tiled twin: the view-aware threshold + one NMS per frame on caller-supplied rows of every view
+// fh_postprocess_rows_dev on the rows of every view of tiled frames: the plan's view table + one NMS per frame
 int fh_postprocess_rows_tiled_dev(const float* rows, const int* frame_rows, const int* frame_cols, int n, const fh_tiling* t, int in_w,
                                   int in_h, int rows_per_view, int feat, float score_thr, float nms_thr, fh_face* out, int max_pf,
                                   int* counts, void* stream) {
@@ -523,32 +547,20 @@ int fh_postprocess_rows_tiled_dev(const float* rows, const int* frame_rows, cons
             FH_HIP(hipMemsetAsync(counts, 0, (size_t)n * sizeof(int), s));
             return n;
         }
-        // one scratch set per calling thread, fenced by an event across streams, never destroyed: as fh_postprocess_rows_dev
-        struct Scratch { fh::DevBuf cand, keys, ws, count; fh::TilePlan plan; fh::TileTable tab; hipEvent_t done = nullptr; hipStream_t last = nullptr; bool used = false; };
-        thread_local Scratch* scp = new Scratch();
-        Scratch& sc = *scp;
-        if (!sc.done) FH_HIP(hipEventCreateWithFlags(&sc.done, hipEventDisableTiming));
-        if (sc.used && sc.last != s) FH_HIP(hipStreamWaitEvent(s, sc.done, 0));
-        int cap = 1;
-        while (cap < rows_per_view) cap <<= 1;
+        RowsScratch& sc = RowsScratch::mine();
+        sc.begin(s);
+        fh::PostArgs a = rows_source(rows, 0, rows_per_view, feat, score_thr);
         static const uint8_t live = 0;                                     // (the planner only asks whether a frame HAS pixels)
         std::vector<fh::FrameIn> fr((size_t)n);
         for (int i = 0; i < n; ++i) fr[(size_t)i] = fh::FrameIn{&live, frame_rows[i], frame_cols[i], 0};
-        const int V = sc.plan.plan(fr.data(), n, TL(t), in_w, in_h, cap, FH_TILE_MAX_VIEWS);
-        if (V <= 0) {
+        a.V = sc.plan.plan(fr.data(), n, TL(t), in_w, in_h, a.cap, FH_TILE_MAX_VIEWS);
+        if (a.V <= 0) {
             FH_HIP(hipMemsetAsync(counts, 0, (size_t)n * sizeof(int), s));
             return n;
         }
         sc.tab.upload(sc.plan, s);
-        sc.cand.ensure((size_t)V * cap * sizeof(fh::FaceRec));
-        sc.keys.ensure(sc.plan.key_total * sizeof(unsigned long long));
-        sc.ws.ensure(sc.plan.key_total * sizeof(int));
-        sc.count.ensure((size_t)n * sizeof(int));
-        fh::tiled_postprocess(nullptr, rows, rows_per_view, feat, sc.plan, sc.tab, cap, t->border, score_thr, nms_thr, sc.cand.as<fh::FaceRec>(),
-                              sc.keys.as<unsigned long long>(), sc.ws.as<int>(), sc.count.as<int>(), reinterpret_cast<fh::FaceRec*>(out),
-                              max_pf, counts, s);
-        FH_HIP(hipEventRecord(sc.done, s));
-        sc.last = s; sc.used = true;
+        a.border = t->border;
+        sc.run(a, n, sc.plan.key_total, &sc.tab, nms_thr, out, max_pf, counts, s);
         return n;
     });
 }

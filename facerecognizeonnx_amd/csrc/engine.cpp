@@ -789,18 +789,27 @@ void TileTable::upload(const TilePlan& p, hipStream_t s) {
     st_.send(vb + sb, s);
 }
 
-void tiled_postprocess(const TiledHeads* heads, const float* rows, int rows_per_view, int feat, const TilePlan& plan, const TileTable& tab,
-                       int cap, int border, float score_thr, float nms_thr, FaceRec* cand, unsigned long long* keys, int* sup, int* count,
-                       FaceRec* out, int max_out, int* counts, hipStream_t s) {
-    const int n = (int)plan.segs.size();
-    FH_HIP(hipMemsetAsync(count, 0, (size_t)n * sizeof(int), s));
-    TiledArgs a{};
-    a.views = tab.views(); a.segs = tab.segs(); a.V = (int)plan.views.size(); a.cap = cap; a.border = border; a.thr = score_thr;
-    a.cand = cand; a.keys = keys; a.count = count;
-    if (heads) launch_scrfd_decode_tiled(*heads, a, s);
-    else launch_rows_threshold_tiled(rows, rows_per_view, feat, a, s);
-    launch_sort_nms_frames(cand, keys, count, tab.segs(), cap, n, nms_thr, out, counts, max_out, sup, s);
+void postprocess_views(PostArgs a, int n_frames, const TileTable* tab, float nms_thr, int* sup, FaceRec* out, int max_out, int* counts,
+                       hipStream_t s) {
+    FH_HIP(hipMemsetAsync(a.count, 0, (size_t)n_frames * sizeof(int), s));
+    a.views = tab ? tab->views() : nullptr;
+    a.segs = tab ? tab->segs() : nullptr;
+    if (a.rows) launch_rows_threshold(a, s);
+    else launch_scrfd_decode(a, s);
+    launch_sort_nms(a.cand, a.keys, a.count, a.segs, a.cap, n_frames, nms_thr, out, counts, max_out, sup, s);
     FH_HIP(hipGetLastError());
+}
+
+PostArgs Detector::post_source(int V, float score_thr) {
+    PostArgs a{};
+    if (predecoded_) { a.rows = net_.output(0); a.n_rows = anchors_; a.feat = feat_; }
+    else {
+        for (int i = 0; i < 3; ++i) { a.score[i] = net_.output(i); a.bbox[i] = net_.output(3 + i); a.kps[i] = net_.output(6 + i); }
+        a.inH = net_.in_h(); a.inW = net_.in_w();
+    }
+    a.V = V; a.cap = cap_; a.border = -1; a.thr = score_thr;
+    a.cand = cand_.as<FaceRec>(); a.keys = keys_.as<unsigned long long>(); a.count = count_.as<int>();
+    return a;
 }
 
 int Detector::run_network_tiled_dev(const FrameIn* frames, int n, const Tiling& t, hipStream_t s) {
@@ -820,14 +829,9 @@ void Detector::detect_tiled_dev(const FrameIn* frames, int n, const Tiling& t, f
     keys_.ensure(tplan_.key_total * sizeof(unsigned long long));          // (reserve(V) sized them for V * cap: a frame's segment is
     ws_.ensure(tplan_.key_total * sizeof(int));                           //  the power of two above its views * cap)
     count_.ensure((size_t)n * sizeof(int));
-    TiledHeads h{};
-    if (!predecoded_) {
-        for (int i = 0; i < 3; ++i) { h.score[i] = net_.output(i); h.bbox[i] = net_.output(3 + i); h.kps[i] = net_.output(6 + i); }
-        h.inH = net_.in_h(); h.inW = net_.in_w();
-    }
-    tiled_postprocess(predecoded_ ? nullptr : &h, predecoded_ ? net_.output(0) : nullptr, anchors_, feat_, tplan_, ttab_, cap_, t.border,
-                      score_thr, nms_thr, cand_.as<FaceRec>(), keys_.as<unsigned long long>(), ws_.as<int>(), count_.as<int>(), out,
-                      max_out, counts, s);
+    PostArgs a = post_source(V, score_thr);
+    a.border = t.border;
+    postprocess_views(a, n, &ttab_, nms_thr, ws_.as<int>(), out, max_out, counts, s);
 }
 
 void Detector::run_input_dev(const float* input, int n, hipStream_t s) {
@@ -840,22 +844,11 @@ void Detector::run_input_dev(const float* input, int n, hipStream_t s) {
 
 void Detector::postprocess_dev(int n, float score_thr, float nms_thr, FaceRec* out, int max_out, int* counts, hipStream_t s) {
     if (anchors_ <= 0) { FH_HIP(hipMemsetAsync(counts, 0, (size_t)n * sizeof(int), s)); return; }
-    FH_HIP(hipMemsetAsync(count_.p, 0, (size_t)n * sizeof(int), s));
     if (ragged_ && n > table_.size()) throw std::runtime_error("detector: more frames than the last ragged call described");
-    const float* scales = ragged_ ? table_.scales() : nullptr;       // per frame after a ragged run, else the uniform scale_
-    if (predecoded_) {
-        launch_rows_threshold(net_.output(0), n, anchors_, feat_, scale_, score_thr, cand_.as<FaceRec>(),
-                              keys_.as<unsigned long long>(), count_.as<int>(), cap_, s, scales);
-    } else {
-        DecodeArgs a{};
-        for (int i = 0; i < 3; ++i) { a.score[i] = net_.output(i); a.bbox[i] = net_.output(3 + i); a.kps[i] = net_.output(6 + i); }
-        a.inH = net_.in_h(); a.inW = net_.in_w(); a.B = n; a.scale = scale_; a.scales = scales; a.thr = score_thr;
-        a.cand = cand_.as<FaceRec>(); a.keys = keys_.as<unsigned long long>(); a.count = count_.as<int>(); a.cap = cap_;
-        launch_scrfd_decode(a, s);
-    }
-    launch_sort_nms(cand_.as<FaceRec>(), keys_.as<unsigned long long>(), count_.as<int>(), cap_, n, nms_thr, out, counts, max_out,
-                    ws_.as<int>(), s);
-    FH_HIP(hipGetLastError());
+    PostArgs a = post_source(n, score_thr);
+    a.scale = scale_;
+    a.scales = ragged_ ? table_.scales() : nullptr;                  // per frame after a ragged run, else the uniform scale_
+    postprocess_views(a, n, nullptr, nms_thr, ws_.as<int>(), out, max_out, counts, s);
 }
 
 void Detector::detect_dev(const uint8_t* frames, int n, int rows, int cols, int step, long stride, float score_thr, float nms_thr,

@@ -204,11 +204,12 @@ class TileTable {
     StagedTable st_;
 };
 
-// decode / threshold (view-aware) + one NMS per frame on the rows of a tiled call: heads == nullptr -> pre-decoded rows
-// [V][rows_per_view][feat].  counts of frames without views are 0.
-void tiled_postprocess(const TiledHeads* heads, const float* rows, int rows_per_view, int feat, const TilePlan& plan, const TileTable& tab,
-                       int cap, int border, float score_thr, float nms_thr, FaceRec* cand, unsigned long long* keys, int* sup, int* count,
-                       FaceRec* out, int max_out, int* counts, hipStream_t s);
+// The detector's post-process on the a.V views of n_frames frames: zero the counts, decode (a.rows == nullptr: the SCRFD heads) or
+// threshold (a.rows: pre-decoded rows [V][n_rows][feat]), then one NMS per frame.  The caller fills the candidate source, thr, cap, V
+// and the buffers.  tab == nullptr: a flat or ragged call, one view per frame (V == n_frames) with a.scale / a.scales; else the tables
+// of a tiled call, whose a.border applies.  counts of frames without views are 0.  sup: the NMS' flags, sized as a.keys.
+void postprocess_views(PostArgs a, int n_frames, const TileTable* tab, float nms_thr, int* sup, FaceRec* out, int max_out, int* counts,
+                       hipStream_t s);
 
 class Detector {
   public:
@@ -235,8 +236,8 @@ class Detector {
     void detect_ragged_dev(const FrameIn* frames, int n, float score_thr, float nms_thr, FaceRec* out, int max_out, int* counts,
                            hipStream_t s);
     const FrameTable& frame_table() const { return table_; }   // of the last ragged call: handed to the recogniser's align by the pipeline
-    // Tiled detection (include/facehip.h): the views of all frames are ONE ragged batch (table_ then holds the VIEWS), decoded by the
-    // view-aware kernels and merged by one NMS per frame.  run_network_tiled_dev returns the total view count (0: only empty frames),
+    // Tiled detection (include/facehip.h): the views of all frames are ONE ragged batch (table_ then holds the VIEWS), decoded with the
+    // plan's view table and merged by one NMS per frame.  run_network_tiled_dev returns the total view count (0: only empty frames),
     // or throws std::invalid_argument when the call has more than kTileMaxViews views — before anything is launched.
     int run_network_tiled_dev(const FrameIn* frames, int n, const Tiling& t, hipStream_t s);
     void detect_tiled_dev(const FrameIn* frames, int n, const Tiling& t, float score_thr, float nms_thr, FaceRec* out, int max_out,
@@ -247,6 +248,7 @@ class Detector {
 
   private:
     void reserve(int n, int rows, int cols);
+    PostArgs post_source(int V, float score_thr);         // the network's outputs of V views + this object's buffers, no views yet
     Net net_;
     bool predecoded_ = false;
     int anchors_ = 0, feat_ = 15, cap_ = 0, nb_ = 0;

@@ -4,7 +4,6 @@
 // arithmetic are meant to be bit-identical to the CPU oracle (oracle/face_oracle.c).
 #include <hip/hip_runtime.h>
 
-#include "face_emit.h"
 #include "face_iou.h"
 #include "kernels.h"
 
@@ -267,69 +266,143 @@ void launch_letterbox_ragged(const FrameDesc* table, int n, int inH, int inW, ui
 // the float difference.  Payload goes to cand[frame][anchor]; the surviving anchors' sort keys
 // (score descending, anchor index ascending — the total order this build fixes for the
 // reference's unstable std::sort, :357) are compacted with one atomic per survivor.
+//
+// One body serves flat, ragged and tiled calls (kernels.h: PostArgs).  A call's views went through the network as ONE batch, one row
+// block per view; per view the candidates get the reference's row arithmetic (emit_face, in VIEW coordinates), then
+//   the border rule   tiles only: a box within `border` pixels of an INTERIOR edge of its tile is dropped (the face is cut there;
+//                     the neighbouring tile or the whole-frame view sees it whole),
+//   the shift         x += view.x, y += view.y in integers, every landmark coordinate + (float)view.x / (float)view.y (one fp32 add
+//                     after the division; view 0 is at the origin and is not touched),
+// and the key is appended to the FRAME's list with the frame's counter; its low word local_view * cap + index makes the sort's order
+// (score descending, view ascending, index ascending).  The payload stays in the per-view [view][cap] blocks.  A flat or ragged frame
+// is a frame of one view: index 0, at the origin, no interior edges, the frame's own scale, payload block b and key segment
+// [b * cap, (b + 1) * cap).  TABLES = false is that case with the view folded in at compile time, so it carries no table and none of the
+// tile steps; the launchers pick the instantiation from PostArgs::views.
 // ------------------------------------------------------------------------------------------
-// (make_key / emit_face: face_emit.h, shared with the view-aware kernels of tiled_kernels.hip)
-__global__ __launch_bounds__(256) void scrfd_decode_kernel(const DecodeArgs a) {
+// score descending, then the 32-bit index ascending — the total order this build fixes for the reference's unstable std::sort (:357)
+__device__ __forceinline__ unsigned long long make_key(float score, unsigned idx) {
+    unsigned u = __float_as_uint(score);
+    u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);        // ascending-orderable
+    return ((unsigned long long)(~u) << 32) | idx;          // descending score, ascending index
+}
+
+// /scale, int truncation, width from the float difference
+__device__ __forceinline__ void emit_face(const float* o15, float scale, FaceRec* f) {
+    const float x1 = o15[0] / scale, y1 = o15[1] / scale, x2 = o15[2] / scale, y2 = o15[3] / scale;
+    f->x = (int)x1; f->y = (int)y1; f->w = (int)(x2 - x1); f->h = (int)(y2 - y1);
+    f->score = o15[4];
+#pragma unroll
+    for (int j = 0; j < 10; ++j) f->lm[j] = o15[5 + j] / scale;
+}
+
+template <bool TABLES>
+__device__ __forceinline__ ViewDesc view_of(const PostArgs& a, int b) {
+    if (TABLES) return a.views[b];
+    return ViewDesc{b, 0, 0, 0, 0, 0, 0, a.scales ? a.scales[b] : a.scale};
+}
+
+// candidate r of view gv (described by v), as the reference's row o15 -> payload block + the frame's key list
+template <bool TABLES>
+__device__ __forceinline__ void emit_view_face(const float* o15, const ViewDesc& v, int gv, int r, const PostArgs& a) {
+    FaceRec f;
+    emit_face(o15, v.scale, &f);
+    size_t key_off = (size_t)v.frame * a.cap;
+    int seg_cap = a.cap;
+    if (TABLES) {
+        if (a.border >= 0 && v.edges) {                      // (view 0: edges == 0)
+            const long long b = a.border;
+            if ((v.edges & 1) && f.x <= b) return;
+            if ((v.edges & 2) && f.y <= b) return;
+            if ((v.edges & 4) && (long long)f.x + f.w >= v.w - b) return;
+            if ((v.edges & 8) && (long long)f.y + f.h >= v.h - b) return;
+        }
+        if (v.local != 0) {
+            const float fx = (float)v.x, fy = (float)v.y;
+            f.x = (int)((unsigned)f.x + (unsigned)v.x); f.y = (int)((unsigned)f.y + (unsigned)v.y);
+#pragma unroll
+            for (int j = 0; j < 5; ++j) { f.lm[2 * j] += fx; f.lm[2 * j + 1] += fy; }
+        }
+        const FrameSeg sg = a.segs[v.frame];
+        key_off = (size_t)sg.key_off; seg_cap = sg.seg_cap;
+    }
+    a.cand[(size_t)gv * a.cap + r] = f;
+    const int pos = atomicAdd(a.count + v.frame, 1);
+    if (pos < seg_cap) a.keys[key_off + pos] = make_key(f.score, (unsigned)(v.local * a.cap + r));
+}
+
+// SCRFD anchor r of view b -> the reference's row o[15] (the step the reference lacks); false: its score is not above thr.
+// cx + d * fs must stay two roundings (-ffp-contract=off).
+__device__ __forceinline__ bool scrfd_anchor_row(const PostArgs& a, int b, int r, float* o) {
     const int gw8 = a.inW / 8, gh8 = a.inH / 8, gw16 = a.inW / 16, gh16 = a.inH / 16, gw32 = a.inW / 32, gh32 = a.inH / 32;
     const int n8 = gw8 * gh8 * 2, n16 = gw16 * gh16 * 2, n32 = gw32 * gh32 * 2;
-    const int N = n8 + n16 + n32;
-    const int b = blockIdx.y;                              // one grid row per frame: no 64-bit index arithmetic per anchor
-    const float scale = a.scales ? a.scales[b] : a.scale;  // per frame on the ragged path
-    if (!(scale > 0.f)) return;                            // a dead frame emits nothing: its count stays 0
-    for (int r = blockIdx.x * blockDim.x + threadIdx.x; r < N; r += gridDim.x * blockDim.x) {
-        int si, i, gw, s, ns;
-        if (r < n8) { si = 0; i = r; gw = gw8; s = 8; ns = n8; }
-        else if (r < n8 + n16) { si = 1; i = r - n8; gw = gw16; s = 16; ns = n16; }
-        else { si = 2; i = r - n8 - n16; gw = gw32; s = 32; ns = n32; }
-        const float score = a.score[si][(size_t)b * ns + i];
-        if (!(score > a.thr)) continue;
-        const int cell = i >> 1;
-        const int gy = cell / gw, gx = cell - gy * gw;
-        const float cx = (float)(gx * s), cy = (float)(gy * s), fs = (float)s;
-        const float* d = a.bbox[si] + ((size_t)b * ns + i) * 4;
-        const float* k = a.kps[si] + ((size_t)b * ns + i) * 10;
-        float o[15];
-        o[0] = cx - d[0] * fs; o[1] = cy - d[1] * fs; o[2] = cx + d[2] * fs; o[3] = cy + d[3] * fs;
-        o[4] = score;
+    int si, i, gw, s, ns;
+    if (r < n8) { si = 0; i = r; gw = gw8; s = 8; ns = n8; }
+    else if (r < n8 + n16) { si = 1; i = r - n8; gw = gw16; s = 16; ns = n16; }
+    else { si = 2; i = r - n8 - n16; gw = gw32; s = 32; ns = n32; }
+    // (constant indices: a per-lane index into the by-value argument struct would force a copy of it into scratch)
+    const float* sc = si == 0 ? a.score[0] : si == 1 ? a.score[1] : a.score[2];
+    const float score = sc[(size_t)b * ns + i];
+    if (!(score > a.thr)) return false;
+    const int cell = i >> 1;
+    const int gy = cell / gw, gx = cell - gy * gw;
+    const float cx = (float)(gx * s), cy = (float)(gy * s), fs = (float)s;
+    const float* d = (si == 0 ? a.bbox[0] : si == 1 ? a.bbox[1] : a.bbox[2]) + ((size_t)b * ns + i) * 4;
+    const float* k = (si == 0 ? a.kps[0] : si == 1 ? a.kps[1] : a.kps[2]) + ((size_t)b * ns + i) * 10;
+    o[0] = cx - d[0] * fs; o[1] = cy - d[1] * fs; o[2] = cx + d[2] * fs; o[3] = cy + d[3] * fs;
+    o[4] = score;
 #pragma unroll
-        for (int j = 0; j < 5; ++j) { o[5 + 2 * j] = cx + k[2 * j] * fs; o[6 + 2 * j] = cy + k[2 * j + 1] * fs; }
-        emit_face(o, scale, a.cand + (size_t)b * a.cap + r);
-        const int pos = atomicAdd(a.count + b, 1);
-        if (pos < a.cap) a.keys[(size_t)b * a.cap + pos] = make_key(score, (unsigned)r);
+    for (int j = 0; j < 5; ++j) { o[5 + 2 * j] = cx + k[2 * j] * fs; o[6 + 2 * j] = cy + k[2 * j + 1] * fs; }
+    return true;
+}
+
+static inline int scrfd_anchors(const PostArgs& a) {
+    return ((a.inW / 8) * (a.inH / 8) + (a.inW / 16) * (a.inH / 16) + (a.inW / 32) * (a.inH / 32)) * 2;
+}
+
+// grid = ceil(anchors / 256) x V: one grid row per view, so the view is uniform in the workgroup and no anchor needs 64-bit index
+// arithmetic (the head tensors hold one row block per view, in plan order)
+template <bool TABLES>
+__global__ __launch_bounds__(256) void scrfd_decode_kernel(const PostArgs a, int N) {
+    const int b = blockIdx.y;
+    const ViewDesc v = view_of<TABLES>(a, b);
+    if (!(v.scale > 0.f)) return;                            // a dead view emits nothing: it adds nothing to its frame's count
+    for (int r = blockIdx.x * blockDim.x + threadIdx.x; r < N && r < a.cap; r += gridDim.x * blockDim.x) {
+        float o[15];
+        if (scrfd_anchor_row(a, b, r, o)) emit_view_face<TABLES>(o, v, b, r, a);
     }
 }
 
-void launch_scrfd_decode(const DecodeArgs& a, hipStream_t s) {
-    const int N = ((a.inW / 8) * (a.inH / 8) + (a.inW / 16) * (a.inH / 16) + (a.inW / 32) * (a.inH / 32)) * 2;
-    if (N <= 0 || a.B <= 0) return;
-    hipLaunchKernelGGL(scrfd_decode_kernel, dim3((N + 255) / 256, a.B), dim3(256), 0, s, a);
+void launch_scrfd_decode(const PostArgs& a, hipStream_t s) {
+    const int N = scrfd_anchors(a);
+    if (N <= 0 || a.V <= 0) return;
+    auto kernel = a.views ? scrfd_decode_kernel<true> : scrfd_decode_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3((N + 255) / 256, a.V), dim3(256), 0, s, a, N);
 }
 
-// The reference's own layout: rows [n, feat >= 15] = x1,y1,x2,y2,score,kps (src/face_detector.cpp:242-325)
-__global__ __launch_bounds__(256) void rows_threshold_kernel(const float* __restrict__ rows, int B, int n, int feat, float scale_all,
-                                                             const float* __restrict__ scales, float thr, FaceRec* cand,
-                                                             unsigned long long* keys, int* count, int cap) {
-    const long total = (long)B * n;
+// The reference's own layout: rows [V][n_rows][feat >= 15] = x1,y1,x2,y2,score,kps (src/face_detector.cpp:242-325).  One grid-stride
+// loop over the rows of all views: the rows entry of the C ABI takes far more frames than a grid's second dimension holds.
+template <bool TABLES>
+__global__ __launch_bounds__(256) void rows_threshold_kernel(const PostArgs a) {
+    const int n = a.n_rows;
+    const long total = (long)a.V * n;
     for (long t = (long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (long)gridDim.x * blockDim.x) {
         const int b = (int)(t / n);
         const int r = (int)(t - (long)b * n);
-        const float* o = rows + (size_t)t * feat;
-        const float score = o[4];
-        const float scale = scales ? scales[b] : scale_all;
-        if (!(score > thr) || r >= cap || !(scale > 0.f)) continue;      // (a dead frame of the ragged path emits nothing)
+        const float* o = a.rows + (size_t)t * a.feat;
+        if (!(o[4] > a.thr) || r >= a.cap) continue;
+        const ViewDesc v = view_of<TABLES>(a, b);
+        if (!(v.scale > 0.f)) continue;                      // a dead view emits nothing
         float o15[15];
 #pragma unroll
         for (int j = 0; j < 15; ++j) o15[j] = o[j];
-        emit_face(o15, scale, cand + (size_t)b * cap + r);
-        const int pos = atomicAdd(count + b, 1);
-        if (pos < cap) keys[(size_t)b * cap + pos] = make_key(score, (unsigned)r);
+        emit_view_face<TABLES>(o15, v, b, r, a);
     }
 }
 
-void launch_rows_threshold(const float* rows, int B, int n, int feat, float scale, float thr, FaceRec* cand,
-                           unsigned long long* keys, int* count, int cap, hipStream_t s, const float* scales) {
-    hipLaunchKernelGGL(rows_threshold_kernel, dim3(grid_for((long)B * n)), dim3(256), 0, s, rows, B, n, feat, scale, scales, thr, cand,
-                       keys, count, cap);
+void launch_rows_threshold(const PostArgs& a, hipStream_t s) {
+    if (a.n_rows <= 0 || a.V <= 0) return;
+    auto kernel = a.views ? rows_threshold_kernel<true> : rows_threshold_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3(grid_for((long)a.V * a.n_rows)), dim3(256), 0, s, a);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -422,38 +495,26 @@ __device__ __forceinline__ void sort_nms_segment(const FaceRec* __restrict__ fc,
     if (tid == 0) *out_count = run_base;
 }
 
-// one workgroup per frame; the frame's segment is its [cap] block (cap is a power of two >= count, host guarantees)
-__global__ __launch_bounds__(NMS_T) void sort_nms_kernel(const FaceRec* __restrict__ cand, unsigned long long* __restrict__ keys_g,
-                                                         const int* __restrict__ count, int cap, float thr, FaceRec* __restrict__ out,
-                                                         int* __restrict__ out_count, int max_out, int* __restrict__ ws) {
-    const int b = blockIdx.x;
-    sort_nms_segment(cand + (size_t)b * cap, keys_g + (size_t)b * cap, ws + (size_t)b * cap, min(count[b], cap), thr,
-                     out + (size_t)b * max_out, out_count + b, max_out);
-}
-
-// Tiled detection: one workgroup per FRAME over the candidates of all its views.  The frame owns the payload blocks of its views
+// One workgroup per FRAME over the candidates of all its views.  The frame owns the payload blocks of its views
 // (cand[first_view .. first_view + views)[cap], which the keys' low words local_view * cap + index address) and the key / flag segment
-// [key_off, key_off + seg_cap) — seg_cap the power of two >= views * cap.
-__global__ __launch_bounds__(NMS_T) void sort_nms_frames_kernel(const FaceRec* __restrict__ cand, unsigned long long* __restrict__ keys_g,
-                                                                const int* __restrict__ count, const FrameSeg* __restrict__ segs, int cap,
-                                                                float thr, FaceRec* __restrict__ out, int* __restrict__ out_count,
-                                                                int max_out, int* __restrict__ ws) {
+// [key_off, key_off + seg_cap) — seg_cap the power of two >= views * cap.  segs == null: frame b has one view, block b and the segment
+// [b * cap, (b + 1) * cap) (cap is a power of two >= count, host guarantees).
+__global__ __launch_bounds__(NMS_T) void sort_nms_kernel(const FaceRec* __restrict__ cand, unsigned long long* __restrict__ keys_g,
+                                                         const int* __restrict__ count, const FrameSeg* __restrict__ segs, int cap,
+                                                         float thr, FaceRec* __restrict__ out, int* __restrict__ out_count,
+                                                         int max_out, int* __restrict__ ws) {
     const int b = blockIdx.x;
-    const FrameSeg sg = segs[b];
-    sort_nms_segment(cand + (size_t)sg.first_view * cap, keys_g + sg.key_off, ws + sg.key_off, min(count[b], sg.seg_cap), thr,
+    size_t first_view = (size_t)b, key_off = (size_t)b * cap;
+    int seg_cap = cap;
+    if (segs) { const FrameSeg sg = segs[b]; first_view = (size_t)sg.first_view; key_off = (size_t)sg.key_off; seg_cap = sg.seg_cap; }
+    sort_nms_segment(cand + first_view * cap, keys_g + key_off, ws + key_off, min(count[b], seg_cap), thr,
                      out + (size_t)b * max_out, out_count + b, max_out);
 }
 
-void launch_sort_nms(const FaceRec* cand, unsigned long long* keys, const int* count, int cap, int B, float nms_thr, FaceRec* out,
-                     int* out_count, int max_out, int* order_ws, hipStream_t s) {
-    hipLaunchKernelGGL(sort_nms_kernel, dim3(B), dim3(NMS_T), 0, s, cand, keys, count, cap, nms_thr, out, out_count, max_out,
-                       order_ws);
-}
-
-void launch_sort_nms_frames(const FaceRec* cand, unsigned long long* keys, const int* count, const FrameSeg* segs, int cap, int n_frames,
-                            float nms_thr, FaceRec* out, int* out_count, int max_out, int* order_ws, hipStream_t s) {
+void launch_sort_nms(const FaceRec* cand, unsigned long long* keys, const int* count, const FrameSeg* segs, int cap, int n_frames,
+                     float nms_thr, FaceRec* out, int* out_count, int max_out, int* order_ws, hipStream_t s) {
     if (n_frames <= 0) return;
-    hipLaunchKernelGGL(sort_nms_frames_kernel, dim3(n_frames), dim3(NMS_T), 0, s, cand, keys, count, segs, cap, nms_thr, out, out_count,
+    hipLaunchKernelGGL(sort_nms_kernel, dim3(n_frames), dim3(NMS_T), 0, s, cand, keys, count, segs, cap, nms_thr, out, out_count,
                        max_out, order_ws);
 }
 

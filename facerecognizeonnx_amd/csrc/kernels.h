@@ -245,30 +245,10 @@ void launch_stem_conv_u8(const uint8_t* src, long img_stride, int srcH, int srcW
                          float* out1, float* out2, const float* s2, const float* t2, hipStream_t s, const unsigned* wfrag = nullptr,
                          int cus = 0);
 
-struct DecodeArgs {
-    const float* score[3];  // per stride [B, gh*gw*2]
-    const float* bbox[3];   // [B, gh*gw*2, 4]
-    const float* kps[3];    // [B, gh*gw*2, 10]
-    int inH, inW, B;
-    float scale, thr;
-    const float* scales;    // [B] per-frame letterbox scale (the ragged path) or null = `scale` for every frame; a frame whose scale is
-                            // not > 0 (a dead frame) emits nothing
-    FaceRec* cand;          // [B][cap]
-    unsigned long long* keys;   // [B][cap]  sort keys (score desc, anchor index asc)
-    int* count;             // [B]
-    int cap;
-};
-void launch_scrfd_decode(const DecodeArgs& a, hipStream_t s);
-// generic [rows, feat>=15] pre-decoded layout (src/face_detector.cpp:242-325)
-// scales (optional, device [B]): per-frame scale as DecodeArgs::scales
-void launch_rows_threshold(const float* rows, int B, int n, int feat, float scale, float thr, FaceRec* cand,
-                           unsigned long long* keys, int* count, int cap, hipStream_t s, const float* scales = nullptr);
-// sort by key + greedy integer-IoU NMS (src/face_detector.cpp:340-384); writes survivors
-// (score-descending) to out[B][max_out], counts to out_count[B].
-void launch_sort_nms(const FaceRec* cand, unsigned long long* keys, const int* count, int cap, int B, float nms_thr,
-                     FaceRec* out, int* out_count, int max_out, int* order_ws, hipStream_t s);
-
-// ---- tiled detection (tiled_kernels.hip; the contract is stated in include/facehip.h) ----------------------------------------------
+// ---- detector post-process: decode / threshold per VIEW, one NMS per FRAME (flat, ragged and tiled calls alike) ---------------------
+// A call's frames are cut into views; every view went through the network (or arrives as caller's rows) as one row block.  A flat or
+// ragged call is the case of one view per frame and needs no tables; a tiled call (include/facehip.h: fh_det_detect_tiled_dev) brings
+// both.
 // One row per VIEW of a call, in plan order (the views of frame 0, then of frame 1, ...): the frame it belongs to, its index among the
 // frame's views, its rectangle in the frame, its interior-edge mask (fh_view::edges; 0 for view 0) and its letterbox scale
 // (fh_letterbox_plan of h x w; 0 = a dead view, which emits nothing).
@@ -282,28 +262,34 @@ static_assert(sizeof(ViewDesc) == 32, "ViewDesc is a 32-byte table row");
 struct FrameSeg {
     int32_t first_view, views, key_off, seg_cap;
 };
-struct TiledArgs {
-    const ViewDesc* views;      // [V]
-    const FrameSeg* segs;       // [n_frames]
-    int V, cap, border;         // border < 0: the border rule is off
+struct PostArgs {
+    // the candidates: SCRFD heads (launch_scrfd_decode) ...
+    const float* score[3];      // per stride [V, gh*gw*2]
+    const float* bbox[3];       // [V, gh*gw*2, 4]
+    const float* kps[3];        // [V, gh*gw*2, 10]
+    int inH, inW;
+    // ... or the reference's own layout (launch_rows_threshold): [V][n_rows][feat >= 15] = x1,y1,x2,y2,score,kps
+    const float* rows;
+    int n_rows, feat;
+    // the views: both tables (a tiled call) or neither
+    const ViewDesc* views;      // [V], or null: view b is frame b, whole and at the origin, with scale scales ? scales[b] : scale
+    const FrameSeg* segs;       // [n_frames], or null: frame b owns payload block b and the key / flag segment [b * cap, (b + 1) * cap)
+    const float* scales;        // (views == null) [V] per-frame letterbox scale of a ragged call, or null
+    float scale;                // a view or frame whose scale is not > 0 (a dead one) emits nothing
+    int V, cap, border;         // cap: candidates per view, a power of two; border < 0: the border rule is off
     float thr;
     FaceRec* cand;              // [V][cap] payload, one block per view
     unsigned long long* keys;   // per-frame segments; key = (score desc, local_view * cap + index asc)
     int* count;                 // [n_frames]
 };
-// the view-aware twins of launch_scrfd_decode / launch_rows_threshold: the same row arithmetic per view (emit_face), then the border
-// rule, the integer / fp32 shift into frame coordinates, and the key appended to the FRAME's list
-struct TiledHeads {
-    const float* score[3];      // per stride [V, gh*gw*2]
-    const float* bbox[3];
-    const float* kps[3];
-    int inH, inW;
-};
-void launch_scrfd_decode_tiled(const TiledHeads& h, const TiledArgs& a, hipStream_t s);
-void launch_rows_threshold_tiled(const float* rows, int rows_per_view, int feat, const TiledArgs& a, hipStream_t s);
-// launch_sort_nms with one workgroup per frame over the frame's segment (face_kernels.hip, the same sort + sweep + compaction)
-void launch_sort_nms_frames(const FaceRec* cand, unsigned long long* keys, const int* count, const FrameSeg* segs, int cap, int n_frames,
-                            float nms_thr, FaceRec* out, int* out_count, int max_out, int* order_ws, hipStream_t s);
+// Per candidate with score > thr: the reference's row arithmetic in VIEW coordinates, the border rule (a box within `border` pixels of
+// an interior edge of its tile is dropped), the shift into frame coordinates, the payload store and the key appended to the FRAME's list
+void launch_scrfd_decode(const PostArgs& a, hipStream_t s);
+void launch_rows_threshold(const PostArgs& a, hipStream_t s);
+// sort by key + greedy integer-IoU NMS (src/face_detector.cpp:340-384), one workgroup per frame over the frame's segment (segs, or
+// null = the identity segment as PostArgs::segs); writes survivors (score-descending) to out[n_frames][max_out], counts to out_count[n_frames].
+void launch_sort_nms(const FaceRec* cand, unsigned long long* keys, const int* count, const FrameSeg* segs, int cap, int n_frames,
+                     float nms_thr, FaceRec* out, int* out_count, int max_out, int* order_ws, hipStream_t s);
 
 // FaceRecognizer::alignFace (src/face_recognizer.cpp:93-133): similarity estimate + warpAffine
 //   faces[n] with frame index frame_of[n]; writes crops [n,112,112,3] BGR u8 and ok[n].

@@ -26,7 +26,8 @@ ap.add_argument("--overlap", type=int, default=128)
 ap.add_argument("--border", type=int, default=2)
 ap.add_argument("--cases", nargs="+", default=["1080x1920", "2160x3840"])
 ap.add_argument("--profile", type=int, default=0, help="N tiled steps, then N ragged-on-the-views steps, of --cases and nothing else "
-                "(for a separate `rocprofv3 --kernel-trace --stats` run: the two legs use differently named decode / NMS kernels)")
+                "(for a separate `rocprofv3 --kernel-trace --stats` run: the two legs use the two instantiations of the decode kernel; "
+                "their NMS launches differ in grid size, one workgroup per frame against one per view)")
 ap.add_argument("--md", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "tiled_ab.md"))
 a = ap.parse_args()
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

@@ -267,6 +267,78 @@ def test_crafted_rows_more_than_2048_survivors_in_one_frame():
     assert cnt[1] > 2048 and cnt[0] == 3 and cnt[2] == 0
 
 
+def _rows_flat(rows, thr, nms, max_pf):
+    """rows [n][R][15] through fh_postprocess_rows_dev at scale 1; returns (records [n][max_pf], counts)."""
+    n, R, feat = rows.shape
+    d = dev(rows)
+    out = torch.full((n, max_pf, 15), 3.0, device="cuda"); cnt = torch.full((n,), -1, dtype=torch.int32, device="cuda")
+    rc = fa.lib().fh_postprocess_rows_dev(d.data_ptr(), n, R, feat, 1.0, thr, nms, out.data_ptr(), max_pf, cnt.data_ptr(), 0)
+    assert rc == n, _lib.last_error()
+    torch.cuda.synchronize()
+    return _records(out, n, max_pf), cnt.cpu().numpy()
+
+
+def test_one_frame_is_one_view_on_callers_rows():
+    """A frame that fits one tile has one view: index 0, at the origin, no interior edges, scale 1.  The flat entry and the tiled entry
+    must then give the same bytes (untouched tail included) on the crafted rows of the flat tests — 0, 1, a few hundred, 2048 and 2049
+    survivors, ties, NaN / -inf / == thr scores, zero-area boxes, negative coordinates — with the border rule on and off, and both must
+    be the oracle's records."""
+    from tests.test_gpu_parity import _crafted_rows
+    rng = np.random.default_rng(77)
+    R, thr, nms = 2560, 0.5, 0.4
+    lives = [0, 1, 300, 2048, 2049]
+    rows = np.stack([_crafted_rows(rng, R, nl, 15, thr) for nl in lives])
+    refs = [oracle.postprocess_rows(rows[b], 1.0, thr, nms) for b in range(len(lives))]
+    assert [len(oracle.threshold_rows(rows[b], 1.0, thr)) for b in range(len(lives))] == lives
+    assert tile_model.plan(IN, IN, 128, 128, 32) == [(0, 0, IN, IN, 0)] and tile_model.letterbox_scale(IN, IN, IN, IN) == 1.0
+    frames = [(IN, IN)] * len(lives)
+    for max_pf in (100, 4096):                                 # below and above the largest count
+        flat, fcnt = _rows_flat(rows, thr, nms, max_pf)
+        for border in (2, -1):
+            rec, cnt = _rows_tiled(frames, [[rows[b]] for b in range(len(lives))], fa.Tiling(128, 32, border), thr, nms, max_pf, R)
+            assert cnt.tobytes() == fcnt.tobytes() and rec.tobytes() == flat.tobytes(), (max_pf, border)
+        for b, ref in enumerate(refs):
+            assert fcnt[b] == len(ref), (b, fcnt[b], len(ref))
+            k = min(len(ref), max_pf)
+            assert flat[b, :k].tobytes() == ref[:k].tobytes(), (b, max_pf)
+    assert max(len(r) for r in refs) > 100
+
+
+def test_more_frames_than_a_grids_second_dimension():
+    """fh_postprocess_rows_dev with 65 537 frames of two rows: every frame's count and records follow from a vectorised expression
+    (disjoint integer boxes, so the NMS keeps every survivor; order = score descending, then row), and the frames around 65 535 are
+    checked against the oracle as well."""
+    n, thr, nms = 65537, 0.5, 0.4
+    b = np.arange(n)
+    rows = np.zeros((n, 2, 15), np.float32)
+    for j in range(2):
+        x1 = 100 * j + b % 37; y1 = 5 + b % 11
+        rows[:, j, 0] = x1; rows[:, j, 1] = y1; rows[:, j, 2] = x1 + 3 + b % 5; rows[:, j, 3] = y1 + 4 + j
+        rows[:, j, 5:15] = (b % 1024)[:, None] + 16 * j + np.arange(10)[None, :]
+    rows[:, 0, 4] = np.where(b % 3 == 0, 0.25, 0.75)                                  # row 0: dead in every third frame
+    rows[:, 1, 4] = np.choose(b % 4, [0.375, 0.875, 0.75, 0.625])                     # row 1: dead / ahead / tied (row 0 first) / behind
+    err = _lib.last_error()                                                           # (sticky: an earlier test's text may stand)
+    rec, cnt = _rows_flat(rows, thr, nms, 2)                                          # asserts rc == n
+    assert _lib.last_error() == err
+    live = rows[:, :, 4] > thr
+    first = np.where(live[:, 0] & live[:, 1], (rows[:, 1, 4] > rows[:, 0, 4]).astype(int), live[:, 1].astype(int))
+    want = np.zeros((n, 2), fa.FACE_DTYPE)
+    want.view(np.float32).reshape(n, 2, 15)[:] = 3.0                                  # the untouched tail of _rows_flat's buffer
+    for slot in range(2):
+        src = rows[b, first if slot == 0 else 1 - first]
+        on = live.sum(1) > slot
+        w = want[:, slot]
+        w["x"][on] = src[on, 0].astype(np.int32); w["y"][on] = src[on, 1].astype(np.int32)
+        w["w"][on] = (src[on, 2] - src[on, 0]).astype(np.int32); w["h"][on] = (src[on, 3] - src[on, 1]).astype(np.int32)
+        w["score"][on] = src[on, 4]; w["lm"][on] = src[on, 5:15]
+    assert set(np.unique(live.sum(1))) == {0, 1, 2}
+    assert cnt.tobytes() == live.sum(1).astype(np.int32).tobytes()
+    assert rec.tobytes() == want.tobytes()
+    for f in (0, 65534, 65535, 65536):
+        ref = oracle.postprocess_rows(rows[f], 1.0, thr, nms)
+        assert cnt[f] == len(ref) and rec[f, :len(ref)].tobytes() == ref.tobytes(), f
+
+
 # ---------------------------------------------------------------------------------------------- pipeline, host entry, limits
 def test_tiled_pipeline(models_, base):
     det, rec = models_
