@@ -17,13 +17,13 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cstring>
 #include <stdexcept>
 
 #include "dwpw_tile.h"
 #include "gemm_tile.h"
 #include "kernels.h"
 #include "plan.h"
+#include "stem_tile.h"
 
 namespace fh {
 
@@ -303,7 +303,7 @@ static void launch_dwpw_cfg(const ConvArgs& a, hipStream_t s) {
 //   1. the prefetched u8 window (9S+3 rows x (17S+3) pixels, as aligned dwords) goes registers -> LDS; the next tile's loads are issued
 //   2. stem on the matrix cores, v_mfma_f32_16x16x32_bf16: rows = 16 output channels (A = weights), columns = 16 halo pixels (B),
 //      K = the 27 taps of the 3 x 9-byte window (+5 zeros).  u8 values (and the 127.5 of the conv padding) are exact in bf16, every
-//      fp32 weight travels as three bf16 terms (hi + mid + lo = w exactly: stem_pack_wfrag), every product is exact in fp32 and the
+//      fp32 weight travels as three bf16 terms (hi + mid + lo = w exactly: the packer is in stem.hip), every product is exact in fp32 and the
 //      accumulator is fp32: the fp32 FMA chain's value up to summation order, at a tenth of its vector instructions.
 //      Lane l of a group: pixel l & 15, K block g = l >> 4 (g < 3: bytes 0..7 of window row g; g = 3: byte 8 of rows 0..2); the result
 //      comes back as pixel l & 15, channels 4g..4g+3 = one 16-byte column of the halo image [180 pixels][16 channels].
@@ -311,33 +311,6 @@ static void launch_dwpw_cfg(const ConvArgs& a, hipStream_t s) {
 //   4. pointwise product on v_mfma_f32_32x32x2_f32 (K = 16), bias + ReLU, stores.
 // Three barriers per tile.  Tiles are dealt so that the workgroups of one XCD work on neighbouring tiles at the same time (shared
 // window rows hit that XCD's L2).
-
-// Folded stem weights wf [27][16] (tap-major: (ky*9 + kx*3 + byte) x channel) as the A fragments of v_mfma_f32_16x16x32_bf16: three
-// bf16 terms (hi, mid, lo — their sum is the fp32 weight exactly), lane l = channel l & 15, K block l >> 4; K index 8g + j = byte j of
-// window row g (g < 3), 24 + r = byte 8 of row r, 27..31 = 0.  One [3][64][4]-dword block per 16 output channels.
-void stem_pack_wfrag(const float* wf, int Cout, unsigned* out) {             // Cout % 16 == 0; out: [Cout / 16][3][64][4] dwords
-    auto bf = [](float x) {                                                // round to nearest even, as bits
-        unsigned u; memcpy(&u, &x, 4);
-        u += 0x7fffu + ((u >> 16) & 1u);
-        return u >> 16;
-    };
-    auto fl = [](unsigned b) { unsigned u = b << 16; float x; memcpy(&x, &u, 4); return x; };
-    for (int cb = 0; cb < Cout / 16; ++cb)
-        for (int l = 0; l < 64; ++l)
-            for (int j = 0; j < 8; ++j) {
-                const int co = cb * 16 + (l & 15), k = 8 * (l >> 4) + j;
-                float w = 0.f;
-                if (k < 24) w = wf[((k >> 3) * 9 + (k & 7)) * Cout + co];
-                else if (k < 27) w = wf[((k - 24) * 9 + 8) * Cout + co];
-                const unsigned hi = bf(w); const float r1 = w - fl(hi);
-                const unsigned mid = bf(r1); const float r2 = r1 - fl(mid);
-                const unsigned t[3] = {hi, mid, bf(r2)};
-                for (int q = 0; q < 3; ++q) {
-                    unsigned& d = out[((cb * 3 + q) * 64 + l) * 4 + (j >> 1)];
-                    d = (j & 1) ? (d | (t[q] << 16)) : t[q];
-                }
-            }
-}
 
 constexpr int FR_PITCH = 32;                                               // dwords per staged u8 row: (17*2+3)*3 + 3 bytes <= 128
 constexpr int FR_ROWS = 21;                                                // 9*2 + 3
@@ -376,7 +349,6 @@ __global__ __launch_bounds__(256, 4) void front_kernel(const ConvArgs p, const i
     //  s_waitcnt below and would otherwise wait at their first use, inside the tile loop, draining the window prefetch with them)
     asm volatile("" ::"v"(wq_hi), "v"(wq_mid), "v"(wq_lo), "v"(sbias));
 #endif
-    const bf16x8 w_hi = __builtin_bit_cast(bf16x8, wq_hi), w_mid = __builtin_bit_cast(bf16x8, wq_mid), w_lo = __builtin_bit_cast(bf16x8, wq_lo);
     const int fh2 = lane >> 5;
 
     // ---- everything about a lane's three stem groups that does not depend on the tile: halo pixel (hy, hx), its slot in the staged
@@ -394,6 +366,7 @@ __global__ __launch_bounds__(256, 4) void front_kernel(const ConvArgs p, const i
     }
     // a halo pixel lies inside the map and its 3x3 window inside the net input iff  AY0 <= ay <= AY1  and  AX0 <= ax <= AX1 (tiles whose
     // whole halo does take the plain path; the others patch the conv padding in, see the stem below)
+    // (not stem_interior: AX0 = 1 against the NET INPUT — the staging below clamps and shifts row-end dwords, so every image byte is staged exactly)
     const int AY0 = 1, AY1 = min(p.H - 1, (p.u8_inH - 2) / S), AX0 = 1, AX1 = min(p.W - 1, (p.u8_inW - 2) / S);
 
     // ---- tiles of this workgroup (xcd_run); (n, tyi, txi) is the tile being PREFETCHED
@@ -470,15 +443,7 @@ __global__ __launch_bounds__(256, 4) void front_kernel(const ConvArgs p, const i
         // global memory: border tiles (14.5 % of a 640x640 frame's) cost twice an inner tile and the slowest wave ran 20 % above the mean.
         const unsigned* st = stage[buf];
         auto stem_finish = [&](const float (&f)[8], bool inmap, bool store, int hp) __attribute__((always_inline)) {
-            v4u bq;                                                         // fp32 -> bf16 by truncation: exact for 0..255 and 127.5
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-                bq[i] = __builtin_amdgcn_perm(__builtin_bit_cast(unsigned, f[2 * i + 1]), __builtin_bit_cast(unsigned, f[2 * i]), 0x07060302u);
-            const bf16x8 bfrag = __builtin_bit_cast(bf16x8, bq);
-            v4f a4 = sbias;
-            a4 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w_lo, bfrag, a4, 0, 0, 0);
-            a4 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w_mid, bfrag, a4, 0, 0, 0);
-            a4 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w_hi, bfrag, a4, 0, 0, 0);
+            v4f a4 = stem_mfma3(f, sbias, wq_lo, wq_mid, wq_hi);
             if (p.stem_act == (int)Act::RELU) {
 #pragma unroll
                 for (int c = 0; c < 4; ++c) a4[c] = a4[c] > 0.f ? a4[c] : 0.f;
@@ -512,17 +477,12 @@ __global__ __launch_bounds__(256, 4) void front_kernel(const ConvArgs p, const i
                 unsigned n0 = __builtin_amdgcn_perm(d1, d0, selA);
                 const unsigned n1 = __builtin_amdgcn_perm(d2, d1, alsel);
                 n0 = __builtin_amdgcn_perm(d2, n0, selC);
-                f[0] = (float)(n0 & 255u); f[1] = (float)((n0 >> 8) & 255u); f[2] = (float)((n0 >> 16) & 255u); f[3] = (float)(n0 >> 24);
-                f[4] = (float)(n1 & 255u); f[5] = (float)((n1 >> 8) & 255u); f[6] = (float)((n1 >> 16) & 255u); f[7] = (float)(n1 >> 24);
+                stem_unpack8(n0, n1, f);
             } else if (hp >= 0) {
                 if (g < 3) {                                                // 8 bytes at an unaligned position: 3 aligned dwords
                     const unsigned pos = ((STEP4 ? base_lo : base_lo + (unsigned)(g_rq[i] * step)) & 3u) + (unsigned)g_cb[i];
                     const unsigned* q = st + g_rq[i] * FR_PITCH + (pos >> 2);
-                    const unsigned sh = pos & 3u;
-                    const unsigned d0 = q[0], d1 = q[1], d2 = q[2];
-                    const unsigned n0 = __builtin_amdgcn_alignbyte(d1, d0, sh), n1 = __builtin_amdgcn_alignbyte(d2, d1, sh);
-                    f[0] = (float)(n0 & 255u); f[1] = (float)((n0 >> 8) & 255u); f[2] = (float)((n0 >> 16) & 255u); f[3] = (float)(n0 >> 24);
-                    f[4] = (float)(n1 & 255u); f[5] = (float)((n1 >> 8) & 255u); f[6] = (float)((n1 >> 16) & 255u); f[7] = (float)(n1 >> 24);
+                    stem_unpack<8>(q[0], q[1], q[2], pos & 3u, f);
                 } else {
 #pragma unroll
                     for (int r = 0; r < 3; ++r) {

@@ -1,5 +1,5 @@
 // dwpw_tile.h — the tile body of the PERSISTENT depthwise 3x3 -> pointwise 1x1 kernels, each piece once: dwpw_reg_kernel,
-// dwpw_reg2_kernel and front_kernel (dwpw_mfma.hip) are composed from it; stem_mfma_kernel (ops_misc.hip) takes the walk.
+// dwpw_reg2_kernel and front_kernel (dwpw_mfma.hip) are composed from it; stem_mfma_kernel (stem.hip) takes the walk.
 //
 // The tile: 8 x 16 output pixels, 256 threads = 4 waves.  A wave owns 32 pixels for the whole K loop, lane = (pixel r = lane & 31, half
 // h = lane >> 5).  For the 8-channel step j the lane evaluates the depthwise 3x3 (+bias +ReLU) of channels 8j + 4h .. + 3 of ITS pixel

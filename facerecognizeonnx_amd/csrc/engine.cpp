@@ -397,10 +397,14 @@ void Net::run_u8(const uint8_t* src, long img_stride, int srcH, int srcW, int st
         const float* P = params_.as<float>();
         KernelTimer& timer = KernelTimer::get();
         timer.begin(s);
-        launch_stem_conv_u8(src, img_stride, srcH, srcW, step, batch, plan_.inH, plan_.inW, op.stride, op.Cout, P + d.w27, P + d.bias, P + d.wf,
-                            P + d.bf, d.has_slope ? P + d.slope : nullptr, (int)op.act, op.out >= 0 ? tensor_ptr(op.out) : nullptr,
-                            op.out2 >= 0 && !d.bn_fold_dst ? tensor_ptr(op.out2) : nullptr, d.has_aff ? P + d.s2 : nullptr,
-                            d.has_aff ? P + d.t2 : nullptr, s, d.wfr ? reinterpret_cast<const unsigned*>(P + d.wfr) : nullptr, cus);
+        StemArgs a{};
+        a.src = src; a.img_stride = img_stride; a.srcH = srcH; a.srcW = srcW; a.step = step; a.B = batch; a.inH = plan_.inH; a.inW = plan_.inW;
+        a.stride = op.stride; a.Cout = op.Cout; a.w27 = P + d.w27; a.bias = P + d.bias; a.wf = P + d.wf; a.biasf = P + d.bf;
+        a.wfrag = d.wfr ? reinterpret_cast<const unsigned*>(P + d.wfr) : nullptr;
+        a.slope = d.has_slope ? P + d.slope : nullptr; a.act = (int)op.act; a.cus = cus;
+        a.out1 = op.out >= 0 ? tensor_ptr(op.out) : nullptr; a.out2 = op.out2 >= 0 && !d.bn_fold_dst ? tensor_ptr(op.out2) : nullptr;
+        if (d.has_aff) { a.s2 = P + d.s2; a.t2 = P + d.t2; }
+        launch_stem(a, s);
         timer.end(s, 5, 2.0 * op.macs * batch, op.bytes * batch);
         run(batch, s, 1);
         return;

@@ -80,7 +80,7 @@ struct ConvArgs {
     int dw_act;
     int dw_stride;          // 1 | 2
     // fused u8 stem in FRONT of the depthwise part (launch_dwpw with u8_src != null): `in` is not read — the workgroup computes the
-    // stem convolution (3x3, 3 -> 16 channels, stride u8_stride, preprocess folded into stem_wf / stem_bf as for launch_stem_conv_u8)
+    // stem convolution (3x3, 3 -> 16 channels, stride u8_stride, preprocess folded into stem_wf / stem_bf as StemArgs::wf / biasf)
     // for its halo pixels straight from the BGR u8 frames.  H x W = the stem's output grid = the depthwise input.
     const uint8_t* u8_src;
     long u8_img_stride;
@@ -149,7 +149,6 @@ size_t conv_halo_wfrag_floats(int Cin, int Cout);
 void conv_halo_pack_weights(const float* w_ohwi, int Cout, int Cin, float* dst);
 void launch_conv_halo(const ConvArgs& a, const float* wfrag, hipStream_t s);
 // depthwise 3x3 stride 1 (+bias +act) fused with the 1x1 conv that consumes it (dwpw_mfma.hip)
-void stem_pack_wfrag(const float* wf, int Cout, unsigned* out);   // wf [27][Cout] (folded stem weights) -> [Cout/16][3][64][4] dwords, see dwpw_mfma.hip
 bool front_fused_ok(int Cin, int Cout, int dw_stride);   // the opening block (u8 stem + depthwise + pointwise) has a one-kernel form
 void launch_dwpw(const ConvArgs& a, hipStream_t s);
 // Winograd F(4x4,3x3) form of a 3x3 stride-1 pad-1 convolution (winograd.hip): a = the convolution's arguments,
@@ -234,16 +233,25 @@ void launch_det_preprocess(const uint8_t* frames, long img_stride, int rows, int
                            int inH, int inW, int newH, int newW, float* out, hipStream_t s);
 // FaceRecognizer::preprocess (src/face_recognizer.cpp:135-150) on aligned crops → NHWC4
 void launch_rec_preprocess(const uint8_t* crops, int n, int H, int W, float* out, hipStream_t s);
-// preprocess fused into the graph's first Conv 3x3 (Cin = 3): u8 BGR image -> [B,Ho,Wo,Cout] fp32.
-// w27 = [27][Cout] with k = (ky*3+kx)*3 + ci (ci in RGB order); act as fh::Act.
-// wf / biasf (optional): the same filter with the normalisation folded in, for the thread-per-pixel kernel: wf[(tap*3 + j)][Cout] =
-// w27[tap*3 + (2-j)] / 128 (j = byte of the BGR pixel), biasf = bias - 127.5/128 * sum_k w27[k].
-// wfrag (optional, Cout % 16 == 0, Cout <= 64): the folded weights as bf16 MFMA fragments (stem_pack_wfrag) -> matrix-core stem kernel
-// cus: compute units the persistent grids are sized for (0 = the whole device), as ConvArgs::cus
-void launch_stem_conv_u8(const uint8_t* src, long img_stride, int srcH, int srcW, int step, int B, int inH, int inW, int stride,
-                         int Cout, const float* w27, const float* bias, const float* wf, const float* biasf, const float* slope, int act,
-                         float* out1, float* out2, const float* s2, const float* t2, hipStream_t s, const unsigned* wfrag = nullptr,
-                         int cus = 0);
+
+// ---- the graph's first Conv 3x3 (Cin = 3, pad 1) fused with the u8 preprocess (stem.hip): BGR u8 frames -> [B,Ho,Wo,Cout] fp32 ----
+struct StemArgs {
+    const uint8_t* src;         // B frames of srcH x srcW BGR pixels, row pitch `step` bytes, frame pitch img_stride, pasted at the origin of
+    long img_stride;            // the inH x inW net input (the rest of it is the letterbox canvas, u8 0)
+    int srcH, srcW, step, B;
+    int inH, inW, stride, Cout; // Cout % 4 == 0
+    const float *w27, *bias;    // the literal form: [27][Cout], k = (ky*3+kx)*3 + ci (ci in RGB order), and [Cout]
+    const float *wf, *biasf;    // (optional) the normalisation folded in: wf[tap*3 + j][Cout] = w27[tap*3 + (2-j)] / 128 (j = byte of the BGR
+                                // pixel), biasf = bias - 127.5/128 * sum_k w27[k]: the thread-per-pixel kernel (16 | 32 channels)
+    const unsigned* wfrag;      // (optional, Cout % 16 == 0) wf as bf16 MFMA fragments (stem_pack_wfrag): the matrix-core kernel (48 | 64)
+    const float* slope;         // [Cout] (PReLU) or null
+    int act;                    // fh::Act
+    float *out1, *out2;         // [B,Ho,Wo,Cout] or null; out2 = out1 * s2 + t2
+    const float *s2, *t2;
+    int cus;                    // compute units the persistent grids are sized for (0 = the whole device), as ConvArgs::cus
+};
+void launch_stem(const StemArgs& a, hipStream_t s);
+void stem_pack_wfrag(const float* wf, int Cout, unsigned* out);   // wf [27][Cout] -> [Cout/16][3][64][4] dwords
 
 // ---- detector post-process: decode / threshold per VIEW, one NMS per FRAME (flat, ragged and tiled calls alike) ---------------------
 // A call's frames are cut into views; every view went through the network (or arrives as caller's rows) as one row block.  A flat or

@@ -659,7 +659,7 @@ def _r50_stem_leg(dump=None):
 @pytest.mark.parametrize("mfma", [1, 0])
 def test_r50_stem_u8_path_byte_isolation(tmp_path, mfma):
     """w600k_r50 through fh_rec_embed_aligned_dev: stem_mfma_kernel, and (FACEHIP_STEM_MFMA=0, read once per process: a fresh child) the
-    stem kernel launch_stem_conv_u8 falls back to at 64 output channels, the LDS-tile stem_conv_u8_kernel (the thread-per-pixel form is
+    stem kernel launch_stem falls back to at 64 output channels, the LDS-tile stem_conv_u8_kernel (the thread-per-pixel form is
     what det_500m takes with the front off and the stem on, test_det500m_u8_path_byte_isolation[0-1]).  The child's raw outputs must
     differ from the matrix-core stem's in some bit (another kernel ran: a different summation order) and agree to 1e-4 of scale (the bar of
     test_winograd_switch_changes_only_rounding: rounding-only changes through the whole IResNet-50).

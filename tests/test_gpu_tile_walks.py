@@ -1,7 +1,7 @@
 """Long tile walks of the persistent detector and stem kernels.
 
 front_kernel, dwpw_reg_kernel, dwpw_reg2_kernel (csrc/dwpw_mfma.hip over csrc/dwpw_tile.h), stem_mfma_kernel and stem_conv_u8_kernel
-(csrc/ops_misc.hip) keep
+(csrc/stem.hip) keep
 their workgroups alive: a workgroup computes tile t while tile t + wgs is already on its way into registers, and it reuses one LDS halo /
 stage buffer from tile to tile.  Their launchers give every tile a workgroup of its own as long as there are at most 2 .. 4 tiles per
 compute unit, which is every single-layer case of the other test files — the loop-carried part of the kernels (the prefetch one tile ahead,
@@ -61,7 +61,7 @@ STEM_MFMA, STEM_U8 = "stem_mfma_kernel", "stem_conv_u8_kernel"
 #   stride-1 blocks: 45 x 41 map = 6 x 3 tiles of 8 x 16;  stride-2 blocks: 137 x 185 -> 69 x 93 = 6417 outputs, 9 x 6 tiles, odd sides
 #   (right / bottom padding inside the halo), 7 x 54 = 378 tiles, 378 & 7 = 2;  stride-2 stems: frame 89 x 81 -> 45 x 41;  stems' own
 #   16 x 16 tiles: 3 x 3 per 45 x 41 map.
-# One row per instantiation the launchers can pick (launch_dwpw_reg, dwpw_mfma.hip; launch_stem_conv_u8, ops_misc.hip).  `walkers`: the
+# One row per instantiation the launchers can pick (launch_dwpw_reg, dwpw_mfma.hip; launch_stem, stem.hip).  `walkers`: the
 # persistent kernels of the row, restated from the launchers.  The stem of the other rows runs in a kernel without a tile loop: the
 # thread-per-pixel stem (16 channels), or — 72 channels, more than the u8 stems take — the float preprocess + conv_igemm_kernel.  That
 # convolution goes through launch_conv, whose stream-K cut and tall split follow `cus`, but neither can touch it: K = 36 is two 32-deep
@@ -111,7 +111,7 @@ def _cdiv(a, b):
 
 def _walkers(Cc, Cout, ds, front):
     """Which persistent kernels a row launches: launch_dwpw_reg / front_fused_ok (dwpw_mfma.hip), Net::run_u8 and the stem_ok_ rule
-    (engine.cpp), launch_stem_conv_u8 (ops_misc.hip)."""
+    (engine.cpp), launch_stem (stem.hip)."""
     if front:
         assert Cc == 16 and ds == 1 and Cout <= 32 and Cout % 4 == 0
         return (FRONT,)
@@ -157,7 +157,7 @@ def test_long_tile_walks_are_bitwise_the_one_tile_per_workgroup_form(tmp_path, n
     cus_dev = torch.cuda.get_device_properties(0).multi_processor_count
     for k, t in tiles.items():
         # cus = 0: grid = max(8, floor8(min(ceil8(tiles), CUs * OCC))) with OCC >= 2 (launch_dwpw_reg_cfg, launch_dwpw_reg2_cfg, launch_front:
-        # dwpw_mfma.hip; launch_stem_mfma: ops_misc.hip), min(tiles, 256 * 8) blocks for stem_conv_u8_kernel: a workgroup per tile
+        # dwpw_mfma.hip; launch_stem_mfma: stem.hip), min(tiles, 256 * 8) blocks for stem_conv_u8_kernel: a workgroup per tile
         if k == STEM_U8:
             assert t <= 256 * 8, (k, t)
         else:

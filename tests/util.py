@@ -196,3 +196,35 @@ def halo_graph(path, H, W, Cin, Cout, res):
     b.node("Reshape", [y, b.init("shape", np.array([-1, Cout], np.int64))], outputs=["out"])
     b.add_output("out", ["A", Cout])
     return b.save(path)
+
+
+def stem_graph(path, H, W, C, stride, act, bn, seed):
+    """input [1,3,H,W] -> y = Conv3x3(3 -> C) stride `stride` (+ReLU | +PReLU | nothing) -> depthwise 3x3 of y, or (bn) of
+    BatchNormalization(y) with y added back, so that the stem's plain map, its affine second output, s2 / t2 and the slope are all live
+    -> [H'W', C]"""
+    from facerecognizeonnx_amd.synth.onnx_writer import OnnxBuilder
+    rng = np.random.default_rng(seed)
+    b = OnnxBuilder("stem")
+    x = b.add_input("input.1", [1, 3, H, W])
+    y = b.node("Conv", [x, b.init("stem.w", (rng.standard_normal((C, 3, 3, 3)) / 5).astype(np.float32)),
+                        b.init("stem.b", (rng.standard_normal(C) / 10).astype(np.float32))],
+               kernel_shape=[3, 3], strides=[stride, stride], pads=[1, 1, 1, 1], dilations=[1, 1], group=1)
+    if act == "relu":
+        y = b.node("Relu", [y])
+    elif act == "prelu":
+        y = b.node("PRelu", [y, b.init("stem.slope", (0.25 * rng.uniform(0.5, 1.5, (C, 1, 1))).astype(np.float32))])
+    z = y
+    if bn:
+        z = b.node("BatchNormalization", [y, b.init("bn.weight", rng.uniform(0.5, 1.5, C).astype(np.float32)),
+                                          b.init("bn.bias", (rng.standard_normal(C) / 10).astype(np.float32)),
+                                          b.init("bn.running_mean", (rng.standard_normal(C) / 10).astype(np.float32)),
+                                          b.init("bn.running_var", rng.uniform(0.5, 1.5, C).astype(np.float32))], epsilon=1e-5, momentum=0.9)
+    z = b.node("Conv", [z, b.init("dw.w", (rng.standard_normal((C, 1, 3, 3)) / 3).astype(np.float32)),
+                        b.init("dw.b", (rng.standard_normal(C) / 10).astype(np.float32))],
+               kernel_shape=[3, 3], strides=[1, 1], pads=[1, 1, 1, 1], dilations=[1, 1], group=C)
+    if bn:
+        z = b.node("Add", [z, y])
+    z = b.node("Transpose", [z], perm=[0, 2, 3, 1])
+    b.node("Reshape", [z, b.init("shape", np.array([-1, C], np.int64))], outputs=["out"])
+    b.add_output("out", ["A", C])
+    return b.save(path)
