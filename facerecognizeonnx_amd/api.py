@@ -282,6 +282,11 @@ class FaceRecognizer:
         check(_lib.lib().fh_rec_set_precision(self._h, modes[mode], C.byref(worst)), "fh_rec_set_precision")
         return float(worst.value)
 
+    def set_wino_x3(self, on: bool = True) -> int:
+        """The fp32 mode's Winograd GEMMs: six bf16 MFMAs on exactly split operands (fp32 results; the default) or, off, the native
+        f32 MFMA kernels.  Returns the number of layers that have the form (0 for off)."""
+        return check(_lib.lib().fh_rec_set_wino_x3(self._h, 1 if on else 0), "fh_rec_set_wino_x3")
+
     def precision(self) -> str:
         return "bf16x2" if _lib.lib().fh_rec_get_precision(self._h) == 1 else "fp32"
 

@@ -1546,6 +1546,14 @@ int fh_det_set_conv_cfg(fh_det* d, int cfg, int stream_k) {
 }
 int fh_det_set_winograd(fh_det* d, int on) { if (!d) return arg_error("null handle"); d->det.net().winograd = on != 0; return FH_OK; }
 int fh_rec_set_winograd(fh_rec* r, int on) { if (!r) return arg_error("null handle"); r->rec.net().winograd = on != 0; return FH_OK; }
+// the fp32 mode's Winograd GEMMs: 1 = three-piece bf16 (six bf16 MFMAs, fp32 results; the default unless FACEHIP_WINO_X3=0), 0 = the native
+// f32 MFMA kernels.  Returns the number of layers that have the form (0 with on = 0), or an error code.  Synchronous on first use (the split weights).
+int fh_rec_set_wino_x3(fh_rec* r, int on) {
+    if (!r) return arg_error("null handle");
+    Owns owns(&r->rec.net());
+    return guarded([&] { return r->rec.net().set_wino_x3(on != 0, nullptr); });
+}
+int fh_rec_get_wino_x3(fh_rec* r) { return r && r->rec.net().wino_x3() ? 1 : 0; }
 int fh_rec_set_wino_fusion(fh_rec* r, int on) { if (!r) return arg_error("null handle"); r->rec.net().fuse_wino = on != 0; return FH_OK; }
 // Opt-in precision mode of the recogniser, gated: the mode is only entered if, on a fixed pseudo-random batch of aligned crops, every
 // embedding it produces stays within 1 - cos < 1e-3 of the fp32 path's (north-star tolerance).  Otherwise the handle stays fp32.
@@ -1635,12 +1643,12 @@ int fh_resize_u8c3_dev(const uint8_t* src, int sh, int sw, int sstep, uint8_t* d
 // precision = FH_PREC_BF16X2: the split-bf16 operand format (U packed here as Net::set_bf16x2 does, V by the input transform)
 int fh_conv_winograd_ex_dev(const float* d_in, const float* w_ohwi, const float* d_bias, float* d_out, int batch, int h, int w, int cin,
                             int cout, int precision, void* stream) {
-    if (!d_in || !w_ohwi || !d_out || cin % 32 || cout % 4 || (precision != FH_PREC_FP32 && precision != FH_PREC_BF16X2))
+    if (!d_in || !w_ohwi || !d_out || cin % 32 || cout % 4 || (precision != FH_PREC_FP32 && precision != FH_PREC_BF16X2 && precision != FH_PREC_F32X3))
         return arg_error("fh_conv_winograd_dev: bad argument");
-    const bool bf2 = precision == FH_PREC_BF16X2;
+    const bool bf2 = precision == FH_PREC_BF16X2, x3 = precision == FH_PREC_F32X3;
     Owns owns(nullptr);                                                  // (no Net: the process-wide watchdog record)
     return guarded([&] {
-        if (bf2 && !fh::wino_gemm_ok_bf16x2(cin, cout)) throw std::runtime_error("winograd: this layer has no split-bf16 GEMM");
+        if ((bf2 || x3) && !fh::wino_gemm_ok_bf16x2(cin, cout)) throw std::runtime_error("winograd: this layer has no split-bf16 GEMM");
         const int rows = fh::conv_wt_rows(cout);
         std::vector<float> u36((size_t)36 * rows * cin, 0.f), uf((size_t)cout * cin);
         std::vector<double> uall((size_t)cout * cin * 36);
@@ -1665,6 +1673,9 @@ int fh_conv_winograd_ex_dev(const float* d_in, const float* w_ohwi, const float*
         if (bf2) {
             dUp.ensure(u36.size() * sizeof(float));
             fh::launch_pack_bf16x2(dU.as<float>(), dUp.as<float>(), (long)u36.size(), S(stream));
+        } else if (x3) {
+            dUp.ensure(36 * fh::wino_x3_floats(rows, cin) * sizeof(float));
+            fh::launch_pack_x3(dU.as<float>(), dUp.as<float>(), rows, cin, S(stream));
         }
         static fh::DevBuf slabs;
         static unsigned slabs_gen = 0;
@@ -1674,7 +1685,7 @@ int fh_conv_winograd_ex_dev(const float* d_in, const float* w_ohwi, const float*
         a.in = d_in; a.bias = d_bias; a.out1 = d_out; a.slabs = slabs.as<float>(); a.sk_enable = 1;
         a.B = batch; a.H = h; a.W = w; a.Ho = h; a.Wo = w; a.Cin = cin; a.Cout = cout; a.ks = 3; a.stride = 1; a.pad = 1;
         a.act = (int)fh::Act::NONE; a.res_mode = (int)fh::ResMode::NONE;
-        fh::launch_conv_winograd(a, (bf2 ? dUp : dU).as<float>(), dV.as<float>(), dM.as<float>(), 2, nullptr, nullptr, S(stream), bf2);
+        fh::launch_conv_winograd(a, (bf2 || x3 ? dUp : dU).as<float>(), dV.as<float>(), dM.as<float>(), 2, nullptr, nullptr, S(stream), precision);
         FH_HIP(hipStreamSynchronize(S(stream)));                 // the workspaces die with this scope
         return 0;
     });
@@ -1711,27 +1722,30 @@ long long fh_debug_wino_gemm_rows(int batch, int h, int w, int k, int n, int mix
 }
 int fh_debug_wino_gemm_dev(const float* d_V, const float* d_U, float* d_M, int batch, int h, int w, int k, int n, int precision, int mixed,
                            void* stream) {
-    if (!d_V || !d_U || !d_M || (precision != FH_PREC_FP32 && precision != FH_PREC_BF16X2))
+    if (!d_V || !d_U || !d_M || (precision != FH_PREC_FP32 && precision != FH_PREC_BF16X2 && precision != FH_PREC_F32X3))
         return arg_error("fh_debug_wino_gemm_dev: bad argument");
     fh::WinoPlanes pl{};
     const long long rows = wino_gemm_rows(batch, h, w, k, n, mixed, &pl);
     if (rows == -2) return arg_error("fh_debug_wino_gemm_dev: the mixed tiling does not apply to this layer");
     if (rows < 0) return arg_error("fh_debug_wino_gemm_dev: bad argument (k % 32 == 0, n % 32 == 0)");
-    const bool bf2 = precision == FH_PREC_BF16X2;
+    const bool bf2 = precision == FH_PREC_BF16X2, x3 = precision == FH_PREC_F32X3;
     Owns owns(nullptr);                                                  // (no Net: the process-wide watchdog record)
     return guarded([&] {
-        if (bf2 && !fh::wino_gemm_ok_bf16x2(k, n)) throw std::runtime_error("winograd: this layer has no split-bf16 GEMM");
+        if ((bf2 || x3) && !fh::wino_gemm_ok_bf16x2(k, n)) throw std::runtime_error("winograd: this layer has no split-bf16 GEMM");
         const size_t nv = (size_t)rows * k, nu = (size_t)36 * fh::conv_wt_rows(n) * k;
         fh::DevBuf dVp, dUp;
         if (bf2) {                                                       // the caller's operands stay f32: packed copies
             dVp.ensure(nv * sizeof(float)); dUp.ensure(nu * sizeof(float));
             fh::launch_pack_bf16x2(d_V, dVp.as<float>(), (long)nv, S(stream));
             fh::launch_pack_bf16x2(d_U, dUp.as<float>(), (long)nu, S(stream));
+        } else if (x3) {                                                 // V stays the caller's f32; U split here as Net::set_wino_x3 does
+            dUp.ensure(36 * fh::wino_x3_floats(fh::conv_wt_rows(n), k) * sizeof(float));
+            fh::launch_pack_x3(d_U, dUp.as<float>(), fh::conv_wt_rows(n), k, S(stream));
         }
         fh::ConvArgs a{};
         a.B = batch; a.H = h; a.W = w; a.Ho = h; a.Wo = w; a.Cin = k; a.Cout = n; a.ks = 3; a.stride = 1; a.pad = 1;
         a.act = (int)fh::Act::NONE; a.res_mode = (int)fh::ResMode::NONE;
-        fh::launch_wino_gemm(a, bf2 ? dUp.as<float>() : d_U, bf2 ? dVp.as<float>() : d_V, d_M, 2, bf2, S(stream), mixed ? &pl : nullptr);
+        fh::launch_wino_gemm(a, bf2 || x3 ? dUp.as<float>() : d_U, bf2 ? dVp.as<float>() : d_V, d_M, 2, precision, S(stream), mixed ? &pl : nullptr);
         FH_HIP(hipGetLastError());
         FH_HIP(hipStreamSynchronize(S(stream)));                 // the packed copies die with this scope
         return 0;

@@ -218,6 +218,7 @@ Net::Net(const std::string& onnx_path, int default_h, int default_w) {
                 }
                 d.w36 = push(u36.data(), u36.size());
                 d.w36n = u36.size();
+                d.w36k = op.Cin;
                 d.wino = true;
                 d.bf2 = wino_gemm_ok_bf16x2(op.Cin, op.Cout);
                 const size_t tiles = (size_t)((op.H + 3) / 4) * ((op.W + 3) / 4);
@@ -427,6 +428,21 @@ int Net::set_bf16x2(bool on, hipStream_t s) {
     return on ? layers : 0;
 }
 
+int Net::set_wino_x3(bool on, hipStream_t s) {
+    int layers = 0;
+    size_t total = 0;
+    for (auto& d : dev_)
+        if (d.wino && d.bf2) { d.w36x = total; total += 36 * wino_x3_floats((int)(d.w36n / 36 / d.w36k), d.w36k); ++layers; }
+    if (on && layers > 0 && w36_x3_.bytes < total * sizeof(float)) {       // split once, on the device; the f32 image stays (the switch needs it)
+        w36_x3_.ensure(total * sizeof(float));
+        for (const auto& d : dev_)
+            if (d.wino && d.bf2) launch_pack_x3(params_.as<float>() + d.w36, w36_x3_.as<float>() + d.w36x, (int)(d.w36n / 36 / d.w36k), d.w36k, s);
+        FH_HIP(hipStreamSynchronize(s));
+    }
+    wino_x3_ = on && layers > 0;
+    return on ? layers : 0;
+}
+
 void Net::run(int batch, hipStream_t s, int first_op) {
     if (batch <= 0) return;
     if ((sk_gen_ != conv_error_generation() || conv_error_pending(sk_rec_.p)) && partial_.p) {   // a stream-K hand-off timed out somewhere since: late helper arrivals may have
@@ -509,6 +525,10 @@ void Net::run(int batch, hipStream_t s, int first_op) {
                     // the producer of V and the consumer must agree: the decision depends on the map and the batch only
                     WinoPlanes pl;
                     const bool mix = wcfg == 2 && wino_mix_layout(batch, op.H, op.W, op.Cin, op.Cout, &pl);
+                    // the fp32 path's GEMM: three-piece bf16 (fp32 results, gemm_tile.h) where the handle has it on and the launch pays
+                    const long row_tiles = mix ? pl.total_tiles : 36 * wino_rows((long)batch * ((op.H + 3) / 4) * ((op.W + 3) / 4)) / 128;
+                    const bool x3 = !bf2 && wino_x3_ && d.bf2 && force_cfg < 0 && wcfg == 2 && wino_x3_pays(row_tiles, op.Cin, op.Cout);
+                    const float* const u36 = bf2 ? w36_bf_.as<float>() + d.w36p : x3 ? w36_x3_.as<float>() + d.w36x : P + d.w36;
                     if (!v_ready) {                                     // (else the previous layer's fused transform already wrote V)
                         const float* in_s = nullptr; const float* in_t = nullptr;
                         if (d.aff_src >= 0) {
@@ -518,8 +538,7 @@ void Net::run(int batch, hipStream_t s, int first_op) {
                         if (mix) launch_wino_mix(a, pl, nullptr, wino_v_.as<float>(), 0, in_s, in_t, bf2, s);
                         else launch_wino_input(a, wino_v_.as<float>(), in_s, in_t, bf2, s);
                     }
-                    launch_wino_gemm(a, bf2 ? w36_bf_.as<float>() + d.w36p : P + d.w36, wino_v_.as<float>(), wino_m_.as<float>(), wcfg, bf2, s,
-                                     mix ? &pl : nullptr);
+                    launch_wino_gemm(a, u36, wino_v_.as<float>(), wino_m_.as<float>(), wcfg, bf2 ? 1 : x3 ? 2 : 0, s, mix ? &pl : nullptr);
                     v_ready = false;
                     if (d.fuse_next && fuse_wino && i + 1 < plan_.ops.size()) {
                         const POp& nx = plan_.ops[i + 1];
@@ -866,6 +885,7 @@ void Detector::detect_dev(const uint8_t* frames, int n, int rows, int cols, int 
 Recognizer::Recognizer(const std::string& onnx_path) : net_(onnx_path, 112, 112) {      // src/face_recognizer.cpp:8-9
     const auto& o = net_.plan().outputs.at(0);
     dim_ = o.rows * o.cols;                       // feature size comes from the output shape (:286-294)
+    if (wino_x3_default()) net_.set_wino_x3(true, nullptr);      // the fp32 mode's Winograd GEMMs: three-piece bf16 (FACEHIP_WINO_X3=0: native f32)
 }
 
 void Recognizer::embed_aligned_dev(const uint8_t* crops, int n, float* out, hipStream_t s, float* raw_out) {

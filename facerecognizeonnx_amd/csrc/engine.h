@@ -64,6 +64,11 @@ class Net {
     // f32 accumulate); transforms, epilogues and every other layer stay fp32.  Returns the number of layers that switch.
     int set_bf16x2(bool on, hipStream_t s);
     bool bf16x2() const { return bf16x2_; }
+    // the fp32 mode's Winograd GEMMs as six bf16 MFMAs on three-piece operands (fp32 results, not bit-identical to the f32 MFMA; gemm_tile.h):
+    // the recogniser's default (fh_rec_set_wino_x3, FACEHIP_WINO_X3), off for every other Net.  on: the weights are split once, on the
+    // device, into a second image of 1.5 x the f32 one's bytes.  Returns the number of layers that have the form.
+    int set_wino_x3(bool on, hipStream_t s);
+    bool wino_x3() const { return wino_x3_; }
     int cus = 0;                                          // CUs of the stream this net runs on when it is CU-masked (0 = all)
     int force_cfg = -1;                                   // tuning hook: conv tile config override
     bool sk_enable = true;                                // tuning hook: stream-K remainder wave
@@ -72,7 +77,7 @@ class Net {
     long long config_word() const {
         return (long long)fuse_stem | (long long)fuse_front << 1 | (long long)winograd << 2 | (long long)halo_conv << 3 |
                (long long)fold_shortcut << 4 | (long long)fuse_wino << 5 | (long long)bf16x2_ << 6 | (long long)sk_enable << 7 |
-               (long long)(cus & 0xffff) << 8 | (long long)((force_cfg + 1) & 0xff) << 24;
+               (long long)(cus & 0xffff) << 8 | (long long)((force_cfg + 1) & 0xff) << 24 | (long long)wino_x3_ << 32;
     }
 
   private:
@@ -85,7 +90,9 @@ class Net {
         size_t dww = 0, dwb = 0;                              // fused depthwise front end (DWPW)
         size_t w36 = 0;                                       // Winograd F(4,3) weights U[36][rows][Cin]
         size_t w36n = 0, w36p = 0;                            // ... their float count; offset of the split-bf16 copy in w36_bf_ (bf2 layers)
-        bool bf2 = false;                                     // this layer's GEMM has a split-bf16 form
+        size_t w36x = 0;                                      // ... offset of the three-piece (x3) image in w36_x3_ (bf2 layers)
+        int w36k = 0;                                         // ... Cin
+        bool bf2 = false;                                     // this layer's GEMM has a split-bf16 (and a three-piece) form
         size_t wfrag = 0;                                     // halo-conv weights in MFMA fragment order (conv_halo.hip)
         bool halo = false;                                    // eligible for the spatial-tile 3x3 kernel
         bool wino = false;                                    // eligible: 3x3 stride 1 pad 1, Cin >= 128
@@ -113,8 +120,8 @@ class Net {
     float* tensor_ptr(int t) const { return arena_.as<float>() + plan_.tensors[t].offset * (size_t)cap_; }
     Plan plan_;
     std::vector<DevOp> dev_;
-    DevBuf params_, arena_, partial_, wino_v_, wino_m_, w36_bf_;
-    bool bf16x2_ = false;
+    DevBuf params_, arena_, partial_, wino_v_, wino_m_, w36_bf_, w36_x3_;
+    bool bf16x2_ = false, wino_x3_ = false;
     size_t wino_maxc_ = 0;
     size_t wino_elems_ = 0;                                   // per image: 36 * tiles * max(Cin, Cout) of the largest Winograd op
     int cap_ = 0;

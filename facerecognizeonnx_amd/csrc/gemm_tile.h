@@ -1,5 +1,5 @@
 // gemm_tile.h — the "lean GEMM" tile: ONE loader, ONE K-chunk body and ONE turn-around store, shared by wino_gemm_kernel,
-// wino_gemm_pers_kernel, wino_gemm_bf16x2_kernel (winograd.hip) and conv_pw_kernel (conv_mfma.hip); with it the vector typedefs, the
+// wino_gemm_pers_kernel, wino_gemm_bf16x2_kernel, wino_gemm_x3_kernel (winograd.hip) and conv_pw_kernel (conv_mfma.hip); with it the vector typedefs, the
 // LDS-DMA wrapper and the XCD-contiguous tile order every .hip file of the library uses.
 //
 // The tile: 128 rows of the "pixel" operand (V / the activations) x BN rows of the weight operand, both with contiguous rows of K
@@ -177,6 +177,109 @@ __device__ __forceinline__ void gemm_mma_bf16x2(v16f (&acc)[TN], const v4f* cons
             acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh, xh, acc[j], 0, 0, 0);
         }
     }
+}
+
+// ---- the three-piece bf16 form ("x3"): fp32 products from six bf16 MFMAs.  V stays plain fp32 in memory and in LDS and is split in
+// registers; U was split once (wino_pack_x3_kernel, winograd.hip) into three bf16 planes stored as the LDS image itself.
+// THE SPLIT RULE (one rule for both operands; tests/wino_x3_model.py states the same):
+//     h = x with its low 16 bits cleared (truncation: never overflows, a finite x gives a finite h)
+//     m = bf16_rne(x - h)          (x - h is exact in fp32; |x - h| < 2^-7 |x|, so the rounding cannot overflow either)
+//     l = bf16_rne(x - h - m)      (exact in fp32, and a multiple of x's last bit with at most 8 significant bits: the rounding is exact)
+// so x = h + m + l exactly for every finite x whose pieces are zero or bf16-normal, with |m| <= 2^-7 |x| and |l| <= 2^-16 |x|.  +-Inf
+// gives (Inf, NaN, NaN), NaN gives (NaN or Inf, NaN, NaN): a non-finite operand always leaves a NaN piece that meets every product.
+// THE PRODUCT ORDER, per output and 16-deep step (w = weight piece, x = pixel piece), smallest first:
+//     w_l x_h,  w_h x_l,  w_m x_m,  w_m x_h,  w_h x_m,  w_h x_h        (dropped: m l, l m, l l <= 2^-23 + 2^-23 + 2^-32 of |w x|)
+// Order of additions per output: ks (two 16-deep steps per chunk), then the six products in this order.
+typedef float v2f_ __attribute__((ext_vector_type(2)));
+typedef __bf16 bf16x2_ __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ void gemm_split3(const v4f lo4, const v4f hi4, bf16x8& h, bf16x8& m, bf16x8& l) {   // 8 fp32 -> 8 h, 8 m, 8 l
+    v4u hw, mw, lw;
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+        const float a = p < 2 ? lo4[2 * p] : hi4[2 * p - 4], b = p < 2 ? lo4[2 * p + 1] : hi4[2 * p - 3];
+        const unsigned ab = __builtin_bit_cast(unsigned, a), bb = __builtin_bit_cast(unsigned, b);
+        hw[p] = __builtin_amdgcn_perm(bb, ab, 0x07060302u);                                               // (a's high half, b's high half)
+        const v2f_ r = {a - __builtin_bit_cast(float, ab & 0xffff0000u), b - __builtin_bit_cast(float, bb & 0xffff0000u)};
+        mw[p] = __builtin_bit_cast(unsigned, __builtin_convertvector(r, bf16x2_));                       // v_cvt_pk_bf16_f32
+        const v2f_ q = {r[0] - __builtin_bit_cast(float, mw[p] << 16), r[1] - __builtin_bit_cast(float, mw[p] & 0xffff0000u)};
+        lw[p] = __builtin_bit_cast(unsigned, __builtin_convertvector(q, bf16x2_));
+    }
+    h = __builtin_bit_cast(bf16x8, hw); m = __builtin_bit_cast(bf16x8, mw); l = __builtin_bit_cast(bf16x8, lw);
+}
+
+// The x3 tile buffer: the fp32 pixel image of the f32 tile ([128 rows][8 float4 columns], same swizzle), then three weight planes h, m, l
+// of [BN rows][4 slots of 8 bf16] — slot q of row n holds k = 8 q .. 8 q + 7 of the 32-deep chunk and sits at column q ^ ((n >> 2) & 3):
+// the 16 lanes of a ds_read_b128 group (rows of one residue mod 4 with four different n >> 2 & 3) then hit 64 different banks.
+// 6 bytes per weight element: 128 x 64 tiles 28 KB per buffer (56 KB), 128 x 128 tiles 40 KB (80 KB: two workgroups fill a CU's 160 KB).
+// The global x3 image of U is this layout for whole [rows][32 k] chunks: [frequency][plane][chunk][row][4 slots], so a wave's LDS-DMA
+// request reads 1 KB of consecutive bytes.
+template <int BN> constexpr int gemm_buf_slots_x3() { return GEMM_BM * 8 + 3 * BN * 4; }
+template <int BN> using GemmLdsX3 = v4f[2][gemm_buf_slots_x3<BN>()];
+struct GemmSrcX3 {
+    const float* a;
+    const v4f* b;             // this thread's 16 bytes of plane h, pass 0, current chunk
+    size_t a32, bplane, bchunk;     // floats between 32-row passes of V; float4s between planes / chunks of U
+    v4f* dA;
+    v4f* dB;
+};
+// ... for the tile at row m0 of A [rows][lda] and row n0 of the x3 image B3 (one frequency) of `brows` rows and `chunks` chunks
+template <int BN>
+__device__ __forceinline__ GemmSrcX3 gemm_src_x3(GemmLdsX3<BN>& lds, const float* A, const int m0, const int lda, const float* B3, const int n0,
+                                                 const int brows, const int chunks, const GemmLane& l) {
+    return GemmSrcX3{A + (size_t)(m0 + l.lrow()) * lda + l.lqs() * 4, reinterpret_cast<const v4f*>(B3) + (size_t)n0 * 4 + l.tid, (size_t)32 * lda,
+                     (size_t)chunks * brows * 4, (size_t)brows * 4, &lds[0][l.wid * 64], &lds[0][GEMM_BM * 8 + l.wid * 64]};
+}
+template <int BN>
+__device__ __forceinline__ void gemm_load_chunk_x3(GemmSrcX3& s, const int buf) {
+    v4f* const dA = s.dA + buf * gemm_buf_slots_x3<BN>();
+    v4f* const dB = s.dB + buf * gemm_buf_slots_x3<BN>();
+#pragma unroll
+    for (int i = 0; i < GEMM_BM / 32; ++i) lds_dma16(s.a + i * s.a32, dA + i * 32 * 8);
+#pragma unroll
+    for (int p = 0; p < 3; ++p)
+#pragma unroll
+        for (int i = 0; i < BN / 64; ++i) lds_dma16(reinterpret_cast<const float*>(s.b + p * s.bplane + i * 256), dB + p * BN * 4 + i * 256);
+    s.a += 32; s.b += s.bchunk;
+}
+template <int TN>
+__device__ __forceinline__ void gemm_mma_x3(v16f (&acc)[TN], const v4f* const tile, const GemmLane& l) {
+    constexpr int PL = TN * 32 * 4;                                          // float4 slots per weight plane
+    const v4f* const X = tile + l.wid * (32 * 8) + l.fr * 8;
+    const v4f* const Wt = tile + GEMM_BM * 8 + l.fr * 4;
+    const int wsw = (l.fr >> 2) & 3;
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) {
+        const int c0 = (4 * ks + 2 * l.fh2) ^ l.fsw, c1 = (4 * ks + 2 * l.fh2 + 1) ^ l.fsw;
+        const int wc = (2 * ks + l.fh2) ^ wsw;
+        bf16x8 xh, xm, xl, wh[TN], wm[TN], wl[TN];
+#pragma unroll
+        for (int j = 0; j < TN; ++j) {
+            wh[j] = __builtin_bit_cast(bf16x8, Wt[j * 32 * 4 + wc]);
+            wm[j] = __builtin_bit_cast(bf16x8, Wt[PL + j * 32 * 4 + wc]);
+            wl[j] = __builtin_bit_cast(bf16x8, Wt[2 * PL + j * 32 * 4 + wc]);
+        }
+        gemm_split3(X[c0], X[c1], xh, xm, xl);
+        // (product outer, j inner: consecutive MFMAs write different accumulators; per accumulator the order is the documented one)
+#pragma unroll
+        for (int j = 0; j < TN; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wl[j], xh, acc[j], 0, 0, 0);
+#pragma unroll
+        for (int j = 0; j < TN; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh[j], xl, acc[j], 0, 0, 0);
+#pragma unroll
+        for (int j = 0; j < TN; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wm[j], xm, acc[j], 0, 0, 0);
+#pragma unroll
+        for (int j = 0; j < TN; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wm[j], xh, acc[j], 0, 0, 0);
+#pragma unroll
+        for (int j = 0; j < TN; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh[j], xm, acc[j], 0, 0, 0);
+#pragma unroll
+        for (int j = 0; j < TN; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh[j], xh, acc[j], 0, 0, 0);
+    }
+}
+// the K-chunk body: request the next chunk, multiply the current one, barrier (as gemm_chunk_f32)
+template <int BN>
+__device__ __forceinline__ void gemm_chunk_x3(v16f (&acc)[BN / 32], GemmLdsX3<BN>& lds, const int buf, const bool more, GemmSrcX3& src, const GemmLane& l) {
+    if (more) gemm_load_chunk_x3<BN>(src, buf ^ 1);
+    gemm_mma_x3<BN / 32>(acc, lds[buf], l);
+    __syncthreads();
 }
 
 // ---- stores: a wave's 32 x (32 TN) accumulator block -> M [rows][N] as whole lines.  A lane's accumulators are 4-column pieces of

@@ -154,16 +154,23 @@ void launch_dwpw(const ConvArgs& a, hipStream_t s);
 // Winograd F(4x4,3x3) form of a 3x3 stride-1 pad-1 convolution (winograd.hip): a = the convolution's arguments,
 // wt36 = U[36][conv_wt_rows(Cout)][Cin], V / M = workspaces of 36 * tiles * max(Cin, Cout) floats each
 // in_scale / in_shift (optional): per-input-channel affine applied to in-image pixels by the input transform
-// bf16x2: the split-bf16 operand format below (wt36 already packed; the input transform packs V)
+// prec: 0 = native f32; 1 = the split-bf16 operand format below (wt36 already packed; the input transform packs V); 2 = the three-piece
+// bf16 GEMM (wt36 = the launch_pack_x3 image; V stays fp32)
 void launch_conv_winograd(const ConvArgs& a, const float* wt36, float* V, float* M, int cfg, const float* in_scale, const float* in_shift,
-                          hipStream_t s, bool bf16x2 = false);
+                          hipStream_t s, int prec = 0);
 // the three stages separately, and stage 3 of one convolution fused with stage 1 of the next (same map, C = Cout = next Cin)
 // pack / bf16x2 / pack_next: the opt-in split-bf16 operand format (V and U as (hi, mid) bf16 pairs in 32-bit words, see winograd.hip)
 struct WinoPlanes;
 void launch_wino_input(const ConvArgs& a, float* V, const float* in_scale, const float* in_shift, bool pack, hipStream_t s);
-void launch_wino_gemm(const ConvArgs& a, const float* wt36, const float* V, float* M, int cfg, bool bf16x2, hipStream_t s,
-                      const WinoPlanes* mix = nullptr);   // mix: V / M in the mixed-tiling layout (lean kernel only)
-bool wino_gemm_ok_bf16x2(int Cin, int Cout);
+void launch_wino_gemm(const ConvArgs& a, const float* wt36, const float* V, float* M, int cfg, int prec, hipStream_t s,
+                      const WinoPlanes* mix = nullptr);   // mix: V / M in the mixed-tiling layout (lean kernel only); prec as above
+bool wino_gemm_ok_bf16x2(int Cin, int Cout);              // ... which also says whether the layer has the three-piece (x3) form
+// Three-piece bf16 GEMM ("x3", gemm_tile.h): fp32 U [36][rows][K] -> its x3 image of 36 * wino_x3_floats(rows, K) floats; whether a handle's
+// fp32 path uses it by default (FACEHIP_WINO_X3, read once); whether it pays for a launch of row_tiles 128-row tiles
+void launch_pack_x3(const float* in, float* out, int rows, int K, hipStream_t s);
+inline size_t wino_x3_floats(int rows, int K) { return (size_t)rows * K * 3 / 2; }
+bool wino_x3_default();
+bool wino_x3_pays(long row_tiles, int Cin, int Cout);
 void launch_wino_output(const ConvArgs& a, const float* M, hipStream_t s);
 bool wino_can_fuse(int H, int W, int C, bool touches_memory);
 void launch_wino_fused(const ConvArgs& a, const float* M, float* Vnext, int feed_aff, bool pack_next, hipStream_t s);

@@ -22,6 +22,7 @@
 #include <algorithm>
 #include <cstdlib>
 #include <stdexcept>
+#include <type_traits>
 
 #include "gemm_tile.h"
 #include "kernels.h"
@@ -37,6 +38,25 @@ __global__ __launch_bounds__(256) void pack_bf16x2_kernel(const float* __restric
 void launch_pack_bf16x2(const float* in, float* out, long n, hipStream_t s) {       // n % 4 == 0
     const long n4 = n / 4;
     if (n4 > 0) hipLaunchKernelGGL(pack_bf16x2_kernel, dim3((unsigned)std::min<long>((n4 + 255) / 256, 256 * 64)), dim3(256), 0, s, in, out, n4);
+}
+
+// fp32 U [36][rows][K] -> the x3 image (gemm_tile.h: three bf16 planes per frequency in LDS order, wino_x3_floats(rows, K) floats each).
+// One thread per 8 consecutive k of a row.
+__global__ __launch_bounds__(256) void wino_pack_x3_kernel(const float* __restrict__ in, v4u* __restrict__ out, int rows, int K, long n8) {
+    const int k8n = K >> 3, chunks = K >> 5;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n8; i += (long)gridDim.x * 256) {
+        const int k8 = (int)(i % k8n), n = (int)(i / k8n % rows), f = (int)(i / k8n / rows);
+        const float* src = in + ((size_t)f * rows + n) * K + 8 * k8;
+        bf16x8 h, m, l;
+        gemm_split3(*reinterpret_cast<const v4f*>(src), *reinterpret_cast<const v4f*>(src + 4), h, m, l);
+        const size_t plane = (size_t)chunks * rows * 4;
+        v4u* o = out + (size_t)f * 3 * plane + ((size_t)(k8 >> 2) * rows + n) * 4 + ((k8 & 3) ^ ((n >> 2) & 3));
+        o[0] = __builtin_bit_cast(v4u, h); o[plane] = __builtin_bit_cast(v4u, m); o[2 * plane] = __builtin_bit_cast(v4u, l);
+    }
+}
+void launch_pack_x3(const float* in, float* out, int rows, int K, hipStream_t s) {    // K % 32 == 0; out: 36 * wino_x3_floats(rows, K) floats
+    const long n8 = 36L * rows * (K / 8);
+    if (n8 > 0) hipLaunchKernelGGL(wino_pack_x3_kernel, dim3((unsigned)std::min<long>((n8 + 255) / 256, 256 * 64)), dim3(256), 0, s, in, reinterpret_cast<v4u*>(out), rows, K, n8);
 }
 
 // in [B,H,W,C] -> V [36][NT][C], NT = B*TY*TX tiles of 4x4 outputs (input patch rows 4ty-1 .. 4ty+4)
@@ -304,29 +324,32 @@ __global__ __launch_bounds__(256, OCC) void wino_gemm_kernel(const float* __rest
 // stores in flight) with a raw s_barrier — `__syncthreads()` would drain the stores too.  Results are bit-identical to wino_gemm_kernel
 // (same tile arithmetic in the same order).  MEASURED AND NOT THE DEFAULT (see wino_pers_enabled): kept behind FACEHIP_WINO_PERS=1 as the
 // record of the experiment the round-4 review asked for, with its own oracle test.
-template <int BN, int OCC>
+// X3: the three-piece bf16 step (gemm_mma_x3) on the x3 tile buffers; U is then the x3 image and wt_gs its floats per frequency.
+template <int BN, int OCC, bool X3 = false>
 __global__ __launch_bounds__(256, OCC) void wino_gemm_pers_kernel(const float* __restrict__ V, const float* __restrict__ U, float* __restrict__ M,
                                                                  const int K, const int N, const WinoPlanes pl, const long wt_gs,
                                                                  const int tiles_n, const int chunks, const int ntiles) {
     constexpr int BM = GEMM_BM, TN = BN / 32;
-    constexpr int BUF = gemm_buf_slots<BN>();
+    constexpr int BUF = X3 ? gemm_buf_slots_x3<BN>() : gemm_buf_slots<BN>();
     __shared__ v4f lds[2][BUF];
     const GemmLane l = gemm_lane();
     // XCD-contiguous tile order over the VIRTUAL block index (gridDim.x is a multiple of 8: vb % 8 = this workgroup's XCD for every vb)
     auto tile_of = [&](int vb) { return xcd_tile(vb, ntiles); };
-    GemmSrc src;
+    typename std::conditional<X3, GemmSrcX3, GemmSrc>::type src;
     auto point_at = [&](int tile) {
         const int tile_n = tile % tiles_n, tile_m = tile / tiles_n;
         const float* Ug = U + (size_t)wino_plane_freq(pl, tile_m) * wt_gs;
-        src = gemm_src<BN>(lds, V, tile_m * BM, K, Ug, tile_n * BN, K, l);
+        if constexpr (X3) src = gemm_src_x3<BN>(lds, V, tile_m * BM, K, Ug, tile_n * BN, (int)(wt_gs * 2 / 3 / K), chunks, l);
+        else src = gemm_src<BN>(lds, V, tile_m * BM, K, Ug, tile_n * BN, K, l);
     };
+    auto load_chunk = [&](int buf) { if constexpr (X3) gemm_load_chunk_x3<BN>(src, buf); else gemm_load_chunk<BN>(src, buf); };
     // turn-around in 32-column blocks: 4 waves x 32 x 36 floats = 18 KB <= one buffer
     using Store = GemmStore<TN, 1>;
     static_assert(Store::BYTES <= BUF * sizeof(v4f), "store scratch must fit ONE tile buffer");
     int base = 0;                                                           // buffer that holds the current tile's chunk 0
     int vb = blockIdx.x;
     point_at(tile_of(vb));
-    gemm_load_chunk<BN>(src, 0);
+    load_chunk(0);
     __syncthreads();
     for (;;) {
         const int tile = tile_of(vb);
@@ -336,14 +359,17 @@ __global__ __launch_bounds__(256, OCC) void wino_gemm_pers_kernel(const float* _
         for (int j = 0; j < TN; ++j)
 #pragma unroll
             for (int e = 0; e < 16; ++e) acc[j][e] = 0.f;
-        for (int kc = 0; kc < chunks; ++kc) gemm_chunk_f32<BN>(acc, lds, (base + kc) & 1, kc + 1 < chunks, src, l);
+        for (int kc = 0; kc < chunks; ++kc) {
+            if constexpr (X3) gemm_chunk_x3<BN>(acc, lds, (base + kc) & 1, kc + 1 < chunks, src, l);
+            else gemm_chunk_f32<BN>(acc, lds, (base + kc) & 1, kc + 1 < chunks, src, l);
+        }
         // every wave is past the last chunk: both buffers are free.  last = the buffer of the final chunk -> scratch; the other -> next tile
         const int last = (base + chunks - 1) & 1;
         const int nvb = vb + gridDim.x;
         const bool more = nvb < ntiles;
         if (more) {
             point_at(tile_of(nvb));
-            gemm_load_chunk<BN>(src, last ^ 1);
+            load_chunk(last ^ 1);
 #if defined(__HIP_DEVICE_COMPILE__)
             __builtin_amdgcn_sched_barrier(0);                              // (the DMA is issued in front of the stores it is counted against)
 #endif
@@ -388,6 +414,33 @@ __global__ __launch_bounds__(256, OCC) void wino_gemm_bf16x2_kernel(const float*
         gemm_mma_bf16x2<TN>(acc, lds[buf], l);
         __syncthreads();
     }
+    static_assert(GemmStore<TN, JB>::BYTES <= sizeof(lds), "store scratch");
+    gemm_store_lines<TN, JB>(acc, reinterpret_cast<float*>(&lds[0][0]), M, N, m0, n0, l.wid, l.lane);
+}
+
+// Three-piece bf16 form of the same GEMM (gemm_tile.h, "x3"): fp32 results from six v_mfma_f32_32x32x16_bf16 per 16-deep step instead of
+// eight v_mfma_f32_32x32x2_f32 — 192 matrix-pipe cycles per 32x32 block against 512.  V is the f32 kernel's V; U is the x3 image
+// (launch_pack_x3) and wt_gs its floats per frequency, from which the image's row count conv_wt_rows(N) follows.
+template <int BN, int OCC>
+__global__ __launch_bounds__(256, OCC) void wino_gemm_x3_kernel(const float* __restrict__ V, const float* __restrict__ U, float* __restrict__ M,
+                                                               const int K, const int N, const WinoPlanes pl, const long wt_gs,
+                                                               const int tiles_n, const int chunks) {
+    constexpr int BM = GEMM_BM, TN = BN / 32, JB = TN >= 2 ? 2 : 1;
+    __shared__ v4f lds[2][gemm_buf_slots_x3<BN>()];
+    const GemmLane l = gemm_lane();
+    const int tile = xcd_tile(blockIdx.x, gridDim.x);
+    const int tile_n = tile % tiles_n, tile_m = tile / tiles_n;
+    const int m0 = tile_m * BM, n0 = tile_n * BN;
+    const float* Ug = U + (size_t)wino_plane_freq(pl, tile_m) * wt_gs;
+    GemmSrcX3 src = gemm_src_x3<BN>(lds, V, m0, K, Ug, n0, (int)(wt_gs * 2 / 3 / K), chunks, l);
+    v16f acc[TN];
+#pragma unroll
+    for (int j = 0; j < TN; ++j)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) acc[j][e] = 0.f;
+    gemm_load_chunk_x3<BN>(src, 0);
+    __syncthreads();
+    for (int kc = 0; kc < chunks; ++kc) gemm_chunk_x3<BN>(acc, lds, kc & 1, kc + 1 < chunks, src, l);
     static_assert(GemmStore<TN, JB>::BYTES <= sizeof(lds), "store scratch");
     gemm_store_lines<TN, JB>(acc, reinterpret_cast<float*>(&lds[0][0]), M, N, m0, n0, l.wid, l.lane);
 }
@@ -489,7 +542,34 @@ bool wino_mix_layout(int B, int H, int W, int Cin, int Cout, WinoPlanes* out) {
     return true;
 }
 
-void launch_wino_gemm(const ConvArgs& a, const float* wt36, const float* V, float* M, int cfg, bool bf16x2, hipStream_t s, const WinoPlanes* mix) {
+// x3 default of the recogniser's fp32 path (FACEHIP_WINO_X3=0: the native f32 GEMMs), read once
+bool wino_x3_default() {
+    static const int v = [] { const char* e = getenv("FACEHIP_WINO_X3"); return e ? atoi(e) : 1; }();
+    return v != 0;
+}
+// 128x128 or 128x64 x3 tiles?  Both shapes hold two workgroups per CU (80 and 56 KB of LDS).  Measured on IResNet-50 at B = 128 (GEMM sum of
+// the 38 launches, three alternating runs each): wide tiles everywhere 2 246-2 252 us, narrow everywhere 2 503-2 514 — per layer 54 against 61 us
+// (14x14x256), 104 against 124-128 (28x28, 128 -> 256), 70 against 70-72 (7x7x512): half the V traffic per FLOP and half the LDS-DMA
+// requests per MFMA.  So: wide wherever the launch has at least one wide tile per slot; below that the narrow tile, which fills twice as
+// many slots.  FACEHIP_WINO_X3_BN = 64 / 128 forces one (A / B timing).
+static bool wino_x3_pick_bn128(long row_tiles, int Cout, int cus) {
+    static const int force = [] { const char* e = getenv("FACEHIP_WINO_X3_BN"); return e ? atoi(e) : 0; }();
+    if (Cout % 128) return false;
+    if (force) return force == 128;
+    return row_tiles * (Cout / 128) >= wino_slots(2, cus);
+}
+// Does the x3 kernel pay for this launch?  The per-shape predicate of the engine: a layer class where it measured no faster than the f32
+// kernel would stay f32 here.  None does: on IResNet-50 (x3 against f32, alternating runs; the f32 side's own spread is 1-4 %) 28x28x128
+// 76-80 -> 57-65 us, 14x14x256 (mixed tiling) 74-78 -> 53-55, 7x7x512 91-96 -> 69-73 at B = 128; 47 -> 40, 52 -> 45, 58 -> 44 at B = 64;
+// 148 -> 120, 147 -> 101, 168 -> 123 at B = 256 (profiles/wino_x3.md).
+bool wino_x3_pays(long row_tiles, int Cin, int Cout) {
+    (void)row_tiles; (void)Cin; (void)Cout;
+    return true;
+}
+
+// prec: 0 = the native f32 kernels, 1 = split-bf16 words in V and wt36 (FH_PREC_BF16X2), 2 = x3: V fp32, wt36 the x3 image (FH_PREC_F32X3)
+void launch_wino_gemm(const ConvArgs& a, const float* wt36, const float* V, float* M, int cfg, int prec, hipStream_t s, const WinoPlanes* mix) {
+    const bool bf16x2 = prec == 1, x3 = prec == 2;
     const int TY = (a.H + 3) / 4, TX = (a.W + 3) / 4;
     const long NT = (long)a.B * TY * TX;
     if (NT <= 0) return;
@@ -531,7 +611,15 @@ void launch_wino_gemm(const ConvArgs& a, const float* wt36, const float* V, floa
             return true;
         };
         timer.begin(s);
-        if (bf16x2) {
+        if (x3) {
+            if (!wino_gemm_ok_bf16x2(a.Cin, a.Cout)) throw std::runtime_error("winograd: this layer has no three-piece bf16 GEMM");
+            g.wt_gs = (long)wino_x3_floats(conv_wt_rows(a.Cout), a.Cin);
+            if (wino_x3_pick_bn128(row_tiles, a.Cout, a.cus)) {
+                if (!launch_pers(wino_gemm_pers_kernel<128, 2, true>, 128, 2)) launch(wino_gemm_x3_kernel<128, 2>, 128);
+            } else {
+                if (!launch_pers(wino_gemm_pers_kernel<64, 2, true>, 64, 2)) launch(wino_gemm_x3_kernel<64, 2>, 64);
+            }
+        } else if (bf16x2) {
             if (!wino_gemm_ok_bf16x2(a.Cin, a.Cout)) throw std::runtime_error("winograd: this layer has no split-bf16 GEMM");
             launch(wino_gemm_bf16x2_kernel<64, 3>, 64);
         } else if (wide && a.Cout % 128 == 0 && wino_pick_bn128(row_tiles, a.Cout, mix != nullptr, a.cus)) {
@@ -552,7 +640,7 @@ void launch_wino_gemm(const ConvArgs& a, const float* wt36, const float* V, floa
             launch(wino_gemm_kernel<32, 4>, 32);
         timer.end(s, 7, g.t_flops, g.t_bytes);
     } else {
-        if (bf16x2) throw std::runtime_error("winograd: this layer has no split-bf16 GEMM");
+        if (bf16x2 || x3) throw std::runtime_error("winograd: this layer has no split-bf16 GEMM");
         launch_conv(g, cfg, s);                              // generic grouped instantiation of conv_igemm_kernel
     }
 }
@@ -717,16 +805,17 @@ void launch_wino_mix(const ConvArgs& a, const WinoPlanes& pl, const float* M, fl
 
 // all three stages of one convolution (used by the single-layer test entry point); bf16x2: wt36 holds split-bf16 words, V is packed
 void launch_conv_winograd(const ConvArgs& a, const float* wt36, float* V, float* M, int cfg, const float* in_scale, const float* in_shift,
-                          hipStream_t s, bool bf16x2) {
+                          hipStream_t s, int prec) {
+    const bool bf16x2 = prec == 1;
     WinoPlanes pl;
     if (cfg == 2 && wino_mix_layout(a.B, a.H, a.W, a.Cin, a.Cout, &pl)) {
         launch_wino_mix(a, pl, nullptr, V, 0, in_scale, in_shift, bf16x2, s);
-        launch_wino_gemm(a, wt36, V, M, cfg, bf16x2, s, &pl);
+        launch_wino_gemm(a, wt36, V, M, cfg, prec, s, &pl);
         launch_wino_mix(a, pl, M, nullptr, 0, nullptr, nullptr, false, s);
         return;
     }
     launch_wino_input(a, V, in_scale, in_shift, bf16x2, s);
-    launch_wino_gemm(a, wt36, V, M, cfg, bf16x2, s);
+    launch_wino_gemm(a, wt36, V, M, cfg, prec, s);
     launch_wino_output(a, M, s);
 }
 

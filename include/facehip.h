@@ -849,9 +849,18 @@ FH_API int fh_rec_set_shortcut_fold(fh_rec* r, int on);
  * The call is GATED: it embeds a fixed pseudo-random batch of 64 crops in both modes and enters the mode only if every pair of
  * embeddings agrees to 1 - cos < 1e-3; otherwise it returns FH_ERR_STATE, the handle stays fp32 and fh_last_error() quotes the measured
  * value.  *worst (may be NULL) receives the measured max(1 - cos).  Returns the number of layers switched (>= 1), or < 0. */
-enum fh_precision { FH_PREC_FP32 = 0, FH_PREC_BF16X2 = 1 };
+/* FH_PREC_F32X3 is no mode of fh_rec_set_precision: it names, for the single-kernel entry points below, the three-piece bf16 form of
+ * the Winograd GEMM that the fp32 mode runs by default (fh_rec_set_wino_x3); there FH_PREC_FP32 means the native f32 MFMA kernels. */
+enum fh_precision { FH_PREC_FP32 = 0, FH_PREC_BF16X2 = 1, FH_PREC_F32X3 = 2 };
 FH_API int fh_rec_set_precision(fh_rec* r, int mode, float* worst);
 FH_API int fh_rec_get_precision(fh_rec* r);
+/* The fp32 mode's Winograd GEMMs.  on (default; FACEHIP_WINO_X3=0 in the environment makes off the default): every fp32 operand is split
+ * EXACTLY into three bf16 pieces (8 + 8 + 8 significand bits) and six of the nine piece products run on bf16 MFMAs with f32 accumulation —
+ * fp32 results (the dropped terms are below 2^-22 of each product, under the f32 accumulation's own rounding), not bit-identical to the
+ * f32 MFMA's.  The split weights are a second device image of 1.5 x the Winograd weights' bytes.  off: the native f32 MFMA kernels.
+ * Returns the number of layers that have the form (0 for off), or < 0.  Synchronous the first time it is switched on. */
+FH_API int fh_rec_set_wino_x3(fh_rec* r, int on);
+FH_API int fh_rec_get_wino_x3(fh_rec* r);
 /* A handle whose stream is restricted to a subset of the CUs (hipExtStreamCreateWithCUMask, e.g. detector and
  * recogniser side by side on disjoint CU sets) should say how many it gets: it sizes the convolution kernels'
  * remainder round.  0 = the whole device (default). */
@@ -888,7 +897,9 @@ FH_API int fh_conv_winograd_dev(const float* d_in, const float* w_ohwi_host, con
                                 int cin, int cout, void* stream);
 /* The same with a precision argument (enum fh_precision).  FH_PREC_BF16X2: the split-bf16 operand format of fh_rec_set_precision on this
  * one layer — the weight image is packed as the engine packs it, the input transform writes packed V, the GEMM is the three-product bf16
- * form.  Layers without that form (cin % 32 != 0 or cout % 64 != 0) are refused ("... no split-bf16 GEMM"). */
+ * form.  Layers without that form (cin % 32 != 0 or cout % 64 != 0) are refused ("... no split-bf16 GEMM").  FH_PREC_F32X3: the three-piece bf16
+ * GEMM of fh_rec_set_wino_x3 on this one layer (V stays fp32, the weight image is split as the engine splits it; same layers);
+ * FH_PREC_FP32: the native f32 MFMA kernels. */
 FH_API int fh_conv_winograd_ex_dev(const float* d_in, const float* w_ohwi_host, const float* d_bias, float* d_out, int batch, int h, int w,
                                    int cin, int cout, int precision, void* stream);
 /* The same convolution in the fused Winograd F(2x2,3x3) form the 64-channel stages use (conv_wino2.hip): cin == 64, cout % 64 == 0;
@@ -942,7 +953,8 @@ FH_API int fh_debug_pack_bf16x2_dev(const float* d_in, float* d_out, long long n
  * operands.  d_V [rows][k] and d_M [rows][n] in the plane layout the transforms use (rows = fh_debug_wino_gemm_rows: 36 planes of the
  * tile count rounded up to 256 or, mixed != 0, the planes of the mixed F(4x4) / F(2x2) tiling — refused where that tiling does not
  * apply); d_U [36][fh_conv_wt_rows(n)][k] row-major.  k % 32 == 0, n % 32 == 0.  precision = FH_PREC_BF16X2 packs copies of V and U
- * and runs the three-product bf16 kernel (n % 64 == 0).  Synchronous. */
+ * and runs the three-product bf16 kernel (n % 64 == 0); FH_PREC_F32X3 splits a copy of U into three bf16 planes and runs the six-product
+ * kernel on the caller's f32 V (n % 64 == 0); FH_PREC_FP32 runs the native f32 MFMA kernels.  Synchronous. */
 FH_API long long fh_debug_wino_gemm_rows(int batch, int h, int w, int k, int n, int mixed);
 FH_API int fh_debug_wino_gemm_dev(const float* d_V, const float* d_U, float* d_M, int batch, int h, int w, int k, int n, int precision,
                                   int mixed, void* stream);
