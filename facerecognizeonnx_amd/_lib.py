@@ -238,6 +238,7 @@ PROTOTYPES = {
     "fh_det_set_cus": (_i, [_vp, _i]),
     "fh_rec_set_cus": (_i, [_vp, _i]),
     "fh_debug_streamk": (_i, [_i, _i]),
+    "fh_debug_conv_plan": (_i, [_i, _vp, _i, _vp, _i]),
     "fh_debug_wino_slots": (_i, [_i]),
     "fh_debug_cluster_tiles": (_i, [_i]),
     "fh_debug_hist_copies": (_i, [_i]),

@@ -1810,6 +1810,45 @@ int fh_rec_graph_stats(fh_rec* r, long long* replays) {
 }
 int fh_debug_wino_slots(int slots) { fh::wino_debug_slots(slots); return 0; }
 int fh_debug_streamk(int drop_publish, int timeout_ms) { fh::conv_debug_streamk(drop_publish, timeout_ms); return 0; }
+// conv_plan.h asked without a GPU, with the default switches (ConvKnobs{}); see include/facehip.h for the five questions
+int fh_debug_conv_plan(int what, const int* in, int n_in, long long* out, int n_out) {
+    static const int BMs[4] = {128, 256, 128, 64}, BNs[4] = {128, 64, 32, 64};
+    const fh::ConvKnobs knobs;
+    auto need = [&](int ni, int no) { return n_in == ni && n_out == no && out && (in || !ni); };
+    auto geom = [&] {       // in: B, H, W, Cin, Cout, ks, stride, pad, n_outs, up2x
+        const int Ho = (in[1] + 2 * in[7] - in[5]) / in[6] + 1, Wo = (in[2] + 2 * in[7] - in[5]) / in[6] + 1;
+        return fh::ConvGeom{(long)in[0] * Ho * Wo, in[1], in[2], in[3], Ho, Wo, in[4], in[5], in[6], in[7], fh::conv_kpad(in[5] * in[5] * in[3]), in[8],
+                            false, false, in[9] != 0, false};
+    };
+    auto shape_ok = [&] { return in[0] > 0 && in[1] > 0 && in[2] > 0 && in[3] > 0 && in[4] > 0 && in[5] > 0 && in[6] > 0 && in[7] >= 0 && in[10] > 0 &&
+                                 in[1] + 2 * in[7] >= in[5] && in[2] + 2 * in[7] >= in[5]; };      // (a non-empty output grid)
+    if (what == 0 && need(8, 9) && in[0] >= 0 && in[1] > 0 && in[2] > 0 && in[3] > 0 && in[4] > 0) {
+        const fh::ConvSkPlan p = fh::conv_streamk_plan(in[0], in[1], in[2], in[3], in[4], in[5], in[6], in[7] != 0, knobs);
+        const int v[9] = {p.full, p.rem, p.helpers, p.owners, p.fixup, p.units, p.q, p.owner_chunks, p.maxp};
+        for (int i = 0; i < 9; ++i) out[i] = v[i];
+    } else if (what == 1 && need(11, 1) && shape_ok()) {
+        out[0] = fh::conv_pw_bn(geom(), in[10], knobs);
+    } else if (what == 2 && need(12, 3) && shape_ok() && in[11] >= -1 && in[11] < 4) {
+        const fh::ConvGeom g = geom();
+        const int cfg = in[11] < 0 ? fh::conv_pick_cfg(g.M, g.Cout) : in[11], BM = BMs[cfg], BN = BNs[cfg];
+        const int tiles_n = (g.Cout + BN - 1) / BN, tiles = (int)((g.M + BM - 1) / BM) * tiles_n;
+        fh::ConvTallPlan t{0, 0, 0};
+        if (cfg == 1 || cfg == 2) t = fh::conv_tall_plan(g, BM, BN, 32, tiles, tiles_n, in[10], knobs);
+        out[0] = t.tiles; out[1] = t.tiles ? t.rows_a : 0; out[2] = t.tiles ? (long long)t.lds : 0;
+    } else if (what == 3 && need(4, 2) && in[0] >= 0 && in[1] > in[0] && in[2] > 0 && in[3] > 0) {
+        out[0] = out[1] = fh::conv_sk_nparts(in[0], in[2], in[3]);
+        for (int r = in[0] + 1; r < in[1]; ++r) {
+            const int n = fh::conv_sk_nparts(r, in[2], in[3]);
+            if (n < out[0]) out[0] = n;
+            if (n > out[1]) out[1] = n;
+        }
+    } else if (what == 4 && need(0, 2)) {
+        out[0] = (long long)fh::SK_SLAB_FLOATS; out[1] = (long long)fh::SK_COUNTERS;
+    } else {
+        return arg_error("fh_debug_conv_plan: unknown question, wrong array lengths or a non-positive size");
+    }
+    return n_out;
+}
 int fh_conv_forward_dev(const float* in, const float* wt, const float* bias, float* out, int batch, int h, int w, int cin, int cout,
                         int ks, int stride, int kpad, int cfg, void* stream) {
     if (!in || !wt || !out || batch <= 0 || (ks != 1 && ks != 3) || cin % 4) return arg_error("fh_conv_forward_dev: bad argument");

@@ -35,340 +35,23 @@
 // order and runs the epilogue — deterministic, no float atomics, no second kernel.  When a tile
 // would need more than 3 slabs (the 25088-deep FC as split-K, tiny remainders) there are no
 // owners: every segment goes to a slab and conv_fixup_kernel sums them in a second launch.
+//
+// Where the pieces live: conv_tile.h — tile shape, activation, the epilogue's vectors (ConvEpVec), the slab address rule and the
+// epilogue with its four forms (and why conv_igemm_kernel keeps some of it written out); conv_plan.h — every launch decision (stream-K split, conv_tall_kernel / conv_pw_kernel take-over, tile
+// config, environment switches) as host arithmetic.  This file: the kernels' loaders, K loops and stream-K roles, and the launchers.
 #include <hip/hip_runtime.h>
 
 #include <atomic>
-
-#include <algorithm>
 #include <cstdio>
-#include <cstdlib>
 #include <cstring>
 #include <mutex>
 #include <stdexcept>
 #include <vector>
 
-#include "gemm_tile.h"
+#include "conv_tile.h"
 #include "kernels.h"
-#include "plan.h"
 
 namespace fh {
-
-// stream-K workspace: accumulator slabs followed by one counter word per remainder tile
-constexpr size_t SK_SLAB_FLOATS = (size_t)2 * 1280 * 128 * 128;
-constexpr size_t SK_COUNTERS = 4096;
-
-// The same with the activation a compile-time constant: the epilogues' hot paths switch ONCE per tile (with_act) instead of running
-// apply_act's branch tree per element — inlined 16 times per 32 x 32 block it made the epilogue thousands of basic blocks
-// (phase stamps of conv_pw_kernel, scripts/pw_ablate.sh: first block in LDS -> last store issued 7.7 -> 5.8 us of a 37 us tile).
-template <int A>
-__device__ __forceinline__ float act_c(float v, float slope) {
-    if constexpr (A == (int)Act::RELU) return v > 0.f ? v : 0.f;
-    else if constexpr (A == (int)Act::PRELU) return v >= 0.f ? v : v * slope;
-    else if constexpr (A == (int)Act::SIGMOID) return 1.0f / (1.0f + expf(-v));
-    else return v;
-}
-template <int A> struct ActC { static constexpr int value = A; };
-template <class F>
-__device__ __forceinline__ void with_act(int act, F&& f) {
-    if (act == (int)Act::RELU) f(ActC<(int)Act::RELU>{});
-    else if (act == (int)Act::PRELU) f(ActC<(int)Act::PRELU>{});
-    else if (act == (int)Act::SIGMOID) f(ActC<(int)Act::SIGMOID>{});
-    else f(ActC<(int)Act::NONE>{});
-}
-// ds_write_b128 the compiler does not see (p points into LDS; ordered before later LDS accesses of the wave by the LDS queue itself)
-__device__ __forceinline__ float apply_act(float v, int act, float slope) {
-    if (act == (int)Act::RELU) return v > 0.f ? v : 0.f;
-    if (act == (int)Act::PRELU) return v >= 0.f ? v : v * slope;
-    if (act == (int)Act::SIGMOID) return 1.0f / (1.0f + expf(-v));
-    return v;
-}
-
-template <int BM, int BN, int WM, int WN>
-struct Tile {
-    static constexpr int T = WM * WN * 64;
-    static constexpr int TM = BM / WM / 32, TN = BN / WN / 32;
-    static constexpr int RP = T / 8;                    // tile rows filled per loader pass
-    static constexpr int AL = BM / RP, BL = BN / RP;
-    static constexpr int SLAB = BM * BN;                // floats per accumulator slab
-    static_assert(TM >= 1 && TN >= 1 && AL >= 1 && BL >= 1 && RP % 16 == 0, "tile shape");
-};
-
-// ---- epilogue shared by the main kernel and the fix-up kernel -------------------------------
-// C/D map of the 32x32 MFMA: column (= pixel here) = lane & 31, row (= channel) = (reg&3) + 8*(reg>>2) + 4*(lane>>5)
-// ep (optional): the tile's per-channel vectors in LDS, float [12][BN]: rows 0..8 = bias (one per border class when bias_cls, else row 0),
-// 9 = PReLU slope, 10 / 11 = s2 / t2 of the second output; channels >= Cout hold 0.  With it the epilogue issues NO global load between
-// its stores: on this ISA loads and stores share one in-order counter (vmcnt), so a load issued after a store can only be waited for
-// together with that store's acknowledgement — bias / slope loads interleaved with the stores turned the epilogue into a chain of
-// store round trips (16 per 256x64 tile, a third of the tile's time).  The residual reads are issued up front for the same reason.
-// whole-line epilogue (conv_epilogue: tr) when rows are whole 128-byte lines; ep_direct = A / B switch (FACEHIP_EP_DIRECT): 1 = never,
-// 3 = for every Cout % 4 == 0 (measured: the 16-channel FPN laterals lose 5 % to their idle tail lanes)
-__device__ __forceinline__ bool conv_ep_lines(const ConvArgs& p) { return p.ep_direct == 0 ? (p.Cout & 31) == 0 : p.ep_direct == 3; }
-template <int BM, int BN, int WM, int WN>
-__device__ __forceinline__ void conv_epilogue(const ConvArgs& p, v16f (&acc)[BM / WM / 32][BN / WN / 32], int m0, int n0,
-                                              int wm, int wn, int lane, int only_i = -1, int only_j = -1, const float* ep = nullptr,
-                                              float* tr = nullptr) {
-    using TL = Tile<BM, BN, WM, WN>;
-    const int fr = lane & 31, fh2 = lane >> 5;
-    const int HoWo = p.Ho * p.Wo;
-    const int M = p.B * HoWo;
-    const float* __restrict__ res = p.res;
-    float* __restrict__ out1 = p.out1;
-    float* __restrict__ out2 = p.out2;
-    const bool vec = (p.Cout & 3) == 0;
-    if (p.n_outs > 0) {                                  // merged sibling convs: per-channel-range destination
-#pragma unroll
-        for (int i = 0; i < TL::TM; ++i) {
-            const int m = m0 + (wm * TL::TM + i) * 32 + fr;
-            if (m >= M || (only_i >= 0 && i != only_i)) continue;
-#pragma unroll
-            for (int j = 0; j < TL::TN; ++j) {
-                if (only_j >= 0 && j != only_j) continue;
-                const int cb = n0 + (wn * TL::TN + j) * 32 + 4 * fh2;
-#pragma unroll
-                for (int e = 0; e < 16; ++e) {
-                    const int co = cb + 8 * (e >> 2) + (e & 3);
-                    if (co >= p.Cout) continue;
-                    const int g = co >= p.oc0[2] && p.n_outs > 2 ? 2 : co >= p.oc0[1] ? 1 : 0;
-                    const int cg = p.oc0[g + 1] - p.oc0[g];
-                    const float v = apply_act(acc[i][j][e] + p.bias[co], p.oact[g], 0.f);
-                    p.outs[g][(size_t)m * cg + (co - p.oc0[g])] = v;
-                }
-            }
-        }
-        return;
-    }
-    if (ep && vec && tr && only_i < 0 && only_j < 0) {
-        // Whole-line form (round 4).  A lane's accumulators are 4-channel pieces of ITS pixel row: written straight from registers, one
-        // store instruction puts 32 bytes into each of 32 rows — a quarter of a 128-byte line per row, 8 instructions (and 8 residual
-        // reads) per line.  Here each 32 x 32 block is turned around in a wave-private LDS scratch (tr: [waves][32 rows][36 floats], the
-        // 16 lanes of a b128 phase hit different banks on the write side) and a lane takes float4 column cq of rows rr, rr + 8, rr + 16,
-        // rr + 24: one instruction then moves 8 rows x ONE whole line, for stores and residual reads alike, and the per-channel vectors of
-        // a block are the same for all four of a lane's rows (whole lines when Cout % 32 == 0, whole 128-byte runs otherwise).  Same arithmetic
-        // per element: bit-identical results.
-        float* const blk = tr + (wm * WN + wn) * (32 * 36);
-        const int rr = lane >> 3, cq = lane & 7;
-#ifdef FACEHIP_PW_ABL
-        const unsigned long long est0 = wall_clock64();
-        unsigned long long est1 = 0, est2 = 0, est3 = 0;
-#endif
-        // Loads and stores share ONE in-order counter (vmcnt): a wait for a residual load that sits behind a store in program order is a
-        // wait for that store's acknowledgement (~0.36 us; with the residual a run-time flag the compiler kept such a wait in front of every
-        // row group even when there was no residual).  So the residual is a compile-time flag here, a block's residual reads are issued
-        // first and consumed two row groups at a time BEFORE those groups' stores.  (What remains between blocks is the compiler's
-        // vmcnt(0) in front of the next block's LDS stores — it protects the registers the pending global stores read; giving every stored
-        // value a register of its own removed it and changed nothing: the tile's 48 KB leave at the chip's ~5 TB/s write rate together
-        // with every other workgroup's, scripts/pw_phases.py.)
-        auto body = [&](auto AC, auto RC) {
-        constexpr int A = decltype(AC)::value;
-        constexpr bool R = decltype(RC)::value != 0;
-#pragma unroll
-        for (int i = 0; i < TL::TM; ++i) {
-            const int mb = m0 + (wm * TL::TM + i) * 32 + rr;               // this lane's rows: mb + 8 k
-            int cls4 = 0;                                                   // border class of row k in bits 4k .. 4k+3
-            if (p.bias_cls) {
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const int mc = min(mb + 8 * k, M - 1);
-                    const int n = mc / HoWo, rem = mc - n * HoWo;
-                    const int oy = rem / p.Wo, ox = rem - oy * p.Wo;
-                    cls4 |= (3 * (oy == 0 ? 0 : oy == p.Ho - 1 ? 2 : 1) + (ox == 0 ? 0 : ox == p.Wo - 1 ? 2 : 1)) << (4 * k);
-                }
-            }
-            auto res_row = [&](int m) -> size_t {
-                if (p.res_mode != (int)ResMode::UP2X) return (size_t)m * p.Cout;
-                const int n = m / HoWo, rem = m - n * HoWo;
-                const int oy = rem / p.Wo, ox = rem - oy * p.Wo;
-                return ((size_t)(n * (p.Ho >> 1) + (oy >> 1)) * (p.Wo >> 1) + (ox >> 1)) * p.Cout;
-            };
-#pragma unroll
-            for (int j = 0; j < TL::TN; ++j) {
-                const int cl = (wn * TL::TN + j) * 32 + 4 * cq;            // channel within the tile
-                const int co = n0 + cl;
-                if (n0 + (wn * TL::TN + j) * 32 >= p.Cout) continue;       // (a padded column block; wave-uniform)
-                const bool cok = co < p.Cout;                              // (the last block of a Cout that is not a multiple of 32: its tail lanes idle)
-                v4f r4[4];
-                if constexpr (R) {
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) r4[k] = cok ? *reinterpret_cast<const v4f*>(res + res_row(min(mb + 8 * k, M - 1)) + co) : v4f{0.f, 0.f, 0.f, 0.f};
-                }
-                wave_lds_order();                                            // (the previous block's scratch reads lie above these writes)
-#pragma unroll
-                for (int g = 0; g < 4; ++g)
-                    *reinterpret_cast<v4f*>(blk + fr * 36 + 8 * g + 4 * fh2) = v4f{acc[i][j][4 * g], acc[i][j][4 * g + 1], acc[i][j][4 * g + 2], acc[i][j][4 * g + 3]};
-                wave_lds_order();                                            // (lane (rr, cq) reads rows other lanes wrote)
-                v4f sl = {0.f, 0.f, 0.f, 0.f}, s2 = sl, t2 = sl;
-                if constexpr (A == (int)Act::PRELU) sl = *reinterpret_cast<const v4f*>(ep + 9 * BN + cl);
-                if (out2) { s2 = *reinterpret_cast<const v4f*>(ep + 10 * BN + cl); t2 = *reinterpret_cast<const v4f*>(ep + 11 * BN + cl); }
-#ifdef FACEHIP_PW_ABL
-                if (i == 0 && j == 0) est1 = wall_clock64();                // first block's accumulators written to LDS (issued)
-#endif
-                // (two row groups at a time: their arithmetic, then their stores — four at a time spill in the 128-register instantiations)
-#pragma unroll
-                for (int h = 0; h < 2; ++h) {
-                    v4f vk[2];
-#pragma unroll
-                    for (int q = 0; q < 2; ++q) {
-                        const int k = 2 * h + q;
-                        const v4f a4 = *reinterpret_cast<const v4f*>(blk + (rr + 8 * k) * 36 + 4 * cq);
-                        const v4f b4 = *reinterpret_cast<const v4f*>(ep + ((cls4 >> (4 * k)) & 15) * BN + cl);
-#pragma unroll
-                        for (int c = 0; c < 4; ++c) vk[q][c] = act_c<A>(a4[c] + b4[c], sl[c]);
-                        if constexpr (R) vk[q] += r4[k];
-                    }
-#if defined(__HIP_DEVICE_COMPILE__)
-                    __builtin_amdgcn_sched_barrier(0);                      // (every wait of this half lies above its stores)
-#endif
-#ifdef FACEHIP_PW_ABL
-                    if (i == 0 && j == 0 && h == 0) est2 = wall_clock64();  // first block's first values ready
-#endif
-#pragma unroll
-                    for (int q = 0; q < 2; ++q) {
-                        const int m = mb + 8 * (2 * h + q);
-#ifdef FACEHIP_PW_ABL
-                        if ((p.sk_test_drop & 16) && lane != 0) continue;  // (diagnostic: every instruction of the epilogue but 63 of 64 lanes' stores)
-#endif
-                        if (m < M && cok) {
-                            const size_t row = (size_t)m * p.Cout + co;
-                            if (out1) *reinterpret_cast<v4f*>(out1 + row) = vk[q];
-                            if (out2) *reinterpret_cast<v4f*>(out2 + row) = vk[q] * s2 + t2;
-                        }
-                    }
-                }
-#ifdef FACEHIP_PW_ABL
-                if (i == 0 && j == 0) est3 = wall_clock64();                // first block's four stores issued
-#endif
-            }
-        }
-        };
-        with_act(p.act, [&](auto AC) {
-            if (p.res_mode != (int)ResMode::NONE) body(AC, ActC<1>{}); else body(AC, ActC<0>{});
-        });
-#ifdef FACEHIP_PW_ABL
-        if (threadIdx.x == 0 && p.slabs && p.Cout == 288 && p.Cin == 288) {   // (phase stamps of conv_pw_kernel, second half: see there)
-            unsigned long long* o = reinterpret_cast<unsigned long long*>(p.slabs) + 8192 + (size_t)blockIdx.x * 4;
-            o[0] = est0; o[1] = est1; o[2] = wall_clock64();
-            unsigned long long* o2 = reinterpret_cast<unsigned long long*>(p.slabs) + 16384 + (size_t)blockIdx.x * 2;
-            o2[0] = est2; o2[1] = est3;
-        }
-#endif
-        return;
-    }
-    if (ep && vec) {
-        // per 32-pixel row block: its TN*4 residual float4s first, then per accumulator quad vectors from LDS, arithmetic, stores
-        // (all TM row blocks' residuals up front would not fit the register file of the large tiles)
-        with_act(p.act, [&](auto AC) {
-        constexpr int A = decltype(AC)::value;
-#pragma unroll
-        for (int i = 0; i < TL::TM; ++i) {
-            const int m = m0 + (wm * TL::TM + i) * 32 + fr;
-            if (m >= M) continue;
-            const size_t row = (size_t)m * p.Cout;
-            int cls = 0;
-            size_t rrow = row;
-            if (p.bias_cls || p.res_mode == (int)ResMode::UP2X) {
-                const int n = m / HoWo, rem = m - n * HoWo;
-                const int oy = rem / p.Wo, ox = rem - oy * p.Wo;
-                // BatchNorm shift folded in: taps that fall on the zero padding contribute none of it
-                if (p.bias_cls) cls = 3 * (oy == 0 ? 0 : oy == p.Ho - 1 ? 2 : 1) + (ox == 0 ? 0 : ox == p.Wo - 1 ? 2 : 1);
-                if (p.res_mode == (int)ResMode::UP2X) rrow = ((size_t)(n * (p.Ho >> 1) + (oy >> 1)) * (p.Wo >> 1) + (ox >> 1)) * p.Cout;
-            }
-            v4f r4[TL::TN][4];
-            if (p.res_mode != (int)ResMode::NONE) {
-#pragma unroll
-                for (int j = 0; j < TL::TN; ++j)
-#pragma unroll
-                    for (int g = 0; g < 4; ++g) {
-                        const int co = n0 + (wn * TL::TN + j) * 32 + 4 * fh2 + 8 * g;
-                        r4[j][g] = co < p.Cout ? *reinterpret_cast<const v4f*>(res + rrow + co) : v4f{0.f, 0.f, 0.f, 0.f};
-                    }
-            }
-#pragma unroll
-            for (int j = 0; j < TL::TN; ++j) {
-                const int cl = (wn * TL::TN + j) * 32 + 4 * fh2;           // channel within the tile
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    const int co = n0 + cl + 8 * g;
-                    if (co >= p.Cout) continue;
-                    const v4f b4 = *reinterpret_cast<const v4f*>(ep + cls * BN + cl + 8 * g);
-                    v4f sl = {0.f, 0.f, 0.f, 0.f};
-                    if constexpr (A == (int)Act::PRELU) sl = *reinterpret_cast<const v4f*>(ep + 9 * BN + cl + 8 * g);
-                    v4f v;
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) v[c] = act_c<A>(acc[i][j][4 * g + c] + b4[c], sl[c]);
-                    if (p.res_mode != (int)ResMode::NONE) v += r4[j][g];
-                    if (out1) *reinterpret_cast<v4f*>(out1 + row + co) = v;
-                    if (out2) {
-                        const v4f s2 = *reinterpret_cast<const v4f*>(ep + 10 * BN + cl + 8 * g), t2 = *reinterpret_cast<const v4f*>(ep + 11 * BN + cl + 8 * g);
-                        *reinterpret_cast<v4f*>(out2 + row + co) = v * s2 + t2;
-                    }
-                }
-            }
-        }
-        });
-        return;
-    }
-#pragma unroll
-    for (int i = 0; i < TL::TM; ++i) {
-        const int m = m0 + (wm * TL::TM + i) * 32 + fr;
-        if (m >= M || (only_i >= 0 && i != only_i)) continue;
-        const size_t row = (size_t)m * p.Cout;
-        size_t rrow = row;
-        const float* __restrict__ bias = p.bias;
-        if (p.bias_cls) {                                   // BatchNorm shift folded in: taps that fall on the zero padding contribute none of it
-            const int n = m / HoWo, rem = m - n * HoWo;
-            const int oy = rem / p.Wo, ox = rem - oy * p.Wo;
-            const int cls = 3 * (oy == 0 ? 0 : oy == p.Ho - 1 ? 2 : 1) + (ox == 0 ? 0 : ox == p.Wo - 1 ? 2 : 1);
-            bias += cls * p.Cout;
-        }
-        if (p.res_mode == (int)ResMode::UP2X) {
-            const int n = m / HoWo, rem = m - n * HoWo;
-            const int oy = rem / p.Wo, ox = rem - oy * p.Wo;
-            rrow = ((size_t)(n * (p.Ho >> 1) + (oy >> 1)) * (p.Wo >> 1) + (ox >> 1)) * p.Cout;
-        }
-#pragma unroll
-        for (int j = 0; j < TL::TN; ++j) {
-            if (only_j >= 0 && j != only_j) continue;
-            const int cb = n0 + (wn * TL::TN + j) * 32 + 4 * fh2;
-            if (vec) {
-                v4f r4[4];
-                if (p.res_mode != (int)ResMode::NONE) {
-#pragma unroll
-                    for (int g = 0; g < 4; ++g) {
-                        const int co = cb + 8 * g;
-                        r4[g] = co < p.Cout ? *reinterpret_cast<const v4f*>(res + rrow + co) : v4f{0.f, 0.f, 0.f, 0.f};
-                    }
-                }
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    const int co = cb + 8 * g;
-                    if (co >= p.Cout) continue;
-                    const v4f b4 = bias ? *reinterpret_cast<const v4f*>(bias + co) : v4f{0.f, 0.f, 0.f, 0.f};
-                    v4f sl = {0.f, 0.f, 0.f, 0.f};
-                    if (p.act == (int)Act::PRELU) sl = *reinterpret_cast<const v4f*>(p.slope + co);
-                    v4f v;
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) v[c] = apply_act(acc[i][j][4 * g + c] + b4[c], p.act, sl[c]);
-                    if (p.res_mode != (int)ResMode::NONE) v += r4[g];
-                    if (out1) *reinterpret_cast<v4f*>(out1 + row + co) = v;
-                    if (out2) {
-                        const v4f s2 = *reinterpret_cast<const v4f*>(p.s2 + co), t2 = *reinterpret_cast<const v4f*>(p.t2 + co);
-                        *reinterpret_cast<v4f*>(out2 + row + co) = v * s2 + t2;
-                    }
-                }
-            } else {
-#pragma unroll
-                for (int e = 0; e < 16; ++e) {
-                    const int co = cb + 8 * (e >> 2) + (e & 3);
-                    if (co >= p.Cout) continue;
-                    float v = apply_act(acc[i][j][e] + (bias ? bias[co] : 0.f), p.act, p.slope ? p.slope[co] : 0.f);
-                    if (p.res_mode != (int)ResMode::NONE) v += res[rrow + co];
-                    if (out1) out1[row + co] = v;
-                    if (out2) out2[row + co] = v * p.s2[co] + p.t2[co];
-                }
-            }
-        }
-    }
-}
 
 // GRP: grouped form (several GEMMs stacked along M with one weight matrix each, see ConvArgs::wt_group_rows) — a separate
 // instantiation, so that the ungrouped convolutions keep their register allocation.
@@ -396,28 +79,22 @@ __global__ __launch_bounds__(WM * WN * 64, OCC) void conv_igemm_kernel(const Con
     const int fr = lane & 31, fh2 = lane >> 5;
     const int fsw = (fr >> 1) & 7;
 
-    // ---- which tile(s) and which K range: plain tiles first, then helpers, then owners
-    // Workgroups are dealt round-robin over the 8 XCDs (blockIdx % 8), each with its own L2.  Give every XCD
-    // a CONTIGUOUS range of tiles instead, so that the tiles_n workgroups that read the same pixels (and the
-    // neighbours that share their halo rows) hit the same L2 instead of fetching the input once per XCD.
-    auto xcd_contiguous = [](int b, int n) {
-        const int q = n >> 3, r = n & 7, x = b & 7;
-        return x * q + min(x, r) + (b >> 3);
-    };
+    // ---- which tile(s) and which K range: plain tiles first, then helpers, then owners — each group in XCD-contiguous order (xcd_tile),
+    // so that the tiles_n workgroups that read the same pixels (and the neighbours that share their halo rows) hit the same L2
     enum { PLAIN = 0, HELPER = 1, OWNER = 2 };
     int role = PLAIN, tile = 0, c_begin = 0, c_end = chunks;
     int hu = 0, hu_end = 0, helper_id = 0;                  // helper: its run of units [hu, hu_end)
     const int Kh = chunks - p.sk_owner_chunks;              // chunks per remainder tile that helpers compute
     if ((int)blockIdx.x < p.sk_full) {
-        tile = xcd_contiguous(blockIdx.x, p.sk_full);
+        tile = xcd_tile((int)blockIdx.x, p.sk_full);
     } else if ((int)blockIdx.x < p.sk_full + p.sk_helpers) {
         role = HELPER;
-        helper_id = xcd_contiguous(blockIdx.x - p.sk_full, p.sk_helpers);
+        helper_id = xcd_tile((int)blockIdx.x - p.sk_full, p.sk_helpers);
         hu = helper_id * p.sk_q;
         hu_end = min(p.sk_units, hu + p.sk_q);
     } else {
         role = OWNER;
-        tile = p.sk_full + xcd_contiguous(blockIdx.x - p.sk_full - p.sk_helpers, p.sk_rem);
+        tile = p.sk_full + xcd_tile((int)blockIdx.x - p.sk_full - p.sk_helpers, p.sk_rem);
         c_end = p.sk_owner_chunks;
     }
     unsigned* const sk_counters = reinterpret_cast<unsigned*>(p.slabs + SK_SLAB_FLOATS);
@@ -564,19 +241,18 @@ __global__ __launch_bounds__(WM * WN * 64, OCC) void conv_igemm_kernel(const Con
 #pragma unroll
                 for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
 
-        // the epilogue's per-channel vectors (see conv_epilogue: ep), fetched now into a few registers and parked in LDS once the K loop
-        // has released it — no global read is left for the epilogue to wait on
-        constexpr int EPN = (12 * BN + WM * WN * 64 - 1) / (WM * WN * 64);
+        // the epilogue's per-channel vectors: no global read is left for the epilogue to wait on
         const bool use_ep = role != HELPER && p.n_outs == 0 && (p.Cout & 3) == 0;
-        float epv[EPN];
+        using EpVec = ConvEpVec<BN, TL::T>;                  // (its layout; the two loops are written out here, see conv_tile.h)
+        float epv[EpVec::N];
 #pragma unroll
-        for (int k = 0; k < EPN; ++k) {
-            const int e = tid + k * (WM * WN * 64), a = e / BN, c = e - a * BN, co = n0 + c;
+        for (int k = 0; k < EpVec::N; ++k) {
+            const int e = tid + k * TL::T, a = e / BN, c = e - a * BN, co = n0 + c;
             float v = 0.f;
-            if (use_ep && a < 12 && co < p.Cout) {
-                if (a < 9) { if (p.bias && (a == 0 || p.bias_cls)) v = p.bias[a * p.Cout + co]; }
-                else if (a == 9) { if (p.act == (int)Act::PRELU) v = p.slope[co]; }
-                else if (p.out2) v = a == 10 ? p.s2[co] : p.t2[co];
+            if (use_ep && a < EP_ROWS && co < p.Cout) {
+                if (a < EP_SLOPE) { if (p.bias && (a == 0 || p.bias_cls)) v = p.bias[a * p.Cout + co]; }
+                else if (a == EP_SLOPE) { if (p.act == (int)Act::PRELU) v = p.slope[co]; }
+                else if (p.out2) v = a == EP_S2 ? p.s2[co] : p.t2[co];
             }
             epv[k] = v;
         }
@@ -625,7 +301,7 @@ __global__ __launch_bounds__(WM * WN * 64, OCC) void conv_igemm_kernel(const Con
 
         if (role == HELPER) {
             const int r = tile - p.sk_full;
-            float* __restrict__ slab = p.slabs + ((size_t)r * p.sk_maxp + part) * TL::SLAB;
+            float* __restrict__ slab = conv_slab<TL>(p, r, part);
 #pragma unroll
             for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -633,7 +309,7 @@ __global__ __launch_bounds__(WM * WN * 64, OCC) void conv_igemm_kernel(const Con
 #pragma unroll
                     for (int g = 0; g < 4; ++g) {
                         v4f v = {acc[i][j][4 * g], acc[i][j][4 * g + 1], acc[i][j][4 * g + 2], acc[i][j][4 * g + 3]};
-                        *reinterpret_cast<v4f*>(slab + ((size_t)((i * TN + j) * 4 + g) * TL::T + tid) * 4) = v;
+                        *reinterpret_cast<v4f*>(slab + conv_slab_at<TL>(i * TN + j, g, tid)) = v;
                     }
             if (p.sk_owner_chunks > 0) {
                 // publish (cdna_hip_programming.md Guideline 16, counter form): every wave drains its stores,
@@ -650,8 +326,8 @@ __global__ __launch_bounds__(WM * WN * 64, OCC) void conv_igemm_kernel(const Con
         }
         if (role == OWNER) {
             const int r = tile - p.sk_full;
-            const int nparts = ((r + 1) * Kh - 1) / p.sk_q - (r * Kh) / p.sk_q + 1;
-            if (tid == 0) {                                 // ONE lane polls relaxed, then ONE acquire
+            const int nparts = conv_sk_nparts(r, Kh, p.sk_q);
+            if (tid == 0) {                              // ONE lane polls relaxed, then ONE acquire
                 // Bounded wait: forward progress rests on helpers (lower block indices) being dispatched before owners, which HIP
                 // does not promise.  Past sk_timeout (default 2 s of the constant 100 MHz clock — five orders of magnitude beyond any
                 // real wait) the owner gives up: it reports (tile, arrivals seen, arrivals expected) through its Net's host-visible
@@ -679,14 +355,14 @@ __global__ __launch_bounds__(WM * WN * 64, OCC) void conv_igemm_kernel(const Con
             __syncthreads();
             if (*sk_gave_up) return;                        // (workgroup-uniform; an owner runs exactly one tile)
             for (int q = 0; q < nparts; ++q) {              // K order: own chunks first, then the helpers' runs
-                const float* slab = p.slabs + ((size_t)r * p.sk_maxp + q) * TL::SLAB;
+                const float* slab = conv_slab<TL>(p, r, q);
 #pragma unroll
                 for (int i = 0; i < TM; ++i)
 #pragma unroll
                     for (int j = 0; j < TN; ++j)
 #pragma unroll
                         for (int g = 0; g < 4; ++g) {
-                            const v4f v = *reinterpret_cast<const v4f*>(slab + ((size_t)((i * TN + j) * 4 + g) * TL::T + tid) * 4);
+                            const v4f v = *reinterpret_cast<const v4f*>(slab + conv_slab_at<TL>(i * TN + j, g, tid));
 #pragma unroll
                             for (int c = 0; c < 4; ++c) acc[i][j][4 * g + c] += v[c];
                         }
@@ -695,15 +371,16 @@ __global__ __launch_bounds__(WM * WN * 64, OCC) void conv_igemm_kernel(const Con
         float* const ep = reinterpret_cast<float*>(&lds[0][0]);            // (every wave is past the K loop's last barrier: LDS is free)
         if (use_ep) {
 #pragma unroll
-            for (int k = 0; k < EPN; ++k) {
-                const int e = tid + k * (WM * WN * 64);
-                if (e < 12 * BN) ep[e] = epv[k];
+            for (int k = 0; k < EpVec::N; ++k) {
+                const int e = tid + k * TL::T;
+                if (e < EpVec::FLOATS) ep[e] = epv[k];
             }
             __syncthreads();
         }
-        // (the transposition scratch of the whole-line epilogue sits behind the 12 x BN vectors: both fit the tile buffers of every shape)
-        static_assert((12 * BN + WM * WN * 32 * 36) * sizeof(float) <= sizeof(lds), "epilogue scratch");
-        conv_epilogue<BM, BN, WM, WN>(p, acc, m0, n0, wm, wn, lane, -1, -1, use_ep ? ep : nullptr, use_ep && conv_ep_lines(p) ? ep + 12 * BN : nullptr);
+        // (the transposition scratch of the whole-line epilogue sits behind the vectors: both fit the tile buffers of every shape)
+        static_assert((EpVec::FLOATS + WM * WN * 32 * 36) * sizeof(float) <= sizeof(lds), "epilogue scratch");
+        conv_epilogue<BM, BN, WM, WN>(p, acc, m0, n0, wm, wn, lane, -1, -1, use_ep ? ep : nullptr,
+                                      use_ep && conv_ep_wants_lines(p) ? ep + EpVec::FLOATS : nullptr);
     } while (role == HELPER && hu < hu_end);
 }
 
@@ -720,7 +397,7 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_fixup_kernel(const ConvArgs
     const int sub = blockIdx.x - r * (TM * TN);
     const int si = sub / TN, sj = sub - si * TN;
     const int tile = p.sk_full + r;
-    const int nparts = ((r + 1) * chunks - 1) / p.sk_q - (r * chunks) / p.sk_q + 1;
+    const int nparts = conv_sk_nparts(r, chunks, p.sk_q);   // (no owners: the helpers compute all of a tile's chunks)
     v16f acc[TM][TN];
 #pragma unroll
     for (int i = 0; i < TM; ++i)
@@ -731,15 +408,7 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_fixup_kernel(const ConvArgs
     v16f sum;
 #pragma unroll
     for (int e = 0; e < 16; ++e) sum[e] = 0.f;
-    for (int q = 0; q < nparts; ++q) {
-        const float* __restrict__ slab = p.slabs + ((size_t)r * p.sk_maxp + q) * TL::SLAB;
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const v4f v = *reinterpret_cast<const v4f*>(slab + ((size_t)((si * TN + sj) * 4 + g) * TL::T + tid) * 4);
-#pragma unroll
-            for (int c = 0; c < 4; ++c) sum[4 * g + c] += v[c];
-        }
-    }
+    for (int q = 0; q < nparts; ++q) conv_slab_add<TL>(conv_slab<TL>(p, r, q), sum, si * TN + sj, tid);
 #pragma unroll
     for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -747,7 +416,7 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_fixup_kernel(const ConvArgs
             if (i == si && j == sj) acc[i][j] = sum;
     const int gtile = tile + p.tile0;                       // (see conv_igemm_kernel)
     const int tile_n = gtile % tiles_n, tile_m = gtile / tiles_n;
-    conv_epilogue<BM, BN, WM, WN>(p, acc, tile_m * BM, tile_n * BN, wm, wn, lane, si, sj);
+    conv_epilogue<BM, BN, WM, WN, EP_MERGED | EP_PLAIN>(p, acc, tile_m * BM, tile_n * BN, wm, wn, lane, si, sj);
 }
 
 int conv_wt_rows(int Cout) { return (Cout + 127) / 128 * 128; }
@@ -801,11 +470,7 @@ __global__ __launch_bounds__(WM * WN * 64, OCC) void conv_tall_kernel(const Conv
     const int lrow = tid >> 3;
     const int lqs = (tid & 7) ^ ((lrow >> 1) & 7);                         // (RP % 16 == 0: the key of row i * RP + lrow is that of lrow)
     const int fr = lane & 31, fh2 = lane >> 5;
-    int tile;
-    {
-        const int n = gridDim.x, q = n >> 3, r = n & 7, x = blockIdx.x & 7;
-        tile = x * q + min(x, r) + (int)(blockIdx.x >> 3);                 // XCD-contiguous tile order (as conv_igemm_kernel)
-    }
+    const int tile = xcd_tile(blockIdx.x, gridDim.x);
     const int tile_n = tile % tiles_n, tile_m = tile / tiles_n;
     const int m0 = tile_m * BM, n0 = tile_n * BN;
     const int np = rows_a / RP;
@@ -854,20 +519,8 @@ __global__ __launch_bounds__(WM * WN * 64, OCC) void conv_tall_kernel(const Conv
 #pragma unroll
             for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
 
-    // the epilogue's per-channel vectors (see conv_epilogue: ep), parked in LDS after the K loop
-    constexpr int EPN = (12 * BN + WM * WN * 64 - 1) / (WM * WN * 64);
-    float epv[EPN];
-#pragma unroll
-    for (int k = 0; k < EPN; ++k) {
-        const int e = tid + k * (WM * WN * 64), a = e / BN, c = e - a * BN, co = n0 + c;
-        float v = 0.f;
-        if (a < 12 && co < p.Cout) {
-            if (a < 9) { if (p.bias && (a == 0 || p.bias_cls)) v = p.bias[a * p.Cout + co]; }
-            else if (a == 9) { if (p.act == (int)Act::PRELU) v = p.slope[co]; }
-            else if (p.out2) v = a == 10 ? p.s2[co] : p.t2[co];
-        }
-        epv[k] = v;
-    }
+    ConvEpVec<BN, TL::T> epv;                                              // the epilogue's per-channel vectors, parked in LDS after the K loop
+    epv.fetch(p, n0, tid, true);
 
     const int NC = Cin >> 5;
     const int rbase = (wm * TM * 32 + fr);                                 // this lane's row in the tile (block 0)
@@ -914,13 +567,9 @@ __global__ __launch_bounds__(WM * WN * 64, OCC) void conv_tall_kernel(const Conv
     }
     __syncthreads();                                                       // K loop over: LDS is free
     float* const ep = reinterpret_cast<float*>(Bs);
-#pragma unroll
-    for (int k = 0; k < EPN; ++k) {
-        const int e = tid + k * (WM * WN * 64);
-        if (e < 12 * BN) ep[e] = epv[k];
-    }
+    epv.park(ep, tid);
     __syncthreads();
-    conv_epilogue<BM, BN, WM, WN>(p, acc, m0, n0, wm, wn, lane, -1, -1, ep);
+    conv_epilogue<BM, BN, WM, WN, EP_MERGED | EP_QUADS>(p, acc, m0, n0, wm, wn, lane, -1, -1, ep);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
@@ -966,20 +615,9 @@ __global__ __launch_bounds__(256, OCC) void conv_pw_kernel(const ConvArgs p, con
 #pragma unroll
         for (int e = 0; e < 16; ++e) acc[0][j][e] = 0.f;
 
-    // the epilogue's per-channel vectors (see conv_epilogue: ep), parked in LDS after the K loop
-    constexpr int EPN = (12 * BN + 255) / 256;
-    float epv[EPN];
-#pragma unroll
-    for (int k = 0; k < EPN; ++k) {
-        const int e = tid + k * 256, a = e / BN, c = e - a * BN, co = n0 + c;
-        float v = 0.f;
-        if (a < 12 && co < p.Cout) {
-            if (a < 9) { if (p.bias && (a == 0 || p.bias_cls)) v = p.bias[a * p.Cout + co]; }
-            else if (a == 9) { if (p.act == (int)Act::PRELU) v = p.slope[co]; }
-            else if (p.out2) v = a == 10 ? p.s2[co] : p.t2[co];
-        }
-        epv[k] = v;
-    }
+    using EpVec = ConvEpVec<BN, 256>;                                       // the epilogue's per-channel vectors, parked in LDS after the K loop
+    EpVec epv;
+    epv.fetch(p, n0, tid, true);
 
 #ifdef FACEHIP_PW_ABL
     const int abl = p.sk_test_drop;
@@ -1005,18 +643,14 @@ __global__ __launch_bounds__(256, OCC) void conv_pw_kernel(const ConvArgs p, con
     if ((abl & 8) && acc[0][0][0] != 123.456f) return;
 #endif
     float* const ep = reinterpret_cast<float*>(&lds[0][0]);
-#pragma unroll
-    for (int k = 0; k < EPN; ++k) {
-        const int e = tid + k * 256;
-        if (e < 12 * BN) ep[e] = epv[k];
-    }
+    epv.park(ep, tid);
     __syncthreads();
-    static_assert((12 * BN + 4 * 32 * 36) * sizeof(float) <= sizeof(lds), "epilogue scratch");
+    static_assert((EpVec::FLOATS + 4 * 32 * 36) * sizeof(float) <= sizeof(lds), "epilogue scratch");
 #ifdef FACEHIP_PW_ABL
     const bool stamp = tid == 0 && p.slabs && p.Cout == 288 && p.Cin == 288;
     if (stamp) reinterpret_cast<unsigned long long*>(p.slabs)[8192 + (size_t)blockIdx.x * 4 + 3] = wall_clock64();
 #endif
-    conv_epilogue<BM, BN, 4, 1>(p, acc, m0, n0, l.wid, 0, l.lane, -1, -1, ep, conv_ep_lines(p) ? ep + 12 * BN : nullptr);
+    conv_epilogue<BM, BN, 4, 1, EP_LINES | EP_QUADS>(p, acc, m0, n0, l.wid, 0, l.lane, -1, -1, ep, conv_ep_wants_lines(p) ? ep + EpVec::FLOATS : nullptr);
 #ifdef FACEHIP_PW_ABL
     if (stamp) {
         const unsigned long long ts3 = wall_clock64();                  // stores issued
@@ -1044,52 +678,27 @@ static void launch_pw_cfg(const ConvArgs& a, long M, hipStream_t s) {
     timer.end(s, 11, a.t_flops, a.t_bytes);
 }
 
-static int ep_direct_env() {                         // FACEHIP_EP_DIRECT=1: the epilogues store straight from the accumulator registers (A / B timing)
-    static const int v = [] { const char* e = getenv("FACEHIP_EP_DIRECT"); return e ? atoi(e) : 0; }();
-    return v;
+static ConvGeom conv_geom(const ConvArgs& a) {        // what the predicates of conv_plan.h look at
+    return ConvGeom{(long)a.B * a.Ho * a.Wo, a.H, a.W, a.Cin, a.Ho, a.Wo, a.Cout, a.ks, a.stride, a.pad, a.Kpad, a.n_outs,
+                    a.wt_group_rows > 0, a.sc_in != nullptr, a.res_mode == (int)ResMode::UP2X, a.no_pw != 0};
 }
-// true = launched
+
+// true = launched (eligibility and tile width: conv_pw_bn)
 static bool launch_pw(ConvArgs a, hipStream_t s) {
-    static int on = -1;
-    if (on < 0) { const char* e = getenv("FACEHIP_CONV_PW"); on = e ? atoi(e) : 1; }       // (0 = conv_igemm_kernel everywhere: A / B timing)
-    const long M = (long)a.B * a.Ho * a.Wo;
-    if (!on || a.no_pw || a.ks != 1 || a.stride != 1 || a.pad != 0 || a.wt_group_rows > 0 || a.sc_in || a.n_outs > 0 || (a.Cin & 3) || (a.Cout & 3) ||
-        (M & 127) || a.H != a.Ho || a.W != a.Wo || a.Kpad % 32 || a.Kpad < a.Cin)
-        return false;
+    const ConvGeom g = conv_geom(a);
+    const int bn = conv_pw_bn(g, a.cus > 0 ? a.cus : conv_num_cus(), conv_knobs());
+    if (!bn) return false;
+    // conv_pw_kernel instantiates the whole-line and per-quad epilogues only (EP_LINES | EP_QUADS): hold the predicate to that
+    if (a.n_outs > 0 || (a.Cout & 3)) throw std::logic_error("conv_pw_bn admitted a layer conv_pw_kernel has no epilogue form for");
     a.zeros = conv_zero_line();
-    a.ep_direct = ep_direct_env();
+    a.ep_direct = conv_knobs().ep_direct;
 #ifdef FACEHIP_PW_ABL
     { static const int abl = [] { const char* e = getenv("FACEHIP_PW_ABL"); return e ? atoi(e) : 0; }(); a.sk_test_drop = abl; }
 #endif
-    const int cus = a.cus > 0 ? a.cus : conv_num_cus();
-    auto cols = [&](int bn) { return (a.Cout + bn - 1) / bn * bn; };
-    // widest tile whose padded columns cost <= 7 %; the 32-wide one otherwise (the generic kernel pads the same way)
-    int bn = 32;
-    if (cols(64) * 100 <= a.Cout * 107) bn = 64;
-    if (cols(96) * 100 <= a.Cout * 107 && cols(96) <= cols(64)) bn = 96;
-    const long tiles = (M / 128) * (cols(bn) / bn);
-    if (tiles < (long)cus) return false;                                    // fewer tiles than CUs: the generic kernel cuts K over the chip
-    if (bn == 96) launch_pw_cfg<96, 2>(a, M, s);
-    else if (bn == 64) launch_pw_cfg<64, 3>(a, M, s);
-    else launch_pw_cfg<32, 4>(a, M, s);
+    if (bn == 96) launch_pw_cfg<96, 2>(a, g.M, s);
+    else if (bn == 64) launch_pw_cfg<64, 3>(a, g.M, s);
+    else launch_pw_cfg<32, 4>(a, g.M, s);
     return true;
-}
-
-static int tall_enabled() {
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("FACEHIP_CONV_TALL"); v = e ? atoi(e) : 1; }       // (0 = conv_igemm_kernel everywhere: A / B timing)
-    return v;
-}
-
-int conv_pick_cfg(long M, int Cout) {
-    // padded-column waste per candidate tile width; prefer the wider tile when it costs <= 10 % more
-    auto cols = [&](int bn) { return (Cout + bn - 1) / bn * bn; };
-    int bn = 32;
-    if (cols(64) * 10 <= cols(32) * 11) bn = 64;
-    if (cols(128) * 10 <= cols(bn) * 11) bn = 128;
-    if (bn == 128) return 0;
-    if (bn == 64) return (M / 256) * (cols(64) / 64) >= 1024 ? 1 : 3;
-    return 2;
 }
 
 static int g_num_cus = 0;
@@ -1115,7 +724,8 @@ size_t conv_slab_floats() { return SK_SLAB_FLOATS + SK_COUNTERS; }   // slabs + 
 void conv_workspace_init(float* ws) { (void)hipMemset(ws + SK_SLAB_FLOATS, 0, SK_COUNTERS * sizeof(unsigned)); }
 void conv_workspace_reset_async(float* ws, hipStream_t s) { (void)hipMemsetAsync(ws + SK_SLAB_FLOATS, 0, SK_COUNTERS * sizeof(unsigned), s); }
 
-// ---- stream-K watchdog: a host-mapped (pinned, device-visible) record an owner writes when its hand-off wait times out
+// ---- stream-K watchdog, host state (records, generations, the test hook conv_debug_streamk): a host-mapped (pinned, device-visible)
+// record an owner writes when its hand-off wait times out
 static unsigned* g_sk_err = nullptr;
 static std::atomic<unsigned> g_sk_generation{0};      // (handles may be driven from different host threads)
 static unsigned g_sk_timeout = (unsigned)((2000ull * 100000ull) >> 16);      // 2 s in units of 2^16 ticks of the 100 MHz wall clock
@@ -1171,151 +781,61 @@ void conv_debug_streamk(int drop_publish, int timeout_ms) {
     g_sk_timeout = (unsigned)(((unsigned long long)(timeout_ms > 0 ? timeout_ms : 2000) * 100000ull) >> 16);
 }
 
-static int sk_b_ratio() {                              // fix-up form only when a tile is cut into >= ratio/2 pieces (tuning hook)
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("FACEHIP_SK_B_RATIO"); v = e ? atoi(e) : 4; }
-    return v;
-}
-static int g_sk_min_owner = -1;
-static int sk_min_owner() {
-    if (g_sk_min_owner < 0) {
-        const char* e = getenv("FACEHIP_SK_MIN_OWNER");   // tuning hook
-        g_sk_min_owner = e ? atoi(e) : 12;
-    }
-    return g_sk_min_owner;
-}
-static int g_sk_margin2 = -1;                         // helpers' head start over the owners, in half chunks
-static int sk_margin2() {
-    if (g_sk_margin2 < 0) {
-        const char* e = getenv("FACEHIP_SK_MARGIN");      // tuning hook
-        g_sk_margin2 = e ? atoi(e) : 3;
-    }
-    return g_sk_margin2;
-}
-
-template <int BM, int BN, int WM, int WN, int OCC>
-static void launch_cfg_tail(ConvArgs a, int resident_per_cu, int cfg_tag, hipStream_t s, const int T, const int tiles_n, const int S);
-
+// One tile config: conv_tall_kernel for the whole rounds it takes (conv_tall_plan), then conv_igemm_kernel for the tiles from tile0 on,
+// cut as conv_streamk_plan says, then conv_fixup_kernel if the plan has no owners.
+// (conv_tall_kernel, 256x64: IResNet's stage 1 / 2.  128x32: SCRFD's merged 64 -> 30 head convolutions at B = 128 — 340 -> 330 us on
+// 80x80, 98 -> 91 on 40x40: a small gain, because with three phase-locked workgroups per CU the image load at the top of each of the two
+// chunks stays exposed; a three-deep weight ring (two taps ahead, barrier with vmcnt(1)) changed nothing: 306 against 307 us)
 template <int BM, int BN, int WM, int WN, int OCC>
 static void launch_cfg(ConvArgs a, int resident_per_cu, int cfg_tag, hipStream_t s) {
-    const long M = (long)a.B * a.Ho * a.Wo;
-    const int tiles_m = (int)((M + BM - 1) / BM), tiles_n = (a.Cout + BN - 1) / BN;
-    const bool grouped = a.wt_group_rows > 0;
-    const int T = tiles_m * tiles_n;
-    const int S = (a.cus > 0 ? a.cus : num_cus()) * resident_per_cu;
+    using TL = Tile<BM, BN, WM, WN>;
+    const ConvGeom g = conv_geom(a);
+    const int tiles_n = (a.Cout + BN - 1) / BN, tiles = (int)((g.M + BM - 1) / BM) * tiles_n;
+    const int cus = a.cus > 0 ? a.cus : num_cus();
     a.zeros = conv_zero_line();
     a.tile0 = 0;
-    // 3x3 stride-1 layers on maps up to 112 wide: the whole ROUNDS of tiles run in conv_tall_kernel (one LDS image per 32-channel chunk
-    // for all nine taps), the remainder below with tile0 = the first tile it did not take
-    // (256x64: IResNet's stage 1 / 2.  128x32: SCRFD's merged 64 -> 30 head convolutions at B = 128 — 340 -> 330 us on 80x80, 98 -> 91 on
-    // 40x40: a small gain, because with three phase-locked workgroups per CU the image load at the top of each of the two chunks stays
-    // exposed; a three-deep weight ring (two taps ahead, barrier with vmcnt(1)) changed nothing: 306 against 307 us)
     if constexpr ((BM == 256 && BN == 64) || (BM == 128 && BN == 32)) {
-        constexpr int TOCC = BM == 256 ? 2 : 3;                             // resident workgroups per CU of the tall form (LDS)
-        const int St = (a.cus > 0 ? a.cus : num_cus()) * TOCC;
-        if (tall_enabled() && !grouped && !a.sc_in && a.ks == 3 && a.stride == 1 && a.pad == 1 && (a.Cin & 31) == 0 &&
-            a.H == a.Ho && a.W == a.Wo && a.W <= 112 && (BN == 32 ? a.n_outs > 0 || (a.Cout & 3) == 0 : a.n_outs == 0 && (a.Cout & 3) == 0) &&
-            a.res_mode != (int)ResMode::UP2X && T >= St) {
-            constexpr int RPt = Tile<BM, BN, WM, WN>::RP;
-            const int rows_a = (BM + 2 * a.W + 2 + RPt - 1) / RPt * RPt;
-            const size_t lds = ((size_t)rows_a * 8 + 2 * BN * 8) * sizeof(v4f);
-            int tall_tiles = (T / St) * St;
-            tall_tiles -= tall_tiles % tiles_n;
-            // A matrix-core-bound launch takes as long as its busiest CU has tiles (measured on the Winograd GEMMs), not whole
-            // chip-wide rounds: when the remainder is at most one more tile per CU and a tile is short (< ~30 us of one CU's matrix cores),
-            // running it here costs less than the second launch + fix-up of the split (SCRFD's 80x80 head convolution: 6 400 tiles = 25 per
-            // CU exactly: 329 + 38 us -> 343 us); IResNet's 256x64 tiles (44 us each) keep the split.
-            {
-                const int cus_ = a.cus > 0 ? a.cus : num_cus();
-                const double tile_us = 2.0 * BM * BN * (double)a.Kpad / 0.43e6;      // ~110 TFLOP/s over 256 CUs
-                if (tall_tiles > 0 && T - tall_tiles <= cus_ && tile_us < 30.0) tall_tiles = T;
+        constexpr int TOCC = BM == 256 ? 2 : 3;                             // (= conv_tall_plan's occ)
+        const ConvTallPlan t = conv_tall_plan(g, BM, BN, TL::RP, tiles, tiles_n, cus, conv_knobs());
+        if (t.tiles > 0) {
+            // conv_tall_kernel instantiates the merged and per-quad epilogues only (EP_MERGED | EP_QUADS): hold the predicate to that
+            if (a.n_outs == 0 && (a.Cout & 3)) throw std::logic_error("conv_tall_plan admitted a layer conv_tall_kernel has no epilogue form for");
+            static bool attr_set = false;
+            if (!attr_set) {
+                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_tall_kernel<BM, BN, WM, WN, TOCC>), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
+                attr_set = true;
             }
-            if (lds <= (size_t)(160 / TOCC) * 1024 && tall_tiles > 0) {
-                static bool attr_set = false;
-                if (!attr_set) {
-                    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_tall_kernel<BM, BN, WM, WN, TOCC>), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-                    attr_set = true;
-                }
-                KernelTimer& tt = KernelTimer::get();
-                tt.begin(s);
-                hipLaunchKernelGGL((conv_tall_kernel<BM, BN, WM, WN, TOCC>), dim3((unsigned)tall_tiles), dim3(WM * WN * 64), lds, s, a, tiles_n, rows_a);
-                tt.end(s, 10, a.t_flops * ((double)tall_tiles / T), a.t_bytes * ((double)tall_tiles / T));
-                a.t_flops *= (double)(T - tall_tiles) / T; a.t_bytes *= (double)(T - tall_tiles) / T;
-                a.tile0 = tall_tiles;
-                if (tall_tiles == T) return;
-            }
+            const double part = (double)t.tiles / tiles;
+            KernelTimer& tt = KernelTimer::get();
+            tt.begin(s);
+            hipLaunchKernelGGL((conv_tall_kernel<BM, BN, WM, WN, TOCC>), dim3((unsigned)t.tiles), dim3(TL::T), t.lds, s, a, tiles_n, t.rows_a);
+            tt.end(s, 10, a.t_flops * part, a.t_bytes * part);
+            a.t_flops *= (double)(tiles - t.tiles) / tiles; a.t_bytes *= (double)(tiles - t.tiles) / tiles;
+            a.tile0 = t.tiles;
+            if (t.tiles == tiles) return;
         }
     }
-    return launch_cfg_tail<BM, BN, WM, WN, OCC>(a, resident_per_cu, cfg_tag, s, T - a.tile0, tiles_n, S);
-}
-
-template <int BM, int BN, int WM, int WN, int OCC>
-static void launch_cfg_tail(ConvArgs a, int resident_per_cu, int cfg_tag, hipStream_t s, const int T, const int tiles_n, const int S) {
-    const bool grouped = a.wt_group_rows > 0;
     const int chunks = a.Kpad / 32;
-    int full = (T / S) * S;
-    int R = T - full;
-    int helpers = 0, owners = 0;
-    bool fixup = false;
-    a.sk_units = 0; a.sk_q = 1; a.sk_owner_chunks = 0; a.sk_maxp = 1;
-    // (a matrix-core-bound launch ends with its busiest CU: leaving R remainder tiles whole costs (ceil(R / CUs) - R / CUs) tile times of
-    //  imbalance; cutting them over the chip costs a fix-up launch (10-17 us).  Short tiles — SCRFD's 20x20 head convolutions, 11 us —
-    //  stay whole: 31 + 17 us -> 25 us; IResNet's 44 us tiles keep the split.)
-    const int cus_ = a.cus > 0 ? a.cus : num_cus();
-    const double tile_us = 2.0 * BM * BN * (double)a.Kpad / 0.43e6;                  // ~110 TFLOP/s over 256 CUs
-    const bool cheap_whole = ((R + cus_ - 1) / cus_ - (double)R / cus_) * tile_us < 10.0;
-    if (R > 0 && R * 10 <= S * 9 && a.slabs && a.sk_enable && !cheap_whole) {   // worth it only if the last round is <= 90 % full
-        // (1) owners + helpers inside the launch
-        const int H = S - R;
-        const int q_o = (int)(((long)R * chunks + (long)H * sk_margin2() / 2 + S - 1) / S);
-        const int Kh = chunks - q_o;
-        // (the hand-off costs an owner ~8 us — fence, poll, slab reads: only worth it next to >= 12 chunks of its own work)
-        if (Kh >= 1 && q_o >= sk_min_owner() && R <= (int)SK_COUNTERS) {
-            const long U = (long)R * Kh;
-            const int q_h = (int)((U + H - 1) / H);
-            const int maxp = (Kh + q_h - 1) / q_h + 1;
-            if (maxp <= 3 && (size_t)R * maxp * BM * BN <= SK_SLAB_FLOATS) {
-                a.sk_units = (int)U; a.sk_q = q_h; a.sk_owner_chunks = q_o; a.sk_maxp = maxp;
-                helpers = (int)((U + q_h - 1) / q_h); owners = R;
-            }
-        }
-        // (2) otherwise: every segment to a slab, reduced by the fix-up kernel
-        if (!owners) {
-            const long U = (long)R * chunks;
-            int q = (int)((U + S - 1) / S);
-            // do not cut segments shorter than 8 chunks — 24 for very deep K (the 25 088-deep FC: 61 slabs per tile made the fix-up kernel,
-            // 16 workgroups summing them one after the other, take 35 of the layer's 80 us; 21 slabs: 48 + 20 us)
-            // (the tail of a convolution whose whole rounds ran in conv_tall_kernel is a few tiles on an otherwise empty chip: cut them finer)
-            static int tail_q = -1;
-            if (tail_q < 0) { const char* e = getenv("FACEHIP_TALL_TAIL_Q"); tail_q = e ? atoi(e) : 3; }
-            const int min_q = a.tile0 > 0 ? std::min(chunks, tail_q) : chunks < 8 ? chunks : chunks >= 256 ? 24 : 8;
-            if (q < min_q) q = min_q;
-            const int maxp = (chunks + q - 1) / q + 1;
-            if (q * sk_b_ratio() <= chunks * 2 && q < chunks && (size_t)R * maxp * BM * BN <= SK_SLAB_FLOATS) {
-                a.sk_units = (int)U; a.sk_q = q; a.sk_maxp = maxp;
-                helpers = (int)((U + q - 1) / q); fixup = true;
-            }
-        }
-    }
-    if (!helpers) { full = T; R = 0; }
-    a.sk_full = full; a.sk_helpers = helpers; a.sk_rem = R;
-    a.sk_err = owners ? (a.sk_err ? a.sk_err : conv_error_words()) : nullptr; a.sk_timeout = g_sk_timeout; a.sk_test_drop = g_sk_test_drop;
-    a.ep_direct = ep_direct_env();
+    const ConvSkPlan pl = conv_streamk_plan(tiles - a.tile0, cus * resident_per_cu, chunks, TL::SLAB, cus, a.Kpad, a.tile0, a.slabs && a.sk_enable, conv_knobs());
+    a.sk_full = pl.full; a.sk_helpers = pl.helpers; a.sk_rem = pl.rem;
+    a.sk_units = pl.units; a.sk_q = pl.q; a.sk_owner_chunks = pl.owner_chunks; a.sk_maxp = pl.maxp;
+    a.sk_err = pl.owners ? (a.sk_err ? a.sk_err : conv_error_words()) : nullptr; a.sk_timeout = g_sk_timeout; a.sk_test_drop = g_sk_test_drop;
+    a.ep_direct = conv_knobs().ep_direct;
     KernelTimer& timer = KernelTimer::get();
     timer.begin(s);
-    const dim3 grid((unsigned)(full + helpers + owners));
-    if (grouped) {                                             // (wt_group_rows % BM == 0 and Cin % 32 == 0: the caller's contract)
-        hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, WM, WN, OCC, true, true>), grid, dim3(WM * WN * 64), 0, s, a, tiles_n, chunks);
+    const dim3 grid((unsigned)(pl.full + pl.helpers + pl.owners));
+    if (g.grouped) {                                           // (wt_group_rows % BM == 0 and Cin % 32 == 0: the caller's contract)
+        hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, WM, WN, OCC, true, true>), grid, dim3(TL::T), 0, s, a, tiles_n, chunks);
     } else if (a.sc_in)                                        // (launch_conv checked Cin % 32 == 0)
-        hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, WM, WN, OCC, true, false, true>), grid, dim3(WM * WN * 64), 0, s, a, tiles_n, chunks);
+        hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, WM, WN, OCC, true, false, true>), grid, dim3(TL::T), 0, s, a, tiles_n, chunks);
     else if ((a.Cin & 31) == 0)
-        hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, WM, WN, OCC, true, false>), grid, dim3(WM * WN * 64), 0, s, a, tiles_n, chunks);
+        hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, WM, WN, OCC, true, false>), grid, dim3(TL::T), 0, s, a, tiles_n, chunks);
     else
-        hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, WM, WN, OCC, false, false>), grid, dim3(WM * WN * 64), 0, s, a, tiles_n, chunks);
-    timer.end(s, grouped ? 7 : cfg_tag, a.t_flops, a.t_bytes);   // (grouped = Winograd GEMM: its own tag)
-    if (fixup) {
+        hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, WM, WN, OCC, false, false>), grid, dim3(TL::T), 0, s, a, tiles_n, chunks);
+    timer.end(s, g.grouped ? 7 : cfg_tag, a.t_flops, a.t_bytes);   // (grouped = Winograd GEMM: its own tag)
+    if (pl.fixup) {
         timer.begin(s);
-        hipLaunchKernelGGL((conv_fixup_kernel<BM, BN, WM, WN>), dim3((unsigned)(R * (BM / WM / 32) * (BN / WN / 32))), dim3(WM * WN * 64), 0, s, a, tiles_n, chunks);
+        hipLaunchKernelGGL((conv_fixup_kernel<BM, BN, WM, WN>), dim3((unsigned)(pl.rem * TL::TM * TL::TN)), dim3(TL::T), 0, s, a, tiles_n, chunks);
         timer.end(s, 6, 0.0, 0.0);
     }
 }

@@ -14,8 +14,9 @@
 // around the loop (several tiles per workgroup, counted waits, phase stamps) and the epilogue.  The pieces are plain
 // __forceinline__ functions over the kernel's own `__shared__ v4f lds[2][(128 + BN) * 8]`: every kernel keeps its name, its LDS size
 // and the register budget of the loop written out in place.
-// conv_igemm_kernel / conv_tall_kernel (2 x 2 wave tiles, fragment ring, per-lane tap masks) and the halo kernels take only the
-// typedefs, lds_dma16 and xcd_tile from here.
+// conv_igemm_kernel / conv_tall_kernel (2 x 2 wave tiles, fragment ring, per-lane tap masks; their shared pieces and the epilogue all
+// three convolution kernels run are in conv_tile.h, which includes this header) and the halo kernels take only the typedefs, lds_dma16
+// and xcd_tile from here.
 #pragma once
 #include <hip/hip_runtime.h>
 

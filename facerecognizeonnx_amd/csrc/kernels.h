@@ -7,6 +7,8 @@
 
 #include <vector>
 
+#include "conv_plan.h"
+
 namespace fh {
 
 void hip_check(hipError_t e, const char* what);
@@ -114,9 +116,9 @@ struct ConvArgs {
     int tile0;              // filled in by launch_conv: first tile conv_igemm_kernel computes (the tiles before it ran in conv_tall_kernel)
 };
 
-// cfg: 0 = 128x128 tile, 1 = 256x64, 2 = 128x32, 3 = 64x64 (256 threads each); -1 = choose.
+// cfg: 0 = 128x128 tile, 1 = 256x64, 2 = 128x32, 3 = 64x64 (256 threads each); -1 = choose (conv_pick_cfg).  Which kernels a layer
+// gets and how its remainder tiles are cut is host arithmetic in conv_plan.h; the kernels' shared device pieces are in conv_tile.h.
 void launch_conv(const ConvArgs& a, int cfg, hipStream_t s);
-int conv_pick_cfg(long M, int Cout);
 void conv_workspace_init(float* ws);          // zero the counter words of a freshly allocated stream-K workspace
 void conv_workspace_reset_async(float* ws, hipStream_t s);   // the same, stream-ordered (after a reported hand-off time-out)
 // Stream-K watchdog.  An owner workgroup whose helpers never arrive gives up after a bounded wait and reports through a host-mapped

@@ -932,6 +932,16 @@ FH_API int fh_rec_graph_stats(fh_rec* r, long long* replays);
  * next call on the same handle (or fh_det_sync / fh_rec_sync) returns FH_ERR_DEVICE ("stream-K hand-off timed out ...") instead of
  * the process hanging with the GPU; other handles are unaffected. */
 FH_API int fh_debug_streamk(int drop_publish, int timeout_ms);
+/* The launch arithmetic of the direct convolutions (csrc/conv_plan.h) — host only, no GPU, the default tuning switches.  `in` holds n_in
+ * ints, `out` receives n_out values; returns n_out, or FH_ERR_ARG for an unknown question, wrong lengths or a non-positive size.
+ *   what 0  stream-K remainder: in = T tiles, S resident workgroup slots, K chunks per tile, accumulators per tile, CUs, Kpad, tile0,
+ *           slabs allowed (8) -> out = full, rem, helpers, owners, fixup, units, q, owner_chunks, maxp (9; ConvSkPlan)
+ *   what 1  conv_pw_kernel: in = B, H, W, Cin, Cout, ksize, stride, pad, merged outputs, residual through 2x up-sampling, CUs (11)
+ *           -> out = its tile width 96 / 64 / 32, or 0 = the layer stays with conv_igemm_kernel (1)
+ *   what 2  conv_tall_kernel: in = the same 11, tile config 0..3 or -1 = automatic (12) -> out = tiles it takes, LDS image rows, LDS bytes (3)
+ *   what 3  slabs per remainder tile: in = r0, r1, chunks per tile left to the helpers, q (4) -> out = min, max over r0 <= r < r1 (2)
+ *   what 4  the workspace: in = nothing -> out = slab floats, counter words (2) */
+FH_API int fh_debug_conv_plan(int what, const int* in, int n_in, long long* out, int n_out);
 /* Test hook of the multi-tile Winograd GEMM (winograd.hip wino_gemm_pers_kernel): launches with more tiles than resident workgroup
  * slots walk several tiles per workgroup; slots > 0 makes the launcher pretend the device has that many (rounded up to 8), so that small
  * test layers take the multi-tile path with many tiles per workgroup; 0 restores the device's own count. */

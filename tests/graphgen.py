@@ -459,7 +459,8 @@ def _m_fc_splitk(n):
 
 
 def _m_pw_tall(n):
-    """1x1 s1 and 3x3 s1 layers with enough pixels at B_hi for conv_pw_kernel / conv_tall_kernel (conv_mfma.hip:1105, 1266)."""
+    """1x1 s1 and 3x3 s1 layers with enough pixels at B_hi for conv_pw_kernel / conv_tall_kernel (conv_plan.h: launch_pw's
+    eligibility predicate conv_pw_bn, conv_tall_kernel's take-over predicate conv_tall_plan)."""
     x = conv_act(n, "input", 32, 3, 1, act="relu", bn=False)
     a = conv_act(n, x, 32, 1, 1, act="relu", bn=False)
     b = conv_act(n, a, 32, 3, 1, act="prelu", bn=False)

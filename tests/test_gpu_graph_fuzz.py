@@ -61,10 +61,10 @@ def _layer_forms(o, sc_targets):
         out.append(("wino2", lambda B: B * per // 4 >= WINO2_MIN_BLOCKS))                      # engine.cpp:488, conv_wino2.hip:384-411
     elif (o["ks"] == 1 and o["stride"] == 1 and o["Cout"] <= 32 and o["Cin"] % 4 == 0 and o["Cout"] % 4 == 0 and not merged and
           o["i"] not in sc_targets):
-        out.append(("pw", lambda B: B * hw % 128 == 0 and B * hw // 128 >= N_CUS))             # conv_mfma.hip:1109-1124 (32-wide tiles)
+        out.append(("pw", lambda B: B * hw % 128 == 0 and B * hw // 128 >= N_CUS))             # conv_plan.h conv_pw_bn, launch_pw's eligibility (32-wide tiles)
     elif (s1 and o["Cin"] % 32 == 0 and o["Cout"] <= 32 and o["W"] <= 112 and "sc<-op" not in o["text"] and
           "+res(up2x)" not in o["text"]):
-        out.append(("tall", lambda B: -(-B * hw // 128) >= N_CUS * 3))                         # conv_mfma.hip:1266-1270, 128x32 tiles
+        out.append(("tall", lambda B: -(-B * hw // 128) >= N_CUS * 3))                         # conv_plan.h conv_tall_plan, conv_tall_kernel's take-over (128x32 tiles)
     return out
 
 

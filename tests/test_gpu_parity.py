@@ -65,6 +65,10 @@ CONV_CASES = [
     (64, 20, 20, 152, 288, 1, 1, -1),
     (72, 20, 20, 72, 152, 1, 1, -1),
     (256, 20, 20, 40, 64, 1, 1, -1),
+    # Cout % 4 != 0: the scalar branch of the plain epilogue — through conv_fixup_kernel (4 tiles of 128x128, 18 chunks cut in 8s) and
+    # straight from conv_igemm_kernel (whole tiles)
+    (2, 14, 14, 64, 126, 3, 1, 0),
+    (1, 9, 11, 32, 30, 3, 1, 2),
 ]
 
 

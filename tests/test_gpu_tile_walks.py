@@ -65,7 +65,7 @@ STEM_MFMA, STEM_U8 = "stem_mfma_kernel", "stem_conv_u8_kernel"
 # persistent kernels of the row, restated from the launchers.  The stem of the other rows runs in a kernel without a tile loop: the
 # thread-per-pixel stem (16 channels), or — 72 channels, more than the u8 stems take — the float preprocess + conv_igemm_kernel.  That
 # convolution goes through launch_conv, whose stream-K cut and tall split follow `cus`, but neither can touch it: K = 36 is two 32-deep
-# chunks, launch_cfg_tail never cuts below min(chunks, 8) chunks per segment, and the tall form needs Cin % 32 == 0.  Every tile is
+# chunks, conv_streamk_plan (csrc/conv_plan.h) never cuts below min(chunks, 8) chunks per segment, and the tall form needs Cin % 32 == 0.  Every tile is
 # computed whole by one workgroup whatever `cus` is, so the bitwise leg holds for those rows too.
 #   id                H   W  Cc Cout ds ss pad4 front  walkers
 CASES = [
