@@ -1554,6 +1554,7 @@ int fh_rec_set_wino_x3(fh_rec* r, int on) {
     return guarded([&] { return r->rec.net().set_wino_x3(on != 0, nullptr); });
 }
 int fh_rec_get_wino_x3(fh_rec* r) { return r && r->rec.net().wino_x3() ? 1 : 0; }
+int fh_rec_get_conv_x3(fh_rec* r) { return r ? r->rec.net().conv_x3_layers() : 0; }
 int fh_rec_set_wino_fusion(fh_rec* r, int on) { if (!r) return arg_error("null handle"); r->rec.net().fuse_wino = on != 0; return FH_OK; }
 // Opt-in precision mode of the recogniser, gated: the mode is only entered if, on a fixed pseudo-random batch of aligned crops, every
 // embedding it produces stays within 1 - cos < 1e-3 of the fp32 path's (north-star tolerance).  Otherwise the handle stays fp32.
@@ -1844,6 +1845,8 @@ int fh_debug_conv_plan(int what, const int* in, int n_in, long long* out, int n_
         }
     } else if (what == 4 && need(0, 2)) {
         out[0] = (long long)fh::SK_SLAB_FLOATS; out[1] = (long long)fh::SK_COUNTERS;
+    } else if (what == 5 && need(4, 2) && in[0] >= 0 && in[1] > 0 && in[2] > 0 && in[3] > 0) {
+        out[0] = fh::conv_x3_pays(in[0], in[1], in[2], in[3], knobs) ? 1 : 0; out[1] = fh::conv_x3_bn(in[2]);
     } else {
         return arg_error("fh_debug_conv_plan: unknown question, wrong array lengths or a non-positive size");
     }
@@ -1851,7 +1854,17 @@ int fh_debug_conv_plan(int what, const int* in, int n_in, long long* out, int n_
 }
 int fh_conv_forward_dev(const float* in, const float* wt, const float* bias, float* out, int batch, int h, int w, int cin, int cout,
                         int ks, int stride, int kpad, int cfg, void* stream) {
-    if (!in || !wt || !out || batch <= 0 || (ks != 1 && ks != 3) || cin % 4) return arg_error("fh_conv_forward_dev: bad argument");
+    return fh_conv_forward_ex_dev(in, wt, bias, out, batch, h, w, cin, cout, ks, stride, kpad, cfg, FH_PREC_FP32, nullptr, 0, 0, 0, 0, 0, stream);
+}
+int fh_conv_forward_ex_dev(const float* in, const float* wt, const float* bias, float* out, int batch, int h, int w, int cin, int cout,
+                           int ks, int stride, int kpad, int cfg, int precision, const float* sc_in, int sc_h, int sc_w, int sc_c, int sc_stride,
+                           int cus, void* stream) {
+    if (!in || !wt || !out || batch <= 0 || (ks != 1 && ks != 3) || cin % 4 || cout <= 0 || stride <= 0 || cus < 0 ||
+        (precision != FH_PREC_FP32 && precision != FH_PREC_F32X3) || (sc_in && (sc_h <= 0 || sc_w <= 0 || sc_c <= 0 || sc_stride <= 0)))
+        return arg_error("fh_conv_forward_dev: bad argument");
+    const bool x3 = precision == FH_PREC_F32X3;
+    if (x3 && !fh::conv_x3_ok(cin, cout))
+        return arg_error("fh_conv_forward_ex_dev: this layer has no three-piece bf16 form (it needs cin % 32 == 0 and cout % 64 == 0)");
     Owns owns(nullptr);                                                  // (no Net: the process-wide watchdog record)
     return guarded([&] {
         fh::ConvArgs a{};
@@ -1860,11 +1873,28 @@ int fh_conv_forward_dev(const float* in, const float* wt, const float* bias, flo
         a.B = batch; a.H = h; a.W = w; a.Cin = cin; a.Cout = cout; a.ks = ks; a.stride = stride; a.pad = pad;
         a.Ho = (h + 2 * pad - ks) / stride + 1; a.Wo = (w + 2 * pad - ks) / stride + 1;
         a.Kpad = kpad;
+        a.cus = cus;
+        if (sc_in) {
+            if ((a.Ho - 1) * sc_stride >= sc_h || (a.Wo - 1) * sc_stride >= sc_w) throw std::runtime_error("conv: the shortcut's input does not cover the output grid");
+            a.sc_in = sc_in; a.sc_H = sc_h; a.sc_W = sc_w; a.sc_C = sc_c; a.sc_stride = sc_stride;
+        }
         static fh::DevBuf slabs;                 // test entry point only: one shared workspace
         static unsigned slabs_gen = 0;
         if (!slabs.p) { slabs.ensure(fh::conv_slab_floats() * sizeof(float)); fh::conv_workspace_init(slabs.as<float>()); slabs_gen = fh::conv_error_generation(); }
         if (slabs_gen != fh::conv_error_generation()) { fh::conv_workspace_reset_async(slabs.as<float>(), S(stream)); slabs_gen = fh::conv_error_generation(); }
         a.slabs = slabs.as<float>(); a.sk_enable = 1;
+        if (x3) {                                // the weights split here as Net::set_wino_x3 splits them
+            static fh::DevBuf w3;
+            const int rows = fh::conv_wt_rows(cout);
+            FH_HIP(hipStreamSynchronize(S(stream)));                      // (an earlier call's launch may still read w3)
+            w3.ensure(fh::wino_x3_floats(rows, kpad) * sizeof(float));
+            fh::launch_pack_x3(wt, w3.as<float>(), rows, kpad, S(stream), 1);
+            a.wt = w3.as<float>();
+            fh::launch_conv_x3(a, 0, S(stream));
+            FH_HIP(hipGetLastError());
+            FH_HIP(hipStreamSynchronize(S(stream)));
+            return 0;
+        }
         fh::launch_conv(a, cfg, S(stream));
         FH_HIP(hipGetLastError());
         return 0;

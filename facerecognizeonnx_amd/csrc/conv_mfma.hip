@@ -56,17 +56,28 @@ namespace fh {
 // GRP: grouped form (several GEMMs stacked along M with one weight matrix each, see ConvArgs::wt_group_rows) — a separate
 // instantiation, so that the ungrouped convolutions keep their register allocation.
 // SC: with the folded-shortcut tap (ConvArgs::sc_in) — its own instantiation for the same reason.
-template <int BM, int BN, int WM, int WN, int OCC, bool FAST, bool GRP, bool SC = false>
+// X3: the K loop on three bf16 pieces and six v_mfma_f32_32x32x16_bf16 per 16-deep step (gemm_tile.h, "x3": fp32 products, 0.375 of the
+// f32 instruction's matrix-pipe cycles) — its own instantiations again.  The tile is the x3 GEMM's: 128 x BN, four waves of 32 pixel rows
+// x BN channels (Tile<128, BN, 4, 1>), so gemm_mma_x3 and GemmLane apply as they are.  The pixel operand is the fp32 LDS image below,
+// filled by the same tap_setup / load_chunk (zero line, tenth tap) and split in registers; p.wt is the x3 image of the [rows][Kpad]
+// weights (launch_pack_x3 with one frequency: [plane][chunk][row][4 slots], rows = conv_wt_rows(Cout)), fetched as gemm_load_chunk_x3
+// fetches U.  Everything around the K loop — roles, slabs, hand-off, epilogue — is the f32 kernel's.
+// Order of additions per output: chunks in K order (tap-major, the shortcut tap last), then the two 16-deep steps of a chunk, then the
+// six products in gemm_tile.h's order; with stream-K the owner's chunks first, then the helpers' slabs in K order.  Deterministic.
+template <int BM, int BN, int WM, int WN, int OCC, bool FAST, bool GRP, bool SC = false, bool X3 = false>
 __global__ __launch_bounds__(WM * WN * 64, OCC) void conv_igemm_kernel(const ConvArgs p_by_value, const int tiles_n, const int chunks) {
+    static_assert(!X3 || (FAST && !GRP && BM == GEMM_BM && WM == 4 && WN == 1 && BN % 64 == 0), "x3 K loop: the x3 GEMM's tile only");
     // The argument block is read where it already lies — the kernarg segment (constant address space, scalar loads) — instead of
     // through the by-value parameter: clang materialises that one as a private copy which the optimiser usually removes again, and when
     // it does not (it stopped doing so when this kernel grew the folded-shortcut tap) all 384 bytes live in scratch memory and every
     // field access becomes a scratch load: -25 % on every convolution.
     // (the instantiations without that tap keep the by-value form: there the copy is optimised away and the fields sit in SGPRs)
-    const ConvArgs& p = SC ? *(const ConvArgs*)__builtin_amdgcn_kernarg_segment_ptr() : p_by_value;      // first explicit argument = offset 0
+    // (the x3 instantiations read it there too, with or without the tap: by value the one without spilled 141 SGPRs instead of 65)
+    const ConvArgs& p = SC || X3 ? *(const ConvArgs*)__builtin_amdgcn_kernarg_segment_ptr() : p_by_value;      // first explicit argument = offset 0
     using TL = Tile<BM, BN, WM, WN>;
     constexpr int TM = TL::TM, TN = TL::TN, RP = TL::RP, AL = TL::AL, BL = TL::BL;
-    __shared__ v4f lds[2][(BM + BN) * 8];
+    constexpr int BUF = X3 ? gemm_buf_slots_x3<BN>() : (BM + BN) * 8;      // float4 slots per tile buffer
+    __shared__ v4f lds[2][BUF];
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);      // wave-uniform by construction: keep it scalar
@@ -101,7 +112,7 @@ __global__ __launch_bounds__(WM * WN * 64, OCC) void conv_igemm_kernel(const Con
     // stream-K owner: "my hand-off wait timed out" flag.  The LAST word of the LDS images (free once the K loop is over, and beyond the
     // 12 * BN floats the epilogue parks there) — a variable of its own would cost the 256x64 / 128x32 tiles a workgroup per CU
     // (their images fill 80 / 40 KB exactly).
-    volatile int* const sk_gave_up = reinterpret_cast<volatile int*>(&lds[1][0]) + ((BM + BN) * 8 * 4 - 1);
+    volatile int* const sk_gave_up = reinterpret_cast<volatile int*>(&lds[1][0]) + (BUF * 4 - 1);
 
     do {
         int part = 0;
@@ -125,21 +136,25 @@ __global__ __launch_bounds__(WM * WN * 64, OCC) void conv_igemm_kernel(const Con
         // wave-uniform base + 16*l, i.e. pass i of wave `wid` fills rows i*RP + wid*8 + (l>>3), 16-byte
         // column l&7 — the LDS image stays lane-linear and the XOR swizzle is applied to the SOURCE:
         // the lane fetches k-column (l&7) ^ ((row>>1)&7)  (cdna_hip_programming.md §5.4 rule 21).
-        const float* a_ptr[AL];
-        const float* sc_ptr[AL];                            // folded shortcut (ConvArgs::sc_in): this row's pixel of the 1x1 convolution's input
+        // (x3: the register file is full — a row's pixel is kept as a 32-bit element offset, launch_conv bounds the tensors to 2^31
+        //  elements, and the shortcut's pixel is worked out again from the row index when the tenth tap begins, once per tile)
+        const float* a_ptr[X3 ? 1 : AL];
+        int a_off[X3 ? AL : 1];                             // (x3: float offset of the row's first input pixel from p.in, swizzled column included)
+        const float* sc_ptr[X3 ? 1 : AL];                   // folded shortcut (ConvArgs::sc_in): this row's pixel of the 1x1 convolution's input
         unsigned a_mask[AL];
 #pragma unroll
         for (int i = 0; i < AL; ++i) {
             const int m = m0 + lrow + i * RP;
-            a_ptr[i] = p.zeros; a_mask[i] = 0; sc_ptr[i] = p.zeros;
+            a_ptr[X3 ? 0 : i] = p.zeros; a_off[X3 ? i : 0] = 0; a_mask[i] = 0; sc_ptr[X3 ? 0 : i] = p.zeros;
             if (p.ks == 1 && p.stride == 1) {               // plain GEMM rows (1x1 convs, FC, gallery): no pixel arithmetic at all
-                if (m < M) { a_ptr[i] = p.in + (long)m * p.Cin + lqs * 4; a_mask[i] = 1u; }
+                if (m < M) { a_ptr[X3 ? 0 : i] = p.in + (long)m * p.Cin + lqs * 4; a_off[X3 ? i : 0] = m * p.Cin + lqs * 4; a_mask[i] = 1u; }
             } else if (m < M) {
                 const int n = m / HoWo, rem = m - n * HoWo;
                 const int oy = rem / p.Wo, ox = rem - oy * p.Wo;
                 const int iy0 = oy * p.stride - p.pad, ix0 = ox * p.stride - p.pad;
-                a_ptr[i] = p.in + (long)(((n * p.H + iy0) * p.W + ix0) * p.Cin) + lqs * 4;
-                if (SC) sc_ptr[i] = p.sc_in + (long)(((n * p.sc_H + oy * p.sc_stride) * p.sc_W + ox * p.sc_stride) * p.sc_C) + lqs * 4;
+                a_ptr[X3 ? 0 : i] = p.in + (long)(((n * p.H + iy0) * p.W + ix0) * p.Cin) + lqs * 4;
+                a_off[X3 ? i : 0] = ((n * p.H + iy0) * p.W + ix0) * p.Cin + lqs * 4;
+                if (SC && !X3) sc_ptr[i] = p.sc_in + (long)(((n * p.sc_H + oy * p.sc_stride) * p.sc_W + ox * p.sc_stride) * p.sc_C) + lqs * 4;
                 unsigned mk = 0;
                 if (p.ks == 3) {
 #pragma unroll
@@ -157,6 +172,10 @@ __global__ __launch_bounds__(WM * WN * 64, OCC) void conv_igemm_kernel(const Con
         unsigned w_off[BL];
 #pragma unroll
         for (int i = 0; i < BL; ++i) w_off[i] = (unsigned)(((lrow + i * RP) * p.Kpad + lqs * 4) * 4);
+        // x3: this thread's 16 bytes of plane h of the current chunk (a plane of one chunk and tile is BN * 64 consecutive bytes)
+        const int w3_rows = X3 ? (p.Cout + 127) / 128 * 128 : 0;                          // (= conv_wt_rows(Cout), the image's row count)
+        const v4f* w3 = reinterpret_cast<const v4f*>(g_wt) + ((size_t)c_begin * w3_rows + n0) * 4 + tid;
+        const size_t w3_plane = (size_t)chunks * w3_rows * 4, w3_chunk = (size_t)w3_rows * 4;
 
         const unsigned long long zero_addr = (unsigned long long)p.zeros + (unsigned long long)(lane & 0) ;
         v4f* const dstA = &lds[0][wid * 64];               // + buf*(BM+BN)*8 + i*RP*8; the hardware adds 16*lane
@@ -177,7 +196,13 @@ __global__ __launch_bounds__(WM * WN * 64, OCC) void conv_igemm_kernel(const Con
 #pragma unroll
                 for (int i = 0; i < AL; ++i) {
                     const bool on = a_mask[i] != 0;
-                    cur[i] = (const float*)(on ? (unsigned long long)(sc_ptr[i] + ld_ci) : zero_addr);
+                    const float* sp = sc_ptr[X3 ? 0 : i];
+                    if constexpr (X3) {                     // (a_mask != 0: the row is a real pixel, m < M)
+                        const int m = m0 + lrow + i * RP;
+                        const int n = m / HoWo, rem = m - n * HoWo, oy = rem / p.Wo, ox = rem - oy * p.Wo;
+                        sp = p.sc_in + (long)(((n * p.sc_H + oy * p.sc_stride) * p.sc_W + ox * p.sc_stride) * p.sc_C) + lqs * 4;
+                    }
+                    cur[i] = (const float*)(on ? (unsigned long long)(sp + ld_ci) : zero_addr);
                     adv[i] = on ? 32 : 0;
                 }
                 return;
@@ -186,7 +211,7 @@ __global__ __launch_bounds__(WM * WN * 64, OCC) void conv_igemm_kernel(const Con
             const int toff = (ksz == 3 ? (ky * inW + kx) * Cin : 0) + ld_ci;
 #pragma unroll
             for (int i = 0; i < AL; ++i) {
-                const unsigned long long real = (unsigned long long)(a_ptr[i] + toff);
+                const unsigned long long real = (unsigned long long)(X3 ? p.in + (a_off[X3 ? i : 0] + toff) : a_ptr[X3 ? 0 : i] + toff);
                 const bool on = ((a_mask[i] >> ld_tap) & 1u) != 0;
                 cur[i] = (const float*)(on ? real : zero_addr);
                 adv[i] = on ? 32 : 0;
@@ -198,14 +223,22 @@ __global__ __launch_bounds__(WM * WN * 64, OCC) void conv_igemm_kernel(const Con
             tap_setup();
         }
         auto load_chunk = [&](int kc, int buf) __attribute__((always_inline)) {
-            v4f* const dA = dstA + buf * ((BM + BN) * 8);
-            v4f* const dB = dstB + buf * ((BM + BN) * 8);
+            v4f* const dA = dstA + buf * BUF;
+            v4f* const dB = dstB + buf * BUF;
             if (FAST) {
 #pragma unroll
                 for (int i = 0; i < AL; ++i) { lds_dma16(cur[i], dA + i * RP * 8); cur[i] += adv[i]; }
+                if constexpr (X3) {                         // (as gemm_load_chunk_x3)
+#pragma unroll
+                    for (int pl = 0; pl < 3; ++pl)
+#pragma unroll
+                        for (int i = 0; i < BN / 64; ++i) lds_dma16(reinterpret_cast<const float*>(w3 + pl * w3_plane + i * 256), dB + pl * BN * 4 + i * 256);
+                    w3 += w3_chunk;
+                } else {
 #pragma unroll
                 for (int i = 0; i < BL; ++i) lds_dma16(reinterpret_cast<const float*>(w_base + w_off[i]), dB + i * RP * 8);
                 w_base += 128;
+                }
                 ld_ci += 32;
                 if (ld_ci >= Cin && ld_tap < taps) { ld_ci = 0; ++ld_tap; tap_setup(); }      // wave-uniform branch
                 return;
@@ -224,7 +257,7 @@ __global__ __launch_bounds__(WM * WN * 64, OCC) void conv_igemm_kernel(const Con
 #pragma unroll
             for (int i = 0; i < AL; ++i) {
                 // integer select (v_cndmask), not a branch: border lanes read the zero line
-                const unsigned long long real = (unsigned long long)(a_ptr[i] + toff);
+                const unsigned long long real = (unsigned long long)(a_ptr[X3 ? 0 : i] + toff);
                 const unsigned long long sel = (kvalid && ((a_mask[i] >> tap) & 1u)) ? real : zero_addr;
                 lds_dma16((const float*)sel, dA + i * RP * 8);
             }
@@ -258,6 +291,10 @@ __global__ __launch_bounds__(WM * WN * 64, OCC) void conv_igemm_kernel(const Con
         }
 
         auto compute = [&](int buf) {
+            if constexpr (X3) {
+                gemm_mma_x3<TN>(acc[0], lds[buf], GemmLane{tid, lane, wid, fr, fh2, fsw});
+                return;
+            }
             const v4f* X = lds[buf] + (wm * TM * 32 + fr) * 8;
             const v4f* Wt = lds[buf] + BM * 8 + (wn * TN * 32 + fr) * 8;
             v4f x[2][TM], w[2][TN];
@@ -379,8 +416,9 @@ __global__ __launch_bounds__(WM * WN * 64, OCC) void conv_igemm_kernel(const Con
         }
         // (the transposition scratch of the whole-line epilogue sits behind the vectors: both fit the tile buffers of every shape)
         static_assert((EpVec::FLOATS + WM * WN * 32 * 36) * sizeof(float) <= sizeof(lds), "epilogue scratch");
-        conv_epilogue<BM, BN, WM, WN>(p, acc, m0, n0, wm, wn, lane, -1, -1, use_ep ? ep : nullptr,
-                                      use_ep && conv_ep_wants_lines(p) ? ep + EpVec::FLOATS : nullptr);
+        // (x3: launch_conv_x3 admits Cout % 64 == 0 without merged outputs and launch_cfg pins ep_direct to 0 — the whole-line form alone)
+        conv_epilogue<BM, BN, WM, WN, X3 ? EP_LINES : EP_ALL>(p, acc, m0, n0, wm, wn, lane, -1, -1, use_ep ? ep : nullptr,
+                                                             use_ep && conv_ep_wants_lines(p) ? ep + EpVec::FLOATS : nullptr);
     } while (role == HELPER && hu < hu_end);
 }
 
@@ -786,7 +824,8 @@ void conv_debug_streamk(int drop_publish, int timeout_ms) {
 // (conv_tall_kernel, 256x64: IResNet's stage 1 / 2.  128x32: SCRFD's merged 64 -> 30 head convolutions at B = 128 — 340 -> 330 us on
 // 80x80, 98 -> 91 on 40x40: a small gain, because with three phase-locked workgroups per CU the image load at the top of each of the two
 // chunks stays exposed; a three-deep weight ring (two taps ahead, barrier with vmcnt(1)) changed nothing: 306 against 307 us)
-template <int BM, int BN, int WM, int WN, int OCC>
+// X3: conv_igemm_kernel's three-piece bf16 instantiations (a.wt = the x3 weight image; launch_conv_x3 checked the layer's form).
+template <int BM, int BN, int WM, int WN, int OCC, bool X3 = false>
 static void launch_cfg(ConvArgs a, int resident_per_cu, int cfg_tag, hipStream_t s) {
     using TL = Tile<BM, BN, WM, WN>;
     const ConvGeom g = conv_geom(a);
@@ -794,7 +833,7 @@ static void launch_cfg(ConvArgs a, int resident_per_cu, int cfg_tag, hipStream_t
     const int cus = a.cus > 0 ? a.cus : num_cus();
     a.zeros = conv_zero_line();
     a.tile0 = 0;
-    if constexpr ((BM == 256 && BN == 64) || (BM == 128 && BN == 32)) {
+    if constexpr (!X3 && ((BM == 256 && BN == 64) || (BM == 128 && BN == 32))) {
         constexpr int TOCC = BM == 256 ? 2 : 3;                             // (= conv_tall_plan's occ)
         const ConvTallPlan t = conv_tall_plan(g, BM, BN, TL::RP, tiles, tiles_n, cus, conv_knobs());
         if (t.tiles > 0) {
@@ -820,11 +859,14 @@ static void launch_cfg(ConvArgs a, int resident_per_cu, int cfg_tag, hipStream_t
     a.sk_full = pl.full; a.sk_helpers = pl.helpers; a.sk_rem = pl.rem;
     a.sk_units = pl.units; a.sk_q = pl.q; a.sk_owner_chunks = pl.owner_chunks; a.sk_maxp = pl.maxp;
     a.sk_err = pl.owners ? (a.sk_err ? a.sk_err : conv_error_words()) : nullptr; a.sk_timeout = g_sk_timeout; a.sk_test_drop = g_sk_test_drop;
-    a.ep_direct = conv_knobs().ep_direct;
+    a.ep_direct = X3 ? 0 : conv_knobs().ep_direct;             // (the x3 instantiations hold the whole-line epilogue only)
     KernelTimer& timer = KernelTimer::get();
     timer.begin(s);
     const dim3 grid((unsigned)(pl.full + pl.helpers + pl.owners));
-    if (g.grouped) {                                           // (wt_group_rows % BM == 0 and Cin % 32 == 0: the caller's contract)
+    if constexpr (X3) {
+        if (a.sc_in) hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, WM, WN, OCC, true, false, true, true>), grid, dim3(TL::T), 0, s, a, tiles_n, chunks);
+        else hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, WM, WN, OCC, true, false, false, true>), grid, dim3(TL::T), 0, s, a, tiles_n, chunks);
+    } else if (g.grouped) {                                    // (wt_group_rows % BM == 0 and Cin % 32 == 0: the caller's contract)
         hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, WM, WN, OCC, true, true>), grid, dim3(TL::T), 0, s, a, tiles_n, chunks);
     } else if (a.sc_in)                                        // (launch_conv checked Cin % 32 == 0)
         hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, WM, WN, OCC, true, false, true>), grid, dim3(TL::T), 0, s, a, tiles_n, chunks);
@@ -840,15 +882,33 @@ static void launch_cfg(ConvArgs a, int resident_per_cu, int cfg_tag, hipStream_t
     }
 }
 
-void launch_conv(const ConvArgs& a, int cfg, hipStream_t s) {
-    const long M = (long)a.B * a.Ho * a.Wo;
-    if (M <= 0) return;
+static void conv_check(const ConvArgs& a, long M) {
     // the loader and the epilogue index pixels and tensor elements with 32-bit integers
     if ((long)a.B * a.H * a.W * a.Cin >= (1L << 31) || M * a.Cout >= (1L << 31))
         throw std::runtime_error("conv: tensor too large for the 32-bit element offsets of one launch (split the batch)");
     if (a.sc_in && (a.ks != 3 || a.Cin % 32 != 0 || a.sc_C % 32 != 0 || a.Kpad != 9 * a.Cin + a.sc_C || a.wt_group_rows > 0 ||
                     (long)a.B * a.sc_H * a.sc_W * a.sc_C >= (1L << 31)))
         throw std::runtime_error("conv: folded shortcut needs a 3x3 convolution with Cin % 32 == 0, sc_C % 32 == 0 and Kpad = 9*Cin + sc_C");
+}
+
+// The three-piece bf16 form of one layer: a.wt = the x3 image of its [conv_wt_rows(Cout)][Kpad] weights.  tag: the timer tag the layer's
+// f32 launch would carry (the launch is booked there, with the same f32-equivalent FLOPs).
+void launch_conv_x3(const ConvArgs& a, int tag, hipStream_t s) {
+    const long M = (long)a.B * a.Ho * a.Wo;
+    if (M <= 0) return;
+    conv_check(a, M);
+    if (!conv_x3_ok(a.Cin, a.Cout) || a.wt_group_rows > 0 || a.Kpad % 32 || a.n_outs > 0 || (a.ks != 1 && a.ks != 3) ||
+        a.Kpad != a.ks * a.ks * a.Cin + (a.sc_in ? a.sc_C : 0))
+        throw std::runtime_error("conv: this layer has no three-piece bf16 form (it needs Cin % 32 == 0, Cout % 64 == 0, one group)");
+    if (conv_x3_bn(a.Cout) == 128) launch_cfg<128, 128, 4, 1, 2, true>(a, 2, tag, s);
+    else launch_cfg<128, 64, 4, 1, 2, true>(a, 2, tag, s);
+}
+bool conv_x3_ok(int Cin, int Cout) { return Cin > 0 && Cin % 32 == 0 && conv_x3_bn(Cout) != 0; }
+
+void launch_conv(const ConvArgs& a, int cfg, hipStream_t s) {
+    const long M = (long)a.B * a.Ho * a.Wo;
+    if (M <= 0) return;
+    conv_check(a, M);
     if (launch_pw(a, s)) return;
     if (cfg < 0) cfg = conv_pick_cfg(M, a.Cout);
     switch (cfg) {

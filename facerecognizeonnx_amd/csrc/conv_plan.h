@@ -26,6 +26,8 @@ struct ConvKnobs {
     int conv_pw = 1;         // FACEHIP_CONV_PW / FACEHIP_CONV_TALL: 0 = conv_igemm_kernel everywhere (A / B timing)
     int conv_tall = 1;
     int ep_direct = 0;       // FACEHIP_EP_DIRECT: see ConvArgs::ep_direct
+    int conv_x3 = 1;         // FACEHIP_CONV_X3: 0 = the folded-shortcut layers stay on the f32 MFMA even where the handle's x3 switch is on,
+                             // 2 = x3 wherever the layer has the form, whatever conv_x3_pays would say (A / B timing)
 };
 inline const ConvKnobs& conv_knobs() {
     static const ConvKnobs k = [] {
@@ -33,7 +35,7 @@ inline const ConvKnobs& conv_knobs() {
         auto env = [](const char* name, int& x) { if (const char* e = getenv(name)) x = atoi(e); };
         env("FACEHIP_SK_B_RATIO", v.sk_b_ratio); env("FACEHIP_SK_MIN_OWNER", v.sk_min_owner); env("FACEHIP_SK_MARGIN", v.sk_margin2);
         env("FACEHIP_TALL_TAIL_Q", v.tall_tail_q); env("FACEHIP_CONV_PW", v.conv_pw); env("FACEHIP_CONV_TALL", v.conv_tall);
-        env("FACEHIP_EP_DIRECT", v.ep_direct);
+        env("FACEHIP_EP_DIRECT", v.ep_direct); env("FACEHIP_CONV_X3", v.conv_x3);
         return v;
     }();
     return k;
@@ -56,6 +58,20 @@ inline int conv_pick_cfg(long M, int Cout) {
     if (bn == 128) return 0;
     if (bn == 64) return (M / 256) * (cols(64) / 64) >= 1024 ? 1 : 3;
     return 2;
+}
+
+// The three-piece bf16 K loop of conv_igemm_kernel ("x3", gemm_tile.h) exists for 128 x BN tiles of four 32-row waves, BN = 128 where
+// Cout % 128 == 0 and 64 where Cout % 64 == 0; 0 = the layer has no such form (it also needs Cin % 32 == 0 and no groups: the caller's part).
+inline int conv_x3_bn(int Cout) { return Cout <= 0 ? 0 : Cout % 128 == 0 ? 128 : Cout % 64 == 0 ? 64 : 0; }
+// Does the x3 K loop pay for a launch of `tiles` 128 x conv_x3_bn(Cout) tiles of depth Kpad on `cus` CUs?  Measured on IResNet-50's four
+// folded-shortcut layers (Kpad 640 / 1216 / 2432 / 4864) at B = 8, 32, 64, 128, 256, f32 against x3 in one session (profiles/conv_x3.md):
+// every layer gains at every batch, 0.61-0.69 of the f32 time from B = 64 up and still 0.68-0.95 at B = 8, where the smallest launch is
+// 16 tiles on 256 CUs cut by stream-K.  So the form is on from there up — one tile per 16 CUs, 20 chunks — and what lies below, which
+// nothing measured, stays on the f32 kernel.  Monotone in `tiles` and in Kpad.
+inline bool conv_x3_pays(long tiles, int Kpad, int Cout, int cus, const ConvKnobs& k) {
+    if (!k.conv_x3 || !conv_x3_bn(Cout) || Kpad % 32 || cus <= 0) return false;
+    if (k.conv_x3 == 2) return true;
+    return tiles * 16 >= (long)cus && Kpad >= 640;
 }
 
 // One tile's time on one CU's matrix cores (~110 TFLOP/s over 256 CUs).  A matrix-core-bound launch takes as long as its busiest CU

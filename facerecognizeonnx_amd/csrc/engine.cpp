@@ -440,6 +440,22 @@ int Net::set_wino_x3(bool on, hipStream_t s) {
         FH_HIP(hipStreamSynchronize(s));
     }
     wino_x3_ = on && layers > 0;
+    // the folded-shortcut direct convolutions: one x3 image per layer of its concatenated [rows][9 Cin + sc_C] weights
+    size_t sc_total = 0;
+    conv_x3_n_ = 0;
+    for (size_t i = 0; i < dev_.size(); ++i) {
+        DevOp& d = dev_[i];
+        d.sc_x3 = d.sc_src >= 0 && plan_.ops[i].ks == 3 && conv_x3_ok(plan_.ops[i].Cin, plan_.ops[i].Cout) && d.Kpad_sc % 32 == 0;
+        if (d.sc_x3) { d.wt_sc_x3 = sc_total; sc_total += wino_x3_floats(conv_wt_rows(plan_.ops[i].Cout), d.Kpad_sc); ++conv_x3_n_; }
+    }
+    if (on && conv_x3_n_ > 0 && wsc_x3_.bytes < sc_total * sizeof(float)) {
+        wsc_x3_.ensure(sc_total * sizeof(float));
+        for (size_t i = 0; i < dev_.size(); ++i)
+            if (dev_[i].sc_x3)
+                launch_pack_x3(params_.as<float>() + dev_[i].wt_sc, wsc_x3_.as<float>() + dev_[i].wt_sc_x3, conv_wt_rows(plan_.ops[i].Cout), dev_[i].Kpad_sc, s, 1);
+        FH_HIP(hipStreamSynchronize(s));
+    }
+    conv_x3_ = on && conv_x3_n_ > 0;
     return on ? layers : 0;
 }
 
@@ -560,7 +576,14 @@ void Net::run(int batch, hipStream_t s, int first_op) {
                     tag = 7;
                     break;
                 }
-                launch_conv(a, cfg, s);
+                // a folded-shortcut layer's K loop on three bf16 pieces where the handle has the form on and the launch pays (conv_plan.h)
+                if (conv_x3_ && d.sc_x3 && a.sc_in && conv_x3_pays(((M + 127) / 128) * (op.Cout / conv_x3_bn(op.Cout)), a.Kpad, op.Cout,
+                                                                     cus > 0 ? cus : conv_num_cus(), conv_knobs())) {
+                    a.wt = wsc_x3_.as<float>() + d.wt_sc_x3;
+                    launch_conv_x3(a, cfg, s);
+                } else {
+                    launch_conv(a, cfg, s);
+                }
                 tag = cfg;
                 break;
             }

@@ -69,6 +69,9 @@ class Net {
     // device, into a second image of 1.5 x the f32 one's bytes.  Returns the number of layers that have the form.
     int set_wino_x3(bool on, hipStream_t s);
     bool wino_x3() const { return wino_x3_; }
+    // The same switch governs the direct convolutions with a folded shortcut (IResNet's stride-2 3x3 layers): their K loop on three bf16
+    // pieces (conv_mfma.hip, X3) where conv_x3_pays says the launch gains.  Number of layers that have the form while the switch is on.
+    int conv_x3_layers() const { return conv_x3_ ? conv_x3_n_ : 0; }
     int cus = 0;                                          // CUs of the stream this net runs on when it is CU-masked (0 = all)
     int force_cfg = -1;                                   // tuning hook: conv tile config override
     bool sk_enable = true;                                // tuning hook: stream-K remainder wave
@@ -77,7 +80,7 @@ class Net {
     long long config_word() const {
         return (long long)fuse_stem | (long long)fuse_front << 1 | (long long)winograd << 2 | (long long)halo_conv << 3 |
                (long long)fold_shortcut << 4 | (long long)fuse_wino << 5 | (long long)bf16x2_ << 6 | (long long)sk_enable << 7 |
-               (long long)(cus & 0xffff) << 8 | (long long)((force_cfg + 1) & 0xff) << 24 | (long long)wino_x3_ << 32;
+               (long long)(cus & 0xffff) << 8 | (long long)((force_cfg + 1) & 0xff) << 24 | (long long)wino_x3_ << 32 | (long long)conv_x3_ << 33;
     }
 
   private:
@@ -107,6 +110,8 @@ class Net {
         int sc_src = -1;                                      // 3x3 conv that can take op[sc_src] (1x1 shortcut) into its K loop ...
         size_t wt_sc = 0, bias_sc = 0;                        // ... weights [rows][9*Cin + sc_C] and summed bias for that form
         int Kpad_sc = 0;
+        size_t wt_sc_x3 = 0;                                  // ... offset of that form's three-piece (x3) weight image in wsc_x3_
+        bool sc_x3 = false;                                   // ... which exists (Cin % 32 == 0, Cout % 64 == 0)
         bool sc_dst = false;                                  // ... and the shortcut's side: skipped when its consumer folds it
         bool fuse_next = false;                               // Winograd op followed by another on the same small map: fused transform kernel
         bool fuse_feed_aff = false;                           //   the next conv sees out * s2 + t2 (its block's BatchNorm) instead of out
@@ -120,8 +125,9 @@ class Net {
     float* tensor_ptr(int t) const { return arena_.as<float>() + plan_.tensors[t].offset * (size_t)cap_; }
     Plan plan_;
     std::vector<DevOp> dev_;
-    DevBuf params_, arena_, partial_, wino_v_, wino_m_, w36_bf_, w36_x3_;
-    bool bf16x2_ = false, wino_x3_ = false;
+    DevBuf params_, arena_, partial_, wino_v_, wino_m_, w36_bf_, w36_x3_, wsc_x3_;
+    bool bf16x2_ = false, wino_x3_ = false, conv_x3_ = false;
+    int conv_x3_n_ = 0;
     size_t wino_maxc_ = 0;
     size_t wino_elems_ = 0;                                   // per image: 36 * tiles * max(Cin, Cout) of the largest Winograd op
     int cap_ = 0;

@@ -119,6 +119,12 @@ struct ConvArgs {
 // cfg: 0 = 128x128 tile, 1 = 256x64, 2 = 128x32, 3 = 64x64 (256 threads each); -1 = choose (conv_pick_cfg).  Which kernels a layer
 // gets and how its remainder tiles are cut is host arithmetic in conv_plan.h; the kernels' shared device pieces are in conv_tile.h.
 void launch_conv(const ConvArgs& a, int cfg, hipStream_t s);
+// The same layer on conv_igemm_kernel's three-piece bf16 K loop ("x3", gemm_tile.h: fp32 products from six bf16 MFMAs; 128 x 128 or 128 x 64
+// tiles): a.wt = launch_pack_x3(weights [conv_wt_rows(Cout)][Kpad], ..., freqs = 1).  conv_x3_ok: the layer has the form (Cin % 32 == 0,
+// Cout % 64 == 0; ungrouped, Kpad = ks*ks*Cin + sc_C: checked by the launcher).  tag: the timer tag to book the launch under.  Whether the
+// form pays for a launch is conv_x3_pays (conv_plan.h).
+void launch_conv_x3(const ConvArgs& a, int tag, hipStream_t s);
+bool conv_x3_ok(int Cin, int Cout);
 void conv_workspace_init(float* ws);          // zero the counter words of a freshly allocated stream-K workspace
 void conv_workspace_reset_async(float* ws, hipStream_t s);   // the same, stream-ordered (after a reported hand-off time-out)
 // Stream-K watchdog.  An owner workgroup whose helpers never arrive gives up after a bounded wait and reports through a host-mapped
@@ -169,7 +175,8 @@ void launch_wino_gemm(const ConvArgs& a, const float* wt36, const float* V, floa
 bool wino_gemm_ok_bf16x2(int Cin, int Cout);              // ... which also says whether the layer has the three-piece (x3) form
 // Three-piece bf16 GEMM ("x3", gemm_tile.h): fp32 U [36][rows][K] -> its x3 image of 36 * wino_x3_floats(rows, K) floats; whether a handle's
 // fp32 path uses it by default (FACEHIP_WINO_X3, read once); whether it pays for a launch of row_tiles 128-row tiles
-void launch_pack_x3(const float* in, float* out, int rows, int K, hipStream_t s);
+// (freqs: matrices in `in`; 1 = one [rows][K] weight matrix of a direct convolution, launch_conv_x3)
+void launch_pack_x3(const float* in, float* out, int rows, int K, hipStream_t s, int freqs = 36);
 inline size_t wino_x3_floats(int rows, int K) { return (size_t)rows * K * 3 / 2; }
 bool wino_x3_default();
 bool wino_x3_pays(long row_tiles, int Cin, int Cout);

@@ -54,8 +54,8 @@ __global__ __launch_bounds__(256) void wino_pack_x3_kernel(const float* __restri
         o[0] = __builtin_bit_cast(v4u, h); o[plane] = __builtin_bit_cast(v4u, m); o[2 * plane] = __builtin_bit_cast(v4u, l);
     }
 }
-void launch_pack_x3(const float* in, float* out, int rows, int K, hipStream_t s) {    // K % 32 == 0; out: 36 * wino_x3_floats(rows, K) floats
-    const long n8 = 36L * rows * (K / 8);
+void launch_pack_x3(const float* in, float* out, int rows, int K, hipStream_t s, int freqs) {    // K % 32 == 0; out: freqs * wino_x3_floats(rows, K) floats
+    const long n8 = (long)freqs * rows * (K / 8);
     if (n8 > 0) hipLaunchKernelGGL(wino_pack_x3_kernel, dim3((unsigned)std::min<long>((n8 + 255) / 256, 256 * 64)), dim3(256), 0, s, in, reinterpret_cast<v4u*>(out), rows, K, n8);
 }
 

@@ -861,6 +861,10 @@ FH_API int fh_rec_get_precision(fh_rec* r);
  * Returns the number of layers that have the form (0 for off), or < 0.  Synchronous the first time it is switched on. */
 FH_API int fh_rec_set_wino_x3(fh_rec* r, int on);
 FH_API int fh_rec_get_wino_x3(fh_rec* r);
+/* The same switch governs the direct convolutions that carry a folded shortcut (IResNet's stride-2 3x3 layers): where the launch gains
+ * (fh_debug_conv_plan question 5) their K loop runs on the same three pieces and six products.  Number of layers of this handle that have
+ * that form while the switch is on (0 while it is off). */
+FH_API int fh_rec_get_conv_x3(fh_rec* r);
 /* A handle whose stream is restricted to a subset of the CUs (hipExtStreamCreateWithCUMask, e.g. detector and
  * recogniser side by side on disjoint CU sets) should say how many it gets: it sizes the convolution kernels'
  * remainder round.  0 = the whole device (default). */
@@ -891,6 +895,17 @@ FH_API int fh_resize_u8c3_dev(const uint8_t* d_src, int sh, int sw, int sstep, u
                               void* stream);
 FH_API int fh_conv_forward_dev(const float* d_in, const float* d_wt_packed, const float* d_bias, float* d_out, int batch,
                                int h, int w, int cin, int cout, int ksize, int stride, int kpad, int cfg, void* stream);
+/* The same with a precision argument, an optional folded shortcut and the CU count the launcher plans with.  precision = FH_PREC_FP32: the
+ * f32 MFMA kernels; FH_PREC_F32X3: conv_igemm_kernel's three-piece bf16 K loop (fp32 products from six bf16 MFMAs; cfg is ignored, the
+ * tile is 128 x 128 or 128 x 64) on a copy of the weights split here as the engine splits them — refused for layers without the form
+ * ("... no three-piece bf16 form": cin % 32 != 0, cout % 64 != 0; this entry point has no grouped layers).  d_sc_in (may be NULL): the input
+ * [batch][sc_h][sc_w][sc_c] of a 1x1 convolution of stride sc_stride on the same output grid, run as a tenth tap of the K loop: d_wt_packed
+ * is then [fh_conv_wt_rows(cout)][9 cin + sc_c] with the shortcut's weights behind the 3x3 ones, kpad = 9 cin + sc_c, ksize = 3,
+ * cin % 32 == 0, sc_c % 32 == 0.  cus > 0: the launcher plans the stream-K remainder as for a device of that many CUs (ConvArgs::cus), so
+ * that small layers reach every role; 0 = the device's own count.  Synchronous for FH_PREC_F32X3. */
+FH_API int fh_conv_forward_ex_dev(const float* d_in, const float* d_wt_packed, const float* d_bias, float* d_out, int batch,
+                                  int h, int w, int cin, int cout, int ksize, int stride, int kpad, int cfg, int precision,
+                                  const float* d_sc_in, int sc_h, int sc_w, int sc_c, int sc_stride, int cus, void* stream);
 /* 3x3 stride-1 pad-1 convolution (+bias) in the Winograd F(4x4,3x3) form the deep layers use; w_ohwi = HOST weights
  * [cout][3*3][cin]; cin % 32 == 0, cout % 4 == 0.  Synchronous. */
 FH_API int fh_conv_winograd_dev(const float* d_in, const float* w_ohwi_host, const float* d_bias, float* d_out, int batch, int h, int w,
@@ -940,7 +955,9 @@ FH_API int fh_debug_streamk(int drop_publish, int timeout_ms);
  *           -> out = its tile width 96 / 64 / 32, or 0 = the layer stays with conv_igemm_kernel (1)
  *   what 2  conv_tall_kernel: in = the same 11, tile config 0..3 or -1 = automatic (12) -> out = tiles it takes, LDS image rows, LDS bytes (3)
  *   what 3  slabs per remainder tile: in = r0, r1, chunks per tile left to the helpers, q (4) -> out = min, max over r0 <= r < r1 (2)
- *   what 4  the workspace: in = nothing -> out = slab floats, counter words (2) */
+ *   what 4  the workspace: in = nothing -> out = slab floats, counter words (2)
+ *   what 5  the three-piece bf16 K loop of a direct convolution: in = 128-row tiles x column tiles of the x3 tile width, Kpad, Cout, CUs (4)
+ *           -> out = 1 if the launch runs it (conv_x3_pays), x3 tile width 128 / 64 or 0 = Cout has no such form (2) */
 FH_API int fh_debug_conv_plan(int what, const int* in, int n_in, long long* out, int n_out);
 /* Test hook of the multi-tile Winograd GEMM (winograd.hip wino_gemm_pers_kernel): launches with more tiles than resident workgroup
  * slots walk several tiles per workgroup; slots > 0 makes the launcher pretend the device has that many (rounded up to 8), so that small
