@@ -53,6 +53,7 @@ TRACK_LINK_MEMORY = 256                                        # FH_TRACK_LINK_M
 HIST_BINS = 2048                                               # FH_HIST_BINS
 TAG_ALL = 0xFFFFFFFF                                           # FH_TAG_ALL
 RANGE_MAX_CAP = 1024                                           # FH_RANGE_MAX_CAP
+TOPK_DEEP_MAX = 1024                                           # FH_TOPK_DEEP_MAX
 ROC_POINT_DTYPE = np.dtype([("threshold", "<f4"), ("bin", "<i4"), ("true_accepts", "<u8"), ("false_accepts", "<u8"), ("genuine", "<u8"),
                             ("impostor", "<u8")])              # fh_roc_point
 assert ROC_POINT_DTYPE.itemsize == 40
@@ -208,6 +209,9 @@ PROTOTYPES = {
     "fh_tracker_set_stream_masks": (_i, [_vp, _vp]),
     "fh_gallery_range_dev": (_i, [_vp, _vp, _vp, _i, _f, _i, _vp, _vp, _vp, _vp, _vp]),
     "fh_range_from_scores": (_i, [_vp, _ll, _ll, _vp, C.c_uint32, _f, _i, C.POINTER(_ll), _vp, _vp]),
+    "fh_gallery_topk_deep_dev": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),
+    "fh_topk_from_scores": (_i, [_vp, _ll, _ll, _vp, C.c_uint32, _i, _vp, _vp]),
+    "fh_debug_deep_blocks": (_i, [_vp, _ll, _vp, C.c_uint32, _i, _vp]),
     "fh_comm_unique_id": (_i, [_vp]),
     "fh_comm_create": (_vp, [_i, _i, _vp, _i]),
     "fh_comm_destroy": (None, [_vp]),

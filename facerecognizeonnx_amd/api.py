@@ -836,6 +836,31 @@ class Gallery:
         out = (counts[:nq].cpu().numpy(), sc[:nq].cpu().numpy(), ix[:nq].cpu().numpy())
         return out + (di[:nq].cpu().numpy(),) if ids else out
 
+    def topk_deep_dev(self, q_ptr: int, nq: int, k: int, scores_ptr: Optional[int] = None, idx_ptr: Optional[int] = None,
+                      ids_ptr: Optional[int] = None, masks_ptr: Optional[int] = None, stream: int = 0):
+        """Deep top-k (fh_gallery_topk_deep_dev): scores / idx / ids [nq][k] (device, each optional, not all three) = the best
+        min(k, eligible) rows of every query — admitted rows with masks (device uint32[nq]); a NaN or -inf score is never listed —
+        (score desc, global row asc), empty slots (-1.0, -1, -1).  1 <= k <= TOPK_DEEP_MAX, no threshold.  Scores are the fp32
+        scan's, bit for bit, in either scan mode.  ids needs a labelled gallery.  Asynchronous on `stream`."""
+        check(_lib.lib().fh_gallery_topk_deep_dev(self._h, q_ptr, masks_ptr, nq, k, scores_ptr, idx_ptr, ids_ptr, stream),
+              "fh_gallery_topk_deep_dev")
+
+    def topk_deep(self, queries, k: int, masks=None, ids: bool = False):
+        """(scores float32[nq, k], indices int32[nq, k][, ids int32[nq, k]]) of topk_deep_dev for host queries [nq, dim] (masks:
+        uint32[nq], optional) — a synchronous convenience that uploads, allocates and copies back."""
+        import torch
+        q = np.array(queries, np.float32, order="C").reshape(-1, self.dim)      # (a copy: torch takes no read-only array)
+        nq = q.shape[0]
+        qd = torch.from_numpy(q).cuda()
+        md = None if masks is None else torch.from_numpy(np.ascontiguousarray(np.asarray(masks).astype(np.uint32)).view(np.int32).reshape(nq)).cuda()
+        sc = torch.empty((max(nq, 1), k), dtype=torch.float32, device="cuda")
+        ix = torch.empty((max(nq, 1), k), dtype=torch.int32, device="cuda")
+        di = torch.empty((max(nq, 1), k), dtype=torch.int32, device="cuda") if ids else None
+        self.topk_deep_dev(qd.data_ptr(), nq, k, sc.data_ptr(), ix.data_ptr(), None if di is None else di.data_ptr(),
+                           None if md is None else md.data_ptr(), torch.cuda.current_stream().cuda_stream)
+        out = (sc[:nq].cpu().numpy(), ix[:nq].cpu().numpy())
+        return out + (di[:nq].cpu().numpy(),) if ids else out
+
     def tag_stats(self):
         """(tiles_scanned, tiles_skipped): the (workgroup, 128-row tile) visits the tagged scans multiplied / skipped since the last
         call (resets; waits for the handle's queued work)."""
@@ -985,6 +1010,25 @@ def range_from_scores(scores, threshold: float, cap: int = 64, index_base: int =
                                           int(mask) & 0xFFFFFFFF, float(np.float32(threshold)), cap, C.byref(count), out_s.ctypes.data,
                                           out_i.ctypes.data), "fh_range_from_scores")
     return int(count.value), out_s, out_i
+
+
+def topk_from_scores(scores, k: int, index_base: int = 0, tags=None, mask: int = _lib.TAG_ALL):
+    """(listed, scores float32[k], indices int32[k]) of fh_topk_from_scores — host only, the one definition of the deep top-k, for ONE
+    query's row of mapped scores: a row is eligible iff (tag & mask) != 0 (tags=None: every row carries TAG_ALL) and its score is
+    neither a NaN nor -inf; the lists hold the best min(k, eligible) rows (score desc, index_base + position asc) and (-1.0, -1)
+    behind them — the list part of range_from_scores(threshold=-inf, cap=k)."""
+    scores = np.ascontiguousarray(scores, np.float32).reshape(-1)
+    n = scores.size
+    if tags is not None:
+        tags = np.ascontiguousarray(np.asarray(tags).reshape(-1).astype(np.uint32))
+        if tags.size != n:
+            raise ValueError("topk_from_scores: need one tag per score")
+    k = int(k)
+    out_s, out_i = np.empty(max(k, 0), np.float32), np.empty(max(k, 0), np.int32)
+    listed = check(_lib.lib().fh_topk_from_scores(scores.ctypes.data if n else None, n, int(index_base),
+                                                  None if tags is None or n == 0 else tags.ctypes.data, int(mask) & 0xFFFFFFFF, k,
+                                                  out_s.ctypes.data, out_i.ctypes.data), "fh_topk_from_scores")
+    return int(listed), out_s, out_i
 
 
 def plan_describe(path: str, default_h: int, default_w: int) -> str:

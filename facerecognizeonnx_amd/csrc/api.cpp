@@ -10,6 +10,7 @@
 
 #include "../../include/facehip.h"
 #include "cluster_plan.h"
+#include "deep_plan.h"
 #include "range_plan.h"
 #include "roc_plan.h"
 #include "engine.h"
@@ -1514,6 +1515,46 @@ int fh_gallery_range_dev(fh_gallery* g, const float* d_queries, const uint32_t* 
         return FH_ERR_STATE;
     }
     return guarded([&] { g->g.range_dev(d_queries, d_masks, nq, threshold, cap, d_counts, d_scores, d_indices, d_ids, S(stream)); return nq; });
+}
+
+// ---- deep top-k: the rule and the block rule on the host (deep_plan.h), the same on the scan's accumulators (gallery_deep.hip)
+static_assert(FH_TOPK_DEEP_MAX == fh::kDeepMaxK && FH_TOPK_DEEP_MAX == fh::GAL_DEEP_MAX, "facehip.h and kernels.h mirror deep_plan.h");
+int fh_topk_from_scores(const float* scores, long long n, long long index_base, const uint32_t* tags, uint32_t mask, int k, float* out_scores,
+                        int* out_indices) {
+    int listed = -1;
+    const int rc = guarded([&] {                                   // (its scratch may run out of memory)
+        listed = fh::topk_from_scores(scores, n, index_base, tags, mask, k, out_scores, out_indices);
+        return 0;
+    });
+    if (rc < 0) return rc;
+    return listed < 0 ? arg_error("fh_topk_from_scores: bad argument (null scores, k outside 1..1024, index beyond 31 bits)") : listed;
+}
+int fh_debug_deep_blocks(const float* scores, long long n, const uint32_t* tags, uint32_t mask, int k, long long* out_blocks) {
+    if (!out_blocks) return arg_error("fh_debug_deep_blocks: null argument");
+    int chosen = -1;
+    const int rc = guarded([&] {
+        std::vector<long long> blocks;
+        chosen = fh::deep_chosen_blocks(scores, n, tags, mask, k, &blocks);
+        std::copy(blocks.begin(), blocks.end(), out_blocks);
+        return 0;
+    });
+    if (rc < 0) return rc;
+    return chosen < 0 ? arg_error("fh_debug_deep_blocks: bad argument (null scores, k outside 1..1024)") : chosen;
+}
+int fh_gallery_topk_deep_dev(fh_gallery* g, const float* d_queries, const uint32_t* d_masks, int nq, int k, float* d_scores, int* d_indices,
+                             int* d_ids, void* stream) {
+    if (!g) return arg_error("fh_gallery_topk_deep_dev: null handle");
+    if (nq < 0 || nq > 256) return arg_error("fh_gallery_topk_deep_dev: need 0 <= nq <= 256");
+    if (k < 1 || k > FH_TOPK_DEEP_MAX) return arg_error("fh_gallery_topk_deep_dev: need 1 <= k <= FH_TOPK_DEEP_MAX");
+    if (g->g.dim() % 64) return arg_error("fh_gallery_topk_deep_dev: the gallery's dim must be a multiple of 64");
+    if (!d_scores && !d_indices && !d_ids) return arg_error("fh_gallery_topk_deep_dev: all three list pointers are null");
+    if (nq == 0) return 0;
+    if (!d_queries) return arg_error("fh_gallery_topk_deep_dev: null argument");
+    if (d_ids && g->g.size() > 0 && !g->g.labelled()) {
+        g_err = "gallery: fh_gallery_topk_deep_dev with d_ids needs a labelled gallery (rows enrolled with ids, or fh_gallery_set_ids)";
+        return FH_ERR_STATE;
+    }
+    return guarded([&] { g->g.topk_deep_dev(d_queries, d_masks, nq, k, d_scores, d_indices, d_ids, S(stream)); return nq; });
 }
 
 int fh_debug_topk_merge_strided_dev(const float* ps, const int* pi, int nparts, int nq, int k, long long part_stride, float* scores, int* indices,

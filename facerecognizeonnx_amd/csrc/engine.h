@@ -413,6 +413,13 @@ class Gallery {
     // of that) lives in the handle and grows, synchronously, with the first call of a larger (Q, size).
     void range_dev(const float* q, const unsigned* masks, int Q, float thr, int cap, long long* counts, float* out_score, int* out_row,
                    int* out_id, hipStream_t s);
+    // Deep top-k (gallery_deep.hip; the rule: deep_plan.h): out_score / out_row / out_id [Q][k] — each may be null — = the best
+    // min(k, eligible) rows of every query (admitted rows only with masks; a NaN or -inf score is never listed), (score desc, global
+    // row asc), empty slots (-1, -1, -1); 1 <= k <= 1024.  Always the fp32 rows, whatever the scan mode; it touches neither the part /
+    // seed lists nor the F16_RERANK state.  out_id needs a labelled gallery unless empty.  Q and k are checked by the caller.
+    // Asynchronous; the scratch (block maxima, twice the size of range_dev's hit bitmap; the chosen blocks and their rows' scores, 132
+    // bytes per list entry) lives in the handle and grows, synchronously, with the first call of a larger (Q, size, k).
+    void topk_deep_dev(const float* q, const unsigned* masks, int Q, int k, float* out_score, int* out_row, int* out_id, hipStream_t s);
     // removes every row whose id is listed (stable compaction through a second buffer: transiently the surviving fp32 rows, ids and
     // fp16 rows exist twice, plus 4 bytes per survivor); synchronous; returns the number of rows removed
     long remove_ids(const int* ids_host, long n_ids);
@@ -484,6 +491,7 @@ class Gallery {
     DevBuf cl_deg_, cl_parent_, cl_best_;                        // cluster_dev: degree, union-find parent, best core neighbour per row
     DevBuf cl_hist_;                                             // pair_hist_dev: the histogram the workgroups flush into
     DevBuf rg_hits_, rg_units_;                                  // range_dev: hit bitmap [32-row block][query], hits per (8192 rows, query)
+    DevBuf dp_bmax_, dp_bmax_t_, dp_chosen_, dp_cand_;           // topk_deep_dev: best eligible score [32-row block][query] and [query][block]; chosen blocks [query][k]; their rows' scores [query][k][32]
     // F16_RERANK state: [max|g|, max|g^|, max|g - g^| (float bits), non-finite / > 65504 flag] on the device and its host copy,
     // per-call scratch, the certified / fallback counters
     bool f16_bad_ = false;

@@ -1,6 +1,6 @@
 // gallery_host.cpp — the host side of fh::Gallery (engine.h): the row store (one capacity, the per-row columns that share it), the
 // maintenance calls written on its three operations (reserve, append, compact), the two queries over the one fp32 scan sequence
-// (gallery_scan.h: launch_gallery_scan) and the F16_RERANK path (gallery_f16.hip), and the threshold search (gallery_range.hip).
+// (gallery_scan.h: launch_gallery_scan) and the F16_RERANK path (gallery_f16.hip), the threshold search (gallery_range.hip) and the deep top-k (gallery_deep.hip).
 #include "engine.h"
 
 #include "gallery_scan.h"
@@ -405,6 +405,23 @@ void Gallery::range_dev(const float* q, const unsigned* masks, int Q, float thr,
     rg_units_.ensure(gallery_range_units_bytes(n_, Q));
     launch_gallery_range(rows_.as<float>(), n_, dim_, qpack_.as<float>(), tags_.as<unsigned>(), masks, Q, base_, thr, cap,
                          rg_hits_.as<unsigned>(), rg_units_.as<int>(), out_id ? ids_.as<int>() : nullptr, counts, out_score, out_row, out_id, s);
+    FH_HIP(hipGetLastError());
+}
+
+// The deep top-k: the scan with the block maxima as its epilogue, then blocks, rows and lists (gallery_deep.hip) — on the fp32 rows
+// always, as the threshold search; its only scratch is its own.
+void Gallery::topk_deep_dev(const float* q, const unsigned* masks, int Q, int k, float* out_score, int* out_row, int* out_id, hipStream_t s) {
+    if (dim_ % 64) throw std::runtime_error("gallery: dim must be a multiple of 64");
+    if (out_id) need_labelled("fh_gallery_topk_deep_dev with d_ids");
+    if (masks && n_ > 0) need_tags();
+    pack_queries(q, Q, s);
+    dp_bmax_.ensure(gallery_deep_bmax_bytes(n_, Q));
+    dp_bmax_t_.ensure(gallery_deep_bmax_t_bytes(n_, Q));
+    dp_chosen_.ensure(gallery_deep_chosen_bytes(Q, k));
+    dp_cand_.ensure(gallery_deep_cand_bytes(Q, k));
+    launch_gallery_deep(rows_.as<float>(), n_, dim_, qpack_.as<float>(), tags_.as<unsigned>(), masks, Q, base_, k, dp_bmax_.as<float>(),
+                        dp_bmax_t_.as<float>(), dp_chosen_.as<int>(), dp_cand_.as<float>(), out_id ? ids_.as<int>() : nullptr, out_score,
+                        out_row, out_id, s);
     FH_HIP(hipGetLastError());
 }
 

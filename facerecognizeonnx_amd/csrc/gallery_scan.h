@@ -1,7 +1,8 @@
 // gallery_scan.h — the streaming 1:N scan of the gallery: ONE body, instantiated as gallery_topk_kernel (gallery.hip: fp32 rows, lists of
 // rows), gallery_topk_ids_kernel (gallery_ids.hip: fp32 rows, lists of identities), their tagged twins (gallery_tags.hip) and
 // gal16_scan_kernel (gallery_f16.hip: fp16 rows, 32-deep candidate lists) and gallery_range_kernel (gallery_range.hip: fp32 rows, no
-// lists at all — a bit per (row, query) whose score is above a threshold); with it the ranking predicate, the kernel arguments, the
+// lists at all — a bit per (row, query) whose score is above a threshold) and gallery_bmax_kernel (gallery_deep.hip: fp32 rows, no lists —
+// the best score per (32-row block, query)); with it the ranking predicate, the kernel arguments, the
 // two-pass launcher the top-k scans share, the one launcher of the four fp32 top-k scans and the re-score of single (row, query) pairs.
 // The multiply of one (128-row tile, 64-row tile) pair — THE K loop — is gal_tile_dot below, written once: this body calls it with the
 // query tile as B, cluster_pair_body (gallery_cluster.hip: DBSCAN's degree / link passes and the pair histogram) with gallery rows as B.
@@ -36,6 +37,9 @@
 //     every lane turns its 2 x 16 accumulators into hit bits ((acc + 1) / 2 > thr, row < G, tag & mask) and the wave stores one 32-bit
 //     word per (32-row block, query).  No LDS beyond the query chunks, no barrier beyond the K loop's, no atomics; masks are optional at
 //     run time (p.qmask), every tile is multiplied and a workgroup's tiles are the contiguous run.
+//   * DEEP (gallery_bmax_kernel, gallery_deep.hip): the twin of RANGE — the same K loop, then every lane reduces its 2 x 16 accumulators
+//     to the MAXIMUM score over its eligible rows (row < G, admitted, not a NaN, > -inf; -inf if none), takes the maximum with lane
+//     fr ^ 32 and the wave stores one float per (32-row block, query): the block maxima the deep top-k selects its blocks from.
 //
 // Round 3, measured and NOT kept (1 M x 512, Q = 64, k = 16; this kernel: 0.82 ms per call = seed pass 88 us + scan ~700 + two merges
 // 39 us each): a scan with the whole 64-query tile RESIDENT in LDS (128 KB, one 8-wave workgroup per CU, no per-chunk barrier, query
@@ -93,6 +97,8 @@ struct GalArgs {
     // RANGE (gallery_range.hip) — behind the TAGS fields in turn; it also reads tags / qmask (qmask null: every row admitted)
     float range_thr;          // row r is a hit of query q iff (acc + 1) / 2 > range_thr (and r < G, and admitted)
     unsigned* hits;           // [row_tiles * 4][tiles_n * 64]: bit b of word [m][q] = row 32 m + b is a hit of query q
+    // DEEP (gallery_deep.hip) — behind the RANGE fields in turn; it reads tags / qmask as RANGE does
+    float* bmax;              // [row_tiles * 4][tiles_n * 64]: the best eligible score of rows 32 m .. 32 m + 31 for query q, -inf if none
 };
 
 // ---- host side (gallery.hip); they sit here and not in kernels.h because they speak of GalArgs
@@ -262,10 +268,13 @@ __device__ __forceinline__ v16f gal_rescore32(const float* a_ptr, int a_step, co
 //
 // T: element type of rows and queries (float | _Float16); KD: list depth; KFIX: k is KD (else the runtime p.k <= KD).
 // RANGE: no lists — the epilogue is the hit bitmap (KD, KFIX, IDS and TAGS play no part; see the header).
-template <typename T, int KD, bool KFIX, bool IDS, bool TAGS = false, bool RANGE = false>
+// DEEP: no lists — the epilogue is the block maxima (as RANGE; never both).
+template <typename T, int KD, bool KFIX, bool IDS, bool TAGS = false, bool RANGE = false, bool DEEP = false>
 __device__ __forceinline__ void gallery_scan_body(const GalArgs& p) {
     constexpr bool F16 = std::is_same<T, _Float16>::value;
     static_assert(!RANGE || (!F16 && !IDS && !TAGS), "the threshold scan reads fp32 rows and takes its masks at run time");
+    static_assert(!DEEP || (!F16 && !IDS && !TAGS && !RANGE), "the block-maximum scan reads fp32 rows and takes its masks at run time");
+    constexpr bool LISTS = !RANGE && !DEEP;                   // the top-k scans: lists, queues, thresholds, seeds
     constexpr int BM = GAL_BM, BN = GAL_BN, TN = BN / 32;
     constexpr int EC = 16 / (int)sizeof(T), CD = 16 * EC;     // elements per 16-byte column, chunk depth (16 columns)
     __shared__ v4f ldsq[2][BN * 16];                          // query chunk [64 rows][CD k], 16-byte column XOR (row & 15)
@@ -288,7 +297,7 @@ __device__ __forceinline__ void gallery_scan_body(const GalArgs& p) {
     }
     const int tile_n = t % p.tiles_n, part = t / p.tiles_n;
     const int n0 = tile_n * BN;
-    if constexpr (!F16 && !RANGE) {                           // (the fp16 scan is never the compacted fall-back: no test, its scalar side stays lean)
+    if constexpr (!F16 && LISTS) {                            // (the fp16 scan is never the compacted fall-back: no test, its scalar side stays lean)
         if (p.qcount && n0 >= *p.qcount) return;              // (workgroup-uniform, before any barrier)
     }
     const int K = p.dim, chunks = K / CD, k = KFIX ? KD : p.k;
@@ -303,7 +312,7 @@ __device__ __forceinline__ void gallery_scan_body(const GalArgs& p) {
 #pragma unroll
         for (int i = 0; i < KD; ++i) ld[i] = -1;
     }
-    if (!RANGE && tid < BN) {
+    if (LISTS && tid < BN) {
         float ts = -INFINITY; int ti = INT_MAX;                   // (-inf, INT_MAX): below every real entry, whatever the rows' norms (compareFaces does not clamp, face_recognizer.cpp:320-334)
         if (p.seed_i && n0 + tid < p.Q) {
             const size_t o = (size_t)(n0 + tid) * k + (k - 1);
@@ -311,7 +320,7 @@ __device__ __forceinline__ void gallery_scan_body(const GalArgs& p) {
         }
         cnt[tid] = 0; tau_s[tid] = ts; tau_i[tid] = ti;
     }
-    if (!RANGE && tid == 0) overflow = 0;
+    if (LISTS && tid == 0) overflow = 0;
     unsigned U = 0;                                           // TAGS: OR of the tile's 64 masks (every wave forms it: no barrier needed)
     int n_scan = 0, n_skip = 0;
     if constexpr (TAGS) {
@@ -386,6 +395,36 @@ __device__ __forceinline__ void gallery_scan_body(const GalArgs& p) {
             }
             // word [32-row block of the gallery][query, padded to whole tiles]: every word of the bitmap is written by exactly one lane
             p.hits[((size_t)rt * 4 + wid) * ((size_t)p.tiles_n * BN) + n0 + lane] = fh2 ? word[1] : word[0];
+            continue;
+        }
+        // ---- block-maximum epilogue: the same lane pairs as the threshold epilogue — after one exchange per query block lane l owns the
+        // maximum of query n0 + l over the wave's 32 rows, and the wave stores 64 floats = 256 contiguous bytes of row [block] of bmax
+        if constexpr (DEEP) {
+            static_assert(TN == 2, "one query block per lane half");
+            unsigned tg[16];                               // the tags of the lane's 16 rows (rows behind G, and a call without masks: unused)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                const long row = rbase + gal_acc_row(e);
+                tg[e] = p.qmask && row < p.G ? p.tags[row] : 0xFFFFFFFFu;
+            }
+            float best[TN];
+#pragma unroll
+            for (int j = 0; j < TN; ++j) {
+                const int qn = n0 + j * 32 + fr;
+                const unsigned mq = qn >= p.Q ? 0u : p.qmask ? p.qmask[qn] : 0xFFFFFFFFu;     // (queries behind Q: no eligible row)
+                float m = -INFINITY;
+#pragma unroll
+                for (int e = 0; e < 16; ++e) {
+                    const long row = rbase + gal_acc_row(e);
+                    const float sc = gal_score(acc[j][e]);
+                    const bool ok = row < p.G && (tg[e] & mq) != 0 && sc > m;                 // (false for a NaN score, and for -inf)
+                    m = ok ? sc : m;
+                }
+                const float o = __shfl_xor(m, 32);
+                best[j] = o > m ? o : m;
+            }
+            // every word of bmax is written by exactly one lane
+            p.bmax[((size_t)rt * 4 + wid) * ((size_t)p.tiles_n * BN) + n0 + lane] = fh2 ? best[1] : best[0];
             continue;
         }
         // ---- top-k epilogue
@@ -480,7 +519,7 @@ __device__ __forceinline__ void gallery_scan_body(const GalArgs& p) {
             insert();
         }
     }
-    if (!RANGE && tid < BN && n0 + tid < p.Q) {
+    if (LISTS && tid < BN && n0 + tid < p.Q) {
         const size_t o = ((size_t)part * p.Q + n0 + tid) * k;
 #pragma unroll
         for (int pos = 0; pos < KD; ++pos)

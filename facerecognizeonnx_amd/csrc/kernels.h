@@ -437,6 +437,21 @@ void launch_gallery_range(const float* rows, long G, int dim, const float* qpack
                           long idx_base, float thr, int cap, unsigned* hits, int* unit_cnt, const int* ids, long long* counts, float* out_s,
                           int* out_i, int* out_d, hipStream_t s);
 
+// gallery_deep.hip — exact top-k of 1 <= k <= GAL_DEEP_MAX rows per query (fh_gallery_topk_deep_dev; the rule and the block rule:
+// deep_plan.h): the scan of gallery_scan.h with the maximum per (32-row block, query) as its epilogue, then per query the best k blocks
+// by that maximum, their rows re-scored from the fp32 rows and the best k of those.  qpacked, tags / masks, ids, out_* [Q][k] as for
+// launch_gallery_range; bmax / bmax_t (the maxima by block and by query), chosen (the chosen blocks [Q][k]) and cand (their rows' scores
+// [Q][k][32]): scratch of gallery_deep_*_bytes, each written before it is read: never cleared.  G == 0: empty lists.  Q <= 0 launches
+// nothing.
+constexpr int GAL_DEEP_MAX = 1024;
+size_t gallery_deep_bmax_bytes(long G, int Q);
+size_t gallery_deep_bmax_t_bytes(long G, int Q);
+size_t gallery_deep_chosen_bytes(int Q, int k);
+size_t gallery_deep_cand_bytes(int Q, int k);
+void launch_gallery_deep(const float* rows, long G, int dim, const float* qpacked, const unsigned* tags, const unsigned* masks, int Q,
+                         long idx_base, int k, float* bmax, float* bmax_t, int* chosen, float* cand, const int* ids, float* out_s,
+                         int* out_i, int* out_d, hipStream_t s);
+
 // detect -> embed hand-off: first min(count,F) faces per frame, densely packed (n <= 4096 frames)
 void launch_select_faces(const FaceRec* det, const int* counts, int n, int per_frame, int F, FaceRec* faces, int* frame_of,
                          int* total, hipStream_t s);

@@ -818,6 +818,47 @@ FH_API int fh_gallery_range_dev(fh_gallery* g, const float* d_queries, const uin
 FH_API int fh_range_from_scores(const float* scores, long long n, long long index_base, const uint32_t* tags /* or NULL */, uint32_t mask,
                                 float threshold, int cap, long long* count, float* out_scores, int* out_indices);
 
+/* ---- deep top-k: the best k rows of every query for 16 < k <= 1024 too, with NO threshold asked of the caller — the best 50 for a human
+ * reviewer, the best 200 to re-rank with another model, the best 1000 for an audit.  (fh_gallery_topk_dev stops at 16, the depth of the
+ * scan's register lists; fh_gallery_range_dev goes deeper but needs a threshold the caller does not know in advance.)
+ *   eligible  row r is eligible for query q iff it is ADMITTED (d_masks == NULL, or (tag[r] & mask[q]) != 0; a gallery whose tags were
+ *             never set carries FH_TAG_ALL), its mapped score is not a NaN, and its mapped score is > -inf.
+ *   lists     row q of d_scores / d_indices / d_ids [nq][k] holds the best min(k, eligible) rows ranked as everywhere (score descending,
+ *             then global row index ascending); the slots behind them carry (-1.0f, -1, -1); nothing outside [nq][k] is written.  This
+ *             is by definition the list part of fh_gallery_range_dev(threshold = -inf, cap = k).  Indices are global (index_base +
+ *             position).  d_ids = each listed row's identity id and needs a labelled gallery (FH_ERR_STATE otherwise, unless the gallery
+ *             is empty).  Any subset of the three may be NULL, not all of them.
+ *   scores    the fp32 scan's, bit for bit, whichever scan mode the gallery is in (the call always reads the fp32 rows and leaves
+ *             fh_gallery_scan_stats and fh_gallery_tag_stats alone).  For finite rows and queries and k <= 16 the lists are bit for bit
+ *             those of fh_gallery_topk_dev (with masks: of fh_gallery_topk_tagged_dev).
+ *   limits    nq <= 256, dim % 64 == 0, 1 <= k <= FH_TOPK_DEEP_MAX.  FH_ERR_ARG before anything is launched for a NULL handle or
+ *             queries, all three list pointers NULL, a bad k, nq outside 0..256 or such a dim; nq == 0 returns 0.  An empty gallery gives
+ *             empty lists.  Returns nq.
+ *   cost      one scan of the gallery — the block-maximum scan: the best eligible score of every (32-row block, query) — then per query
+ *             the best k blocks by that maximum and the re-score of their rows: at most 32 k rows per query, WHATEVER the data (the
+ *             exact top-k lies in those blocks: DESIGN.md 3.4c has the proof).  That tail grows with k — 32 k * dim * 4 bytes of row
+ *             reads per query, 64 MB at k = 1024 and dim 512, and 32 k MFMAs per 64 of dim — and dominates the call at k = 1024
+ *             (measured at 1 M x 512, nq = 64: 0.76 ms at k = 16, 0.93 ms at k = 128, 2.3 ms at k = 1024; profiles/gallery_deep.md).
+ *   execution asynchronous on `stream`; two calls with the same inputs produce identical bytes (no atomics, nothing timing-dependent).
+ *             Scratch lives in the handle and grows, synchronously, on the first call of a larger (nq, rows, k): two floats per (32-row
+ *             block, query of a whole 64-query tile) — twice the range call's hit bitmap — and 132 bytes per list entry (nq * k).
+ *   sharding  there is no sharded entry point: a shard's call already returns global indices; fh_topk_merge_dev merges lists of
+ *             k <= 16 only, so deeper per-shard lists are merged by the caller (concatenate, sort by (score desc, index asc), cut).
+ *   out of scope   deep lists of IDENTITIES (one entry per id), tile skip for masks, k above 1024.
+ *   topk_from_scores   host only, no GPU, and the one definition of the rule: the same answer for ONE query from its row of n
+ *             precomputed mapped scores (global index = index_base + position).  tags == NULL: every row carries FH_TAG_ALL.
+ *             out_scores / out_indices [k] (either may be NULL) as above.  Returns the number of entries listed; FH_ERR_ARG — nothing
+ *             written — for n < 0, NULL scores with n > 0, a bad k or an index beyond 31 bits. */
+#define FH_TOPK_DEEP_MAX 1024
+FH_API int fh_gallery_topk_deep_dev(fh_gallery* g, const float* d_queries, const uint32_t* d_masks /* [nq] or NULL */, int nq, int k,
+                                    float* d_scores /* [nq][k] or NULL */, int* d_indices /* [nq][k] or NULL */,
+                                    int* d_ids /* [nq][k] or NULL */, void* stream);
+FH_API int fh_topk_from_scores(const float* scores, long long n, long long index_base, const uint32_t* tags /* or NULL */,
+                               uint32_t mask, int k, float* out_scores, int* out_indices);
+/* test hook: the chosen blocks of deep_plan.h's block rule for one query's scores, best first, into out_blocks [k]; returns their number */
+FH_API int fh_debug_deep_blocks(const float* scores, long long n, const uint32_t* tags /* or NULL */, uint32_t mask, int k,
+                                long long* out_blocks);
+
 /* ---- measurement hooks (bench.py): per-launch HIP-event timing of the network kernels.
  * Tags 0..3 = conv_igemm tile configs (128x128, 256x64, 128x32, 64x64), 4 = depthwise / depthwise+pointwise,
  * 5 = other graph ops, 6 = conv stream-K fix-up, 7 = Winograd GEMM (its FLOPs = executed; bytes slot = the layer's
