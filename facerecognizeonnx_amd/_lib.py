@@ -40,6 +40,24 @@ class FhView(C.Structure):
     _fields_ = [("x", C.c_int32), ("y", C.c_int32), ("w", C.c_int32), ("h", C.c_int32), ("edges", C.c_int32)]
 
 
+class FhJpegComp(C.Structure):
+    """fh_jpeg_comp: one component of an fh_jpeg_desc.  160 bytes."""
+    _fields_ = [("h", C.c_int32), ("v", C.c_int32), ("wblocks", C.c_int32), ("hblocks", C.c_int32), ("dw", C.c_int32), ("dh", C.c_int32),
+                ("coef_off", C.c_int64), ("quant", C.c_uint16 * 64)]
+
+
+class FhJpegDesc(C.Structure):
+    """fh_jpeg_desc: what JPEG reconstruction needs besides the coefficients (fh_jpeg_header / fh_jpeg_entropy fill it).  528 bytes."""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("rows", C.c_int32), ("cols", C.c_int32), ("ncomp", C.c_int32),
+                ("hmax", C.c_int32), ("vmax", C.c_int32), ("color", C.c_int32), ("orientation", C.c_int32), ("reserved", C.c_int32),
+                ("coef_count", C.c_int64), ("comp", FhJpegComp * 3)]
+
+
+class FhBlob(C.Structure):
+    """fh_blob: the bytes of one file.  16 bytes."""
+    _fields_ = [("bytes", C.c_void_p), ("n", C.c_size_t)]
+
+
 TRACK_DTYPE = np.dtype([(k, "<i4") for k in ("id", "x", "y", "w", "h", "last_seen", "last_embed", "hits")])
 assert TRACK_DTYPE.itemsize == 32
 TRACK_MAX = 64                                                 # FH_TRACK_MAX
@@ -231,6 +249,15 @@ PROTOTYPES = {
     "fh_imread": (_i, [C.c_char_p, C.POINTER(_vp), C.POINTER(_i), C.POINTER(_i)]),
     "fh_image_decode": (_i, [_vp, C.c_size_t, C.POINTER(_vp), C.POINTER(_i), C.POINTER(_i)]),
     "fh_image_free": (None, [_vp]),
+    "fh_jpeg_header": (_i, [_vp, C.c_size_t, _vp]),
+    "fh_jpeg_entropy": (_i, [_vp, C.c_size_t, _vp, _vp, C.c_size_t]),
+    "fh_jpeg_reconstruct": (_i, [_vp, _vp, _vp, _i]),
+    "fh_jpeg_desc_check": (_i, [_vp]),
+    "fh_jpegdec_create": (_vp, []),
+    "fh_jpegdec_destroy": (None, [_vp]),
+    "fh_jpeg_reconstruct_batch_dev": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp]),
+    "fh_jpeg_decode_batch": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp]),
+    "fh_pipeline_run_files": (_i, [_vp, _vp, _vp, _vp, _i, _i, _f, _f, _i, _vp, _vp, _vp, _i, _vp]),
     "fh_det_set_winograd": (_i, [_vp, _i]),
     "fh_rec_set_winograd": (_i, [_vp, _i]),
     "fh_rec_set_wino_fusion": (_i, [_vp, _i]),

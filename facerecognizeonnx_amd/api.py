@@ -568,6 +568,92 @@ def pipeline_images(det: FaceDetector, rec: FaceRecognizer, images, faces_per_fr
     return faces[:m].copy(), frame_of[:m].copy(), emb[:m].copy()
 
 
+def _blobs(files):
+    """(fh_blob array, the buffers it points into) from a list of paths or bytes-like objects; an unreadable path is an empty blob."""
+    keep = []
+    arr = (_lib.FhBlob * max(len(files), 1))()
+    for i, f in enumerate(files):
+        if isinstance(f, (bytes, bytearray, memoryview)):
+            data = bytes(f)
+        else:
+            try:
+                with open(f, "rb") as fp:
+                    data = fp.read()
+            except OSError:
+                data = b""
+        buf = C.create_string_buffer(data, len(data)) if data else None
+        keep.append(buf)
+        arr[i].bytes, arr[i].n = (C.addressof(buf) if buf is not None else None), len(data)
+    return arr, keep
+
+
+class JpegDecoder:
+    """fh_jpegdec: JPEG files -> BGR pictures with the entropy decoding on host threads and everything behind it (IDCT, up-sampling,
+    colour conversion, EXIF orientation) on the GPU; the pixels are fh_image_decode's, bit for bit."""
+
+    def __init__(self):
+        self.handle = _lib.lib().fh_jpegdec_create()
+        if not self.handle:
+            raise _lib.FaceHipError(f"fh_jpegdec_create failed: {_lib.last_error()}")
+
+    def __del__(self):
+        h, self.handle = getattr(self, "handle", None), None
+        if h:
+            _lib.lib().fh_jpegdec_destroy(h)
+
+    def decode_dev(self, files, threads: int = 0, stream: int = 0):
+        """fh_jpeg_decode_batch: files = list of paths or bytes.  Returns (fh_frame array of DEVICE images, valid until the next call on
+        this decoder; status int32[n]: 0 JPEG on the device, 1 another format decoded on the host, < 0 not decodable = empty frame)."""
+        files = list(files)
+        n = len(files)
+        blobs, keep = _blobs(files)
+        frames = (_lib.FhFrame * max(n, 1))()
+        frames._n = n
+        status = np.full(max(n, 1), -1, np.int32)
+        if n:
+            check(_lib.lib().fh_jpeg_decode_batch(self.handle, blobs, n, int(threads), frames, status.ctypes.data, stream), "fh_jpeg_decode_batch")
+        del keep
+        return frames, status[:n]
+
+    def decode(self, files, threads: int = 0):
+        """decode_dev, then the pictures copied back: (list of uint8[rows, cols, 3] BGR arrays, None for a file that cannot be decoded;
+        status as decode_dev)."""
+        frames, status = self.decode_dev(files, threads)
+        out = []
+        for i in range(len(status)):
+            f = frames[i]
+            if not f.bgr:
+                out.append(None)
+                continue
+            a = np.empty((f.rows, f.cols, 3), np.uint8)
+            check(_lib.lib().fh_memcpy_d2h(a.ctypes.data, f.bgr, a.nbytes), "fh_memcpy_d2h")   # (synchronous: behind the decode on stream 0)
+            out.append(a)
+        return out, status
+
+
+def pipeline_files(det: FaceDetector, rec: FaceRecognizer, files, faces_per_frame: int = 1, scoreThreshold: float = 0.5,
+                   nmsThreshold: float = 0.4, cap: Optional[int] = None, threads: int = 0, decoder: Optional[JpegDecoder] = None):
+    """pipeline_images from FILES (paths or bytes): JPEGs are entropy-decoded on `threads` host threads and reconstructed on the GPU
+    (fh_pipeline_run_files), other formats decoded on the host.  Returns (faces, frame_of, emb, status) — the first three exactly as
+    imread per file + pipeline_images gives them; status[i] 0 / 1 / < 0 as JpegDecoder.decode_dev."""
+    files = list(files)
+    n = len(files)
+    dim = rec.feature_dim()
+    if n == 0:
+        return np.zeros(0, FACE_DTYPE), np.zeros(0, np.int32), np.zeros((0, dim), np.float32), np.zeros(0, np.int32)
+    dec = decoder if decoder is not None else JpegDecoder()
+    blobs, keep = _blobs(files)
+    room = n * faces_per_frame if cap is None else max(int(cap), 0)
+    faces = np.zeros(max(room, 1), FACE_DTYPE); frame_of = np.zeros(max(room, 1), np.int32); emb = np.zeros((max(room, 1), dim), np.float32)
+    status = np.full(n, -1, np.int32)
+    total = check(_lib.lib().fh_pipeline_run_files(det.handle, rec.handle, dec.handle, blobs, n, int(threads), scoreThreshold, nmsThreshold,
+                                                   faces_per_frame, faces.ctypes.data, frame_of.ctypes.data, emb.ctypes.data, room,
+                                                   status.ctypes.data), "fh_pipeline_run_files")
+    del keep
+    m = min(total, room)
+    return faces[:m].copy(), frame_of[:m].copy(), emb[:m].copy(), status
+
+
 def pipeline_submit_dev(det: FaceDetector, rec: FaceRecognizer, frames_ptr: int, n: int, rows: int, cols: int,
                         faces_per_frame: int, faces_ptr: int, frame_of_ptr: int, emb_ptr: int, total_ptr: int,
                         stream_det: int, stream_rec: int, scoreThreshold: float = 0.5, nmsThreshold: float = 0.4) -> int:

@@ -1,7 +1,7 @@
 """Text-mode counterpart of the reference's demo executable (reference src/main.cpp:264-319):
 
     python -m facerecognizeonnx_amd.cli detect  <image>            [--det det.onnx] [--tile N --overlap M [--border B]]
-    python -m facerecognizeonnx_amd.cli compare <image1> <image2>  [--det det.onnx] [--rec rec.onnx]
+    python -m facerecognizeonnx_amd.cli compare <image1> <image2>  [--det det.onnx] [--rec rec.onnx] [--device-jpeg]
     python -m facerecognizeonnx_amd.cli simple  <image1> <image2>  [--rec rec.onnx]
 
 Same flows as testDetection / testRecognition / testRecognitionSimple (main.cpp:39-199) — detect, take
@@ -9,6 +9,8 @@ faces[0] of each image, extractFeature, compareFaces, threshold 0.6 — but boxe
 are printed instead of drawn (no GUI, no webcam).  Images are read by the library's own cv::imread replacement
 (fh_imread: JPEG / PNG / BMP / PPM -> BGR u8) or from `.npy` arrays of shape [rows, cols, 3] (BGR u8).
 `detect --tile N` runs the tiled detection of large frames (whole frame + overlapping N x N tiles, one merged NMS; facehip.h).
+`compare --device-jpeg` reads both files through fh_pipeline_run_files: JPEGs are entropy-decoded on host threads and reconstructed on the
+GPU (the same pixels), then detected and embedded in one call; without the flag nothing changes.
 Model paths default to the reference's (models/det_500m.onnx, models/w600k_r50.onnx, main.cpp:269-270).
 """
 from __future__ import annotations
@@ -28,6 +30,29 @@ def imread(path: str):
     return api.imread(path)
 
 
+def compare_files(det, rec, a) -> int:
+    """compare (main.cpp:67-134) with the files decoded, detected and embedded by one fh_pipeline_run_files call: faces[0] of each."""
+    if len(a.images) < 2:
+        print("need two images", file=sys.stderr)
+        return -1
+    faces, frame_of, emb, status = api.pipeline_files(det, rec, a.images[:2], faces_per_frame=1, scoreThreshold=a.score, nmsThreshold=a.nms)
+    for p, st in zip(a.images, status):
+        if st < 0:
+            print(f"Cannot read image: {p}", file=sys.stderr)                   # main.cpp:43-46
+            return -1
+    n1, n2 = int(np.count_nonzero(frame_of == 0)), int(np.count_nonzero(frame_of == 1))
+    print(f"Image 1: {n1} faces, Image 2: {n2} faces (the first of each)")
+    if not n1 or not n2:
+        print("No face detected in one of the images")
+        return -1
+    e1, e2 = emb[int(np.flatnonzero(frame_of == 0)[0])], emb[int(np.flatnonzero(frame_of == 1)[0])]
+    print(f"Feature dimension: {e1.size}")
+    sim = rec.compareFaces(e1, e2)
+    print(f"Similarity: {sim:.6f}")
+    print("Same person" if sim > 0.6 else "Different person")                  # main.cpp:118
+    return 0
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(prog="facerecognizeonnx_amd.cli")
     ap.add_argument("mode", choices=["detect", "compare", "simple"])
@@ -39,6 +64,7 @@ def main(argv=None) -> int:
     ap.add_argument("--tile", type=int, default=0, help="detect: tile side in pixels (0 = plain detection)")
     ap.add_argument("--overlap", type=int, default=0, help="detect --tile: overlap of neighbouring tiles in pixels")
     ap.add_argument("--border", type=int, default=2, help="detect --tile: drop boxes within this many pixels of an interior tile edge (< 0: off)")
+    ap.add_argument("--device-jpeg", action="store_true", help="compare: decode the files through fh_pipeline_run_files (JPEG reconstruction on the GPU)")
     a = ap.parse_args(argv)
     det, rec = FaceDetector(), FaceRecognizer()
     if a.mode != "simple" and not det.loadModel(a.det):
@@ -47,6 +73,11 @@ def main(argv=None) -> int:
     if a.mode != "detect" and not rec.loadModel(a.rec):
         print("Failed to load face recognizer model", file=sys.stderr)         # main.cpp:280-284
         return -1
+    if a.device_jpeg:
+        if a.mode != "compare" or any(p.endswith(".npy") for p in a.images):
+            print("--device-jpeg applies to compare on image files", file=sys.stderr)
+            return -1
+        return compare_files(det, rec, a)
     imgs = [imread(p) for p in a.images]
     for p, im in zip(a.images, imgs):
         if im is None:

@@ -1,11 +1,13 @@
 // api.cpp — the extern "C" boundary declared in include/facehip.h.
 #include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <cstddef>
 #include <cstdio>
 #include <cstring>
 #include <memory>
 #include <string>
+#include <thread>
 #include <vector>
 
 #include "../../include/facehip.h"
@@ -15,6 +17,7 @@
 #include "roc_plan.h"
 #include "engine.h"
 #include "group_ids.h"
+#include "jpeg_dev.h"
 #include "track_plan.h"
 
 static_assert(sizeof(fh_face) == 60 && sizeof(fh::FaceRec) == 60, "FaceBox mirror must stay 60 bytes");
@@ -847,6 +850,168 @@ int fh_pipeline_run_images(fh_det* d, fh_rec* r, const fh_frame* imgs, int n, fl
         }
         FH_HIP(hipMemcpyAsync(d->arena.p, h, bytes, hipMemcpyHostToDevice, s));
         const int total = pipeline_ragged(d, r, dev_frames.data(), n, score_thr, nms_thr, F, d->i_faces.as<fh_face>(), d->i_fo.as<int>(),
+                                          d->i_emb.as<float>(), s);
+        FH_HIP(hipStreamSynchronize(s));
+        const int m = total < cap ? total : cap;
+        if (m > 0) {
+            if (faces) FH_HIP(hipMemcpy(faces, d->i_faces.p, (size_t)m * sizeof(fh_face), hipMemcpyDeviceToHost));
+            if (frame_of) FH_HIP(hipMemcpy(frame_of, d->i_fo.p, (size_t)m * sizeof(int), hipMemcpyDeviceToHost));
+            if (emb) FH_HIP(hipMemcpy(emb, d->i_emb.p, (size_t)m * dim * sizeof(float), hipMemcpyDeviceToHost));
+        }
+        return total;
+    });
+}
+
+// ---------------------------------------------------------------------------------- JPEG: host entropy decode, device reconstruction
+struct fh_jpegdec {
+    fh::JpegDev dev;
+    PinnedBuf h_arena;                   // fh_jpeg_decode_batch: [coefficients of every JPEG | pixels of every host-decoded file]
+    fh::DevBuf d_arena, d_pix;           // its device copy / the reconstructed pictures, packed row by row
+    hipEvent_t ev_copy = nullptr;        // behind the copy out of h_arena: the next call rewrites the arena only after it
+    bool copy_pending = false;
+    ~fh_jpegdec() { if (ev_copy) { if (copy_pending) (void)hipEventSynchronize(ev_copy); (void)hipEventDestroy(ev_copy); } }
+};
+namespace {
+// fn(i) for every i in [0, n) on `threads` host threads (the caller's included), one index per task.  fn must not throw.
+extern "C++" template <class F>
+void for_each_file(int n, int threads, F&& fn) {
+    if (threads <= 1) { for (int i = 0; i < n; ++i) fn(i); return; }
+    std::atomic<int> next{0};
+    auto work = [&] { for (int i; (i = next.fetch_add(1)) < n;) fn(i); };
+    std::vector<std::thread> pool;
+    try {
+        for (int t = 1; t < threads; ++t) pool.emplace_back(work);
+    } catch (...) {                                                           // no more threads to be had: the ones that started finish the job
+    }
+    work();
+    for (std::thread& t : pool) t.join();
+}
+// null, or why fh_jpeg_reconstruct_batch_dev refuses the call (fh_jpeg_desc_check's complaint is already in g_err then: "")
+const char* bad_jpeg_batch(const fh_jpeg_desc* descs, int n, const int16_t* d_coef, const long long* coef_base, const fh_frame* out) {
+    if (!descs || !d_coef || !coef_base || !out) return "null argument";
+    if (n <= 0 || n > 4096) return "need 1 <= n <= 4096 images";
+    if (reinterpret_cast<uintptr_t>(d_coef) & 1) return "d_coef must be 2-byte aligned";
+    for (int i = 0; i < n; ++i) {
+        if (!out[i].bgr) continue;
+        if (fh_jpeg_desc_check(&descs[i]) != 0) return "";
+        if (coef_base[i] < 0) return "a negative coef_base";
+        if (out[i].rows != descs[i].rows || out[i].cols != descs[i].cols) return "an output frame's rows / cols differ from its descriptor's";
+        if ((long long)out[i].step < (long long)out[i].cols * 3) return "an output frame's step is smaller than cols * 3";
+    }
+    return nullptr;
+}
+// fh_jpeg_decode_batch's body (arguments checked): returns the number of decoded images; status may be null
+int jpeg_decode_batch(fh_jpegdec* dec, const fh_blob* files, int n, int threads, fh_frame* frames_out, int* status, hipStream_t s) {
+    threads = threads <= 0 ? std::min(16, n) : std::min(threads, 16);
+    struct File { int kind = -1; fh_jpeg_desc desc; size_t coef_off = 0, px_off = 0; unsigned char* px = nullptr; int rows = 0, cols = 0; };
+    std::vector<File> f((size_t)n);                                           // kind: 0 JPEG, 1 decoded on the host, -1 not decodable
+    bool any_other = false;
+    for (int i = 0; i < n; ++i) {
+        const fh_blob& b = files[i];
+        if (!b.bytes || b.n == 0) continue;
+        if (b.n >= 3 && b.bytes[0] == 0xFF && b.bytes[1] == 0xD8) { if (fh_jpeg_header(b.bytes, b.n, &f[(size_t)i].desc) == 0) f[(size_t)i].kind = 0; }
+        else { f[(size_t)i].kind = 1; any_other = true; }
+    }
+    if (any_other)                                                            // their sizes are known only once they are decoded
+        for_each_file(n, threads, [&](int i) {
+            File& x = f[(size_t)i];
+            if (x.kind == 1 && fh_image_decode(files[i].bytes, files[i].n, &x.px, &x.rows, &x.cols) != 0) x.kind = -1;
+        });
+    size_t coef_elems = 0, host_px = 0, dev_px = 0;
+    for (File& x : f) {
+        if (x.kind == 0) { x.coef_off = coef_elems; coef_elems += ((size_t)x.desc.coef_count + 63) & ~(size_t)63; dev_px += (size_t)x.desc.rows * x.desc.cols * 3; }
+        if (x.kind == 1) { x.px_off = host_px; host_px += (size_t)x.rows * x.cols * 3; }
+    }
+    const size_t coef_bytes = coef_elems * sizeof(int16_t), arena_bytes = coef_bytes + host_px;
+    if (dec->copy_pending) { FH_HIP(hipEventSynchronize(dec->ev_copy)); dec->copy_pending = false; }
+    if (arena_bytes) { dec->h_arena.ensure(arena_bytes); dec->d_arena.ensure(arena_bytes); }
+    if (dev_px) dec->d_pix.ensure(dev_px);
+    uint8_t* const h = static_cast<uint8_t*>(dec->h_arena.p);
+    for_each_file(n, threads, [&](int i) {
+        File& x = f[(size_t)i];
+        if (x.kind == 0) {
+            const size_t cap = (size_t)x.desc.coef_count;
+            if (fh_jpeg_entropy(files[i].bytes, files[i].n, &x.desc, reinterpret_cast<int16_t*>(h) + x.coef_off, cap) != 0) x.kind = -1;
+        } else if (x.kind == 1) {
+            memcpy(h + coef_bytes + x.px_off, x.px, (size_t)x.rows * x.cols * 3);
+            fh_image_free(x.px);
+            x.px = nullptr;
+        }
+    });
+    std::vector<fh_jpeg_desc> descs;
+    std::vector<long long> base;
+    std::vector<fh_frame> out;
+    size_t px_off = 0;
+    int decoded = 0;
+    for (int i = 0; i < n; ++i) {
+        const File& x = f[(size_t)i];
+        fh_frame& o = frames_out[i];
+        o = fh_frame{nullptr, 0, 0, 0};
+        if (status) status[i] = x.kind;
+        if (x.kind == 0) {
+            o = fh_frame{dec->d_pix.as<uint8_t>() + px_off, x.desc.rows, x.desc.cols, x.desc.cols * 3};
+            px_off += (size_t)x.desc.rows * x.desc.cols * 3;
+            descs.push_back(x.desc); base.push_back((long long)x.coef_off); out.push_back(o);
+        } else if (x.kind == 1) {
+            o = fh_frame{dec->d_arena.as<uint8_t>() + coef_bytes + x.px_off, x.rows, x.cols, x.cols * 3};
+        }
+        decoded += x.kind >= 0;
+    }
+    if (decoded == 0) return 0;
+    if (!dec->ev_copy) FH_HIP(hipEventCreateWithFlags(&dec->ev_copy, hipEventDisableTiming));
+    FH_HIP(hipMemcpyAsync(dec->d_arena.p, h, arena_bytes, hipMemcpyHostToDevice, s));
+    FH_HIP(hipEventRecord(dec->ev_copy, s));
+    dec->copy_pending = true;
+    if (!descs.empty()) {
+        if (const char* bad = bad_jpeg_batch(descs.data(), (int)descs.size(), dec->d_arena.as<int16_t>(), base.data(), out.data()))
+            throw std::runtime_error(std::string("fh_jpeg_decode_batch: ") + (*bad ? bad : g_err.c_str()));
+        dec->dev.reconstruct(descs.data(), (int)descs.size(), dec->d_arena.as<int16_t>(), base.data(), FI(out.data()), s);
+    }
+    return decoded;
+}
+}  // namespace
+
+fh_jpegdec* fh_jpegdec_create(void) {
+    fh_jpegdec* h = nullptr;
+    const int rc = guarded([&] { h = new fh_jpegdec(); return 0; });
+    return rc == 0 ? h : nullptr;
+}
+void fh_jpegdec_destroy(fh_jpegdec* dec) { delete dec; }
+
+int fh_jpeg_reconstruct_batch_dev(fh_jpegdec* dec, const fh_jpeg_desc* descs, int n, const int16_t* d_coef, const long long* coef_base,
+                                  const fh_frame* out_frames, void* stream) {
+    if (!dec) return arg_error("fh_jpeg_reconstruct_batch_dev: null handle");
+    if (const char* bad = bad_jpeg_batch(descs, n, d_coef, coef_base, out_frames)) {
+        if (*bad) g_err = std::string("fh_jpeg_reconstruct_batch_dev: ") + bad;
+        return FH_ERR_ARG;
+    }
+    return guarded([&] { dec->dev.reconstruct(descs, n, d_coef, coef_base, FI(out_frames), S(stream)); return n; });
+}
+
+int fh_jpeg_decode_batch(fh_jpegdec* dec, const fh_blob* files, int n, int threads, fh_frame* frames_out, int* status, void* stream) {
+    if (!dec || !files || !frames_out) return arg_error("fh_jpeg_decode_batch: null argument");
+    if (n <= 0 || n > 4096) return arg_error("fh_jpeg_decode_batch: need 1 <= n <= 4096 files");
+    return guarded([&] { return jpeg_decode_batch(dec, files, n, threads, frames_out, status, S(stream)); });
+}
+
+// fh_pipeline_run_images from file bytes: the decode above, then the ragged pipeline on the same stream.
+int fh_pipeline_run_files(fh_det* d, fh_rec* r, fh_jpegdec* dec, const fh_blob* files, int n, int threads, float score_thr, float nms_thr, int F,
+                          fh_face* faces, int* frame_of, float* emb, int cap, int* status) {
+    if (!d || !r || !dec) return arg_error("fh_pipeline_run_files: null handle");
+    if (!files) return arg_error("fh_pipeline_run_files: null files");
+    if (n <= 0 || n > 4096) return arg_error("fh_pipeline_run_files: need 1 <= n <= 4096 files");
+    if (F <= 0 || cap < 0) return arg_error("fh_pipeline_run_files: bad size");
+    Owns owns(&d->det.net(), &r->rec.net());
+    return guarded([&] {
+        hipStream_t s = d->cs.get();
+        FH_HIP(hipStreamSynchronize(s));
+        std::vector<fh_frame> frames((size_t)n);
+        if (jpeg_decode_batch(dec, files, n, threads, frames.data(), status, s) == 0) return 0;   // only empty images: no faces
+        const int dim = r->rec.dim();
+        d->i_faces.ensure((size_t)n * F * sizeof(fh_face));
+        d->i_fo.ensure((size_t)n * F * sizeof(int));
+        d->i_emb.ensure((size_t)n * F * dim * sizeof(float));
+        const int total = pipeline_ragged(d, r, frames.data(), n, score_thr, nms_thr, F, d->i_faces.as<fh_face>(), d->i_fo.as<int>(),
                                           d->i_emb.as<float>(), s);
         FH_HIP(hipStreamSynchronize(s));
         const int m = total < cap ? total : cap;

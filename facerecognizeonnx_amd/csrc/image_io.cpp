@@ -12,6 +12,11 @@
 // sampling factors libjpeg up-samples with h2v1 / h2v2 / h1v2 "fancy" or integer replication, restart
 // intervals), PNG (all colour types, 1..16 bit, Adam7; inflate from zlib), BMP (24/32-bit BI_RGB),
 // binary PPM / PGM.  Host code: runs on the CPU exactly as the reference's imread does.
+//
+// The JPEG decoder comes in two halves (include/facehip.h, "JPEG in two halves"): the parse up to dense int16 coefficient planes
+// (fh_jpeg_header / fh_jpeg_entropy, struct Jpeg) and the reconstruction from them (fh_jpeg_reconstruct, struct Recon), which
+// csrc/jpeg_dev.hip restates for the device and is held to, bit for bit.  fh_image_decode of a JPEG is the first followed by the second.
+// This file stays plain C++: no HIP headers, no threads (tests/test_host_sanitize.py builds it with g++ alone).
 #include <zlib.h>
 
 #include <algorithm>
@@ -19,6 +24,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -78,10 +84,10 @@ struct Component {
     int id = 0, h = 1, v = 1, tq = 0;
     int wblocks = 0, hblocks = 0;            // allocated block grid (padded to whole MCUs)
     int dw = 0, dh = 0;                      // "downsampled" real sample dimensions
-    std::vector<int16_t> coef;               // [hblocks][wblocks][64], natural order
-    uint16_t quant[64];
+    int16_t* coef = nullptr;                 // [hblocks][wblocks][64], natural order: the caller's memory (fh_jpeg_entropy), at coef_off
+    long long coef_off = 0;
+    uint16_t quant[64] = {0};
     bool quant_latched = false;
-    std::vector<uint8_t> plane;              // IDCT output, (hblocks*8) x (wblocks*8)
 };
 
 struct BitReader {
@@ -143,6 +149,11 @@ struct Jpeg {
     bool adobe = false;
     int adobe_transform = 0;
     int orientation = 1;
+    // where the coefficients go: `cap` int16 elements at coef_mem (fh_jpeg_entropy), or nowhere (fh_jpeg_header stops at the frame header)
+    int16_t* coef_mem = nullptr;
+    size_t cap = 0;
+    bool header_only = false;
+    long long coef_count = 0;
 
     static int u16(const uint8_t* p) { return (p[0] << 8) | p[1]; }
 
@@ -193,8 +204,16 @@ struct Jpeg {
             c.wblocks = mcux * c.h; c.hblocks = mcuy * c.v;
             c.dw = (int)(((long)width * c.h + hmax - 1) / hmax);
             c.dh = (int)(((long)height * c.v + vmax - 1) / vmax);
-            c.coef.assign((size_t)c.wblocks * c.hblocks * 64, 0);
+            if (hmax % c.h || vmax % c.v) fail("JPEG: fractional sampling ratio");
+            c.coef_off = coef_count;
+            coef_count += (long long)c.wblocks * c.hblocks * 64;
         }
+        if (header_only) return;
+        // the one place that decides where coefficients may land: the geometry is fixed here (a second frame header is an error), every
+        // block index of a scan stays inside its component's grid, so nothing at or behind coef_mem + coef_count is written
+        if ((unsigned long long)coef_count > cap) fail("JPEG: the coefficient buffer is too small for this frame");
+        memset(coef_mem, 0, (size_t)coef_count * sizeof(int16_t));
+        for (int i = 0; i < ncomp; ++i) comp[i].coef = coef_mem + comp[i].coef_off;
     }
 
     // ---- one scan ------------------------------------------------------------------------------
@@ -350,7 +369,7 @@ struct Jpeg {
 
         auto do_block = [&](int i, int bx, int by) {
             Component& c = comp[ci[i]];
-            int16_t* blk = &c.coef[((size_t)by * c.wblocks + bx) * 64];
+            int16_t* blk = c.coef + ((size_t)by * c.wblocks + bx) * 64;
             if (!progressive) decode_block_baseline(br, blk, dc[td[i]], ac[ta[i]], pred[i]);
             else if (ss == 0) { if (ah == 0) decode_dc_first(br, blk, dc[td[i]], pred[i], al); else decode_dc_refine(br, blk, al); }
             else { if (ah == 0) decode_ac_first(br, blk, ac[ta[i]], ss, se, al); else decode_ac_refine(br, blk, ac[ta[i]], ss, se, al); }
@@ -384,8 +403,151 @@ struct Jpeg {
         return (size_t)(q - d);
     }
 
+    // ---- the marker loop: everything (fh_jpeg_entropy) or up to the frame header (fh_jpeg_header) ----
+    void parse() {
+        if (n < 4 || d[0] != 0xFF || d[1] != 0xD8) fail("JPEG: no SOI");
+        size_t pos = 2;
+        bool have_sof = false, done = false;
+        while (!done) {
+            while (pos < n && d[pos] != 0xFF) ++pos;
+            while (pos < n && d[pos] == 0xFF) ++pos;
+            if (pos >= n) break;
+            const int m = d[pos++];
+            if (m == 0xD9) break;
+            if (m == 0x01 || (m >= 0xD0 && m <= 0xD7)) continue;
+            if (pos + 2 > n) fail("JPEG: truncated marker");
+            const int len = u16(d + pos) - 2;
+            const uint8_t* p = d + pos + 2;
+            if (len < 0 || pos + 2 + (size_t)len > n) fail("JPEG: truncated segment");
+            switch (m) {
+                case 0xC0: case 0xC1: case 0xC2:
+                    if (have_sof) fail("JPEG: more than one frame");
+                    progressive = m == 0xC2;
+                    read_sof(p, len);
+                    have_sof = true;
+                    if (header_only) return;
+                    break;
+                case 0xC3: case 0xC5: case 0xC6: case 0xC7: case 0xC9: case 0xCA: case 0xCB: case 0xCD: case 0xCE: case 0xCF:
+                    fail("JPEG: lossless / hierarchical / arithmetic-coded files are not supported");
+                case 0xC4: {
+                    int o = 0;
+                    while (o + 17 <= len) {
+                        const int tc = p[o] >> 4, th = p[o] & 15;
+                        if (tc > 1 || th > 3) fail("JPEG: bad DHT");
+                        Huff& h = tc ? ac[th] : dc[th];
+                        int total = 0;
+                        h.bits[0] = 0;
+                        for (int i = 1; i <= 16; ++i) { h.bits[i] = p[o + i]; total += h.bits[i]; }
+                        if (total > 256 || o + 17 + total > len) fail("JPEG: bad DHT");
+                        memset(h.vals, 0, sizeof(h.vals));
+                        memcpy(h.vals, p + o + 17, total);
+                        h.build();
+                        o += 17 + total;
+                    }
+                    break;
+                }
+                case 0xDB: {
+                    int o = 0;
+                    while (o < len) {
+                        const int pq = p[o] >> 4, tq = p[o] & 15;
+                        if (tq > 3 || pq > 1 || o + 1 + 64 * (pq + 1) > len) fail("JPEG: bad DQT");
+                        for (int i = 0; i < 64; ++i) qt[tq][kZigzag[i]] = pq ? (uint16_t)u16(p + o + 1 + 2 * i) : p[o + 1 + i];
+                        qt_present[tq] = true;
+                        o += 1 + 64 * (pq + 1);
+                    }
+                    break;
+                }
+                case 0xDD:
+                    if (len < 2) fail("JPEG: bad DRI");
+                    restart_interval = u16(p);
+                    break;
+                case 0xE1: parse_exif(p, len); break;
+                case 0xEE:
+                    if (len >= 12 && memcmp(p, "Adobe", 5) == 0) { adobe = true; adobe_transform = p[11]; }
+                    break;
+                case 0xDA:
+                    if (!have_sof) fail("JPEG: scan before frame header");
+                    pos = read_scan(pos + 2, len);
+                    continue;
+                default: break;
+            }
+            pos += 2 + (size_t)len;
+        }
+        if (!have_sof) fail("JPEG: no frame header");
+        for (int i = 0; i < ncomp; ++i)
+            if (!comp[i].quant_latched) fail("JPEG: component without a scan");
+    }
+
+    // what reconstruction needs (fh_jpeg_desc, include/facehip.h); after a header-only parse the quantisers are still zero
+    void fill_desc(fh_jpeg_desc* o) const {
+        memset(o, 0, sizeof(*o));
+        o->width = width; o->height = height;
+        o->orientation = orientation;
+        o->rows = orientation >= 5 ? width : height; o->cols = orientation >= 5 ? height : width;
+        o->ncomp = ncomp; o->hmax = hmax; o->vmax = vmax;
+        const bool rgb = ncomp == 3 && (adobe ? adobe_transform == 0 : (comp[0].id == 'R' && comp[1].id == 'G' && comp[2].id == 'B'));
+        o->color = ncomp == 1 ? 0 : rgb ? 2 : 1;
+        o->coef_count = coef_count;
+        for (int i = 0; i < ncomp; ++i) {
+            const Component& c = comp[i];
+            fh_jpeg_comp& oc = o->comp[i];
+            oc.h = c.h; oc.v = c.v; oc.wblocks = c.wblocks; oc.hblocks = c.hblocks; oc.dw = c.dw; oc.dh = c.dh;
+            oc.coef_off = c.coef_off;
+            memcpy(oc.quant, c.quant, sizeof(oc.quant));
+        }
+    }
+};
+
+// fh_jpeg_desc_check's body: null when the descriptor is one the parser could have produced, else the complaint.  Everything both
+// reconstructions index with is pinned here: the block grids and sample sizes follow from width / height and the sampling factors, the
+// coefficient ranges lie inside [0, coef_count) and apart from each other.
+const char* bad_desc(const fh_jpeg_desc* o) {
+    if (!o) return "null descriptor";
+    if (o->ncomp != 1 && o->ncomp != 3) return "ncomp must be 1 or 3";
+    if (o->width <= 0 || o->height <= 0 || o->width > (1 << 20) || o->height > (1 << 20) || (long long)o->width * o->height > kMaxPixels)
+        return "unreasonable image size";
+    if (o->orientation < 1 || o->orientation > 8) return "orientation outside 1..8";
+    const bool swap = o->orientation >= 5;
+    if (o->rows != (swap ? o->width : o->height) || o->cols != (swap ? o->height : o->width)) return "rows / cols do not follow from width / height and the orientation";
+    if (o->color < 0 || o->color > 2 || (o->ncomp == 1) != (o->color == 0)) return "color must be 0 for one component and 1 or 2 for three";
+    if (o->hmax < 1 || o->hmax > 4 || o->vmax < 1 || o->vmax > 4) return "hmax / vmax outside 1..4";
+    int hm = 0, vm = 0;
+    for (int i = 0; i < o->ncomp; ++i) {
+        const fh_jpeg_comp& c = o->comp[i];
+        if (c.h < 1 || c.h > 4 || c.v < 1 || c.v > 4) return "a sampling factor outside 1..4";
+        if (o->hmax % c.h || o->vmax % c.v) return "fractional sampling ratio";
+        hm = std::max(hm, c.h); vm = std::max(vm, c.v);
+    }
+    if (hm != o->hmax || vm != o->vmax) return "hmax / vmax are not the largest sampling factors";
+    const int mcux = (o->width + 8 * o->hmax - 1) / (8 * o->hmax), mcuy = (o->height + 8 * o->vmax - 1) / (8 * o->vmax);
+    if (o->coef_count < 0) return "negative coef_count";
+    for (int i = 0; i < o->ncomp; ++i) {
+        const fh_jpeg_comp& c = o->comp[i];
+        if (c.wblocks != mcux * c.h || c.hblocks != mcuy * c.v) return "a block grid does not match width / height";
+        if (c.dw != (int)(((long long)o->width * c.h + o->hmax - 1) / o->hmax) || c.dh != (int)(((long long)o->height * c.v + o->vmax - 1) / o->vmax))
+            return "dw / dh do not match width / height";
+        const long long len = (long long)c.wblocks * c.hblocks * 64;
+        if (c.coef_off < 0 || c.coef_off > o->coef_count || len > o->coef_count - c.coef_off) return "a coef_off range exceeds coef_count";
+        for (int j = 0; j < i; ++j) {
+            const fh_jpeg_comp& e = o->comp[j];
+            const long long elen = (long long)e.wblocks * e.hblocks * 64;
+            if (c.coef_off < e.coef_off + elen && e.coef_off < c.coef_off + len) return "coef_off ranges overlap";
+        }
+    }
+    return nullptr;
+}
+
+// fh_jpeg_reconstruct's working state: the components' IDCT output planes, then up-sampling and colour conversion to an Image
+struct Recon {
+    struct RComp {
+        int h, v, wblocks, hblocks, dw, dh;
+        std::vector<uint8_t> plane;              // IDCT output, (hblocks*8) x (wblocks*8)
+    };
+    int width = 0, height = 0, ncomp = 0, hmax = 1, vmax = 1;
+    RComp comp[3];
+
     // ---- inverse DCT: jidctint.c "islow" (13-bit constants, 2 extra bits between the passes) ----
-    static inline uint8_t range_limit(int x) {                   // libjpeg's centred range-limit table, index & 1023
+    static inline uint8_t range_limit(int x) {                 // libjpeg's centred range-limit table, index & 1023
         const int i = x & 1023;
         if (i < 128) return (uint8_t)(i + 128);
         if (i < 512) return 255;
@@ -445,7 +607,7 @@ struct Jpeg {
 
     // ---- chroma up-sampling to full resolution: jdsample.c --------------------------------------
     // src: c.plane (stride sw) with real size dw x dh; result: width x height samples
-    std::vector<uint8_t> upsample(const Component& c) const {
+    std::vector<uint8_t> upsample(const RComp& c) const {
         const int sw = c.wblocks * 8;
         const uint8_t* src = c.plane.data();
         std::vector<uint8_t> out((size_t)width * height);
@@ -507,84 +669,19 @@ struct Jpeg {
         return out;
     }
 
-    Image decode() {
-        if (n < 4 || d[0] != 0xFF || d[1] != 0xD8) fail("JPEG: no SOI");
-        size_t pos = 2;
-        bool have_sof = false, done = false;
-        while (!done) {
-            while (pos < n && d[pos] != 0xFF) ++pos;
-            while (pos < n && d[pos] == 0xFF) ++pos;
-            if (pos >= n) break;
-            const int m = d[pos++];
-            if (m == 0xD9) break;
-            if (m == 0x01 || (m >= 0xD0 && m <= 0xD7)) continue;
-            if (pos + 2 > n) fail("JPEG: truncated marker");
-            const int len = u16(d + pos) - 2;
-            const uint8_t* p = d + pos + 2;
-            if (len < 0 || pos + 2 + (size_t)len > n) fail("JPEG: truncated segment");
-            switch (m) {
-                case 0xC0: case 0xC1: case 0xC2:
-                    if (have_sof) fail("JPEG: more than one frame");
-                    progressive = m == 0xC2;
-                    read_sof(p, len);
-                    have_sof = true;
-                    break;
-                case 0xC3: case 0xC5: case 0xC6: case 0xC7: case 0xC9: case 0xCA: case 0xCB: case 0xCD: case 0xCE: case 0xCF:
-                    fail("JPEG: lossless / hierarchical / arithmetic-coded files are not supported");
-                case 0xC4: {
-                    int o = 0;
-                    while (o + 17 <= len) {
-                        const int tc = p[o] >> 4, th = p[o] & 15;
-                        if (tc > 1 || th > 3) fail("JPEG: bad DHT");
-                        Huff& h = tc ? ac[th] : dc[th];
-                        int total = 0;
-                        h.bits[0] = 0;
-                        for (int i = 1; i <= 16; ++i) { h.bits[i] = p[o + i]; total += h.bits[i]; }
-                        if (total > 256 || o + 17 + total > len) fail("JPEG: bad DHT");
-                        memset(h.vals, 0, sizeof(h.vals));
-                        memcpy(h.vals, p + o + 17, total);
-                        h.build();
-                        o += 17 + total;
-                    }
-                    break;
-                }
-                case 0xDB: {
-                    int o = 0;
-                    while (o < len) {
-                        const int pq = p[o] >> 4, tq = p[o] & 15;
-                        if (tq > 3 || pq > 1 || o + 1 + 64 * (pq + 1) > len) fail("JPEG: bad DQT");
-                        for (int i = 0; i < 64; ++i) qt[tq][kZigzag[i]] = pq ? (uint16_t)u16(p + o + 1 + 2 * i) : p[o + 1 + i];
-                        qt_present[tq] = true;
-                        o += 1 + 64 * (pq + 1);
-                    }
-                    break;
-                }
-                case 0xDD:
-                    if (len < 2) fail("JPEG: bad DRI");
-                    restart_interval = u16(p);
-                    break;
-                case 0xE1: parse_exif(p, len); break;
-                case 0xEE:
-                    if (len >= 12 && memcmp(p, "Adobe", 5) == 0) { adobe = true; adobe_transform = p[11]; }
-                    break;
-                case 0xDA:
-                    if (!have_sof) fail("JPEG: scan before frame header");
-                    pos = read_scan(pos + 2, len);
-                    continue;
-                default: break;
-            }
-            pos += 2 + (size_t)len;
-        }
-        if (!have_sof) fail("JPEG: no frame header");
-
+    // de-quantise + IDCT every block, up-sample, convert: the picture as coded (the orientation comes after)
+    Image run(const fh_jpeg_desc& o, const int16_t* coef) {
+        width = o.width; height = o.height; ncomp = o.ncomp; hmax = o.hmax; vmax = o.vmax;
         for (int i = 0; i < ncomp; ++i) {
-            Component& c = comp[i];
-            if (!c.quant_latched) fail("JPEG: component without a scan");
+            const fh_jpeg_comp& oc = o.comp[i];
+            RComp& c = comp[i];
+            c.h = oc.h; c.v = oc.v; c.wblocks = oc.wblocks; c.hblocks = oc.hblocks; c.dw = oc.dw; c.dh = oc.dh;
             c.plane.assign((size_t)c.wblocks * 8 * c.hblocks * 8, 0);
             const int stride = c.wblocks * 8;
+            const int16_t* cc = coef + oc.coef_off;
             for (int by = 0; by < c.hblocks; ++by)
                 for (int bx = 0; bx < c.wblocks; ++bx)
-                    idct_islow(&c.coef[((size_t)by * c.wblocks + bx) * 64], c.quant, &c.plane[(size_t)by * 8 * stride + bx * 8], stride);
+                    idct_islow(&cc[((size_t)by * c.wblocks + bx) * 64], oc.quant, &c.plane[(size_t)by * 8 * stride + bx * 8], stride);
         }
         Image img;
         img.rows = height; img.cols = width;
@@ -594,8 +691,7 @@ struct Jpeg {
             for (size_t i = 0; i < y.size(); ++i) img.bgr[3 * i] = img.bgr[3 * i + 1] = img.bgr[3 * i + 2] = y[i];
         } else {
             const std::vector<uint8_t> p0 = upsample(comp[0]), p1 = upsample(comp[1]), p2 = upsample(comp[2]);
-            const bool rgb = adobe ? adobe_transform == 0 : (comp[0].id == 'R' && comp[1].id == 'G' && comp[2].id == 'B');
-            if (rgb) {
+            if (o.color == 2) {
                 for (size_t i = 0; i < p0.size(); ++i) { img.bgr[3 * i] = p2[i]; img.bgr[3 * i + 1] = p1[i]; img.bgr[3 * i + 2] = p0[i]; }
             } else {                                              // jdcolor.c ycc_rgb_convert, SCALEBITS = 16
                 int cr_r[256], cb_b[256];
@@ -839,25 +935,96 @@ Image decode_pnm(const uint8_t* d, size_t n) {
 }
 
 Image decode_any(const uint8_t* d, size_t n) {
-    if (n >= 3 && d[0] == 0xFF && d[1] == 0xD8) {
-        Jpeg j;
-        j.d = d; j.n = n;
-        Image img = j.decode();
-        return apply_orientation(std::move(img), j.orientation);
-    }
     if (n >= 8 && d[0] == 0x89 && d[1] == 'P') return decode_png(d, n);
     if (n >= 2 && d[0] == 'B' && d[1] == 'M') return decode_bmp(d, n);
     if (n >= 2 && d[0] == 'P' && (d[1] == '6' || d[1] == '5')) return decode_pnm(d, n);
     fail("unrecognised image format (JPEG, PNG, BMP, PPM/PGM are supported)");
 }
 
+bool is_jpeg(const uint8_t* d, size_t n) { return n >= 3 && d[0] == 0xFF && d[1] == 0xD8; }
+
+// The two halves of the JPEG decoder (fh_jpeg_header / fh_jpeg_entropy, fh_jpeg_reconstruct); both throw DecodeError.
+void jpeg_parse(const uint8_t* d, size_t n, fh_jpeg_desc* desc, int16_t* coef, size_t cap, bool header_only) {
+    Jpeg j;
+    j.d = d; j.n = n;
+    j.coef_mem = coef; j.cap = cap; j.header_only = header_only;
+    j.parse();
+    j.fill_desc(desc);
+}
+void jpeg_reconstruct(const fh_jpeg_desc& o, const int16_t* coef, uint8_t* bgr, size_t step) {
+    if (const char* bad = bad_desc(&o)) fail(std::string("JPEG descriptor: ") + bad);
+    Recon rc;
+    const Image img = apply_orientation(rc.run(o, coef), o.orientation);
+    const size_t row = (size_t)img.cols * 3;
+    for (int y = 0; y < img.rows; ++y) memcpy(bgr + (size_t)y * step, &img.bgr[(size_t)y * row], row);
+}
+
+// set_error + the C ABI's return value around a throwing body
+template <class F>
+int jpeg_call(const char* fn, F&& f) {
+    try {
+        f();
+        return 0;
+    } catch (const DecodeError& e) {
+        fh::set_error(e.msg);
+    } catch (const std::exception& e) {
+        fh::set_error(std::string(fn) + ": " + e.what());
+    }
+    return -1;
+}
+
 }  // namespace
 
 extern "C" {
 
+int fh_jpeg_header(const unsigned char* bytes, size_t n, fh_jpeg_desc* desc) {
+    if (!bytes || !desc) { fh::set_error("fh_jpeg_header: null argument"); return -1; }
+    return jpeg_call("fh_jpeg_header", [&] {
+        if (!is_jpeg(bytes, n)) fail("JPEG: no SOI");
+        jpeg_parse(bytes, n, desc, nullptr, 0, true);
+    });
+}
+
+int fh_jpeg_entropy(const unsigned char* bytes, size_t n, fh_jpeg_desc* desc, int16_t* coef, size_t cap) {
+    if (!bytes || !desc || !coef) { fh::set_error("fh_jpeg_entropy: null argument"); return -1; }
+    return jpeg_call("fh_jpeg_entropy", [&] {
+        if (!is_jpeg(bytes, n)) fail("JPEG: no SOI");
+        jpeg_parse(bytes, n, desc, coef, cap, false);
+    });
+}
+
+int fh_jpeg_desc_check(const fh_jpeg_desc* desc) {
+    if (const char* bad = bad_desc(desc)) { fh::set_error(std::string("fh_jpeg_desc_check: ") + bad); return FH_ERR_ARG; }
+    return 0;
+}
+
+int fh_jpeg_reconstruct(const fh_jpeg_desc* desc, const int16_t* coef, unsigned char* bgr, int step) {
+    if (!desc || !coef || !bgr) { fh::set_error("fh_jpeg_reconstruct: null argument"); return FH_ERR_ARG; }
+    if (const char* bad = bad_desc(desc)) { fh::set_error(std::string("fh_jpeg_reconstruct: ") + bad); return FH_ERR_ARG; }
+    if ((long long)step < (long long)desc->cols * 3) { fh::set_error("fh_jpeg_reconstruct: step is smaller than cols * 3"); return FH_ERR_ARG; }
+    return jpeg_call("fh_jpeg_reconstruct", [&] { jpeg_reconstruct(*desc, coef, bgr, (size_t)step); });
+}
+
 int fh_image_decode(const unsigned char* bytes, size_t n, unsigned char** bgr, int* rows, int* cols) {
     if (!bytes || !bgr || !rows || !cols) { fh::set_error("fh_image_decode: null argument"); return -1; }
     *bgr = nullptr; *rows = *cols = 0;
+    if (is_jpeg(bytes, n)) {                                      // fh_jpeg_entropy, then fh_jpeg_reconstruct
+        unsigned char* out = nullptr;
+        const int rc = jpeg_call("fh_image_decode", [&] {
+            fh_jpeg_desc o;
+            jpeg_parse(bytes, n, &o, nullptr, 0, true);
+            const std::unique_ptr<int16_t[]> coef(new int16_t[(size_t)o.coef_count]);
+            jpeg_parse(bytes, n, &o, coef.get(), (size_t)o.coef_count, false);
+            const size_t size = (size_t)o.rows * o.cols * 3;
+            out = static_cast<unsigned char*>(malloc(size ? size : 1));
+            if (!out) fail("fh_image_decode: out of memory");
+            jpeg_reconstruct(o, coef.get(), out, (size_t)o.cols * 3);
+            *rows = o.rows; *cols = o.cols;
+        });
+        if (rc != 0) { free(out); *rows = *cols = 0; return -1; }
+        *bgr = out;
+        return 0;
+    }
     try {
         Image img = decode_any(bytes, n);
         unsigned char* out = static_cast<unsigned char*>(malloc(img.bgr.size() ? img.bgr.size() : 1));

@@ -930,6 +930,74 @@ FH_API int fh_imread(const char* path, unsigned char** bgr, int* rows, int* cols
 FH_API int fh_image_decode(const unsigned char* bytes, size_t n, unsigned char** bgr, int* rows, int* cols);
 FH_API void fh_image_free(unsigned char* bgr);
 
+/* ---- JPEG in two halves: entropy decoding on the host, pixel reconstruction on the device.  Huffman decoding is serial per file and
+ * independent across files (host threads); everything behind it — de-quantisation, the islow IDCT, chroma up-sampling, YCbCr -> RGB, the
+ * EXIF orientation — is integer arithmetic that is independent per pixel (kernels, csrc/jpeg_dev.hip).  The cut is the decoder's own
+ * intermediate: every component's coefficients as a dense int16 plane.  fh_imread / fh_image_decode keep their behaviour and their bits:
+ * for a JPEG, fh_image_decode IS fh_jpeg_entropy followed by fh_jpeg_reconstruct.
+ *
+ * fh_jpeg_desc  what reconstruction needs besides the coefficients; a POD, 528 bytes.  width / height as coded (before the
+ *           orientation), rows / cols of the picture handed out (after it: swapped for orientations 5..8); ncomp 1 or 3; hmax / vmax the
+ *           largest sampling factors; color 0 grey, 1 YCbCr, 2 RGB (an Adobe marker with transform 0, or component ids 'R','G','B');
+ *           orientation 1..8 (EXIF tag 0x0112; 1 when absent); coef_count = int16 elements of all components.  Per component: sampling
+ *           factors h / v, the block grid wblocks x hblocks (padded to whole MCUs: ceil(width / (8 hmax)) * h, likewise down), the real
+ *           sample size dw = ceil(width * h / hmax) / dh, coef_off = where its [hblocks][wblocks][64] coefficients (natural order, not
+ *           zigzag) start, in int16 elements, and quant[64], natural order, the table latched at the component's first scan.
+ * fh_jpeg_header  reads markers up to the frame header only: sizes, sampling factors, block grids, coef_count, and the orientation / Adobe
+ *           marker when they stand in front of the frame header (where writers put them) — enough to size buffers.  quant stays zero.
+ * fh_jpeg_entropy  the whole parse: zero-fills coef[0 .. coef_count) in the CALLER's memory, decodes every scan into it and completes
+ *           *desc.  cap = the int16 elements coef holds; coef_count > cap is an error, and nothing at or behind coef + coef_count is ever
+ *           written, whatever later markers of a damaged file say.  A damaged header is an error; entropy data that ends early decodes as
+ *           zeros (libjpeg's behaviour, as fh_image_decode).
+ * fh_jpeg_reconstruct  host: coefficients -> BGR u8 [rows][cols] at pitch `step` (>= cols * 3; bytes of a row behind cols * 3 are not
+ *           written).  The bit-exact oracle of the device path.
+ * fh_jpeg_desc_check  the one validator both reconstructions run first: FH_ERR_ARG for ncomp / sampling factors out of range, hmax % h or
+ *           vmax % v != 0, block grids or dw / dh that do not follow from width / height, coef_off ranges that overlap or pass coef_count,
+ *           an orientation outside 1..8, rows / cols that do not follow from it, a color outside 0..2 or one that disagrees with ncomp.  A
+ *           descriptor can be made by hand: a bad one never reaches a kernel.
+ * All five: 0 on success, < 0 + fh_last_error().  Host code, no GPU. */
+typedef struct fh_jpeg_comp {
+    int32_t h, v, wblocks, hblocks, dw, dh;
+    int64_t coef_off;
+    uint16_t quant[64];
+} fh_jpeg_comp;                                                                          /* 160 bytes */
+typedef struct fh_jpeg_desc {
+    int32_t width, height, rows, cols, ncomp, hmax, vmax, color, orientation, reserved;
+    int64_t coef_count;
+    fh_jpeg_comp comp[3];
+} fh_jpeg_desc;                                                                          /* 528 bytes */
+FH_API int fh_jpeg_header(const unsigned char* bytes, size_t n, fh_jpeg_desc* desc);
+FH_API int fh_jpeg_entropy(const unsigned char* bytes, size_t n, fh_jpeg_desc* desc, int16_t* coef, size_t cap);
+FH_API int fh_jpeg_reconstruct(const fh_jpeg_desc* desc, const int16_t* coef, unsigned char* bgr, int step);
+FH_API int fh_jpeg_desc_check(const fh_jpeg_desc* desc);
+/* fh_jpegdec  owner of the device side: the device copy of the descriptor table, the workspace of IDCT output planes, and (for
+ *           fh_jpeg_decode_batch) the pinned coefficient arena, its device copy and the device pixel arena.  All grow on demand.
+ * fh_jpeg_reconstruct_batch_dev  fh_jpeg_reconstruct for n images (1 <= n <= 4096) in TWO launches, whatever n is: descs = HOST array
+ *           (read before the call returns), d_coef = DEVICE int16, coef_base[i] = image i's offset in it (int16 elements; image i reads
+ *           [coef_base[i], coef_base[i] + descs[i].coef_count)), out_frames[i].bgr = DEVICE memory for rows x cols pixels at pitch step >=
+ *           cols * 3, whose rows / cols must equal the descriptor's.  A slot with bgr == NULL is skipped.  Only the bytes
+ *           [row * step, row * step + cols * 3) of a frame are written, and they equal fh_jpeg_reconstruct's for every descriptor
+ *           fh_jpeg_desc_check accepts and every int16 / uint16 value.  Every descriptor is checked before anything is launched: one bad
+ *           one fails the call with FH_ERR_ARG and nothing is written.  Asynchronous on `stream`; returns n. */
+typedef struct fh_jpegdec fh_jpegdec;
+FH_API fh_jpegdec* fh_jpegdec_create(void);
+FH_API void fh_jpegdec_destroy(fh_jpegdec* dec);
+FH_API int fh_jpeg_reconstruct_batch_dev(fh_jpegdec* dec, const fh_jpeg_desc* descs, int n, const int16_t* d_coef, const long long* coef_base,
+                                         const fh_frame* out_frames, void* stream);
+/* fh_jpeg_decode_batch  n files (1 <= n <= 4096) -> n device images.  fh_jpeg_header sizes one pinned coefficient arena and one device
+ *           pixel arena; fh_jpeg_entropy runs on up to `threads` host threads (clipped to [1, 16]; 0 = min(16, n)), one file per task,
+ *           straight into the pinned arena; ONE host-to-device copy; one fh_jpeg_reconstruct_batch_dev.  frames_out[i] describes image i
+ *           in the device arena (step = cols * 3), valid until the next call on `dec`.  status[i]: 0 = JPEG, reconstructed on the device;
+ *           1 = another format fh_image_decode accepts, decoded on the host (by the same threads), pixels sent in the same copy; < 0 = not
+ *           decodable: frames_out[i] is the empty frame (cv::imread's empty Mat) and the call still succeeds.  status may be NULL.
+ *           Asynchronous on `stream` behind the host work; returns the number of decoded images.
+ * fh_pipeline_run_files  the above followed by fh_pipeline_run_ragged_dev on the detector's own stream, blocking: outputs, cap and return
+ *           value as fh_pipeline_run_images, and every result equals, bit for bit, fh_image_decode per file + fh_pipeline_run_images. */
+typedef struct fh_blob { const unsigned char* bytes; size_t n; } fh_blob;
+FH_API int fh_jpeg_decode_batch(fh_jpegdec* dec, const fh_blob* files, int n, int threads, fh_frame* frames_out, int* status, void* stream);
+FH_API int fh_pipeline_run_files(fh_det* d, fh_rec* r, fh_jpegdec* dec, const fh_blob* files, int n, int threads, float score_thr,
+                                 float nms_thr, int faces_per_frame, fh_face* faces, int* frame_of, float* emb, int cap, int* status);
+
 /* ---- single kernels exposed for parity tests and micro-benchmarks (device pointers). */
 FH_API int fh_memcpy_d2h(void* host_dst, const void* dev_src, size_t bytes);   /* synchronous */
 FH_API int fh_resize_u8c3_dev(const uint8_t* d_src, int sh, int sw, int sstep, uint8_t* d_dst, int dh, int dw, int dstep,

@@ -1,0 +1,27 @@
+"""AddressSanitizer + UndefinedBehaviorSanitizer over the host half of the JPEG split (fh_jpeg_header -> exactly sized heap buffers ->
+fh_jpeg_entropy -> fh_jpeg_reconstruct, csrc/image_io.cpp) as a stand-alone CPU program: tests/native/jpeg_split_sanitize.cpp.  Every
+JPEG fixture and a few hundred seeded damaged variants of each (truncations, byte flips, 16-byte splats): no report, no write outside
+the buffers, 0 failures."""
+import os
+import shutil
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "facerecognizeonnx_amd", "csrc")
+
+
+@pytest.mark.timeout(600)
+def test_jpeg_split_survives_damaged_inputs_under_asan_ubsan(tmp_path):
+    if not shutil.which("g++"):
+        pytest.skip("no host compiler")
+    exe = str(tmp_path / "jpeg_split_sanitize")
+    cmd = ["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-omit-frame-pointer", "-fno-sanitize-recover=undefined",
+           "-o", exe, os.path.join(ROOT, "tests", "native", "jpeg_split_sanitize.cpp"), os.path.join(CSRC, "image_io.cpp"), "-lz"]
+    b = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=400)
+    assert b.returncode == 0, b.stdout[-3000:]
+    env = dict(os.environ, ASAN_OPTIONS="allocator_may_return_null=1:max_allocation_size_mb=4096:detect_leaks=1")
+    r = subprocess.run([exe, os.path.join(ROOT, "tests", "golden")], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True,
+                       timeout=400)
+    assert r.returncode == 0 and "0 failures" in r.stdout, r.stdout[-4000:]
