@@ -72,6 +72,10 @@ HIST_BINS = 2048                                               # FH_HIST_BINS
 TAG_ALL = 0xFFFFFFFF                                           # FH_TAG_ALL
 RANGE_MAX_CAP = 1024                                           # FH_RANGE_MAX_CAP
 TOPK_DEEP_MAX = 1024                                           # FH_TOPK_DEEP_MAX
+PAIRS_MAX_CAP = 1024                                           # FH_PAIRS_MAX_CAP
+PAIRS_ROOM = 65536                                             # FH_PAIRS_ROOM
+PAIRS_CLASS = {"genuine": 0, "impostor": 1, "any": 2}          # enum fh_pairs_class
+PAIRS_SIDE = {"above": 0, "not_above": 1}                      # enum fh_pairs_side
 ROC_POINT_DTYPE = np.dtype([("threshold", "<f4"), ("bin", "<i4"), ("true_accepts", "<u8"), ("false_accepts", "<u8"), ("genuine", "<u8"),
                             ("impostor", "<u8")])              # fh_roc_point
 assert ROC_POINT_DTYPE.itemsize == 40
@@ -216,6 +220,8 @@ PROTOTYPES = {
     "fh_hist_bin": (_i, [_f]),
     "fh_roc_from_hist": (_i, [_vp, _d, _vp]),
     "fh_gallery_pair_hist_dev": (_i, [_vp, _vp, _vp, _vp]),
+    "fh_pairs_from_scores": (_i, [_vp, _i, _vp, _i, _i, _f, _i, _ll, _vp, _vp, _vp, _vp]),
+    "fh_gallery_pairs_dev": (_i, [_vp, _i, _i, _f, _i, _vp, _vp, _vp, _vp, _vp]),
     "fh_gallery_set_ids": (_ll, [_vp, _vp, _i]),
     "fh_gallery_set_tags": (_ll, [_vp, _ll, _ll, _vp, _i]),
     "fh_gallery_get_tags": (_ll, [_vp, _ll, _ll, _vp]),
@@ -274,6 +280,7 @@ PROTOTYPES = {
     "fh_debug_wino_slots": (_i, [_i]),
     "fh_debug_cluster_tiles": (_i, [_i]),
     "fh_debug_hist_copies": (_i, [_i]),
+    "fh_debug_pairs_room": (_i, [_i]),
     "fh_debug_tag_skip": (_i, [_i]),
     "fh_debug_topk_merge_strided_dev": (_i, [_vp, _vp, _i, _i, _i, _ll, _vp, _vp, _vp]),
     "fh_set_graph_replay": (_i, [_i]),

@@ -841,6 +841,37 @@ class Gallery:
         out = buf.cpu().numpy().view(np.uint64)
         return out[:2 * _lib.HIST_BINS].reshape(2, _lib.HIST_BINS).copy(), out[2 * _lib.HIST_BINS:].copy()
 
+    def pairs_dev(self, cls, side, threshold: float, cap: int, info_ptr: int, scores_ptr: Optional[int] = None,
+                  rows_ptr: Optional[int] = None, ids_ptr: Optional[int] = None, stream: int = 0):
+        """The pair audit (fh_gallery_pairs_dev): WHICH pairs of rows of class `cls` ("genuine": same id, "impostor", "any") score
+        strictly above `threshold` (side "above") or at or below it ("not_above"), most extreme first.  info[4] (device uint64) =
+        (count, nan, returned, complete); scores [cap] (device float32), rows [cap][2] (device int32: 0-based positions i < j) and ids
+        [cap][2] (device int32) — each optional — hold the first `returned` pairs of the ordered list and (-1.0, -1, -1) behind them.
+        complete == 0: the bin the cap falls into did not fit the library's candidate room and the list stops before it — it is still
+        an exact prefix.  A pair's score is the fp32 scan's.  "genuine" / "impostor" and ids need a labelled gallery.
+        1 <= cap <= PAIRS_MAX_CAP.  Asynchronous on `stream`."""
+        check(_lib.lib().fh_gallery_pairs_dev(self._h, _pairs_enum(_lib.PAIRS_CLASS, cls, "class"), _pairs_enum(_lib.PAIRS_SIDE, side, "side"),
+                                              float(np.float32(threshold)), int(cap), info_ptr, scores_ptr, rows_ptr, ids_ptr, stream),
+              "fh_gallery_pairs_dev")
+
+    def pairs(self, cls, side, threshold: float, cap: int = 64, ids: Optional[bool] = None):
+        """(info dict — count, nan, returned, complete —, scores float32[returned], rows int32[returned, 2], ids int32[returned, 2] or
+        None) of pairs_dev — a synchronous convenience that allocates and copies back.  ids: whether the listed rows' ids are fetched
+        (they need a labelled gallery); by default they are for the classes "genuine" and "impostor", which need one anyway."""
+        import torch
+        cap = int(cap)
+        n = max(cap, 1)
+        with_ids = _pairs_enum(_lib.PAIRS_CLASS, cls, "class") != _lib.PAIRS_CLASS["any"] if ids is None else bool(ids)
+        info = torch.empty(4, dtype=torch.int64, device="cuda")
+        scores = torch.empty(n, dtype=torch.float32, device="cuda")
+        rows = torch.empty((n, 2), dtype=torch.int32, device="cuda")
+        ids = torch.empty((n, 2), dtype=torch.int32, device="cuda") if with_ids else None
+        self.pairs_dev(cls, side, threshold, cap, info.data_ptr(), scores.data_ptr(), rows.data_ptr(), ids.data_ptr() if with_ids else None,
+                       torch.cuda.current_stream().cuda_stream)
+        d = _pairs_info(info.cpu().numpy().view(np.uint64))
+        m = d["returned"]
+        return d, scores[:m].cpu().numpy(), rows[:m].cpu().numpy(), ids[:m].cpu().numpy() if with_ids else None
+
     def set_ids(self, ids) -> int:
         """Replace the ids of all rows by position (int32[len(self)] >= 0, host array or a device tensor) and make the gallery labelled
         (fh_gallery_set_ids); with noise="self" labels: cluster -> set_ids -> fuse.  Synchronous; returns the row count."""
@@ -1076,6 +1107,46 @@ def roc_from_hist(hist, max_far: float):
         d["tar"] = d["true_accepts"] / d["genuine"]
         pts.append(d)
     return pts[0], pts[1]
+
+
+def _pairs_enum(table, value, what):
+    """a name of the table -> the enum; an int passes through (the library checks it)."""
+    if isinstance(value, str):
+        if value not in table:
+            raise ValueError(f"pairs {what} {value!r}: expected one of {sorted(table)}")
+        return table[value]
+    return int(value)
+
+
+def _pairs_info(info):
+    return {k: int(v) for k, v in zip(("count", "nan", "returned", "complete"), info)}
+
+
+def pairs_from_scores(scores, ids, cls, side, threshold: float, cap: int = 64, room: Optional[int] = None):
+    """(info dict, scores float32[cap], rows int32[cap, 2], ids int32[cap, 2]) of fh_pairs_from_scores — host only, the one definition
+    of the pair audit: of the pairs i < j of the square matrix `scores` (only its upper triangle is read) that are of class `cls`
+    ("genuine": ids[i] == ids[j], "impostor", "any"; ids=None allows only "any") and whose score is strictly above `threshold` (side
+    "above") or at or below it ("not_above"; a NaN score is on neither side and counted in info["nan"]), the most extreme
+    info["returned"] — score descending (ascending for "not_above"), then i, then j — and (-1.0, -1, -1) behind them.
+    info["count"] is exact.  returned = min(cap, count) and complete = 1 unless the score bin the cap falls into, together with the
+    bins beyond it, holds more than `room` pairs (default PAIRS_ROOM, at least cap): then the list stops before that bin, complete = 0."""
+    scores = np.ascontiguousarray(scores, np.float32)
+    if scores.ndim != 2 or scores.shape[0] != scores.shape[1]:
+        raise ValueError("pairs_from_scores: need a square matrix")
+    n = scores.shape[0]
+    if ids is not None:
+        ids = np.ascontiguousarray(np.asarray(ids).reshape(-1).astype(np.int32))
+        if ids.size != n:
+            raise ValueError("pairs_from_scores: need one id per row")
+    cap = int(cap)
+    room = max(_lib.PAIRS_ROOM, cap) if room is None else int(room)
+    m = max(cap, 0)
+    info, out_s, out_r, out_d = np.zeros(4, np.uint64), np.empty(m, np.float32), np.empty((m, 2), np.int32), np.empty((m, 2), np.int32)
+    check(_lib.lib().fh_pairs_from_scores(scores.ctypes.data if n else None, n, None if ids is None else ids.ctypes.data,
+                                          _pairs_enum(_lib.PAIRS_CLASS, cls, "class"), _pairs_enum(_lib.PAIRS_SIDE, side, "side"),
+                                          float(np.float32(threshold)), cap, room, info.ctypes.data, out_s.ctypes.data, out_r.ctypes.data,
+                                          out_d.ctypes.data), "fh_pairs_from_scores")
+    return _pairs_info(info), out_s, out_r, out_d
 
 
 def range_from_scores(scores, threshold: float, cap: int = 64, index_base: int = 0, tags=None, mask: int = _lib.TAG_ALL):

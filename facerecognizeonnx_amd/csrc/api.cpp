@@ -13,6 +13,7 @@
 #include "../../include/facehip.h"
 #include "cluster_plan.h"
 #include "deep_plan.h"
+#include "pairs_plan.h"
 #include "range_plan.h"
 #include "roc_plan.h"
 #include "engine.h"
@@ -1652,6 +1653,45 @@ int fh_gallery_pair_hist_dev(fh_gallery* g, unsigned long long* d_hist, unsigned
     return guarded([&] { g->g.pair_hist_dev(d_hist, d_nan, S(stream)); return (int)FH_OK; });
 }
 int fh_debug_hist_copies(int copies) { fh::cluster_debug_hist_copies(copies); return 0; }
+
+// ---- the pair audit: the rule on the host (pairs_plan.h), the same rule on the pair pass's accumulators (gallery_cluster.hip,
+// gallery_pairs.hip)
+static_assert(FH_PAIRS_GENUINE == fh::kPairsGenuine && FH_PAIRS_IMPOSTOR == fh::kPairsImpostor && FH_PAIRS_ANY == fh::kPairsAny &&
+              FH_PAIRS_ABOVE == fh::kPairsAbove && FH_PAIRS_NOT_ABOVE == fh::kPairsNotAbove && FH_PAIRS_MAX_CAP == fh::kPairsMaxCap &&
+              FH_PAIRS_ROOM == fh::kPairsRoom, "facehip.h mirrors pairs_plan.h and kernels.h");
+namespace {
+const char* bad_pairs(int cls, int side, float threshold, int cap) {
+    if (threshold != threshold) return "the threshold is a NaN";
+    if (cls != FH_PAIRS_GENUINE && cls != FH_PAIRS_IMPOSTOR && cls != FH_PAIRS_ANY) return "unknown class";
+    if (side != FH_PAIRS_ABOVE && side != FH_PAIRS_NOT_ABOVE) return "unknown side";
+    if (cap < 1 || cap > FH_PAIRS_MAX_CAP) return "need 1 <= cap <= FH_PAIRS_MAX_CAP";
+    return nullptr;
+}
+}  // namespace
+int fh_pairs_from_scores(const float* scores, int n, const int* ids, int cls, int side, float threshold, int cap, long long room,
+                         unsigned long long* info, float* out_scores, int* out_rows, int* out_ids) {
+    if (const char* why = bad_pairs(cls, side, threshold, cap)) return frames_error("fh_pairs_from_scores", why);
+    int listed = -1;
+    const int rc = guarded([&] {                                   // (its scratch may run out of memory)
+        listed = fh::pairs_from_scores(scores, n, ids, cls, side, threshold, cap, room, info, out_scores, out_rows, out_ids);
+        return 0;
+    });
+    if (rc < 0) return rc;
+    return listed < 0 ? arg_error("fh_pairs_from_scores: bad argument (n < 0, null scores or info, a class without ids, room < cap)") : listed;
+}
+int fh_gallery_pairs_dev(fh_gallery* g, int cls, int side, float threshold, int cap, unsigned long long* d_info, float* d_scores, int* d_rows,
+                         int* d_ids, void* stream) {
+    if (!g || !d_info) return arg_error("fh_gallery_pairs_dev: null argument");
+    if (const char* why = bad_pairs(cls, side, threshold, cap)) return frames_error("fh_gallery_pairs_dev", why);
+    if (g->g.dim() % 64) return arg_error("fh_gallery_pairs_dev: the gallery's dim must be a multiple of 64");
+    if ((cls != FH_PAIRS_ANY || d_ids) && g->g.size() > 0 && !g->g.labelled()) {
+        g_err = "gallery: fh_gallery_pairs_dev with a class other than FH_PAIRS_ANY or with d_ids needs a labelled gallery (rows enrolled with "
+                "ids, or fh_gallery_set_ids)";
+        return FH_ERR_STATE;
+    }
+    return guarded([&] { g->g.pairs_dev(cls, side, threshold, cap, d_info, d_scores, d_rows, d_ids, S(stream)); return (int)FH_OK; });
+}
+int fh_debug_pairs_room(int room) { fh::pairs_debug_room(room); return 0; }
 
 // ---- threshold search: the rule on the host (range_plan.h), the same rule on the scan's accumulators (gallery_range.hip)
 static_assert(FH_RANGE_MAX_CAP == fh::kRangeMaxCap && FH_TAG_ALL == fh::kRangeTagAll, "facehip.h mirrors range_plan.h");

@@ -439,6 +439,12 @@ class Gallery {
     // hist [2][2048] and nan [2] (may be null), both device, both overwritten.  Needs a labelled gallery unless empty (the caller
     // checks).  Asynchronous; the scratch (the histogram the workgroups flush into) lives in the handle and is cleared on s at every call.
     void pair_hist_dev(unsigned long long* hist, unsigned long long* nan, hipStream_t s);
+    // The pair audit (gallery_cluster.hip, gallery_pairs.hip; the rule: pairs_plan.h): info [4] = {count, nan, returned, complete};
+    // out_score [cap], out_rows / out_ids [cap][2] — each may be null — = the first `returned` selected pairs, most extreme first,
+    // (-1, -1, -1) behind them; positions are 0-based.  cls, side, thr and cap are checked by the caller, as is the labelled state (a
+    // class other than "any" and out_ids need ids unless the gallery is empty).  Asynchronous; the scratch (counters by rank, the cut,
+    // the slot counter, gallery_pairs_room(cap) candidates of 16 bytes) lives in the handle and its head is cleared on s at every call.
+    void pairs_dev(int cls, int side, float thr, int cap, unsigned long long* info, float* out_score, int* out_rows, int* out_ids, hipStream_t s);
     // replaces every row's id by position (host or device list, checked by the caller: none negative); synchronous
     void set_ids(const int* ids, bool device_src);
     bool labelled() const { return ids_.live; }                  // meaningful while size() > 0; an empty gallery takes either kind
@@ -490,6 +496,7 @@ class Gallery {
     DevBuf qpack_, ps_, pi_, pd_, best_i_, seed_s_, seed_i_, seed_d_;    // packed queries; part / seed lists of the fp32 scan (pd_, seed_d_: id planes)
     DevBuf cl_deg_, cl_parent_, cl_best_;                        // cluster_dev: degree, union-find parent, best core neighbour per row
     DevBuf cl_hist_;                                             // pair_hist_dev: the histogram the workgroups flush into
+    DevBuf cl_pairs_;                                            // pairs_dev: counters by rank, cut, slot counter, candidates
     DevBuf rg_hits_, rg_units_;                                  // range_dev: hit bitmap [32-row block][query], hits per (8192 rows, query)
     DevBuf dp_bmax_, dp_bmax_t_, dp_chosen_, dp_cand_;           // topk_deep_dev: best eligible score [32-row block][query] and [query][block]; chosen blocks [query][k]; their rows' scores [query][k][32]
     // F16_RERANK state: [max|g|, max|g^|, max|g - g^| (float bits), non-finite / > 65504 flag] on the device and its host copy,

@@ -32,6 +32,18 @@
 //             counters are flushed to the scratch histogram with 64-bit global atomics.
 //   write-out the caller's hist [2][2048] and nan [2] (may be null) are overwritten from the scratch.
 //
+// fh_gallery_pairs_dev (the rule: pairs_plan.h) is the pair pass twice more — clear the scratch, count pass, cut, collect pass, select
+// (the cut and the select kernel: gallery_pairs.hip):
+//   count     the histogram epilogue with the selection filter in front: a live pair of the class on the asked side of the threshold is
+//             ONE LDS atomicAdd into the workgroup's histogram BY RANK (pairs_rank: bin 2047 - b for "above", b for "not above"), a
+//             NaN-scored pair of the class one into the NaN counter; flushed as the histogram pass flushes.  Row ids come by shuffle as
+//             above; with class "any" no id is read at all (an unlabelled gallery has none).
+//   collect   the cut kernel left the last rank to collect in the scratch (-1: nothing, the workgroups leave at once).  A selected pair
+//             of rank <= cut is appended to the candidate buffer {score, i, j, -}: per accumulator position a wave takes __ballot of the
+//             hit predicate, its first hit lane adds __popcll of it to the ONE device-scope counter, and lane l stores at
+//             base + the hits below l.  By the cut rule the counter never exceeds `room`; the store is bounded by room all the same.
+//             One 16-byte vector store per candidate.  The buffer is read by a later launch (the select kernel): plain loads there.
+//
 // Memory model (MI355X: eight XCDs whose L2s are not coherent with each other, and a vector L1 that another CU's stores never refresh):
 // inside the link kernel EVERY read of parent[] is an agent-scope relaxed atomic load (served by L2, never by a stale L1 line) and
 // every write is an atomic RMW (atomicCAS; atomicMin for the path halving).  A find that kept seeing a stale "I am a root" would fail
@@ -45,6 +57,7 @@
 
 #include "gallery_scan.h"
 #include "kernels.h"
+#include "pairs_plan.h"
 #include "roc_plan.h"
 
 namespace fh {
@@ -64,11 +77,18 @@ struct ClusterArgs {
     const int* ids;                     // [G]
     unsigned long long* hist;           // [copies][kHistSlots]
     int copies;
+    // the two passes of the pair audit only (ids: null for class "any"; hist: kPairsSlots counters by rank; thr: the threshold)
+    int pcls, pside;
+    const int* cut;                     // the last rank to collect (written by the cut kernel, an earlier launch)
+    unsigned* cand_cnt;                 // the one slot counter
+    int4* cand;                         // [room] {score bits, i, j, 0}
+    unsigned room;
 };
 
 // one histogram: [2][kHistBins] bins (plane 0 genuine, plane 1 impostor), then the two NaN counters
 constexpr int kHistSlots = 2 * kHistBins + 2;
-enum { PAIR_DEGREE = 0, PAIR_LINK = 1, PAIR_HIST = 2 };
+enum { PAIR_DEGREE = 0, PAIR_LINK = 1, PAIR_HIST = 2, PAIR_COUNT = 3, PAIR_COLLECT = 4 };
+static_assert(kPairsSlots <= kHistSlots, "the count pass keeps its counters in the histogram pass's LDS");
 constexpr int kHistDefaultCopies = 1;     // measured: 1, 8, 64 and 512 copies time the same (profiles/gallery_hist.md)
 
 // the histogram pass's per-workgroup counters: 16 KB + 8 bytes beside the body's 32 KB, so two workgroups still share a CU's 160 KB
@@ -185,6 +205,58 @@ __device__ __forceinline__ void pair_hist_tile(const ClusterArgs& p, const v16f 
     }
 }
 
+// The two epilogues of the pair audit.  rank: pairs_rank of an accumulator that is a live pair of the class, -1 otherwise.
+__device__ __forceinline__ int pair_audit_rank(const ClusterArgs& p, float sc, bool live, int row_id, int col_id) {
+    return live && pairs_in_class(p.pcls, row_id, col_id) ? pairs_rank(sc, p.pside, p.thr) : -1;
+}
+
+// count: the histogram epilogue behind the selection filter; counters by rank, then the class's NaN counter
+__device__ __forceinline__ void pair_count_tile(const ClusterArgs& p, const v16f (&acc)[2], const PairCols& c, long wrow0, int fr, int fh2) {
+    unsigned* h = pair_hist_lds();
+    const long arow = wrow0 + fr;
+    const int my_id = p.ids && arow < p.G ? p.ids[arow] : 0;
+#pragma unroll
+    for (int e = 0; e < 16; ++e) {
+        const int r = gal_acc_row(e) + 4 * fh2;
+        const long row = wrow0 + r;
+        const int row_id = __shfl(my_id, r);
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int rank = pair_audit_rank(p, gal_score(acc[j][e]), c.ok[j] && row < c.col[j], row_id, c.id[j]);
+            if (rank >= 0) atomicAdd(&h[rank], 1u);
+            else if (rank == -2) atomicAdd(&h[kHistBins], 1u);
+        }
+    }
+}
+
+// collect: selected pairs of rank <= cut go to the candidate buffer; one atomic per wave and accumulator position that has a hit
+__device__ __forceinline__ void pair_collect_tile(const ClusterArgs& p, const v16f (&acc)[2], const PairCols& c, long wrow0, int lane, int cut) {
+    const int fr = lane & 31, fh2 = lane >> 5;
+    const long arow = wrow0 + fr;
+    const int my_id = p.ids && arow < p.G ? p.ids[arow] : 0;
+    const unsigned long long below = (1ull << lane) - 1ull;
+#pragma unroll
+    for (int e = 0; e < 16; ++e) {
+        const int r = gal_acc_row(e) + 4 * fh2;
+        const long row = wrow0 + r;
+        const int row_id = __shfl(my_id, r);
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const float sc = gal_score(acc[j][e]);
+            const int rank = pair_audit_rank(p, sc, c.ok[j] && row < c.col[j], row_id, c.id[j]);
+            const bool hit = rank >= 0 && rank <= cut;
+            const unsigned long long b = __ballot(hit);
+            if (b == 0ull) continue;                               // (wave-uniform)
+            const int first = __ffsll((long long)b) - 1;
+            unsigned base = 0u;
+            if (lane == first) base = atomicAdd(p.cand_cnt, (unsigned)__popcll(b));
+            base = (unsigned)__shfl((int)base, first);
+            const unsigned slot = base + (unsigned)__popcll(b & below);
+            if (hit && slot < p.room) p.cand[slot] = make_int4((int)__float_as_uint(sc), (int)row, (int)c.col[j], 0);
+        }
+    }
+}
+
 // setup -> per A tile: gal_tile_dot (gallery_scan.h: THE K loop, with the B chunks fetched from gallery rows) + the mode's epilogue -> flush
 template <int MODE>
 __device__ __forceinline__ void cluster_pair_body(const ClusterArgs& p) {
@@ -206,6 +278,15 @@ __device__ __forceinline__ void cluster_pair_body(const ClusterArgs& p) {
         unsigned* h = pair_hist_lds();
         for (int i = tid; i < kHistSlots; i += 256) h[i] = 0u;           // (the first tile's barriers come before the first add)
     }
+    if constexpr (MODE == PAIR_COUNT) {
+        unsigned* h = pair_hist_lds();
+        for (int i = tid; i < kPairsSlots; i += 256) h[i] = 0u;
+    }
+    int cut = -1;                                                        // collect: the last rank to take (workgroup-uniform)
+    if constexpr (MODE == PAIR_COLLECT) {
+        cut = *p.cut;
+        if (cut < 0) return;                                             // nothing to collect (before any barrier)
+    }
 
     // B loader: pass i fills rows i*16 + (tid >> 4), slot tid & 15 <- source 16-byte column (tid & 15) ^ (row & 15)
     const int qrow = tid >> 4;
@@ -226,6 +307,7 @@ __device__ __forceinline__ void cluster_pair_body(const ClusterArgs& p) {
         c.id[j] = 0;
         if constexpr (MODE == PAIR_LINK) c.core[j] = c.ok[j] && p.deg[c.col[j]] + 1 >= p.min_pts;
         if constexpr (MODE == PAIR_HIST) c.id[j] = c.ok[j] ? p.ids[c.col[j]] : 0;
+        if constexpr (MODE == PAIR_COUNT || MODE == PAIR_COLLECT) c.id[j] = p.ids && c.ok[j] ? p.ids[c.col[j]] : 0;
     }
 
     for (int rt = rt0; rt < rt1; ++rt) {
@@ -245,7 +327,18 @@ __device__ __forceinline__ void cluster_pair_body(const ClusterArgs& p) {
         const long wrow0 = m0 + wid * 32;                  // the wave's 32-row block
         if constexpr (MODE == PAIR_DEGREE) pair_degree_tile(p, acc, c, wrow0, lane, fh2);
         else if constexpr (MODE == PAIR_LINK) pair_link_tile(p, acc, c, wrow0, fr, fh2);
-        else pair_hist_tile(p, acc, c, wrow0, fr, fh2);
+        else if constexpr (MODE == PAIR_HIST) pair_hist_tile(p, acc, c, wrow0, fr, fh2);
+        else if constexpr (MODE == PAIR_COUNT) pair_count_tile(p, acc, c, wrow0, fr, fh2);
+        else pair_collect_tile(p, acc, c, wrow0, lane, cut);
+    }
+    if constexpr (MODE == PAIR_COUNT) {
+        // as the histogram pass below: a 32-bit counter holds a run's adds, non-zero counters go to the scratch with 64-bit atomics
+        unsigned* h = pair_hist_lds();
+        __syncthreads();
+        for (int i = tid; i < kPairsSlots; i += 256) {
+            const unsigned cnt = h[i];
+            if (cnt) atomicAdd(p.hist + i, (unsigned long long)cnt);
+        }
     }
     if constexpr (MODE == PAIR_HIST) {
         // A run of t tiles adds at most t * 128 * 64 = t * 8192 to one 32-bit counter; the launcher keeps t <= 2^18 (automatic runs are at
@@ -271,6 +364,8 @@ __device__ __forceinline__ void cluster_pair_body(const ClusterArgs& p) {
 __global__ __launch_bounds__(256, 2) void cluster_degree_kernel(const ClusterArgs p) { cluster_pair_body<PAIR_DEGREE>(p); }
 __global__ __launch_bounds__(256, 2) void cluster_link_kernel(const ClusterArgs p) { cluster_pair_body<PAIR_LINK>(p); }
 __global__ __launch_bounds__(256, 2) void cluster_hist_kernel(const ClusterArgs p) { cluster_pair_body<PAIR_HIST>(p); }
+__global__ __launch_bounds__(256, 2) void cluster_pairs_count_kernel(const ClusterArgs p) { cluster_pair_body<PAIR_COUNT>(p); }
+__global__ __launch_bounds__(256, 2) void cluster_pairs_collect_kernel(const ClusterArgs p) { cluster_pair_body<PAIR_COLLECT>(p); }
 
 // sums the privatised copies into the caller's buffers (both overwritten); d_nan may be null
 __global__ __launch_bounds__(256) void cluster_hist_reduce_kernel(const unsigned long long* __restrict__ part, int copies,
@@ -322,6 +417,7 @@ __global__ __launch_bounds__(256) void cluster_flatten_kernel(long G, int min_pt
 
 int g_cluster_tiles = 0;
 int g_hist_copies = 0;
+long g_pairs_room = 0;
 
 // the pair passes' grid: tiles, the run length (A tiles per workgroup) and the number of workgroups
 unsigned cluster_pair_grid(ClusterArgs& a, long G) {
@@ -348,6 +444,7 @@ unsigned cluster_pair_grid(ClusterArgs& a, long G) {
 
 void cluster_debug_tiles(int tiles_per_wg) { g_cluster_tiles = tiles_per_wg > 0 ? tiles_per_wg : 0; }
 void cluster_debug_hist_copies(int copies) { g_hist_copies = copies > 0 ? (copies > 4096 ? 4096 : copies) : 0; }
+void pairs_debug_room(long room) { g_pairs_room = room > 0 ? (room > (1L << 24) ? (1L << 24) : room) : 0; }
 
 void launch_gallery_cluster(const float* gal, long G, int dim, float thr, int min_pts, bool noise_self, int* deg, int* parent,
                             unsigned long long* best, int* labels, int* info, hipStream_t s) {
@@ -383,6 +480,35 @@ void launch_gallery_pair_hist(const float* gal, const int* ids, long G, int dim,
     FH_HIP(hipMemsetAsync(scratch, 0, gallery_pair_hist_scratch_bytes(), s));
     hipLaunchKernelGGL(cluster_hist_kernel, dim3(grid), dim3(256), 0, s, a);
     hipLaunchKernelGGL(cluster_hist_reduce_kernel, dim3((kHistSlots + 255) / 256), dim3(256), 0, s, scratch, a.copies, hist, nan);
+}
+
+// The pair audit.  scratch: kPairsHead 64-bit words — the counters by rank, the NaN counter, {cut, slot counter}, {returned, -} — then
+// the candidates; the head is cleared on s first.  At most `room` candidates are ever appended (the cut sees to it).
+long gallery_pairs_room(int cap) {
+    const long room = g_pairs_room > 0 ? g_pairs_room : kPairsRoom;
+    return room > cap ? room : cap;
+}
+size_t gallery_pairs_scratch_bytes(int cap) { return kPairsHead * sizeof(unsigned long long) + (size_t)gallery_pairs_room(cap) * sizeof(int4); }
+
+void launch_gallery_pairs(const float* gal, const int* ids, long G, int dim, int cls, int side, float thr, int cap,
+                          unsigned long long* scratch, unsigned long long* info, float* out_s, int* out_rows, int* out_ids, hipStream_t s) {
+    if (G <= 0) return;
+    if (dim % 64) throw std::runtime_error("gallery: dim must be a multiple of 64");
+    const long room = gallery_pairs_room(cap);
+    ClusterArgs a{};
+    a.gal = gal; a.zeros = conv_zero_line(); a.G = G; a.dim = dim; a.thr = thr;
+    a.ids = cls == kPairsAny ? nullptr : ids; a.hist = scratch; a.copies = 1;
+    a.pcls = cls; a.pside = side;
+    int* words = reinterpret_cast<int*>(scratch + kPairsSlots);
+    a.cut = words; a.cand_cnt = reinterpret_cast<unsigned*>(words + 1);
+    a.cand = reinterpret_cast<int4*>(scratch + kPairsHead); a.room = (unsigned)room;
+    const unsigned grid = cluster_pair_grid(a, G);
+    FH_HIP(hipMemsetAsync(scratch, 0, kPairsHead * sizeof(unsigned long long), s));
+    hipLaunchKernelGGL(cluster_pairs_count_kernel, dim3(grid), dim3(256), 0, s, a);
+    launch_pairs_cut(scratch, cap, room, info, s);
+    if (!out_s && !out_rows && !out_ids) return;                         // the count-only form
+    hipLaunchKernelGGL(cluster_pairs_collect_kernel, dim3(grid), dim3(256), 0, s, a);
+    launch_pairs_select(scratch, room, side, cap, ids, out_s, out_rows, out_ids, s);
 }
 
 }  // namespace fh

@@ -293,6 +293,21 @@ void Gallery::pair_hist_dev(unsigned long long* hist, unsigned long long* nan, h
     FH_HIP(hipGetLastError());
 }
 
+void Gallery::pairs_dev(int cls, int side, float thr, int cap, unsigned long long* info, float* out_score, int* out_rows, int* out_ids,
+                        hipStream_t s) {
+    if (dim_ % 64) throw std::runtime_error("gallery: dim must be a multiple of 64");
+    if (n_ == 0) {
+        launch_pairs_empty(cap, info, out_score, out_rows, out_ids, s);
+        FH_HIP(hipGetLastError());
+        return;
+    }
+    if (n_ > (long)INT_MAX) throw std::runtime_error("gallery: row positions must fit in 31 bits");
+    cl_pairs_.ensure(gallery_pairs_scratch_bytes(cap));
+    launch_gallery_pairs(rows_.as<float>(), ids_.live ? ids_.as<int>() : nullptr, n_, dim_, cls, side, thr, cap,
+                         cl_pairs_.as<unsigned long long>(), info, out_score, out_rows, out_ids, s);
+    FH_HIP(hipGetLastError());
+}
+
 void Gallery::set_ids(const int* ids, bool device_src) {
     if (n_ == 0) return;
     FH_HIP(hipDeviceSynchronize());                              // queued scans still read the ids that are about to change

@@ -401,6 +401,25 @@ void launch_gallery_pair_hist(const float* gal, const int* ids, long G, int dim,
                               unsigned long long* nan, hipStream_t s);
 size_t gallery_pair_hist_scratch_bytes();
 void cluster_debug_hist_copies(int copies);   // measurement hook: privatised histogram copies the workgroups flush into (0 = default)
+// The pair audit (fh_gallery_pairs_dev; the rule: pairs_plan.h): the pair pass with the count epilogue, the cut, the pair pass with the
+// collect epilogue, the select kernel — all on s.  info [4] = {count, nan, returned, complete}; out_s [cap], out_rows / out_ids [cap][2]
+// (each may be null; out_ids needs ids) = the first `returned` pairs of the ordered list, (-1.0f, -1, -1) behind them.  ids may be null
+// for class "any".  scratch holds gallery_pairs_scratch_bytes(cap); its head is cleared on s first.  G <= 0 launches nothing.
+constexpr int kPairsSlots = 2048 + 1;         // 64-bit words of the scratch: selected pairs by rank, then the class's NaN-scored pairs
+constexpr int kPairsHead = kPairsSlots + 3;   // ... {int cut, unsigned slot counter}, {returned}, one word of padding: candidates 16-byte aligned
+constexpr long kPairsRoom = 65536;            // candidates held at most (16 bytes each)
+void launch_gallery_pairs(const float* gal, const int* ids, long G, int dim, int cls, int side, float thr, int cap,
+                          unsigned long long* scratch, unsigned long long* info, float* out_s, int* out_rows, int* out_ids, hipStream_t s);
+long gallery_pairs_room(int cap);             // max(the room in force, cap)
+size_t gallery_pairs_scratch_bytes(int cap);
+void pairs_debug_room(long room);             // test hook: the candidate room (0 = kPairsRoom)
+// gallery_pairs.hip — the one-workgroup kernels of the audit.  cut: pairs_cut over the scratch's counters -> info, and the last rank to
+// collect + `returned` into the scratch.  select: the best `cap` candidates under pairs_before (bitonic sort in LDS, a batch at a time),
+// the three lists and their padding.  empty: info = {0, 0, 0, 1} and empty lists (an empty gallery).
+void launch_pairs_cut(unsigned long long* scratch, int cap, long room, unsigned long long* info, hipStream_t s);
+void launch_pairs_select(const unsigned long long* scratch, long room, int side, int cap, const int* ids, float* out_s, int* out_rows,
+                         int* out_ids, hipStream_t s);
+void launch_pairs_empty(int cap, unsigned long long* info, float* out_s, int* out_rows, int* out_ids, hipStream_t s);
 
 // gallery_f16.hip — the opt-in F16_RERANK scan (fh_gallery_set_scan): an fp16 copy of the rows is scanned for the top GAL16_KC candidates
 // per query, the candidates are re-scored from the fp32 rows exactly as gallery_topk_kernel scores them, and a per-query certificate

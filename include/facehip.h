@@ -730,6 +730,59 @@ FH_API int fh_hist_bin(float score);
 FH_API int fh_roc_from_hist(const unsigned long long* hist, double max_far, fh_roc_point out[2]);
 FH_API int fh_gallery_pair_hist_dev(fh_gallery* g, unsigned long long* d_hist, unsigned long long* d_nan, void* stream);
 
+/* ---- the pair audit: WHICH pairs lie behind a threshold.  The histogram says how many impostor pairs a threshold accepts and how many
+ * genuine pairs it rejects; these calls list them.  Impostor pairs above the threshold are people enrolled twice under two ids, or label
+ * errors; genuine pairs at or below it are a wrong photo filed under a person, or a ruined template.  The flow: fh_gallery_pair_hist_dev
+ * -> fh_roc_from_hist -> the pairs -> fh_gallery_remove_ids / fh_gallery_set_ids / fh_gallery_fuse_ids.
+ *   pairs_from_scores   host only, no GPU, and the one place the rule is defined.  scores[n][n] row-major, taken as symmetric: only the
+ *               entries with i < j are read.  ids[n] or NULL.
+ *               class     a pair (i, j), i < j, is genuine iff ids[i] == ids[j]; cls = FH_PAIRS_GENUINE, FH_PAIRS_IMPOSTOR or
+ *                         FH_PAIRS_ANY.  With ids == NULL only FH_PAIRS_ANY is legal.
+ *               selected  the pair is in the class, its score is not a NaN, and it passes the side test in fp32: FH_PAIRS_ABOVE
+ *                         `s > threshold` (strict: the test of labelling, clustering and range search), FH_PAIRS_NOT_ABOVE
+ *                         `s <= threshold`.  A NaN-scored pair of the class is selected by neither side and counted in `nan`, so
+ *                         count(ABOVE) + count(NOT_ABOVE) + nan = the class's pairs at any threshold; and at threshold = b / 2048.0f,
+ *                         b in 1..2047, count(ABOVE) is the suffix sum A[b] of fh_gallery_pair_hist_dev's plane.
+ *               order     most extreme first.  ABOVE: score descending, then i ascending, then j ascending; NOT_ABOVE: score ascending,
+ *                         then i, then j.  Scores are compared as fp32 values (a mapped score is never -0).
+ *               the cut   bounds the memory and is part of the contract.  Selected pairs are binned by fh_hist_bin; bins are walked
+ *                         from the extreme end (2047 downward for ABOVE, 0 upward for NOT_ABOVE); cum(b) = the selected pairs in bins
+ *                         at least as extreme as b; want = min(cap, count); b* = the first bin with cum(b*) >= want.  cum(b*) <= room:
+ *                         returned = want, complete = 1.  Otherwise returned = cum of the bins strictly more extreme than b* (< cap),
+ *                         complete = 0.  Either way the list is EXACTLY the first `returned` entries of the full ordered list: nothing
+ *                         approximate is ever returned.  count == 0: returned = 0, complete = 1.
+ *               outputs   info[4] = {count, nan, returned, complete}; count is never clipped.  out_scores [cap], out_rows [cap][2]
+ *                         (positions i < j), out_ids [cap][2] (the two rows' ids; -1 with ids == NULL): any of them may be NULL.  Slots
+ *                         behind `returned` carry (-1.0f, -1, -1).
+ *               Returns `returned`.  FH_ERR_ARG, nothing written: n < 0, NULL scores with n > 0, NULL info, a NaN threshold, an unknown
+ *               cls or side, a class other than FH_PAIRS_ANY without ids, cap outside 1..FH_PAIRS_MAX_CAP, room < cap.  All indexing in
+ *               64 bits.
+ *   pairs_dev   exactly pairs_from_scores with room = max(FH_PAIRS_ROOM, cap) on s(i, j) = the fp32 mapped score the scan reports for
+ *               query = row i against row j (see fh_gallery_cluster_dev: the same pair pass with two more epilogues), over the fp32
+ *               rows whatever the scan mode.  Positions are 0-based: the index base, tags, and the scan and tag statistics play no
+ *               part.  d_info [4], d_scores [cap], d_rows [cap][2], d_ids [cap][2] are device buffers; any subset of the three lists
+ *               may be NULL (all three: counts only, one pair pass).  Asynchronous on `stream`; returns FH_OK.  Two pair passes — count
+ *               (per-bin counters of the selected pairs), then, after a one-workgroup cut, collect (the pairs in the bins the cut
+ *               admits, appended through one atomic counter) — and a one-workgroup select that sorts the candidates.  The order in
+ *               which candidates are appended depends on timing, the selection is under a total order: two calls with the same inputs
+ *               produce identical bytes.  FH_ERR_ARG before anything is launched: a NULL handle or d_info, a NaN threshold, a bad cls,
+ *               side or cap, dim % 64 != 0.  FH_ERR_STATE for a non-empty UNLABELLED gallery with a class other than FH_PAIRS_ANY or a
+ *               non-NULL d_ids.  An empty gallery writes {0, 0, 0, 1} to d_info and empty lists, and launches nothing else.  Scratch
+ *               lives in the handle, grows on demand and is cleared on `stream` by every call: 16 KB of counters, the cut, the counter
+ *               and 16 bytes per candidate (1 MB).  When complete == 0 the caller tightens the threshold to the last returned score
+ *               and calls again.
+ *   out of scope  pairs across two galleries or across shards; tag filtering; cap above 1024; any automatic re-run when complete == 0. */
+#define FH_PAIRS_MAX_CAP 1024
+#define FH_PAIRS_ROOM 65536
+enum fh_pairs_class { FH_PAIRS_GENUINE = 0, FH_PAIRS_IMPOSTOR = 1, FH_PAIRS_ANY = 2 };
+enum fh_pairs_side { FH_PAIRS_ABOVE = 0, FH_PAIRS_NOT_ABOVE = 1 };
+FH_API int fh_pairs_from_scores(const float* scores, int n, const int* ids /* or NULL */, int cls, int side, float threshold, int cap,
+                                long long room, unsigned long long* info, float* out_scores /* [cap] or NULL */,
+                                int* out_rows /* [cap][2] or NULL */, int* out_ids /* [cap][2] or NULL */);
+FH_API int fh_gallery_pairs_dev(fh_gallery* g, int cls, int side, float threshold, int cap, unsigned long long* d_info,
+                                float* d_scores /* [cap] or NULL */, int* d_rows /* [cap][2] or NULL */, int* d_ids /* [cap][2] or NULL */,
+                                void* stream);
+
 /* ---- watchlists: row tags and tag-filtered exact 1:N search.  One gallery serves several tenants, doors or lists: every row carries a
  * uint32 TAG (a bit set of up to 32 caller-defined groups), every query a uint32 MASK, and row r is ADMITTED for query q iff
  * (tag[r] & mask[q]) != 0.  The predicate sits inside the scan's admission test, so a tagged query is answered from its admitted rows
@@ -1079,6 +1132,10 @@ FH_API int fh_debug_cluster_tiles(int tiles_per_wg);
 /* Measurement hook of fh_gallery_pair_hist_dev: the number of privatised histogram copies its workgroups flush into (1..4096; 0 restores
  * the default, 1).  The result does not depend on it (scripts/gallery_hist_ab.py --copies). */
 FH_API int fh_debug_hist_copies(int copies);
+/* Test hook of fh_gallery_pairs_dev: the candidate room of the cut (FH_PAIRS_ROOM by default).  room > 0 replaces it, 0 restores the
+ * default; the value in force for a call is max(room, cap).  A small room makes a small gallery take the "boundary bin does not fit"
+ * branch of the cut. */
+FH_API int fh_debug_pairs_room(int room);
 /* Test / measurement hook of the tagged scans (gallery_tags.hip): 0 = every tile is multiplied, none is skipped; non-zero (the default)
  * = tiles without an admitted row for any of a workgroup's queries are skipped.  The answer is the same bits either way. */
 FH_API int fh_debug_tag_skip(int on);
