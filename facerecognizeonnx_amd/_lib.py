@@ -270,6 +270,9 @@ PROTOTYPES = {
     "fh_rec_set_wino_x3": (_i, [_vp, _i]),
     "fh_rec_get_wino_x3": (_i, [_vp]),
     "fh_rec_get_conv_x3": (_i, [_vp]),
+    "fh_rec_get_pw_x3": (_i, [_vp]),
+    "fh_det_set_x3": (_i, [_vp, _i]),
+    "fh_det_get_x3": (_i, [_vp]),
     "fh_rec_set_shortcut_fold": (_i, [_vp, _i]),
     "fh_rec_set_precision": (_i, [_vp, _i, C.POINTER(C.c_float)]),
     "fh_rec_get_precision": (_i, [_vp]),
@@ -294,6 +297,7 @@ PROTOTYPES = {
     "fh_resize_u8c3_dev": (_i, [_vp, _i, _i, _i, _vp, _i, _i, _i, _vp]),
     "fh_conv_forward_dev": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "fh_conv_forward_ex_dev": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _i, _i, _i, _vp]),
+    "fh_conv_forward_ep_dev": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "fh_conv_winograd_dev": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "fh_conv_winograd_ex_dev": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "fh_debug_pack_bf16x2_dev": (_i, [_vp, _vp, _ll]),

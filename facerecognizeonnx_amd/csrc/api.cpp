@@ -1801,6 +1801,16 @@ int fh_rec_set_wino_x3(fh_rec* r, int on) {
 }
 int fh_rec_get_wino_x3(fh_rec* r) { return r && r->rec.net().wino_x3() ? 1 : 0; }
 int fh_rec_get_conv_x3(fh_rec* r) { return r ? r->rec.net().conv_x3_layers() : 0; }
+int fh_rec_get_pw_x3(fh_rec* r) { return r ? r->rec.net().pw_x3_layers() : 0; }
+// the detector's 1x1 stride-1 convolutions: 1 = three-piece bf16 (conv_pw_x3_kernel where conv_pw_x3_bn / conv_pw_x3_pays admit the launch; the
+// default unless FACEHIP_DET_X3=0), 0 = the native f32 kernels everywhere.  Returns the number of layers that have the form (0 with on = 0), or
+// an error code.  Synchronous on first use (the split weights).
+int fh_det_set_x3(fh_det* d, int on) {
+    if (!d) return arg_error("null handle");
+    Owns owns(&d->det.net());
+    return guarded([&] { return d->det.net().set_pw_x3(on != 0, nullptr); });
+}
+int fh_det_get_x3(fh_det* d) { return d ? d->det.net().pw_x3_layers() : 0; }
 int fh_rec_set_wino_fusion(fh_rec* r, int on) { if (!r) return arg_error("null handle"); r->rec.net().fuse_wino = on != 0; return FH_OK; }
 // Opt-in precision mode of the recogniser, gated: the mode is only entered if, on a fixed pseudo-random batch of aligned crops, every
 // embedding it produces stays within 1 - cos < 1e-3 of the fp32 path's (north-star tolerance).  Otherwise the handle stays fp32.
@@ -2093,6 +2103,13 @@ int fh_debug_conv_plan(int what, const int* in, int n_in, long long* out, int n_
         out[0] = (long long)fh::SK_SLAB_FLOATS; out[1] = (long long)fh::SK_COUNTERS;
     } else if (what == 5 && need(4, 2) && in[0] >= 0 && in[1] > 0 && in[2] > 0 && in[3] > 0) {
         out[0] = fh::conv_x3_pays(in[0], in[1], in[2], in[3], knobs) ? 1 : 0; out[1] = fh::conv_x3_bn(in[2]);
+    } else if (what == 6 && need(11, 3) && shape_ok()) {
+        const fh::ConvGeom g = geom();
+        const int bn = fh::conv_pw_x3_bn(g, in[10], knobs);
+        out[0] = bn; out[1] = bn ? (g.M / 128) * ((g.Cout + bn - 1) / bn) : 0;
+        out[2] = bn && fh::conv_pw_x3_pays(out[1], g.Kpad, g.Cout, in[10], knobs) ? 1 : 0;
+    } else if (what == 7 && need(4, 1) && in[0] >= 0 && in[1] > 0 && in[2] > 0 && in[3] > 0) {
+        out[0] = fh::conv_pw_x3_pays(in[0], in[1], in[2], in[3], knobs) ? 1 : 0;
     } else {
         return arg_error("fh_debug_conv_plan: unknown question, wrong array lengths or a non-positive size");
     }
@@ -2105,11 +2122,21 @@ int fh_conv_forward_dev(const float* in, const float* wt, const float* bias, flo
 int fh_conv_forward_ex_dev(const float* in, const float* wt, const float* bias, float* out, int batch, int h, int w, int cin, int cout,
                            int ks, int stride, int kpad, int cfg, int precision, const float* sc_in, int sc_h, int sc_w, int sc_c, int sc_stride,
                            int cus, void* stream) {
-    if (!in || !wt || !out || batch <= 0 || (ks != 1 && ks != 3) || cin % 4 || cout <= 0 || stride <= 0 || cus < 0 ||
+    return fh_conv_forward_ep_dev(in, wt, bias, out, batch, h, w, cin, cout, ks, stride, kpad, cfg, precision, sc_in, sc_h, sc_w, sc_c, sc_stride, cus,
+                                  0, nullptr, stream);
+}
+int fh_conv_forward_ep_dev(const float* in, const float* wt, const float* bias, float* out, int batch, int h, int w, int cin, int cout,
+                           int ks, int stride, int kpad, int cfg, int precision, const float* sc_in, int sc_h, int sc_w, int sc_c, int sc_stride,
+                           int cus, int act, const float* res, void* stream) {
+    static const char* const no_pw_x3 = "fh_conv_forward_ex_dev: this 1x1 layer has no three-piece bf16 form (it needs stride 1, cin % 4 == 0, "
+                                        "cout % 4 == 0, kpad % 32 == 0, whole 128-row tiles and a tile per CU)";
+    const bool x3 = precision == FH_PREC_F32X3, pw3 = x3 && ks == 1;
+    if (pw3 && in && wt && out && batch > 0 && cin > 0 && cout > 0 && (cin % 4 || cout % 4 || stride != 1 || sc_in || kpad % 32 || kpad < cin))
+        return arg_error(no_pw_x3);
+    if (!in || !wt || !out || batch <= 0 || (ks != 1 && ks != 3) || cin % 4 || cout <= 0 || stride <= 0 || cus < 0 || (act != 0 && act != 1) ||
         (precision != FH_PREC_FP32 && precision != FH_PREC_F32X3) || (sc_in && (sc_h <= 0 || sc_w <= 0 || sc_c <= 0 || sc_stride <= 0)))
         return arg_error("fh_conv_forward_dev: bad argument");
-    const bool x3 = precision == FH_PREC_F32X3;
-    if (x3 && !fh::conv_x3_ok(cin, cout))
+    if (x3 && !pw3 && !fh::conv_x3_ok(cin, cout))
         return arg_error("fh_conv_forward_ex_dev: this layer has no three-piece bf16 form (it needs cin % 32 == 0 and cout % 64 == 0)");
     Owns owns(nullptr);                                                  // (no Net: the process-wide watchdog record)
     return guarded([&] {
@@ -2120,6 +2147,8 @@ int fh_conv_forward_ex_dev(const float* in, const float* wt, const float* bias, 
         a.Ho = (h + 2 * pad - ks) / stride + 1; a.Wo = (w + 2 * pad - ks) / stride + 1;
         a.Kpad = kpad;
         a.cus = cus;
+        a.act = act;
+        if (res) { a.res = res; a.res_mode = (int)fh::ResMode::SAME; }
         if (sc_in) {
             if ((a.Ho - 1) * sc_stride >= sc_h || (a.Wo - 1) * sc_stride >= sc_w) throw std::runtime_error("conv: the shortcut's input does not cover the output grid");
             a.sc_in = sc_in; a.sc_H = sc_h; a.sc_W = sc_w; a.sc_C = sc_c; a.sc_stride = sc_stride;
@@ -2135,8 +2164,12 @@ int fh_conv_forward_ex_dev(const float* in, const float* wt, const float* bias, 
             FH_HIP(hipStreamSynchronize(S(stream)));                      // (an earlier call's launch may still read w3)
             w3.ensure(fh::wino_x3_floats(rows, kpad) * sizeof(float));
             fh::launch_pack_x3(wt, w3.as<float>(), rows, kpad, S(stream), 1);
-            a.wt = w3.as<float>();
-            fh::launch_conv_x3(a, 0, S(stream));
+            if (pw3) {                           // (forced: conv_pw_x3_pays is the engine's question, the form's existence this call's)
+                if (!fh::launch_conv_pw_x3(a, w3.as<float>(), true, S(stream))) throw std::invalid_argument(no_pw_x3);
+            } else {
+                a.wt = w3.as<float>();
+                fh::launch_conv_x3(a, 0, S(stream));
+            }
             FH_HIP(hipGetLastError());
             FH_HIP(hipStreamSynchronize(S(stream)));
             return 0;

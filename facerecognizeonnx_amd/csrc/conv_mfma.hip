@@ -699,6 +699,63 @@ __global__ __launch_bounds__(256, OCC) void conv_pw_kernel(const ConvArgs p, con
 #endif
 }
 
+// conv_pw_x3_kernel — the same GEMM with its K loop on three bf16 pieces and six v_mfma_f32_32x32x16_bf16 per 16-deep step (gemm_tile.h,
+// "x3": fp32 products, 0.375 of the f32 instruction's matrix-pipe cycles).  The pixel operand stays the fp32 LDS image of conv_pw_kernel
+// (same swizzle, same zero line behind K, chosen by source address) and is split in registers by gemm_mma_x3; p.wt is the x3 image of the
+// [conv_wt_rows(Cout)][Kpad] weights (launch_pack_x3 with one frequency: [plane][chunk][row][4 slots]; rows behind Cout and columns behind
+// K are zero in all three planes because they are zero in the f32 image).  BN = 96 / 64 / 32 (conv_pw_x3_bn); the 32-row remainder of a
+// 96- or 32-wide plane is a half pass of the loader that waves 0 and 1 request.  LDS per workgroup: 68 / 56 / 44 KB.
+// Order of additions per output: chunks in K order, the two 16-deep steps of a chunk, the six products in gemm_tile.h's order.
+template <int BN, int OCC>
+__global__ __launch_bounds__(256, OCC) void conv_pw_x3_kernel(const ConvArgs p, const int tiles_n, const int chunks) {
+    constexpr int BM = GEMM_BM, TN = BN / 32;
+    __shared__ v4f lds[2][gemm_buf_slots_x3<BN>()];
+    const GemmLane l = gemm_lane();
+    const int tid = l.tid;
+    const int tile = xcd_tile(blockIdx.x, gridDim.x);
+    const int tile_n = tile % tiles_n, tile_m = tile / tiles_n;
+    const int m0 = tile_m * BM, n0 = tile_n * BN;
+    const int K = p.Cin;
+
+    GemmSrcX3 src = gemm_src_x3<BN>(lds, p.in, m0, K, p.wt, n0, (p.Cout + 127) / 128 * 128, chunks, l);   // (rows = conv_wt_rows(Cout))
+    const float* const zsrc = p.zeros + l.lqs() * 4;
+    int kleft = K - l.lqs() * 4;                                            // > 0: this lane's float4 of the current chunk lies inside a row
+    const bool b_half = l.wid < 2;                                          // (wave-uniform)
+    v16f acc[1][TN];
+#pragma unroll
+    for (int j = 0; j < TN; ++j)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) acc[0][j][e] = 0.f;
+
+    using EpVec = ConvEpVec<BN, 256>;
+    EpVec epv;
+    epv.fetch(p, n0, tid, true);
+
+    gemm_load_chunk_x3<BN>(src, 0, kleft > 0, zsrc, b_half);
+    kleft -= 32;
+    __syncthreads();
+    for (int kc = 0; kc < chunks; ++kc) {
+        if (kc + 1 < chunks) gemm_load_chunk_x3<BN>(src, (kc & 1) ^ 1, kleft > 0, zsrc, b_half);
+        gemm_mma_x3<TN>(acc[0], lds[kc & 1], l);
+        __syncthreads();
+        kleft -= 32;
+    }
+    float* const ep = reinterpret_cast<float*>(&lds[0][0]);
+    epv.park(ep, tid);
+    __syncthreads();
+    static_assert((EpVec::FLOATS + 4 * 32 * 36) * sizeof(float) <= sizeof(GemmLdsX3<BN>), "epilogue scratch");
+    conv_epilogue<BM, BN, 4, 1, EP_LINES | EP_QUADS>(p, acc, m0, n0, l.wid, 0, l.lane, -1, -1, ep, conv_ep_wants_lines(p) ? ep + EpVec::FLOATS : nullptr);
+}
+
+template <int BN, int OCC>
+static void launch_pw_x3_cfg(const ConvArgs& a, long M, hipStream_t s) {
+    const int tiles_n = (a.Cout + BN - 1) / BN;
+    KernelTimer& timer = KernelTimer::get();
+    timer.begin(s);
+    hipLaunchKernelGGL((conv_pw_x3_kernel<BN, OCC>), dim3((unsigned)((M / 128) * tiles_n)), dim3(256), 0, s, a, tiles_n, a.Kpad / 32);
+    timer.end(s, 11, a.t_flops, a.t_bytes);       // (booked where the f32 launch is, with the same f32-equivalent FLOPs)
+}
+
 template <int BN, int OCC>
 static void launch_pw_cfg(const ConvArgs& a, long M, hipStream_t s) {
     const int tiles_n = (a.Cout + BN - 1) / BN;
@@ -736,6 +793,32 @@ static bool launch_pw(ConvArgs a, hipStream_t s) {
     if (bn == 96) launch_pw_cfg<96, 2>(a, g.M, s);
     else if (bn == 64) launch_pw_cfg<64, 3>(a, g.M, s);
     else launch_pw_cfg<32, 4>(a, g.M, s);
+    return true;
+}
+
+// The three-piece bf16 form of a 1x1 stride-1 layer: wt3 = the x3 image of its [conv_wt_rows(Cout)][Kpad] weights (a.wt, the f32 image, is
+// what the launch falls back on).  true = launched on conv_pw_x3_kernel; false = the layer has no such form at this batch (conv_pw_x3_bn) or,
+// unless `force`, the form does not pay for the launch (conv_pw_x3_pays) — the caller then runs launch_conv.
+static void conv_check(const ConvArgs& a, long M);
+bool launch_conv_pw_x3(ConvArgs a, const float* wt3, bool force, hipStream_t s) {
+    const long M = (long)a.B * a.Ho * a.Wo;
+    if (M <= 0 || !wt3) return false;
+    const ConvGeom g = conv_geom(a);
+    const int cus = a.cus > 0 ? a.cus : conv_num_cus();
+    const int bn = conv_pw_x3_bn(g, cus, conv_knobs());
+    if (!bn) return false;
+    const int tiles_n = (a.Cout + bn - 1) / bn;
+    if (!force && !conv_pw_x3_pays((M / 128) * tiles_n, a.Kpad, a.Cout, cus, conv_knobs())) return false;
+    conv_check(a, M);
+    // (the kernel's epilogue forms and the rows its loader reads of the image: hold the predicate to them)
+    if (a.n_outs > 0 || (a.Cout & 3) || tiles_n * bn > conv_wt_rows(a.Cout))
+        throw std::logic_error("conv_pw_x3_bn admitted a layer conv_pw_x3_kernel has no form for");
+    a.wt = wt3;
+    a.zeros = conv_zero_line();
+    a.ep_direct = conv_knobs().ep_direct;
+    if (bn == 96) launch_pw_x3_cfg<96, 2>(a, M, s);
+    else if (bn == 64) launch_pw_x3_cfg<64, 2>(a, M, s);
+    else launch_pw_x3_cfg<32, 3>(a, M, s);
     return true;
 }
 

@@ -28,6 +28,8 @@ struct ConvKnobs {
     int ep_direct = 0;       // FACEHIP_EP_DIRECT: see ConvArgs::ep_direct
     int conv_x3 = 1;         // FACEHIP_CONV_X3: 0 = the folded-shortcut layers stay on the f32 MFMA even where the handle's x3 switch is on,
                              // 2 = x3 wherever the layer has the form, whatever conv_x3_pays would say (A / B timing)
+    int pw_x3 = 1;           // FACEHIP_PW_X3: the same three values for the 1x1 stride-1 layers (conv_pw_x3_pays)
+    int pw_x3_bn = 0;        // FACEHIP_PW_X3_BN: 64 = 64-wide x3 tiles where the rule would take 32-wide ones (A / B timing)
 };
 inline const ConvKnobs& conv_knobs() {
     static const ConvKnobs k = [] {
@@ -35,7 +37,7 @@ inline const ConvKnobs& conv_knobs() {
         auto env = [](const char* name, int& x) { if (const char* e = getenv(name)) x = atoi(e); };
         env("FACEHIP_SK_B_RATIO", v.sk_b_ratio); env("FACEHIP_SK_MIN_OWNER", v.sk_min_owner); env("FACEHIP_SK_MARGIN", v.sk_margin2);
         env("FACEHIP_TALL_TAIL_Q", v.tall_tail_q); env("FACEHIP_CONV_PW", v.conv_pw); env("FACEHIP_CONV_TALL", v.conv_tall);
-        env("FACEHIP_EP_DIRECT", v.ep_direct); env("FACEHIP_CONV_X3", v.conv_x3);
+        env("FACEHIP_EP_DIRECT", v.ep_direct); env("FACEHIP_CONV_X3", v.conv_x3); env("FACEHIP_PW_X3", v.pw_x3); env("FACEHIP_PW_X3_BN", v.pw_x3_bn);
         return v;
     }();
     return k;
@@ -91,6 +93,34 @@ inline int conv_pw_bn(const ConvGeom& g, int cus, const ConvKnobs& k) {
     if (cols(64) * 100 <= g.Cout * 107) bn = 64;
     if (cols(96) * 100 <= g.Cout * 107 && cols(96) <= cols(64)) bn = 96;
     return (g.M / 128) * (cols(bn) / bn) < (long)cus ? 0 : bn;
+}
+
+// conv_pw_x3_kernel (the same GEMM on three bf16 pieces): the tile width it runs the layer with, or 0 = no such form — never a form where
+// conv_pw_bn has none.  96 where the f32 kernel takes 96 (N = 288: three exact tiles; the padded columns then never exceed the weight
+// image's conv_wt_rows), 64 where 64-wide tiles pad <= 7 %, else the narrow width: 32 (N = 152: 160 columns) unless FACEHIP_PW_X3_BN = 64
+// asks for 64 (192 columns, two accumulator blocks per pixel split) for A / B timing.  At least one tile per CU, as conv_pw_bn.
+inline int conv_pw_x3_bn(const ConvGeom& g, int cus, const ConvKnobs& k) {
+    if (!conv_pw_bn(g, cus, k)) return 0;
+    auto cols = [&](int bn) { return (g.Cout + bn - 1) / bn * bn; };
+    int bn = k.pw_x3_bn == 64 ? 64 : 32;
+    if (cols(64) * 100 <= g.Cout * 107) bn = 64;
+    if (cols(96) * 100 <= g.Cout * 107 && cols(96) <= cols(64)) bn = 96;
+    return (g.M / 128) * (cols(bn) / bn) < (long)cus ? 0 : bn;
+}
+// Does the x3 form pay for a launch of `tiles` 128 x conv_pw_x3_bn tiles of depth Kpad on `cus` CUs?  FACEHIP_PW_X3: 0 = never (the 1x1s
+// stay on conv_pw_kernel with the handle's switch on), 2 = wherever the form exists (A / B timing), 1 = the measured rule below.
+// Measured on SCRFD det_500m's thirteen conv_pw launches at B = 64, 128, 256, f32 against x3 in three alternating runs on 256 CUs
+// (profiles/pw_x3.md; us at B = 128, min-max): 20x20x288 -> 288 84-89 -> 55-64, 20x20x152 -> 288 56-59 -> 41-43, 40x40x152 -> 152 112-114 ->
+// 90-93, 40x40x72 -> 152 92.1-92.5 -> 86.8-87.4 (three chunks: the smallest gain of a deep class, 6 %, still ten times the f32 side's
+// spread), 80x80x72 -> 16 79-80 -> 74, 40x40x152 -> 16 36.6-36.9 -> 35.7-36.2, 20x20x64 -> 64 15.4-15.6 -> 14.0-14.1; the same classes
+// gain at B = 64 and 256.  Two classes do not: one chunk (20x20x16 -> 64: 14.6-14.8 against 14.6-14.7) — so Kpad >= 64 — and a 16-channel
+// lateral with under two tiles per CU (20x20x288 -> 16, 400 half-empty 32-wide tiles at B = 128: 16.8 -> 17.3-17.7; at B = 256, 800 tiles,
+// 28.0-29.0 -> 26.7-27.0) — so Cout < 32 asks for two tiles per CU.  Monotone in `tiles` and in Kpad.
+constexpr int PW_X3_MIN_KPAD = 64;
+inline bool conv_pw_x3_pays(long tiles, int Kpad, int Cout, int cus, const ConvKnobs& k) {
+    if (!k.pw_x3 || Cout <= 0 || (Cout & 3) || Kpad <= 0 || Kpad % 32 || cus <= 0) return false;
+    if (k.pw_x3 == 2) return true;
+    return tiles >= (long)cus * (Cout < 32 ? 2 : 1) && Kpad >= PW_X3_MIN_KPAD;
 }
 
 // conv_tall_kernel's take-over of a 3x3 stride-1 pad-1 layer with Cin % 32 == 0 on a map up to 112 wide, for the 256x64 and 128x32

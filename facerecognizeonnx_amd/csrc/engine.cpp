@@ -456,7 +456,30 @@ int Net::set_wino_x3(bool on, hipStream_t s) {
         FH_HIP(hipStreamSynchronize(s));
     }
     conv_x3_ = on && conv_x3_n_ > 0;
+    set_pw_x3(on, s);
     return on ? layers : 0;
+}
+
+int Net::set_pw_x3(bool on, hipStream_t s) {
+    // the 1x1 stride-1 convolutions: one x3 image per layer of its [rows][Kpad] weights (which batches run on it: conv_pw_x3_bn / _pays)
+    size_t total = 0;
+    pw_x3_n_ = 0;
+    for (size_t i = 0; i < dev_.size(); ++i) {
+        const POp& op = plan_.ops[i];
+        DevOp& d = dev_[i];
+        d.pw_x3 = op.kind == OpKind::CONV && op.ks == 1 && op.stride == 1 && op.pad == 0 && op.Cin % 4 == 0 && op.Cout % 4 == 0 && op.outs.empty() &&
+                  d.Kpad % 32 == 0 && d.Kpad >= op.Cin && d.sc_src < 0 && !d.sc_dst;
+        if (d.pw_x3) { d.wt_pw_x3 = total; total += wino_x3_floats(conv_wt_rows(op.Cout), d.Kpad); ++pw_x3_n_; }
+    }
+    if (on && pw_x3_n_ > 0 && wpw_x3_.bytes < total * sizeof(float)) {     // split once, on the device; the f32 image stays (the switch needs it)
+        wpw_x3_.ensure(total * sizeof(float));
+        for (size_t i = 0; i < dev_.size(); ++i)
+            if (dev_[i].pw_x3)
+                launch_pack_x3(params_.as<float>() + dev_[i].wt, wpw_x3_.as<float>() + dev_[i].wt_pw_x3, conv_wt_rows(plan_.ops[i].Cout), dev_[i].Kpad, s, 1);
+        FH_HIP(hipStreamSynchronize(s));
+    }
+    pw_x3_ = on && pw_x3_n_ > 0;
+    return pw_x3_layers();
 }
 
 void Net::run(int batch, hipStream_t s, int first_op) {
@@ -581,6 +604,9 @@ void Net::run(int batch, hipStream_t s, int first_op) {
                                                                      cus > 0 ? cus : conv_num_cus(), conv_knobs())) {
                     a.wt = wsc_x3_.as<float>() + d.wt_sc_x3;
                     launch_conv_x3(a, cfg, s);
+                } else if (pw_x3_ && d.pw_x3 && force_cfg < 0 && launch_conv_pw_x3(a, wpw_x3_.as<float>() + d.wt_pw_x3, false, s)) {
+                    // (a 1x1 stride-1 layer on three bf16 pieces: the launcher asked conv_pw_x3_bn and conv_pw_x3_pays — geometry, batch, CUs and
+                    //  the switches only, so the same batch runs the same kernels)
                 } else {
                     launch_conv(a, cfg, s);
                 }
@@ -662,6 +688,12 @@ Detector::Detector(const std::string& onnx_path) : net_(onnx_path, 640, 640) {  
     // anything else: "Unexpected output shape format" -> zero faces (src/face_detector.cpp:326-328)
     cap_ = 1;
     while (cap_ < std::max(anchors_, 1)) cap_ <<= 1;
+    if (det_x3_default()) net_.set_pw_x3(true, nullptr);         // the 1x1 convolutions on three bf16 pieces (fh_det_set_x3; FACEHIP_DET_X3=0: native f32)
+}
+
+bool det_x3_default() {
+    static const int v = [] { const char* e = getenv("FACEHIP_DET_X3"); return e ? atoi(e) : 1; }();
+    return v != 0;
 }
 
 void Detector::reserve(int n, int rows, int cols) {

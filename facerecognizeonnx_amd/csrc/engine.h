@@ -72,6 +72,11 @@ class Net {
     // The same switch governs the direct convolutions with a folded shortcut (IResNet's stride-2 3x3 layers): their K loop on three bf16
     // pieces (conv_mfma.hip, X3) where conv_x3_pays says the launch gains.  Number of layers that have the form while the switch is on.
     int conv_x3_layers() const { return conv_x3_ ? conv_x3_n_ : 0; }
+    // ... and, with a switch of their own underneath, the 1x1 stride-1 convolutions (conv_pw_x3_kernel, where conv_pw_x3_bn / conv_pw_x3_pays
+    // admit the launch).  set_wino_x3 sets it too (MobileFaceNet's 1x1s ride on the recogniser's switch); the detector sets it alone
+    // (fh_det_set_x3, FACEHIP_DET_X3).  Returns / reports the number of layers that have the 1x1 form while it is on.
+    int set_pw_x3(bool on, hipStream_t s);
+    int pw_x3_layers() const { return pw_x3_ ? pw_x3_n_ : 0; }
     int cus = 0;                                          // CUs of the stream this net runs on when it is CU-masked (0 = all)
     int force_cfg = -1;                                   // tuning hook: conv tile config override
     bool sk_enable = true;                                // tuning hook: stream-K remainder wave
@@ -80,7 +85,8 @@ class Net {
     long long config_word() const {
         return (long long)fuse_stem | (long long)fuse_front << 1 | (long long)winograd << 2 | (long long)halo_conv << 3 |
                (long long)fold_shortcut << 4 | (long long)fuse_wino << 5 | (long long)bf16x2_ << 6 | (long long)sk_enable << 7 |
-               (long long)(cus & 0xffff) << 8 | (long long)((force_cfg + 1) & 0xff) << 24 | (long long)wino_x3_ << 32 | (long long)conv_x3_ << 33;
+               (long long)(cus & 0xffff) << 8 | (long long)((force_cfg + 1) & 0xff) << 24 | (long long)wino_x3_ << 32 | (long long)conv_x3_ << 33 |
+               (long long)pw_x3_ << 34;
     }
 
   private:
@@ -112,6 +118,8 @@ class Net {
         int Kpad_sc = 0;
         size_t wt_sc_x3 = 0;                                  // ... offset of that form's three-piece (x3) weight image in wsc_x3_
         bool sc_x3 = false;                                   // ... which exists (Cin % 32 == 0, Cout % 64 == 0)
+        size_t wt_pw_x3 = 0;                                  // 1x1 stride-1 convolution: offset of its three-piece (x3) weight image in wpw_x3_ ...
+        bool pw_x3 = false;                                   // ... which exists (plain CONV, Cin % 4 == 0, Cout % 4 == 0, Kpad % 32 == 0, one output)
         bool sc_dst = false;                                  // ... and the shortcut's side: skipped when its consumer folds it
         bool fuse_next = false;                               // Winograd op followed by another on the same small map: fused transform kernel
         bool fuse_feed_aff = false;                           //   the next conv sees out * s2 + t2 (its block's BatchNorm) instead of out
@@ -125,9 +133,9 @@ class Net {
     float* tensor_ptr(int t) const { return arena_.as<float>() + plan_.tensors[t].offset * (size_t)cap_; }
     Plan plan_;
     std::vector<DevOp> dev_;
-    DevBuf params_, arena_, partial_, wino_v_, wino_m_, w36_bf_, w36_x3_, wsc_x3_;
-    bool bf16x2_ = false, wino_x3_ = false, conv_x3_ = false;
-    int conv_x3_n_ = 0;
+    DevBuf params_, arena_, partial_, wino_v_, wino_m_, w36_bf_, w36_x3_, wsc_x3_, wpw_x3_;
+    bool bf16x2_ = false, wino_x3_ = false, conv_x3_ = false, pw_x3_ = false;
+    int conv_x3_n_ = 0, pw_x3_n_ = 0;
     size_t wino_maxc_ = 0;
     size_t wino_elems_ = 0;                                   // per image: 36 * tiles * max(Cin, Cout) of the largest Winograd op
     int cap_ = 0;
@@ -223,6 +231,8 @@ class TileTable {
 // of a tiled call, whose a.border applies.  counts of frames without views are 0.  sup: the NMS' flags, sized as a.keys.
 void postprocess_views(PostArgs a, int n_frames, const TileTable* tab, float nms_thr, int* sup, FaceRec* out, int max_out, int* counts,
                        hipStream_t s);
+
+bool det_x3_default();   // the detector's 1x1 convolutions on three bf16 pieces unless FACEHIP_DET_X3=0 (read once)
 
 class Detector {
   public:

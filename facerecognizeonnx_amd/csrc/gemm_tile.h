@@ -1,5 +1,5 @@
 // gemm_tile.h — the "lean GEMM" tile: ONE loader, ONE K-chunk body and ONE turn-around store, shared by wino_gemm_kernel,
-// wino_gemm_pers_kernel, wino_gemm_bf16x2_kernel, wino_gemm_x3_kernel (winograd.hip) and conv_pw_kernel (conv_mfma.hip); with it the vector typedefs, the
+// wino_gemm_pers_kernel, wino_gemm_bf16x2_kernel, wino_gemm_x3_kernel (winograd.hip), conv_pw_kernel and conv_pw_x3_kernel (conv_mfma.hip); with it the vector typedefs, the
 // LDS-DMA wrapper and the XCD-contiguous tile order every .hip file of the library uses.
 //
 // The tile: 128 rows of the "pixel" operand (V / the activations) x BN rows of the weight operand, both with contiguous rows of K
@@ -230,16 +230,24 @@ __device__ __forceinline__ GemmSrcX3 gemm_src_x3(GemmLdsX3<BN>& lds, const float
     return GemmSrcX3{A + (size_t)(m0 + l.lrow()) * lda + l.lqs() * 4, reinterpret_cast<const v4f*>(B3) + (size_t)n0 * 4 + l.tid, (size_t)32 * lda,
                      (size_t)chunks * brows * 4, (size_t)brows * 4, &lds[0][l.wid * 64], &lds[0][GEMM_BM * 8 + l.wid * 64]};
 }
+// a_live / a_dead: as gemm_load_chunk (conv_pw_x3_kernel's zero line behind K — by source address; a zero fp32 splits into three zero
+// pieces).  A plane moves in passes of 64 rows (256 threads x 16 bytes); BN % 64 == 32 leaves a half pass of 32 rows, 128 float4s, which the
+// waves with b_half set (the caller's wave-uniform wid < 2) request: 96-wide tiles are 18 wave requests of 1 KB per chunk, 32-wide ones 6.
 template <int BN>
-__device__ __forceinline__ void gemm_load_chunk_x3(GemmSrcX3& s, const int buf) {
+__device__ __forceinline__ void gemm_load_chunk_x3(GemmSrcX3& s, const int buf, const bool a_live = true, const float* const a_dead = nullptr,
+                                                   const bool b_half = false) {
     v4f* const dA = s.dA + buf * gemm_buf_slots_x3<BN>();
     v4f* const dB = s.dB + buf * gemm_buf_slots_x3<BN>();
 #pragma unroll
-    for (int i = 0; i < GEMM_BM / 32; ++i) lds_dma16(s.a + i * s.a32, dA + i * 32 * 8);
+    for (int i = 0; i < GEMM_BM / 32; ++i) lds_dma16(a_live ? s.a + i * s.a32 : a_dead, dA + i * 32 * 8);
 #pragma unroll
-    for (int p = 0; p < 3; ++p)
+    for (int p = 0; p < 3; ++p) {
 #pragma unroll
         for (int i = 0; i < BN / 64; ++i) lds_dma16(reinterpret_cast<const float*>(s.b + p * s.bplane + i * 256), dB + p * BN * 4 + i * 256);
+        if constexpr (BN % 64 != 0) {
+            if (b_half) lds_dma16(reinterpret_cast<const float*>(s.b + p * s.bplane + (BN / 64) * 256), dB + p * BN * 4 + (BN / 64) * 256);
+        }
+    }
     s.a += 32; s.b += s.bchunk;
 }
 template <int TN>

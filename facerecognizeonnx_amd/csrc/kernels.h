@@ -125,6 +125,10 @@ void launch_conv(const ConvArgs& a, int cfg, hipStream_t s);
 // form pays for a launch is conv_x3_pays (conv_plan.h).
 void launch_conv_x3(const ConvArgs& a, int tag, hipStream_t s);
 bool conv_x3_ok(int Cin, int Cout);
+// A 1x1 stride-1 layer on conv_pw_x3_kernel (conv_pw_kernel's GEMM with the x3 K loop): wt3 = launch_pack_x3(a.wt = the f32 image
+// [conv_wt_rows(Cout)][Kpad], ..., freqs = 1).  false = not launched: the layer has no such form at this batch (conv_pw_x3_bn, conv_plan.h)
+// or — unless force — the form does not pay for the launch (conv_pw_x3_pays); the caller then runs launch_conv.  Booked under tag 11.
+bool launch_conv_pw_x3(ConvArgs a, const float* wt3, bool force, hipStream_t s);
 void conv_workspace_init(float* ws);          // zero the counter words of a freshly allocated stream-K workspace
 void conv_workspace_reset_async(float* ws, hipStream_t s);   // the same, stream-ordered (after a reported hand-off time-out)
 // Stream-K watchdog.  An owner workgroup whose helpers never arrive gives up after a bounded wait and reports through a host-mapped

@@ -959,6 +959,17 @@ FH_API int fh_rec_get_wino_x3(fh_rec* r);
  * (fh_debug_conv_plan question 5) their K loop runs on the same three pieces and six products.  Number of layers of this handle that have
  * that form while the switch is on (0 while it is off). */
 FH_API int fh_rec_get_conv_x3(fh_rec* r);
+/* ... and the 1x1 stride-1 convolutions (all of MobileFaceNet's; IResNet has none): where the launch gains (fh_debug_conv_plan question 6)
+ * they run on conv_pw_x3_kernel, the plain GEMM on the same three pieces.  Number of layers of this handle that have that form while the
+ * switch is on (0 while it is off). */
+FH_API int fh_rec_get_pw_x3(fh_rec* r);
+/* The detector's own switch for the same form of its 1x1 stride-1 convolutions (SCRFD's 288 / 152 / 72-deep ones and the FPN laterals).
+ * on is the default (FACEHIP_DET_X3=0 in the environment makes off the default); off: the native f32 kernels, the bits of a build without
+ * the form.  Which launches take it depends on layer geometry, batch and CU count only (FACEHIP_PW_X3 = 0 / 2 in the environment: none /
+ * all that have the form).  fh_det_set_x3 returns the number of layers that have the form (0 for off), or < 0; synchronous the first
+ * time it is switched on.  fh_det_get_x3: that number while the switch is on, 0 while it is off. */
+FH_API int fh_det_set_x3(fh_det* d, int on);
+FH_API int fh_det_get_x3(fh_det* d);
 /* A handle whose stream is restricted to a subset of the CUs (hipExtStreamCreateWithCUMask, e.g. detector and
  * recogniser side by side on disjoint CU sets) should say how many it gets: it sizes the convolution kernels'
  * remainder round.  0 = the whole device (default). */
@@ -1064,10 +1075,19 @@ FH_API int fh_conv_forward_dev(const float* d_in, const float* d_wt_packed, cons
  * [batch][sc_h][sc_w][sc_c] of a 1x1 convolution of stride sc_stride on the same output grid, run as a tenth tap of the K loop: d_wt_packed
  * is then [fh_conv_wt_rows(cout)][9 cin + sc_c] with the shortcut's weights behind the 3x3 ones, kpad = 9 cin + sc_c, ksize = 3,
  * cin % 32 == 0, sc_c % 32 == 0.  cus > 0: the launcher plans the stream-K remainder as for a device of that many CUs (ConvArgs::cus), so
- * that small layers reach every role; 0 = the device's own count.  Synchronous for FH_PREC_F32X3. */
+ * that small layers reach every role; 0 = the device's own count.  Synchronous for FH_PREC_F32X3.
+ * ksize = 1, stride = 1 with FH_PREC_F32X3: conv_pw_x3_kernel (the 1x1 GEMM on three bf16 pieces; kpad % 32 == 0, kpad >= cin), refused
+ * with the same message where the layer has no such form: cin % 4 != 0, cout % 4 != 0, batch * h * w % 128 != 0 or fewer tiles than CUs
+ * (question 6 of fh_debug_conv_plan; pass a small `cus` for small layers).  Every other ksize = 1 layer is refused under FH_PREC_F32X3. */
 FH_API int fh_conv_forward_ex_dev(const float* d_in, const float* d_wt_packed, const float* d_bias, float* d_out, int batch,
                                   int h, int w, int cin, int cout, int ksize, int stride, int kpad, int cfg, int precision,
                                   const float* d_sc_in, int sc_h, int sc_w, int sc_c, int sc_stride, int cus, void* stream);
+/* The same with the epilogue's activation and residual: act = 0 none / 1 ReLU, d_res (may be NULL) = a tensor of the output's shape added
+ * after the activation.  fh_conv_forward_ex_dev is this call with act = 0 and no residual. */
+FH_API int fh_conv_forward_ep_dev(const float* d_in, const float* d_wt_packed, const float* d_bias, float* d_out, int batch,
+                                  int h, int w, int cin, int cout, int ksize, int stride, int kpad, int cfg, int precision,
+                                  const float* d_sc_in, int sc_h, int sc_w, int sc_c, int sc_stride, int cus, int act, const float* d_res,
+                                  void* stream);
 /* 3x3 stride-1 pad-1 convolution (+bias) in the Winograd F(4x4,3x3) form the deep layers use; w_ohwi = HOST weights
  * [cout][3*3][cin]; cin % 32 == 0, cout % 4 == 0.  Synchronous. */
 FH_API int fh_conv_winograd_dev(const float* d_in, const float* w_ohwi_host, const float* d_bias, float* d_out, int batch, int h, int w,
@@ -1119,7 +1139,10 @@ FH_API int fh_debug_streamk(int drop_publish, int timeout_ms);
  *   what 3  slabs per remainder tile: in = r0, r1, chunks per tile left to the helpers, q (4) -> out = min, max over r0 <= r < r1 (2)
  *   what 4  the workspace: in = nothing -> out = slab floats, counter words (2)
  *   what 5  the three-piece bf16 K loop of a direct convolution: in = 128-row tiles x column tiles of the x3 tile width, Kpad, Cout, CUs (4)
- *           -> out = 1 if the launch runs it (conv_x3_pays), x3 tile width 128 / 64 or 0 = Cout has no such form (2) */
+ *           -> out = 1 if the launch runs it (conv_x3_pays), x3 tile width 128 / 64 or 0 = Cout has no such form (2)
+ *   what 6  conv_pw_x3_kernel: in = the 11 of question 1 -> out = its tile width 96 / 64 / 32 or 0 = no such form at this batch
+ *           (conv_pw_x3_bn; never a form where question 1 answers 0), its tiles, 1 if the launch runs it with the handle's switch on (3)
+ *   what 7  conv_pw_x3_pays alone: in = tiles, Kpad, Cout, CUs (4) -> out = 1 if such a launch runs the x3 form (1) */
 FH_API int fh_debug_conv_plan(int what, const int* in, int n_in, long long* out, int n_out);
 /* Test hook of the multi-tile Winograd GEMM (winograd.hip wino_gemm_pers_kernel): launches with more tiles than resident workgroup
  * slots walk several tiles per workgroup; slots > 0 makes the launcher pretend the device has that many (rounded up to 8), so that small
