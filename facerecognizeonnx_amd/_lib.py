@@ -264,6 +264,17 @@ PROTOTYPES = {
     "fh_jpeg_reconstruct_batch_dev": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp]),
     "fh_jpeg_decode_batch": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp]),
     "fh_pipeline_run_files": (_i, [_vp, _vp, _vp, _vp, _i, _i, _f, _f, _i, _vp, _vp, _vp, _i, _vp]),
+    "fh_jpeg_quant_tables": (_i, [_i, _vp, _vp]),
+    "fh_jpeg_enc_desc": (_i, [_i, _i, _i, _i, _i, _vp]),
+    "fh_jpeg_enc_check": (_i, [_vp]),
+    "fh_jpeg_forward": (_i, [_vp, _vp, _i, _vp, C.c_size_t]),
+    "fh_jpeg_write": (_i, [_vp, _vp, _vp, C.c_size_t, _vp]),
+    "fh_jpeg_write_bound": (C.c_size_t, [_vp]),
+    "fh_imwrite_jpeg": (_i, [C.c_char_p, _vp, _i, _i, _i, _i, _i]),
+    "fh_jpegenc_create": (_vp, []),
+    "fh_jpegenc_destroy": (None, [_vp]),
+    "fh_jpeg_forward_batch_dev": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp]),
+    "fh_jpeg_encode_batch": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "fh_det_set_winograd": (_i, [_vp, _i]),
     "fh_rec_set_winograd": (_i, [_vp, _i]),
     "fh_rec_set_wino_fusion": (_i, [_vp, _i]),

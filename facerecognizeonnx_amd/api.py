@@ -631,6 +631,83 @@ class JpegDecoder:
         return out, status
 
 
+class JpegEncoder:
+    """fh_jpegenc: BGR pictures -> baseline JPEG files with colour conversion, chroma down-sampling, the forward DCT and quantisation on
+    the GPU and the Huffman coding on host threads; the coefficients are the ones libjpeg stores for the same pixels, bit for bit, and the
+    bytes are fh_jpeg_write(fh_jpeg_forward(...))'s."""
+
+    SUBSAMPLING = {"4:4:4": 0, "444": 0, 0: 0, "4:2:2": 1, "422": 1, 1: 1, "4:2:0": 2, "420": 2, 2: 2}
+
+    def __init__(self):
+        self.handle = _lib.lib().fh_jpegenc_create()
+        if not self.handle:
+            raise _lib.FaceHipError(f"fh_jpegenc_create failed: {_lib.last_error()}")
+
+    def __del__(self):
+        h, self.handle = getattr(self, "handle", None), None
+        if h:
+            _lib.lib().fh_jpegenc_destroy(h)
+
+    def encode_dev(self, frames, quality: int = 95, subsampling="4:2:0", threads: int = 0, stream: int = 0):
+        """fh_jpeg_encode_batch: frames = DEVICE pictures as frame_array takes them ((ptr, rows, cols[, step]) or None).  Blocking.
+        Returns a list of bytes, None for an empty frame."""
+        arr = frame_array(frames)
+        n = _frame_count(arr)
+        if n == 0:
+            return []
+        blobs = (_lib.FhBlob * n)()
+        check(_lib.lib().fh_jpeg_encode_batch(self.handle, arr, n, int(quality), self.SUBSAMPLING[subsampling], int(threads), blobs, stream),
+              "fh_jpeg_encode_batch")
+        return [C.string_at(b.bytes, b.n) if b.bytes else None for b in blobs]
+
+    def encode(self, frames, quality: int = 95, subsampling="4:2:0", threads: int = 0):
+        """encode_dev on HOST pictures (uint8[rows, cols, 3] BGR arrays; None or an empty array = an empty frame), uploaded first."""
+        import torch
+        imgs = [_img(f) for f in frames]
+        keep = [None if a is None else torch.from_numpy(np.ascontiguousarray(a)).cuda() for a in imgs]
+        torch.cuda.synchronize()
+        out = self.encode_dev([None if t is None else (t.data_ptr(), t.shape[0], t.shape[1]) for t in keep], quality, subsampling, threads)
+        del keep
+        return out
+
+
+def imwrite(path: str, image, quality: int = 95, subsampling="4:2:0") -> bool:
+    """cv::imwrite(path.jpg, image): the host encoder (fh_imwrite_jpeg).  False when the file cannot be written."""
+    a = _img(image)
+    if a is None:
+        return False
+    return _lib.lib().fh_imwrite_jpeg(str(path).encode(), a.ctypes.data, a.shape[0], a.shape[1], a.strides[0], int(quality),
+                                      JpegEncoder.SUBSAMPLING[subsampling]) == 0
+
+
+def face_chips(rec: FaceRecognizer, image, faces, quality: int = 95, subsampling="4:2:0", encoder: Optional[JpegEncoder] = None):
+    """The aligned crop of every face of one HOST picture as a JPEG file: fh_rec_align_dev -> fh_jpeg_encode_batch, pixels and
+    coefficients never leave the device.  faces = FACE_DTYPE records (FaceDetector.detect_records).  Returns (list of bytes — None for a
+    face whose crop is empty —, the crops uint8[n, H, W, 3] as the device made them)."""
+    import torch
+    a = _img(image)
+    faces = np.ascontiguousarray(faces, FACE_DTYPE)
+    n = len(faces)
+    h, w = C.c_int(0), C.c_int(0)
+    check(_lib.lib().fh_rec_input_size(rec.handle, C.byref(h), C.byref(w)), "fh_rec_input_size")
+    if a is None or n == 0:
+        return [], np.zeros((0, h.value, w.value, 3), np.uint8)
+    img = torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    d_faces = torch.from_numpy(faces.view(np.uint8).reshape(-1).copy()).cuda()
+    d_fo = torch.zeros(n, dtype=torch.int32, device="cuda")
+    crops = torch.zeros((n, h.value, w.value, 3), dtype=torch.uint8, device="cuda")
+    ok = torch.zeros(n, dtype=torch.int32, device="cuda")
+    torch.cuda.synchronize()
+    check(_lib.lib().fh_rec_align_dev(rec.handle, img.data_ptr(), a.shape[0], a.shape[1], a.shape[1] * 3, 0, d_faces.data_ptr(), d_fo.data_ptr(),
+                                      n, crops.data_ptr(), ok.data_ptr(), 0), "fh_rec_align_dev")
+    rec.sync()
+    live = ok.cpu().numpy() != 0
+    enc = encoder if encoder is not None else JpegEncoder()
+    one = h.value * w.value * 3
+    files = enc.encode_dev([(crops.data_ptr() + i * one, h.value, w.value) if live[i] else None for i in range(n)], quality, subsampling)
+    return files, crops.cpu().numpy()
+
+
 def pipeline_files(det: FaceDetector, rec: FaceRecognizer, files, faces_per_frame: int = 1, scoreThreshold: float = 0.5,
                    nmsThreshold: float = 0.4, cap: Optional[int] = None, threads: int = 0, decoder: Optional[JpegDecoder] = None):
     """pipeline_images from FILES (paths or bytes): JPEGs are entropy-decoded on `threads` host threads and reconstructed on the GPU

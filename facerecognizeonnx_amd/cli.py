@@ -1,6 +1,6 @@
 """Text-mode counterpart of the reference's demo executable (reference src/main.cpp:264-319):
 
-    python -m facerecognizeonnx_amd.cli detect  <image>            [--det det.onnx] [--tile N --overlap M [--border B]]
+    python -m facerecognizeonnx_amd.cli detect  <image>            [--det det.onnx] [--tile N --overlap M [--border B]] [--chips DIR [--rec rec.onnx]]
     python -m facerecognizeonnx_amd.cli compare <image1> <image2>  [--det det.onnx] [--rec rec.onnx] [--device-jpeg]
     python -m facerecognizeonnx_amd.cli simple  <image1> <image2>  [--rec rec.onnx]
 
@@ -9,6 +9,9 @@ faces[0] of each image, extractFeature, compareFaces, threshold 0.6 — but boxe
 are printed instead of drawn (no GUI, no webcam).  Images are read by the library's own cv::imread replacement
 (fh_imread: JPEG / PNG / BMP / PPM -> BGR u8) or from `.npy` arrays of shape [rows, cols, 3] (BGR u8).
 `detect --tile N` runs the tiled detection of large frames (whole frame + overlapping N x N tiles, one merged NMS; facehip.h).
+`detect --chips DIR` also writes every detected face's aligned crop as DIR/<image>_<k>.jpg: the recogniser's alignment
+(fh_rec_align_dev, so the recogniser model is loaded too) and the JPEG encoder's forward path run on the GPU, the Huffman coding on host
+threads (fh_jpeg_encode_batch).
 `compare --device-jpeg` reads both files through fh_pipeline_run_files: JPEGs are entropy-decoded on host threads and reconstructed on the
 GPU (the same pixels), then detected and embedded in one call; without the flag nothing changes.
 Model paths default to the reference's (models/det_500m.onnx, models/w600k_r50.onnx, main.cpp:269-270).
@@ -16,6 +19,7 @@ Model paths default to the reference's (models/det_500m.onnx, models/w600k_r50.o
 from __future__ import annotations
 
 import argparse
+import os
 import sys
 
 import numpy as np
@@ -64,13 +68,18 @@ def main(argv=None) -> int:
     ap.add_argument("--tile", type=int, default=0, help="detect: tile side in pixels (0 = plain detection)")
     ap.add_argument("--overlap", type=int, default=0, help="detect --tile: overlap of neighbouring tiles in pixels")
     ap.add_argument("--border", type=int, default=2, help="detect --tile: drop boxes within this many pixels of an interior tile edge (< 0: off)")
+    ap.add_argument("--chips", default=None, metavar="DIR", help="detect: write every face's aligned crop as DIR/<image>_<k>.jpg")
+    ap.add_argument("--chip-quality", type=int, default=95, help="detect --chips: JPEG quality")
     ap.add_argument("--device-jpeg", action="store_true", help="compare: decode the files through fh_pipeline_run_files (JPEG reconstruction on the GPU)")
     a = ap.parse_args(argv)
     det, rec = FaceDetector(), FaceRecognizer()
     if a.mode != "simple" and not det.loadModel(a.det):
         print("Failed to load face detector model", file=sys.stderr)           # main.cpp:274-278
         return -1
-    if a.mode != "detect" and not rec.loadModel(a.rec):
+    if a.chips is not None and a.mode != "detect":
+        print("--chips applies to detect", file=sys.stderr)
+        return -1
+    if (a.mode != "detect" or a.chips is not None) and not rec.loadModel(a.rec):
         print("Failed to load face recognizer model", file=sys.stderr)         # main.cpp:280-284
         return -1
     if a.device_jpeg:
@@ -92,6 +101,17 @@ def main(argv=None) -> int:
         print(f"Detected {len(faces)} faces")
         for i, f in enumerate(faces):
             print(f"Face {i}: box={f.box} score={f.score:.4f} landmarks={np.round(f.landmarks, 1).tolist()}")
+        if a.chips is not None and faces:
+            os.makedirs(a.chips, exist_ok=True)
+            files, _ = api.face_chips(rec, imgs[0], np.concatenate([f.to_record() for f in faces]), quality=a.chip_quality)
+            stem = os.path.splitext(os.path.basename(a.images[0]))[0]
+            for k, data in enumerate(files):
+                if data is None:
+                    continue
+                path = os.path.join(a.chips, f"{stem}_{k}.jpg")
+                with open(path, "wb") as fp:
+                    fp.write(data)
+                print(f"Chip {k}: {path} ({len(data)} bytes)")
         return 0
     if len(imgs) < 2:
         print("need two images", file=sys.stderr)

@@ -19,6 +19,7 @@
 #include "engine.h"
 #include "group_ids.h"
 #include "jpeg_dev.h"
+#include "jpeg_enc.h"
 #include "track_plan.h"
 
 static_assert(sizeof(fh_face) == 60 && sizeof(fh::FaceRec) == 60, "FaceBox mirror must stay 60 bytes");
@@ -1023,6 +1024,119 @@ int fh_pipeline_run_files(fh_det* d, fh_rec* r, fh_jpegdec* dec, const fh_blob* 
         }
         return total;
     });
+}
+
+// ---------------------------------------------------------------------------------- JPEG out: device forward path, host Huffman coding
+struct fh_jpegenc {
+    fh::JpegEnc dev;
+    fh::DevBuf d_coef;                   // fh_jpeg_encode_batch: the coefficients of every frame ...
+    PinnedBuf h_coef;                    // ... and where the one device-to-host copy lands
+    std::vector<unsigned char> bytes[16];   // the byte arena: per host thread, the files it wrote, back to back
+};
+namespace {
+// null, or why fh_jpeg_forward_batch_dev refuses the call (fh_jpeg_enc_check's complaint is already in g_err then: "")
+const char* bad_enc_batch(const fh_jpeg_desc* descs, int n, const fh_frame* frames, const int16_t* d_coef, const long long* coef_base) {
+    if (!descs || !d_coef || !coef_base || !frames) return "null argument";
+    if (n <= 0 || n > 4096) return "need 1 <= n <= 4096 images";
+    if (reinterpret_cast<uintptr_t>(d_coef) & 1) return "d_coef must be 2-byte aligned";
+    for (int i = 0; i < n; ++i) {
+        if (!frames[i].bgr) continue;
+        if (fh_jpeg_enc_check(&descs[i]) != 0) return "";
+        if (coef_base[i] < 0) return "a negative coef_base";
+        if (frames[i].rows != descs[i].rows || frames[i].cols != descs[i].cols) return "a frame's rows / cols differ from its descriptor's";
+        if ((long long)frames[i].step < (long long)frames[i].cols * 3) return "a frame's step is smaller than cols * 3";
+    }
+    return nullptr;
+}
+// fh_jpeg_encode_batch's body (arguments checked): returns the number of files written
+int jpeg_encode_batch(fh_jpegenc* enc, const fh_frame* frames, int n, int quality, int subsampling, int threads, fh_blob* files_out, hipStream_t s) {
+    threads = threads <= 0 ? std::min(16, n) : std::min(threads, 16);
+    std::vector<fh_jpeg_desc> descs((size_t)n);
+    std::vector<long long> base((size_t)n, 0);
+    std::vector<fh_frame> live((size_t)n);
+    std::vector<int> order;                                                   // the live frames
+    size_t coef_elems = 0;
+    for (int i = 0; i < n; ++i) {
+        files_out[i] = fh_blob{nullptr, 0};
+        live[(size_t)i] = frames[i];
+        if (!(frames[i].bgr && frames[i].rows > 0 && frames[i].cols > 0)) { live[(size_t)i] = fh_frame{nullptr, 0, 0, 0}; continue; }
+        if (fh_jpeg_enc_desc(frames[i].cols, frames[i].rows, 0, subsampling, quality, &descs[(size_t)i]) != 0) throw std::runtime_error(g_err);
+        base[(size_t)i] = (long long)coef_elems;
+        coef_elems += (size_t)descs[(size_t)i].coef_count;                    // a multiple of 64: every image starts 128-byte aligned
+        order.push_back(i);
+    }
+    if (order.empty()) return 0;
+    enc->d_coef.ensure(coef_elems * sizeof(int16_t));
+    enc->h_coef.ensure(coef_elems * sizeof(int16_t));
+    enc->dev.forward(descs.data(), n, FI(live.data()), enc->d_coef.as<int16_t>(), base.data(), s);
+    FH_HIP(hipMemcpyAsync(enc->h_coef.p, enc->d_coef.p, coef_elems * sizeof(int16_t), hipMemcpyDeviceToHost, s));
+    FH_HIP(hipStreamSynchronize(s));
+    // one file per task; a thread appends its files to its own buffer (which may move as it grows: offsets now, pointers after the join)
+    struct Where { int thread = -1; size_t off = 0, size = 0; };
+    std::vector<Where> where((size_t)n);
+    const int16_t* const coef = static_cast<const int16_t*>(enc->h_coef.p);
+    const int m = (int)order.size();
+    std::atomic<int> next{0};
+    std::atomic<bool> failed{false};
+    auto work = [&](int t) {
+        std::vector<unsigned char>& buf = enc->bytes[t];
+        size_t used = 0;
+        for (int k; (k = next.fetch_add(1)) < m;) {
+            const int i = order[(size_t)k];
+            const size_t bound = fh_jpeg_write_bound(&descs[(size_t)i]);
+            size_t written = 0;
+            try {
+                if (buf.size() < used + bound) buf.resize(std::max(used + bound, buf.size() * 2));
+            } catch (...) { failed = true; continue; }
+            if (fh_jpeg_write(&descs[(size_t)i], coef + base[(size_t)i], buf.data() + used, bound, &written) != 0) { failed = true; continue; }
+            where[(size_t)i] = Where{t, used, written};
+            used += written;
+        }
+    };
+    {
+        std::vector<std::thread> pool;
+        try {
+            for (int t = 1; t < threads; ++t) pool.emplace_back(work, t);
+        } catch (...) {                                                       // no more threads to be had: the ones that started finish the job
+        }
+        work(0);
+        for (std::thread& t : pool) t.join();
+    }
+    if (failed) throw std::runtime_error("fh_jpeg_encode_batch: a file could not be written (out of memory, or coefficients without a baseline code)");
+    for (int i : order) files_out[i] = fh_blob{enc->bytes[where[(size_t)i].thread].data() + where[(size_t)i].off, where[(size_t)i].size};
+    return m;
+}
+}  // namespace
+
+fh_jpegenc* fh_jpegenc_create(void) {
+    fh_jpegenc* h = nullptr;
+    const int rc = guarded([&] { h = new fh_jpegenc(); return 0; });
+    return rc == 0 ? h : nullptr;
+}
+void fh_jpegenc_destroy(fh_jpegenc* enc) { delete enc; }
+
+int fh_jpeg_forward_batch_dev(fh_jpegenc* enc, const fh_jpeg_desc* descs, int n, const fh_frame* frames, int16_t* d_coef, const long long* coef_base,
+                              void* stream) {
+    if (!enc) return arg_error("fh_jpeg_forward_batch_dev: null handle");
+    if (const char* bad = bad_enc_batch(descs, n, frames, d_coef, coef_base)) {
+        if (*bad) g_err = std::string("fh_jpeg_forward_batch_dev: ") + bad;
+        return FH_ERR_ARG;
+    }
+    return guarded([&] { enc->dev.forward(descs, n, FI(frames), d_coef, coef_base, S(stream)); return n; });
+}
+
+int fh_jpeg_encode_batch(fh_jpegenc* enc, const fh_frame* frames, int n, int quality, int subsampling, int threads, fh_blob* files_out,
+                         void* stream) {
+    if (!enc || !frames || !files_out) return arg_error("fh_jpeg_encode_batch: null argument");
+    if (n <= 0 || n > 4096) return arg_error("fh_jpeg_encode_batch: need 1 <= n <= 4096 frames");
+    if (subsampling < 0 || subsampling > 2) return arg_error("fh_jpeg_encode_batch: subsampling must be 0 (4:4:4), 1 (4:2:2) or 2 (4:2:0)");
+    for (int i = 0; i < n; ++i) {
+        const fh_frame& f = frames[i];
+        if (!(f.bgr && f.rows > 0 && f.cols > 0)) continue;
+        if (f.rows > 65535 || f.cols > 65535) return arg_error("fh_jpeg_encode_batch: a frame is larger than 65535 in one direction");
+        if ((long long)f.step < (long long)f.cols * 3) return arg_error("fh_jpeg_encode_batch: a frame's step is smaller than cols * 3");
+    }
+    return guarded([&] { return jpeg_encode_batch(enc, frames, n, quality, subsampling, threads, files_out, S(stream)); });
 }
 
 // Two-stream form for streaming callers: detect (+ decode + NMS + face selection) on stream_det, align + embed on stream_rec

@@ -16,6 +16,8 @@
 // The JPEG decoder comes in two halves (include/facehip.h, "JPEG in two halves"): the parse up to dense int16 coefficient planes
 // (fh_jpeg_header / fh_jpeg_entropy, struct Jpeg) and the reconstruction from them (fh_jpeg_reconstruct, struct Recon), which
 // csrc/jpeg_dev.hip restates for the device and is held to, bit for bit.  fh_image_decode of a JPEG is the first followed by the second.
+// The way out is here too (include/facehip.h, "JPEG out"): fh_jpeg_enc_desc / fh_jpeg_forward / fh_jpeg_write / fh_imwrite_jpeg, libjpeg's
+// forward path and a baseline writer; csrc/jpeg_enc.hip restates fh_jpeg_forward for the device and is held to it, bit for bit.
 // This file stays plain C++: no HIP headers, no threads (tests/test_host_sanitize.py builds it with g++ alone).
 #include <zlib.h>
 
@@ -973,9 +975,377 @@ int jpeg_call(const char* fn, F&& f) {
     return -1;
 }
 
+// =====================================================================================================
+// JPEG out (include/facehip.h, "JPEG out"): libjpeg's forward path restated — jccolor.c, jcsample.c (no smoothing), jfdctint.c "islow",
+// jcdctmgr.c's quantiser, jccoefct.c's dummy blocks — and a baseline writer with the Annex K Huffman tables (jchuff.c without `optimize`).
+// fh_jpeg_forward is the oracle csrc/jpeg_enc.hip is held to, bit for bit.
+// =====================================================================================================
+const uint8_t kBaseLuma[64] = {16, 11, 10, 16, 24,  40,  51,  61,  12, 12, 14, 19, 26,  58,  60,  55,  14, 13, 16, 24, 40,  57,  69,  56,
+                               14, 17, 22, 29, 51,  87,  80,  62,  18, 22, 37, 56, 68,  109, 103, 77,  24, 35, 55, 64, 81,  104, 113, 92,
+                               49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99};
+const uint8_t kBaseChroma[64] = {17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99,
+                                 47, 66, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99,
+                                 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99};
+
+// ITU T.81 Annex K.3: bits[1..16] and the symbols, DC / AC, luminance / chrominance
+struct StdHuff { uint8_t bits[17]; int nvals; const uint8_t* vals; };
+const uint8_t kDcVals[12] = {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11};
+const uint8_t kAcLumaVals[162] = {
+    0x01, 0x02, 0x03, 0x00, 0x04, 0x11, 0x05, 0x12, 0x21, 0x31, 0x41, 0x06, 0x13, 0x51, 0x61, 0x07, 0x22, 0x71, 0x14, 0x32, 0x81, 0x91, 0xa1,
+    0x08, 0x23, 0x42, 0xb1, 0xc1, 0x15, 0x52, 0xd1, 0xf0, 0x24, 0x33, 0x62, 0x72, 0x82, 0x09, 0x0a, 0x16, 0x17, 0x18, 0x19, 0x1a, 0x25, 0x26,
+    0x27, 0x28, 0x29, 0x2a, 0x34, 0x35, 0x36, 0x37, 0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47, 0x48, 0x49, 0x4a, 0x53, 0x54, 0x55, 0x56,
+    0x57, 0x58, 0x59, 0x5a, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6a, 0x73, 0x74, 0x75, 0x76, 0x77, 0x78, 0x79, 0x7a, 0x83, 0x84, 0x85,
+    0x86, 0x87, 0x88, 0x89, 0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99, 0x9a, 0xa2, 0xa3, 0xa4, 0xa5, 0xa6, 0xa7, 0xa8, 0xa9, 0xaa,
+    0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba, 0xc2, 0xc3, 0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3, 0xd4, 0xd5, 0xd6,
+    0xd7, 0xd8, 0xd9, 0xda, 0xe1, 0xe2, 0xe3, 0xe4, 0xe5, 0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf1, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9,
+    0xfa};
+const uint8_t kAcChromaVals[162] = {
+    0x00, 0x01, 0x02, 0x03, 0x11, 0x04, 0x05, 0x21, 0x31, 0x06, 0x12, 0x41, 0x51, 0x07, 0x61, 0x71, 0x13, 0x22, 0x32, 0x81, 0x08, 0x14, 0x42,
+    0x91, 0xa1, 0xb1, 0xc1, 0x09, 0x23, 0x33, 0x52, 0xf0, 0x15, 0x62, 0x72, 0xd1, 0x0a, 0x16, 0x24, 0x34, 0xe1, 0x25, 0xf1, 0x17, 0x18, 0x19,
+    0x1a, 0x26, 0x27, 0x28, 0x29, 0x2a, 0x35, 0x36, 0x37, 0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47, 0x48, 0x49, 0x4a, 0x53, 0x54, 0x55,
+    0x56, 0x57, 0x58, 0x59, 0x5a, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6a, 0x73, 0x74, 0x75, 0x76, 0x77, 0x78, 0x79, 0x7a, 0x82, 0x83,
+    0x84, 0x85, 0x86, 0x87, 0x88, 0x89, 0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99, 0x9a, 0xa2, 0xa3, 0xa4, 0xa5, 0xa6, 0xa7, 0xa8,
+    0xa9, 0xaa, 0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba, 0xc2, 0xc3, 0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3, 0xd4,
+    0xd5, 0xd6, 0xd7, 0xd8, 0xd9, 0xda, 0xe2, 0xe3, 0xe4, 0xe5, 0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9,
+    0xfa};
+const StdHuff kStdHuff[4] = {                                              // index = class * 2 + table: DC0, DC1, AC0, AC1
+    {{0, 0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0}, 12, kDcVals},
+    {{0, 0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0}, 12, kDcVals},
+    {{0, 0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 0x7d}, 162, kAcLumaVals},
+    {{0, 0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 0x77}, 162, kAcChromaVals},
+};
+
+// code and length of every symbol (jchuff.c jpeg_make_c_derived_tbl); built once, on first use
+struct EncHuff {
+    uint16_t code[4][256];
+    uint8_t len[4][256];
+    EncHuff() {
+        memset(code, 0, sizeof(code)); memset(len, 0, sizeof(len));
+        for (int t = 0; t < 4; ++t) {
+            int c = 0, k = 0;
+            for (int l = 1; l <= 16; ++l) {
+                for (int i = 0; i < kStdHuff[t].bits[l]; ++i, ++k) { code[t][kStdHuff[t].vals[k]] = (uint16_t)c++; len[t][kStdHuff[t].vals[k]] = (uint8_t)l; }
+                c <<= 1;
+            }
+        }
+    }
+};
+const EncHuff& enc_huff() { static const EncHuff h; return h; }
+
+// fh_jpeg_enc_check's body: bad_desc plus what the forward path and the writer rely on
+const char* bad_enc_desc(const fh_jpeg_desc* o) {
+    if (const char* bad = bad_desc(o)) return bad;
+    if (o->width > 65535 || o->height > 65535) return "width / height above 65535 do not fit a frame header";
+    if (o->orientation != 1) return "the encoder writes orientation 1 only";
+    if (o->color != 0 && o->color != 1) return "the encoder writes grey (color 0) or YCbCr (color 1) only";
+    if (o->ncomp == 1 && (o->comp[0].h != 1 || o->comp[0].v != 1)) return "a grey picture's sampling factors must be 1 x 1";
+    if (o->ncomp == 3) {
+        const fh_jpeg_comp& y = o->comp[0];
+        if (o->comp[1].h != 1 || o->comp[1].v != 1 || o->comp[2].h != 1 || o->comp[2].v != 1) return "chroma sampling factors must be 1 x 1";
+        if (!((y.h == 1 && y.v == 1) || (y.h == 2 && y.v == 1) || (y.h == 2 && y.v == 2))) return "luma sampling factors must be 1 x 1 (4:4:4), 2 x 1 (4:2:2) or 2 x 2 (4:2:0)";
+    }
+    for (int i = 0; i < o->ncomp; ++i)
+        for (int k = 0; k < 64; ++k)
+            if (o->comp[i].quant[k] < 1 || o->comp[i].quant[k] > 255) return "a quantiser outside 1..255 (baseline)";
+    return nullptr;
+}
+
+// jfdctint.c on one 8x8 block of centred samples (s - 128), in place: the result is 8 x the DCT.  int suffices: |sample| <= 128, the row
+// pass's largest term is below 8 * 128 * 25172 * 2 < 2^27, its outputs are below 2^13 (8 * 128 * 4 on the DC path), the column pass's
+// largest term is below 8 * 2^13 * 25172 * 2 < 2^31 (libjpeg's own claim for 8-bit samples: its INT32 is 32 bits wide).
+inline int fdct_descale(int x, int n) { return (x + (1 << (n - 1))) >> n; }
+template <int PASS>                                                          // 0: rows (stride 1), 1: columns (stride 8)
+inline void fdct_1d(int* d) {
+    constexpr int S = PASS ? 8 : 1;
+    constexpr int F0_298 = 2446, F0_390 = 3196, F0_541 = 4433, F0_765 = 6270, F0_899 = 7373, F1_175 = 9633, F1_501 = 12299, F1_847 = 15137,
+                  F1_961 = 16069, F2_053 = 16819, F2_562 = 20995, F3_072 = 25172;
+    constexpr int N = PASS ? 15 : 11;                                      // CONST_BITS + PASS1_BITS / CONST_BITS - PASS1_BITS
+    int tmp0 = d[0] + d[7 * S], tmp7 = d[0] - d[7 * S], tmp1 = d[S] + d[6 * S], tmp6 = d[S] - d[6 * S];
+    int tmp2 = d[2 * S] + d[5 * S], tmp5 = d[2 * S] - d[5 * S], tmp3 = d[3 * S] + d[4 * S], tmp4 = d[3 * S] - d[4 * S];
+    const int tmp10 = tmp0 + tmp3, tmp13 = tmp0 - tmp3, tmp11 = tmp1 + tmp2, tmp12 = tmp1 - tmp2;
+    if (PASS == 0) { d[0] = (tmp10 + tmp11) * 4; d[4 * S] = (tmp10 - tmp11) * 4; }
+    else { d[0] = fdct_descale(tmp10 + tmp11, 2); d[4 * S] = fdct_descale(tmp10 - tmp11, 2); }
+    int z1 = (tmp12 + tmp13) * F0_541;
+    d[2 * S] = fdct_descale(z1 + tmp13 * F0_765, N);
+    d[6 * S] = fdct_descale(z1 + tmp12 * (-F1_847), N);
+    z1 = tmp4 + tmp7;
+    int z2 = tmp5 + tmp6, z3 = tmp4 + tmp6, z4 = tmp5 + tmp7;
+    const int z5 = (z3 + z4) * F1_175;
+    tmp4 *= F0_298; tmp5 *= F2_053; tmp6 *= F3_072; tmp7 *= F1_501;
+    z1 *= -F0_899; z2 *= -F2_562; z3 *= -F1_961; z4 *= -F0_390;
+    z3 += z5; z4 += z5;
+    d[7 * S] = fdct_descale(tmp4 + z1 + z3, N);
+    d[5 * S] = fdct_descale(tmp5 + z2 + z4, N);
+    d[3 * S] = fdct_descale(tmp6 + z2 + z3, N);
+    d[S] = fdct_descale(tmp7 + z1 + z4, N);
+}
+// jcdctmgr.c's quantiser on a coefficient scaled by 8: qv = 8 q, round half away from zero
+inline int16_t fdct_quant(int c, int q) {
+    const int qv = q * 8, t = (c < 0 ? -c : c) + (qv >> 1);
+    return (int16_t)(c < 0 ? -(t / qv) : t / qv);
+}
+
+// jccolor.c rgb_ycc_convert, SCALEBITS = 16: component ci (0 Y, 1 Cb, 2 Cr) of a B, G, R pixel
+inline int ycc_of(const uint8_t* p, int ci) {
+    const int b = p[0], g = p[1], r = p[2];
+    if (ci == 0) return (19595 * r + 38470 * g + 7471 * b + 32768) >> 16;
+    if (ci == 1) return (-11059 * r - 21709 * g + 32768 * b + (128 << 16) + 32767) >> 16;
+    return (32768 * r - 27439 * g - 5329 * b + (128 << 16) + 32767) >> 16;
+}
+
+// fh_jpeg_forward's body; the descriptor passed bad_enc_desc
+void jpeg_forward(const fh_jpeg_desc& o, const uint8_t* bgr, size_t step, int16_t* coef) {
+    const int W = o.width, H = o.height;
+    for (int ci = 0; ci < o.ncomp; ++ci) {
+        const fh_jpeg_comp& c = o.comp[ci];
+        const int hx = o.hmax / c.h, vx = o.vmax / c.v;                      // 1 or 2; vx == 2 only with hx == 2
+        const int bw = (c.dw + 7) / 8, bh = (c.dh + 7) / 8;                  // the real blocks
+        // the component's sample plane over the real blocks.  Columns: the last picture column repeats (clamped index).  Rows: the last
+        // picture row repeats up to a multiple of vmax, then the last DOWN-SAMPLED row repeats (jcprepct.c): sample row min(sy, dh - 1).
+        std::vector<uint8_t> plane((size_t)bw * 8 * bh * 8);
+        auto px = [&](int x, int y) { return ycc_of(bgr + (size_t)std::min(y, H - 1) * step + (size_t)std::min(x, W - 1) * 3, ci); };
+        for (int sy = 0; sy < bh * 8; ++sy) {
+            const int y = std::min(sy, c.dh - 1);
+            uint8_t* row = &plane[(size_t)sy * bw * 8];
+            for (int sx = 0; sx < bw * 8; ++sx) {
+                int v;
+                if (hx == 1) v = px(sx, y);
+                else if (vx == 1) v = (px(2 * sx, y) + px(2 * sx + 1, y) + (sx & 1)) >> 1;                                  // h2v1_downsample
+                else v = (px(2 * sx, 2 * y) + px(2 * sx + 1, 2 * y) + px(2 * sx, 2 * y + 1) + px(2 * sx + 1, 2 * y + 1) + 1 + (sx & 1)) >> 2;   // h2v2
+                row[sx] = (uint8_t)v;
+            }
+        }
+        int16_t* out = coef + c.coef_off;
+        for (int by = 0; by < bh; ++by)
+            for (int bx = 0; bx < bw; ++bx) {
+                int d[64];
+                for (int r = 0; r < 8; ++r)
+                    for (int k = 0; k < 8; ++k) d[r * 8 + k] = (int)plane[((size_t)by * 8 + r) * bw * 8 + (size_t)bx * 8 + k] - 128;
+                for (int r = 0; r < 8; ++r) fdct_1d<0>(d + r * 8);
+                for (int k = 0; k < 8; ++k) fdct_1d<1>(d + k);
+                int16_t* blk = out + ((size_t)by * c.wblocks + bx) * 64;
+                for (int k = 0; k < 64; ++k) blk[k] = fdct_quant(d[k], c.quant[k]);
+            }
+        // jccoefct.c's dummy blocks: AC zero; right of the real ones DC = the block to the left; below them DC = the last block of the
+        // row above in the same MCU column
+        for (int by = 0; by < c.hblocks; ++by)
+            for (int bx = 0; bx < c.wblocks; ++bx) {
+                if (by < bh && bx < bw) continue;
+                const int sy = std::min(by, bh - 1), sx = std::min(by < bh ? bx : bx / c.h * c.h + c.h - 1, bw - 1);
+                int16_t* blk = out + ((size_t)by * c.wblocks + bx) * 64;
+                memset(blk, 0, 64 * sizeof(int16_t));
+                blk[0] = out[((size_t)sy * c.wblocks + sx) * 64];
+            }
+    }
+}
+
+// The writer's sink: counts every byte, stores those in front of `cap`.  Entropy-coded bits gather in a 64-bit word and leave four bytes
+// at a time; a word without a 0xFF byte that fits in front of `cap` is stored whole, any other goes byte by byte (0xFF is followed by a
+// stuffed zero).
+struct ByteSink {
+    uint8_t* out;
+    size_t cap, pos = 0;
+    uint64_t acc = 0;
+    int nbits = 0;                                                         // valid low bits of acc; below 32 between calls
+    void byte(int b) { if (pos < cap) out[pos] = (uint8_t)b; ++pos; }
+    void u16(int v) { byte(v >> 8); byte(v & 255); }
+    void marker(int m) { byte(0xFF); byte(m); }
+    void data_byte(int b) { byte(b); if (b == 0xFF) byte(0); }
+    void bits(unsigned code, int n) {                                      // n <= 27 per call
+        acc = (acc << n) | code; nbits += n;
+        if (nbits < 32) return;
+        nbits -= 32;
+        const uint32_t w = (uint32_t)(acc >> nbits);
+        if (pos + 4 <= cap && ((~w - 0x01010101u) & w & 0x80808080u) == 0) {
+            out[pos] = (uint8_t)(w >> 24); out[pos + 1] = (uint8_t)(w >> 16); out[pos + 2] = (uint8_t)(w >> 8); out[pos + 3] = (uint8_t)w;
+            pos += 4;
+        } else {
+            data_byte((int)(w >> 24)); data_byte((int)((w >> 16) & 255)); data_byte((int)((w >> 8) & 255)); data_byte((int)(w & 255));
+        }
+    }
+    void flush() {                                                         // pad the last byte with ones
+        if (nbits & 7) { const int pad = 8 - (nbits & 7); acc = (acc << pad) | ((1u << pad) - 1); nbits += pad; }
+        for (; nbits > 0; nbits -= 8) data_byte((int)((acc >> (nbits - 8)) & 255));
+    }
+};
+
+inline int bit_length(unsigned v) { return v ? 32 - __builtin_clz(v) : 0; }
+
+// jchuff.c encode_one_block; false for a DC difference outside +-2047 or an AC value outside +-1023
+bool encode_block(ByteSink& s, const EncHuff& h, const int16_t* blk, int& pred, int dc_tbl, int ac_tbl) {
+    const int diff = blk[0] - pred;
+    pred = blk[0];
+    int t = diff < 0 ? -diff : diff, t2 = diff < 0 ? diff - 1 : diff;
+    int n = bit_length((unsigned)t);
+    if (n > 11) return false;
+    s.bits(((unsigned)h.code[dc_tbl][n] << n) | ((unsigned)t2 & ((1u << n) - 1)), h.len[dc_tbl][n] + n);
+    uint64_t nz = 0;                                                       // bit k: the coefficient at zigzag position k is not zero
+    for (int k = 1; k < 64; ++k) nz |= (uint64_t)(blk[kZigzag[k]] != 0) << k;
+    int prev = 0;
+    for (; nz; nz &= nz - 1) {
+        const int k = __builtin_ctzll(nz), v = blk[kZigzag[k]];
+        int run = k - prev - 1;
+        prev = k;
+        for (; run > 15; run -= 16) s.bits(h.code[ac_tbl][0xF0], h.len[ac_tbl][0xF0]);
+        t = v < 0 ? -v : v; t2 = v < 0 ? v - 1 : v;
+        n = bit_length((unsigned)t);
+        if (n > 10) return false;
+        const int sym = (run << 4) | n;
+        s.bits(((unsigned)h.code[ac_tbl][sym] << n) | ((unsigned)t2 & ((1u << n) - 1)), h.len[ac_tbl][sym] + n);
+    }
+    if (prev != 63) s.bits(h.code[ac_tbl][0], h.len[ac_tbl][0]);           // EOB unless the last coefficient was coded
+    return true;
+}
+
+// fh_jpeg_write's body (the descriptor passed bad_enc_desc): false for a coefficient the baseline tables cannot code.  s.pos = the size.
+bool jpeg_write(const fh_jpeg_desc& o, const int16_t* coef, ByteSink& s) {
+    const int nc = o.ncomp;
+    int tq[3] = {0, 1, 1};                                                 // libjpeg's assignment; a third table only where Cr's differs from Cb's
+    if (nc == 3 && memcmp(o.comp[2].quant, o.comp[1].quant, sizeof(o.comp[1].quant)) != 0) tq[2] = 2;
+    s.marker(0xD8);
+    s.marker(0xE0); s.u16(16);
+    for (const char* p = "JFIF"; *p; ++p) s.byte(*p);
+    s.byte(0); s.byte(1); s.byte(1); s.byte(0); s.u16(1); s.u16(1); s.byte(0); s.byte(0);
+    for (int i = 0; i < nc; ++i) {
+        if (i == 2 && tq[2] == 1) continue;
+        s.marker(0xDB); s.u16(67); s.byte(tq[i]);
+        for (int k = 0; k < 64; ++k) s.byte(o.comp[i].quant[kZigzag[k]]);
+    }
+    s.marker(0xC0); s.u16(8 + 3 * nc); s.byte(8); s.u16(o.height); s.u16(o.width); s.byte(nc);
+    for (int i = 0; i < nc; ++i) { s.byte(i + 1); s.byte((o.comp[i].h << 4) | o.comp[i].v); s.byte(tq[i]); }
+    for (int t = 0; t < 4; ++t) {                                          // DC0, AC0 (, DC1, AC1): libjpeg's order
+        const int idx = (t & 1) * 2 + (t >> 1);
+        if (nc == 1 && (t >> 1)) continue;
+        const StdHuff& h = kStdHuff[idx];
+        s.marker(0xC4); s.u16(2 + 1 + 16 + h.nvals); s.byte(((t & 1) << 4) | (t >> 1));
+        for (int l = 1; l <= 16; ++l) s.byte(h.bits[l]);
+        for (int k = 0; k < h.nvals; ++k) s.byte(h.vals[k]);
+    }
+    s.marker(0xDA); s.u16(6 + 2 * nc); s.byte(nc);
+    for (int i = 0; i < nc; ++i) { s.byte(i + 1); s.byte(i ? 0x11 : 0x00); }
+    s.byte(0); s.byte(63); s.byte(0);
+    int pred[3] = {0, 0, 0};
+    const EncHuff& huff = enc_huff();
+    const int mcux = o.comp[0].wblocks / o.comp[0].h, mcuy = o.comp[0].hblocks / o.comp[0].v;
+    for (int my = 0; my < mcuy; ++my)
+        for (int mx = 0; mx < mcux; ++mx)
+            for (int i = 0; i < nc; ++i) {
+                const fh_jpeg_comp& c = o.comp[i];
+                for (int y = 0; y < c.v; ++y)
+                    for (int x = 0; x < c.h; ++x) {
+                        const int16_t* blk = coef + c.coef_off + ((size_t)(my * c.v + y) * c.wblocks + (size_t)(mx * c.h + x)) * 64;
+                        if (!encode_block(s, huff, blk, pred[i], i ? 1 : 0, i ? 3 : 2)) return false;
+                    }
+            }
+    s.flush();
+    s.marker(0xD9);
+    return true;
+}
+
+// headers (at most 2 + 18 + 3 * 69 + 19 + 2 * 33 + 2 * 183 + 14 + 2 < 1024 bytes) + per block the longest codes: DC 11 + 11 bits,
+// 63 AC values of 16 + 10 bits = 1660 bits < 208 bytes, every one of them stuffed
+size_t jpeg_write_bound(const fh_jpeg_desc& o) {
+    size_t blocks = 0;
+    for (int i = 0; i < o.ncomp; ++i) blocks += (size_t)o.comp[i].wblocks * o.comp[i].hblocks;
+    return 1024 + blocks * 416;
+}
+
 }  // namespace
 
 extern "C" {
+
+int fh_jpeg_quant_tables(int quality, uint16_t* luma, uint16_t* chroma) {
+    if (!luma || !chroma) { fh::set_error("fh_jpeg_quant_tables: null argument"); return FH_ERR_ARG; }
+    const int q = quality < 1 ? 1 : quality > 100 ? 100 : quality;         // jpeg_quality_scaling
+    const int scale = q < 50 ? 5000 / q : 200 - 2 * q;
+    for (int k = 0; k < 64; ++k) {
+        const int l = (kBaseLuma[k] * scale + 50) / 100, c = (kBaseChroma[k] * scale + 50) / 100;
+        luma[k] = (uint16_t)(l < 1 ? 1 : l > 255 ? 255 : l);
+        chroma[k] = (uint16_t)(c < 1 ? 1 : c > 255 ? 255 : c);
+    }
+    return 0;
+}
+
+int fh_jpeg_enc_desc(int width, int height, int gray, int subsampling, int quality, fh_jpeg_desc* d) {
+    if (!d) { fh::set_error("fh_jpeg_enc_desc: null descriptor"); return FH_ERR_ARG; }
+    if (width < 1 || height < 1 || width > 65535 || height > 65535) { fh::set_error("fh_jpeg_enc_desc: need 1 <= width, height <= 65535"); return FH_ERR_ARG; }
+    if (!gray && (subsampling < 0 || subsampling > 2)) { fh::set_error("fh_jpeg_enc_desc: subsampling must be 0 (4:4:4), 1 (4:2:2) or 2 (4:2:0)"); return FH_ERR_ARG; }
+    uint16_t luma[64], chroma[64];
+    fh_jpeg_quant_tables(quality, luma, chroma);
+    memset(d, 0, sizeof(*d));
+    d->width = d->cols = width; d->height = d->rows = height;
+    d->ncomp = gray ? 1 : 3; d->color = gray ? 0 : 1; d->orientation = 1;
+    d->hmax = !gray && subsampling >= 1 ? 2 : 1; d->vmax = !gray && subsampling == 2 ? 2 : 1;
+    const int mcux = (width + 8 * d->hmax - 1) / (8 * d->hmax), mcuy = (height + 8 * d->vmax - 1) / (8 * d->vmax);
+    for (int i = 0; i < d->ncomp; ++i) {
+        fh_jpeg_comp& c = d->comp[i];
+        c.h = i ? 1 : d->hmax; c.v = i ? 1 : d->vmax;
+        c.wblocks = mcux * c.h; c.hblocks = mcuy * c.v;
+        c.dw = (width * c.h + d->hmax - 1) / d->hmax; c.dh = (height * c.v + d->vmax - 1) / d->vmax;
+        c.coef_off = d->coef_count;
+        d->coef_count += (int64_t)c.wblocks * c.hblocks * 64;
+        memcpy(c.quant, i ? chroma : luma, sizeof(c.quant));
+    }
+    return 0;
+}
+
+int fh_jpeg_enc_check(const fh_jpeg_desc* desc) {
+    if (const char* bad = bad_enc_desc(desc)) { fh::set_error(std::string("fh_jpeg_enc_check: ") + bad); return FH_ERR_ARG; }
+    return 0;
+}
+
+int fh_jpeg_forward(const fh_jpeg_desc* desc, const unsigned char* bgr, int step, int16_t* coef, size_t cap) {
+    if (!desc || !bgr || !coef) { fh::set_error("fh_jpeg_forward: null argument"); return FH_ERR_ARG; }
+    if (const char* bad = bad_enc_desc(desc)) { fh::set_error(std::string("fh_jpeg_forward: ") + bad); return FH_ERR_ARG; }
+    if ((long long)step < (long long)desc->cols * 3) { fh::set_error("fh_jpeg_forward: step is smaller than cols * 3"); return FH_ERR_ARG; }
+    if ((unsigned long long)desc->coef_count > cap) { fh::set_error("fh_jpeg_forward: the coefficient buffer is too small for this descriptor"); return FH_ERR_ARG; }
+    return jpeg_call("fh_jpeg_forward", [&] { jpeg_forward(*desc, bgr, (size_t)step, coef); });
+}
+
+size_t fh_jpeg_write_bound(const fh_jpeg_desc* desc) {
+    if (bad_enc_desc(desc)) return 0;
+    return jpeg_write_bound(*desc);
+}
+
+int fh_jpeg_write(const fh_jpeg_desc* desc, const int16_t* coef, unsigned char* out, size_t cap, size_t* written) {
+    if (written) *written = 0;
+    if (!desc || !coef || !written || (!out && cap)) { fh::set_error("fh_jpeg_write: null argument"); return FH_ERR_ARG; }
+    if (const char* bad = bad_enc_desc(desc)) { fh::set_error(std::string("fh_jpeg_write: ") + bad); return FH_ERR_ARG; }
+    ByteSink s{out, cap};
+    if (!jpeg_write(*desc, coef, s)) {
+        fh::set_error("fh_jpeg_write: a DC difference outside +-2047 or an AC coefficient outside +-1023 has no baseline code");
+        return FH_ERR_ARG;
+    }
+    *written = s.pos;
+    if (s.pos > cap) { fh::set_error("fh_jpeg_write: the output buffer is too small (see *written)"); return FH_ERR_ARG; }
+    return 0;
+}
+
+int fh_imwrite_jpeg(const char* path, const unsigned char* bgr, int rows, int cols, int step, int quality, int subsampling) {
+    if (!path || !bgr) { fh::set_error("fh_imwrite_jpeg: null argument"); return FH_ERR_ARG; }
+    fh_jpeg_desc d;
+    if (rows < 1 || cols < 1 || fh_jpeg_enc_desc(cols, rows, 0, subsampling, quality, &d) != 0) {
+        if (rows < 1 || cols < 1) fh::set_error("fh_imwrite_jpeg: empty image");
+        return FH_ERR_ARG;
+    }
+    if ((long long)step < (long long)cols * 3) { fh::set_error("fh_imwrite_jpeg: step is smaller than cols * 3"); return FH_ERR_ARG; }
+    size_t n = 0;
+    std::vector<unsigned char> bytes;
+    const int rc = jpeg_call("fh_imwrite_jpeg", [&] {
+        std::vector<int16_t> coef((size_t)d.coef_count);
+        jpeg_forward(d, bgr, (size_t)step, coef.data());
+        bytes.resize(jpeg_write_bound(d));
+        ByteSink s{bytes.data(), bytes.size()};
+        if (!jpeg_write(d, coef.data(), s) || s.pos > bytes.size()) fail("fh_imwrite_jpeg: the coefficients have no baseline code");
+        n = s.pos;
+    });
+    if (rc != 0) return rc;
+    FILE* f = fopen(path, "wb");
+    if (!f) { fh::set_error(std::string("fh_imwrite_jpeg: cannot open ") + path); return -1; }
+    const bool ok = fwrite(bytes.data(), 1, n, f) == n;
+    if (fclose(f) != 0 || !ok) { fh::set_error(std::string("fh_imwrite_jpeg: cannot write ") + path); return -1; }
+    return 0;
+}
 
 int fh_jpeg_header(const unsigned char* bytes, size_t n, fh_jpeg_desc* desc) {
     if (!bytes || !desc) { fh::set_error("fh_jpeg_header: null argument"); return -1; }

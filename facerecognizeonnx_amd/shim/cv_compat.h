@@ -12,10 +12,12 @@
 #include <cstring>
 #include <memory>
 #include <string>
+#include <vector>
 
 extern "C" {                                          // include/facehip.h (libfacehip.so)
 int fh_imread(const char* path, unsigned char** bgr, int* rows, int* cols);
 void fh_image_free(unsigned char* bgr);
+int fh_imwrite_jpeg(const char* path, const unsigned char* bgr, int rows, int cols, int step, int quality, int subsampling);
 }
 
 #ifndef CV_8UC3
@@ -77,6 +79,30 @@ inline Mat imread(const std::string& path) {
     std::memcpy(m.data, p, (size_t)r * c * 3);
     fh_image_free(p);
     return m;
+}
+
+// cv::imwrite(path, img[, params]) for ".jpg" / ".jpeg": the library's own baseline encoder (csrc/image_io.cpp, libjpeg's arithmetic),
+// OpenCV's defaults — quality 95, 4:2:0 chroma — unless params holds IMWRITE_JPEG_QUALITY (1) / IMWRITE_JPEG_SAMPLING_FACTOR (7: 0x111111
+// = 4:4:4, 0x211111 = 4:2:2, 0x221111 = 4:2:0).  false for an empty image, another extension or a file that cannot be written.
+enum { IMWRITE_JPEG_QUALITY = 1, IMWRITE_JPEG_SAMPLING_FACTOR = 7 };
+enum { IMWRITE_JPEG_SAMPLING_FACTOR_411 = 0x411111, IMWRITE_JPEG_SAMPLING_FACTOR_420 = 0x221111, IMWRITE_JPEG_SAMPLING_FACTOR_422 = 0x211111,
+       IMWRITE_JPEG_SAMPLING_FACTOR_444 = 0x111111 };
+inline bool imwrite(const std::string& path, const Mat& img, const std::vector<int>& params = std::vector<int>()) {
+    const size_t dot = path.rfind('.');
+    std::string ext = dot == std::string::npos ? "" : path.substr(dot);
+    for (char& c : ext) c = (char)(c >= 'A' && c <= 'Z' ? c - 'A' + 'a' : c);
+    if (img.empty() || (ext != ".jpg" && ext != ".jpeg" && ext != ".jpe")) return false;
+    int quality = 95, sub = 2;
+    for (size_t i = 0; i + 1 < params.size(); i += 2) {
+        if (params[i] == IMWRITE_JPEG_QUALITY) quality = params[i + 1] < 0 ? 0 : params[i + 1] > 100 ? 100 : params[i + 1];
+        if (params[i] == IMWRITE_JPEG_SAMPLING_FACTOR) {
+            if (params[i + 1] == IMWRITE_JPEG_SAMPLING_FACTOR_444) sub = 0;
+            else if (params[i + 1] == IMWRITE_JPEG_SAMPLING_FACTOR_422) sub = 1;
+            else if (params[i + 1] == IMWRITE_JPEG_SAMPLING_FACTOR_420) sub = 2;
+            else return false;                                          // 4:1:1 and 4:4:0 are not written
+        }
+    }
+    return fh_imwrite_jpeg(path.c_str(), img.data, img.rows, img.cols, (int)img.step, quality, sub) == 0;
 }
 
 }  // namespace cv

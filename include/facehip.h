@@ -1062,6 +1062,64 @@ FH_API int fh_jpeg_decode_batch(fh_jpegdec* dec, const fh_blob* files, int n, in
 FH_API int fh_pipeline_run_files(fh_det* d, fh_rec* r, fh_jpegdec* dec, const fh_blob* files, int n, int threads, float score_thr,
                                  float nms_thr, int faces_per_frame, fh_face* faces, int* frame_of, float* emb, int cap, int* status);
 
+/* ---- JPEG out: the decode split in mirror image.  Colour conversion, chroma down-sampling, the forward DCT and quantisation are integer
+ * arithmetic that is independent per block (kernels, csrc/jpeg_enc.hip); Huffman coding is serial per file and independent across files
+ * (host threads).  The cut is the same dense int16 coefficient plane per component, described by the same fh_jpeg_desc.  The arithmetic
+ * is libjpeg's (jccolor.c, jcsample.c without smoothing, jfdctint.c "islow", jcdctmgr.c, jccoefct.c's dummy blocks): the coefficients
+ * are, bit for bit, the ones libjpeg(-turbo) stores for the same pixels, sampling and quality (tests/test_jpeg_enc_cpu.py, against files
+ * written by Pillow).  The files are baseline sequential JFIF with the four Annex K Huffman tables (libjpeg without `optimize`), one
+ * interleaved scan; no restart markers, no EXIF, no progressive mode.
+ *
+ * fh_jpeg_quant_tables  libjpeg's jpeg_quality_scaling on the Annex K base tables: quality clipped to 1..100, scale = 5000 / q below 50,
+ *           200 - 2 q otherwise, entry = (base * scale + 50) / 100 clamped to 1..255.  Natural order.
+ * fh_jpeg_enc_desc  the descriptor of a width x height picture (1..65535 each): gray != 0 one component (subsampling is ignored), else
+ *           Y Cb Cr with subsampling 0 = 4:4:4, 1 = 4:2:2 (luma 2 x 1), 2 = 4:2:0 (luma 2 x 2); block grids padded to whole MCUs, dw / dh,
+ *           coef_off (multiples of 64), coef_count and quant (fh_jpeg_quant_tables of `quality`) filled; orientation 1, color 0 or 1,
+ *           rows / cols = height / width.
+ * fh_jpeg_enc_check  fh_jpeg_desc_check plus what the forward paths and the writer rely on: orientation 1, color 0 or 1, width and
+ *           height <= 65535, sampling factors of one of the layouts above (chroma 1 x 1; grey 1 x 1), every quantiser in 1..255.  Both
+ *           forward paths and the writer run it first: a bad descriptor never reaches a kernel and nothing is written.
+ * fh_jpeg_forward  host: BGR u8 [rows][cols] at pitch `step` (>= cols * 3) -> all coef_count coefficients, natural order, dummy blocks
+ *           of the padded grid included.  A grey descriptor takes Y from the B, G, R of every pixel (what cv::imwrite does with a
+ *           3-channel image; a caller with grey data passes B = G = R, which gives Y = that value).  cap < coef_count is an error raised
+ *           before the first write.  The bit-exact oracle of the device path.
+ * fh_jpeg_write  coefficients -> the file's bytes.  A DC difference outside +-2047 or an AC value outside +-1023 (which no forward path
+ *           produces) returns FH_ERR_ARG, *written = 0.  Otherwise *written = the size of the file whatever cap is; cap smaller than that
+ *           returns FH_ERR_ARG and nothing at or behind out + cap is written, so that a caller can size and retry.
+ * fh_jpeg_write_bound  an upper bound of *written for the descriptor (0 for one fh_jpeg_enc_check refuses).
+ * fh_imwrite_jpeg  fh_jpeg_enc_desc + fh_jpeg_forward + fh_jpeg_write + a file write: cv::imwrite(path.jpg, bgr) with
+ *           IMWRITE_JPEG_QUALITY = quality and the chroma sampling chosen by `subsampling`.
+ * All: 0 on success, < 0 + fh_last_error().  Host code, no GPU. */
+FH_API int fh_jpeg_quant_tables(int quality, uint16_t* luma, uint16_t* chroma);
+FH_API int fh_jpeg_enc_desc(int width, int height, int gray, int subsampling, int quality, fh_jpeg_desc* desc);
+FH_API int fh_jpeg_enc_check(const fh_jpeg_desc* desc);
+FH_API int fh_jpeg_forward(const fh_jpeg_desc* desc, const unsigned char* bgr, int step, int16_t* coef, size_t cap);
+FH_API int fh_jpeg_write(const fh_jpeg_desc* desc, const int16_t* coef, unsigned char* out, size_t cap, size_t* written);
+FH_API size_t fh_jpeg_write_bound(const fh_jpeg_desc* desc);
+FH_API int fh_imwrite_jpeg(const char* path, const unsigned char* bgr, int rows, int cols, int step, int quality, int subsampling);
+/* fh_jpegenc  owner of the device side: the device copy of the descriptor table, the workspace of sample planes and (for
+ *           fh_jpeg_encode_batch) the device and pinned coefficient arenas and the output byte arena.  All grow on demand.
+ * fh_jpeg_forward_batch_dev  fh_jpeg_forward for n images (1 <= n <= 4096) of any sizes and layouts in TWO launches, whatever n is: descs =
+ *           HOST array (read before the call returns), frames[i].bgr = DEVICE pixels at any address and any pitch step >= cols * 3, whose
+ *           rows / cols must equal the descriptor's; d_coef = DEVICE int16 (2-byte aligned), image i writes [coef_base[i], coef_base[i] +
+ *           descs[i].coef_count).  A slot with bgr == NULL is skipped and its coefficient range is not written.  Only bytes
+ *           [row * step, row * step + cols * 3) of real rows are read.  The coefficients equal fh_jpeg_forward's for every descriptor
+ *           fh_jpeg_enc_check accepts and every pixel value.  Every descriptor is checked before anything is launched: one bad one fails the
+ *           call with FH_ERR_ARG and nothing is written.  Asynchronous on `stream`; returns n.
+ * fh_jpeg_encode_batch  n DEVICE frames (1 <= n <= 4096) -> n files: a descriptor per frame (fh_jpeg_enc_desc, colour), the forward
+ *           path on the device, ONE device-to-host copy of the coefficient arena into pinned memory, fh_jpeg_write on up to `threads` host
+ *           threads (clipped to [1, 16]; 0 = min(16, n)), one file per task.  files_out[i] points into the handle's byte arena, valid until
+ *           the next call on `enc`; an empty frame (bgr == NULL or a non-positive size) gives {NULL, 0} and the call still succeeds.  Every
+ *           file equals fh_jpeg_write(fh_jpeg_forward(...)) on the host, byte for byte, whatever `threads` is.  Blocking; returns the number
+ *           of files written. */
+typedef struct fh_jpegenc fh_jpegenc;
+FH_API fh_jpegenc* fh_jpegenc_create(void);
+FH_API void fh_jpegenc_destroy(fh_jpegenc* enc);
+FH_API int fh_jpeg_forward_batch_dev(fh_jpegenc* enc, const fh_jpeg_desc* descs, int n, const fh_frame* frames, int16_t* d_coef,
+                                     const long long* coef_base, void* stream);
+FH_API int fh_jpeg_encode_batch(fh_jpegenc* enc, const fh_frame* frames, int n, int quality, int subsampling, int threads, fh_blob* files_out,
+                                void* stream);
+
 /* ---- single kernels exposed for parity tests and micro-benchmarks (device pointers). */
 FH_API int fh_memcpy_d2h(void* host_dst, const void* dev_src, size_t bytes);   /* synchronous */
 FH_API int fh_resize_u8c3_dev(const uint8_t* d_src, int sh, int sw, int sstep, uint8_t* d_dst, int dh, int dw, int dstep,
