@@ -1255,6 +1255,17 @@ const char* bad_identity(const fh_tracker* t, const fh_gallery* g) {
     if (g->g.dim() != t->t.identity_dim()) return "the gallery's dim is not the identity dim";
     return nullptr;
 }
+// what the two identify calls check alike, in their order (ptrs: the call's own device pointers are all given).  Null on success.
+const char* bad_identify_call(fh_tracker* t, fh_gallery* g, bool ptrs, const int* quality, const float* emb, int total, int n,
+                              int per_frame, const int* stream_of, const char* weighted_needs_quality) {
+    if (!t || !g || !ptrs) return "null argument";
+    if (const char* bad = bad_track_batch(t, n, per_frame, stream_of)) return bad;
+    if (const char* bad = bad_identity(t, g)) return bad;
+    if (total < 0 || (long long)total > (long long)n * per_frame) return "need 0 <= total <= n * per_frame";
+    if (total > 0 && !emb) return "null embeddings with total > 0";
+    if (!quality && t->t.identity_pool() == FH_TRACK_POOL_WEIGHTED) return weighted_needs_quality;
+    return nullptr;
+}
 }  // namespace
 int fh_pipeline_run_tracked_dev(fh_det* d, fh_rec* r, fh_tracker* t, const uint8_t* frames, int n, int rows, int cols, int step,
                                 long long stride, const int* stream_of, float score_thr, float nms_thr, int F, fh_face* all, int* counts,
@@ -1338,12 +1349,9 @@ int fh_track_identify_q_dev(fh_tracker* t, fh_gallery* g, float threshold, const
                             const int* quality, const float* emb, int total, int n, int per_frame, const int* stream_of, int* label,
                             float* score, void* stream) {
     const char* const fn = quality ? "fh_track_identify_q_dev" : "fh_track_identify_dev";
-    if (!t || !g || !track || !slot || !embed || !label || !score) return frames_error(fn, "null argument");
-    if (const char* bad = bad_track_batch(t, n, per_frame, stream_of)) return frames_error(fn, bad);
-    if (const char* bad = bad_identity(t, g)) return frames_error(fn, bad);
-    if (total < 0 || (long long)total > (long long)n * per_frame) return frames_error(fn, "need 0 <= total <= n * per_frame");
-    if (total > 0 && !emb) return frames_error(fn, "null embeddings with total > 0");
-    if (!quality && t->t.identity_pool() == FH_TRACK_POOL_WEIGHTED) return frames_error(fn, "the weighted pool needs the qualities (fh_track_identify_q_dev)");
+    const char* const bad = bad_identify_call(t, g, track && slot && embed && label && score, quality, emb, total, n, per_frame, stream_of,
+                                              "the weighted pool needs the qualities (fh_track_identify_q_dev)");
+    if (bad) return frames_error(fn, bad);
     if (t->t.relink()) {
         g_err = std::string(fn) + ": re-linking is on for this tracker: call fh_track_identify_link_dev";
         return FH_ERR_STATE;
@@ -1409,13 +1417,9 @@ int fh_tracker_set_stream_masks(fh_tracker* t, const uint32_t* masks_host) {
 int fh_track_identify_link_dev(fh_tracker* t, fh_gallery* g, float threshold, const int* track, const int* slot, const int* embed,
                                const int* quality, const float* emb, int total, int n, int per_frame, const int* stream_of, int* label,
                                float* score, int* root, void* stream) {
-    const char* const fn = "fh_track_identify_link_dev";
-    if (!t || !g || !track || !slot || !embed || !label || !score || !root) return frames_error(fn, "null argument");
-    if (const char* bad = bad_track_batch(t, n, per_frame, stream_of)) return frames_error(fn, bad);
-    if (const char* bad = bad_identity(t, g)) return frames_error(fn, bad);
-    if (total < 0 || (long long)total > (long long)n * per_frame) return frames_error(fn, "need 0 <= total <= n * per_frame");
-    if (total > 0 && !emb) return frames_error(fn, "null embeddings with total > 0");
-    if (!quality && t->t.identity_pool() == FH_TRACK_POOL_WEIGHTED) return frames_error(fn, "the weighted pool needs the qualities");
+    const char* const bad = bad_identify_call(t, g, track && slot && embed && label && score && root, quality, emb, total, n, per_frame,
+                                              stream_of, "the weighted pool needs the qualities");
+    if (bad) return frames_error("fh_track_identify_link_dev", bad);
     return guarded([&] {
         t->t.identify_dev(g->g, threshold, track, slot, embed, quality, emb, total, n, per_frame, stream_of, label, score, S(stream), root);
         return n;

@@ -323,7 +323,7 @@ class Recognizer {
 // TrackIdent and one fp32 sum row per (stream, slot), pooled, labelled against a gallery and carried forward by identify_dev.  Best
 // shot (set_bestshot): one int32 best_q per (stream, slot), kept by the update kernel when it is given the faces' qualities.
 // Re-linking (enable_relink): per stream a table of max_tracks + memory TrackLink records — the slots' rows, then a memory of lost
-// tracks with sums of its own — through which identify_dev's stage A resumes a lost track when its face comes back.
+// tracks with sums of its own — through which identify_dev's stage A resumes a lost track when its face comes back.  (tracker.cpp)
 class Gallery;
 class Tracker {
   public:
@@ -380,12 +380,14 @@ class Tracker {
   private:
     int* heads() const { return state_.as<int>(); }
     TrackState* slots() const { return reinterpret_cast<TrackState*>(state_.as<int>() + 2 * (size_t)streams_); }
+    std::vector<TrackState> slots_of(int stream);                // the slots of one stream, copied to the host; synchronous
+    const int* send_plan(StagedTable& table, const int* stream_of, int n, hipStream_t s);    // stream_of's plan through plan_ | iplan_
     int streams_;
     TrackParams p_;
     DevBuf state_, embed_, slot_;                                // [streams][2] heads, then [streams][max_tracks] slots
     bool bestshot_ = false;
     DevBuf best_, quality_;                                      // [streams][max_tracks] best_q / the pipeline's [n][per_frame] qualities
-    StagedTable plan_, iplan_;                                   // order[n], then starts[streams + 1] (update's / identify's)
+    StagedTable plan_, iplan_;                                   // order[n], starts[streams + 1] of update / identify (a queued update still reads its own)
     void clear_identity(int first, int count);
     int idim_ = 0, ipool_ = 0;
     DevBuf ident_, isum_;                                        // [streams][max_tracks] TrackIdent / [streams][max_tracks][idim_] sums

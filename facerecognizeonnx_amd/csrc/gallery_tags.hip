@@ -70,11 +70,10 @@ __global__ __launch_bounds__(256) void track_query_masks_kernel(const unsigned* 
     const int j1 = min(frame_off[f + 1], total);              // (qmask holds `total` words)
     for (int j = max(frame_off[f], 0); j < j1; ++j) qmask[j] = m;
 }
-void launch_track_query_masks(const unsigned* stream_mask, int streams, const int* order, const int* starts, const int* frame_off, int n,
-                              int total, unsigned* qmask, hipStream_t s) {
-    if (n <= 0) return;
-    hipLaunchKernelGGL(track_query_masks_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, stream_mask, streams, order, starts,
-                       frame_off, n, total, qmask);
+void launch_track_query_masks(const unsigned* stream_mask, int streams, const TrackCall& c, unsigned* qmask, hipStream_t s) {
+    if (c.n <= 0) return;
+    hipLaunchKernelGGL(track_query_masks_kernel, dim3((unsigned)((c.n + 255) / 256)), dim3(256), 0, s, stream_mask, streams, c.order, c.starts,
+                       c.frame_off, c.n, c.total, qmask);
 }
 
 }  // namespace fh

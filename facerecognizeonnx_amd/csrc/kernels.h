@@ -377,10 +377,6 @@ void gallery_debug_tag_skip(int on);                         // 0: tagged scans 
 void launch_tag_tile_or(const unsigned* tags, long G, long first, long n, unsigned* tile_or, hipStream_t s);
 // dst_tags[j] = OR of src_tags[order[i]], starts[j] <= i < starts[j + 1] (the inverted index of fh_gallery_group_ids), j < m
 void launch_fuse_tags(const unsigned* src_tags, const int* order, const long long* starts, long m, unsigned* dst_tags, hipStream_t s);
-// qmask[j] = stream_mask[stream of the frame that query j belongs to] for the `total` queries of a Tracker::identify_dev
-// (order / starts: the stream plan of track_plan.h on the device; frame_off [n + 1]: the frames' first queries)
-void launch_track_query_masks(const unsigned* stream_mask, int streams, const int* order, const int* starts, const int* frame_off, int n,
-                              int total, unsigned* qmask, hipStream_t s);
 
 // gallery_fuse.hip — template pooling (fh_gallery_fuse_ids): one wave per work item sums the rows src[order[begin + i]], i < count,
 // strictly in that order (p = row0; p = p + row1; ...), into row `out` of dst (final != 0; L2-normalised when `unit` and count > 1: a
@@ -485,6 +481,7 @@ void launch_select_faces(const FaceRec* det, const int* counts, int n, int per_f
 struct TrackState {         // layout of fh_track_state, 32 B; id = -1: a free slot
     int32_t id, x, y, w, h, last_seen, last_embed, hits;
 };
+constexpr TrackState kFreeTrack{-1, 0, 0, 0, 0, 0, 0, 0};
 struct TrackParams {
     int max_tracks;         // 1 .. 64 slots per stream (one lane each)
     float iou_thr;
@@ -511,18 +508,29 @@ struct TrackIdent {
     int32_t owner, n_emb, label;    // owner = the track id the entry belongs to, -1: none
     float score;
 };
-// frame_off[n + 1] = the exclusive prefix of the frames' flag counts: the rank of a flagged entry is frame_off[f] + the flags before it
-void launch_track_ranks(const int* embed, int n, int per_frame, int* frame_off, hipStream_t s);
+constexpr TrackIdent kFreeIdent{-1, 0, -1, -1.0f};
 constexpr int kTrackPoolLast = 0, kTrackPoolSum = 1, kTrackPoolWeighted = 2;     // enum fh_track_pool
-// stage A: one wave per (stream, slot), one more per stream for the untracked faces; writes queries[min(total, flags)][dim].  quality =
-// [n][per_frame], read only by kTrackPoolWeighted (which needs it).
-void launch_track_pool(TrackIdent* ident, float* sums, int streams, int max_tracks, int dim, int pool, const int* track, const int* slot,
-                       const int* embed, const int* quality, const int* frame_off, const float* emb, int total, int per_frame, const int* order,
-                       const int* starts, float* queries, hipStream_t s);
+struct TrackIdentState {
+    TrackIdent* ident;      // [streams][max_tracks]
+    float* sums;            // [streams][max_tracks][dim]
+    int streams, max_tracks, dim, pool;
+};
+// One identify call (Tracker::identify_dev) as its kernels see it: what the update wrote, the stream plan (track_plan.h), the ranks.
+struct TrackCall {
+    const int *track, *slot, *embed;    // [n][per_frame], the update's outputs
+    const int* quality;                 // [n][per_frame], read only by kTrackPoolWeighted (which needs it); else may be null
+    int* frame_off;                     // [n + 1] = the flags before each frame, written by launch_track_ranks: rank = frame_off[f] + those before it in f
+    const int *order, *starts;          // [n], [streams + 1], on the device
+    int n, per_frame, total;            // total = the embeddings given: a flagged entry of rank >= total is nobody's
+};
+void launch_track_ranks(const TrackCall& c, hipStream_t s);
+// stage A: one wave per (stream, slot), one more per stream for the untracked faces; emb [total][dim] -> queries[min(total, flags)][dim]
+void launch_track_pool(const TrackIdentState& st, const TrackCall& c, const float* emb, float* queries, hipStream_t s);
 // stage C: one wave per stream; ans_label / ans_score = [total] answers of the queries; label / score = [n][per_frame], written entirely
-void launch_track_propagate(TrackIdent* ident, int streams, int max_tracks, const int* track, const int* slot, const int* embed,
-                            const int* frame_off, const int* ans_label, const float* ans_score, int total, int per_frame, const int* order,
-                            const int* starts, int* label, float* score, hipStream_t s);
+void launch_track_propagate(const TrackIdentState& st, const TrackCall& c, const int* ans_label, const float* ans_score, int* label,
+                            float* score, hipStream_t s);
+// gallery_tags.hip, the tracker's watchlist per camera: qmask[j] = stream_mask[stream of the frame that query j belongs to], j < c.total
+void launch_track_query_masks(const unsigned* stream_mask, int streams, const TrackCall& c, unsigned* qmask, hipStream_t s);
 
 // Track re-linking (track_ident.hip; include/facehip.h, "track re-linking").  Per stream a table of max_tracks + memory records: rows
 // below max_tracks belong to the slots (their sums are the identity's `sums`), the rest is the memory of lost tracks (`msums`).
@@ -531,6 +539,7 @@ struct TrackLink {          // layout of fh_track_link, 32 B; owner = -1: a free
     float score;
     int32_t last_seen, links, pad;
 };
+constexpr TrackLink kFreeLink{-1, -1, 0, -1, -1.0f, 0, 0, 0};
 constexpr int kTrackLinkMemory = 256;                                            // memory rows per stream, at most
 struct TrackLinkParams {
     int memory;             // 0 .. kTrackLinkMemory
@@ -539,10 +548,8 @@ struct TrackLinkParams {
 };
 // stage A with re-linking on: one workgroup per stream; heads = the tracker's [streams][2] (frame_no, next_id) after the update.
 // Writes queries as launch_track_pool does (the untracked faces' copies included) and root[n][per_frame] entirely.
-void launch_track_link(TrackLink* links, TrackIdent* ident, float* sums, float* msums, const int* heads, int streams, int max_tracks,
-                       TrackLinkParams lp, int dim, int pool, const int* track, const int* slot, const int* embed, const int* quality,
-                       const int* frame_off, const float* emb, int total, int per_frame, const int* order, const int* starts, float* queries,
-                       int* root, hipStream_t s);
+void launch_track_link(const TrackIdentState& st, TrackLink* links, float* msums, const int* heads, TrackLinkParams lp, const TrackCall& c,
+                       const float* emb, float* queries, int* root, hipStream_t s);
 // re-linking off: root[i] = track[i] where slot[i] >= 0, else -1 (entries = n * per_frame)
 void launch_track_roots(const int* track, const int* slot, long entries, int* root, hipStream_t s);
 

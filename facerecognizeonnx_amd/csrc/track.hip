@@ -5,6 +5,7 @@
 
 #include "face_iou.h"
 #include "kernels.h"
+#include "track_dev.h"
 
 namespace fh {
 
@@ -42,7 +43,7 @@ __global__ __launch_bounds__(64) void track_update_kernel(int* __restrict__ head
     const int b = starts[s], e = starts[s + 1];
     if (b == e) return;                                                 // no frame of this stream in the call
     const bool usable = lane < p.max_tracks;
-    TrackState st{-1, 0, 0, 0, 0, 0, 0, 0};
+    TrackState st = kFreeTrack;
     if (usable) st = slots[(size_t)s * p.max_tracks + lane];
     constexpr bool bestshot = BESTSHOT;                                 // (the launcher: quality and best_q are both given)
     int bq = 0;
@@ -160,19 +161,8 @@ __global__ __launch_bounds__(256) void track_select_kernel(const FaceRec* __rest
                                                            const int* __restrict__ trk, int n, int per_frame, FaceRec* __restrict__ faces,
                                                            int* __restrict__ frame_of, int* __restrict__ track_of, int* __restrict__ total) {
     __shared__ int offs[4097];
-    for (int b = threadIdx.x; b < n; b += 256) {
-        int c = 0;
-        for (int j = 0; j < per_frame; ++j) c += embed[(size_t)b * per_frame + j] != 0;
-        offs[b + 1] = c;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int acc = 0;
-        offs[0] = 0;
-        for (int b = 1; b <= n; ++b) { acc += offs[b]; offs[b] = acc; }
-        total[0] = acc;
-    }
-    __syncthreads();
+    flagged_prefix(embed, n, per_frame, offs);
+    if (threadIdx.x == 0) total[0] = offs[n];
     for (int b = threadIdx.x; b < n; b += 256) {
         int o = offs[b];
         for (int j = 0; j < per_frame; ++j) {

@@ -10,83 +10,24 @@
 #include <hip/hip_runtime.h>
 
 #include "kernels.h"
+#include "track_dev.h"
 
 namespace fh {
 
-namespace {
-
-__device__ __forceinline__ float4 add4(const float4 a, const float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
-__device__ __forceinline__ float4 mul4(const float w, const float4 a) { return make_float4(w * a.x, w * a.y, w * a.z, w * a.w); }
-__device__ __forceinline__ float wave_sum(float s) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-    return s;
-}
-
-// The entries of frames order[b .. e) in time order, 64 per round, one per lane.  per_frame <= 64: a round holds the next 64 / per_frame
-// whole frames, lane = k * per_frame + j; otherwise a round is one 64-entry piece of one frame.  body(valid, k, nk, idx, flagged, rank)
-// is called by the WHOLE wave once per round: k = the lane's frame within the round (nk of them), idx = f * per_frame + j, rank = the
-// entry's position among the call's flagged entries in (frame, slot) order (meaningful where flagged).  Every loop bound is uniform.
-template <class Body>
-__device__ __forceinline__ void walk_entries(const int* __restrict__ order, int b, int e, int per_frame, const int* __restrict__ embed,
-                                             const int* __restrict__ frame_off, int lane, Body&& body) {
-    if (per_frame <= 64) {
-        const int G = 64 / per_frame, k = lane / per_frame, j = lane - k * per_frame;
-        const unsigned long long before = ((1ull << j) - 1ull) << (k * per_frame);      // the lanes of my frame in front of me
-        for (int i0 = b; i0 < e; i0 += G) {
-            const int nk = min(G, e - i0);
-            const bool valid = k < nk;
-            const int f = valid ? order[i0 + k] : 0;
-            const size_t idx = (size_t)f * per_frame + j;
-            const bool fl = valid && embed[idx] != 0;
-            const unsigned long long flm = __ballot(fl);
-            body(valid, k, nk, idx, fl, frame_off[f] + __popcll(flm & before));
-        }
-    } else {
-        for (int i = b; i < e; ++i) {
-            const int f = order[i];
-            int base = frame_off[f];
-            for (int j0 = 0; j0 < per_frame; j0 += 64) {
-                const bool valid = j0 + lane < per_frame;
-                const size_t idx = (size_t)f * per_frame + j0 + lane;
-                const bool fl = valid && embed[idx] != 0;
-                const unsigned long long flm = __ballot(fl);
-                body(valid, 0, 1, idx, fl, base + __popcll(flm & ((1ull << lane) - 1ull)));
-                base += __popcll(flm);
-            }
-        }
-    }
-}
-
-}  // namespace
-
-// ------------------------------------------------------------------------------------------
 // The flagged entries before each frame (track_select_kernel's prefix, kept): frame_off[0 .. n].  n <= 4096 frames.
-// ------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void track_ranks_kernel(const int* __restrict__ embed, int n, int per_frame, int* __restrict__ frame_off) {
     __shared__ int offs[4097];
-    for (int b = threadIdx.x; b < n; b += 256) {
-        int c = 0;
-        for (int j = 0; j < per_frame; ++j) c += embed[(size_t)b * per_frame + j] != 0;
-        offs[b + 1] = c;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int acc = 0;
-        offs[0] = 0;
-        for (int b = 1; b <= n; ++b) { acc += offs[b]; offs[b] = acc; }
-    }
-    __syncthreads();
+    flagged_prefix(embed, n, per_frame, offs);
     for (int b = threadIdx.x; b <= n; b += 256) frame_off[b] = offs[b];
 }
 
 // ------------------------------------------------------------------------------------------
 // Stage A.  Wave (s, l), l < max_tracks, owns slot l of stream s: it picks the flagged entries whose slot is l with a ballot and runs
-// their chain in time order — (re)open: sum = row, query = row verbatim; else sum += row (POOL_SUM; POOL_LAST: sum = row) and the
-// query is the normalised sum.  POOL_WEIGHTED is POOL_SUM with every row entering the sum as wq * row, wq = (float)max(quality, 1): one
-// multiply, then one add per component (the file is built without contraction).  Wave (s, max_tracks) copies the rows of the stream's
-// untracked faces.  Each lane owns the 16-byte
-// columns lane, lane + 64, ...; the sum row lives in the state and is read, added to and written back by the lane that owns the column.
+// their chain in time order, every face through pool_row (track_dev.h) — (re)open: sum = row, query = row verbatim; else sum += row
+// (POOL_SUM; POOL_LAST: sum = row, query = row) and the query is the normalised sum.  POOL_WEIGHTED is POOL_SUM with every row entering
+// the sum as wq * row, wq = (float)max(quality, 1): one multiply, then one add per component (the file is built without contraction).
+// Wave (s, max_tracks) copies the rows of the stream's untracked faces.  Each lane owns the 16-byte columns lane, lane + 64, ...; the
+// sum row lives in the state and is read, added to and written back by the lane that owns the column.
 // A flagged entry of rank >= total is nobody's.
 // ------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void track_pool_kernel(TrackIdent* __restrict__ ident, float4* __restrict__ sums, int streams,
@@ -122,27 +63,10 @@ __global__ __launch_bounds__(256) void track_pool_kernel(TrackIdent* __restrict_
             float4* const q = queries + (size_t)q_e * vpr;
             if (my < 0) {
                 for (int c = lane; c < vpr; c += 64) q[c] = row[c];
-            } else if (owner != t_e || pool == kTrackPoolLast) {
-                if (owner != t_e) { owner = t_e; n_emb = 1; } else ++n_emb;
-                for (int c = lane; c < vpr; c += 64) {
-                    const float4 v = row[c];
-                    sm[c] = weighted ? mul4(wq, v) : v;
-                    q[c] = v;
-                }
             } else {
-                ++n_emb;
-                float sq = 0.f;
-                for (int c = lane; c < vpr; c += 64) {
-                    const float4 a = add4(sm[c], weighted ? mul4(wq, row[c]) : row[c]);
-                    sm[c] = a;
-                    sq += a.x * a.x + a.y * a.y + a.z * a.z + a.w * a.w;
-                }
-                const float norm = sqrtf(wave_sum(sq));
-                const bool scale = norm > 0.f;                           // false for a zero sum and for NaN
-                for (int c = lane; c < vpr; c += 64) {                   // (every lane re-reads the sums it stored itself)
-                    const float4 a = sm[c];
-                    q[c] = scale ? make_float4(a.x / norm, a.y / norm, a.z / norm, a.w / norm) : a;
-                }
+                const bool open = owner != t_e;
+                if (open) { owner = t_e; n_emb = 1; } else ++n_emb;
+                pool_row(sm, sm, row, q, nullptr, wq, weighted, !open && pool != kTrackPoolLast, lane, vpr);
             }
         }
     });
@@ -164,7 +88,7 @@ __global__ __launch_bounds__(64) void track_propagate_kernel(TrackIdent* __restr
     const int b = starts[s], e = starts[s + 1];
     if (b == e) return;
     const bool usable = lane < max_tracks;
-    TrackIdent st{-1, 0, -1, -1.0f};
+    TrackIdent st = kFreeIdent;
     if (usable) st = ident[(size_t)s * max_tracks + lane];
 
     walk_entries(order, b, e, per_frame, embed, frame_off, lane, [&](bool valid, int k, int nk, size_t idx, bool fl, int rank) {
@@ -212,10 +136,6 @@ __global__ __launch_bounds__(64) void track_propagate_kernel(TrackIdent* __restr
 // No atomics, nothing that depends on timing: every barrier is reached by all four waves under conditions that all four evaluate alike.
 // ------------------------------------------------------------------------------------------
 namespace {
-// component-wise choice (a float4 chosen whole at run time would live in scratch)
-__device__ __forceinline__ float4 sel4(bool c, const float4 a, const float4 b) {
-    return make_float4(c ? a.x : b.x, c ? a.y : b.y, c ? a.z : b.z, c ? a.w : b.w);
-}
 // a candidate (score, owner, row); row < 0 = none
 __device__ __forceinline__ void link_put(TrackLink& d, int owner, int root, int n_emb, int label, float score, int last_seen, int links) {
     d.owner = owner; d.root = root; d.n_emb = n_emb; d.label = label; d.score = score; d.last_seen = last_seen; d.links = links; d.pad = 0;
@@ -303,27 +223,12 @@ __global__ __launch_bounds__(256) void track_link_kernel(TrackLink* __restrict__
                 float4* const q = queries + (size_t)q_e * vpr;
                 float4* const sm = slot_sums + (size_t)s_e * vpr;
                 const bool open = __shfl(owner, s_e) != t_e;
-                if (!open) {                                             // 2. a continued track: track_pool_kernel's arithmetic
+                if (!open) {                                             // 2. a continued track
                     if (wave == 0) {
                         tab[s_e].n_emb += 1;
                         tab[s_e].last_seen = t;
                         if (lane == src) root_out = tab[s_e].root;
-                        if (pool == kTrackPoolLast) {
-                            for (int c = lane; c < vpr; c += 64) { const float4 v = row[c]; sm[c] = v; q[c] = v; }
-                        } else {
-                            float sq = 0.f;
-                            for (int c = lane; c < vpr; c += 64) {
-                                const float4 a = add4(sm[c], weighted ? mul4(wq, row[c]) : row[c]);
-                                sm[c] = a;
-                                sq += a.x * a.x + a.y * a.y + a.z * a.z + a.w * a.w;
-                            }
-                            const float norm = sqrtf(wave_sum(sq));
-                            const bool scale = norm > 0.f;
-                            for (int c = lane; c < vpr; c += 64) {
-                                const float4 a = sm[c];
-                                q[c] = scale ? make_float4(a.x / norm, a.y / norm, a.z / norm, a.w / norm) : a;
-                            }
-                        }
+                        pool_row(sm, sm, row, q, nullptr, wq, weighted, pool != kTrackPoolLast, lane, vpr);
                     }
                     continue;
                 }
@@ -405,32 +310,10 @@ __global__ __launch_bounds__(256) void track_link_kernel(TrackLink* __restrict__
                         to = b_row;
                     }
                 }
-                // the sums: every column is read whole before it is written, by the lane that owns it, so the rows may coincide
-                const float4* const cs = w_row >= 0 ? sum_row(w_row) : sm;
-                float4* const ts = to >= 0 ? sum_row(to) : sm;
-                const bool pooled = w_row >= 0 && pool != kTrackPoolLast;
-                float sq = 0.f;
-                for (int c = lane; c < vpr; c += 64) {
-                    const float4 a = sm[c], base = cs[c], v = row[c];
-                    const float4 in = sel4(weighted, mul4(wq, v), v);
-                    if (to >= 0) ts[c] = a;
-                    if (pooled) {
-                        const float4 n4 = add4(base, in);
-                        sm[c] = n4;
-                        sq += n4.x * n4.x + n4.y * n4.y + n4.z * n4.z + n4.w * n4.w;
-                    } else {
-                        sm[c] = sel4(w_row >= 0, v, in);               // a resumed POOL_LAST track: sum = row; a new one: as today
-                        q[c] = v;
-                    }
-                }
-                if (pooled) {
-                    const float norm = sqrtf(wave_sum(sq));
-                    const bool scale = norm > 0.f;
-                    for (int c = lane; c < vpr; c += 64) {
-                        const float4 a = sm[c];
-                        q[c] = scale ? make_float4(a.x / norm, a.y / norm, a.z / norm, a.w / norm) : a;
-                    }
-                }
+                // the sums: the old ones retire to row `to`, the face joins the winner's (a resumed POOL_LAST track and a new one: sum =
+                // the face).  pool_row reads every column whole before it writes it, so the three rows may coincide
+                pool_row(sm, w_row >= 0 ? sum_row(w_row) : sm, row, q, to >= 0 ? sum_row(to) : nullptr, wq, weighted,
+                         w_row >= 0 && pool != kTrackPoolLast, lane, vpr);
                 if (to >= 0) link_put(tab[to], o_owner, o_root, o_n, o_label, o_score, o_seen, o_links);
                 link_put(tab[s_e], t_e, r_root, r_n, r_label, r_score, t, r_links);
                 if (lane == src) root_out = r_root;
@@ -456,37 +339,34 @@ __global__ __launch_bounds__(256) void track_roots_kernel(const int* __restrict_
     if (i < entries) root[i] = slot[i] >= 0 ? track[i] : -1;
 }
 
-void launch_track_link(TrackLink* links, TrackIdent* ident, float* sums, float* msums, const int* heads, int streams, int max_tracks,
-                       TrackLinkParams lp, int dim, int pool, const int* track, const int* slot, const int* embed, const int* quality,
-                       const int* frame_off, const float* emb, int total, int per_frame, const int* order, const int* starts, float* queries,
-                       int* root, hipStream_t s) {
-    hipLaunchKernelGGL(track_link_kernel, dim3(streams), dim3(256), 0, s, links, ident, reinterpret_cast<float4*>(sums),
-                       reinterpret_cast<float4*>(msums), heads, max_tracks, lp, dim / 4, pool, track, slot, embed, quality, frame_off,
-                       reinterpret_cast<const float4*>(emb), total, per_frame, order, starts, reinterpret_cast<float4*>(queries), root);
+// The launchers unpack the call into the kernels' own parameters: a pointer that arrives inside a struct loses its __restrict__.
+void launch_track_link(const TrackIdentState& st, TrackLink* links, float* msums, const int* heads, TrackLinkParams lp, const TrackCall& c,
+                       const float* emb, float* queries, int* root, hipStream_t s) {
+    hipLaunchKernelGGL(track_link_kernel, dim3(st.streams), dim3(256), 0, s, links, st.ident, reinterpret_cast<float4*>(st.sums),
+                       reinterpret_cast<float4*>(msums), heads, st.max_tracks, lp, st.dim / 4, st.pool, c.track, c.slot, c.embed, c.quality,
+                       c.frame_off, reinterpret_cast<const float4*>(emb), c.total, c.per_frame, c.order, c.starts,
+                       reinterpret_cast<float4*>(queries), root);
 }
 
 void launch_track_roots(const int* track, const int* slot, long entries, int* root, hipStream_t s) {
     hipLaunchKernelGGL(track_roots_kernel, dim3((unsigned)((entries + 255) / 256)), dim3(256), 0, s, track, slot, entries, root);
 }
 
-void launch_track_ranks(const int* embed, int n, int per_frame, int* frame_off, hipStream_t s) {
-    hipLaunchKernelGGL(track_ranks_kernel, dim3(1), dim3(256), 0, s, embed, n, per_frame, frame_off);
+void launch_track_ranks(const TrackCall& c, hipStream_t s) {
+    hipLaunchKernelGGL(track_ranks_kernel, dim3(1), dim3(256), 0, s, c.embed, c.n, c.per_frame, c.frame_off);
 }
 
-void launch_track_pool(TrackIdent* ident, float* sums, int streams, int max_tracks, int dim, int pool, const int* track, const int* slot,
-                       const int* embed, const int* quality, const int* frame_off, const float* emb, int total, int per_frame, const int* order,
-                       const int* starts, float* queries, hipStream_t s) {
-    const int waves = streams * (max_tracks + 1);
-    hipLaunchKernelGGL(track_pool_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, ident, reinterpret_cast<float4*>(sums), streams,
-                       max_tracks, dim / 4, pool, track, slot, embed, quality, frame_off, reinterpret_cast<const float4*>(emb), total, per_frame,
-                       order, starts, reinterpret_cast<float4*>(queries));
+void launch_track_pool(const TrackIdentState& st, const TrackCall& c, const float* emb, float* queries, hipStream_t s) {
+    const int waves = st.streams * (st.max_tracks + 1);
+    hipLaunchKernelGGL(track_pool_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, st.ident, reinterpret_cast<float4*>(st.sums),
+                       st.streams, st.max_tracks, st.dim / 4, st.pool, c.track, c.slot, c.embed, c.quality, c.frame_off,
+                       reinterpret_cast<const float4*>(emb), c.total, c.per_frame, c.order, c.starts, reinterpret_cast<float4*>(queries));
 }
 
-void launch_track_propagate(TrackIdent* ident, int streams, int max_tracks, const int* track, const int* slot, const int* embed,
-                            const int* frame_off, const int* ans_label, const float* ans_score, int total, int per_frame, const int* order,
-                            const int* starts, int* label, float* score, hipStream_t s) {
-    hipLaunchKernelGGL(track_propagate_kernel, dim3(streams), dim3(64), 0, s, ident, max_tracks, track, slot, embed, frame_off, ans_label,
-                       ans_score, total, per_frame, order, starts, label, score);
+void launch_track_propagate(const TrackIdentState& st, const TrackCall& c, const int* ans_label, const float* ans_score, int* label,
+                            float* score, hipStream_t s) {
+    hipLaunchKernelGGL(track_propagate_kernel, dim3(st.streams), dim3(64), 0, s, st.ident, st.max_tracks, c.track, c.slot, c.embed,
+                       c.frame_off, ans_label, ans_score, c.total, c.per_frame, c.order, c.starts, label, score);
 }
 
 }  // namespace fh

@@ -283,6 +283,66 @@ def test_random_rows_follow_the_stated_order(gals, dim, pool):
         assert model.links_made >= 1 and "refused" in model.events                # (the premise; also held without a GPU)
 
 
+# ---------------------------------------------------------------------------------------------- 4b. one pooling step
+def run_steady(trk, clip, cuts, gal, rows, qual, weighted):
+    """The clip through update + identify_link in calls of `cuts` frames: the queries, labels, scores and roots of all calls, in order."""
+    out = dict(queries=[], label=[], score=[], root=[], track=[])
+    per, a, at = clip.per_frame, 0, 0
+    for frames in cuts:
+        part, n = clip.sub(a, a + frames), frames
+        i32 = lambda v: torch.full((n, per), v, dtype=torch.int32, device="cuda")      # noqa: E731
+        track, embed, slot, label, root = i32(77), i32(77), i32(77), i32(77), i32(77)
+        score = torch.full((n, per), 7.0, device="cuda")
+        d, cnt, d_q = dev_records(part.det), dev(part.counts), dev(qual[a:a + n])
+        assert trk.update_dev(d.data_ptr(), cnt.data_ptr(), n, per, track.data_ptr(), embed.data_ptr(), slot_ptr=slot.data_ptr(),
+                              quality_ptr=d_q.data_ptr() if weighted else None) == n
+        torch.cuda.synchronize()
+        total = int(embed.cpu().numpy().sum())
+        assert total == 2 * n                                                     # refresh 1: both faces of every frame are pooled
+        d_emb = dev(rows[at:at + total])
+        assert trk.identify_dev(gal.g, THRESHOLD, track.data_ptr(), slot.data_ptr(), embed.data_ptr(), d_emb.data_ptr(), total, n, per,
+                                label.data_ptr(), score.data_ptr(), quality_ptr=d_q.data_ptr(), root_ptr=root.data_ptr()) == n
+        torch.cuda.synchronize()
+        out["queries"].append(from_device(trk.queries_ptr(), (total, gal.dim)))
+        for key, t in (("label", label), ("score", score), ("root", root), ("track", track)):
+            out[key].append(t.cpu().numpy())
+        a, at = a + n, at + total
+    return {k: np.concatenate(v) for k, v in out.items()}
+
+
+@pytest.mark.parametrize("cuts", [(6,), (2, 4)])
+@pytest.mark.parametrize("pool", POOLS)
+@pytest.mark.parametrize("dim", (64, 192))
+def test_continued_tracks_pool_alike_with_relinking_off_and_on(gals, dim, pool, cuts):
+    """Two faces that never leave, pooled in every frame (refresh 1): the first frame opens both tracks, the other five continue them.
+    Nothing is ever lost, so re-linking has nothing to link, and the pool kernel (re-linking off) and the link kernel (on) must write
+    the same queries, labels, scores and sums, bit for bit: both take the one pooling step of track_dev.h."""
+    clip = lc.Clip([[(0, lc.A), (1, lc.B)]] * 6, 3)
+    kw = dict(streams=1, max_tracks=4, iou_thr=0.3, max_missed=1, refresh=1)
+    rows = lc.random_rows(clip.person.reshape(-1)[clip.person.reshape(-1) >= 0], dim, seed=dim)
+    qual = qualities(clip)
+    runs = {}
+    for on in (False, True):
+        trk = fa.Tracker(**kw)
+        if pool == lm.POOL_WEIGHTED:
+            trk.clear_bestshot()                                                  # opts the tracker into the quality feature
+        trk.enable_identity(dim, pool)
+        if on:
+            trk.enable_relink(4, 0.6, 8)
+        runs[on] = (trk, run_steady(trk, clip, cuts, gals(dim), rows, qual, pool == lm.POOL_WEIGHTED))
+    (off_trk, off), (on_trk, on) = runs[False], runs[True]
+    assert set(off["track"].reshape(-1)) == {-1, 0, 1}                            # (the premise: two tracks, opened once)
+    for key in ("track", "queries", "label", "score"):
+        assert off[key].tobytes() == on[key].tobytes(), key
+    assert np.array_equal(on["root"], on["track"]) and np.array_equal(off["root"], off["track"])    # every root is the entry's own track id
+    (recs, sums), (on_recs, on_sums), (link_recs, link_sums) = (off_trk.identity(0, sums=True), on_trk.identity(0, sums=True),
+                                                                on_trk.links(0, sums=True))
+    assert len(recs) == 2 and recs.tobytes() == on_recs.tobytes() and sums.tobytes() == on_sums.tobytes()
+    assert list(recs["id"]) == [0, 1] and list(recs["n_emb"]) == [6, 6]
+    assert sums.tobytes() == link_sums[:2].tobytes() and not link_sums[2:4].any() and sums.any()    # the slots' rows; free rows report zero
+    assert list(link_recs["owner"][:4]) == [0, 1, -1, -1] and list(link_recs["n_emb"][:2]) == [6, 6]
+
+
 # ---------------------------------------------------------------------------------------------- 5. off, errors, state
 def test_relink_off_is_the_old_call_plus_own_roots(gals):
     case, dim = tc.Case("three_streams_exhausted"), 192
