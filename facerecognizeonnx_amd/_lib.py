@@ -282,6 +282,7 @@ PROTOTYPES = {
     "fh_rec_get_wino_x3": (_i, [_vp]),
     "fh_rec_get_conv_x3": (_i, [_vp]),
     "fh_rec_get_pw_x3": (_i, [_vp]),
+    "fh_rec_get_wino2_x3": (_i, [_vp]),
     "fh_det_set_x3": (_i, [_vp, _i]),
     "fh_det_get_x3": (_i, [_vp]),
     "fh_rec_set_shortcut_fold": (_i, [_vp, _i]),
@@ -315,6 +316,8 @@ PROTOTYPES = {
     "fh_debug_wino_gemm_rows": (_ll, [_i, _i, _i, _i, _i, _i]),
     "fh_debug_wino_gemm_dev": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "fh_debug_wino2_clock_mhz": (_d, []),
+    "fh_conv_wino2_prec_dev": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "fh_debug_wino2_pack_x3": (_i, [_vp, _i, _i, _vp]),
     "fh_conv_wino2_dev": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "fh_conv_wino2_ex_dev": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "fh_conv_wt_rows": (_i, [_i]),

@@ -1920,6 +1920,7 @@ int fh_rec_set_wino_x3(fh_rec* r, int on) {
 int fh_rec_get_wino_x3(fh_rec* r) { return r && r->rec.net().wino_x3() ? 1 : 0; }
 int fh_rec_get_conv_x3(fh_rec* r) { return r ? r->rec.net().conv_x3_layers() : 0; }
 int fh_rec_get_pw_x3(fh_rec* r) { return r ? r->rec.net().pw_x3_layers() : 0; }
+int fh_rec_get_wino2_x3(fh_rec* r) { return r ? r->rec.net().wino2_x3_layers() : 0; }
 // the detector's 1x1 stride-1 convolutions: 1 = three-piece bf16 (conv_pw_x3_kernel where conv_pw_x3_bn / conv_pw_x3_pays admit the launch; the
 // default unless FACEHIP_DET_X3=0), 0 = the native f32 kernels everywhere.  Returns the number of layers that have the form (0 with on = 0), or
 // an error code.  Synchronous on first use (the split weights).
@@ -2162,6 +2163,46 @@ int fh_conv_wino2_dev(const float* d_in, const float* w_ohwi, const float* d_bia
     return fh_conv_wino2_ex_dev(d_in, w_ohwi, d_bias, d_slope, d_res, d_out, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, batch, h, w,
                                 cin, cout, act, bias_cls, stream);
 }
+// The plain form of the same layer with a precision argument: FH_PREC_FP32 = wino2_kernel, FH_PREC_F32X3 = wino2_x3_kernel on an image
+// packed here as the engine packs it (forced: wino2_x3_pays is the engine's question, the form's existence this call's)
+int fh_conv_wino2_prec_dev(const float* d_in, const float* w_ohwi, const float* d_bias, const float* d_slope, const float* d_res, float* d_out,
+                           float* d_out2, const float* d_s2, const float* d_t2, int batch, int h, int w, int cin, int cout, int act, int bias_cls,
+                           int precision, int cus, void* stream) {
+    if (!d_in || !w_ohwi || batch <= 0 || h <= 0 || w <= 0 || cin <= 0 || cout <= 0 || cus < 0 || (!d_out && !d_out2) ||
+        (precision != FH_PREC_FP32 && precision != FH_PREC_F32X3))
+        return arg_error("fh_conv_wino2_prec_dev: bad argument");
+    if (d_out2 && (!d_s2 || !d_t2)) return arg_error("fh_conv_wino2_prec_dev: a second output needs its scale and shift");
+    if (precision == FH_PREC_F32X3 && !fh::wino2_x3_shape_ok(cin, cout))
+        return arg_error("fh_conv_wino2_prec_dev: this layer has no three-piece bf16 form (it needs cin == 64 and cout % 64 == 0)");
+    if (cin != 64 || cout % 64) return arg_error("fh_conv_wino2_prec_dev: plain layers need cin == 64 and cout % 64 == 0");
+    Owns owns(nullptr);
+    return guarded([&] {
+        fh::ConvArgs a{};
+        a.in = d_in; a.bias = d_bias; a.slope = d_slope; a.res = d_res; a.out1 = d_out; a.out2 = d_out2; a.s2 = d_s2; a.t2 = d_t2;
+        a.B = batch; a.H = h; a.W = w; a.Ho = h; a.Wo = w; a.Cin = cin; a.Cout = cout; a.ks = 3; a.stride = 1; a.pad = 1;
+        a.act = act; a.bias_cls = bias_cls; a.res_mode = d_res ? (int)fh::ResMode::SAME : (int)fh::ResMode::NONE;
+        a.cus = cus;
+        const bool x3 = precision == FH_PREC_F32X3;
+        if (!(x3 ? fh::wino2_x3_ok(a) : fh::wino2_ok(a))) throw std::runtime_error("fh_conv_wino2_prec_dev: layer shape not supported by the fused F(2x2) kernel");
+        std::vector<float> u(x3 ? fh::wino2_x3_weight_floats(cin, cout) : fh::wino2_weight_floats(cin, cout));
+        if (x3) fh::wino2_pack_weights_x3(w_ohwi, cout, cin, reinterpret_cast<unsigned short*>(u.data()));
+        else fh::wino2_pack_weights(w_ohwi, cout, cin, u.data());
+        fh::DevBuf dU;
+        dU.ensure(u.size() * sizeof(float));
+        FH_HIP(hipMemcpy(dU.p, u.data(), u.size() * sizeof(float), hipMemcpyHostToDevice));
+        a.wt = dU.as<float>();
+        if (x3) fh::launch_wino2_x3(a, S(stream)); else fh::launch_wino2(a, S(stream));
+        FH_HIP(hipGetLastError());
+        FH_HIP(hipStreamSynchronize(S(stream)));                 // the weight image dies with this scope
+        return 0;
+    });
+}
+// wino2_pack_weights_x3 on the host, for the layout tests: dst = 16 * cin * cout * 3 bf16 words
+int fh_debug_wino2_pack_x3(const float* w_ohwi, int cout, int cin, unsigned short* dst) {
+    if (!w_ohwi || !dst || !fh::wino2_x3_shape_ok(cin, cout))
+        return arg_error("fh_debug_wino2_pack_x3: this layer has no three-piece bf16 form (it needs cin == 64 and cout % 64 == 0)");
+    return guarded([&] { fh::wino2_pack_weights_x3(w_ohwi, cout, cin, dst); return 0; });
+}
 double fh_debug_wino2_clock_mhz(void) { return fh::wino2_debug_clock_mhz(); }
 int fh_conv_wt_rows(int cout) { return fh::conv_wt_rows(cout); }
 int fh_conv_pack_weights(const float* w_ohwi, int cout, int cin, int ksize, float* dst_packed) {
@@ -2228,6 +2269,8 @@ int fh_debug_conv_plan(int what, const int* in, int n_in, long long* out, int n_
         out[2] = bn && fh::conv_pw_x3_pays(out[1], g.Kpad, g.Cout, in[10], knobs) ? 1 : 0;
     } else if (what == 7 && need(4, 1) && in[0] >= 0 && in[1] > 0 && in[2] > 0 && in[3] > 0) {
         out[0] = fh::conv_pw_x3_pays(in[0], in[1], in[2], in[3], knobs) ? 1 : 0;
+    } else if (what == 8 && need(2, 1) && in[0] >= 0 && in[1] > 0) {
+        out[0] = fh::wino2_x3_pays(in[0], in[1], knobs) ? 1 : 0;
     } else {
         return arg_error("fh_debug_conv_plan: unknown question, wrong array lengths or a non-positive size");
     }

@@ -30,6 +30,7 @@ struct ConvKnobs {
                              // 2 = x3 wherever the layer has the form, whatever conv_x3_pays would say (A / B timing)
     int pw_x3 = 1;           // FACEHIP_PW_X3: the same three values for the 1x1 stride-1 layers (conv_pw_x3_pays)
     int pw_x3_bn = 0;        // FACEHIP_PW_X3_BN: 64 = 64-wide x3 tiles where the rule would take 32-wide ones (A / B timing)
+    int wino2_x3 = 1;        // FACEHIP_WINO2_X3: the same three values for the fused F(2x2) Winograd layers (wino2_x3_pays)
 };
 inline const ConvKnobs& conv_knobs() {
     static const ConvKnobs k = [] {
@@ -38,6 +39,7 @@ inline const ConvKnobs& conv_knobs() {
         env("FACEHIP_SK_B_RATIO", v.sk_b_ratio); env("FACEHIP_SK_MIN_OWNER", v.sk_min_owner); env("FACEHIP_SK_MARGIN", v.sk_margin2);
         env("FACEHIP_TALL_TAIL_Q", v.tall_tail_q); env("FACEHIP_CONV_PW", v.conv_pw); env("FACEHIP_CONV_TALL", v.conv_tall);
         env("FACEHIP_EP_DIRECT", v.ep_direct); env("FACEHIP_CONV_X3", v.conv_x3); env("FACEHIP_PW_X3", v.pw_x3); env("FACEHIP_PW_X3_BN", v.pw_x3_bn);
+        env("FACEHIP_WINO2_X3", v.wino2_x3);
         return v;
     }();
     return k;
@@ -121,6 +123,19 @@ inline bool conv_pw_x3_pays(long tiles, int Kpad, int Cout, int cus, const ConvK
     if (!k.pw_x3 || Cout <= 0 || (Cout & 3) || Kpad <= 0 || Kpad % 32 || cus <= 0) return false;
     if (k.pw_x3 == 2) return true;
     return tiles >= (long)cus * (Cout < 32 ? 2 : 1) && Kpad >= PW_X3_MIN_KPAD;
+}
+
+// wino2_x3_kernel (conv_wino2.hip: the fused F(2x2) Winograd layer on three bf16 pieces): does it pay for a launch of `workgroups`
+// (tile groups x 64-channel column tiles) on `cus` CUs?  FACEHIP_WINO2_X3: 0 = never, 2 = wherever the form exists (A / B timing),
+// 1 = the measured rule.  Measured on 56x56x64 -> 64 / 128, 112x112x64 -> 64 and 80x80x64 -> 64 at B = 8, 64, 128, 256, f32 against x3 in
+// three alternating runs on 256 CUs (profiles/wino2_x3.md): every launch gains, 0.75-0.89 of the f32 time, the smallest one too (B = 8 on
+// 56 x 56: 392 workgroups, 29.6 -> 24.7 us).  So the form is on from there up — three workgroups per two CUs — and what lies below, which
+// nothing measured, stays on the f32 kernel.  Monotone in `workgroups`.  Whether the layer runs on the fused form at all is decided before
+// this, by wino2_blocks (engine.cpp).
+inline bool wino2_x3_pays(long workgroups, int cus, const ConvKnobs& k) {
+    if (!k.wino2_x3 || workgroups <= 0 || cus <= 0) return false;
+    if (k.wino2_x3 == 2) return true;
+    return workgroups * 2 >= (long)cus * 3;
 }
 
 // conv_tall_kernel's take-over of a 3x3 stride-1 pad-1 layer with Cin % 32 == 0 on a map up to 112 wide, for the 256x64 and 128x32

@@ -321,6 +321,227 @@ __global__ __launch_bounds__(64 * NW, NW == 1 ? 2 : 3) void wino2_kernel(const C
 #endif
 }
 
+// ------------------------------------------------------------------------------------------------------------------------------------
+// wino2_x3_kernel — the same algorithm with its products on v_mfma_f32_16x16x32_bf16: fp32 products from three bf16 pieces per operand
+// and six MFMAs per 32-deep step (gemm_tile.h: THE SPLIT RULE, THE PRODUCT ORDER), 0.375 of the f32 instruction's matrix-pipe cycles.
+// Plain layers only (Cout % 64 == 0, no merged outputs).  What differs from wino2_kernel is the K loop and the weight image alone:
+//   * the bf16 instruction's C layout (col = lane & 15, row = 4 (lane >> 4) + reg) is the f32 one's, so lane = tile, accumulator block
+//     cb = channels 16 cb + 4 kq + e, y_update and the epilogue are the f32 kernel's;
+//   * K ORDER BY PERMUTATION: a sum over K does not care which eight channels a lane holds as long as A and B agree.  The patch reads stay
+//     exactly wino2_kernel's (the same rb[], the same swizzle, column 4 g + kq: conflict-free, scripts/wino2_banks.py); step s in {0, 1}
+//     of a frequency takes the groups g = 2 s and 2 s + 1, so B element j of lane (tn, kq) is channel 16 (2 s + (j >> 2)) + 4 kq + (j & 3)
+//     and the weight image (wino2_pack_weights_x3) carries the same permutation;
+//   * per step: 8 ds_read_b128 -> two float4 of V (three adds each, wino2_kernel's order) -> gemm_split3 on the pair -> 6 CB MFMAs,
+//     product-outer, cb-inner: l h, h l, m m, m h, h m, h h (weight piece first);
+//   * REGISTERS: ONE patch buffer — the next step's eight reads go out as soon as V is formed and land under the split and the MFMAs
+//     (32 registers instead of the 64 of wino2_kernel's double buffer); the weight ring stays two steps deep (2 x 3 x CB x 4 registers).
+// No barrier but the halo's, one basic block: every trap of docs/kernels.md 3.1l applies (pinned updates and V, sched_barrier around the
+// MFMA block, opaque scalars in the addresses, the 256-byte LDS alignment check in the launcher).
+
+__device__ __forceinline__ constexpr int w2_key(int pr, int pc) { return 2 * ((pc + 4 * (pr & 1)) & 7); }
+
+// the halo of tile group (gn, gy, gx) -> LDS, wino2_kernel's layout (its comment at "---- halo")
+template <int NW>
+__device__ __forceinline__ void w2_load_halo(const ConvArgs& p, char* const halo, const int lane, const int wv, const int gn, const int gy, const int gx) {
+    const int H = p.H, W = p.W;
+    const int col = lane & 15, pl = lane >> 4;
+    const int y0 = 8 * gy - 1 + (pl >> 1), x0 = 8 * gx - 1 + (pl & 1);
+    const float* const img = p.in + ((size_t)gn * H * W + (size_t)y0 * W + x0) * 64;   // (may point in front of the image: only dereferenced when in range)
+#pragma unroll
+    for (int i = 0; i < 25; ++i) {
+        const int pr = i / 5, pc = i - 5 * pr;
+        const int y = y0 + 2 * pr, x = x0 + 2 * pc;
+        const bool ok = (unsigned)y < (unsigned)H && (unsigned)x < (unsigned)W;
+        if (NW > 1 && (i % NW) != wv) continue;                            // (wave-uniform: the waves of a workgroup take alternate pieces)
+        lds_dma16(ok ? img + ((long)2 * pr * W + 2 * pc) * 64 + ((col ^ w2_key(pr, pc)) << 2) : p.zeros, halo + i * 1024);
+    }
+}
+
+// M of frequency F -> the four output accumulators with A^T's coefficients, pinned (wino2_kernel's y_update)
+template <int F, int CB>
+__device__ __forceinline__ void w2_y_update(v4f (&Y)[2][2][CB], const v4f (&M)[CB]) {
+    constexpr int i = F >> 2, j = F & 3;
+    constexpr int c00 = kAT[0][i] * kAT[0][j], c01 = kAT[0][i] * kAT[1][j], c10 = kAT[1][i] * kAT[0][j], c11 = kAT[1][i] * kAT[1][j];
+#pragma unroll
+    for (int cb = 0; cb < CB; ++cb) {
+        if constexpr (c00 > 0) Y[0][0][cb] += M[cb]; else if constexpr (c00 < 0) Y[0][0][cb] -= M[cb];
+        if constexpr (c01 > 0) Y[0][1][cb] += M[cb]; else if constexpr (c01 < 0) Y[0][1][cb] -= M[cb];
+        if constexpr (c10 > 0) Y[1][0][cb] += M[cb]; else if constexpr (c10 < 0) Y[1][0][cb] -= M[cb];
+        if constexpr (c11 > 0) Y[1][1][cb] += M[cb]; else if constexpr (c11 < 0) Y[1][1][cb] -= M[cb];
+        if constexpr (c00 != 0) asm volatile("" : "+v"(Y[0][0][cb]));
+        if constexpr (c01 != 0) asm volatile("" : "+v"(Y[0][1][cb]));
+        if constexpr (c10 != 0) asm volatile("" : "+v"(Y[1][0][cb]));
+        if constexpr (c11 != 0) asm volatile("" : "+v"(Y[1][1][cb]));
+    }
+}
+
+// the plain epilogue on the 2x2 pixels at (oy0, ox0) of image gn, channels n0 + 16 cb + e: every load before the first store
+// (wino2_kernel's, see there)
+template <int CB>
+__device__ __forceinline__ void w2_store_plain(const ConvArgs& p, const v4f (&Y)[2][2][CB], const int gn, const int oy0, const int ox0, const int n0) {
+    const int Cout = p.Cout;
+    const float* __restrict__ res = p.res;
+    float* __restrict__ out1 = p.out1;
+    float* __restrict__ out2 = p.out2;
+    const bool relu = p.act == (int)Act::RELU, prelu = p.act == (int)Act::PRELU;
+    bool live[4]; size_t row[4]; v4f b4[4][CB], r4[4][CB], sl[CB];
+#pragma unroll
+    for (int cb = 0; cb < CB; ++cb) sl[cb] = prelu ? *reinterpret_cast<const v4f*>(p.slope + n0 + 16 * cb) : v4f{1.f, 1.f, 1.f, 1.f};
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int oy = oy0 + (q >> 1), ox = ox0 + (q & 1);
+        live[q] = oy < p.Ho && ox < p.Wo;
+        const int oyc = min(oy, p.Ho - 1), oxc = min(ox, p.Wo - 1);         // (clamped: dead pixels load a neighbour's vectors and store nothing)
+        row[q] = (((size_t)gn * p.Ho + oyc) * p.Wo + oxc) * Cout + n0;
+        const int cls = p.bias_cls ? 3 * (oyc == 0 ? 0 : oyc == p.Ho - 1 ? 2 : 1) + (oxc == 0 ? 0 : oxc == p.Wo - 1 ? 2 : 1) : 0;
+#pragma unroll
+        for (int cb = 0; cb < CB; ++cb) {
+            b4[q][cb] = p.bias ? *reinterpret_cast<const v4f*>(p.bias + cls * Cout + n0 + 16 * cb) : v4f{0.f, 0.f, 0.f, 0.f};
+            if (p.res_mode != (int)ResMode::NONE) r4[q][cb] = *reinterpret_cast<const v4f*>(res + row[q] + 16 * cb);
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        if (!live[q]) continue;
+#pragma unroll
+        for (int cb = 0; cb < CB; ++cb) {
+            v4f v;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[e] = act1(Y[q >> 1][q & 1][cb][e] + b4[q][cb][e], relu, sl[cb][e]);
+            if (p.res_mode != (int)ResMode::NONE) v += r4[q][cb];
+            if (out1) *reinterpret_cast<v4f*>(out1 + row[q] + 16 * cb) = v;
+            if (out2) {
+                const v4f s2 = *reinterpret_cast<const v4f*>(p.s2 + n0 + 16 * cb), t2 = *reinterpret_cast<const v4f*>(p.t2 + n0 + 16 * cb);
+                *reinterpret_cast<v4f*>(out2 + row[q] + 16 * cb) = v * s2 + t2;
+            }
+        }
+    }
+}
+
+// <CB = 2, NW = 2> is the one instantiation: 160 registers, three waves per SIMD — the six workgroups per CU the halo allows.  <4, 1> at one
+// wave per SIMD (238 + 32 registers, four workgroups per CU) measured 0.85-0.93 of the f32 kernel where this one has 0.75-0.89
+// (profiles/wino2_x3.md); at two waves per SIMD it would spill.
+template <int CB, int NW>
+__global__ __launch_bounds__(64 * NW, 3) void wino2_x3_kernel(const ConvArgs p, const int tiles_n, const int tgx, const int tgy) {
+    extern __shared__ v4f w2sm[];
+    char* const halo = reinterpret_cast<char*>(w2sm);                      // [5][5] plane pixels x [4 parity planes] x 16 x 16 B
+    const int lane = threadIdx.x & 63;
+    const int wv = NW == 1 ? 0 : __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
+    int blk;
+    {
+        const int n = gridDim.x, q = n >> 3, r = n & 7, x = blockIdx.x & 7;
+        blk = x * q + min(x, r) + (int)(blockIdx.x >> 3);                  // XCD-contiguous order
+    }
+    const int tile_n = blk % tiles_n, tg = blk / tiles_n;
+    const int per_img = tgx * tgy;
+    const int gn = tg / per_img, rem = tg - gn * per_img;
+    const int gy = rem / tgx, gx = rem - gy * tgx;
+    const int tn = lane & 15, kq = lane >> 4, tr = tn >> 2, tc = tn & 3;
+    w2_load_halo<NW>(p, halo, lane, wv, gn, gy, gx);
+    typedef const __attribute__((address_space(3))) v4f* lds_v4f;
+    const unsigned halo_base = (unsigned)(size_t)(__attribute__((address_space(3))) char*)halo;
+    unsigned rb[16];
+#pragma unroll
+    for (int dy = 0; dy < 4; ++dy)
+#pragma unroll
+        for (int dx = 0; dx < 4; ++dx) {
+            const int pl = (dy & 1) * 2 + (dx & 1), pr = tr + (dy >> 1), pc = tc + (dx >> 1);
+            rb[dy * 4 + dx] = halo_base + (unsigned)((4 * (pr * 5 + pc) + pl) * 256 + ((w2_key(pr, pc) ^ kq) << 4));
+        }
+    // weights of this column tile and wave: step k = 2 f + s is 3 planes x CB fragments of 1 KB (64 lanes x 8 bf16), the waves' steps
+    // interleaved: [16 f][2 s][NW][3][CB][64][8].  A wave-uniform running pointer + the lane's 16-byte offset, as in wino2_kernel.
+    constexpr unsigned WSTEP = 3 * CB * 1024;
+    const char* wstep = reinterpret_cast<const char*>(p.wt) + ((size_t)tile_n * 32 * NW + (size_t)wv) * WSTEP;
+    const unsigned wlane = lane * 16;
+    bf16x8 wr[2][3][CB] = {};                                              // [ring][plane h, m, l][cb]
+    auto fetch_w = [&](bool advance, int buf) __attribute__((always_inline)) {
+        unsigned adv = advance ? NW * WSTEP : 0;
+        asm volatile("" : "+s"(adv));
+        wstep += adv;
+#pragma unroll
+        for (int pl = 0; pl < 3; ++pl)
+#pragma unroll
+            for (int cb = 0; cb < CB; ++cb) wr[buf][pl][cb] = *reinterpret_cast<const bf16x8*>(wstep + wlane + (pl * CB + cb) * 1024);
+    };
+    v4f Y[2][2][CB], Mp[CB];
+#pragma unroll
+    for (int cb = 0; cb < CB; ++cb) {
+        Mp[cb] = v4f{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int a = 0; a < 4; ++a) Y[a >> 1][a & 1][cb] = v4f{0.f, 0.f, 0.f, 0.f};
+    }
+    v4f d[8] = {};                                                         // the patch values of ONE step: groups g = 2 s (0..3) and 2 s + 1 (4..7)
+    auto fetch_d = [&](auto fc, auto sc) __attribute__((always_inline)) {
+        constexpr int f = decltype(fc)::value, s = decltype(sc)::value;
+        constexpr int fi = f >> 2, fj = f & 3;
+        constexpr int ya = kYA[fi], yb = kYB[fi], xa = kYA[fj], xb = kYB[fj];
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            unsigned gxr = (2 * s + h) << 6;                               // group g = columns 4 g .. 4 g + 3 (an opaque scalar, as in wino2_kernel)
+            asm volatile("" : "+s"(gxr));
+            d[4 * h + 0] = *reinterpret_cast<lds_v4f>((size_t)(rb[ya * 4 + xa] ^ gxr));
+            d[4 * h + 1] = *reinterpret_cast<lds_v4f>((size_t)(rb[ya * 4 + xb] ^ gxr));
+            d[4 * h + 2] = *reinterpret_cast<lds_v4f>((size_t)(rb[yb * 4 + xa] ^ gxr));
+            d[4 * h + 3] = *reinterpret_cast<lds_v4f>((size_t)(rb[yb * 4 + xb] ^ gxr));
+        }
+    };
+    auto stage = [&](auto fc) __attribute__((always_inline)) {
+        constexpr int f = decltype(fc)::value;
+        constexpr int fi = f >> 2, fj = f & 3;
+        constexpr int sab = kSA[fi] * kSB[fj], sba = kSB[fi] * kSA[fj], sbb = kSB[fi] * kSB[fj];
+        v4f M[CB];
+#pragma unroll
+        for (int cb = 0; cb < CB; ++cb) M[cb] = v4f{0.f, 0.f, 0.f, 0.f};
+        auto step = [&](auto sc) __attribute__((always_inline)) {
+            constexpr int s = decltype(sc)::value, k = f * 2 + s;
+            fetch_w(k + 1 < 32, (k + 1) & 1);                              // fragments of step k + 1 (past the end: a harmless re-fetch)
+            __builtin_amdgcn_sched_barrier(0);
+            v4f v0 = d[0], v1 = d[4];
+            v0 = sab > 0 ? v0 + d[1] : v0 - d[1];  v1 = sab > 0 ? v1 + d[5] : v1 - d[5];
+            v0 = sba > 0 ? v0 + d[2] : v0 - d[2];  v1 = sba > 0 ? v1 + d[6] : v1 - d[6];
+            v0 = sbb > 0 ? v0 + d[3] : v0 - d[3];  v1 = sbb > 0 ? v1 + d[7] : v1 - d[7];
+            asm volatile("" : "+v"(v0), "+v"(v1));
+            __builtin_amdgcn_sched_barrier(0);
+            if constexpr (s == 0) fetch_d(IC<f>{}, IC<1>{});               // the patch buffer is free: the next step's reads land under the MFMAs
+            else if constexpr (f < 15) fetch_d(IC<f + 1>{}, IC<0>{});
+            bf16x8 vh, vm, vl;
+            gemm_split3(v0, v1, vh, vm, vl);
+            asm volatile("" : "+v"(vh), "+v"(vm), "+v"(vl));
+            __builtin_amdgcn_sched_barrier(0);
+            const bf16x8 (&w)[3][CB] = wr[k & 1];
+#pragma unroll
+            for (int cb = 0; cb < CB; ++cb) M[cb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[2][cb], vh, M[cb], 0, 0, 0);
+#pragma unroll
+            for (int cb = 0; cb < CB; ++cb) M[cb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[0][cb], vl, M[cb], 0, 0, 0);
+#pragma unroll
+            for (int cb = 0; cb < CB; ++cb) M[cb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[1][cb], vm, M[cb], 0, 0, 0);
+#pragma unroll
+            for (int cb = 0; cb < CB; ++cb) M[cb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[1][cb], vh, M[cb], 0, 0, 0);
+#pragma unroll
+            for (int cb = 0; cb < CB; ++cb) M[cb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[0][cb], vm, M[cb], 0, 0, 0);
+#pragma unroll
+            for (int cb = 0; cb < CB; ++cb) M[cb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[0][cb], vh, M[cb], 0, 0, 0);
+            __builtin_amdgcn_sched_barrier(0);
+        };
+        step(IC<0>{});
+        w2_y_update<(f + 15) & 15, CB>(Y, Mp);                             // the previous frequency's result -> the outputs, in the shadow of this one's MFMAs
+        step(IC<1>{});                                                     // (for f = 0, Mp = 0 is added: exact, and +0 stays +0)
+#pragma unroll
+        for (int cb = 0; cb < CB; ++cb) Mp[cb] = M[cb];
+        __builtin_amdgcn_sched_barrier(0);
+    };
+    fetch_w(false, 0);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                       // the halo has landed: LDS-DMA is ordered for its own wave by vmcnt alone
+    if constexpr (NW > 1) __syncthreads();                                 // ... and for the sibling wave's pieces by the workgroup's only barrier
+    fetch_d(IC<0>{}, IC<0>{});
+    stage(IC<0>{}); stage(IC<1>{}); stage(IC<2>{}); stage(IC<3>{}); stage(IC<4>{}); stage(IC<5>{}); stage(IC<6>{}); stage(IC<7>{});
+    stage(IC<8>{}); stage(IC<9>{}); stage(IC<10>{}); stage(IC<11>{}); stage(IC<12>{}); stage(IC<13>{}); stage(IC<14>{}); stage(IC<15>{});
+    w2_y_update<15, CB>(Y, Mp);
+    asm volatile("" ::: "memory");                                         // (one basic block: keeps the epilogue's loads behind the K loop, as in wino2_kernel)
+    __builtin_amdgcn_sched_barrier(0);
+    w2_store_plain<CB>(p, Y, gn, 2 * (4 * gy + tr), 2 * (4 * gx + tc), (tile_n * NW + wv) * 16 * CB + 4 * kq);
+}
+
 bool shape_ok(int Cin, int Cout) { return Cin == 64 && (Cout % 64 == 0 || Cout <= 32); }   // (<= 32: merged outputs only, see wino2_ok)
 
 template <int CB, int NW, bool MERGED>
@@ -341,6 +562,23 @@ void launch_cb(const ConvArgs& a, hipStream_t s) {
     hipLaunchKernelGGL((wino2_kernel<CB, NW, MERGED>), dim3((unsigned)(n_tg * tiles_n)), dim3(64 * NW), 25600, s, a, tiles_n, tgx, tgy, (int)n_tg);
     // booked with the FLOPs the matrix cores EXECUTE (padded tiles / channels included); bytes slot: the layer's direct-form FLOPs, as tag 7
     timer.end(s, 12, 2.0 * 16 * 16.0 * (double)n_tg * a.Cin * (16.0 * CB * NW * tiles_n), a.t_flops);
+}
+
+template <int CB, int NW>
+void launch_x3_cb(const ConvArgs& a, hipStream_t s) {
+    const int tgy = ((a.H + 1) / 2 + 3) / 4, tgx = ((a.W + 1) / 2 + 3) / 4;
+    const long n_tg = (long)a.B * tgy * tgx;
+    const int tiles_n = a.Cout / 64;
+    static const bool lds_ok = [] {                                        // (the address XOR in fetch_d: as launch_cb)
+        hipFuncAttributes fa{};
+        FH_HIP(hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(&wino2_x3_kernel<CB, NW>)));
+        return fa.sharedSizeBytes % 256 == 0;
+    }();
+    if (!lds_ok) throw std::runtime_error("wino2: static LDS moved the halo off its 256-byte alignment (see the address XOR in fetch_d)");
+    KernelTimer& timer = KernelTimer::get();
+    timer.begin(s);
+    hipLaunchKernelGGL((wino2_x3_kernel<CB, NW>), dim3((unsigned)(n_tg * tiles_n)), dim3(64 * NW), 25600, s, a, tiles_n, tgx, tgy);
+    timer.end(s, 12, 2.0 * 16 * 16.0 * (double)n_tg * a.Cin * (64.0 * tiles_n), a.t_flops);   // (booked as launch_cb books the f32 form)
 }
 
 }  // namespace
@@ -368,6 +606,41 @@ void wino2_pack_weights(const float* w, int Cout, int Cin, float* dst) {
                     const size_t step = ((size_t)tn * 16 + (i * 4 + jj)) * 4 + j;
                     dst[(step * CB + cb) * 256 + (kq * 16 + m) * 4 + e] = (float)u;
                 }
+        }
+}
+
+// The three-piece bf16 image of the same U for wino2_x3_kernel: U_f in fp64, rounded to fp32, split by THE SPLIT RULE (gemm_tile.h) on the
+// host.  [column tile of 64][16 f][2 s][2 waves][3 planes h, m, l][2 cb][64 lanes (m = lane & 15, kq = lane >> 4)][8 bf16];
+// element j of lane (m, kq) in step s = U_f[cout = 64 tn + 32 wave + 16 cb + m][cin = 16 (2 s + (j >> 2)) + 4 kq + (j & 3)] — the
+// K permutation of the kernel's patch reads.  6 bytes per element.
+bool wino2_x3_shape_ok(int Cin, int Cout) { return Cin == 64 && Cout > 0 && Cout % 64 == 0; }
+size_t wino2_x3_weight_floats(int Cin, int Cout) { return (size_t)16 * Cin * Cout * 3 / 2; }
+void wino2_pack_weights_x3(const float* w, int Cout, int Cin, unsigned short* dst) {
+    static const double Gm[4][3] = {{1, 0, 0}, {.5, .5, .5}, {.5, -.5, .5}, {0, 0, 1}};
+    if (!wino2_x3_shape_ok(Cin, Cout)) throw std::runtime_error("wino2_pack_weights_x3: layer shape not supported");
+    constexpr int CB = 2, nw = 2;                                          // wino2_x3_kernel<2, 2>
+    auto bits = [](float x) { unsigned u; memcpy(&u, &x, 4); return u; };
+    auto flt = [](unsigned u) { float x; memcpy(&x, &u, 4); return x; };
+    auto rne = [&](float x) { const unsigned u = bits(x); return (u + 0x7fffu + ((u >> 16) & 1u)) & 0xffff0000u; };   // finite x: bf16, nearest even
+    for (int co = 0; co < Cout; ++co)
+        for (int ci = 0; ci < Cin; ++ci) {
+            double g[3][3], t[4][3];
+            for (int k = 0; k < 9; ++k) g[k / 3][k % 3] = w[((size_t)co * 9 + k) * Cin + ci];
+            for (int i = 0; i < 4; ++i)
+                for (int x = 0; x < 3; ++x) t[i][x] = Gm[i][0] * g[0][x] + Gm[i][1] * g[1][x] + Gm[i][2] * g[2][x];
+            const int tn = co / 64, wave = (co % 64) / (16 * CB), cb = (co % (16 * CB)) / 16, m = co % 16;
+            const int gq = ci / 16, kq = (ci % 16) / 4, e = ci % 4, st = gq >> 1, j = 4 * (gq & 1) + e;
+            for (int f = 0; f < 16; ++f) {
+                const int i = f >> 2, jj = f & 3;
+                const volatile float u = (float)(t[i][0] * Gm[jj][0] + t[i][1] * Gm[jj][1] + t[i][2] * Gm[jj][2]);
+                const unsigned hb = bits(u) & 0xffff0000u;
+                const volatile float r = u - flt(hb);
+                const unsigned mb = rne(r);
+                const volatile float q = r - flt(mb);
+                const unsigned pieces[3] = {hb, mb, rne(q)};
+                const size_t step = (((size_t)tn * 16 + f) * 2 + st) * nw + wave;
+                for (int pl = 0; pl < 3; ++pl) dst[(((step * 3 + pl) * CB + cb) * 64 + kq * 16 + m) * 8 + j] = (unsigned short)(pieces[pl] >> 16);
+            }
         }
 }
 
@@ -415,6 +688,16 @@ void launch_wino2(const ConvArgs& a_in, hipStream_t s) {
     if (a.Cout <= 32) launch_cb<2, 1, true>(a, s);
     else if (nw == 2) launch_cb<2, 2, false>(a, s);
     else launch_cb<4, 1, false>(a, s);
+}
+
+// The same layer on wino2_x3_kernel: a.wt = wino2_pack_weights_x3's image.  Plain layers only.
+bool wino2_x3_ok(const ConvArgs& a) { return wino2_ok(a) && a.n_outs == 0 && wino2_x3_shape_ok(a.Cin, a.Cout); }
+long wino2_x3_workgroups(const ConvArgs& a) { return (long)a.B * (((a.H + 1) / 2 + 3) / 4) * (((a.W + 1) / 2 + 3) / 4) * (a.Cout / 64); }
+void launch_wino2_x3(const ConvArgs& a_in, hipStream_t s) {
+    if (!wino2_x3_ok(a_in)) throw std::runtime_error("launch_wino2_x3: layer shape not supported");
+    ConvArgs a = a_in;
+    a.zeros = conv_zero_line();
+    launch_x3_cb<2, 2>(a, s);
 }
 
 }  // namespace fh

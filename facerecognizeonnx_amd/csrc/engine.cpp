@@ -198,6 +198,13 @@ Net::Net(const std::string& onnx_path, int default_h, int default_w) {
                     wino2_pack_weights(op.weight.data(), op.Cout, op.Cin, u.data());
                     d.w2 = push(u.data(), u.size());
                     d.w2ok = true;
+                    if (wino2_x3_ok(probe)) {                               // the same U on three bf16 pieces (Net::set_wino_x3 selects it)
+                        std::vector<float> u3(wino2_x3_weight_floats(op.Cin, op.Cout));
+                        wino2_pack_weights_x3(op.weight.data(), op.Cout, op.Cin, reinterpret_cast<unsigned short*>(u3.data()));
+                        d.w2x = push(u3.data(), u3.size());
+                        d.w2x_ok = true;
+                        ++wino2_x3_n_;
+                    }
                 }
             }
             // Winograd F(4x4,3x3) image of the same filter: U[f] = G g G^T in fp64, one packed [rows][Cin] matrix per frequency
@@ -455,6 +462,7 @@ int Net::set_wino_x3(bool on, hipStream_t s) {
         FH_HIP(hipStreamSynchronize(s));
     }
     conv_x3_ = on && conv_x3_n_ > 0;
+    wino2_x3_ = on && wino2_x3_n_ > 0;                                     // (the fused F(2x2) layers' image was built at load time)
     set_pw_x3(on, s);
     return on ? layers : 0;
 }
@@ -549,6 +557,11 @@ void Net::run(int batch, hipStream_t s, int first_op) {
                 // fused F(2x2,3x3) for the 64-channel 3x3 layers once there is about one one-wave workgroup per CU (wino2_blocks counts them
                 // in fours); below that the direct kernel's split-K fills the chip better
                 if (d.w2ok && winograd && force_cfg < 0 && d.sc_src < 0 && wino2_blocks(a) >= wino2_min_blocks()) {
+                    if (wino2_x3_ && d.w2x_ok && wino2_x3_pays(wino2_x3_workgroups(a), cus > 0 ? cus : conv_num_cus(), conv_knobs())) {
+                        a.wt = P + d.w2x;
+                        launch_wino2_x3(a, s);
+                        break;
+                    }
                     a.wt = P + d.w2;
                     launch_wino2(a, s);
                     break;

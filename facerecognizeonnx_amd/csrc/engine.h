@@ -77,6 +77,8 @@ class Net {
     // (fh_det_set_x3, FACEHIP_DET_X3).  Returns / reports the number of layers that have the 1x1 form while it is on.
     int set_pw_x3(bool on, hipStream_t s);
     int pw_x3_layers() const { return pw_x3_ ? pw_x3_n_ : 0; }
+    // ... and the fused F(2x2) Winograd layers (wino2_x3_kernel, where wino2_x3_pays admits the launch; their image is built at load time).
+    int wino2_x3_layers() const { return wino2_x3_ ? wino2_x3_n_ : 0; }
     int cus = 0;                                          // CUs of the stream this net runs on when it is CU-masked (0 = all)
     int force_cfg = -1;                                   // tuning hook: conv tile config override
     bool sk_enable = true;                                // tuning hook: stream-K remainder wave
@@ -86,7 +88,7 @@ class Net {
         return (long long)fuse_stem | (long long)fuse_front << 1 | (long long)winograd << 2 | (long long)halo_conv << 3 |
                (long long)fold_shortcut << 4 | (long long)fuse_wino << 5 | (long long)bf16x2_ << 6 | (long long)sk_enable << 7 |
                (long long)(cus & 0xffff) << 8 | (long long)((force_cfg + 1) & 0xff) << 24 | (long long)wino_x3_ << 32 | (long long)conv_x3_ << 33 |
-               (long long)pw_x3_ << 34;
+               (long long)pw_x3_ << 34 | (long long)wino2_x3_ << 35;
     }
 
   private:
@@ -107,6 +109,8 @@ class Net {
         bool wino = false;                                    // eligible: 3x3 stride 1 pad 1, Cin >= 128
         size_t w2 = 0;                                        // fused Winograd F(2x2,3x3) image of the filter (conv_wino2.hip): 3x3 stride 1 pad 1,
         bool w2ok = false;                                    //   32 <= Cin < 128, Cout % 64 == 0 (IResNet's 64-channel stages)
+        size_t w2x = 0;                                       // ... its three-piece (x3) image (wino2_pack_weights_x3) ...
+        bool w2x_ok = false;                                  // ... which exists (plain layers: Cout % 64 == 0, no merged outputs)
         int aff_src = -1;                                     // Winograd op whose input is op[aff_src]'s second (BatchNorm) output and its only
                                                               // consumer: the transform reads op[aff_src].out and applies that affine itself
         int aff_dst = -1;                                     // ... and the producer's side of the same link
@@ -134,8 +138,8 @@ class Net {
     Plan plan_;
     std::vector<DevOp> dev_;
     DevBuf params_, arena_, partial_, wino_v_, wino_m_, w36_bf_, w36_x3_, wsc_x3_, wpw_x3_;
-    bool bf16x2_ = false, wino_x3_ = false, conv_x3_ = false, pw_x3_ = false;
-    int conv_x3_n_ = 0, pw_x3_n_ = 0;
+    bool bf16x2_ = false, wino_x3_ = false, conv_x3_ = false, pw_x3_ = false, wino2_x3_ = false;
+    int conv_x3_n_ = 0, pw_x3_n_ = 0, wino2_x3_n_ = 0;
     size_t wino_maxc_ = 0;
     size_t wino_elems_ = 0;                                   // per image: 36 * tiles * max(Cin, Cout) of the largest Winograd op
     int cap_ = 0;

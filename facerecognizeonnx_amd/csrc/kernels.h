@@ -151,7 +151,16 @@ void wino2_pack_weights(const float* w_ohwi, int Cout, int Cin, float* dst);
 bool wino2_ok(const ConvArgs& a);
 void launch_wino2(const ConvArgs& a, hipStream_t s);
 long wino2_blocks(const ConvArgs& a);          // workgroups the launch would have
-double wino2_debug_clock_mhz();                // diagnostic builds (scripts/wino2_prof.sh): median in-kernel shader clock of the last launch
+// ... and its three-piece bf16 form (wino2_x3_kernel: fp32 products on six bf16 MFMAs), plain layers with Cout % 64 == 0 only: a.wt =
+// the wino2_pack_weights_x3 image (wino2_x3_weight_floats floats, built on the host).  Whether a
+// launch of `workgroups` gains from it is wino2_x3_pays' question (conv_plan.h).  Booked under tag 12 like the f32 form.
+bool wino2_x3_shape_ok(int Cin, int Cout);
+size_t wino2_x3_weight_floats(int Cin, int Cout);
+void wino2_pack_weights_x3(const float* w_ohwi, int Cout, int Cin, unsigned short* dst);
+bool wino2_x3_ok(const ConvArgs& a);
+long wino2_x3_workgroups(const ConvArgs& a);
+void launch_wino2_x3(const ConvArgs& a, hipStream_t s);
+double wino2_debug_clock_mhz();              // diagnostic builds (scripts/wino2_prof.sh): median in-kernel shader clock of the last launch
 const float* conv_zero_line();                // 8 KiB of device zeros (target of padded / dead loads)
 int conv_num_cus();                           // compute units of the current device
 // dense 3x3 stride-1 convolutions with 16 input channels and <= 64 output channels on an 8x16 spatial tile with an LDS halo

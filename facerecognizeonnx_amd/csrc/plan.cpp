@@ -290,7 +290,7 @@ static Plan build_plan_impl(const OnnxModel& m, int inH, int inW) {
             x.group = (int)n.attr_i("group", 1);
             auto st = n.attr_ints("strides"); auto pd = n.attr_ints("pads"); auto dl = n.attr_ints("dilations");
             x.stride = st.empty() ? 1 : (int)st[0];
-            if (!st.empty() && st[0] != st[1]) fail("anisotropic stride");
+            if (!st.empty() && (st.size() < 2 || st[0] != st[1])) fail("anisotropic stride");   // (a one-entry list: a damaged file)
             x.pad = pd.empty() ? 0 : (int)pd[0];
             for (auto p : pd) if (p != x.pad) fail("asymmetric padding");
             for (auto d : dl) if (d != 1) fail("dilation != 1");

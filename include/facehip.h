@@ -963,6 +963,11 @@ FH_API int fh_rec_get_conv_x3(fh_rec* r);
  * they run on conv_pw_x3_kernel, the plain GEMM on the same three pieces.  Number of layers of this handle that have that form while the
  * switch is on (0 while it is off). */
 FH_API int fh_rec_get_pw_x3(fh_rec* r);
+/* ... and the fused F(2x2) Winograd layers with 64 input channels (IResNet's stage 1 and stage-2 entry): where the launch gains
+ * (fh_debug_conv_plan question 8) they run on wino2_x3_kernel, the same fused kernel with its products on the three pieces
+ * (FACEHIP_WINO2_X3 = 0 / 2 in the environment: none / every launch that has the form).  Number of layers of this handle that have that
+ * form while the switch is on (0 while it is off). */
+FH_API int fh_rec_get_wino2_x3(fh_rec* r);
 /* The detector's own switch for the same form of its 1x1 stride-1 convolutions (SCRFD's 288 / 152 / 72-deep ones and the FPN laterals).
  * on is the default (FACEHIP_DET_X3=0 in the environment makes off the default); off: the native f32 kernels, the bits of a build without
  * the form.  Which launches take it depends on layer geometry, batch and CU count only (FACEHIP_PW_X3 = 0 / 2 in the environment: none /
@@ -1200,8 +1205,18 @@ FH_API int fh_debug_streamk(int drop_publish, int timeout_ms);
  *           -> out = 1 if the launch runs it (conv_x3_pays), x3 tile width 128 / 64 or 0 = Cout has no such form (2)
  *   what 6  conv_pw_x3_kernel: in = the 11 of question 1 -> out = its tile width 96 / 64 / 32 or 0 = no such form at this batch
  *           (conv_pw_x3_bn; never a form where question 1 answers 0), its tiles, 1 if the launch runs it with the handle's switch on (3)
- *   what 7  conv_pw_x3_pays alone: in = tiles, Kpad, Cout, CUs (4) -> out = 1 if such a launch runs the x3 form (1) */
+ *   what 7  conv_pw_x3_pays alone: in = tiles, Kpad, Cout, CUs (4) -> out = 1 if such a launch runs the x3 form (1)
+ *   what 8  wino2_x3_pays: in = workgroups, CUs (2) -> out = 1 if such a launch of the fused F(2x2) layer runs wino2_x3_kernel (1) */
 FH_API int fh_debug_conv_plan(int what, const int* in, int n_in, long long* out, int n_out);
+/* The plain form of fh_conv_wino2_ex_dev (no merged outputs) with a precision argument and the CU count: FH_PREC_FP32 = wino2_kernel,
+ * FH_PREC_F32X3 = wino2_x3_kernel (fp32 products from six bf16 MFMAs) on an image split here as the engine splits it — refused for layers
+ * without the form ("... no three-piece bf16 form": cin != 64 or cout % 64 != 0).  Synchronous. */
+FH_API int fh_conv_wino2_prec_dev(const float* d_in, const float* w_ohwi_host, const float* d_bias, const float* d_slope, const float* d_res,
+                                  float* d_out, float* d_out2, const float* d_s2, const float* d_t2, int batch, int h, int w, int cin,
+                                  int cout, int act, int bias_cls, int precision, int cus, void* stream);
+/* The host pack of that image, for the layout tests: dst = 16 * cin * cout * 3 bf16 words in the order
+ * [cout / 64][16 f][2 s][2 waves][3 planes h, m, l][2][64 lanes][8]. */
+FH_API int fh_debug_wino2_pack_x3(const float* w_ohwi_host, int cout, int cin, unsigned short* dst);
 /* Test hook of the multi-tile Winograd GEMM (winograd.hip wino_gemm_pers_kernel): launches with more tiles than resident workgroup
  * slots walk several tiles per workgroup; slots > 0 makes the launcher pretend the device has that many (rounded up to 8), so that small
  * test layers take the multi-tile path with many tiles per workgroup; 0 restores the device's own count. */
