@@ -318,6 +318,8 @@ PROTOTYPES = {
     "fh_debug_wino2_clock_mhz": (_d, []),
     "fh_conv_wino2_prec_dev": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "fh_debug_wino2_pack_x3": (_i, [_vp, _i, _i, _vp]),
+    "fh_debug_stem_pack": (_i, [_vp, _i, _vp]),
+    "fh_debug_det_run_pasted_dev": (_i, [_vp, _vp, _i, _i, _i, _i, _ll, _vp]),
     "fh_conv_wino2_dev": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "fh_conv_wino2_ex_dev": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "fh_conv_wt_rows": (_i, [_i]),

@@ -454,6 +454,13 @@ int fh_det_run_network_dev(fh_det* d, const uint8_t* frames, int n, int rows, in
     Owns owns(&d->det.net());
     return guarded([&] { d->det.run_network_dev(frames, n, rows, cols, step, (long)stride, S(stream)); return n; });
 }
+// Net::run_u8 on frames taken as they are — pasted at the net input's origin, no letterbox resize — for the stem tests
+int fh_debug_det_run_pasted_dev(fh_det* d, const uint8_t* frames, int n, int rows, int cols, int step, long long stride, void* stream) {
+    if (!d || !frames || n <= 0 || rows <= 0 || cols <= 0 || step < cols * 3 || rows > d->det.net().in_h() || cols > d->det.net().in_w())
+        return arg_error("fh_debug_det_run_pasted_dev: bad argument (the frame must fit the net input)");
+    Owns owns(&d->det.net());
+    return guarded([&] { d->det.net().reserve(n); d->det.net().run_u8(frames, (long)stride, rows, cols, step, n, S(stream)); return n; });
+}
 int fh_det_run_input_dev(fh_det* d, const float* input, int n, void* stream) {
     if (!d || !input || n <= 0) return arg_error("fh_det_run_input_dev: bad argument");
     if (d->det.net().plan().tensors[d->det.net().plan().input].C != 4) return arg_error("fh_det_run_input_dev: the graph input is not a 3-channel image");
@@ -2202,6 +2209,11 @@ int fh_debug_wino2_pack_x3(const float* w_ohwi, int cout, int cin, unsigned shor
     if (!w_ohwi || !dst || !fh::wino2_x3_shape_ok(cin, cout))
         return arg_error("fh_debug_wino2_pack_x3: this layer has no three-piece bf16 form (it needs cin == 64 and cout % 64 == 0)");
     return guarded([&] { fh::wino2_pack_weights_x3(w_ohwi, cout, cin, dst); return 0; });
+}
+// stem_pack_wfrag on the host, for the layout tests: out = cout / 16 * 3 * 64 * 4 dwords
+int fh_debug_stem_pack(const float* wf, int cout, unsigned* out) {
+    if (!wf || !out || cout <= 0 || cout % 16) return arg_error("fh_debug_stem_pack: bad argument (cout % 16 == 0)");
+    return guarded([&] { fh::stem_pack_wfrag(wf, cout, out); return 0; });
 }
 double fh_debug_wino2_clock_mhz(void) { return fh::wino2_debug_clock_mhz(); }
 int fh_conv_wt_rows(int cout) { return fh::conv_wt_rows(cout); }

@@ -1217,6 +1217,13 @@ FH_API int fh_conv_wino2_prec_dev(const float* d_in, const float* w_ohwi_host, c
 /* The host pack of that image, for the layout tests: dst = 16 * cin * cout * 3 bf16 words in the order
  * [cout / 64][16 f][2 s][2 waves][3 planes h, m, l][2][64 lanes][8]. */
 FH_API int fh_debug_wino2_pack_x3(const float* w_ohwi_host, int cout, int cin, unsigned short* dst);
+/* The host pack of the matrix-core stems' weights (stem_mfma_kernel, front_kernel), for the layout tests: wf = the folded filter
+ * [27][cout] (tap-major: (ky * 9 + kx * 3 + byte) x channel), cout % 16 == 0 -> out = cout / 16 * 3 * 64 * 4 dwords in the order
+ * [cout / 16][3 pieces hi, mid, lo][64 lanes][4], two bf16 per dword.  Needs no device. */
+FH_API int fh_debug_stem_pack(const float* wf, int cout, unsigned* out);
+/* fh_det_run_network_dev without the letterbox plan, for the stem tests: the n device frames (rows <= input height, cols <= input width)
+ * are pasted at the net input's origin as they are — scale 1 whatever their shape — and the rest of the net input is canvas.  Returns n. */
+FH_API int fh_debug_det_run_pasted_dev(fh_det* det, const uint8_t* d_frames, int n, int rows, int cols, int step, long long stride, void* stream);
 /* Test hook of the multi-tile Winograd GEMM (winograd.hip wino_gemm_pers_kernel): launches with more tiles than resident workgroup
  * slots walk several tiles per workgroup; slots > 0 makes the launcher pretend the device has that many (rounded up to 8), so that small
  * test layers take the multi-tile path with many tiles per workgroup; 0 restores the device's own count. */

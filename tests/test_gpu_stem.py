@@ -4,7 +4,8 @@ launch_stem picks the kernel from the stem's channel count: 8 / 24 -> stem_conv_
 the interior plus stem_conv_border_kernel for the frame around it, 48 / 64 -> stem_mfma_kernel (matrix cores).  Each runs at stride 1 and
 2 on a static 64 x 64 net input (4 x 4 / 2 x 2 tiles of 16 x 16 per image, batch 3), with frames whose longer side is exactly 64 — letterbox
 scale 1, so the bytes reach the stem as they are and the rest of the net input is canvas:
-  64 x 41, pitch 41 * 3 + 1   canvas on the right, a different misalignment in every row
+  64 x 41, pitch 41 * 3 + 1   canvas on the right; the pitch is 124, a multiple of 4: every row is misaligned alike
+  64 x 41, pitch 41 * 3 + 2   the same frame with a different misalignment in every row
   41 x 64, pitch 192          canvas below, every row aligned
   64 x 3 and 64 x 1           no interior pixel at all, rows shorter than one 12-byte window
 with ReLU, PReLU and no activation, and (bn) a BatchNormalization behind the stem whose plain map stays in use: out1, out2, s2 / t2 and
@@ -36,7 +37,7 @@ def _gpu():
 
 B, HW = 3, 64
 #         rows cols pitch
-FRAMES = [(64, 41, 41 * 3 + 1), (41, 64, 192), (64, 3, 3 * 3 + 1), (64, 1, 5)]
+FRAMES = [(64, 41, 41 * 3 + 1), (64, 41, 41 * 3 + 2), (41, 64, 192), (64, 3, 3 * 3 + 1), (64, 1, 5)]
 CHANNELS = (8, 24, 16, 32, 48, 64)
 # every kernel family sees every activation, each with and without the second output
 CASES = [(c, s, act, (i + j + s) % 2 == 1) for i, c in enumerate(CHANNELS) for s in (1, 2) for j, act in enumerate(("relu", "prelu", "none"))]
