@@ -33,6 +33,11 @@
 //
 // Numerics: the interpolation points of F(2x2, 3x3) are {0, 1, -1, inf}; G has entries 1 and 1/2 — rounding stays within ~3x of the
 // direct fp32 form (tests/test_gpu_round4.py bars single layers at 5e-5 abs on O(1) outputs; winograd.hip's F(4x4) needs 2e-4).
+//
+// Layout of this file: THE TILE BODY (walk, halo, patch addresses, patch reads and V, the A^T fold, the plain epilogue — each stated once
+// with its design note), then wino2_kernel (products on f32 MFMAs; also the merged-sibling epilogue and the diagnostic switches) and
+// wino2_x3_kernel (products on six bf16 MFMAs), which differ in their weight ring and K loop alone; then one launcher (launch_w2) and
+// the two weight packers.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -66,281 +71,34 @@ template <int V> struct IC { static constexpr int value = V; };          // comp
                                                                           // 16 instantiations (`#pragma unroll` gives up on a body of this size, and a
                                                                           // run-time f turns every B^T / A^T coefficient into a branch)
 
-// NW = waves per workgroup that share ONE halo: wave w computes the 16 CB channels [16 CB w, 16 CB (w + 1)) of the workgroup's 16 CB NW-channel
-// column tile (NW = 1: the original one-wave form).  MERGED selects the merged-sibling epilogue (per-channel-range destinations).
-// NW = 2, CB = 2 on the plain 64-channel layers: the 25.6 KB halo limits a CU to six workgroups either way, so six waves of 226 registers
-// (1.5 per SIMD: two SIMDs carry two waves, two carry one) become twelve of 112 (three per SIMD) — DESIGN.md 3.1.
-template <int CB, int NW, bool MERGED>
-__global__ __launch_bounds__(64 * NW, NW == 1 ? 2 : 3) void wino2_kernel(const ConvArgs p, const int tiles_n, const int tgx, const int tgy, const int n_tg) {
-    extern __shared__ v4f w2sm[];
-    char* const halo = reinterpret_cast<char*>(w2sm);                      // [5][5] plane pixels x [4 parity planes] x 16 x 16 B
-    const int lane = threadIdx.x & 63;
-    const int wv = NW == 1 ? 0 : __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
-    constexpr int CBT = CB * NW;                                           // 16-channel blocks per column tile in the weight image
-#ifdef FACEHIP_W2_PROF
-    const long long prof_c0 = __builtin_readcyclecounter(), prof_r0 = __builtin_amdgcn_s_memrealtime();   // shader clock vs the constant 100 MHz counter
-#endif
-    int blk;
-    {
-        const int n = gridDim.x, q = n >> 3, r = n & 7, x = blockIdx.x & 7;
-        blk = x * q + min(x, r) + (int)(blockIdx.x >> 3);                  // XCD-contiguous order
-    }
+// ====================================================================================================================================
+// THE TILE BODY: everything wino2_kernel and wino2_x3_kernel have in common, each piece stated once.  What a kernel keeps for itself is
+// its weight ring, its K loop (step / stage) and, for wino2_kernel, the merged-sibling epilogue and the diagnostic switches.
+// Both kernels are ONE basic block without scratch: the pins (asm volatile "+v"), the sched_barrier(0) brackets around the MFMA block and
+// the opaque scalars ("+s") below and in the kernels are part of the register budget, not decoration (docs/kernels.md 3.1l).  The pieces
+// take the kernel's by-value ConvArgs by const reference and are always inlined: .private_segment_fixed_size must stay 0
+// (profiles/wino2_tile_refactor.md has every instantiation's figures).
+
+// Walk.  Workgroup -> (column tile, image, tile group) in XCD-contiguous order, column tile fastest: the tiles_n workgroups around one
+// halo are neighbours on one L2.  Lane -> tile (tr, tc) of the 4 x 4 group and k quarter kq.
+struct W2Walk { int tile_n, gn, gy, gx, kq, tr, tc; };
+__device__ __forceinline__ W2Walk w2_walk(const int lane, const int tiles_n, const int tgx, const int tgy) {
+    const int blk = xcd_tile(blockIdx.x, (int)gridDim.x);
     const int tile_n = blk % tiles_n, tg = blk / tiles_n;
-    const int H = p.H, W = p.W;
     const int per_img = tgx * tgy;
     const int gn = tg / per_img, rem = tg - gn * per_img;
     const int gy = rem / tgx, gx = rem - gy * tgx;
-    (void)n_tg;
-    const int tn = lane & 15, kq = lane >> 4, tr = tn >> 2, tc = tn & 3;
-    auto key = [](int pr, int pc) { return 2 * ((pc + 4 * (pr & 1)) & 7); };
-
-    // ---- halo: 25 pieces of 4 LDS rows x 16 columns.  LDS row 4 i + pl holds pixel i = 5 pr + pc of parity plane pl, so piece i is the same
-    // plane pixel of the four planes: its lanes' plane is lane >> 4 (computed once), its (pr, pc) and swizzle key are compile-time constants
-    // — ~10 VALU per piece instead of ~30 with plane-major rows (the bank a read hits does not depend on its row: a row is all 64 banks)
-    {
-        const int col = lane & 15, pl = lane >> 4;
-        const int y0 = 8 * gy - 1 + (pl >> 1), x0 = 8 * gx - 1 + (pl & 1);
-        const float* const img = p.in + ((size_t)gn * H * W + (size_t)y0 * W + x0) * 64;   // (may point in front of the image: only dereferenced when in range)
-#pragma unroll
-        for (int i = 0; i < 25; ++i) {
-            const int pr = i / 5, pc = i - 5 * pr;
-            const int y = y0 + 2 * pr, x = x0 + 2 * pc;
-            const bool ok = (unsigned)y < (unsigned)H && (unsigned)x < (unsigned)W;
-            if (NW > 1 && (i % NW) != wv) continue;                        // (wave-uniform: the waves of a workgroup take alternate pieces)
-            lds_dma16(ok ? img + ((long)2 * pr * W + 2 * pc) * 64 + ((col ^ key(pr, pc)) << 2) : p.zeros, halo + i * 1024);
-        }
-    }
-    typedef const __attribute__((address_space(3))) v4f* lds_v4f;
-    const unsigned halo_base = (unsigned)(size_t)(__attribute__((address_space(3))) char*)halo;
-    unsigned rb[16];
-#pragma unroll
-    for (int dy = 0; dy < 4; ++dy)
-#pragma unroll
-        for (int dx = 0; dx < 4; ++dx) {
-            const int pl = (dy & 1) * 2 + (dx & 1), pr = tr + (dy >> 1), pc = tc + (dx >> 1);
-            rb[dy * 4 + dx] = halo_base + (unsigned)((4 * (pr * 5 + pc) + pl) * 256 + ((key(pr, pc) ^ kq) << 4));
-        }
-    // weights of this column tile: step (f, j) = CB KB at ((f * 4 + j) * CB) * 256 floats; cb-th fragment + cb * 256
-    // (a wave-uniform running pointer + the lane's 16-byte offset: with compile-time step offsets the 64 step addresses are hoisted out of
-    //  the loop into 128 registers)
-    const char* wstep = reinterpret_cast<const char*>(p.wt + ((size_t)tile_n * 64 * CBT + (size_t)wv * CB) * 256);
-    const unsigned wlane = lane * 16;
-    constexpr int WD = 2;                                                  // weight ring: fragments are requested WD - 1 steps (512 MFMA cycles each) ahead
-    v4f wr[WD][CB] = {};                                                   // (WD = 4 measured the same: 196.0 vs 194.6 us on 56x56x64, and costs 32 registers)
-#ifdef FACEHIP_W2_PROF
-    const bool abl_w = p.sk_test_drop & 4, abl_d = p.sk_test_drop & 8, abl_y = p.sk_test_drop & 16, abl_st = p.sk_test_drop & 2;   // ablations (wrong results)
-#else
-    constexpr bool abl_w = false, abl_d = false, abl_y = false, abl_st = false;
-#endif
-    auto fetch_w = [&](bool advance, int buf) __attribute__((always_inline)) {
-        if (abl_w) return;
-        unsigned adv = advance ? CBT * 1024 : 0;
-        asm volatile("" : "+s"(adv));
-        wstep += adv;
-#pragma unroll
-        for (int cb = 0; cb < CB; ++cb) wr[buf][cb] = *reinterpret_cast<const v4f*>(wstep + wlane + cb * 1024);
-    };
-    v4f Y[2][2][CB], Mp[CB];
-#pragma unroll
-    for (int cb = 0; cb < CB; ++cb) {
-        Mp[cb] = v4f{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int a = 0; a < 4; ++a) Y[a >> 1][a & 1][cb] = v4f{0.f, 0.f, 0.f, 0.f};
-    }
-    auto y_update = [&](auto fc, const v4f (&M)[CB]) __attribute__((always_inline)) {
-        constexpr int f = decltype(fc)::value, i = f >> 2, j = f & 3;
-        if (abl_y && f != 5) return;
-        constexpr int c00 = kAT[0][i] * kAT[0][j], c01 = kAT[0][i] * kAT[1][j], c10 = kAT[1][i] * kAT[0][j], c11 = kAT[1][i] * kAT[1][j];
-#pragma unroll
-        for (int cb = 0; cb < CB; ++cb) {
-            if constexpr (c00 > 0) Y[0][0][cb] += M[cb]; else if constexpr (c00 < 0) Y[0][0][cb] -= M[cb];
-            if constexpr (c01 > 0) Y[0][1][cb] += M[cb]; else if constexpr (c01 < 0) Y[0][1][cb] -= M[cb];
-            if constexpr (c10 > 0) Y[1][0][cb] += M[cb]; else if constexpr (c10 < 0) Y[1][0][cb] -= M[cb];
-            if constexpr (c11 > 0) Y[1][1][cb] += M[cb]; else if constexpr (c11 < 0) Y[1][1][cb] -= M[cb];
-            // pinned here: pure arithmetic floats freely in this barrier-free kernel, and left alone the scheduler defers the updates —
-            // every deferred frequency keeps its 4 CB accumulator registers alive (256 registers + spills by the tenth frequency)
-            if constexpr (c00 != 0) asm volatile("" : "+v"(Y[0][0][cb]));
-            if constexpr (c01 != 0) asm volatile("" : "+v"(Y[0][1][cb]));
-            if constexpr (c10 != 0) asm volatile("" : "+v"(Y[1][0][cb]));
-            if constexpr (c11 != 0) asm volatile("" : "+v"(Y[1][1][cb]));
-        }
-    };
-    v4f d[2][4] = {};
-    auto fetch_d = [&](auto fc, auto jc, auto bc) __attribute__((always_inline)) {
-        constexpr int f = decltype(fc)::value, j = decltype(jc)::value, buf = decltype(bc)::value;
-        constexpr int fi = f >> 2, fj = f & 3;
-        constexpr int ya = kYA[fi], yb = kYB[fi], xa = kYA[fj], xb = kYB[fj];
-        if (abl_d) return;
-        unsigned gxr = j << 6;                                             // k-step group j = columns 4 j .. 4 j + 3 (an opaque scalar: a compile-time
-        asm volatile("" : "+s"(gxr));                                      //  XOR is hoisted — 48 addresses in registers; for j = 0 too: reads that depend on nothing float stages ahead)
-        d[buf][0] = *reinterpret_cast<lds_v4f>((size_t)(rb[ya * 4 + xa] ^ gxr));
-        d[buf][1] = *reinterpret_cast<lds_v4f>((size_t)(rb[ya * 4 + xb] ^ gxr));
-        d[buf][2] = *reinterpret_cast<lds_v4f>((size_t)(rb[yb * 4 + xa] ^ gxr));
-        d[buf][3] = *reinterpret_cast<lds_v4f>((size_t)(rb[yb * 4 + xb] ^ gxr));
-    };
-    auto stage = [&](auto fc) __attribute__((always_inline)) {
-        constexpr int f = decltype(fc)::value;
-        constexpr int fi = f >> 2, fj = f & 3;
-        constexpr int sab = kSA[fi] * kSB[fj], sba = kSB[fi] * kSA[fj], sbb = kSB[fi] * kSB[fj];
-        v4f M[CB];
-#pragma unroll
-        for (int cb = 0; cb < CB; ++cb) M[cb] = v4f{0.f, 0.f, 0.f, 0.f};
-        auto step = [&](auto jc) __attribute__((always_inline)) {
-            constexpr int j = decltype(jc)::value, k = f * 4 + j;
-            fetch_w(k + WD - 1 < 64, (k + WD - 1) % WD);                    // fragments of step k + WD - 1 (past the end: a harmless re-fetch)
-            if constexpr (j < 3) fetch_d(IC<f>{}, IC<j + 1>{}, IC<(k + 1) & 1>{});
-            else if constexpr (f < 15) fetch_d(IC<f + 1>{}, IC<0>{}, IC<(k + 1) & 1>{});
-            __builtin_amdgcn_sched_barrier(0);
-            const v4f* dd = d[k & 1];
-            v4f v = dd[0];
-            v = sab > 0 ? v + dd[1] : v - dd[1];
-            v = sba > 0 ? v + dd[2] : v - dd[2];
-            v = sbb > 0 ? v + dd[3] : v - dd[3];
-            asm volatile("" : "+v"(v));
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-#pragma unroll
-                for (int cb = 0; cb < CB; ++cb) M[cb] = __builtin_amdgcn_mfma_f32_16x16x4f32(wr[k % WD][cb][e], v[e], M[cb], 0, 0, 0);
-            __builtin_amdgcn_sched_barrier(0);
-        };
-        step(IC<0>{}); step(IC<1>{});
-        y_update(IC<(f + 15) & 15>{}, Mp);                                 // the previous frequency's result -> the outputs, in the shadow of this one's MFMAs
-        step(IC<2>{}); step(IC<3>{});
-#pragma unroll
-        for (int cb = 0; cb < CB; ++cb) Mp[cb] = M[cb];
-        __builtin_amdgcn_sched_barrier(0);
-    };
-    fetch_w(false, 0);
-#pragma unroll
-    for (int q = 1; q < WD - 1; ++q) fetch_w(true, q);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                       // the halo has landed: LDS-DMA is ordered for its own wave by vmcnt alone
-    if constexpr (NW > 1) __syncthreads();                                 // ... and for the sibling wave's pieces by the workgroup's only barrier
-    fetch_d(IC<0>{}, IC<0>{}, IC<0>{});
-    stage(IC<0>{}); stage(IC<1>{}); stage(IC<2>{}); stage(IC<3>{}); stage(IC<4>{}); stage(IC<5>{}); stage(IC<6>{}); stage(IC<7>{});
-    stage(IC<8>{}); stage(IC<9>{}); stage(IC<10>{}); stage(IC<11>{}); stage(IC<12>{}); stage(IC<13>{}); stage(IC<14>{}); stage(IC<15>{});
-    y_update(IC<15>{}, Mp);
-
-    // ---- epilogue: lane = tile (tr, tc), accumulator block cb = channels 16 cb + 4 kq .. + 3 of the column tile
-    // (the kernel has no barrier, i.e. it is ONE basic block: without this fence the epilogue's bias / slope / residual loads are scheduled
-    //  in front of the K loop and their ~80 destination registers are spilled through it)
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-    if (abl_st && lane != 0) return;                                       // (lane 0 goes on to the clock stamp; 63 of 64 lanes' stores are gone)
-    const int oy0 = 2 * (4 * gy + tr), ox0 = 2 * (4 * gx + tc);
-    const int n0 = (tile_n * NW + wv) * 16 * CB, Cout = p.Cout;
-    const float* __restrict__ res = p.res;
-    float* __restrict__ out1 = p.out1;
-    float* __restrict__ out2 = p.out2;
-    const bool relu = p.act == (int)Act::RELU, prelu = p.act == (int)Act::PRELU;
-    float bm[CB][4];                                                       // merged form: this lane's 8 bias values, fetched once (no load between the stores)
-    if constexpr (MERGED) {
-#pragma unroll
-        for (int cb = 0; cb < CB; ++cb)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) { const int co = n0 + 16 * cb + 4 * kq + e; bm[cb][e] = co < Cout ? p.bias[co] : 0.f; }
-    }
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b) {
-            const int oy = oy0 + a, ox = ox0 + b;
-            if (!MERGED || oy >= p.Ho || ox >= p.Wo) continue;
-            const size_t pix = ((size_t)gn * p.Ho + oy) * p.Wo + ox;       // (merged convolutions carry no folded BatchNorm: wino2_ok)
-            if constexpr (MERGED) {                                        // merged sibling convolutions: per-channel-range destination and activation
-#pragma unroll
-                for (int cb = 0; cb < CB; ++cb)
-#pragma unroll
-                    for (int e = 0; e < 4; e += 2) {                       // channel pairs: one 8-byte store where both land in one destination, aligned
-                        const int co = n0 + 16 * cb + 4 * kq + e;
-                        if (co >= Cout) continue;
-                        const int g = co >= p.oc0[2] && p.n_outs > 2 ? 2 : co >= p.oc0[1] ? 1 : 0;
-                        const int cg = p.oc0[g + 1] - p.oc0[g], ga = p.oact[g];
-                        auto fin = [&](float v) { return ga == (int)Act::RELU ? fmaxf(v, 0.f) : ga == (int)Act::SIGMOID ? 1.0f / (1.0f + expf(-v)) : v; };
-                        float* const dst = p.outs[g] + pix * cg + (co - p.oc0[g]);
-                        const float v0 = fin(Y[a][b][cb][e] + bm[cb][e]);
-                        if (co + 1 < p.oc0[g + 1] && !((cg | (co - p.oc0[g])) & 1)) {
-                            *reinterpret_cast<float2*>(dst) = float2{v0, fin(Y[a][b][cb][e + 1] + bm[cb][e + 1])};
-                        } else {
-                            dst[0] = v0;
-                            if (co + 1 < Cout) {                          // the pair straddles two destinations (or is unaligned): scalar stores
-                                const int g1 = co + 1 >= p.oc0[2] && p.n_outs > 2 ? 2 : co + 1 >= p.oc0[1] ? 1 : 0;
-                                const int cg1 = p.oc0[g1 + 1] - p.oc0[g1], ga1 = p.oact[g1];
-                                float v1 = Y[a][b][cb][e + 1] + bm[cb][e + 1];
-                                v1 = ga1 == (int)Act::RELU ? fmaxf(v1, 0.f) : ga1 == (int)Act::SIGMOID ? 1.0f / (1.0f + expf(-v1)) : v1;
-                                p.outs[g1][pix * cg1 + (co + 1 - p.oc0[g1])] = v1;
-                            }
-                        }
-                    }
-                continue;
-            }
-        }
-    if constexpr (!MERGED) {
-        // Every load of the epilogue goes out BEFORE the first store: bias per pixel (its border class), slope, residual — 36 float4 per lane
-        // in flight together, ONE global-memory latency.  (Per pixel "load, wait, compute, store" was four latencies in a row: with the
-        // stores masked to one lane of 64 the epilogue still cost 33 of the layer's 195 us — it was never the traffic.)
-        const int n0 = (tile_n * NW + wv) * 16 * CB + 4 * kq;
-        bool live[4]; size_t row[4]; v4f b4[4][CB], r4[4][CB], sl[CB];
-#pragma unroll
-        for (int cb = 0; cb < CB; ++cb) sl[cb] = prelu ? *reinterpret_cast<const v4f*>(p.slope + n0 + 16 * cb) : v4f{1.f, 1.f, 1.f, 1.f};
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int oy = oy0 + (q >> 1), ox = ox0 + (q & 1);
-            live[q] = oy < p.Ho && ox < p.Wo;
-            const int oyc = min(oy, p.Ho - 1), oxc = min(ox, p.Wo - 1);     // (clamped: dead pixels load a neighbour's vectors and store nothing)
-            row[q] = (((size_t)gn * p.Ho + oyc) * p.Wo + oxc) * Cout + n0;
-            const int cls = p.bias_cls ? 3 * (oyc == 0 ? 0 : oyc == p.Ho - 1 ? 2 : 1) + (oxc == 0 ? 0 : oxc == p.Wo - 1 ? 2 : 1) : 0;
-#pragma unroll
-            for (int cb = 0; cb < CB; ++cb) {
-                b4[q][cb] = p.bias ? *reinterpret_cast<const v4f*>(p.bias + cls * Cout + n0 + 16 * cb) : v4f{0.f, 0.f, 0.f, 0.f};
-                if (p.res_mode != (int)ResMode::NONE) r4[q][cb] = *reinterpret_cast<const v4f*>(res + row[q] + 16 * cb);
-            }
-        }
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            if (!live[q]) continue;
-#pragma unroll
-            for (int cb = 0; cb < CB; ++cb) {
-                v4f v;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = act1(Y[q >> 1][q & 1][cb][e] + b4[q][cb][e], relu, sl[cb][e]);
-                if (p.res_mode != (int)ResMode::NONE) v += r4[q][cb];
-                if (out1) *reinterpret_cast<v4f*>(out1 + row[q] + 16 * cb) = v;
-                if (out2) {
-                    const v4f s2 = *reinterpret_cast<const v4f*>(p.s2 + n0 + 16 * cb), t2 = *reinterpret_cast<const v4f*>(p.t2 + n0 + 16 * cb);
-                    *reinterpret_cast<v4f*>(out2 + row[q] + 16 * cb) = v * s2 + t2;
-                }
-            }
-        }
-    }
-#ifdef FACEHIP_W2_PROF
-    if (lane == 0 && p.slabs && blockIdx.x < (1u << 17)) {                 // this wave's mean shader clock in MHz x 10 -> the diagnostic buffer (never an output)
-        const long long dc = __builtin_readcyclecounter() - prof_c0, dr = (long long)__builtin_amdgcn_s_memrealtime() - prof_r0;
-        reinterpret_cast<float*>(p.slabs)[blockIdx.x] = (float)(dc * 1000 / (dr + 1));
-    }
-#endif
+    const int tn = lane & 15;
+    return {tile_n, gn, gy, gx, lane >> 4, tn >> 2, tn & 3};
 }
 
-// ------------------------------------------------------------------------------------------------------------------------------------
-// wino2_x3_kernel — the same algorithm with its products on v_mfma_f32_16x16x32_bf16: fp32 products from three bf16 pieces per operand
-// and six MFMAs per 32-deep step (gemm_tile.h: THE SPLIT RULE, THE PRODUCT ORDER), 0.375 of the f32 instruction's matrix-pipe cycles.
-// Plain layers only (Cout % 64 == 0, no merged outputs).  What differs from wino2_kernel is the K loop and the weight image alone:
-//   * the bf16 instruction's C layout (col = lane & 15, row = 4 (lane >> 4) + reg) is the f32 one's, so lane = tile, accumulator block
-//     cb = channels 16 cb + 4 kq + e, y_update and the epilogue are the f32 kernel's;
-//   * K ORDER BY PERMUTATION: a sum over K does not care which eight channels a lane holds as long as A and B agree.  The patch reads stay
-//     exactly wino2_kernel's (the same rb[], the same swizzle, column 4 g + kq: conflict-free, scripts/wino2_banks.py); step s in {0, 1}
-//     of a frequency takes the groups g = 2 s and 2 s + 1, so B element j of lane (tn, kq) is channel 16 (2 s + (j >> 2)) + 4 kq + (j & 3)
-//     and the weight image (wino2_pack_weights_x3) carries the same permutation;
-//   * per step: 8 ds_read_b128 -> two float4 of V (three adds each, wino2_kernel's order) -> gemm_split3 on the pair -> 6 CB MFMAs,
-//     product-outer, cb-inner: l h, h l, m m, m h, h m, h h (weight piece first);
-//   * REGISTERS: ONE patch buffer — the next step's eight reads go out as soon as V is formed and land under the split and the MFMAs
-//     (32 registers instead of the 64 of wino2_kernel's double buffer); the weight ring stays two steps deep (2 x 3 x CB x 4 registers).
-// No barrier but the halo's, one basic block: every trap of docs/kernels.md 3.1l applies (pinned updates and V, sched_barrier around the
-// MFMA block, opaque scalars in the addresses, the 256-byte LDS alignment check in the launcher).
-
+// Halo.  The swizzle key of plane pixel (pr, pc): XORed into the 16-byte column on the way in (source side) and on the way out (rb[]).
 __device__ __forceinline__ constexpr int w2_key(int pr, int pc) { return 2 * ((pc + 4 * (pr & 1)) & 7); }
 
-// the halo of tile group (gn, gy, gx) -> LDS, wino2_kernel's layout (its comment at "---- halo")
+// The 64-channel halo of tile group (gn, gy, gx) -> LDS: 25 pieces of 4 LDS rows x 16 columns.  LDS row 4 i + pl holds pixel i = 5 pr + pc
+// of parity plane pl, so piece i is the same plane pixel of the four planes: its lanes' plane is lane >> 4 (computed once), its (pr, pc)
+// and swizzle key are compile-time constants — ~10 VALU per piece instead of ~30 with plane-major rows (the bank a read hits does not
+// depend on its row: a row is all 64 banks).  The NW waves of a workgroup take alternate pieces.
 template <int NW>
 __device__ __forceinline__ void w2_load_halo(const ConvArgs& p, char* const halo, const int lane, const int wv, const int gn, const int gy, const int gx) {
     const int H = p.H, W = p.W;
@@ -352,12 +110,58 @@ __device__ __forceinline__ void w2_load_halo(const ConvArgs& p, char* const halo
         const int pr = i / 5, pc = i - 5 * pr;
         const int y = y0 + 2 * pr, x = x0 + 2 * pc;
         const bool ok = (unsigned)y < (unsigned)H && (unsigned)x < (unsigned)W;
-        if (NW > 1 && (i % NW) != wv) continue;                            // (wave-uniform: the waves of a workgroup take alternate pieces)
+        if (NW > 1 && (i % NW) != wv) continue;                            // (wave-uniform)
         lds_dma16(ok ? img + ((long)2 * pr * W + 2 * pc) * 64 + ((col ^ w2_key(pr, pc)) << 2) : p.zeros, halo + i * 1024);
     }
 }
 
-// M of frequency F -> the four output accumulators with A^T's coefficients, pinned (wino2_kernel's y_update)
+// Patch addresses.  rb[4 dy + dx] = the ABSOLUTE LDS byte address of patch pixel (dy, dx) of tile (tr, tc), column kq of k-step group 0:
+// plane (dy & 1, dx & 1), plane pixel (tr + dy / 2, tc + dx / 2).  Group g is rb[] ^ (g << 6) — valid while the halo sits at a 256-byte
+// aligned LDS address, which launch_w2 checks.
+__device__ __forceinline__ void w2_patch_addrs(unsigned (&rb)[16], const char* const halo, const int tr, const int tc, const int kq) {
+    const unsigned halo_base = (unsigned)(size_t)(__attribute__((address_space(3))) const char*)halo;
+#pragma unroll
+    for (int dy = 0; dy < 4; ++dy)
+#pragma unroll
+        for (int dx = 0; dx < 4; ++dx) {
+            const int pl = (dy & 1) * 2 + (dx & 1), pr = tr + (dy >> 1), pc = tc + (dx >> 1);
+            rb[dy * 4 + dx] = halo_base + (unsigned)((4 * (pr * 5 + pc) + pl) * 256 + ((w2_key(pr, pc) ^ kq) << 4));
+        }
+}
+
+// Patch reads.  The four patch pixels frequency F = (i, j) needs — rows (kYA[i], kYB[i]) x columns (kYA[j], kYB[j]) — of k-step group g
+// (columns 4 g .. 4 g + 3).  The group offset is an opaque scalar: a compile-time XOR is hoisted out of the unrolled loop — 48 addresses
+// in registers; for g = 0 too: reads that depend on nothing float stages ahead.
+template <int F>
+__device__ __forceinline__ void w2_read_patch(v4f* const d, const unsigned (&rb)[16], const int g) {
+    typedef const __attribute__((address_space(3))) v4f* lds_v4f;
+    constexpr int ya = kYA[F >> 2], yb = kYB[F >> 2], xa = kYA[F & 3], xb = kYB[F & 3];
+    unsigned gxr = g << 6;
+    asm volatile("" : "+s"(gxr));
+    d[0] = *reinterpret_cast<lds_v4f>((size_t)(rb[ya * 4 + xa] ^ gxr));
+    d[1] = *reinterpret_cast<lds_v4f>((size_t)(rb[ya * 4 + xb] ^ gxr));
+    d[2] = *reinterpret_cast<lds_v4f>((size_t)(rb[yb * 4 + xa] ^ gxr));
+    d[3] = *reinterpret_cast<lds_v4f>((size_t)(rb[yb * 4 + xb] ^ gxr));
+}
+
+// V.  V_F = (B^T d B)[i][j] from the four values of w2_read_patch<F>: three signed adds, in this order (tests/wino2_x3_model.py states
+// the same), for the N k-step groups of a step at once: chain n reads d[4 n .. 4 n + 3], and each add is written for all chains before the
+// next one (chain after chain, the x3 kernel's K loop gains 27 s_waitcnt).  The caller pins the result in front of its MFMAs.
+template <int F, int N>
+__device__ __forceinline__ void w2_form_v(v4f (&v)[N], const v4f* const d) {
+    constexpr int fi = F >> 2, fj = F & 3;
+    constexpr int sab = kSA[fi] * kSB[fj], sba = kSB[fi] * kSA[fj], sbb = kSB[fi] * kSB[fj];
+#pragma unroll
+    for (int n = 0; n < N; ++n) v[n] = d[4 * n];
+#pragma unroll
+    for (int n = 0; n < N; ++n) v[n] = sab > 0 ? v[n] + d[4 * n + 1] : v[n] - d[4 * n + 1];
+#pragma unroll
+    for (int n = 0; n < N; ++n) v[n] = sba > 0 ? v[n] + d[4 * n + 2] : v[n] - d[4 * n + 2];
+#pragma unroll
+    for (int n = 0; n < N; ++n) v[n] = sbb > 0 ? v[n] + d[4 * n + 3] : v[n] - d[4 * n + 3];
+}
+
+// A^T fold.  M of frequency F -> the four output accumulators with A^T's {0, +-1} coefficients.
 template <int F, int CB>
 __device__ __forceinline__ void w2_y_update(v4f (&Y)[2][2][CB], const v4f (&M)[CB]) {
     constexpr int i = F >> 2, j = F & 3;
@@ -368,6 +172,8 @@ __device__ __forceinline__ void w2_y_update(v4f (&Y)[2][2][CB], const v4f (&M)[C
         if constexpr (c01 > 0) Y[0][1][cb] += M[cb]; else if constexpr (c01 < 0) Y[0][1][cb] -= M[cb];
         if constexpr (c10 > 0) Y[1][0][cb] += M[cb]; else if constexpr (c10 < 0) Y[1][0][cb] -= M[cb];
         if constexpr (c11 > 0) Y[1][1][cb] += M[cb]; else if constexpr (c11 < 0) Y[1][1][cb] -= M[cb];
+        // pinned here: pure arithmetic floats freely in this barrier-free kernel, and left alone the scheduler defers the updates —
+        // every deferred frequency keeps its 4 CB accumulator registers alive (256 registers + spills by the tenth frequency)
         if constexpr (c00 != 0) asm volatile("" : "+v"(Y[0][0][cb]));
         if constexpr (c01 != 0) asm volatile("" : "+v"(Y[0][1][cb]));
         if constexpr (c10 != 0) asm volatile("" : "+v"(Y[1][0][cb]));
@@ -375,8 +181,19 @@ __device__ __forceinline__ void w2_y_update(v4f (&Y)[2][2][CB], const v4f (&M)[C
     }
 }
 
-// the plain epilogue on the 2x2 pixels at (oy0, ox0) of image gn, channels n0 + 16 cb + e: every load before the first store
-// (wino2_kernel's, see there)
+// The fold over the 16 frequencies (see IC)
+template <class Stage>
+__device__ __forceinline__ void w2_each_freq(Stage&& stage) {
+    stage(IC<0>{}); stage(IC<1>{}); stage(IC<2>{}); stage(IC<3>{}); stage(IC<4>{}); stage(IC<5>{}); stage(IC<6>{}); stage(IC<7>{});
+    stage(IC<8>{}); stage(IC<9>{}); stage(IC<10>{}); stage(IC<11>{}); stage(IC<12>{}); stage(IC<13>{}); stage(IC<14>{}); stage(IC<15>{});
+}
+
+// Plain epilogue on the 2x2 pixels at (oy0, ox0) of image gn, channels n0 + 16 cb + e (n0 includes the lane's 4 kq): bias (its pixel's
+// border class when the block's BatchNorm is folded in) -> ReLU / PReLU -> + residual -> store (+ second output).
+// Every load goes out BEFORE the first store: bias, slope, residual — 36 float4 per lane in flight together, ONE global-memory latency.
+// (Per pixel "load, wait, compute, store" was four latencies in a row: with the stores masked to one lane of 64 the epilogue still cost
+// 33 of the layer's 195 us — it was never the traffic.)  The caller fences it off from the K loop: the kernel is one basic block, and
+// unfenced these loads are scheduled in front of the K loop and their ~80 destination registers spilled through it.
 template <int CB>
 __device__ __forceinline__ void w2_store_plain(const ConvArgs& p, const v4f (&Y)[2][2][CB], const int gn, const int oy0, const int ox0, const int n0) {
     const int Cout = p.Cout;
@@ -418,6 +235,169 @@ __device__ __forceinline__ void w2_store_plain(const ConvArgs& p, const v4f (&Y)
     }
 }
 
+// ====================================================================================================================================
+// NW = waves per workgroup that share ONE halo: wave w computes the 16 CB channels [16 CB w, 16 CB (w + 1)) of the workgroup's 16 CB NW-channel
+// column tile (NW = 1: the original one-wave form).  MERGED selects the merged-sibling epilogue (per-channel-range destinations).
+// NW = 2, CB = 2 on the plain 64-channel layers: the 25.6 KB halo limits a CU to six workgroups either way, so six waves of 226 registers
+// (1.5 per SIMD: two SIMDs carry two waves, two carry one) become twelve of 112 (three per SIMD) — DESIGN.md 3.1.
+template <int CB, int NW, bool MERGED>
+__global__ __launch_bounds__(64 * NW, NW == 1 ? 2 : 3) void wino2_kernel(const ConvArgs p, const int tiles_n, const int tgx, const int tgy) {
+    extern __shared__ v4f w2sm[];
+    char* const halo = reinterpret_cast<char*>(w2sm);                      // [5][5] plane pixels x [4 parity planes] x 16 x 16 B
+    const int lane = threadIdx.x & 63;
+    const int wv = NW == 1 ? 0 : __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
+    constexpr int CBT = CB * NW;                                           // 16-channel blocks per column tile in the weight image
+#ifdef FACEHIP_W2_PROF
+    const long long prof_c0 = __builtin_readcyclecounter(), prof_r0 = __builtin_amdgcn_s_memrealtime();   // shader clock vs the constant 100 MHz counter
+#endif
+    const W2Walk t = w2_walk(lane, tiles_n, tgx, tgy);
+    w2_load_halo<NW>(p, halo, lane, wv, t.gn, t.gy, t.gx);
+    unsigned rb[16];
+    w2_patch_addrs(rb, halo, t.tr, t.tc, t.kq);
+    // weights of this column tile: step (f, j) = CB KB at ((f * 4 + j) * CB) * 256 floats; cb-th fragment + cb * 256
+    // (a wave-uniform running pointer + the lane's 16-byte offset: with compile-time step offsets the 64 step addresses are hoisted out of
+    //  the loop into 128 registers)
+    const char* wstep = reinterpret_cast<const char*>(p.wt + ((size_t)t.tile_n * 64 * CBT + (size_t)wv * CB) * 256);
+    const unsigned wlane = lane * 16;
+    constexpr int WD = 2;                                                  // weight ring: fragments are requested WD - 1 steps (512 MFMA cycles each) ahead
+    v4f wr[WD][CB] = {};                                                   // (WD = 4 measured the same: 196.0 vs 194.6 us on 56x56x64, and costs 32 registers)
+#ifdef FACEHIP_W2_PROF
+    const bool abl_w = p.sk_test_drop & 4, abl_d = p.sk_test_drop & 8, abl_y = p.sk_test_drop & 16, abl_st = p.sk_test_drop & 2;   // ablations (wrong results)
+#else
+    constexpr bool abl_w = false, abl_d = false, abl_y = false, abl_st = false;
+#endif
+    auto fetch_w = [&](bool advance, int buf) __attribute__((always_inline)) {
+        if (abl_w) return;
+        unsigned adv = advance ? CBT * 1024 : 0;
+        asm volatile("" : "+s"(adv));
+        wstep += adv;
+#pragma unroll
+        for (int cb = 0; cb < CB; ++cb) wr[buf][cb] = *reinterpret_cast<const v4f*>(wstep + wlane + cb * 1024);
+    };
+    v4f Y[2][2][CB], Mp[CB];
+#pragma unroll
+    for (int cb = 0; cb < CB; ++cb) {
+        Mp[cb] = v4f{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int a = 0; a < 4; ++a) Y[a >> 1][a & 1][cb] = v4f{0.f, 0.f, 0.f, 0.f};
+    }
+    auto y_update = [&](auto fc, const v4f (&M)[CB]) __attribute__((always_inline)) {
+        constexpr int f = decltype(fc)::value;
+        if (abl_y && f != 5) return;
+        w2_y_update<f, CB>(Y, M);
+    };
+    v4f d[2][4] = {};                                                      // the patch values of two steps: a double buffer
+    auto fetch_d = [&](auto fc, auto jc, auto bc) __attribute__((always_inline)) {
+        if (abl_d) return;
+        w2_read_patch<decltype(fc)::value>(d[decltype(bc)::value], rb, decltype(jc)::value);   // k-step group j
+    };
+    auto stage = [&](auto fc) __attribute__((always_inline)) {
+        constexpr int f = decltype(fc)::value;
+        v4f M[CB];
+#pragma unroll
+        for (int cb = 0; cb < CB; ++cb) M[cb] = v4f{0.f, 0.f, 0.f, 0.f};
+        auto step = [&](auto jc) __attribute__((always_inline)) {
+            constexpr int j = decltype(jc)::value, k = f * 4 + j;
+            fetch_w(k + WD - 1 < 64, (k + WD - 1) % WD);                    // fragments of step k + WD - 1 (past the end: a harmless re-fetch)
+            if constexpr (j < 3) fetch_d(IC<f>{}, IC<j + 1>{}, IC<(k + 1) & 1>{});
+            else if constexpr (f < 15) fetch_d(IC<f + 1>{}, IC<0>{}, IC<(k + 1) & 1>{});
+            __builtin_amdgcn_sched_barrier(0);
+            v4f v[1];
+            w2_form_v<f>(v, d[k & 1]);
+            asm volatile("" : "+v"(v[0]));
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+#pragma unroll
+                for (int cb = 0; cb < CB; ++cb) M[cb] = __builtin_amdgcn_mfma_f32_16x16x4f32(wr[k % WD][cb][e], v[0][e], M[cb], 0, 0, 0);
+            __builtin_amdgcn_sched_barrier(0);
+        };
+        step(IC<0>{}); step(IC<1>{});
+        y_update(IC<(f + 15) & 15>{}, Mp);                                 // the previous frequency's result -> the outputs, in the shadow of this one's MFMAs
+        step(IC<2>{}); step(IC<3>{});
+#pragma unroll
+        for (int cb = 0; cb < CB; ++cb) Mp[cb] = M[cb];
+        __builtin_amdgcn_sched_barrier(0);
+    };
+    fetch_w(false, 0);
+#pragma unroll
+    for (int q = 1; q < WD - 1; ++q) fetch_w(true, q);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                       // the halo has landed: LDS-DMA is ordered for its own wave by vmcnt alone
+    if constexpr (NW > 1) __syncthreads();                                 // ... and for the sibling wave's pieces by the workgroup's only barrier
+    fetch_d(IC<0>{}, IC<0>{}, IC<0>{});
+    w2_each_freq(stage);
+    y_update(IC<15>{}, Mp);
+
+    // ---- epilogue: lane = tile (tr, tc), accumulator block cb = channels 16 cb + 4 kq .. + 3 of the column tile (fenced: w2_store_plain)
+    asm volatile("" ::: "memory");
+    __builtin_amdgcn_sched_barrier(0);
+    if (abl_st && lane != 0) return;                                       // (lane 0 goes on to the clock stamp; 63 of 64 lanes' stores are gone)
+    const int oy0 = 2 * (4 * t.gy + t.tr), ox0 = 2 * (4 * t.gx + t.tc);
+    const int n0 = (t.tile_n * NW + wv) * 16 * CB;
+    if constexpr (!MERGED) {
+        w2_store_plain<CB>(p, Y, t.gn, oy0, ox0, n0 + 4 * t.kq);
+    } else {                                                               // merged sibling convolutions: per-channel-range destination and activation
+        const int kq = t.kq, Cout = p.Cout;
+        float bm[CB][4];                                                   // this lane's 8 bias values, fetched once (no load between the stores)
+#pragma unroll
+        for (int cb = 0; cb < CB; ++cb)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) { const int co = n0 + 16 * cb + 4 * kq + e; bm[cb][e] = co < Cout ? p.bias[co] : 0.f; }
+#pragma unroll
+        for (int a = 0; a < 2; ++a)
+#pragma unroll
+            for (int b = 0; b < 2; ++b) {
+                const int oy = oy0 + a, ox = ox0 + b;
+                if (oy >= p.Ho || ox >= p.Wo) continue;
+                const size_t pix = ((size_t)t.gn * p.Ho + oy) * p.Wo + ox;  // (merged convolutions carry no folded BatchNorm: wino2_ok)
+#pragma unroll
+                for (int cb = 0; cb < CB; ++cb)
+#pragma unroll
+                    for (int e = 0; e < 4; e += 2) {                       // channel pairs: one 8-byte store where both land in one destination, aligned
+                        const int co = n0 + 16 * cb + 4 * kq + e;
+                        if (co >= Cout) continue;
+                        const int g = co >= p.oc0[2] && p.n_outs > 2 ? 2 : co >= p.oc0[1] ? 1 : 0;
+                        const int cg = p.oc0[g + 1] - p.oc0[g], ga = p.oact[g];
+                        auto fin = [&](float v) { return ga == (int)Act::RELU ? fmaxf(v, 0.f) : ga == (int)Act::SIGMOID ? 1.0f / (1.0f + expf(-v)) : v; };
+                        float* const dst = p.outs[g] + pix * cg + (co - p.oc0[g]);
+                        const float v0 = fin(Y[a][b][cb][e] + bm[cb][e]);
+                        if (co + 1 < p.oc0[g + 1] && !((cg | (co - p.oc0[g])) & 1)) {
+                            *reinterpret_cast<float2*>(dst) = float2{v0, fin(Y[a][b][cb][e + 1] + bm[cb][e + 1])};
+                        } else {
+                            dst[0] = v0;
+                            if (co + 1 < Cout) {                          // the pair straddles two destinations (or is unaligned): scalar stores
+                                const int g1 = co + 1 >= p.oc0[2] && p.n_outs > 2 ? 2 : co + 1 >= p.oc0[1] ? 1 : 0;
+                                const int cg1 = p.oc0[g1 + 1] - p.oc0[g1], ga1 = p.oact[g1];
+                                float v1 = Y[a][b][cb][e + 1] + bm[cb][e + 1];
+                                v1 = ga1 == (int)Act::RELU ? fmaxf(v1, 0.f) : ga1 == (int)Act::SIGMOID ? 1.0f / (1.0f + expf(-v1)) : v1;
+                                p.outs[g1][pix * cg1 + (co + 1 - p.oc0[g1])] = v1;
+                            }
+                        }
+                    }
+            }
+    }
+#ifdef FACEHIP_W2_PROF
+    if (lane == 0 && p.slabs && blockIdx.x < (1u << 17)) {                 // this wave's mean shader clock in MHz x 10 -> the diagnostic buffer (never an output)
+        const long long dc = __builtin_readcyclecounter() - prof_c0, dr = (long long)__builtin_amdgcn_s_memrealtime() - prof_r0;
+        reinterpret_cast<float*>(p.slabs)[blockIdx.x] = (float)(dc * 1000 / (dr + 1));
+    }
+#endif
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------------
+// wino2_x3_kernel — the same algorithm with its products on v_mfma_f32_16x16x32_bf16: fp32 products from three bf16 pieces per operand
+// and six MFMAs per 32-deep step (gemm_tile.h: THE SPLIT RULE, THE PRODUCT ORDER), 0.375 of the f32 instruction's matrix-pipe cycles.
+// Plain layers only (Cout % 64 == 0, no merged outputs).  What differs from wino2_kernel is the K loop and the weight image alone:
+//   * the bf16 instruction's C layout (col = lane & 15, row = 4 (lane >> 4) + reg) is the f32 one's, so lane = tile, accumulator block
+//     cb = channels 16 cb + 4 kq + e, and the whole tile body above applies unchanged;
+//   * K ORDER BY PERMUTATION: a sum over K does not care which eight channels a lane holds as long as A and B agree.  The patch reads stay
+//     w2_read_patch's (the same rb[], the same swizzle, column 4 g + kq: conflict-free, scripts/wino2_banks.py); step s in {0, 1}
+//     of a frequency takes the groups g = 2 s and 2 s + 1, so B element j of lane (tn, kq) is channel 16 (2 s + (j >> 2)) + 4 kq + (j & 3)
+//     and the weight image (wino2_pack_weights_x3) carries the same permutation;
+//   * per step: 8 ds_read_b128 -> two float4 of V (w2_form_v) -> gemm_split3 on the pair -> 6 CB MFMAs,
+//     product-outer, cb-inner: l h, h l, m m, m h, h m, h h (weight piece first);
+//   * REGISTERS: ONE patch buffer — the next step's eight reads go out as soon as V is formed and land under the split and the MFMAs
+//     (32 registers instead of the 64 of wino2_kernel's double buffer); the weight ring stays two steps deep (2 x 3 x CB x 4 registers).
 // <CB = 2, NW = 2> is the one instantiation: 160 registers, three waves per SIMD — the six workgroups per CU the halo allows.  <4, 1> at one
 // wave per SIMD (238 + 32 registers, four workgroups per CU) measured 0.85-0.93 of the f32 kernel where this one has 0.75-0.89
 // (profiles/wino2_x3.md); at two waves per SIMD it would spill.
@@ -427,31 +407,14 @@ __global__ __launch_bounds__(64 * NW, 3) void wino2_x3_kernel(const ConvArgs p, 
     char* const halo = reinterpret_cast<char*>(w2sm);                      // [5][5] plane pixels x [4 parity planes] x 16 x 16 B
     const int lane = threadIdx.x & 63;
     const int wv = NW == 1 ? 0 : __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
-    int blk;
-    {
-        const int n = gridDim.x, q = n >> 3, r = n & 7, x = blockIdx.x & 7;
-        blk = x * q + min(x, r) + (int)(blockIdx.x >> 3);                  // XCD-contiguous order
-    }
-    const int tile_n = blk % tiles_n, tg = blk / tiles_n;
-    const int per_img = tgx * tgy;
-    const int gn = tg / per_img, rem = tg - gn * per_img;
-    const int gy = rem / tgx, gx = rem - gy * tgx;
-    const int tn = lane & 15, kq = lane >> 4, tr = tn >> 2, tc = tn & 3;
-    w2_load_halo<NW>(p, halo, lane, wv, gn, gy, gx);
-    typedef const __attribute__((address_space(3))) v4f* lds_v4f;
-    const unsigned halo_base = (unsigned)(size_t)(__attribute__((address_space(3))) char*)halo;
+    const W2Walk t = w2_walk(lane, tiles_n, tgx, tgy);
+    w2_load_halo<NW>(p, halo, lane, wv, t.gn, t.gy, t.gx);
     unsigned rb[16];
-#pragma unroll
-    for (int dy = 0; dy < 4; ++dy)
-#pragma unroll
-        for (int dx = 0; dx < 4; ++dx) {
-            const int pl = (dy & 1) * 2 + (dx & 1), pr = tr + (dy >> 1), pc = tc + (dx >> 1);
-            rb[dy * 4 + dx] = halo_base + (unsigned)((4 * (pr * 5 + pc) + pl) * 256 + ((w2_key(pr, pc) ^ kq) << 4));
-        }
+    w2_patch_addrs(rb, halo, t.tr, t.tc, t.kq);
     // weights of this column tile and wave: step k = 2 f + s is 3 planes x CB fragments of 1 KB (64 lanes x 8 bf16), the waves' steps
     // interleaved: [16 f][2 s][NW][3][CB][64][8].  A wave-uniform running pointer + the lane's 16-byte offset, as in wino2_kernel.
     constexpr unsigned WSTEP = 3 * CB * 1024;
-    const char* wstep = reinterpret_cast<const char*>(p.wt) + ((size_t)tile_n * 32 * NW + (size_t)wv) * WSTEP;
+    const char* wstep = reinterpret_cast<const char*>(p.wt) + ((size_t)t.tile_n * 32 * NW + (size_t)wv) * WSTEP;
     const unsigned wlane = lane * 16;
     bf16x8 wr[2][3][CB] = {};                                              // [ring][plane h, m, l][cb]
     auto fetch_w = [&](bool advance, int buf) __attribute__((always_inline)) {
@@ -473,22 +436,11 @@ __global__ __launch_bounds__(64 * NW, 3) void wino2_x3_kernel(const ConvArgs p, 
     v4f d[8] = {};                                                         // the patch values of ONE step: groups g = 2 s (0..3) and 2 s + 1 (4..7)
     auto fetch_d = [&](auto fc, auto sc) __attribute__((always_inline)) {
         constexpr int f = decltype(fc)::value, s = decltype(sc)::value;
-        constexpr int fi = f >> 2, fj = f & 3;
-        constexpr int ya = kYA[fi], yb = kYB[fi], xa = kYA[fj], xb = kYB[fj];
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            unsigned gxr = (2 * s + h) << 6;                               // group g = columns 4 g .. 4 g + 3 (an opaque scalar, as in wino2_kernel)
-            asm volatile("" : "+s"(gxr));
-            d[4 * h + 0] = *reinterpret_cast<lds_v4f>((size_t)(rb[ya * 4 + xa] ^ gxr));
-            d[4 * h + 1] = *reinterpret_cast<lds_v4f>((size_t)(rb[ya * 4 + xb] ^ gxr));
-            d[4 * h + 2] = *reinterpret_cast<lds_v4f>((size_t)(rb[yb * 4 + xa] ^ gxr));
-            d[4 * h + 3] = *reinterpret_cast<lds_v4f>((size_t)(rb[yb * 4 + xb] ^ gxr));
-        }
+        w2_read_patch<f>(d, rb, 2 * s);
+        w2_read_patch<f>(d + 4, rb, 2 * s + 1);
     };
     auto stage = [&](auto fc) __attribute__((always_inline)) {
         constexpr int f = decltype(fc)::value;
-        constexpr int fi = f >> 2, fj = f & 3;
-        constexpr int sab = kSA[fi] * kSB[fj], sba = kSB[fi] * kSA[fj], sbb = kSB[fi] * kSB[fj];
         v4f M[CB];
 #pragma unroll
         for (int cb = 0; cb < CB; ++cb) M[cb] = v4f{0.f, 0.f, 0.f, 0.f};
@@ -496,16 +448,14 @@ __global__ __launch_bounds__(64 * NW, 3) void wino2_x3_kernel(const ConvArgs p, 
             constexpr int s = decltype(sc)::value, k = f * 2 + s;
             fetch_w(k + 1 < 32, (k + 1) & 1);                              // fragments of step k + 1 (past the end: a harmless re-fetch)
             __builtin_amdgcn_sched_barrier(0);
-            v4f v0 = d[0], v1 = d[4];
-            v0 = sab > 0 ? v0 + d[1] : v0 - d[1];  v1 = sab > 0 ? v1 + d[5] : v1 - d[5];
-            v0 = sba > 0 ? v0 + d[2] : v0 - d[2];  v1 = sba > 0 ? v1 + d[6] : v1 - d[6];
-            v0 = sbb > 0 ? v0 + d[3] : v0 - d[3];  v1 = sbb > 0 ? v1 + d[7] : v1 - d[7];
-            asm volatile("" : "+v"(v0), "+v"(v1));
+            v4f v[2];
+            w2_form_v<f>(v, d);
+            asm volatile("" : "+v"(v[0]), "+v"(v[1]));
             __builtin_amdgcn_sched_barrier(0);
             if constexpr (s == 0) fetch_d(IC<f>{}, IC<1>{});               // the patch buffer is free: the next step's reads land under the MFMAs
             else if constexpr (f < 15) fetch_d(IC<f + 1>{}, IC<0>{});
             bf16x8 vh, vm, vl;
-            gemm_split3(v0, v1, vh, vm, vl);
+            gemm_split3(v[0], v[1], vh, vm, vl);
             asm volatile("" : "+v"(vh), "+v"(vm), "+v"(vl));
             __builtin_amdgcn_sched_barrier(0);
             const bf16x8 (&w)[3][CB] = wr[k & 1];
@@ -534,55 +484,45 @@ __global__ __launch_bounds__(64 * NW, 3) void wino2_x3_kernel(const ConvArgs p, 
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                       // the halo has landed: LDS-DMA is ordered for its own wave by vmcnt alone
     if constexpr (NW > 1) __syncthreads();                                 // ... and for the sibling wave's pieces by the workgroup's only barrier
     fetch_d(IC<0>{}, IC<0>{});
-    stage(IC<0>{}); stage(IC<1>{}); stage(IC<2>{}); stage(IC<3>{}); stage(IC<4>{}); stage(IC<5>{}); stage(IC<6>{}); stage(IC<7>{});
-    stage(IC<8>{}); stage(IC<9>{}); stage(IC<10>{}); stage(IC<11>{}); stage(IC<12>{}); stage(IC<13>{}); stage(IC<14>{}); stage(IC<15>{});
+    w2_each_freq(stage);
     w2_y_update<15, CB>(Y, Mp);
-    asm volatile("" ::: "memory");                                         // (one basic block: keeps the epilogue's loads behind the K loop, as in wino2_kernel)
+    asm volatile("" ::: "memory");                                         // (fenced: w2_store_plain)
     __builtin_amdgcn_sched_barrier(0);
-    w2_store_plain<CB>(p, Y, gn, 2 * (4 * gy + tr), 2 * (4 * gx + tc), (tile_n * NW + wv) * 16 * CB + 4 * kq);
+    w2_store_plain<CB>(p, Y, t.gn, 2 * (4 * t.gy + t.tr), 2 * (4 * t.gx + t.tc), (t.tile_n * NW + wv) * 16 * CB + 4 * t.kq);
 }
 
 bool shape_ok(int Cin, int Cout) { return Cin == 64 && (Cout % 64 == 0 || Cout <= 32); }   // (<= 32: merged outputs only, see wino2_ok)
 
-template <int CB, int NW, bool MERGED>
-void launch_cb(const ConvArgs& a, hipStream_t s) {
-    const int tgy = ((a.H + 1) / 2 + 3) / 4, tgx = ((a.W + 1) / 2 + 3) / 4;
+constexpr int w2_groups(int extent) { return ((extent + 1) / 2 + 3) / 4; }   // 4 x 4 tile groups (8 x 8 outputs) along a map side
+
+// One workgroup of NW waves per (tile group, column tile of COLS channels); KERNEL(args, tiles_n, tgx, tgy) with 25.6 KB of dynamic LDS.
+template <auto KERNEL, int COLS, int NW>
+void launch_w2(const ConvArgs& a, hipStream_t s) {
+    const int tgy = w2_groups(a.H), tgx = w2_groups(a.W);
     const long n_tg = (long)a.B * tgy * tgx;
-    const int tiles_n = (a.Cout + 16 * CB * NW - 1) / (16 * CB * NW);      // column tiles of 16 CB NW channels: one workgroup each
-    // The kernel XORs swizzle keys into ABSOLUTE LDS addresses (rb[] ^ (j << 6)): that equals base + (offset ^ key) only while the dynamic
-    // LDS base is 256-byte aligned, i.e. 0 — true as long as the kernel declares no static __shared__ object.  Checked once per instantiation.
+    const int tiles_n = (a.Cout + COLS - 1) / COLS;
+    // The kernels XOR swizzle keys into ABSOLUTE LDS addresses (w2_patch_addrs, w2_read_patch): that equals base + (offset ^ key) only while
+    // the dynamic LDS base is 256-byte aligned, i.e. 0 — true as long as the kernel declares no static __shared__ object.  Checked once per
+    // instantiation.
     static const bool lds_ok = [] {
         hipFuncAttributes fa{};
-        FH_HIP(hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(&wino2_kernel<CB, NW, MERGED>)));
+        FH_HIP(hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(KERNEL)));
         return fa.sharedSizeBytes % 256 == 0;
     }();
-    if (!lds_ok) throw std::runtime_error("wino2: static LDS moved the halo off its 256-byte alignment (see the address XOR in fetch_d)");
+    if (!lds_ok) throw std::runtime_error("wino2: static LDS moved the halo off its 256-byte alignment (see the address XOR in w2_read_patch)");
     KernelTimer& timer = KernelTimer::get();
     timer.begin(s);
-    hipLaunchKernelGGL((wino2_kernel<CB, NW, MERGED>), dim3((unsigned)(n_tg * tiles_n)), dim3(64 * NW), 25600, s, a, tiles_n, tgx, tgy, (int)n_tg);
+    hipLaunchKernelGGL(KERNEL, dim3((unsigned)(n_tg * tiles_n)), dim3(64 * NW), 25600, s, a, tiles_n, tgx, tgy);
     // booked with the FLOPs the matrix cores EXECUTE (padded tiles / channels included); bytes slot: the layer's direct-form FLOPs, as tag 7
-    timer.end(s, 12, 2.0 * 16 * 16.0 * (double)n_tg * a.Cin * (16.0 * CB * NW * tiles_n), a.t_flops);
-}
-
-template <int CB, int NW>
-void launch_x3_cb(const ConvArgs& a, hipStream_t s) {
-    const int tgy = ((a.H + 1) / 2 + 3) / 4, tgx = ((a.W + 1) / 2 + 3) / 4;
-    const long n_tg = (long)a.B * tgy * tgx;
-    const int tiles_n = a.Cout / 64;
-    static const bool lds_ok = [] {                                        // (the address XOR in fetch_d: as launch_cb)
-        hipFuncAttributes fa{};
-        FH_HIP(hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(&wino2_x3_kernel<CB, NW>)));
-        return fa.sharedSizeBytes % 256 == 0;
-    }();
-    if (!lds_ok) throw std::runtime_error("wino2: static LDS moved the halo off its 256-byte alignment (see the address XOR in fetch_d)");
-    KernelTimer& timer = KernelTimer::get();
-    timer.begin(s);
-    hipLaunchKernelGGL((wino2_x3_kernel<CB, NW>), dim3((unsigned)(n_tg * tiles_n)), dim3(64 * NW), 25600, s, a, tiles_n, tgx, tgy);
-    timer.end(s, 12, 2.0 * 16 * 16.0 * (double)n_tg * a.Cin * (64.0 * tiles_n), a.t_flops);   // (booked as launch_cb books the f32 form)
+    timer.end(s, 12, 2.0 * 16 * 16.0 * (double)n_tg * a.Cin * ((double)COLS * tiles_n), a.t_flops);
 }
 
 }  // namespace
 
+// The two packers below each keep their own fp64 G g G^T loop and the x3 packer its own statement of THE SPLIT RULE: one shared U function
+// and a named host split (byte-identical images) changed the packers' speed, and scripts/wino2_bench.py, which packs on the host in front
+// of every launch, then measured 56x56x64 -> 128 4-7 % slower on BOTH kernels with the kernels' code unchanged
+// (profiles/wino2_tile_refactor.md 3: new kernels + these packers run at the parent's level, the parent's kernels + shared packers do not).
 // U_f = G g G^T per (output channel, input channel) in fp64, G = [1 0 0; .5 .5 .5; .5 -.5 .5; 0 0 1], in the order the kernel streams it:
 // [column tile][16 f][4 g][CB blocks of 16 channels][64 lanes (m = lane & 15, kq = lane >> 4)][4 floats],
 // element = U_f[cout = 16 CB tn + 16 cb + m][cin = 16 g + 4 kq + e]; channels >= Cout are zero rows.  w = [Cout][9 taps][Cin] (the engine's layout).
@@ -670,7 +610,7 @@ double wino2_debug_clock_mhz() {
 
 // one-wave workgroups of the launch, in units of four (= the 256-thread workgroups the engine's cross-over is expressed in)
 long wino2_blocks(const ConvArgs& a) {
-    return (long)a.B * (((a.H + 1) / 2 + 3) / 4) * (((a.W + 1) / 2 + 3) / 4) * ((a.Cout + 63) / 64) / 4;
+    return (long)a.B * w2_groups(a.H) * w2_groups(a.W) * ((a.Cout + 63) / 64) / 4;
 }
 
 // a.wt = wino2_pack_weights' image of the filter; everything else as for launch_conv
@@ -685,19 +625,19 @@ void launch_wino2(const ConvArgs& a_in, hipStream_t s) {
     a.slabs = g_w2_clock;
     // plain 64-channel column tiles: two waves of 32 channels around one halo (FACEHIP_WINO2_NW=1: the one-wave form of round 4, for A / B timing)
     static const int nw = [] { const char* e = getenv("FACEHIP_WINO2_NW"); return e ? atoi(e) : 2; }();
-    if (a.Cout <= 32) launch_cb<2, 1, true>(a, s);
-    else if (nw == 2) launch_cb<2, 2, false>(a, s);
-    else launch_cb<4, 1, false>(a, s);
+    if (a.Cout <= 32) launch_w2<wino2_kernel<2, 1, true>, 32, 1>(a, s);
+    else if (nw == 2) launch_w2<wino2_kernel<2, 2, false>, 64, 2>(a, s);
+    else launch_w2<wino2_kernel<4, 1, false>, 64, 1>(a, s);
 }
 
 // The same layer on wino2_x3_kernel: a.wt = wino2_pack_weights_x3's image.  Plain layers only.
 bool wino2_x3_ok(const ConvArgs& a) { return wino2_ok(a) && a.n_outs == 0 && wino2_x3_shape_ok(a.Cin, a.Cout); }
-long wino2_x3_workgroups(const ConvArgs& a) { return (long)a.B * (((a.H + 1) / 2 + 3) / 4) * (((a.W + 1) / 2 + 3) / 4) * (a.Cout / 64); }
+long wino2_x3_workgroups(const ConvArgs& a) { return (long)a.B * w2_groups(a.H) * w2_groups(a.W) * (a.Cout / 64); }
 void launch_wino2_x3(const ConvArgs& a_in, hipStream_t s) {
     if (!wino2_x3_ok(a_in)) throw std::runtime_error("launch_wino2_x3: layer shape not supported");
     ConvArgs a = a_in;
     a.zeros = conv_zero_line();
-    launch_x3_cb<2, 2>(a, s);
+    launch_w2<wino2_x3_kernel<2, 2>, 64, 2>(a, s);
 }
 
 }  // namespace fh

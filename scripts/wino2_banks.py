@@ -2,7 +2,8 @@
 """CPU model of conv_wino2.hip's data movement (no GPU): (1) every ds_read_b128 of the K loop, per 16-lane service group, counted for
 LDS bank conflicts; (2) the whole kernel emulated in numpy on small layers — halo planes with the swizzled columns, lane -> tile map,
 B^T d B / G g G^T / A^T M A, the packed weight order, the accumulator layout of v_mfma_f32_16x16x4_f32 — against a direct convolution.
-Mirrors the kernel's index arithmetic one to one (halo rows, key, rb[], weight steps)."""
+Mirrors the index arithmetic of the tile body one to one (w2_load_halo's rows, w2_key, w2_patch_addrs' rb[], w2_read_patch's group XOR,
+the weight steps); wino2_x3_kernel makes the same reads."""
 import numpy as np
 
 # lanes a ds_read_b128 serves together (MI355X_MICROARCH.md, LDS table)

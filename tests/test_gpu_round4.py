@@ -208,13 +208,8 @@ WINO2_CASES = [
 ]
 
 
-@pytest.mark.parametrize("B,H,W,Cin,Cout,act,with_res,cls", WINO2_CASES)
-def test_wino2_fused_conv_layer_matches_oracle(B, H, W, Cin, Cout, act, with_res, cls):
-    """The fused Winograd F(2x2,3x3) kernel (conv_wino2.hip) that takes the 3x3 stride-1 convolutions of w600k_r50's 64-channel stages
-    (and, through the network tests, SCRFD's merged 64 -> 30 head convolutions)
-    (Conv nodes inside session_->Run, face_recognizer.cpp:279-283) against the oracle's direct fp32 convolution: bias per border class
-    (the block's BatchNorm folded in), PReLU / ReLU, residual.  5e-5 absolute on O(1) outputs: F(2x2) rounds ~3x coarser than the direct
-    form's 2e-5 bar (points 0, +-1, inf), far inside F(4x4)'s 2e-4."""
+def check_wino2_case(B, H, W, Cin, Cout, act, with_res, cls):
+    """One WINO2_CASES row through fh_conv_wino2_dev against the oracle's direct fp32 convolution, 5e-5 absolute."""
     rng = np.random.default_rng(B * 1000 + H * 10 + Cin + Cout)
     x = rng.standard_normal((B, Cin, H, W)).astype(np.float32)
     w = (rng.standard_normal((Cout, Cin, 3, 3)) / np.sqrt(Cin * 9)).astype(np.float32)
@@ -247,6 +242,47 @@ def test_wino2_fused_conv_layer_matches_oracle(B, H, W, Cin, Cout, act, with_res
     got = out.cpu().numpy().transpose(0, 3, 1, 2)
     assert not np.isnan(got).any()
     np.testing.assert_allclose(got, ref.astype(np.float32), rtol=0, atol=5e-5)
+
+
+@pytest.mark.parametrize("B,H,W,Cin,Cout,act,with_res,cls", WINO2_CASES)
+def test_wino2_fused_conv_layer_matches_oracle(B, H, W, Cin, Cout, act, with_res, cls):
+    """The fused Winograd F(2x2,3x3) kernel (conv_wino2.hip) that takes the 3x3 stride-1 convolutions of w600k_r50's 64-channel stages
+    (and, through the network tests, SCRFD's merged 64 -> 30 head convolutions)
+    (Conv nodes inside session_->Run, face_recognizer.cpp:279-283) against the oracle's direct fp32 convolution: bias per border class
+    (the block's BatchNorm folded in), PReLU / ReLU, residual.  5e-5 absolute on O(1) outputs: F(2x2) rounds ~3x coarser than the direct
+    form's 2e-5 bar (points 0, +-1, inf), far inside F(4x4)'s 2e-4."""
+    check_wino2_case(B, H, W, Cin, Cout, act, with_res, cls)
+
+
+WINO2_NW1_CASES = [(1, 2, 2, 64, 64, 0, False, True), (5, 13, 17, 64, 64, 1, True, False), (2, 30, 22, 64, 192, 2, True, True)]
+
+_WINO2_NW1_WORKER = r"""
+import os, sys
+sys.path.insert(0, sys.argv[1])
+import facerecognizeonnx_amd as fa
+from oracle import oracle
+from tests.test_gpu_round4 import WINO2_NW1_CASES, check_wino2_case
+assert os.environ.get("FACEHIP_WINO2_NW") == "1"
+fa._lib.check(fa.lib().fh_init(0), "fh_init")
+oracle.set_threads(min(16, os.cpu_count() or 8))
+for case in WINO2_NW1_CASES:
+    check_wino2_case(*case)
+    print("wino2 nw1 case", case, "ok", flush=True)
+print("wino2 nw1 ok")
+"""
+
+
+@pytest.mark.timeout(150)
+def test_wino2_one_wave_form_matches_oracle_in_a_child_process(tmp_path):
+    """`wino2_kernel<4, 1, false>` — one wave per workgroup, all 64 channels of the column tile — is reached only through
+    FACEHIP_WINO2_NW=1, which the library reads once per process: a fresh child process with the variable set runs three WINO2_CASES rows
+    (a single tile; ragged tile groups with ReLU + residual; three column tiles with PReLU, residual and the 9 bias classes) against the
+    same oracle at the same 5e-5 bar as the two-wave form above."""
+    script = tmp_path / "wino2_nw1_worker.py"
+    script.write_text(_WINO2_NW1_WORKER)
+    p = subprocess.run([sys.executable, str(script), ROOT], env=dict(os.environ, FACEHIP_WINO2_NW="1"), stdout=subprocess.PIPE,
+                       stderr=subprocess.STDOUT, text=True, timeout=120)
+    assert p.returncode == 0 and "wino2 nw1 ok" in p.stdout, p.stdout[-3000:]
 
 
 _dw_graph = util.dw_graph                            # (shared with tests/test_gpu_locality.py)
