@@ -275,6 +275,13 @@ PROTOTYPES = {
     "fh_jpegenc_destroy": (None, [_vp]),
     "fh_jpeg_forward_batch_dev": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp]),
     "fh_jpeg_encode_batch": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "fh_jpeg_write_header": (_i, [_vp, _vp, C.c_size_t, _vp]),
+    "fh_jpeg_scan_bits": (_i, [_vp, _vp, _vp, C.c_size_t]),
+    "fh_jpeg_code_batch_dev": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    "fh_jpeg_encode_batch_gpu": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
+    "fh_jpeg_stuff_chunk": (_i, []),
+    "fh_debug_jpeg_arena": (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(C.c_size_t)]),
+    "fh_debug_jpeg_scan_bits": (_ll, [_vp, _vp, C.c_size_t]),
     "fh_det_set_winograd": (_i, [_vp, _i]),
     "fh_rec_set_winograd": (_i, [_vp, _i]),
     "fh_rec_set_wino_fusion": (_i, [_vp, _i]),

@@ -633,8 +633,8 @@ class JpegDecoder:
 
 class JpegEncoder:
     """fh_jpegenc: BGR pictures -> baseline JPEG files with colour conversion, chroma down-sampling, the forward DCT and quantisation on
-    the GPU and the Huffman coding on host threads; the coefficients are the ones libjpeg stores for the same pixels, bit for bit, and the
-    bytes are fh_jpeg_write(fh_jpeg_forward(...))'s."""
+    the GPU and the Huffman coding on host threads (coder = "host", the default) or on the GPU as well (coder = "device"); the
+    coefficients are the ones libjpeg stores for the same pixels, bit for bit, and the bytes are fh_jpeg_write(fh_jpeg_forward(...))'s."""
 
     SUBSAMPLING = {"4:4:4": 0, "444": 0, 0: 0, "4:2:2": 1, "422": 1, 1: 1, "4:2:0": 2, "420": 2, 2: 2}
 
@@ -648,25 +648,33 @@ class JpegEncoder:
         if h:
             _lib.lib().fh_jpegenc_destroy(h)
 
-    def encode_dev(self, frames, quality: int = 95, subsampling="4:2:0", threads: int = 0, stream: int = 0):
+    def encode_dev(self, frames, quality: int = 95, subsampling="4:2:0", threads: int = 0, stream: int = 0, coder: str = "host"):
         """fh_jpeg_encode_batch: frames = DEVICE pictures as frame_array takes them ((ptr, rows, cols[, step]) or None).  Blocking.
-        Returns a list of bytes, None for an empty frame."""
+        coder = "host": Huffman coding on `threads` host threads; "device": on the GPU too (fh_jpeg_encode_batch_gpu; `threads` is not
+        used), only the files' bytes come back.  The same bytes either way.  Returns a list of bytes, None for an empty frame."""
+        if coder not in ("host", "device"):
+            raise ValueError('coder must be "host" or "device"')
         arr = frame_array(frames)
         n = _frame_count(arr)
         if n == 0:
             return []
         blobs = (_lib.FhBlob * n)()
-        check(_lib.lib().fh_jpeg_encode_batch(self.handle, arr, n, int(quality), self.SUBSAMPLING[subsampling], int(threads), blobs, stream),
-              "fh_jpeg_encode_batch")
+        if coder == "device":
+            check(_lib.lib().fh_jpeg_encode_batch_gpu(self.handle, arr, n, int(quality), self.SUBSAMPLING[subsampling], blobs, stream),
+                  "fh_jpeg_encode_batch_gpu")
+        else:
+            check(_lib.lib().fh_jpeg_encode_batch(self.handle, arr, n, int(quality), self.SUBSAMPLING[subsampling], int(threads), blobs, stream),
+                  "fh_jpeg_encode_batch")
         return [C.string_at(b.bytes, b.n) if b.bytes else None for b in blobs]
 
-    def encode(self, frames, quality: int = 95, subsampling="4:2:0", threads: int = 0):
+    def encode(self, frames, quality: int = 95, subsampling="4:2:0", threads: int = 0, coder: str = "host"):
         """encode_dev on HOST pictures (uint8[rows, cols, 3] BGR arrays; None or an empty array = an empty frame), uploaded first."""
         import torch
         imgs = [_img(f) for f in frames]
         keep = [None if a is None else torch.from_numpy(np.ascontiguousarray(a)).cuda() for a in imgs]
         torch.cuda.synchronize()
-        out = self.encode_dev([None if t is None else (t.data_ptr(), t.shape[0], t.shape[1]) for t in keep], quality, subsampling, threads)
+        out = self.encode_dev([None if t is None else (t.data_ptr(), t.shape[0], t.shape[1]) for t in keep], quality, subsampling, threads,
+                              coder=coder)
         del keep
         return out
 
@@ -680,9 +688,10 @@ def imwrite(path: str, image, quality: int = 95, subsampling="4:2:0") -> bool:
                                       JpegEncoder.SUBSAMPLING[subsampling]) == 0
 
 
-def face_chips(rec: FaceRecognizer, image, faces, quality: int = 95, subsampling="4:2:0", encoder: Optional[JpegEncoder] = None):
-    """The aligned crop of every face of one HOST picture as a JPEG file: fh_rec_align_dev -> fh_jpeg_encode_batch, pixels and
-    coefficients never leave the device.  faces = FACE_DTYPE records (FaceDetector.detect_records).  Returns (list of bytes — None for a
+def face_chips(rec: FaceRecognizer, image, faces, quality: int = 95, subsampling="4:2:0", encoder: Optional[JpegEncoder] = None,
+               coder: str = "host"):
+    """The aligned crop of every face of one HOST picture as a JPEG file: fh_rec_align_dev -> fh_jpeg_encode_batch, pixels never
+    leave the device (nor, with coder = "device", the coefficients: JpegEncoder.encode_dev).  faces = FACE_DTYPE records (FaceDetector.detect_records).  Returns (list of bytes — None for a
     face whose crop is empty —, the crops uint8[n, H, W, 3] as the device made them)."""
     import torch
     a = _img(image)
@@ -704,7 +713,8 @@ def face_chips(rec: FaceRecognizer, image, faces, quality: int = 95, subsampling
     live = ok.cpu().numpy() != 0
     enc = encoder if encoder is not None else JpegEncoder()
     one = h.value * w.value * 3
-    files = enc.encode_dev([(crops.data_ptr() + i * one, h.value, w.value) if live[i] else None for i in range(n)], quality, subsampling)
+    files = enc.encode_dev([(crops.data_ptr() + i * one, h.value, w.value) if live[i] else None for i in range(n)], quality, subsampling,
+                           coder=coder)
     return files, crops.cpu().numpy()
 
 

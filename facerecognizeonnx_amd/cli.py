@@ -1,6 +1,6 @@
 """Text-mode counterpart of the reference's demo executable (reference src/main.cpp:264-319):
 
-    python -m facerecognizeonnx_amd.cli detect  <image>            [--det det.onnx] [--tile N --overlap M [--border B]] [--chips DIR [--rec rec.onnx]]
+    python -m facerecognizeonnx_amd.cli detect  <image>            [--det det.onnx] [--tile N --overlap M [--border B]] [--chips DIR [--rec rec.onnx] [--coder device]]
     python -m facerecognizeonnx_amd.cli compare <image1> <image2>  [--det det.onnx] [--rec rec.onnx] [--device-jpeg]
     python -m facerecognizeonnx_amd.cli simple  <image1> <image2>  [--rec rec.onnx]
 
@@ -11,7 +11,7 @@ are printed instead of drawn (no GUI, no webcam).  Images are read by the librar
 `detect --tile N` runs the tiled detection of large frames (whole frame + overlapping N x N tiles, one merged NMS; facehip.h).
 `detect --chips DIR` also writes every detected face's aligned crop as DIR/<image>_<k>.jpg: the recogniser's alignment
 (fh_rec_align_dev, so the recogniser model is loaded too) and the JPEG encoder's forward path run on the GPU, the Huffman coding on host
-threads (fh_jpeg_encode_batch).
+threads (fh_jpeg_encode_batch); with `--coder device` the Huffman coding runs on the GPU as well (fh_jpeg_encode_batch_gpu), the same bytes.
 `compare --device-jpeg` reads both files through fh_pipeline_run_files: JPEGs are entropy-decoded on host threads and reconstructed on the
 GPU (the same pixels), then detected and embedded in one call; without the flag nothing changes.
 Model paths default to the reference's (models/det_500m.onnx, models/w600k_r50.onnx, main.cpp:269-270).
@@ -70,6 +70,7 @@ def main(argv=None) -> int:
     ap.add_argument("--border", type=int, default=2, help="detect --tile: drop boxes within this many pixels of an interior tile edge (< 0: off)")
     ap.add_argument("--chips", default=None, metavar="DIR", help="detect: write every face's aligned crop as DIR/<image>_<k>.jpg")
     ap.add_argument("--chip-quality", type=int, default=95, help="detect --chips: JPEG quality")
+    ap.add_argument("--coder", choices=["host", "device"], default="host", help="detect --chips: where the Huffman coding runs")
     ap.add_argument("--device-jpeg", action="store_true", help="compare: decode the files through fh_pipeline_run_files (JPEG reconstruction on the GPU)")
     a = ap.parse_args(argv)
     det, rec = FaceDetector(), FaceRecognizer()
@@ -103,7 +104,8 @@ def main(argv=None) -> int:
             print(f"Face {i}: box={f.box} score={f.score:.4f} landmarks={np.round(f.landmarks, 1).tolist()}")
         if a.chips is not None and faces:
             os.makedirs(a.chips, exist_ok=True)
-            files, _ = api.face_chips(rec, imgs[0], np.concatenate([f.to_record() for f in faces]), quality=a.chip_quality)
+            files, _ = api.face_chips(rec, imgs[0], np.concatenate([f.to_record() for f in faces]), quality=a.chip_quality,
+                                      coder=a.coder)
             stem = os.path.splitext(os.path.basename(a.images[0]))[0]
             for k, data in enumerate(files):
                 if data is None:

@@ -1039,6 +1039,8 @@ struct fh_jpegenc {
     fh::DevBuf d_coef;                   // fh_jpeg_encode_batch: the coefficients of every frame ...
     PinnedBuf h_coef;                    // ... and where the one device-to-host copy lands
     std::vector<unsigned char> bytes[16];   // the byte arena: per host thread, the files it wrote, back to back
+    fh::JpegHuff huff;                   // fh_jpeg_code_batch_dev: the device coder and its device byte arena
+    PinnedBuf h_files;                   // fh_jpeg_encode_batch_gpu: where the one copy of that arena lands
 };
 namespace {
 // null, or why fh_jpeg_forward_batch_dev refuses the call (fh_jpeg_enc_check's complaint is already in g_err then: "")
@@ -1055,16 +1057,38 @@ const char* bad_enc_batch(const fh_jpeg_desc* descs, int n, const fh_frame* fram
     }
     return nullptr;
 }
-// fh_jpeg_encode_batch's body (arguments checked): returns the number of files written
-int jpeg_encode_batch(fh_jpegenc* enc, const fh_frame* frames, int n, int quality, int subsampling, int threads, fh_blob* files_out, hipStream_t s) {
-    threads = threads <= 0 ? std::min(16, n) : std::min(threads, 16);
-    std::vector<fh_jpeg_desc> descs((size_t)n);
-    std::vector<long long> base((size_t)n, 0);
-    std::vector<fh_frame> live((size_t)n);
-    std::vector<int> order;                                                   // the live frames
-    size_t coef_elems = 0;
+// null, or why fh_jpeg_code_batch_dev refuses the call (as bad_enc_batch; a live slot is one with coef_base[i] >= 0)
+const char* bad_code_batch(const fh_jpeg_desc* descs, int n, const int16_t* d_coef, const long long* coef_base, const fh_blob* files) {
+    if (!descs || !d_coef || !coef_base || !files) return "null argument";
+    if (n <= 0 || n > 4096) return "need 1 <= n <= 4096 images";
+    if (reinterpret_cast<uintptr_t>(d_coef) & 1) return "d_coef must be 2-byte aligned";
+    size_t blocks = 0;
     for (int i = 0; i < n; ++i) {
-        files_out[i] = fh_blob{nullptr, 0};
+        if (coef_base[i] < 0) continue;
+        if (fh_jpeg_enc_check(&descs[i]) != 0) return "";
+        blocks += (fh_jpeg_write_bound(&descs[i]) - 1024) / 416;              // the bound is 1024 + 416 bytes a block
+    }
+    if (blocks >= ((size_t)1 << 31)) return "the batch has 2^31 blocks or more: the coder's block indices are 31-bit";
+    return nullptr;
+}
+// null, or why fh_jpeg_encode_batch / _gpu refuse the call
+const char* bad_encode_frames(const fh_jpegenc* enc, const fh_frame* frames, int n, int subsampling, const fh_blob* files_out) {
+    if (!enc || !frames || !files_out) return "null argument";
+    if (n <= 0 || n > 4096) return "need 1 <= n <= 4096 frames";
+    if (subsampling < 0 || subsampling > 2) return "subsampling must be 0 (4:4:4), 1 (4:2:2) or 2 (4:2:0)";
+    for (int i = 0; i < n; ++i) {
+        const fh_frame& f = frames[i];
+        if (!(f.bgr && f.rows > 0 && f.cols > 0)) continue;
+        if (f.rows > 65535 || f.cols > 65535) return "a frame is larger than 65535 in one direction";
+        if ((long long)f.step < (long long)f.cols * 3) return "a frame's step is smaller than cols * 3";
+    }
+    return nullptr;
+}
+// the descriptors of fh_jpeg_encode_batch / _gpu: one per live frame, the images' coefficients back to back; order = the live frames
+void encode_descs(const fh_frame* frames, int n, int quality, int subsampling, std::vector<fh_jpeg_desc>& descs, std::vector<long long>& base,
+                  std::vector<fh_frame>& live, size_t& coef_elems, std::vector<int>& order) {
+    coef_elems = 0;
+    for (int i = 0; i < n; ++i) {
         live[(size_t)i] = frames[i];
         if (!(frames[i].bgr && frames[i].rows > 0 && frames[i].cols > 0)) { live[(size_t)i] = fh_frame{nullptr, 0, 0, 0}; continue; }
         if (fh_jpeg_enc_desc(frames[i].cols, frames[i].rows, 0, subsampling, quality, &descs[(size_t)i]) != 0) throw std::runtime_error(g_err);
@@ -1072,6 +1096,45 @@ int jpeg_encode_batch(fh_jpegenc* enc, const fh_frame* frames, int n, int qualit
         coef_elems += (size_t)descs[(size_t)i].coef_count;                    // a multiple of 64: every image starts 128-byte aligned
         order.push_back(i);
     }
+}
+// fh_jpeg_encode_batch_gpu's body (arguments checked): returns the number of files written
+int jpeg_encode_batch_gpu(fh_jpegenc* enc, const fh_frame* frames, int n, int quality, int subsampling, fh_blob* files_out, hipStream_t s) {
+    std::vector<fh_jpeg_desc> descs((size_t)n);
+    std::vector<long long> base((size_t)n, -1);                               // -1: the coder's mark of a skipped slot
+    std::vector<fh_frame> live((size_t)n);
+    size_t coef_elems = 0;
+    for (int i = 0; i < n; ++i) files_out[i] = fh_blob{nullptr, 0};
+    std::vector<int> order;
+    encode_descs(frames, n, quality, subsampling, descs, base, live, coef_elems, order);
+    if (order.empty()) return 0;
+    enc->d_coef.ensure(coef_elems * sizeof(int16_t));
+    enc->dev.forward(descs.data(), n, FI(live.data()), enc->d_coef.as<int16_t>(), base.data(), s);
+    if (const char* bad = bad_code_batch(descs.data(), n, enc->d_coef.as<int16_t>(), base.data(), files_out))
+        throw std::runtime_error(std::string("fh_jpeg_encode_batch_gpu: ") + (*bad ? bad : g_err.c_str()));
+    std::vector<fh_blob> dev_files((size_t)n);
+    std::vector<int> status((size_t)n);
+    const int m = enc->huff.code(descs.data(), n, enc->d_coef.as<int16_t>(), base.data(), dev_files.data(), status.data(), s);
+    for (int i = 0; i < n; ++i)
+        if (status[(size_t)i] < 0) throw std::runtime_error("fh_jpeg_encode_batch_gpu: coefficients without a baseline code");   // (no forward path makes them)
+    const size_t bytes = enc->huff.arena_used();
+    enc->h_files.ensure(bytes);
+    FH_HIP(hipMemcpyAsync(enc->h_files.p, enc->huff.arena().p, bytes, hipMemcpyDeviceToHost, s));
+    FH_HIP(hipStreamSynchronize(s));
+    const unsigned char* const d0 = enc->huff.arena().as<unsigned char>();
+    for (int i = 0; i < n; ++i)
+        if (dev_files[(size_t)i].bytes) files_out[i] = fh_blob{static_cast<unsigned char*>(enc->h_files.p) + (dev_files[(size_t)i].bytes - d0), dev_files[(size_t)i].n};
+    return m;
+}
+// fh_jpeg_encode_batch's body (arguments checked): returns the number of files written
+int jpeg_encode_batch(fh_jpegenc* enc, const fh_frame* frames, int n, int quality, int subsampling, int threads, fh_blob* files_out, hipStream_t s) {
+    threads = threads <= 0 ? std::min(16, n) : std::min(threads, 16);
+    std::vector<fh_jpeg_desc> descs((size_t)n);
+    std::vector<long long> base((size_t)n, 0);
+    std::vector<fh_frame> live((size_t)n);
+    size_t coef_elems = 0;
+    for (int i = 0; i < n; ++i) files_out[i] = fh_blob{nullptr, 0};
+    std::vector<int> order;                                                   // the live frames
+    encode_descs(frames, n, quality, subsampling, descs, base, live, coef_elems, order);
     if (order.empty()) return 0;
     enc->d_coef.ensure(coef_elems * sizeof(int16_t));
     enc->h_coef.ensure(coef_elems * sizeof(int16_t));
@@ -1134,16 +1197,40 @@ int fh_jpeg_forward_batch_dev(fh_jpegenc* enc, const fh_jpeg_desc* descs, int n,
 
 int fh_jpeg_encode_batch(fh_jpegenc* enc, const fh_frame* frames, int n, int quality, int subsampling, int threads, fh_blob* files_out,
                          void* stream) {
-    if (!enc || !frames || !files_out) return arg_error("fh_jpeg_encode_batch: null argument");
-    if (n <= 0 || n > 4096) return arg_error("fh_jpeg_encode_batch: need 1 <= n <= 4096 frames");
-    if (subsampling < 0 || subsampling > 2) return arg_error("fh_jpeg_encode_batch: subsampling must be 0 (4:4:4), 1 (4:2:2) or 2 (4:2:0)");
-    for (int i = 0; i < n; ++i) {
-        const fh_frame& f = frames[i];
-        if (!(f.bgr && f.rows > 0 && f.cols > 0)) continue;
-        if (f.rows > 65535 || f.cols > 65535) return arg_error("fh_jpeg_encode_batch: a frame is larger than 65535 in one direction");
-        if ((long long)f.step < (long long)f.cols * 3) return arg_error("fh_jpeg_encode_batch: a frame's step is smaller than cols * 3");
-    }
+    if (const char* bad = bad_encode_frames(enc, frames, n, subsampling, files_out)) { g_err = std::string("fh_jpeg_encode_batch: ") + bad; return FH_ERR_ARG; }
     return guarded([&] { return jpeg_encode_batch(enc, frames, n, quality, subsampling, threads, files_out, S(stream)); });
+}
+
+int fh_jpeg_code_batch_dev(fh_jpegenc* enc, const fh_jpeg_desc* descs, int n, const int16_t* d_coef, const long long* coef_base,
+                           fh_blob* files_dev_out, int* status, void* stream) {
+    if (!enc) return arg_error("fh_jpeg_code_batch_dev: null handle");
+    if (const char* bad = bad_code_batch(descs, n, d_coef, coef_base, files_dev_out)) {
+        if (*bad) g_err = std::string("fh_jpeg_code_batch_dev: ") + bad;
+        return FH_ERR_ARG;
+    }
+    return guarded([&] { return enc->huff.code(descs, n, d_coef, coef_base, files_dev_out, status, S(stream)); });
+}
+
+int fh_jpeg_encode_batch_gpu(fh_jpegenc* enc, const fh_frame* frames, int n, int quality, int subsampling, fh_blob* files_out, void* stream) {
+    if (const char* bad = bad_encode_frames(enc, frames, n, subsampling, files_out)) { g_err = std::string("fh_jpeg_encode_batch_gpu: ") + bad; return FH_ERR_ARG; }
+    return guarded([&] { return jpeg_encode_batch_gpu(enc, frames, n, quality, subsampling, files_out, S(stream)); });
+}
+
+int fh_jpeg_stuff_chunk(void) { return FH_JPEG_STUFF_CHUNK; }
+
+int fh_debug_jpeg_arena(fh_jpegenc* enc, int fill, void** dev, size_t* bytes) {
+    if (!enc || !dev || !bytes) return arg_error("fh_debug_jpeg_arena: null argument");
+    *dev = enc->huff.arena().p; *bytes = enc->huff.arena().bytes;
+    if (fill < 0 || !*bytes) return 0;
+    return guarded([&] { FH_HIP(hipDeviceSynchronize()); FH_HIP(hipMemset(*dev, fill & 255, *bytes)); FH_HIP(hipDeviceSynchronize()); return 0; });
+}
+
+long long fh_debug_jpeg_scan_bits(fh_jpegenc* enc, uint32_t* bits, size_t cap) {
+    if (!enc || (!bits && cap)) return arg_error("fh_debug_jpeg_scan_bits: null argument");
+    const long long B = enc->huff.blocks();
+    if ((unsigned long long)B > cap) return arg_error("fh_debug_jpeg_scan_bits: the output holds fewer entries than the last call had blocks");
+    const int rc = guarded([&] { if (B) FH_HIP(hipMemcpy(bits, enc->huff.bits().p, (size_t)B * sizeof(uint32_t), hipMemcpyDeviceToHost)); return 0; });
+    return rc < 0 ? rc : B;
 }
 
 // Two-stream form for streaming callers: detect (+ decode + NMS + face selection) on stream_det, align + embed on stream_rec

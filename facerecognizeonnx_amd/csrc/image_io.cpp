@@ -1171,8 +1171,15 @@ struct ByteSink {
 
 inline int bit_length(unsigned v) { return v ? 32 - __builtin_clz(v) : 0; }
 
-// jchuff.c encode_one_block; false for a DC difference outside +-2047 or an AC value outside +-1023
-bool encode_block(ByteSink& s, const EncHuff& h, const int16_t* blk, int& pred, int dc_tbl, int ac_tbl) {
+// fh_jpeg_scan_bits's sink: the bits encode_block emits, counted
+struct BitCount {
+    uint32_t n = 0;
+    void bits(unsigned, int k) { n += (uint32_t)k; }
+};
+
+// jchuff.c encode_one_block into a ByteSink or a BitCount; false for a DC difference outside +-2047 or an AC value outside +-1023
+template <class Sink>
+bool encode_block(Sink& s, const EncHuff& h, const int16_t* blk, int& pred, int dc_tbl, int ac_tbl) {
     const int diff = blk[0] - pred;
     pred = blk[0];
     int t = diff < 0 ? -diff : diff, t2 = diff < 0 ? diff - 1 : diff;
@@ -1197,8 +1204,8 @@ bool encode_block(ByteSink& s, const EncHuff& h, const int16_t* blk, int& pred, 
     return true;
 }
 
-// fh_jpeg_write's body (the descriptor passed bad_enc_desc): false for a coefficient the baseline tables cannot code.  s.pos = the size.
-bool jpeg_write(const fh_jpeg_desc& o, const int16_t* coef, ByteSink& s) {
+// fh_jpeg_write_header's body and the front of jpeg_write: SOI .. the SOS header, everything in front of the first entropy-coded byte
+void jpeg_write_header(const fh_jpeg_desc& o, ByteSink& s) {
     const int nc = o.ncomp;
     int tq[3] = {0, 1, 1};                                                 // libjpeg's assignment; a third table only where Cr's differs from Cb's
     if (nc == 3 && memcmp(o.comp[2].quant, o.comp[1].quant, sizeof(o.comp[1].quant)) != 0) tq[2] = 2;
@@ -1224,6 +1231,12 @@ bool jpeg_write(const fh_jpeg_desc& o, const int16_t* coef, ByteSink& s) {
     s.marker(0xDA); s.u16(6 + 2 * nc); s.byte(nc);
     for (int i = 0; i < nc; ++i) { s.byte(i + 1); s.byte(i ? 0x11 : 0x00); }
     s.byte(0); s.byte(63); s.byte(0);
+}
+
+// fh_jpeg_write's body (the descriptor passed bad_enc_desc): false for a coefficient the baseline tables cannot code.  s.pos = the size.
+bool jpeg_write(const fh_jpeg_desc& o, const int16_t* coef, ByteSink& s) {
+    const int nc = o.ncomp;
+    jpeg_write_header(o, s);
     int pred[3] = {0, 0, 0};
     const EncHuff& huff = enc_huff();
     const int mcux = o.comp[0].wblocks / o.comp[0].h, mcuy = o.comp[0].hblocks / o.comp[0].v;
@@ -1242,15 +1255,50 @@ bool jpeg_write(const fh_jpeg_desc& o, const int16_t* coef, ByteSink& s) {
     return true;
 }
 
+// fh_jpeg_scan_bits's body: jpeg_write's walk over the blocks with the counting sink; false as jpeg_write
+bool jpeg_scan_bits(const fh_jpeg_desc& o, const int16_t* coef, uint32_t* bits) {
+    int pred[3] = {0, 0, 0};
+    const EncHuff& huff = enc_huff();
+    const int mcux = o.comp[0].wblocks / o.comp[0].h, mcuy = o.comp[0].hblocks / o.comp[0].v;
+    for (int my = 0; my < mcuy; ++my)
+        for (int mx = 0; mx < mcux; ++mx)
+            for (int i = 0; i < o.ncomp; ++i) {
+                const fh_jpeg_comp& c = o.comp[i];
+                for (int y = 0; y < c.v; ++y)
+                    for (int x = 0; x < c.h; ++x) {
+                        const int16_t* blk = coef + c.coef_off + ((size_t)(my * c.v + y) * c.wblocks + (size_t)(mx * c.h + x)) * 64;
+                        BitCount n;
+                        if (!encode_block(n, huff, blk, pred[i], i ? 1 : 0, i ? 3 : 2)) return false;
+                        *bits++ = n.n;
+                    }
+            }
+    return true;
+}
+
+// the blocks of the interleaved scan: every component's padded grid
+size_t jpeg_scan_blocks(const fh_jpeg_desc& o) {
+    size_t blocks = 0;
+    for (int i = 0; i < o.ncomp; ++i) blocks += (size_t)o.comp[i].wblocks * o.comp[i].hblocks;
+    return blocks;
+}
+
 // headers (at most 2 + 18 + 3 * 69 + 19 + 2 * 33 + 2 * 183 + 14 + 2 < 1024 bytes) + per block the longest codes: DC 11 + 11 bits,
 // 63 AC values of 16 + 10 bits = 1660 bits < 208 bytes, every one of them stuffed
 size_t jpeg_write_bound(const fh_jpeg_desc& o) {
-    size_t blocks = 0;
-    for (int i = 0; i < o.ncomp; ++i) blocks += (size_t)o.comp[i].wblocks * o.comp[i].hblocks;
-    return 1024 + blocks * 416;
+    return 1024 + jpeg_scan_blocks(o) * 416;
 }
 
 }  // namespace
+
+namespace fh {
+// The writer's code tables for the device coder (jpeg_huff.hip): entry [t * 256 + symbol] = length << 16 | code, t = DC0, DC1, AC0, AC1
+// as kStdHuff; 0 for a symbol without a code.
+void jpeg_huff_codes(uint32_t* tab) {
+    const EncHuff& h = enc_huff();
+    for (int t = 0; t < 4; ++t)
+        for (int k = 0; k < 256; ++k) tab[t * 256 + k] = (uint32_t)h.len[t][k] << 16 | h.code[t][k];
+}
+}  // namespace fh
 
 extern "C" {
 
@@ -1318,6 +1366,28 @@ int fh_jpeg_write(const fh_jpeg_desc* desc, const int16_t* coef, unsigned char* 
     }
     *written = s.pos;
     if (s.pos > cap) { fh::set_error("fh_jpeg_write: the output buffer is too small (see *written)"); return FH_ERR_ARG; }
+    return 0;
+}
+
+int fh_jpeg_write_header(const fh_jpeg_desc* desc, unsigned char* out, size_t cap, size_t* written) {
+    if (written) *written = 0;
+    if (!desc || !written || (!out && cap)) { fh::set_error("fh_jpeg_write_header: null argument"); return FH_ERR_ARG; }
+    if (const char* bad = bad_enc_desc(desc)) { fh::set_error(std::string("fh_jpeg_write_header: ") + bad); return FH_ERR_ARG; }
+    ByteSink s{out, cap};
+    jpeg_write_header(*desc, s);
+    *written = s.pos;
+    if (s.pos > cap) { fh::set_error("fh_jpeg_write_header: the output buffer is too small (see *written)"); return FH_ERR_ARG; }
+    return 0;
+}
+
+int fh_jpeg_scan_bits(const fh_jpeg_desc* desc, const int16_t* coef, uint32_t* bits, size_t cap) {
+    if (!desc || !coef || (!bits && cap)) { fh::set_error("fh_jpeg_scan_bits: null argument"); return FH_ERR_ARG; }
+    if (const char* bad = bad_enc_desc(desc)) { fh::set_error(std::string("fh_jpeg_scan_bits: ") + bad); return FH_ERR_ARG; }
+    if (jpeg_scan_blocks(*desc) > cap) { fh::set_error("fh_jpeg_scan_bits: the output holds fewer entries than the scan has blocks"); return FH_ERR_ARG; }
+    if (!jpeg_scan_bits(*desc, coef, bits)) {
+        fh::set_error("fh_jpeg_scan_bits: a DC difference outside +-2047 or an AC coefficient outside +-1023 has no baseline code");
+        return FH_ERR_ARG;
+    }
     return 0;
 }
 

@@ -22,4 +22,33 @@ class JpegEnc {
     DevBuf planes_;
 };
 
+// image_io.cpp: the host writer's code tables, [DC0, DC1, AC0, AC1][256] entries of length << 16 | code
+void jpeg_huff_codes(uint32_t* tab);
+
+// The Huffman coder on the device (jpeg_huff.hip): owns the staged tables of a call, the per-block bit counts and offsets, the unstuffed
+// streams, the 0xFF counts and the byte arena the files are assembled in.  All grow on demand.
+class JpegHuff {
+  public:
+    JpegHuff() = default;
+    JpegHuff(const JpegHuff&) = delete;
+    JpegHuff& operator=(const JpegHuff&) = delete;
+    ~JpegHuff();
+    // fh_jpeg_code_batch_dev's body, arguments already checked (every live descriptor through fh_jpeg_enc_check; live = coef_base[i] >= 0):
+    // files[i] = {device pointer into the arena, size} and status[i] (0 coded, 1 skipped, FH_ERR_ARG uncodable) for every slot; returns the
+    // number of files coded.  Synchronises s twice; the assembling kernel is asynchronous on s.
+    int code(const fh_jpeg_desc* descs, int n, const int16_t* d_coef, const long long* coef_base, fh_blob* files, int* status, hipStream_t s);
+    const DevBuf& arena() const { return arena_; }
+    size_t arena_used() const { return used_; }                            // bytes of the last call's files
+    const DevBuf& bits() const { return bits_; }
+    long long blocks() const { return blocks_; }                           // of the last call: entries of bits()
+
+  private:
+    StagedTable geom_, place_, files_;                                     // the tables of the size / pack, the stuffing and the assembling passes
+    DevBuf bits_, off_, partial_, totals_, raw_, ff_, ffoff_, arena_;
+    void* h_totals_ = nullptr;                                             // pinned: what the two synchronisations bring back, a few bytes per image
+    size_t h_totals_bytes_ = 0;
+    size_t used_ = 0;
+    long long blocks_ = 0;
+};
+
 }  // namespace fh

@@ -1069,7 +1069,7 @@ FH_API int fh_pipeline_run_files(fh_det* d, fh_rec* r, fh_jpegdec* dec, const fh
 
 /* ---- JPEG out: the decode split in mirror image.  Colour conversion, chroma down-sampling, the forward DCT and quantisation are integer
  * arithmetic that is independent per block (kernels, csrc/jpeg_enc.hip); Huffman coding is serial per file and independent across files
- * (host threads).  The cut is the same dense int16 coefficient plane per component, described by the same fh_jpeg_desc.  The arithmetic
+ * (host threads; or, opt-in, parallel over blocks on the device: fh_jpeg_code_batch_dev below).  The cut is the same dense int16 coefficient plane per component, described by the same fh_jpeg_desc.  The arithmetic
  * is libjpeg's (jccolor.c, jcsample.c without smoothing, jfdctint.c "islow", jcdctmgr.c, jccoefct.c's dummy blocks): the coefficients
  * are, bit for bit, the ones libjpeg(-turbo) stores for the same pixels, sampling and quality (tests/test_jpeg_enc_cpu.py, against files
  * written by Pillow).  The files are baseline sequential JFIF with the four Annex K Huffman tables (libjpeg without `optimize`), one
@@ -1092,6 +1092,11 @@ FH_API int fh_pipeline_run_files(fh_det* d, fh_rec* r, fh_jpegdec* dec, const fh
  *           produces) returns FH_ERR_ARG, *written = 0.  Otherwise *written = the size of the file whatever cap is; cap smaller than that
  *           returns FH_ERR_ARG and nothing at or behind out + cap is written, so that a caller can size and retry.
  * fh_jpeg_write_bound  an upper bound of *written for the descriptor (0 for one fh_jpeg_enc_check refuses).
+ * fh_jpeg_write_header  the bytes fh_jpeg_write emits in front of the first entropy-coded byte (SOI .. the SOS header), from the same code;
+ *           cap / *written as fh_jpeg_write (*written = the size whatever cap is; nothing at or behind out + cap is written).
+ * fh_jpeg_scan_bits  bits[b] = the bits fh_jpeg_write's block coder emits for block b of the scan, in SCAN order: MCU by MCU, inside an
+ *           MCU component by component, v rows of h blocks each.  cap = the entries `bits` holds (>= the blocks of all components).
+ *           FH_ERR_ARG for a coefficient fh_jpeg_write refuses.  The host rule of the device coder's size pass.
  * fh_imwrite_jpeg  fh_jpeg_enc_desc + fh_jpeg_forward + fh_jpeg_write + a file write: cv::imwrite(path.jpg, bgr) with
  *           IMWRITE_JPEG_QUALITY = quality and the chroma sampling chosen by `subsampling`.
  * All: 0 on success, < 0 + fh_last_error().  Host code, no GPU. */
@@ -1101,9 +1106,12 @@ FH_API int fh_jpeg_enc_check(const fh_jpeg_desc* desc);
 FH_API int fh_jpeg_forward(const fh_jpeg_desc* desc, const unsigned char* bgr, int step, int16_t* coef, size_t cap);
 FH_API int fh_jpeg_write(const fh_jpeg_desc* desc, const int16_t* coef, unsigned char* out, size_t cap, size_t* written);
 FH_API size_t fh_jpeg_write_bound(const fh_jpeg_desc* desc);
+FH_API int fh_jpeg_write_header(const fh_jpeg_desc* desc, unsigned char* out, size_t cap, size_t* written);
+FH_API int fh_jpeg_scan_bits(const fh_jpeg_desc* desc, const int16_t* coef, uint32_t* bits, size_t cap);
 FH_API int fh_imwrite_jpeg(const char* path, const unsigned char* bgr, int rows, int cols, int step, int quality, int subsampling);
 /* fh_jpegenc  owner of the device side: the device copy of the descriptor table, the workspace of sample planes and (for
- *           fh_jpeg_encode_batch) the device and pinned coefficient arenas and the output byte arena.  All grow on demand.
+ *           fh_jpeg_encode_batch) the device and pinned coefficient arenas and the output byte arena, and the device Huffman coder's
+ *           tables, streams and device byte arena (fh_jpeg_code_batch_dev).  All grow on demand.
  * fh_jpeg_forward_batch_dev  fh_jpeg_forward for n images (1 <= n <= 4096) of any sizes and layouts in TWO launches, whatever n is: descs =
  *           HOST array (read before the call returns), frames[i].bgr = DEVICE pixels at any address and any pitch step >= cols * 3, whose
  *           rows / cols must equal the descriptor's; d_coef = DEVICE int16 (2-byte aligned), image i writes [coef_base[i], coef_base[i] +
@@ -1116,7 +1124,27 @@ FH_API int fh_imwrite_jpeg(const char* path, const unsigned char* bgr, int rows,
  *           threads (clipped to [1, 16]; 0 = min(16, n)), one file per task.  files_out[i] points into the handle's byte arena, valid until
  *           the next call on `enc`; an empty frame (bgr == NULL or a non-positive size) gives {NULL, 0} and the call still succeeds.  Every
  *           file equals fh_jpeg_write(fh_jpeg_forward(...)) on the host, byte for byte, whatever `threads` is.  Blocking; returns the number
- *           of files written. */
+ *           of files written.
+ *
+ * Huffman coding on the device (kernels, csrc/jpeg_huff.hip): baseline coding is parallel over blocks — a block's code depends on its
+ * own 64 coefficients and the DC of the previous block of its component in scan order, its place in the stream is a prefix sum of code
+ * lengths, and byte stuffing a second prefix sum over bytes.  No kernel waits for another workgroup; nothing depends on timing.
+ * fh_jpeg_code_batch_dev  fh_jpeg_write for n images (1 <= n <= 4096) whose coefficients lie in DEVICE memory: descs / d_coef / coef_base
+ *           as fh_jpeg_forward_batch_dev, except that the SKIPPED slots are those with coef_base[i] < 0 (their descriptors are not looked
+ *           at).  Every live descriptor passes fh_jpeg_enc_check before anything is launched: one bad one fails the call with FH_ERR_ARG
+ *           and nothing is written; so does a batch of 2^31 blocks or more.  The files lie back to back, in slot order, in a device byte
+ *           arena owned by the handle: files_dev_out[i] = {DEVICE pointer, size}, valid until the next call on `enc`.  status[i] (may be
+ *           NULL): 0 = coded, the file equals fh_jpeg_write's byte for byte; 1 = skipped slot; FH_ERR_ARG = the image holds a DC
+ *           difference outside +-2047 or an AC value outside +-1023 — its file is {NULL, 0}, as a skipped slot's, and the other images
+ *           are still written.  d_coef is only read.  The call synchronises `stream` TWICE (after the size pass, for the images' bit
+ *           totals, and after the 0xFF count, for the files' sizes); the last kernels are asynchronous on `stream`.  Returns the number
+ *           of files coded.
+ * fh_jpeg_encode_batch_gpu  fh_jpeg_encode_batch without host coding: the same descriptors and forward path, then
+ *           fh_jpeg_code_batch_dev, then ONE device-to-host copy of the file bytes alone into pinned memory (a third synchronisation).
+ *           files_out[i] points into that host arena, valid until the next call on `enc`; an empty frame gives {NULL, 0}.  The bytes
+ *           equal fh_jpeg_encode_batch's.  Blocking; returns the number of files written.
+ * FH_JPEG_STUFF_CHUNK (fh_jpeg_stuff_chunk())  the bytes of an image's unstuffed stream one workgroup of the stuffing passes handles. */
+#define FH_JPEG_STUFF_CHUNK 1024
 typedef struct fh_jpegenc fh_jpegenc;
 FH_API fh_jpegenc* fh_jpegenc_create(void);
 FH_API void fh_jpegenc_destroy(fh_jpegenc* enc);
@@ -1124,6 +1152,16 @@ FH_API int fh_jpeg_forward_batch_dev(fh_jpegenc* enc, const fh_jpeg_desc* descs,
                                      const long long* coef_base, void* stream);
 FH_API int fh_jpeg_encode_batch(fh_jpegenc* enc, const fh_frame* frames, int n, int quality, int subsampling, int threads, fh_blob* files_out,
                                 void* stream);
+FH_API int fh_jpeg_code_batch_dev(fh_jpegenc* enc, const fh_jpeg_desc* descs, int n, const int16_t* d_coef, const long long* coef_base,
+                                  fh_blob* files_dev_out, int* status, void* stream);
+FH_API int fh_jpeg_encode_batch_gpu(fh_jpegenc* enc, const fh_frame* frames, int n, int quality, int subsampling, fh_blob* files_out,
+                                    void* stream);
+FH_API int fh_jpeg_stuff_chunk(void);
+/* test hooks: the device byte arena of the last fh_jpeg_code_batch_dev (its base and capacity; fill in 0..255 sets every byte of it to
+ * that value first, fill < 0 leaves it alone), and the size pass's bits per block of that call — the live images' blocks in scan order,
+ * image after image — copied to the host (returns the count; cap = entries of `bits`). */
+FH_API int fh_debug_jpeg_arena(fh_jpegenc* enc, int fill, void** dev, size_t* bytes);
+FH_API long long fh_debug_jpeg_scan_bits(fh_jpegenc* enc, uint32_t* bits, size_t cap);
 
 /* ---- single kernels exposed for parity tests and micro-benchmarks (device pointers). */
 FH_API int fh_memcpy_d2h(void* host_dst, const void* dev_src, size_t bytes);   /* synchronous */

@@ -6,6 +6,10 @@ process (this script calls itself with --leg), alternated over --rounds rounds:
   kernels     the two forward kernels alone on frames resident in HBM (events around fh_jpeg_forward_batch_dev), against their traffic
               floor: pixels read once, sample planes written and read once, coefficients written once
   encode_t1/16  fh_jpeg_encode_batch end to end (kernels, one device-to-host copy, Huffman coding on 1 / 16 threads), blocking
+  coder       the device Huffman coder alone on coefficients resident in HBM (events around fh_jpeg_code_batch_dev, its two stream
+              synchronisations included)
+  encode_gpu  fh_jpeg_encode_batch_gpu end to end (kernels, the device coder, one device-to-host copy of the files' bytes), blocking
+--legs picks a subset (with --md: profiles/jpeg_huff.md was written with --legs huff_t16,kernels,encode_t16,encode_t1,coder,encode_gpu).
 Nothing here is a gate.  Writes --md (default profiles/jpeg_enc.md) and prints one JSON line per leg run.  Needs a GPU; no fallback."""
 import argparse
 import ctypes as C
@@ -25,13 +29,14 @@ ap.add_argument("--steps", type=int, default=5, help="timed steps per leg run")
 ap.add_argument("--warmup", type=int, default=2)
 ap.add_argument("--leg", default="", help="internal: run one leg in this process and print its JSON line")
 ap.add_argument("--load", default="frames640", help="internal: the workload of --leg")
+ap.add_argument("--legs", default="", help="comma-separated subset of the legs (default: all)")
 ap.add_argument("--md", default=os.path.join(ROOT, "profiles", "jpeg_enc.md"))
 a = ap.parse_args()
 sys.path.insert(0, ROOT)
 
 IMAGE = os.path.join(ROOT, "tests", "golden", "images", "c1_640x640.jpg")
 LOADS = {"frames640": (128, 640), "chips112": (1024, 112)}
-LEGS = ("pillow", "huff_t1", "huff_t16", "kernels", "encode_t16", "encode_t1")
+LEGS = ("pillow", "huff_t1", "huff_t16", "kernels", "encode_t16", "encode_t1", "coder", "encode_gpu")
 QUALITY, SUB = 90, 2
 
 
@@ -154,7 +159,7 @@ def leg_kernels(load):
     return {"ms": per, "equal_host": same, "floor_bytes": n * floor_bytes(side)}
 
 
-def leg_encode(load, threads):
+def leg_encode(load, threads, coder="host"):
     import torch
     import facerecognizeonnx_amd as fa
     fa.lib().fh_init(0)
@@ -164,10 +169,47 @@ def leg_encode(load, threads):
     sizes = []
 
     def step():
-        sizes[:] = [len(f) for f in enc.encode_dev(frames, QUALITY, SUB, threads)]
+        sizes[:] = [len(f) for f in enc.encode_dev(frames, QUALITY, SUB, threads, coder=coder)]
     out = {"ms": wall(step, a.warmup, a.steps), "bytes": sum(sizes)}
+    if coder == "device":
+        n, side = LOADS[load]
+        out["coef_bytes"] = n * side * side * 3                                # 4:2:0: 1.5 int16 per pixel
+        out["equal_host"] = enc.encode_dev(frames, QUALITY, SUB, 16) == enc.encode_dev(frames, QUALITY, SUB, coder="device")
     del keep
     return out
+
+
+def leg_coder(load):
+    import numpy as np
+    import torch
+    import facerecognizeonnx_amd as fa
+    from facerecognizeonnx_amd import _lib
+    L = fa.lib()
+    L.fh_init(0)
+    n, side = LOADS[load]
+    keep, frames = device_frames(load)
+    d = _lib.FhJpegDesc()
+    assert L.fh_jpeg_enc_desc(side, side, 0, SUB, QUALITY, C.byref(d)) == 0
+    count = int(d.coef_count)
+    descs = (_lib.FhJpegDesc * n)(*([d] * n))
+    base = np.arange(n, dtype=np.int64) * count
+    d_coef = torch.zeros(n * count, dtype=torch.int16, device="cuda")
+    enc = fa.JpegEncoder()
+    s = torch.cuda.current_stream().cuda_stream
+    assert L.fh_jpeg_forward_batch_dev(enc.handle, descs, n, fa.frame_array(frames), d_coef.data_ptr(), base.ctypes.data, s) == n
+    torch.cuda.synchronize()
+    blobs, status = (_lib.FhBlob * n)(), np.zeros(n, np.int32)
+    per = []
+    for k in range(a.warmup + 2 * a.steps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        assert L.fh_jpeg_code_batch_dev(enc.handle, descs, n, d_coef.data_ptr(), base.ctypes.data, blobs, status.ctypes.data, s) == n
+        e1.record()
+        torch.cuda.synchronize()
+        if k >= a.warmup:
+            per.append(e0.elapsed_time(e1))
+    del keep
+    return {"ms": per, "bytes": sum(b.n for b in blobs), "coef_bytes": n * count * 2}
 
 
 def run_leg(leg, load):
@@ -177,6 +219,10 @@ def run_leg(leg, load):
         r = leg_huff(load, int(leg[6:]))
     elif leg == "kernels":
         r = leg_kernels(load)
+    elif leg == "coder":
+        r = leg_coder(load)
+    elif leg == "encode_gpu":
+        r = leg_encode(load, 0, coder="device")
     else:
         r = leg_encode(load, int(leg[8:]))
     r.update(leg=leg, load=load)
@@ -194,9 +240,10 @@ def main():
     if a.leg:
         return run_leg(a.leg, a.load)
     res = {}
+    legs = [leg for leg in LEGS if not a.legs or leg in a.legs.split(",")]
     for rnd in range(a.rounds):
         for load in LOADS:
-            for leg in LEGS:
+            for leg in legs:
                 p = subprocess.run([sys.executable, os.path.abspath(__file__), "--leg", leg, "--load", load, "--steps", str(a.steps), "--warmup",
                                     str(a.warmup)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
                 line = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
@@ -207,16 +254,18 @@ def main():
                     continue
                 print(line[-1], flush=True)
                 res.setdefault((load, leg), []).append(json.loads(line[-1]))
-    md = ["# JPEG out: forward DCT on the device, Huffman coding on host threads", "",
+    title = "Huffman coding on host threads" if "encode_gpu" not in legs else "Huffman coding on host threads or on the device"
+    md = [f"# JPEG out: forward DCT on the device, {title}", "",
           f"`scripts/jpeg_enc_ab.py` on one MI355X, quality {QUALITY}, 4:2:0.  Every leg in a fresh process, the legs alternated over {a.rounds} "
           f"rounds, {a.steps} timed steps per process after {a.warmup} warm-up steps; figures are medians over all samples, in ms per BATCH.  "
           f"`os.cpu_count()` = {os.cpu_count()}; the library never uses more than 16 threads.  Nothing here is a gate.", ""]
     for load, (n, side) in LOADS.items():
         md += [f"## {n} x {side} x {side}", "", "| leg | ms per batch | per image | note |", "|---|---|---|---|"]
         names = {"pillow": "Pillow `save` per image, one core (CPU baseline)", "huff_t1": "`fh_jpeg_write` alone, 1 thread", "huff_t16": "`fh_jpeg_write` alone, 16 threads",
-                 "kernels": "the two kernels (`fh_jpeg_forward_batch_dev`)", "encode_t16": "`fh_jpeg_encode_batch`, threads = 16", "encode_t1": "`fh_jpeg_encode_batch`, threads = 1"}
+                 "kernels": "the two kernels (`fh_jpeg_forward_batch_dev`)", "encode_t16": "`fh_jpeg_encode_batch`, threads = 16", "encode_t1": "`fh_jpeg_encode_batch`, threads = 1",
+                 "coder": "the device coder alone (`fh_jpeg_code_batch_dev`)", "encode_gpu": "`fh_jpeg_encode_batch_gpu`"}
         med = {}
-        for leg in LEGS:
+        for leg in legs:
             runs = res.get((load, leg))
             if not runs:
                 md.append(f"| {names[leg]} | not measured | | |")
@@ -229,10 +278,19 @@ def main():
                         f"coefficients equal the host's: {all(r['equal_host'] for r in runs)}")
             elif "bytes" in runs[0]:
                 note = f"{runs[0]['bytes'] / n / 1e3:.1f} kB per file"
+                if leg == "coder":
+                    note += f"; {runs[0]['coef_bytes'] / 1e6:.1f} MB of coefficients read twice; 2 stream synchronisations per call"
+                if leg == "encode_gpu":
+                    note += (f"; {runs[0]['bytes'] / 1e6:.1f} MB copied to the host against {runs[0]['coef_bytes'] / 1e6:.1f} MB of coefficients; "
+                             f"3 stream synchronisations per call; files equal the host coder's: {all(r['equal_host'] for r in runs)}")
             md.append(f"| {names[leg]} | {text} | {med[leg] / n * 1e3:.1f} us | {note} |")
         if "pillow" in med and "encode_t16" in med:
             md += ["", f"Pillow loop / `fh_jpeg_encode_batch` (16 threads): **{med['pillow'] / med['encode_t16']:.1f}x**; "
                        f"(1 thread): {med['pillow'] / med['encode_t1']:.2f}x." if "encode_t1" in med else ""]
+        if "encode_gpu" in med and "encode_t16" in med:
+            t16 = [v for r in res[(load, "encode_t16")] for v in r["ms"]]
+            md += ["", f"`fh_jpeg_encode_batch` (16 threads) / `fh_jpeg_encode_batch_gpu`, same rounds: **{med['encode_t16'] / med['encode_gpu']:.1f}x** "
+                       f"({med['encode_t16']:.3f} ms against {med['encode_gpu']:.3f} ms; the 16-thread leg's own samples span {min(t16):.3f}-{max(t16):.3f} ms)."]
         md.append("")
     md += ["The kernels' figure is taken with events around the call, so it includes the descriptor-table copy.  `jpeg_dev.hip` is unchanged (the "
            "encoder keeps a private copy of `find_entry`), so `fh_jpeg_decode_batch` was not re-timed.", ""]
